@@ -2,7 +2,16 @@
 """bench.py -- the headline benchmark of the MI355X DSP hot path (BASELINE.json's metric:
 "IQ Msamples/s ingested (waterfall + GPS acq)").
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload W] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload W] [--full] [--dump-outputs DIR] [--no-cpu]
+
+A plain run (no --full) measures the headline and nothing else: it sets up the `acq` workload, warms up,
+times exactly K steps, writes the last timed step's outputs if --dump-outputs is given, and prints one
+JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step = milliseconds per timed step).
+--full is everything else: the default becomes `all`, and the line gains the cpu_baseline legs, the live
+counter passes, kernel-only times, roofline, step spread, the result checks against the oracle, the
+host-memory ingest figure and the build / GPU identity record.  (The other workloads, chosen with --workload,
+keep their own checks and roofline either way; there --full adds the cpu_baseline legs, the counter passes
+and the identity record.)
 
 With --gpus N > 1 (and no WORLD_SIZE in the environment) this process only LAUNCHES: it starts N
 rank processes (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT set, one per GPU), relays
@@ -26,7 +35,7 @@ Workloads (all inputs synthetic, seeded, resident in HBM before the timed region
   acq10ms    BASELINE configs[4]: joint L1 C/A + QZSS + Galileo E1B, 10 ms coherent (65536-point
              transforms), 256 Doppler bins, all 59 SVs.  --shard sv: ONE block, the SV list split
              over the ranks (strong scaling), results all-gathered and merged.
-  all        (default) the six above; ONE JSON line whose top level is `acq` (metric, value,
+  all        (--full's default) the six above; ONE JSON line whose top level is `acq` (metric, value,
              roofline, cpu_baseline) and whose "workloads" object holds every workload's own
              value, step times, roofline (traffic measured live) and cpu_baseline.
   acq59      the 4 ms shape with the reference's whole SV list (36 C/A + QZSS, 23 E1B): profiles the
@@ -65,6 +74,7 @@ HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s mea
 VALU_PEAK_TFLOPS = 157.3     # fp32 vector peak (MI355X_MICROARCH.md)
 INT_PEAK_TOPS = 78.6         # 256 CUs x 4 SIMD-32 x 32 lanes x 2.4 GHz: one 32-bit integer op per lane per clock
 ZOOMS14 = [0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 14]      # BASELINE configs[2]
+HEADLINE_METRIC = "IQ Msamples/s ingested (waterfall + GPS acq); value = GPS acq, BASELINE configs[1]"
 
 
 # ------------------------------------------------------------------------------------------------
@@ -403,7 +413,7 @@ def live_traffic_passes(args):
     wls = [w for w in (ALL_WORKLOADS if args.workload == "all" else [args.workload]) if w in TRAFFIC_KERNELS]
     if not wls:
         return
-    child = [sys.executable, os.path.abspath(__file__), "--workload", args.workload, "--pmc-child",
+    child = [sys.executable, os.path.abspath(__file__), "--workload", args.workload, "--pmc-child", "--full",
              "--no-cpu", "--no-live-traffic", "--frames", str(args.frames), "--receivers", str(args.receivers)]
     if args.blocks is not None:
         child += ["--blocks", str(args.blocks)]
@@ -520,10 +530,12 @@ def preroll(step, warmup, dist=None):
         step()
 
 
-def timed_steps(dist, step, steps, warmup):
+def timed_steps(dist, step, steps, warmup, spread=True, after=None):
     """W untimed steps, then EXACTLY K steps bracketed by barrier + synchronize on both sides, max
-    over ranks; then the same K steps once more with a device event between steps for the spread
-    (not part of the headline time).  -> (seconds, host enqueue seconds, spread dict)"""
+    over ranks; then (spread=True, --full) the same K steps once more with a device event between steps
+    for the spread (not part of the headline time).  after(): called once the K timed steps are done and
+    before anything else runs (--dump-outputs reads the last timed step's results there).
+    -> (seconds, host enqueue seconds, spread dict or None)"""
     import torch
     preroll(step, warmup, dist)
     dist.barrier()                                   # barrier, then synchronize
@@ -535,6 +547,10 @@ def timed_steps(dist, step, steps, warmup):
     local = time.perf_counter() - t0
     dist.barrier()                                   # ... every rank's are: the slowest rank's time counts
     elapsed = dist.max_over_ranks(local)
+    if after is not None:
+        after()
+    if not spread:
+        return elapsed, t_enq, None
     if not torch.cuda.is_available():                # (the launcher self-test: the same K steps once more, host clock)
         dts = []
         for i in range(steps):
@@ -574,6 +590,27 @@ class DevBytes:
 
     def __init__(self, dptr, nbytes):
         self.__cuda_array_interface__ = {"shape": (int(nbytes),), "typestr": "|u1", "data": (int(dptr), False), "version": 2}
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_acq_outputs(d, s):
+    """--dump-outputs DIR: what a caller of the timed path receives from its last step -- Searcher.fetch(): the winner of
+    every (block, SV) and every (block, SV, Doppler bin) cell -- as DIR/<name>.npy, the float fields float32, the integer
+    ones float64 (exact).  The inputs are seeded: two builds given the same arguments can be compared array for array."""
+    import numpy as np
+    res, cells = s.fetch(want_cells=True)
+    arrays = {"acq_snr": res["snr"], "acq_dop": res["dop"], "acq_code_phase": res["idx"], "acq_valid": res["valid"],
+              "acq_cell_snr": cells["snr"], "acq_cell_max_pwr": cells["max_pwr"], "acq_cell_tot_pwr": cells["tot_pwr"],
+              "acq_cell_idx": cells["idx"]}
+    arrays = {k: np.ascontiguousarray(v, np.float32 if v.dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, total
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), a)
+    log("outputs of the last timed step: %d arrays, %.1f MB in %s" % (len(arrays), total / 1e6, d))
 
 
 def run_acq(args, dist, ten_ms=False, all_svs=False):
@@ -639,7 +676,26 @@ def run_acq(args, dist, ten_ms=False, all_svs=False):
         out = pmc_window(ctx, wl, step, lambda: torch.cuda.synchronize(dev))
         s.close(); ctx.close()
         return out
-    elapsed, t_enq, spread = timed_steps(dist, step, args.steps, args.warmup)
+    dump = (lambda: dump_acq_outputs(args.dump_outputs, s)) if (args.dump_outputs and dist.rank == 0) else None
+    elapsed, t_enq, spread = timed_steps(dist, step, args.steps, args.warmup, spread=args.full, after=dump)
+    metric = "IQ Msamples/s ingested (GPS acq: Sample + %d SV x %d Doppler Correlate)" % (nsv_all, ndop)
+    # weak scaling: every rank its own blocks; --shard sv (strong): the same B blocks, searched once by all ranks
+    value = round(float(B) * nsamples * args.steps * (1 if shard_sv else dist.world) / elapsed / 1e6, 3)
+    workload = (("BASELINE configs[4]: GPS L1 C/A + QZSS + Galileo E1B joint acquisition, 10 ms coherent "
+                 "(163680 samples @16.368 MS/s -> 65536-point transforms), 256 Doppler bins of 62.44 Hz, "
+                 "59 SVs (36 C/A, 23 E1B), synthetic int16 IQ resident in HBM") if ten_ms else
+                (("the reference's whole SV list on BASELINE configs[1]'s blocks: 36 C/A + QZSS and 23 Galileo E1B SVs "
+                  "x 41 Doppler bins, 4 ms coherent, synthetic int16 IQ @16.368 MS/s resident in HBM") if all_svs else
+                 ("BASELINE configs[1]: 32 GPS L1 C/A SVs x 41 Doppler bins, 4 ms coherent FFT correlate, "
+                  "synthetic int16 IQ @16.368 MS/s resident in HBM")))
+    if not args.full:
+        # a plain run: the timed steps and nothing else (kernel-only times, the result checks, the roofline and the
+        # host-memory ingest figure are --full's)
+        s.close()
+        ctx.close()
+        return {"metric": metric, "value": value, "unit": "Msamples/s", "ms_per_step": round(elapsed / args.steps * 1e3, 5),
+                "dtype": "f32", "config": {"workload": workload, "blocks_per_step_per_gpu": B, "samples_per_block": nsamples},
+                "host_enqueue_ms_per_step": round(t_enq / args.steps * 1e3, 5)}
 
     # dominant kernel alone: Correlate() launches back to back, HIP events on its own stream
     kreps = max(10, min(args.steps, 200))
@@ -704,21 +760,14 @@ def run_acq(args, dist, ten_ms=False, all_svs=False):
     traffic, source, _ = measured_traffic(wl, B)
     tfl = flops_launch / (kernel_ms * 1e-3) / 1e12
     out = {
-        "metric": "IQ Msamples/s ingested (GPS acq: Sample + %d SV x %d Doppler Correlate)" % (nsv_all, ndop),
-        # weak scaling: every rank its own blocks; --shard sv (strong): the same B blocks, searched once by all ranks
-        "value": round(float(B) * nsamples * args.steps * (1 if shard_sv else dist.world) / elapsed / 1e6, 3),
+        "metric": metric,
+        "value": value,
         "unit": "Msamples/s",
         "ms_per_step": round(elapsed / args.steps * 1e3, 5),
         "step_ms_spread": spread,
         "dtype": "f32",
         "config": {
-            "workload": ("BASELINE configs[4]: GPS L1 C/A + QZSS + Galileo E1B joint acquisition, 10 ms coherent "
-                         "(163680 samples @16.368 MS/s -> 65536-point transforms), 256 Doppler bins of 62.44 Hz, "
-                         "59 SVs (36 C/A, 23 E1B), synthetic int16 IQ resident in HBM") if ten_ms else
-                        (("the reference's whole SV list on BASELINE configs[1]'s blocks: 36 C/A + QZSS and 23 Galileo E1B SVs "
-                          "x 41 Doppler bins, 4 ms coherent, synthetic int16 IQ @16.368 MS/s resident in HBM") if all_svs else
-                         ("BASELINE configs[1]: 32 GPS L1 C/A SVs x 41 Doppler bins, 4 ms coherent FFT correlate, "
-                          "synthetic int16 IQ @16.368 MS/s resident in HBM")),
+            "workload": workload,
             "blocks_per_step_per_gpu": B, "samples_per_block": nsamples, "cells_per_step_per_gpu": cells,
             "parallelism": ("--shard sv: the same %d block(s) on every GPU, the %d SVs split over %d GPU(s) by cost (E1B = %.1f C/A; "
                             "rank loads %s of mean %.2f), winners all-gathered over RCCL every step"
@@ -2081,8 +2130,15 @@ def summary_line(line):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", default="all",
-                    choices=["all", "acq", "acq59", "acq10ms", "wf14", "ddc14", "cfg2_chain", "waterfall", "ddc", "receivers", "receivers_light", "stub"])
+    ap.add_argument("--workload", default=None,
+                    choices=["all", "acq", "acq59", "acq10ms", "wf14", "ddc14", "cfg2_chain", "waterfall", "ddc", "receivers", "receivers_light", "stub"],
+                    help="default: the headline (acq, BASELINE configs[1]); with --full: all")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline's timed steps: every workload in one line (unless --workload), the "
+                         "cpu_baseline legs, the live counter passes, kernel-only times, roofline, step spread, result checks "
+                         "against the oracle, the host-memory ingest figure and the build / GPU identity record")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (acquisition workloads)")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
@@ -2104,6 +2160,15 @@ def main():
                     help="(internal) counter-pass mode: a few steps of every workload between marker kernels, no timing")
     args = ap.parse_args()
     args.log2n_given = args.log2n is not None
+    args.headline = args.workload is None
+    if args.headline:
+        args.workload = "all" if args.full else "acq"
+    if not args.full:
+        if args.workload == "all":
+            ap.error("--workload all runs with --full")
+        args.no_cpu = args.no_live_traffic = True          # the cpu_baseline legs and the counter passes are --full's
+    if args.dump_outputs and args.workload not in ("all", "acq", "acq59", "acq10ms"):
+        ap.error("--dump-outputs is written by the acquisition workloads (acq, acq59, acq10ms; all: acq's)")
     if args.cpu_seconds is None:
         args.cpu_seconds = 4.0 if args.workload == "all" else 10.0
     args.workload = {"waterfall": "wf14", "ddc": "ddc14"}.get(args.workload, args.workload)
@@ -2150,6 +2215,8 @@ def main():
             a.steps, a.warmup = min(args.steps, 20), min(args.warmup, 3)       # 3.4 ms steps; the default K = 200 is sized for acq
         if args.workload == "all" and wl in RX_MIX:
             a.steps, a.warmup = min(args.steps, 40), min(args.warmup, 4)
+        if args.workload == "all" and wl != "acq":
+            a.dump_outputs = None                                               # the headline's outputs only
         fn = {"acq": lambda: run_acq(a, dist), "acq10ms": lambda: run_acq(a, dist, ten_ms=True),
               "acq59": lambda: run_acq(a, dist, all_svs=True), "wf14": lambda: run_wf14(a, dist),
               "ddc14": lambda: run_ddc14(a, dist), "cfg2_chain": lambda: run_cfg2_chain(a, dist),
@@ -2190,7 +2257,7 @@ def main():
         else:
             a = rs["acq"]
             line = dict(a, **common)
-            line["metric"] = "IQ Msamples/s ingested (waterfall + GPS acq); value = GPS acq, BASELINE configs[1]"
+            line["metric"] = HEADLINE_METRIC
             line["workloads"] = dict({"acq": {k: a[k] for k in a if k not in ("metric", "config")}},
                                      **{wl: rs[wl] for wl in rs if wl != "acq"})
             line["config"]["also_in_this_line"] = ("workloads.wf14 / ddc14 / cfg2_chain: BASELINE configs[2] (frames, DDC, end to "
@@ -2209,10 +2276,13 @@ def main():
     else:
         r = run(args.workload)
         line = dict(common, **r)
+        if args.headline:                                    # a plain run: the headline of the --full line, measured alone
+            line["metric"] = HEADLINE_METRIC
         if dist.world > 1:
             same_fields(line)
     if args.workload != "stub" and not args.pmc_child:
-        line["box"] = box_identity(dist.local_rank)
+        if args.full:
+            line["box"] = box_identity(dist.local_rank)
         if dist.share_gpu:
             line["invalid_for_scaling"] = ("KIWIGPU_BENCH_SHARE_GPU=1: %d ranks on ONE GPU, process group over gloo -- a rehearsal of the "
                                            "N > 1 code path (sharding, gathers, merge, line fields), not a scaling measurement" % dist.world)
@@ -2223,12 +2293,14 @@ def main():
             out = line
         elif args.workload == "stub":
             out = compact_line(line)
+        elif not args.full:
+            out = line                                       # small already: nothing to move to stderr
         else:
             publish_full_line(line)
             out = compact_line(line)
         os.write(json_fd, (json.dumps(out, separators=(",", ":")) + "\n").encode())
     dist.close()
-    if dist.rank == 0 and args.workload != "stub" and not args.pmc_child:
+    if dist.rank == 0 and args.workload != "stub" and not args.pmc_child and args.full:
         # The LAST line on stderr: every workload's step time, roofline fraction + the roof that binds it (v: vector
         # arithmetic, h: HBM), counter traffic / algorithmic bytes, and whether its post-timed-region result check ran --
         # a record that keeps only the tail of stderr still holds all of them.

@@ -19,7 +19,7 @@ def test_process_group_path_over_rccl_with_one_rank():
     env.update(KIWIGPU_BENCH_FORCE_DIST="1", KIWIGPU_BENCH_FORCE_SV="1", KIWIGPU_BENCH_PREROLL_S="0.05", KIWIGPU_BENCH_WATCHDOG_S="240",
                MASTER_ADDR="127.0.0.1", MASTER_PORT="29541")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "acq10ms", "--shard", "sv", "--steps", "6", "--warmup", "2",
-                          "--no-cpu", "--no-live-traffic", "--full-line"], env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
+                          "--full", "--no-cpu", "--no-live-traffic", "--full-line"], env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["scaling"] == "strong" and line["steps"] == 6
@@ -44,19 +44,19 @@ def test_two_ranks_over_rccl_strong_and_weak():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR")}
     env.update(KIWIGPU_BENCH_PREROLL_S="0.05", KIWIGPU_BENCH_WATCHDOG_S="240")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "acq10ms", "--shard", "sv", "--steps", "6",
-                          "--warmup", "2", "--no-cpu", "--no-live-traffic", "--full-line"], env=env, capture_output=True, text=True, timeout=600,
+                          "--warmup", "2", "--full", "--no-cpu", "--no-live-traffic", "--full-line"], env=env, capture_output=True, text=True, timeout=600,
                          cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["scaling"] == "strong" and line["steps"] == 6 and line["value"] > 0
     assert "all-gathered over RCCL every step" in line["config"]["parallelism"] and "invalid_for_scaling" not in line
     single = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "acq10ms", "--steps", "6", "--warmup", "2",
-                             "--no-cpu", "--no-live-traffic", "--full-line"], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+                             "--full", "--no-cpu", "--no-live-traffic", "--full-line"], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert single.returncode == 0, single.stderr[-4000:]
     one = json.loads([l for l in single.stdout.splitlines() if l.startswith("{")][-1])
     assert sorted(line["found_svs"]) == sorted(one["found_svs"]), (line["found_svs"], one["found_svs"])     # merged winners = the unsharded run's
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "receivers", "--steps", "8", "--warmup", "2",
-                          "--no-cpu", "--no-live-traffic"], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--full", "--no-cpu", "--no-live-traffic"], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1 and len(lines[0]) <= 8192                       # ONE compact line from rank 0

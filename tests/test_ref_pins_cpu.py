@@ -178,22 +178,11 @@ def test_cic_shapes_match_reference_cic_gen_c(oracle):
     assert oracle.ddc_rx_decim(oracle.RX_STD) == 1736 * 3 * 2 and oracle.ddc_rx_decim(oracle.RX_WIDE) == 1543 * 2 * 2
 
 
-@pytest.mark.skipif(not os.path.isfile("/root/reference/verilog/rx/fir_iq.sv"), reason="reference tree not present")
 def test_all_three_cicf_tap_sets_match_fir_iq_sv(oracle):
-    """fir_iq.sv:45-123: the RX_CFG == 3, RX_CFG == 14 and default coefficient tables."""
+    """fir_iq.sv:45-123: the RX_CFG == 3, RX_CFG == 14 and default coefficient tables (the three `assign taps[..]` runs in file
+    order, parsed into tests/golden/ref_text_pins.json by tools/make_ref_text_golden.py)."""
     import ctypes as C
-    import re
-    text = open("/root/reference/verilog/rx/fir_iq.sv").read()
-    # the three `assign taps[..] = COEFF'('sh.....)` runs, in file order: RX_CFG == 3, == 14, default
-    allt = [(int(i), int(h, 16)) for i, h in
-            re.findall(r"assign taps\[\s*(\d+)\]\s*=\s*COEFF'\('sh([0-9a-f]{5})\)", text)]
-    sets, cur = [], []
-    for i, v in allt:
-        if i == 0 and cur:
-            sets.append(cur)
-            cur = []
-        cur.append(v)
-    sets.append(cur)
+    sets = json.load(open(os.path.join(GOLD, "ref_text_pins.json")))["fir_iq_sv"]["tap_sets"]
     assert [len(x) for x in sets] == [33, 9, 33]
     L = oracle.lib()
     for name, n, want in (("ko_cicf_taps65_wide", 33, sets[0]), ("ko_cicf_taps17", 9, sets[1]),
@@ -245,24 +234,20 @@ def test_squelch_oracle_matches_reference_squelch_cpp(oracle):
     assert closed[2] and not closed[7] and closed[11], closed          # noise closes it, a quiet carrier opens it, noise again
 
 
-@pytest.mark.skipif(not os.path.isfile("/root/reference/rx/rx_filter.h"), reason="reference tree not present")
 def test_deemphasis_tables_match_rx_filter_h():
     """rx/rx_filter.h:29-73: the four [2][79] de-emphasis tables the host mirror carries (flydog_sdr_gps_amd/deemp.py) are the
-    reference's numbers, and the reference's CFir, handed them, answers an impulse with exactly them (fir_ref.npz)."""
-    import re
+    reference's numbers (parsed into tests/golden/ref_text_pins.json by tools/make_ref_text_golden.py), and the reference's CFir,
+    handed them, answers an impulse with exactly them (fir_ref.npz)."""
     from flydog_sdr_gps_amd import deemp
-    text = open("/root/reference/rx/rx_filter.h").read()
+    ref = json.load(open(os.path.join(GOLD, "ref_text_pins.json")))["rx_filter_h"]
     g = np.load(os.path.join(GOLD, "fir_ref.npz"))
     for name in ("nfm_deemp_12000", "nfm_deemp_20250", "am_ssb_deemp_12000", "am_ssb_deemp_20250"):
-        body = re.search(r"const float %s\[N_NFM_DEEMP\]\[N_DEEMP_TAPS\] = \{(.*?)\n\};" % name, text, re.S).group(1)
-        rows = re.findall(r"\{([^{}]*)\}", body)
-        tab = np.array([[float(v) for v in re.sub(r"//[^\n]*", "", r).replace("\n", " ").split(",") if v.strip()] for r in rows],
-                       np.float32)
+        tab = np.array(ref["tables"][name], np.float32)
         assert tab.shape == (2, deemp.N_DEEMP_TAPS)
         assert np.array_equal(getattr(deemp, name.upper()), tab), name
         for k in range(2):
             assert np.array_equal(g["%s_%d_out" % (name, k)][:79], tab[k])
-    assert int(re.search(r"#define N_DEEMP_TAPS (\d+)", text).group(1)) == deemp.N_DEEMP_TAPS
+    assert ref["N_DEEMP_TAPS"] == deemp.N_DEEMP_TAPS
 
 
 # ---- the FFT-dependent rows, pinned by the reference's own gps/search.cpp and rx/CuteSDR/fastfir.cpp -------------------------

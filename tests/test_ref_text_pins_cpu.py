@@ -1,7 +1,7 @@
 """The literal tables of the reference files that cannot be compiled here (they include <fftw3.h>, absent from the image),
-pinned by TEXT: the numbers are parsed from /root/reference at test time, in the build container, and compared with what the
-oracle and the product compute from them -- as tests/test_ref_pins_cpu.py does for fir_iq.sv's taps.  Nothing of the reference
-is kept under tests/: on a box without the tree the whole file skips.
+pinned by TEXT: the numbers parsed from the reference's files (tests/golden/ref_text_pins.json, written from the reference tree by
+tools/make_ref_text_golden.py; numbers only, no text of the reference) are compared with what the oracle and the product compute
+from them -- as tests/test_ref_pins_cpu.py does for fir_iq.sv's taps.
 
   gps/search.cpp:100-136    COEF[31][2], column FT      -> the oracle's half-band decimator (impulse response),
                                                            kg_acq.hip's c_hb_even / HB_CENTRE
@@ -11,21 +11,16 @@ is kept under tests/: on a box without the tree the whole file skips.
   rx/CuteSDR/fastfir.cpp:61-95, 102-146  CIC p1 / p2 (both rates), the five window functions' constants
                                                         -> ko.fir_window / ko.fir_cic_coeffs, kg_snd.hip's literals
 """
+import json
 import os
 import re
 
 import numpy as np
-import pytest
 
-REFERENCE = os.environ.get("REFERENCE", "/root/reference")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-pytestmark = pytest.mark.skipif(not os.path.isfile(os.path.join(REFERENCE, "gps", "search.cpp")), reason="reference tree not present")
+PINS = json.load(open(os.path.join(ROOT, "tests", "golden", "ref_text_pins.json")))
 
 NUM = r"[-+]?(?:\d+\.\d*|\.\d+|\d+)(?:[eE][-+]?\d+)?"
-
-
-def ref_lines(rel, lo, hi):
-    return "".join(open(os.path.join(REFERENCE, rel)).read().splitlines(True)[lo - 1:hi])
 
 
 def strip_comments(text):
@@ -37,11 +32,8 @@ def our(rel):
 
 
 def test_half_band_taps_are_search_cpp_coef_column_ft(oracle):
-    text = open(os.path.join(REFERENCE, "gps", "search.cpp")).read()
-    ft = int(re.search(r"#define FT\s+(\d+)", text).group(1))
-    ntaps = int(re.search(r"#define NTAPS\s+(\d+)", text).group(1))
-    body = re.search(r"static float COEF\[NTAPS\]\[2\][^=]*=\s*\{(.*?)\}\s*;", text, re.S).group(1)
-    vals = [float(v) for v in re.findall(NUM, strip_comments(body))]
+    ref = PINS["search_cpp"]
+    ft, ntaps, vals = ref["FT"], ref["NTAPS"], ref["COEF"]
     assert ft == 0 and ntaps == 31 and len(vals) == 62
     coef = np.array(vals, np.float32).reshape(31, 2)[:, ft]
     assert np.array_equal(coef, coef[::-1]) and np.all(coef[1:15:2] == 0) and coef[15] == np.float32(0.500009)
@@ -64,9 +56,7 @@ def test_half_band_taps_are_search_cpp_coef_column_ft(oracle):
 
 
 def test_quadrature_oscillator_tables_are_search_cpp_lo_sin_lo_cos(oracle):
-    text = ref_lines("gps/search.cpp", 380, 392)
-    lo_sin = [int(v) for v in re.search(r"lo_sin\[\]\s*=\s*\{([^}]*)\}", text).group(1).split(",")]
-    lo_cos = [int(v) for v in re.search(r"lo_cos\[\]\s*=\s*\{([^}]*)\}", text).group(1).split(",")]
+    lo_sin, lo_cos = PINS["search_cpp"]["lo_sin"], PINS["search_cpp"]["lo_cos"]        # gps/search.cpp:383-384
     assert (lo_sin, lo_cos) == ([1, 1, 0, 0], [1, 0, 0, 1])
     osrc = our("oracle/kiwi_oracle.c")
     assert [int(v) for v in re.search(r"lo_sin\[4\]\s*=\s*\{([^}]*)\}", osrc).group(1).split(",")] == lo_sin
@@ -110,16 +100,8 @@ def window_from_constants(consts, n, denom, f32_cos):
 
 def test_waterfall_windows_and_cic_comp_are_rx_waterfall_cpp_constants(oracle):
     from flydog_sdr_gps_amd import wf
-    text = strip_comments(ref_lines("rx/rx_waterfall.cpp", 128, 190))
-    scale = float(re.search(r"adc_scale_decim = powf\(2, (-?\d+)\)", text).group(1))
-    gain = float(re.search(r"#define WINDOW_GAIN\s+(%s)" % NUM, text).group(1))
-    cases = re.split(r"case WINF_WF_", text)
-    consts = {}
-    for c in cases[1:]:
-        name = re.match(r"(\w+)", c).group(1)
-        body = c.split("break;")[0]
-        vals = [float(v) for v in re.findall(r"(?<![\w.])(0\.\d+)(?![\w.])", body)]
-        consts[name] = vals
+    ref = PINS["rx_waterfall_cpp"]                                     # rx/rx_waterfall.cpp:128-190
+    scale, gain, consts = ref["adc_scale_decim_log2"], ref["WINDOW_GAIN"], ref["windows"]
     assert consts["HANNING"] == [0.5, 0.5] and consts["HAMMING"] == [0.54, 0.46]
     assert consts["BLACKMAN_HARRIS"] == [0.35875, 0.48829, 0.14128, 0.01168] and scale == -16 and gain == 1.0
     base = np.float32(2.0 ** scale * gain)
@@ -132,11 +114,9 @@ def test_waterfall_windows_and_cic_comp_are_rx_waterfall_cpp_constants(oracle):
         assert np.array_equal(got_p[k], want), name
     assert np.all(got_o[3] == base) and np.all(got_p[3] == base)
     # CIC_comp (:175-185)
-    p1 = float(re.search(r"p1 = (%s)f" % NUM, text).group(1))
-    p2 = float(re.search(r"p2 = (%s)f" % NUM, text).group(1))
-    m = re.search(r"CIC_comp\[i\] = (%s) \+ cic_comp / (%s);" % (NUM, NUM), text)
-    assert (p1, p2, float(m.group(1)), float(m.group(2))) == (-2.969, 36.26, 0.5, 2.0)
-    assert "pow(sincf, -5)" in text
+    p1, p2 = ref["cic_comp_p1"], ref["cic_comp_p2"]
+    assert (p1, p2, ref["cic_comp_offset"], ref["cic_comp_divisor"]) == (-2.969, 36.26, 0.5, 2.0)
+    assert ref["sincf_power"] == -5                                    # pow(sincf, -5)
     # (the host mirror evaluates sinf / pow / exp with numpy instead of the C library: a few float steps, far inside the 1e-5 bar)
     assert np.allclose(wf.cic_comp_table(), oracle.wf_cic_comp(), rtol=2e-6, atol=0)
     osrc = our("oracle/kiwi_oracle_wf.c")
@@ -144,19 +124,15 @@ def test_waterfall_windows_and_cic_comp_are_rx_waterfall_cpp_constants(oracle):
 
 
 def test_fastfir_windows_and_cic_constants_are_fastfir_cpp_text(oracle):
-    text = strip_comments(ref_lines("rx/CuteSDR/fastfir.cpp", 61, 146))
+    ref = PINS["fastfir_cpp"]                                          # rx/CuteSDR/fastfir.cpp:61-146, rx/rx_sound.h
     names = {"BLACKMAN_NUTTALL": 0, "BLACKMAN_HARRIS": 1, "NUTTALL": 2, "HANNING": 3, "HAMMING": 4}
-    hdr = open(os.path.join(REFERENCE, "rx", "rx_sound.h")).read()
     for name, k in names.items():
-        assert int(re.search(r"#define WINF_SND_%s\s+(\d+)" % name, hdr).group(1)) == k
-    consts = {}
-    for c in re.split(r"case WINF_SND_", text)[1:]:
-        name = re.match(r"(\w+)", c).group(1)
-        consts[name] = [float(v) for v in re.findall(r"(?<![\w.])(0\.\d+)(?![\w.])", c.split("break;")[0])]
+        assert ref["WINF_SND"][name] == k
+    consts = ref["windows"]
     assert consts == {"BLACKMAN_NUTTALL": [0.3635819, 0.4891775, 0.1365995, 0.0106411],
                       "BLACKMAN_HARRIS": [0.35875, 0.48829, 0.14128, 0.01168],
                       "NUTTALL": [0.355768, 0.487396, 0.144232, 0.012604], "HANNING": [0.5, 0.5], "HAMMING": [0.54, 0.46]}
-    assert "window_func = WINF_SND_BLACKMAN_NUTTALL" in text           # window_func < 0 (:105-106)
+    assert ref["window_when_negative"] == "BLACKMAN_NUTTALL"           # window_func < 0 (:105-106)
     for name, k in names.items():
         # m_pWindowTbl[i] = a0 - a1 MCOS((K_2PI*i)/(CONV_FIR_SIZE-1)) + ...: TYPEREAL float, MCOS = cosf, the sum in double
         want = window_from_constants(consts[name], 513, 512.0, True).astype(np.float32)
@@ -170,8 +146,6 @@ def test_fastfir_windows_and_cic_constants_are_fastfir_cpp_text(oracle):
     theirs = sorted(set(v for vals in consts.values() for v in vals))
     assert all(v in ours for v in theirs), (theirs, ours)
     # the CIC compensation constants of both sound rates (:70-73)
-    p = re.search(r"p1 = \(snd_rate == SND_RATE_3CH \? (%s)f : (%s)f\)" % (NUM, NUM), text)
-    q = re.search(r"p2 = \(snd_rate == SND_RATE_3CH \? (%s)f\s*: (%s)f\s*\)" % (NUM, NUM), text)
-    assert [float(v) for v in p.groups() + q.groups()] == [-3.107, -2.969, 32.04, 36.26]
+    assert ref["cic_p1"] + ref["cic_p2"] == [-3.107, -2.969, 32.04, 36.26]
     for s in (our("oracle/kiwi_oracle_snd.c"), src):
         assert "-3.107f : -2.969f" in s and "32.04f : 36.26f" in s

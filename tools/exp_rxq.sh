@@ -1,14 +1,15 @@
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 cd $R
+out=${1:?usage: tools/exp_rxq.sh <output directory>}
 for cond in cpu nocpu; do
   if [ $cond = cpu ]; then extra=""; else extra="--no-cpu"; fi
-  rm -rf $R/gpurun_out/rxq_$cond
-  timeout 900 rocprofv3 --kernel-trace --output-format csv -d $R/gpurun_out/rxq_$cond -- python3 bench.py --full-line --no-live-traffic $extra --steps 40 --warmup 4 > $R/gpurun_out/rxq_$cond.log 2>&1
-  echo "== $cond"; grep SUMMARY $R/gpurun_out/rxq_$cond.log | cut -c1-300
-  python3 - $cond <<'PY'
+  rm -rf $out/rxq_$cond
+  timeout 900 rocprofv3 --kernel-trace --output-format csv -d $out/rxq_$cond -- python3 bench.py --full --full-line --no-live-traffic $extra --steps 40 --warmup 4 > $out/rxq_$cond.log 2>&1
+  echo "== $cond"; grep SUMMARY $out/rxq_$cond.log | cut -c1-300
+  python3 - $cond "$out" <<'PY'
 import csv,glob,collections,sys
-fs=glob.glob('gpurun_out/rxq_%s/**/*kernel_trace.csv'%sys.argv[1],recursive=True)
+fs=glob.glob('%s/rxq_%s/**/*kernel_trace.csv'%(sys.argv[2],sys.argv[1]),recursive=True)
 best=max(fs,key=lambda f:sum(1 for _ in open(f)))
 rows=list(csv.DictReader(open(best)))
 rows.sort(key=lambda r:int(r["Start_Timestamp"]))
@@ -27,4 +28,4 @@ for r in win: d[(r["Kernel_Name"][:30],r["Queue_Id"])].append((int(r["End_Timest
 for k,v in sorted(d.items(),key=lambda kv:-sum(kv[1]))[:12]: print("   %-32s q%s n %3d avg %7.1f us"%(k[0],k[1],len(v),sum(v)/len(v)))
 PY
 done
-find gpurun_out/rxq_cpu gpurun_out/rxq_nocpu -name "*.csv" -delete
+find $out/rxq_cpu $out/rxq_nocpu -name "*.csv" -delete

@@ -1,0 +1,164 @@
+"""Generates the reference-derived data the CPU tests pin against, so that they run without the reference tree:
+
+  ref_text_pins.json  the literal tables and constants of reference files, parsed from their text: the CIC structure of the
+                      generated verilog/rx/cic_*.vh, the CICF taps of verilog/rx/fir_iq.sv, the Sats[] rows of gps/sats.cpp,
+                      the de-emphasis tables of rx/rx_filter.h, COEF / lo_sin / lo_cos of gps/search.cpp, the window and
+                      CIC-compensation constants of rx/rx_waterfall.cpp and rx/CuteSDR/fastfir.cpp (+ rx/rx_sound.h's
+                      WINF_SND_* numbers)
+  cacode_ref.npz      the C/A chips of every non-E1B row of Sats[], as the reference's own gps/cacode.h produces them
+                      (oracle/_ref/cacode_ref, built by oracle/build_ref.sh)
+
+Numbers only: no text of the reference is stored.  Run where the reference tree is present and oracle/_ref/ has been built:
+REFERENCE=<reference tree> python tools/make_ref_text_golden.py"""
+import json
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+GOLD = os.path.join(ROOT, "tests", "golden")
+REFERENCE = os.environ.get("REFERENCE", "")
+NUM = r"[-+]?(?:\d+\.\d*|\.\d+|\d+)(?:[eE][-+]?\d+)?"
+
+
+def text(rel):
+    return open(os.path.join(REFERENCE, rel)).read()
+
+
+def lines(rel, lo, hi):
+    return "".join(text(rel).splitlines(True)[lo - 1:hi])
+
+
+def strip_comments(t):
+    return re.sub(r"//[^\n]*", "", t)
+
+
+def cic_vh(rel):
+    """Structural constants of a generated verilog/rx/cic_*.vh: [N, R, Bin, Bout, integrator widths, comb widths,
+    comb input truncations, [out msb, out width, rounding bit]]."""
+    txt = text(rel)
+    n, r, bin_, bout = (int(v) for v in re.search(r"N=(\d+) R=(\d+) M=1 Bin=(\d+) Bout=(\d+)", txt).groups())
+    integ = [int(w) for w in re.findall(r"cic_integrator #\(\.WIDTH\((\d+)\)\)", txt)]
+    comb = [int(w) for w in re.findall(r"cic_comb #\(\.WIDTH\((\d+)\)\)", txt)]
+    trunc = []
+    for blk in re.findall(r"cic_comb #.*?\);", txt, flags=re.S):
+        src_w = re.search(r"\.in_data\((\w+)\[(\d+) -:(\d+)\]\)", blk)
+        decl = re.search(r"wire signed \[(\d+):0\] %s;" % src_w.group(1), txt)
+        trunc.append(int(decl.group(1)) + 1 - int(src_w.group(3)))      # declared width - bits taken
+    m = re.search(r"assign out = comb\d_data\[(\d+) -:(\d+)\] \+ comb\d_data\[(\d+)\];", txt)
+    return [n, r, bin_, bout, integ, comb, trunc, [int(v) for v in m.groups()]]
+
+
+def fir_iq_sv():
+    txt = text("verilog/rx/fir_iq.sv")
+    branch = txt[txt.index("end else begin // N=5,R=3"):]
+    default = [int(h, 16) for _, h in re.findall(r"assign taps\[\s*(\d+)\]\s*=\s*COEFF'\('sh([0-9a-fA-F]+)\);", branch)][:33]
+    # the three `assign taps[..] = COEFF'('sh.....)` runs, in file order: RX_CFG == 3, == 14, default
+    allt = [(int(i), int(h, 16)) for i, h in re.findall(r"assign taps\[\s*(\d+)\]\s*=\s*COEFF'\('sh([0-9a-f]{5})\)", txt)]
+    sets, cur = [], []
+    for i, v in allt:
+        if i == 0 and cur:
+            sets.append(cur)
+            cur = []
+        cur.append(v)
+    sets.append(cur)
+    return {"default_branch_taps": default, "tap_sets": sets}
+
+
+def sats_rows():
+    txt = text("gps/sats.cpp")
+    body = txt[txt.index("SATELLITE Sats[] = {"):]
+    body = body[:body.index("{-1}")]
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)          # the SBAS block is commented out
+    body = re.sub(r"//[^\n]*", "", body)
+    rows = re.findall(r"\{\s*(\d+)\s*,\s*(\d+)\s*,\s*(\d+)\s*,\s*(\w+)\s*\}", body)
+    lit = lambda v: int(v, 8) if len(v) > 1 and v[0] == "0" else int(v)      # noqa: E731 -- C literal: leading 0 = octal
+    return [[int(p), lit(t1), lit(t2), kind] for p, t1, t2, kind in rows]
+
+
+def rx_filter_h():
+    txt = text("rx/rx_filter.h")
+    tabs = {}
+    for name in ("nfm_deemp_12000", "nfm_deemp_20250", "am_ssb_deemp_12000", "am_ssb_deemp_20250"):
+        body = re.search(r"const float %s\[N_NFM_DEEMP\]\[N_DEEMP_TAPS\] = \{(.*?)\n\};" % name, txt, re.S).group(1)
+        rows = re.findall(r"\{([^{}]*)\}", body)
+        tabs[name] = [[float(v) for v in re.sub(r"//[^\n]*", "", r).replace("\n", " ").split(",") if v.strip()] for r in rows]
+    return {"N_DEEMP_TAPS": int(re.search(r"#define N_DEEMP_TAPS (\d+)", txt).group(1)), "tables": tabs}
+
+
+def search_cpp():
+    txt = text("gps/search.cpp")
+    body = re.search(r"static float COEF\[NTAPS\]\[2\][^=]*=\s*\{(.*?)\}\s*;", txt, re.S).group(1)
+    lo = lines("gps/search.cpp", 380, 392)
+    return {"FT": int(re.search(r"#define FT\s+(\d+)", txt).group(1)),
+            "NTAPS": int(re.search(r"#define NTAPS\s+(\d+)", txt).group(1)),
+            "COEF": [float(v) for v in re.findall(NUM, strip_comments(body))],
+            "lo_sin": [int(v) for v in re.search(r"lo_sin\[\]\s*=\s*\{([^}]*)\}", lo).group(1).split(",")],
+            "lo_cos": [int(v) for v in re.search(r"lo_cos\[\]\s*=\s*\{([^}]*)\}", lo).group(1).split(",")]}
+
+
+def window_consts(t, prefix):
+    out = {}
+    for c in re.split(r"case %s" % prefix, t)[1:]:
+        out[re.match(r"(\w+)", c).group(1)] = [float(v) for v in re.findall(r"(?<![\w.])(0\.\d+)(?![\w.])", c.split("break;")[0])]
+    return out
+
+
+def rx_waterfall_cpp():
+    t = strip_comments(lines("rx/rx_waterfall.cpp", 128, 190))
+    m = re.search(r"CIC_comp\[i\] = (%s) \+ cic_comp / (%s);" % (NUM, NUM), t)
+    return {"adc_scale_decim_log2": float(re.search(r"adc_scale_decim = powf\(2, (-?\d+)\)", t).group(1)),
+            "WINDOW_GAIN": float(re.search(r"#define WINDOW_GAIN\s+(%s)" % NUM, t).group(1)),
+            "windows": window_consts(t, "WINF_WF_"),
+            "cic_comp_p1": float(re.search(r"p1 = (%s)f" % NUM, t).group(1)),
+            "cic_comp_p2": float(re.search(r"p2 = (%s)f" % NUM, t).group(1)),
+            "cic_comp_offset": float(m.group(1)), "cic_comp_divisor": float(m.group(2)),
+            "sincf_power": int(re.search(r"pow\(sincf, (-?\d+)\)", t).group(1))}
+
+
+def fastfir_cpp():
+    t = strip_comments(lines("rx/CuteSDR/fastfir.cpp", 61, 146))
+    hdr = text("rx/rx_sound.h")
+    names = ("BLACKMAN_NUTTALL", "BLACKMAN_HARRIS", "NUTTALL", "HANNING", "HAMMING")
+    p = re.search(r"p1 = \(snd_rate == SND_RATE_3CH \? (%s)f : (%s)f\)" % (NUM, NUM), t)
+    q = re.search(r"p2 = \(snd_rate == SND_RATE_3CH \? (%s)f\s*: (%s)f\s*\)" % (NUM, NUM), t)
+    return {"WINF_SND": {n: int(re.search(r"#define WINF_SND_%s\s+(\d+)" % n, hdr).group(1)) for n in names},
+            "windows": window_consts(t, "WINF_SND_"),
+            "window_when_negative": re.search(r"window_func = WINF_SND_(\w+)", t).group(1),
+            "cic_p1": [float(v) for v in p.groups()], "cic_p2": [float(v) for v in q.groups()]}
+
+
+def cacode_chips():
+    from flydog_sdr_gps_amd import sats
+    exe = os.path.join(ROOT, "oracle", "_ref", "cacode_ref")
+    taps, chips = [], []
+    for _, t1, t2, kind in sats.SATS:
+        if kind == sats.E1B:
+            continue
+        s = subprocess.check_output([exe, str(t1), str(t2)]).decode().strip()
+        taps.append((t1, t2))
+        chips.append(np.frombuffer(s.encode(), np.uint8) - ord("0"))
+    return np.array(taps, np.int32), np.packbits(np.stack(chips), axis=1)
+
+
+def main():
+    if not os.path.isfile(os.path.join(REFERENCE, "gps", "sats.cpp")):
+        sys.exit("make_ref_text_golden.py: set REFERENCE to the reference tree")
+    pins = {"_source": "tools/make_ref_text_golden.py: numbers parsed from the reference's text",
+            "cic_vh": {f: cic_vh("verilog/rx/" + f) for f in ("cic_wf1.vh", "cic_rx1_12k.vh", "cic_rx2_12k.vh")},
+            "fir_iq_sv": fir_iq_sv(), "sats_cpp": sats_rows(), "rx_filter_h": rx_filter_h(), "search_cpp": search_cpp(),
+            "rx_waterfall_cpp": rx_waterfall_cpp(), "fastfir_cpp": fastfir_cpp()}
+    with open(os.path.join(GOLD, "ref_text_pins.json"), "w") as f:
+        json.dump(pins, f, indent=1)
+        f.write("\n")
+    taps, packed = cacode_chips()
+    np.savez_compressed(os.path.join(GOLD, "cacode_ref.npz"), taps=taps, chips_packed=packed)
+    print("wrote tests/golden/ref_text_pins.json, tests/golden/cacode_ref.npz (%d C/A rows)" % len(taps))
+
+
+if __name__ == "__main__":
+    main()
