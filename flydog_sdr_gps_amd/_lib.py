@@ -132,6 +132,10 @@ SYMBOLS = {
     "kg_post_reset": (_i, [_vp, _i]),
     "kg_post_process_dev": (_i, [_vp, _vp, _i, _vp, _sz, _i, _vp, _vp, _vp, _sz]),
     "kg_post_smeter": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "kg_post_sam_setup": (_i, [_vp, _i, _i]),
+    "kg_post_sam_pll": (_i, [_vp, _i, _i]),
+    "kg_post_set_sam_mparam": (_i, [_vp, _i, _i]),
+    "kg_post_sam_state": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "kg_post_cfir_init_lp": (_i, [_vp, _i, _i, _i, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float]),
     "kg_post_cfir_init_const": (_i, [_vp, _i, _i, _i, _vp, C.c_float]),
     "kg_post_cfir_get_taps": (_i, [_vp, _i, _i, _vp]),
@@ -181,6 +185,7 @@ SYMBOLS = {
     "kg_rxbank_set_little_endian": (_i, [_vp, _i, _i]),
     "kg_post_get_mode": (_i, [_vp, _i]),
     "kg_math_dev": (_i, [_vp, _i, C.c_float, _vp, C.c_uint32, C.c_size_t, _vp]),
+    "kg_math_atan2f_dev": (_i, [_vp, _vp, _vp, C.c_size_t, _vp]),
     "kg_rxbank_poll": (_i, [_vp]),
     "kg_rxbank_ready": (_i, [_vp]),
     "kg_rxbank_join": (_i, [_vp, _i]),

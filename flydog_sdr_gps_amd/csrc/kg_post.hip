@@ -23,12 +23,22 @@
 //     N-1 (fir.cpp:79-91), so the order of the float additions rotates with the write position: sample number g (since the
 //     filter was initialised) starts its sum at the tap of age g mod N, runs up to age N-1 and wraps to age 0.  Restated per
 //     output sample, that is a sum every lane can do for its own sample -- in that order, over a linear history in LDS;
-//   * the squelch's noise average is one more sequential recursion (lane 0); its verdict applies to the whole block.
+//   * the squelch's noise average is one more sequential recursion (lane 0); its verdict applies to the whole block;
+//   * the synchronous-AM family (rx/rx_sound.cpp:791-806, rx/wdsp/SAM_demod.cpp) is split by dependence, not by sample: lane 0
+//     walks only the PLL (sinf / cosf of the phase error, the correlator, atan2f, omega2, fil_out, phzerror; the libm functions are
+//     kg_libm_trig.h's restatements) and leaves sin / cos per sample in LDS; the four Hilbert all-pass chains a, b, c, d, which do not feed
+//     the PLL, run on lanes 0..3 at once; the per-mode audio formulas run across all lanes; the fade leveler / DC block recursions of
+//     audio, audiou, audion on lanes 0..2; the mono16 cast and the stores across all lanes.  No recurrence is reassociated.
+//     The SAM state is a parallel table (post_sam) and the stage lives in its own instance of the kernel (post_kernel<true>,
+//     launched only for a batch that holds a SAM-family channel), so the other modes' kernel is the one it was.
 #include "kg_common.h"
 #include "kg_libm.h"
+#include "kg_libm_trig.h"
 
 #include <math.h>
+#include <stddef.h>
 #include <stdlib.h>
+#include <string.h>
 #include <new>
 #include <vector>
 
@@ -57,6 +67,22 @@ struct post_chan {
     int sq_state, sq_set;         // m_SquelchState, m_SetSquelch
     int sq_rc, squelched;         // the last nsq_nc_sq; s->squelched (rx_sound.cpp:877)
     int deemp, deemp_nfm;         // s->deemp, s->deemp_nfm (rx_sound_cmd.cpp:554)
+};
+
+// wdsp_SAM_t (SAM_demod.cpp:36-66) of a channel, the globals wdsp_SAM_demod_init() derives from snd_rate (:69-80, :154-163),
+// and s->SAM_mparam / s->isChanNull (rx_sound_cmd.cpp:216, rx_sound.cpp:802)
+#define SAM_STAGES 7              // SAM_PLL_HILBERT_STAGES
+#define SAM_ABCD (3 * SAM_STAGES + 3)
+struct post_sam {
+    double z1, z1_u, z1_n;        // DC block
+    float phzerror, fil_out, omega2, sam_carrier, sam_lowpass, zeta, omegaN, g1, g2;
+    float dc, dc_insert, dcu, dc_insertu;                 // fade leveler
+    float abcd[4][SAM_ABCD];      // Hilbert filter variables a, b, c, d
+    float dsI, dsQ;
+    int type;
+    // not reset by PLL_RESET
+    int is_chan_null, snd_rate, mparam;
+    float omega_min, omega_max, mtauR, onem_mtauR, mtauI, onem_mtauI;
 };
 
 #define POST_MAXTAPS 97           // MAX_NUMCOEF, fir.h:20
@@ -141,6 +167,157 @@ __device__ __forceinline__ void post_squelch_block(post_chan *__restrict__ pc, c
     __syncthreads();
 }
 
+// ---- the synchronous-AM family (rx/rx_sound.cpp:791-806 -> wdsp_SAM_demod, rx/wdsp/SAM_demod.cpp:210-346) ----
+// SAM_demod.cpp:85-103: the double literals as the reference's f32_t arrays hold them
+__device__ __constant__ const float sam_c0[SAM_STAGES] = {(float) -0.328201924180698, (float) -0.744171491539427, (float) -0.923022915444215,
+                                                          (float) -0.978490468768238, (float) -0.994128272402075, (float) -0.998458978159551,
+                                                          (float) -0.999790306259206};
+__device__ __constant__ const float sam_c1[SAM_STAGES] = {(float) -0.0991227952747244, (float) -0.565619728761389, (float) -0.857467122550052,
+                                                          (float) -0.959123933111275, (float) -0.988739372718090, (float) -0.996959189310611,
+                                                          (float) -0.999282492800792};
+
+// wdsp_SAM_demod(rx_chan, mode, SAM_mparam, n, agc_samps_c, out_samps_s2) over the AGC output in s_agc (LDS).  Mono modes: out_samps_s2
+// as mono16-valued floats into aud (LDS); stereo (SAS, QAM) and channel-null SAM: the pair written back into agc_samps_c, here pagc
+// (global, the row the gain loop wrote).  es, ec, cI, audu, audn: LDS scratch of n floats each; ps: 4 x KG_POST_MAX_SAMPLES floats.
+__device__ __forceinline__ void post_sam_block(post_sam *__restrict__ ws, int mode, const float2 *s_agc, float *es, float *ec, float *cI,
+                                               float *ps, float *aud, float *audu, float *audn, float2 *pagc, int n, int lane)
+{
+    const double K_2PI = 2.0 * 3.14159265358979323846;                 // datatypes.h:103
+    const int mparam = ws->mparam, which = mparam & 3;                  // CHAN_NULL_WHICH (wdsp.h:5-10)
+    const bool is_null = mode == KG_POST_SAM && which != 0;
+    const bool need_ps = (mode != KG_POST_SAM && mode != KG_POST_QAM) || is_null;
+    const bool stereo_or_null = mode == KG_POST_SAS || mode == KG_POST_QAM || is_null;
+    const bool fade = (mparam & 4) != 0, dcb = (mparam & 8) != 0;     // FADE_LEVELER, DC_BLOCK
+
+    // 1. the PLL: one dependent chain per sample (:218-223, :331-342), lane 0; sin / cos of the phase error stay for the others
+    if (lane == 0) {
+        float phz = ws->phzerror, fil = ws->fil_out, om2 = ws->omega2;
+        const float g1 = ws->g1, g2 = ws->g2, omin = ws->omega_min, omax = ws->omega_max;
+        for (int j = 0; j < n; j++) {
+            const float sn = kg_libm::sinf_glibc(phz), cs = kg_libm::cosf_glibc(phz);
+            es[j] = sn; ec[j] = cs;
+            const float2 x = s_agc[j];
+            const float ai = cs * x.x, bi = sn * x.x, aq = cs * x.y, bq = sn * x.y;
+            const float corrI = +ai + bq, corrQ = -bi + aq;
+            const float det = kg_libm::atan2f_glibc(corrQ, corrI);
+            const float del_out = fil;
+            om2 = om2 + g2 * det;
+            om2 = om2 < omin ? omin : (om2 > omax ? omax : om2);          // CLAMP (types.h:115)
+            fil = g1 * det + om2;
+            phz = phz + del_out;
+            // wrap round 2 pi in double (:341-342); one pass suffices for any finite phase the loop can reach, the bound keeps an
+            // infinite one (which the reference would loop on forever) from hanging the wave
+            for (int it = 0; phz >= K_2PI && it < 64; it++) phz = phz - K_2PI;
+            for (int it = 0; phz < 0.0 && it < 64; it++) phz = phz + K_2PI;
+        }
+        ws->phzerror = phz; ws->fil_out = fil; ws->omega2 = om2;
+        float car = 0.08 * (om2 * (float) ws->snd_rate) / K_2PI;         // :346-348
+        car = car + 0.92 * ws->sam_lowpass;
+        ws->sam_carrier = car; ws->sam_lowpass = car;
+        ws->is_chan_null = is_null;                                      // the return value, s->isChanNull (rx_sound.cpp:802)
+    }
+    __syncthreads();
+
+    // 2. the four Hilbert all-pass chains (:225-256): independent recurrences, lanes 0..3 = a (dsI: ai one sample late), b (bi),
+    //    c (dsQ: bq one sample late), d (aq); each keeps its 24-entry shift register in registers
+    if (need_ps && lane < 4) {
+        float r[SAM_ABCD];
+#pragma unroll
+        for (int k = 0; k < SAM_ABCD; k++) r[k] = ws->abcd[lane][k];
+        float cc[SAM_STAGES];
+#pragma unroll
+        for (int k = 0; k < SAM_STAGES; k++) cc[k] = (lane & 1) ? sam_c1[k] : sam_c0[k];
+        const bool delayed = lane == 0 || lane == 2;
+        float ds = lane == 0 ? ws->dsI : ws->dsQ;
+        const float *e = (lane == 0 || lane == 3) ? ec : es;
+        for (int j = 0; j < n; j++) {
+            const float2 x = s_agc[j];
+            const float v = e[j] * (lane < 2 ? x.x : x.y);
+            r[0] = delayed ? ds : v;
+            ds = v;
+#pragma unroll
+            for (int k = 0; k < 3 * SAM_STAGES; k += 3) r[k + 3] = cc[k / 3] * (r[k] - r[k + 5]) + r[k + 2];
+            ps[lane * KG_POST_MAX_SAMPLES + j] = r[3 * SAM_STAGES];
+#pragma unroll
+            for (int k = SAM_ABCD - 1; k > 0; k--) r[k] = r[k - 1];
+        }
+#pragma unroll
+        for (int k = 0; k < SAM_ABCD; k++) ws->abcd[lane][k] = r[k];
+        if (lane == 0) ws->dsI = ds;
+        if (lane == 2) ws->dsQ = ds;
+    }
+    __syncthreads();
+
+    // 3. the mode's audio (:258-300), every sample on its own
+    for (int j = lane; j < n; j += 64) {
+        const float2 x = s_agc[j];
+        const float sn = es[j], cs = ec[j];
+        const float ai = cs * x.x, bi = sn * x.x, aq = cs * x.y, bq = sn * x.y;
+        const float corrI = +ai + bq, corrQ = -bi + aq;
+        float ai_ps = 0, bi_ps = 0, bq_ps = 0, aq_ps = 0;
+        if (need_ps) {
+            ai_ps = ps[j]; bi_ps = ps[KG_POST_MAX_SAMPLES + j];
+            bq_ps = ps[2 * KG_POST_MAX_SAMPLES + j]; aq_ps = ps[3 * KG_POST_MAX_SAMPLES + j];
+        }
+        const float lsb = (ai_ps + bi_ps) - (aq_ps - bq_ps), usb = (ai_ps - bi_ps) + (aq_ps + bq_ps);
+        float audio = 0, audiou = 0, audion = 0;
+        if (mode == KG_POST_SAM) {
+            if (is_null) { audio = lsb; audiou = usb; audion = which == 1 ? audio - audiou : audiou - audio; }
+            else audio = corrI;
+        } else if (mode == KG_POST_SAU) audio = usb;
+        else if (mode == KG_POST_SAL) audio = lsb;
+        else if (mode == KG_POST_SAS) { audio = lsb; audiou = usb; }
+        else {                                                          // C-QUAM
+            audio = corrI / 2 + corrQ / 2; audio *= 2;
+            audiou = corrI / 2 - corrQ / 2; audiou *= 2;
+        }
+        aud[j] = audio; audu[j] = audiou; audn[j] = audion; cI[j] = corrI;
+    }
+    __syncthreads();
+
+    // 4. fade leveler + DC block (:305-329): three independent recursions, lanes 0..2
+    const bool walk = lane == 0 ? (fade || dcb) : lane == 1 ? stereo_or_null && (fade || dcb) : lane == 2 ? is_null && dcb : false;
+    if (walk) {
+        float *a = lane == 0 ? aud : lane == 1 ? audu : audn;
+        double z1 = lane == 0 ? ws->z1 : lane == 1 ? ws->z1_u : ws->z1_n;
+        float dc = lane == 0 ? ws->dc : ws->dcu, dci = lane == 0 ? ws->dc_insert : ws->dc_insertu;
+        const bool lev = fade && lane < 2;
+        const float mR = ws->mtauR, omR = ws->onem_mtauR, mI = ws->mtauI, omI = ws->onem_mtauI;
+        for (int j = 0; j < n; j++) {
+            float audio = a[j];
+            if (lev) {
+                dc = mR * dc + omR * audio;
+                dci = mI * dci + omI * cI[j];
+                audio = audio + dci - dc;
+            }
+            if (dcb) {
+                const float z0 = audio + (z1 * 0.99f);                  // DC_ALPHA
+                audio = z0 - z1;
+                z1 = z0;
+            }
+            a[j] = audio;
+        }
+        if (lane == 0) { ws->z1 = z1; ws->dc = dc; ws->dc_insert = dci; }
+        else if (lane == 1) { ws->z1_u = z1; ws->dcu = dc; ws->dc_insertu = dci; }
+        else ws->z1_n = z1;
+    }
+    __syncthreads();
+
+    // 5. outputs (:307-329): out[i] (TYPEMONO16), the stereo / nulled pair back into agc_samps_c
+    for (int j = lane; j < n; j += 64) {
+        if (!stereo_or_null) {
+            aud[j] = (float) post_mono16(aud[j]);
+        } else if (is_null) {
+            const float an = audn[j];
+            aud[j] = (float) post_mono16(an);
+            if (pagc) pagc[j] = which == 1 ? make_float2(an, 0.f) : make_float2(0.f, an);
+        } else if (pagc) {
+            pagc[j] = make_float2(aud[j], audu[j]);
+        }
+    }
+    __syncthreads();
+}
+
 // The two seams called on their own: m_*_FIR[ch].ProcessFilter(n, in, out) (kind 0: real -> real, 1: real -> mono16, 2: mono16 ->
 // mono16) and m_Squelch[ch].PerformFMSquelch(n, in, out) -- the same device functions as the fused pass below.
 __global__ __launch_bounds__(64) void post_cfir_kernel(post_cfir *__restrict__ cfir_tab, const int *__restrict__ chans, int slot, int kind,
@@ -179,8 +356,10 @@ __global__ __launch_bounds__(64) void post_squelch_kernel(post_chan *__restrict_
     for (int j = lane; j < n; j += 64) out[(size_t) row * out_stride + j] = (short) res[j];
 }
 
+template <bool kSam>
 __global__ __launch_bounds__(64) void post_kernel(
-    post_chan *__restrict__ chan_tab, post_cfir *__restrict__ cfir_tab, float2 *__restrict__ ring_in, float *__restrict__ ring_mag,
+    post_chan *__restrict__ chan_tab, post_cfir *__restrict__ cfir_tab, post_sam *__restrict__ sam_tab, float2 *__restrict__ ring_in,
+    float *__restrict__ ring_mag,
     const int *__restrict__ chans, const float2 *__restrict__ fir, size_t in_stride, int n,
     short *__restrict__ o_s16, float *__restrict__ o_demod, float2 *__restrict__ o_agc, size_t out_stride, int by_chan)
 {
@@ -356,7 +535,15 @@ __global__ __launch_bounds__(64) void post_kernel(
         // rx_sound.cpp:876: m_Squelch.PerformFMSquelch(ns_out, demod_samps_r, out_samps_s2)
         post_squelch_block(pc, c, fir4 + POST_FIR_SQ_HP, bufB, s_taps, bufA, s_db, n, lane, &s_sq);
     }
-    if (c.mode == KG_POST_IQ) return;
+    if constexpr (kSam) {
+        if (c.mode >= KG_POST_SAM) {                    // rx_sound.cpp:791-806 (the AGC output is in s_agc and pagc)
+            __shared__ float s_ps[4 * KG_POST_MAX_SAMPLES];
+            __shared__ float s_aux[2 * KG_POST_MAX_SAMPLES];
+            post_sam_block(sam_tab + ch, c.mode, s_agc, bufA, bufA + KG_POST_MAX_SAMPLES, bufB, s_ps, s_db, s_aux,
+                           s_aux + KG_POST_MAX_SAMPLES, pagc, n, lane);
+        }
+    }
+    if (c.mode == KG_POST_IQ || c.mode == KG_POST_SAS || c.mode == KG_POST_QAM) return;      // stereo: no out_samps_s2 (IS_STEREO)
     // rx_sound.cpp:898-907: de-emphasis, out_samps_s2 in place
     const bool nbfm = c.mode == KG_POST_NBFM;
     const bool de_emp = nbfm ? c.deemp_nfm != 0 : c.deemp != 0;
@@ -391,6 +578,8 @@ struct kg_post {
     float2 *d_ring_in;
     float *d_ring_mag;
     post_cfir *d_cfir;                   // [nchan][POST_NFIR]
+    post_sam *d_sam;                     // [nchan]
+    std::vector<post_sam> h_sam;         // parameters only (the PLL type, its gains, the snd_rate constants, mparam)
     std::vector<post_chan> h_chan;       // parameters only; the state lives on the device
     std::vector<post_host> h_args;
     std::vector<post_cfir> h_cfir;       // taps as designed / handed over; pos and hist are the device's
@@ -414,6 +603,60 @@ template <typename T> static int post_put(kg_post *p, int ch, T post_chan::*fiel
     const size_t off = (size_t) ((char *) &(p->h_chan[ch].*field) - (char *) &p->h_chan[ch]);
     KG_HIP(hipMemcpyAsync((char *) (p->d_chan + ch) + off, &(p->h_chan[ch].*field), sizeof(T),
                           hipMemcpyHostToDevice, p->ctx->stream));
+    return KG_OK;
+}
+
+template <typename T> static int sam_put(kg_post *p, int ch, T post_sam::*field, const T &v)
+{
+    p->h_sam[ch].*field = v;
+    const size_t off = (size_t) ((char *) &(p->h_sam[ch].*field) - (char *) &p->h_sam[ch]);
+    KG_HIP(hipMemcpyAsync((char *) (p->d_sam + ch) + off, &(p->h_sam[ch].*field), sizeof(T), hipMemcpyHostToDevice, p->ctx->stream));
+    return KG_OK;
+}
+
+static bool post_is_sam(int mode) { return mode >= KG_POST_SAM && mode <= KG_POST_QAM; }
+
+// ---- wdsp_SAM_demod_init() and wdsp_SAM_PLL() (SAM_demod.cpp:113-163) on the host: f32_t members, double literals, int snd_rate
+static void sam_init_consts(post_sam &w, int snd_rate)
+{
+    const double K_2PI = 2.0 * 3.14159265358979323846;
+    const float pll_fmax = +22000.0, tauR = 0.02, tauI = 1.4;
+    w.snd_rate = snd_rate;
+    w.omega_min = K_2PI * (-pll_fmax) / snd_rate;
+    w.omega_max = K_2PI * pll_fmax / snd_rate;
+    w.mtauR = expf(-1 / (snd_rate * tauR));
+    w.onem_mtauR = 1.0 - w.mtauR;
+    w.mtauI = expf(-1 / (snd_rate * tauI));
+    w.onem_mtauI = 1.0 - w.mtauI;
+}
+
+static void sam_gains(post_sam &w)
+{
+    const int snd_rate = w.snd_rate;
+    w.g1 = 1.0 - expf(-2.0 * w.omegaN * w.zeta / snd_rate);
+    w.g2 = -w.g1 + 2.0 * (1 - expf(-w.omegaN * w.zeta / snd_rate) * cosf(w.omegaN / snd_rate * sqrtf(1.0 - w.zeta * w.zeta)));
+}
+
+static void sam_pll_host(post_sam &w, int type)       // PLL_RESET = -1, PLL_DX, PLL_MED, PLL_FAST (wdsp.h:14)
+{
+    if (type == -1) {
+        type = w.type;
+        memset(&w, 0, offsetof(post_sam, is_chan_null));
+        if (type == -1) type = 1;
+        sam_pll_host(w, type);
+        return;
+    }
+    if (type == 0) { w.zeta = 0.2; w.omegaN = 70; }
+    else if (type == 1) { w.zeta = 0.65; w.omegaN = 200.0; }
+    else { w.zeta = 1.0; w.omegaN = 500; }
+    sam_gains(w);
+    w.type = type;
+}
+
+// the PLL state as PLL_RESET leaves it, on the device
+static int sam_upload_reset(kg_post *p, int ch)
+{
+    KG_HIP(hipMemcpyAsync(p->d_sam + ch, &p->h_sam[ch], offsetof(post_sam, is_chan_null), hipMemcpyHostToDevice, p->ctx->stream));
     return KG_OK;
 }
 
@@ -558,6 +801,14 @@ int kg_post_create(kg_ctx *ctx, int nchan, kg_post **out)
     KG_HIP(hipMalloc((void **) &p->d_ring_in, sizeof(float2) * POST_CIRC * (size_t) nchan));
     KG_HIP(hipMalloc((void **) &p->d_ring_mag, sizeof(float) * POST_CIRC * (size_t) nchan));
     KG_HIP(hipMalloc((void **) &p->d_cfir, sizeof(post_cfir) * POST_NFIR * (size_t) nchan));
+    KG_HIP(hipMalloc((void **) &p->d_sam, sizeof(post_sam) * (size_t) nchan));
+    post_sam w;                                     // a new connection at snd_rate 12000: PLL(MED), PLL(RESET) (rx_sound.cpp:302-303)
+    memset(&w, 0, sizeof w);
+    sam_init_consts(w, 12000);
+    sam_pll_host(w, 1);
+    sam_pll_host(w, -1);
+    p->h_sam.assign(nchan, w);
+    KG_HIP(hipMemcpyAsync(p->d_sam, p->h_sam.data(), sizeof(post_sam) * nchan, hipMemcpyHostToDevice, ctx->stream));
     post_cfir f0;
     memset(&f0, 0, sizeof f0);
     f0.ntaps = 1;                                   // CFir::CFir(), fir.cpp:60-64 (its coefficient is indeterminate there: 0 here;
@@ -590,6 +841,7 @@ void kg_post_destroy(kg_post *p)
     (void) hipSetDevice(p->ctx->device);
     (void) hipStreamSynchronize(p->ctx->stream);
     (void) hipFree(p->d_chan); (void) hipFree(p->d_ring_in); (void) hipFree(p->d_ring_mag); (void) hipFree(p->d_cfir);
+    (void) hipFree(p->d_sam);
     kg_stage_cache_free(&p->list_cache);
     delete p;
 }
@@ -668,7 +920,15 @@ int kg_post_set_mode(kg_post *p, int ch, int mode)
 {
     int rc = post_check(p, ch, "kg_post_set_mode");
     if (rc) return rc;
-    KG_REQUIRE(mode >= KG_POST_IQ && mode <= KG_POST_NBFM, KG_ERR_INVALID, "kg_post_set_mode: mode %d", mode);
+    KG_REQUIRE(mode >= KG_POST_IQ && mode <= KG_POST_QAM, KG_ERR_INVALID, "kg_post_set_mode: mode %d", mode);
+    if (post_is_sam(mode) || post_is_sam(p->h_chan[ch].mode)) {
+        // rx_sound_cmd.cpp:214-226: a non-SAM -> SAM transition resets the PLL; every mode change clears s->isChanNull
+        if (post_is_sam(mode) && !post_is_sam(p->h_chan[ch].mode)) {
+            sam_pll_host(p->h_sam[ch], -1);
+            if ((rc = sam_upload_reset(p, ch))) return rc;
+        }
+        if ((rc = sam_put(p, ch, &post_sam::is_chan_null, 0))) return rc;
+    }
     if ((rc = post_put(p, ch, &post_chan::mode, mode))) return rc;
     KG_HIP(hipStreamSynchronize(p->ctx->stream));
     return KG_OK;
@@ -679,8 +939,15 @@ __global__ void math_kernel(int fn, float base, const float *__restrict__ x, uns
 {
     for (size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t) gridDim.x * blockDim.x) {
         const float v = x ? x[i] : __uint_as_float(first + (unsigned) i);
-        y[i] = fn == KG_MATH_LOG10F ? kg_libm::log10f_glibc(v) : fn == KG_MATH_POWF ? kg_libm::powf_glibc_pos(base, v) : kg_libm::expf_glibc(v);
+        y[i] = fn == KG_MATH_LOG10F ? kg_libm::log10f_glibc(v) : fn == KG_MATH_POWF ? kg_libm::powf_glibc_pos(base, v)
+             : fn == KG_MATH_SINF ? kg_libm::sinf_glibc(v) : fn == KG_MATH_COSF ? kg_libm::cosf_glibc(v) : kg_libm::expf_glibc(v);
     }
+}
+
+__global__ void atan2f_kernel(const float *__restrict__ y, const float *__restrict__ x, size_t n, float *__restrict__ out)
+{
+    for (size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t) gridDim.x * blockDim.x)
+        out[i] = kg_libm::atan2f_glibc(y[i], x[i]);
 }
 
 int kg_math_dev(kg_ctx *ctx, int fn, float base, const void *d_x, uint32_t first_bits, size_t n, void *d_y)
@@ -688,13 +955,90 @@ int kg_math_dev(kg_ctx *ctx, int fn, float base, const void *d_x, uint32_t first
     int rc = kg_ctx_use(ctx);
     if (rc) return rc;
     KG_REQUIRE(d_y && n >= 1 && ((uintptr_t) d_y & 3) == 0 && ((uintptr_t) d_x & 3) == 0, KG_ERR_INVALID, "kg_math_dev: bad argument");
-    KG_REQUIRE(fn == KG_MATH_LOG10F || fn == KG_MATH_POWF || fn == KG_MATH_EXPF, KG_ERR_INVALID, "kg_math_dev: unknown function");
+    KG_REQUIRE(fn == KG_MATH_LOG10F || fn == KG_MATH_POWF || fn == KG_MATH_EXPF || fn == KG_MATH_SINF || fn == KG_MATH_COSF, KG_ERR_INVALID,
+               "kg_math_dev: unknown function");
     KG_REQUIRE(fn != KG_MATH_POWF || (base >= 1.17549435e-38f && base < __builtin_huge_valf()), KG_ERR_INVALID,
                "kg_math_dev: powf's base must be positive, finite and normal (CAgc's is 10)");
     const size_t blocks = (n + 255) / 256;
     hipLaunchKernelGGL(math_kernel, dim3((unsigned) (blocks < 16384 ? blocks : 16384)), dim3(256), 0, ctx->stream, fn, base,
                        (const float *) d_x, first_bits, n, (float *) d_y);
     KG_HIP(hipGetLastError());
+    return KG_OK;
+}
+
+int kg_math_atan2f_dev(kg_ctx *ctx, const void *d_y, const void *d_x, size_t n, void *d_out)
+{
+    int rc = kg_ctx_use(ctx);
+    if (rc) return rc;
+    KG_REQUIRE(d_y && d_x && d_out && n >= 1 && ((uintptr_t) d_y & 3) == 0 && ((uintptr_t) d_x & 3) == 0 && ((uintptr_t) d_out & 3) == 0,
+               KG_ERR_INVALID, "kg_math_atan2f_dev: bad argument");
+    const size_t blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(atan2f_kernel, dim3((unsigned) (blocks < 16384 ? blocks : 16384)), dim3(256), 0, ctx->stream, (const float *) d_y,
+                       (const float *) d_x, n, (float *) d_out);
+    KG_HIP(hipGetLastError());
+    return KG_OK;
+}
+
+int kg_post_sam_setup(kg_post *p, int ch, int snd_rate)
+{
+    int rc = post_check(p, ch, "kg_post_sam_setup");
+    if (rc) return rc;
+    KG_REQUIRE(snd_rate == 12000 || snd_rate == 20250, KG_ERR_INVALID, "kg_post_sam_setup: snd_rate %d (12000 or 20250)", snd_rate);
+    post_sam &w = p->h_sam[ch];
+    sam_init_consts(w, snd_rate);
+    sam_gains(w);                                   // what wdsp_SAM_PLL() computes from then on
+    const size_t a = offsetof(post_sam, snd_rate), b = offsetof(post_sam, onem_mtauI) + sizeof(float);
+    KG_HIP(hipMemcpyAsync((char *) (p->d_sam + ch) + a, (char *) &w + a, b - a, hipMemcpyHostToDevice, p->ctx->stream));
+    if ((rc = sam_put(p, ch, &post_sam::g1, w.g1))) return rc;
+    if ((rc = sam_put(p, ch, &post_sam::g2, w.g2))) return rc;
+    KG_HIP(hipStreamSynchronize(p->ctx->stream));
+    return KG_OK;
+}
+
+int kg_post_sam_pll(kg_post *p, int ch, int type)
+{
+    int rc = post_check(p, ch, "kg_post_sam_pll");
+    if (rc) return rc;
+    KG_REQUIRE(type >= -1 && type <= 2, KG_ERR_INVALID, "kg_post_sam_pll: type %d (-1 reset, 0 DX, 1 MED, 2 FAST)", type);
+    post_sam &w = p->h_sam[ch];
+    sam_pll_host(w, type);
+    if (type == -1) {
+        if ((rc = sam_upload_reset(p, ch))) return rc;
+    } else {
+        if ((rc = sam_put(p, ch, &post_sam::zeta, w.zeta))) return rc;
+        if ((rc = sam_put(p, ch, &post_sam::omegaN, w.omegaN))) return rc;
+        if ((rc = sam_put(p, ch, &post_sam::g1, w.g1))) return rc;
+        if ((rc = sam_put(p, ch, &post_sam::g2, w.g2))) return rc;
+        if ((rc = sam_put(p, ch, &post_sam::type, w.type))) return rc;
+    }
+    KG_HIP(hipStreamSynchronize(p->ctx->stream));
+    return KG_OK;
+}
+
+int kg_post_set_sam_mparam(kg_post *p, int ch, int mparam)
+{
+    int rc = post_check(p, ch, "kg_post_set_sam_mparam");
+    if (rc) return rc;
+    if ((rc = sam_put(p, ch, &post_sam::mparam, mparam & 0xf))) return rc;         // MODE_FLAGS_SAM (rx_sound.h:39)
+    KG_HIP(hipStreamSynchronize(p->ctx->stream));
+    return KG_OK;
+}
+
+int kg_post_sam_state(kg_post *p, const int32_t *chans, int nch, float *carrier, int32_t *is_chan_null, float *phzerror)
+{
+    KG_REQUIRE(p && chans, KG_ERR_INVALID, "kg_post_sam_state: null argument");
+    int rc = kg_ctx_use(p->ctx);
+    if (rc) return rc;
+    std::vector<post_sam> h(p->nchan);
+    KG_HIP(hipMemcpyAsync(h.data(), p->d_sam, sizeof(post_sam) * p->nchan, hipMemcpyDeviceToHost, p->ctx->stream));
+    KG_HIP(hipStreamSynchronize(p->ctx->stream));
+    for (int i = 0; i < nch; i++) {
+        KG_REQUIRE(chans[i] >= 0 && chans[i] < p->nchan, KG_ERR_INVALID, "kg_post_sam_state: chans[%d] = %d", i, chans[i]);
+        const float c = h[chans[i]].sam_carrier;
+        if (carrier) carrier[i] = c != c ? 0.f : c;                                      // wdsp_SAM_carrier() (SAM_demod.cpp:165-170)
+        if (is_chan_null) is_chan_null[i] = h[chans[i]].is_chan_null;
+        if (phzerror) phzerror[i] = h[chans[i]].phzerror;
+    }
     return KG_OK;
 }
 
@@ -715,6 +1059,9 @@ int kg_post_reset(kg_post *p, int ch)
     if ((rc = post_put(p, ch, &post_chan::z1, 0.0))) return rc;
     if ((rc = post_put(p, ch, &post_chan::last_re, 0.f))) return rc;
     if ((rc = post_put(p, ch, &post_chan::last_im, 0.f))) return rc;
+    sam_pll_host(p->h_sam[ch], 1);                  // rx_sound.cpp:302-303
+    sam_pll_host(p->h_sam[ch], -1);
+    if ((rc = sam_upload_reset(p, ch))) return rc;
     KG_HIP(hipStreamSynchronize(p->ctx->stream));
     return KG_OK;
 }
@@ -731,6 +1078,7 @@ int kg_post_process_dev(kg_post *p, const int32_t *chans, int nch, const void *d
     KG_REQUIRE(in_stride >= (size_t) nsamps && out_stride >= (size_t) nsamps, KG_ERR_INVALID,
                "kg_post_process_dev: stride smaller than nsamps");
     std::vector<char> seen(p->nchan, 0);
+    bool any_sam = false;
     for (int i = 0; i < nch; i++) {
         KG_REQUIRE(chans[i] >= 0 && chans[i] < p->nchan && !seen[chans[i]], KG_ERR_INVALID,
                    "kg_post_process_dev: chans[%d] = %d out of range or listed twice", i, chans[i]);
@@ -743,15 +1091,18 @@ int kg_post_process_dev(kg_post *p, const int32_t *chans, int nch, const void *d
                    "kg_post_process_dev: channel %d is in NBFM mode without kg_post_squelch_setup + kg_post_squelch_set (rx_sound.cpp:261-262)", ch);
         KG_REQUIRE(!(mode == KG_POST_NBFM && p->h_chan[ch].deemp_nfm) || fr[POST_FIR_DEEMP_NFM], KG_ERR_STATE,
                    "kg_post_process_dev: channel %d has NBFM de-emphasis on and no m_nfm_deemp_FIR coefficients", ch);
-        KG_REQUIRE(!((mode == KG_POST_AM || mode == KG_POST_SSB) && p->h_chan[ch].deemp) || fr[POST_FIR_DEEMP_AM_SSB], KG_ERR_STATE,
+        const bool mono_am_ssb = mode == KG_POST_AM || mode == KG_POST_SSB || mode == KG_POST_SAM || mode == KG_POST_SAU || mode == KG_POST_SAL;
+        KG_REQUIRE(!(mono_am_ssb && p->h_chan[ch].deemp) || fr[POST_FIR_DEEMP_AM_SSB], KG_ERR_STATE,
                    "kg_post_process_dev: channel %d has AM/SSB de-emphasis on and no m_am_ssb_deemp_FIR coefficients", ch);
+        any_sam |= post_is_sam(mode);
     }
     hipStream_t st = p->ctx->stream;
     void *d_list = nullptr;
     if ((rc = kg_ctx_stage_cached(p->ctx, &p->list_cache, chans, sizeof(int) * nch, &d_list))) return rc;
     KG_PLAN_ONLY(p->ctx);
-    hipLaunchKernelGGL(post_kernel, dim3(nch), dim3(64), 0, st, p->d_chan, p->d_cfir, p->d_ring_in, p->d_ring_mag,
-                       (const int *) d_list, (const float2 *) d_fir, in_stride, nsamps,
+    // a batch with a SAM-family channel takes the kernel instance with the SAM stage (and its LDS); every other batch the one without
+    hipLaunchKernelGGL(any_sam ? post_kernel<true> : post_kernel<false>, dim3(nch), dim3(64), 0, st, p->d_chan, p->d_cfir, p->d_sam,
+                       p->d_ring_in, p->d_ring_mag, (const int *) d_list, (const float2 *) d_fir, in_stride, nsamps,
                        (short *) d_s16, (float *) d_demod, (float2 *) d_agc, out_stride, p->ctx->rows_by_chan);
     KG_HIP(hipGetLastError());
     return KG_OK;

@@ -170,11 +170,13 @@ static int bank_pass(kg_rxbank *b, const void *d_adc, bool plan)
                                           b->d_agc + o, b->firo_stride)))
                 return rc;
             tk.lap(b, PF_POST, pf);
-            // the real modes' blocks go through the ADPCM coder, the IQ mode's out as (s2_t) pairs (rx_sound.cpp:1076-1140)
+            // the real modes' blocks go through the ADPCM coder, the stereo modes' (IS_STEREO: IQ, SAS, QAM) as (s2_t) pairs of the agc
+            // buffer, where SAS / QAM leave their (L, R) pair (rx_sound.cpp:1042-1140)
             b->real_list.clear(); b->iq_le_list.clear(); b->iq_be_list.clear();
             for (int i = 0; i < NB; i++) {
                 const int k = b->blk_list[i];
-                if (kg_post_get_mode(b->post, k) != KG_POST_IQ) b->real_list.push_back(k);
+                const int m = kg_post_get_mode(b->post, k);
+                if (m != KG_POST_IQ && m != KG_POST_SAS && m != KG_POST_QAM) b->real_list.push_back(k);
                 else (b->little_endian[k] ? b->iq_le_list : b->iq_be_list).push_back(k);
             }
             if (!b->real_list.empty() &&

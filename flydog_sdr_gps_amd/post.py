@@ -15,6 +15,11 @@ Reference                                                              here
   m_Squelch.PerformFMSquelch        rx/rx_sound.cpp:876-877          -> Post.process (mode NBFM, s16), Post.squelch_state
   "SET de_emp=%d nfm=%d"            rx/rx_sound_cmd.cpp:543-585      -> Post.set_de_emp (tables: deemp.py)
   m_*_deemp_FIR.ProcessFilter       rx/rx_sound.cpp:898-907          -> Post.process (s16, in place)
+  wdsp_SAM_demod (SAM/SAU/SAL/SAS/QAM) rx/rx_sound.cpp:791-806      -> Post.process (modes SAM .. QAM)
+  wdsp_SAM_demod_init()             rx/wdsp/SAM_demod.cpp:154-163    -> Post.sam_setup
+  wdsp_SAM_PLL(type), SET sam_pll=  SAM_demod.cpp:113-152            -> Post.sam_pll
+  s->SAM_mparam                     rx/rx_sound_cmd.cpp:216          -> Post.set_sam_mparam
+  wdsp_SAM_carrier(), s->isChanNull SAM_demod.cpp:165-170            -> Post.sam_state
 """
 import ctypes as C
 
@@ -23,6 +28,11 @@ import numpy as np
 from ._lib import Context, check, ptr, own_rows
 
 MODE_IQ, MODE_SSB, MODE_AM, MODE_NBFM = range(4)      # KG_POST_* of include/kiwigpu.h
+MODE_SAM, MODE_SAU, MODE_SAL, MODE_SAS, MODE_QAM = range(4, 9)
+SAM_MODES = (MODE_SAM, MODE_SAU, MODE_SAL, MODE_SAS, MODE_QAM)
+STEREO_MODES = (MODE_IQ, MODE_SAS, MODE_QAM)          # IS_STEREO (rx/mode.h:45-55): the packet carries IQ payload
+PLL_RESET, PLL_DX, PLL_MED, PLL_FAST = -1, 0, 1, 2    # rx/wdsp/wdsp.h:14
+CHAN_NULL_LSB, CHAN_NULL_USB, FADE_LEVELER, DC_BLOCK = 1, 2, 4, 8    # SAM_mparam bits, wdsp.h:5-10
 MAX_SAMPLES = 1024                                    # KG_POST_MAX_SAMPLES
 CFIR_AM, CFIR_DEEMP_NFM, CFIR_DEEMP_AM_SSB, CFIR_SQUELCH_HP = range(4)  # KG_CFIR_*
 CFIR_REAL_REAL, CFIR_REAL_MONO16, CFIR_MONO16_MONO16 = range(3)        # the ProcessFilter overloads
@@ -67,6 +77,25 @@ class Post:
 
     def reset(self, ch):
         check(self.lib.kg_post_reset(self.h, int(ch)), "kg_post_reset")
+
+    # ---- the synchronous-AM demodulator (rx/wdsp/SAM_demod.cpp) ----
+    def sam_setup(self, ch, snd_rate):
+        check(self.lib.kg_post_sam_setup(self.h, int(ch), int(snd_rate)), "kg_post_sam_setup")
+
+    def sam_pll(self, ch, pll_type):
+        check(self.lib.kg_post_sam_pll(self.h, int(ch), int(pll_type)), "kg_post_sam_pll")
+
+    def set_sam_mparam(self, ch, mparam):
+        check(self.lib.kg_post_set_sam_mparam(self.h, int(ch), int(mparam)), "kg_post_set_sam_mparam")
+
+    def sam_state(self, chans):
+        """-> (SAM_carrier float32[n] (NaN -> 0), isChanNull int32[n], phzerror float32[n]) after the last pass"""
+        chans = np.ascontiguousarray(chans, np.int32)
+        car = np.zeros(chans.size, np.float32)
+        null = np.zeros(chans.size, np.int32)
+        phz = np.zeros(chans.size, np.float32)
+        check(self.lib.kg_post_sam_state(self.h, ptr(chans), chans.size, ptr(car), ptr(null), ptr(phz)), "kg_post_sam_state")
+        return car, null, phz
 
     # ---- CFir objects (rx/CuteSDR/fir.cpp) ----
     def cfir_init_lp(self, ch, which, numtaps, scale, astop, fpass, fstop, fs):
@@ -203,7 +232,7 @@ class Post:
         return avg, taps
 
 
-MATH_LOG10F, MATH_POWF, MATH_EXPF = 0, 1, 2          # KG_MATH_*
+MATH_LOG10F, MATH_POWF, MATH_EXPF, MATH_SINF, MATH_COSF = 0, 1, 2, 3, 4          # KG_MATH_*
 
 
 def math_dev(ctx, fn, x=None, first_bits=0, n=None, base=10.0):
@@ -232,3 +261,23 @@ def math_dev(ctx, fn, x=None, first_bits=0, n=None, base=10.0):
 
 def log10f(ctx, x=None, first_bits=0, n=None):
     return math_dev(ctx, MATH_LOG10F, x, first_bits, n)
+
+
+def math_atan2f_dev(ctx, y, x):
+    """kg_math_atan2f_dev: the device's atan2f (glibc 2.35's e_atan2f.c restated, csrc/kg_libm_trig.h) over float32 arrays -> float32"""
+    y = np.ascontiguousarray(y, np.float32).reshape(-1)
+    x = np.ascontiguousarray(x, np.float32).reshape(-1)
+    assert y.size == x.size and y.size >= 1
+    n = y.size
+    out = np.empty(n, np.float32)
+    d_y, d_x, d_o = ctx.alloc(4 * n), ctx.alloc(4 * n), ctx.alloc(4 * n)
+    try:
+        ctx.upload(d_y, y)
+        ctx.upload(d_x, x)
+        check(ctx.lib.kg_math_atan2f_dev(ctx.h, C.c_void_p(d_y), C.c_void_p(d_x), n, C.c_void_p(d_o)), "kg_math_atan2f_dev")
+        ctx.sync()
+        ctx.download(d_o, out)
+    finally:
+        for d in (d_y, d_x, d_o):
+            ctx.free(d)
+    return out

@@ -124,10 +124,11 @@ class RxBank:
               "kg_rxbank_set_wf_pkt")
         self.params[rx], self.overlapped[rx] = params, bool(overlapped)
 
-    def set_audio(self, rx, phase_inc, lo=300.0, hi=2700.0, fs=None, mode=post_mod.MODE_SSB, de_emp=0, squelch=0):
+    def set_audio(self, rx, phase_inc, lo=300.0, hi=2700.0, fs=None, mode=post_mod.MODE_SSB, de_emp=0, squelch=0, sam_mparam=0):
         """A connection's `SET mod= low_cut= high_cut= freq=`, `SET de_emp=`, `SET squelch=` for receiver rx: NCO, passband
         filter and the post-AM-detector filter designed with it (rx/rx_sound_cmd.cpp:268-282), AGC / S-meter / detector, the
-        squelch of a new connection (rx/rx_sound.cpp:261-262) then the command's value, the mode's de-emphasis filter."""
+        squelch of a new connection (rx/rx_sound.cpp:261-262) then the command's value, the mode's de-emphasis filter.
+        mode: any post.MODE_* (the SAM family included: its PLL at the nominal snd_rate nearest fs, SAM_mparam = sam_mparam)."""
         fs = self.fs if fs is None else fs
         fmax = int(fs / 2 - 1)                          # the handler clamps the client's cuts first (rx_sound_cmd.cpp:248-250)
         lo, hi = max(float(lo), float(-fmax)), min(float(hi), float(fmax))
@@ -137,6 +138,8 @@ class RxBank:
         self.post.set_am_passband(rx, lo, hi, fs)
         self.post.set_agc(rx, True, False, -100, 50, 6, 1000, fs)
         self.post.set_smeter(rx, fs)
+        self.post.sam_setup(rx, 12000 if abs(fs - 12000.0) < abs(fs - 20250.0) else 20250)
+        self.post.set_sam_mparam(rx, sam_mparam)
         self.post.set_mode(rx, mode)
         self.post.reset(rx)
         self.post.squelch_setup(rx, fs)

@@ -418,9 +418,17 @@ enum {                      /* what follows the S-meter for a channel (the `swit
     KG_POST_IQ   = 0,       /* MODE_IQ/DRM: CAgc complex -> complex (rx_sound.cpp:1096-1100)                      -> d_agc */
     KG_POST_SSB  = 1,       /* MODE_USB/USN/LSB/LSN/CW/CWN: CAgc complex -> mono16 (:893)                         -> d_s16 */
     KG_POST_AM   = 2,       /* MODE_AM/AMN: CAgc, envelope, DC-removal IIR (:766-783) -> d_demod; m_AM_FIR (:787) -> d_s16 */
-    KG_POST_NBFM = 3        /* MODE_NBFM/NNFM: CAgc, fmdemod_quadri + clipper (:845-875) -> d_demod;
+    KG_POST_NBFM = 3,       /* MODE_NBFM/NNFM: CAgc, fmdemod_quadri + clipper (:845-875) -> d_demod;
                              * m_Squelch.PerformFMSquelch (:876, rx/CuteSDR/squelch.cpp:151-231)                  -> d_s16 */
-};                          /* SSB, AM, NBFM: then the de-emphasis filter over d_s16 in place when it is on (:898-907)   */
+    /* the synchronous-AM family (:791-806): CAgc, then wdsp_SAM_demod() (rx/wdsp/SAM_demod.cpp:210-356) over the AGC output */
+    KG_POST_SAM  = 4,       /* MODE_SAM: corr[I]; with a channel null (kg_post_set_sam_mparam) the nulled sideband   -> d_s16
+                             * (and (audion, 0) / (0, audion) written over d_agc, as over agc_samps_c)                 */
+    KG_POST_SAU  = 5,       /* MODE_SAU: the upper sideband of the phase-shifted products                           -> d_s16 */
+    KG_POST_SAL  = 6,       /* MODE_SAL: the lower sideband                                                          -> d_s16 */
+    KG_POST_SAS  = 7,       /* MODE_SAS: (lsb, usb) over d_agc; stereo (IS_STEREO): no d_s16, the packet is IQ payload    */
+    KG_POST_QAM  = 8        /* MODE_QAM: C-QUAM (L, R) = corr[I] +- corr[Q] over d_agc; stereo as SAS                     */
+};                          /* SSB, AM, NBFM, SAM, SAU, SAL: then the de-emphasis filter over d_s16 in place when it is on
+                             * (:898-907; the SAM family takes the AM / SSB filter)                                       */
 
 #define KG_POST_MAX_SAMPLES 1024  /* per call and channel; c2s_sound() hands over ns_out = 512 */
 
@@ -445,15 +453,34 @@ int kg_post_get_mode(kg_post *post, int chan);              /* -> KG_POST_*, or 
  * functions restate the GNU C Library 2.35 algorithms of this image (csrc/kg_libm.h) and equal them bit for bit on every argument
  * (tests/test_libm_gpu.py, tools/check_libm.py --exhaustive), which is what makes the audio chain's outputs the reference's own bits.
  * Enqueue only. */
-enum { KG_MATH_LOG10F = 0, KG_MATH_POWF = 1, KG_MATH_EXPF = 2 };
+enum { KG_MATH_LOG10F = 0, KG_MATH_POWF = 1, KG_MATH_EXPF = 2,
+       KG_MATH_SINF = 3, KG_MATH_COSF = 4 };   /* the SAM PLL's sinf / cosf of its phase error (rx/wdsp/SAM_demod.cpp:218-219) */
 int kg_math_dev(kg_ctx *ctx, int fn, float base, const void *d_x, uint32_t first_bits, size_t n, void *d_y);
+/* d_out[i] = atan2f(d_y[i], d_x[i]): the SAM PLL's phase detector (SAM_demod.cpp:331), the image's glibc 2.35 e_atan2f.c restated
+ * (csrc/kg_libm_trig.h; tests/test_sam_libm_gpu.py, tools/check_sam_libm.cpp).  Enqueue only. */
+int kg_math_atan2f_dev(kg_ctx *ctx, const void *d_y, const void *d_x, size_t n, void *d_out);
 /* A new connection on the channel: sMeterAvg_dB = 0, z1 = 0 (rx_sound.cpp:244,250),
- * conn->last_sample = 0.  The AGC object persists across connections, as m_Agc[] does. */
+ * conn->last_sample = 0, wdsp_SAM_PLL(PLL_MED) + wdsp_SAM_PLL(PLL_RESET) (:302-303).  The AGC object persists across
+ * connections, as m_Agc[] does. */
 int kg_post_reset(kg_post *post, int chan);
+/* The synchronous-AM demodulator of a channel (rx/wdsp/SAM_demod.cpp).  kg_post_set_mode from a non-SAM mode into KG_POST_SAM ..
+ * KG_POST_QAM resets its PLL, and every mode change clears isChanNull (rx_sound_cmd.cpp:214-226).
+ * kg_post_sam_setup: wdsp_SAM_demod_init() (:154-163) for the server's nominal snd_rate, 12000 or 20250 (not frate): omega_min / max
+ * and the fade leveler's constants; the PLL gains are recomputed at that rate.  A fresh object is at 12000, PLL MED, reset.
+ * kg_post_sam_pll: wdsp_SAM_PLL(type) (:113-152), `SET sam_pll=%d` (rx_sound_cmd.cpp:444-451): -1 PLL_RESET (the previous type,
+ * state cleared), 0 DX, 1 MED, 2 FAST.  kg_post_set_sam_mparam: s->SAM_mparam = mparam & MODE_FLAGS_SAM (rx_sound_cmd.cpp:216):
+ * bits 0-1 the channel null (1 LSB, 2 USB), 4 FADE_LEVELER, 8 DC_BLOCK (wdsp.h:5-10).  The gains and constants are computed on the
+ * host with the reference's float / double expressions and the host libm. */
+int kg_post_sam_setup(kg_post *post, int chan, int snd_rate);
+int kg_post_sam_pll(kg_post *post, int chan, int type);
+int kg_post_set_sam_mparam(kg_post *post, int chan, int mparam);
+/* After the last pass: carrier[i] = wdsp_SAM_carrier() (SAM_demod.cpp:165-170, the UI's carrier offset in Hz, NaN -> 0),
+ * is_chan_null[i] = s->isChanNull (rx_sound.cpp:802), phzerror[i] = the PLL's phase.  Any output may be NULL.  Synchronises. */
+int kg_post_sam_state(kg_post *post, const int32_t *chans, int nch, float *carrier, int32_t *is_chan_null, float *phzerror);
 /* One pass over nsamps FIR output samples of each listed channel (d_fir + i*in_stride,
  * complex float).  Outputs (any may be NULL) at row i*out_stride of d_s16 (int16: out_samps_s2, every
- * mode but IQ), d_demod (float: the detector's output, AM / NBFM), d_agc (complex float: the AGC's output,
- * every mode but SSB).  Float -> mono16 is
+ * mode but IQ, SAS and QAM), d_demod (float: the detector's output, AM / NBFM), d_agc (complex float: the AGC's output,
+ * every mode but SSB; in SAS / QAM the stereo pair and in channel-null SAM the nulled pair written over it, rx_sound.cpp:802).  Float -> mono16 is
  * the reference's (TYPEMONO16) cast: truncation; outside the int16 range (undefined in
  * C) the low 16 bits of the int32 conversion, as x86 does.  Enqueue only. */
 int kg_post_process_dev(kg_post *post, const int32_t *chans, int nch, const void *d_fir, size_t in_stride,
@@ -705,8 +732,9 @@ int kg_rxbank_audio_map(kg_rxbank *bank, int32_t *nrec, int32_t *nfir, int32_t *
 int kg_rxbank_set_wf_pkt(kg_rxbank *bank, int rx, uint32_t x_bin_server, uint32_t zoom, int use_compression);
 /* snd_service() unpack parameters (default: rescale of rx/data_pump.cpp:73-74, no DC offset, no inversion) */
 /* "SET little-endian" of a connection (rx/rx_sound.cpp:1076-1096): the byte order of receiver rx's IQ-mode payload (default:
- * network order).  A receiver whose kg_post mode is KG_POST_IQ gets its sound blocks as IQ payload rows (bufs.iq_pay), the
- * others as ADPCM rows (bufs.adpcm); the mode is read at every step. */
+ * network order).  A receiver whose kg_post mode is stereo (IS_STEREO: KG_POST_IQ, KG_POST_SAS, KG_POST_QAM) gets its sound blocks
+ * as IQ payload rows (bufs.iq_pay; SAS / QAM: their (L, R) pair, rx_sound.cpp:1047-1049), the others as ADPCM rows (bufs.adpcm);
+ * the mode is read at every step. */
 int kg_rxbank_set_little_endian(kg_rxbank *bank, int rx, int little_endian);
 int kg_rxbank_set_unpack(kg_rxbank *bank, float rescale, float dc_i, float dc_q, int spectral_inversion);
 

@@ -1,5 +1,6 @@
 """Times kg_post_process_dev for a batch of receiver channels (512 samples per channel and
-launch, the ns_out of c2s_sound()).  usage: python tools/time_post.py [nchan ...]"""
+launch, the ns_out of c2s_sound()), mode by mode (SAM: plain; SAU / SAS: the Hilbert chains; QAM: fade leveler + DC block).
+usage: python tools/time_post.py [nchan ...]"""
 import os
 import sys
 
@@ -16,12 +17,13 @@ for nchan in [int(a) for a in sys.argv[1:]] or [14, 128, 1024, 8192]:
     t = np.arange(n)
     x = (3000 * np.exp(2j * np.pi * rng.uniform(0.01, 0.2, (nchan, 1)) * t)
          + rng.normal(0, 30, (nchan, n)) + 1j * rng.normal(0, 30, (nchan, n))).astype(np.complex64)
-    for mode in (post.MODE_SSB, post.MODE_AM, post.MODE_NBFM):
+    for mode in (post.MODE_SSB, post.MODE_AM, post.MODE_NBFM, post.MODE_SAM, post.MODE_SAU, post.MODE_SAS, post.MODE_QAM):
         for ch in range(nchan):
             P.set_agc(ch, True, ch & 1, -100, 50, 6, 1000, 12000.0)
             P.set_smeter(ch, 12000.0)
             P.set_mode(ch, mode)
             P.set_am_passband(ch, -4900, 4900, 12000.0); P.squelch_setup(ch, 12000.0); P.squelch_set(ch, 0, 0)
+            P.set_sam_mparam(ch, 12 if mode == post.MODE_QAM else 0)
         chans = np.arange(nchan, dtype=np.int32)
         d_x = ctx.alloc(x.nbytes); ctx.upload(d_x, x)
         d_s = ctx.alloc(nchan * n * 2); d_d = ctx.alloc(nchan * n * 4); d_a = ctx.alloc(nchan * n * 8)
