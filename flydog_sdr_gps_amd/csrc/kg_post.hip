@@ -31,9 +31,18 @@
 //     audio, audiou, audion on lanes 0..2; the mono16 cast and the stores across all lanes.  No recurrence is reassociated.
 //     The SAM state is a parallel table (post_sam) and the stage lives in its own instance of the kernel (post_kernel<true>,
 //     launched only for a batch that holds a SAM-family channel), so the other modes' kernel is the one it was.
+//   * the noise-reduction switch (rx/rx_sound.cpp:933-949: wdsp's variable-leak LMS, rx/wdsp/ANR.cpp, and the original 121-tap LMS,
+//     rx/kiwi/lms.cpp) is split by dependence too.  What depends only on the stage's input -- the d values, wdsp's sigma of every
+//     sample (a serial sum of its own) and its double division -- runs per sample across the lanes ahead of the recursion; the tap
+//     products and the weight / coefficient updates run across the lanes (one tap per lane and pass); the ordered sums y / fir and
+//     the scalar recurrences (kg_nr.h, shared with the host driver of tests/test_nr_cpu.py) are walked by every lane at once over the
+//     products in LDS, so no lane waits for a broadcast.  Nothing is reassociated.  The stage is a kernel of its own (post_nr_kernel)
+//     that kg_post_process_dev enqueues behind post_kernel only for a batch that holds a channel with NR on, over that launch's
+//     d_s16 rows in place.
 #include "kg_common.h"
 #include "kg_libm.h"
 #include "kg_libm_trig.h"
+#include "kg_nr.h"
 
 #include <math.h>
 #include <stddef.h>
@@ -554,6 +563,162 @@ __global__ __launch_bounds__(64) void post_kernel(
         for (int j = lane; j < n; j += 64) ps16[j] = (short) s_db[j];
 }
 
+// ---- the noise-reduction switch (rx/rx_sound.cpp:933-949) ----
+// A channel's s->nr_algo / s->nr_enable[] and its four filter objects: wdsp_ANR[type][ch] (ANR.cpp:40) and m_LMS[ch][type]
+// (lms.cpp:17).  The objects persist across connections, mode changes and algo switches, as the reference's statics do; a fresh
+// kg_post holds them zeroed, as the statics start.
+struct post_nr {
+    int algo, en[2], pad;
+    kg_nr::anr_t anr[2];
+    kg_nr::lms_t lms[2];
+    float anr_d[2][kg_nr::ANR_DLINE], anr_w[2][kg_nr::ANR_DLINE];
+    float lms_ring[2][kg_nr::LMS_RING], lms_coef[2][128];
+};
+#define NR_HIST 512               // history in front of the block in X: every age either filter reads (ANR <= 511, CLMS <= 420)
+#define NR_WPL (kg_nr::ANR_DLINE / 64)    // ANR weights per lane at taps = 512
+
+__device__ __forceinline__ bool post_is_stereo(int mode) { return mode == KG_POST_IQ || mode == KG_POST_SAS || mode == KG_POST_QAM; }
+
+// wdsp_ANR_filter(ch, nr_type, n, io, io) (ANR.cpp:64-116) over the int16-valued floats io (LDS, in place).  X: LDS, NR_HIST + n
+// floats (the d values by age, linear: X[NR_HIST + i - m] = d[(in_idx_i + m) & 511]); P: LDS, 512 floats, 16-byte aligned;
+// S, Q: LDS, n floats.
+__device__ __forceinline__ void post_anr_block(post_nr *__restrict__ nr, int t, float *io, float *X, float *P, float *S, float *Q, int n, int lane)
+{
+    kg_nr::anr_t w = nr->anr[t];
+    float *dl = nr->anr_d[t], *wt = nr->anr_w[t];
+    const int T = w.taps < 0 ? 0 : w.taps, K = (T + 63) / 64;
+    for (int m = lane + 1; m <= NR_HIST; m += 64) X[NR_HIST - m] = dl[(w.in_idx + m) & kg_nr::ANR_MASK];
+    for (int i = lane; i < n; i += 64) X[NR_HIST + i] = kg_nr::sample_in((short) io[i]);
+    __syncthreads();
+    // sigma and inv_sigp of every sample depend on the input alone: one sample per lane, its sum serial in j (:76-81, :83)
+    for (int i = lane; i < n; i += 64) {
+        const float *x = X + NR_HIST + i;
+        float sigma = 0;
+        for (int j = 0; j < T; j++) {
+            const float v = x[-(int) (((unsigned) j + (unsigned) w.delay) & kg_nr::ANR_MASK)];
+            sigma += v * v;
+        }
+        S[i] = sigma;
+        Q[i] = kg_nr::anr_inv_sigp(sigma);
+    }
+    float wr[NR_WPL];
+    int ag[NR_WPL];
+#pragma unroll
+    for (int k = 0; k < NR_WPL; k++) {
+        const int j = lane + 64 * k;
+        wr[k] = j < T ? wt[j] : 0.f;
+        ag[k] = (int) (((unsigned) j + (unsigned) w.delay) & kg_nr::ANR_MASK);
+    }
+    __syncthreads();
+    for (int i = 0; i < n; i++) {
+        const float *x = X + NR_HIST + i;
+#pragma unroll
+        for (int k = 0; k < NR_WPL; k++)
+            if (k < K && lane + 64 * k < T) P[lane + 64 * k] = wr[k] * x[-ag[k]];                // w->w[j] * w->d[idx]
+        __syncthreads();
+        float y = 0;                                                                            // :77-81, in j order
+        int j = 0;
+        for (; j + 4 <= T; j += 4) {
+            const float4 p = *(const float4 *) (P + j);
+            y += p.x; y += p.y; y += p.z; y += p.w;
+        }
+        for (; j < T; j++) y += P[j];
+        float c0, c1;
+        const short o = kg_nr::anr_step(w, t, x[0], y, S[i], Q[i], c0, c1);                    // :83-107, every lane
+#pragma unroll
+        for (int k = 0; k < NR_WPL; k++)
+            if (k < K) wr[k] = kg_nr::anr_weight(wr[k], x[-ag[k]], c0, c1);                     // :109-112
+        if (lane == 0) io[i] = o;
+        __syncthreads();
+    }
+    const int in_idx = (w.in_idx - n) & kg_nr::ANR_MASK;                                        // :114, n times
+#pragma unroll
+    for (int k = 0; k < NR_WPL; k++)
+        if (lane + 64 * k < T) wt[lane + 64 * k] = wr[k];
+    for (int m = lane + 1; m <= NR_HIST; m += 64) dl[(in_idx + m) & kg_nr::ANR_MASK] = X[NR_HIST + n - m];
+    if (lane == 0) { w.in_idx = in_idx; nr->anr[t] = w; }
+    __syncthreads();
+}
+
+// CLMS::ProcessFilter(n, io, io) (lms.cpp:83-123).  The ring of L = m_dlen + 121 floats, linear: X[NR_HIST + i - a] is the sample of
+// age a at sample i, and tap c of the Wiener filter reads age m_dlen + 120 - c.  X, P as post_anr_block.
+__device__ __forceinline__ void post_lms_block(post_nr *__restrict__ nr, int t, float *io, float *X, float *P, int n, int lane)
+{
+    kg_nr::lms_t m = nr->lms[t];
+    float *ring = nr->lms_ring[t], *coef = nr->lms_coef[t];
+    const int L = m.dlen + kg_nr::LMSLEN;
+    for (int a = lane + 1; a < L; a += 64) X[NR_HIST - a] = ring[(m.dlp - a + L) % L];
+    for (int i = lane; i < n; i += 64) X[NR_HIST + i] = kg_nr::sample_in((short) io[i]);
+    const bool two = lane + 64 < kg_nr::LMSLEN;
+    float cr0 = coef[lane], cr1 = two ? coef[lane + 64] : 0.f;
+    const int off0 = m.dlen + kg_nr::LMSLEN - 1 - lane, off1 = off0 - 64;
+    __syncthreads();
+    for (int i = 0; i < n; i++) {
+        const float *x = X + NR_HIST + i;
+        P[lane] = x[-off0] * cr0;                                                               // m_dline[m_dlp] * m_lmscoef[i]
+        if (two) P[lane + 64] = x[-off1] * cr1;
+        __syncthreads();
+        float fir = 0;                                                                          // :95-99, in i order
+        int c = 0;
+        for (; c + 4 <= kg_nr::LMSLEN; c += 4) {
+            const float4 p = *(const float4 *) (P + c);
+            fir += p.x; fir += p.y; fir += p.z; fir += p.w;
+        }
+        for (; c < kg_nr::LMSLEN; c++) fir += P[c];
+        short o = 0;
+        if (m.nr_type == kg_nr::DENOISE) o = kg_nr::lms_out_denoise(fir);                        // :102-104
+        const float err = kg_nr::lms_err(x[0], fir);
+        if (m.nr_type == kg_nr::AUTONOTCH) o = kg_nr::sample_out(err);                           // :108-110
+        const float err2 = kg_nr::lms_err2(err, m.beta);
+        cr0 = kg_nr::lms_coef(x[-off0], err2, cr0, m.decay);                                    // :116-120
+        if (two) cr1 = kg_nr::lms_coef(x[-off1], err2, cr1, m.decay);
+        if (lane == 0) io[i] = o;
+        __syncthreads();
+    }
+    const int dlp = (m.dlp + n) % L;
+    coef[lane] = cr0;
+    if (two) coef[lane + 64] = cr1;
+    for (int a = lane + 1; a <= L; a += 64) ring[(dlp - a + L) % L] = X[NR_HIST + n - a];
+    if (lane == 0) nr->lms[t].dlp = dlp;
+    __syncthreads();
+}
+
+// kFused: the stage of c2s_sound() behind post_kernel, over its d_s16 rows in place: channels in a stereo mode, with an algo other
+// than NR_WDSP / NR_ORIG or with neither type enabled return at once; else auto-notch, then denoise (:933-949).
+// !kFused: kg_post_nr_process_dev, the filter of `type` under each listed channel's algo.
+template <bool kFused>
+__global__ __launch_bounds__(64) void post_nr_kernel(post_nr *__restrict__ nr_tab, const post_chan *__restrict__ chan_tab,
+                                                     const int *__restrict__ chans, int type, const short *in, size_t in_stride, int n,
+                                                     short *out, size_t out_stride, int by_chan)
+{
+    __shared__ float X[NR_HIST + KG_POST_MAX_SAMPLES];
+    __shared__ __attribute__((aligned(16))) float P[kg_nr::ANR_DLINE];
+    __shared__ float S[KG_POST_MAX_SAMPLES], Q[KG_POST_MAX_SAMPLES], io[KG_POST_MAX_SAMPLES];
+    const int lane = threadIdx.x, ch = chans[blockIdx.x];
+    post_nr *nr = nr_tab + ch;
+    const int algo = nr->algo;
+    bool an = type == kg_nr::AUTONOTCH, dn = type == kg_nr::DENOISE;
+    if (kFused) {
+        if (post_is_stereo(chan_tab[ch].mode) || (algo != KG_NR_WDSP && algo != KG_NR_ORIG)) return;
+        an = nr->en[kg_nr::AUTONOTCH] != 0; dn = nr->en[kg_nr::DENOISE] != 0;
+        if (!an && !dn) return;
+    }
+    const int row = kFused && by_chan ? ch : (int) blockIdx.x;                     // kg_ctx::rows_by_chan (the fused pass only)
+    const short *src = in + (size_t) row * in_stride;
+    short *dst = out + (size_t) row * out_stride;
+    for (int i = lane; i < n; i += 64) io[i] = (float) src[i];
+    __syncthreads();
+    if (an) {
+        if (algo == KG_NR_WDSP) post_anr_block(nr, kg_nr::AUTONOTCH, io, X, P, S, Q, n, lane);
+        else post_lms_block(nr, kg_nr::AUTONOTCH, io, X, P, n, lane);
+    }
+    if (dn) {
+        if (algo == KG_NR_WDSP) post_anr_block(nr, kg_nr::DENOISE, io, X, P, S, Q, n, lane);
+        else post_lms_block(nr, kg_nr::DENOISE, io, X, P, n, lane);
+    }
+    for (int i = lane; i < n; i += 64) dst[i] = (short) io[i];
+}
+
 __global__ void post_reset_rings_kernel(float2 *ring_in, float *ring_mag, int ch0)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x, ch = ch0 + blockIdx.y;
@@ -571,6 +736,11 @@ struct post_host {               // the SetParameters() arguments last seen (agc
     float slope_factor, sample_rate;
 };
 
+struct post_nr_host {             // the snd_t fields of the noise-reduction commands (rx_sound.h:130-132)
+    int algo, en[2];
+    float param[2][kg_nr::NPARAMS];
+};
+
 struct kg_post {
     kg_ctx *ctx;
     int nchan;
@@ -585,6 +755,8 @@ struct kg_post {
     std::vector<post_cfir> h_cfir;       // taps as designed / handed over; pos and hist are the device's
     std::vector<char> h_fir_ready;       // [nchan][POST_NFIR]: initialised since create
     std::vector<char> h_sq_ready;        // kg_post_squelch_setup AND kg_post_squelch_set were called
+    post_nr *d_nr;                       // [nchan]
+    std::vector<post_nr_host> h_nr;      // s->nr_algo, s->nr_enable[], s->nr_param[][] (the filter states are the device's)
     kg_stage_cache list_cache = {};      // the channel list of the last process call
 };
 
@@ -785,6 +957,22 @@ static int post_reset_agc_state(kg_post *p, int ch)         // agc.cpp:117-131
     return KG_OK;
 }
 
+// ---- the noise-reduction commands' state (rx/rx_sound_cmd.cpp:464-471, :505-523) ----
+static bool nr_active(const post_nr_host &h, int mode)
+{
+    return (h.algo == KG_NR_WDSP || h.algo == KG_NR_ORIG) && (h.en[0] || h.en[1]) &&
+           mode != KG_POST_IQ && mode != KG_POST_SAS && mode != KG_POST_QAM;
+}
+
+static int nr_put_ctl(kg_post *p, int ch)          // s->nr_algo and s->nr_enable[] to the device
+{
+    const post_nr_host &h = p->h_nr[ch];
+    const int v[3] = {h.algo, h.en[0], h.en[1]};
+    KG_HIP(hipMemcpyAsync((char *) (p->d_nr + ch) + offsetof(post_nr, algo), v, sizeof v, hipMemcpyHostToDevice, p->ctx->stream));
+    KG_HIP(hipStreamSynchronize(p->ctx->stream));      // (v is on the stack)
+    return KG_OK;
+}
+
 extern "C" {
 
 int kg_post_create(kg_ctx *ctx, int nchan, kg_post **out)
@@ -802,6 +990,11 @@ int kg_post_create(kg_ctx *ctx, int nchan, kg_post **out)
     KG_HIP(hipMalloc((void **) &p->d_ring_mag, sizeof(float) * POST_CIRC * (size_t) nchan));
     KG_HIP(hipMalloc((void **) &p->d_cfir, sizeof(post_cfir) * POST_NFIR * (size_t) nchan));
     KG_HIP(hipMalloc((void **) &p->d_sam, sizeof(post_sam) * (size_t) nchan));
+    KG_HIP(hipMalloc((void **) &p->d_nr, sizeof(post_nr) * (size_t) nchan));
+    KG_HIP(hipMemsetAsync(p->d_nr, 0, sizeof(post_nr) * (size_t) nchan, ctx->stream));     // the zeroed statics, NR_OFF_
+    post_nr_host nh;
+    memset(&nh, 0, sizeof nh);
+    p->h_nr.assign(nchan, nh);
     post_sam w;                                     // a new connection at snd_rate 12000: PLL(MED), PLL(RESET) (rx_sound.cpp:302-303)
     memset(&w, 0, sizeof w);
     sam_init_consts(w, 12000);
@@ -841,7 +1034,7 @@ void kg_post_destroy(kg_post *p)
     (void) hipSetDevice(p->ctx->device);
     (void) hipStreamSynchronize(p->ctx->stream);
     (void) hipFree(p->d_chan); (void) hipFree(p->d_ring_in); (void) hipFree(p->d_ring_mag); (void) hipFree(p->d_cfir);
-    (void) hipFree(p->d_sam);
+    (void) hipFree(p->d_sam); (void) hipFree(p->d_nr);
     kg_stage_cache_free(&p->list_cache);
     delete p;
 }
@@ -1062,6 +1255,8 @@ int kg_post_reset(kg_post *p, int ch)
     sam_pll_host(p->h_sam[ch], 1);                  // rx_sound.cpp:302-303
     sam_pll_host(p->h_sam[ch], -1);
     if ((rc = sam_upload_reset(p, ch))) return rc;
+    memset(&p->h_nr[ch], 0, sizeof(post_nr_host));  // :236-240: memset(s) zeroes nr_enable / nr_param, nr_algo = NR_OFF_; the filters stay
+    if ((rc = nr_put_ctl(p, ch))) return rc;
     KG_HIP(hipStreamSynchronize(p->ctx->stream));
     return KG_OK;
 }
@@ -1078,7 +1273,7 @@ int kg_post_process_dev(kg_post *p, const int32_t *chans, int nch, const void *d
     KG_REQUIRE(in_stride >= (size_t) nsamps && out_stride >= (size_t) nsamps, KG_ERR_INVALID,
                "kg_post_process_dev: stride smaller than nsamps");
     std::vector<char> seen(p->nchan, 0);
-    bool any_sam = false;
+    bool any_sam = false, any_nr = false;
     for (int i = 0; i < nch; i++) {
         KG_REQUIRE(chans[i] >= 0 && chans[i] < p->nchan && !seen[chans[i]], KG_ERR_INVALID,
                    "kg_post_process_dev: chans[%d] = %d out of range or listed twice", i, chans[i]);
@@ -1095,7 +1290,10 @@ int kg_post_process_dev(kg_post *p, const int32_t *chans, int nch, const void *d
         KG_REQUIRE(!(mono_am_ssb && p->h_chan[ch].deemp) || fr[POST_FIR_DEEMP_AM_SSB], KG_ERR_STATE,
                    "kg_post_process_dev: channel %d has AM/SSB de-emphasis on and no m_am_ssb_deemp_FIR coefficients", ch);
         any_sam |= post_is_sam(mode);
+        any_nr |= nr_active(p->h_nr[ch], mode);
     }
+    KG_REQUIRE(!any_nr || d_s16, KG_ERR_INVALID,
+               "kg_post_process_dev: a listed channel has noise reduction on, and it runs over d_s16: d_s16 must not be NULL");
     hipStream_t st = p->ctx->stream;
     void *d_list = nullptr;
     if ((rc = kg_ctx_stage_cached(p->ctx, &p->list_cache, chans, sizeof(int) * nch, &d_list))) return rc;
@@ -1105,6 +1303,12 @@ int kg_post_process_dev(kg_post *p, const int32_t *chans, int nch, const void *d
                        p->d_ring_in, p->d_ring_mag, (const int *) d_list, (const float2 *) d_fir, in_stride, nsamps,
                        (short *) d_s16, (float *) d_demod, (float2 *) d_agc, out_stride, p->ctx->rows_by_chan);
     KG_HIP(hipGetLastError());
+    // rx_sound.cpp:933-949 over the rows just written, only for a batch that holds a channel with NR on (the others return at once)
+    if (any_nr) {
+        hipLaunchKernelGGL(post_nr_kernel<true>, dim3(nch), dim3(64), 0, st, p->d_nr, p->d_chan, (const int *) d_list, -1,
+                           (const short *) d_s16, out_stride, nsamps, (short *) d_s16, out_stride, p->ctx->rows_by_chan);
+        KG_HIP(hipGetLastError());
+    }
     return KG_OK;
 }
 
@@ -1282,4 +1486,106 @@ int kg_post_smeter(kg_post *p, const int32_t *chans, int nch, float *avg_dB, flo
     return KG_OK;
 }
 
+int kg_post_set_nr_algo(kg_post *p, int ch, int algo)
+{
+    int rc = post_check(p, ch, "kg_post_set_nr_algo");
+    if (rc) return rc;
+    KG_REQUIRE(algo != KG_NR_SPECTRAL, KG_ERR_INVALID, "kg_post_set_nr_algo: NR_SPECTRAL is not implemented");
+    post_nr_host &h = p->h_nr[ch];
+    h.algo = algo;                                  // rx_sound_cmd.cpp:465-469: any other value is a switch without a case
+    h.en[0] = h.en[1] = 0;
+    return nr_put_ctl(p, ch);
+}
+
+int kg_post_set_nr_enable(kg_post *p, int ch, int type, int en)
+{
+    int rc = post_check(p, ch, "kg_post_set_nr_enable");
+    if (rc) return rc;
+    KG_REQUIRE(type == KG_NR_DENOISE || type == KG_NR_AUTONOTCH, KG_ERR_INVALID, "kg_post_set_nr_enable: type %d", type);
+    p->h_nr[ch].en[type] = en;                      // :506-509
+    return nr_put_ctl(p, ch);
+}
+
+int kg_post_set_nr_param(kg_post *p, int ch, int type, int param, float pval)
+{
+    int rc = post_check(p, ch, "kg_post_set_nr_param");
+    if (rc) return rc;
+    KG_REQUIRE(type == KG_NR_DENOISE || type == KG_NR_AUTONOTCH, KG_ERR_INVALID, "kg_post_set_nr_param: type %d", type);
+    KG_REQUIRE(param >= 0 && param < kg_nr::NPARAMS, KG_ERR_INVALID, "kg_post_set_nr_param: param %d (0..%d)", param, kg_nr::NPARAMS - 1);
+    post_nr_host &h = p->h_nr[ch];
+    float v[kg_nr::NPARAMS];
+    memcpy(v, h.param[type], sizeof v);
+    v[param] = pval;                                // :512-521: stored, then type `type` of the current algo re-initialised from v
+    KG_REQUIRE(h.algo != KG_NR_WDSP || kg_nr::anr_params_ok(v), KG_ERR_INVALID,
+               "kg_post_set_nr_param: wdsp_ANR_init would be undefined on taps %g, delay %g (finite, in int; taps <= 512, "
+               "delay <= INT_MAX - 1022)", (double) v[0], (double) v[1]);
+    KG_REQUIRE(h.algo != KG_NR_ORIG || kg_nr::lms_params_ok(v), KG_ERR_INVALID,
+               "kg_post_set_nr_param: CLMS::Initialize would convert a NaN delay-line length");
+    memcpy(h.param[type], v, sizeof v);
+    post_nr *d = p->d_nr + ch;
+    hipStream_t st = p->ctx->stream;
+    if (h.algo == KG_NR_WDSP) {
+        post_nr f;                                  // (a staging copy; only the slot of `type` is used)
+        kg_nr::anr_init(f.anr[type], f.anr_d[type], f.anr_w[type], v);
+        KG_HIP(hipMemcpyAsync(&d->anr[type], &f.anr[type], sizeof f.anr[type], hipMemcpyHostToDevice, st));
+        KG_HIP(hipMemcpyAsync(d->anr_d[type], f.anr_d[type], sizeof f.anr_d[type], hipMemcpyHostToDevice, st));
+        KG_HIP(hipMemcpyAsync(d->anr_w[type], f.anr_w[type], sizeof f.anr_w[type], hipMemcpyHostToDevice, st));
+        KG_HIP(hipStreamSynchronize(st));
+    } else if (h.algo == KG_NR_ORIG) {
+        post_nr f;
+        memset(f.lms_coef[type], 0, sizeof f.lms_coef[type]);
+        kg_nr::lms_init(f.lms[type], f.lms_ring[type], f.lms_coef[type], type, v);
+        KG_HIP(hipMemcpyAsync(&d->lms[type], &f.lms[type], sizeof f.lms[type], hipMemcpyHostToDevice, st));
+        KG_HIP(hipMemcpyAsync(d->lms_ring[type], f.lms_ring[type], sizeof f.lms_ring[type], hipMemcpyHostToDevice, st));
+        KG_HIP(hipMemcpyAsync(d->lms_coef[type], f.lms_coef[type], sizeof f.lms_coef[type], hipMemcpyHostToDevice, st));
+        KG_HIP(hipStreamSynchronize(st));
+    }
+    return KG_OK;
+}
+
+int kg_post_nr_process_dev(kg_post *p, const int32_t *chans, int nch, int type, const void *d_in, size_t in_stride, int nsamps,
+                           void *d_out, size_t out_stride)
+{
+    KG_REQUIRE(p && chans && d_in && d_out, KG_ERR_INVALID, "kg_post_nr_process_dev: null argument");
+    int rc = kg_ctx_use(p->ctx);
+    if (rc) return rc;
+    KG_REQUIRE(type == KG_NR_DENOISE || type == KG_NR_AUTONOTCH, KG_ERR_INVALID, "kg_post_nr_process_dev: type %d", type);
+    KG_REQUIRE(nsamps >= 1 && nsamps <= KG_POST_MAX_SAMPLES && in_stride >= (size_t) nsamps && out_stride >= (size_t) nsamps, KG_ERR_INVALID,
+               "kg_post_nr_process_dev: nsamps %d (1..%d), strides %zu / %zu", nsamps, KG_POST_MAX_SAMPLES, in_stride, out_stride);
+    void *d_list = nullptr;
+    if ((rc = post_list(p, chans, nch, "kg_post_nr_process_dev", &d_list))) return rc;
+    for (int i = 0; i < nch; i++)
+        KG_REQUIRE(p->h_nr[chans[i]].algo == KG_NR_WDSP || p->h_nr[chans[i]].algo == KG_NR_ORIG, KG_ERR_STATE,
+                   "kg_post_nr_process_dev: channel %d: its algo is %d (KG_NR_WDSP or KG_NR_ORIG)", chans[i], p->h_nr[chans[i]].algo);
+    KG_PLAN_ONLY(p->ctx);
+    hipLaunchKernelGGL(post_nr_kernel<false>, dim3(nch), dim3(64), 0, p->ctx->stream, p->d_nr, p->d_chan, (const int *) d_list, type,
+                       (const short *) d_in, in_stride, nsamps, (short *) d_out, out_stride, 0);
+    KG_HIP(hipGetLastError());
+    return KG_OK;
+}
+
+int kg_post_nr_state(kg_post *p, const int32_t *chans, int nch, int type, int32_t *anr_i, float *anr_f, int32_t *lms_i, float *anr_w,
+                     float *lms_coef)
+{
+    KG_REQUIRE(p && chans && nch >= 0, KG_ERR_INVALID, "kg_post_nr_state: null argument");
+    int rc = kg_ctx_use(p->ctx);
+    if (rc) return rc;
+    KG_REQUIRE(type == KG_NR_DENOISE || type == KG_NR_AUTONOTCH, KG_ERR_INVALID, "kg_post_nr_state: type %d", type);
+    post_nr h;
+    for (int i = 0; i < nch; i++) {
+        KG_REQUIRE(chans[i] >= 0 && chans[i] < p->nchan, KG_ERR_INVALID, "kg_post_nr_state: chans[%d] = %d", i, chans[i]);
+        KG_HIP(hipMemcpyAsync(&h, p->d_nr + chans[i], sizeof h, hipMemcpyDeviceToHost, p->ctx->stream));
+        KG_HIP(hipStreamSynchronize(p->ctx->stream));
+        const kg_nr::anr_t &a = h.anr[type];
+        const kg_nr::lms_t &m = h.lms[type];
+        if (anr_i) { anr_i[3 * i] = a.in_idx; anr_i[3 * i + 1] = a.taps; anr_i[3 * i + 2] = a.delay; }
+        if (anr_f) { anr_f[2 * i] = a.lidx; anr_f[2 * i + 1] = a.ngamma; }
+        if (lms_i) { lms_i[3 * i] = m.dlp; lms_i[3 * i + 1] = m.dlen; lms_i[3 * i + 2] = m.nr_type; }
+        if (anr_w) memcpy(anr_w + (size_t) i * kg_nr::ANR_DLINE, h.anr_w[type], sizeof h.anr_w[type]);
+        if (lms_coef) memcpy(lms_coef + (size_t) i * kg_nr::LMSLEN, h.lms_coef[type], sizeof(float) * kg_nr::LMSLEN);
+    }
+    return KG_OK;
+}
+
 }  // extern "C"
+

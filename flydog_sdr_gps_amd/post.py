@@ -20,6 +20,10 @@ Reference                                                              here
   wdsp_SAM_PLL(type), SET sam_pll=  SAM_demod.cpp:113-152            -> Post.sam_pll
   s->SAM_mparam                     rx/rx_sound_cmd.cpp:216          -> Post.set_sam_mparam
   wdsp_SAM_carrier(), s->isChanNull SAM_demod.cpp:165-170            -> Post.sam_state
+  "SET nr algo=" / "SET nr type= en=" / "SET nr type= param= pval="
+                                    rx/rx_sound_cmd.cpp:464-523      -> Post.set_nr_algo / set_nr_enable / set_nr_param
+  the noise-reduction switch (NR_WDSP: wdsp_ANR_filter, NR_ORIG: CLMS::ProcessFilter)
+                                    rx/rx_sound.cpp:933-949          -> Post.process (s16, in place), Post.nr_process, Post.nr_state
 """
 import ctypes as C
 
@@ -36,6 +40,11 @@ CHAN_NULL_LSB, CHAN_NULL_USB, FADE_LEVELER, DC_BLOCK = 1, 2, 4, 8    # SAM_mpara
 MAX_SAMPLES = 1024                                    # KG_POST_MAX_SAMPLES
 CFIR_AM, CFIR_DEEMP_NFM, CFIR_DEEMP_AM_SSB, CFIR_SQUELCH_HP = range(4)  # KG_CFIR_*
 CFIR_REAL_REAL, CFIR_REAL_MONO16, CFIR_MONO16_MONO16 = range(3)        # the ProcessFilter overloads
+NR_OFF, NR_WDSP, NR_ORIG, NR_SPECTRAL = range(4)      # KG_NR_* (nr_algo_e, rx/rx_noise.h:9); NR_SPECTRAL is refused
+NR_DENOISE, NR_AUTONOTCH = 0, 1                       # nr_type_e
+NR_DELAY, NR_BETA, NR_DECAY = 0, 1, 2                 # NR_ORIG's parameters (extensions/noise_filter/noise_filter.h)
+NR_TAPS, NR_DLY, NR_GAIN, NR_LEAKAGE = 0, 1, 2, 3     # NR_WDSP's
+NR_PARAMS = 8
 
 
 class Post:
@@ -98,6 +107,54 @@ class Post:
         return car, null, phz
 
     # ---- CFir objects (rx/CuteSDR/fir.cpp) ----
+    # ---- the noise-reduction switch (rx/rx_sound.cpp:933-949) ----
+    def set_nr_algo(self, ch, algo):
+        """`SET nr algo=`: the algo, both enables cleared, no filter state touched"""
+        check(self.lib.kg_post_set_nr_algo(self.h, int(ch), int(algo)), "kg_post_set_nr_algo")
+
+    def set_nr_enable(self, ch, nr_type, en):
+        check(self.lib.kg_post_set_nr_enable(self.h, int(ch), int(nr_type), int(en)), "kg_post_set_nr_enable")
+
+    def set_nr_param(self, ch, nr_type, param, pval):
+        """`SET nr type= param= pval=`: stores the float and re-initialises that type of the current algo from its whole vector"""
+        check(self.lib.kg_post_set_nr_param(self.h, int(ch), int(nr_type), int(param), float(np.float32(pval))), "kg_post_set_nr_param")
+
+    def nr_process_dev(self, chans, nr_type, d_in, in_stride, nsamps, d_out, out_stride=None):
+        chans = np.ascontiguousarray(chans, np.int32)
+        check(self.lib.kg_post_nr_process_dev(self.h, ptr(chans), chans.size, int(nr_type), ptr(int(d_in)), int(in_stride), int(nsamps),
+                                              ptr(int(d_out)), int(out_stride if out_stride is not None else nsamps)),
+              "kg_post_nr_process_dev")
+
+    def nr_process(self, chans, nr_type, x):
+        """x: int16 [len(chans), n] (host).  -> int16 [len(chans), n]: the filter of nr_type under each channel's algo"""
+        own_rows(self, "nr_process()")
+        chans = np.ascontiguousarray(chans, np.int32)
+        x = np.ascontiguousarray(x, np.int16).reshape(chans.size, -1)
+        n = x.shape[1]
+        y = np.empty_like(x)
+        ctx = self.ctx
+        b = ctx.alloc(x.nbytes)
+        try:
+            ctx.upload(b, x)
+            self.nr_process_dev(chans, nr_type, b, n, n, b, n)
+            ctx.sync()
+            ctx.download(b, y)
+        finally:
+            ctx.free(b)
+        return y
+
+    def nr_state(self, chans, nr_type, weights=False):
+        """-> dict: anr_i int32[n, 3] (in_idx, taps, delay), anr_f float32[n, 2] (lidx, ngamma), lms_i int32[n, 3] (dlp, dlen, nr_type)
+        and with weights=True anr_w float32[n, 512], lms_coef float32[n, 121]"""
+        chans = np.ascontiguousarray(chans, np.int32)
+        n = chans.size
+        r = dict(anr_i=np.zeros((n, 3), np.int32), anr_f=np.zeros((n, 2), np.float32), lms_i=np.zeros((n, 3), np.int32))
+        if weights:
+            r.update(anr_w=np.zeros((n, 512), np.float32), lms_coef=np.zeros((n, 121), np.float32))
+        check(self.lib.kg_post_nr_state(self.h, ptr(chans), n, int(nr_type), ptr(r["anr_i"]), ptr(r["anr_f"]), ptr(r["lms_i"]),
+                                        ptr(r.get("anr_w")), ptr(r.get("lms_coef"))), "kg_post_nr_state")
+        return r
+
     def cfir_init_lp(self, ch, which, numtaps, scale, astop, fpass, fstop, fs):
         """CFir::InitLPFilter -> tap count"""
         return check(self.lib.kg_post_cfir_init_lp(self.h, int(ch), int(which), int(numtaps), float(scale), float(astop), float(fpass),

@@ -171,6 +171,18 @@ class RxBank:
         if phase_inc is not None:
             self.set_audio(rx, phase_inc, **audio)
 
+    def set_nr(self, rx, algo, params=None, enable=(0, 0)):
+        """The noise-reduction commands for receiver rx as a client sends them (rx/rx_sound_cmd.cpp:464-523): `SET nr algo=`, then
+        every parameter one at a time (params: {type: [value of param 0, 1, ...]}), then the enables (denoise, auto-notch).  Call it
+        after set_audio, whose connection start clears them (post.NR_* constants)."""
+        self.post.set_nr_algo(rx, algo)
+        for t, vals in (params or {}).items():
+            for k, v in enumerate(vals):
+                self.post.set_nr_param(rx, t, k, v)
+        for t in (post_mod.NR_DENOISE, post_mod.NR_AUTONOTCH):
+            if enable[t]:
+                self.post.set_nr_enable(rx, t, enable[t])
+
     def set_little_endian(self, rx, little_endian):
         check(self.lib.kg_rxbank_set_little_endian(self.h, int(rx), int(bool(little_endian))), "kg_rxbank_set_little_endian")
         self.little_endian[rx] = bool(little_endian)

@@ -485,6 +485,47 @@ int kg_post_sam_state(kg_post *post, const int32_t *chans, int nch, float *carri
  * C) the low 16 bits of the int32 conversion, as x86 does.  Enqueue only. */
 int kg_post_process_dev(kg_post *post, const int32_t *chans, int nch, const void *d_fir, size_t in_stride,
                         int nsamps, void *d_s16, void *d_demod, void *d_agc, size_t out_stride);
+/* The noise-reduction switch of c2s_sound() (rx/rx_sound.cpp:933-949), after the de-emphasis filter and the NBFM squelch, in place
+ * on out_samps_s2 of every mode but the stereo ones (KG_POST_IQ, KG_POST_SAS, KG_POST_QAM): the auto-notch first, then the denoiser,
+ * each when enabled.  Two of the reference's three algorithms: NR_WDSP, wdsp's variable-leak LMS (rx/wdsp/ANR.cpp), and NR_ORIG,
+ * the 121-tap LMS (rx/kiwi/lms.cpp), bit for bit.  kg_post_process_dev runs it over its d_s16 rows for every listed channel whose
+ * algo is KG_NR_WDSP or KG_NR_ORIG with a type enabled; such a batch needs d_s16 (NULL is refused with KG_ERR_INVALID: the
+ * filter states must advance as the reference's do).  A batch with no such channel launches what it launched before. */
+enum { KG_NR_OFF = 0, KG_NR_WDSP = 1, KG_NR_ORIG = 2, KG_NR_SPECTRAL = 3 };     /* nr_algo_e, rx/rx_noise.h:9 */
+enum { KG_NR_DENOISE = 0, KG_NR_AUTONOTCH = 1 };                                 /* nr_type_e, rx/rx_noise.h:10 */
+enum { KG_NR_DELAY = 0, KG_NR_BETA = 1, KG_NR_DECAY = 2,                         /* NR_ORIG's parameters, extensions/noise_filter/noise_filter.h */
+       KG_NR_TAPS = 0, KG_NR_DLY = 1, KG_NR_GAIN = 2, KG_NR_LEAKAGE = 3,         /* NR_WDSP's */
+       KG_NR_PARAMS = 8 };                                                       /* NOISE_PARAMS, rx/rx_noise.h:4 */
+/* The three commands, with the reference's side effects.
+ * kg_post_set_nr_algo: `SET nr algo=` (rx_sound_cmd.cpp:464-471): the algo, and both enables cleared; no filter state changes.
+ * kg_post_set_nr_enable: `SET nr type= en=` (:505-510): any nonzero en enables.
+ * kg_post_set_nr_param: `SET nr type= param= pval=` (:511-521): the value is stored, then type `type` of the CURRENT algo is
+ * initialised from the whole stored vector of that type (wdsp_ANR_init or CLMS::Initialize, on the host in the reference's types);
+ * under any other algo only the value is stored.
+ * The filter objects of each algo and type persist across algo switches, mode changes (kg_post_set_mode leaves NR alone) and
+ * connections; kg_post_reset clears the algo (KG_NR_OFF), the enables and the stored parameters, as a new connection does
+ * (rx_sound.cpp:236-240).  A fresh object's filters are zeroed, as the reference's statics start: an enabled filter that was never
+ * initialised runs as that zero state does (a never-initialised CLMS is a denoiser in either slot).
+ * Refused with KG_ERR_INVALID, the inputs on which the reference is undefined or which are not implemented:
+ *   KG_NR_SPECTRAL (out of scope: it runs over its own transform);
+ *   a type other than KG_NR_DENOISE / KG_NR_AUTONOTCH (m_LMS[ch][2] is out of bounds);
+ *   a param index outside 0..7;
+ *   under KG_NR_WDSP, a vector whose taps or delay is NaN, infinite or outside int (the (int) conversion), taps > 512 (overruns
+ *   w[]) or delay > INT_MAX - 1022 (in_idx + j + delay overflows); under KG_NR_ORIG, a NaN delay-line length (its conversion).
+ *   The value is then not stored. */
+int kg_post_set_nr_algo(kg_post *post, int chan, int algo);
+int kg_post_set_nr_enable(kg_post *post, int chan, int type, int en);
+int kg_post_set_nr_param(kg_post *post, int chan, int type, int param, float pval);
+/* The standalone call site: wdsp_ANR_filter(ch, type, ...) or m_LMS[ch][type].ProcessFilter(...) under each listed channel's current
+ * algo (KG_NR_WDSP or KG_NR_ORIG, else KG_ERR_STATE), whatever its enables and mode: nsamps int16 at row i of d_in -> row i of d_out
+ * (d_in == d_out allowed).  The same device code as the fused pass.  Enqueue only. */
+int kg_post_nr_process_dev(kg_post *post, const int32_t *chans, int nch, int type, const void *d_in, size_t in_stride, int nsamps,
+                           void *d_out, size_t out_stride);
+/* The filter states of `type` for the listed channels, any output may be NULL: anr_i[3 i ..] = wdsp in_idx, taps, delay;
+ * anr_f[2 i ..] = lidx, ngamma; lms_i[3 i ..] = CLMS m_dlp, m_dlen, m_nr_type; anr_w[512 i ..] = wdsp w[]; lms_coef[121 i ..] =
+ * m_lmscoef[].  Synchronises. */
+int kg_post_nr_state(kg_post *post, const int32_t *chans, int nch, int type, int32_t *anr_i, float *anr_f, int32_t *lms_i,
+                     float *anr_w, float *lms_coef);
 /* The CFir objects of a channel (rx/rx_sound.cpp:153-156; rx/CuteSDR/fir.cpp): the filter behind the AM detector and the
  * two de-emphasis filters.  (CSquelch owns a fourth, its noise high-pass: kg_post_squelch_setup.) */
 enum { KG_CFIR_AM = 0, KG_CFIR_DEEMP_NFM = 1, KG_CFIR_DEEMP_AM_SSB = 2,
