@@ -92,6 +92,22 @@ SYMBOLS = {
     "kg_wf_frames_at_dev": (_i, [_vp, _i, _vp, _vp, C.c_uint64, _vp, _vp]),
     "kg_wf_frames": (_i, [_vp, _i, _vp, _vp, _vp]),
     "kg_wf_debug_frame": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "kg_wf_nb_setup": (_i, [_vp, _i, _vp]),
+    "kg_wf_set_nb": (_i, [_vp, _i, _i]),
+    "kg_wf_nb_frames_dev": (_i, [_vp, _i, _vp, _vp, C.c_uint64, _vp, _vp]),
+    "kg_wf_nb_state": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "kg_nb_create": (_i, [_vp, _i, _i, C.POINTER(_vp)]),
+    "kg_nb_destroy": (None, [_vp]),
+    "kg_nb_setup": (_i, [_vp, _i, C.c_float, _vp]),
+    "kg_nb_process_dev": (_i, [_vp, _vp, _i, _vp, _sz, _vp, _vp, _sz]),
+    "kg_nb_process": (_i, [_vp, _i, _vp, _i, _vp]),
+    "kg_nb_state": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "kg_rxbank_nb": (_vp, [_vp]),
+    "kg_rxbank_set_nb_algo": (_i, [_vp, _i, _i]),
+    "kg_rxbank_set_nb_enable": (_i, [_vp, _i, _i, _i]),
+    "kg_rxbank_set_nb_param": (_i, [_vp, _i, _i, _i, C.c_float, C.c_float]),
+    "kg_rxbank_set_nb_gate": (_i, [_vp, _i, _i, _i, C.c_float]),
+    "kg_rxbank_nb_cmd_state": (_i, [_vp, _i, _vp, _vp]),
     "kg_ddc_create": (_i, [_vp, _i, _sz, C.POINTER(_vp)]),
     "kg_ddc_destroy": (None, [_vp]),
     "kg_ddc_set_wf": (_i, [_vp, _i, C.c_uint64, _i]),

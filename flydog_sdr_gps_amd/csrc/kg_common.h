@@ -36,7 +36,7 @@ void kg_set_error(const char *fmt, ...);
 // REPLAY pass -- the same calls with the same arguments, after the block's one upload was enqueued -- they answer the same
 // addresses again, checking that the table is the one planned.
 enum { KG_ARENA_OFF = 0, KG_ARENA_PLAN = 1, KG_ARENA_REPLAY = 2 };
-#define KG_ARENA_MAX_ENTRIES 192     /* <= 12 tables per step + 4 per sound block of the step (kg_rxbank_create checks its step against it) */
+#define KG_ARENA_MAX_ENTRIES 196     /* <= 16 tables per step + 4 per sound block of the step (kg_rxbank_create checks its step against it) */
 struct kg_arena {
     int mode;
     unsigned char *h_base, *d_base;           // the current slot of the owner's ring (pinned host / device)
@@ -152,3 +152,22 @@ __attribute__((visibility("hidden"))) int kg_ddc_use_side_stream(kg_ddc *ddc, hi
 // that inherits a stream inherits its placement.  Synchronise a stream before giving it back.
 int kg_stream_get(int device, hipStream_t *out);          // the device is current (kg_ctx_use) when this is called
 void kg_stream_put(int device, hipStream_t s);
+
+// kg_nb.hip, for kg_wf.hip (not part of the ABI): a set of CNoiseProc states on the device (kg_nb.h), one per channel, and the
+// waterfall's blanker pre-pass over them.
+struct kg_nb_store;
+__attribute__((visibility("hidden"))) int kg_nb_store_create(int nchan, kg_nb_store **out);   // *out is set even on failure (destroy it)
+__attribute__((visibility("hidden"))) void kg_nb_store_destroy(kg_nb_store *s);                // the caller has drained the stream
+__attribute__((visibility("hidden"))) int kg_nb_store_was_setup(const kg_nb_store *s, int ch);
+// SetupBlanker(ch, sample_rate, nb_param) in stream order (refusals as kg_nb_setup's, messages under `who`)
+__attribute__((visibility("hidden"))) int kg_nb_store_setup(kg_ctx *ctx, kg_nb_store *s, int ch, float sample_rate, const float *nb_param,
+                                                            const char *who);
+__attribute__((visibility("hidden"))) int kg_nb_store_state(kg_ctx *ctx, kg_nb_store *s, const int32_t *chans, int nch, int32_t *ints,
+                                                            float *flts, const char *who);
+// ProcessBlankerOneShot on windowed frames: d_chl [nbch] {channel, first frame, frame count, window function}, d_fl [frames]
+// {first iq_t of the frame in d_iq, row of d_out}; d_out rows of 8192 complex floats.  Enqueue only, no checks.
+__attribute__((visibility("hidden"))) int kg_nb_wf_launch(kg_ctx *ctx, kg_nb_store *s, int nbch, const void *d_chl, const void *d_fl,
+                                                          const void *d_iq, const float *d_windows, void *d_out);
+// kg_nb.hip, for kg_rxbank.hip: whether channel ch of an audio blanker object was set up
+struct kg_nb;
+__attribute__((visibility("hidden"))) int kg_nb_was_setup(const kg_nb *nb, int ch);

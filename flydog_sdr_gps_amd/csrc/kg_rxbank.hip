@@ -20,6 +20,7 @@
 // below is called twice per step, first in the context's PLAN mode (kg_common.h, kg_arena: tables collected, nothing
 // launched, no state advanced), then -- behind the one transfer -- for real.
 #include "kg_common.h"
+#include "kg_nb.h"
 
 #include <chrono>
 #include <math.h>
@@ -51,6 +52,15 @@ struct kg_rxbank {
     hipStream_t s_ddc2;                         // the waterfall DDC's second stream (R = 1 bypass, pass B of R <= 8 beside the rest)
     kg_ctx *c_main, *c_side, *c_tail;
     kg_ddc *ddc; kg_wf *wf; kg_rxddc *rx; kg_fir *fir; kg_post *post; kg_adpcm *adpcm;
+    kg_nb *nb;                                  // m_NoiseProc_snd[] (the waterfall's blankers are kg_wf's)
+    // per receiver: the noise-blanker command state of snd_t and wf_inst_t (rx/rx_sound_cmd.cpp:454-501, :660-672)
+    struct nb_cmd {
+        int algo, snd_en[4], wf_en[4];
+        float snd_param[4][8], wf_param[4][8];
+        int wf_change[4], wf_setup;
+    };
+    std::vector<nb_cmd> nbc;
+    std::vector<int32_t> nb_list, nb_cnt;       // scratch: this step's blanked receivers and their record counts
     // device buffers
     short2 *d_wfiq; size_t wf_stride;           // [nrx][wf_stride] iq_t: a one-shot receiver uses pairs 0 .. 8191 of its row, an overlapped one all of it
     unsigned char *d_rows, *d_pkts;             // [frame][1024], [frame][BANK_PKT_STRIDE]
@@ -143,6 +153,16 @@ static int bank_pass(kg_rxbank *b, const void *d_adc, bool plan)
         if (nrec_max > 0 &&
             (rc = kg_dpump_unpack_rows_dev(b->c_side, b->d_raw, b->nrec_max, nrec_max, NR, b->enabled.data(), b->rescale, b->dc_i, b->dc_q,
                                            b->spectral_inversion, b->d_xin, b->nrec_max)))
+            return rc;
+        // the pre-filter blanker (rx_sound.cpp:593-598): in place on the unpacked rows, before CFastFIR
+        b->nb_list.clear(); b->nb_cnt.clear();
+        for (int i = 0; i < NA; i++) {
+            const kg_rxbank::nb_cmd &c = b->nbc[act[i]];
+            if (c.snd_en[KG_NB_BLANKER] && c.algo == KG_NB_STD) { b->nb_list.push_back(act[i]); b->nb_cnt.push_back(b->h_nrec[i]); }
+        }
+        if (!b->nb_list.empty() &&
+            (rc = kg_nb_process_dev(b->nb, b->nb_list.data(), (int) b->nb_list.size(), b->d_xin, b->nrec_max, b->nb_cnt.data(), b->d_xin,
+                                    b->nrec_max)))
             return rc;
         tk.lap(b, PF_UNPACK, pf);
         if (!plan && b->tail_pending) {                       // the coders of the step before have read fir_out
@@ -288,7 +308,112 @@ static int bank_pass(kg_rxbank *b, const void *d_adc, bool plan)
     return KG_OK;
 }
 
+// `SET zoom=` with a new zoom (rx_waterfall.cpp:460): the waterfall blanker is set up again before the next frame
+static void bank_nb_zoom_change(kg_rxbank *b, int rx)
+{
+    kg_rxbank::nb_cmd &c = b->nbc[rx];
+    if (c.wf_en[KG_NB_BLANKER] && c.wf_en[KG_NB_WF]) c.wf_change[KG_NB_BLANKER] = 1;
+}
+
+static int bank_nb_rx(kg_rxbank *b, int rx, const char *who)
+{
+    KG_REQUIRE(b != nullptr, KG_ERR_INVALID, "%s: null argument", who);
+    KG_REQUIRE(rx >= 0 && rx < b->nrx, KG_ERR_INVALID, "%s: receiver %d (0..%d)", who, rx, b->nrx - 1);
+    return KG_OK;
+}
+
+// SetupBlanker's refusals for a parameter vector at `rate`, without touching any blanker
+static int bank_nb_check(const float *prm, float rate, const char *who)
+{
+    kg_nbk::st t{};
+    const int r = kg_nbk::setup(t, true, rate, prm);
+    KG_REQUIRE(r == kg_nbk::SETUP_OK, KG_ERR_INVALID, "%s: gate %g us / threshold %g at %g Hz is refused (kg_nb_setup)", who,
+               (double) prm[KG_NB_GATE], (double) prm[KG_NB_THRESHOLD], (double) rate);
+    return KG_OK;
+}
+
 extern "C" {
+
+int kg_rxbank_set_nb_algo(kg_rxbank *b, int rx, int algo)
+{
+    int rc = bank_nb_rx(b, rx, "kg_rxbank_set_nb_algo");
+    if (rc) return rc;
+    KG_REQUIRE(algo == KG_NB_OFF || algo == KG_NB_STD, KG_ERR_INVALID, "kg_rxbank_set_nb_algo: algo %d (%s)", algo,
+               algo == KG_NB_WILD ? "NB_WILD is not implemented" : "not an nb_algo_e");
+    kg_rxbank::nb_cmd &c = b->nbc[rx];
+    c.algo = algo;                                                               // rx_sound_cmd.cpp:454-462
+    memset(c.snd_en, 0, sizeof c.snd_en);
+    memset(c.wf_en, 0, sizeof c.wf_en);
+    return KG_OK;
+}
+
+int kg_rxbank_set_nb_enable(kg_rxbank *b, int rx, int type, int en)
+{
+    int rc = bank_nb_rx(b, rx, "kg_rxbank_set_nb_enable");
+    if (rc) return rc;
+    KG_REQUIRE(type >= 0 && type < 4, KG_ERR_INVALID, "kg_rxbank_set_nb_enable: type %d (0..3)", type);
+    KG_REQUIRE(!(type == KG_NB_CLICK && en), KG_ERR_INVALID, "kg_rxbank_set_nb_enable: NB_CLICK test pulses are not implemented");
+    kg_rxbank::nb_cmd &c = b->nbc[rx];
+    KG_REQUIRE(!(type == KG_NB_BLANKER && en && c.algo == KG_NB_STD && !kg_nb_was_setup(b->nb, rx)), KG_ERR_STATE,
+               "kg_rxbank_set_nb_enable: receiver %d's audio blanker was never set up (send its parameters first)", rx);
+    c.snd_en[type] = en;                                                         // rx_sound_cmd.cpp:477-483
+    c.wf_en[type] = en;
+    return KG_OK;
+}
+
+int kg_rxbank_set_nb_param(kg_rxbank *b, int rx, int type, int param, float pval, float frate)
+{
+    int rc = bank_nb_rx(b, rx, "kg_rxbank_set_nb_param");
+    if (rc) return rc;
+    KG_REQUIRE(type >= 0 && type < 4 && param >= 0 && param < 8, KG_ERR_INVALID, "kg_rxbank_set_nb_param: type %d param %d", type, param);
+    kg_rxbank::nb_cmd &c = b->nbc[rx];
+    float snd[8], wfp[8];
+    memcpy(snd, c.snd_param[type], sizeof snd);
+    memcpy(wfp, c.wf_param[type], sizeof wfp);
+    snd[param] = pval;
+    wfp[param] = pval;
+    const bool to_wf = c.algo == KG_NB_STD || type == KG_NB_CLICK;               // rx_sound_cmd.cpp:491-494
+    const bool setup = type == KG_NB_BLANKER && c.algo == KG_NB_STD;              // :496-500
+    if (setup && (rc = bank_nb_check(snd, frate, "kg_rxbank_set_nb_param"))) return rc;
+    if (to_wf && type == KG_NB_BLANKER && (rc = bank_nb_check(wfp, (float) KG_WF_NFFT, "kg_rxbank_set_nb_param"))) return rc;
+    if (setup && (rc = kg_nb_setup(b->nb, rx, frate, snd))) return rc;           // SetupBlanker("SND", frate, ...)
+    c.snd_param[type][param] = pval;
+    if (to_wf) {
+        c.wf_param[type][param] = pval;
+        c.wf_change[type] = 1;
+    }
+    return KG_OK;
+}
+
+int kg_rxbank_set_nb_gate(kg_rxbank *b, int rx, int nb, int th, float frate)
+{
+    int rc = bank_nb_rx(b, rx, "kg_rxbank_set_nb_gate");
+    if (rc) return rc;
+    kg_rxbank::nb_cmd &c = b->nbc[rx];
+    float snd[8];
+    memcpy(snd, c.snd_param[KG_NB_BLANKER], sizeof snd);
+    snd[KG_NB_GATE] = nb;                                                        // rx_sound_cmd.cpp:660-672
+    snd[KG_NB_THRESHOLD] = th;
+    if (nb && (rc = bank_nb_check(snd, frate, "kg_rxbank_set_nb_gate"))) return rc;
+    if (nb && (rc = kg_nb_setup(b->nb, rx, frate, snd))) return rc;
+    memcpy(c.snd_param[KG_NB_BLANKER], snd, sizeof snd);
+    c.snd_en[KG_NB_BLANKER] = nb ? 1 : 0;
+    return KG_OK;
+}
+
+int kg_rxbank_nb_cmd_state(kg_rxbank *b, int rx, int32_t *ints, float *flts)
+{
+    int rc = bank_nb_rx(b, rx, "kg_rxbank_nb_cmd_state");
+    if (rc) return rc;
+    const kg_rxbank::nb_cmd &c = b->nbc[rx];
+    if (ints) {
+        ints[0] = c.algo;
+        for (int t = 0; t < 4; t++) { ints[1 + t] = c.snd_en[t]; ints[5 + t] = c.wf_en[t]; ints[9 + t] = c.wf_change[t]; }
+        ints[13] = c.wf_setup;
+    }
+    if (flts) { memcpy(flts, c.snd_param, sizeof c.snd_param); memcpy(flts + 32, c.wf_param, sizeof c.wf_param); }
+    return KG_OK;
+}
 
 void kg_rxbank_destroy(kg_rxbank *b)
 {
@@ -296,7 +421,7 @@ void kg_rxbank_destroy(kg_rxbank *b)
     (void) hipSetDevice(b->device);
     for (hipStream_t s : {b->s_main, b->s_side, b->s_tail, b->s_ddc2, b->s_up}) if (s) (void) hipStreamSynchronize(s);
     if (b->c_main && b->c_side && b->c_tail) bank_set_arena(b, KG_ARENA_OFF);
-    kg_adpcm_destroy(b->adpcm); kg_post_destroy(b->post); kg_fir_destroy(b->fir); kg_rxddc_destroy(b->rx);
+    kg_adpcm_destroy(b->adpcm); kg_post_destroy(b->post); kg_fir_destroy(b->fir); kg_rxddc_destroy(b->rx); kg_nb_destroy(b->nb);
     kg_wf_destroy(b->wf); kg_ddc_destroy(b->ddc);
     kg_ctx_destroy(b->c_tail); kg_ctx_destroy(b->c_side); kg_ctx_destroy(b->c_main);
     (void) hipFree(b->d_wfiq); (void) hipFree(b->d_rows); (void) hipFree(b->d_pkts); (void) hipFree(b->d_raw);
@@ -384,6 +509,7 @@ int kg_rxbank_create(int device, int nrx, size_t adc_samples_per_step, int rx_mo
     b->decim_rx = kg_rxddc_decim(b->rx);
     b->nrec_max = b->n / (size_t) b->decim_rx + 2;
     BANK_TRY(kg_fir_create(b->c_side, nrx, (int) b->nrec_max, &b->fir));
+    BANK_TRY(kg_nb_create(b->c_side, nrx, (int) b->nrec_max, &b->nb));
     BANK_TRY(kg_post_create(b->c_tail, nrx, &b->post));
     BANK_TRY(kg_adpcm_create(b->c_tail, nrx, &b->adpcm));
     b->wf_stride = BANK_RING_PAIRS;
@@ -409,14 +535,14 @@ int kg_rxbank_create(int device, int nrx, size_t adc_samples_per_step, int rx_mo
     {   // what a step's tables can take: <= 12 of them + a channel list for S-meter / AGC / detector and one for the coder per sound
         // block (a receiver can complete nrec_max / 512 + 1 blocks in a step) -- checked HERE, not found out by every later step
         const size_t blocks_max = b->nrec_max / KG_FIR_OUT + 1;
-        if (12 + 4 * blocks_max > KG_ARENA_MAX_ENTRIES) {
+        if (16 + 4 * blocks_max > KG_ARENA_MAX_ENTRIES) {
             kg_set_error("kg_rxbank_create: %zu ADC samples per step are up to %zu sound blocks per receiver and step; the step table holds %d "
-                         "(a step of at most %zu samples)", b->n, blocks_max, (KG_ARENA_MAX_ENTRIES - 12) / 4,
-                         (size_t) ((KG_ARENA_MAX_ENTRIES - 12) / 4 - 1) * KG_FIR_OUT * (size_t) b->decim_rx);
+                         "(a step of at most %zu samples)", b->n, blocks_max, (KG_ARENA_MAX_ENTRIES - 16) / 4,
+                         (size_t) ((KG_ARENA_MAX_ENTRIES - 16) / 4 - 1) * KG_FIR_OUT * (size_t) b->decim_rx);
             kg_rxbank_destroy(b);
             return KG_ERR_INVALID;
         }
-        b->slot_bytes = (8192 + (size_t) (384 + 12 * blocks_max) * nrx + 63) & ~(size_t) 63;
+        b->slot_bytes = (8192 + (size_t) (448 + 12 * blocks_max) * nrx + 63) & ~(size_t) 63;     // (+ 64 per receiver: the blankers' tables)
     }
     BANK_HIP(hipHostMalloc((void **) &b->h_slots, b->slot_bytes * BANK_SLOTS, hipHostMallocDefault));
     BANK_HIP(hipMalloc((void **) &b->d_slots, b->slot_bytes * BANK_SLOTS));
@@ -440,6 +566,7 @@ int kg_rxbank_create(int device, int nrx, size_t adc_samples_per_step, int rx_mo
     b->h_nrec.assign(nrx, 0); b->h_nfir.assign(nrx, 0); b->chan_of.assign(nrx, 0); b->pkt_bytes.assign(nrx, 0); b->rx_of_frame.assign(nrx, -1);
     b->out_off.assign(nrx, 0); b->max_out.assign(nrx, 0); b->h_nw.assign(nrx, 0); b->frame_off.assign(nrx, 0);
     b->enabled.assign(nrx, 1); b->pkt_step.resize(nrx);
+    b->nbc.assign(nrx, kg_rxbank::nb_cmd{});
     memset(&b->arena, 0, sizeof b->arena);
     memset(&b->last, 0, sizeof b->last);
     BANK_HIP(hipDeviceSynchronize());
@@ -456,6 +583,7 @@ kg_fir *kg_rxbank_fir(kg_rxbank *b) { return b ? b->fir : nullptr; }
 kg_post *kg_rxbank_post(kg_rxbank *b) { return b ? b->post : nullptr; }
 kg_adpcm *kg_rxbank_adpcm(kg_rxbank *b) { return b ? b->adpcm : nullptr; }
 kg_ctx *kg_rxbank_ctx(kg_rxbank *b) { return b ? b->c_main : nullptr; }
+kg_nb *kg_rxbank_nb(kg_rxbank *b) { return b ? b->nb : nullptr; }
 
 int kg_rxbank_set_wf(kg_rxbank *b, int rx, uint64_t phase_inc, int decim, int overlapped)
 {
@@ -476,6 +604,7 @@ int kg_rxbank_set_wf(kg_rxbank *b, int rx, uint64_t phase_inc, int decim, int ov
     for (hipStream_t s : {b->s_main, b->s_side, b->s_tail}) KG_HIP(hipStreamSynchronize(s));
     int rc = kg_ddc_set_wf(b->ddc, rx, phase_inc, decim);
     if (rc) return rc;
+    if (b->wf_set[rx] && decim != b->decim[rx]) bank_nb_zoom_change(b, rx);
     b->decim[rx] = decim; b->overlapped[rx] = overlapped ? 1 : 0; b->wf_set[rx] = 1;
     b->ring_w[rx] = 0; b->ring_total[rx] = 0;             // CmdWFReset: the sampler starts empty ("fill pipe")
     return KG_OK;
@@ -507,6 +636,8 @@ int kg_rxbank_join(kg_rxbank *b, int rx)
     for (hipStream_t s : {b->s_side, b->s_tail}) KG_HIP(hipStreamSynchronize(s));
     b->snd_seq[rx] = 0; b->last_nrec[rx] = 0; b->last_nfir[rx] = 0;
     b->wf_set[rx] = 0; b->ring_w[rx] = 0; b->ring_total[rx] = 0;
+    b->nbc[rx] = kg_rxbank::nb_cmd{};                      // memset(snd_t) / memset(wf_inst_t): algo NB_OFF, enables and params 0;
+    if ((rc = kg_wf_set_nb(b->wf, rx, 0))) return rc;     // the blankers' states stay (the reference's CNoiseProc arrays are globals)
     b->active[rx] = 1;
     return KG_OK;
 }
@@ -549,6 +680,7 @@ int kg_rxbank_set_unpack(kg_rxbank *b, float rescale, float dc_i, float dc_q, in
 int kg_rxbank_set_wf_pkt(kg_rxbank *b, int rx, uint32_t x_bin_server, uint32_t zoom, int use_compression)
 {
     KG_REQUIRE(b && rx >= 0 && rx < b->nrx, KG_ERR_INVALID, "kg_rxbank_set_wf_pkt: receiver %d", rx);
+    if (zoom != b->pkt[rx].zoom) bank_nb_zoom_change(b, rx);
     b->pkt[rx].x_bin_server = x_bin_server; b->pkt[rx].zoom = zoom; b->pkt[rx].use_compression = use_compression ? 1 : 0;
     return KG_OK;
 }
@@ -565,6 +697,20 @@ int kg_rxbank_step(kg_rxbank *b, const void *d_adc, void *adc_ready_event, kg_rx
     a.h_base = b->h_slots + (size_t) slot * b->slot_bytes; a.d_base = b->d_slots + (size_t) slot * b->slot_bytes;
     a.cap = b->slot_bytes; a.used = 0; a.nent = 0; a.cursor = 0;
     tk.lap(b, PF_UPLOAD, true);
+    {   // rx_waterfall.cpp:1087-1096: a pending parameter change is set up before the receiver's next frame, once both enables are on
+        int rc0;
+        for (int k = 0; k < b->nrx; k++) {
+            if (!b->active[k]) continue;
+            kg_rxbank::nb_cmd &c = b->nbc[k];
+            const bool both = c.wf_en[KG_NB_BLANKER] && c.wf_en[KG_NB_WF];
+            if (both && c.wf_change[KG_NB_BLANKER]) {
+                if ((rc0 = kg_wf_nb_setup(b->wf, k, c.wf_param[KG_NB_BLANKER]))) return rc0;
+                c.wf_change[KG_NB_BLANKER] = 0;
+                c.wf_setup = 1;
+            }
+            if ((rc0 = kg_wf_set_nb(b->wf, k, both && c.wf_setup))) return rc0;
+        }
+    }
     bank_set_arena(b, KG_ARENA_PLAN);
     int rc = bank_pass(b, d_adc, true);
     tk.lap(b, PF_PLAN, true);

@@ -57,7 +57,9 @@ struct wf_chan_dev {
 #define WF_CLAIM_STRIDE 32      // ints between the frame-claim counters (a 128-byte line each): eight groups + the exit count
 #define WF_LDS_BYTES (2 * SUB * sizeof(float2) + 240 * sizeof(float2) + 16)       // + pass-1 twiddles + the claimed frame index
 
-template <bool TAPS>
+// NB: the instance for calls with blanked frames (kg_wf_set_nb): frame f with nbslot[f] >= 0 takes the blanker pre-pass's windowed,
+// blanked frame nbf[nbslot[f]] (8192 complex floats) instead of int16 x window; every other frame is read as in the plain instance.
+template <bool TAPS, bool NB>
 __global__ __launch_bounds__(256, 2) void wf_frame_kernel(
     const short2 *__restrict__ iq,            // iq_t {i, q}: frame f = 8192 of them from iq + 2 * frames[f].y
     const int2 *__restrict__ frames,          // [nframes] {channel, offset of the frame's first sample in units of two iq_t}
@@ -68,7 +70,8 @@ __global__ __launch_bounds__(256, 2) void wf_frame_kernel(
     int nframes,
     unsigned char *__restrict__ out,          // [nframes][1024]
     int *__restrict__ claim,                  // [9][WF_CLAIM_STRIDE]: per group, frames handed out beyond the first two per workgroup; [8]: workgroups done
-    float *__restrict__ tap_pwr, float *__restrict__ tap_pwr_out, float *__restrict__ tap_db)
+    float *__restrict__ tap_pwr, float *__restrict__ tap_pwr_out, float *__restrict__ tap_db,
+    const float2 *__restrict__ nbf, const int *__restrict__ nbslot)
 {
     extern __shared__ __attribute__((aligned(16))) float2 smem[];
     float2 *tileA = smem, *tileB = smem + SUB;
@@ -116,7 +119,16 @@ __global__ __launch_bounds__(256, 2) void wf_frame_kernel(
 #pragma unroll
         for (int j = 0; j < 16; j++) { const u2 v = ld8(rs, j); wv[j] = float2{__uint_as_float(v[0]), __uint_as_float(v[1])}; }
     };
+    int slot = -1;                            // NB: the current frame's row of nbf, or -1
     auto windowed = [&](cf (&x)[16], int g) {
+        if constexpr (NB) {
+            if (slot >= 0) {                  // (wave-uniform) the pre-pass already windowed and blanked this frame
+                const float2 *src = nbf + (size_t) slot * WF_NFFT;
+#pragma unroll
+                for (int j = 0; j < 16; j++) { const float2 v = src[2 * (t + 256 * j) + g]; x[j] = cf{v.x, v.y}; }
+                return;
+            }
+        }
         // sample_wf(): fi = (float)(s2_t)i * window[sn]  (:1054-1061)
 #pragma unroll
         for (int j = 0; j < 16; j++) {
@@ -174,6 +186,7 @@ __global__ __launch_bounds__(256, 2) void wf_frame_kernel(
         int claimed = 0;
         if (t == 0) claimed = __hip_atomic_fetch_add(&claim[cg * WF_CLAIM_STRIDE], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 
+        if constexpr (NB) slot = nbslot[f];
         cf x[16], y0[16], y1[16];
         windowed(x, 0);
         kg_subfft4096_l<-1>(x, y0, tileA, tileB, tw1, p2, t);
@@ -365,6 +378,17 @@ struct kg_wf {
     std::vector<char> chan_set;
     bool tables_set;
     int grid;
+    // the noise blankers (m_NoiseProc_wf[]): states, on / off, each channel's window function (the pre-pass windows), the
+    // pre-pass's output rows and the NB instance's frame -> row table
+    kg_nb_store *nb;
+    std::vector<char> nb_on;
+    std::vector<int> win_of;
+    float2 *d_nbf; int nbf_cap;
+    std::vector<int> nb_slot, nb_chan_first;
+    struct pre_chan { int ch, first, count, wfn; };
+    struct pre_frame { unsigned off; int slot; };
+    std::vector<pre_chan> pre_c;
+    std::vector<pre_frame> pre_f;
 };
 
 extern "C" {
@@ -382,17 +406,24 @@ int kg_wf_create(kg_ctx *ctx, int nchan, kg_wf **out)
     w->chan_set.assign(nchan, 0);
     w->d_iq = nullptr; w->d_out = nullptr; w->stage_cap = 0;
     w->d_tap_pwr = w->d_tap_pwr_out = w->d_tap_db = nullptr;
+    w->nb = nullptr; w->d_nbf = nullptr; w->nbf_cap = 0;
+    w->nb_on.assign(nchan, 0); w->win_of.assign(nchan, 0);
+    if ((rc = kg_nb_store_create(nchan, &w->nb)) != KG_OK) return rc;
     KG_HIP(hipMalloc((void **) &w->d_chans, sizeof(wf_chan_dev) * nchan));
     KG_HIP(hipMalloc((void **) &w->d_windows, sizeof(float) * 4 * WF_NFFT));
     KG_HIP(hipMalloc((void **) &w->d_cic, sizeof(float) * WF_NFFT));
     KG_HIP(hipMalloc((void **) &w->d_claim, sizeof(int) * 9 * WF_CLAIM_STRIDE));
     KG_HIP(hipMemset(w->d_claim, 0, sizeof(int) * 9 * WF_CLAIM_STRIDE));
-    KG_HIP(hipFuncSetAttribute((const void *) wf_frame_kernel<false>,
+    KG_HIP(hipFuncSetAttribute((const void *) wf_frame_kernel<false, false>,
                                hipFuncAttributeMaxDynamicSharedMemorySize, WF_LDS_BYTES));
-    KG_HIP(hipFuncSetAttribute((const void *) wf_frame_kernel<true>,
+    KG_HIP(hipFuncSetAttribute((const void *) wf_frame_kernel<true, false>,
+                               hipFuncAttributeMaxDynamicSharedMemorySize, WF_LDS_BYTES));
+    KG_HIP(hipFuncSetAttribute((const void *) wf_frame_kernel<false, true>,
+                               hipFuncAttributeMaxDynamicSharedMemorySize, WF_LDS_BYTES));
+    KG_HIP(hipFuncSetAttribute((const void *) wf_frame_kernel<true, true>,
                                hipFuncAttributeMaxDynamicSharedMemorySize, WF_LDS_BYTES));
     int occ = 0;
-    KG_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, wf_frame_kernel<false>, 256, WF_LDS_BYTES));
+    KG_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, wf_frame_kernel<false, false>, 256, WF_LDS_BYTES));
     if (occ < 1) occ = 1;
     if (const char *e = kg_tuning_env("KIWIGPU_WF_WGS_PER_CU")) {      // experiment: fewer workgroups per CU
         const int v = atoi(e);
@@ -411,6 +442,8 @@ void kg_wf_destroy(kg_wf *w)
     (void) hipFree(w->d_chans); (void) hipFree(w->d_windows); (void) hipFree(w->d_cic); (void) hipFree(w->d_claim);
     (void) hipFree(w->d_iq); (void) hipFree(w->d_out);
     (void) hipFree(w->d_tap_pwr); (void) hipFree(w->d_tap_pwr_out); (void) hipFree(w->d_tap_db);
+    (void) hipFree(w->d_nbf);
+    kg_nb_store_destroy(w->nb);
     for (int k = 0; k < WF_TABLE_WAYS; k++) kg_stage_cache_free(&w->chan_of_cache[k]);
     delete w;
 }
@@ -504,7 +537,61 @@ int kg_wf_set_channel(kg_wf *w, int ch, const kg_wf_chan_cfg *cfg, const uint16_
     KG_HIP(hipStreamSynchronize(st));         // frames in flight may read the old record
     KG_HIP(hipMemcpy(w->d_chans + ch, &h, sizeof h, hipMemcpyHostToDevice));
     w->chan_set[ch] = 1;
+    w->win_of[ch] = cfg->window_func;
     return KG_OK;
+}
+
+// The blanker pre-pass (kg_nb.hip) over the frames of channels whose blanker is on (all = every frame: the standalone call site):
+// one workgroup per such channel, its frames in list order.  Frame f goes to row w->nb_slot[f] of d_rows (-1: not blanked; rows
+// numbered in list order, or f itself when `all`); d_rows null: w->d_nbf, grown as needed.  Tables staged; *nblank = 0: nothing
+// to do, nothing staged.
+static int wf_prepass(kg_wf *w, int nframes, const int32_t *chan_of, const uint64_t *frame_off, bool all, const void *d_iq,
+                      float2 *d_rows, int *nblank)
+{
+    w->nb_slot.assign(nframes, -1);
+    w->nb_chan_first.assign(w->nchan, -1);
+    w->pre_c.clear();
+    int nb = 0;
+    for (int f = 0; f < nframes; f++) {
+        const int c = chan_of[f];
+        if (!all && !w->nb_on[c]) continue;
+        if (w->nb_chan_first[c] < 0) {
+            w->nb_chan_first[c] = (int) w->pre_c.size();
+            w->pre_c.push_back(kg_wf::pre_chan{c, 0, 0, w->win_of[c]});
+        }
+        w->pre_c[w->nb_chan_first[c]].count++;
+        nb++;
+    }
+    *nblank = nb;
+    if (nb == 0) return KG_OK;
+    int first = 0;
+    for (auto &pc : w->pre_c) { pc.first = first; first += pc.count; pc.count = 0; }
+    w->pre_f.resize(nb);
+    int row = 0;
+    for (int f = 0; f < nframes; f++) {
+        const int c = chan_of[f];
+        if (!all && !w->nb_on[c]) continue;
+        kg_wf::pre_chan &pc = w->pre_c[w->nb_chan_first[c]];
+        w->nb_slot[f] = all ? f : row++;
+        const uint64_t off = frame_off ? frame_off[f] : (uint64_t) f * WF_NFFT;
+        w->pre_f[pc.first + pc.count++] = kg_wf::pre_frame{(unsigned) off, w->nb_slot[f]};
+    }
+    if (!d_rows) {
+        if (nb > w->nbf_cap) {
+            KG_HIP(hipStreamSynchronize(w->ctx->stream));       // frames in flight may still read the old rows
+            (void) hipFree(w->d_nbf);
+            w->d_nbf = nullptr; w->nbf_cap = 0;
+            KG_HIP(hipMalloc((void **) &w->d_nbf, sizeof(float2) * WF_NFFT * (size_t) nb));
+            w->nbf_cap = nb;
+        }
+        d_rows = w->d_nbf;
+    }
+    void *d_c = nullptr, *d_f = nullptr;
+    int rc = kg_ctx_stage(w->ctx, w->pre_c.data(), sizeof(kg_wf::pre_chan) * w->pre_c.size(), &d_c);
+    if (rc) return rc;
+    if ((rc = kg_ctx_stage(w->ctx, w->pre_f.data(), sizeof(kg_wf::pre_frame) * w->pre_f.size(), &d_f))) return rc;
+    if (w->ctx->arena && w->ctx->arena->mode == KG_ARENA_PLAN) return KG_OK;
+    return kg_nb_wf_launch(w->ctx, w->nb, (int) w->pre_c.size(), d_c, d_f, d_iq, w->d_windows, d_rows);
 }
 
 static int wf_launch(kg_wf *w, int nframes, const int32_t *chan_of, const uint64_t *frame_off, uint64_t iq_len,
@@ -537,21 +624,30 @@ static int wf_launch(kg_wf *w, int nframes, const int32_t *chan_of, const uint64
                                           sizeof(int2) * nframes, &d_chan_of);
         if (rc) return rc;
     }
+    // frames of channels with the blanker on: the pre-pass, then the NB instance over the whole list
+    int nblank = 0;
+    void *d_slot = nullptr;
+    {
+        int rc = wf_prepass(w, nframes, chan_of, frame_off, false, d_iq, nullptr, &nblank);
+        if (rc) return rc;
+        if (nblank && (rc = kg_ctx_stage(w->ctx, w->nb_slot.data(), sizeof(int) * nframes, &d_slot))) return rc;
+    }
     KG_PLAN_ONLY(w->ctx);
     const int grid = nframes < w->grid ? nframes : w->grid;
+#define WF_LAUNCH(TAPS_, NB_, TP_, TPO_, TDB_)                                                                                         \
+    hipLaunchKernelGGL((wf_frame_kernel<TAPS_, NB_>), dim3(grid), dim3(256), WF_LDS_BYTES, st,                                        \
+                       (const short2 *) d_iq, (const int2 *) d_chan_of, (const wf_chan_dev *) w->d_chans,                             \
+                       (const float *) w->d_windows, (const float *) w->d_cic,                                                        \
+                       (const float2 *) w->ctx->d_tab4096, (const float2 *) w->ctx->d_tab8192, nframes,                               \
+                       (unsigned char *) d_out, w->d_claim, TP_, TPO_, TDB_, (const float2 *) w->d_nbf, (const int *) d_slot)
     if (!taps) {
-        hipLaunchKernelGGL(wf_frame_kernel<false>, dim3(grid), dim3(256), WF_LDS_BYTES, st,
-                           (const short2 *) d_iq, (const int2 *) d_chan_of, (const wf_chan_dev *) w->d_chans,
-                           (const float *) w->d_windows, (const float *) w->d_cic,
-                           (const float2 *) w->ctx->d_tab4096, (const float2 *) w->ctx->d_tab8192, nframes,
-                           (unsigned char *) d_out, w->d_claim, (float *) nullptr, (float *) nullptr, (float *) nullptr);
+        if (!nblank) WF_LAUNCH(false, false, (float *) nullptr, (float *) nullptr, (float *) nullptr);
+        else WF_LAUNCH(false, true, (float *) nullptr, (float *) nullptr, (float *) nullptr);
     } else {
-        hipLaunchKernelGGL(wf_frame_kernel<true>, dim3(grid), dim3(256), WF_LDS_BYTES, st,
-                           (const short2 *) d_iq, (const int2 *) d_chan_of, (const wf_chan_dev *) w->d_chans,
-                           (const float *) w->d_windows, (const float *) w->d_cic,
-                           (const float2 *) w->ctx->d_tab4096, (const float2 *) w->ctx->d_tab8192, nframes,
-                           (unsigned char *) d_out, w->d_claim, w->d_tap_pwr, w->d_tap_pwr_out, w->d_tap_db);
+        if (!nblank) WF_LAUNCH(true, false, w->d_tap_pwr, w->d_tap_pwr_out, w->d_tap_db);
+        else WF_LAUNCH(true, true, w->d_tap_pwr, w->d_tap_pwr_out, w->d_tap_db);
     }
+#undef WF_LAUNCH
     KG_HIP(hipGetLastError());
     return KG_OK;
 }
@@ -628,6 +724,55 @@ int kg_wf_debug_frame(kg_wf *w, int ch, const int16_t *iq, uint8_t *out, float *
     KG_HIP(hipMemcpyAsync(dB, w->d_tap_db, sizeof(float) * WF_WIDTH, hipMemcpyDeviceToHost, st));
     KG_HIP(hipStreamSynchronize(st));
     return KG_OK;
+}
+
+int kg_wf_nb_setup(kg_wf *w, int ch, const float *nb_param)
+{
+    KG_REQUIRE(w != nullptr, KG_ERR_INVALID, "kg_wf_nb_setup: null argument");
+    int rc = kg_ctx_use(w->ctx);
+    if (rc) return rc;
+    return kg_nb_store_setup(w->ctx, w->nb, ch, (float) WF_NFFT, nb_param, "kg_wf_nb_setup");     // u4_t srate = WF_C_NSAMPS (:1090)
+}
+
+int kg_wf_set_nb(kg_wf *w, int ch, int on)
+{
+    KG_REQUIRE(w != nullptr, KG_ERR_INVALID, "kg_wf_set_nb: null argument");
+    KG_REQUIRE(ch >= 0 && ch < w->nchan, KG_ERR_INVALID, "kg_wf_set_nb: channel %d (0..%d)", ch, w->nchan - 1);
+    KG_REQUIRE(!on || kg_nb_store_was_setup(w->nb, ch), KG_ERR_STATE, "kg_wf_set_nb: channel %d's blanker was never set up "
+               "(kg_wf_nb_setup)", ch);
+    w->nb_on[ch] = on ? 1 : 0;
+    return KG_OK;
+}
+
+int kg_wf_nb_frames_dev(kg_wf *w, int nframes, const int32_t *chan_of, const uint64_t *frame_off, uint64_t iq_len,
+                        const void *d_iq, void *d_out)
+{
+    KG_REQUIRE(w && chan_of && frame_off && d_iq && d_out, KG_ERR_INVALID, "kg_wf_nb_frames_dev: null argument");
+    int rc = kg_ctx_use(w->ctx);
+    if (rc) return rc;
+    KG_REQUIRE(((uintptr_t) d_iq & 7) == 0 && ((uintptr_t) d_out & 7) == 0, KG_ERR_INVALID,
+               "kg_wf_nb_frames_dev: d_iq and d_out must be 8-byte aligned");
+    KG_REQUIRE(w->tables_set, KG_ERR_STATE, "kg_wf_nb_frames_dev: kg_wf_set_tables was not called");
+    KG_REQUIRE(nframes >= 1, KG_ERR_INVALID, "kg_wf_nb_frames_dev: nframes %d", nframes);
+    for (int f = 0; f < nframes; f++) {
+        const int c = chan_of[f];
+        KG_REQUIRE(c >= 0 && c < w->nchan, KG_ERR_INVALID, "kg_wf_nb_frames_dev: chan_of[%d] = %d out of range", f, c);
+        KG_REQUIRE(w->chan_set[c], KG_ERR_STATE, "kg_wf_nb_frames_dev: channel %d is not configured (its window)", c);
+        KG_REQUIRE(kg_nb_store_was_setup(w->nb, c), KG_ERR_STATE, "kg_wf_nb_frames_dev: channel %d's blanker was never set up", c);
+        KG_REQUIRE(frame_off[f] < ((uint64_t) 1 << 32) && frame_off[f] + WF_NFFT <= iq_len, KG_ERR_INVALID,
+                   "kg_wf_nb_frames_dev: frame %d at %llu + 8192 runs past iq_len %llu", f, (unsigned long long) frame_off[f],
+                   (unsigned long long) iq_len);
+    }
+    int nblank = 0;
+    return wf_prepass(w, nframes, chan_of, frame_off, true, d_iq, (float2 *) d_out, &nblank);
+}
+
+int kg_wf_nb_state(kg_wf *w, const int32_t *chans, int nch, int32_t *ints, float *flts)
+{
+    KG_REQUIRE(w != nullptr, KG_ERR_INVALID, "kg_wf_nb_state: null argument");
+    int rc = kg_ctx_use(w->ctx);
+    if (rc) return rc;
+    return kg_nb_store_state(w->ctx, w->nb, chans, nch, ints, flts, "kg_wf_nb_state");
 }
 
 }  // extern "C"

@@ -11,10 +11,12 @@ import ctypes as C
 
 import numpy as np
 
+from . import nb as nb_mod
 from . import post as post_mod
 from . import wf as wf_mod
 from ._lib import Context, borrow, check, load_library, ptr
 from .ddc import RX_DECIM, RX_STD, Ddc, RxDdc, rx_phase_inc
+from .nb import NoiseBlanker
 from .post import Post
 from .snd import RESCALE, FastFir
 from .wf import Waterfall, WfParams
@@ -88,6 +90,7 @@ class RxBank:
         self.fir = borrow(FastFir, self.ctx, self.lib.kg_rxbank_fir(h), nchan=nrx)
         self.post = borrow(Post, self.ctx, self.lib.kg_rxbank_post(h), nchan=nrx)
         self.adpcm = borrow(Adpcm, self.ctx, self.lib.kg_rxbank_adpcm(h), nchan=nrx)
+        self.nb = borrow(NoiseBlanker, self.ctx, self.lib.kg_rxbank_nb(h), nchan=nrx)
         b = BufsC()
         check(self.lib.kg_rxbank_buffers(h, C.byref(b)), "kg_rxbank_buffers")
         self.bufs = b
@@ -103,7 +106,7 @@ class RxBank:
         if getattr(self, "h", None):
             self.lib.kg_rxbank_destroy(self.h)
             self.h = None
-            for o in (self.ddc, self.wf, self.rxddc, self.fir, self.post, self.adpcm, self.ctx):
+            for o in (self.ddc, self.wf, self.rxddc, self.fir, self.post, self.adpcm, self.nb, self.ctx):
                 o.h = None
 
     def __del__(self):
@@ -182,6 +185,31 @@ class RxBank:
         for t in (post_mod.NR_DENOISE, post_mod.NR_AUTONOTCH):
             if enable[t]:
                 self.post.set_nr_enable(rx, t, enable[t])
+
+    def set_nb(self, rx, algo, params=None, enable=(0, 0), frate=None):
+        """The noise-blanker commands for receiver rx as a client sends them (rx/rx_sound_cmd.cpp:454-501): `SET nb algo=`, then the
+        blanker's parameters one at a time (params: [gate_usec, threshold]), then the enables (NB_BLANKER, NB_WF).  frate: the
+        connection's audio rate (default: the bank's nominal one)."""
+        frate = self.fs if frate is None else frate
+        check(self.lib.kg_rxbank_set_nb_algo(self.h, int(rx), int(algo)), "kg_rxbank_set_nb_algo")
+        for k, v in enumerate(params or []):
+            check(self.lib.kg_rxbank_set_nb_param(self.h, int(rx), nb_mod.NB_BLANKER, k, float(np.float32(v)), float(np.float32(frate))),
+                  "kg_rxbank_set_nb_param")
+        for t in (nb_mod.NB_BLANKER, nb_mod.NB_WF):
+            if enable[t]:
+                check(self.lib.kg_rxbank_set_nb_enable(self.h, int(rx), t, int(enable[t])), "kg_rxbank_set_nb_enable")
+
+    def set_nb_gate(self, rx, nb, th, frate=None):
+        """kiwiclient's legacy `SET nb=<gate> th=<threshold>` (rx/rx_sound_cmd.cpp:660-672)."""
+        frate = self.fs if frate is None else frate
+        check(self.lib.kg_rxbank_set_nb_gate(self.h, int(rx), int(nb), int(th), float(np.float32(frate))), "kg_rxbank_set_nb_gate")
+
+    def nb_cmd_state(self, rx):
+        """-> (ints[14]: algo, snd enable[4], wf enable[4], wf nb_param_change[4], wf nb_setup; floats [2, 4, 8]: snd / wf nb_param)"""
+        ints = np.zeros(14, np.int32)
+        flts = np.zeros((2, 4, 8), np.float32)
+        check(self.lib.kg_rxbank_nb_cmd_state(self.h, int(rx), ptr(ints), ptr(flts)), "kg_rxbank_nb_cmd_state")
+        return ints, flts
 
     def set_little_endian(self, rx, little_endian):
         check(self.lib.kg_rxbank_set_little_endian(self.h, int(rx), int(bool(little_endian))), "kg_rxbank_set_little_endian")

@@ -207,3 +207,33 @@ class Waterfall:
         check(self.lib.kg_wf_debug_frame(self.h, int(ch), ptr(iq), ptr(out), ptr(pwr), ptr(pwr_out),
                                          ptr(dB)), "kg_wf_debug_frame")
         return out, pwr, pwr_out, dB
+
+    # ---- the noise blanker (m_NoiseProc_wf[], rx/rx_waterfall.cpp:1087-1099)
+    def nb_setup(self, ch, params):
+        """SetupBlanker("WF", 8192, params): params = [gate_usec, threshold, ...] (up to 8 values)."""
+        p = np.zeros(8, _f32)
+        p[:len(params)] = params
+        check(self.lib.kg_wf_nb_setup(self.h, int(ch), ptr(p)), "kg_wf_nb_setup")
+
+    def set_nb(self, ch, on):
+        """The blanker of channel ch on or off for every later frame of that channel."""
+        check(self.lib.kg_wf_set_nb(self.h, int(ch), int(bool(on))), "kg_wf_set_nb")
+
+    def nb_frames(self, chan_of, d_iq, d_out, frame_off, iq_len):
+        """The standalone call site: window + ProcessBlankerOneShot for each listed frame (frame_off / iq_len in iq_t pairs, as
+        frames_dev); frame f written to d_out + f * 64 KiB as 8192 complex floats.  Enqueue only."""
+        chan_of = np.ascontiguousarray(chan_of, np.int32)
+        frame_off = np.ascontiguousarray(frame_off, np.uint64)
+        if frame_off.size != chan_of.size:
+            raise ValueError("frame_off and chan_of differ in length")
+        check(self.lib.kg_wf_nb_frames_dev(self.h, chan_of.size, ptr(chan_of), ptr(frame_off), int(iq_len), ptr(int(d_iq)),
+                                           ptr(int(d_out))), "kg_wf_nb_frames_dev")
+
+    def nb_state(self, chans):
+        """-> (ints [n, 6]: m_Mptr, m_Dptr, m_BlankCounter, m_MagSamples, m_DelaySamples, m_GateSamples; floats [n, 2]: m_Ratio,
+        m_MagAveSum)"""
+        chans = np.ascontiguousarray(np.atleast_1d(chans), np.int32)
+        ints = np.empty((chans.size, 6), np.int32)
+        flts = np.empty((chans.size, 2), np.float32)
+        check(self.lib.kg_wf_nb_state(self.h, ptr(chans), chans.size, ptr(ints), ptr(flts)), "kg_wf_nb_state")
+        return ints, flts

@@ -247,6 +247,23 @@ int kg_wf_frames_at_dev(kg_wf *wf, int nframes, const int32_t *chan_of, const ui
 int kg_wf_debug_frame(kg_wf *wf, int ch, const int16_t *iq, uint8_t *out, float *pwr,
                       float *pwr_out, float *dB);
 
+/* The waterfall's noise blanker (rx/rx_waterfall.cpp:1087-1099, rx/CuteSDR/noiseproc.cpp): one CNoiseProc per channel, the
+ * m_NoiseProc_wf[] array.  kg_wf_nb_setup is SetupBlanker("WF", 8192, nb_param) -- the sample rate is WF_C_NSAMPS, not the
+ * channel's -- with kg_nb_setup's refusals; it resets the blanker in stream order.  kg_wf_set_nb switches the blanker of a
+ * channel on or off (on: refused with KG_ERR_STATE for a channel that was never set up).  While it is on, every frame of that
+ * channel in kg_wf_frames_dev / kg_wf_frames_at_dev / kg_wf_frames / kg_wf_debug_frame (which applies it as a one-frame call does)
+ * is windowed and then run through ProcessBlankerOneShot(8192) -- its state carried from frame to frame in list order, the delay of
+ * D + 1 with D samples skipped (the frame moves by one sample, its first sample is the previous frame's last), the zero flush --
+ * before the transform.  A call without a blanked channel launches what it launched before. */
+int kg_wf_nb_setup(kg_wf *wf, int ch, const float *nb_param /* [KG_NB_PARAMS] */);
+int kg_wf_set_nb(kg_wf *wf, int ch, int on);
+/* The standalone call site: window + ProcessBlankerOneShot for a list of frames (chan_of / frame_off / iq_len as
+ * kg_wf_frames_at_dev; every listed channel set up, on or not), frame f written to d_out + f * 8192 as complex floats. */
+int kg_wf_nb_frames_dev(kg_wf *wf, int nframes, const int32_t *chan_of, const uint64_t *frame_off, uint64_t iq_len,
+                        const void *d_iq, void *d_out);
+/* kg_nb_state's layout for the waterfall blankers.  Synchronises. */
+int kg_wf_nb_state(kg_wf *wf, const int32_t *chans, int nch, int32_t *ints, float *flts);
+
 /* ------------------------------------------------------------------------ */
 /* Waterfall DDC.  In the reference this is FPGA fabric behind SPI commands:   */
 /* WATERFALL_1CIC (verilog/rx/waterfall_1cic.v:20-144) = IQ_MIXER (iq_mixer.v)  */
@@ -403,6 +420,39 @@ int kg_fir_process_dev(kg_fir *fir, const int32_t *chans, int nch, const void *d
  * audio DDCs were started at different times deliver different record counts in one data-pump interval. */
 int kg_fir_process_each_dev(kg_fir *fir, const int32_t *chans, int nch, const void *d_in, size_t in_stride,
                             const int32_t *n_each, void *d_out, size_t out_stride, int32_t *nout);
+
+/* ---------------------------------------------------------------------------
+ * The standard noise blanker, NB_STD (rx/CuteSDR/noiseproc.cpp, CNoiseProc): the m_NoiseProc_snd[] array of rx/rx_sound.cpp.
+ * Its audio call site (rx_sound.cpp:593-598, NB_STD_POST_FILTER undefined) runs ProcessBlanker in place on the unpacked block,
+ * right before CFastFIR, when nb_enable[NB_BLANKER] && nb_algo == NB_STD. */
+enum { KG_NB_OFF = 0, KG_NB_STD = 1, KG_NB_WILD = 2 };                           /* nb_algo_e, rx/rx_noise.h:6 */
+enum { KG_NB_BLANKER = 0, KG_NB_WF = 1, KG_NB_CLICK = 2 };                       /* nb_type_e, rx/rx_noise.h:7 */
+enum { KG_NB_GATE = 0, KG_NB_THRESHOLD = 1,                                      /* extensions/noise_blank/noise_blank.h */
+       KG_NB_PARAMS = 8 };                                                       /* NOISE_PARAMS, rx/rx_noise.h:4 */
+#define KG_NB_MAG_CAP 1024         /* the largest m_MagSamples (0.005 x sample rate) a setup accepts */
+
+typedef struct kg_nb kg_nb;
+
+/* max_in: the largest InLength of one ProcessBlanker call. */
+int kg_nb_create(kg_ctx *ctx, int nchan, int max_in, kg_nb **out);
+void kg_nb_destroy(kg_nb *nb);
+/* SetupBlanker(id, sample_rate, nb_param) (noiseproc.cpp:89-145), in stream order: m_GateSamples = (int) (GateUsec * 1e-6 *
+ * SampleRate) clamped to [3, 4096], m_MagSamples = (int) (0.005 * SampleRate) at least 1, the threshold clamped to [0, 100] (NaN
+ * passes), m_Ratio = .005 * Threshold * M, m_DelaySamples = G / 2; pointers, counter, sum and both rings reset.  sample_rate 0:
+ * only the reset.  Refused (nothing changes): KG_ERR_INVALID for a gate product that is NaN or outside int, a sample rate that is
+ * NaN, infinite or gives m_MagSamples above KG_NB_MAG_CAP; KG_ERR_STATE for sample rate 0 on a channel never set up. */
+int kg_nb_setup(kg_nb *nb, int ch, float sample_rate, const float *nb_param /* [KG_NB_PARAMS] */);
+/* ProcessBlanker(n_each[i], in, out) (noiseproc.cpp:147-203) on complex floats (TYPECPX) for each listed channel: n_each[i] >= 0
+ * samples from row i of d_in to row i of d_out (rows chans[i] on a receiver bank's context, kg_ctx::rows_by_chan; strides in
+ * complex samples; d_in == d_out allowed).  A channel that was never set up is refused with KG_ERR_STATE (the reference's rings
+ * are uninitialised there).  Nothing is launched when every count is 0.  Enqueue only. */
+int kg_nb_process_dev(kg_nb *nb, const int32_t *chans, int nch, const void *d_in, size_t in_stride, const int32_t *n_each,
+                      void *d_out, size_t out_stride);
+/* The same for one channel with host buffers; synchronous (in == out allowed). */
+int kg_nb_process(kg_nb *nb, int ch, const float *in, int n, float *out);
+/* The state of each listed channel: ints[6 i ..] = m_Mptr, m_Dptr, m_BlankCounter, m_MagSamples, m_DelaySamples, m_GateSamples;
+ * flts[2 i ..] = m_Ratio, m_MagAveSum (either may be NULL).  Synchronises. */
+int kg_nb_state(kg_nb *nb, const int32_t *chans, int nch, int32_t *ints, float *flts);
 
 /* ---------------------------------------------------------------------------
  * What consumes the CFastFIR output in c2s_sound(), per receiver channel
@@ -748,6 +798,32 @@ kg_rxddc *kg_rxbank_rxddc(kg_rxbank *bank);   /* kg_rxddc_set_freq */
 kg_fir *kg_rxbank_fir(kg_rxbank *bank);       /* kg_fir_setup */
 kg_post *kg_rxbank_post(kg_rxbank *bank);     /* kg_post_set_agc / _set_smeter / _set_mode / _reset */
 kg_adpcm *kg_rxbank_adpcm(kg_rxbank *bank);
+/* The noise blanker (NB_STD) of the bank's receivers: m_NoiseProc_snd[] (kg_nb; the waterfall's m_NoiseProc_wf[] are kg_rxbank_wf's).
+ * The commands keep snd_t's and wf_inst_t's NB state per receiver, with the reference's side effects on both:
+ *   kg_rxbank_set_nb_algo    `SET nb algo=` (rx_sound_cmd.cpp:454-462): the algo; both the audio and the waterfall enables cleared.
+ *   kg_rxbank_set_nb_enable  `SET nb type= en=` (:477-483): both enables of that type.
+ *   kg_rxbank_set_nb_param   `SET nb type= param= pval=` (:485-501): the audio value stored; under NB_STD or for NB_CLICK also the
+ *                            waterfall's, with its change pending; NB_BLANKER under NB_STD: SetupBlanker("SND", frate, ...) at once.
+ *   kg_rxbank_set_nb_gate    kiwiclient's `SET nb= th=` (:660-672): gate, threshold and the audio enable only; SetupBlanker when nb != 0,
+ *                            whatever the algo.
+ * A step runs the audio blanker in place on the unpacked records (kg_rxbank_bufs.rx_in: what CFastFIR was fed) of every active
+ * receiver with enable[NB_BLANKER] under NB_STD (rx_sound.cpp:593-598).  Before a receiver's next frame, with both waterfall
+ * enables (NB_BLANKER, NB_WF) on, a pending change sets up its waterfall blanker (kg_wf_nb_setup); its frames are then blanked
+ * (rx_waterfall.cpp:1087-1099).  A zoom change through kg_rxbank_set_wf (decimation) or kg_rxbank_set_wf_pkt (zoom) makes the change
+ * pending when both enables are on (:460).  kg_rxbank_join clears the receiver's NB command state on both sides (algo NB_OFF,
+ * enables, params, pending changes, nb_setup) and keeps the blankers' states.
+ * Refused at the command, nothing changed: KG_NB_WILD or another algo (KG_ERR_INVALID, not implemented); a type outside 0..3 or a
+ * param outside 0..7 (KG_ERR_INVALID); enabling KG_NB_CLICK (KG_ERR_INVALID: test pulses are not implemented); enabling
+ * KG_NB_BLANKER under KG_NB_STD before the audio blanker was set up (KG_ERR_STATE); a value that kg_nb_setup refuses at frate (audio)
+ * or at 8192 (the waterfall's). */
+kg_nb *kg_rxbank_nb(kg_rxbank *bank);
+int kg_rxbank_set_nb_algo(kg_rxbank *bank, int rx, int algo);
+int kg_rxbank_set_nb_enable(kg_rxbank *bank, int rx, int type, int en);
+int kg_rxbank_set_nb_param(kg_rxbank *bank, int rx, int type, int param, float pval, float frate);
+int kg_rxbank_set_nb_gate(kg_rxbank *bank, int rx, int nb, int th, float frate);
+/* The command state of receiver rx: ints[14] = algo, snd enable[4], wf enable[4], wf nb_param_change[4], wf nb_setup; flts[64] =
+ * snd nb_param[4][8], wf nb_param[4][8] (either may be NULL). */
+int kg_rxbank_nb_cmd_state(kg_rxbank *bank, int rx, int32_t *ints, float *flts);
 /* CmdSetWFFreq + CmdSetWFDecim + the sampler mode sample_wf() decides on (rx/rx_waterfall.cpp:962-1008):
  *   overlapped == 0   CmdWFReset + the one-shot sampler every step: the non-overlapped frame (:1005-1041); needs
  *                     8192 * decim <= adc_samples_per_step

@@ -1,0 +1,167 @@
+"""The standard noise blanker (NB_STD) on the CPU: flydog_sdr_gps_amd/csrc/kg_nb.h -- the arithmetic the kernels share -- through
+tools/nb_host_driver.cpp against the reference's own CNoiseProc (tests/golden/nb_ref.npz, tools/make_ref_nb_golden.py), bit for bit,
+end states included; SetupBlanker's derivation over a grid; the constants and the C ABI."""
+import hashlib
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests import nb_signals
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+G = np.load(os.path.join(ROOT, "tests", "golden", "nb_ref.npz"))
+
+
+@pytest.fixture(scope="module")
+def driver(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("nb") / "nb_host_driver")
+    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-o", exe, os.path.join(ROOT, "tools", "nb_host_driver.cpp")],
+                   check=True)
+    return exe
+
+
+def digest(b):
+    return np.frombuffer(hashlib.sha256(bytes(b)).digest()[:16], np.uint8)
+
+
+def scenario_input(name):
+    sig = G[name + "_sig"]
+    script = [str(l) for l in G[name + "_script"]]
+    if name in set(G["wf_names"]):
+        from flydog_sdr_gps_amd import wf
+        frames = nb_signals.wf_frames(str(sig[0]), int(sig[2]), int(sig[1]))
+        return script, nb_signals.windowed(frames, wf.window_functions()[int(sig[3])])
+    n = sum(int(l.split()[1]) for l in script if l[0] == "B")
+    return script, nb_signals.audio(str(sig[0]), n, int(sig[1]))
+
+
+def run(exe, tmp, script, x):
+    np.ascontiguousarray(x, np.float32).tofile(str(tmp / "in.bin"))
+    (tmp / "s.txt").write_text("\n".join(script) + "\n")
+    subprocess.run([exe, str(tmp / "s.txt"), str(tmp / "in.bin"), str(tmp / "out.bin")], check=True)
+    return (tmp / "out.bin").read_bytes()
+
+
+def split(raw, script):
+    outs, ints, flts, p = [], [], [], 0
+    for l in script:
+        if l[0] in "BF":
+            n = 8192 if l[0] == "F" else int(l.split()[1])
+            outs.append(np.frombuffer(raw[p:p + 8 * n], np.float32).reshape(n, 2)); p += 8 * n
+        elif l[0] in "ST":
+            ints.append(np.frombuffer(raw[p:p + 24], np.int32)); flts.append(np.frombuffer(raw[p + 24:p + 32], np.float32)); p += 32
+    assert p == len(raw)
+    return outs, np.array(ints, np.int32), np.array(flts, np.float32)
+
+
+@pytest.mark.parametrize("name", [str(n) for n in G["audio_names"]] + [str(n) for n in G["wf_names"]])
+def test_host_driver_matches_reference(driver, tmp_path, name):
+    script, x = scenario_input(name)
+    outs, si, sf = split(run(driver, tmp_path, script, x), script)
+    want = G[name + "_sha"]
+    assert len(outs) == len(want)
+    for k, o in enumerate(outs):
+        assert np.array_equal(digest(o.tobytes()), want[k]), (name, "block", k)
+    assert np.array_equal(si, G[name + "_state_i"]), (name, si, G[name + "_state_i"])
+    assert np.array_equal(sf.view(np.uint32), G[name + "_state_f"].view(np.uint32)), (name, sf, G[name + "_state_f"])
+    if name + "_keep" in G:
+        for k, fr in zip(G[name + "_keep"], G[name + "_frames"]):
+            assert np.array_equal(outs[k].view(np.uint32), fr.view(np.uint32)), (name, k)
+    else:
+        y = np.concatenate(outs)
+        assert np.array_equal(np.packbits(np.all(y == 0, axis=1)), G[name + "_blanked"])
+
+
+def test_scenarios_exercise_the_blanker():
+    """the pinned scenarios trigger, flush and carry: not a set of pass-throughs.  The D + 1 samples after a setup are the zeroed
+    delay line's and do not count."""
+    for name in [str(n) for n in G["audio_names"]]:
+        script = [str(l) for l in G[name + "_script"]]
+        blanked = np.unpackbits(G[name + "_blanked"]).astype(bool)
+        keep = np.ones(blanked.size, bool)
+        p, D = 0, 0
+        for l in script:
+            if l[0] == "U":
+                a = l.split()[1:]
+                if float(a[0]) != 0:
+                    D = derive(float(a[0]), float(a[1]), float(a[2]))[1]
+                keep[p:p + D + 1] = False
+            elif l[0] == "B":
+                p += int(l.split()[1])
+        keep = keep[:p]
+        n = int(np.count_nonzero(blanked[:p] & keep))
+        if name == "snd_th_nan":
+            assert n == 0, name                                # a NaN ratio never triggers
+        else:
+            assert n >= 3, (name, n)
+    si = G["wf_wide_flush_state_i"]
+    assert si[0, 4] == 409 and si[0, 5] == 819                  # D, G of a wide gate at the waterfall's 8192
+    assert G["snd_gate_clamped_state_i"][0, 5] == 4096 and G["snd_gate_clamped_state_i"][0, 4] == 2048
+    assert G["snd_gate_below3_state_i"][0, 5] == 3
+    assert G["snd_setup_between_state_i"][2, 3] == 101          # a rate-0 setup keeps the previous derivation
+
+
+def derive(rate, gate, th):
+    """SetupBlanker's derivation (noiseproc.cpp:89-145) in numpy: the double products, the (int) truncations, the float ratio"""
+    rate, gate, th = np.float32(rate), np.float32(gate), np.float32(th)
+    g = float(gate) * 1e-6 * float(rate)
+    G_ = min(max(int(g), 3), 4096)
+    M = max(int(0.005 * float(rate)), 1)
+    t = float(th)
+    if t < 0:
+        t = 0.0
+    elif t > 100:
+        t = 100.0
+    ratio = np.float32(.005 * t * float(np.float32(M)))
+    return M, max(G_ // 2, 1), G_, ratio
+
+
+def test_setup_derivation_grid(driver):
+    rates = [12000.0, 20250.0, 8192.0, 12000.37, 11998.9, 1.0, 199.99, 204799.0]
+    gates = [0.0, 1.0, 99.9, 100.0, 166.7, 250.0, 1000.0, 3e5, 1e7]
+    ths = [-5.0, 0.0, 0.5, 33.3, 50.0, 99.99, 100.0, 150.0]
+    for r in rates:
+        for g in gates:
+            for t in ths:
+                out = subprocess.run([driver, "--setup", "%.9g" % r, "%.9g" % g, "%.9g" % t], check=True, capture_output=True,
+                                     text=True).stdout.split()
+                M, D, G_, ratio = derive(r, g, t)
+                assert int(out[0]) == 0 and (int(out[1]), int(out[2]), int(out[3])) == (M, D, G_), (r, g, t, out)
+                assert np.float32(float.fromhex(out[4])) == ratio, (r, g, t, out, ratio)
+    # refusals: the reference is undefined there (the (int) conversions; a magnitude ring beyond the cap)
+    for r, g, t, code in [(12000.0, 1e30, 50.0, 1), (12000.0, float("nan"), 50.0, 1), (205000.0, 100.0, 50.0, 2),
+                          (float("inf"), 100.0, 50.0, 2), (float("nan"), 100.0, 50.0, 2), (0.0, 100.0, 50.0, 3)]:
+        out = subprocess.run([driver, "--setup", "%r" % r, "%r" % g, "%r" % t], check=True, capture_output=True, text=True).stdout
+        assert int(out.split()[0]) == code, (r, g, t, out)
+    # a NaN threshold passes the clamp: the ratio is NaN (the blanker never triggers)
+    out = subprocess.run([driver, "--setup", "12000", "100", "nan"], check=True, capture_output=True, text=True).stdout.split()
+    assert np.isnan(float.fromhex(out[4]))
+
+
+def test_constants_equal_the_reference():
+    header = open(os.path.join(ROOT, "include", "kiwigpu.h")).read()
+    have = {m.group(1): int(m.group(2)) for m in re.finditer(r"\bKG_(NB_[A-Z_]+) = (-?\d+)", header)}
+    ref = dict(zip([str(n) for n in G["const_names"]], [int(v) for v in G["const_values"]]))
+    for k in ("NB_OFF", "NB_STD", "NB_WILD", "NB_BLANKER", "NB_WF", "NB_CLICK", "NB_GATE", "NB_THRESHOLD"):
+        assert have[k] == ref[k], k
+    assert have["NB_PARAMS"] == ref["NOISE_PARAMS"]
+    from flydog_sdr_gps_amd import nb
+    assert (nb.NB_OFF, nb.NB_STD, nb.NB_WILD, nb.NB_BLANKER, nb.NB_WF, nb.NB_CLICK, nb.NB_GATE, nb.NB_THRESHOLD, nb.NB_PARAMS) == \
+        (ref["NB_OFF"], ref["NB_STD"], ref["NB_WILD"], ref["NB_BLANKER"], ref["NB_WF"], ref["NB_CLICK"], ref["NB_GATE"],
+         ref["NB_THRESHOLD"], ref["NOISE_PARAMS"])
+    assert "#define KG_NB_MAG_CAP %d" % nb.MAG_CAP in header
+
+
+def test_new_symbols_declared_bound_exported():
+    from flydog_sdr_gps_amd import _lib
+    header = open(os.path.join(ROOT, "include", "kiwigpu.h")).read()
+    new = ["kg_nb_create", "kg_nb_destroy", "kg_nb_setup", "kg_nb_process_dev", "kg_nb_process", "kg_nb_state",
+           "kg_wf_nb_setup", "kg_wf_set_nb", "kg_wf_nb_frames_dev", "kg_wf_nb_state"]
+    lib = _lib.load_library()
+    for s in new:
+        assert re.search(r"\b%s\s*\(" % s, header), s
+        assert s in _lib.SYMBOLS, s
+        assert getattr(lib, s) is not None
