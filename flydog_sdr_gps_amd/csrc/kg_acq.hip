@@ -269,33 +269,20 @@ struct acq_walk {
 };
 
 // Work item = (cell, k2): one 4096-point sub-transform.  The operands of the
-// NEXT item are loaded while the current one is transformed (PREFETCH).
+// NEXT item are loaded while the current one is transformed.
 //
 // Wave-uniform constants of the combine twiddle W_N^{n*k2}, n = t + 256 m:
 // W_N^{256 m k2} = W_R^{m k2} with R = N / 256 and, with m = 4a + b,
 // = W_R^{4a k2} * W_R^{b k2}.  comb[k2] = { W_R^{k2}, W_R^{2 k2}, W_R^{3 k2},
 // W_R^{4 k2}, W_R^{8 k2}, W_R^{12 k2}, -, - } (host-built, fp32 roundings of double
-// values); quart[k2][q] = W_P^{q k2}: the factor of output quarter q (NQ = 4).
-
-// Round 4: the second exchange without the swizzle (kg_fft.h, kg_subfft4096_l: its writer has the slot column in the lane, its
-// stores and loads are conflict-free as they stand): one address register instead of sixteen.  -DACQ_X2_SWIZZLE=1: as before.
-#ifndef ACQ_X2_SWIZZLE
-#define ACQ_X2_SWIZZLE 0
-#endif
-#if ACQ_X2_SWIZZLE
-#define ACQ_X2_WR(t, th, tl, m) ((th) * 256 + 16 * (m) + ((tl) ^ (m)))
-#define ACQ_X2_RD(t, rd) (rd)
-#else
-#define ACQ_X2_WR(t, th, tl, m) ((t) + 16 * (15 * (th) + (m)))
-#define ACQ_X2_RD(t, rd) (t)
-#endif
-template <int P, int NQ, bool PREFETCH, bool STAMPS = false>   // PREFETCH: always true (kept in the names)
-__global__ __launch_bounds__(256, NQ == 1 ? 2 : 1) void acq_correlate_kernel(
+// values); quart[k2][q] = W_P^{q k2}: the factor of output quarter q (acq_correlate8_kernel).
+template <int P, bool STAMPS = false>
+__global__ __launch_bounds__(256, 2) void acq_correlate_kernel(
     const float2 *__restrict__ data,  // [nblocks][P][4096]
     const float2 *__restrict__ code,  // [max_sats][P][8 rows][2 (256 + 2 H)]
     const float2 *__restrict__ tab4096, const float2 *__restrict__ tabN,
     const float2 *__restrict__ comb,           // [P][8]
-    const float2 *__restrict__ quart,          // [P][4]
+    const float2 *__restrict__ quart,          // [P][4]; unused here (acq_correlate8_kernel reads the same table)
     const acq_pair_desc *__restrict__ pairs,   // pair p belongs to XCD group p & 7
     int *__restrict__ claim,                   // [8][ACQ_CLAIM_STRIDE] per-group cell counters, zero at launch
     acq_walk walk,
@@ -409,29 +396,18 @@ __global__ __launch_bounds__(256, NQ == 1 ? 2 : 1) void acq_correlate_kernel(
         int claimed = 0;
         // (the counter's value only, and the atomic optimizer off: see wf_frame_kernel -- otherwise wave 0 waits for it here)
         if (t == 0) claimed = __hip_atomic_fetch_add(&claim[xcd * ACQ_CLAIM_STRIDE], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        cf acc[NQ][16];
+        cf acc[16];
         // The twiddle-accumulate of item k2 is DEFERRED into item k2+1's exchanges, where a wave otherwise
-        // only waits (slots: behind the stores before a barrier, or after it while the tile reads are in
-        // flight).  yprev holds the deferred item's transform; for NQ == 1 (256 registers, two workgroups per
-        // CU) the code rows of the next item are fetched during pass 2 to make room, the data rows keep their
-        // place in the conjugate product and pass 0.  NQ == 4 runs one workgroup per CU -- nothing else
-        // fills its waits; slots {0,0,1,1} measured best for it (<4,4> 1.67 -> 1.53 ms on the acq59 workload).
-        cf yprev[16], pbase = cf{0.f, 0.f}, pg[3], pG[3], pQ[3];
-        (void) pQ;
-        // acc[4a + b] (+)= yv[4a + b] * (bs * W_R^{4a kp}) * W_R^{b kp} for a in [a0, a1): C[4a + b] = B[a] * g[b]
-        // is formed first (wave-uniform factors), the products accumulate through fused multiply-adds
-        auto accumulate = [&](const cf (&yv)[16], int kp, cf bs, const cf (&g)[3], const cf (&G)[3],
-                              const cf (&Q)[3], int a0, int a1) {
-            (void) Q;
+        // only waits.  yprev holds the deferred item's transform; with 256 registers (two workgroups per CU)
+        // the code rows of the next item are fetched during pass 2 to make room, the data rows keep their
+        // place in the conjugate product and pass 0.
+        cf yprev[16], pbase = cf{0.f, 0.f}, pg[3], pG[3];
+        // acc[4a + b] (+)= yv[4a + b] * (bs * W_R^{4a kp}) * W_R^{b kp}: C[4a + b] = B[a] * g[b] is formed
+        // first (wave-uniform factors), the products accumulate through fused multiply-adds
+        auto accumulate = [&](const cf (&yv)[16], int kp, cf bs, const cf (&g)[3], const cf (&G)[3]) {
             if (kp == 0) {
 #pragma unroll
-                for (int q = 0; q < NQ; q++)
-#pragma unroll
-                    for (int a = 0; a < 4; a++)
-                        if (a >= a0 && a < a1) {
-#pragma unroll
-                            for (int b4 = 0; b4 < 4; b4++) acc[q][4 * a + b4] = yv[4 * a + b4];
-                        }
+                for (int m = 0; m < 16; m++) acc[m] = yv[m];
                 return;
             }
             // B[a] = bs * W_R^{4a kp}: the three products in one block (kg_fft.h, batched products)
@@ -439,66 +415,17 @@ __global__ __launch_bounds__(256, NQ == 1 ? 2 : 1) void acq_correlate_kernel(
             kg_cmul1x3s(B1, B2, B3, bs, G[0], G[1], G[2]);
 #pragma unroll
             for (int a = 0; a < 4; a++) {
-                if (a < a0 || a >= a1) continue;
                 const cf Ba = a == 0 ? bs : (a == 1 ? B1 : (a == 2 ? B2 : B3));
                 const cf C0 = Ba;
                 cf C1, C2, C3;
                 kg_cmul1x3s(C1, C2, C3, Ba, g[0], g[1], g[2]);
-                if constexpr (NQ == 1) {
-                    kg_cmac4v(acc[0][4 * a], acc[0][4 * a + 1], acc[0][4 * a + 2], acc[0][4 * a + 3],
-                              yv[4 * a], yv[4 * a + 1], yv[4 * a + 2], yv[4 * a + 3], C0, C1, C2, C3);
-                } else {
-                    // four output quarters: z[m] = y[m] * C[m] once, then acc_q[m] += z[m] * W_P^(q*kp)
-                    cf z0 = yv[4 * a], z1 = yv[4 * a + 1], z2 = yv[4 * a + 2], z3 = yv[4 * a + 3];
-                    kg_cmul4v<false>(z0, z1, z2, z3, C0, C1, C2, C3);
-                    const cf z[4] = {z0, z1, z2, z3};
-#pragma unroll
-                    for (int b = 0; b < 4; b++) {
-                        const int m = 4 * a + b;
-                        acc[0][m] = acc[0][m] + z[b];
-                        if constexpr (P == 4) {            // quarters 1..3: times j^(q*kp), wave-uniform
-                            if (kp == 1) {
-                                acc[1][m] = kg_addj(acc[1][m], z[b]); acc[2][m] = acc[2][m] - z[b];
-                                acc[3][m] = kg_subj(acc[3][m], z[b]);
-                            } else if (kp == 2) {
-                                acc[1][m] = acc[1][m] - z[b]; acc[2][m] = acc[2][m] + z[b];
-                                acc[3][m] = acc[3][m] - z[b];
-                            } else {
-                                acc[1][m] = kg_subj(acc[1][m], z[b]); acc[2][m] = acc[2][m] - z[b];
-                                acc[3][m] = kg_addj(acc[3][m], z[b]);
-                            }
-                        }
-                    }
-                    if constexpr (P != 4) {                // times W_16^(q*kp), wave-uniform
-#pragma unroll
-                        for (int q = 1; q < 4; q++)
-                            kg_cmac4s(acc[q][4 * a], acc[q][4 * a + 1], acc[q][4 * a + 2], acc[q][4 * a + 3],
-                                      z0, z1, z2, z3, Q[q - 1]);
-                    }
-                }
+                kg_cmac4v(acc[4 * a], acc[4 * a + 1], acc[4 * a + 2], acc[4 * a + 3],
+                          yv[4 * a], yv[4 * a + 1], yv[4 * a + 2], yv[4 * a + 3], C0, C1, C2, C3);
             }
         };
-        // where the four quarters (a = 0..3) of the deferred accumulate go: slot 0 = behind the pass-0 stores,
-        // before barrier 1; 1 = after barrier 1, pass-1 tile reads in flight; 2 = behind the pass-1 stores,
-        // before barrier 2; 3 = after barrier 2, pass-2 tile reads in flight
-#ifndef KG_DEFER_PLACE
-#define KG_DEFER_PLACE {1, 1, 1, 1}
-#endif
-#ifndef KG_DEFER_PLACE4
-#define KG_DEFER_PLACE4 {0, 0, 1, 1}
-#endif
-        auto deferred = [&](int slot, int k2) {
-            constexpr int place1[4] = KG_DEFER_PLACE, place4[4] = KG_DEFER_PLACE4;
-            int a0 = 4, a1 = 0;                                // the run of quarters placed in this slot
-#pragma unroll
-            for (int a = 0; a < 4; a++)
-                if ((NQ == 1 ? place1[a] : place4[a]) == slot) { a0 = a < a0 ? a : a0; a1 = a + 1; }
-            if (a0 < a1 && k2 > 0) {                           // (an empty slot leaves nothing behind, not even the test)
-                kg_pin();
-                accumulate(yprev, k2 - 1, pbase, pg, pG, pQ, a0, a1);
-                kg_pin();
-            }
-        };
+        // (a lambda of its own, not the three statements at the call: the inlining order decides the register allocation of
+        // the item loop, and this is the order the measured kernel was built with)
+        auto accumulate_fenced = [&](int kp) { kg_pin(); accumulate(yprev, kp, pbase, pg, pG); kg_pin(); };
         const int tl = t & 15, th = t >> 4;
         const int rd = t ^ (th & 15);              // P(t + 256 j) = 256 j + (t ^ ((t >> 4) & 15)), kg_fft.h
         // rolled on purpose: unrolled (or with k2 a template constant) the
@@ -523,10 +450,6 @@ __global__ __launch_bounds__(256, NQ == 1 ? 2 : 1) void acq_correlate_kernel(
             const bool same = k2 < P - 1;
             const acq_rsrc nr = fetch_prepare(same ? cur.data_off : nxt.data_off, same ? cur.code_off : nxt.code_off,
                                               same ? cur.dop : nxt.dop, (k2 + 1) & (P - 1));
-#ifndef KG_FUSED_TW
-#define KG_FUSED_TW 1
-#endif
-#if KG_FUSED_TW
             // Round 4: conj(data) * code (simd_multiply_conjugate_ccc, support/simd.cpp:39-67) FUSED into the first stage of
             // pass 0 (kg_cc_radix16_h, kg_fft.h): 99 packed instructions where products + butterfly took 112, and no copies
             // of the code operands (the in-place products needed sixteen).  The next item's data rows are requested two at
@@ -536,109 +459,60 @@ __global__ __launch_bounds__(256, NQ == 1 ? 2 : 1) void acq_correlate_kernel(
             kg_cc_radix16_h<+1>(c, d, y, [&](int s) {
                 kg_pin();
                 if (s < 4) {
-                    if constexpr (NQ == 1) { fetch_drow(nr, 2 * s); fetch_drow(nr, 2 * s + 1); }
-                    else { fetch_row(nr, 2 * s); fetch_row(nr, 2 * s + 1); }
+                    fetch_drow(nr, 2 * s); fetch_drow(nr, 2 * s + 1);
                 } else {
 #pragma unroll
                     for (int m = s - 4; m < 16; m += 4) kg_st_tile(&tileA[16 * t + (m ^ tl)], y[m]);
                 }
                 kg_pin();
             });
-#else
-            // conj(data) * code, simd_multiply_conjugate_ccc (support/simd.cpp:39-67)
-#pragma unroll
-            for (int j = 0; j < 16; j += 4) {
-                x[j] = c[j]; x[j + 1] = c[j + 1]; x[j + 2] = c[j + 2]; x[j + 3] = c[j + 3];
-                kg_cmul4v<true>(x[j], x[j + 1], x[j + 2], x[j + 3], d[j], d[j + 1], d[j + 2], d[j + 3]);
-                if (STAMPS && j == 12) KG_STAMP(STAMPS, sti, 9);
-                if (j >= 4) {                                   // rows 0..2 (registers of the batch before)
-                    kg_pin();
-                    if constexpr (NQ == 1) fetch_drow(nr, j / 4 - 1); else fetch_row(nr, j / 4 - 1);
-                    kg_pin();
-                }
-            }
-            KG_STAMP(STAMPS, sti, 10);
-            // pass 0 (no twiddles), out index 16 t + m: rows 3..7 between its first-stage groups, the LDS
-            // stores group by group as the outputs become final
-            kg_radix16_h<+1>(x, y, [&](int s) {
-                kg_pin();
-                if (s < 4) {
-                    if constexpr (NQ == 1) { fetch_drow(nr, 3 + s); if (s == 3) fetch_drow(nr, 7); }
-                    else { fetch_row(nr, 3 + s); if (s == 3) fetch_row(nr, 7); }
-                } else {
-#pragma unroll
-                    for (int m = s - 4; m < 16; m += 4) kg_st_tile(&tileA[16 * t + (m ^ tl)], y[m]);
-                }
-                kg_pin();
-            });
-#endif
             KG_STAMP(STAMPS, sti, 0);
-            deferred(0, k2);
             KG_STAMP(STAMPS, sti, 1);
             __syncthreads();
             KG_STAMP(STAMPS, sti, 2);
 #pragma unroll
             for (int j = 0; j < 16; j++) x[j] = kg_ld_tile(&tileA[rd + 256 * j]);
-            deferred(1, k2);
+            // the deferred accumulate of item k2 - 1: after barrier 1, while the pass-1 tile reads are in flight
+            // (one of an item's four waits -- behind the stores before either barrier, or after it with the tile reads
+            // in flight; moving it between them changed nothing, DESIGN_HISTORY)
+            if (k2 > 0) accumulate_fenced(k2 - 1);
             if (STAMPS) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             KG_STAMP(STAMPS, sti, 3);
-            // pass 1: twiddle W256^(j*(t&15)), out index (t>>4)*256 + (t&15) + 16 m
-#if KG_FUSED_TW
+            // pass 1: twiddle W256^(j*(t&15)), out index (t>>4)*256 + (t&15) + 16 m = t + 16 (15 th + m).  Round 4: this second
+            // exchange has no swizzle (kg_fft.h, kg_subfft4096_l: its writer has the slot column in the lane, its stores and loads
+            // are conflict-free as they stand): one address register instead of sixteen.
             kg_tw_radix16_h<+1>(x, y, tw.p1, [&](int s) {
-#else
-            kg_twiddle16<+1>(x, tw.p1);
-            kg_radix16_h<+1>(x, y, [&](int s) {
-#endif
                 if (s >= 4) {
                     kg_pin();
 #pragma unroll
-                    for (int m = s - 4; m < 16; m += 4) kg_st_tile(&tileB[ACQ_X2_WR(t, th, tl, m)], y[m]);
+                    for (int m = s - 4; m < 16; m += 4) kg_st_tile(&tileB[t + 16 * (15 * th + m)], y[m]);
                     kg_pin();
                 }
             });
             KG_STAMP(STAMPS, sti, 4);
-            deferred(2, k2);
             __syncthreads();
             KG_STAMP(STAMPS, sti, 5);
             // wave-uniform constants (s_load), hidden behind pass 2
-            cf g[3], G[3], Q[3];
-            (void) Q;
+            cf g[3], G[3];
 #pragma unroll
             for (int i = 0; i < 3; i++) { g[i] = kg_ld(&comb[8 * k2 + i]); G[i] = kg_ld(&comb[8 * k2 + 3 + i]); }
-            if constexpr (NQ == 4 && P != 4) {
 #pragma unroll
-                for (int q = 1; q < 4; q++) Q[q - 1] = kg_ld(&quart[4 * k2 + q]);
-            }
-#pragma unroll
-            for (int j = 0; j < 16; j++) x[j] = kg_ld_tile(&tileB[ACQ_X2_RD(t, rd) + 256 * j]);
-            deferred(3, k2);
+            for (int j = 0; j < 16; j++) x[j] = kg_ld_tile(&tileB[t + 256 * j]);
             if (STAMPS) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             KG_STAMP(STAMPS, sti, 6);
             // pass 2: twiddle W4096^(j*t), out index t + 256 m (kept in registers)
-            // (NQ == 1: the next item's code rows, two per first-stage group)
-            auto crows = [&](int s) {
-                if constexpr (NQ == 1) {
-                    if (s < 4) { kg_pin(); fetch_crow(nr, 2 * s); fetch_crow(nr, 2 * s + 1); kg_pin(); }
-                }
-            };
-#if KG_FUSED_TW
-            kg_tw_radix16_h<+1>(x, yprev, tw.p2, crows);
-#else
-            kg_twiddle16<+1>(x, tw.p2);
-            kg_radix16_h<+1>(x, yprev, crows);
-#endif
+            // (the next item's code rows, two per first-stage group)
+            kg_tw_radix16_h<+1>(x, yprev, tw.p2, [&](int s) {
+                if (s < 4) { kg_pin(); fetch_crow(nr, 2 * s); fetch_crow(nr, 2 * s + 1); kg_pin(); }
+            });
             pbase = base;
 #pragma unroll
             for (int i = 0; i < 3; i++) { pg[i] = g[i]; pG[i] = G[i]; }
-            if constexpr (NQ == 4 && P != 4) {
-#pragma unroll
-                for (int i = 0; i < 3; i++) pQ[i] = Q[i];
-            }
             KG_STAMP(STAMPS, sti, 7);
             KG_STAMP(STAMPS, sti, 11);
             if (STAMPS) st_item++;
         }
-        accumulate(yprev, P - 1, pbase, pg, pG, pQ, 0, 4);     // the cell's last item
+        accumulate(yprev, P - 1, pbase, pg, pG);               // the cell's last item
 
         // search.cpp:486-490: power, first maximum (strict >), running total
         // Row r = m + 16 q holds n = t + 256 r.  `limit` is wave-uniform, so a row lies wholly inside the
@@ -647,7 +521,7 @@ __global__ __launch_bounds__(256, NQ == 1 ? 2 : 1) void acq_correlate_kernel(
         const int limit = cur.limit, full_rows = limit >> 8;
         float bp = 0.f, sum = 0.f;
         int bi = 0;
-        if constexpr (NQ == 1 && P == 4) {
+        if constexpr (P == 4) {
             // the 16368-lag kernel's form of the scan (acq_correlate8_kernel): powers kept, total in packed pairs, maximum
             // by fmax, the lane's FIRST row holding it from a row mask built with a compare and an add-with-carry per row
             // (acq 0.796 -> 0.789 ms; P = 16 keeps the serial form below: its sixteen more registers of powers spilled there,
@@ -656,7 +530,7 @@ __global__ __launch_bounds__(256, NQ == 1 ? 2 : 1) void acq_correlate_kernel(
             float pw[16];
 #pragma unroll
             for (int m = 0; m < 16; m++) {
-                const cf sq = acc[0][m] * acc[0][m];
+                const cf sq = acc[m] * acc[m];
                 pw[m] = sq.x + sq.y;
                 if (m >= full_rows) {
                     asm volatile("");
@@ -685,11 +559,11 @@ __global__ __launch_bounds__(256, NQ == 1 ? 2 : 1) void acq_correlate_kernel(
             }
             const unsigned rowmask = qm[0] | (qm[1] << 8);
             bi = t + 256 * (int) __builtin_ctz(rowmask | 0x80000000u);
-        } else if constexpr (NQ == 1) {
+        } else {
             int br = 0;
 #pragma unroll
             for (int m = 0; m < 16; m++) {
-                const cf v = acc[0][m];
+                const cf v = acc[m];
                 const cf sq = v * v;
                 const float pw = sq.x + sq.y;
                 if (m < full_rows) {
@@ -703,21 +577,6 @@ __global__ __launch_bounds__(256, NQ == 1 ? 2 : 1) void acq_correlate_kernel(
                 }
             }
             bi = t + 256 * br;
-        } else {
-            // (one workgroup per CU: the straight masked scan measured faster here than a test per row or
-            // per output quarter, 1.53 against 1.64 ms for <4,4> on the acq59 workload)
-#pragma unroll
-            for (int q = 0; q < NQ; q++) {
-#pragma unroll
-                for (int m = 0; m < 16; m++) {
-                    const int n = t + 256 * m + SUB * q;
-                    const cf v = acc[q][m];
-                    const float pw = v.x * v.x + v.y * v.y;
-                    const bool in = n < limit, take = in & (pw > bp);
-                    bp = take ? pw : bp; bi = take ? n : bi;
-                    sum += in ? pw : 0.f;
-                }
-            }
         }
 #define ACQ_RED_STEP(L)                                                               \
         {                                                                                \
@@ -904,10 +763,6 @@ __global__ __launch_bounds__(512, 1) void acq_correlate8_kernel(
         for (int m = 0; m < 8; m++) kg_st_tile(&tile1[w1 + 8 * (m ^ b1)], y[m]);
         __syncthreads();
     }
-#ifndef KG_E1B_HANDOVER
-#define KG_E1B_HANDOVER(P) true
-#endif
-    constexpr bool HANDOVER = KG_E1B_HANDOVER(P);
     int prev_out = -1, prev_limit = 1;
     // waves 0..3: lane i reduces its own and lane i + 256's hand-over values, then the wave; red[wave] out
     auto reduce_pairs = [&]() {
@@ -926,8 +781,8 @@ __global__ __launch_bounds__(512, 1) void acq_correlate8_kernel(
         }
     };
     auto merge_store = [&](int out, int limit) {
-        if (i < 64) {                                  // lanes 0..3 (0..7 without the hand-over) of wave 0 merge the wave results
-            const acq_red r = red[HANDOVER ? (i & 3) : (i & 7)];
+        if (i < 64) {                                  // lanes 0..3 of wave 0 merge the wave results
+            const acq_red r = red[i & 3];
             float bp = r.p, sum = r.s;
             int mi = r.i;
 #define ACQ_RED_STEP(L)                                                               \
@@ -939,7 +794,6 @@ __global__ __launch_bounds__(512, 1) void acq_correlate8_kernel(
                 sum += os;                                                               \
             }
             ACQ_RED_STEP(0) ACQ_RED_STEP(1)
-            if (!HANDOVER) ACQ_RED_STEP(2)
 #undef ACQ_RED_STEP
             if (i == 0) {
                 const float ave = sum / (float) limit;     // :493
@@ -952,12 +806,8 @@ __global__ __launch_bounds__(512, 1) void acq_correlate8_kernel(
     };
     for (;;) {
         const bool more = nxt_idx < ncell;
-#ifndef KG_E1B_EAGER_DESCRIBE
         const acq_pend pend = describe_issue(more ? nxt_idx : cur_idx);
         acq_cell_desc nxt = cur;                       // (resolved at item P - 2, the first one that addresses the next cell)
-#else
-        const acq_cell_desc nxt = describe(more ? nxt_idx : cur_idx);
-#endif
         int claimed = 0;
         // (lane 0 of wave 7 claims: wave 0 already carries the result merge and store of every cell)
         if (i == 448) claimed = __hip_atomic_fetch_add(&claim[xcd * ACQ_CLAIM_STRIDE], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -976,9 +826,7 @@ __global__ __launch_bounds__(512, 1) void acq_correlate8_kernel(
             // prefetch of every item would be waited for on the spot)
             unsigned long long *sti = (STAMPS && st && st_item < 60) ? st + 16 + 16 * st_item : nullptr;
             KG_STAMP(STAMPS, sti, 0);
-#ifndef KG_E1B_EAGER_DESCRIBE
             if (k2 == P - 2) nxt = describe_resolve(pend);
-#endif
             // The operands of item n+2 -- (cur, k2 + 2) or (nxt, k2 + 2 - P); ONE set of load sites, never skipped --
             // are requested one row (a data and a code load, two legs each) at a time BETWEEN the arithmetic blocks of both phases:
             // a buffer load costs the CU's one texture addresser about twenty cycles, all eight waves reach the same
@@ -989,12 +837,11 @@ __global__ __launch_bounds__(512, 1) void acq_correlate8_kernel(
             auto ld = [&](int j) { kg_pin(); fetch_row(nr, j); kg_pin(); };
             // ---- phase A: pass 2 of this item | conj-multiply + pass 0 of the next
             {
-                cf xa[8], ya[8], xb[8], yb[8];
+                cf xa[8], ya[8], yb[8];
 #pragma unroll
                 for (int j = 0; j < 8; j++) xa[j] = kg_ld_tile(&tile1[r1 + 512 * j]);
                 // conj(data) * code, simd_multiply_conjugate_ccc (support/simd.cpp:39-67) -- round 4: fused into pass 0's first
                 // stage, as the inter-pass twiddles are into theirs (kg_fft.h: 6 of 42 / 44 packed instructions per pass)
-                (void) xb;
                 KG_STAMP(STAMPS, sti, 1);
                 kg_cc_radix8_h<+1>(c, d, yb, [&]() { ld(0); });
 #pragma unroll
@@ -1039,7 +886,6 @@ __global__ __launch_bounds__(512, 1) void acq_correlate8_kernel(
                 for (int q = 0; q < 4; q++)
 #pragma unroll
                     for (int m = 0; m < 8; m++) acc[q][m] = y[m];
-                if (!HANDOVER && prev_out >= 0) merge_store(prev_out, prev_limit);      // the cell before (wave 0; see the cell end)
             } else {
                 // z[m] = y[m] * base * W^{4a k2} * W^{b k2}, m = 4a + b; then acc_q[m] += z[m] * W_P^{q k2}
                 const cf B1 = kg_cmul(base, G);
@@ -1077,8 +923,8 @@ __global__ __launch_bounds__(512, 1) void acq_correlate8_kernel(
             }
             // The cell before: its wave reductions in item 1 (waves 0..3, which wait ~700 cycles at this barrier otherwise),
             // its merge and store in item 2 (wave 0) -- see the cell end.
-            if (HANDOVER && k2 == 1 && prev_out >= 0) reduce_pairs();
-            if (HANDOVER && k2 == 2 && prev_out >= 0) merge_store(prev_out, prev_limit);
+            if (k2 == 1 && prev_out >= 0) reduce_pairs();
+            if (k2 == 2 && prev_out >= 0) merge_store(prev_out, prev_limit);
             KG_STAMP(STAMPS, sti, 8);
             if (STAMPS) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             KG_STAMP(STAMPS, sti, 9);
@@ -1143,14 +989,7 @@ __global__ __launch_bounds__(512, 1) void acq_correlate8_kernel(
         // barrier waits for.  Every lane hands its three values over through LDS (three stores) instead; waves 0..3 reduce
         // their own and their partner's in item 1 of the next cell and wave 0 merges and stores in item 2, both inside the
         // ~700 cycles those waves wait at the phase-B barrier anyway (profiles/r03_e1b8_stamps_final.txt).
-        if (HANDOVER) {
-            xch_p[i] = bp; xch_i[i] = bi; xch_s[i] = sum;
-        } else {                                       // in place: every wave reduces its own lanes here
-            float wmax = bp, wsum = sum;
-            kg_wave_max_sum(wmax, wsum);
-            const int wn = kg_wave_min(bp == wmax ? bi : 0x7fffffff);
-            if ((i & 63) == 0) { red[i >> 6].p = wmax; red[i >> 6].i = wn; red[i >> 6].s = wsum; }
-        }
+        xch_p[i] = bp; xch_i[i] = bi; xch_s[i] = sum;
         KG_STAMP(STAMPS, stc, 2);
         if (i == 448) *red_claim = 2 * nslots + claimed;
         __syncthreads();
@@ -1158,10 +997,8 @@ __global__ __launch_bounds__(512, 1) void acq_correlate8_kernel(
         const int nn_idx = __builtin_amdgcn_readfirstlane(*red_claim);
         prev_out = cur.out; prev_limit = limit;
         if (!more) {                                   // the workgroup's last cell: nothing to hide behind
-            if (HANDOVER) {
-                reduce_pairs();
-                __syncthreads();
-            }
+            reduce_pairs();
+            __syncthreads();
             merge_store(prev_out, prev_limit);
         }
         KG_STAMP(STAMPS, stc, 4);
@@ -1220,10 +1057,10 @@ struct kg_acq {
     float2 *d_comb;        // [P][8]  combine constants (acq_correlate_kernel)
     float2 *d_quart;       // [P][4]
     float2 *d_comb8;       // [P][4]  combine constants of the 512-thread four-quarter kernel
-    int grid8;             // its persistent grid; 0: use acq_correlate_kernel<P, 4> (KIWIGPU_ACQ_E1B8=0)
+    int grid8;             // its persistent grid (>= 8)
     float2 *d_code;        // [max_sats][P planes with halo]
     float2 *d_data;        // [max_blocks][P][4096]  layout A
-    float2 *d_data_b;      // [max_blocks][P][4096]  layout B (the 512-thread kernel's); null when that kernel is off
+    float2 *d_data_b;      // [max_blocks][P][4096]  layout B (the 512-thread kernel's); null until an SV needs it (ensure_data_b)
     std::vector<char> code_layout;   // per SV: 0 = A, 1 = B
     float2 *d_td;          // [max_blocks][N]  decimated time-domain samples per block
     float2 *d_td_code;     // [N]              same, for the code-table build
@@ -1448,9 +1285,9 @@ static int acq_init(kg_acq *a)
     // persistent grid: resident workgroups per CU x CUs, rounded to a multiple of 8 (XCDs)
     int occ1 = 0;
 #define ACQ_SETUP(PP)                                                                                          \
-    KG_HIP(hipFuncSetAttribute((const void *) acq_correlate_kernel<PP, 1, true>,                              \
+    KG_HIP(hipFuncSetAttribute((const void *) acq_correlate_kernel<PP>,                                       \
                                hipFuncAttributeMaxDynamicSharedMemorySize, ACQ_LDS_BYTES));                   \
-    KG_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ1, acq_correlate_kernel<PP, 1, true>, 256,        \
+    KG_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ1, acq_correlate_kernel<PP>, 256,                 \
                                                         ACQ_LDS_BYTES));
     if (P == 4) { ACQ_SETUP(4) } else { ACQ_SETUP(16) }
 #undef ACQ_SETUP
@@ -1460,8 +1297,7 @@ static int acq_init(kg_acq *a)
         if (v >= 1 && v < occ1) occ1 = v;
     }
     a->grid1 = (ctx->num_cus * occ1) & ~7;
-    // the 16368-lag window runs on the 512-thread form (one workgroup = eight waves per CU, two per SIMD); round 3's
-    // 256-thread four-accumulator form (acq_correlate_kernel<P, 4>) is no longer instantiated
+    // the 16368-lag window runs on the 512-thread form (one workgroup = eight waves per CU, two per SIMD)
     if (P == 4)
         KG_HIP(hipFuncSetAttribute((const void *) acq_correlate8_kernel<4>,
                                    hipFuncAttributeMaxDynamicSharedMemorySize, ACQ8_LDS_BYTES));
@@ -1546,7 +1382,7 @@ void kg_acq_destroy(kg_acq *a)
 // host, once; afterwards every Sample() writes both layouts in its combine kernel.
 static int ensure_data_b(kg_acq *a)
 {
-    if (a->d_data_b || a->grid8 == 0) return KG_OK;
+    if (a->d_data_b) return KG_OK;
     const size_t n = (size_t) a->fft_len * a->max_blocks;
     KG_HIP(hipStreamSynchronize(a->fstream));
     KG_HIP(hipStreamSynchronize(a->ctx->stream));
@@ -1578,7 +1414,7 @@ static int set_limit(kg_acq *a, int sat, int limit)
                a->max_sats - 1);
     KG_REQUIRE(limit >= 1 && limit <= 4 * SUB, KG_ERR_INVALID, "limit %d out of range (1..%d)", limit,
                4 * SUB);
-    const int layout = (limit > SUB && a->grid8 > 0) ? 1 : 0;        // which kernel will read this SV's code spectrum
+    const int layout = limit > SUB ? 1 : 0;                         // which kernel will read this SV's code spectrum
     if (layout) {
         // layout B of the data spectra first: if it cannot be had the SV keeps what it had (an earlier code with its own
         // limit and layout stays searchable; nothing points the 512-thread kernel at a buffer that does not exist)
@@ -1866,18 +1702,17 @@ int kg_acq_get_data_td(kg_acq *a, int block, float *td)
 
 }  // extern "C"
 
-template <int P, int NQ, bool STAMPS>
+template <int P, bool STAMPS>
 static void launch_correlate(kg_acq *a, hipStream_t st, int first, const acq_pair_desc *d_pairs, int npairs,
                              unsigned long long *d_stamps)
 {
-    static_assert(NQ == 1, "the four-accumulator form is not built any more (acq_correlate8_kernel took its place)");
     const int grid = a->grid1;
     const acq_walk w = {npairs, a->ndop, a->dop_lo};
-    hipLaunchKernelGGL((acq_correlate_kernel<P, NQ, true, STAMPS>), dim3(grid), dim3(256), ACQ_LDS_BYTES, st,
+    hipLaunchKernelGGL((acq_correlate_kernel<P, STAMPS>), dim3(grid), dim3(256), ACQ_LDS_BYTES, st,
                        (const float2 *) (a->d_data + (size_t) first * a->fft_len), (const float2 *) a->d_code,
                        (const float2 *) a->ctx->d_tab4096, (const float2 *) a->d_tabN,
                        (const float2 *) a->d_comb, (const float2 *) a->d_quart, d_pairs,
-                       a->d_claim + (NQ == 1 ? 0 : 8 * ACQ_CLAIM_STRIDE), w, a->halo, a->d_cells, d_stamps);
+                       a->d_claim, w, a->halo, a->d_cells, d_stamps);
 }
 
 extern "C" {
@@ -1936,25 +1771,23 @@ int kg_acq_correlate_blocks_async(kg_acq *a, int first, int nblocks, const int *
     }
     if (a->own_fstream && (rc = wait_once(st, a->ev_ready, a->ready_of, first, nblocks)) != KG_OK) return rc;   // RAW
     if (a->np1 > 0) {
-        if (a->P == 4) launch_correlate<4, 1, false>(a, st, first, a->d_pairs1, a->np1, nullptr);
-        else launch_correlate<16, 1, false>(a, st, first, a->d_pairs1, a->np1, nullptr);
+        if (a->P == 4) launch_correlate<4, false>(a, st, first, a->d_pairs1, a->np1, nullptr);
+        else launch_correlate<16, false>(a, st, first, a->d_pairs1, a->np1, nullptr);
         KG_HIP(hipGetLastError());
     }
     if (a->np4 > 0) {
-        {
-            KG_REQUIRE(a->d_data_b != nullptr, KG_ERR_STATE, "kg_acq_correlate_async: a long-window code without its layout of the data spectra");
-            const acq_walk w = {a->np4, a->ndop, a->dop_lo};
-            if (a->P == 4)
-                hipLaunchKernelGGL(acq_correlate8_kernel<4>, dim3(a->grid8), dim3(512), ACQ8_LDS_BYTES, st,
-                                   (const float2 *) (a->d_data_b + (size_t) first * a->fft_len), (const float2 *) a->d_code,
-                                   (const float2 *) a->ctx->d_tab4096, (const float2 *) a->d_tabN, (const float2 *) a->d_comb8,
-                                   (const float2 *) a->d_quart, a->d_pairs4, a->d_claim + 8 * ACQ_CLAIM_STRIDE, w, a->halo, a->d_cells);
-            else
-                hipLaunchKernelGGL(acq_correlate8_kernel<16>, dim3(a->grid8), dim3(512), ACQ8_LDS_BYTES, st,
-                                   (const float2 *) (a->d_data_b + (size_t) first * a->fft_len), (const float2 *) a->d_code,
-                                   (const float2 *) a->ctx->d_tab4096, (const float2 *) a->d_tabN, (const float2 *) a->d_comb8,
-                                   (const float2 *) a->d_quart, a->d_pairs4, a->d_claim + 8 * ACQ_CLAIM_STRIDE, w, a->halo, a->d_cells);
-        }
+        KG_REQUIRE(a->d_data_b != nullptr, KG_ERR_STATE, "kg_acq_correlate_async: a long-window code without its layout of the data spectra");
+        const acq_walk w = {a->np4, a->ndop, a->dop_lo};
+        if (a->P == 4)
+            hipLaunchKernelGGL(acq_correlate8_kernel<4>, dim3(a->grid8), dim3(512), ACQ8_LDS_BYTES, st,
+                               (const float2 *) (a->d_data_b + (size_t) first * a->fft_len), (const float2 *) a->d_code,
+                               (const float2 *) a->ctx->d_tab4096, (const float2 *) a->d_tabN, (const float2 *) a->d_comb8,
+                               (const float2 *) a->d_quart, a->d_pairs4, a->d_claim + 8 * ACQ_CLAIM_STRIDE, w, a->halo, a->d_cells);
+        else
+            hipLaunchKernelGGL(acq_correlate8_kernel<16>, dim3(a->grid8), dim3(512), ACQ8_LDS_BYTES, st,
+                               (const float2 *) (a->d_data_b + (size_t) first * a->fft_len), (const float2 *) a->d_code,
+                               (const float2 *) a->ctx->d_tab4096, (const float2 *) a->d_tabN, (const float2 *) a->d_comb8,
+                               (const float2 *) a->d_quart, a->d_pairs4, a->d_claim + 8 * ACQ_CLAIM_STRIDE, w, a->halo, a->d_cells);
         KG_HIP(hipGetLastError());
     }
     const int npairs = nblocks * nsats;
@@ -2006,7 +1839,7 @@ int kg_acq_debug_corr_stamps(kg_acq *a, int nblocks, const int *sats, int nsats,
     int rc = kg_acq_correlate_async(a, nblocks, sats, nsats);      // builds the lists, warms up
     if (rc) return rc;
     hipStream_t st = a->ctx->stream;
-    if (a->np1 == 0 && a->np4 > 0 && a->grid8 > 0) {           // an all-E1B list: the 512-thread kernel's stamps
+    if (a->np1 == 0 && a->np4 > 0) {                           // an all-E1B list: the 512-thread kernel's stamps
         unsigned long long *d = nullptr;
         const size_t bytes = sizeof(unsigned long long) * (512 + 4 * 1024);
         KG_HIP(hipMalloc((void **) &d, bytes));
@@ -2043,13 +1876,13 @@ int kg_acq_debug_corr_stamps(kg_acq *a, int nblocks, const int *sats, int nsats,
     KG_HIP(hipMemset(d, 0, bytes));
     KG_HIP(hipMemsetAsync(a->d_claim, 0, sizeof(int) * 16 * ACQ_CLAIM_STRIDE, st));
     if (a->P == 4) {
-        KG_HIP(hipFuncSetAttribute((const void *) acq_correlate_kernel<4, 1, true, true>,
+        KG_HIP(hipFuncSetAttribute((const void *) acq_correlate_kernel<4, true>,
                                    hipFuncAttributeMaxDynamicSharedMemorySize, ACQ_LDS_BYTES));
-        launch_correlate<4, 1, true>(a, st, 0, a->d_pairs1, a->np1, d);
+        launch_correlate<4, true>(a, st, 0, a->d_pairs1, a->np1, d);
     } else {
-        KG_HIP(hipFuncSetAttribute((const void *) acq_correlate_kernel<16, 1, true, true>,
+        KG_HIP(hipFuncSetAttribute((const void *) acq_correlate_kernel<16, true>,
                                    hipFuncAttributeMaxDynamicSharedMemorySize, ACQ_LDS_BYTES));
-        launch_correlate<16, 1, true>(a, st, 0, a->d_pairs1, a->np1, d);
+        launch_correlate<16, true>(a, st, 0, a->d_pairs1, a->np1, d);
     }
     KG_HIP(hipGetLastError());
     KG_HIP(hipMemsetAsync(a->d_claim, 0, sizeof(int) * 16 * ACQ_CLAIM_STRIDE, st));

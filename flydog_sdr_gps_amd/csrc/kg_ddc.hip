@@ -289,11 +289,6 @@ DDC_DEV ddc_state4 ddc_add_state(const ddc_state4 &a, const ddc_state4 &b) { ret
 //   DDC_NARROW  the 64-bit form alone: pass A of any decimation in runs of at most 1024 samples, pass B of 16 <= R <= 256
 //   DDC_WIDE    pass B of R >= 512 alone (96-bit integrators)
 enum { DDC_ALL = 0, DDC_NARROW = 1, DDC_WIDE = 2 };
-#ifdef KG_DDC_ONE_FORM           // A/B build: every launch carries every form (round 4's shape)
-static const bool DDC_ONE_FORM = true;
-#else
-static const bool DDC_ONE_FORM = false;
-#endif
 template <bool PASS_B, int MODE>
 DDC_DEV void ddc_wf_run_body(
     const short *__restrict__ adc, long n, int L, int nruns,
@@ -357,26 +352,22 @@ DDC_DEV void ddc_wf_run_body(
     // Round 4: TWO groups ahead.  With the ADC stream coming from HBM (a block larger than the Infinity Cache, or one the
     // DMA engine has just written) the first touch of a 128-byte line -- one in eight of a lane's loads -- takes longer than
     // the one group of arithmetic the load used to run ahead of: the bench's rotation of nine 32 MiB blocks cost ddc14
-    // 0.44 -> 0.47 ms.  KG_DDC_AHEAD=1 restores the single look-ahead.
-#ifndef KG_DDC_AHEAD
-#define KG_DDC_AHEAD 2
-#endif
+    // 0.44 -> 0.47 ms.
     const long last_grp = g1 - 8;                                  // start of the run's last whole group (callers check s0 + 8 <= g1)
     int4 ahead = make_int4(0, 0, 0, 0), ahead2 = make_int4(0, 0, 0, 0);
     if (s0 + 8 <= g1) {
         ahead = *(const int4 *) (adc + s0);
-        if (KG_DDC_AHEAD == 2) ahead2 = *(const int4 *) (adc + (s0 + 8 <= last_grp ? s0 + 8 : last_grp));
+        ahead2 = *(const int4 *) (adc + (s0 + 8 <= last_grp ? s0 + 8 : last_grp));
     }
     auto samples8 = [&](long t, short (&buf)[8]) {                 // callers guarantee t + 8 <= g1 and walk t in steps of 8 from s0
         const int4 v = ahead;
-        if (KG_DDC_AHEAD == 2) {
-            ahead = ahead2;
-            const long tn = t + 16 <= last_grp ? t + 16 : last_grp;     // (the last groups re-read the run's last one: one load site, never skipped)
-            ahead2 = *(const int4 *) (adc + tn);
-        } else {
-            const long tn = (t + 16 <= g1) ? t + 8 : t;
-            ahead = *(const int4 *) (adc + tn);
-        }
+        ahead = ahead2;
+        // (g1 is not needed here any more -- the single look-ahead that read it is gone -- but it stays captured, at this place:
+        // without the capture the compiler allocates the registers of every kernel built from this body differently, and that
+        // is a change to time on a GPU)
+        (void) g1;
+        const long tn = t + 16 <= last_grp ? t + 16 : last_grp;         // (the last groups re-read the run's last one: one load site, never skipped)
+        ahead2 = *(const int4 *) (adc + tn);
         buf[0] = (short) v.x; buf[1] = (short) (v.x >> 16); buf[2] = (short) v.y; buf[3] = (short) (v.y >> 16);
         buf[4] = (short) v.z; buf[5] = (short) (v.z >> 16); buf[6] = (short) v.w; buf[7] = (short) (v.w >> 16);
     };
@@ -1898,7 +1889,7 @@ static int ddc_push_impl(kg_ddc *d, const void *d_adc, size_t n, const int32_t *
     const unsigned gx = (unsigned) ((nruns + DDC_THREADS - 1) / DDC_THREADS);
     if (!h_run.empty()) {
         // (runs of at most 1024 samples: every decimation integrates from zero in 64 bits -- the narrow form alone)
-        auto pass_a = (L <= 1024 && !DDC_ONE_FORM) ? ddc_wf_run_kernel<false, DDC_NARROW> : ddc_wf_run_kernel<false, DDC_ALL>;
+        auto pass_a = L <= 1024 ? ddc_wf_run_kernel<false, DDC_NARROW> : ddc_wf_run_kernel<false, DDC_ALL>;
         hipLaunchKernelGGL(pass_a, dim3(gx, (unsigned) h_run.size()), dim3(DDC_THREADS), 0, st,
                            (const short *) d_adc, (long) n, L, nruns, (const ddc_chan *) d->d_chans, s_list,
                            (const u32 *) d->d_nco, d_local, d_c0rel, d_tau, s_c0off,
@@ -1974,7 +1965,7 @@ static int ddc_push_impl(kg_ddc *d, const void *d_adc, size_t n, const int32_t *
     // waves gain).
     const long fill = (long) d->ctx->num_cus * 4 * 2 * 64;
     const size_t nbig = h_rest.size() - nmid;
-    const bool split = !DDC_ONE_FORM && (nmid == 0 || (long) nmid * nruns >= fill) && (nbig == 0 || (long) nbig * nruns >= fill);
+    const bool split = (nmid == 0 || (long) nmid * nruns >= fill) && (nbig == 0 || (long) nbig * nruns >= fill);
     auto pass_b_rest = [&](hipStream_t s) {
         if (h_rest.empty()) return;
         if (!split) { pass_b(s, h_rest.size(), s_selrest, 0, DDC_ALL); return; }

@@ -920,16 +920,26 @@ def test_cpp_waterfall_example_builds_and_refuses_without_a_gpu(tmp_path):
 # ---- round 5: no experiment code in the product, tuning switches gated, the receiver bank's surface -------------------
 def test_no_knock_out_code_and_no_four_accumulator_kernel_in_the_product():
     """the knock-out builds (ACQ_KO / E1B_KO / KG_WF_KO: results wrong by construction) are gone from the
-    sources, and the superseded four-accumulator correlator acq_correlate_kernel<P, 4, ...> is not in the shipped library."""
+    sources, and so are the compile-time A/B switches that kept a superseded form of a kernel next to the shipped one (KG_EXP_*:
+    wrong values too).  The superseded four-accumulator correlator is neither in the shipped library -- acq_correlate_kernel
+    is built as <4 | 16, STAMPS> and as nothing else -- nor in the source (its template argument NQ)."""
     import glob
     import subprocess
-    for f in glob.glob(os.path.join(ROOT, "flydog_sdr_gps_amd", "csrc", "*.h*")):
+    retired = ("KG_FUSED_TW", "ACQ_X2_SWIZZLE", "KG_DEFER_PLACE", "KG_DEFER_PLACE4", "KG_E1B_HANDOVER", "KG_E1B_EAGER_DESCRIBE",
+               "KG_TILE_ST_PAIRED", "KG_WF_FUSED_TW", "KG_DDC_ONE_FORM", "KG_DDC_AHEAD", "KG_EXP_NCO", "KG_EXP_WF_LOG10F", "KG_EXP_")
+    sources = glob.glob(os.path.join(ROOT, "flydog_sdr_gps_amd", "csrc", "*.h*"))
+    assert sources
+    for f in sources:
         text = open(f).read()
         assert "_KO" not in text and "KO_" not in text, f
+        for name in retired:
+            assert name not in text, (f, name)
+    acq = open(os.path.join(ROOT, "flydog_sdr_gps_amd", "csrc", "kg_acq.hip")).read()
+    assert "acq_correlate_kernel" in acq and not re.search(r"\bNQ\b", acq)
     lib = os.path.join(ROOT, "flydog_sdr_gps_amd", "libkiwigpu.so")
     syms = subprocess.run(["nm", "-C", lib], capture_output=True, text=True, check=True).stdout
     kernels = [ln for ln in syms.splitlines() if "acq_correlate_kernel<" in ln]
-    assert kernels and all(re.search(r"acq_correlate_kernel<(4|16), 1, true", ln) for ln in kernels), kernels[:3]
+    assert kernels and all(re.search(r"acq_correlate_kernel<(4|16), (false|true)>", ln) for ln in kernels), kernels[:3]
 
 
 def test_tuning_variables_are_read_only_behind_kiwigpu_tuning():

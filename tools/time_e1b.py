@@ -1,4 +1,4 @@
-"""Times Correlate() for Galileo E1B codes (4092 chips, 16368-sample window: the NQ = 4 kernel)
+"""Times Correlate() for Galileo E1B codes (4092 chips, 16368-sample window: acq_correlate8_kernel)
 next to the same number of C/A codes.  Random memory codes: timing does not depend on them.
 usage: python tools/time_e1b.py [B ...]"""
 import os
