@@ -157,6 +157,11 @@ SYMBOLS = {
     "kg_post_set_nr_param": (_i, [_vp, _i, _i, _i, C.c_float]),
     "kg_post_nr_process_dev": (_i, [_vp, _vp, _i, _i, _vp, _sz, _i, _vp, _sz]),
     "kg_post_nr_state": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "kg_post_nrs_select": (_i, [_vp, _i]),
+    "kg_post_nrs_setup": (_i, [_vp, _i]),
+    "kg_post_nrs_passband": (_i, [_vp, _i, C.c_double, C.c_double]),
+    "kg_post_nrs_process_dev": (_i, [_vp, _vp, _i, _vp, _sz, _i, _vp, _sz]),
+    "kg_post_nrs_state": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "kg_post_cfir_init_lp": (_i, [_vp, _i, _i, _i, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float]),
     "kg_post_cfir_init_const": (_i, [_vp, _i, _i, _i, _vp, C.c_float]),
     "kg_post_cfir_get_taps": (_i, [_vp, _i, _i, _vp]),

@@ -39,10 +39,19 @@
 //     products in LDS, so no lane waits for a broadcast.  Nothing is reassociated.  The stage is a kernel of its own (post_nr_kernel)
 //     that kg_post_process_dev enqueues behind post_kernel only for a batch that holds a channel with NR on, over that launch's
 //     d_s16 rows in place.
+//   * NR_SPECTRAL (rx/Teensy/NR_spectral.cpp), the third algorithm of that switch, is transform work: per 512 samples two
+//     50 %-overlapped 512-point frames, each a forward transform, per-bin gains and an inverse transform.  One wave per channel
+//     (post_nrs_kernel), the channel's nine 256-float arrays and the frame in LDS for the whole call.  Each of the three radix-8 passes
+//     of the reference's transform is 64 independent butterflies, one per lane, through LDS; the digit reversal is the last pass's
+//     store address, the inverse's conjugate and scale a sign at the first load and a factor at the last store.  The per-bin
+//     expressions (kg_nrs.h, shared with the host driver) run four bins per lane; the two ordered sums pre_power / post_power are
+//     walked by every lane over LDS; each smoothed gain is its own ordered sum of <= 9 terms.  Nothing is reassociated.
 #include "kg_common.h"
 #include "kg_libm.h"
 #include "kg_libm_trig.h"
 #include "kg_nr.h"
+#include "kg_nrs.h"
+#include "kg_tables.h"
 
 #include <math.h>
 #include <stddef.h>
@@ -719,6 +728,149 @@ __global__ __launch_bounds__(64) void post_nr_kernel(post_nr *__restrict__ nr_ta
     for (int i = lane; i < n; i += 64) dst[i] = (short) io[i];
 }
 
+// ---- NR_SPECTRAL (rx/rx_sound.cpp:945-947 -> rx/Teensy/NR_spectral.cpp) ----
+// The transform's twiddles and the sqrt-Hann window (kg_tables.h) where a lane can index them.
+__device__ const kg_nrs_tw_t NRS_TW = KG_NRS_TW;
+__device__ const kg_nrs_win_t NRS_WIN = KG_NRS_WIN;
+enum { NRS_LSB, NRS_LIFFT, NRS_NEST, NRS_XT, NRS_PSLP, NRS_POST, NRS_PRIO, NRS_HK, NRS_G, NRS_ARRAYS };   // nr_spectral_t's order
+
+// arm_cfft_f32(len512, F, inverse, 1) on F (LDS), one butterfly per lane and pass.  A lane owns its eight points in passes 0 and
+// 1; the last pass stores to the digit-reversed places, so every lane has loaded before any stores.
+__device__ __forceinline__ void post_nrs_cfft(float2 *F, int lane, bool inverse)
+{
+    const float invL = 1.0f / (float) kg_nrs::FFT_FULL;
+    for (int pass = 0; pass < 3; pass++) {
+        int i1, n2, j, mod;
+        float xr[8], xi[8];
+        kg_nrs::bfly_index(pass, lane, i1, n2, j, mod);
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const float2 v = F[i1 + k * n2];
+            xr[k] = v.x; xi[k] = (inverse && pass == 0) ? -v.y : v.y;              // "conjugate input data"
+        }
+        kg_nrs::bfly_compute(pass, j, mod, NRS_TW.v, xr, xi);
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const int i = i1 + k * n2;
+            if (pass < 2) F[i] = make_float2(xr[k], xi[k]);
+            else if (!inverse) F[kg_nrs::rev3(i)] = make_float2(xr[k], xi[k]);
+            else F[kg_nrs::rev3(i)] = make_float2(xr[k] * invL, -(xi[k]) * invL);    // "conjugate and scale output data"
+        }
+        __syncthreads();
+    }
+}
+
+// kFused: the stage of c2s_sound() behind post_kernel over its d_s16 rows in place, for the listed channels whose algo is
+// NR_SPECTRAL and whose mode is not a stereo one (the others return at once).  !kFused: kg_post_nrs_process_dev.
+// n is a multiple of 512: nr_spectral_process(ch, 512, ...) once per 512 samples.
+template <bool kFused>
+__global__ __launch_bounds__(64) void post_nrs_kernel(kg_nrs::state_t *__restrict__ tab, const post_nr *__restrict__ nr_tab,
+                                                      const post_chan *__restrict__ chan_tab, const int *__restrict__ chans,
+                                                      kg_nrs::rate_t rt, const short *in, size_t in_stride, int n, short *out,
+                                                      size_t out_stride, int by_chan)
+{
+    using namespace kg_nrs;
+    __shared__ float2 F[FFT_FULL];
+    __shared__ float A[NRS_ARRAYS][FFT_HALF];
+    __shared__ float X[FFT_HALF];
+    const int lane = threadIdx.x, ch = chans[blockIdx.x];
+    if (kFused && (nr_tab[ch].algo != KG_NR_SPECTRAL || post_is_stereo(chan_tab[ch].mode))) return;
+    const int row = kFused && by_chan ? ch : (int) blockIdx.x;
+    const short *src = in + (size_t) row * in_stride;
+    short *dst = out + (size_t) row * out_stride;
+    state_t *s = tab + ch;
+    int first_time = s->first_time, init_counter = s->init_counter;
+    const int lo3 = s->vad_lo, hi3 = s->vad_hi;
+    const par_t par = s->par;
+    float *g_arr = s->last_sample_buffer;                                           // the nine arrays lie one behind the other
+    for (int a = 0; a < NRS_ARRAYS; a++)
+        for (int q = 0; q < 4; q++) A[a][lane + 64 * q] = g_arr[a * FFT_HALF + lane + 64 * q];
+    if (first_time == 1) {                                                          // :126-135
+        for (int q = 0; q < 4; q++) {
+            const int b = lane + 64 * q;
+            A[NRS_LSB][b] = 0.0; A[NRS_G][b] = 1.0; A[NRS_HK][b] = 1.0; A[NRS_NEST][b] = 0.0; A[NRS_PSLP][b] = 0.5;
+        }
+        first_time = 2;
+    }
+    __syncthreads();
+    for (int f = 0; f < n / FFT_HALF; f++) {                                        // frame f: samples f * 256 .. of the call
+        int VAD_low = 0, VAD_high = 0;
+        for (int q = 0; q < 4; q++) {                                               // :140-161
+            const int i = lane + 64 * q;
+            const float f_samp = (float) src[f * FFT_HALF + i];
+            F[i] = make_float2(A[NRS_LSB][i] * NRS_WIN.v[i / 2], 0.0f);
+            F[FFT_HALF + i] = make_float2(f_samp * NRS_WIN.v[(FFT_HALF + i) / 2], 0.0f);
+            A[NRS_LSB][i] = f_samp;
+        }
+        __syncthreads();
+        post_nrs_cfft(F, lane, false);
+        for (int q = 0; q < 4; q++) {
+            const int b = lane + 64 * q;
+            X[b] = mag2(F[b].x, F[b].y);
+        }
+        if (first_time == 2) {                                                      // :173-186
+            for (int q = 0; q < 4; q++) {
+                const int b = lane + 64 * q;
+                startup_bin(X[b], A[NRS_NEST][b], A[NRS_XT][b]);
+            }
+            init_counter = (init_counter + 1) & 255;
+            if (init_counter > INIT_FRAMES - 1) { init_counter = 0; first_time = 3; }
+        }
+        if (first_time == 3) {
+            VAD_low = lo3; VAD_high = hi3;
+            for (int q = 0; q < 4; q++) {
+                const int b = lane + 64 * q;
+                track_bin(par, rt.ap, rt.ax, X[b], A[NRS_XT][b], A[NRS_PSLP][b]);
+                snr_bin(par, rt.snr_prio_min, X[b], A[NRS_XT][b], A[NRS_HK][b], A[NRS_POST][b], A[NRS_PRIO][b]);
+                if (b >= VAD_low && b < VAD_high) gain_bin(A[NRS_POST][b], A[NRS_PRIO][b], A[NRS_G][b], A[NRS_HK][b]);
+            }
+            __syncthreads();
+            float pre_power = 0.0, post_power = 0.0;                                // :265-271, every lane walks both sums
+            for (int b = VAD_low; b < VAD_high; b++) power_step(X[b], A[NRS_G][b], pre_power, post_power);
+            const int NN = smoothing_width(pre_power, post_power);
+            for (int q = 0; q < 4; q++) {                                           // :284-314: reads NR_G, writes its own NR_Nest
+                const int b = lane + 64 * q;
+                float nest;
+                if (smooth_bin(A[NRS_G], b, VAD_low, VAD_high, NN, nest)) A[NRS_NEST][b] = nest;
+            }
+            __syncthreads();
+            for (int q = 0; q < 4; q++) {                                           // :317-320
+                const int b = lane + 64 * q;
+                if (b >= VAD_low + NN / 2 && b < VAD_high - NN / 2) A[NRS_G][b] = A[NRS_NEST][b];
+            }
+        }
+        __syncthreads();
+        for (int q = 0; q < 4; q++) {                                               // :329-338: bin b and bin 511 - b, as written
+            const int b = lane + 64 * q;
+            if (b >= VAD_low && b < VAD_high) {
+                const float g = A[NRS_G][b];
+                const int ai = FFT_FULL - b - 1;
+                F[b] = make_float2(F[b].x * g, F[b].y * g);
+                F[ai] = make_float2(F[ai].x * g, F[ai].y * g);
+            }
+        }
+        __syncthreads();
+        post_nrs_cfft(F, lane, true);
+        for (int q = 0; q < 4; q++) {                                               // :344-357
+            const int i = lane + 64 * q;
+            const float re = F[i].x * NRS_WIN.v[i / 2];
+            dst[f * FFT_HALF + i] = out_sample(re, A[NRS_LIFFT][i], par.final_gain);
+            A[NRS_LIFFT][i] = F[FFT_HALF + i].x * NRS_WIN.v[(FFT_HALF + i) / 2];
+        }
+        __syncthreads();
+    }
+    for (int a = 0; a < NRS_ARRAYS; a++)
+        for (int q = 0; q < 4; q++) g_arr[a * FFT_HALF + lane + 64 * q] = A[a][lane + 64 * q];
+    if (lane == 0) { s->first_time = first_time; s->init_counter = init_counter; }
+}
+
+__global__ void post_nrs_vad_kernel(kg_nrs::state_t *tab, int nchan, int vad_lo, int vad_hi)     // a fresh object's passband bins
+{
+    const int ch = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ch < nchan) { tab[ch].vad_lo = vad_lo; tab[ch].vad_hi = vad_hi; }
+}
+
 __global__ void post_reset_rings_kernel(float2 *ring_in, float *ring_mag, int ch0)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x, ch = ch0 + blockIdx.y;
@@ -741,6 +893,13 @@ struct post_nr_host {             // the snd_t fields of the noise-reduction com
     float param[2][kg_nr::NPARAMS];
 };
 
+struct post_nrs_host {            // NR_SPECTRAL's host side: s->norm_locut / norm_hicut (rx_sound.h:91), nr_spectral_t's init flag
+    bool init;
+    float norm_locut, norm_hicut;
+    int vad[2];                   // VAD_low, VAD_high of that passband at the object's rate (what the device state holds)
+    kg_nrs::par_t par;
+};
+
 struct kg_post {
     kg_ctx *ctx;
     int nchan;
@@ -757,6 +916,10 @@ struct kg_post {
     std::vector<char> h_sq_ready;        // kg_post_squelch_setup AND kg_post_squelch_set were called
     post_nr *d_nr;                       // [nchan]
     std::vector<post_nr_host> h_nr;      // s->nr_algo, s->nr_enable[], s->nr_param[][] (the filter states are the device's)
+    kg_nrs::state_t *d_nrs;              // [nchan]: nr_spectral[] (NR_spectral.cpp:69)
+    std::vector<post_nrs_host> h_nrs;
+    int nrs_snd_rate;                    // the reference's global snd_rate as NR_SPECTRAL sees it (kg_post_nrs_setup; 12000 at create)
+    kg_nrs::rate_t nrs_rate;             // tinc .. ap, snr_prio_min at that rate
     kg_stage_cache list_cache = {};      // the channel list of the last process call
 };
 
@@ -964,6 +1127,17 @@ static bool nr_active(const post_nr_host &h, int mode)
            mode != KG_POST_IQ && mode != KG_POST_SAS && mode != KG_POST_QAM;
 }
 
+static bool nrs_active(const post_nr_host &h, int mode)
+{
+    return h.algo == KG_NR_SPECTRAL && mode != KG_POST_IQ && mode != KG_POST_SAS && mode != KG_POST_QAM;   // the enables are not consulted
+}
+
+static int nrs_put_vad(kg_post *p, int ch)         // VAD_low / VAD_high to the device (h_nrs is stable storage; the caller synchronises)
+{
+    KG_HIP(hipMemcpyAsync(&p->d_nrs[ch].vad_lo, p->h_nrs[ch].vad, sizeof(int) * 2, hipMemcpyHostToDevice, p->ctx->stream));
+    return KG_OK;
+}
+
 static int nr_put_ctl(kg_post *p, int ch)          // s->nr_algo and s->nr_enable[] to the device
 {
     const post_nr_host &h = p->h_nr[ch];
@@ -995,6 +1169,16 @@ int kg_post_create(kg_ctx *ctx, int nchan, kg_post **out)
     post_nr_host nh;
     memset(&nh, 0, sizeof nh);
     p->h_nr.assign(nchan, nh);
+    KG_HIP(hipMalloc((void **) &p->d_nrs, sizeof(kg_nrs::state_t) * (size_t) nchan));
+    KG_HIP(hipMemsetAsync(p->d_nrs, 0, sizeof(kg_nrs::state_t) * (size_t) nchan, ctx->stream));     // the zeroed static nr_spectral[]
+    post_nrs_host sh;
+    memset(&sh, 0, sizeof sh);
+    p->nrs_snd_rate = 12000;
+    p->nrs_rate = kg_nrs::rate_consts(p->nrs_snd_rate);
+    kg_nrs::vad_bins(0.f, 0.f, p->nrs_snd_rate, sh.vad[0], sh.vad[1]);
+    p->h_nrs.assign(nchan, sh);
+    hipLaunchKernelGGL(post_nrs_vad_kernel, dim3((nchan + 255) / 256), dim3(256), 0, ctx->stream, p->d_nrs, nchan, sh.vad[0], sh.vad[1]);
+    KG_HIP(hipGetLastError());
     post_sam w;                                     // a new connection at snd_rate 12000: PLL(MED), PLL(RESET) (rx_sound.cpp:302-303)
     memset(&w, 0, sizeof w);
     sam_init_consts(w, 12000);
@@ -1034,7 +1218,7 @@ void kg_post_destroy(kg_post *p)
     (void) hipSetDevice(p->ctx->device);
     (void) hipStreamSynchronize(p->ctx->stream);
     (void) hipFree(p->d_chan); (void) hipFree(p->d_ring_in); (void) hipFree(p->d_ring_mag); (void) hipFree(p->d_cfir);
-    (void) hipFree(p->d_sam); (void) hipFree(p->d_nr);
+    (void) hipFree(p->d_sam); (void) hipFree(p->d_nr); (void) hipFree(p->d_nrs);
     kg_stage_cache_free(&p->list_cache);
     delete p;
 }
@@ -1257,6 +1441,10 @@ int kg_post_reset(kg_post *p, int ch)
     if ((rc = sam_upload_reset(p, ch))) return rc;
     memset(&p->h_nr[ch], 0, sizeof(post_nr_host));  // :236-240: memset(s) zeroes nr_enable / nr_param, nr_algo = NR_OFF_; the filters stay
     if ((rc = nr_put_ctl(p, ch))) return rc;
+    post_nrs_host &sh = p->h_nrs[ch];               // memset(s) zeroes norm_locut / norm_hicut too; nr_spectral[ch] stays
+    sh.norm_locut = sh.norm_hicut = 0.f;
+    kg_nrs::vad_bins(0.f, 0.f, p->nrs_snd_rate, sh.vad[0], sh.vad[1]);
+    if ((rc = nrs_put_vad(p, ch))) return rc;
     KG_HIP(hipStreamSynchronize(p->ctx->stream));
     return KG_OK;
 }
@@ -1273,7 +1461,7 @@ int kg_post_process_dev(kg_post *p, const int32_t *chans, int nch, const void *d
     KG_REQUIRE(in_stride >= (size_t) nsamps && out_stride >= (size_t) nsamps, KG_ERR_INVALID,
                "kg_post_process_dev: stride smaller than nsamps");
     std::vector<char> seen(p->nchan, 0);
-    bool any_sam = false, any_nr = false;
+    bool any_sam = false, any_nr = false, any_nrs = false;
     for (int i = 0; i < nch; i++) {
         KG_REQUIRE(chans[i] >= 0 && chans[i] < p->nchan && !seen[chans[i]], KG_ERR_INVALID,
                    "kg_post_process_dev: chans[%d] = %d out of range or listed twice", i, chans[i]);
@@ -1291,9 +1479,13 @@ int kg_post_process_dev(kg_post *p, const int32_t *chans, int nch, const void *d
                    "kg_post_process_dev: channel %d has AM/SSB de-emphasis on and no m_am_ssb_deemp_FIR coefficients", ch);
         any_sam |= post_is_sam(mode);
         any_nr |= nr_active(p->h_nr[ch], mode);
+        any_nrs |= nrs_active(p->h_nr[ch], mode);
     }
-    KG_REQUIRE(!any_nr || d_s16, KG_ERR_INVALID,
+    KG_REQUIRE(!(any_nr || any_nrs) || d_s16, KG_ERR_INVALID,
                "kg_post_process_dev: a listed channel has noise reduction on, and it runs over d_s16: d_s16 must not be NULL");
+    KG_REQUIRE(!any_nrs || nsamps % kg_nrs::FFT_FULL == 0, KG_ERR_INVALID,
+               "kg_post_process_dev: a listed channel has spectral noise reduction on, which runs on blocks of %d samples: nsamps %d",
+               kg_nrs::FFT_FULL, nsamps);
     hipStream_t st = p->ctx->stream;
     void *d_list = nullptr;
     if ((rc = kg_ctx_stage_cached(p->ctx, &p->list_cache, chans, sizeof(int) * nch, &d_list))) return rc;
@@ -1306,6 +1498,11 @@ int kg_post_process_dev(kg_post *p, const int32_t *chans, int nch, const void *d
     // rx_sound.cpp:933-949 over the rows just written, only for a batch that holds a channel with NR on (the others return at once)
     if (any_nr) {
         hipLaunchKernelGGL(post_nr_kernel<true>, dim3(nch), dim3(64), 0, st, p->d_nr, p->d_chan, (const int *) d_list, -1,
+                           (const short *) d_s16, out_stride, nsamps, (short *) d_s16, out_stride, p->ctx->rows_by_chan);
+        KG_HIP(hipGetLastError());
+    }
+    if (any_nrs) {                                  // :945-947, likewise
+        hipLaunchKernelGGL(post_nrs_kernel<true>, dim3(nch), dim3(64), 0, st, p->d_nrs, p->d_nr, p->d_chan, (const int *) d_list, p->nrs_rate,
                            (const short *) d_s16, out_stride, nsamps, (short *) d_s16, out_stride, p->ctx->rows_by_chan);
         KG_HIP(hipGetLastError());
     }
@@ -1490,7 +1687,7 @@ int kg_post_set_nr_algo(kg_post *p, int ch, int algo)
 {
     int rc = post_check(p, ch, "kg_post_set_nr_algo");
     if (rc) return rc;
-    KG_REQUIRE(algo != KG_NR_SPECTRAL, KG_ERR_INVALID, "kg_post_set_nr_algo: NR_SPECTRAL is not implemented");
+    KG_REQUIRE(algo != KG_NR_SPECTRAL, KG_ERR_INVALID, "kg_post_set_nr_algo: NR_SPECTRAL is selected by kg_post_nrs_select");
     post_nr_host &h = p->h_nr[ch];
     h.algo = algo;                                  // rx_sound_cmd.cpp:465-469: any other value is a switch without a case
     h.en[0] = h.en[1] = 0;
@@ -1539,7 +1736,125 @@ int kg_post_set_nr_param(kg_post *p, int ch, int type, int param, float pval)
         KG_HIP(hipMemcpyAsync(d->lms_ring[type], f.lms_ring[type], sizeof f.lms_ring[type], hipMemcpyHostToDevice, st));
         KG_HIP(hipMemcpyAsync(d->lms_coef[type], f.lms_coef[type], sizeof f.lms_coef[type], hipMemcpyHostToDevice, st));
         KG_HIP(hipStreamSynchronize(st));
+    } else if (h.algo == KG_NR_SPECTRAL) {          // :520: nr_spectral_init(rx_chan, s->nr_param[n_type]), one state for either type
+        post_nrs_host &sh = p->h_nrs[ch];
+        kg_nrs::state_t *ds = p->d_nrs + ch;
+        kg_nrs::state_t f;                          // (a staging copy of the first init's seeds)
+        if (!sh.init) {                             // NR_spectral.cpp:85-101
+            sh.init = true;
+            kg_nrs::init_first(f);
+            KG_HIP(hipMemcpyAsync(&ds->first_time, &f.first_time, sizeof(int), hipMemcpyHostToDevice, st));
+            KG_HIP(hipMemcpyAsync(ds->last_sample_buffer, f.last_sample_buffer, sizeof f.last_sample_buffer, hipMemcpyHostToDevice, st));
+            KG_HIP(hipMemcpyAsync(ds->NR_Hk_old, f.NR_Hk_old, sizeof f.NR_Hk_old, hipMemcpyHostToDevice, st));
+            KG_HIP(hipMemcpyAsync(ds->NR_SNR_post, f.NR_SNR_post, sizeof f.NR_SNR_post, hipMemcpyHostToDevice, st));
+            KG_HIP(hipMemcpyAsync(ds->NR_SNR_prio, f.NR_SNR_prio, sizeof f.NR_SNR_prio, hipMemcpyHostToDevice, st));
+        }
+        kg_nrs::init_params(sh.par, v);             // :103-108
+        KG_HIP(hipMemcpyAsync(&ds->par, &sh.par, sizeof sh.par, hipMemcpyHostToDevice, st));
+        KG_HIP(hipStreamSynchronize(st));
     }
+    return KG_OK;
+}
+
+int kg_post_nrs_select(kg_post *p, int ch)
+{
+    int rc = post_check(p, ch, "kg_post_nrs_select");
+    if (rc) return rc;
+    const post_nrs_host &sh = p->h_nrs[ch];
+    KG_REQUIRE(kg_nrs::vad_ok(sh.vad[0], sh.vad[1]), KG_ERR_INVALID,
+               "kg_post_nrs_select: channel %d: passband %g..%g Hz is bins %d..%d at %d Hz; NR_spectral.cpp indexes outside its arrays "
+               "unless VAD_high >= %d and VAD_low <= %d (kg_post_nrs_passband first)", ch, (double) sh.norm_locut, (double) sh.norm_hicut,
+               sh.vad[0], sh.vad[1], p->nrs_snd_rate, kg_nrs::VAD_HIGH_MIN, kg_nrs::VAD_LOW_MAX);
+    post_nr_host &h = p->h_nr[ch];
+    h.algo = KG_NR_SPECTRAL;                        // rx_sound_cmd.cpp:465-469
+    h.en[0] = h.en[1] = 0;
+    return nr_put_ctl(p, ch);
+}
+
+int kg_post_nrs_setup(kg_post *p, int snd_rate)
+{
+    KG_REQUIRE(p != nullptr, KG_ERR_INVALID, "kg_post_nrs_setup: null object");
+    int rc = kg_ctx_use(p->ctx);
+    if (rc) return rc;
+    KG_REQUIRE(snd_rate >= 1000 && snd_rate <= 1000000, KG_ERR_INVALID, "kg_post_nrs_setup: snd_rate %d", snd_rate);
+    std::vector<int> vad(2 * (size_t) p->nchan);
+    for (int ch = 0; ch < p->nchan; ch++) {
+        kg_nrs::vad_bins(p->h_nrs[ch].norm_locut, p->h_nrs[ch].norm_hicut, snd_rate, vad[2 * ch], vad[2 * ch + 1]);
+        KG_REQUIRE(p->h_nr[ch].algo != KG_NR_SPECTRAL || kg_nrs::vad_ok(vad[2 * ch], vad[2 * ch + 1]), KG_ERR_INVALID,
+                   "kg_post_nrs_setup: at %d Hz channel %d's passband is bins %d..%d, outside what NR_SPECTRAL can run on", snd_rate, ch,
+                   vad[2 * ch], vad[2 * ch + 1]);
+    }
+    p->nrs_snd_rate = snd_rate;
+    p->nrs_rate = kg_nrs::rate_consts(snd_rate);
+    for (int ch = 0; ch < p->nchan; ch++) {
+        p->h_nrs[ch].vad[0] = vad[2 * ch]; p->h_nrs[ch].vad[1] = vad[2 * ch + 1];
+        if ((rc = nrs_put_vad(p, ch))) return rc;
+    }
+    KG_HIP(hipStreamSynchronize(p->ctx->stream));
+    return KG_OK;
+}
+
+int kg_post_nrs_passband(kg_post *p, int ch, double locut, double hicut)
+{
+    int rc = post_check(p, ch, "kg_post_nrs_passband");
+    if (rc) return rc;
+    float nl, nh;
+    int vl, vh;
+    kg_nrs::norm_passband(locut, hicut, nl, nh);    // rx_sound_cmd.cpp:252-266
+    kg_nrs::vad_bins(nl, nh, p->nrs_snd_rate, vl, vh);
+    KG_REQUIRE(p->h_nr[ch].algo != KG_NR_SPECTRAL || kg_nrs::vad_ok(vl, vh), KG_ERR_INVALID,
+               "kg_post_nrs_passband: channel %d runs NR_SPECTRAL, and %g..%g Hz is bins %d..%d at %d Hz: NR_spectral.cpp indexes outside "
+               "its arrays unless VAD_high >= %d and VAD_low <= %d", ch, (double) nl, (double) nh, vl, vh, p->nrs_snd_rate,
+               kg_nrs::VAD_HIGH_MIN, kg_nrs::VAD_LOW_MAX);
+    post_nrs_host &sh = p->h_nrs[ch];
+    sh.norm_locut = nl; sh.norm_hicut = nh;
+    sh.vad[0] = vl; sh.vad[1] = vh;
+    if ((rc = nrs_put_vad(p, ch))) return rc;
+    KG_HIP(hipStreamSynchronize(p->ctx->stream));
+    return KG_OK;
+}
+
+int kg_post_nrs_process_dev(kg_post *p, const int32_t *chans, int nch, const void *d_in, size_t in_stride, int nsamps, void *d_out,
+                            size_t out_stride)
+{
+    KG_REQUIRE(p && chans && d_in && d_out, KG_ERR_INVALID, "kg_post_nrs_process_dev: null argument");
+    int rc = kg_ctx_use(p->ctx);
+    if (rc) return rc;
+    KG_REQUIRE(nsamps >= kg_nrs::FFT_FULL && nsamps <= KG_NRS_MAX_SAMPLES && nsamps % kg_nrs::FFT_FULL == 0 && in_stride >= (size_t) nsamps &&
+               out_stride >= (size_t) nsamps, KG_ERR_INVALID,
+               "kg_post_nrs_process_dev: nsamps %d (a multiple of %d up to %d), strides %zu / %zu", nsamps, kg_nrs::FFT_FULL,
+               KG_NRS_MAX_SAMPLES, in_stride, out_stride);
+    void *d_list = nullptr;
+    if ((rc = post_list(p, chans, nch, "kg_post_nrs_process_dev", &d_list))) return rc;
+    for (int i = 0; i < nch; i++)
+        KG_REQUIRE(p->h_nr[chans[i]].algo == KG_NR_SPECTRAL, KG_ERR_STATE,
+                   "kg_post_nrs_process_dev: channel %d: its algo is %d (kg_post_nrs_select)", chans[i], p->h_nr[chans[i]].algo);
+    KG_PLAN_ONLY(p->ctx);
+    hipLaunchKernelGGL(post_nrs_kernel<false>, dim3(nch), dim3(64), 0, p->ctx->stream, p->d_nrs, p->d_nr, p->d_chan, (const int *) d_list,
+                       p->nrs_rate, (const short *) d_in, in_stride, nsamps, (short *) d_out, out_stride, 0);
+    KG_HIP(hipGetLastError());
+    return KG_OK;
+}
+
+int kg_post_nrs_state(kg_post *p, const int32_t *chans, int nch, int32_t *ints, float *scalars, float *rate, float *arrays)
+{
+    KG_REQUIRE(p && chans && nch >= 0, KG_ERR_INVALID, "kg_post_nrs_state: null argument");
+    int rc = kg_ctx_use(p->ctx);
+    if (rc) return rc;
+    for (int i = 0; i < nch; i++) {
+        KG_REQUIRE(chans[i] >= 0 && chans[i] < p->nchan, KG_ERR_INVALID, "kg_post_nrs_state: chans[%d] = %d", i, chans[i]);
+        kg_nrs::state_t hs;
+        KG_HIP(hipMemcpyAsync(&hs, p->d_nrs + chans[i], sizeof hs, hipMemcpyDeviceToHost, p->ctx->stream));
+        KG_HIP(hipStreamSynchronize(p->ctx->stream));
+        const post_nrs_host &sh = p->h_nrs[chans[i]];
+        if (ints) { ints[4 * i] = hs.first_time; ints[4 * i + 1] = hs.init_counter; ints[4 * i + 2] = hs.vad_lo; ints[4 * i + 3] = hs.vad_hi; }
+        if (scalars) {
+            const float v[8] = {hs.par.final_gain, hs.par.alpha, hs.par.asnr, hs.par.xih1, hs.par.xih1r, hs.par.pfac, sh.norm_locut, sh.norm_hicut};
+            memcpy(scalars + 8 * (size_t) i, v, sizeof v);
+        }
+        if (arrays) memcpy(arrays + (size_t) i * NRS_ARRAYS * kg_nrs::FFT_HALF, hs.last_sample_buffer, sizeof(float) * NRS_ARRAYS * kg_nrs::FFT_HALF);
+    }
+    if (rate) memcpy(rate, &p->nrs_rate, sizeof p->nrs_rate);
     return KG_OK;
 }
 

@@ -24,6 +24,11 @@ Reference                                                              here
                                     rx/rx_sound_cmd.cpp:464-523      -> Post.set_nr_algo / set_nr_enable / set_nr_param
   the noise-reduction switch (NR_WDSP: wdsp_ANR_filter, NR_ORIG: CLMS::ProcessFilter)
                                     rx/rx_sound.cpp:933-949          -> Post.process (s16, in place), Post.nr_process, Post.nr_state
+  "SET nr algo=3", nr_spectral_init, s->norm_locut / norm_hicut
+                                    rx/rx_sound_cmd.cpp:464-471, :520, :252-266
+                                                                     -> Post.nrs_select / set_nr_param / nrs_passband / nrs_setup
+  NR_SPECTRAL: nr_spectral_process  rx/rx_sound.cpp:945-947, rx/Teensy/NR_spectral.cpp
+                                                                     -> Post.process (s16, in place), Post.nrs_process, Post.nrs_state
 """
 import ctypes as C
 
@@ -40,11 +45,42 @@ CHAN_NULL_LSB, CHAN_NULL_USB, FADE_LEVELER, DC_BLOCK = 1, 2, 4, 8    # SAM_mpara
 MAX_SAMPLES = 1024                                    # KG_POST_MAX_SAMPLES
 CFIR_AM, CFIR_DEEMP_NFM, CFIR_DEEMP_AM_SSB, CFIR_SQUELCH_HP = range(4)  # KG_CFIR_*
 CFIR_REAL_REAL, CFIR_REAL_MONO16, CFIR_MONO16_MONO16 = range(3)        # the ProcessFilter overloads
-NR_OFF, NR_WDSP, NR_ORIG, NR_SPECTRAL = range(4)      # KG_NR_* (nr_algo_e, rx/rx_noise.h:9); NR_SPECTRAL is refused
+NR_OFF, NR_WDSP, NR_ORIG, NR_SPECTRAL = range(4)      # KG_NR_* (nr_algo_e, rx/rx_noise.h:9); NR_SPECTRAL: Post.nrs_select
 NR_DENOISE, NR_AUTONOTCH = 0, 1                       # nr_type_e
 NR_DELAY, NR_BETA, NR_DECAY = 0, 1, 2                 # NR_ORIG's parameters (extensions/noise_filter/noise_filter.h)
 NR_TAPS, NR_DLY, NR_GAIN, NR_LEAKAGE = 0, 1, 2, 3     # NR_WDSP's
 NR_PARAMS = 8
+NR_S_GAIN, NR_ALPHA, NR_ASNR = 0, 1, 2                # NR_SPECTRAL's (either type index reaches the one state)
+NRS_BLOCK = 512                                       # nr_spectral_process runs on blocks of FFT_FULL samples
+NRS_ARRAYS = ("last_sample_buffer", "last_iFFT_result", "NR_Nest", "xt", "pslp", "NR_SNR_post", "NR_SNR_prio", "NR_Hk_old", "NR_G")
+NRS_VAD_HIGH_MIN, NRS_VAD_LOW_MAX = 17, 244           # the passbands NR_spectral.cpp's smoothing loops stay inside their arrays on
+
+
+def nrs_norm_passband(locut, hicut):
+    """rx_sound_cmd.cpp:252-266 from the clamped cuts -> (norm_locut, norm_hicut) as float32"""
+    locut, hicut = float(locut), float(hicut)
+    if locut <= 0 and hicut >= 0:
+        return np.float32(0.0), np.float32(max(-locut, hicut))
+    if locut > 0:
+        return np.float32(locut), np.float32(hicut)
+    return np.float32(-hicut), np.float32(-locut)
+
+
+def nrs_vad_bins(norm_locut, norm_hicut, snd_rate):
+    """NR_spectral.cpp:214-238 -> (VAD_low, VAD_high); float32 arithmetic as there"""
+    binw = np.float32(snd_rate) / np.float32(512)
+    lo = int(np.floor(np.float32(norm_locut) / binw))
+    hi = int(np.ceil(np.float32(norm_hicut) / binw))
+    if lo == hi:
+        hi += 1
+    lo = 1 if lo < 1 else min(lo, 254)
+    hi = 2 if hi < 2 else min(hi, 256)
+    return lo, hi
+
+
+def nrs_passband_ok(locut, hicut, snd_rate):
+    lo, hi = nrs_vad_bins(*nrs_norm_passband(locut, hicut), snd_rate)
+    return hi >= NRS_VAD_HIGH_MIN and lo <= NRS_VAD_LOW_MAX
 
 
 class Post:
@@ -153,6 +189,59 @@ class Post:
             r.update(anr_w=np.zeros((n, 512), np.float32), lms_coef=np.zeros((n, 121), np.float32))
         check(self.lib.kg_post_nr_state(self.h, ptr(chans), n, int(nr_type), ptr(r["anr_i"]), ptr(r["anr_f"]), ptr(r["lms_i"]),
                                         ptr(r.get("anr_w")), ptr(r.get("lms_coef"))), "kg_post_nr_state")
+        return r
+
+    # ---- NR_SPECTRAL (rx/Teensy/NR_spectral.cpp) ----
+    def nrs_select(self, ch):
+        """`SET nr algo=3`: NR_SPECTRAL, both enables cleared.  Refused while the channel's passband (nrs_passband) is one on which
+        the reference indexes outside its arrays.  Any set_nr_algo afterwards leaves it."""
+        check(self.lib.kg_post_nrs_select(self.h, int(ch)), "kg_post_nrs_select")
+
+    def nrs_setup(self, snd_rate):
+        """the reference's snd_rate for NR_SPECTRAL (tinc .. ap, the bin width): 12000 until called"""
+        check(self.lib.kg_post_nrs_setup(self.h, int(snd_rate)), "kg_post_nrs_setup")
+
+    def nrs_passband(self, ch, locut, hicut):
+        """s->norm_locut / norm_hicut from the clamped cuts of `SET mod= low_cut= high_cut=`"""
+        check(self.lib.kg_post_nrs_passband(self.h, int(ch), float(locut), float(hicut)), "kg_post_nrs_passband")
+
+    def nrs_process_dev(self, chans, d_in, in_stride, nsamps, d_out, out_stride=None):
+        chans = np.ascontiguousarray(chans, np.int32)
+        check(self.lib.kg_post_nrs_process_dev(self.h, ptr(chans), chans.size, ptr(int(d_in)), int(in_stride), int(nsamps),
+                                               ptr(int(d_out)), int(out_stride if out_stride is not None else nsamps)),
+              "kg_post_nrs_process_dev")
+
+    def nrs_process(self, chans, x, in_place=True):
+        """x: int16 [len(chans), n] (host), n a multiple of 512.  -> int16 [len(chans), n]: nr_spectral_process per 512 samples"""
+        own_rows(self, "nrs_process()")
+        chans = np.ascontiguousarray(chans, np.int32)
+        x = np.ascontiguousarray(x, np.int16).reshape(chans.size, -1)
+        n = x.shape[1]
+        y = np.empty_like(x)
+        ctx = self.ctx
+        b = ctx.alloc(x.nbytes)
+        o = b if in_place else ctx.alloc(x.nbytes)
+        try:
+            ctx.upload(b, x)
+            self.nrs_process_dev(chans, b, n, n, o, n)
+            ctx.sync()
+            ctx.download(o, y)
+        finally:
+            ctx.free(b)
+            if not in_place:
+                ctx.free(o)
+        return y
+
+    def nrs_state(self, chans):
+        """-> dict: ints int32[n, 4] (first_time, init_counter, VAD_low, VAD_high), scalars float32[n, 8] (final_gain, alpha, asnr,
+        xih1, xih1r, pfac, norm_locut, norm_hicut), rate float32[6] (tinc, tax, tap, ax, ap, snr_prio_min), arrays float32[n, 9, 256]
+        in NRS_ARRAYS' order"""
+        chans = np.ascontiguousarray(chans, np.int32)
+        n = chans.size
+        r = dict(ints=np.zeros((n, 4), np.int32), scalars=np.zeros((n, 8), np.float32), rate=np.zeros(6, np.float32),
+                 arrays=np.zeros((n, 9, 256), np.float32))
+        check(self.lib.kg_post_nrs_state(self.h, ptr(chans), n, ptr(r["ints"]), ptr(r["scalars"]), ptr(r["rate"]), ptr(r["arrays"])),
+              "kg_post_nrs_state")
         return r
 
     def cfir_init_lp(self, ch, which, numtaps, scale, astop, fpass, fstop, fs):

@@ -145,6 +145,13 @@ class RxBank:
         self.post.set_sam_mparam(rx, sam_mparam)
         self.post.set_mode(rx, mode)
         self.post.reset(rx)
+        # s->norm_locut / norm_hicut of the same command (rx_sound_cmd.cpp:252-266), which NR_SPECTRAL's passband bins follow; the
+        # stage's snd_rate is one per kg_post (the reference's is a global): the nominal rate nearest fs
+        nominal = 12000 if abs(fs - 12000.0) < abs(fs - 20250.0) else 20250
+        if getattr(self, "_nrs_rate", 12000) != nominal:
+            self.post.nrs_setup(nominal)
+            self._nrs_rate = nominal
+        self.post.nrs_passband(rx, lo, hi)
         self.post.squelch_setup(rx, fs)
         self.post.squelch_set(rx, 0, 0)
         if squelch:
@@ -177,8 +184,13 @@ class RxBank:
     def set_nr(self, rx, algo, params=None, enable=(0, 0)):
         """The noise-reduction commands for receiver rx as a client sends them (rx/rx_sound_cmd.cpp:464-523): `SET nr algo=`, then
         every parameter one at a time (params: {type: [value of param 0, 1, ...]}), then the enables (denoise, auto-notch).  Call it
-        after set_audio, whose connection start clears them (post.NR_* constants)."""
-        self.post.set_nr_algo(rx, algo)
+        after set_audio, whose connection start clears them (post.NR_* constants).  post.NR_SPECTRAL (`SET nr algo=3`) is selected
+        through Post.nrs_select: its parameters (gain, alpha, active SNR) go through either type, its enables are not consulted, and
+        it is refused on a passband (set_audio's lo / hi) on which the reference indexes outside its arrays."""
+        if algo == post_mod.NR_SPECTRAL:
+            self.post.nrs_select(rx)
+        else:
+            self.post.set_nr_algo(rx, algo)
         for t, vals in (params or {}).items():
             for k, v in enumerate(vals):
                 self.post.set_nr_param(rx, t, k, v)

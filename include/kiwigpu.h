@@ -537,8 +537,8 @@ int kg_post_process_dev(kg_post *post, const int32_t *chans, int nch, const void
                         int nsamps, void *d_s16, void *d_demod, void *d_agc, size_t out_stride);
 /* The noise-reduction switch of c2s_sound() (rx/rx_sound.cpp:933-949), after the de-emphasis filter and the NBFM squelch, in place
  * on out_samps_s2 of every mode but the stereo ones (KG_POST_IQ, KG_POST_SAS, KG_POST_QAM): the auto-notch first, then the denoiser,
- * each when enabled.  Two of the reference's three algorithms: NR_WDSP, wdsp's variable-leak LMS (rx/wdsp/ANR.cpp), and NR_ORIG,
- * the 121-tap LMS (rx/kiwi/lms.cpp), bit for bit.  kg_post_process_dev runs it over its d_s16 rows for every listed channel whose
+ * each when enabled.  The two LMS algorithms: NR_WDSP, wdsp's variable-leak LMS (rx/wdsp/ANR.cpp), and NR_ORIG,
+ * the 121-tap LMS (rx/kiwi/lms.cpp), bit for bit (the third, NR_SPECTRAL, has calls of its own below: kg_post_nrs_*).  kg_post_process_dev runs it over its d_s16 rows for every listed channel whose
  * algo is KG_NR_WDSP or KG_NR_ORIG with a type enabled; such a batch needs d_s16 (NULL is refused with KG_ERR_INVALID: the
  * filter states must advance as the reference's do).  A batch with no such channel launches what it launched before. */
 enum { KG_NR_OFF = 0, KG_NR_WDSP = 1, KG_NR_ORIG = 2, KG_NR_SPECTRAL = 3 };     /* nr_algo_e, rx/rx_noise.h:9 */
@@ -557,7 +557,7 @@ enum { KG_NR_DELAY = 0, KG_NR_BETA = 1, KG_NR_DECAY = 2,                        
  * (rx_sound.cpp:236-240).  A fresh object's filters are zeroed, as the reference's statics start: an enabled filter that was never
  * initialised runs as that zero state does (a never-initialised CLMS is a denoiser in either slot).
  * Refused with KG_ERR_INVALID, the inputs on which the reference is undefined or which are not implemented:
- *   KG_NR_SPECTRAL (out of scope: it runs over its own transform);
+ *   KG_NR_SPECTRAL in kg_post_set_nr_algo (it is selected by kg_post_nrs_select, which carries its passband rule);
  *   a type other than KG_NR_DENOISE / KG_NR_AUTONOTCH (m_LMS[ch][2] is out of bounds);
  *   a param index outside 0..7;
  *   under KG_NR_WDSP, a vector whose taps or delay is NaN, infinite or outside int (the (int) conversion), taps > 512 (overruns
@@ -576,6 +576,42 @@ int kg_post_nr_process_dev(kg_post *post, const int32_t *chans, int nch, int typ
  * m_lmscoef[].  Synchronises. */
 int kg_post_nr_state(kg_post *post, const int32_t *chans, int nch, int type, int32_t *anr_i, float *anr_f, int32_t *lms_i,
                      float *anr_w, float *lms_coef);
+/* NR_SPECTRAL, the third algorithm of that switch (rx/rx_sound.cpp:945-947 -> rx/Teensy/NR_spectral.cpp, the UHSDR spectral-weighting
+ * denoiser): per 512 samples two 50 %-overlapped 512-point frames, each windowed, transformed (CMSIS arm_cfft_f32, radix 8), weighted
+ * per passband bin and transformed back; the output lags the input by 256 samples.  Bit for bit against the reference's code run with
+ * the transform tables of DESIGN.md ("Spectral noise reduction": the reference tree declares them and defines them nowhere).  It runs
+ * whenever the algo is KG_NR_SPECTRAL and the mode is not a stereo one; the enables are not consulted (:945-947).  One state per
+ * channel (nr_spectral[], NR_spectral.cpp:69), kept across algo switches, modes and connections like the LMS states; a state that
+ * was never initialised is all zeros and runs as such (final_gain 0: silence), as in the reference.
+ * kg_post_nrs_select: `SET nr algo=3` (rx_sound_cmd.cpp:464-471): algo = KG_NR_SPECTRAL, both enables cleared, no state touched.  Any
+ *   kg_post_set_nr_algo afterwards leaves it; kg_post_reset returns to KG_NR_OFF, zeroes the passband (memset(s)) and keeps the state.
+ * kg_post_set_nr_param under KG_NR_SPECTRAL (:520): stores the value and runs nr_spectral_init from that type's whole stored vector
+ *   (KG_NRS_GAIN, KG_NRS_ALPHA, KG_NRS_ASNR; either type index re-parameterises the one state); the first one per channel also
+ *   arms the start-up phase (first_time = 1) and seeds four arrays (NR_spectral.cpp:85-101).
+ * kg_post_nrs_setup: the reference's global snd_rate as this stage sees it: tinc .. ap (NR_spectral.cpp:89-93, host libm) and the bin
+ *   width of the passband.  One value per object (the reference's are file-scope); 12000 until called.
+ * kg_post_nrs_passband: s->norm_locut / norm_hicut as rx_sound_cmd.cpp:252-266 forms them from the clamped cuts of `SET mod=
+ *   low_cut= high_cut=` (:248-250); VAD_low / VAD_high follow (NR_spectral.cpp:214-238).  kg_post_set_am_passband is unchanged.
+ * The passband rule: NR_spectral.cpp's smoothing loops (:284-314) index NR_G[] down to VAD_high - 2 NN + 1 and up to VAD_low + NN/2
+ *   + NN - 2 with a data-dependent NN <= 9, i.e. outside the arrays unless VAD_high >= 17 and VAD_low <= 244 (at 12 kHz: a
+ *   norm_hicut above about 375 Hz).  The command that would put a KG_NR_SPECTRAL channel on such a passband is refused with
+ *   KG_ERR_INVALID and the previous setting kept: kg_post_nrs_select, kg_post_nrs_passband, kg_post_nrs_setup.
+ * kg_post_process_dev runs the stage over its d_s16 rows for every listed channel with KG_NR_SPECTRAL in a mono mode; such a batch
+ *   needs d_s16 and nsamps % 512 == 0 (KG_ERR_INVALID, nothing enqueued).  A batch without such a channel launches what it launched before. */
+enum { KG_NRS_MAX_SAMPLES = 4096 };                              /* kg_post_nrs_process_dev: at most eight blocks a call */
+enum { KG_NRS_GAIN = 0, KG_NRS_ALPHA = 1, KG_NRS_ASNR = 2 };      /* NR_S_GAIN, NR_ALPHA, NR_ASNR, extensions/noise_filter/noise_filter.h:24-26 */
+int kg_post_nrs_select(kg_post *post, int chan);
+int kg_post_nrs_setup(kg_post *post, int snd_rate);
+int kg_post_nrs_passband(kg_post *post, int chan, double locut, double hicut);
+/* The standalone call site: nr_spectral_process(ch, 512, ...) once per 512 samples of row i of d_in -> row i of d_out (d_in == d_out
+ * allowed) for each listed channel (its algo must be KG_NR_SPECTRAL, else KG_ERR_STATE), whatever its mode.  nsamps: a positive
+ * multiple of 512 (the reference asserts 512) up to KG_NRS_MAX_SAMPLES, else KG_ERR_INVALID.  The same device code as the fused pass.  Enqueue only. */
+int kg_post_nrs_process_dev(kg_post *post, const int32_t *chans, int nch, const void *d_in, size_t in_stride, int nsamps, void *d_out,
+                            size_t out_stride);
+/* The states of the listed channels, any output may be NULL: ints[4 i ..] = first_time, init_counter, VAD_low, VAD_high;
+ * scalars[8 i ..] = final_gain, alpha, asnr, xih1, xih1r, pfac, norm_locut, norm_hicut; rate[6] = tinc, tax, tap, ax, ap, snr_prio_min;
+ * arrays[9 * 256 i ..] = last_sample_buffer, last_iFFT_result, NR_Nest, xt, pslp, NR_SNR_post, NR_SNR_prio, NR_Hk_old, NR_G.  Synchronises. */
+int kg_post_nrs_state(kg_post *post, const int32_t *chans, int nch, int32_t *ints, float *scalars, float *rate, float *arrays);
 /* The CFir objects of a channel (rx/rx_sound.cpp:153-156; rx/CuteSDR/fir.cpp): the filter behind the AM detector and the
  * two de-emphasis filters.  (CSquelch owns a fourth, its noise high-pass: kg_post_squelch_setup.) */
 enum { KG_CFIR_AM = 0, KG_CFIR_DEEMP_NFM = 1, KG_CFIR_DEEMP_AM_SSB = 2,

@@ -1,5 +1,6 @@
 """Randomised differential soak: many random configurations of every stateful module through the
-C ABI against the oracle (bit-exact where the module is integer, the module's bar otherwise).
+C ABI against the oracle (bit-exact where the module is integer, the module's bar otherwise); `nrs`, the spectral noise
+reduction, against its host driver (tools/nrs_host_driver.cpp), bit-exact.
 usage: python tools/fuzz_parity.py [seconds per module] [seed] [module name: only that one]
 A failing `post` trial leaves its story (mode, parameter sets, inputs) in gpurun_out/fuzz_fail_post_<k>.npz."""
 import os
@@ -443,7 +444,76 @@ def trial_rxbank():
         bank.close()
 
 
-for name, fn in (("rxbank", trial_rxbank), ("tail", trial_tail), ("acq", trial_acq), ("wf ddc", trial_wfddc), ("rx ddc", trial_rxddc), ("fastfir", trial_fir), ("post", trial_post), ("wire", trial_wire), ("wf frames", trial_wf)):
+_nrs = {}
+
+
+def trial_nrs():
+    """NR_SPECTRAL: a random script (rate, passbands, parameters through either type, algo switches, a new connection, stereo and
+    zero blocks, calls of 1..4 blocks) through tools/nrs_host_driver.cpp (csrc/kg_nrs.h on the host) and through
+    kg_post_nrs_process_dev: every output sample and every state value equal."""
+    import tempfile
+    from tests import nrs_common as nc
+    if not _nrs:
+        _nrs["tmp"] = tempfile.mkdtemp(prefix="nrs_fuzz")
+        _nrs["exe"] = nc.build_driver(_nrs["tmp"])
+    rate = int(rng.choice([12000, 20250]))
+    fmax = rate // 2 - 1
+
+    def passband():
+        while True:
+            lo, hi = sorted(float(np.rint(v)) for v in rng.uniform(-fmax, fmax, 2))
+            if rng.random() < 0.3:
+                lo, hi = -hi if hi > 0 else lo, abs(hi)
+            if lo < hi and post.nrs_passband_ok(lo, hi, rate):
+                return "M %g %g" % (lo, hi)
+    lines = [passband(), "A 3"]
+    nb = int(rng.integers(8, 48))
+    for b in range(nb):
+        r = rng.random()
+        if r < 0.12 or b == 0:
+            lines.append("P %d %d %.9g" % (rng.integers(0, 2), rng.integers(0, 3),
+                                           [10 ** rng.uniform(-1.5, 1.5), rng.uniform(0.9, 0.99), 10 ** rng.uniform(0.2, 3)][int(rng.integers(0, 3))]))
+        elif r < 0.16:
+            lines.append(passband())
+        elif r < 0.19:
+            lines += ["A %d" % rng.integers(0, 3), "B 512 0", "A 3"]
+        elif r < 0.21:
+            lines += ["C", passband(), "A 3"]
+        lines.append("B 512 %d" % (rng.random() < 0.05))
+    lines.append("S")
+    nblk = sum(1 for l in lines if l[0] == "B")
+    x = np.concatenate([adc_block(512) if rng.random() > 0.08 else np.zeros(512, np.int16) for _ in range(nblk)])
+    want, wst, _, rc = nc.run_driver(_nrs["exe"], rate, lines, x, _nrs["tmp"])
+    assert rc == 0, ("host driver", rc, lines)
+    P = Post(ctx, nchan=2)
+    try:
+        P.nrs_setup(rate)
+        r = nc.Replay(P, 1, lines, x)
+        while True:
+            nxt = r.step()
+            if nxt is None:
+                break
+            if not nxt[1]:
+                r.done(nxt[0])
+                continue
+            run = [nxt[0]]
+            k = int(rng.integers(1, 5))
+            while len(run) < k and r.peek_is_block():
+                run.append(r.step()[0])
+            r.done(P.nrs_process([1], np.concatenate(run)[None, :], in_place=bool(rng.integers(0, 2)))[0])
+        y = r.output()
+        bad = np.flatnonzero(y != want)
+        assert bad.size == 0, ("nrs output", rate, bad.size, bad[:4], lines)
+        iv, fv, arr = wst[-1]
+        st = r.states[-1]
+        assert list(st["ints"][0, :2]) == list(iv), ("nrs first_time / init_counter", st["ints"][0], iv, lines)
+        for a in range(9):
+            assert nc.fdigest(st["arrays"][0, a]) == nc.fdigest(arr[a]), ("nrs state", nc.ARRAYS[a], lines)
+    finally:
+        P.close()
+
+
+for name, fn in (("nrs", trial_nrs), ("rxbank", trial_rxbank), ("tail", trial_tail), ("acq", trial_acq), ("wf ddc", trial_wfddc), ("rx ddc", trial_rxddc), ("fastfir", trial_fir), ("post", trial_post), ("wire", trial_wire), ("wf frames", trial_wf)):
     soak(name, fn)
 print("failures:", fails)
 if _acq:
