@@ -104,6 +104,7 @@ SYMBOLS = {
     "kg_nb_state": (_i, [_vp, _vp, _i, _vp, _vp]),
     "kg_rxbank_nb": (_vp, [_vp]),
     "kg_rxbank_set_nb_algo": (_i, [_vp, _i, _i]),
+    "kg_rxbank_nbw_select": (_i, [_vp, _i]),
     "kg_rxbank_set_nb_enable": (_i, [_vp, _i, _i, _i]),
     "kg_rxbank_set_nb_param": (_i, [_vp, _i, _i, _i, C.c_float, C.c_float]),
     "kg_rxbank_set_nb_gate": (_i, [_vp, _i, _i, _i, C.c_float]),
@@ -162,6 +163,10 @@ SYMBOLS = {
     "kg_post_nrs_passband": (_i, [_vp, _i, C.c_double, C.c_double]),
     "kg_post_nrs_process_dev": (_i, [_vp, _vp, _i, _vp, _sz, _i, _vp, _sz]),
     "kg_post_nrs_state": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "kg_post_nbw_init": (_i, [_vp, _i, _vp]),
+    "kg_post_set_nbw": (_i, [_vp, _i, _i]),
+    "kg_post_nbw_process_dev": (_i, [_vp, _vp, _i, _vp, _sz, _i, _vp, _sz]),
+    "kg_post_nbw_state": (_i, [_vp, _vp, _i, _vp, _vp]),
     "kg_post_cfir_init_lp": (_i, [_vp, _i, _i, _i, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float]),
     "kg_post_cfir_init_const": (_i, [_vp, _i, _i, _i, _vp, C.c_float]),
     "kg_post_cfir_get_taps": (_i, [_vp, _i, _i, _vp]),

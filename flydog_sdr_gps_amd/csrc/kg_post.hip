@@ -46,11 +46,15 @@
 //     store address, the inverse's conjugate and scale a sign at the first load and a factor at the last store.  The per-bin
 //     expressions (kg_nrs.h, shared with the host driver) run four bins per lane; the two ordered sums pre_power / post_power are
 //     walked by every lane over LDS; each smoothed gain is its own ordered sum of <= 9 terms.  Nothing is reassociated.
+//   * NB_WILD (rx/Teensy/NB_Wild.cpp), the noise blanker of the post-filter chain (rx_sound.cpp:922-931, ahead of the NR switch), is
+//     a kernel of its own too (post_nbw_kernel), enqueued between post_kernel and the NR kernels only for a batch that holds a
+//     channel with the stage on.  One wave per channel; its split between lanes and serial walks is at the kernel.
 #include "kg_common.h"
 #include "kg_libm.h"
 #include "kg_libm_trig.h"
 #include "kg_nr.h"
 #include "kg_nrs.h"
+#include "kg_nbw.h"
 #include "kg_tables.h"
 
 #include <math.h>
@@ -871,6 +875,86 @@ __global__ void post_nrs_vad_kernel(kg_nrs::state_t *tab, int nchan, int vad_lo,
     if (ch < nchan) { tab[ch].vad_lo = vad_lo; tab[ch].vad_hi = vad_hi; }
 }
 
+// ---- NB_WILD (rx/rx_sound.cpp:922-931 -> rx/Teensy/NB_Wild.cpp) ----
+// kFused: the stage of c2s_sound() behind post_kernel (de-emphasis) and ahead of the NR kernels, over d_s16 rows in place, for the
+// listed channels whose switch is on and whose mode is not a stereo one (the others return at once).  !kFused:
+// kg_post_nbw_process_dev.  n is a multiple of 512: nb_Wild_process(ch, 512, ...) once per 512 samples.
+// One wave per channel.  Across lanes: the order + 1 autocorrelation lags (a lane walks its own 512 - i terms in order), the two FIR
+// passes (one output per lane and step, its taps in order), the copies and a repair's blend.  Serial, because the arithmetic chains:
+// Levinson-Durbin (lane 0), the variance's two 512-term sums (every lane walks them, the reads are broadcasts), the scan (the
+// threshold tests run across lanes into eight 64-bit words; the walk over them, which skips PL samples behind a hit and stops at 20,
+// is serial and every lane makes it), and per hit, in hit order, the forward prediction on lane 0 beside the backward one on lane 1
+// (each step feeds the next).
+template <bool kFused>
+__global__ __launch_bounds__(64) void post_nbw_kernel(kg_nbw::state_t *__restrict__ tab, const post_chan *__restrict__ chan_tab,
+                                                      const int *__restrict__ chans, const short *in, size_t in_stride, int n, short *out,
+                                                      size_t out_stride, int by_chan)
+{
+    using namespace kg_nbw;
+    __shared__ float WB[DIM_WBUF], T1[BLOCK], T2[BLOCK];
+    __shared__ float R[MAX_ORDER + 1], LP[MAX_ORDER + 1], RL[MAX_ORDER + 1], ANY[MAX_ORDER + 1], NLP[MAX_ORDER], NRL[MAX_ORDER];
+    __shared__ float RFW[MAX_IMPULSE_LEN + MAX_ORDER], RBW[MAX_IMPULSE_LEN + MAX_ORDER];
+    __shared__ int POS[N_IMPULSE_COUNT];
+    __shared__ unsigned long long FL[BLOCK / 64];
+    const int lane = threadIdx.x, ch = chans[blockIdx.x];
+    state_t *s = tab + ch;
+    if (kFused && (!s->on || post_is_stereo(chan_tab[ch].mode))) return;
+    const int row = kFused && by_chan ? ch : (int) blockIdx.x;
+    const short *src = in + (size_t) row * in_stride;
+    short *dst = out + (size_t) row * out_stride;
+    const float thresh = s->thresh;
+    // the host admits the stage only on a usable vector; the clamps keep every index inside the arrays whatever the table holds
+    const int order = min(max(s->taps, 1), (int) MAX_ORDER);
+    const int il = impulse_length(min(max(s->impulse_samples, 2), (int) MAX_IMPULSE_LEN)), PL = half_length(il);
+    const int hist = 2 * PL + 2 * order;
+    const float *x = WB + order + PL;
+    for (int i = lane; i < hist; i += 64) WB[i] = s->hist[i];
+    for (int b = 0; b < n / BLOCK; b++) {
+        for (int i = lane; i < BLOCK; i += 64) WB[hist + i] = (float) src[b * BLOCK + i];                 // :258, :91
+        __syncthreads();
+        if (lane <= order) R[lane] = autocorr(x, lane, BLOCK);                                              // :102-109
+        __syncthreads();
+        if (lane == 0) levinson((float *) R, order, (float *) LP, (float *) RL, (float *) ANY);            // :111-143
+        __syncthreads();
+        for (int i = lane; i < BLOCK; i += 64) T1[i] = fir_sample(x, i, RL, order + 1);                     // :149
+        __syncthreads();
+        for (int i = lane; i < BLOCK; i += 64) T2[i] = fir_sample(T1, i, LP, order + 1);                    // :155
+        if (lane < order) { NLP[lane] = -LP[1 + lane]; NRL[lane] = -RL[lane]; }                             // :187-188
+        __syncthreads();
+        const float sigma2 = variance(T2, BLOCK), lpc_power = power(LP, order);                             // :157-158
+        const float impulse_threshold = threshold(thresh, sigma2, lpc_power);                               // :160
+        for (int q = 0; q < BLOCK / 64; q++) {                                                              // :167 for every sample
+            const unsigned long long m = __ballot(over(T2[lane + 64 * q], impulse_threshold));
+            if (lane == 0) FL[q] = m;
+        }
+        __syncthreads();
+        int count = scan_flags(FL, order, PL, BLOCK, POS);                      // :162-176 (every lane stores the same positions)
+        count = __builtin_amdgcn_readfirstlane(count);                                                      // (every lane counted the same)
+        __syncthreads();
+        for (int j = 0; j < count; j++) {                                                                   // :193-235, in hit order
+            const int pos = POS[j];
+            if (lane < order) {
+                RFW[lane] = WB[fw_base(pos, lane)];
+                RBW[il + lane] = WB[bw_base(pos, lane, order, PL)];
+            }
+            __syncthreads();
+            if (lane == 0) predict_fw((float *) RFW, NRL, order, il);
+            else if (lane == 1) predict_bw((float *) RBW, NLP, order, il);
+            __syncthreads();
+            if (lane < il) WB[repair_base(pos, order) + lane] = blend(RFW[order + lane], RBW[lane], lane, il);
+            __syncthreads();
+        }
+        for (int i = lane; i < BLOCK; i += 64) dst[b * BLOCK + i] = out_sample(x[i]);                       // :239, :260
+        __syncthreads();
+        float carry[2];
+        for (int q = 0; q < 2; q++) carry[q] = lane + 64 * q < hist ? WB[BLOCK + lane + 64 * q] : 0.0f;    // :242
+        __syncthreads();
+        for (int q = 0; q < 2; q++) if (lane + 64 * q < hist) WB[lane + 64 * q] = carry[q];
+        __syncthreads();
+    }
+    for (int i = lane; i < hist; i += 64) s->hist[i] = WB[i];
+}
+
 __global__ void post_reset_rings_kernel(float2 *ring_in, float *ring_mag, int ch0)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x, ch = ch0 + blockIdx.y;
@@ -920,6 +1004,8 @@ struct kg_post {
     std::vector<post_nrs_host> h_nrs;
     int nrs_snd_rate;                    // the reference's global snd_rate as NR_SPECTRAL sees it (kg_post_nrs_setup; 12000 at create)
     kg_nrs::rate_t nrs_rate;             // tinc .. ap, snr_prio_min at that rate
+    kg_nbw::state_t *d_nbw;              // [nchan]: nb_Wild[] (NB_Wild.cpp:36) and the stage's switch
+    std::vector<kg_nbw::state_t> h_nbw;  // thresh, taps, impulse_samples and the switch (hist is the device's)
     kg_stage_cache list_cache = {};      // the channel list of the last process call
 };
 
@@ -1138,6 +1224,19 @@ static int nrs_put_vad(kg_post *p, int ch)         // VAD_low / VAD_high to the 
     return KG_OK;
 }
 
+static_assert(KG_NBW_HIST == kg_nbw::HIST_MAX && KG_NB_PARAMS == kg_nr::NPARAMS, "kiwigpu.h and kg_nbw.h disagree");
+static bool nbw_active(const kg_nbw::state_t &h, int mode)
+{
+    return h.on && mode != KG_POST_IQ && mode != KG_POST_SAS && mode != KG_POST_QAM;
+}
+
+static int nbw_put_on(kg_post *p, int ch, int on)  // the stage's switch to the device (h_nbw is stable storage; the caller synchronises)
+{
+    p->h_nbw[ch].on = on;
+    KG_HIP(hipMemcpyAsync(&p->d_nbw[ch].on, &p->h_nbw[ch].on, sizeof(int), hipMemcpyHostToDevice, p->ctx->stream));
+    return KG_OK;
+}
+
 static int nr_put_ctl(kg_post *p, int ch)          // s->nr_algo and s->nr_enable[] to the device
 {
     const post_nr_host &h = p->h_nr[ch];
@@ -1179,6 +1278,11 @@ int kg_post_create(kg_ctx *ctx, int nchan, kg_post **out)
     p->h_nrs.assign(nchan, sh);
     hipLaunchKernelGGL(post_nrs_vad_kernel, dim3((nchan + 255) / 256), dim3(256), 0, ctx->stream, p->d_nrs, nchan, sh.vad[0], sh.vad[1]);
     KG_HIP(hipGetLastError());
+    KG_HIP(hipMalloc((void **) &p->d_nbw, sizeof(kg_nbw::state_t) * (size_t) nchan));
+    KG_HIP(hipMemsetAsync(p->d_nbw, 0, sizeof(kg_nbw::state_t) * (size_t) nchan, ctx->stream));     // the zeroed static nb_Wild[]
+    kg_nbw::state_t wh;
+    memset(&wh, 0, sizeof wh);
+    p->h_nbw.assign(nchan, wh);
     post_sam w;                                     // a new connection at snd_rate 12000: PLL(MED), PLL(RESET) (rx_sound.cpp:302-303)
     memset(&w, 0, sizeof w);
     sam_init_consts(w, 12000);
@@ -1218,7 +1322,7 @@ void kg_post_destroy(kg_post *p)
     (void) hipSetDevice(p->ctx->device);
     (void) hipStreamSynchronize(p->ctx->stream);
     (void) hipFree(p->d_chan); (void) hipFree(p->d_ring_in); (void) hipFree(p->d_ring_mag); (void) hipFree(p->d_cfir);
-    (void) hipFree(p->d_sam); (void) hipFree(p->d_nr); (void) hipFree(p->d_nrs);
+    (void) hipFree(p->d_sam); (void) hipFree(p->d_nr); (void) hipFree(p->d_nrs); (void) hipFree(p->d_nbw);
     kg_stage_cache_free(&p->list_cache);
     delete p;
 }
@@ -1445,6 +1549,7 @@ int kg_post_reset(kg_post *p, int ch)
     sh.norm_locut = sh.norm_hicut = 0.f;
     kg_nrs::vad_bins(0.f, 0.f, p->nrs_snd_rate, sh.vad[0], sh.vad[1]);
     if ((rc = nrs_put_vad(p, ch))) return rc;
+    if ((rc = nbw_put_on(p, ch, 0))) return rc;     // memset(s) zeroes nb_enable[]; nb_Wild[ch] stays
     KG_HIP(hipStreamSynchronize(p->ctx->stream));
     return KG_OK;
 }
@@ -1461,7 +1566,7 @@ int kg_post_process_dev(kg_post *p, const int32_t *chans, int nch, const void *d
     KG_REQUIRE(in_stride >= (size_t) nsamps && out_stride >= (size_t) nsamps, KG_ERR_INVALID,
                "kg_post_process_dev: stride smaller than nsamps");
     std::vector<char> seen(p->nchan, 0);
-    bool any_sam = false, any_nr = false, any_nrs = false;
+    bool any_sam = false, any_nr = false, any_nrs = false, any_nbw = false;
     for (int i = 0; i < nch; i++) {
         KG_REQUIRE(chans[i] >= 0 && chans[i] < p->nchan && !seen[chans[i]], KG_ERR_INVALID,
                    "kg_post_process_dev: chans[%d] = %d out of range or listed twice", i, chans[i]);
@@ -1480,7 +1585,11 @@ int kg_post_process_dev(kg_post *p, const int32_t *chans, int nch, const void *d
         any_sam |= post_is_sam(mode);
         any_nr |= nr_active(p->h_nr[ch], mode);
         any_nrs |= nrs_active(p->h_nr[ch], mode);
+        any_nbw |= nbw_active(p->h_nbw[ch], mode);
     }
+    KG_REQUIRE(!any_nbw || (d_s16 && nsamps % kg_nbw::BLOCK == 0), KG_ERR_INVALID,
+               "kg_post_process_dev: a listed channel has the Wild noise blanker on, which runs over d_s16 on blocks of %d samples: "
+               "d_s16 %s, nsamps %d", kg_nbw::BLOCK, d_s16 ? "given" : "NULL", nsamps);
     KG_REQUIRE(!(any_nr || any_nrs) || d_s16, KG_ERR_INVALID,
                "kg_post_process_dev: a listed channel has noise reduction on, and it runs over d_s16: d_s16 must not be NULL");
     KG_REQUIRE(!any_nrs || nsamps % kg_nrs::FFT_FULL == 0, KG_ERR_INVALID,
@@ -1495,6 +1604,11 @@ int kg_post_process_dev(kg_post *p, const int32_t *chans, int nch, const void *d
                        p->d_ring_in, p->d_ring_mag, (const int *) d_list, (const float2 *) d_fir, in_stride, nsamps,
                        (short *) d_s16, (float *) d_demod, (float2 *) d_agc, out_stride, p->ctx->rows_by_chan);
     KG_HIP(hipGetLastError());
+    if (any_nbw) {                                  // rx_sound.cpp:922-931 over the rows just written, ahead of the NR switch
+        hipLaunchKernelGGL(post_nbw_kernel<true>, dim3(nch), dim3(64), 0, st, p->d_nbw, p->d_chan, (const int *) d_list,
+                           (const short *) d_s16, out_stride, nsamps, (short *) d_s16, out_stride, p->ctx->rows_by_chan);
+        KG_HIP(hipGetLastError());
+    }
     // rx_sound.cpp:933-949 over the rows just written, only for a batch that holds a channel with NR on (the others return at once)
     if (any_nr) {
         hipLaunchKernelGGL(post_nr_kernel<true>, dim3(nch), dim3(64), 0, st, p->d_nr, p->d_chan, (const int *) d_list, -1,
@@ -1855,6 +1969,84 @@ int kg_post_nrs_state(kg_post *p, const int32_t *chans, int nch, int32_t *ints, 
         if (arrays) memcpy(arrays + (size_t) i * NRS_ARRAYS * kg_nrs::FFT_HALF, hs.last_sample_buffer, sizeof(float) * NRS_ARRAYS * kg_nrs::FFT_HALF);
     }
     if (rate) memcpy(rate, &p->nrs_rate, sizeof p->nrs_rate);
+    return KG_OK;
+}
+
+int kg_post_nbw_init(kg_post *p, int ch, const float *nb_param)
+{
+    int rc = post_check(p, ch, "kg_post_nbw_init");
+    if (rc) return rc;
+    KG_REQUIRE(nb_param != nullptr, KG_ERR_INVALID, "kg_post_nbw_init: null argument");
+    kg_nbw::state_t &h = p->h_nbw[ch];
+    kg_nbw::state_t v = h;
+    kg_nbw::init_params(v, nb_param);               // NB_Wild.cpp:42-44
+    KG_REQUIRE(!h.on || kg_nbw::usable(v), KG_ERR_INVALID,
+               "kg_post_nbw_init: channel %d has the stage on, and NB_Wild.cpp cannot run on thresh %g, taps %g, samples %g (thresh "
+               "finite, taps 1..%d, samples 2..%d)", ch, (double) nb_param[kg_nbw::P_THRESH], (double) nb_param[kg_nbw::P_TAPS],
+               (double) nb_param[kg_nbw::P_SAMPLES], kg_nbw::MAX_ORDER, kg_nbw::MAX_IMPULSE_LEN);
+    h.thresh = v.thresh; h.taps = v.taps; h.impulse_samples = v.impulse_samples;
+    hipStream_t st = p->ctx->stream;
+    KG_HIP(hipMemsetAsync(p->d_nbw[ch].hist, 0, sizeof h.hist, st));                        // :41, the history included
+    KG_HIP(hipMemcpyAsync(&p->d_nbw[ch], &h, offsetof(kg_nbw::state_t, hist), hipMemcpyHostToDevice, st));
+    KG_HIP(hipStreamSynchronize(st));
+    return KG_OK;
+}
+
+int kg_post_set_nbw(kg_post *p, int ch, int on)
+{
+    int rc = post_check(p, ch, "kg_post_set_nbw");
+    if (rc) return rc;
+    on = on != 0;
+    KG_REQUIRE(!on || kg_nbw::usable(p->h_nbw[ch]), KG_ERR_STATE,
+               "kg_post_set_nbw: channel %d: NB_Wild.cpp cannot run on thresh %g, taps %d, samples %d (kg_post_nbw_init first: thresh "
+               "finite, taps 1..%d, samples 2..%d)", ch, (double) p->h_nbw[ch].thresh, p->h_nbw[ch].taps, p->h_nbw[ch].impulse_samples,
+               kg_nbw::MAX_ORDER, kg_nbw::MAX_IMPULSE_LEN);
+    if ((rc = nbw_put_on(p, ch, on))) return rc;
+    KG_HIP(hipStreamSynchronize(p->ctx->stream));
+    return KG_OK;
+}
+
+int kg_post_nbw_process_dev(kg_post *p, const int32_t *chans, int nch, const void *d_in, size_t in_stride, int nsamps, void *d_out,
+                            size_t out_stride)
+{
+    KG_REQUIRE(p && chans && d_in && d_out, KG_ERR_INVALID, "kg_post_nbw_process_dev: null argument");
+    int rc = kg_ctx_use(p->ctx);
+    if (rc) return rc;
+    KG_REQUIRE(nsamps >= kg_nbw::BLOCK && nsamps <= KG_NBW_MAX_SAMPLES && nsamps % kg_nbw::BLOCK == 0 && in_stride >= (size_t) nsamps &&
+               out_stride >= (size_t) nsamps, KG_ERR_INVALID,
+               "kg_post_nbw_process_dev: nsamps %d (a multiple of %d up to %d), strides %zu / %zu", nsamps, kg_nbw::BLOCK,
+               KG_NBW_MAX_SAMPLES, in_stride, out_stride);
+    void *d_list = nullptr;
+    if ((rc = post_list(p, chans, nch, "kg_post_nbw_process_dev", &d_list))) return rc;
+    for (int i = 0; i < nch; i++)
+        KG_REQUIRE(kg_nbw::usable(p->h_nbw[chans[i]]), KG_ERR_STATE,
+                   "kg_post_nbw_process_dev: channel %d: thresh %g, taps %d, samples %d is not a vector NB_Wild.cpp can run on "
+                   "(kg_post_nbw_init)", chans[i], (double) p->h_nbw[chans[i]].thresh, p->h_nbw[chans[i]].taps,
+                   p->h_nbw[chans[i]].impulse_samples);
+    KG_PLAN_ONLY(p->ctx);
+    hipLaunchKernelGGL(post_nbw_kernel<false>, dim3(nch), dim3(64), 0, p->ctx->stream, p->d_nbw, p->d_chan, (const int *) d_list,
+                       (const short *) d_in, in_stride, nsamps, (short *) d_out, out_stride, 0);
+    KG_HIP(hipGetLastError());
+    return KG_OK;
+}
+
+int kg_post_nbw_state(kg_post *p, const int32_t *chans, int nch, int32_t *ints, float *floats)
+{
+    KG_REQUIRE(p && chans && nch >= 0, KG_ERR_INVALID, "kg_post_nbw_state: null argument");
+    int rc = kg_ctx_use(p->ctx);
+    if (rc) return rc;
+    for (int i = 0; i < nch; i++) {
+        KG_REQUIRE(chans[i] >= 0 && chans[i] < p->nchan, KG_ERR_INVALID, "kg_post_nbw_state: chans[%d] = %d", i, chans[i]);
+        kg_nbw::state_t hs;
+        KG_HIP(hipMemcpyAsync(&hs, p->d_nbw + chans[i], sizeof hs, hipMemcpyDeviceToHost, p->ctx->stream));
+        KG_HIP(hipStreamSynchronize(p->ctx->stream));
+        if (ints) { ints[3 * i] = hs.taps; ints[3 * i + 1] = hs.impulse_samples; ints[3 * i + 2] = hs.on; }
+        if (floats) {
+            float *f = floats + (size_t) i * (1 + kg_nbw::HIST_MAX);
+            f[0] = hs.thresh;
+            memcpy(f + 1, hs.hist, sizeof hs.hist);     // (an init zeroes all of it; a call writes the first 2 * order + 2 * PL)
+        }
+    }
     return KG_OK;
 }
 

@@ -332,6 +332,19 @@ static int bank_nb_check(const float *prm, float rate, const char *who)
     return KG_OK;
 }
 
+// `SET nb algo=` (rx_sound_cmd.cpp:454-462): the algo, both sides' enables cleared, no blanker state touched.  With the audio enable
+// gone the Wild stage is off whatever the new algo.
+static int bank_nb_algo(kg_rxbank *b, int rx, int algo)
+{
+    int rc = kg_post_set_nbw(b->post, rx, 0);
+    if (rc) return rc;
+    kg_rxbank::nb_cmd &c = b->nbc[rx];
+    c.algo = algo;
+    memset(c.snd_en, 0, sizeof c.snd_en);
+    memset(c.wf_en, 0, sizeof c.wf_en);
+    return KG_OK;
+}
+
 extern "C" {
 
 int kg_rxbank_set_nb_algo(kg_rxbank *b, int rx, int algo)
@@ -339,12 +352,15 @@ int kg_rxbank_set_nb_algo(kg_rxbank *b, int rx, int algo)
     int rc = bank_nb_rx(b, rx, "kg_rxbank_set_nb_algo");
     if (rc) return rc;
     KG_REQUIRE(algo == KG_NB_OFF || algo == KG_NB_STD, KG_ERR_INVALID, "kg_rxbank_set_nb_algo: algo %d (%s)", algo,
-               algo == KG_NB_WILD ? "NB_WILD is not implemented" : "not an nb_algo_e");
-    kg_rxbank::nb_cmd &c = b->nbc[rx];
-    c.algo = algo;                                                               // rx_sound_cmd.cpp:454-462
-    memset(c.snd_en, 0, sizeof c.snd_en);
-    memset(c.wf_en, 0, sizeof c.wf_en);
-    return KG_OK;
+               algo == KG_NB_WILD ? "NB_WILD is selected by kg_rxbank_nbw_select" : "not an nb_algo_e");
+    return bank_nb_algo(b, rx, algo);
+}
+
+int kg_rxbank_nbw_select(kg_rxbank *b, int rx)
+{
+    int rc = bank_nb_rx(b, rx, "kg_rxbank_nbw_select");
+    if (rc) return rc;
+    return bank_nb_algo(b, rx, KG_NB_WILD);
 }
 
 int kg_rxbank_set_nb_enable(kg_rxbank *b, int rx, int type, int en)
@@ -356,6 +372,7 @@ int kg_rxbank_set_nb_enable(kg_rxbank *b, int rx, int type, int en)
     kg_rxbank::nb_cmd &c = b->nbc[rx];
     KG_REQUIRE(!(type == KG_NB_BLANKER && en && c.algo == KG_NB_STD && !kg_nb_was_setup(b->nb, rx)), KG_ERR_STATE,
                "kg_rxbank_set_nb_enable: receiver %d's audio blanker was never set up (send its parameters first)", rx);
+    if (type == KG_NB_BLANKER && c.algo == KG_NB_WILD && (rc = kg_post_set_nbw(b->post, rx, en))) return rc;   // rx_sound.cpp:924-929
     c.snd_en[type] = en;                                                         // rx_sound_cmd.cpp:477-483
     c.wf_en[type] = en;
     return KG_OK;
@@ -377,6 +394,7 @@ int kg_rxbank_set_nb_param(kg_rxbank *b, int rx, int type, int param, float pval
     if (setup && (rc = bank_nb_check(snd, frate, "kg_rxbank_set_nb_param"))) return rc;
     if (to_wf && type == KG_NB_BLANKER && (rc = bank_nb_check(wfp, (float) KG_WF_NFFT, "kg_rxbank_set_nb_param"))) return rc;
     if (setup && (rc = kg_nb_setup(b->nb, rx, frate, snd))) return rc;           // SetupBlanker("SND", frate, ...)
+    if (type == KG_NB_BLANKER && c.algo == KG_NB_WILD && (rc = kg_post_nbw_init(b->post, rx, snd))) return rc;   // :498: nb_Wild_init
     c.snd_param[type][param] = pval;
     if (to_wf) {
         c.wf_param[type][param] = pval;
@@ -395,6 +413,8 @@ int kg_rxbank_set_nb_gate(kg_rxbank *b, int rx, int nb, int th, float frate)
     snd[KG_NB_GATE] = nb;                                                        // rx_sound_cmd.cpp:660-672
     snd[KG_NB_THRESHOLD] = th;
     if (nb && (rc = bank_nb_check(snd, frate, "kg_rxbank_set_nb_gate"))) return rc;
+    // under NB_WILD the command changes the enable and never calls nb_Wild_init: the stage keeps the vector of its last init
+    if (c.algo == KG_NB_WILD && (rc = kg_post_set_nbw(b->post, rx, nb ? 1 : 0))) return rc;
     if (nb && (rc = kg_nb_setup(b->nb, rx, frate, snd))) return rc;
     memcpy(c.snd_param[KG_NB_BLANKER], snd, sizeof snd);
     c.snd_en[KG_NB_BLANKER] = nb ? 1 : 0;

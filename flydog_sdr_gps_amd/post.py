@@ -29,6 +29,13 @@ Reference                                                              here
                                                                      -> Post.nrs_select / set_nr_param / nrs_passband / nrs_setup
   NR_SPECTRAL: nr_spectral_process  rx/rx_sound.cpp:945-947, rx/Teensy/NR_spectral.cpp
                                                                      -> Post.process (s16, in place), Post.nrs_process, Post.nrs_state
+  nb_Wild_init (`SET nb type=0 param= pval=` under NB_WILD)
+                                    rx/rx_sound_cmd.cpp:498, rx/Teensy/NB_Wild.cpp:38-46
+                                                                     -> Post.nbw_init
+  s->nb_enable[NB_BLANKER] && s->nb_algo == NB_WILD
+                                    rx/rx_sound.cpp:924-929          -> Post.set_nbw
+  NB_WILD: nb_Wild_process          rx/rx_sound.cpp:929, rx/Teensy/NB_Wild.cpp:60-261
+                                                                     -> Post.process (s16, in place), Post.nbw_process, Post.nbw_state
 """
 import ctypes as C
 
@@ -54,6 +61,14 @@ NR_S_GAIN, NR_ALPHA, NR_ASNR = 0, 1, 2                # NR_SPECTRAL's (either ty
 NRS_BLOCK = 512                                       # nr_spectral_process runs on blocks of FFT_FULL samples
 NRS_ARRAYS = ("last_sample_buffer", "last_iFFT_result", "NR_Nest", "xt", "pslp", "NR_SNR_post", "NR_SNR_prio", "NR_Hk_old", "NR_G")
 NRS_VAD_HIGH_MIN, NRS_VAD_LOW_MAX = 17, 244           # the passbands NR_spectral.cpp's smoothing loops stay inside their arrays on
+NB_THRESH, NB_TAPS, NB_SAMPLES = 0, 1, 2              # NB_WILD's parameters (extensions/noise_blank/noise_blank.h)
+NBW_BLOCK = 512                                       # nb_Wild_process runs on the call site's ns_out
+NBW_MAX_ORDER, NBW_MAX_IMPULSE_LEN, NBW_HIST = 40, 41, 120    # NB_Wild.cpp:23-24; the most a call carries to the next
+
+
+def nbw_delay(taps, impulse_samples):
+    """order + PL: by how many samples the Wild blanker's output lags its input (NB_Wild.cpp:66-68, :239)"""
+    return int(taps) + ((int(impulse_samples) | 1) - 1) // 2
 
 
 def nrs_norm_passband(locut, hicut):
@@ -243,6 +258,56 @@ class Post:
         check(self.lib.kg_post_nrs_state(self.h, ptr(chans), n, ptr(r["ints"]), ptr(r["scalars"]), ptr(r["rate"]), ptr(r["arrays"])),
               "kg_post_nrs_state")
         return r
+
+    # ---- NB_WILD (rx/Teensy/NB_Wild.cpp) ----
+    def nbw_init(self, ch, nb_param):
+        """nb_Wild_init: the state and its history zeroed, then thresh, taps, impulse_samples from nb_param (NB_THRESH, NB_TAPS,
+        NB_SAMPLES; up to NR_PARAMS values, the rest 0).  Never refused while the stage is off."""
+        v = np.zeros(NR_PARAMS, np.float32)
+        p = np.asarray(nb_param, np.float32).ravel()
+        v[:p.size] = p
+        check(self.lib.kg_post_nbw_init(self.h, int(ch), ptr(v)), "kg_post_nbw_init")
+
+    def set_nbw(self, ch, on):
+        """the stage's switch (nb_enable[NB_BLANKER] && nb_algo == NB_WILD); reset() clears it"""
+        check(self.lib.kg_post_set_nbw(self.h, int(ch), int(bool(on))), "kg_post_set_nbw")
+
+    def nbw_process_dev(self, chans, d_in, in_stride, nsamps, d_out, out_stride=None):
+        chans = np.ascontiguousarray(chans, np.int32)
+        check(self.lib.kg_post_nbw_process_dev(self.h, ptr(chans), chans.size, ptr(int(d_in)), int(in_stride), int(nsamps),
+                                               ptr(int(d_out)), int(out_stride if out_stride is not None else nsamps)),
+              "kg_post_nbw_process_dev")
+
+    def nbw_process(self, chans, x, in_place=True):
+        """x: int16 [len(chans), n] (host), n a multiple of 512.  -> int16 [len(chans), n]: nb_Wild_process per 512 samples"""
+        own_rows(self, "nbw_process()")
+        chans = np.ascontiguousarray(chans, np.int32)
+        x = np.ascontiguousarray(x, np.int16).reshape(chans.size, -1)
+        n = x.shape[1]
+        y = np.empty_like(x)
+        ctx = self.ctx
+        b = ctx.alloc(x.nbytes)
+        o = b if in_place else ctx.alloc(x.nbytes)
+        try:
+            ctx.upload(b, x)
+            self.nbw_process_dev(chans, b, n, n, o, n)
+            ctx.sync()
+            ctx.download(o, y)
+        finally:
+            ctx.free(b)
+            if not in_place:
+                ctx.free(o)
+        return y
+
+    def nbw_state(self, chans):
+        """-> dict: ints int32[n, 3] (taps, impulse_samples, the switch), thresh float32[n], hist float32[n, 120] (working_buffer's
+        head: a call writes its first 2 * order + 2 * PL, the rest is 0)"""
+        chans = np.ascontiguousarray(chans, np.int32)
+        n = chans.size
+        ints = np.zeros((n, 3), np.int32)
+        flts = np.zeros((n, 1 + NBW_HIST), np.float32)
+        check(self.lib.kg_post_nbw_state(self.h, ptr(chans), n, ptr(ints), ptr(flts)), "kg_post_nbw_state")
+        return dict(ints=ints, thresh=flts[:, 0].copy(), hist=flts[:, 1:].copy())
 
     def cfir_init_lp(self, ch, which, numtaps, scale, astop, fpass, fstop, fs):
         """CFir::InitLPFilter -> tap count"""

@@ -201,9 +201,15 @@ class RxBank:
     def set_nb(self, rx, algo, params=None, enable=(0, 0), frate=None):
         """The noise-blanker commands for receiver rx as a client sends them (rx/rx_sound_cmd.cpp:454-501): `SET nb algo=`, then the
         blanker's parameters one at a time (params: [gate_usec, threshold]), then the enables (NB_BLANKER, NB_WF).  frate: the
-        connection's audio rate (default: the bank's nominal one)."""
+        connection's audio rate (default: the bank's nominal one).  nb.NB_WILD (`SET nb algo=2`) goes through kg_rxbank_nbw_select;
+        its params are [thresh, taps, impulse_samples] (post.NB_THRESH ..), every message runs nb_Wild_init, and enabling NB_BLANKER
+        switches the Wild stage of the receiver's kg_post on: its audio then lags by taps + impulse_samples // 2 samples.  Call it
+        after set_audio, whose connection start switches the stage off."""
         frate = self.fs if frate is None else frate
-        check(self.lib.kg_rxbank_set_nb_algo(self.h, int(rx), int(algo)), "kg_rxbank_set_nb_algo")
+        if algo == nb_mod.NB_WILD:
+            check(self.lib.kg_rxbank_nbw_select(self.h, int(rx)), "kg_rxbank_nbw_select")
+        else:
+            check(self.lib.kg_rxbank_set_nb_algo(self.h, int(rx), int(algo)), "kg_rxbank_set_nb_algo")
         for k, v in enumerate(params or []):
             check(self.lib.kg_rxbank_set_nb_param(self.h, int(rx), nb_mod.NB_BLANKER, k, float(np.float32(v)), float(np.float32(frate))),
                   "kg_rxbank_set_nb_param")

@@ -612,6 +612,36 @@ int kg_post_nrs_process_dev(kg_post *post, const int32_t *chans, int nch, const 
  * scalars[8 i ..] = final_gain, alpha, asnr, xih1, xih1r, pfac, norm_locut, norm_hicut; rate[6] = tinc, tax, tap, ax, ap, snr_prio_min;
  * arrays[9 * 256 i ..] = last_sample_buffer, last_iFFT_result, NR_Nest, xt, pslp, NR_SNR_post, NR_SNR_prio, NR_Hk_old, NR_G.  Synchronises. */
 int kg_post_nrs_state(kg_post *post, const int32_t *chans, int nch, int32_t *ints, float *scalars, float *rate, float *arrays);
+/* NB_WILD, the second algorithm of the noise-blanker switch (rx/rx_sound.cpp:922-931 -> rx/Teensy/NB_Wild.cpp, Michael Wild's LPC
+ * blanker): per 512 samples an LPC model of the block (order = taps), the block inverse- and matched-filtered, up to 20 impulses found
+ * above thresh * sqrt(variance * coefficient power), and impulse_samples | 1 samples around each replaced by the cross-fade of a forward
+ * and a backward prediction.  The output is the input delayed by order + PL samples (PL = ((impulse_samples | 1) - 1) / 2) with the
+ * repaired stretches; every output sample equals the reference's.  It sits behind de-emphasis and ahead of the noise-reduction switch,
+ * in the modes that are not stereo ones.  One state per channel (nb_Wild[], NB_Wild.cpp:36), kept across modes and connections.
+ * kg_post_nbw_init: nb_Wild_init (NB_Wild.cpp:38-46; called by `SET nb type=0 param= pval=` under NB_WILD, rx_sound_cmd.cpp:498):
+ *   zeroes the whole state, the history included, then takes thresh, (s1_t) taps and (s1_t) impulse_samples from nb_param[KG_NBW_THRESH,
+ *   KG_NBW_TAPS, KG_NBW_SAMPLES] (a value outside signed char, whose conversion C leaves undefined, is recorded as 0).  A vector is
+ *   usable when thresh is finite, taps is 1..40 and impulse_samples 2..41: with taps 0 or fewer than 2 samples the reference divides 0
+ *   by 0 and NaN samples reach its output, beyond 40 / 41 it leaves its arrays.  Storing is never refused while the stage is off (the
+ *   client's three parameter messages pass through unusable vectors); with the stage on an unusable vector is KG_ERR_INVALID, nothing changed.
+ * kg_post_set_nbw: the stage's switch, s->nb_enable[NB_BLANKER] && s->nb_algo == NB_WILD (rx_sound.cpp:924-929), held by the caller.
+ *   Switching on with an unusable vector is KG_ERR_STATE.  kg_post_reset clears the switch and keeps the state, as memset(s) does.
+ * kg_post_process_dev runs the stage behind post_kernel and ahead of the NR stages over its d_s16 rows for every listed channel with the
+ *   switch on in a mono mode; such a batch needs d_s16 and nsamps % 512 == 0 (KG_ERR_INVALID, nothing enqueued).  A batch without such
+ *   a channel launches what it launched before. */
+enum { KG_NBW_MAX_SAMPLES = 4096 };                              /* kg_post_nbw_process_dev: at most eight blocks a call */
+enum { KG_NBW_THRESH = 0, KG_NBW_TAPS = 1, KG_NBW_SAMPLES = 2 };  /* NB_THRESH, NB_TAPS, NB_SAMPLES, extensions/noise_blank/noise_blank.h */
+enum { KG_NBW_HIST = 120 };                                      /* 2 * 40 + 2 * 20: the most a call carries to the next */
+int kg_post_nbw_init(kg_post *post, int chan, const float *nb_param /* [KG_NB_PARAMS] */);
+int kg_post_set_nbw(kg_post *post, int chan, int on);
+/* The standalone call site: nb_Wild_process(ch, 512, ...) (NB_Wild.cpp:253-261) once per 512 samples of row i of d_in -> row i of d_out
+ * (d_in == d_out allowed) for each listed channel, whatever its mode and switch; its vector must be usable, else KG_ERR_STATE.  nsamps:
+ * a positive multiple of 512 up to KG_NBW_MAX_SAMPLES, else KG_ERR_INVALID.  The same device code as the fused pass.  Enqueue only. */
+int kg_post_nbw_process_dev(kg_post *post, const int32_t *chans, int nch, const void *d_in, size_t in_stride, int nsamps, void *d_out,
+                            size_t out_stride);
+/* The states of the listed channels, either output may be NULL: ints[3 i ..] = taps, impulse_samples, the switch; floats[121 i ..] =
+ * thresh, then working_buffer[0 .. KG_NBW_HIST) of which a call writes the first 2 * order + 2 * PL (the rest is 0).  Synchronises. */
+int kg_post_nbw_state(kg_post *post, const int32_t *chans, int nch, int32_t *ints, float *floats);
 /* The CFir objects of a channel (rx/rx_sound.cpp:153-156; rx/CuteSDR/fir.cpp): the filter behind the AM detector and the
  * two de-emphasis filters.  (CSquelch owns a fourth, its noise high-pass: kg_post_squelch_setup.) */
 enum { KG_CFIR_AM = 0, KG_CFIR_DEEMP_NFM = 1, KG_CFIR_DEEMP_AM_SSB = 2,
@@ -834,26 +864,38 @@ kg_rxddc *kg_rxbank_rxddc(kg_rxbank *bank);   /* kg_rxddc_set_freq */
 kg_fir *kg_rxbank_fir(kg_rxbank *bank);       /* kg_fir_setup */
 kg_post *kg_rxbank_post(kg_rxbank *bank);     /* kg_post_set_agc / _set_smeter / _set_mode / _reset */
 kg_adpcm *kg_rxbank_adpcm(kg_rxbank *bank);
-/* The noise blanker (NB_STD) of the bank's receivers: m_NoiseProc_snd[] (kg_nb; the waterfall's m_NoiseProc_wf[] are kg_rxbank_wf's).
+/* The noise blankers (NB_STD, NB_WILD) of the bank's receivers: m_NoiseProc_snd[] (kg_nb; the waterfall's m_NoiseProc_wf[] are
+ * kg_rxbank_wf's) and nb_Wild[] (kg_rxbank_post's kg_post_nbw_*).
  * The commands keep snd_t's and wf_inst_t's NB state per receiver, with the reference's side effects on both:
  *   kg_rxbank_set_nb_algo    `SET nb algo=` (rx_sound_cmd.cpp:454-462): the algo; both the audio and the waterfall enables cleared.
+ *   kg_rxbank_nbw_select     `SET nb algo=2`: the same with algo = KG_NB_WILD (kg_rxbank_set_nb_algo keeps refusing the value); no
+ *                            blanker state touched.
  *   kg_rxbank_set_nb_enable  `SET nb type= en=` (:477-483): both enables of that type.
  *   kg_rxbank_set_nb_param   `SET nb type= param= pval=` (:485-501): the audio value stored; under NB_STD or for NB_CLICK also the
- *                            waterfall's, with its change pending; NB_BLANKER under NB_STD: SetupBlanker("SND", frate, ...) at once.
+ *                            waterfall's, with its change pending; NB_BLANKER under NB_STD: SetupBlanker("SND", frate, ...) at once;
+ *                            NB_BLANKER under NB_WILD: nb_Wild_init from the whole stored vector (kg_post_nbw_init: state and history
+ *                            zeroed on every message), nothing stored on the waterfall side.
  *   kg_rxbank_set_nb_gate    kiwiclient's `SET nb= th=` (:660-672): gate, threshold and the audio enable only; SetupBlanker when nb != 0,
- *                            whatever the algo.
+ *                            whatever the algo; never nb_Wild_init.
+ * Under NB_WILD the audio enable of NB_BLANKER (kg_rxbank_set_nb_enable, kg_rxbank_set_nb_gate) is the Wild stage's switch
+ * (kg_post_set_nbw): the stage runs inside the step's kg_post pass, behind de-emphasis, and delays the receiver's audio by order + PL
+ * samples; the step's NB_STD audio blanker does not run; the waterfall side keeps the rules below.  Selecting any algo,
+ * kg_rxbank_join and kg_post_reset switch the stage off.
  * A step runs the audio blanker in place on the unpacked records (kg_rxbank_bufs.rx_in: what CFastFIR was fed) of every active
  * receiver with enable[NB_BLANKER] under NB_STD (rx_sound.cpp:593-598).  Before a receiver's next frame, with both waterfall
  * enables (NB_BLANKER, NB_WF) on, a pending change sets up its waterfall blanker (kg_wf_nb_setup); its frames are then blanked
  * (rx_waterfall.cpp:1087-1099).  A zoom change through kg_rxbank_set_wf (decimation) or kg_rxbank_set_wf_pkt (zoom) makes the change
  * pending when both enables are on (:460).  kg_rxbank_join clears the receiver's NB command state on both sides (algo NB_OFF,
  * enables, params, pending changes, nb_setup) and keeps the blankers' states.
- * Refused at the command, nothing changed: KG_NB_WILD or another algo (KG_ERR_INVALID, not implemented); a type outside 0..3 or a
+ * Refused at the command, nothing changed: KG_NB_WILD in kg_rxbank_set_nb_algo (KG_ERR_INVALID: kg_rxbank_nbw_select) or a value that
+ * is no nb_algo_e (KG_ERR_INVALID); a type outside 0..3 or a
  * param outside 0..7 (KG_ERR_INVALID); enabling KG_NB_CLICK (KG_ERR_INVALID: test pulses are not implemented); enabling
  * KG_NB_BLANKER under KG_NB_STD before the audio blanker was set up (KG_ERR_STATE); a value that kg_nb_setup refuses at frate (audio)
- * or at 8192 (the waterfall's). */
+ * or at 8192 (the waterfall's); under KG_NB_WILD, enabling KG_NB_BLANKER on a vector NB_Wild.cpp cannot run on (KG_ERR_STATE) and a
+ * parameter that makes the vector such a one while the stage is on (KG_ERR_INVALID): see kg_post_nbw_init. */
 kg_nb *kg_rxbank_nb(kg_rxbank *bank);
 int kg_rxbank_set_nb_algo(kg_rxbank *bank, int rx, int algo);
+int kg_rxbank_nbw_select(kg_rxbank *bank, int rx);
 int kg_rxbank_set_nb_enable(kg_rxbank *bank, int rx, int type, int en);
 int kg_rxbank_set_nb_param(kg_rxbank *bank, int rx, int type, int param, float pval, float frate);
 int kg_rxbank_set_nb_gate(kg_rxbank *bank, int rx, int nb, int th, float frate);

@@ -1,6 +1,7 @@
 """Randomised differential soak: many random configurations of every stateful module through the
 C ABI against the oracle (bit-exact where the module is integer, the module's bar otherwise); `nrs`, the spectral noise
-reduction, against its host driver (tools/nrs_host_driver.cpp), bit-exact.
+reduction, and `nbw`, the Wild noise blanker, against their host drivers (tools/nrs_host_driver.cpp, tools/nbw_host_driver.cpp),
+bit-exact.
 usage: python tools/fuzz_parity.py [seconds per module] [seed] [module name: only that one]
 A failing `post` trial leaves its story (mode, parameter sets, inputs) in gpurun_out/fuzz_fail_post_<k>.npz."""
 import os
@@ -513,7 +514,58 @@ def trial_nrs():
         P.close()
 
 
-for name, fn in (("nrs", trial_nrs), ("rxbank", trial_rxbank), ("tail", trial_tail), ("acq", trial_acq), ("wf ddc", trial_wfddc), ("rx ddc", trial_rxddc), ("fastfir", trial_fir), ("post", trial_post), ("wire", trial_wire), ("wf frames", trial_wf)):
+_nbw = {}
+
+
+def trial_nbw():
+    """NB_WILD: a random script (the three parameter messages, single re-inits in mid-stream over the whole range of taps and
+    impulse_samples, the enable off and on, another algo and back, a new connection, stereo, zero and clicky blocks, calls of 1..8
+    blocks) through tools/nbw_host_driver.cpp (csrc/kg_nbw.h on the host) and through kg_post_nbw_process_dev: every output sample
+    and every state value equal."""
+    import tempfile
+    from tests import nbw_common as nc
+    if not _nbw:
+        _nbw["tmp"] = tempfile.mkdtemp(prefix="nbw_fuzz")
+        _nbw["exe"] = nc.build_driver(_nbw["tmp"])
+
+    lines = nc.random_script(rng)
+    blocks = []
+    for l in lines:
+        if l[0] == "B":
+            x = adc_block(512) if rng.random() > 0.08 else np.zeros(512, np.int16)
+            for p_ in rng.integers(0, 512, int(rng.integers(0, 4))):
+                x[p_] = rng.choice([-1, 1]) * rng.integers(8000, 32767)
+            blocks.append(x)
+    x = np.concatenate(blocks)
+    want, wst, _, _, rc = nc.run_driver(_nbw["exe"], lines, x, _nbw["tmp"])
+    assert rc == 0, ("host driver", rc, lines)
+    P = Post(ctx, nchan=2)
+    try:
+        r = nc.Replay(P, 1, lines, x)
+        while True:
+            nxt = r.step()
+            if nxt is None:
+                break
+            if not nxt[1]:
+                r.done(nxt[0])
+                continue
+            run = [nxt[0]]
+            k = int(rng.integers(1, 9))
+            while len(run) < k and r.peek_is_block():
+                run.append(r.step()[0])
+            r.done(P.nbw_process([1], np.concatenate(run)[None, :], in_place=bool(rng.integers(0, 2)))[0])
+        y = r.output()
+        bad = np.flatnonzero(y != want)
+        assert bad.size == 0, ("nbw output", bad.size, bad[:4], lines)
+        iv, th, hist = wst[-1]
+        st = r.states[-1]
+        assert st["ints"][0, :2].tolist() == iv[:2].tolist() and st["thresh"][0].view(np.uint32) == th.view(np.uint32)[0], ("nbw vector", st["ints"], iv, lines)
+        assert np.array_equal(st["hist"][0].view(np.uint32), hist.view(np.uint32)), ("nbw history", lines)
+    finally:
+        P.close()
+
+
+for name, fn in (("nbw", trial_nbw), ("nrs", trial_nrs), ("rxbank", trial_rxbank), ("tail", trial_tail), ("acq", trial_acq), ("wf ddc", trial_wfddc), ("rx ddc", trial_rxddc), ("fastfir", trial_fir), ("post", trial_post), ("wire", trial_wire), ("wf frames", trial_wf)):
     soak(name, fn)
 print("failures:", fails)
 if _acq:
