@@ -3,16 +3,33 @@
  * Part 3: the waterfall DDC the reference runs in FPGA fabric
  * (verilog/rx/iq_mixer.v, cic_prune_var.v + cic_wf1.vh, waterfall_1cic.v).
  *
- * SELF-REFERENTIAL, FPGA PARITY UNPINNED: the NCO is a closed Xilinx DDS
- * Compiler IP with phase dithering (verilog/ipcore_properties/
+ * A hand restatement of the Verilog, not executed reference code: no simulator
+ * (iverilog/verilator) is in this image.  What it rests on:
+ *
+ * UNPINNED, frozen here and documented in DESIGN.md: the NCO is a closed Xilinx
+ * DDS Compiler IP with phase dithering (verilog/ipcore_properties/
  * ipcore_dds_sin_cos_13b_15b_48b.txt) whose table and dither sequence are not
- * in the tree, and no simulator (iverilog/verilator) is in this image.  What
- * IS restated bit for bit from the Verilog: the mixer's product/rounding
- * (iq_mixer.v:43-51), the pruned CIC's register widths, truncations, rounding
- * and R = 1 bypass (cic_wf1.vh, cic_prune_var.v).  Frozen here and documented
- * in DESIGN.md: the sine table (round(16383*cos/sin), 13-bit address = phase
- * bits 47:35, no dither), phase(n) = phase0 + n*inc, and pipeline register
- * delays dropped (pure latency): output k closes on input sample R*k + R-1.
+ * in the tree -- the sine table is round(16383*cos/sin) without dither; and
+ * pipeline register delays are dropped (pure latency).
+ *
+ * HELD BY AN INDEPENDENT DERIVATION, everything else: tests/ddc_exact.py models
+ * both down-converters as exact running sums (no register width, wrap or comb
+ * width in it) and derives from the structure how far a faithful pruned form
+ * may be from that; this file (tests/test_ddc_exact_cpu.py) and the kernels
+ * (tests/test_ddc_exact_gpu.py) must stay inside it, and ten misreadings of the
+ * Verilog applied to the model -- table address bits, phase advanced early,
+ * Q negated, I/Q swapped, a pre-shift one bit off, the closing sample one late,
+ * the FIR's decimation phase, another mode's taps or R2, the record's bytes 4/5
+ * -- miss it by 4x or more.  The parameters the restatement uses (SIGN, MANTISSA,
+ * RND, the decimation case list and its shifts, the R = 1 slice, the widths
+ * rx.v instantiates, the FIR's decimate-by-2 flag) are parsed from the Verilog
+ * into tests/golden/ref_text_pins.json; register widths and truncations are
+ * cic_gen.c's own output (tests/golden/cic_ref.json).
+ *
+ * Restated: the mixer's product/rounding (iq_mixer.v:43-51), the pruned CIC's
+ * register widths, truncations, rounding and R = 1 bypass (cic_wf1.vh,
+ * cic_prune_var.v); 13-bit table address = phase bits 47:35; phase(n) =
+ * phase0 + n*inc; output k closes on input sample R*k + R-1.
  */
 #include "kiwi_oracle.h"
 
@@ -184,7 +201,7 @@ int ko_ddc_shape(int which, int r, int *o)
 /* [54 -: 26], combs 22/21/20 dropping 4/1/1 LSBs, out = comb3[19 -: 18] +     */
 /* comb3[1]); the checked-in cic_rx1_12k.vh is the stale R = 926 variant of    */
 /* the same structure.  rx2: cic_rx2_12k.vh (26 bits throughout, out =        */
-/* comb5[25 -: 24] + comb5[1]).  SELF-REFERENTIAL like the waterfall DDC.      */
+/* comb5[25 -: 24] + comb5[1]).  Held by the exact model like the waterfall DDC. */
 /* ======================================================================== */
 
 /* fir_iq.sv:91-123, the default (rx4/rx8) table: taps[0..32], symmetric */
@@ -284,7 +301,8 @@ int ko_ddc_rx_mode(ko_ddc_rx_state *s, const int16_t *adc, long n, uint64_t phas
         }
         if (!strobe2) continue;
         /* fir_iq: shift register, NT symmetric taps, 42-bit accumulator, out = acc[41 -: 24],
-         * an output on every second input (decim_by_2 starts at 0, fir_iq.sv:125-170) */
+         * an output on every second input: the flag decim_by_2 starts at 0 and an input that finds it 1 emits,
+         * so the first record comes from the SECOND input (fir_iq.sv:125-170) */
         int32_t y[2];
         for (int c = 0; c < 2; c++) {
             memmove(&s->fir_buf[c][1], &s->fir_buf[c][0], sizeof(int32_t) * (NT - 1));

@@ -10,6 +10,9 @@ from them -- as tests/test_ref_pins_cpu.py does for fir_iq.sv's taps.
   rx/rx_waterfall.cpp:175-185 CIC_comp p1 / p2, scaling -> ko.wf_cic_comp, wf.cic_comp_table
   rx/CuteSDR/fastfir.cpp:61-95, 102-146  CIC p1 / p2 (both rates), the five window functions' constants
                                                         -> ko.fir_window / ko.fir_cic_coeffs, kg_snd.hip's literals
+  verilog/rx/iq_mixer.v, cic_prune_var.v, rx.v, waterfall_1cic.v, fir_iq.sv (through verilog/kiwi.gen.vh): the parameters of the two
+                            down-converters             -> the shifts and slices oracle/kiwi_oracle_ddc.c restates, the constants
+                                                           of the exact model (tests/ddc_exact.py)
 """
 import json
 import os
@@ -149,3 +152,77 @@ def test_fastfir_windows_and_cic_constants_are_fastfir_cpp_text(oracle):
     assert ref["cic_p1"] + ref["cic_p2"] == [-3.107, -2.969, 32.04, 36.26]
     for s in (our("oracle/kiwi_oracle_snd.c"), src):
         assert "-3.107f : -2.969f" in s and "32.04f : 36.26f" in s
+
+
+def test_ddc_shifts_and_slices_follow_from_the_verilog_parameters(oracle):
+    """What the DDC restatement rests on, recomputed from the Verilog's own parameters (numbers and signal names only): the mixer's
+    `>> 11` + bit 10 (waterfall) and `>> 13` + bit 12 (audio), the variable pre-shift 65 - 5 log2 R, the R = 1 slice `>> 8`, the
+    widths and decimations rx.v and waterfall_1cic.v instantiate, the order of the three output words, and which of every two FIR
+    inputs emits."""
+    import json
+    from tests import ddc_exact as dx
+    v = PINS["verilog_ddc"]
+    prm, mixer, prune, fir = v["params"], v["iq_mixer_v"], v["cic_prune_var_v"], v["fir_iq_sv"]
+    osrc = our("oracle/kiwi_oracle_ddc.c")
+    # mixer: {prod[SIGN], prod[MANTISSA -: MANTISSA_W]} + prod[RND] keeps prod down to bit RND + 1 and rounds with bit RND
+    assert mixer["out_slice_names"] == ["SIGN", "MANTISSA", "MANTISSA_W", "RND"] and (mixer["i_from"], mixer["q_from"]) == ("cos", "sin")
+    for width, shift in ((prm["WF1_BITS"], 11), (prm["RX1_BITS"], 13)):
+        m = mixer["for_OUT_WIDTH"][str(width)]
+        assert (m["SIGN"], m["MANTISSA"]) == (35, 33) and m["MANTISSA_W"] == width - 1 and m["RND"] == m["MANTISSA"] - m["MANTISSA_W"]
+        assert m["RND"] + 1 == shift == 35 - width and m["ZFILL"] == 18 - prm["ADC_BITS"] == 2
+        assert ("(prod >> %d) + ((prod >> %d) & 1)" % (shift, shift - 1)) in osrc
+        assert m["MANTISSA"] - m["MANTISSA_W"] + 1 + m["MANTISSA_W"] == m["SIGN"] - 1          # the slice sits right below bit 34 = sign
+    assert (mixer["dds_bits"], mixer["dds_zero_fill"], mixer["factor_bits"], mixer["product_bits"], mixer["phase_bits"]) == (15, 3, 18, 36, 48)
+    assert prm["ADC_BITS"] + 2 == mixer["dds_bits"] + mixer["dds_zero_fill"] == mixer["factor_bits"]
+    assert "adc * 4" in osrc and "dds * 8" in osrc and 4 * 8 == 32           # the model's adc * dds * 32
+    assert (dx.WF_W, dx.RX_W, dx.NCO_AMPL) == (prm["WF1_BITS"], prm["RX1_BITS"], 2 ** (mixer["dds_bits"] - 1) - 1)
+    # the instances
+    wf = v["instances"]["waterfall_1cic_v"]
+    assert wf["IQ_MIXER"] == {"IN_WIDTH": 16, "OUT_WIDTH": 24}
+    assert wf["cic_prune_var"] == {"INCLUDE": "wf1", "STAGES": 5, "DECIMATION": -8192, "GROWTH": 65, "IN_WIDTH": 24, "OUT_WIDTH": 16}
+    cic = json.load(open(os.path.join(ROOT, "tests", "golden", "cic_ref.json")))
+    assert prune["ACC_WIDTH"] == 24 + 65 == cic["cic_wf1"]["acc"]
+    # the variable pre-shift: ACC_WIDTH - (IN_WIDTH + STAGES clog2(R)) for the case list 1 .. 8192, nothing for R = 1 or an unlisted R
+    assert prune["decim_shift"] == [[1, 0]] + [[1 << l, 89 - (24 + 5 * l)] for l in range(1, 14)] and prune["default_shift"] == 0
+    assert all(sh == 65 - 5 * l == dx.wf_shift(l) for l, (_, sh) in enumerate(prune["decim_shift"]) if l)
+    assert "65 - 5 * log2r" in osrc and prune["fixed_decimation_shift"] == 0
+    # R = 1: in[IN_WIDTH-1 -: OUT_WIDTH]
+    msb, width = prune["r1_slice"]
+    assert (msb, width) == (23, 16) and msb + 1 - width == 8 and "(m[c] >> 8)" in osrc
+    assert prune["strobe_when_sample_no_is_decim_minus"] == 1 and "(uint32_t) (R - 1)" in osrc
+    # rx.v: mixer 16 -> 22, rx1 22 -> 18, rx2 18 -> 24, FIR on 24 bits; decimations per configuration
+    rx = v["instances"]["rx_v"]
+    for cfg, mode in (("4", dx.RX_STD), ("8", dx.RX_STD), ("3", dx.RX_WIDE), ("14", dx.RX_14)):
+        i = rx[cfg]
+        assert i["IQ_MIXER"] == {"IN_WIDTH": 16, "OUT_WIDTH": 22} and i["fir_iq"] == {"WIDTH": 24}
+        assert (i["rx1"]["INCLUDE"], i["rx1"]["STAGES"], i["rx1"]["IN_WIDTH"], i["rx1"]["OUT_WIDTH"]) == ("rx1", 3, 22, 18)
+        assert (i["rx2"]["INCLUDE"], i["rx2"]["STAGES"], i["rx2"]["IN_WIDTH"], i["rx2"]["OUT_WIDTH"]) == ("rx2", 5, 18, 24)
+        c1, c2, _ = dx.RX_MODES[mode]
+        assert (i["rx1"]["DECIMATION"], i["rx2"]["DECIMATION"]) == (cic[c1]["R"], cic[c2]["R"])
+        assert (cic[c1]["Bin"], cic[c1]["Bout"], cic[c2]["Bin"], cic[c2]["Bout"]) == (22, 18, 18, 24)
+        assert oracle.ddc_rx_decim(mode) == i["rx1"]["DECIMATION"] * i["rx2"]["DECIMATION"] * 2 == dx.rx_decim(mode)
+    # the three 16-bit words {i[15:0]}, {q[15:0]}, {i[23 -: 8], q[23 -: 8]}: little-endian, so byte 4 is Q's top byte and byte 5 is I's
+    assert rx["words"] == [["i", 16], ["q", 16], ["i", 8, "q", 8]]
+    vals = {"i": 0x123456, "q": -0x234567 & 0xFFFFFF}
+    words = [vals[rx["words"][0][0]] & 0xFFFF, vals[rx["words"][1][0]] & 0xFFFF, (vals[rx["words"][2][0]] >> 16) << 8 | vals[rx["words"][2][2]] >> 16]
+    rec = np.array(words, "<u2").view(np.uint8)
+    assert dx.unpack_records(rec) == ([0x123456], [-0x234567])
+    # fir_iq.sv: out = acc[ACCOUT -: WIDTH] drops COEFF bits; the flag starts at 0 and a 1 emits: the FIRST record comes from the SECOND input
+    assert (fir["COEFF"], fir["ACCW"], fir["ACCOUT"]) == (18, 42, 41) and fir["out_slice_names"] == ["ACCOUT", "WIDTH"]
+    assert fir["ACCOUT"] + 1 - 24 == fir["COEFF"] == dx.FIR_COEFF_BITS and "(acc >> 18)" in osrc
+    assert fir["NTAPS"] == {"14": 17, "other": 65}
+    assert (fir["decim_by_2_initial"], fir["decim_by_2_value_that_emits"]) == (0, 1)
+    for mode in (dx.RX_STD, dx.RX_WIDE, dx.RX_14):
+        per_fir_input = dx.rx_decim(mode) // 2
+        adc = np.full(2 * per_fir_input, 1000, np.int16)
+        assert oracle.ddc_rx(adc[:2 * per_fir_input - 1], 0, mode=mode)[0].size == 0          # one FIR input: nothing yet
+        assert oracle.ddc_rx(adc, 0, mode=mode)[0].size == 6                                   # the second one emits
+    # and the whole R = 1 path from the numbers alone: ((adc << ZFILL) * (dds << fill) >> RND + 1) + bit RND, then the slice
+    rng = np.random.default_rng(5)
+    adc = rng.integers(-32768, 32768, 8192).astype(np.int16)
+    c, s = oracle.ddc_nco_table()
+    got, _ = oracle.ddc_wf(adc, 1 << (mixer["phase_bits"] - 13), 0)
+    rnd = mixer["for_OUT_WIDTH"]["24"]["RND"]
+    for col, tab in ((0, c), (1, s)):
+        prod = (adc.astype(np.int64) << 2) * (tab.astype(np.int64) << mixer["dds_zero_fill"])
+        assert np.array_equal(got[:, col], ((prod >> (rnd + 1)) + ((prod >> rnd) & 1)) >> (msb + 1 - width))

@@ -4,7 +4,9 @@
                       generated verilog/rx/cic_*.vh, the CICF taps of verilog/rx/fir_iq.sv, the Sats[] rows of gps/sats.cpp,
                       the de-emphasis tables of rx/rx_filter.h, COEF / lo_sin / lo_cos of gps/search.cpp, the window and
                       CIC-compensation constants of rx/rx_waterfall.cpp and rx/CuteSDR/fastfir.cpp (+ rx/rx_sound.h's
-                      WINF_SND_* numbers)
+                      WINF_SND_* numbers), and the parameters of the down-converters' Verilog that the DDC oracle and the exact
+                      model of tests/ddc_exact.py rest on (verilog/rx/iq_mixer.v, cic_prune_var.v, rx.v, waterfall_1cic.v,
+                      fir_iq.sv, resolved through verilog/kiwi.gen.vh) -- as numbers and signal names, evaluated here
   cacode_ref.npz      the C/A chips of every non-E1B row of Sats[], as the reference's own gps/cacode.h produces them
                       (oracle/_ref/cacode_ref, built by oracle/build_ref.sh)
 
@@ -132,6 +134,107 @@ def fastfir_cpp():
             "cic_p1": [float(v) for v in p.groups()], "cic_p2": [float(v) for v in q.groups()]}
 
 
+def _vparams(txt, env):
+    """`localparam NAME = <integer expression>;` of a Verilog text, evaluated in order on top of env (names -> ints; clog2 as
+    kiwi.gen.vh defines it: ceil(log2) above 1).  Only the values are kept."""
+    out = dict(env)
+    fns = {"clog2": lambda v: 1 if v <= 1 else (v - 1).bit_length()}
+    for name, expr in re.findall(r"localparam\s+(\w+)\s*=\s*([^;?]+);", re.sub(r"//[^\n]*", "", txt)):
+        if re.fullmatch(r"[\w\s+\-*()]+", expr):
+            try:
+                out[name] = int(eval(expr, {"__builtins__": {}}, dict(out, **fns)))      # noqa: S307 -- arithmetic on names only
+            except (NameError, TypeError):
+                pass
+    return out
+
+
+def _instances(txt, module, env):
+    """Every `module #(.P(v), ...)` of a Verilog text: {P: value}, names resolved through env, strings kept."""
+    res = []
+    for body in re.findall(r"^\s*%s\s*#\((.*?)\)\s*$" % module, re.sub(r"//[^\n]*", "", txt), flags=re.M):
+        inst = {}
+        for k, v in re.findall(r"\.(\w+)\(\s*([^()]*(?:\([^()]*\))?[^()]*)\)", body):
+            v = v.strip()
+            inst[k] = v.strip('"') if v.startswith('"') else int(eval(v, {"__builtins__": {}}, dict(env)))      # noqa: S307
+        res.append(inst)
+    return res
+
+
+def verilog_ddc():
+    gen = text("verilog/kiwi.gen.vh")
+    env = _vparams(gen, {})
+    by_cfg = {}
+    for name in ("RX1_DECIM", "RX2_DECIM"):                  # the RX_CFG ladders: configuration -> decimation
+        ladder = re.search(r"localparam %s = ([^;]+);" % name, gen).group(1)
+        by_cfg[name] = {cfg: env[sym] for cfg, sym in re.findall(r"\(RX_CFG == (\d+)\)\?\s*(\w+)", ladder)}
+    # iq_mixer.v
+    mix_txt = text("verilog/rx/iq_mixer.v")
+    mixer = {"for_OUT_WIDTH": {}}
+    for w in (env["RX1_BITS"], env["WF1_BITS"]):
+        pm = _vparams(mix_txt, {"IN_WIDTH": env["ADC_BITS"], "OUT_WIDTH": w})
+        mixer["for_OUT_WIDTH"][str(w)] = {k: pm[k] for k in ("ZFILL", "SIGN", "MANTISSA", "MANTISSA_W", "RND")}
+    code = re.sub(r"//[^\n]*", "", mix_txt)
+    m = re.search(r"assign out_i = \{ prod_i\[(\w+)\], prod_i\[(\w+) -:(\w+)\] \} \+ prod_i\[(\w+)\];", code)
+    mixer["out_slice_names"] = list(m.groups())              # {sign bit, [msb -: width]} + [rounding bit]
+    hi, = re.findall(r"wire signed \[(\d+):0\] dds_sin, dds_cos;", code)
+    fill, = re.findall(r"assign cos = \{dds_cos, (\d+)'b0\};", code)
+    fac, = re.findall(r"reg signed \[(\d+):0\] mx, my_i, my_q;", code)
+    prod, = re.findall(r"reg signed \[(\d+):0\] prod_i, prod_q;", code)
+    pinc, = re.findall(r"input wire signed \[(\d+):0\] phase_inc", code)
+    mixer.update(dds_bits=int(hi) + 1, dds_zero_fill=int(fill), factor_bits=int(fac) + 1, product_bits=int(prod) + 1,
+                 phase_bits=int(pinc) + 1, i_from=re.search(r"my_i <= (\w+);", code).group(1), q_from=re.search(r"my_q <= (\w+);", code).group(1))
+    # waterfall_1cic.v and rx.v: what they instantiate
+    wf_txt, rx_txt = text("verilog/rx/waterfall_1cic.v"), text("verilog/rx/rx.v")
+    wenv = _vparams(wf_txt, dict(env, IN_WIDTH=env["ADC_BITS"]))
+    wf_cic = _instances(wf_txt, "cic_prune_var", wenv)
+    assert wf_cic[0] == wf_cic[1]                            # I and Q
+    inst = {"waterfall_1cic_v": {"IQ_MIXER": _instances(wf_txt, "IQ_MIXER", wenv)[0], "cic_prune_var": wf_cic[0]}, "rx_v": {}}
+    for cfg in sorted(by_cfg["RX1_DECIM"], key=int):
+        renv = _vparams(rx_txt, dict(env, IN_WIDTH=env["ADC_BITS"], RX1_DECIM=by_cfg["RX1_DECIM"][cfg], RX2_DECIM=by_cfg["RX2_DECIM"][cfg]))
+        cics = _instances(rx_txt, "cic_prune_var", renv)
+        assert cics[0] == cics[1] and cics[2] == cics[3]
+        inst["rx_v"][cfg] = {"IQ_MIXER": _instances(rx_txt, "IQ_MIXER", renv)[0], "rx1": cics[0], "rx2": cics[2],
+                             "fir_iq": _instances(rx_txt, "fir_iq", renv)[0]}
+    m = re.search(r"rx_dout = rd_i\? rx_cic_out_(\w)\[(\d+):0\] : \( rd_q\? rx_cic_out_(\w)\[(\d+):0\] : "
+                  r"\{rx_cic_out_(\w)\[RXO_BITS-1 -:(\d+)\], rx_cic_out_(\w)\[RXO_BITS-1 -:(\d+)\]\} \)", rx_txt)
+    g = m.groups()                                           # 16-bit words: low 16 of i, low 16 of q, {top 8 of .., top 8 of ..}
+    inst["rx_v"]["words"] = [[g[0], int(g[1]) + 1], [g[2], int(g[3]) + 1], [g[4], int(g[5]), g[6], int(g[7])]]
+    # cic_prune_var.v: the variable pre-shift of the instance the waterfall builds, and the R = 1 slice
+    cp_txt = re.sub(r"//[^\n]*", "", text("verilog/rx/cic_prune_var.v"))
+    w = wf_cic[0]
+    cenv = _vparams(cp_txt, dict(env, IN_WIDTH=w["IN_WIDTH"], OUT_WIDTH=w["OUT_WIDTH"], STAGES=w["STAGES"], GROWTH=w["GROWTH"]))
+    block = cp_txt[cp_txt.index("if (DECIMATION == %d)" % w["DECIMATION"]):]
+    block = block[:block.index("endgenerate")]
+    cases = []
+    for d, rhs in re.findall(r"^\s*(\d+): in <= ([^;]+);", block, flags=re.M):
+        sh = re.fullmatch(r"in_data << \((\w+) - (\w+)\)", rhs.strip())
+        cases.append([int(d), cenv[sh.group(1)] - cenv[sh.group(2)] if sh else 0])
+    s1 = re.search(r"if \(decim == 1\)\s*out_data <= in\[([\w\-]+) -:(\w+)\];", cp_txt)
+    cnt = re.search(r"if \(sample_no == \(decim-(\d+)\)\)", cp_txt)
+    prune = {"ACC_WIDTH": cenv["ACC_WIDTH"], "decim_shift": cases, "default_shift": 0 if re.search(r"default: in <= in_data;", block) else None,
+             "r1_slice": [int(eval(s1.group(1), {"__builtins__": {}}, dict(cenv))), cenv[s1.group(2)]],      # noqa: S307 -- [msb, width]
+             "strobe_when_sample_no_is_decim_minus": int(cnt.group(1)),
+             "fixed_decimation_shift": 0 if re.search(r"if \(DECIMATION > 0\)\s*begin\s*always @\(posedge clock\)\s*in <= in_data;", cp_txt) else None}
+    # fir_iq.sv: the decimate-by-2 flag
+    fir_txt = re.sub(r"//[^\n]*", "", text("verilog/rx/fir_iq.sv"))
+    fenv = _vparams(fir_txt, dict(env, WIDTH=env["RXO_BITS"]))
+    init = re.findall(r"initial decim_by_2 = (\d);", fir_txt)
+    run = fir_txt[fir_txt.index("STATE_COMPUTE_SUM && next_state == STATE_COPY_OUTPUT"):]
+    run = run[:run.index("end")]
+    emits = re.findall(r"out_strobe <= (~|!)?decim_by_2;", run)
+    toggles = re.findall(r"decim_by_2 <= decim_by_2 \^ 1'b1;", run)
+    nt = re.search(r"localparam NTAPS = \(RX_CFG == (\d+) \? (\d+) : (\d+)\);", fir_txt)
+    fir = {"COEFF": fenv["COEFF"], "ACCW": fenv["ACCW"], "ACCOUT": fenv["ACCOUT"], "out_slice_names": list(re.search(
+               r"out_data_i <= accI\[(\w+) -:(\w+)\];", run).groups()),
+           "NTAPS": {nt.group(1): int(nt.group(2)), "other": int(nt.group(3))}}
+    if len(init) == 1 and len(emits) == 1 and len(toggles) == 1:          # unambiguous: one initial value, one strobe, one toggle per input
+        fir["decim_by_2_initial"] = int(init[0])
+        fir["decim_by_2_value_that_emits"] = 0 if emits[0] else 1
+    return {"params": {k: env[k] for k in ("ADC_BITS", "RX1_BITS", "RX2_BITS", "RXO_BITS", "RX1_STAGES", "RX2_STAGES", "WF1_BITS", "WFO_BITS",
+                                          "WF1_STAGES", "WF_1CIC_MAXD", "RX1_STD_DECIM", "RX2_STD_DECIM", "RX1_WIDE_DECIM", "RX2_WIDE_DECIM")},
+            "decim_by_RX_CFG": by_cfg, "iq_mixer_v": mixer, "instances": inst, "cic_prune_var_v": prune, "fir_iq_sv": fir}
+
+
 def cacode_chips():
     from flydog_sdr_gps_amd import sats
     exe = os.path.join(ROOT, "oracle", "_ref", "cacode_ref")
@@ -151,7 +254,7 @@ def main():
     pins = {"_source": "tools/make_ref_text_golden.py: numbers parsed from the reference's text",
             "cic_vh": {f: cic_vh("verilog/rx/" + f) for f in ("cic_wf1.vh", "cic_rx1_12k.vh", "cic_rx2_12k.vh")},
             "fir_iq_sv": fir_iq_sv(), "sats_cpp": sats_rows(), "rx_filter_h": rx_filter_h(), "search_cpp": search_cpp(),
-            "rx_waterfall_cpp": rx_waterfall_cpp(), "fastfir_cpp": fastfir_cpp()}
+            "rx_waterfall_cpp": rx_waterfall_cpp(), "fastfir_cpp": fastfir_cpp(), "verilog_ddc": verilog_ddc()}
     with open(os.path.join(GOLD, "ref_text_pins.json"), "w") as f:
         json.dump(pins, f, indent=1)
         f.write("\n")
