@@ -188,6 +188,14 @@ SYMBOLS = {
     "kg_wf_packets_dev": (_i, [_vp, _vp, _sz, _i, _vp, _vp, _sz, _vp]),
     "kg_fir_process_taps_dev": (_i, [_vp, _vp, _i, _vp, _sz, _i, _vp, _sz, _vp, _vp, _vp, _sz]),
     "kg_fir_refilter_dev": (_i, [_vp, _vp, _i, _vp, _vp, _sz, _vp, _sz]),
+    "kg_snd_spec_rows_dev": (_i, [_vp, _vp, _sz, _i, _vp, _vp, _sz]),
+    "kg_snd_spec_due": (_i, [_vp, C.c_uint32]),
+    "kg_fir_process_spec_dev": (_i, [_vp, _vp, _i, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _sz]),
+    "kg_rxbank_set_spec": (_i, [_vp, _i, _i]),
+    "kg_rxbank_null_fir": (_vp, [_vp]),
+    "kg_rxbank_spec_max": (_i, [_vp]),
+    "kg_rxbank_spec_map": (_i, [_vp, _vp, _vp, _vp]),
+    "kg_rxbank_spec_rows": (_i, [_vp, _vp, _vp]),
     "kg_fir_set_coef_plain": (_i, [_vp, _i, _vp]),
     "kg_snd_gps_begin": (None, [_vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]),
     "kg_snd_gps_stamp": (None, [_vp, _i, _i, _i, _i, _i, C.c_double, C.c_double, C.c_uint64, _vp]),

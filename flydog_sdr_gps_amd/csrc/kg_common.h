@@ -36,7 +36,7 @@ void kg_set_error(const char *fmt, ...);
 // REPLAY pass -- the same calls with the same arguments, after the block's one upload was enqueued -- they answer the same
 // addresses again, checking that the table is the one planned.
 enum { KG_ARENA_OFF = 0, KG_ARENA_PLAN = 1, KG_ARENA_REPLAY = 2 };
-#define KG_ARENA_MAX_ENTRIES 196     /* <= 16 tables per step + 4 per sound block of the step (kg_rxbank_create checks its step against it) */
+#define KG_ARENA_MAX_ENTRIES 244     /* <= 16 tables per step + 5 per sound block of the step (kg_rxbank_create checks its step against it) */
 struct kg_arena {
     int mode;
     unsigned char *h_base, *d_base;           // the current slot of the owner's ring (pinned host / device)
@@ -137,6 +137,22 @@ extern "C" __attribute__((visibility("hidden"))) void kg_nco_table_build(short *
 // kg_ddc.hip, for kg_rxbank.hip (not part of the ABI): the DDC's second stream supplied by the owner.
 struct kg_ddc;
 __attribute__((visibility("hidden"))) int kg_ddc_use_side_stream(kg_ddc *ddc, hipStream_t stream);
+
+// kg_snd.hip, for kg_rxbank.hip (not part of the ABI): kg_fir_process_spec_dev with the rows placed by the caller.  Per list entry
+// i: inst[i]; the leading row_n[i] completed blocks give a row (null: all of them); block b's row goes to d_rows + row_base[i] *
+// row_unit + 1024 b (null: entry i, or the channel on a bank's context); rows_bytes: the extent of d_rows.
+struct kg_fir_spec_req {
+    void *d_rows; size_t row_unit, rows_bytes;
+    const int32_t *inst, *row_n, *row_base;
+};
+__attribute__((visibility("hidden"))) int kg_fir_process_rows_(kg_fir *f, const int32_t *chans, int nch, const void *d_in, size_t in_stride,
+                                                               const int32_t *n_each, void *d_out, size_t out_stride, int32_t *nout,
+                                                               const kg_fir_spec_req *req);
+
+// kg_post.hip, for kg_rxbank.hip: how many kg_post_set_mode / kg_post_set_sam_mparam calls channel ch has seen (each clears
+// s->isChanNull, rx_sound_cmd.cpp:202-228), and its s->SAM_mparam
+__attribute__((visibility("hidden"))) uint32_t kg_post_mode_cmds_(const kg_post *p, int ch);
+__attribute__((visibility("hidden"))) int kg_post_sam_mparam_(const kg_post *p, int ch);
 
 // The library's own streams come from a per-device pool and go back to it; they are never destroyed.  Which hardware queue a
 // NEW stream lands on is the runtime's choice at that moment, and streams created after others had been destroyed were seen

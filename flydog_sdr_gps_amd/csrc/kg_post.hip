@@ -1007,6 +1007,7 @@ struct kg_post {
     kg_nbw::state_t *d_nbw;              // [nchan]: nb_Wild[] (NB_Wild.cpp:36) and the stage's switch
     std::vector<kg_nbw::state_t> h_nbw;  // thresh, taps, impulse_samples and the switch (hist is the device's)
     kg_stage_cache list_cache = {};      // the channel list of the last process call
+    std::vector<uint32_t> mode_cmds;     // per channel: kg_post_set_mode / kg_post_set_sam_mparam calls so far (kg_post_mode_cmds_)
 };
 
 static int post_check(kg_post *p, int ch, const char *who)
@@ -1283,6 +1284,7 @@ int kg_post_create(kg_ctx *ctx, int nchan, kg_post **out)
     kg_nbw::state_t wh;
     memset(&wh, 0, sizeof wh);
     p->h_nbw.assign(nchan, wh);
+    p->mode_cmds.assign(nchan, 0);
     post_sam w;                                     // a new connection at snd_rate 12000: PLL(MED), PLL(RESET) (rx_sound.cpp:302-303)
     memset(&w, 0, sizeof w);
     sam_init_consts(w, 12000);
@@ -1411,6 +1413,7 @@ int kg_post_set_mode(kg_post *p, int ch, int mode)
         if ((rc = sam_put(p, ch, &post_sam::is_chan_null, 0))) return rc;
     }
     if ((rc = post_put(p, ch, &post_chan::mode, mode))) return rc;
+    p->mode_cmds[ch]++;
     KG_HIP(hipStreamSynchronize(p->ctx->stream));
     return KG_OK;
 }
@@ -1501,6 +1504,7 @@ int kg_post_set_sam_mparam(kg_post *p, int ch, int mparam)
     int rc = post_check(p, ch, "kg_post_set_sam_mparam");
     if (rc) return rc;
     if ((rc = sam_put(p, ch, &post_sam::mparam, mparam & 0xf))) return rc;         // MODE_FLAGS_SAM (rx_sound.h:39)
+    p->mode_cmds[ch]++;                                                            // the n == 5 case of rx_sound_cmd.cpp:202
     KG_HIP(hipStreamSynchronize(p->ctx->stream));
     return KG_OK;
 }
@@ -2096,3 +2100,6 @@ int kg_post_nr_state(kg_post *p, const int32_t *chans, int nch, int type, int32_
 
 }  // extern "C"
 
+// for kg_rxbank.hip (not part of the ABI): what its mirror of s->specAF_instance / s->isChanNull needs without a device sync
+uint32_t kg_post_mode_cmds_(const kg_post *p, int ch) { return p->mode_cmds[ch]; }
+int kg_post_sam_mparam_(const kg_post *p, int ch) { return p->h_sam[ch].mparam; }

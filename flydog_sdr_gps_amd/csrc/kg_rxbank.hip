@@ -21,6 +21,7 @@
 // launched, no state advanced), then -- behind the one transfer -- for real.
 #include "kg_common.h"
 #include "kg_nb.h"
+#include "kg_spec.h"
 
 #include <chrono>
 #include <math.h>
@@ -48,6 +49,7 @@ struct kg_rxbank {
     int device, nrx, mode, decim_rx;
 
     size_t n;                                   // ADC samples per step
+    size_t blocks_max;                          // sound blocks a receiver can complete in one step
     hipStream_t s_main, s_side, s_tail, s_up;   // waterfall chain / audio chain / both sequential coders / the table upload
     hipStream_t s_ddc2;                         // the waterfall DDC's second stream (R = 1 bypass, pass B of R <= 8 beside the rest)
     kg_ctx *c_main, *c_side, *c_tail;
@@ -61,6 +63,17 @@ struct kg_rxbank {
     };
     std::vector<nb_cmd> nbc;
     std::vector<int32_t> nb_list, nb_cnt;       // scratch: this step's blanked receivers and their record counts
+    // the audio spectrum (`SET spc_=2`, rx/rx_sound.cpp:175-220): per receiver s->specAF_FFT != NULL, the host's mirror of
+    // s->specAF_instance / s->isChanNull and the kg_post mode commands it has seen (each clears the mirror)
+    kg_fir *nullfir;                            // m_chan_null_FIR[] (rx_sound.cpp:151), on the tail stream behind kg_post
+    std::vector<char> spec_on;
+    std::vector<kg_spec::emit_t> spec_mirror, spec_mirror2;
+    std::vector<uint32_t> spec_cmds;
+    unsigned char *d_spec; size_t spec_max;     // [spec_max][1024] u8: the step's rows in map order
+    int spec_n;                                 // rows of the last step
+    std::vector<int32_t> spec_rx, spec_inst, spec_blk, spec_rx2, spec_inst2, spec_blk2;     // the last step's map; this pass's
+    std::vector<char> sam_null;                 // scratch, per active entry: runs kg_post in channel-null SAM this step
+    std::vector<int32_t> pb_inst, pb_n, pb_base, null_row, null_list, null_each, null_inst, null_n, null_base;
     // device buffers
     short2 *d_wfiq; size_t wf_stride;           // [nrx][wf_stride] iq_t: a one-shot receiver uses pairs 0 .. 8191 of its row, an overlapped one all of it
     unsigned char *d_rows, *d_pkts;             // [frame][1024], [frame][BANK_PKT_STRIDE]
@@ -142,7 +155,8 @@ static int bank_pass(kg_rxbank *b, const void *d_adc, bool plan)
     }
     const int NA = (int) b->act.size();
     const int32_t *act = b->act.data();
-    int nrec_max = 0, nfir_max = 0;
+    int nrec_max = 0, nfir_max = 0, nspec = 0;
+    bool any_pb = false;
     if (!plan) for (int k = 0; k < NR; k++) { b->last_nrec[k] = 0; b->last_nfir[k] = 0; }
     // ---- audio chain (side stream): rx.v -> rx_iq_t -> snd_service() unpack -> CFastFIR; the tail: S-meter, CAgc, detector, ADPCM
     if (NA > 0) {
@@ -170,8 +184,37 @@ static int bank_pass(kg_rxbank *b, const void *d_adc, bool plan)
             b->tail_pending = false;
         }
         tk.lap(b, PF_EVENTS, pf);
-        if ((rc = kg_fir_process_each_dev(b->fir, act, NA, b->d_xin, b->nrec_max, b->h_nrec.data(), b->d_firo, b->firo_stride, b->h_nfir.data())))
-            return rc;
+        // which blocks of this step give a row: the reference's rule (kg_spec.h), walked on a copy of the mirror that the real
+        // pass commits.  Rows are numbered in emission order, receiver by receiver.
+        nspec = 0;
+        for (int i = 0; i < NA; i++) {
+            const int k = act[i];
+            kg_spec::emit_t m = b->spec_mirror[k];
+            if (kg_post_mode_cmds_(b->post, k) != b->spec_cmds[k]) kg_spec::emit_clear(m);
+            const int mode = kg_post_get_mode(b->post, k);
+            const bool sam_family = mode >= KG_POST_SAM && mode <= KG_POST_QAM;
+            b->sam_null[i] = mode == KG_POST_SAM && (kg_post_sam_mparam_(b->post, k) & 3);
+            const int nblk = (kg_fir_pos(b->fir, k) + b->h_nrec[i]) / KG_FIR_OUT;
+            b->pb_inst[i] = KG_SPEC_PASSBAND; b->pb_n[i] = 0; b->pb_base[i] = 0;
+            for (int blk = 0; blk < nblk; blk++) {
+                const kg_spec::rows_t r = kg_spec::emit_block(m, b->spec_on[k] != 0, sam_family, b->sam_null[i] != 0);
+                if (r.passband) {                          // only ever the leading blocks: the mirror leaves PASSBAND once per step at most
+                    if (b->pb_n[i]++ == 0) b->pb_base[i] = nspec;
+                    b->spec_rx2[nspec] = k; b->spec_inst2[nspec] = KG_SPEC_PASSBAND; b->spec_blk2[nspec] = blk; nspec++;
+                }
+                b->null_row[(size_t) i * b->blocks_max + blk] = r.chan_null ? nspec : -1;
+                if (r.chan_null) { b->spec_rx2[nspec] = k; b->spec_inst2[nspec] = KG_SPEC_CHAN_NULL; b->spec_blk2[nspec] = blk; nspec++; }
+                if (r.passband) any_pb = true;
+            }
+            b->spec_mirror2[k] = m;
+        }
+        if (any_pb) {
+            const kg_fir_spec_req req = {b->d_spec, KG_SPEC_ROW, b->spec_max * KG_SPEC_ROW, b->pb_inst.data(), b->pb_n.data(), b->pb_base.data()};
+            rc = kg_fir_process_rows_(b->fir, act, NA, b->d_xin, b->nrec_max, b->h_nrec.data(), b->d_firo, b->firo_stride, b->h_nfir.data(), &req);
+        } else {
+            rc = kg_fir_process_each_dev(b->fir, act, NA, b->d_xin, b->nrec_max, b->h_nrec.data(), b->d_firo, b->firo_stride, b->h_nfir.data());
+        }
+        if (rc) return rc;
         tk.lap(b, PF_FIR, pf);
         for (int i = 0; i < NA; i++) if (b->h_nfir[i] > nfir_max) nfir_max = b->h_nfir[i];
     }
@@ -189,6 +232,20 @@ static int bank_pass(kg_rxbank *b, const void *d_adc, bool plan)
             if ((rc = kg_post_process_dev(b->post, b->blk_list.data(), NB, b->d_firo + o, b->firo_stride, KG_FIR_OUT, b->d_s16 + o, nullptr,
                                           b->d_agc + o, b->firo_stride)))
                 return rc;
+            // rx_sound.cpp:804: the block's nulled pair through m_chan_null_FIR without an output buffer, rows on or not
+            b->null_list.clear(); b->null_n.clear(); b->null_base.clear();
+            for (int i = 0; i < NA; i++)
+                if (b->sam_null[i] && b->h_nfir[i] >= (int) (o + KG_FIR_OUT)) {
+                    const int row = b->null_row[(size_t) i * b->blocks_max + blk];
+                    b->null_list.push_back(act[i]); b->null_n.push_back(row >= 0 ? 1 : 0); b->null_base.push_back(row >= 0 ? row : 0);
+                }
+            if (!b->null_list.empty()) {
+                const int NN = (int) b->null_list.size();
+                const kg_fir_spec_req req = {b->d_spec, KG_SPEC_ROW, b->spec_max * KG_SPEC_ROW, b->null_inst.data(), b->null_n.data(), b->null_base.data()};
+                if ((rc = kg_fir_process_rows_(b->nullfir, b->null_list.data(), NN, b->d_agc + o, b->firo_stride, b->null_each.data(), nullptr, 0,
+                                               nullptr, &req)))
+                    return rc;
+            }
             tk.lap(b, PF_POST, pf);
             // the real modes' blocks go through the ADPCM coder, the stereo modes' (IS_STEREO: IQ, SAS, QAM) as (s2_t) pairs of the agc
             // buffer, where SAS / QAM leave their (L, R) pair (rx_sound.cpp:1042-1140)
@@ -295,6 +352,12 @@ static int bank_pass(kg_rxbank *b, const void *d_adc, bool plan)
             if (b->overlapped[k]) { b->ring_w[k] = b->ring_w2[k]; b->ring_total[k] = b->ring_total2[k]; }
         }
         for (int f = 0; f < nframes; f++) b->rx_of_frame[f] = b->chan_of[f];
+        for (int i = 0; i < NA; i++) {
+            b->spec_mirror[act[i]] = b->spec_mirror2[act[i]];
+            b->spec_cmds[act[i]] = kg_post_mode_cmds_(b->post, act[i]);
+        }
+        b->spec_n = nspec;
+        b->spec_rx.swap(b->spec_rx2); b->spec_inst.swap(b->spec_inst2); b->spec_blk.swap(b->spec_blk2);
         kg_rxbank_step_info &s = b->last;
         const int first = NA > 0 ? act[0] : 0;             // the step's scalar audio fields: the lowest-numbered active receiver's
         s.step = b->step; s.nframes = nframes; s.nrec = NA > 0 ? b->h_nrec[0] : 0; s.nfir = NA > 0 ? b->h_nfir[0] : 0;
@@ -441,12 +504,12 @@ void kg_rxbank_destroy(kg_rxbank *b)
     (void) hipSetDevice(b->device);
     for (hipStream_t s : {b->s_main, b->s_side, b->s_tail, b->s_ddc2, b->s_up}) if (s) (void) hipStreamSynchronize(s);
     if (b->c_main && b->c_side && b->c_tail) bank_set_arena(b, KG_ARENA_OFF);
-    kg_adpcm_destroy(b->adpcm); kg_post_destroy(b->post); kg_fir_destroy(b->fir); kg_rxddc_destroy(b->rx); kg_nb_destroy(b->nb);
+    kg_adpcm_destroy(b->adpcm); kg_post_destroy(b->post); kg_fir_destroy(b->nullfir); kg_fir_destroy(b->fir); kg_rxddc_destroy(b->rx); kg_nb_destroy(b->nb);
     kg_wf_destroy(b->wf); kg_ddc_destroy(b->ddc);
     kg_ctx_destroy(b->c_tail); kg_ctx_destroy(b->c_side); kg_ctx_destroy(b->c_main);
     (void) hipFree(b->d_wfiq); (void) hipFree(b->d_rows); (void) hipFree(b->d_pkts); (void) hipFree(b->d_raw);
     (void) hipFree(b->d_xin); (void) hipFree(b->d_firo); (void) hipFree(b->d_s16); (void) hipFree(b->d_pay);
-    (void) hipFree(b->d_agc); (void) hipFree(b->d_iqpay);
+    (void) hipFree(b->d_agc); (void) hipFree(b->d_iqpay); (void) hipFree(b->d_spec);
     if (b->h_slots) (void) hipHostFree(b->h_slots);
     (void) hipFree(b->d_slots);
     for (int i = 0; i < BANK_SLOTS; i++) for (int j = 0; j < 3; j++) if (b->ev_end[i][j]) (void) hipEventDestroy(b->ev_end[i][j]);
@@ -532,6 +595,7 @@ int kg_rxbank_create(int device, int nrx, size_t adc_samples_per_step, int rx_mo
     BANK_TRY(kg_nb_create(b->c_side, nrx, (int) b->nrec_max, &b->nb));
     BANK_TRY(kg_post_create(b->c_tail, nrx, &b->post));
     BANK_TRY(kg_adpcm_create(b->c_tail, nrx, &b->adpcm));
+    BANK_TRY(kg_fir_create(b->c_tail, nrx, KG_FIR_OUT, &b->nullfir));
     b->wf_stride = BANK_RING_PAIRS;
     b->firo_stride = ((b->nrec_max + KG_FIR_OUT - 1) / KG_FIR_OUT + 1) * KG_FIR_OUT;
     BANK_HIP(hipMalloc((void **) &b->d_wfiq, sizeof(short2) * b->wf_stride * nrx));
@@ -554,15 +618,19 @@ int kg_rxbank_create(int device, int nrx, size_t adc_samples_per_step, int rx_mo
     b->little_endian.assign(nrx, 0);
     {   // what a step's tables can take: <= 12 of them + a channel list for S-meter / AGC / detector and one for the coder per sound
         // block (a receiver can complete nrec_max / 512 + 1 blocks in a step) -- checked HERE, not found out by every later step
-        const size_t blocks_max = b->nrec_max / KG_FIR_OUT + 1;
-        if (16 + 4 * blocks_max > KG_ARENA_MAX_ENTRIES) {
+        // (+ one for the channel-null filter per sound block)
+        const size_t blocks_max = b->blocks_max = b->nrec_max / KG_FIR_OUT + 1;
+        if (16 + 5 * blocks_max > KG_ARENA_MAX_ENTRIES) {
             kg_set_error("kg_rxbank_create: %zu ADC samples per step are up to %zu sound blocks per receiver and step; the step table holds %d "
-                         "(a step of at most %zu samples)", b->n, blocks_max, (KG_ARENA_MAX_ENTRIES - 16) / 4,
-                         (size_t) ((KG_ARENA_MAX_ENTRIES - 16) / 4 - 1) * KG_FIR_OUT * (size_t) b->decim_rx);
+                         "(a step of at most %zu samples)", b->n, blocks_max, (KG_ARENA_MAX_ENTRIES - 16) / 5,
+                         (size_t) ((KG_ARENA_MAX_ENTRIES - 16) / 5 - 1) * KG_FIR_OUT * (size_t) b->decim_rx);
             kg_rxbank_destroy(b);
             return KG_ERR_INVALID;
         }
-        b->slot_bytes = (8192 + (size_t) (448 + 12 * blocks_max) * nrx + 63) & ~(size_t) 63;     // (+ 64 per receiver: the blankers' tables)
+        // (+ 64 per receiver: the blankers' tables; the audio spectrum: 12 bytes per receiver in CFastFIR's table, and per sound block
+        // the channel-null filter's table of 8 ints per receiver and its alignment)
+        b->slot_bytes = (8192 + 64 * blocks_max + (size_t) (448 + 16 + (12 + 32) * blocks_max) * nrx + 63) & ~(size_t) 63;
+        b->spec_max = 2 * blocks_max * (size_t) nrx;                         // a passband and a channel-null row per sound block
     }
     BANK_HIP(hipHostMalloc((void **) &b->h_slots, b->slot_bytes * BANK_SLOTS, hipHostMallocDefault));
     BANK_HIP(hipMalloc((void **) &b->d_slots, b->slot_bytes * BANK_SLOTS));
@@ -587,6 +655,14 @@ int kg_rxbank_create(int device, int nrx, size_t adc_samples_per_step, int rx_mo
     b->out_off.assign(nrx, 0); b->max_out.assign(nrx, 0); b->h_nw.assign(nrx, 0); b->frame_off.assign(nrx, 0);
     b->enabled.assign(nrx, 1); b->pkt_step.resize(nrx);
     b->nbc.assign(nrx, kg_rxbank::nb_cmd{});
+    BANK_HIP(hipMalloc((void **) &b->d_spec, b->spec_max * KG_SPEC_ROW));
+    BANK_HIP(hipMemset(b->d_spec, 0, b->spec_max * KG_SPEC_ROW));
+    b->spec_on.assign(nrx, 0); b->spec_mirror.assign(nrx, kg_spec::emit_t{KG_SPEC_PASSBAND}); b->spec_mirror2 = b->spec_mirror;
+    b->spec_cmds.assign(nrx, 0); b->spec_n = 0;
+    for (std::vector<int32_t> *v : {&b->spec_rx, &b->spec_inst, &b->spec_blk, &b->spec_rx2, &b->spec_inst2, &b->spec_blk2}) v->assign(b->spec_max, 0);
+    b->sam_null.assign(nrx, 0); b->pb_inst.assign(nrx, KG_SPEC_PASSBAND); b->pb_n.assign(nrx, 0); b->pb_base.assign(nrx, 0);
+    b->null_row.assign(b->blocks_max * (size_t) nrx, -1);
+    b->null_each.assign(nrx, KG_FIR_OUT); b->null_inst.assign(nrx, KG_SPEC_CHAN_NULL);
     memset(&b->arena, 0, sizeof b->arena);
     memset(&b->last, 0, sizeof b->last);
     BANK_HIP(hipDeviceSynchronize());
@@ -604,6 +680,39 @@ kg_post *kg_rxbank_post(kg_rxbank *b) { return b ? b->post : nullptr; }
 kg_adpcm *kg_rxbank_adpcm(kg_rxbank *b) { return b ? b->adpcm : nullptr; }
 kg_ctx *kg_rxbank_ctx(kg_rxbank *b) { return b ? b->c_main : nullptr; }
 kg_nb *kg_rxbank_nb(kg_rxbank *b) { return b ? b->nb : nullptr; }
+kg_fir *kg_rxbank_null_fir(kg_rxbank *b) { return b ? b->nullfir : nullptr; }
+
+// `SET spc_=%d` (rx_sound_cmd.cpp:332-339)
+int kg_rxbank_set_spec(kg_rxbank *b, int rx, int n)
+{
+    KG_REQUIRE(b && rx >= 0 && rx < b->nrx, KG_ERR_INVALID, "kg_rxbank_set_spec: receiver %d", rx);
+    b->spec_on[rx] = kg_spec::cmd_on(n) ? 1 : 0;
+    return KG_OK;
+}
+
+int kg_rxbank_spec_max(kg_rxbank *b)
+{
+    KG_REQUIRE(b != nullptr, KG_ERR_INVALID, "kg_rxbank_spec_max: null argument");
+    return (int) b->spec_max;
+}
+
+int kg_rxbank_spec_map(kg_rxbank *b, int32_t *rx_of_row, int32_t *inst_of_row, int32_t *blk_of_row)
+{
+    KG_REQUIRE(b != nullptr, KG_ERR_INVALID, "kg_rxbank_spec_map: null argument");
+    for (int r = 0; r < b->spec_n; r++) {
+        if (rx_of_row) rx_of_row[r] = b->spec_rx[r];
+        if (inst_of_row) inst_of_row[r] = b->spec_inst[r];
+        if (blk_of_row) blk_of_row[r] = b->spec_blk[r];
+    }
+    return b->spec_n;
+}
+
+int kg_rxbank_spec_rows(kg_rxbank *b, void **d_rows, size_t *row_stride)
+{
+    KG_REQUIRE(b && d_rows && row_stride, KG_ERR_INVALID, "kg_rxbank_spec_rows: null argument");
+    *d_rows = b->d_spec; *row_stride = KG_SPEC_ROW;
+    return KG_OK;
+}
 
 int kg_rxbank_set_wf(kg_rxbank *b, int rx, uint64_t phase_inc, int decim, int overlapped)
 {
@@ -651,11 +760,14 @@ int kg_rxbank_join(kg_rxbank *b, int rx)
     int rc;
     if ((rc = kg_rxddc_reset(b->rx, rx))) return rc;
     if ((rc = kg_fir_reset(b->fir, rx))) return rc;
+    if ((rc = kg_fir_reset(b->nullfir, rx))) return rc;
     if ((rc = kg_post_reset(b->post, rx))) return rc;
     if ((rc = kg_adpcm_set_state(b->adpcm, rx, 0, 0))) return rc;
     for (hipStream_t s : {b->s_side, b->s_tail}) KG_HIP(hipStreamSynchronize(s));
     b->snd_seq[rx] = 0; b->last_nrec[rx] = 0; b->last_nfir[rx] = 0;
     b->wf_set[rx] = 0; b->ring_w[rx] = 0; b->ring_total[rx] = 0;
+    b->spec_on[rx] = 0; kg_spec::emit_clear(b->spec_mirror[rx]);      // memset(snd_t): specAF_FFT NULL, isChanNull false
+    b->spec_cmds[rx] = kg_post_mode_cmds_(b->post, rx);
     b->nbc[rx] = kg_rxbank::nb_cmd{};                      // memset(snd_t) / memset(wf_inst_t): algo NB_OFF, enables and params 0;
     if ((rc = kg_wf_set_nb(b->wf, rx, 0))) return rc;     // the blankers' states stay (the reference's CNoiseProc arrays are globals)
     b->active[rx] = 1;

@@ -23,6 +23,8 @@
 // of its four outputs.
 #include "kg_common.h"
 #include "kg_fft.h"
+#include "kg_libm.h"
+#include "kg_spec.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -124,17 +126,89 @@ KG_DEV void fir_fft1024(cf (&x)[16], float2 *tile, const fir_tw &tw, int t)
 
 #define FIR_WAVES 4                          // (channel, block) pairs per workgroup
 
+// ---------------------------------------------------------------------------
+// the audio spectrum row, specAF_FFT (rx/rx_sound.cpp:175-220; csrc/kg_spec.h)
+// ---------------------------------------------------------------------------
+template <int LANE> KG_DEV unsigned quad_bcast(unsigned v)         // lane LANE of every quad of lanes, to all four
+{
+    return (unsigned) __builtin_amdgcn_mov_dpp((int) v, LANE * 0x55, 0xf, 0xf, true);
+}
+
+// Lane t holds the bytes of bins t + 64 j, four to a dword: p[m] = bytes of j = 4 m .. 4 m + 3.  Bin i goes to row[i ^ 512]
+// (rx_sound.cpp:214-215), so per j the 64 lanes' bytes are 64 consecutive bytes of the row.  A 4 x 4 byte transpose inside every
+// quad of lanes (lane 4 q + r ends with j = 4 r .. 4 r + 3 of bins 4 q .. 4 q + 3) turns sixteen byte stores per lane into four
+// dword stores.  The whole wave is active.
+KG_DEV void spec_store_row(const unsigned (&p)[4], unsigned char *__restrict__ row, int t)
+{
+    const int r = t & 3;
+    unsigned q[4];
+#pragma unroll
+    for (int m = 0; m < 4; m++) {
+        const unsigned v0 = quad_bcast<0>(p[m]), v1 = quad_bcast<1>(p[m]), v2 = quad_bcast<2>(p[m]), v3 = quad_bcast<3>(p[m]);
+        if (m == 0 || m == r) { q[0] = v0; q[1] = v1; q[2] = v2; q[3] = v3; }    // lane r' of the quad's p[r]
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const unsigned d = ((q[0] >> (8 * k)) & 0xffu) | (((q[1] >> (8 * k)) & 0xffu) << 8) | (((q[2] >> (8 * k)) & 0xffu) << 16) |
+                           (((q[3] >> (8 * k)) & 0xffu) << 24);
+        *reinterpret_cast<unsigned *>(row + (t & ~3) + 64 * ((4 * r + k) ^ 8)) = d;
+    }
+}
+
+// x[j] = bin t + 64 j of the spectrum handed to specAF_FFT -> its row
+KG_DEV void spec_row_from_regs(const cf (&x)[16], int inst, unsigned char *__restrict__ row, int t)
+{
+    const float scale = kg_spec::scale(inst);
+    unsigned p[4];
+#pragma unroll
+    for (int m = 0; m < 4; m++) {
+        p[m] = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) p[m] |= (unsigned) kg_spec::bin_byte(x[4 * m + k].x, scale) << (8 * k);
+    }
+    spec_store_row(p, row, t);
+}
+
+// One wave per row: row r from the 1024 complex floats at spec + r * spec_stride
+__global__ __launch_bounds__(64 * FIR_WAVES) void snd_spec_rows_kernel(const float2 *__restrict__ spec, long spec_stride, int nrows,
+                                                                      const int *__restrict__ inst, unsigned char *__restrict__ rows,
+                                                                      long row_stride)
+{
+    const int w = threadIdx.x >> 6, t = threadIdx.x & 63;
+    const int r = blockIdx.x * FIR_WAVES + w;
+    if (r >= nrows) return;                                            // whole wave leaves together
+    const float2 *src = spec + (long) r * spec_stride;
+    cf x[16];
+#pragma unroll
+    for (int j = 0; j < 16; j++) x[j] = kg_ld(&src[t + 64 * j]);
+    spec_row_from_regs(x, inst[r], rows + (long) r * row_stride, t);
+}
+
+// What the SPEC form of the block kernel adds: per list entry the instance, the number of leading blocks that give a row and the
+// row of its block 0, in units of row_unit bytes (block b at + 1024 b).
+struct fir_spec_args {
+    unsigned char *rows; long row_unit;
+    const int *inst, *row_n, *row_base;
+};
+struct fir_no_spec {};
+template <bool SPEC> struct fir_spec_sel { typedef fir_no_spec type; };
+template <> struct fir_spec_sel<true> { typedef fir_spec_args type; };
+
 // One wave per (list entry, block).  in: per-channel history buffers
 // [512 old | new samples...]; block b reads [512 b, 512 b + 1024).
 // TAPS: also store the extension taps of fastfir.cpp:278-302 (either pointer may be null):
 // pre = forward spectrum x m_CIC, post = the filtered spectrum, 1024 points per block.
-template <bool TAPS>
+// SPEC (an instantiation of its own: the other two compile to what they were without it): also the audio spectrum row of
+// :301-302 from the registers that hold the product of :293; out may be null (the OutBuf == NULL call of :306: no backward
+// transform).
+template <bool TAPS, bool SPEC = false>
 __global__ __launch_bounds__(64 * FIR_WAVES) void fir_block_kernel(
     const float2 *__restrict__ hist, long hist_stride, const int *__restrict__ chan_list,
     const int *__restrict__ nblk, const float2 *__restrict__ coef,     // [nchan][1024]
     const float2 *__restrict__ tab4096, float2 *__restrict__ out, long out_stride, int max_blk,
     const float *__restrict__ cic, const int *__restrict__ cic_on,     // m_CIC = the table where do_CIC_comp, else 1.0 (:156)
-    float2 *__restrict__ tap_pre, float2 *__restrict__ tap_post, long tap_stride, int by_chan /* rows of out by channel */)
+    float2 *__restrict__ tap_pre, float2 *__restrict__ tap_post, long tap_stride, int by_chan /* rows of out by channel */,
+    typename fir_spec_sel<SPEC>::type sp)
 {
     (void) max_blk;                           // the grid is sized from it; rows check their own nblk
     __shared__ __attribute__((aligned(16))) float2 tiles[FIR_WAVES][FIR_FFT];
@@ -163,6 +237,15 @@ __global__ __launch_bounds__(64 * FIR_WAVES) void fir_block_kernel(
         float2 *p = tap_post + (long) li * tap_stride + (long) FIR_FFT * blk;
 #pragma unroll
         for (int j = 0; j < 16; j++) kg_st(&p[t + 64 * j], x[j]);
+    }
+    if constexpr (SPEC) {
+        if (blk < sp.row_n[li])                                        // specAF_FFT, :301-302
+            spec_row_from_regs(x, sp.inst[li], sp.rows + (long) sp.row_base[li] * sp.row_unit + (long) FIR_FFT * blk, t);
+        if (!out) return;                                              // :306
+        // the twiddles are read again instead of staying live across the sixteen log10f (the compiler must not see the same address)
+        const float2 *tab = tab4096;
+        asm volatile("" : "+s"(tab));
+        fir_tw_load(tw, tab, t);
     }
     fir_fft1024<+1, true>(x, tile, tw, t);                             // :304
     float2 *dst = out + (long) (by_chan ? ch : li) * out_stride + (long) FIR_OUT * blk;
@@ -453,7 +536,7 @@ int kg_fir_pos(kg_fir *f, int ch)                 // FirPos(), fastfir.h:33
 
 static int fir_process_impl(kg_fir *f, const int32_t *chans, int nch, const void *d_in, size_t in_stride, int n,
                             void *d_out, size_t out_stride, int32_t *nout, void *d_pre, void *d_post, size_t tap_stride,
-                            const int32_t *n_each = nullptr);
+                            const int32_t *n_each = nullptr, const kg_fir_spec_req *spec = nullptr);
 
 int kg_fir_process_dev(kg_fir *f, const int32_t *chans, int nch, const void *d_in, size_t in_stride, int n,
                        void *d_out, size_t out_stride, int32_t *nout)
@@ -474,6 +557,45 @@ int kg_fir_process_taps_dev(kg_fir *f, const int32_t *chans, int nch, const void
                             void *d_out, size_t out_stride, int32_t *nout, void *d_pre, void *d_post, size_t tap_stride)
 {
     return fir_process_impl(f, chans, nch, d_in, in_stride, n, d_out, out_stride, nout, d_pre, d_post, tap_stride);
+}
+
+// kg_fir_process_each_dev with the audio spectrum row of every completed block (fastfir.cpp:301-302 -> rx_sound.cpp:197-218)
+int kg_fir_process_spec_dev(kg_fir *f, const int32_t *chans, int nch, const void *d_in, size_t in_stride, const int32_t *n_each,
+                            void *d_out, size_t out_stride, int32_t *nout, void *d_rows, size_t row_stride, const int32_t *inst,
+                            void *d_post, size_t tap_stride)
+{
+    KG_REQUIRE(n_each && d_rows && inst, KG_ERR_INVALID, "kg_fir_process_spec_dev: null argument");
+    KG_REQUIRE(((uintptr_t) d_rows & 3) == 0 && (row_stride & 3) == 0, KG_ERR_INVALID,
+               "kg_fir_process_spec_dev: d_rows and row_stride must be multiples of 4 bytes");
+    const kg_fir_spec_req req = {d_rows, row_stride, (size_t) -1, inst, nullptr, nullptr};
+    return fir_process_impl(f, chans, nch, d_in, in_stride, 0, d_out, out_stride, nout, nullptr, d_post, tap_stride, n_each, &req);
+}
+
+int kg_snd_spec_rows_dev(kg_ctx *ctx, const void *d_spec, size_t spec_stride, int nrows, const int32_t *inst, void *d_rows,
+                         size_t row_stride)
+{
+    int rc = kg_ctx_use(ctx);
+    if (rc) return rc;
+    KG_REQUIRE(d_spec && inst && d_rows, KG_ERR_INVALID, "kg_snd_spec_rows_dev: null argument");
+    KG_REQUIRE(nrows >= 1 && nrows <= (1 << 20), KG_ERR_INVALID, "kg_snd_spec_rows_dev: nrows %d", nrows);
+    KG_REQUIRE(((uintptr_t) d_spec & 7) == 0 && ((uintptr_t) d_rows & 3) == 0 && (row_stride & 3) == 0, KG_ERR_INVALID,
+               "kg_snd_spec_rows_dev: d_spec must be 8-byte aligned, d_rows and row_stride multiples of 4 bytes");
+    KG_REQUIRE(row_stride >= FIR_FFT || nrows == 1, KG_ERR_INVALID, "kg_snd_spec_rows_dev: row_stride %zu < 1024", row_stride);
+    for (int r = 0; r < nrows; r++)
+        KG_REQUIRE(inst[r] == kg_spec::PASSBAND || inst[r] == kg_spec::CHAN_NULL, KG_ERR_INVALID, "kg_snd_spec_rows_dev: inst[%d] = %d", r, inst[r]);
+    void *d_inst = nullptr;
+    if ((rc = kg_ctx_stage(ctx, inst, sizeof(int) * (size_t) nrows, &d_inst))) return rc;
+    KG_PLAN_ONLY(ctx);
+    hipLaunchKernelGGL(snd_spec_rows_kernel, dim3((nrows + FIR_WAVES - 1) / FIR_WAVES), dim3(64 * FIR_WAVES), 0, ctx->stream,
+                       (const float2 *) d_spec, (long) spec_stride, nrows, (const int *) d_inst, (unsigned char *) d_rows, (long) row_stride);
+    KG_HIP(hipGetLastError());
+    return KG_OK;
+}
+
+int kg_snd_spec_due(uint32_t *last_ms, uint32_t now_ms)
+{
+    KG_REQUIRE(last_ms != nullptr, KG_ERR_INVALID, "kg_snd_spec_due: null argument");
+    return kg_spec::due(last_ms, now_ms);
 }
 
 int kg_fir_refilter_dev(kg_fir *f, const int32_t *chans, int nch, const int32_t *nblk, const void *d_pre,
@@ -507,11 +629,17 @@ int kg_fir_refilter_dev(kg_fir *f, const int32_t *chans, int nch, const int32_t 
 
 }  // extern "C"
 
+int kg_fir_process_rows_(kg_fir *f, const int32_t *chans, int nch, const void *d_in, size_t in_stride, const int32_t *n_each,
+                         void *d_out, size_t out_stride, int32_t *nout, const kg_fir_spec_req *req)
+{
+    return fir_process_impl(f, chans, nch, d_in, in_stride, 0, d_out, out_stride, nout, nullptr, nullptr, 0, n_each, req);
+}
+
 static int fir_process_impl(kg_fir *f, const int32_t *chans, int nch, const void *d_in, size_t in_stride, int n,
                             void *d_out, size_t out_stride, int32_t *nout, void *d_pre, void *d_post, size_t tap_stride,
-                            const int32_t *n_each)
+                            const int32_t *n_each, const kg_fir_spec_req *spec)
 {
-    KG_REQUIRE(f && chans && d_in && d_out, KG_ERR_INVALID, "kg_fir_process_dev: null argument");
+    KG_REQUIRE(f && chans && d_in && (d_out || spec), KG_ERR_INVALID, "kg_fir_process_dev: null argument");
     int rc = kg_ctx_use(f->ctx);
     if (rc) return rc;
     KG_REQUIRE(nch >= 1 && nch <= f->nchan, KG_ERR_INVALID, "kg_fir_process_dev: nch %d", nch);
@@ -523,8 +651,9 @@ static int fir_process_impl(kg_fir *f, const int32_t *chans, int nch, const void
         }
     }
     KG_REQUIRE(n >= 0 && n <= f->max_in, KG_ERR_INVALID, "kg_fir_process_dev: n %d (max %d)", n, f->max_in);
-    std::vector<int> h_fill(nch), h_nblk(nch), h_rem(nch);
+    std::vector<int> h_fill(nch), h_nblk(nch), h_rem(nch), h_spec(spec ? 3 * (size_t) nch : 0);
     int max_blk = 0;
+    bool any_row = false;
     f->seen.assign(f->nchan, 0);                  // (a flag per channel: no quadratic search of the list)
     for (int i = 0; i < nch; i++) {
         const int ch = chans[i];
@@ -536,28 +665,43 @@ static int fir_process_impl(kg_fir *f, const int32_t *chans, int nch, const void
         const int tot = f->fill[ch] + (n_each ? n_each[i] : n);
         h_nblk[i] = tot / FIR_OUT;
         h_rem[i] = tot % FIR_OUT;
-        KG_REQUIRE((size_t) h_nblk[i] * FIR_OUT <= out_stride || h_nblk[i] == 0, KG_ERR_INVALID,
+        KG_REQUIRE(!d_out || (size_t) h_nblk[i] * FIR_OUT <= out_stride || h_nblk[i] == 0, KG_ERR_INVALID,
                    "kg_fir_process_dev: out_stride %zu < %d outputs", out_stride, h_nblk[i] * FIR_OUT);
         KG_REQUIRE(!(d_pre || d_post) || (size_t) h_nblk[i] * FIR_FFT <= tap_stride, KG_ERR_INVALID,
                    "kg_fir_process_taps_dev: tap_stride %zu < %d blocks of 1024", tap_stride, h_nblk[i]);
+        if (spec) {                               // rows: the leading row_n[i] blocks (all where null) from row row_base[i] on
+            const int rn = spec->row_n ? (spec->row_n[i] < h_nblk[i] ? spec->row_n[i] : h_nblk[i]) : h_nblk[i];
+            const int rb = spec->row_base ? spec->row_base[i] : (f->ctx->rows_by_chan ? ch : i);
+            KG_REQUIRE(spec->inst[i] == kg_spec::PASSBAND || spec->inst[i] == kg_spec::CHAN_NULL, KG_ERR_INVALID,
+                       "kg_fir_process_spec_dev: inst[%d] = %d", i, spec->inst[i]);
+            KG_REQUIRE(rn <= 0 || (rb >= 0 && (size_t) rn * FIR_FFT <= spec->rows_bytes &&
+                                   (size_t) rb * spec->row_unit <= spec->rows_bytes - (size_t) rn * FIR_FFT), KG_ERR_INVALID,
+                       "kg_fir_process_spec_dev: %d rows from row %d do not fit the row buffer", rn, rb);
+            KG_REQUIRE(rn <= 0 || spec->row_base || (size_t) rn * FIR_FFT <= spec->row_unit || nch == 1, KG_ERR_INVALID,
+                       "kg_fir_process_spec_dev: row_stride %zu < %d rows of 1024", spec->row_unit, rn);
+            h_spec[i] = spec->inst[i]; h_spec[nch + i] = rn > 0 ? rn : 0; h_spec[2 * nch + i] = rn > 0 ? rb : 0;
+            if (rn > 0) any_row = true;
+        }
         if (h_nblk[i] > max_blk) max_blk = h_nblk[i];
         if (nout) nout[i] = h_nblk[i] * FIR_OUT;
     }
     if (n == 0) return KG_OK;
     hipStream_t st = f->ctx->stream;
     // per-call tables through the context's staging ring (no stream synchronisation)
-    const int *s_list, *s_fill, *s_nblk, *s_rem, *s_each = nullptr;
+    const int *s_list, *s_fill, *s_nblk, *s_rem, *s_each = nullptr, *s_spec = nullptr;
     {
-        std::vector<int> pack((n_each ? 5 : 4) * (size_t) nch);
+        std::vector<int> pack(((n_each ? 5 : 4) + (spec ? 3 : 0)) * (size_t) nch);
         memcpy(pack.data(), chans, sizeof(int) * nch);
         memcpy(pack.data() + nch, h_fill.data(), sizeof(int) * nch);
         memcpy(pack.data() + 2 * nch, h_nblk.data(), sizeof(int) * nch);
         memcpy(pack.data() + 3 * nch, h_rem.data(), sizeof(int) * nch);
         if (n_each) memcpy(pack.data() + 4 * nch, n_each, sizeof(int) * nch);
+        if (spec) memcpy(pack.data() + (n_each ? 5 : 4) * nch, h_spec.data(), sizeof(int) * h_spec.size());
         void *base = nullptr;
         if ((rc = kg_ctx_stage(f->ctx, pack.data(), sizeof(int) * pack.size(), &base))) return rc;
         s_list = (const int *) base; s_fill = s_list + nch; s_nblk = s_list + 2 * nch; s_rem = s_list + 3 * nch;
         if (n_each) s_each = s_list + 4 * nch;
+        if (spec) s_spec = s_list + (n_each ? 5 : 4) * nch;
     }
     const int by_chan = f->ctx->rows_by_chan;
     KG_PLAN_ONLY(f->ctx);
@@ -566,17 +710,26 @@ static int fir_process_impl(kg_fir *f, const int32_t *chans, int nch, const void
     KG_HIP(hipGetLastError());
     if (max_blk > 0) {
         const dim3 grid((max_blk + FIR_WAVES - 1) / FIR_WAVES, nch);
-        if (d_pre || d_post)
+        if (spec) {
+            // (with no output, no row and no tap a block leaves nothing behind: only position and history advance, below)
+            if (d_out || any_row || d_post)
+                hipLaunchKernelGGL((fir_block_kernel<true, true>), grid, dim3(64 * FIR_WAVES), 0, st,
+                                   (const float2 *) f->d_hist, f->hist_stride, s_list, s_nblk,
+                                   (const float2 *) f->d_coef, (const float2 *) f->ctx->d_tab4096, (float2 *) d_out,
+                                   (long) out_stride, max_blk, (const float *) nullptr, (const int *) nullptr, (float2 *) nullptr, (float2 *) d_post,
+                                   (long) tap_stride, by_chan,
+                                   fir_spec_args{(unsigned char *) spec->d_rows, (long) spec->row_unit, s_spec, s_spec + nch, s_spec + 2 * nch});
+        } else if (d_pre || d_post)
             hipLaunchKernelGGL(fir_block_kernel<true>, grid, dim3(64 * FIR_WAVES), 0, st,
                                (const float2 *) f->d_hist, f->hist_stride, s_list, s_nblk,
                                (const float2 *) f->d_coef, (const float2 *) f->ctx->d_tab4096, (float2 *) d_out,
                                (long) out_stride, max_blk, (const float *) f->d_cic, (const int *) f->d_cic_on, (float2 *) d_pre, (float2 *) d_post,
-                               (long) tap_stride, by_chan);
+                               (long) tap_stride, by_chan, fir_no_spec{});
         else
             hipLaunchKernelGGL(fir_block_kernel<false>, grid, dim3(64 * FIR_WAVES), 0, st,
                                (const float2 *) f->d_hist, f->hist_stride, s_list, s_nblk,
                                (const float2 *) f->d_coef, (const float2 *) f->ctx->d_tab4096, (float2 *) d_out,
-                               (long) out_stride, max_blk, (const float *) nullptr, (const int *) nullptr, (float2 *) nullptr, (float2 *) nullptr, 0L, by_chan);
+                               (long) out_stride, max_blk, (const float *) nullptr, (const int *) nullptr, (float2 *) nullptr, (float2 *) nullptr, 0L, by_chan, fir_no_spec{});
         KG_HIP(hipGetLastError());
         hipLaunchKernelGGL(fir_shift_kernel, dim3(nch), dim3(1024), 0, st, f->d_hist, f->hist_stride,
                            s_list, s_nblk, s_rem);

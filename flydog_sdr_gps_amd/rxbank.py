@@ -91,6 +91,7 @@ class RxBank:
         self.post = borrow(Post, self.ctx, self.lib.kg_rxbank_post(h), nchan=nrx)
         self.adpcm = borrow(Adpcm, self.ctx, self.lib.kg_rxbank_adpcm(h), nchan=nrx)
         self.nb = borrow(NoiseBlanker, self.ctx, self.lib.kg_rxbank_nb(h), nchan=nrx)
+        self.null_fir = borrow(FastFir, self.ctx, self.lib.kg_rxbank_null_fir(h), nchan=nrx)     # m_chan_null_FIR[]
         b = BufsC()
         check(self.lib.kg_rxbank_buffers(h, C.byref(b)), "kg_rxbank_buffers")
         self.bufs = b
@@ -106,7 +107,7 @@ class RxBank:
         if getattr(self, "h", None):
             self.lib.kg_rxbank_destroy(self.h)
             self.h = None
-            for o in (self.ddc, self.wf, self.rxddc, self.fir, self.post, self.adpcm, self.nb, self.ctx):
+            for o in (self.ddc, self.wf, self.rxddc, self.fir, self.null_fir, self.post, self.adpcm, self.nb, self.ctx):
                 o.h = None
 
     def __del__(self):
@@ -138,6 +139,7 @@ class RxBank:
         self.rxddc.set_freq(rx, phase_inc)
         if not self.fir.setup(rx, lo, hi, 0.0, fs):
             raise ValueError("set_audio: CFastFIR::SetupParameters rejects the passband %g .. %g Hz at %g Hz (fastfir.cpp:193-200)" % (lo, hi, fs))
+        self.null_fir.setup(rx, lo, hi, 0.0, fs)         # m_chan_null_FIR is designed with it (rx_sound_cmd.cpp:274-275)
         self.post.set_am_passband(rx, lo, hi, fs)
         self.post.set_agc(rx, True, False, -100, 50, 6, 1000, fs)
         self.post.set_smeter(rx, fs)
@@ -228,6 +230,28 @@ class RxBank:
         flts = np.zeros((2, 4, 8), np.float32)
         check(self.lib.kg_rxbank_nb_cmd_state(self.h, int(rx), ptr(ints), ptr(flts)), "kg_rxbank_nb_cmd_state")
         return ints, flts
+
+    def set_spec(self, rx, n):
+        """`SET spc_=n` (rx/rx_sound_cmd.cpp:332-339): 2 (SPEC_SND_AF) switches receiver rx's audio spectrum rows on, anything else
+        off.  Call it after set_audio / join, whose connection start clears it."""
+        check(self.lib.kg_rxbank_set_spec(self.h, int(rx), int(n)), "kg_rxbank_set_spec")
+
+    def spec_map(self):
+        """-> (rx_of_row, inst_of_row, blk_of_row) of the last step's audio spectrum rows, in emission order per receiver"""
+        m = check(self.lib.kg_rxbank_spec_max(self.h), "kg_rxbank_spec_max")
+        rx_of, inst, blk = (np.zeros(m, np.int32) for _ in range(3))
+        n = check(self.lib.kg_rxbank_spec_map(self.h, ptr(rx_of), ptr(inst), ptr(blk)), "kg_rxbank_spec_map")
+        return rx_of[:n], inst[:n], blk[:n]
+
+    def spec_rows(self):
+        """-> uint8 [rows, 1024]: the last step's audio spectrum rows (after sync()), row r described by spec_map()[.][r]"""
+        n = check(self.lib.kg_rxbank_spec_map(self.h, None, None, None), "kg_rxbank_spec_map")
+        d, stride = C.c_void_p(), C.c_size_t()
+        check(self.lib.kg_rxbank_spec_rows(self.h, C.byref(d), C.byref(stride)), "kg_rxbank_spec_rows")
+        out = np.zeros((n, int(stride.value)), np.uint8)
+        if n:
+            self.ctx.download(int(d.value), out)
+        return out[:, :1024]
 
     def set_little_endian(self, rx, little_endian):
         check(self.lib.kg_rxbank_set_little_endian(self.h, int(rx), int(bool(little_endian))), "kg_rxbank_set_little_endian")

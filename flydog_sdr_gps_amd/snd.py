@@ -11,7 +11,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import Context, check, ptr, own_rows
+from ._lib import Context, check, load_library, ptr, own_rows
 
 # rescale = MPOW(2, -RXOUT_SCALE + CUTESDR_SCALE) * MPOW(10, CICF_GAIN_dB/20)  (float arithmetic)
 RESCALE = float(np.float32(2.0 ** -8) * np.float32(np.power(np.float32(10.0), np.float32(4.5 / 20.0))))
@@ -61,6 +61,40 @@ def unpack_rows_dev(ctx, d_raw, raw_stride, nsamps, nchans, d_out, out_stride, e
     check(ctx.lib.kg_dpump_unpack_rows_dev(ctx.h, C.c_void_p(int(d_raw)), int(raw_stride), int(nsamps), int(nchans),
                                            ptr(en), rescale, dc_i, dc_q, int(bool(spectral_inversion)),
                                            C.c_void_p(int(d_out)), int(out_stride)), "kg_dpump_unpack_rows_dev")
+
+
+SPEC_PASSBAND, SPEC_CHAN_NULL = 0, 1          # KG_SPEC_*: SND_INSTANCE_FFT_PASSBAND / _CHAN_NULL (rx/rx_sound.h:34-35)
+
+
+def spec_rows_dev(ctx, d_spec, spec_stride, inst, d_rows, row_stride=1024):
+    """specAF_FFT's rows (rx/rx_sound.cpp:197-216) from device spectra: row r from the 1024 complex floats at d_spec + r *
+    spec_stride with the scale of inst[r], to d_rows + r * row_stride.  Enqueue only."""
+    inst = np.ascontiguousarray(inst, np.int32)
+    check(ctx.lib.kg_snd_spec_rows_dev(ctx.h, C.c_void_p(int(d_spec)), int(spec_stride), int(inst.size), ptr(inst),
+                                       C.c_void_p(int(d_rows)), int(row_stride)), "kg_snd_spec_rows_dev")
+
+
+def spec_rows(ctx, spec, inst):
+    """The same with host arrays: spec complex64 [nrows, 1024] -> uint8 [nrows, 1024]."""
+    spec = np.ascontiguousarray(spec, np.complex64).reshape(-1, 1024)
+    out = np.zeros((spec.shape[0], 1024), np.uint8)
+    d_spec, d_rows = ctx.alloc(spec.nbytes), ctx.alloc(out.nbytes)
+    try:
+        ctx.upload(d_spec, spec)
+        spec_rows_dev(ctx, d_spec, 1024, inst, d_rows)
+        ctx.sync()
+        ctx.download(d_rows, out)
+    finally:
+        ctx.free(d_spec)
+        ctx.free(d_rows)
+    return out
+
+
+def spec_due(last_ms, now_ms):
+    """kg_snd_spec_due, the 125 ms limiter of rx_sound.cpp:186-195 -> (fires, new last_ms)"""
+    last = C.c_uint32(int(last_ms))
+    r = check(load_library().kg_snd_spec_due(C.byref(last), int(now_ms) & 0xffffffff), "kg_snd_spec_due")
+    return bool(r), int(last.value)
 
 
 class FastFir:
@@ -152,6 +186,45 @@ class FastFir:
             for d in (d_in, d_out, d_pre, d_post):
                 ctx.free(d)
         return out[:n].copy(), pre[:n // 512].copy(), post[:n // 512].copy()
+
+    def process_spec_dev(self, chans, d_in, in_stride, n_each, d_out, out_stride, d_rows, row_stride, inst, d_post=None, tap_stride=0):
+        """kg_fir_process_spec_dev on device buffers (d_out / d_post may be None) -> nout per entry.  Enqueue only."""
+        chans, n_each, inst = (np.ascontiguousarray(v, np.int32) for v in (chans, n_each, inst))
+        nout = np.zeros(chans.size, np.int32)
+        check(self.lib.kg_fir_process_spec_dev(self.h, ptr(chans), chans.size, ptr(int(d_in)), int(in_stride), ptr(n_each),
+                                               ptr(int(d_out)) if d_out else None, int(out_stride), ptr(nout), ptr(int(d_rows)),
+                                               int(row_stride), ptr(inst), ptr(int(d_post)) if d_post else None, int(tap_stride)),
+              "kg_fir_process_spec_dev")
+        return nout
+
+    def process_spec(self, ch, x, inst=SPEC_PASSBAND, want_out=True, want_post=False):
+        """ProcessData with the audio spectrum row of every completed block (fastfir.cpp:301-302 -> rx_sound.cpp:197-218), host
+        arrays: -> (out or None, rows uint8 [nblk, 1024], post [nblk, 1024] or None).  want_out=False is the OutBuf == NULL call
+        of the channel-null filter (rx_sound.cpp:804)."""
+        own_rows(self, "process_spec()")
+        x = np.ascontiguousarray(x, np.complex64)
+        maxblk = x.size // 512 + 2
+        ctx = self.ctx
+        d_in, d_out = ctx.alloc(max(x.nbytes, 8)), ctx.alloc((x.size + 512) * 8)
+        d_rows, d_post = ctx.alloc(maxblk * 1024), ctx.alloc(maxblk * 1024 * 8)
+        try:
+            ctx.upload(d_in, x)
+            nout = self.process_spec_dev([ch], d_in, max(x.size, 1), [x.size], d_out if want_out else None, x.size + 512, d_rows,
+                                         maxblk * 1024, [inst], d_post if want_post else None, maxblk * 1024)
+            ctx.sync()
+            n = int(nout[0])
+            out = np.zeros(max(n, 1), np.complex64)
+            rows, post = np.zeros((maxblk, 1024), np.uint8), np.zeros((maxblk, 1024), np.complex64)
+            if n:
+                if want_out:
+                    ctx.download(d_out, out[:n])
+                ctx.download(d_rows, rows)
+                if want_post:
+                    ctx.download(d_post, post)
+        finally:
+            for d in (d_in, d_out, d_rows, d_post):
+                ctx.free(d)
+        return (out[:n].copy() if want_out else None), rows[:n // 512].copy(), (post[:n // 512].copy() if want_post else None)
 
     def process_taps_edit(self, ch, x, edit):
         """ProcessData when a PRE_FILTERED extension rewrites the spectrum it is handed (`buf_modified`,

@@ -824,6 +824,35 @@ int kg_fir_refilter_dev(kg_fir *fir, const int32_t *chans, int nch, const int32_
  * m_pFilterCoef_CIC; kg_fir_set_coef alone uses the same array for both. */
 int kg_fir_set_coef_plain(kg_fir *fir, int ch, const float *coef_fft);
 
+/* ---------------------------------------------------------------------------
+ * The audio spectrum display, `SET spc_=2` (SPEC_SND_AF): specAF_FFT (rx/rx_sound.cpp:175-220), called from inside
+ * CFastFIR::ProcessData with the filtered spectrum of every completed block (rx/CuteSDR/fastfir.cpp:251-253, :301-302).  A row is
+ * 1024 bytes: per bin pwr = re * re (the real part only, :198), dB = 10.0 * log10f(pwr * scale + 1e-30) clamped to [-200, 0] and
+ * decremented, (u1_t) (int) dB stored at bin ^ 512 (:208-216); scale = 10 * 2 / (CUTESDR_MAX_VAL^2 * 1024^2) times 1e6 for the
+ * passband filter's rows and times 0.0004 for the channel-null filter's (:201-202).  Bytes span 55 (a zero bin) .. 255.  The device's
+ * log10f is the host libm's bit for bit, so a row is an exact function of the spectrum (csrc/kg_spec.h is the one definition for
+ * both).  NaN input is outside the contract ((int) NaN is undefined in the reference); +-inf and overflow give byte 255. */
+enum { KG_SPEC_PASSBAND = 0, KG_SPEC_CHAN_NULL = 1 };      /* SND_INSTANCE_FFT_PASSBAND, SND_INSTANCE_FFT_CHAN_NULL, rx/rx_sound.h:34-35 */
+#define KG_SPEC_ROW 1024                                   /* FFT_WIDTH, rx_sound.cpp:180 */
+/* Row r from the 1024 complex floats at d_spec + r*spec_stride (complex samples; what kg_fir_process_taps_dev wrote to d_post)
+ * with the scale of inst[r] (KG_SPEC_*), to d_rows + r*row_stride (bytes; d_rows and row_stride multiples of 4).  Enqueue only. */
+int kg_snd_spec_rows_dev(kg_ctx *ctx, const void *d_spec, size_t spec_stride, int nrows, const int32_t *inst, void *d_rows,
+                         size_t row_stride);
+/* "limit update rate" (rx_sound.cpp:186-195), host only, the clock is the caller's: returns 1 when a row handed over at now_ms is to
+ * be sent (snd_send_msg_data, :218).  Fires only when now_ms > *last_ms + 125; then *last_ms += 125 if it is non-zero, else
+ * *last_ms = now_ms.  With *last_ms = 0 at the start of a connection the first call fires only when now_ms > 125. */
+int kg_snd_spec_due(uint32_t *last_ms, uint32_t now_ms);
+/* kg_fir_process_each_dev plus the row of every completed block, formed from the registers that hold the filtered spectrum
+ * (fastfir.cpp:293 -> :301-302): block b of list entry i at d_rows + i*row_stride + 1024 b with the scale of inst[i] (on a receiver
+ * bank's objects: row chans[i], like every caller-visible buffer there).  d_post / tap_stride as in kg_fir_process_taps_dev (may be
+ * NULL / 0): the same values the bytes were formed from.  d_out may be NULL -- the OutBuf == NULL call of fastfir.cpp:306, the
+ * channel-null filter's (rx_sound.cpp:804): no backward transform, history and FirPos() advance as with an output buffer, and
+ * nout[i] / 512 still says how many blocks (rows) entry i completed.  No spectrum goes to memory unless d_post is given.
+ * d_rows and row_stride: multiples of 4 bytes.  Enqueue only. */
+int kg_fir_process_spec_dev(kg_fir *fir, const int32_t *chans, int nch, const void *d_in, size_t in_stride,
+                            const int32_t *n_each, void *d_out, size_t out_stride, int32_t *nout, void *d_rows,
+                            size_t row_stride, const int32_t *inst, void *d_post, size_t tap_stride);
+
 /* Diagnostics: re-runs the 4096-point stage of the forward FFT of `block` in a
  * stamped build of the kernel and returns 4 s_memrealtime readings (100 MHz):
  * start, inputs + twiddles loaded, transform done, results stored. */
@@ -902,6 +931,30 @@ int kg_rxbank_set_nb_gate(kg_rxbank *bank, int rx, int nb, int th, float frate);
 /* The command state of receiver rx: ints[14] = algo, snd enable[4], wf enable[4], wf nb_param_change[4], wf nb_setup; flts[64] =
  * snd nb_param[4][8], wf nb_param[4][8] (either may be NULL). */
 int kg_rxbank_nb_cmd_state(kg_rxbank *bank, int rx, int32_t *ints, float *flts);
+/* The audio spectrum rows of the bank's receivers (see kg_snd_spec_rows_dev).
+ *   kg_rxbank_set_spec   `SET spc_=%d` (rx_sound_cmd.cpp:332-339): n outside 0..2 becomes 0; only 2 (SPEC_SND_AF) switches the
+ *                        receiver's rows on.  kg_rxbank_join clears it.
+ *   kg_rxbank_null_fir   the bank's second kg_fir, m_chan_null_FIR[] (rx_sound.cpp:151): the host designs it together with the
+ *                        passband filter (kg_fir_setup on both, rx_sound_cmd.cpp:274-275).  kg_rxbank_join resets the receiver's
+ *                        channel in it.  A receiver that reaches channel-null SAM without a filter there fails the step.
+ * A step's one CFastFIR launch gives the passband rows.  Behind a sound block's kg_post pass, every receiver that ran it in
+ * KG_POST_SAM with mparam & 3 feeds that block's 512 nulled AGC samples (bufs.agc) to the channel-null filter without an output
+ * buffer, whether its rows are on or not (rx_sound.cpp:804).  Which blocks give a row is the reference's rule, kept per receiver
+ * on the host as a mirror of s->specAF_instance / s->isChanNull (rx_sound_cmd.cpp:227-228, rx_sound.cpp:802-803): cleared by every
+ * kg_post_set_mode and kg_post_set_sam_mparam on the bank's kg_post, set behind a processed block to mode == SAM && (mparam & 3).
+ * A passband block gives a row (x 1e6) only while the mirror says PASSBAND at that block -- the first block after entering
+ * channel-null SAM still does; the channel-null filter gives one (x 0.0004) per 1024-sample fill of its own.
+ *   kg_rxbank_spec_map   the rows of the last step, row r at d_rows + r*row_stride: receiver, KG_SPEC_* instance and sound block of
+ *                        the step (arrays of kg_rxbank_spec_max() entries, any may be NULL), per receiver in the reference's
+ *                        emission order -- a block's passband row, then the channel-null row completed by feeding that block.
+ *                        Returns the number of rows.  The host sends each behind kg_snd_spec_due.
+ *   kg_rxbank_spec_rows  the device buffer (valid until kg_rxbank_destroy; read behind kg_rxbank_sync).
+ * A step in which no receiver has its rows on and none is in channel-null SAM enqueues what it enqueued without any of this. */
+int kg_rxbank_set_spec(kg_rxbank *bank, int rx, int n);
+kg_fir *kg_rxbank_null_fir(kg_rxbank *bank);
+int kg_rxbank_spec_max(kg_rxbank *bank);
+int kg_rxbank_spec_map(kg_rxbank *bank, int32_t *rx_of_row, int32_t *inst_of_row, int32_t *blk_of_row);
+int kg_rxbank_spec_rows(kg_rxbank *bank, void **d_rows, size_t *row_stride);
 /* CmdSetWFFreq + CmdSetWFDecim + the sampler mode sample_wf() decides on (rx/rx_waterfall.cpp:962-1008):
  *   overlapped == 0   CmdWFReset + the one-shot sampler every step: the non-overlapped frame (:1005-1041); needs
  *                     8192 * decim <= adc_samples_per_step
