@@ -29,6 +29,10 @@ void kg_set_error(const char *fmt, ...);
         }                                                                          \
     } while (0)
 
+// A caller's device pointer (NULL passes: optional buffers) sits at a multiple of `a` bytes, a power of two: the width of the
+// widest load or store a kernel makes through it (include/kiwigpu.h states the rule per entry point).
+#define KG_ALIGNED(p, a) ((((uintptr_t) (p)) & ((uintptr_t) (a) - 1)) == 0)
+
 // One step's small tables of EVERY stage of a receiver bank in one pinned host block, uploaded with ONE transfer
 // (kg_rxbank.hip).  While a context's `arena` is set and active, kg_ctx_stage / kg_ctx_stage_cached[_ways] neither copy
 // nor cache: in the PLAN pass they append the table to the host block and answer the address it will have on the

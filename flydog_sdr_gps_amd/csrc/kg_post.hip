@@ -1569,6 +1569,8 @@ int kg_post_process_dev(kg_post *p, const int32_t *chans, int nch, const void *d
                "kg_post_process_dev: nsamps %d (1..%d)", nsamps, KG_POST_MAX_SAMPLES);
     KG_REQUIRE(in_stride >= (size_t) nsamps && out_stride >= (size_t) nsamps, KG_ERR_INVALID,
                "kg_post_process_dev: stride smaller than nsamps");
+    KG_REQUIRE(KG_ALIGNED(d_fir, 8) && KG_ALIGNED(d_s16, 2) && KG_ALIGNED(d_demod, 4) && KG_ALIGNED(d_agc, 8), KG_ERR_INVALID,
+               "kg_post_process_dev: misaligned pointer (d_fir and d_agc 8 bytes, d_demod 4, d_s16 2)");
     std::vector<char> seen(p->nchan, 0);
     bool any_sam = false, any_nr = false, any_nrs = false, any_nbw = false;
     for (int i = 0; i < nch; i++) {
@@ -1668,6 +1670,8 @@ int kg_post_cfir_process_dev(kg_post *p, const int32_t *chans, int nch, int whic
     int rc = kg_ctx_use(p->ctx);
     if (rc || (rc = post_which(which, false, "kg_post_cfir_process_dev"))) return rc;
     KG_REQUIRE(kind >= KG_CFIR_REAL_REAL && kind <= KG_CFIR_MONO16_MONO16, KG_ERR_INVALID, "kg_post_cfir_process_dev: kind %d", kind);
+    KG_REQUIRE(KG_ALIGNED(d_in, kind == KG_CFIR_MONO16_MONO16 ? 2 : 4) && KG_ALIGNED(d_out, kind == KG_CFIR_REAL_REAL ? 4 : 2), KG_ERR_INVALID,
+               "kg_post_cfir_process_dev: misaligned pointer (float rows 4 bytes, int16 rows 2)");
     KG_REQUIRE(nsamps >= 1 && nsamps <= KG_POST_MAX_SAMPLES && in_stride >= (size_t) nsamps && out_stride >= (size_t) nsamps, KG_ERR_INVALID,
                "kg_post_cfir_process_dev: nsamps %d (1..%d), strides %zu / %zu", nsamps, KG_POST_MAX_SAMPLES, in_stride, out_stride);
     void *d_list = nullptr;
@@ -1691,6 +1695,7 @@ int kg_post_squelch_perform_dev(kg_post *p, const int32_t *chans, int nch, const
     KG_REQUIRE(nsamps >= 1 && nsamps <= KG_POST_MAX_SAMPLES && in_stride >= (size_t) nsamps && out_stride >= (size_t) nsamps, KG_ERR_INVALID,
                "kg_post_squelch_perform_dev: nsamps %d (1..%d; squelch.cpp:155 returns at once past 1024), strides %zu / %zu", nsamps,
                KG_POST_MAX_SAMPLES, in_stride, out_stride);
+    KG_REQUIRE(KG_ALIGNED(d_in, 4) && KG_ALIGNED(d_out, 2), KG_ERR_INVALID, "kg_post_squelch_perform_dev: misaligned pointer (d_in 4 bytes, d_out 2)");
     void *d_list = nullptr;
     if ((rc = post_list(p, chans, nch, "kg_post_squelch_perform_dev", &d_list))) return rc;
     for (int i = 0; i < nch; i++)
@@ -1936,6 +1941,7 @@ int kg_post_nrs_process_dev(kg_post *p, const int32_t *chans, int nch, const voi
                             size_t out_stride)
 {
     KG_REQUIRE(p && chans && d_in && d_out, KG_ERR_INVALID, "kg_post_nrs_process_dev: null argument");
+    KG_REQUIRE(KG_ALIGNED(d_in, 2) && KG_ALIGNED(d_out, 2), KG_ERR_INVALID, "kg_post_nrs_process_dev: int16 rows must be 2-byte aligned");
     int rc = kg_ctx_use(p->ctx);
     if (rc) return rc;
     KG_REQUIRE(nsamps >= kg_nrs::FFT_FULL && nsamps <= KG_NRS_MAX_SAMPLES && nsamps % kg_nrs::FFT_FULL == 0 && in_stride >= (size_t) nsamps &&
@@ -2014,6 +2020,7 @@ int kg_post_nbw_process_dev(kg_post *p, const int32_t *chans, int nch, const voi
                             size_t out_stride)
 {
     KG_REQUIRE(p && chans && d_in && d_out, KG_ERR_INVALID, "kg_post_nbw_process_dev: null argument");
+    KG_REQUIRE(KG_ALIGNED(d_in, 2) && KG_ALIGNED(d_out, 2), KG_ERR_INVALID, "kg_post_nbw_process_dev: int16 rows must be 2-byte aligned");
     int rc = kg_ctx_use(p->ctx);
     if (rc) return rc;
     KG_REQUIRE(nsamps >= kg_nbw::BLOCK && nsamps <= KG_NBW_MAX_SAMPLES && nsamps % kg_nbw::BLOCK == 0 && in_stride >= (size_t) nsamps &&
@@ -2058,6 +2065,7 @@ int kg_post_nr_process_dev(kg_post *p, const int32_t *chans, int nch, int type, 
                            void *d_out, size_t out_stride)
 {
     KG_REQUIRE(p && chans && d_in && d_out, KG_ERR_INVALID, "kg_post_nr_process_dev: null argument");
+    KG_REQUIRE(KG_ALIGNED(d_in, 2) && KG_ALIGNED(d_out, 2), KG_ERR_INVALID, "kg_post_nr_process_dev: int16 rows must be 2-byte aligned");
     int rc = kg_ctx_use(p->ctx);
     if (rc) return rc;
     KG_REQUIRE(type == KG_NR_DENOISE || type == KG_NR_AUTONOTCH, KG_ERR_INVALID, "kg_post_nr_process_dev: type %d", type);

@@ -536,7 +536,8 @@ int kg_fir_pos(kg_fir *f, int ch)                 // FirPos(), fastfir.h:33
 
 static int fir_process_impl(kg_fir *f, const int32_t *chans, int nch, const void *d_in, size_t in_stride, int n,
                             void *d_out, size_t out_stride, int32_t *nout, void *d_pre, void *d_post, size_t tap_stride,
-                            const int32_t *n_each = nullptr, const kg_fir_spec_req *spec = nullptr);
+                            const int32_t *n_each = nullptr, const kg_fir_spec_req *spec = nullptr,
+                            const char *who = "kg_fir_process_dev");
 
 int kg_fir_process_dev(kg_fir *f, const int32_t *chans, int nch, const void *d_in, size_t in_stride, int n,
                        void *d_out, size_t out_stride, int32_t *nout)
@@ -550,13 +551,15 @@ int kg_fir_process_each_dev(kg_fir *f, const int32_t *chans, int nch, const void
                             void *d_out, size_t out_stride, int32_t *nout)
 {
     KG_REQUIRE(n_each != nullptr, KG_ERR_INVALID, "kg_fir_process_each_dev: null argument");
-    return fir_process_impl(f, chans, nch, d_in, in_stride, 0, d_out, out_stride, nout, nullptr, nullptr, 0, n_each);
+    return fir_process_impl(f, chans, nch, d_in, in_stride, 0, d_out, out_stride, nout, nullptr, nullptr, 0, n_each, nullptr,
+                            "kg_fir_process_each_dev");
 }
 
 int kg_fir_process_taps_dev(kg_fir *f, const int32_t *chans, int nch, const void *d_in, size_t in_stride, int n,
                             void *d_out, size_t out_stride, int32_t *nout, void *d_pre, void *d_post, size_t tap_stride)
 {
-    return fir_process_impl(f, chans, nch, d_in, in_stride, n, d_out, out_stride, nout, d_pre, d_post, tap_stride);
+    return fir_process_impl(f, chans, nch, d_in, in_stride, n, d_out, out_stride, nout, d_pre, d_post, tap_stride, nullptr, nullptr,
+                            "kg_fir_process_taps_dev");
 }
 
 // kg_fir_process_each_dev with the audio spectrum row of every completed block (fastfir.cpp:301-302 -> rx_sound.cpp:197-218)
@@ -568,7 +571,8 @@ int kg_fir_process_spec_dev(kg_fir *f, const int32_t *chans, int nch, const void
     KG_REQUIRE(((uintptr_t) d_rows & 3) == 0 && (row_stride & 3) == 0, KG_ERR_INVALID,
                "kg_fir_process_spec_dev: d_rows and row_stride must be multiples of 4 bytes");
     const kg_fir_spec_req req = {d_rows, row_stride, (size_t) -1, inst, nullptr, nullptr};
-    return fir_process_impl(f, chans, nch, d_in, in_stride, 0, d_out, out_stride, nout, nullptr, d_post, tap_stride, n_each, &req);
+    return fir_process_impl(f, chans, nch, d_in, in_stride, 0, d_out, out_stride, nout, nullptr, d_post, tap_stride, n_each, &req,
+                            "kg_fir_process_spec_dev");
 }
 
 int kg_snd_spec_rows_dev(kg_ctx *ctx, const void *d_spec, size_t spec_stride, int nrows, const int32_t *inst, void *d_rows,
@@ -605,6 +609,7 @@ int kg_fir_refilter_dev(kg_fir *f, const int32_t *chans, int nch, const int32_t 
     int rc = kg_ctx_use(f->ctx);
     if (rc) return rc;
     KG_REQUIRE(nch >= 1 && nch <= f->nchan, KG_ERR_INVALID, "kg_fir_refilter_dev: nch %d", nch);
+    KG_REQUIRE(KG_ALIGNED(d_pre, 8) && KG_ALIGNED(d_out, 8), KG_ERR_INVALID, "kg_fir_refilter_dev: complex-float buffers must be 8-byte aligned");
     int max_blk = 0;
     for (int i = 0; i < nch; i++) {
         KG_REQUIRE(chans[i] >= 0 && chans[i] < f->nchan && f->coef_set[chans[i]], KG_ERR_STATE,
@@ -632,17 +637,22 @@ int kg_fir_refilter_dev(kg_fir *f, const int32_t *chans, int nch, const int32_t 
 int kg_fir_process_rows_(kg_fir *f, const int32_t *chans, int nch, const void *d_in, size_t in_stride, const int32_t *n_each,
                          void *d_out, size_t out_stride, int32_t *nout, const kg_fir_spec_req *req)
 {
-    return fir_process_impl(f, chans, nch, d_in, in_stride, 0, d_out, out_stride, nout, nullptr, nullptr, 0, n_each, req);
+    return fir_process_impl(f, chans, nch, d_in, in_stride, 0, d_out, out_stride, nout, nullptr, nullptr, 0, n_each, req,
+                            "kg_fir_process_rows_");
 }
 
 static int fir_process_impl(kg_fir *f, const int32_t *chans, int nch, const void *d_in, size_t in_stride, int n,
                             void *d_out, size_t out_stride, int32_t *nout, void *d_pre, void *d_post, size_t tap_stride,
-                            const int32_t *n_each, const kg_fir_spec_req *spec)
+                            const int32_t *n_each, const kg_fir_spec_req *spec, const char *who)
 {
     KG_REQUIRE(f && chans && d_in && (d_out || spec), KG_ERR_INVALID, "kg_fir_process_dev: null argument");
     int rc = kg_ctx_use(f->ctx);
     if (rc) return rc;
     KG_REQUIRE(nch >= 1 && nch <= f->nchan, KG_ERR_INVALID, "kg_fir_process_dev: nch %d", nch);
+    const void *const bufs[4] = {d_in, d_out, d_pre, d_post};
+    static const char *const buf_name[4] = {"d_in", "d_out", "d_pre", "d_post"};
+    for (int k = 0; k < 4; k++)
+        KG_REQUIRE(KG_ALIGNED(bufs[k], 8), KG_ERR_INVALID, "%s: %s is not 8-byte aligned (complex floats)", who, buf_name[k]);
     if (n_each) {                                 // every entry its own InLength: n = the largest
         n = 0;
         for (int i = 0; i < nch; i++) {

@@ -18,6 +18,12 @@
  *     (where they return results) synchronise;
  *   - the library owns all device memory it allocates; callers keep ownership
  *     of every buffer they pass in;
+ *   - footprint of a "_dev" call: it reads only the stated extent of every input row and writes only the stated extent of every
+ *     output row (a row with count 0, a disabled channel, an output a mode does not produce: nothing); the bytes between a row's
+ *     extent and its stride, in front of row 0 and behind the last row are neither read nor written, no input is written unless
+ *     the call is told to work in place, and no output depends on what its buffer held before.  Each entry point states the
+ *     alignment its pointers and strides need; a pointer that misses it is refused with KG_ERR_INVALID and nothing is enqueued
+ *     (tests/test_containment_*_gpu.py hold every entry point to this, at exactly that alignment);
  *   - there is NO CPU fallback: without a usable gfx950 device kg_ctx_create
  *     fails with KG_ERR_NO_DEVICE.
  *   - the reference runs this path from cooperative coroutines on one host
@@ -154,7 +160,9 @@ int kg_acq_get_code_fft(kg_acq *acq, int sat, float *code_fft);      /* natural 
 int kg_acq_sample_bits(kg_acq *acq, int block, const uint8_t *packed);
 int kg_acq_sample_bits_dev(kg_acq *acq, int block, const void *d_packed);
 /* Extension (BASELINE.json configs[1]): NSAMPLES complex int16 samples
- * (i,q interleaved) at the FS/4 IF; mix by (-j)^n, then as Sample(). */
+ * (i,q interleaved) at the FS/4 IF; mix by (-j)^n, then as Sample().
+ * _dev forms read nsamples / 8 bytes at d_packed (any address) resp. 4 * nsamples bytes per block at d_iq (d_iq and stride_bytes
+ * multiples of 4) and write no caller memory. */
 int kg_acq_sample_iq16(kg_acq *acq, int block, const int16_t *iq);
 int kg_acq_sample_iq16_dev(kg_acq *acq, int block, const void *d_iq);
 /* nblocks consecutive blocks from one device array, block b at d_iq + b*stride_bytes:
@@ -232,7 +240,9 @@ int kg_wf_set_channel(kg_wf *wf, int ch, const kg_wf_chan_cfg *cfg, const uint16
 /* nframes frames; frame f belongs to channel chan_of[f] (host array), its input is
  * iq[f][8192] {int16 i, int16 q} (struct iq_t, :95-97) and its output out[f][1024]
  * bytes (wf_pkt_t.un.buf).  _dev: device pointers, enqueue only.  A frame's start is
- * kept as a 32-bit sample offset: nframes <= 524288 (2^32 / 8192) per call. */
+ * kept as a 32-bit sample offset: nframes <= 524288 (2^32 / 8192) per call.
+ * Alignment (all three _dev forms): d_iq 8 bytes (with even frame_off every frame then is), d_out 4 bytes (kg_wf_nb_frames_dev: 8).
+ * Read: the 8192 pairs of each listed frame, nothing between or around frames; written: 1024 bytes per frame at d_out + 1024 f. */
 int kg_wf_frames_dev(kg_wf *wf, int nframes, const int32_t *chan_of, const void *d_iq, void *d_out);
 int kg_wf_frames(kg_wf *wf, int nframes, const int32_t *chan_of, const int16_t *iq, uint8_t *out);
 /* The same for frames that are NOT back to back: frame f starts frame_off[f] samples (iq_t pairs; even,
@@ -295,8 +305,11 @@ long kg_ddc_wf_outputs(kg_ddc *ddc, int ch, size_t n);
  * d_out + i*out_stride (in pairs); nouts[i] (may be NULL) receives the count.
  * State (NCO phase, CIC registers, decimation phase) carries over to the next
  * call, so a stream may be pushed in pieces of any length.  Enqueue only.
- * d_adc and the rows may sit at any 2- / 4-byte alignment; R = 1 channels are fastest (16-byte stores) when d_adc is
- * 8-byte aligned and every row 16-byte aligned, i.e. d_out 16-byte aligned and out_stride a multiple of 4. */
+ * d_adc and the rows may sit at any 2- / 4-byte alignment (d_adc a multiple of 2, d_out of 4, any out_stride); R = 1 channels are
+ * fastest (16-byte stores) when d_adc is 8-byte aligned and every row 16-byte aligned, i.e. d_out 16-byte aligned and out_stride
+ * a multiple of 4.  Read: n samples at d_adc; written: the nouts[i] pairs of row i and nothing else, at either alignment (a 16-byte
+ * store never runs past the last pair).  The same holds for kg_ddc_wf_capture_dev (min(max_out, n >> log2 R) pairs per row) and
+ * kg_ddc_wf_step_dev (pairs out_off[i] .. out_off[i] + nouts[i] of row i: the pairs in front of out_off[i] are not written either). */
 int kg_ddc_wf_push_dev(kg_ddc *ddc, const void *d_adc, size_t n, const int32_t *chan_list,
                        int nlist, void *d_out, size_t out_stride, int64_t *nouts);
 /* The reference's NON-OVERLAPPED waterfall frame (sample_wf(), rx/rx_waterfall.cpp:1005-1041): CmdWFReset with
@@ -362,7 +375,9 @@ long kg_rxddc_outputs(kg_rxddc *ddc, int ch, size_t n);     /* records the next 
 /* n ADC samples (device int16 array) through the listed channels: channel
  * chan_list[i] writes nouts[i] rx_iq_t records {u16 i, u16 q, u8 q3, u8 i3}
  * (rx/data_pump.h:27-30) to d_out + i*out_stride records.  State carries over
- * between calls.  Enqueue only. */
+ * between calls.  Enqueue only.  d_adc and d_out: multiples of 2 bytes (a record is 6 bytes: rows are 2-byte aligned at any
+ * out_stride).  Read: n samples at d_adc and nothing behind them (16 bytes at a time where a run of the stream starts at a
+ * 16-byte address, sample by sample elsewhere).  Written: 6 * nouts[i] bytes of row i. */
 int kg_rxddc_push_dev(kg_rxddc *ddc, const void *d_adc, size_t n, const int32_t *chan_list,
                       int nlist, void *d_out, size_t out_stride, int32_t *nouts);
 
@@ -374,7 +389,9 @@ int kg_rxddc_push_dev(kg_rxddc *ddc, const void *d_adc, size_t n, const int32_t 
  * -> out[ch][nsamps] TYPECPX: re = q*rescale + DC_offset_I, im = i*rescale +
  * DC_offset_Q (I and Q as given when spectral_inversion).  enabled[ch] == 0 leaves
  * that channel's output untouched (rx_channels[ch].data_enabled).  Device buffers;
- * enabled is a host array.  Synchronous. */
+ * enabled is a host array.  Synchronous.  d_raw: a multiple of 2 bytes, d_out of 8 (out_stride in complex samples; both unpack
+ * calls).  Read: the 6 * nsamps bytes of each record row (here: 6 * nsamps * nchans bytes); written: 8 * nsamps bytes of every
+ * enabled channel's row. */
 int kg_dpump_unpack_dev(kg_ctx *ctx, const void *d_raw, int nsamps, int nchans,
                         const uint8_t *enabled, float rescale, float dc_i, float dc_q,
                         int spectral_inversion, void *d_out, size_t out_stride);
@@ -413,7 +430,9 @@ int kg_fir_pos(kg_fir *fir, int ch);                        /* CFastFIR::FirPos(
 int kg_fir_process(kg_fir *fir, int ch, const float *in, int n, float *out);
 /* The same for a list of channels at once, device buffers: channel chans[i] takes
  * n samples from d_in + i*in_stride and writes nout[i] samples to d_out + i*out_stride
- * (strides in complex samples).  Enqueue only. */
+ * (strides in complex samples).  Enqueue only.  Every device buffer of the kg_fir_*_dev calls (d_in, d_out, d_pre, d_post) is read
+ * and written as complex floats: 8-byte aligned, else KG_ERR_INVALID.  Read: n (n_each[i]) samples of row i; written: 8 * nout[i]
+ * bytes of row i, nothing for a row that completes no block. */
 int kg_fir_process_dev(kg_fir *fir, const int32_t *chans, int nch, const void *d_in,
                        size_t in_stride, int n, void *d_out, size_t out_stride, int32_t *nout);
 /* The same with an InLength of its own for every listed channel (n_each[i] >= 0 samples at row i of d_in): connections whose
@@ -445,7 +464,8 @@ int kg_nb_setup(kg_nb *nb, int ch, float sample_rate, const float *nb_param /* [
 /* ProcessBlanker(n_each[i], in, out) (noiseproc.cpp:147-203) on complex floats (TYPECPX) for each listed channel: n_each[i] >= 0
  * samples from row i of d_in to row i of d_out (rows chans[i] on a receiver bank's context, kg_ctx::rows_by_chan; strides in
  * complex samples; d_in == d_out allowed).  A channel that was never set up is refused with KG_ERR_STATE (the reference's rings
- * are uninitialised there).  Nothing is launched when every count is 0.  Enqueue only. */
+ * are uninitialised there).  Nothing is launched when every count is 0.  Enqueue only.  d_in and d_out: 8-byte aligned; in place
+ * needs in_stride == out_stride.  Read and written: 8 * n_each[i] bytes of row i. */
 int kg_nb_process_dev(kg_nb *nb, const int32_t *chans, int nch, const void *d_in, size_t in_stride, const int32_t *n_each,
                       void *d_out, size_t out_stride);
 /* The same for one channel with host buffers; synchronous (in == out allowed). */
@@ -502,7 +522,7 @@ int kg_post_get_mode(kg_post *post, int chan);              /* -> KG_POST_*, or 
  * normal); KG_MATH_EXPF: aperture_auto()'s IIR gain (rx/rx_waterfall.cpp:1199).  The reference calls the platform's libm; the device
  * functions restate the GNU C Library 2.35 algorithms of this image (csrc/kg_libm.h) and equal them bit for bit on every argument
  * (tests/test_libm_gpu.py, tools/check_libm.py --exhaustive), which is what makes the audio chain's outputs the reference's own bits.
- * Enqueue only. */
+ * Enqueue only.  d_x, d_y (and kg_math_atan2f_dev's three arrays): 4-byte aligned; 4 * n bytes read resp. written. */
 enum { KG_MATH_LOG10F = 0, KG_MATH_POWF = 1, KG_MATH_EXPF = 2,
        KG_MATH_SINF = 3, KG_MATH_COSF = 4 };   /* the SAM PLL's sinf / cosf of its phase error (rx/wdsp/SAM_demod.cpp:218-219) */
 int kg_math_dev(kg_ctx *ctx, int fn, float base, const void *d_x, uint32_t first_bits, size_t n, void *d_y);
@@ -532,7 +552,11 @@ int kg_post_sam_state(kg_post *post, const int32_t *chans, int nch, float *carri
  * mode but IQ, SAS and QAM), d_demod (float: the detector's output, AM / NBFM), d_agc (complex float: the AGC's output,
  * every mode but SSB; in SAS / QAM the stereo pair and in channel-null SAM the nulled pair written over it, rx_sound.cpp:802).  Float -> mono16 is
  * the reference's (TYPEMONO16) cast: truncation; outside the int16 range (undefined in
- * C) the low 16 bits of the int32 conversion, as x86 does.  Enqueue only. */
+ * C) the low 16 bits of the int32 conversion, as x86 does.  Enqueue only.
+ * Alignment: d_fir and d_agc 8 bytes, d_demod 4, d_s16 2 (each dereferenced as its element type; in_stride / out_stride in
+ * elements, ONE out_stride for the three outputs), else KG_ERR_INVALID.  Read: nsamps samples of row i of d_fir.  Written: nsamps
+ * elements of row i of each output the channel's mode produces; a row of an output the mode does NOT produce is not written at
+ * all -- d_s16 in IQ / SAS / QAM, d_demod in every mode but AM / NBFM, d_agc in SSB -- and keeps what the caller left there. */
 int kg_post_process_dev(kg_post *post, const int32_t *chans, int nch, const void *d_fir, size_t in_stride,
                         int nsamps, void *d_s16, void *d_demod, void *d_agc, size_t out_stride);
 /* The noise-reduction switch of c2s_sound() (rx/rx_sound.cpp:933-949), after the de-emphasis filter and the NBFM squelch, in place
@@ -568,7 +592,9 @@ int kg_post_set_nr_enable(kg_post *post, int chan, int type, int en);
 int kg_post_set_nr_param(kg_post *post, int chan, int type, int param, float pval);
 /* The standalone call site: wdsp_ANR_filter(ch, type, ...) or m_LMS[ch][type].ProcessFilter(...) under each listed channel's current
  * algo (KG_NR_WDSP or KG_NR_ORIG, else KG_ERR_STATE), whatever its enables and mode: nsamps int16 at row i of d_in -> row i of d_out
- * (d_in == d_out allowed).  The same device code as the fused pass.  Enqueue only. */
+ * (d_in == d_out allowed).  The same device code as the fused pass.  Enqueue only.  The three standalone stages (this one,
+ * kg_post_nrs_process_dev, kg_post_nbw_process_dev): d_in and d_out 2-byte aligned, strides in int16 elements; read and written:
+ * 2 * nsamps bytes of row i. */
 int kg_post_nr_process_dev(kg_post *post, const int32_t *chans, int nch, int type, const void *d_in, size_t in_stride, int nsamps,
                            void *d_out, size_t out_stride);
 /* The filter states of `type` for the listed channels, any output may be NULL: anr_i[3 i ..] = wdsp in_idx, taps, delay;
@@ -658,11 +684,13 @@ int kg_post_cfir_get_taps(kg_post *post, int chan, int which, float *taps);    /
 /* m_*_FIR[chan].ProcessFilter(nsamps, in, out) on its own, for a list of channels (rows in_stride / out_stride elements apart;
  * float or int16 by `kind`; in == out allowed): the same device code as inside kg_post_process_dev.  The sums run in the
  * reference's order (fir.cpp:79-91: over the circular buffer's positions, so the first tap of the sum rotates with the
- * write position): bit-exact.  Enqueue only. */
+ * write position): bit-exact.  Enqueue only.  Float rows 4-byte aligned, int16 rows 2-byte (by `kind`, in and out each), else
+ * KG_ERR_INVALID; nsamps elements of row i read and written. */
 int kg_post_cfir_process_dev(kg_post *post, const int32_t *chans, int nch, int which, int kind, const void *d_in, size_t in_stride,
                              int nsamps, void *d_out, size_t out_stride);
 /* m_Squelch[chan].PerformFMSquelch(nsamps, in, out) on its own (squelch.cpp:151-231): float detector samples -> mono16 (1 when
- * squelched); the return values through kg_post_squelch_state.  Enqueue only. */
+ * squelched); the return values through kg_post_squelch_state.  Enqueue only.  d_in 4-byte aligned (4 * nsamps bytes of row i
+ * read), d_out 2-byte (2 * nsamps bytes written). */
 int kg_post_squelch_perform_dev(kg_post *post, const int32_t *chans, int nch, const void *d_in, size_t in_stride, int nsamps,
                                 void *d_out, size_t out_stride);
 /* The post-AM-detector filter as a passband change designs it (rx/rx_sound_cmd.cpp:248-250, 268-282): the cuts clamped to
@@ -707,17 +735,19 @@ int kg_adpcm_set_state(kg_adpcm *a, int chan, int index, int previous);
 int kg_adpcm_get_state(kg_adpcm *a, int chan, int *index, int *previous);
 /* encode_ima_adpcm_i16_e8(out_samps_s2, bp_real_u1, ns_out, &s->adpcm_snd) (ima_adpcm.cpp:185-197,
  * rx/rx_sound.cpp:1122) for a list of channels: row i of d_s16 (int16, in_stride samples apart)
- * -> nsamps/2 bytes at d_out + i*out_stride (bytes).  nsamps even.  Enqueue only. */
+ * -> nsamps/2 bytes at d_out + i*out_stride (bytes).  nsamps even.  Enqueue only.  d_s16: a multiple of 2 bytes; d_out and
+ * out_stride: any. */
 int kg_adpcm_encode_dev(kg_adpcm *a, const int32_t *chans, int nch, const void *d_s16, size_t in_stride,
                         int nsamps, void *d_out, size_t out_stride);
 /* The uncompressed payload (rx/rx_sound.cpp:1126-1140): int16 rows copied as they are
- * (little_endian != 0) or byte-swapped to network order.  Enqueue only. */
+ * (little_endian != 0) or byte-swapped to network order.  Enqueue only.  d_s16, d_out and out_stride (bytes): multiples of 2;
+ * 2 * nsamps bytes of row i read and written. */
 int kg_snd_payload_dev(kg_ctx *ctx, const void *d_s16, size_t in_stride, int nch, int nsamps,
                        int little_endian, void *d_out, size_t out_stride);
 /* The IQ modes' payload (rx/rx_sound.cpp:1076-1096; MODE_IQ, and SAS / QAM / DRM monitor with their own sources): row i of d_cpx
  * (complex float: the AGC's output, d_agc of kg_post_process_dev) -> nsamps x {(s2_t) re, (s2_t) im}, 4 nsamps bytes at
  * d_out + i*out_stride, little-endian as they are or in network order.  chans: NULL (rows 0 .. nch-1), or the channel list
- * (a receiver bank's rows go by channel).  Enqueue only. */
+ * (a receiver bank's rows go by channel).  Enqueue only.  d_cpx: 8-byte aligned; d_out and out_stride (bytes): multiples of 2. */
 int kg_snd_iq_payload_dev(kg_ctx *ctx, const int32_t *chans, int nch, const void *d_cpx, size_t in_stride, int nsamps,
                           int little_endian, void *d_out, size_t out_stride);
 /* The 10 header bytes of snd_pkt_real_t (rx/rx_sound.h:42-48; rx/rx_sound.cpp:252,
@@ -756,7 +786,8 @@ typedef struct {
  * kg_wf_frames_dev leaves them): header + either the row or, compressed, the 10 pad bytes
  * (copies of the first pixel) and the row through encode_ima_adpcm_u8_e8 with a fresh state
  * (rx_waterfall.cpp:1622-1631).  Packet i starts at d_pkts + i*pkt_stride (>= KG_WF_PKT_MAX);
- * pkt_bytes[i] (host) = what goes on the wire: 16 + wf->out_bytes.  Enqueue only. */
+ * pkt_bytes[i] (host) = what goes on the wire: 16 + wf->out_bytes.  Enqueue only.  Any alignment (bytes).  Read: 1024 bytes of
+ * row i; written: exactly pkt_bytes[i] bytes of packet i -- the rest of a compressed packet's KG_WF_PKT_MAX is not touched. */
 int kg_wf_packets_dev(kg_ctx *ctx, const void *d_rows, size_t row_stride, int nrows,
                       const kg_wf_pkt_info *info, void *d_pkts, size_t pkt_stride, int32_t *pkt_bytes);
 
@@ -788,7 +819,8 @@ int kg_aper_create(kg_ctx *ctx, int nchan, kg_aper **out);
 void kg_aper_destroy(kg_aper *a);
 /* The averaging half of aperture_auto() (rx/rx_waterfall.cpp:1183-1222) for row i of d_rows
  * (1024 u8 pixels, row_stride apart) and channel chans[i]; pixels go through dB_wire_to_dBm()
- * with waterfall_cal (rx/rx_util.cpp:905-912).  Enqueue only. */
+ * with waterfall_cal (rx/rx_util.cpp:905-912).  Enqueue only.  Any alignment; 1024 bytes of row i are read, no caller memory is
+ * written. */
 int kg_aper_update_dev(kg_aper *a, const int32_t *chans, int nrows, const void *d_rows, size_t row_stride,
                        const kg_aper_cfg *cfg, int waterfall_cal);
 /* The reporting half (:1233-1272): signal = highest 5 dB band present (at least -80), noise =
@@ -806,7 +838,8 @@ int kg_aper_get(kg_aper *a, int chan, float *avg_pwr);            /* 1024 floats
  * edits the buffer (the `buf_modified` path, :286-290) is not supported on this path.  The
  * other taps of c2s_sound() are plain buffers of this API: receive_iq_pre_fir = the unpack
  * output, receive_iq_pre_agc = the FIR output (an iq_buf_t ring when d_out walks
- * [N_DPBUF][512]), receive_iq_post_agc / receive_real / receive_S_meter = kg_post outputs. */
+ * [N_DPBUF][512]), receive_iq_post_agc / receive_real / receive_S_meter = kg_post outputs.
+ * Written: 8 * 1024 * (nout[i] / 512) bytes of row i of each tap given (8-byte aligned, tap_stride in complex samples). */
 int kg_fir_process_taps_dev(kg_fir *fir, const int32_t *chans, int nch, const void *d_in, size_t in_stride, int n,
                             void *d_out, size_t out_stride, int32_t *nout, void *d_pre, void *d_post,
                             size_t tap_stride);
@@ -817,7 +850,8 @@ int kg_fir_process_taps_dev(kg_fir *fir, const int32_t *chans, int nch, const vo
  * filters a modified buffer -- m_pFilterCoef (the coefficients WITHOUT the CIC compensation) times the
  * edited block, backward transform, samples 512..1023 -- into d_out + i*out_stride + 512 b, replacing
  * what kg_fir_process_taps_dev wrote there.  The un-compensated coefficients are those kg_fir_setup
- * designed, or what kg_fir_set_coef_plain handed over.  Enqueue only. */
+ * designed, or what kg_fir_set_coef_plain handed over.  Enqueue only.  d_pre and d_out: 8-byte aligned; 1024 * nblk[i] samples of
+ * row i read, 512 * nblk[i] written. */
 int kg_fir_refilter_dev(kg_fir *fir, const int32_t *chans, int nch, const int32_t *nblk, const void *d_pre,
                         size_t tap_stride, void *d_out, size_t out_stride);
 /* m_pFilterCoef[1024] (complex float) for kg_fir_refilter_dev when kg_fir_set_coef supplied
@@ -835,7 +869,8 @@ int kg_fir_set_coef_plain(kg_fir *fir, int ch, const float *coef_fft);
 enum { KG_SPEC_PASSBAND = 0, KG_SPEC_CHAN_NULL = 1 };      /* SND_INSTANCE_FFT_PASSBAND, SND_INSTANCE_FFT_CHAN_NULL, rx/rx_sound.h:34-35 */
 #define KG_SPEC_ROW 1024                                   /* FFT_WIDTH, rx_sound.cpp:180 */
 /* Row r from the 1024 complex floats at d_spec + r*spec_stride (complex samples; what kg_fir_process_taps_dev wrote to d_post)
- * with the scale of inst[r] (KG_SPEC_*), to d_rows + r*row_stride (bytes; d_rows and row_stride multiples of 4).  Enqueue only. */
+ * with the scale of inst[r] (KG_SPEC_*), to d_rows + r*row_stride (bytes; d_rows and row_stride multiples of 4; d_spec 8-byte
+ * aligned).  1024 bytes of every row are written.  Enqueue only. */
 int kg_snd_spec_rows_dev(kg_ctx *ctx, const void *d_spec, size_t spec_stride, int nrows, const int32_t *inst, void *d_rows,
                          size_t row_stride);
 /* "limit update rate" (rx_sound.cpp:186-195), host only, the clock is the caller's: returns 1 when a row handed over at now_ms is to
@@ -848,7 +883,8 @@ int kg_snd_spec_due(uint32_t *last_ms, uint32_t now_ms);
  * NULL / 0): the same values the bytes were formed from.  d_out may be NULL -- the OutBuf == NULL call of fastfir.cpp:306, the
  * channel-null filter's (rx_sound.cpp:804): no backward transform, history and FirPos() advance as with an output buffer, and
  * nout[i] / 512 still says how many blocks (rows) entry i completed.  No spectrum goes to memory unless d_post is given.
- * d_rows and row_stride: multiples of 4 bytes.  Enqueue only. */
+ * d_rows and row_stride: multiples of 4 bytes; the complex-float buffers as in kg_fir_process_dev.  Written: 1024 * (nout[i] / 512)
+ * bytes of row i of d_rows, 8 * nout[i] of d_out, 8 * 1024 * (nout[i] / 512) of d_post.  Enqueue only. */
 int kg_fir_process_spec_dev(kg_fir *fir, const int32_t *chans, int nch, const void *d_in, size_t in_stride,
                             const int32_t *n_each, void *d_out, size_t out_stride, int32_t *nout, void *d_rows,
                             size_t row_stride, const int32_t *inst, void *d_post, size_t tap_stride);
@@ -1022,7 +1058,11 @@ int kg_rxbank_sync(kg_rxbank *bank);
 /* Frame f of the last step belongs to receiver rx_of_frame[f], was read at wf_iq + frame_off[f] pairs, and its packet has
  * pkt_bytes[f] bytes on the wire (arrays of nrx entries, any may be NULL).  Returns nframes. */
 int kg_rxbank_frame_map(kg_rxbank *bank, int32_t *rx_of_frame, uint64_t *frame_off, int32_t *pkt_bytes);
-/* The bank's device buffers (valid until kg_rxbank_destroy; read them after kg_rxbank_sync or behind the bank's streams). */
+/* The bank's device buffers (valid until kg_rxbank_destroy; read them after kg_rxbank_sync or behind the bank's streams).  A step
+ * writes, of receiver rx's rows, rx_raw / rx_in up to its nrec records, fir_out up to its nfir samples, then s16 and adpcm (the real
+ * modes) or iq_pay (the stereo modes) and agc (every mode but SSB) up to nfir; of frame f < nframes its 1024-byte row and pkt_bytes[f]
+ * bytes of its packet.  Nothing beyond those counts, no row of a receiver that left, no slot beyond nframes, and a step reads none of
+ * these buffers' earlier contents (wf_iq excepted: the samplers' rings). */
 typedef struct {
     void *wf_iq;   size_t wf_iq_stride;   /* [nrx][wf_iq_stride] iq_t: the samplers' rows (one-shot: pairs 0..8191) */
     void *wf_rows;                        /* [frame][1024] u8 */
