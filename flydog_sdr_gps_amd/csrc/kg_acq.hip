@@ -24,7 +24,12 @@
 //      y[n] = sum_{k2=0..3} W_N^{n*k2} * IFFT_4096( X[4*k1 + k2] )[n],  n < 4096
 // i.e. four 4096-point transforms (one 256-thread workgroup, 32 KiB of LDS)
 // whose results are accumulated in registers; the 16384-point product array
-// the reference materialises (rev_buf, :58) never exists.  The Doppler shift
+// the reference materialises (rev_buf, :58) never exists.  The sum is a Horner
+// chain over k2 = 3..0: for the outputs n = t + 256 (c + 4 d) of thread t,
+// W_N^{n*k2} = V[d]^k2 * W_64^{c*k2} with V[d] = W_N^{t + 1024 d} (four per-lane
+// constants); the wave-uniform W_64^{c*k2} is folded into the internal twiddles
+// of the last pass (row c of its second radix-4 stage), so an item adds two
+// fused multiply-adds per point: acc = acc * V[d] + Z'_k2 (acq_correlate_kernel).  The Doppler shift
 // code[(k - dop) mod N] (:471) is, in this layout, a contiguous rotated read
 // of plane (k2 - dop) & 3.  E1B (16368 outputs) keeps four accumulators per
 // point, one per output quarter, in a 512-thread kernel at 8 points per thread
@@ -37,6 +42,7 @@
 // SV's window is longer than 4096 lags).
 #include "kg_common.h"
 #include "kg_fft.h"
+#include "kg_acq_tables.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -271,18 +277,21 @@ struct acq_walk {
 // Work item = (cell, k2): one 4096-point sub-transform.  The operands of the
 // NEXT item are loaded while the current one is transformed.
 //
-// Wave-uniform constants of the combine twiddle W_N^{n*k2}, n = t + 256 m:
-// W_N^{256 m k2} = W_R^{m k2} with R = N / 256 and, with m = 4a + b,
-// = W_R^{4a k2} * W_R^{b k2}.  comb[k2] = { W_R^{k2}, W_R^{2 k2}, W_R^{3 k2},
-// W_R^{4 k2}, W_R^{8 k2}, W_R^{12 k2}, -, - } (host-built, fp32 roundings of double
-// values); quart[k2][q] = W_P^{q k2}: the factor of output quarter q (acq_correlate8_kernel).
+// The combine twiddle W_N^{n*k2}, n = t + 256 m, m = c + 4 d (c: the row of the last pass's second radix-4 stage, d: the
+// output within the row), with R = N / 256:
+//     W_N^{n k2} = ( W_N^t W_{R/4}^d )^{k2} * W_R^{c k2} = V[d]^{k2} * W_R^{c k2}
+// The row part W_R^{c k2} is wave-uniform and rides on the internal twiddles of pass 2 (kg_radix16_stage2f_k):
+// comb[k2][4 (c - 1) + d] = W16^{c d} W_R^{c k2} (kg_acq_row_consts: host-built, each one root of unity rounded from double).
+// The rest is a power of ONE per-lane value per d, so the sum over k2 is a Horner chain walked from k2 = P - 1 down:
+//     y = Z'_0 + V (Z'_1 + V (Z'_2 + ...)),   Z'_k2 = W_R^{c k2} IFFT_4096(X[P k1 + k2])  as pass 2 delivers it
+// -- four per-lane constants V[d] = tabN[t + 1024 d] for the life of the kernel and two fused multiply-adds per point and
+// item; no factor is rebuilt per item.
 template <int P, bool STAMPS = false>
 __global__ __launch_bounds__(256, 2) void acq_correlate_kernel(
     const float2 *__restrict__ data,  // [nblocks][P][4096]
     const float2 *__restrict__ code,  // [max_sats][P][8 rows][2 (256 + 2 H)]
     const float2 *__restrict__ tab4096, const float2 *__restrict__ tabN,
-    const float2 *__restrict__ comb,           // [P][8]
-    const float2 *__restrict__ quart,          // [P][4]; unused here (acq_correlate8_kernel reads the same table)
+    const float2 *__restrict__ comb,           // [P][KG_ACQ_ROWK] row constants of pass 2
     const acq_pair_desc *__restrict__ pairs,   // pair p belongs to XCD group p & 7
     int *__restrict__ claim,                   // [8][ACQ_CLAIM_STRIDE] per-group cell counters, zero at launch
     acq_walk walk,
@@ -310,14 +319,12 @@ __global__ __launch_bounds__(256, 2) void acq_correlate_kernel(
 
     kg_tw4096 tw;
     kg_tw4096_load(tw, tab4096, t);
-    // W_N^{t*k2}, the lane half of the combine twiddle, from registers: W_N^{t*b} (b = 1..3) and,
-    // for P = 16, W_N^{4*t*a} (a = 1..3); no per-item vector load, whose s_waitcnt would also drain
-    // the operand prefetch of the next item
-    cf wb[3], wa[3];
+    // V[d] = W_N^{t + 1024 d} = W_N^t W_{R/4}^d, the Horner factor of outputs m = c + 4 d (both P: N / (R/4) = 1024), from
+    // registers for the life of the kernel: no per-item vector load, whose s_waitcnt would also drain the operand
+    // prefetch of the next item
+    cf V[4];
 #pragma unroll
-    for (int i = 1; i < 4; i++) { wb[i - 1] = kg_ld(&tabN[t * i]); wa[i - 1] = kg_ld(&tabN[(4 * t * i) & (P * SUB - 1)]); }
-    (void) wa;
-    auto sel3 = [](const cf (&w)[3], int i) { return i == 1 ? w[0] : (i == 2 ? w[1] : w[2]); };
+    for (int dd = 0; dd < 4; dd++) V[dd] = kg_ld(&tabN[t + 1024 * dd]);
 
     // XCD-aware: workgroups b and b+8 share an XCD (round-robin dispatch), so the
     // cells of one (block, SV) pair -- one code spectrum -- all belong to one
@@ -359,8 +366,13 @@ __global__ __launch_bounds__(256, 2) void acq_correlate_kernel(
         c[2 * i] = cf{__uint_as_float(cv[0]), __uint_as_float(cv[1])};
         c[2 * i + 1] = cf{__uint_as_float(cv[2]), __uint_as_float(cv[3])};
     };
+    // (the item loop's form: the row offset i * 4096 -- no immediate reaches it -- is set by an s_mov of its own right at the
+    // load; left to the compiler, the seven offsets are loop invariants that occupy seven SGPRs for the life of the kernel,
+    // and the twelve row constants of pass 2 need that room)
     auto fetch_drow = [&](const acq_rsrc &r, int i) {
-        const u4 dv = __builtin_amdgcn_raw_buffer_load_b128(r.drs, r.dvo, i * 4096, 0);
+        int so;
+        asm volatile("s_mov_b32 %0, %1" : "=s"(so) : "i"(i * 4096));
+        const u4 dv = __builtin_amdgcn_raw_buffer_load_b128(r.drs, r.dvo, so, 0);
         d[2 * i] = cf{__uint_as_float(dv[0]), __uint_as_float(dv[1])};
         d[2 * i + 1] = cf{__uint_as_float(dv[2]), __uint_as_float(dv[3])};
     };
@@ -385,7 +397,7 @@ __global__ __launch_bounds__(256, 2) void acq_correlate_kernel(
     int cur_idx = slot, nxt_idx = slot + nslots;
     if (cur_idx >= ncell) return;
     acq_cell_desc cur = describe(cur_idx);
-    fetch(cur.data_off, cur.code_off, cur.dop, 0);
+    fetch(cur.data_off, cur.code_off, cur.dop, P - 1);
 
     int st_item = 0;
     for (;;) {
@@ -397,59 +409,43 @@ __global__ __launch_bounds__(256, 2) void acq_correlate_kernel(
         // (the counter's value only, and the atomic optimizer off: see wf_frame_kernel -- otherwise wave 0 waits for it here)
         if (t == 0) claimed = __hip_atomic_fetch_add(&claim[xcd * ACQ_CLAIM_STRIDE], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         cf acc[16];
-        // The twiddle-accumulate of item k2 is DEFERRED into item k2+1's exchanges, where a wave otherwise
+        // The Horner step of item k2 is DEFERRED into item k2-1's exchanges, where a wave otherwise
         // only waits.  yprev holds the deferred item's transform; with 256 registers (two workgroups per CU)
         // the code rows of the next item are fetched during pass 2 to make room, the data rows keep their
         // place in the conjugate product and pass 0.
-        cf yprev[16], pbase = cf{0.f, 0.f}, pg[3], pG[3];
-        // acc[4a + b] (+)= yv[4a + b] * (bs * W_R^{4a kp}) * W_R^{b kp}: C[4a + b] = B[a] * g[b] is formed
-        // first (wave-uniform factors), the products accumulate through fused multiply-adds
-        auto accumulate = [&](const cf (&yv)[16], int kp, cf bs, const cf (&g)[3], const cf (&G)[3]) {
-            if (kp == 0) {
+        cf yprev[16];
+        // acc[c + 4d] = acc[c + 4d] * V[d] + yv[c + 4d] (yv is scratch afterwards); the cell's first item (k2 = P - 1) is the copy
+        auto accumulate = [&](cf (&yv)[16], bool first) {
+            if (first) {
 #pragma unroll
                 for (int m = 0; m < 16; m++) acc[m] = yv[m];
                 return;
             }
-            // B[a] = bs * W_R^{4a kp}: the three products in one block (kg_fft.h, batched products)
-            cf B1, B2, B3;
-            kg_cmul1x3s(B1, B2, B3, bs, G[0], G[1], G[2]);
 #pragma unroll
-            for (int a = 0; a < 4; a++) {
-                const cf Ba = a == 0 ? bs : (a == 1 ? B1 : (a == 2 ? B2 : B3));
-                const cf C0 = Ba;
-                cf C1, C2, C3;
-                kg_cmul1x3s(C1, C2, C3, Ba, g[0], g[1], g[2]);
-                kg_cmac4v(acc[4 * a], acc[4 * a + 1], acc[4 * a + 2], acc[4 * a + 3],
-                          yv[4 * a], yv[4 * a + 1], yv[4 * a + 2], yv[4 * a + 3], C0, C1, C2, C3);
-            }
+            for (int dd = 0; dd < 4; dd++)
+                kg_horner4v(acc[4 * dd], acc[4 * dd + 1], acc[4 * dd + 2], acc[4 * dd + 3],
+                            yv[4 * dd], yv[4 * dd + 1], yv[4 * dd + 2], yv[4 * dd + 3], V[dd]);
         };
         // (a lambda of its own, not the three statements at the call: the inlining order decides the register allocation of
-        // the item loop, and this is the order the measured kernel was built with)
-        auto accumulate_fenced = [&](int kp) { kg_pin(); accumulate(yprev, kp, pbase, pg, pG); kg_pin(); };
+        // the item loop)
+        auto accumulate_fenced = [&](bool first) { kg_pin(); accumulate(yprev, first); kg_pin(); };
         const int tl = t & 15, th = t >> 4;
         const int rd = t ^ (th & 15);              // P(t + 256 j) = 256 j + (t ^ ((t >> 4) & 15)), kg_fft.h
         // rolled on purpose: unrolled (or with k2 a template constant) the
         // register allocator spills 80+ VGPRs
 #pragma unroll 1
-        for (int k2 = 0; k2 < P; k2++) {
+        for (int k2 = P - 1; k2 >= 0; k2--) {
             unsigned long long *sti = (STAMPS && st && st_item < 24) ? st + 16 + 16 * st_item : nullptr;
             KG_STAMP(STAMPS, sti, 8);
-            cf base;                                           // W_N^{t*k2}, used after the transform
-            if constexpr (P == 4) base = sel3(wb, k2);
-            else {
-                const int ka = k2 >> 2, kb = k2 & 3;
-                const cf A = sel3(wa, ka), Bv = sel3(wb, kb);
-                base = ka == 0 ? Bv : (kb == 0 ? A : kg_cmul(A, Bv));
-            }
             cf x[16], y[16];
-            // The operands of the next item -- (cur, k2+1) or (nxt, 0); the very last item re-reads its own
+            // The operands of the next item -- (cur, k2-1) or (nxt, P-1); the very last item re-reads its own
             // cell, harmless, so that there is ONE load site that is never skipped -- are fetched row by
             // row between the arithmetic groups of this item: a row's registers are free as soon as its
             // products are formed, and sixteen 1 KiB loads issued back to back queue behind each other in
             // the texture addresser for several hundred cycles.
-            const bool same = k2 < P - 1;
+            const bool same = k2 > 0;
             const acq_rsrc nr = fetch_prepare(same ? cur.data_off : nxt.data_off, same ? cur.code_off : nxt.code_off,
-                                              same ? cur.dop : nxt.dop, (k2 + 1) & (P - 1));
+                                              same ? cur.dop : nxt.dop, (k2 - 1) & (P - 1));
             // Round 4: conj(data) * code (simd_multiply_conjugate_ccc, support/simd.cpp:39-67) FUSED into the first stage of
             // pass 0 (kg_cc_radix16_h, kg_fft.h): 99 packed instructions where products + butterfly took 112, and no copies
             // of the code operands (the in-place products needed sixteen).  The next item's data rows are requested two at
@@ -472,10 +468,10 @@ __global__ __launch_bounds__(256, 2) void acq_correlate_kernel(
             KG_STAMP(STAMPS, sti, 2);
 #pragma unroll
             for (int j = 0; j < 16; j++) x[j] = kg_ld_tile(&tileA[rd + 256 * j]);
-            // the deferred accumulate of item k2 - 1: after barrier 1, while the pass-1 tile reads are in flight
+            // the deferred Horner step of item k2 + 1: after barrier 1, while the pass-1 tile reads are in flight
             // (one of an item's four waits -- behind the stores before either barrier, or after it with the tile reads
             // in flight; moving it between them changed nothing, DESIGN_HISTORY)
-            if (k2 > 0) accumulate_fenced(k2 - 1);
+            if (k2 < P - 1) accumulate_fenced(k2 == P - 2);
             if (STAMPS) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             KG_STAMP(STAMPS, sti, 3);
             // pass 1: twiddle W256^(j*(t&15)), out index (t>>4)*256 + (t&15) + 16 m = t + 16 (15 th + m).  Round 4: this second
@@ -492,27 +488,25 @@ __global__ __launch_bounds__(256, 2) void acq_correlate_kernel(
             KG_STAMP(STAMPS, sti, 4);
             __syncthreads();
             KG_STAMP(STAMPS, sti, 5);
-            // wave-uniform constants (s_load), hidden behind pass 2
-            cf g[3], G[3];
+            // the row constants of pass 2: wave-uniform (s_load), there by the time its first stage is through
+            cf rk[KG_ACQ_ROWK];
 #pragma unroll
-            for (int i = 0; i < 3; i++) { g[i] = kg_ld(&comb[8 * k2 + i]); G[i] = kg_ld(&comb[8 * k2 + 3 + i]); }
+            for (int i = 0; i < KG_ACQ_ROWK; i++) rk[i] = kg_ld(&comb[KG_ACQ_ROWK * k2 + i]);
 #pragma unroll
             for (int j = 0; j < 16; j++) x[j] = kg_ld_tile(&tileB[t + 256 * j]);
             if (STAMPS) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             KG_STAMP(STAMPS, sti, 6);
-            // pass 2: twiddle W4096^(j*t), out index t + 256 m (kept in registers)
+            // pass 2: twiddle W4096^(j*t), the row part W_R^{c k2} of the combine twiddle folded into its second stage;
+            // out index t + 256 m (kept in registers)
             // (the next item's code rows, two per first-stage group)
-            kg_tw_radix16_h<+1>(x, yprev, tw.p2, [&](int s) {
+            kg_tw_radix16_hk<+1>(x, yprev, tw.p2, rk, [&](int s) {
                 if (s < 4) { kg_pin(); fetch_crow(nr, 2 * s); fetch_crow(nr, 2 * s + 1); kg_pin(); }
             });
-            pbase = base;
-#pragma unroll
-            for (int i = 0; i < 3; i++) { pg[i] = g[i]; pG[i] = G[i]; }
             KG_STAMP(STAMPS, sti, 7);
             KG_STAMP(STAMPS, sti, 11);
             if (STAMPS) st_item++;
         }
-        accumulate(yprev, P - 1, pbase, pg, pG);               // the cell's last item
+        accumulate(yprev, false);                              // the cell's last item (k2 = 0)
 
         // search.cpp:486-490: power, first maximum (strict >), running total
         // Row r = m + 16 q holds n = t + 256 r.  `limit` is wave-uniform, so a row lies wholly inside the
@@ -1054,8 +1048,8 @@ struct kg_acq {
     size_t code_len;   // float2 per code spectrum (P planes with halo)
     float2 *d_tabN;        // exp(+2 pi i k / N); the context's table for N = 16384
     bool own_tabN;
-    float2 *d_comb;        // [P][8]  combine constants (acq_correlate_kernel)
-    float2 *d_quart;       // [P][4]
+    float2 *d_comb;        // [P][KG_ACQ_ROWK]  row constants of pass 2 (acq_correlate_kernel)
+    float2 *d_quart;       // [P][4]  W_P^{q k2}: the factor of output quarter q (acq_correlate8_kernel)
     float2 *d_comb8;       // [P][4]  combine constants of the 512-thread four-quarter kernel
     int grid8;             // its persistent grid (>= 8)
     float2 *d_code;        // [max_sats][P planes with halo]
@@ -1159,14 +1153,9 @@ static void from_planes(const std::vector<float2> &pl, float *nat, int P, int H,
 // exp(+2 pi i k / n) in double, rounded to fp32, exact on the axes (as kg_ctx's tables).
 static float2 unit_root(long k, long n)
 {
-    k %= n;
-    if (k < 0) k += n;
-    if (k == 0) return make_float2(1.f, 0.f);
-    if (4 * k == n) return make_float2(0.f, 1.f);
-    if (2 * k == n) return make_float2(-1.f, 0.f);
-    if (4 * k == 3 * n) return make_float2(0.f, -1.f);
-    const double a = 2.0 * M_PI * (double) k / (double) n;
-    return make_float2((float) cos(a), (float) sin(a));
+    float2 r;
+    kg_unit_root_f(k, n, &r.x, &r.y);
+    return r;
 }
 
 template <int SRC>
@@ -1217,13 +1206,11 @@ static int acq_init(kg_acq *a)
         KG_HIP(hipMemcpy(a->d_tabN, h.data(), spec, hipMemcpyHostToDevice));
     }
     {
-        const long R = N / 256;
-        std::vector<float2> comb(P * 8, make_float2(1.f, 0.f)), quart(P * 4);
-        static const int mult[6] = {1, 2, 3, 4, 8, 12};
-        for (int k2 = 0; k2 < P; k2++) {
-            for (int i = 0; i < 6; i++) comb[8 * k2 + i] = unit_root((long) mult[i] * k2, R);
+        std::vector<float2> comb(P * KG_ACQ_ROWK), quart(P * 4);
+        static_assert(sizeof(float2) == 2 * sizeof(float), "float2 = (re, im)");
+        kg_acq_row_consts(P, &comb[0].x);
+        for (int k2 = 0; k2 < P; k2++)
             for (int q = 0; q < 4; q++) quart[4 * k2 + q] = unit_root((long) q * k2, P);
-        }
         KG_HIP(hipMalloc((void **) &a->d_comb, sizeof(float2) * comb.size()));
         KG_HIP(hipMalloc((void **) &a->d_quart, sizeof(float2) * quart.size()));
         KG_HIP(hipMemcpy(a->d_comb, comb.data(), sizeof(float2) * comb.size(), hipMemcpyHostToDevice));
@@ -1711,7 +1698,7 @@ static void launch_correlate(kg_acq *a, hipStream_t st, int first, const acq_pai
     hipLaunchKernelGGL((acq_correlate_kernel<P, STAMPS>), dim3(grid), dim3(256), ACQ_LDS_BYTES, st,
                        (const float2 *) (a->d_data + (size_t) first * a->fft_len), (const float2 *) a->d_code,
                        (const float2 *) a->ctx->d_tab4096, (const float2 *) a->d_tabN,
-                       (const float2 *) a->d_comb, (const float2 *) a->d_quart, d_pairs,
+                       (const float2 *) a->d_comb, d_pairs,
                        a->d_claim, w, a->halo, a->d_cells, d_stamps);
 }
 

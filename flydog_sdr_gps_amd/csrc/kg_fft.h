@@ -95,18 +95,9 @@ template <int SIGN> KG_DEV cf kg_sub_sj(cf a, cf b) { return SIGN > 0 ? kg_subj(
 #define KG_MUL_(r, a, w) "v_pk_mul_f32 " r ", " a ", " w " op_sel_hi:[1,0]\n\t"
 #define KG_FMA_(a, w, r, neg) "v_pk_fma_f32 " a ", " a ", " w ", " r " op_sel:[1,1,0] op_sel_hi:[0,1,1] " neg "\n\t"
 
-// o_i = a * w_i for one a and three wave-uniform w_i, NOT in place (the in-place blocks need a copy of a
-// per product when a is used again: 15 v_mov_b64 per correlator item went on that)
+// o_i = a * w_i for one a and three w_i (vector registers), NOT in place (the in-place blocks need a copy of a
+// per product when a is used again)
 #define KG_FMA3_(o, a, w, neg) "v_pk_fma_f32 " o ", " a ", " w ", " o " op_sel:[1,1,0] op_sel_hi:[0,1,1] " neg "\n\t"
-KG_DEV void kg_cmul1x3s(cf &o0, cf &o1, cf &o2, cf a, cf w0, cf w1, cf w2)
-{
-    asm(KG_MUL_("%0", "%3", "%4") KG_MUL_("%1", "%3", "%5") KG_MUL_("%2", "%3", "%6")
-        KG_FMA3_("%0", "%3", "%4", "neg_lo:[0,1,0]") KG_FMA3_("%1", "%3", "%5", "neg_lo:[0,1,0]")
-        KG_FMA3_("%2", "%3", "%6", "neg_lo:[0,1,0]")
-        : "=&v"(o0), "=&v"(o1), "=&v"(o2) : "v"(a), "s"(w0), "s"(w1), "s"(w2));
-}
-
-// the same with the w_i in vector registers
 KG_DEV void kg_cmul1x3v(cf &o0, cf &o1, cf &o2, cf a, cf w0, cf w1, cf w2)
 {
     asm(KG_MUL_("%0", "%3", "%4") KG_MUL_("%1", "%3", "%5") KG_MUL_("%2", "%3", "%6")
@@ -181,6 +172,18 @@ KG_DEV void kg_cmac4v1(cf &c0, cf &c1, cf &c2, cf &c3, cf y0, cf y1, cf y2, cf y
         KG_MAC2_("%0", "%4", "%8") KG_MAC2_("%1", "%5", "%8") KG_MAC2_("%2", "%6", "%8") KG_MAC2_("%3", "%7", "%8")
         : "+v"(c0), "+v"(c1), "+v"(c2), "+v"(c3)
         : "v"(y0), "v"(y1), "v"(y2), "v"(y3), "v"(w));
+}
+// A Horner step on four points with one factor v (a VGPR pair): c_i <- c_i * v + z_i.  The multiplicand is the destination:
+// the first fused multiply-add (x halves) lands in z_i, the second (y halves) reads it as its addend and writes c_i.
+// z_i is scratch afterwards.  Two packed instructions per point.
+KG_DEV void kg_horner4v(cf &c0, cf &c1, cf &c2, cf &c3, cf &z0, cf &z1, cf &z2, cf &z3, cf v)
+{
+#define KG_HOR2_(c, v, z) "v_pk_fma_f32 " c ", " c ", " v ", " z " op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[0,1,0]\n\t"
+    asm(KG_MAC1_("%4", "%0", "%8") KG_MAC1_("%5", "%1", "%8") KG_MAC1_("%6", "%2", "%8") KG_MAC1_("%7", "%3", "%8")
+        KG_HOR2_("%0", "%8", "%4") KG_HOR2_("%1", "%8", "%5") KG_HOR2_("%2", "%8", "%6") KG_HOR2_("%3", "%8", "%7")
+        : "+v"(c0), "+v"(c1), "+v"(c2), "+v"(c3), "+v"(z0), "+v"(z1), "+v"(z2), "+v"(z3)
+        : "v"(v));
+#undef KG_HOR2_
 }
 #undef KG_MAC1_
 #undef KG_MAC2_
@@ -346,6 +349,53 @@ template <int SIGN, class H> KG_DEV void kg_radix16_stage2f(cf (&x)[16], cf (&y)
 #undef KG_W16C
 }
 
+// kg_radix16_stage2f with a wave-uniform factor r_c per ROW folded into the internal twiddles (the C/A correlator's last pass:
+// r_c = W_R^{c k2}, the row part of its combine twiddle, kg_acq.hip):  out y[c + 4 d] = r_c * (what kg_radix16_stage2f gives).
+// k[4 (c - 1) + d] = W16^(c d) r_c for rows c = 1..3 (SGPR pairs; kg_acq_row_consts builds them); row 0 is unchanged.  With
+// z_d = x[4c + d]:   u0 = k_0 z0,  s02 = u0 + k_2 z2,  d02 = 2 u0 - s02,   u1 = k_1 z1,  s13 = u1 + k_3 z3,  d13 = 2 u1 - s13
+// -- every row has a general factor on z0, and row 2 no longer an add and a subtract for its W^4 = SIGN j.
+// 50 packed instructions (8 + 3 * 14) against 43.
+template <int SIGN, class H> KG_DEV void kg_radix16_stage2f_k(cf (&x)[16], cf (&y)[16], const cf (&k)[12], H hook)
+{
+    const cf two = cf{2.0f, 2.0f};
+    kg_radix4<SIGN>(x[0], x[1], x[2], x[3]);                        // row 0: no twiddles
+    y[0] = x[0]; y[4] = x[1]; y[8] = x[2]; y[12] = x[3];
+    hook(4);
+    cf u0[3], u1[3], s02[3], s13[3], d02[3], d13[3];
+    // the six products u0_c, u1_c, then the six sums s02_c, s13_c
+#define KG_S2K_PRODUCTS_(F2)                                                                                                     \
+    asm(KG_MUL_("%0", "%6", "%12") KG_MUL_("%1", "%7", "%13") KG_MUL_("%2", "%8", "%14")                                           \
+        KG_MUL_("%3", "%9", "%15") KG_MUL_("%4", "%10", "%16") KG_MUL_("%5", "%11", "%17")                                         \
+        F2("%0", "%6", "%12") F2("%1", "%7", "%13") F2("%2", "%8", "%14") F2("%3", "%9", "%15") F2("%4", "%10", "%16") F2("%5", "%11", "%17") \
+        : "=&v"(u0[0]), "=&v"(u0[1]), "=&v"(u0[2]), "=&v"(u1[0]), "=&v"(u1[1]), "=&v"(u1[2])                                     \
+        : "v"(x[4]), "v"(x[8]), "v"(x[12]), "v"(x[5]), "v"(x[9]), "v"(x[13]),                                                   \
+          "s"(k[0]), "s"(k[4]), "s"(k[8]), "s"(k[1]), "s"(k[5]), "s"(k[9]))
+#define KG_S2K_SUMS_(F2)                                                                                                         \
+    asm(KG_CFMA1_("%0", "%12", "%18", "%6") KG_CFMA1_("%1", "%13", "%19", "%7") KG_CFMA1_("%2", "%14", "%20", "%8")              \
+        KG_CFMA1_("%3", "%15", "%21", "%9") KG_CFMA1_("%4", "%16", "%22", "%10") KG_CFMA1_("%5", "%17", "%23", "%11")            \
+        F2("%0", "%12", "%18") F2("%1", "%13", "%19") F2("%2", "%14", "%20") F2("%3", "%15", "%21") F2("%4", "%16", "%22") F2("%5", "%17", "%23") \
+        : "=&v"(s02[0]), "=&v"(s02[1]), "=&v"(s02[2]), "=&v"(s13[0]), "=&v"(s13[1]), "=&v"(s13[2])                               \
+        : "v"(u0[0]), "v"(u0[1]), "v"(u0[2]), "v"(u1[0]), "v"(u1[1]), "v"(u1[2]),                                               \
+          "v"(x[6]), "v"(x[10]), "v"(x[14]), "v"(x[7]), "v"(x[11]), "v"(x[15]),                                                 \
+          "s"(k[2]), "s"(k[6]), "s"(k[10]), "s"(k[3]), "s"(k[7]), "s"(k[11]))
+    if constexpr (SIGN > 0) { KG_S2K_PRODUCTS_(KG_CFMA2P_); KG_S2K_SUMS_(KG_CFMA2P_); }
+    else { KG_S2K_PRODUCTS_(KG_CFMA2C_); KG_S2K_SUMS_(KG_CFMA2C_); }
+#undef KG_S2K_PRODUCTS_
+#undef KG_S2K_SUMS_
+    // the six differences d = 2 u - s
+    asm(KG_2CMT_("%0", "%6", "%18", "%12") KG_2CMT_("%1", "%7", "%18", "%13") KG_2CMT_("%2", "%8", "%18", "%14")
+        KG_2CMT_("%3", "%9", "%18", "%15") KG_2CMT_("%4", "%10", "%18", "%16") KG_2CMT_("%5", "%11", "%18", "%17")
+        : "=&v"(d02[0]), "=&v"(d02[1]), "=&v"(d02[2]), "=&v"(d13[0]), "=&v"(d13[1]), "=&v"(d13[2])
+        : "v"(u0[0]), "v"(u0[1]), "v"(u0[2]), "v"(u1[0]), "v"(u1[1]), "v"(u1[2]),
+          "v"(s02[0]), "v"(s02[1]), "v"(s02[2]), "v"(s13[0]), "v"(s13[1]), "v"(s13[2]), "s"(two));
+#pragma unroll
+    for (int c = 1; c < 4; c++) {
+        y[c] = s02[c - 1] + s13[c - 1]; y[c + 8] = s02[c - 1] - s13[c - 1];
+        kg_addsub_sj<SIGN>(y[c + 4], y[c + 12], d02[c - 1], d13[c - 1]);
+        hook(4 + c);
+    }
+}
+
 // First stage behind inter-pass twiddles, fused:  in X[j] (j = 4a + b) and the fifteen twiddles w (w.w[j - 1] for X[j]);
 // out x[4c + b] = u_b[c] = sum_a (w X)[4a + b] (SIGN j)^(a c), the input of kg_radix16_stage2f.  hook(0..3) between its blocks.
 // 54 packed instructions (30 + 32 as products + radix-4s).
@@ -410,6 +460,12 @@ template <int SIGN, class H> KG_DEV void kg_tw_radix16_h(cf (&x)[16], cf (&y)[16
 {
     kg_radix16_stage1_tw<SIGN>(x, w, hook);
     kg_radix16_stage2f<SIGN>(x, y, hook);
+}
+// the same with the row factors k folded into the second stage (kg_radix16_stage2f_k): 104 packed instructions
+template <int SIGN, class H> KG_DEV void kg_tw_radix16_hk(cf (&x)[16], cf (&y)[16], const kg_tw15 &w, const cf (&k)[12], H hook)
+{
+    kg_radix16_stage1_tw<SIGN>(x, w, hook);
+    kg_radix16_stage2f_k<SIGN>(x, y, k, hook);
 }
 // conj-products + radix16 fused (99 instead of 112; no copies of the operands)
 template <int SIGN, class H> KG_DEV void kg_cc_radix16_h(const cf (&c)[16], const cf (&d)[16], cf (&y)[16], H hook)
