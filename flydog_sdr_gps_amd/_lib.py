@@ -200,6 +200,23 @@ SYMBOLS = {
     "kg_snd_gps_begin": (None, [_vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]),
     "kg_snd_gps_stamp": (None, [_vp, _i, _i, _i, _i, _i, C.c_double, C.c_double, C.c_uint64, _vp]),
     "kg_acq_chan_start": (None, [_i, _i, _i, C.c_double, _vp]),
+    "kg_trk_create": (_i, [_vp, _i, _i, _i, C.POINTER(_vp)]),
+    "kg_trk_destroy": (None, [_vp]),
+    "kg_trk_set_sat": (_i, [_vp, _i, _i]),
+    "kg_trk_set_e1b_code": (_i, [_vp, _i, _vp, _i]),
+    "kg_trk_set_rate_lo": (_i, [_vp, _i, C.c_uint32]),
+    "kg_trk_set_rate_cg": (_i, [_vp, _i, C.c_uint32]),
+    "kg_trk_set_gain_lo": (_i, [_vp, _i, _i, _i]),
+    "kg_trk_set_gain_cg": (_i, [_vp, _i, _i, _i]),
+    "kg_trk_set_polarity": (_i, [_vp, _i, _i]),
+    "kg_trk_set_mask": (_i, [_vp, C.c_uint32]),
+    "kg_trk_sampler_reset": (_i, [_vp]),
+    "kg_trk_pause": (_i, [_vp, _i, _i]),
+    "kg_trk_set_loop": (_i, [_vp, _i, _i]),
+    "kg_trk_process_bits_dev": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _vp]),
+    "kg_trk_process_bits": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _vp]),
+    "kg_trk_get_chan": (_i, [_vp, _i, _vp]),
+    "kg_trk_get_clocks": (_i, [_vp, C.POINTER(C.c_uint64), _vp]),
     "kg_aper_create": (_i, [_vp, _i, C.POINTER(_vp)]),
     "kg_aper_destroy": (None, [_vp]),
     "kg_aper_update_dev": (_i, [_vp, _vp, _i, _vp, _sz, _vp, _i]),

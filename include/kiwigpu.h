@@ -830,6 +830,81 @@ int kg_aper_report(kg_aper *a, const int32_t *chans, int n, const int32_t *audio
                    int32_t *noise);
 int kg_aper_get(kg_aper *a, int chan, float *avg_pwr);            /* 1024 floats */
 
+/* ---------------------------------------------------------------------------
+ * GPS tracking channels: what receives the words of kg_acq_chan_start.  A bank of up to KG_TRK_MAX_CHANS channels, each the DEMOD
+ * of verilog/gps/demod.v (code NCO, C/A generator of cacode.v or the E1B code memory, E/P/L replicas, 1-bit mixers, six 20-bit
+ * integrators) plus the soft CPU's per-epoch service of e_cpu/kiwi.gps.asm (GPS_Method: CloseLoop on ip*qp and on pe-pl, the
+ * lock flag, the nav-bit machine), clock for clock, on the packed 1-bit stream kg_acq_sample_bits_dev takes (LSB first in bytes).
+ * Everything is integer; the library is held equal to a literal clock-by-clock model (tools/trk_model.cpp).
+ *
+ * What the reference leaves open and this API fixes:
+ *   - the service delay.  The firmware writes the new NCO words some clocks after ms0, how many depends on its polling and on the
+ *     other channels.  Here: lo_delay and cg_delay clocks after the clock edge that sets ms0 (2 <= lo_delay <= cg_delay <= 8183;
+ *     0 selects KG_TRK_LO_DELAY / KG_TRK_CG_DELAY, the count of the listing for a channel serviced alone).  A word written at edge
+ *     e acts from edge e + 1 on.  lo_delay > cg_delay is refused: GPS_Method is ONE instruction stream in which
+ *     wrReg SET_LO_NCO comes before the code loop's arithmetic starts, so the reference cannot write the code word first; and an
+ *     epoch's record, appended when its service completes (the code word's write), carries the LO word that service wrote.  An ms0 that arrives while a service is still due replaces it (one srq, one service).
+ *   - the E1B code memory's own pipeline: after every full_chip the latched code is the memory chip at the new nchip.
+ *   - registers without a reset value start at 0, cg_en at 1, gps.v's pause counter at 0.
+ * Host commands act between process calls.  A command or getter after a process call waits for the stream, and the first process
+ * call after a command waits for the upload of the channels' state; calls with no command between them only enqueue.
+ * ------------------------------------------------------------------------- */
+typedef struct kg_trk kg_trk;
+enum { KG_TRK_MAX_CHANS = 12,            /* GPS_MAX_CHANS */
+       KG_TRK_E1B_MODE = 0x800, KG_TRK_G2_INIT = 0x400,    /* the CmdSetSat word: E1B_MODE | g2_init | init[10:1] */
+       KG_TRK_E1B_CODELEN = 4092, KG_TRK_CHAN_BYTES = 78,  /* sizeof GPS_CHAN (kiwi.gps.asm:31-45) */
+       KG_TRK_LO_DELAY = 216, KG_TRK_CG_DELAY = 577,
+       KG_TRK_MIN_EPOCH = 8184,          /* clocks: 1023 chips at the largest accepted code rate */
+       KG_TRK_UNLOCKED = 1, KG_TRK_INAV = 2 };             /* kg_trk_epoch.flags */
+typedef struct {
+    uint64_t clock;                 /* the clock edge (0 = the first the bank consumed) that saw ms1: ser_iq latched, the filters restarted */
+    int32_t ip, qp, ie, qe, il, ql; /* the six 20-bit counts the firmware reads, sign-extended */
+    uint32_t lo_rate, cg_rate;      /* the NCO words after this epoch's service (with the loop off: as set) */
+    uint32_t flags;                 /* KG_TRK_UNLOCKED: ch_unlocked != 0; KG_TRK_INAV: ip[19] */
+    uint32_t reserved;              /* 0 */
+} kg_trk_epoch;
+int kg_trk_create(kg_ctx *ctx, int nchan, int lo_delay, int cg_delay, kg_trk **out);
+void kg_trk_destroy(kg_trk *trk);
+/* CmdSetSat.  C/A with taps needs both taps in 1..10 (cacode.v indexes g2[T]); afterwards the channel does not run before a
+ * kg_trk_sampler_reset reaches it (the generator is seeded by `rst` only). */
+int kg_trk_set_sat(kg_trk *trk, int ch, int codegen_init);
+int kg_trk_set_e1b_code(kg_trk *trk, int ch, const uint8_t *chips, int nchips);     /* nchips == 4092, chips 0 / 1 */
+/* SetRate: the integrator <- rate << 32, the NCO word <- rate.  cg: 2^27 <= rate < 2^29 (8 .. 32 clocks per chip; nominal 2^28),
+ * else KG_ERR_INVALID: the closed form relies on nested chip events at least two clocks apart. */
+int kg_trk_set_rate_lo(kg_trk *trk, int ch, uint32_t rate);
+int kg_trk_set_rate_cg(kg_trk *trk, int ch, uint32_t rate);
+int kg_trk_set_gain_lo(kg_trk *trk, int ch, int ki, int kp_minus_ki);               /* each 0..63 */
+int kg_trk_set_gain_cg(kg_trk *trk, int ch, int ki, int kp_minus_ki);
+int kg_trk_set_polarity(kg_trk *trk, int ch, int polarity);                         /* 0..2 */
+int kg_trk_set_mask(kg_trk *trk, uint32_t mask);                                    /* CmdSetMask: bit ch set = not reset */
+int kg_trk_sampler_reset(kg_trk *trk);                                              /* CmdSample's rst on the unmasked channels */
+/* SET_PAUSE: cg_en <- 0 on channel ch, the bank's ONE pause counter <- count (0..65535); the generator stands for count + 1
+ * clocks (a second pause moves the first one's end, gps.v:190-200).
+ * A paused channel's chip events are held.  Held with nchip 0 at a half chip they would hold ms0 set and restart the filters every
+ * clock; that state is not computed.  The command that would lead to it -- this one, kg_trk_set_rate_cg on a paused channel, or a
+ * kg_trk_sampler_reset that reaches a paused channel whose service is still due -- is refused with KG_ERR_STATE and changes
+ * NOTHING: the bank runs on.  For a pause that is about 9 clocks of a 16368-clock epoch (the 8 clocks after an ms0, while nchip is
+ * still 0 and the service is due, and the held half chip itself): process 16 clocks more and pause then, with the count reduced
+ * by those clocks. */
+int kg_trk_pause(kg_trk *trk, int ch, int count);
+int kg_trk_set_loop(kg_trk *trk, int ch, int on);       /* ours, not the reference's: off = the service leaves integrators and NCO words alone */
+/* nclocks >= 1 clocks of every channel.  d_bits: the byte holding the next bit; the bit offset inside it carries over from the
+ * previous call ((clocks consumed so far) % 8), so a stream may be cut anywhere.  Read: ceil((offset + nclocks) / 8) bytes.  One
+ * kg_trk_epoch per completed service is appended to row ch (d_epochs + ch * chan_stride, 8-byte aligned, chan_stride >= cap
+ * records); d_counts[ch] (device, int32) = how many: exactly that many records are written.  cap >= nclocks / 8184 + 2, else
+ * KG_ERR_INVALID.  Enqueue only (see above).  KG_ERR_INVALID, nothing done: a channel without kg_trk_set_sat, or not reset since, or in
+ * E1B mode without a code, or without a code rate.
+ * A channel whose own code loop writes a word outside [2^27, 2^29) STOPS at that clock (the closed form does not hold there): its
+ * count comes back as -1 - n (n records written before the stop), in this and in every later call, kg_trk_get_chan answers
+ * KG_ERR_STATE and, after any command, so does this call; kg_trk_set_rate_cg starts the channel again from where it stopped (the
+ * clocks in between are lost to it).  The other channels are not affected. */
+int kg_trk_process_bits_dev(kg_trk *trk, const uint8_t *d_bits, size_t nclocks, kg_trk_epoch *d_epochs, size_t chan_stride, int cap,
+                            int32_t *d_counts);
+int kg_trk_process_bits(kg_trk *trk, const uint8_t *bits, size_t nclocks, kg_trk_epoch *epochs, size_t chan_stride, int cap,
+                        int32_t *counts);               /* the same on host memory; synchronises */
+int kg_trk_get_chan(kg_trk *trk, int ch, uint8_t *out);                             /* KG_TRK_CHAN_BYTES bytes: GPS_CHAN as CmdGetChan uploads it */
+int kg_trk_get_clocks(kg_trk *trk, uint64_t *clock, uint32_t *replicas);            /* clocks consumed; the 18-bit replica word of each channel */
+
 /* kg_fir_process_dev plus the extension taps of ProcessData (SURVEY.md 8(f) rank 4;
  * rx/CuteSDR/fastfir.cpp:278-302): for block b of list entry i, 1024 complex floats at
  * d_pre / d_post + i*tap_stride + b*1024 (either may be NULL): pre = the forward spectrum
