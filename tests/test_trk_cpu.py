@@ -175,7 +175,7 @@ def test_lock_check_on_the_model(lock_run):
     # the carrier and code loops sit at the scene's Doppler
     lo_hz = r[-200:, 7].astype(float).mean() / 2.0 ** 32 * trk.FS - trk.FC
     cg_hz = r[-200:, 8].astype(float).mean() / 2.0 ** 32 * trk.FS - trk.CPS
-    assert abs(lo_hz - tc.LOCK_DOPPLER) < 20 and abs(cg_hz - tc.LOCK_DOPPLER * trk.CPS / 1575.42e6) < 2
+    assert abs(lo_hz - tc.LOCK_DOPPLER) < 5 and abs(cg_hz - tc.LOCK_DOPPLER * trk.CPS / 1575.42e6) < 2
     # the data bits: the last 12 saved ones are 12 consecutive sent bits, or their complement, ending at the scene's last bit
     ch = np.frombuffer(bytes.fromhex(w["dumps"][0][0][0]), trk.chan_dtype)[0]
     got = trk.nav_bits_of(ch, 12)

@@ -11,6 +11,10 @@ A scenario is a list of steps in the script format of tools/trk_model.cpp: ("S",
 ("L" / "G", ch, rate), ("l" / "g", ch, ki, kp - ki), ("P", ch, pol), ("M", mask), ("R",) sampler reset, ("U", ch, count) pause,
 ("O", ch, on) set_loop, ("X", nclocks), ("D",).  The literal model also restates, here in Python, the C/A generator of cacode.v
 (ca_chips_literal) for the comparison with prn.py.
+
+The signal tests (tests/test_trk_signal_cpu.py, tests/test_trk_signal_gpu.py) take from the end of this file scene() (several satellites
+and gaps in one stream), start_at_bin() / start_acquired() (how a channel is started), signal_report() (what a run says about the
+signal it was given) and signal_cases() (the table of cases).
 """
 import os
 import shutil
@@ -314,11 +318,7 @@ def lock_bits():
 def lock_scenario(bits, start):
     """start: a handoff.ChanStart (or anything with lo_rate, ca_rate, ca_pause)"""
     from flydog_sdr_gps_amd import trk
-    lo, cg = trk.gains(False)
-    steps = [("S", 0, trk.codegen_init(LOCK_SAT)), ("G", 0, NOM), ("l", 0) + lo, ("g", 0) + cg, ("R",), ("X", LOCK_T0),
-             ("L", 0, start.lo_rate), ("G", 0, start.ca_rate)] + ([("U", 0, start.ca_pause - 1)] if start.ca_pause else []) + \
-            [("X", LOCK_MS * CA_EPOCH - LOCK_T0), ("D",)]
-    return Scenario("lock", 1, steps, bits=bits)
+    return start_acquired("lock", bits, trk.codegen_init(LOCK_SAT), False, start, LOCK_T0, LOCK_MS * CA_EPOCH)
 
 
 def fault_scenario():
@@ -326,3 +326,249 @@ def fault_scenario():
     is negative the loop writes 2^27 - 1, outside the closed form's range; channel 1 is an ordinary channel beside it"""
     steps = _setup(0, CA1, cg=RATE_MIN, gc=(0, 0)) + _setup(1, CA7) + [("R",), ("X", 12 * 32736), ("D",)]
     return Scenario("fault", 2, steps, seed=17)
+
+
+# ---- signals (tests/test_trk_signal_cpu.py: the model against what a tracking channel must do; tests/test_trk_signal_gpu.py: the
+# kernel against the model on the same scenes).  Everything a bar is compared with comes from the scene, nothing from the code under test.
+BIN_HZ = 249.755859375              # gps.h: the acquisition's Doppler bin
+L1_HZ = 1575.42e6
+E1B_MODE = 0x800
+NAV_K = {False: 10, True: 30}       # nav bits compared: C/A (one per 20 epochs), E1B (one per epoch)
+
+
+def sat_data(k):
+    """64 seeded data bits of satellite k of a scene (k = 0: the lock check's)"""
+    return np.random.default_rng(5 + k).integers(0, 2, 64).astype(np.uint8)
+
+
+def sat_chips(row):
+    from flydog_sdr_gps_amd import prn, sats
+    _, t1, t2, kind = sats.SATS[row]
+    assert kind != sats.E1B
+    return prn.cacode(t1, t2)
+
+
+def sv(chips, code_phase, doppler_hz, cn0_dbhz, data_bits, boc=False, bit_epochs=20, theta=0.7):
+    """one satellite of scene(): the arguments of trk.scene_bits that describe it"""
+    return dict(chips=np.asarray(chips, np.uint8), code_phase=float(code_phase), doppler_hz=float(doppler_hz), cn0_dbhz=float(cn0_dbhz),
+                data_bits=np.asarray(data_bits, np.int64), boc=bool(boc), bit_epochs=int(bit_epochs), theta=float(theta))
+
+
+def scene(svs, n, seed, gaps=()):
+    """trk.scene_bits generalised: a packed 1-bit IF stream of n clocks holding every satellite of svs.  One noise draw per block comes
+    first and the satellites are added to it, in order, before the sign is taken; gaps: (first clock, end clock) ranges in which no
+    satellite is present.  With one satellite and no gap the bytes are trk.scene_bits' (the CPU test asserts it)."""
+    from flydog_sdr_gps_amd import trk
+    rng = np.random.Generator(np.random.PCG64(seed))
+    out = np.empty((n + 7) // 8, np.uint8)
+    block = 1 << 20
+    for s in range(0, n, block):
+        m = min(block, n - s)
+        t = np.arange(s, s + m, dtype=np.float64)
+        x = rng.standard_normal(m)
+        present = None
+        for g0, g1 in gaps:
+            if g0 < s + m and g1 > s:
+                present = np.ones(m) if present is None else present
+                present[(t >= g0) & (t < g1)] = 0.0
+        for v in svs:
+            chips = v["chips"]
+            a = np.sqrt(4.0 * 10.0 ** (v["cn0_dbhz"] / 10.0) / trk.FS)
+            rate = trk.CPS * (1.0 + v["doppler_hz"] / L1_HZ) / trk.FS
+            pos = t * rate + v["code_phase"]
+            idx = np.floor(pos).astype(np.int64)
+            code = 1.0 - 2.0 * chips[idx % chips.size]
+            if v["boc"]:
+                code = code * np.where(pos - idx >= 0.5, -1.0, 1.0)
+            nbit = (idx // chips.size) // v["bit_epochs"]
+            d = 1.0 - 2.0 * v["data_bits"][nbit % v["data_bits"].size]
+            term = a * d * code * np.cos(2 * np.pi * ((trk.FC + v["doppler_hz"]) / trk.FS) * t + v["theta"])
+            x = x + (term if present is None else term * present)
+        b = (x < 0).astype(np.uint8)
+        if m % 8:
+            b = np.concatenate([b, np.zeros(8 - m % 8, np.uint8)])
+        out[s // 8:s // 8 + b.size // 8] = np.packbits(b, bitorder="little")
+    return out
+
+
+def bits_sent(v, n):
+    """how many data bits of satellite v a scene of n clocks holds, counted as the lock check counts them: its length in bit times"""
+    return n // (16 * v["chips"].size * v["bit_epochs"])
+
+
+def start_at_bin(ch, word, bin, e1b, code=None, gains=None, pol=None):
+    """the command steps (without the reset) of a channel whose NCOs start at the centre of acquisition bin `bin`, with the rates of
+    CHANNEL::Start (the kg_acq_chan_start arithmetic) and the gains CHANNEL::Reset sends (gains: another pair of pairs)"""
+    from flydog_sdr_gps_amd import handoff, trk
+    st = handoff.chan_start(int(e1b), bin, 0, 0.0)
+    lo, cg = gains if gains is not None else trk.gains(bool(e1b))
+    return ([("S", ch, word)] + ([("C", ch, code)] if code is not None else []) + [("G", ch, NOM), ("l", ch) + lo, ("g", ch) + cg] +
+            ([("P", ch, pol)] if pol is not None else []) + [("L", ch, st.lo_rate), ("G", ch, st.ca_rate)])
+
+
+def start_acquired(name, bits, word, e1b, start, t0, nclocks, codes=()):
+    """one channel reset on clock 0 at the nominal code rate and started t0 clocks later, as CHANNEL::Start does, from a
+    handoff.ChanStart (or anything with lo_rate, ca_rate, ca_pause): the two rates, then the pause that lines the code up"""
+    from flydog_sdr_gps_amd import trk
+    lo, cg = trk.gains(bool(e1b))
+    steps = [("S", 0, word)] + ([("C", 0, 0)] if e1b else []) + [("G", 0, NOM), ("l", 0) + lo, ("g", 0) + cg, ("R",), ("X", t0),
+             ("L", 0, start.lo_rate), ("G", 0, start.ca_rate)] + ([("U", 0, start.ca_pause - 1)] if start.ca_pause else []) + \
+            [("X", nclocks - t0), ("D",)]
+    return Scenario(name, 1, steps, bits=bits, codes=codes)
+
+
+def acquire(oracle, chips, bits, e1b):
+    """the oracle's Sample() and Correlate() on the first 8192 bytes -> its result dict"""
+    from flydog_sdr_gps_amd import sats
+    return oracle.correlate(oracle.code_fft(chips, boc=bool(e1b)), oracle.sample_bits(bits[:8192]),
+                            limit=sats.E1B_LIMIT if e1b else sats.L1_LIMIT)[0]
+
+
+def lo_hz(records):
+    from flydog_sdr_gps_amd import trk
+    return np.array([r[7] for r in records], np.float64) / 2.0 ** 32 * trk.FS - trk.FC
+
+
+def unlocked_of(records, part):
+    """(epochs with ca_unlocked set, epochs) over records[part]"""
+    from flydog_sdr_gps_amd import trk
+    f = np.array([r[9] for r in records[part]], np.int64)
+    return int((f & trk.UNLOCKED).sum()), int(f.size)
+
+
+def signal_report(records, chan, truth):
+    """What one channel's run says about the signal it was given.  records: its epoch records; chan: its GPS_CHAN hex of the last
+    dump; truth: dict(doppler_hz, e1b, data_bits (None: not compared), nsent (bits_sent), tail (a slice of the records; None: the
+    last quarter), t0 (records before that clock, before an acquired channel's start, are left out)).  ->
+      lo_err     the mean LO error in Hz over each eighth of the run
+      lo_tail    the mean LO error over the tail
+      unlocked   (epochs with ca_unlocked set, epochs) over the tail
+      margins    (min (pp - pe) / pp, min (pp - pl) / pp) over the tail
+      match      the number of sent bits at which the last K saved nav bits (trk.nav_bits_of, K = 10 for C/A and 30 for E1B) end when
+                 they equal the sent ones up to one global sign -- only the scene's last or second-to-last bit is accepted -- else None
+    """
+    from flydog_sdr_gps_amd import trk
+    records = [r for r in records if r[0] >= truth.get("t0", 0)]
+    r = np.array(records, np.int64).reshape(len(records), 10)
+    n = len(r)
+    tail = truth.get("tail") or slice(n - n // 4, n)
+    err = lo_hz(records) - truth["doppler_hz"]
+    p = r[tail, 1:7].astype(np.float64) ** 2
+    pp, pe, pl = p[:, 0] + p[:, 1], p[:, 2] + p[:, 3], p[:, 4] + p[:, 5]
+    rep = {"lo_err": [float(e.mean()) for e in np.array_split(err, 8)], "lo_tail": float(err[tail].mean()),
+           "unlocked": unlocked_of(records, tail), "margins": (float(((pp - pe) / pp).min()), float(((pp - pl) / pp).min())), "match": None}
+    if truth.get("data_bits") is not None:
+        K = NAV_K[bool(truth["e1b"])]
+        ch = np.frombuffer(bytes.fromhex(chan), trk.chan_dtype)[0]
+        got = trk.nav_bits_of(ch, K)
+        data = np.asarray(truth["data_bits"], np.uint8)
+        for e in (truth["nsent"], truth["nsent"] - 1):
+            if e >= K:
+                sent = data[np.arange(e - K, e) % data.size]
+                if np.array_equal(got, sent) or np.array_equal(got, 1 - sent):
+                    rep["match"] = e
+                    break
+    return rep
+
+
+def report_line(name, ch, rep):
+    return "trk_signal %-18s ch %d  lo_err by eighth %s  tail %+.2f Hz  unlocked %d/%d  margins %.2f/%.2f  nav match %s" % (
+        name, ch, " ".join("%+.1f" % e for e in rep["lo_err"]), rep["lo_tail"], rep["unlocked"][0], rep["unlocked"][1],
+        rep["margins"][0], rep["margins"][1], rep["match"])
+
+
+PRN4 = (5 << 4) + 9
+QZ_ROW = 32                         # the first QZSS row of sats.SATS
+# where the prompt replica of a channel reset on clock 0 stands: half a chip (C/A) or a quarter chip (E1B) behind the early one, so
+# a scene whose code is that far before its epoch's start at clock 0 is lined up; the cases start 0.1 chip beside it
+CA_TAU0, E1B_TAU0 = 1023 - 0.5 + 0.1, 4092 - 0.25 + 0.05
+
+
+def _ca_sv(row, k, bin, off, cn0, tau=CA_TAU0):
+    return sv(sat_chips(row), tau, bin * BIN_HZ + off, cn0, sat_data(k))
+
+
+def _e1b_sv(k, bin, off, cn0, tau=E1B_TAU0):
+    return sv(e1b_code(1), tau, bin * BIN_HZ + off, cn0, sat_data(k), boc=True, bit_epochs=1)
+
+
+def _chan(word, bin, sat, e1b=False, gains=None, pol=None):
+    """sat: the index into the case's svs of the satellite this channel is on, None: not in the scene"""
+    return dict(word=word, bin=bin, sat=sat, e1b=e1b, gains=gains, pol=pol)
+
+
+def signal_cases():
+    """name -> case.  kind "bin": channels started at a bin's centre by start_at_bin; "acquired": one channel acquired by the oracle and
+    started by start_acquired t0 clocks after its reset.  epochs: the CPU length, gpu: the GPU length (None: CPU only), both in epochs
+    (epoch_clocks) of the case's own code (epochs None: GPU only).  gaps / gpu_gaps: in epochs.  tail: the epochs the bars are taken over (None: the last quarter)."""
+    from flydog_sdr_gps_amd import trk
+    C = {}
+
+    def add(name, svs, chans, epochs, gpu=None, e1b=False, kind="bin", seed=101, **kw):
+        C[name] = dict(name=name, svs=svs, chans=chans, epochs=epochs, gpu=gpu, epoch_clocks=E1B_EPOCH if e1b else CA_EPOCH, kind=kind,
+                       seed=seed + len(C), gaps=(), tail=None, pieces=None, max_unlocked=0.0, **kw)
+
+    ca1 = lambda: [_chan(CA1, 6, 0)]
+    # 1. C/A carrier pull-in from inside the acquisition bin
+    add("ca_pull_p100", [_ca_sv(0, 0, 6, 100.0, 55.0)], ca1(), 1500, gpu=800)
+    add("ca_pull_m120", [_ca_sv(0, 0, 6, -120.0, 55.0)], ca1(), 3000)
+    add("ca_pull_p60_48", [_ca_sv(0, 0, 6, 60.0, 48.0)], ca1(), 4000)
+    C["ca_pull_p60_48"]["max_unlocked"] = 0.01
+    C["ca_pull_p100"]["pieces"] = 100001            # the GPU run's X steps
+    # 2. E1B: BOC(1,1), quarter-chip latches, the latched memory code, 4 ms epochs, a nav bit per epoch
+    e1 = lambda pol=0: [_chan(E1B_MODE | 0, -9, 0, e1b=True, pol=pol)]
+    add("e1b_p0", [_e1b_sv(0, -9, 0.0, 50.0)], e1(), 600, e1b=True)
+    add("e1b_p30", [_e1b_sv(0, -9, 30.0, 50.0)], e1(), 600, gpu=200, e1b=True)
+    # 4. QZSS g2_init, negative Doppler
+    add("qzss_m1000", [_ca_sv(QZ_ROW, 0, -4, 25.0, 55.0)], [_chan(trk.codegen_init(QZ_ROW), -4, 0)], 600)
+    # 5. the handoff's edges
+    add("edge_ca_tau0", [_ca_sv(0, 0, 6, 20.0, 55.0, tau=0.1)], [_chan(CA1, None, 0)], 600, kind="acquired")
+    add("edge_ca_tau_end", [_ca_sv(0, 0, -13, -25.0, 55.0, tau=1022.7)], [_chan(CA1, None, 0)], 600, kind="acquired")
+    add("edge_e1b_tau0", [_e1b_sv(0, 4, -15.0, 50.0, tau=0.1)], [_chan(E1B_MODE | 0, None, 0, e1b=True)], 200, e1b=True, kind="acquired")
+    add("edge_e1b_tau1777", [_e1b_sv(0, -9, 20.0, 50.0, tau=1777.25)], [_chan(E1B_MODE | 0, None, 0, e1b=True)], 200, gpu=150, e1b=True,
+        kind="acquired")
+    # 6. loss of signal: 500 epochs of PRN 1, then noise
+    add("loss", [_ca_sv(0, 0, 6, 0.0, 55.0)], ca1(), 900)
+    C["loss"]["tail"] = slice(300, 500)
+    C["loss"]["gaps"] = ((500, 900),)
+    C["loss"].update(gpu=500, gpu_gaps=((300, 500),))
+    # 7. a channel on PRN 1, a scene holding PRN 7 only
+    add("wrong_prn", [_ca_sv(6, 1, 6, 0.0, 55.0)], [_chan(CA1, 6, None)], 400)
+    C["wrong_prn"]["tail"] = slice(200, None)
+    # 8. a bank on one stream: four satellites, six channels (PRN 4 is absent; PRN 1 twice, once with the LO gain lowered by one)
+    def bank(offs, cn0):
+        svs = [_ca_sv(0, 0, 6, offs[0], cn0[0]), _ca_sv(6, 1, -13, offs[1], cn0[1]), _ca_sv(QZ_ROW, 2, 2, offs[2], cn0[2]),
+               _e1b_sv(3, -9, offs[3], cn0[3])]
+        chans = [_chan(CA1, 6, 0), _chan(CA7, -13, 1), _chan(trk.codegen_init(QZ_ROW), 2, 2), _chan(E1B_MODE | 0, -9, 3, e1b=True, pol=0),
+                 _chan(PRN4, 6, None), _chan(CA1, 6, 0, gains=trk.gains(False, adj_lo=-1))]
+        return svs, chans
+    add("bank", *bank((40.0, -55.0, 80.0, 20.0), (52.0, 50.0, 52.0, 50.0)), 1500)
+    add("bank_gpu", *bank((25.0, -25.0, 28.0, 20.0), (55.0,) * 4), None, gpu=600)
+    return C
+
+
+
+def case_scenario(case, gpu=False, oracle=None, epochs=None):
+    """the case at its CPU length (gpu: at its GPU length; epochs: at another one) -> (Scenario, truth per channel (None: its satellite is not in the scene), acquisition (kind "acquired": (the oracle's result,
+    the ChanStart)))"""
+    from flydog_sdr_gps_amd import handoff, trk
+    n = (epochs or case["gpu" if gpu else "epochs"]) * case["epoch_clocks"]
+    gaps = tuple((a * case["epoch_clocks"], b * case["epoch_clocks"]) for a, b in (case.get("gpu_gaps", case["gaps"]) if gpu else case["gaps"]))
+    bits = scene(case["svs"], n, case["seed"], gaps)
+    codes = [e1b_code(1)] if any(c["e1b"] for c in case["chans"]) else []
+    truths = []
+    for c in case["chans"]:
+        v = None if c["sat"] is None else case["svs"][c["sat"]]
+        truths.append(None if v is None else dict(doppler_hz=v["doppler_hz"], e1b=c["e1b"], data_bits=None if gaps else v["data_bits"],
+                                                  nsent=bits_sent(v, n), tail=case["tail"],
+                                                  t0=LOCK_T0 if case["kind"] == "acquired" else 0))
+    if case["kind"] == "acquired":
+        c, v = case["chans"][0], case["svs"][0]
+        acq = acquire(oracle, v["chips"], bits, c["e1b"])
+        start = handoff.chan_start(int(c["e1b"]), acq["dop"], acq["idx"] * handoff.DECIM, LOCK_T0 / trk.FS)
+        return start_acquired(case["name"], bits, c["word"], c["e1b"], start, LOCK_T0, n, codes=codes), truths, (acq, start)
+    steps = []
+    for ch, c in enumerate(case["chans"]):
+        steps += start_at_bin(ch, c["word"], c["bin"], c["e1b"], code=0 if c["e1b"] else None, gains=c["gains"], pol=c["pol"])
+    steps += [("R",)] + (_pieces(n, (case["pieces"],)) if case["pieces"] else [("X", n)]) + [("D",)]
+    return Scenario(case["name"], len(case["chans"]), steps, bits=bits, codes=codes), truths, None
