@@ -249,7 +249,11 @@ struct acq_red { float p; int i; float s; int pad; };
 // Round 4: each claim counter on its own 128-byte line.  Agent-scope atomics on ONE line are served one at a time, some 12.7 ns
 // each chip-wide (the waterfall kernel's single counter was its floor, kg_wf.hip); the eight group counters sat in one line.
 #define ACQ_CLAIM_STRIDE 32
-#define ACQ_LDS_BYTES (2 * SUB * sizeof(float2) + 4 * sizeof(acq_red) + 16)     // + the claimed cell index
+#define ACQ_LDS_BYTES (2 * SUB * sizeof(float2) + 16)     // + the two slots of the claimed cell index
+
+// What one wave of acq_correlate_kernel leaves of a cell: its maximum, the lowest lag holding it and its total.  The four records of
+// a cell -- d_parts[cell][wave], cell = the cell's index in cells[] -- are merged by acq_select_kernel.
+struct __attribute__((aligned(16))) acq_part { float p; int i; float s; int pad; };
 
 // One (block, SV) pair, prepared by the host: 16 bytes = one s_load_dwordx4.  The
 // cells of a launch are the pairs x the Doppler bins; the kernel walks (pair, bin)
@@ -264,8 +268,8 @@ struct acq_pair_desc {
 struct acq_cell_desc { int data_off, code_off, dop, limit, out; };
 
 // Launch constants (kernarg).  The cells of XCD group x are (pair x + 8 pg, bin di) in the order
-// cell = pg * ndop + di.  A persistent workgroup takes cells `slot` and `slot + nslots` and then
-// claims one more at a time from the group's counter (an agent-scope atomic): the two workgroups
+// cell = pg * ndop + di.  A persistent workgroup takes cells `slot`, `slot + nslots` and `slot + 2 nslots`
+// and then claims one more at a time from the group's counter (an agent-scope atomic): the two workgroups
 // of a CU do not run at the same speed -- the older one wins the vector-issue arbitration (810 us
 // against 1036 us for the same 82 cells, profiles/r02_acq_wg_life.txt) -- so a static split leaves
 // every CU half empty for the last fifth of the launch.
@@ -296,15 +300,17 @@ __global__ __launch_bounds__(256, 2) void acq_correlate_kernel(
     int *__restrict__ claim,                   // [8][ACQ_CLAIM_STRIDE] per-group cell counters, zero at launch
     acq_walk walk,
     int halo,                                  // H of the code planes
-    kg_acq_cell *__restrict__ cells,           // [nblocks][nsats][ndop]
+    acq_part *__restrict__ parts,              // [nblocks][nsats][ndop][4 waves]: merged into cells[] by acq_select_kernel
     unsigned long long *__restrict__ stamps = nullptr)
 {
     static_assert(P == 4 || P == 16, "N = 16384 or 65536");
     constexpr int LOGP = P == 4 ? 2 : 4;
     extern __shared__ __attribute__((aligned(16))) float2 smem[];
     float2 *tileA = smem, *tileB = smem + SUB;
-    acq_red *red = (acq_red *) (smem + 2 * SUB);
-    volatile int *red_claim = (volatile int *) (red + 4);
+    // (in the LDS address space by name: through a generic pointer a volatile access is a FLAT one, and the wait behind it
+    // is for every vector-memory operation in flight -- the wave records' stores among them)
+    typedef __attribute__((address_space(3))) volatile int acq_lds_int;
+    acq_lds_int *claim_slot = (acq_lds_int *) (smem + 2 * SUB);
     const int t = threadIdx.x;
     // diagnostics: one workgroup, thread 0, 16 stamps per (cell, k2) item
     unsigned long long *st = (STAMPS && t == 0 && blockIdx.x == 8) ? stamps : nullptr;
@@ -399,10 +405,21 @@ __global__ __launch_bounds__(256, 2) void acq_correlate_kernel(
     acq_cell_desc cur = describe(cur_idx);
     fetch(cur.data_off, cur.code_off, cur.dop, P - 1);
 
+    // The cell boundary has no barrier of its own.  The index of cell k + 3 of this workgroup's walk is claimed at the top of
+    // cell k, PUBLISHED by thread 0 at the end of cell k in claim_slot[k & 1] and READ by every wave at the end of cell k + 1,
+    // where it becomes the `nxt` of cell k + 2.  Two slots suffice:
+    //   read after write: the store precedes thread 0's arrival at the first barrier of cell k + 1's item loop, the loads
+    //     follow the readers' departure from its last (2 P barriers, each with its LDS fence);
+    //   write after read: slot k & 1 is next stored at the end of cell k + 2, and thread 0 cannot leave the first barrier of
+    //     cell k + 2's item loop before every wave has arrived there, its load at the end of cell k + 1 complete.
+    // The third static cell is published here as the cell before the first would have: no slot is ever read unpublished,
+    // whichever of the static cells is the first that does not exist.
+    if (t == 0) claim_slot[1] = slot + 2 * nslots;
+    int par = 0;                                       // k & 1
+
     int st_item = 0;
     for (;;) {
-        // one cell ahead; the cell after that is claimed now and its index crosses the workgroup
-        // through LDS at this cell's last barrier
+        // one cell ahead; the cell three after this one is claimed now
         const bool more = nxt_idx < ncell;
         const acq_cell_desc nxt = describe(more ? nxt_idx : cur_idx);
         int claimed = 0;
@@ -572,40 +589,19 @@ __global__ __launch_bounds__(256, 2) void acq_correlate_kernel(
             }
             bi = t + 256 * br;
         }
-#define ACQ_RED_STEP(L)                                                               \
-        {                                                                                \
-            const float op = kg_xchg<L>(bp), os = kg_xchg<L>(sum);                       \
-            const int oi = kg_xchg<L>(bi);                                               \
-            const bool take = (op > bp) | ((op == bp) & (oi < bi));   /* branch-free */  \
-            bp = take ? op : bp; bi = take ? oi : bi;                                    \
-            sum += os;                                                                   \
-        }
-        // the wave's maximum, the lowest n holding it (what one strict-> scan in ascending n finds), the total
+        // the wave's maximum, the lowest n holding it (what one strict-> scan in ascending n finds), the total: one 16-byte
+        // record per wave; the four are merged, divided and stored as the cell by acq_select_kernel (search.cpp:493-494)
         {
             float wmax = bp, wsum = sum;
             kg_wave_max_sum(wmax, wsum);
             const int wn = kg_wave_min(bp == wmax ? bi : 0x7fffffff);
-            // red[] was last read before this cell's barriers
-            if ((t & 63) == 0) { red[t >> 6].p = wmax; red[t >> 6].i = wn; red[t >> 6].s = wsum; }
+            if ((t & 63) == 0) parts[4 * cur.out + (t >> 6)] = acq_part{wmax, wn, wsum, 0};
         }
-        if (t == 0) *red_claim = 2 * nslots + claimed;
-        __syncthreads();
-        // (rewritten only after eight more barriers; readfirstlane: the index must stay wave-uniform, or
-        // every buffer load below turns into a waterfall loop over its descriptor)
-        const int nn_idx = __builtin_amdgcn_readfirstlane(*red_claim);
-        if (t < 64) {                                  // lanes 0..3 of wave 0 merge the four waves
-            const acq_red r = red[t & 3];
-            bp = r.p; bi = r.i; sum = r.s;
-            ACQ_RED_STEP(0) ACQ_RED_STEP(1)
-            if (t == 0) {
-                const float ave = sum / (float) limit;     // :493
-                kg_acq_cell cc;
-                cc.snr = bp / ave;                         // :494
-                cc.max_pwr = bp; cc.tot_pwr = sum; cc.idx = bi;
-                cells[cur.out] = cc;
-            }
-        }
-#undef ACQ_RED_STEP
+        // (see the head of the loop; readfirstlane: the index must stay wave-uniform, or every buffer load below turns into a
+        // waterfall loop over its descriptor)
+        if (t == 0) claim_slot[par] = 3 * nslots + claimed;
+        const int nn_idx = __builtin_amdgcn_readfirstlane(claim_slot[par ^ 1]);
+        par ^= 1;
         if (STAMPS) wg_cells++;
         if (!more) break;
         cur = nxt; cur_idx = nxt_idx; nxt_idx = nn_idx;
@@ -1004,17 +1000,41 @@ __global__ __launch_bounds__(512, 1) void acq_correlate8_kernel(
 // search.cpp:455,495: best Doppler bin per (block, SV): the serial scan keeps the
 // first bin (ascending dop) holding the maximum snr, and only if it is > 0.
 // One wave per pair; lane l scans bins l, l+64, ...
-__global__ __launch_bounds__(64) void acq_select_kernel(const kg_acq_cell *__restrict__ cells,
+// The wave of pair q of the launch's table [4096-lag pairs | 16368-lag pairs].  The cells of a 16368-lag pair arrive
+// complete (acq_correlate8_kernel).  Those of a 4096-lag pair arrive as four wave records each (acq_correlate_kernel) and
+// are finished here, each bin by its lane: the merge in the order (w0, w1), (w2, w3), then the two halves -- the higher
+// maximum, the lower lag among equals, the totals as (s0 + s1) + (s2 + s3) -- and search.cpp:493-494.
+__global__ __launch_bounds__(64) void acq_select_kernel(kg_acq_cell *__restrict__ cells, const acq_part *__restrict__ parts,
+                                                       const acq_pair_desc *__restrict__ pairs, int np1,
                                                        int npairs, int dop_lo, int ndop,
                                                        kg_acq_result *__restrict__ out, int *__restrict__ claim)
 {
-    const int p = blockIdx.x, lane = threadIdx.x;
-    if (p == 0 && lane < 16) claim[lane * ACQ_CLAIM_STRIDE] = 0;          // the correlators' cell counters, for the next launch
-    if (p >= npairs) return;
+    const int q = blockIdx.x, lane = threadIdx.x;
+    if (q == 0 && lane < 16) claim[lane * ACQ_CLAIM_STRIDE] = 0;          // the correlators' cell counters, for the next launch
+    if (q >= npairs) return;
+    const acq_pair_desc pd = pairs[q];
+    const int p = pd.out / ndop;                                          // the pair's place in results[]
     float bs = 0.f;
     int bd = 0x7fffffff, bidx = 0;
     for (int di = lane; di < ndop; di += 64) {
-        const kg_acq_cell c = cells[(size_t) p * ndop + di];
+        kg_acq_cell c;
+        if (q < np1) {
+            const acq_part *w = parts + 4 * ((size_t) pd.out + di);
+            acq_part a = w[0], b = w[2];
+            const acq_part a1 = w[1], b1 = w[3];
+            auto merge = [](acq_part &x, const acq_part &o) {
+                const bool take = (o.p > x.p) | ((o.p == x.p) & (o.i < x.i));
+                x.p = take ? o.p : x.p; x.i = take ? o.i : x.i;
+                x.s += o.s;
+            };
+            merge(a, a1); merge(b, b1); merge(a, b);
+            const float ave = a.s / (float) pd.limit;      // :493
+            c.snr = a.p / ave;                             // :494
+            c.max_pwr = a.p; c.tot_pwr = a.s; c.idx = a.i;
+            cells[(size_t) pd.out + di] = c;
+        } else {
+            c = cells[(size_t) pd.out + di];
+        }
         if (c.snr > bs) { bs = c.snr; bd = di; bidx = c.idx; }
     }
 #pragma unroll
@@ -1074,6 +1094,7 @@ struct kg_acq {
     hipStream_t cstream; hipEvent_t ev_in_free; bool in_free_set;
     uint8_t *d_chips;  // [E1B_CODELEN max]
     kg_acq_cell *d_cells;
+    acq_part *d_parts;     // [max_blocks][max_sats][ndop][4]  wave records of the 4096-lag correlator, between it and acq_select_kernel
     kg_acq_result *d_results;
     int *d_claim;      // [16][ACQ_CLAIM_STRIDE] cell counters of the C/A ([0..8)) and E1B ([8..16)) launches; zero between launches
     std::vector<int> limits, code_set;
@@ -1237,6 +1258,7 @@ static int acq_init(kg_acq *a)
     { const int rc_ = kg_stream_get(ctx->device, &a->cstream); if (rc_) return rc_; }
     KG_HIP(hipMalloc((void **) &a->d_chips, 8192));
     KG_HIP(hipMalloc((void **) &a->d_cells, sizeof(kg_acq_cell) * (size_t) max_blocks * max_sats * a->ndop));
+    KG_HIP(hipMalloc((void **) &a->d_parts, sizeof(acq_part) * 4 * (size_t) max_blocks * max_sats * a->ndop));
     KG_HIP(hipMalloc((void **) &a->d_results, sizeof(kg_acq_result) * (size_t) max_blocks * max_sats));
     KG_HIP(hipMalloc((void **) &a->d_claim, sizeof(int) * 16 * ACQ_CLAIM_STRIDE));
     KG_HIP(hipMemset(a->d_claim, 0, sizeof(int) * 16 * ACQ_CLAIM_STRIDE));
@@ -1360,7 +1382,7 @@ void kg_acq_destroy(kg_acq *a)
     if (a->ev_batch) (void) hipEventDestroy(a->ev_batch);
     if (a->ev_in_free) (void) hipEventDestroy(a->ev_in_free);
     if (a->cstream) { (void) hipStreamSynchronize(a->cstream); kg_stream_put(a->ctx->device, a->cstream); }
-    (void) hipFree(a->d_cells); (void) hipFree(a->d_results); (void) hipFree(a->d_claim);
+    (void) hipFree(a->d_cells); (void) hipFree(a->d_parts); (void) hipFree(a->d_results); (void) hipFree(a->d_claim);
     delete a;
 }
 
@@ -1699,7 +1721,7 @@ static void launch_correlate(kg_acq *a, hipStream_t st, int first, const acq_pai
                        (const float2 *) (a->d_data + (size_t) first * a->fft_len), (const float2 *) a->d_code,
                        (const float2 *) a->ctx->d_tab4096, (const float2 *) a->d_tabN,
                        (const float2 *) a->d_comb, d_pairs,
-                       a->d_claim, w, a->halo, a->d_cells, d_stamps);
+                       a->d_claim, w, a->halo, a->d_parts, d_stamps);
 }
 
 extern "C" {
@@ -1779,7 +1801,8 @@ int kg_acq_correlate_blocks_async(kg_acq *a, int first, int nblocks, const int *
     }
     const int npairs = nblocks * nsats;
     hipLaunchKernelGGL(acq_select_kernel, dim3(npairs), dim3(64), 0, st,
-                       (const kg_acq_cell *) a->d_cells, npairs, a->dop_lo, a->ndop, a->d_results, a->d_claim);
+                       a->d_cells, (const acq_part *) a->d_parts, a->d_pairs1, a->np1, npairs, a->dop_lo, a->ndop,
+                       a->d_results, a->d_claim);
     KG_HIP(hipGetLastError());
     if (a->own_fstream) {
         KG_HIP(hipEventRecord(a->ev_done[first], st));

@@ -47,6 +47,15 @@ for it in range(24):
 print("mean over %d items (cycles): " % cnt + ", ".join("%s %.0f" % (l, x / cnt) for l, x in zip(labels, tot)))
 per = [items[i + 1][0] - items[i][0] for i in range(len(items) - 1)]
 print("item period (start to start): median %d cycles; in-item %.0f" % (int(np.median(per)), tot.sum() / cnt))
+# the cell boundary: what a cell's period holds beyond its P items (the stamped items are consecutive from the workgroup's
+# first cell on)
+P = s.fft_len // 4096
+cper = [items[P * (k + 1)][0] - items[P * k][0] for k in range((len(items) - 1) // P)]
+if cper:
+    cell, item = int(np.median(cper)), int(np.median([per[i] for i in range(len(per)) if (i + 1) % P]))
+    print("cell period: median %d cycles (%d cells); item period inside a cell %d; outside the items %d cycles per cell = %.1f %%"
+          % (cell, len(cper), item, cell - P * item, 100.0 * (cell - P * item) / cell))
+    print("last item's start to the next cell's first: %s" % [per[i] for i in range(P - 1, len(per), P)])
 
 # every workgroup's life
 nwg = ctx.num_cus * 2
