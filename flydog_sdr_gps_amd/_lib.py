@@ -217,6 +217,13 @@ SYMBOLS = {
     "kg_trk_process_bits": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _vp]),
     "kg_trk_get_chan": (_i, [_vp, _i, _vp]),
     "kg_trk_get_clocks": (_i, [_vp, C.POINTER(C.c_uint64), _vp]),
+    "kg_nav_create": (_i, [_vp, _i, C.POINTER(_vp)]),
+    "kg_nav_destroy": (None, [_vp]),
+    "kg_nav_set_mode": (_i, [_vp, _i, _i]),
+    "kg_nav_push_bits_dev": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _i, _vp]),
+    "kg_nav_push_bits": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _i, _vp]),
+    "kg_nav_push_epochs_dev": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _sz, _i, _vp]),
+    "kg_nav_get_state": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "kg_aper_create": (_i, [_vp, _i, C.POINTER(_vp)]),
     "kg_aper_destroy": (None, [_vp]),
     "kg_aper_update_dev": (_i, [_vp, _vp, _i, _vp, _sz, _vp, _i]),

@@ -905,6 +905,69 @@ int kg_trk_process_bits(kg_trk *trk, const uint8_t *bits, size_t nclocks, kg_trk
 int kg_trk_get_chan(kg_trk *trk, int ch, uint8_t *out);                             /* KG_TRK_CHAN_BYTES bytes: GPS_CHAN as CmdGetChan uploads it */
 int kg_trk_get_clocks(kg_trk *trk, uint64_t *clock, uint32_t *replicas);            /* clocks consumed; the 18-bit replica word of each channel */
 
+/* ---------------------------------------------------------------------------
+ * Nav frame sync: what CHANNEL::Tracking() does with the nav bits of a channel -- the `holding` loop (gps/channel.cpp:441-506),
+ * CHANNEL::ParityCheck (:731-832), L1_parity (:125-135) and, for Galileo, E1B_subframe (gps/GNSS-SDRLIB/sdrnav_gal.cpp:382-514): the
+ * 30 x 8 de-interleave, KA9Q's K = 7 rate-1/2 Viterbi decoder (gps/ka9q-fec/viterbi27_port.cpp, polynomials 0x4f / 0x6d, metrics
+ * from 63 / 0 without renormalisation, ties keep m0, chainback past 6 decisions from state 0), the even/odd test, checkcrc_e1b
+ * (:293-319, CRC-24Q), the alert bits and the health bits decode_word5 reads (:163-174).  All integer, equal to the reference bit for bit.
+ *
+ * A channel is C/A (frames of 300 bits) or E1B (pages of 500 symbols).  It holds the reference's buf / holding and the index of
+ * buf[0] in the channel's stream.  Pushed bits are appended; then, while holding >= 300 / 500, the head is judged as ParityCheck
+ * judges it and nbits are dropped: 1 without a preamble (C/A: 8 bits, either polarity; E1B: the 10 symbols at the head and again
+ * 250 later, the same polarity); C/A 30 (i + 1) when word i is the first to fail L1_parity, 300 after ten good words; E1B 250 on
+ * GPS_ERR_SLIP, else 500.  Every head that passes the preamble test gives one kg_nav_frame, in stream order.  No decision depends
+ * on holding beyond holding >= 300 / 500, so the records do not depend on how the stream is cut into pushes.
+ *
+ * Not here: whatever reads a validated frame into doubles or statistics (Ephemeris[].Subframe, decode_word0..10, CHANNEL::Subframe,
+ * and with them nav.tow_updated, which the host derives from id and data); probation, alert, abort, bits_tow and
+ * expecting_preamble, which are host decisions on id, err, bit and the count of bits pushed (bits_tow = holding - subframe_bits
+ * depends on the reference's 16-bit polling grain: `bit` replaces it); the gps_debug dropped-subframe simulation and TEST_VECTOR.
+ * ------------------------------------------------------------------------- */
+typedef struct kg_nav kg_nav;
+enum { KG_NAV_L1 = 0, KG_NAV_E1B = 1,
+       KG_NAV_ERR_SLIP = 1, KG_NAV_ERR_CRC = 2, KG_NAV_ERR_ALERT = 3, KG_NAV_ERR_OOS = 4, KG_NAV_ERR_PAGE = 5,   /* GPS_ERR_*, gps/gps.h:187-191 */
+       KG_NAV_ERR_PARITY = 16,           /* C/A: L1_parity failed (the reference returns no code of its own, only nbits) */
+       KG_NAV_MAX_PUSH = 65536,          /* bits (epochs) per channel and call */
+       KG_NAV_MAX_HELD = 499 };
+typedef struct {
+    uint64_t bit;          /* index of the frame's first bit in the channel's stream (0 = the first bit pushed since kg_nav_set_mode) */
+    int32_t  err;          /* 0; C/A: KG_NAV_ERR_PARITY; E1B: KG_NAV_ERR_SLIP .. KG_NAV_ERR_PAGE (PAGE cannot occur: a 6-bit id is 0..63) */
+    int32_t  consumed;     /* the nbits ParityCheck returns */
+    int32_t  inverted;     /* 0 / 1 */
+    int32_t  id;           /* C/A: bits 49..51 of the corrected buffer, MSB first (the subframe number, as Ephemeris reads it); on a parity
+                              error the index of the failing word.  E1B: the word type as E1B_subframe returns it (on a CRC error
+                              getbitu(dec_e1b1, 2, 6); on SLIP and ALERT 0) */
+    uint8_t  data[40];     /* C/A and err == 0: the 300 bits as buf holds them after L1_parity, MSB first, 38 bytes + 2 zero; E1B:
+                              dec_e1b1[15] then dec_e1b2[15], then 10 zero; C/A parity error: all zero */
+} kg_nav_frame;
+int kg_nav_create(kg_ctx *ctx, int nchan, kg_nav **out);                            /* 1 <= nchan <= KG_TRK_MAX_CHANS; every channel C/A and empty */
+void kg_nav_destroy(kg_nav *nav);
+/* KG_NAV_L1 or KG_NAV_E1B; empties the channel, restarts its stream index and its nav-bit machine, as Tracking() does on entry (:399-407).
+ * In stream order, without waiting. */
+int kg_nav_set_mode(kg_nav *nav, int ch, int mode);
+/* Appends nbits[ch] (host array, one per channel, 0 .. KG_NAV_MAX_PUSH) bits to every channel and runs the loop above.  d_bits + ch *
+ * chan_stride: one byte per bit, of which only bit 0 is read, as buf is; exactly nbits[ch] bytes of row ch are read.  Records go to row
+ * ch of d_frames (d_frames + ch * frame_stride, 8-byte aligned, frame_stride >= cap), d_counts[ch] (device, int32) = how many: exactly
+ * that many records and nchan counts are written.  cap >= the largest of ceil(nbits[ch] / 30) over the C/A channels and ceil(nbits[ch]
+ * / 250) over the E1B ones, else KG_ERR_INVALID with nothing done: a record's head lies at least 30 / 250 bits behind the one before it, and
+ * with at most 299 / 499 bits held the heads of one call span nbits[ch] positions.  Enqueue only. */
+int kg_nav_push_bits_dev(kg_nav *nav, const uint8_t *d_bits, size_t chan_stride, const int32_t *nbits, kg_nav_frame *d_frames,
+                         size_t frame_stride, int cap, int32_t *d_counts);
+int kg_nav_push_bits(kg_nav *nav, const uint8_t *bits, size_t chan_stride, const int32_t *nbits, kg_nav_frame *frames, size_t frame_stride,
+                     int cap, int32_t *counts);          /* the same on host memory; synchronises */
+/* The same from the rows and counts exactly as kg_trk_process_bits_dev leaves them (d_counts_in[ch] records of row ch, -1 - n from a
+ * stopped channel = n records; epoch_cap: that call's cap, counts above it are cut to it), nothing going back to the host in between:
+ * the nav-bit machine of GPS_Method (e_cpu/kiwi.gps.asm NavSave; every epoch's KG_TRK_INAV flag for E1B, the bit after 19 equal epochs
+ * for C/A, a glitch counted as nav_glitch counts it) gives the bits.  Its nav_ms / nav_prev start at 0 at kg_nav_set_mode, so they equal
+ * the firmware's when both start at the channel's reset.  Of a record only `flags` is read.  cap >= the bound above with nbits[ch] =
+ * epoch_cap (E1B) or ceil(epoch_cap / 20) (C/A).  Enqueue only. */
+int kg_nav_push_epochs_dev(kg_nav *nav, const kg_trk_epoch *d_epochs, size_t chan_stride, const int32_t *d_counts_in, int epoch_cap,
+                           kg_nav_frame *d_frames, size_t frame_stride, int cap, int32_t *d_counts);
+/* holding, the stream index of buf[0], buf[0 .. holding) one byte per bit (room for KG_NAV_MAX_HELD), the bits pushed since
+ * kg_nav_set_mode, and nav[3] = nav_ms, nav_prev, nav_glitch.  Synchronises. */
+int kg_nav_get_state(kg_nav *nav, int ch, int32_t *holding, uint64_t *bit0, uint8_t *held, uint64_t *pushed, int32_t *nav3);
+
 /* kg_fir_process_dev plus the extension taps of ProcessData (SURVEY.md 8(f) rank 4;
  * rx/CuteSDR/fastfir.cpp:278-302): for block b of list entry i, 1024 complex floats at
  * d_pre / d_post + i*tap_stride + b*1024 (either may be NULL): pre = the forward spectrum
