@@ -224,6 +224,19 @@ SYMBOLS = {
     "kg_nav_push_bits": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _i, _vp]),
     "kg_nav_push_epochs_dev": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _sz, _i, _vp]),
     "kg_nav_get_state": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "kg_eph_create": (_i, [_vp, _i, C.POINTER(_vp)]),
+    "kg_eph_destroy": (None, [_vp]),
+    "kg_eph_set_sat": (_i, [_vp, _i, _i, _i]),
+    "kg_eph_clear_sat": (_i, [_vp, _i]),
+    "kg_eph_clear_chan": (_i, [_vp, _i]),
+    "kg_eph_push_frames_dev": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _sz]),
+    "kg_eph_push_frames": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _sz]),
+    "kg_eph_get": (_i, [_vp, _i, _vp]),
+    "kg_eph_get_chan": (_i, [_vp, _i, _vp, _vp]),
+    "kg_eph_get_utc": (_i, [_vp, _vp]),
+    "kg_eph_sv_dev": (_i, [_vp, _vp, _i, _vp]),
+    "kg_eph_sv": (_i, [_vp, _vp, _i, _vp]),
+    "kg_eph_replica": (None, [C.c_uint32, _vp, _vp]),
     "kg_aper_create": (_i, [_vp, _i, C.POINTER(_vp)]),
     "kg_aper_destroy": (None, [_vp]),
     "kg_aper_update_dev": (_i, [_vp, _vp, _i, _vp, _sz, _vp, _i]),

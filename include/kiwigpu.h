@@ -919,8 +919,8 @@ int kg_trk_get_clocks(kg_trk *trk, uint64_t *clock, uint32_t *replicas);        
  * GPS_ERR_SLIP, else 500.  Every head that passes the preamble test gives one kg_nav_frame, in stream order.  No decision depends
  * on holding beyond holding >= 300 / 500, so the records do not depend on how the stream is cut into pushes.
  *
- * Not here: whatever reads a validated frame into doubles or statistics (Ephemeris[].Subframe, decode_word0..10, CHANNEL::Subframe,
- * and with them nav.tow_updated, which the host derives from id and data); probation, alert, abort, bits_tow and
+ * Not here: whatever reads a validated frame into doubles or statistics (Ephemeris[].Subframe, decode_word0..10 and with them
+ * nav.tow_updated: kg_eph, below; CHANNEL::Subframe); probation, alert, abort, bits_tow and
  * expecting_preamble, which are host decisions on id, err, bit and the count of bits pushed (bits_tow = holding - subframe_bits
  * depends on the reference's 16-bit polling grain: `bit` replaces it); the gps_debug dropped-subframe simulation and TEST_VECTOR.
  * ------------------------------------------------------------------------- */
@@ -967,6 +967,90 @@ int kg_nav_push_epochs_dev(kg_nav *nav, const kg_trk_epoch *d_epochs, size_t cha
 /* holding, the stream index of buf[0], buf[0 .. holding) one byte per bit (room for KG_NAV_MAX_HELD), the bits pushed since
  * kg_nav_set_mode, and nav[3] = nav_ms, nav_prev, nav_glitch.  Synchronises. */
 int kg_nav_get_state(kg_nav *nav, int ch, int32_t *holding, uint64_t *bit0, uint8_t *held, uint64_t *pushed, int32_t *nav3);
+
+/* ---------------------------------------------------------------------------
+ * Ephemeris decode and satellite position and clock: what reads a validated frame into numbers and what the position solver asks
+ * of them.  Frames in (the rows and counts of kg_nav_push_*_dev, on the device), EPHEM out: EPHEM::Subframe with Subframe1..4,
+ * LoadPage18 and Valid (gps/ephemeris.cpp:51-110, :218-252) for C/A; decode_page_e1b with decode_word0..6 and 10
+ * (gps/GNSS-SDRLIB/sdrnav_gal.cpp:28-286, :327-359) and EPHEM::PageN, Page0..6 (ephemeris.cpp:256-370) for Galileo.  Then, per
+ * clock snapshot, LoadAtomic's Valid gate and the per-replica body of LoadFromReplicas (gps/solve.cpp:319-361): SNAPSHOT::GetClock
+ * (:168-244), GetClockCorrection, TimeOfEphemerisAge, EccentricAnomaly and GetXYZ (ephemeris.cpp:114-207).
+ *
+ * The decoded state equals the reference's bit for bit, doubles included:
+ *  - rtklib.h's P2_32, P2_33, P2_35, P2_43 and sdrnav_gal.cpp's P2_46 are decimal text that is NOT a power of two as a double (one or
+ *    two ulp below): Galileo's e, tgd, OMGd, deln, idot, f1 and A_0G are the raw field times THAT double, then (angles) times SC2RAD,
+ *    two roundings left to right.  The C/A fields take exact powers of two (pow(2, -n)).
+ *  - gps.h's PI (C/A angles) and rtklib.h's SC2RAD (Galileo angles) are both the text 3.1415926535898, 16 ulp above pi.
+ *  - Galileo's week_gst, toes and toc_gst belong to the CHANNEL (CHANNEL::nav.sdreph; CHANNEL::Start clears none of them,
+ *    channel.cpp:274-278): words 1 and 4 hand on a t_oe / t_oc only once the channel has seen a week (week_gst != 0), Page1 / Page4 /
+ *    Page5 keep the old t_oe / t_oc when handed 0, and a channel bound to another satellite carries its week along.  A satellite's
+ *    slot persists in the same way (EPHEM::Init sets only sat and isE1B).  GST weeks up to 2526 (beyond, the reference's int overflows).
+ *  - Applied: C/A frames with err == 0 (ParityCheck reaches Ephemeris[sat].Subframe only then); E1B frames with err == 0 or
+ *    KG_NAV_ERR_OOS, which decode_word5 raises after Page5 was applied.  SLIP, CRC, ALERT and PARITY frames change nothing.
+ * Position and clock pass through sin, cos, atan2 and sqrt, where the device's library and the host's may differ in the last
+ * bit: x, y, z within 1e-3 m, ct within 2 ulp, t_k within 2 ulp of t_tx of the reference.
+ *
+ * Not here: PosSolver, the EKF, ionosphere and troposphere, LoadReplicas' glitch guard and include_E1B filter; probation, alert,
+ * abort and expecting_preamble (host decisions; the notes carry what bits_tow needs); CHANNEL::Subframe's statistics; tow_time and the
+ * L_* debug members; almanac words 7..9.
+ * ------------------------------------------------------------------------- */
+typedef struct kg_eph kg_eph;
+enum { KG_EPH_MAX_SATS = 64,             /* MAX_SATS, gps/gps.h:123 */
+       KG_EPH_NAVSTAR = 0, KG_EPH_CA = 1, KG_EPH_E1B = 2,        /* a satellite's kind: Navstar; other C/A (QZSS: page 18 leaves UTC alone); Galileo */
+       KG_EPH_SV_NOT_VALID = 1, KG_EPH_SV_POWER = 2, KG_EPH_SV_TOW_DELAYED = 4, KG_EPH_SV_BAD = 8, KG_EPH_SV_TOO_OLD = 16 };
+typedef struct {           /* EPHEM's data members as the decode writes them; unsigned as uint32_t */
+    uint32_t IODN[4];
+    uint32_t IODC, t_oc;
+    double   t_gd, a_f[3];
+    uint32_t IODE2, t_oe;
+    double   C_rs, dn, M_0, C_uc, e, C_us, sqrtA;
+    uint32_t IODE3, kind;  /* kind: KG_EPH_* of the last kg_eph_set_sat on this satellite (isE1B) */
+    double   C_ic, OMEGA_0, C_is, i_0, C_rc, omega, OMEGA_dot, IDOT;
+    double   alpha[4], beta[4];
+    uint32_t week, tow, sub, tow_pg;
+    double   A_0G, A_1G;
+    uint32_t t_0G, WN_0G;
+    int32_t  valid, pad_;  /* EPHEM::Valid now */
+    uint64_t tow_bit;      /* ours: bit_next of the last frame that updated the TOW, so that bits_tow = bits pushed - tow_bit */
+} kg_ephem;
+typedef struct {
+    int32_t  applied;      /* the frame reached the decode */
+    int32_t  tow_updated;  /* nav.tow_updated; 1 for every applied C/A subframe (channel.cpp:827) */
+    int32_t  sub, valid;   /* the satellite's sub and Valid after this frame */
+    uint32_t tow, week;    /* likewise */
+    uint64_t bit_next;     /* the frame's bit + consumed */
+} kg_eph_note;
+typedef struct { int32_t sat, bits, bits_tow, ms, chips, cg_phase; float power; } kg_eph_snap;    /* SNAPSHOT's inputs */
+typedef struct { double x, y, z, ct, t_k; int32_t week, flags; } kg_eph_pos;    /* _sv[0..3], t_k, _week; KG_EPH_SV_* */
+int kg_eph_create(kg_ctx *ctx, int nchan, kg_eph **out);  /* 1 <= nchan <= KG_TRK_MAX_CHANS; 64 satellite slots; everything zero, no channel bound */
+void kg_eph_destroy(kg_eph *eph);
+/* Binds channel ch to satellite slot sat (0 .. 63) of kind KG_EPH_*, as CHANNEL::Start does: the channel keeps its week_gst / toes /
+ * toc_gst and the slot its contents; only the slot's kind (and with it valid) is set.  sat = -1 unbinds: the channel's frames are
+ * then read and noted with applied = 0.  A satellite bound to another channel: KG_ERR_INVALID.  In stream order, without waiting. */
+int kg_eph_set_sat(kg_eph *eph, int ch, int sat, int kind);
+int kg_eph_clear_sat(kg_eph *eph, int sat);                /* ours: the slot back to zero (its kind stays).  In stream order */
+int kg_eph_clear_chan(kg_eph *eph, int ch);                /* ours: the channel's week_gst, toes, toc_gst back to zero.  In stream order */
+/* Reads the rows and counts exactly as kg_nav_push_bits_dev / kg_nav_push_epochs_dev leave them (row ch at d_frames + ch *
+ * frame_stride, d_counts[ch] records, cut to 0 .. cap) and applies every applicable frame of every channel, in stream order, to the
+ * channel's satellite.  One kg_eph_note per frame read goes to row ch of d_notes (d_notes + ch * note_stride, 8-byte aligned,
+ * note_stride >= cap): exactly that many notes are written, nothing else, and the inputs are only read.  Page 18 of Navstar
+ * satellites sets the UTC fields, channels in ascending order.  Enqueue only. */
+int kg_eph_push_frames_dev(kg_eph *eph, const kg_nav_frame *d_frames, size_t frame_stride, const int32_t *d_counts, int cap,
+                           kg_eph_note *d_notes, size_t note_stride);
+int kg_eph_push_frames(kg_eph *eph, const kg_nav_frame *frames, size_t frame_stride, const int32_t *counts, int cap,
+                       kg_eph_note *notes, size_t note_stride);      /* the same on host memory; synchronises */
+int kg_eph_get(kg_eph *eph, int sat, kg_ephem *out);       /* synchronises */
+int kg_eph_get_chan(kg_eph *eph, int ch, int32_t *sat, uint32_t *gst3);     /* the bound satellite (-1: none); week_gst, toes, toc_gst.  Synchronises */
+int kg_eph_get_utc(kg_eph *eph, int32_t *utc3);            /* gps.delta_tLS, delta_tLSF, tLS_valid.  Synchronises */
+/* One kg_eph_pos per snapshot, in the order of LoadFromReplicas: the satellite not Valid (or sat outside 0 .. 63) -> flags =
+ * KG_EPH_SV_NOT_VALID; power < 1e5 or > 5e6 (as doubles) -> KG_EPH_SV_POWER; of either only `flags` is written.  Else GetClock with
+ * the MAX_TOW_DELAY substitution (KG_EPH_SV_TOW_DELAYED); a bad clock -- E1B only: ms not 0 or 4, chips outside 0 .. 4091 -- gives
+ * KG_EPH_SV_BAD and NaN in x, y, z, ct, t_k, as the reference lets NaN run through; t_tx -= GetClockCorrection; ct = C t_tx; t_k;
+ * KG_EPH_SV_TOO_OLD when |t_k| / 60 / 60 >= 4; GetXYZ; week.  d_snaps 4-byte, d_out 8-byte aligned.  Enqueue only. */
+int kg_eph_sv_dev(kg_eph *eph, const kg_eph_snap *d_snaps, int nsnap, kg_eph_pos *d_out);
+int kg_eph_sv(kg_eph *eph, const kg_eph_snap *snaps, int nsnap, kg_eph_pos *out);      /* the same on host memory; synchronises */
+/* chips and cg_phase of a snapshot from the 18-bit replica word of kg_trk_get_clocks, by LoadAtomic's masks (solve.cpp:77-79). */
+void kg_eph_replica(uint32_t word, int32_t *chips, int32_t *cg_phase);
 
 /* kg_fir_process_dev plus the extension taps of ProcessData (SURVEY.md 8(f) rank 4;
  * rx/CuteSDR/fastfir.cpp:278-302): for block b of list entry i, 1024 complex floats at
