@@ -20,16 +20,20 @@
 // pruning (the 5th integrator accumulates floor(I4 / 2^61)) makes the output depend
 // on the exact wrapped value of I4 at every ADC sample, so time cannot simply be
 // cut into independent pieces.  The stream is cut into runs of L samples:
-//   A  every run integrates from a zero state  -> local end state e_r (stored 4 x 128 bit)
-//   S  carry scan: c_{r+1} = T(L) c_r + e_r, where T(L) advances a state over L
-//      zero-input samples (binomial coefficients; validated in tools/ and the
-//      tests).  Chunks of runs per (channel, I/Q), one workgroup each: lane-local
-//      sequential compose, a 6-step wave scan with the affine combine, the wave and
-//      chunk totals folded in log steps, lane-local re-expansion.
-//   B  every run integrates again from its exact carried state, feeds the pruned
-//      5th integrator and records its value at every decimation strobe (relative
-//      to the run start) plus the run total
-//   S2 prefix sum of the run totals (mod 2^28)
+//   A  every run integrates from a zero state -> local end state e_r, advanced to the END
+//      of the channel's share of the block: T(len) advances a state over len zero-input
+//      samples (binomial coefficients; validated in tools/ and the tests)
+//   S  carry scan: end-referred, the states the runs start from are a plain prefix SUM
+//      of pass A's results (the argument is above sub96), taken in levels: over the 256
+//      runs of a workgroup inside pass A itself (ddc_wf_run_kernel), then by one wave per
+//      (channel, I/Q) over the at most 64 workgroup totals, which also adds the carried-in
+//      state and leaves the state after the block (ddc_wf_scan_wg_kernel)
+//   B  every run takes its exact start state back from the end, integrates again, feeds
+//      the pruned 5th integrator and records its value at every decimation strobe
+//      (relative to the run start) plus the run total
+//   S2 prefix sum of the run totals (mod 2^28) in the same levels: inside pass B's
+//      workgroups, then one wave over the workgroup totals (ddc_wf_tau_wg_kernel); the
+//      combs add the two levels
 //   C  per output: absolute I5, the five pruned combs (a 6-tap dependency on
 //      earlier outputs only, so fully parallel), rounding, int16 store.
 // Nothing above bit 88 of an integrator is ever read, so any modulus 2^k with k >= 89 keeps
@@ -123,7 +127,7 @@ DDC_DEV int mix24(int adc, int dds)
 // the 128 x 128-bit product took some forty-five instructions, and a state crosses lanes in 12 shuffles, not 32.
 struct u96 { u32 w[3]; };
 struct sc4 { u96 i[4]; };                     // integrators 1..4, mod 2^96
-struct sc_coef { u64 L, c2; u96 c3; };        // len, len (len+1) / 2 (exact: len < 2^32, asserted where the table is built), len (len+1) (len+2) / 6 mod 2^96
+struct sc_coef { u64 L, c2; u96 c3; };        // len, len (len+1) / 2 (exact: len < 2^32, asserted beside DDC_RUN_MAX), len (len+1) (len+2) / 6 mod 2^96
 DDC_DEV u96 u96_zero() { u96 r; r.w[0] = r.w[1] = r.w[2] = 0; return r; }
 DDC_DEV u96 u96_of(const u128 &v) { u96 r; r.w[0] = (u32) v.lo; r.w[1] = (u32) (v.lo >> 32); r.w[2] = (u32) v.hi; return r; }
 DDC_DEV u128 u128_of(const u96 &v) { return mk128((u64) v.w[0] | ((u64) v.w[1] << 32), (u64) v.w[2]); }
@@ -173,17 +177,6 @@ DDC_DEV sc4 sc_Tc(const sc_coef &k, const sc4 &s)
     return r;
 }
 DDC_DEV sc4 sc_T(u64 len, const sc4 &s) { return sc_Tc(sc_coef_for(len), s); }
-// The lengths the scan's log steps advance a state by are the same in every lane but a few: u << k (u = the samples
-// of a full lane's runs: steps of the wave scan, then of the fold over the wave totals) and v << m (v = a full
-// chunk).  Their coefficients come from the host in the kernel arguments (scalar registers); a lane whose length
-// is another one (the ragged end of the last chunk) computes its own -- the binomials are 40 % of an advance.
-#define DDC_SCAN_TAB 13
-struct sc_tab { u64 len[DDC_SCAN_TAB]; sc_coef c[DDC_SCAN_TAB]; };
-DDC_DEV sc4 sc_T_tab(const sc_tab &t, int j, u64 len, const sc4 &s)
-{
-    if (len == t.len[j]) return sc_Tc(t.c[j], s);
-    return sc_T(len, s);
-}
 DDC_DEV sc4 sc_add(const sc4 &a, const sc4 &b) { sc4 r; for (int k = 0; k < 4; k++) r.i[k] = add96(a.i[k], b.i[k]); return r; }
 DDC_DEV sc4 sc_shfl(const sc4 &s, int src)
 {
@@ -243,18 +236,25 @@ DDC_DEV sc4 sc_Tinv_c(u64 m, u64 c2, const u96 &c3, const sc4 &s)
 // once per (n, L) (ddc_endco_kernel; a steady stream of equal blocks builds it once); an entry with another share of the
 // block (a capture) computes its own.
 struct ddc_endco { u64 m, c2, c2i; u96 c3, c3i; u32 pad[2]; };        // T(m): m, c2, c3;  T(-m): -m, c2i, -c3i
-DDC_DEV ddc_state4 ddc_to_end(const ddc_state4 &e, u64 len, const ddc_endco *__restrict__ co)
+// Pass A: a run's result advanced over its distance `len` to the end (modulo 2^96, as the sums that follow)
+DDC_DEV sc4 ddc_to_end(const ddc_state4 &e, u64 len, const ddc_endco *__restrict__ co)
 {
     if (co) {
         sc_coef k; k.L = co->m; k.c2 = co->c2; k.c3 = co->c3;
-        return state_of(sc_Tc(k, sc_of(e)));
+        return sc_Tc(k, sc_of(e));
     }
-    return state_of(sc_T(len, sc_of(e)));
+    return sc_T(len, sc_of(e));
 }
-DDC_DEV ddc_state4 ddc_from_end(const ddc_state4 &e, u64 len, const ddc_endco *__restrict__ co)
+// Pass B: the state a run starts from = (the sum of its workgroup's runs before it + what the workgroup starts from), both
+// referred to the end, taken back over the run's distance `len` to the end.  (One function, 96 bits from the sum to the
+// inverse advance, and pass A's results likewise as sc4 up to the kernel's prefix sum: the same arithmetic written as
+// separate steps through the 128-bit stored form allocated 100 registers in pass B's narrow form and 131 in pass A's general
+// one, a wave per SIMD fewer each, though its live values never exceed 83 and 102 -- kernel-resource-usage remarks.)
+DDC_DEV ddc_state4 ddc_run_start(const ddc_state4 &before, const ddc_state4 &wg, u64 len, const ddc_endco *__restrict__ co)
 {
-    if (co) return state_of(sc_Tinv_c(co->m, co->c2i, co->c3i, sc_of(e)));
-    return state_of(sc_Tinv(len, sc_of(e)));
+    const sc4 s = sc_add(sc_of(before), sc_of(wg));
+    if (co) return state_of(sc_Tinv_c(co->m, co->c2i, co->c3i, s));
+    return state_of(sc_Tinv(len, s));
 }
 __global__ void ddc_endco_kernel(ddc_endco *__restrict__ tab, long n, int L, int nruns)
 {
@@ -279,9 +279,8 @@ template <int LOG> DDC_DEV void sc_scan_add(sc4 &e, int lane)
     }
 }
 
-DDC_DEV ddc_state4 ddc_add_state(const ddc_state4 &a, const ddc_state4 &b) { return state_of(sc_add(sc_of(a), sc_of(b))); }
-// Passes A and B.  grid = (ceil(nruns / 256), nchan).  The body of a thread's run; the kernel below adds pass A's
-// workgroup-level prefix sum of the end-referred results (endref == 2).
+// Passes A and B.  grid = (ceil(nruns / 256), nchan).  The body of a thread's run; the kernel below adds the
+// workgroup-level prefix sums of pass A's end-referred results and of pass B's integrator-5 totals.
 // MODE (round 5): which of the body's forms an instantiation carries.  The register budget of a kernel is that of its
 // widest form -- with everything in one function 119 / 124 registers, four waves per SIMD, for passes that stall on
 // table reads and dependent adds and gain from every further wave -- so the launches are split by what their entries need:
@@ -294,9 +293,8 @@ DDC_DEV void ddc_wf_run_body(
     const short *__restrict__ adc, long n, int L, int nruns,
     const ddc_chan *__restrict__ chans, const int *__restrict__ chan_list,
     const u32 *__restrict__ nco,              // the 16-bit table T[DDC_TAB] (kg_ddc_create), two entries per word
-    ddc_state4 *__restrict__ local,           // A: out [nlist][2][nruns];  B: in = carried states
+    ddc_state4 *__restrict__ local,           // B: in [nlist][2][nruns]: the end-referred sum of the workgroup's runs before this one
     u32 *__restrict__ c0rel,                  // B: relative I5 at strobes; entry li: I at c0off[li], Q right after
-    u32 *__restrict__ tau,                    // B: [nlist][2][nruns]
     const long *__restrict__ c0off, const long *__restrict__ nouts,
     const int *__restrict__ sel,              // list entries this launch covers (null: all, in order)
     int stage_bytes,                          // pass B, R <= 8: dynamic LDS for the strobe staging tiles, else 0
@@ -304,11 +302,11 @@ DDC_DEV void ddc_wf_run_body(
     const u64 *__restrict__ pdelta,           //   pushed + pdelta[li] (channels retuned or joined at different times differ in age)
     const long *__restrict__ nlim,            // [nlist] samples of the block this entry consumes (capture: 8192 R; else n)
     const int *__restrict__ reset_tab,        // [nlist] capture: the decimation counter starts the block at zero (rst_wf_samp_wr)
-    int endref,                               // states in `local` are referred to the END of the entry's share (sc_Tinv above)
     const ddc_endco *__restrict__ endco, long endco_n,    // [nruns + 1] coefficients of the distances n - k L for a share of endco_n samples
-    const ddc_state4 *__restrict__ wgbase,    // endref == 2, pass B: [nlist][2][gridDim.x] what the workgroup's first run adds to local[]
-    ddc_state4 &outI, ddc_state4 &outQ, bool &have,       // endref == 2, pass A: the run's end-referred result goes to the caller instead of local[]
-    u32 &outTi, u32 &outTq)                                // endref == 2, pass B: the run's integrator-5 totals likewise (instead of tau[])
+    const ddc_state4 *__restrict__ wgbase,    // B: in [nlist][2][gridDim.x] what the workgroup's first run adds to local[]: both are referred to
+                                              //    the END of the entry's share (sc_Tinv above)
+    sc4 &outI, sc4 &outQ, bool &have,         // A: the run's end-referred result, for the caller's prefix sum (have: this thread has a run)
+    u32 &outTi, u32 &outTq)                   // B: the run's integrator-5 totals likewise
 {
     __shared__ short tab[DDC_TAB];
     extern __shared__ u32 stage_lds[];        // [waves][2][64][DDC_STAGE_ROW] when stage_bytes != 0
@@ -322,7 +320,7 @@ DDC_DEV void ddc_wf_run_body(
     n = nlim[li];                             // this entry's share of the block (wave-uniform)
     if (r >= nruns || (long) r * L >= n) return;
     const long s0 = (long) r * L, s1 = (s0 + L < n) ? s0 + L : n;
-    const ddc_endco *co = (endref && n == endco_n) ? endco + (PASS_B ? r : r + 1) : nullptr;
+    const ddc_endco *co = n == endco_n ? endco + (PASS_B ? r : r + 1) : nullptr;
     const long wbI = ((long) li * 2 + 0) * gridDim.x + blockIdx.x, wbQ = ((long) li * 2 + 1) * gridDim.x + blockIdx.x;
     (void) wbI; (void) wbQ;
     // the 48-bit accumulator sits in the TOP bits of a 64-bit register: it wraps by itself (no mask per sample)
@@ -383,9 +381,8 @@ DDC_DEV void ddc_wf_run_body(
         const int sh5 = 5 * log2r - 4;                    // 61 - shift
         u64 I[4], Q[4];
         if (PASS_B) {
-            ddc_state4 a = local[lI], b = local[lQ];
-            if (endref == 2) { a = ddc_add_state(a, wgbase[wbI]); b = ddc_add_state(b, wgbase[wbQ]); }
-            if (endref) { a = ddc_from_end(a, (u64) (n - s0), co); b = ddc_from_end(b, (u64) (n - s0), co); }
+            const ddc_state4 a = ddc_run_start(local[lI], wgbase[wbI], (u64) (n - s0), co);
+            const ddc_state4 b = ddc_run_start(local[lQ], wgbase[wbQ], (u64) (n - s0), co);
             for (int k = 0; k < 4; k++) {
                 I[k] = (a.i[k].lo >> shift) | (a.i[k].hi << (64 - shift));
                 Q[k] = (b.i[k].lo >> shift) | (b.i[k].hi << (64 - shift));
@@ -554,8 +551,7 @@ DDC_DEV void ddc_wf_run_body(
         }
         for (; t < s1; t++) step(adc[t]);                 // ragged end of the block's last run
         if (PASS_B) {
-            if (endref == 2) { outTi = i5i & 0x0FFFFFFFu; outTq = i5q & 0x0FFFFFFFu; have = true; }
-            else { tau[lI] = i5i & 0x0FFFFFFFu; tau[lQ] = i5q & 0x0FFFFFFFu; }
+            outTi = i5i & 0x0FFFFFFFu; outTq = i5q & 0x0FFFFFFFu; have = true;
         } else {
             {   // the bias of pass A's inputs, out of the four integrators: 2^24 x C(len + k - 1, k), k = 1 .. 4, modulo 2^64
                 const u64 len = (u64) (s1 - s0);          // <= 8192: len (len+1) (len+2) (len+3) < 2^53
@@ -573,9 +569,7 @@ DDC_DEV void ddc_wf_run_body(
                 a.i[k] = mk128(I[k] << shift, hi_i);
                 b.i[k] = mk128(Q[k] << shift, hi_q);
             }
-            if (endref) { a = ddc_to_end(a, (u64) (n - s1), co); b = ddc_to_end(b, (u64) (n - s1), co); }
-            if (endref == 2) { outI = a; outQ = b; have = true; }
-            else { local[lI] = a; local[lQ] = b; }
+            outI = ddc_to_end(a, (u64) (n - s1), co); outQ = ddc_to_end(b, (u64) (n - s1), co); have = true;
         }
         return;
     }
@@ -596,9 +590,8 @@ DDC_DEV void ddc_wf_run_body(
         };
         u96 I[4], Q[4];
         {
-            ddc_state4 a = local[lI], b = local[lQ];
-            if (endref == 2) { a = ddc_add_state(a, wgbase[wbI]); b = ddc_add_state(b, wgbase[wbQ]); }
-            if (endref) { a = ddc_from_end(a, (u64) (n - s0), co); b = ddc_from_end(b, (u64) (n - s0), co); }
+            const ddc_state4 a = ddc_run_start(local[lI], wgbase[wbI], (u64) (n - s0), co);
+            const ddc_state4 b = ddc_run_start(local[lQ], wgbase[wbQ], (u64) (n - s0), co);
             for (int k = 0; k < 4; k++) {
                 I[k].w[0] = (u32) a.i[k].lo; I[k].w[1] = (u32) (a.i[k].lo >> 32); I[k].w[2] = (u32) a.i[k].hi;
                 Q[k].w[0] = (u32) b.i[k].lo; Q[k].w[1] = (u32) (b.i[k].lo >> 32); Q[k].w[2] = (u32) b.i[k].hi;
@@ -648,18 +641,15 @@ DDC_DEV void ddc_wf_run_body(
             for (int w = 0; w < 8; w++) step(buf[w]);
         }
         for (; t < s1; t++) step(adc[t]);
-        if (endref == 2) { outTi = i5i & 0x0FFFFFFFu; outTq = i5q & 0x0FFFFFFFu; have = true; }
-        else { tau[lI] = i5i & 0x0FFFFFFFu; tau[lQ] = i5q & 0x0FFFFFFFu; }
+        outTi = i5i & 0x0FFFFFFFu; outTq = i5q & 0x0FFFFFFFu; have = true;
         return;
     }
     if (MODE != DDC_ALL) return;
     // pass A of runs longer than 1024 samples at R >= 512: the zero-state sums need the full width
     ddc_state4 SI, SQ;
     if (PASS_B) {
-        SI = local[lI];
-        SQ = local[lQ];
-        if (endref == 2) { SI = ddc_add_state(SI, wgbase[wbI]); SQ = ddc_add_state(SQ, wgbase[wbQ]); }
-        if (endref) { SI = ddc_from_end(SI, (u64) (n - s0), co); SQ = ddc_from_end(SQ, (u64) (n - s0), co); }
+        SI = ddc_run_start(local[lI], wgbase[wbI], (u64) (n - s0), co);
+        SQ = ddc_run_start(local[lQ], wgbase[wbQ], (u64) (n - s0), co);
     } else {
         for (int k = 0; k < 4; k++) { SI.i[k] = mk128(0, 0); SQ.i[k] = mk128(0, 0); }
     }
@@ -691,16 +681,13 @@ DDC_DEV void ddc_wf_run_body(
     }
     for (; t < s1; t++) step(adc[t]);
     if (PASS_B) {
-        if (endref == 2) { outTi = i5i; outTq = i5q; have = true; }
-        else { tau[lI] = i5i; tau[lQ] = i5q; }
+        outTi = i5i; outTq = i5q; have = true;
     } else {
-        if (endref) { SI = ddc_to_end(SI, (u64) (n - s1), co); SQ = ddc_to_end(SQ, (u64) (n - s1), co); }
-        if (endref == 2) { outI = SI; outQ = SQ; have = true; }
-        else { local[lI] = SI; local[lQ] = SQ; }
+        outI = ddc_to_end(SI, (u64) (n - s1), co); outQ = ddc_to_end(SQ, (u64) (n - s1), co); have = true;
     }
 }
 
-// endref == 2 (round 4): the carry scan's first two levels ride on pass A.  A workgroup's 256 threads hold 256 consecutive runs of
+// Round 4: the carry scan's first two levels ride on pass A.  A workgroup's 256 threads hold 256 consecutive runs of
 // one channel: their end-referred results are prefix-summed right here (additions of 4 x 96 bits: a wave scan, the four wave
 // totals through LDS) -- local[r] = the sum of the workgroup's runs before r, wgtot = the workgroup's total -- and what is
 // left for a kernel of its own is the prefix over at most 64 workgroup totals per (channel, I/Q) (ddc_wf_scan_wg_kernel:
@@ -709,23 +696,26 @@ template <bool PASS_B, int MODE>
 __global__ __launch_bounds__(DDC_THREADS) void ddc_wf_run_kernel(
     const short *__restrict__ adc, long n, int L, int nruns,
     const ddc_chan *__restrict__ chans, const int *__restrict__ chan_list, const u32 *__restrict__ nco,
-    ddc_state4 *__restrict__ local, u32 *__restrict__ c0rel, u32 *__restrict__ tau,
+    ddc_state4 *__restrict__ local,           // [nlist][2][nruns]  A: out = the end-referred sum of the workgroup's runs before r;  B: in
+    u32 *__restrict__ c0rel,
+    u32 *__restrict__ tau,                    // [nlist][2][nruns]  B: out = the integrator-5 total of the workgroup's runs before r
     const long *__restrict__ c0off, const long *__restrict__ nouts, const int *__restrict__ sel, int stage_bytes,
-    u64 pushed, const u64 *__restrict__ pdelta, const long *__restrict__ nlim, const int *__restrict__ reset_tab, int endref,
+    u64 pushed, const u64 *__restrict__ pdelta, const long *__restrict__ nlim, const int *__restrict__ reset_tab,
     const ddc_endco *__restrict__ endco, long endco_n,
-    ddc_state4 *__restrict__ wgtot,           // pass A, endref == 2: [nlist][2][gridDim.x] out
-    const ddc_state4 *__restrict__ wgbase,    // pass B, endref == 2: [nlist][2][gridDim.x] in
-    u32 *__restrict__ wgtau)                  // pass B, endref == 2: [nlist][2][gridDim.x] out: the workgroup's integrator-5 total
+    ddc_state4 *__restrict__ wgtot,           // [nlist][2][gridDim.x]  A: out = the end-referred sum of the workgroup's runs (B: null)
+    const ddc_state4 *__restrict__ wgbase,    // [nlist][2][gridDim.x]  B: in = what ddc_wf_scan_wg_kernel made of wgtot: the carried-in state
+                                              //                        + the workgroups before this one, end-referred (A: null)
+    u32 *__restrict__ wgtau)                  // [nlist][2][gridDim.x]  B: out = the workgroup's integrator-5 total (A: null)
 {
-    ddc_state4 oI, oQ;
+    sc4 oI = sc_zero(), oQ = sc_zero();
     bool have = false;
     u32 oTi = 0, oTq = 0;
-    ddc_wf_run_body<PASS_B, MODE>(adc, n, L, nruns, chans, chan_list, nco, local, c0rel, tau, c0off, nouts, sel, stage_bytes, pushed,
-                            pdelta, nlim, reset_tab, endref, endco, endco_n, wgbase, oI, oQ, have, oTi, oTq);
-    if (PASS_B && endref == 2) {
+    ddc_wf_run_body<PASS_B, MODE>(adc, n, L, nruns, chans, chan_list, nco, local, c0rel, c0off, nouts, sel, stage_bytes, pushed,
+                            pdelta, nlim, reset_tab, endco, endco_n, wgbase, oI, oQ, have, oTi, oTq);
+    if (PASS_B) {
         // The prefix of the runs' integrator-5 totals in the same levels: tau[r] = the sum of the workgroup's runs before r,
         // wgtau = the workgroup's total; ddc_wf_tau_wg_kernel turns the totals into each workgroup's absolute start value and
-        // the combs add the two (ddc_wf_scan_tau_kernel was 16 us on the step's critical path, 100 in a busy GPU).
+        // the combs add the two (a prefix kernel over all runs was 16 us on the step's critical path, 100 in a busy GPU).
         __shared__ u32 s_t[2][DDC_THREADS / 64];
         const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
         const int li = sel ? sel[blockIdx.y] : (int) blockIdx.y;
@@ -750,12 +740,12 @@ __global__ __launch_bounds__(DDC_THREADS) void ddc_wf_run_kernel(
             wgtau[((long) li * 2 + 1) * gridDim.x + blockIdx.x] = (pq + vq) & 0x0FFFFFFFu;
         }
     }
-    if (!PASS_B && endref == 2) {
+    if (!PASS_B) {
         __shared__ sc4 s_w[2][DDC_THREADS / 64];
         const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
         const int li = sel ? sel[blockIdx.y] : (int) blockIdx.y;
         const long r = (long) blockIdx.x * DDC_THREADS + threadIdx.x;
-        sc4 iI = have ? sc_of(oI) : sc_zero(), iQ = have ? sc_of(oQ) : sc_zero();
+        sc4 iI = oI, iQ = oQ;
         sc_scan_add<6>(iI, lane);
         sc_scan_add<6>(iQ, lane);
         if (lane == 63) { s_w[0][wave] = iI; s_w[1][wave] = iQ; }
@@ -997,151 +987,6 @@ __global__ __launch_bounds__(256, 4) void ddc_wf_bypass_kernel(
     }
 }
 
-// Carry scan of the integrator states and prefix sum of the run totals.
-// One wave per (channel, I/Q).  MODE 0: states (after pass A), MODE 1: tau (after pass B).
-DDC_DEV u64 shfl_up64(u64 v, int d)
-{
-    const u32 lo = __shfl_up((u32) v, d), hi = __shfl_up((u32) (v >> 32), d);
-    return ((u64) hi << 32) | lo;
-}
-DDC_DEV u64 shfl64(u64 v, int src)
-{
-    const u32 lo = __shfl((u32) v, src), hi = __shfl((u32) (v >> 32), src);
-    return ((u64) hi << 32) | lo;
-}
-#define DDC_SCAN_WAVES 8
-#define DDC_SCAN_MAX_CHUNKS 16
-// Ordered fold of the affine maps held by lanes 0 .. 2^LOG - 1 (lane order = time order; a lane with
-// len = 0 and e = 0 is the identity): log steps of the inclusive scan instead of a serial chain of
-// wide multiply-adds.  -> the fold of lanes 0 .. lane (every lane of the group must call it)
-template <int LOG> DDC_DEV void ddc_fold_lanes(sc4 &e, u64 &len, int lane, const sc_tab &t, int j0)
-{
-#pragma unroll
-    for (int d = 1, j = j0; d < (1 << LOG); d <<= 1, j++) {
-        const sc4 a = sc_shfl_up(e, d);
-        const u64 alen = shfl_up64(len, d);
-        if (lane >= d) { e = sc_add(sc_T_tab(t, j, len, a), e); len += alen; }
-    }
-}
-// What a chunk of runs does to the integrator state: state_out = T(len) state_in + e.  Published by the
-// workgroup that owns the chunk for the workgroups of the later chunks of the same (channel, I/Q).
-struct ddc_chunk_agg { ddc_state4 e; u64 len; u32 epoch; u32 pad; };
-
-// Carry scan of the integrator states.  A (channel, I/Q) pair's runs are cut into `nchunk` chunks, one
-// workgroup of eight waves each: lane-local composition of a few runs, inclusive scan inside each wave,
-// the eight wave totals folded through LDS -> the chunk's aggregate, published in global memory; the
-// start state of the chunk = the saved state advanced through the aggregates of the chunks before it
-// (waited for one by one; every workgroup publishes before it waits, and workgroups take their chunk
-// numbers from a ticket counter in the order they start, so whoever is waited for is already running);
-// then every lane walks its runs again from its exact start state.  (One workgroup per pair took 120 us
-// for 16 384 runs -- 28 workgroups on 256 CUs, each lane composing 32 runs of 128-bit multiply-adds twice.)
-__global__ __launch_bounds__(64 * DDC_SCAN_WAVES) void ddc_wf_scan_states_kernel(
-    ddc_state4 *__restrict__ local, long n, int L, int nruns, ddc_chan *__restrict__ chans,
-    const int *__restrict__ chan_list, int npairs, int nchunk, ddc_chunk_agg *__restrict__ aggs,
-    u32 *__restrict__ ticket, u32 ticket_base, u32 epoch, const sc_tab tab,
-    const long *__restrict__ nlim, const int *__restrict__ reset_tab)      // per entry: samples consumed; capture: the carried-in state is zero
-{
-    __shared__ sc4 w_state[DDC_SCAN_WAVES];
-    __shared__ u64 w_len[DDC_SCAN_WAVES];
-    __shared__ sc4 s_start;
-    __shared__ u32 s_id;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, gl = threadIdx.x;
-    if (gl == 0) s_id = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - ticket_base;
-    __syncthreads();
-    // (through readfirstlane: the ticket is the same in every lane, and with it everything derived from the entry -- its
-    // share of the block, its run count, the chunk bounds -- stays in scalar registers)
-    const int id = __builtin_amdgcn_readfirstlane((int) s_id), g = id / npairs, pair = id - g * npairs;     // chunk-major: chunk 0 of every pair first
-    const int li = pair >> 1, comp = pair & 1;
-    ddc_chan *ch = chans + chan_list[li];
-    if (ch->log2r == 0) return;                   // (the whole pair: nobody waits for a bypass channel)
-    const int reset_first = reset_tab[li];
-    ddc_state4 *st = local + ((long) li * 2 + comp) * nruns;        // (rows of the whole launch's run count apart)
-    n = nlim[li];                                 // this entry's share of the block and the runs that hold it
-    { const int nr = (int) ((n + L - 1) >> (31 - __builtin_clz(L))); nruns = nr < nruns ? nr : nruns; }    // L is a power of two
-    ddc_chunk_agg *agg = aggs + (long) pair * DDC_SCAN_MAX_CHUNKS;
-    const int cper = (nruns + nchunk - 1) / nchunk;
-    const int c0 = g * cper < nruns ? g * cper : nruns, c1 = c0 + cper < nruns ? c0 + cper : nruns;
-    const int per = (c1 - c0 + 64 * DDC_SCAN_WAVES - 1) / (64 * DDC_SCAN_WAVES);
-    const int r0 = c0 + gl * per < c1 ? c0 + gl * per : c1, r1 = (r0 + per < c1) ? r0 + per : c1;
-    auto run_len = [&](int r) -> u64 { const long s0 = (long) r * L; return (u64) ((s0 + L < n ? s0 + L : n) - s0); };
-    // the saved state is read before anything is published: the last chunk rewrites it at the end, after
-    // it has seen every other chunk's aggregate
-    sc4 saved = sc_zero();
-    if (gl == 0 && !reset_first) saved = sc_of(ch->integ[comp]);
-    // 1. lane-local composition
-    sc4 acc = sc_zero(); u64 len = 0;
-    const sc_coef kL = sc_coef_for((u64) L);      // every run but possibly the last has length L
-    for (int r = r0; r < r1; r++) {
-        const u64 l = run_len(r);
-        acc = sc_add(l == (u64) L ? sc_Tc(kL, acc) : sc_T(l, acc), sc_of(st[r]));
-        len += l;
-    }
-    // 2. inclusive wave scan: earlier lanes first
-    sc4 inc = acc; u64 ilen = len;
-#pragma unroll
-    for (int d = 1, j = 0; d < 64; d <<= 1, j++) {
-        const sc4 a = sc_shfl_up(inc, d);
-        const u64 alen = shfl_up64(ilen, d);
-        if (lane >= d) { inc = sc_add(sc_T_tab(tab, j, ilen, a), inc); ilen += alen; }
-    }
-    if (lane == 63) { w_state[wave] = inc; w_len[wave] = ilen; }
-    __syncthreads();
-    // 3. wave 0: the inclusive prefixes of the eight wave totals (back into w_state / w_len: wave w starts behind
-    // prefix w - 1), the chunk's aggregate out, the aggregates of the earlier chunks in, folded in log steps
-    if (wave == 0) {
-        sc4 e = sc_zero(); u64 l = 0;
-        if (lane < DDC_SCAN_WAVES) { e = w_state[lane]; l = w_len[lane]; }
-        ddc_fold_lanes<3>(e, l, lane, tab, 6);
-        if (lane < DDC_SCAN_WAVES) { w_state[lane] = e; w_len[lane] = l; }
-        if (lane == DDC_SCAN_WAVES - 1 && g + 1 < nchunk) {
-            agg[g].e = state_of(e); agg[g].len = l;
-            __hip_atomic_store(&agg[g].epoch, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        // lanes past the earlier chunks carry a zero aggregate of a full chunk's length: nobody reads their fold, and
-        // with it every lane advances by the table's lengths
-        e = sc_zero();
-        l = tab.len[9];
-        if (lane < g) {
-            while (__hip_atomic_load(&agg[lane].epoch, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != epoch)
-                __builtin_amdgcn_s_sleep(2);
-            ddc_state4 ge;
-            for (int k = 0; k < 4; k++) {          // past the acquire: loads that do not come from a stale line
-                ge.i[k].lo = __hip_atomic_load(&agg[lane].e.i[k].lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                ge.i[k].hi = __hip_atomic_load(&agg[lane].e.i[k].hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            e = sc_of(ge);
-            l = __hip_atomic_load(&agg[lane].len, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        ddc_fold_lanes<4>(e, l, lane, tab, 9);     // DDC_SCAN_MAX_CHUNKS = 16 lanes; lane g - 1: chunks 0 .. g - 1
-        const int src = g > 0 ? g - 1 : 0;
-        e = sc_shfl(e, src); l = shfl64(l, src);
-        if (g == 0) { e = sc_zero(); l = 0; }
-        const sc4 sv = sc_shfl(saved, 0);
-        if (lane == 0) s_start = sc_add(sc_T(l, sv), e);
-    }
-    __syncthreads();
-    // state at the start of this wave's first run: the chunk's start advanced through the earlier waves
-    sc4 ws;
-    {
-        sc4 e = sc_zero(); u64 l = 0;
-        if (wave > 0) { e = w_state[wave - 1]; l = w_len[wave - 1]; }
-        ws = sc_add(sc_T(l, s_start), e);
-    }
-    // exclusive prefix of this lane inside its wave = inclusive of lane - 1
-    sc4 exc = sc_shfl_up(inc, 1); u64 elen = shfl_up64(ilen, 1);
-    if (lane == 0) { exc = sc_zero(); elen = 0; }
-    sc4 c = sc_add(sc_T(elen, ws), exc);
-    // 4. per-run carried states
-    for (int r = r0; r < r1; r++) {
-        const sc4 e = sc_of(st[r]);
-        st[r] = state_of(c);
-        const u64 l = run_len(r);
-        c = sc_add(l == (u64) L ? sc_Tc(kL, c) : sc_T(l, c), e);
-    }
-    // the lane that owns the last run holds the end state
-    if (r1 == nruns && r0 < nruns) ch->integ[comp] = state_of(c);
-}
-
 // ... and of the integrator-5 totals: in = the workgroups' totals, out = integrator 5 at each workgroup's first run.
 __global__ __launch_bounds__(64) void ddc_wf_tau_wg_kernel(u32 *__restrict__ wgtau, int gx, ddc_chan *__restrict__ chans,
                                                           const int *__restrict__ chan_list, const int *__restrict__ reset_tab)
@@ -1157,85 +1002,6 @@ __global__ __launch_bounds__(64) void ddc_wf_tau_wg_kernel(u32 *__restrict__ wgt
     if (lane == 0) x = 0;
     if (lane < gx) wgtau[(long) pair * gx + lane] = (i5 + x) & 0x0FFFFFFFu;
     if (lane == 63) ch->integ5[comp] = (i5 + v) & 0x0FFFFFFFu;       // the state after the call
-}
-
-// Prefix sum of the runs' integrator-5 totals: one workgroup of eight waves per (channel, I/Q).
-// Run r = k * 512 + thread: every load and store of a tile of 512 runs is contiguous across the workgroup
-// (round 2 gave each thread 32 consecutive runs: every access its own line, 28 us for a 16 384-entry prefix).
-// Per tile a wave scan (tile values stay in registers), the (tile, wave) totals -- at most 32 x 8 -- through LDS
-// and one more scan by the first four waves, then the offsets are applied.
-#define DDC_TAU_TILES 32                      // max_runs = 16384 = 32 tiles of 512
-__global__ __launch_bounds__(64 * DDC_SCAN_WAVES) void ddc_wf_scan_tau_kernel(
-    u32 *__restrict__ tau, int nruns, ddc_chan *__restrict__ chans, const int *__restrict__ chan_list,
-    const long *__restrict__ nlim, int L, const int *__restrict__ reset_tab)
-{
-    __shared__ u32 s_tot[DDC_TAU_TILES * DDC_SCAN_WAVES];       // totals, then exclusive offsets
-    __shared__ u32 s_w4[4];
-    const int li = blockIdx.x >> 1, comp = blockIdx.x & 1, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, gl = threadIdx.x;
-    ddc_chan *ch = chans + chan_list[li];
-    if (ch->log2r == 0) return;
-    const int reset_first = reset_tab[li];
-    u32 *tv = tau + ((long) li * 2 + comp) * nruns;
-    {   // the runs this entry walked (li comes from blockIdx: a scalar load, a scalar ntile)
-        const int nr = (int) ((nlim[li] + L - 1) >> (31 - __builtin_clz(L)));       // L is a power of two
-        nruns = nr < nruns ? nr : nruns;
-    }
-    const int ntile = (nruns + 511) >> 9;         // <= DDC_TAU_TILES (kg_ddc_create caps max_runs at 16384)
-    u32 inc[DDC_TAU_TILES], own[DDC_TAU_TILES];
-#pragma unroll
-    for (int k = 0; k < DDC_TAU_TILES; k++) {
-        const int r = (k << 9) + gl;
-        own[k] = (k < ntile && r < nruns) ? tv[r] : 0u;
-    }
-    // eight tiles at a time behind ONE scalar branch (ntile is wave-uniform): a capture's short entries skip the groups of
-    // tiles they lack, and inside a group the eight scans stay independent straight-line chains (a branch per tile made
-    // the continuous case -- all 32 tiles -- 13 -> 20 us: the chains then ran one after the other)
-#pragma unroll
-    for (int g8 = 0; g8 < DDC_TAU_TILES; g8 += 8) {
-        if (g8 < ntile) {
-#pragma unroll
-            for (int k = g8; k < g8 + 8; k++) {
-                u32 v = own[k];                       // (zero past ntile: loaded so above)
-                for (int d = 1; d < 64; d <<= 1) { const u32 a = __shfl_up(v, d); if (lane >= d) v += a; }
-                inc[k] = v;
-                if (lane == 63) s_tot[k * DDC_SCAN_WAVES + wave] = v;
-            }
-        } else {
-#pragma unroll
-            for (int k = g8; k < g8 + 8; k++) {
-                inc[k] = 0;
-                if (lane == 63) s_tot[k * DDC_SCAN_WAVES + wave] = 0;
-            }
-        }
-    }
-    __syncthreads();
-    // exclusive prefix over the 256 (tile, wave) totals, in time order: waves 0..3, one total per lane
-    u32 t = 0, tinc = 0;
-    if (gl < 256) {
-        t = s_tot[gl];
-        tinc = t;
-        for (int d = 1; d < 64; d <<= 1) { const u32 a = __shfl_up(tinc, d); if (lane >= d) tinc += a; }
-        if (lane == 63) s_w4[wave] = tinc;
-    }
-    __syncthreads();
-    if (gl < 256) {
-        u32 base = 0;
-        for (int w = 0; w < wave; w++) base += s_w4[w];
-        s_tot[gl] = base + tinc - t;              // exclusive
-    }
-    const u32 i5 = reset_first ? 0u : ch->integ5[comp];
-    __syncthreads();                              // offsets written; every wave has read the saved value
-#pragma unroll
-    for (int k = 0; k < DDC_TAU_TILES; k++) {
-        const int r = (k << 9) + gl;
-        if (k < ntile && r < nruns)
-            tv[r] = (i5 + s_tot[k * DDC_SCAN_WAVES + wave] + inc[k] - own[k]) & 0x0FFFFFFFu;     // I5 at the run's start
-    }
-    if (gl == 0) {                                // the sum of every run = state after the call
-        u32 total = i5;
-        for (int w = 0; w < 4; w++) total += s_w4[w];
-        ch->integ5[comp] = total & 0x0FFFFFFFu;
-    }
 }
 
 // sign-extend the low `bits` bits
@@ -1258,7 +1024,7 @@ __global__ __launch_bounds__(256) void ddc_wf_comb_kernel(
     const int *__restrict__ wg_start, int nlist,
     short2 *__restrict__ out, long out_stride, const long *__restrict__ out_off,   // entry li writes at out + li out_stride + out_off[li]
     u32 *__restrict__ hist_out,               // [nlist][2][5]
-    const u32 *__restrict__ wgtau, int gx,    // end-referred levels: i5start[] is relative to its run pass workgroup's start value wgtau[li][comp][run / 256]; or null
+    const u32 *__restrict__ wgtau, int gx,    // end-referred levels: i5start[] is relative to its run pass workgroup's start value wgtau[li][comp][run / 256]
     int by_chan)                              // rows of `out` by channel number (kg_ctx::rows_by_chan)
 {
     __shared__ __attribute__((aligned(16))) int s_c0[2][DDC_COMB_TILE + 8];       // [d]: output o0 - 8 + d (three unused slots keep 16-byte rows)
@@ -1274,7 +1040,7 @@ __global__ __launch_bounds__(256) void ddc_wf_comb_kernel(
     auto absolute = [&](int comp, long oo, u32 rel) -> u32 {
         const long g = ((oo + 1) << log2r) - 1 - (long) base;    // sample index of the strobe
         const int run = (int) (g >> log2L);
-        const u32 wb = wgtau ? wgtau[((long) li * 2 + comp) * gx + (run >> 8)] : 0u;
+        const u32 wb = wgtau[((long) li * 2 + comp) * gx + (run >> 8)];
         return (rel + i5start[((long) li * 2 + comp) * nruns + run] + wb) & 0x0FFFFFFFu;
     };
 #pragma unroll
@@ -1383,7 +1149,6 @@ struct kg_ddc {
     // turn, so that push k + 1's run passes may overwrite nothing push k's output stage still reads (deferred mode).
     ddc_state4 *d_local[2]; u32 *d_c0rel[2], *d_tau[2], *d_hist;
     int max_runs; long c0_cap[2];
-    ddc_chunk_agg *d_aggs; u32 *d_ticket; u32 ticket_base, epoch;     // chunked state scan
     hipStream_t side; hipEvent_t ev_fork, ev_join;                   // pass B of the small decimations beside the rest
     bool side_borrowed;                                              // `side` is the owner's (a receiver bank's): not destroyed here
     kg_stage_cache pack_cache;                 // the per-call tables of the last push (a steady stream repeats them: no upload)
@@ -1409,6 +1174,9 @@ static const int DDC_RUN_MIN = 64, DDC_RUN_MAX = 8192, DDC_TARGET_RUNS = 8192;
 static const int DDC_MAX_GX = DDC_TARGET_RUNS * 2 / DDC_THREADS;      // workgroups of a run pass per channel: one lane each in ddc_wf_scan_wg_kernel
 static_assert(DDC_MAX_GX <= 64, "ddc_wf_scan_wg_kernel scans one workgroup total per lane");
 static_assert(DDC_THREADS == 256, "ddc_wf_comb_kernel finds a run's pass-B workgroup as run >> 8");
+// The distances the end-referred states are advanced by are at most one push's share of samples, max_runs x DDC_RUN_MAX.
+static_assert((unsigned long long) DDC_TARGET_RUNS * 2 * DDC_RUN_MAX < (1ull << 32),
+              "sc_coef.c2 and sc_Tinv's c2 are 64 bits wide: an advance of 2^32 samples or more needs a u96 there");
 
 // The object's second stream, handed over by an owner that lays out its streams itself (kg_rxbank.hip: which hardware queue
 // a stream lands on follows from the order streams are created in).  Before the first push.  Not part of the ABI.
@@ -1461,11 +1229,6 @@ int kg_ddc_create(kg_ctx *ctx, int nchan, size_t max_samples, kg_ddc **out)
         KG_HIP(hipMalloc((void **) &d->d_wgtau[p], sizeof(u32) * 2 * (size_t) nchan * DDC_MAX_GX));
     }
     d->endco_n = -1; d->endco_L = 0; d->endco_runs = 0;
-    KG_HIP(hipMalloc((void **) &d->d_aggs, sizeof(ddc_chunk_agg) * 2 * (size_t) nchan * DDC_SCAN_MAX_CHUNKS));
-    KG_HIP(hipMemset(d->d_aggs, 0, sizeof(ddc_chunk_agg) * 2 * (size_t) nchan * DDC_SCAN_MAX_CHUNKS));
-    KG_HIP(hipMalloc((void **) &d->d_ticket, sizeof(u32)));
-    KG_HIP(hipMemset(d->d_ticket, 0, sizeof(u32)));
-    d->ticket_base = 0; d->epoch = 0;
     // NCO table: ONE 16-bit sine table, sin(a) = T[a], cos(a) = T[a + 2048] (kg_common.h, kg_nco_table_build)
     std::vector<short> tab(DDC_TAB);
     kg_nco_table_build(tab.data());
@@ -1484,7 +1247,7 @@ void kg_ddc_destroy(kg_ddc *d)
     (void) hipFree(d->d_chans); (void) hipFree(d->d_nco);
     for (int p = 0; p < 2; p++) { (void) hipFree(d->d_local[p]); (void) hipFree(d->d_tau[p]); (void) hipFree(d->d_c0rel[p]); }
     (void) hipFree(d->d_hist);
-    (void) hipFree(d->d_aggs); (void) hipFree(d->d_ticket); (void) hipFree(d->d_endco);
+    (void) hipFree(d->d_endco);
     for (int p = 0; p < 2; p++) { (void) hipFree(d->d_wgtot[p]); (void) hipFree(d->d_wgbase[p]); (void) hipFree(d->d_wgtau[p]); }
     kg_stage_cache_free(&d->pack_cache);
     if (d->side) { (void) hipEventDestroy(d->ev_fork); (void) hipEventDestroy(d->ev_join); if (!d->side_borrowed) kg_stream_put(d->ctx->device, d->side); }
@@ -1874,11 +1637,9 @@ static int ddc_push_impl(kg_ddc *d, const void *d_adc, size_t n, const int32_t *
         KG_HIP(hipGetLastError());
         if (defer) KG_HIP(hipEventRecord(d->ev_adc, bst));           // the output stream's only reader of d_adc
     }
-    // end-referred carry states (round 4): prefix sums inside pass A's workgroups + one wave per (channel, I/Q) over the
-    // workgroup totals; KIWIGPU_DDC_ENDREF=0: run-start states and the chunked affine scan -- the A/B reference
-    int endref = 2;
-    if (const char *e = kg_tuning_env("KIWIGPU_DDC_ENDREF")) endref = atoi(e) != 0 ? 2 : 0;
-    if (endref && !h_run.empty() && (d->endco_n != n_cover || d->endco_L != L || d->endco_runs != nruns)) {
+    // end-referred carry states (round 4): the coefficients of the runs' distances to the end, then prefix sums inside
+    // pass A's workgroups + one wave per (channel, I/Q) over the workgroup totals
+    if (!h_run.empty() && (d->endco_n != n_cover || d->endco_L != L || d->endco_runs != nruns)) {
         // (a changed block length: rare.  The previous push's pass B may still be reading the old table on the object's
         // second stream)
         if ((rc = ddc_sync_all(d))) return rc;
@@ -1893,56 +1654,13 @@ static int ddc_push_impl(kg_ddc *d, const void *d_adc, size_t n, const int32_t *
         hipLaunchKernelGGL(pass_a, dim3(gx, (unsigned) h_run.size()), dim3(DDC_THREADS), 0, st,
                            (const short *) d_adc, (long) n, L, nruns, (const ddc_chan *) d->d_chans, s_list,
                            (const u32 *) d->d_nco, d_local, d_c0rel, d_tau, s_c0off,
-                           s_nouts, s_selrun, 0, pushed, s_pdelta, s_nlim, s_reset, endref, (const ddc_endco *) d->d_endco, d->endco_n,
+                           s_nouts, s_selrun, 0, pushed, s_pdelta, s_nlim, s_reset, (const ddc_endco *) d->d_endco, d->endco_n,
                            d->d_wgtot[par], (const ddc_state4 *) nullptr, (u32 *) nullptr);
         KG_HIP(hipGetLastError());
     }
-    {
-        // chunks per (channel, I/Q): as many as keep every chunk at least a workgroup's worth of runs and
-        // the whole grid resident at once
-        const int npairs = 2 * nlist;
-        int nchunk = (d->ctx->num_cus * 2) / npairs;
-        if (nchunk > DDC_SCAN_MAX_CHUNKS) nchunk = DDC_SCAN_MAX_CHUNKS;
-        while (nchunk > 1 && nruns / nchunk < 64 * DDC_SCAN_WAVES) nchunk--;
-        if (nchunk < 1) nchunk = 1;
-        // the advance coefficients of the scan's regular steps (sc_tab): a full lane's samples u << 0 .. 8, a full
-        // chunk's v << 0 .. 3
-        sc_tab tab;
-        {
-            const long cper = (nruns + nchunk - 1) / nchunk, per = (cper + 64 * DDC_SCAN_WAVES - 1) / (64 * DDC_SCAN_WAVES);
-            const u64 u = (u64) per * (u64) L, v = (u64) cper * (u64) L;
-            for (int j = 0; j < DDC_SCAN_TAB; j++) {
-                const u64 len = j < 9 ? u << j : v << (j - 9);
-                const unsigned __int128 l = len;
-                // sc_coef keeps c2 = len (len + 1) / 2 in 64 bits (host table and sc_coef_for alike): exact while len < 2^32.
-                // The longest advance is v << 3 <= 8 (n + nchunk L) with n <= max_runs x DDC_RUN_MAX = 2^27 samples per push.
-                static_assert((unsigned long long) DDC_TARGET_RUNS * 2 * DDC_RUN_MAX * 16 <= (1ull << 32),
-                              "sc_coef.c2 is 64 bits wide: an advance of 2^32 samples or more needs a u96 there");
-                KG_REQUIRE(len < (1ull << 32), KG_ERR_INVALID, "kg_ddc_wf_push_dev: scan advance %llu too long for the 64-bit c2",
-                           (unsigned long long) len);
-                const unsigned __int128 c2 = l * (l + 1) / 2;                     // len < 2^32: below 2^63
-                // len (len + 1) (len + 2) / 6 mod 2^96: c2 (len + 2) is 3 x the binomial; divide the exact product
-                // (below 2^111) by 3
-                const unsigned __int128 c3 = c2 * (l + 2) / 3;
-                tab.len[j] = len;
-                tab.c[j].L = len; tab.c[j].c2 = (u64) c2;
-                tab.c[j].c3.w[0] = (u32) c3; tab.c[j].c3.w[1] = (u32) (c3 >> 32); tab.c[j].c3.w[2] = (u32) (c3 >> 64);
-            }
-        }
-        if (endref == 2)
-            hipLaunchKernelGGL(ddc_wf_scan_wg_kernel, dim3((unsigned) npairs), dim3(64), 0, st, (const ddc_state4 *) d->d_wgtot[par],
-                               d->d_wgbase[par], (int) gx, d->d_chans, s_list, s_nlim, s_reset);
-        else
-            hipLaunchKernelGGL(ddc_wf_scan_states_kernel, dim3((unsigned) (npairs * nchunk)), dim3(64 * DDC_SCAN_WAVES), 0, st,
-                               d_local, (long) n, L, nruns, d->d_chans, s_list, npairs, nchunk, d->d_aggs, d->d_ticket,
-                               d->ticket_base, d->epoch + 1, tab, s_nlim, s_reset);
-        KG_HIP(hipGetLastError());
-        // only a launch that was accepted advances the ticket counter and publishes under the new epoch
-        if (endref != 2) {
-            d->epoch++;
-            d->ticket_base += (u32) (npairs * nchunk);
-        }
-    }
+    hipLaunchKernelGGL(ddc_wf_scan_wg_kernel, dim3((unsigned) (2 * nlist)), dim3(64), 0, st, (const ddc_state4 *) d->d_wgtot[par],
+                       d->d_wgbase[par], (int) gx, d->d_chans, s_list, s_nlim, s_reset);
+    KG_HIP(hipGetLastError());
     // Pass B.  The staged strobe flush (R <= 8) needs 34 KiB more LDS, hence its own launch.  Neither
     // launch fills the GPU by itself (a lane walks a whole run: 64 workgroups per channel), so when both
     // kinds of channel are present the staged launch runs beside the other one on a second stream of the
@@ -1956,7 +1674,7 @@ static int ddc_push_impl(kg_ddc *d, const void *d_adc, size_t n, const int32_t *
         auto k = mode == DDC_NARROW ? ddc_wf_run_kernel<true, DDC_NARROW> : (mode == DDC_WIDE ? ddc_wf_run_kernel<true, DDC_WIDE> : ddc_wf_run_kernel<true, DDC_ALL>);
         hipLaunchKernelGGL(k, dim3(gx, (unsigned) nwhich), dim3(DDC_THREADS), stage, s,
                            (const short *) d_adc, (long) n, L, nruns, (const ddc_chan *) d->d_chans, s_list,
-                           (const u32 *) d->d_nco, d_local, d_c0rel, d_tau, s_c0off, s_nouts, sel, stage, pushed, s_pdelta, s_nlim, s_reset, endref, (const ddc_endco *) d->d_endco, d->endco_n,
+                           (const u32 *) d->d_nco, d_local, d_c0rel, d_tau, s_c0off, s_nouts, sel, stage, pushed, s_pdelta, s_nlim, s_reset, (const ddc_endco *) d->d_endco, d->endco_n,
                            (ddc_state4 *) nullptr, (const ddc_state4 *) d->d_wgbase[par], d->d_wgtau[par]);
     };
     // The entries above R = 8 by the form they need (DDC_NARROW / DDC_WIDE: fewer registers, more waves per SIMD) -- as two
@@ -2003,19 +1721,15 @@ static int ddc_push_impl(kg_ddc *d, const void *d_adc, size_t n, const int32_t *
         KG_HIP(hipEventRecord(d->ev_join, d->side));
         KG_HIP(hipStreamWaitEvent(ost, d->ev_join, 0));
     }
-    if (endref == 2)
-        hipLaunchKernelGGL(ddc_wf_tau_wg_kernel, dim3(2 * nlist), dim3(64), 0, ost, d->d_wgtau[par], (int) gx, d->d_chans, s_list,
-                           s_reset);
-    else
-        hipLaunchKernelGGL(ddc_wf_scan_tau_kernel, dim3(2 * nlist), dim3(64 * DDC_SCAN_WAVES), 0, ost, d_tau, nruns, d->d_chans,
-                           s_list, s_nlim, L, s_reset);
+    hipLaunchKernelGGL(ddc_wf_tau_wg_kernel, dim3(2 * nlist), dim3(64), 0, ost, d->d_wgtau[par], (int) gx, d->d_chans, s_list,
+                       s_reset);
     KG_HIP(hipGetLastError());
     if (comb_wgs > 0) {
         hipLaunchKernelGGL(ddc_wf_comb_kernel, dim3((unsigned) comb_wgs), dim3(256), 0, ost,
                            (const u32 *) d_c0rel, (const u32 *) d_tau, log2L, nruns, s_c0off,
                            (const ddc_chan *) d->d_chans, s_list, s_nouts,
                            pushed, s_pdelta, s_reset, s_wgoff, nlist, (short2 *) d_out, (long) out_stride, s_outoff,
-                           d->d_hist, endref == 2 ? (const u32 *) d->d_wgtau[par] : (const u32 *) nullptr, (int) gx, d->ctx->rows_by_chan);
+                           d->d_hist, (const u32 *) d->d_wgtau[par], (int) gx, d->ctx->rows_by_chan);
         KG_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(ddc_wf_finish_kernel, dim3((nlist + 63) / 64), dim3(64), 0, ost, d->d_chans,

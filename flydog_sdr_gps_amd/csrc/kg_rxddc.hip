@@ -19,12 +19,14 @@
 // Parallelisation: the rx1 integrators run at the ADC rate and its third one is
 // pruned (it accumulates integrator2[54 -: 26]), so -- as in kg_ddc.hip -- the
 // stream is cut into runs, run-local states are combined by an exact carry scan
-// (c1' = c1 + e1, c2' = c2 + L*c1 + e2, modulo 2^64 which keeps the low 55 bits
-// exact), the runs are integrated again from their exact states, and a prefix sum
-// of run totals gives the pruned integrator.  Everything after rx1 runs at 72 kHz
-// and is unpruned linear arithmetic in wrapping registers, i.e. exactly an FIR:
-// rx2 is the 11-tap (1 + z + z^2)^5 at stride 3 modulo 2^26, fir_iq the 65-tap
-// filter at stride 2 modulo 2^42 -- computed directly per output sample.
+// (advancing a state over len samples is c1, c2 + len*c1, modulo 2^64 which keeps
+// the low 55 bits exact; referred to the block's end the scan is a plain prefix
+// sum, taken in levels as there), the runs are integrated again from their exact
+// states, and a prefix sum of run totals gives the pruned integrator.  Everything
+// after rx1 runs at 72 kHz and is unpruned linear arithmetic in wrapping registers,
+// i.e. exactly an FIR: rx2 is the 11-tap (1 + z + z^2)^5 at stride 3 modulo 2^26,
+// fir_iq the 65-tap filter at stride 2 modulo 2^42 -- computed directly per output
+// sample.
 #include "kg_common.h"
 
 #include <math.h>
@@ -108,11 +110,11 @@ template <bool PASS_B>
 __global__ __launch_bounds__(RX_THREADS) void rx1_run_kernel(
     const short *__restrict__ adc, long n, int L, int nruns, const rx_chan *__restrict__ chans,
     const int *__restrict__ chan_list, const u32 *__restrict__ nco,
-    u64 *__restrict__ st,                     // [nlist][2 comp][2 integ][nruns]: A out, B in (carried)
+    u64 *__restrict__ st,                     // [nlist][2 comp][2 integ][nruns]: A out, B in: states referred to the END of the block,
+                                              // summed in levels (round 4, below): the sum of the workgroup's runs before r
     u32 *__restrict__ c0rel, u32 *__restrict__ tau, long max_out, rx_mode md,
-    int endref,                               // round 4: states referred to the END of the block, summed in levels (below)
-    u64 *__restrict__ wg,                     // endref: [nlist][4][gridDim.x]: A out = the workgroup's totals, B in = what its first run adds
-    u32 *__restrict__ wgt)                    // endref, pass B: [nlist][2][gridDim.x] out: the workgroup's integrator-3 total
+    u64 *__restrict__ wg,                     // [nlist][4][gridDim.x]: A out = the workgroup's totals, B in = what its first run adds
+    u32 *__restrict__ wgt)                    // pass B: [nlist][2][gridDim.x] out: the workgroup's integrator-3 total
 {
     const u32 RX_R1 = (u32) md.r1;
     const int SH3 = md.sh3;
@@ -122,8 +124,7 @@ __global__ __launch_bounds__(RX_THREADS) void rx1_run_kernel(
     const int li = blockIdx.y;
     const rx_chan ch = chans[chan_list[li]];
     const int r = blockIdx.x * RX_THREADS + threadIdx.x;
-    const bool active = r < nruns;
-    if (!active && !endref) return;               // (the workgroup-level sums of both passes need every thread at their barrier)
+    const bool active = r < nruns;                // (no early return: the workgroup-level sums of both passes need every thread at their barrier)
     const long s0 = active ? (long) r * L : n, s1 = (s0 + L < n) ? s0 + L : n;
     // the 48-bit accumulator sits in the TOP bits of a 64-bit register: it wraps by itself (no mask per sample)
     u64 ph = (ch.phase + (u64) s0 * ch.phase_inc) << 16;
@@ -132,15 +133,13 @@ __global__ __launch_bounds__(RX_THREADS) void rx1_run_kernel(
     u64 *base = st + (long) li * 4 * nruns;
     if (PASS_B && active) {
         a1i = base[0 * nruns + r]; a2i = base[1 * nruns + r]; a1q = base[2 * nruns + r]; a2q = base[3 * nruns + r];
-        if (endref) {
-            // End-referred (kg_ddc.hip, sc_Tinv): what is stored is the sum over the earlier runs of their results advanced
-            // to the block's end -- T(len): c1, c2 + len c1 -- plus the carried-in state advanced likewise; the state this run
-            // starts from is that sum taken back by its distance to the end.
-            const u64 *wb = wg + (long) li * 4 * gridDim.x + blockIdx.x;
-            a1i += wb[0 * gridDim.x]; a2i += wb[1 * gridDim.x]; a1q += wb[2 * gridDim.x]; a2q += wb[3 * gridDim.x];
-            const u64 back = (u64) (n - s0);
-            a2i -= back * a1i; a2q -= back * a1q;
-        }
+        // End-referred (kg_ddc.hip, sc_Tinv): what is stored is the sum over the earlier runs of their results advanced
+        // to the block's end -- T(len): c1, c2 + len c1 -- plus the carried-in state advanced likewise; the state this run
+        // starts from is that sum taken back by its distance to the end.
+        const u64 *wb = wg + (long) li * 4 * gridDim.x + blockIdx.x;
+        a1i += wb[0 * gridDim.x]; a2i += wb[1 * gridDim.x]; a1q += wb[2 * gridDim.x]; a2q += wb[3 * gridDim.x];
+        const u64 back = (u64) (n - s0);
+        a2i -= back * a1i; a2q -= back * a1q;
     }
     u32 i3i = 0, i3q = 0;
     const u64 c0 = (u64) ch.cnt1 + (u64) s0;
@@ -183,11 +182,6 @@ __global__ __launch_bounds__(RX_THREADS) void rx1_run_kernel(
     }
     for (; t < s1; t++) step(adc[t]);
     if (PASS_B) {
-        if (!endref) {
-            tau[((long) li * 2 + 0) * nruns + r] = i3i & 0x03FFFFFFu;
-            tau[((long) li * 2 + 1) * nruns + r] = i3q & 0x03FFFFFFu;
-            return;
-        }
         // the prefix of the runs' integrator-3 totals in the same levels as the carry states: tau[r] = the sum of the
         // workgroup's runs before r, wgt = the workgroup's total (rx1_tau_wg_kernel: its start value; rx1_comb_kernel adds both)
         __shared__ u32 s_t[2][RX_THREADS / 64];
@@ -216,14 +210,10 @@ __global__ __launch_bounds__(RX_THREADS) void rx1_run_kernel(
             const u64 len = (u64) (s1 - s0), b1 = len << 22, b2 = (len * (len + 1) / 2) << 22;
             a1i -= b1; a2i -= b2; a1q -= b1; a2q -= b2;
         }
-        if (!endref) {
-            base[0 * nruns + r] = a1i; base[1 * nruns + r] = a2i; base[2 * nruns + r] = a1q; base[3 * nruns + r] = a2q;
-            return;
-        }
         // Round 4: the carry scan's first two levels ride on pass A (as in kg_ddc.hip).  The run's result advanced to the end of
         // the block, then prefix sums -- plain additions modulo 2^64 -- over the workgroup's 256 consecutive runs: st[r] = the
         // sum of the workgroup's runs before r, wg = the workgroup's total; rx1_scan_wg_kernel does the third level (one
-        // wave per (channel, I/Q) over at most 64 totals) where rx1_scan_kernel was 52 us between the passes.
+        // wave per (channel, I/Q) over at most 64 totals) where a scan kernel over all runs was 52 us between the passes.
         {
             const u64 fwd = (u64) (n - s1);
             a2i += fwd * a1i; a2q += fwd * a1q;
@@ -250,78 +240,6 @@ __global__ __launch_bounds__(RX_THREADS) void rx1_run_kernel(
     }
 }
 
-// carry scan of (i1, i2) per (channel, comp): one wave each
-#define RX_SCAN_WAVES 8
-#define RX_SCAN_PER 16                        // runs per lane held in registers (8192 runs per channel)
-// Carry scan of the two exact integrators over the runs: one workgroup of eight waves per (channel, I/Q)
-// (one wave took 171 us for 128 receivers x 16 384 runs: 256 sequential, uncoalesced steps per lane, twice).
-__global__ __launch_bounds__(64 * RX_SCAN_WAVES) void rx1_scan_kernel(u64 *__restrict__ st, long n, int L, int nruns,
-                                                                     rx_chan *__restrict__ chans, const int *__restrict__ chan_list)
-{
-    __shared__ u64 w1[RX_SCAN_WAVES], w2[RX_SCAN_WAVES], wl[RX_SCAN_WAVES];
-    const int li = blockIdx.x >> 1, comp = blockIdx.x & 1, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, gl = threadIdx.x;
-    rx_chan *ch = chans + chan_list[li];
-    u64 *e1 = st + ((long) li * 4 + 2 * comp) * nruns, *e2 = e1 + nruns;
-    const int per = (nruns + 64 * RX_SCAN_WAVES - 1) / (64 * RX_SCAN_WAVES);
-    const int r0 = gl * per < nruns ? gl * per : nruns, r1 = (r0 + per < nruns) ? r0 + per : nruns;
-    auto run_len = [&](int r) -> u64 { const long s0 = (long) r * L; return (u64) ((s0 + L < n ? s0 + L : n) - s0); };
-    // A lane's runs are consecutive (their order is the composition's), so its loads are its own lines: with up to
-    // RX_SCAN_PER runs per lane they all go out at once into registers and both walks read those (the loop that
-    // loaded a run, waited, composed, and loaded the same runs again for the second walk took 168 us of 16 + 16
-    // dependent round trips for 128 receivers beside the waterfall's pass A).
-    const bool regs = per <= RX_SCAN_PER;
-    u64 f1[RX_SCAN_PER], f2[RX_SCAN_PER];
-    if (regs) {
-#pragma unroll
-        for (int k = 0; k < RX_SCAN_PER; k++) {
-            const int r = r0 + k;
-            f1[k] = r < r1 ? e1[r] : 0ull;
-            f2[k] = r < r1 ? e2[r] : 0ull;
-        }
-    }
-    u64 a1 = 0, a2 = 0, len = 0;
-    if (regs) {
-#pragma unroll
-        for (int k = 0; k < RX_SCAN_PER; k++) {
-            if (r0 + k < r1) { const u64 l = run_len(r0 + k); a2 = a2 + l * a1 + f2[k]; a1 = a1 + f1[k]; len += l; }
-        }
-    } else {
-        for (int r = r0; r < r1; r++) { const u64 l = run_len(r); a2 = a2 + l * a1 + e2[r]; a1 = a1 + e1[r]; len += l; }
-    }
-    u64 i1 = a1, i2 = a2, ilen = len;
-    for (int d = 1; d < 64; d <<= 1) {
-        const u64 p1 = rx_shfl_up64(i1, d), p2 = rx_shfl_up64(i2, d), pl = rx_shfl_up64(ilen, d);
-        if (lane >= d) { i2 = p2 + ilen * p1 + i2; i1 = p1 + i1; ilen += pl; }
-    }
-    if (lane == 63) { w1[wave] = i1; w2[wave] = i2; wl[wave] = ilen; }
-    u64 x1 = rx_shfl_up64(i1, 1), x2 = rx_shfl_up64(i2, 1), xl = rx_shfl_up64(ilen, 1);
-    if (lane == 0) { x1 = 0; x2 = 0; xl = 0; }
-    __syncthreads();
-    // the saved state advanced through the earlier waves, then through the earlier lanes of this one
-    u64 s1 = ch->i1[comp], s2 = ch->i2[comp];
-    __syncthreads();                              // every wave has read the saved state
-    for (int w = 0; w < wave; w++) { s2 = s2 + wl[w] * s1 + w2[w]; s1 = s1 + w1[w]; }
-    u64 c1 = s1 + x1, c2 = s2 + xl * s1 + x2;
-    if (regs) {
-#pragma unroll
-        for (int k = 0; k < RX_SCAN_PER; k++) {
-            const int r = r0 + k;
-            if (r < r1) {
-                const u64 l = run_len(r);
-                e1[r] = c1; e2[r] = c2;
-                c2 = c2 + l * c1 + f2[k]; c1 = c1 + f1[k];
-            }
-        }
-    } else {
-        for (int r = r0; r < r1; r++) {
-            const u64 l = run_len(r), g1 = e1[r], g2 = e2[r];
-            e1[r] = c1; e2[r] = c2;
-            c2 = c2 + l * c1 + g2; c1 = c1 + g1;
-        }
-    }
-    if (r1 == nruns && r0 < nruns) { ch->i1[comp] = c1; ch->i2[comp] = c2; }
-}
-
 // The third level of the end-referred scan: one wave per (channel, I/Q) over its workgroup totals (at most 64: max_runs / 256).
 // In: wg[li][2 comp + {0, 1}][w] = totals of workgroup w; out: the same slots = the carried-in state advanced to the end of the
 // block + the totals of the workgroups before w; the pair's grand total is the state after the block.
@@ -341,59 +259,6 @@ __global__ __launch_bounds__(64) void rx1_scan_wg_kernel(u64 *__restrict__ wg, i
     if (lane == 0) { x1 = 0; x2 = 0; }
     if (lane < gx) { t1[lane] = b1 + x1; t2[lane] = b2 + x2; }
     if (lane == 63) { ch->i1[comp] = b1 + v1; ch->i2[comp] = b2 + v2; }
-}
-
-// Prefix sum of the runs' integrator-3 totals (mod 2^26): one workgroup per (channel, I/Q), run r = k * 512 + thread
-// so that every tile of 512 runs is loaded and stored contiguously (as ddc_wf_scan_tau_kernel, kg_ddc.hip).
-#define RX_TAU_TILES 32                       // max_runs = 16384 = 32 tiles of 512
-__global__ __launch_bounds__(64 * RX_SCAN_WAVES) void rx1_scan_tau_kernel(u32 *__restrict__ tau, int nruns, rx_chan *__restrict__ chans,
-                                                                         const int *__restrict__ chan_list)
-{
-    __shared__ u32 s_tot[RX_TAU_TILES * RX_SCAN_WAVES];
-    __shared__ u32 s_w4[4];
-    const int li = blockIdx.x >> 1, comp = blockIdx.x & 1, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, gl = threadIdx.x;
-    rx_chan *ch = chans + chan_list[li];
-    u32 *tv = tau + ((long) li * 2 + comp) * nruns;
-    const int ntile = (nruns + 511) >> 9;
-    u32 inc[RX_TAU_TILES], own[RX_TAU_TILES];
-#pragma unroll
-    for (int k = 0; k < RX_TAU_TILES; k++) {
-        const int r = (k << 9) + gl;
-        own[k] = (k < ntile && r < nruns) ? tv[r] : 0u;
-    }
-#pragma unroll
-    for (int k = 0; k < RX_TAU_TILES; k++) {
-        u32 v = own[k];
-        for (int d = 1; d < 64; d <<= 1) { const u32 a = __shfl_up(v, d); if (lane >= d) v += a; }
-        inc[k] = v;
-        if (lane == 63) s_tot[k * RX_SCAN_WAVES + wave] = v;
-    }
-    __syncthreads();
-    u32 t = 0, tinc = 0;
-    if (gl < 256) {
-        t = s_tot[gl];
-        tinc = t;
-        for (int d = 1; d < 64; d <<= 1) { const u32 a = __shfl_up(tinc, d); if (lane >= d) tinc += a; }
-        if (lane == 63) s_w4[wave] = tinc;
-    }
-    __syncthreads();
-    if (gl < 256) {
-        u32 base = 0;
-        for (int w = 0; w < wave; w++) base += s_w4[w];
-        s_tot[gl] = base + tinc - t;
-    }
-    const u32 i3 = ch->i3[comp];
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < RX_TAU_TILES; k++) {
-        const int r = (k << 9) + gl;
-        if (k < ntile && r < nruns) tv[r] = (i3 + s_tot[k * RX_SCAN_WAVES + wave] + inc[k] - own[k]) & 0x03FFFFFFu;
-    }
-    if (gl == 0) {
-        u32 total = i3;
-        for (int w = 0; w < 4; w++) total += s_w4[w];
-        ch->i3[comp] = total & 0x03FFFFFFu;
-    }
 }
 
 // ... and of the integrator-3 totals: in = the workgroups' totals, out = integrator 3 at each workgroup's first run.
@@ -417,7 +282,7 @@ __global__ __launch_bounds__(256) void rx1_comb_kernel(
     const rx_chan *__restrict__ chans, const int *__restrict__ chan_list, const long *__restrict__ nouts,
     const u32 *__restrict__ cnt_before, int *__restrict__ c1buf, long c1_stride, u32 *__restrict__ hist_out,
     int RX_R1,
-    const u32 *__restrict__ wgt, int gx)      // end-referred levels: i3start[] is relative to wgt[li][comp][run / 256]; or null
+    const u32 *__restrict__ wgt, int gx)      // end-referred levels: i3start[] is relative to wgt[li][comp][run / 256]
 {
     const int li = blockIdx.y;
     const rx_chan *ch = chans + chan_list[li];
@@ -434,7 +299,7 @@ __global__ __launch_bounds__(256) void rx1_comb_kernel(
             else {
                 const long g = (oo + 1) * RX_R1 - 1 - (long) base;      // sample index of the strobe
                 const int run = (int) (g / L);
-                const u32 wb = wgt ? wgt[((long) li * 2 + comp) * gx + (run >> RX_LOG_THREADS)] : 0u;
+                const u32 wb = wgt[(li * 2 + comp) * gx + (run >> RX_LOG_THREADS)];    // (an int: below 2 x 4096 channels x 64)
                 v = (c0rel[((long) li * 2 + comp) * max_out + oo] + i3start[((long) li * 2 + comp) * nruns + run] + wb) & 0x03FFFFFFu;
             }
             c0[d] = sx((int) v, 26);
@@ -723,36 +588,26 @@ int kg_rxddc_push_dev(kg_rxddc *d, const void *d_adc, size_t n, const int32_t *c
     KG_PLAN_ONLY(d->ctx);
     const dim3 grid((nruns + RX_THREADS - 1) / RX_THREADS, nlist);
     // end-referred carry states, summed inside pass A's workgroups and by one wave per (channel, I/Q) over the workgroup
-    // totals (round 4); KIWIGPU_RXDDC_ENDREF=0: run-start states and rx1_scan_kernel, the A/B reference
-    int endref = 1;
-    if (const char *e = kg_tuning_env("KIWIGPU_RXDDC_ENDREF")) endref = atoi(e) != 0;
+    // totals (round 4)
     static_assert(16384 / RX_THREADS <= 64, "rx1_scan_wg_kernel scans one workgroup total per lane");
     hipLaunchKernelGGL(rx1_run_kernel<false>, grid, dim3(RX_THREADS), 0, st, (const short *) d_adc, (long) n, L, nruns,
                        (const rx_chan *) d->d_chans, s_list, (const u32 *) d->d_nco, d->d_st,
-                       d->d_c0rel, d->d_tau, d->max_out, d->md, endref, d->d_wg, d->d_wgt);
+                       d->d_c0rel, d->d_tau, d->max_out, d->md, d->d_wg, d->d_wgt);
     KG_HIP(hipGetLastError());
-    if (endref)
-        hipLaunchKernelGGL(rx1_scan_wg_kernel, dim3(2 * nlist), dim3(64), 0, st, d->d_wg, (int) grid.x, (long) n, d->d_chans, s_list);
-    else
-        hipLaunchKernelGGL(rx1_scan_kernel, dim3(2 * nlist), dim3(64 * RX_SCAN_WAVES), 0, st, d->d_st, (long) n, L, nruns, d->d_chans,
-                           s_list);
+    hipLaunchKernelGGL(rx1_scan_wg_kernel, dim3(2 * nlist), dim3(64), 0, st, d->d_wg, (int) grid.x, (long) n, d->d_chans, s_list);
     KG_HIP(hipGetLastError());
     hipLaunchKernelGGL(rx1_run_kernel<true>, grid, dim3(RX_THREADS), 0, st, (const short *) d_adc, (long) n, L, nruns,
                        (const rx_chan *) d->d_chans, s_list, (const u32 *) d->d_nco, d->d_st,
-                       d->d_c0rel, d->d_tau, d->max_out, d->md, endref, d->d_wg, d->d_wgt);
+                       d->d_c0rel, d->d_tau, d->max_out, d->md, d->d_wg, d->d_wgt);
     KG_HIP(hipGetLastError());
-    if (endref)
-        hipLaunchKernelGGL(rx1_tau_wg_kernel, dim3(2 * nlist), dim3(64), 0, st, d->d_wgt, (int) grid.x, d->d_chans, s_list);
-    else
-        hipLaunchKernelGGL(rx1_scan_tau_kernel, dim3(2 * nlist), dim3(64 * RX_SCAN_WAVES), 0, st, d->d_tau, nruns, d->d_chans,
-                           s_list);
+    hipLaunchKernelGGL(rx1_tau_wg_kernel, dim3(2 * nlist), dim3(64), 0, st, d->d_wgt, (int) grid.x, d->d_chans, s_list);
     KG_HIP(hipGetLastError());
     if (max_n1 > 0) {
         hipLaunchKernelGGL(rx1_comb_kernel, dim3((unsigned) ((max_n1 + 255) / 256), nlist), dim3(256), 0, st,
                            (const u32 *) d->d_c0rel, (const u32 *) d->d_tau, L, nruns, d->max_out,
                            (const rx_chan *) d->d_chans, s_list, s_nouts,
                            s_cnt, d->d_c1buf, d->c1_stride, d->d_hist, d->md.r1,
-                           endref ? (const u32 *) d->d_wgt : (const u32 *) nullptr, (int) grid.x);
+                           (const u32 *) d->d_wgt, (int) grid.x);
         KG_HIP(hipGetLastError());
     }
     if (max_final > 0) {

@@ -57,11 +57,14 @@ def test_pieces_of_any_length_carry_state(gpu_ctx, oracle):
         d.close()
 
 
-def test_long_blocks_take_the_chunked_state_scan(gpu_ctx, oracle):
-    """2^21 samples in two unequal pushes: 8192+ runs per channel, so the integrator carry scan of a
-    (channel, I/Q) pair is cut into the maximum number of chunks across workgroups (look-back through
-    published aggregates), with the state carried from the first push into the second; R = 1 rides
-    along on the bypass kernel's persistent loop."""
+def test_long_blocks_fill_every_lane_of_the_workgroup_scan(gpu_ctx, oracle):
+    """2^21 samples in two unequal pushes, three channels: an object of this size takes up to 16384
+    runs per channel, i.e. 64 workgroups per channel in the run passes -- the limit DDC_MAX_GX
+    asserts, one workgroup total per lane of ddc_wf_scan_wg_kernel / ddc_wf_tau_wg_kernel.  The
+    first push (2^20 + 12345 samples) takes 8289 runs of 128 samples, 33 workgroups; the second
+    (2^20 - 12345) 16192 runs of 64 samples: all 64 lanes, the last workgroup a ragged one -- with
+    the end-referred state carried from the first push into the second, between two run lengths.
+    R = 1 rides along on the bypass kernel's persistent loop."""
     n = 1 << 21
     adc = adc_stream(n, seed=77, tones=((0.0123, 9000.0), (0.31, 1500.0)))
     chans = [(inc_for(0.0123 + 2.0 ** -20), 6), (inc_for(0.31), 12), (inc_for(0.05), 0)]

@@ -60,7 +60,7 @@ def trial_wfddc():
     subset), one-shot captures (CmdWFReset + sampler, random sampler size), CIC resets, retunes, new phases -- in line or
     with the deferred output stage -- against an oracle channel model that is told the same story."""
     nch = int(rng.integers(1, 5))
-    big = rng.random() < 0.15                        # long blocks: the carry scan cut into chunks across workgroups
+    big = rng.random() < 0.15                        # long blocks: many workgroup totals per channel in the carry scan
     d = Ddc(ctx, nchan=nch, max_samples=1 << (20 if big else 17))
     incs = [int(rng.integers(0, 1 << 48)) for _ in range(nch)]
     l2 = [int(rng.integers(0, 14)) for _ in range(nch)]
