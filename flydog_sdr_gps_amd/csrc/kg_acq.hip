@@ -289,13 +289,15 @@ struct acq_walk {
 // The rest is a power of ONE per-lane value per d, so the sum over k2 is a Horner chain walked from k2 = P - 1 down:
 //     y = Z'_0 + V (Z'_1 + V (Z'_2 + ...)),   Z'_k2 = W_R^{c k2} IFFT_4096(X[P k1 + k2])  as pass 2 delivers it
 // -- four per-lane constants V[d] = tabN[t + 1024 d] for the life of the kernel and two fused multiply-adds per point and
-// item; no factor is rebuilt per item.
+// item; no factor is rebuilt per item.  V is rounded once and term k2 carries that rounding k2 times: the P = 16 chain is
+// restarted at k2 = 8 with a factor of its own (kg_acq_mid_factors, kg_acq_tables.h), which keeps it inside the accuracy
+// budget of tests/test_dft_truth_gpu.py.
 template <int P, bool STAMPS = false>
 __global__ __launch_bounds__(256, 2) void acq_correlate_kernel(
     const float2 *__restrict__ data,  // [nblocks][P][4096]
     const float2 *__restrict__ code,  // [max_sats][P][8 rows][2 (256 + 2 H)]
     const float2 *__restrict__ tab4096, const float2 *__restrict__ tabN,
-    const float2 *__restrict__ comb,           // [P][KG_ACQ_ROWK] row constants of pass 2
+    const float2 *__restrict__ comb,           // [P][KG_ACQ_ROWK] row constants of pass 2; P = 16: + [4][256] restart factors
     const acq_pair_desc *__restrict__ pairs,   // pair p belongs to XCD group p & 7
     int *__restrict__ claim,                   // [8][ACQ_CLAIM_STRIDE] per-group cell counters, zero at launch
     acq_walk walk,
@@ -432,20 +434,36 @@ __global__ __launch_bounds__(256, 2) void acq_correlate_kernel(
         // place in the conjugate product and pass 0.
         cf yprev[16];
         // acc[c + 4d] = acc[c + 4d] * V[d] + yv[c + 4d] (yv is scratch afterwards); the cell's first item (k2 = P - 1) is the copy
-        auto accumulate = [&](cf (&yv)[16], bool first) {
+        // mid (P = 16, the step that takes in item KG_ACQ_MID - 1): the restart factor M[d] = W^MID / V[d]^(MID - 1) in V's place
+        // (kg_acq_tables.h), read once a cell from behind the row constants
+        auto accumulate = [&](cf (&yv)[16], bool first, bool mid = false) {
             if (first) {
 #pragma unroll
                 for (int m = 0; m < 16; m++) acc[m] = yv[m];
                 return;
             }
+            // (into V's own registers and V back behind the step: the kernel has no register to spare, and a second set of factors
+            // pushed V itself into scratch, reloaded by every item)
+            if constexpr (P == 16) {
+                if (mid) {
+#pragma unroll
+                    for (int dd = 0; dd < 4; dd++) V[dd] = kg_ld(&comb[P * KG_ACQ_ROWK + 256 * dd + t]);
+                }
+            }
 #pragma unroll
             for (int dd = 0; dd < 4; dd++)
                 kg_horner4v(acc[4 * dd], acc[4 * dd + 1], acc[4 * dd + 2], acc[4 * dd + 3],
                             yv[4 * dd], yv[4 * dd + 1], yv[4 * dd + 2], yv[4 * dd + 3], V[dd]);
+            if constexpr (P == 16) {
+                if (mid) {
+#pragma unroll
+                    for (int dd = 0; dd < 4; dd++) V[dd] = kg_ld(&tabN[t + 1024 * dd]);
+                }
+            }
         };
         // (a lambda of its own, not the three statements at the call: the inlining order decides the register allocation of
         // the item loop)
-        auto accumulate_fenced = [&](bool first) { kg_pin(); accumulate(yprev, first); kg_pin(); };
+        auto accumulate_fenced = [&](bool first, bool mid) { kg_pin(); accumulate(yprev, first, mid); kg_pin(); };
         const int tl = t & 15, th = t >> 4;
         const int rd = t ^ (th & 15);              // P(t + 256 j) = 256 j + (t ^ ((t >> 4) & 15)), kg_fft.h
         // rolled on purpose: unrolled (or with k2 a template constant) the
@@ -488,7 +506,7 @@ __global__ __launch_bounds__(256, 2) void acq_correlate_kernel(
             // the deferred Horner step of item k2 + 1: after barrier 1, while the pass-1 tile reads are in flight
             // (one of an item's four waits -- behind the stores before either barrier, or after it with the tile reads
             // in flight; moving it between them changed nothing, DESIGN_HISTORY)
-            if (k2 < P - 1) accumulate_fenced(k2 == P - 2);
+            if (k2 < P - 1) accumulate_fenced(k2 == P - 2, P == 16 && k2 == KG_ACQ_MID - 2);
             if (STAMPS) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             KG_STAMP(STAMPS, sti, 3);
             // pass 1: twiddle W256^(j*(t&15)), out index (t>>4)*256 + (t&15) + 16 m = t + 16 (15 th + m).  Round 4: this second
@@ -1068,7 +1086,7 @@ struct kg_acq {
     size_t code_len;   // float2 per code spectrum (P planes with halo)
     float2 *d_tabN;        // exp(+2 pi i k / N); the context's table for N = 16384
     bool own_tabN;
-    float2 *d_comb;        // [P][KG_ACQ_ROWK]  row constants of pass 2 (acq_correlate_kernel)
+    float2 *d_comb;        // [P][KG_ACQ_ROWK]  row constants of pass 2 (acq_correlate_kernel); P = 16: + [4][256] restart factors
     float2 *d_quart;       // [P][4]  W_P^{q k2}: the factor of output quarter q (acq_correlate8_kernel)
     float2 *d_comb8;       // [P][4]  combine constants of the 512-thread four-quarter kernel
     int grid8;             // its persistent grid (>= 8)
@@ -1227,9 +1245,10 @@ static int acq_init(kg_acq *a)
         KG_HIP(hipMemcpy(a->d_tabN, h.data(), spec, hipMemcpyHostToDevice));
     }
     {
-        std::vector<float2> comb(P * KG_ACQ_ROWK), quart(P * 4);
+        std::vector<float2> comb(P * KG_ACQ_ROWK + (P == 16 ? 4 * 256 : 0)), quart(P * 4);
         static_assert(sizeof(float2) == 2 * sizeof(float), "float2 = (re, im)");
         kg_acq_row_consts(P, &comb[0].x);
+        if (P == 16) kg_acq_mid_factors(N, &comb[P * KG_ACQ_ROWK].x);     // the Horner chain's restart factors, [4][256]
         for (int k2 = 0; k2 < P; k2++)
             for (int q = 0; q < 4; q++) quart[4 * k2 + q] = unit_root((long) q * k2, P);
         KG_HIP(hipMalloc((void **) &a->d_comb, sizeof(float2) * comb.size()));

@@ -33,3 +33,29 @@ static inline void kg_acq_row_consts(int P, float *out)
                 kg_unit_root_f((long) c * (d * (R / 16) + k2), R, &o[0], &o[1]);
             }
 }
+
+// The Horner chain of the C/A correlator (acq_correlate_kernel) gives term k2 the factor V^k2 with V = fl(W), W = W_N^{t + 1024 d}:
+// the one rounding of V, W (1 + e), comes out as W^k2 (1 + k2 e) -- 15 e at the far end of the P = 16 chain, a relative error
+// near 1e-6 in a peak's power where the lines of a spectrum sit in the planes k2 = 10 .. 15 (tests/test_dft_truth_gpu.py).  So
+// the P = 16 chain is RESTARTED once: the step that takes in term KG_ACQ_MID - 1 multiplies by M = W^MID / V^(MID - 1) instead
+// of by V, and what the terms MID .. 15 have gathered reaches the end as W^MID (1 + e_M): no term carries more than 7 e + e_M.
+// out: [4][256] (re, im) pairs, entry 256 d + t; V as kg_unit_root_f rounds it, the quotient in double.
+#define KG_ACQ_MID 8
+static inline void kg_acq_mid_factors(long N, float *out)
+{
+    for (int d = 0; d < 4; d++)
+        for (int t = 0; t < 256; t++) {
+            const long n = t + 1024L * d;
+            float vr, vi;
+            kg_unit_root_f(n, N, &vr, &vi);
+            double pr = 1.0, pi = 0.0;                 // V^(MID - 1)
+            for (int i = 0; i < KG_ACQ_MID - 1; i++) {
+                const double r = pr * vr - pi * vi, m = pr * vi + pi * vr;
+                pr = r; pi = m;
+            }
+            const double a = 2.0 * M_PI * (double) ((KG_ACQ_MID * n) % N) / (double) N;
+            const double wr = cos(a), wi = sin(a), q = pr * pr + pi * pi;
+            out[2 * (256 * d + t)] = (float) ((wr * pr + wi * pi) / q);          // W^MID conj(V^7) / |V^7|^2
+            out[2 * (256 * d + t) + 1] = (float) ((wi * pr - wr * pi) / q);
+        }
+}

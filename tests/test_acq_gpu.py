@@ -2,6 +2,8 @@
 
 Bars (BASELINE.json north_star): peak index / Doppler bin bit-exact; float
 results within 1e-5 relative (spectra: relative to the spectrum's max magnitude).
+That is the contract with the reference.  How far the transforms themselves are from
+the exact DFT is held, at fp32 accuracy, by tests/test_dft_truth_gpu.py.
 """
 import numpy as np
 import pytest

@@ -103,3 +103,25 @@ def test_host_built_row_constants(driver, tmp_path, P):
     w32[axis] = (np.round(np.stack([want.real, want.imag], axis=-1)[axis]) + 0.0).astype(np.float32)     # (+ 0.0: no -0)
     assert np.array_equal(got.view(np.uint32), w32.view(np.uint32))
     assert np.all(got[0, [0, 4, 8]] == np.float32([1, 0]))     # k2 = 0: z0 of every row keeps its value exactly
+
+
+def test_restart_factors_halve_the_drift_of_the_65536_chain(driver, tmp_path):
+    """Term k2 of the chain carries V^k2 with V = fl(W): one rounding of V comes out k2 times.  kg_acq_mid_factors gives the step
+    that takes in term 7 the factor M = W^8 / V^7, so terms 8 .. 15 carry V^(k2 - 8) M V^7 = W^8 V^(k2 - 8) (1 + e_M): the
+    table against numpy, and the factor of every term of every lane against W^k2 in float64 (the drift alone, without the
+    roundings of the chain's own arithmetic)."""
+    out = str(tmp_path / "mid.bin")
+    subprocess.run([driver, "mid", out], check=True)
+    got = np.fromfile(out, np.float32).reshape(4, 256, 2)
+    M = got[..., 0].astype(np.float64) + 1j * got[..., 1]
+    n = np.arange(256)[None, :] + 1024 * np.arange(4)[:, None]
+    W = root(n, 65536)
+    V = W.real.astype(np.float32).astype(np.float64) + 1j * W.imag.astype(np.float32).astype(np.float64)
+    want = root(8 * n, 65536) / V ** 7
+    assert np.abs(M - want).max() <= 2.0 ** -23                  # the double quotient, rounded to fp32 per component
+    assert got[0, 0, 0] == 1 and got[0, 0, 1] == 0               # lag 0: every factor is exactly one
+    plain = max(np.abs(V ** k / W ** k - 1).max() for k in range(16))
+    restarted = max(np.abs((V ** k if k < 8 else V ** (k - 8) * M * V ** 7) / W ** k - 1).max() for k in range(16))
+    u = 2.0 ** -24
+    assert restarted <= 8.5 * u                                  # 7 roundings of V and one of M, each at most u in modulus... sqrt(2) u / sqrt(2)
+    assert plain >= 1.8 * restarted, (plain, restarted)
