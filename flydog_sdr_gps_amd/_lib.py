@@ -237,6 +237,13 @@ SYMBOLS = {
     "kg_eph_sv_dev": (_i, [_vp, _vp, _i, _vp]),
     "kg_eph_sv": (_i, [_vp, _vp, _i, _vp]),
     "kg_eph_replica": (None, [C.c_uint32, _vp, _vp]),
+    "kg_pos_create": (_i, [_vp, _vp, C.c_double, C.c_double, C.POINTER(_vp)]),
+    "kg_pos_destroy": (None, [_vp]),
+    "kg_pos_set_mode": (_i, [_vp, _i, _i]),
+    "kg_pos_reset": (_i, [_vp]),
+    "kg_pos_solve_dev": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "kg_pos_solve": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "kg_pos_get_state": (_i, [_vp, _i, _vp]),
     "kg_aper_create": (_i, [_vp, _i, C.POINTER(_vp)]),
     "kg_aper_destroy": (None, [_vp]),
     "kg_aper_update_dev": (_i, [_vp, _vp, _i, _vp, _sz, _vp, _i]),

@@ -7,7 +7,7 @@ Reference                                                                       
   SNAPSHOT::GetClock, LoadFromReplicas' body  gps/solve.cpp:168-244, :319-361      -> Ephemerides.sv / sv_dev
   GetClockCorrection, GetXYZ, ...             gps/ephemeris.cpp:114-207            -> (inside the kernel)
 
-Not here: PosSolver and everything behind GNSSDataForEpoch, the glitch guard, probation / alert / abort, tow_time, almanac words.
+Not here: PosSolver and everything behind GNSSDataForEpoch (pos.py has them), the glitch guard, probation / alert / abort, tow_time, almanac words.
 
 subframe_words() and inav_word() are ENCODERS (raw integer fields -> the words nav.l1_subframe / nav.e1b_page take): input generators
 for tests and synthetic scenes, not part of the measured path.

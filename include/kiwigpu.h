@@ -990,7 +990,7 @@ int kg_nav_get_state(kg_nav *nav, int ch, int32_t *holding, uint64_t *bit0, uint
  * Position and clock pass through sin, cos, atan2 and sqrt, where the device's library and the host's may differ in the last
  * bit: x, y, z within 1e-3 m, ct within 2 ulp, t_k within 2 ulp of t_tx of the reference.
  *
- * Not here: PosSolver, the EKF, ionosphere and troposphere, LoadReplicas' glitch guard and include_E1B filter; probation, alert,
+ * Not here: PosSolver and the EKF (kg_pos, below), ionosphere and troposphere, LoadReplicas' glitch guard and include_E1B filter; probation, alert,
  * abort and expecting_preamble (host decisions; the notes carry what bits_tow needs); CHANNEL::Subframe's statistics; tow_time and the
  * L_* debug members; almanac words 7..9.
  * ------------------------------------------------------------------------- */
@@ -1051,6 +1051,47 @@ int kg_eph_sv_dev(kg_eph *eph, const kg_eph_snap *d_snaps, int nsnap, kg_eph_pos
 int kg_eph_sv(kg_eph *eph, const kg_eph_snap *snaps, int nsnap, kg_eph_pos *out);      /* the same on host memory; synchronises */
 /* chips and cg_phase of a snapshot from the 18-bit replica word of kg_trk_get_clocks, by LoadAtomic's masks (solve.cpp:77-79). */
 void kg_eph_replica(uint32_t word, int32_t *chips, int32_t *cg_phase);
+
+/* ---------------------------------------------------------------------------------------------------------------------------------
+ * The position fix: what turns the rows of kg_eph_sv_dev into a position.  Replaces GNSSDataForEpoch::LoadFromReplicas' compaction
+ * (gps/solve.cpp:319-364), SolveTask's three solvers and its per-epoch statements (solve.cpp:571-578, :616-639), PosSolverImpl
+ * (gps/PosSolver.cpp:32-38, :45-59, :64-144, :169-172), SinglePointPositionSolver.h:20-64, EKFPositionSolver.h:21-124,
+ * PositionSolverBase.h:61-125, Ellipsoid.h:39-63, TNT's matmult / mean / norm / makeDiag and JAMA's LU (pkgs/TNT_JAMA), and of
+ * update_gps_info_after the lines :497-516 (grn_yel_red, ch_has_soln, az/el).  Not here: clock_correction, tod_correction, the gps.*
+ * tables (az / el[last_samp], shadow_map, fix counters, POS_data / MAP_data), the "already have az/el" skip, the glitch counters,
+ * compute_dop.  DESIGN.md 6.13.
+ *
+ * An epoch is nrow rows, row r = channel r: a kg_eph_snap, of which sat and power are read, and the kg_eph_pos kg_eph_sv_dev made of it.  Rows
+ * with KG_EPH_SV_NOT_VALID, and rows whose bit is set in the epoch's `skip` word (the host's glitch guard and include_E1B filter), were
+ * never in Replicas; KG_EPH_SV_POWER rows advance the reference's `i` but do not enter; every other row enters, NaN rows included.
+ * The type of an entering row is kinds[_sat[i]] with the reference's index quirk (see kg_pos.h, load_epoch).  An epoch with no row in
+ * Replicas changes nothing (`if (good == 0) continue;`); its record reports the held state. */
+typedef struct kg_pos kg_pos;
+enum { KG_POS_CALLED = 1,                /* solve() ran on a non-empty set this epoch */
+       KG_POS_POS_VALID = 2, KG_POS_SPP_VALID = 4, KG_POS_EKF_VALID = 8 };      /* pos_valid(), spp_valid(), ekf_valid() after the epoch */
+typedef struct { double x, y, z, t_rx, osc_corr, lambda, phi, alt; int32_t flags, ekf_running, nsv, pad; } kg_pos_fix;   /* pos(), t_rx(), osc_corr(), llh() */
+typedef struct { double elev_deg, azim_deg; int32_t sat, ch, type, week, el, az; } kg_pos_sat;   /* el = az = 0: rejected by solve.cpp:515 or no fix */
+typedef struct { kg_pos_fix fix[3]; kg_pos_sat sat[12]; int32_t chans, grn_yel_red; uint32_t ch_has_soln, pad; } kg_pos_epoch;
+typedef struct {                         /* one solver: PosSolverImpl's members with its two solvers' */
+    double spp_state[4], spp_cov[16], ekf_state[5], ekf_P[25];
+    double pos[3], t_rx, osc_corr, lambda, phi, alt, ct_rx[2];
+    uint64_t ticks_spp[2], ticks_ekf[2];
+    int32_t pos_valid, ekf_running, state_spp[2], ekf_valid, pad;      /* ekf_valid: EKFPositionSolver::_valid */
+} kg_pos_state;
+/* kinds: KG_EPH_* per satellite slot (Sats[].type).  uere, f_osc: PosSolver::make's arguments (the reference: UERE 6.0, ADC_CLOCK_TYP
+ * 124.9999e6), finite and positive.  Three fresh solvers (TNT's unset _state / _cov are zero here), use_kalman 1, plot_e1b 0. */
+int kg_pos_create(kg_ctx *ctx, const int32_t kinds[64], double uere, double f_osc, kg_pos **out);
+void kg_pos_destroy(kg_pos *pos);
+int kg_pos_set_mode(kg_pos *pos, int use_kalman, int plot_e1b);        /* admcfg's two switches (solve.cpp:618-619); in stream order */
+int kg_pos_reset(kg_pos *pos);                                         /* ours: three fresh solvers; the mode stays.  In stream order */
+/* nepoch epochs in order, one launch: epoch e reads rows e * nrow .. e * nrow + nrow - 1 of d_snaps and d_sv, d_ticks[e] (the 48-bit
+ * ADC tick count) and, if d_skip is given, d_skip[e]; writes d_out[e].  1 <= nrow <= KG_TRK_MAX_CHANS, 1 <= nepoch <= 65536;
+ * d_snaps and d_skip 4-byte, d_sv, d_ticks and d_out 8-byte aligned; anything else KG_ERR_INVALID, nothing done.  Enqueue only. */
+int kg_pos_solve_dev(kg_pos *pos, const kg_eph_snap *d_snaps, const kg_eph_pos *d_sv, int nrow, int nepoch, const uint64_t *d_ticks,
+                     const uint32_t *d_skip, kg_pos_epoch *d_out);
+int kg_pos_solve(kg_pos *pos, const kg_eph_snap *snaps, const kg_eph_pos *sv, int nrow, int nepoch, const uint64_t *ticks,
+                 const uint32_t *skip, kg_pos_epoch *out);              /* the same on host memory; synchronises */
+int kg_pos_get_state(kg_pos *pos, int solver, kg_pos_state *out);       /* solver 0 .. 2 (all, not Galileo, only Galileo); synchronises */
 
 /* kg_fir_process_dev plus the extension taps of ProcessData (SURVEY.md 8(f) rank 4;
  * rx/CuteSDR/fastfir.cpp:278-302): for block b of list entry i, 1024 complex floats at
