@@ -6,7 +6,7 @@ mirror of the reference's entry points for the path (gps/search.cpp
 SearchInit / Sample / Correlate).  There is no CPU fallback: without the built
 library and a gfx950 device, constructing a context raises.
 """
-from ._lib import KiwiGpuError, Context, load_library, library_path  # noqa: F401
+from ._lib import KiwiGpuError, Context, load_library, library_path, live_allocs  # noqa: F401
 from .acq import Searcher, AcqResult  # noqa: F401
 from .wf import Waterfall, WfParams  # noqa: F401
 from .ddc import Ddc, RxDdc  # noqa: F401
@@ -22,4 +22,4 @@ from .pos import PositionSolver  # noqa: F401
 from . import sats, prn, synth, shard, wf, snd, post, wire, handoff, nb, trk, nav, eph, pos  # noqa: F401
 
 __all__ = ["KiwiGpuError", "Context", "Searcher", "AcqResult", "Waterfall", "WfParams", "Ddc", "RxDdc", "FastFir", "Post", "NoiseBlanker", "Adpcm", "Aperture", "chan_start", "Tracker", "NavSync", "Ephemerides",
-           "load_library", "library_path", "sats", "prn", "synth", "shard", "wf"]
+           "load_library", "library_path", "live_allocs", "sats", "prn", "synth", "shard", "wf"]

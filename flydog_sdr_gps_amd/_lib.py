@@ -46,6 +46,7 @@ SYMBOLS = {
     "kg_strerror": (C.c_char_p, [_i]),
     "kg_last_error": (C.c_char_p, []),
     "kg_abi_version": (_i, []),
+    "kg_dev_live_allocs": (C.c_int64, []),
     "kg_ctx_create": (_i, [_i, _vp, C.POINTER(_vp)]),
     "kg_ctx_create_on_stream": (_i, [_i, _vp, C.POINTER(_vp)]),
     "kg_ctx_destroy": (None, [_vp]),
@@ -334,6 +335,11 @@ def check(status, where):
         text = lib.kg_last_error().decode() or lib.kg_strerror(status).decode()
         raise KiwiGpuError(status, where, text)
     return status
+
+
+def live_allocs():
+    """The device and pinned allocations the library holds in this process right now (kg_dev_live_allocs)."""
+    return int(load_library().kg_dev_live_allocs())
 
 
 def borrow(cls, ctx, handle, **attrs):

@@ -1084,37 +1084,37 @@ struct kg_acq {
     size_t in_stride;  // bytes of one block of int16 IQ staging: nsamples * 4
     int halo;          // H of the code planes: covers every floor((k2 - dop) / P)
     size_t code_len;   // float2 per code spectrum (P planes with halo)
-    float2 *d_tabN;        // exp(+2 pi i k / N); the context's table for N = 16384
-    bool own_tabN;
-    float2 *d_comb;        // [P][KG_ACQ_ROWK]  row constants of pass 2 (acq_correlate_kernel); P = 16: + [4][256] restart factors
-    float2 *d_quart;       // [P][4]  W_P^{q k2}: the factor of output quarter q (acq_correlate8_kernel)
-    float2 *d_comb8;       // [P][4]  combine constants of the 512-thread four-quarter kernel
+    const float2 *d_tabN;  // exp(+2 pi i k / N): the context's table for N = 16384, own_tabN otherwise
+    kg_dbuf<float2> own_tabN;
+    kg_dbuf<float2> d_comb;        // [P][KG_ACQ_ROWK]  row constants of pass 2 (acq_correlate_kernel); P = 16: + [4][256] restart factors
+    kg_dbuf<float2> d_quart;       // [P][4]  W_P^{q k2}: the factor of output quarter q (acq_correlate8_kernel)
+    kg_dbuf<float2> d_comb8;       // [P][4]  combine constants of the 512-thread four-quarter kernel
     int grid8;             // its persistent grid (>= 8)
-    float2 *d_code;        // [max_sats][P planes with halo]
-    float2 *d_data;        // [max_blocks][P][4096]  layout A
-    float2 *d_data_b;      // [max_blocks][P][4096]  layout B (the 512-thread kernel's); null until an SV needs it (ensure_data_b)
+    kg_dbuf<float2> d_code;        // [max_sats][P planes with halo]
+    kg_dbuf<float2> d_data;        // [max_blocks][P][4096]  layout A
+    kg_dbuf<float2> d_data_b;      // [max_blocks][P][4096]  layout B (the 512-thread kernel's); null until an SV needs it (ensure_data_b)
     std::vector<char> code_layout;   // per SV: 0 = A, 1 = B
-    float2 *d_td;          // [max_blocks][N]  decimated time-domain samples per block
-    float2 *d_td_code;     // [N]              same, for the code-table build
-    float2 *d_fsub;        // [max_blocks][P][4096] sub-transforms awaiting the radix-P combine
-    float2 *d_fsub_code;   // [P][4096]
-    uint8_t *d_in;     // [max_blocks][in_stride]    host-input staging
+    kg_dbuf<float2> d_td;          // [max_blocks][N]  decimated time-domain samples per block
+    kg_dbuf<float2> d_td_code;     // [N]              same, for the code-table build
+    kg_dbuf<float2> d_fsub;        // [max_blocks][P][4096] sub-transforms awaiting the radix-P combine
+    kg_dbuf<float2> d_fsub_code;   // [P][4096]
+    kg_dbuf<uint8_t> d_in;     // [max_blocks][in_stride]    host-input staging
     // Host-buffer Sample() calls return before the copy has run ("enqueue only"), so the
     // caller's samples are first copied into one of a few pinned slots; a slot is reused
     // once the event recorded behind its copy has fired.
-    uint8_t *h_pin[4];
+    kg_hbuf<uint8_t> h_pin[4];
     hipEvent_t ev_pin[4];
     int pin_next;
     // batch calls: one pinned region for all blocks of the call, grown on demand
-    uint8_t *h_batch; size_t batch_cap; hipEvent_t ev_batch;
+    kg_hbuf<uint8_t> h_batch; size_t batch_cap; hipEvent_t ev_batch;
     // its transfer runs on a copy-only stream so that it overlaps the previous batch's
     // correlation: ev_batch = transfer done, ev_in_free = the staging area has been consumed
     hipStream_t cstream; hipEvent_t ev_in_free; bool in_free_set;
-    uint8_t *d_chips;  // [E1B_CODELEN max]
-    kg_acq_cell *d_cells;
-    acq_part *d_parts;     // [max_blocks][max_sats][ndop][4]  wave records of the 4096-lag correlator, between it and acq_select_kernel
-    kg_acq_result *d_results;
-    int *d_claim;      // [16][ACQ_CLAIM_STRIDE] cell counters of the C/A ([0..8)) and E1B ([8..16)) launches; zero between launches
+    kg_dbuf<uint8_t> d_chips;  // [E1B_CODELEN max]
+    kg_dbuf<kg_acq_cell> d_cells;
+    kg_dbuf<acq_part> d_parts;     // [max_blocks][max_sats][ndop][4]  wave records of the 4096-lag correlator, between it and acq_select_kernel
+    kg_dbuf<kg_acq_result> d_results;
+    kg_dbuf<int> d_claim;      // [16][ACQ_CLAIM_STRIDE] cell counters of the C/A ([0..8)) and E1B ([8..16)) launches; zero between launches
     std::vector<int> limits, code_set;
     // The (block, SV) pair tables of the last launch live in a slot of the context's staging
     // ring; they are reused while the SV list is unchanged and the slot has not come round.
@@ -1236,13 +1236,13 @@ static int acq_init(kg_acq *a)
     a->d_pairs1 = a->d_pairs4 = nullptr; a->pairs_seq = 0;
     a->in_stride = (size_t) a->nsamples * 4;
     const size_t spec = sizeof(float2) * N;
-    if (N == 16384) { a->d_tabN = ctx->d_tab16384; a->own_tabN = false; }
+    if (N == 16384) a->d_tabN = ctx->d_tab16384;
     else {
         std::vector<float2> h(N);
         for (int k = 0; k < N; k++) h[k] = unit_root(k, N);
-        KG_HIP(hipMalloc((void **) &a->d_tabN, spec));
-        a->own_tabN = true;
-        KG_HIP(hipMemcpy(a->d_tabN, h.data(), spec, hipMemcpyHostToDevice));
+        KG_TRY(a->own_tabN.alloc(N, "kg_acq_create: twiddle table"));
+        a->d_tabN = a->own_tabN;
+        KG_HIP(hipMemcpy(a->own_tabN, h.data(), spec, hipMemcpyHostToDevice));
     }
     {
         std::vector<float2> comb(P * KG_ACQ_ROWK + (P == 16 ? 4 * 256 : 0)), quart(P * 4);
@@ -1251,35 +1251,35 @@ static int acq_init(kg_acq *a)
         if (P == 16) kg_acq_mid_factors(N, &comb[P * KG_ACQ_ROWK].x);     // the Horner chain's restart factors, [4][256]
         for (int k2 = 0; k2 < P; k2++)
             for (int q = 0; q < 4; q++) quart[4 * k2 + q] = unit_root((long) q * k2, P);
-        KG_HIP(hipMalloc((void **) &a->d_comb, sizeof(float2) * comb.size()));
-        KG_HIP(hipMalloc((void **) &a->d_quart, sizeof(float2) * quart.size()));
+        KG_TRY(a->d_comb.alloc(comb.size(), "kg_acq_create: row constants"));
+        KG_TRY(a->d_quart.alloc(quart.size(), "kg_acq_create: quarter factors"));
         KG_HIP(hipMemcpy(a->d_comb, comb.data(), sizeof(float2) * comb.size(), hipMemcpyHostToDevice));
         KG_HIP(hipMemcpy(a->d_quart, quart.data(), sizeof(float2) * quart.size(), hipMemcpyHostToDevice));
         std::vector<float2> comb8(P * 4);
         for (int k2 = 0; k2 < P; k2++)
             for (int k = 0; k < 4; k++) comb8[4 * k2 + k] = unit_root((long) (k + 1) * k2, N / 512);
-        KG_HIP(hipMalloc((void **) &a->d_comb8, sizeof(float2) * comb8.size()));
+        KG_TRY(a->d_comb8.alloc(comb8.size(), "kg_acq_create: combine constants"));
         KG_HIP(hipMemcpy(a->d_comb8, comb8.data(), sizeof(float2) * comb8.size(), hipMemcpyHostToDevice));
     }
-    KG_HIP(hipMalloc((void **) &a->d_code, sizeof(float2) * a->code_len * max_sats));
-    KG_HIP(hipMalloc((void **) &a->d_data, spec * max_blocks));
-    KG_HIP(hipMalloc((void **) &a->d_td, spec * max_blocks));
-    KG_HIP(hipMalloc((void **) &a->d_td_code, spec));
-    KG_HIP(hipMalloc((void **) &a->d_fsub, spec * max_blocks));
-    KG_HIP(hipMalloc((void **) &a->d_fsub_code, spec));
-    KG_HIP(hipMalloc((void **) &a->d_in, a->in_stride * max_blocks));
+    KG_TRY(a->d_code.alloc(a->code_len * max_sats, "kg_acq_create: code spectra"));
+    KG_TRY(a->d_data.alloc((size_t) N * max_blocks, "kg_acq_create: data spectra"));
+    KG_TRY(a->d_td.alloc((size_t) N * max_blocks, "kg_acq_create: decimated samples"));
+    KG_TRY(a->d_td_code.alloc(N, "kg_acq_create: decimated samples"));
+    KG_TRY(a->d_fsub.alloc((size_t) N * max_blocks, "kg_acq_create: sub-transforms"));
+    KG_TRY(a->d_fsub_code.alloc(N, "kg_acq_create: sub-transforms"));
+    KG_TRY(a->d_in.alloc(a->in_stride * max_blocks, "kg_acq_create: input staging"));
     for (int k = 0; k < 4; k++) {
-        KG_HIP(hipHostMalloc((void **) &a->h_pin[k], a->in_stride, hipHostMallocDefault));
+        KG_TRY(a->h_pin[k].alloc(a->in_stride, "kg_acq_create: pinned input slots"));
         KG_HIP(hipEventCreateWithFlags(&a->ev_pin[k], hipEventDisableTiming));
     }
     KG_HIP(hipEventCreateWithFlags(&a->ev_batch, hipEventDisableTiming));
     KG_HIP(hipEventCreateWithFlags(&a->ev_in_free, hipEventDisableTiming));
-    { const int rc_ = kg_stream_get(ctx->device, &a->cstream); if (rc_) return rc_; }
-    KG_HIP(hipMalloc((void **) &a->d_chips, 8192));
-    KG_HIP(hipMalloc((void **) &a->d_cells, sizeof(kg_acq_cell) * (size_t) max_blocks * max_sats * a->ndop));
-    KG_HIP(hipMalloc((void **) &a->d_parts, sizeof(acq_part) * 4 * (size_t) max_blocks * max_sats * a->ndop));
-    KG_HIP(hipMalloc((void **) &a->d_results, sizeof(kg_acq_result) * (size_t) max_blocks * max_sats));
-    KG_HIP(hipMalloc((void **) &a->d_claim, sizeof(int) * 16 * ACQ_CLAIM_STRIDE));
+    KG_TRY(kg_stream_get(ctx->device, &a->cstream));
+    KG_TRY(a->d_chips.alloc(8192, "kg_acq_create: chips"));
+    KG_TRY(a->d_cells.alloc((size_t) max_blocks * max_sats * a->ndop, "kg_acq_create: cells"));
+    KG_TRY(a->d_parts.alloc(4 * (size_t) max_blocks * max_sats * a->ndop, "kg_acq_create: wave records"));
+    KG_TRY(a->d_results.alloc((size_t) max_blocks * max_sats, "kg_acq_create: results"));
+    KG_TRY(a->d_claim.alloc(16 * ACQ_CLAIM_STRIDE, "kg_acq_create: claim counters"));
     KG_HIP(hipMemset(a->d_claim, 0, sizeof(int) * 16 * ACQ_CLAIM_STRIDE));
     {
         // Sample() and Correlate() run in order on the context's stream.  A second stream
@@ -1290,7 +1290,7 @@ static int acq_init(kg_acq *a)
         // 528 us in order; profiles/r01_streams.txt), so the overlap is opt-in.
         const char *e = kg_tuning_env("KIWIGPU_ACQ_FRONT_STREAM");
         if (e && e[0] == '1') {
-            { const int rc_ = kg_stream_get(ctx->device, &a->fstream); if (rc_) return rc_; }
+            KG_TRY(kg_stream_get(ctx->device, &a->fstream));
             a->own_fstream = true;
         }
     }
@@ -1304,8 +1304,8 @@ static int acq_init(kg_acq *a)
         a->ev_done.push_back(e2);
     }
     KG_HIP(hipMemset(a->d_data, 0, spec * max_blocks));
-    a->d_data_b = nullptr;      // layout B: allocated (and from then on written by every Sample()) when the first code with a
-                                // window longer than 4096 lags is set (ensure_data_b) -- a C/A-only searcher never pays for it
+    // layout B (d_data_b) is allocated, and from then on written by every Sample(), when the first code with a window longer
+    // than 4096 lags is set (ensure_data_b) -- a C/A-only searcher never pays for it
     KG_HIP(hipFuncSetAttribute((const void *) acq_fft_sub_kernel<false>,
                                hipFuncAttributeMaxDynamicSharedMemorySize, 2 * SUB * sizeof(float2)));
     KG_HIP(hipFuncSetAttribute((const void *) acq_fft_sub_kernel<true>,
@@ -1387,21 +1387,11 @@ void kg_acq_destroy(kg_acq *a)
     for (size_t b = 0; b < a->ev_ready.size(); b++) (void) hipEventDestroy(a->ev_ready[b]);
     for (size_t b = 0; b < a->ev_done.size(); b++) (void) hipEventDestroy(a->ev_done[b]);
     if (a->own_fstream) kg_stream_put(a->ctx->device, a->fstream);
-    if (a->own_tabN) (void) hipFree(a->d_tabN);
-    (void) hipFree(a->d_comb); (void) hipFree(a->d_quart); (void) hipFree(a->d_comb8);   // hipFree(nullptr) is a no-op
-    (void) hipFree(a->d_code); (void) hipFree(a->d_data); (void) hipFree(a->d_data_b); (void) hipFree(a->d_td);
-    (void) hipFree(a->d_td_code);
-    (void) hipFree(a->d_fsub); (void) hipFree(a->d_fsub_code);
-    (void) hipFree(a->d_in); (void) hipFree(a->d_chips);
-    for (int k = 0; k < 4; k++) {
-        if (a->h_pin[k]) (void) hipHostFree(a->h_pin[k]);
+    for (int k = 0; k < 4; k++)
         if (a->ev_pin[k]) (void) hipEventDestroy(a->ev_pin[k]);
-    }
-    if (a->h_batch) (void) hipHostFree(a->h_batch);
     if (a->ev_batch) (void) hipEventDestroy(a->ev_batch);
     if (a->ev_in_free) (void) hipEventDestroy(a->ev_in_free);
     if (a->cstream) { (void) hipStreamSynchronize(a->cstream); kg_stream_put(a->ctx->device, a->cstream); }
-    (void) hipFree(a->d_cells); (void) hipFree(a->d_parts); (void) hipFree(a->d_results); (void) hipFree(a->d_claim);
     delete a;
 }
 
@@ -1414,25 +1404,21 @@ static int ensure_data_b(kg_acq *a)
     const size_t n = (size_t) a->fft_len * a->max_blocks;
     KG_HIP(hipStreamSynchronize(a->fstream));
     KG_HIP(hipStreamSynchronize(a->ctx->stream));
-    float2 *d = nullptr;
-    KG_HIP(hipMalloc((void **) &d, sizeof(float2) * n));
+    kg_dbuf<float2> d;                          // published (moved into a->d_data_b) once it holds layout B
+    KG_TRY(d.alloc(n, "kg_acq: layout B of the data spectra"));
     std::vector<float2> pl(a->fft_len), plb, all(n);
     std::vector<float> nat(2 * (size_t) a->fft_len);
-    if (hipMemcpy(all.data(), a->d_data, sizeof(float2) * n, hipMemcpyDeviceToHost) != hipSuccess) {
-        (void) hipFree(d);
-        KG_REQUIRE(false, KG_ERR_HIP, "ensure_data_b: download of the data spectra failed");
-    }
+    KG_REQUIRE(hipMemcpy(all.data(), a->d_data, sizeof(float2) * n, hipMemcpyDeviceToHost) == hipSuccess, KG_ERR_HIP,
+               "ensure_data_b: download of the data spectra failed");
     for (int b = 0; b < a->max_blocks; b++) {
         pl.assign(all.begin() + (size_t) b * a->fft_len, all.begin() + (size_t) (b + 1) * a->fft_len);
         from_planes(pl, nat.data(), a->P, 0, 0);
         to_planes(nat.data(), plb, a->P, 0, 1);
         memcpy(all.data() + (size_t) b * a->fft_len, plb.data(), sizeof(float2) * a->fft_len);
     }
-    if (hipMemcpy(d, all.data(), sizeof(float2) * n, hipMemcpyHostToDevice) != hipSuccess) {
-        (void) hipFree(d);
-        KG_REQUIRE(false, KG_ERR_HIP, "ensure_data_b: upload of layout B failed");
-    }
-    a->d_data_b = d;
+    KG_REQUIRE(hipMemcpy(d, all.data(), sizeof(float2) * n, hipMemcpyHostToDevice) == hipSuccess, KG_ERR_HIP,
+               "ensure_data_b: upload of layout B failed");
+    a->d_data_b.p = d.p; d.p = nullptr;
     return KG_OK;
 }
 
@@ -1479,7 +1465,7 @@ int kg_acq_set_code(kg_acq *a, int sat, const uint8_t *chips, int nchips, int bo
     KG_REQUIRE(nchips >= 1 && nchips <= 8192, KG_ERR_INVALID, "kg_acq_set_code: nchips %d", nchips);
     for (int i = 0; i < nchips; i++)
         KG_REQUIRE(chips[i] <= 1, KG_ERR_INVALID, "kg_acq_set_code: chips[%d] = %d is not 0/1", i, chips[i]);
-    if ((rc = set_limit(a, sat, limit)) != KG_OK) return rc;
+    KG_TRY(set_limit(a, sat, limit));
     KG_HIP(hipMemcpyAsync(a->d_chips, chips, nchips, hipMemcpyHostToDevice, a->ctx->stream));
     // the replica covers all DECIM * N samples, as the reference's covers NSAMPLES (:250)
     float2 *d_sv = a->d_code + (size_t) sat * a->code_len;
@@ -1497,7 +1483,7 @@ int kg_acq_set_code_fft(kg_acq *a, int sat, const float *code_fft, int limit)
     KG_REQUIRE(a && code_fft, KG_ERR_INVALID, "kg_acq_set_code_fft: null argument");
     int rc = kg_ctx_use(a->ctx);
     if (rc) return rc;
-    if ((rc = set_limit(a, sat, limit)) != KG_OK) return rc;
+    KG_TRY(set_limit(a, sat, limit));
     std::vector<float2> pl;
     to_planes(code_fft, pl, a->P, a->halo, a->code_layout[sat]);
     KG_HIP(hipMemcpyAsync(a->d_code + (size_t) sat * a->code_len, pl.data(), sizeof(float2) * a->code_len,
@@ -1556,7 +1542,7 @@ static int stage_host_block(kg_acq *a, uint8_t *d_stage, const void *src, size_t
     if ((bytes & 15) == 0 && bytes >= 65536) {
         const size_t n16 = bytes / 16;
         hipLaunchKernelGGL(acq_stage_copy_kernel, dim3((unsigned) ((n16 + 255) / 256)), dim3(256), 0, a->fstream,
-                           (const uint4 *) a->h_pin[k], (uint4 *) d_stage, n16);
+                           (const uint4 *) a->h_pin[k].p, (uint4 *) d_stage, n16);
         KG_HIP(hipGetLastError());
     } else {
         KG_HIP(hipMemcpyAsync(d_stage, a->h_pin[k], bytes, hipMemcpyHostToDevice, a->fstream));
@@ -1605,7 +1591,7 @@ template <int SRC>
 static int sample_dev(kg_acq *a, int first, int nblocks, const void *d_src, size_t stride)
 {
     int rc;
-    if ((rc = front_begin(a, first, nblocks)) != KG_OK) return rc;
+    KG_TRY(front_begin(a, first, nblocks));
     const size_t off = (size_t) first * a->fft_len;
     rc = launch_frontend<SRC>(a, a->fstream, (const uint8_t *) d_src, stride, nblocks, a->nsamples, 0, 0,
                               a->d_td + off, a->d_fsub + off, a->d_data + off, a->d_data_b ? a->d_data_b + off : nullptr,
@@ -1629,7 +1615,7 @@ int kg_acq_sample_bits(kg_acq *a, int block, const uint8_t *packed)
     if (rc) return rc;
     uint8_t *stage = a->d_in + a->in_stride * block;
     if ((rc = stage_host_block(a, stage, packed, (size_t) a->nsamples / 8))) return rc;
-    if ((rc = sample_dev<SRC_BITS>(a, block, 1, stage, 0)) != KG_OK) return rc;
+    KG_TRY(sample_dev<SRC_BITS>(a, block, 1, stage, 0));
     return staging_consumed(a);
 }
 
@@ -1663,9 +1649,8 @@ int kg_acq_sample_iq16_batch(kg_acq *a, int first, int nblocks, const int16_t *i
     const size_t bytes = a->in_stride * (size_t) nblocks;
     KG_HIP(hipEventSynchronize(a->ev_batch));            // the previous batch has left the pinned region
     if (bytes > a->batch_cap) {
-        if (a->h_batch) KG_HIP(hipHostFree(a->h_batch));
-        a->h_batch = nullptr; a->batch_cap = 0;
-        KG_HIP(hipHostMalloc((void **) &a->h_batch, bytes, hipHostMallocDefault));
+        a->h_batch.reset(); a->batch_cap = 0;
+        KG_TRY(a->h_batch.alloc(bytes, "kg_acq: pinned batch"));
         a->batch_cap = bytes;
     }
     for (int b = 0; b < nblocks; b++)
@@ -1687,7 +1672,7 @@ int kg_acq_sample_iq16(kg_acq *a, int block, const int16_t *iq)
     if (rc) return rc;
     uint8_t *stage = a->d_in + a->in_stride * block;
     if ((rc = stage_host_block(a, stage, iq, a->in_stride))) return rc;
-    if ((rc = sample_dev<SRC_IQ16>(a, block, 1, stage, 0)) != KG_OK) return rc;
+    KG_TRY(sample_dev<SRC_IQ16>(a, block, 1, stage, 0));
     return staging_consumed(a);
 }
 
@@ -1697,7 +1682,7 @@ int kg_acq_set_data_fft(kg_acq *a, int block, const float *data_fft)
     if (rc) return rc;
     std::vector<float2> pl, plb;
     to_planes(data_fft, pl, a->P, 0, 0);
-    if ((rc = front_begin(a, block)) != KG_OK) return rc;
+    KG_TRY(front_begin(a, block));
     KG_HIP(hipMemcpyAsync(a->d_data + (size_t) block * a->fft_len, pl.data(), sizeof(float2) * a->fft_len,
                           hipMemcpyHostToDevice, a->fstream));
     if (a->d_data_b) {
@@ -1705,7 +1690,7 @@ int kg_acq_set_data_fft(kg_acq *a, int block, const float *data_fft)
         KG_HIP(hipMemcpyAsync(a->d_data_b + (size_t) block * a->fft_len, plb.data(), sizeof(float2) * a->fft_len,
                               hipMemcpyHostToDevice, a->fstream));
     }
-    if ((rc = front_end(a, block)) != KG_OK) return rc;
+    KG_TRY(front_end(a, block));
     KG_HIP(hipStreamSynchronize(a->fstream));
     return KG_OK;
 }
@@ -1788,7 +1773,7 @@ int kg_acq_correlate_blocks_async(kg_acq *a, int first, int nblocks, const int *
         a->np1 = (int) tab[0].size(); a->np4 = (int) tab[1].size();
         tab[0].insert(tab[0].end(), tab[1].begin(), tab[1].end());
         void *d = nullptr;
-        if ((rc = kg_ctx_stage(a->ctx, tab[0].data(), sizeof(acq_pair_desc) * tab[0].size(), &d)) != KG_OK) return rc;
+        KG_TRY(kg_ctx_stage(a->ctx, tab[0].data(), sizeof(acq_pair_desc) * tab[0].size(), &d));
         a->d_pairs1 = (const acq_pair_desc *) d;
         a->d_pairs4 = a->d_pairs1 + a->np1;
         a->pairs_seq = a->ctx->ring_next;
@@ -1871,7 +1856,8 @@ int kg_acq_debug_corr_stamps(kg_acq *a, int nblocks, const int *sats, int nsats,
     if (a->np1 == 0 && a->np4 > 0) {                           // an all-E1B list: the 512-thread kernel's stamps
         unsigned long long *d = nullptr;
         const size_t bytes = sizeof(unsigned long long) * (512 + 4 * 1024);
-        KG_HIP(hipMalloc((void **) &d, bytes));
+        kg_scope tmp(a->ctx);
+        KG_TRY(tmp.alloc(&d, 512 + 4 * 1024, "kg_acq_debug_corr_stamps"));
         KG_HIP(hipMemset(d, 0, bytes));
         KG_HIP(hipMemsetAsync(a->d_claim, 0, sizeof(int) * 16 * ACQ_CLAIM_STRIDE, st));
         const acq_walk w = {a->np4, a->ndop, a->dop_lo};
@@ -1894,14 +1880,14 @@ int kg_acq_debug_corr_stamps(kg_acq *a, int nblocks, const int *sats, int nsats,
         KG_HIP(hipMemsetAsync(a->d_claim, 0, sizeof(int) * 16 * ACQ_CLAIM_STRIDE, st));
         KG_HIP(hipStreamSynchronize(st));
         KG_HIP(hipMemcpy(stamps, d, bytes, hipMemcpyDeviceToHost));
-        KG_HIP(hipFree(d));
         return KG_OK;
     }
     KG_REQUIRE(a->np1 > 0, KG_ERR_STATE, "kg_acq_debug_corr_stamps: no C/A SV in the list");
     unsigned long long *d = nullptr;
     const size_t bytes = sizeof(unsigned long long) * (512 + 4 * 1024);
     KG_REQUIRE(a->grid1 <= 1024, KG_ERR_STATE, "kg_acq_debug_corr_stamps: grid %d", a->grid1);
-    KG_HIP(hipMalloc((void **) &d, bytes));
+    kg_scope tmp(a->ctx);
+    KG_TRY(tmp.alloc(&d, 512 + 4 * 1024, "kg_acq_debug_corr_stamps"));
     KG_HIP(hipMemset(d, 0, bytes));
     KG_HIP(hipMemsetAsync(a->d_claim, 0, sizeof(int) * 16 * ACQ_CLAIM_STRIDE, st));
     if (a->P == 4) {
@@ -1917,7 +1903,6 @@ int kg_acq_debug_corr_stamps(kg_acq *a, int nblocks, const int *sats, int nsats,
     KG_HIP(hipMemsetAsync(a->d_claim, 0, sizeof(int) * 16 * ACQ_CLAIM_STRIDE, st));
     KG_HIP(hipStreamSynchronize(st));
     KG_HIP(hipMemcpy(stamps, d, bytes, hipMemcpyDeviceToHost));
-    KG_HIP(hipFree(d));
     return KG_OK;
 }
 
@@ -1928,7 +1913,8 @@ int kg_acq_debug_fft_stamps(kg_acq *a, int block, unsigned long long *stamps, in
     KG_REQUIRE(n >= 4, KG_ERR_INVALID, "kg_acq_debug_fft_stamps: need room for 4 stamps");
     kg_ctx *c = a->ctx;
     unsigned long long *d = nullptr;
-    KG_HIP(hipMalloc((void **) &d, 8 * sizeof(unsigned long long)));
+    kg_scope tmp(c);
+    KG_TRY(tmp.alloc(&d, 8, "kg_acq_debug_fft_stamps"));
     KG_HIP(hipStreamSynchronize(a->fstream));
     for (int rep = 0; rep < 3; rep++) {       // last repetition is the warm one
         hipLaunchKernelGGL(acq_fft_sub_kernel<true>, dim3(a->P, 1), dim3(256), 2 * SUB * sizeof(float2),
@@ -1938,7 +1924,6 @@ int kg_acq_debug_fft_stamps(kg_acq *a, int block, unsigned long long *stamps, in
         KG_HIP(hipStreamSynchronize(c->stream));
     }
     KG_HIP(hipMemcpy(stamps, d, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    KG_HIP(hipFree(d));
     return KG_OK;
 }
 

@@ -21,6 +21,13 @@ void kg_set_error(const char *fmt, ...);
         }                                                                          \
     } while (0)
 
+// A call of the library's own that answers a status: any failure is this function's answer too.
+#define KG_TRY(call)                                                               \
+    do {                                                                           \
+        const int rc_ = (call);                                                    \
+        if (rc_ != KG_OK) return rc_;                                              \
+    } while (0)
+
 #define KG_REQUIRE(cond, status, ...)                                              \
     do {                                                                           \
         if (!(cond)) {                                                             \
@@ -28,6 +35,29 @@ void kg_set_error(const char *fmt, ...);
             return (status);                                                       \
         }                                                                          \
     } while (0)
+
+// Device and pinned memory have ONE door (kg_ctx.hip): nothing else in csrc/ calls hipMalloc, hipHostMalloc, hipFree or
+// hipHostFree.  The door turns hipErrorOutOfMemory into KG_ERR_NOMEM (bytes and `what` in kg_last_error), counts the live
+// allocations (kg_dev_live_allocs) and, under KIWIGPU_TUNING=1, refuses its k-th call for KIWIGPU_FAIL_ALLOC=k.  The four
+// rules of ownership: one door; one owner per buffer (kg_dbuf / kg_hbuf members, freed by `delete`); a
+// grow-on-demand group is released whole, allocated whole and its capacity published last; a host convenience's temporaries
+// belong to a kg_scope.
+__attribute__((visibility("hidden"))) int kg_mem_alloc(void **p, size_t bytes, bool pinned, const char *what);
+__attribute__((visibility("hidden"))) int kg_mem_free(void *p, bool pinned);        // null passes; KG_ERR_HIP for what the runtime will not free
+
+template <typename T, bool PINNED> struct kg_buf {
+    T *p = nullptr;
+    kg_buf() = default;
+    kg_buf(const kg_buf &) = delete;
+    kg_buf &operator=(const kg_buf &) = delete;
+    ~kg_buf() { reset(); }
+    int alloc(size_t n, const char *what) { reset(); return kg_mem_alloc((void **) &p, sizeof(T) * n, PINNED, what); }
+    void reset() { (void) kg_mem_free((void *) p, PINNED); p = nullptr; }
+    operator T *() const { return p; }
+    T *operator->() const { return p; }
+};
+template <typename T> using kg_dbuf = kg_buf<T, false>;      // device memory
+template <typename T> using kg_hbuf = kg_buf<T, true>;       // pinned host memory
 
 // A caller's device pointer (NULL passes: optional buffers) sits at a multiple of `a` bytes, a power of two: the width of the
 // widest load or store a kernel makes through it (include/kiwigpu.h states the rule per entry point).
@@ -94,9 +124,16 @@ int kg_ctx_stage(kg_ctx *ctx, const void *src, size_t bytes, void **d_out);
 // channel map of a batch): the owner keeps a kg_stage_cache; an unchanged table (memcmp with the
 // host copy) costs no transfer at all, a changed one goes through the ring and, in stream order, into
 // the cache's own device buffer (kernels still reading the old contents were enqueued before it).
-struct kg_stage_cache { unsigned char *host; void *dev; size_t cap, bytes; };
-int kg_ctx_stage_cached(kg_ctx *ctx, kg_stage_cache *sc, const void *src, size_t bytes, void **d_out);
+struct kg_stage_cache;
 void kg_stage_cache_free(kg_stage_cache *sc);       // the caller has drained the stream
+struct kg_stage_cache {
+    unsigned char *host = nullptr; void *dev = nullptr; size_t cap = 0, bytes = 0;
+    kg_stage_cache() = default;
+    kg_stage_cache(const kg_stage_cache &) = delete;
+    kg_stage_cache &operator=(const kg_stage_cache &) = delete;
+    ~kg_stage_cache() { kg_stage_cache_free(this); }     // with its owner (whose destroy has drained the stream)
+};
+int kg_ctx_stage_cached(kg_ctx *ctx, kg_stage_cache *sc, const void *src, size_t bytes, void **d_out);
 // The same with `ways` caches looked up in turn and replaced round robin: a caller whose table cycles through a few
 // variants (the frame tables of a streaming waterfall: the slow channel's frame completes every fourth push, so four
 // tables alternate) uploads each of them once.  With one way every push of bench.py's cfg2_chain re-uploaded 64 KiB:
@@ -107,7 +144,32 @@ int kg_ctx_stage_cached_ways(kg_ctx *ctx, kg_stage_cache *sc, int ways, int *vic
 // previous user of the scratch is drained first).  Valid until the next call on this context.
 int kg_ctx_scratch_upload(kg_ctx *ctx, const void *src, size_t bytes, void **d_out);
 
-// The library's tuning switches (KIWIGPU_DDC_RUNS, KIWIGPU_DDC_SIDE, KIWIGPU_DDC_STAGED, KIWIGPU_RXDDC_RUNS,
+// The device temporaries of a host convenience (kg_pos_solve, kg_trk_process_bits ...): lent by alloc(), and freed by the
+// destructor AFTER it has drained the stream -- the caller's host arrays and the temporaries are in use until then, on the
+// failing paths too.
+struct kg_scope {
+    hipStream_t stream;
+    void *lent[4] = {nullptr, nullptr, nullptr, nullptr};
+    int n = 0;
+    explicit kg_scope(const kg_ctx *c) : stream(c->stream) {}
+    kg_scope(const kg_scope &) = delete;
+    kg_scope &operator=(const kg_scope &) = delete;
+    ~kg_scope()
+    {
+        (void) hipStreamSynchronize(stream);
+        while (n > 0) (void) kg_mem_free(lent[--n], false);
+    }
+    template <typename T> int alloc(T **p, size_t count, const char *what)
+    {
+        *p = nullptr;
+        KG_REQUIRE(n < 4, KG_ERR_STATE, "kg_scope: more than 4 temporaries (%s)", what);
+        KG_TRY(kg_mem_alloc(&lent[n], sizeof(T) * count, false, what));
+        *p = (T *) lent[n++];
+        return KG_OK;
+    }
+};
+
+// The library's tuning switches (KIWIGPU_FAIL_ALLOC, KIWIGPU_DDC_RUNS, KIWIGPU_DDC_SIDE, KIWIGPU_DDC_STAGED, KIWIGPU_RXDDC_RUNS,
 // KIWIGPU_WF_WGS_PER_CU, KIWIGPU_ACQ_WGS_PER_CU, KIWIGPU_ACQ_FRONT_STREAM) are A/B aids: they are read
 // ONLY when KIWIGPU_TUNING=1 is set too -- a stray variable in a host's environment does not change what the library does.
 static inline const char *kg_tuning_env(const char *name)
@@ -168,7 +230,7 @@ void kg_stream_put(int device, hipStream_t s);
 // kg_nb.hip, for kg_wf.hip (not part of the ABI): a set of CNoiseProc states on the device (kg_nb.h), one per channel, and the
 // waterfall's blanker pre-pass over them.
 struct kg_nb_store;
-__attribute__((visibility("hidden"))) int kg_nb_store_create(int nchan, kg_nb_store **out);   // *out is set even on failure (destroy it)
+__attribute__((visibility("hidden"))) int kg_nb_store_create(int nchan, kg_nb_store **out);
 __attribute__((visibility("hidden"))) void kg_nb_store_destroy(kg_nb_store *s);                // the caller has drained the stream
 __attribute__((visibility("hidden"))) int kg_nb_store_was_setup(const kg_nb_store *s, int ch);
 // SetupBlanker(ch, sample_rate, nb_param) in stream order (refusals as kg_nb_setup's, messages under `who`)

@@ -3,6 +3,9 @@
 
 #include <math.h>
 #include <stdlib.h>
+#include <atomic>
+#include <mutex>
+#include <string>
 #include <vector>
 
 static thread_local char g_err[512] = "";
@@ -15,15 +18,51 @@ void kg_set_error(const char *fmt, ...)
     va_end(ap);
 }
 
+// The one door for device and pinned memory (kg_common.h).
+static std::atomic<int64_t> g_live_allocs(0);
+static std::mutex g_fail_mutex;
+static std::string g_fail_value;             // KIWIGPU_FAIL_ALLOC as last seen, and the door's calls since it took that value
+static long g_fail_calls = 0;
+
+static bool mem_alloc_refused(void)
+{
+    const char *v = kg_tuning_env("KIWIGPU_FAIL_ALLOC");
+    std::lock_guard<std::mutex> lk(g_fail_mutex);
+    if (!v) { g_fail_value.clear(); g_fail_calls = 0; return false; }
+    if (g_fail_value != v) { g_fail_value = v; g_fail_calls = 0; }
+    return ++g_fail_calls == atol(v);
+}
+
+int kg_mem_alloc(void **p, size_t bytes, bool pinned, const char *what)
+{
+    *p = nullptr;
+    const char *kind = pinned ? "pinned host" : "device";
+    KG_REQUIRE(!mem_alloc_refused(), KG_ERR_NOMEM, "%s: %zu bytes of %s memory refused by KIWIGPU_FAIL_ALLOC", what, bytes, kind);
+    const hipError_t e = pinned ? hipHostMalloc(p, bytes, hipHostMallocDefault) : hipMalloc(p, bytes);
+    if (e != hipSuccess) *p = nullptr;
+    KG_REQUIRE(e != hipErrorOutOfMemory, KG_ERR_NOMEM, "%s: out of %s memory (%zu bytes)", what, kind, bytes);
+    KG_HIP(e);
+    g_live_allocs++;
+    return KG_OK;
+}
+
+int kg_mem_free(void *p, bool pinned)
+{
+    if (!p) return KG_OK;
+    KG_HIP(pinned ? hipHostFree(p) : hipFree(p));
+    g_live_allocs--;
+    return KG_OK;
+}
+
 int kg_ctx_scratch_upload(kg_ctx *c, const void *src, size_t bytes, void **d_out)
 {
     KG_REQUIRE(c && src && d_out && bytes > 0, KG_ERR_INVALID, "kg_ctx_scratch_upload: bad argument");
     KG_HIP(hipStreamSynchronize(c->stream));
     if (bytes > c->scratch_bytes) {
-        if (c->d_scratch) KG_HIP(hipFree(c->d_scratch));
+        (void) kg_mem_free(c->d_scratch, false);
         c->d_scratch = nullptr; c->scratch_bytes = 0;
         const size_t cap = bytes < 4096 ? 4096 : bytes;
-        KG_HIP(hipMalloc(&c->d_scratch, cap));
+        KG_TRY(kg_mem_alloc(&c->d_scratch, cap, false, "kg_ctx_scratch_upload"));
         c->scratch_bytes = cap;
     }
     KG_HIP(hipMemcpy(c->d_scratch, src, bytes, hipMemcpyHostToDevice));
@@ -50,16 +89,33 @@ static int arena_stage(kg_arena *a, const void *src, size_t bytes, void **d_out)
     return KG_OK;
 }
 
+// The staging ring: whole or absent.  h_ring, which the callers test, is set once the device ring and every event exist.
+static void ring_destroy(kg_ctx *c)
+{
+    (void) kg_mem_free(c->h_ring, true); (void) kg_mem_free(c->d_ring, false);
+    c->h_ring = c->d_ring = nullptr;
+    for (int i = 0; i < KG_RING_SLOTS; i++) {
+        if (c->ring_ev[i]) (void) hipEventDestroy(c->ring_ev[i]);
+        c->ring_ev[i] = nullptr;
+    }
+}
+
+static int ring_create(kg_ctx *c)
+{
+    KG_TRY(kg_mem_alloc((void **) &c->d_ring, KG_RING_SLOTS * KG_RING_SLOT_BYTES, false, "staging ring"));
+    for (int i = 0; i < KG_RING_SLOTS; i++) KG_HIP(hipEventCreateWithFlags(&c->ring_ev[i], hipEventDisableTiming));
+    c->ring_next = 0;
+    return kg_mem_alloc((void **) &c->h_ring, KG_RING_SLOTS * KG_RING_SLOT_BYTES, true, "staging ring");
+}
+
 int kg_ctx_stage(kg_ctx *c, const void *src, size_t bytes, void **d_out)
 {
     KG_REQUIRE(c && src && d_out && bytes > 0, KG_ERR_INVALID, "kg_ctx_stage: bad argument");
     if (c->arena && c->arena->mode != KG_ARENA_OFF) return arena_stage(c->arena, src, bytes, d_out);
     if (bytes > KG_RING_SLOT_BYTES) return kg_ctx_scratch_upload(c, src, bytes, d_out);
     if (!c->h_ring) {
-        KG_HIP(hipHostMalloc((void **) &c->h_ring, KG_RING_SLOTS * KG_RING_SLOT_BYTES, hipHostMallocDefault));
-        KG_HIP(hipMalloc((void **) &c->d_ring, KG_RING_SLOTS * KG_RING_SLOT_BYTES));
-        for (int i = 0; i < KG_RING_SLOTS; i++) KG_HIP(hipEventCreateWithFlags(&c->ring_ev[i], hipEventDisableTiming));
-        c->ring_next = 0;
+        const int rc = ring_create(c);
+        if (rc) { ring_destroy(c); return rc; }
     }
     const unsigned long j = c->ring_next++;
     const int slot = (int) (j % KG_RING_SLOTS);
@@ -82,13 +138,12 @@ int kg_ctx_stage_cached(kg_ctx *c, kg_stage_cache *sc, const void *src, size_t b
     if (sc->dev && sc->bytes == bytes && memcmp(sc->host, src, bytes) == 0) { *d_out = sc->dev; return KG_OK; }
     if (bytes > sc->cap) {                      // grows rarely: drain, then replace both copies
         KG_HIP(hipStreamSynchronize(c->stream));
-        if (sc->dev) KG_HIP(hipFree(sc->dev));
-        free(sc->host);
-        sc->dev = nullptr; sc->host = nullptr; sc->cap = sc->bytes = 0;
+        kg_stage_cache_free(sc);
         const size_t cap = bytes < 4096 ? 4096 : bytes + bytes / 2;
         sc->host = (unsigned char *) malloc(cap);
         KG_REQUIRE(sc->host != nullptr, KG_ERR_NOMEM, "kg_ctx_stage_cached: %zu host bytes", cap);
-        KG_HIP(hipMalloc(&sc->dev, cap));
+        const int rc = kg_mem_alloc(&sc->dev, cap, false, "kg_ctx_stage_cached");
+        if (rc) { kg_stage_cache_free(sc); return rc; }
         sc->cap = cap;
     }
     void *d = nullptr;
@@ -115,12 +170,11 @@ int kg_ctx_stage_cached_ways(kg_ctx *c, kg_stage_cache *sc, int ways, int *victi
 void kg_stage_cache_free(kg_stage_cache *sc)
 {
     if (!sc) return;
-    if (sc->dev) (void) hipFree(sc->dev);
+    (void) kg_mem_free(sc->dev, false);
     free(sc->host);
     sc->dev = nullptr; sc->host = nullptr; sc->cap = sc->bytes = 0;
 }
 
-#include <mutex>
 static std::mutex g_stream_mutex;
 static std::vector<std::pair<int, hipStream_t>> g_stream_pool;
 
@@ -170,6 +224,8 @@ const char *kg_last_error(void) { return g_err; }
 
 int kg_abi_version(void) { return KG_ABI_VERSION; }
 
+int64_t kg_dev_live_allocs(void) { return g_live_allocs.load(); }
+
 void kg_nco_table_build(short *tab)
 {
     for (int j = 0; j < 8192; j++) tab[j] = (short) lrint(16383.0 * sin(2.0 * M_PI * j / 8192.0));
@@ -211,9 +267,24 @@ static int make_table(float2 **d, int n)
     h[n / 4] = make_float2(0.f, 1.f);
     h[n / 2] = make_float2(-1.f, 0.f);
     h[3 * n / 4] = make_float2(0.f, -1.f);
-    KG_HIP(hipMalloc((void **) d, sizeof(float2) * n));
+    KG_TRY(kg_mem_alloc((void **) d, sizeof(float2) * n, false, "kg_ctx_create: twiddle table"));
     KG_HIP(hipMemcpy(*d, h.data(), sizeof(float2) * n, hipMemcpyHostToDevice));
     return KG_OK;
+}
+
+static int ctx_init(kg_ctx *c, void *stream, bool use_given)
+{
+    if (use_given) {
+        c->stream = (hipStream_t) stream;
+    } else {
+        KG_TRY(kg_stream_get(c->device, &c->stream));
+        c->own_stream = true;
+    }
+    KG_HIP(hipEventCreate(&c->ev_start));
+    KG_HIP(hipEventCreate(&c->ev_stop));
+    KG_TRY(make_table(&c->d_tab4096, 4096));
+    KG_TRY(make_table(&c->d_tab16384, 16384));
+    return make_table(&c->d_tab8192, 8192);
 }
 
 static int ctx_create(int device, void *stream, bool use_given, kg_ctx **out)
@@ -242,19 +313,8 @@ static int ctx_create(int device, void *stream, bool use_given, kg_ctx **out)
     c->device = device;
     c->num_cus = prop.multiProcessorCount;
     snprintf(c->name, sizeof c->name, "%s (%s)", prop.name, prop.gcnArchName);
-    if (use_given) {
-        c->stream = (hipStream_t) stream;
-        c->own_stream = false;
-    } else {
-        { const int rc_ = kg_stream_get(device, &c->stream); if (rc_) { free(c); return rc_; } }
-        c->own_stream = true;
-    }
-    KG_HIP(hipEventCreate(&c->ev_start));
-    KG_HIP(hipEventCreate(&c->ev_stop));
-    int rc;
-    if ((rc = make_table(&c->d_tab4096, 4096)) != KG_OK) { kg_ctx_destroy(c); return rc; }
-    if ((rc = make_table(&c->d_tab16384, 16384)) != KG_OK) { kg_ctx_destroy(c); return rc; }
-    if ((rc = make_table(&c->d_tab8192, 8192)) != KG_OK) { kg_ctx_destroy(c); return rc; }
+    const int rc = ctx_init(c, stream, use_given);
+    if (rc) { kg_ctx_destroy(c); return rc; }
     *out = c;
     return KG_OK;
 }
@@ -274,16 +334,13 @@ void kg_ctx_destroy(kg_ctx *c)
     if (!c) return;
     (void) hipSetDevice(c->device);
     (void) hipStreamSynchronize(c->stream);
-    (void) hipFree(c->d_tab4096);
-    (void) hipFree(c->d_tab16384);
-    (void) hipFree(c->d_tab8192);
-    if (c->d_scratch) (void) hipFree(c->d_scratch);
-    if (c->h_ring) {
-        (void) hipHostFree(c->h_ring); (void) hipFree(c->d_ring);
-        for (int i = 0; i < KG_RING_SLOTS; i++) (void) hipEventDestroy(c->ring_ev[i]);
-    }
-    (void) hipEventDestroy(c->ev_start);
-    (void) hipEventDestroy(c->ev_stop);
+    (void) kg_mem_free(c->d_tab4096, false);
+    (void) kg_mem_free(c->d_tab16384, false);
+    (void) kg_mem_free(c->d_tab8192, false);
+    (void) kg_mem_free(c->d_scratch, false);
+    ring_destroy(c);
+    if (c->ev_start) (void) hipEventDestroy(c->ev_start);
+    if (c->ev_stop) (void) hipEventDestroy(c->ev_stop);
     if (c->own_stream) kg_stream_put(c->device, c->stream);
     free(c);
 }
@@ -324,10 +381,7 @@ int kg_dev_alloc(kg_ctx *c, size_t bytes, void **out)
     if (rc) return rc;
     KG_REQUIRE(out != nullptr && bytes > 0, KG_ERR_INVALID, "kg_dev_alloc: bad argument");
     *out = nullptr;
-    hipError_t e = hipMalloc(out, bytes);
-    if (e == hipErrorOutOfMemory) { kg_set_error("kg_dev_alloc: out of device memory (%zu bytes)", bytes); return KG_ERR_NOMEM; }
-    KG_HIP(e);
-    return KG_OK;
+    return kg_mem_alloc(out, bytes, false, "kg_dev_alloc");
 }
 
 int kg_dev_free(kg_ctx *c, void *p)
@@ -335,8 +389,7 @@ int kg_dev_free(kg_ctx *c, void *p)
     int rc = kg_ctx_use(c);
     if (rc) return rc;
     KG_HIP(hipStreamSynchronize(c->stream));
-    KG_HIP(hipFree(p));
-    return KG_OK;
+    return kg_mem_free(p, false);
 }
 
 int kg_dev_upload(kg_ctx *c, void *dst, const void *src, size_t bytes)

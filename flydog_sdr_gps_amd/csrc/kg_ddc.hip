@@ -1142,12 +1142,12 @@ struct kg_ddc {
     kg_ctx *ctx;
     int nchan;
     long max_samples;
-    ddc_chan *d_chans;
+    kg_dbuf<ddc_chan> d_chans;
     std::vector<ddc_chan> h_chans;            // host mirror of the scalar fields
-    u32 *d_nco;
+    kg_dbuf<u32> d_nco;
     // Buffers a push's run passes fill and its output stage (run-total prefix, combs, finish) drains: TWO sets, used in
     // turn, so that push k + 1's run passes may overwrite nothing push k's output stage still reads (deferred mode).
-    ddc_state4 *d_local[2]; u32 *d_c0rel[2], *d_tau[2], *d_hist;
+    kg_dbuf<ddc_state4> d_local[2]; kg_dbuf<u32> d_c0rel[2], d_tau[2], d_hist;
     int max_runs; long c0_cap[2];
     hipStream_t side; hipEvent_t ev_fork, ev_join;                   // pass B of the small decimations beside the rest
     bool side_borrowed;                                              // `side` is the owner's (a receiver bank's): not destroyed here
@@ -1165,9 +1165,9 @@ struct kg_ddc {
     bool tail_unjoined;                        // the context's stream has not yet been made to wait for the last output stage
     int parity;                                // buffer set of the NEXT push
     void *after_ev;                            // kg_ddc_wf_tail_after: the next push's writers of the caller's rows wait for it
-    ddc_endco *d_endco; long endco_n; int endco_L, endco_runs;      // end-distance coefficients of the last (n, L, nruns)
-    ddc_state4 *d_wgtot[2], *d_wgbase[2];     // [nchan][2][DDC_MAX_GX] per buffer set: pass A's workgroup totals, pass B's workgroup bases
-    u32 *d_wgtau[2];                           // likewise: the integrator-5 totals of pass B's workgroups, then their start values
+    kg_dbuf<ddc_endco> d_endco; long endco_n; int endco_L, endco_runs;      // end-distance coefficients of the last (n, L, nruns)
+    kg_dbuf<ddc_state4> d_wgtot[2], d_wgbase[2];   // [nchan][2][DDC_MAX_GX] per buffer set: pass A's workgroup totals, pass B's workgroup bases
+    kg_dbuf<u32> d_wgtau[2];                   // likewise: the integrator-5 totals of pass B's workgroups, then their start values
 };
 
 static const int DDC_RUN_MIN = 64, DDC_RUN_MAX = 8192, DDC_TARGET_RUNS = 8192;
@@ -1189,6 +1189,43 @@ int kg_ddc_use_side_stream(kg_ddc *d, hipStream_t s)
     return KG_OK;
 }
 
+static int ddc_init(kg_ddc *d)
+{
+    const int nchan = d->nchan;
+    const size_t max_samples = (size_t) d->max_samples;
+    d->h_chans.assign(nchan, ddc_chan());
+    for (auto &c : d->h_chans) memset(&c, 0, sizeof c);
+    d->max_runs = (int) ((max_samples + DDC_RUN_MIN - 1) / DDC_RUN_MIN);
+    if (d->max_runs > DDC_TARGET_RUNS * 2) d->max_runs = DDC_TARGET_RUNS * 2;
+    d->c0_cap[0] = d->c0_cap[1] = 0;
+    d->h_pushed.assign(nchan, 0);
+    d->h_stale.assign(nchan, 0);
+    d->deferred = false; d->tail = nullptr; d->tail_rec[0] = d->tail_rec[1] = false; d->tail_unjoined = false;
+    d->parity = 0; d->after_ev = nullptr;
+    KG_TRY(d->d_chans.alloc(nchan, "kg_ddc_create: channels"));
+    KG_HIP(hipMemset(d->d_chans, 0, sizeof(ddc_chan) * nchan));
+    KG_TRY(d->d_nco.alloc(sizeof(short) * DDC_TAB / sizeof(u32), "kg_ddc_create: NCO table"));
+    KG_HIP(hipFuncSetAttribute((const void *) ddc_wf_run_kernel<true, DDC_ALL>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               DDC_STAGE_BYTES));
+    for (int p = 0; p < 2; p++) {
+        KG_TRY(d->d_local[p].alloc(2 * (size_t) nchan * d->max_runs, "kg_ddc_create: run states"));
+        KG_TRY(d->d_tau[p].alloc(2 * (size_t) nchan * d->max_runs, "kg_ddc_create: run totals"));
+    }
+    KG_TRY(d->d_hist.alloc(10 * (size_t) nchan, "kg_ddc_create: histories"));
+    KG_TRY(d->d_endco.alloc((size_t) d->max_runs + 1, "kg_ddc_create: end coefficients"));
+    for (int p = 0; p < 2; p++) {
+        KG_TRY(d->d_wgtot[p].alloc(2 * (size_t) nchan * DDC_MAX_GX, "kg_ddc_create: workgroup totals"));
+        KG_TRY(d->d_wgbase[p].alloc(2 * (size_t) nchan * DDC_MAX_GX, "kg_ddc_create: workgroup bases"));
+        KG_TRY(d->d_wgtau[p].alloc(2 * (size_t) nchan * DDC_MAX_GX, "kg_ddc_create: workgroup totals"));
+    }
+    d->endco_n = -1; d->endco_L = 0; d->endco_runs = 0;
+    // NCO table: ONE 16-bit sine table, sin(a) = T[a], cos(a) = T[a + 2048] (kg_common.h, kg_nco_table_build)
+    std::vector<short> tab(DDC_TAB);
+    kg_nco_table_build(tab.data());
+    KG_HIP(hipMemcpy(d->d_nco, tab.data(), sizeof(short) * DDC_TAB, hipMemcpyHostToDevice));
+    return KG_OK;
+}
+
 extern "C" {
 
 int kg_ddc_create(kg_ctx *ctx, int nchan, size_t max_samples, kg_ddc **out)
@@ -1203,39 +1240,12 @@ int kg_ddc_create(kg_ctx *ctx, int nchan, size_t max_samples, kg_ddc **out)
     kg_ddc *d = new (std::nothrow) kg_ddc();
     KG_REQUIRE(d != nullptr, KG_ERR_NOMEM, "kg_ddc_create: alloc");
     d->ctx = ctx; d->nchan = nchan; d->max_samples = (long) max_samples;
-    d->h_chans.assign(nchan, ddc_chan());
-    for (auto &c : d->h_chans) memset(&c, 0, sizeof c);
-    d->max_runs = (int) ((max_samples + DDC_RUN_MIN - 1) / DDC_RUN_MIN);
-    if (d->max_runs > DDC_TARGET_RUNS * 2) d->max_runs = DDC_TARGET_RUNS * 2;
-    d->c0_cap[0] = d->c0_cap[1] = 0; d->d_c0rel[0] = d->d_c0rel[1] = nullptr;
-    d->h_pushed.assign(nchan, 0);
-    d->h_stale.assign(nchan, 0);
-    d->deferred = false; d->tail = nullptr; d->tail_rec[0] = d->tail_rec[1] = false; d->tail_unjoined = false;
-    d->parity = 0; d->after_ev = nullptr;
-    KG_HIP(hipMalloc((void **) &d->d_chans, sizeof(ddc_chan) * nchan));
-    KG_HIP(hipMemset(d->d_chans, 0, sizeof(ddc_chan) * nchan));
-    KG_HIP(hipMalloc((void **) &d->d_nco, sizeof(short) * DDC_TAB));
-    KG_HIP(hipFuncSetAttribute((const void *) ddc_wf_run_kernel<true, DDC_ALL>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               DDC_STAGE_BYTES));
-    for (int p = 0; p < 2; p++) {
-        KG_HIP(hipMalloc((void **) &d->d_local[p], sizeof(ddc_state4) * 2 * (size_t) nchan * d->max_runs));
-        KG_HIP(hipMalloc((void **) &d->d_tau[p], sizeof(u32) * 2 * (size_t) nchan * d->max_runs));
-    }
-    KG_HIP(hipMalloc((void **) &d->d_hist, sizeof(u32) * 10 * (size_t) nchan));
-    KG_HIP(hipMalloc((void **) &d->d_endco, sizeof(ddc_endco) * ((size_t) d->max_runs + 1)));
-    for (int p = 0; p < 2; p++) {
-        KG_HIP(hipMalloc((void **) &d->d_wgtot[p], sizeof(ddc_state4) * 2 * (size_t) nchan * DDC_MAX_GX));
-        KG_HIP(hipMalloc((void **) &d->d_wgbase[p], sizeof(ddc_state4) * 2 * (size_t) nchan * DDC_MAX_GX));
-        KG_HIP(hipMalloc((void **) &d->d_wgtau[p], sizeof(u32) * 2 * (size_t) nchan * DDC_MAX_GX));
-    }
-    d->endco_n = -1; d->endco_L = 0; d->endco_runs = 0;
-    // NCO table: ONE 16-bit sine table, sin(a) = T[a], cos(a) = T[a + 2048] (kg_common.h, kg_nco_table_build)
-    std::vector<short> tab(DDC_TAB);
-    kg_nco_table_build(tab.data());
-    KG_HIP(hipMemcpy(d->d_nco, tab.data(), sizeof(short) * DDC_TAB, hipMemcpyHostToDevice));
+    rc = ddc_init(d);
+    if (rc) { kg_ddc_destroy(d); return rc; }
     *out = d;
     return KG_OK;
 }
+
 
 void kg_ddc_destroy(kg_ddc *d)
 {
@@ -1244,18 +1254,10 @@ void kg_ddc_destroy(kg_ddc *d)
     (void) hipStreamSynchronize(d->ctx->stream);
     if (d->side) (void) hipStreamSynchronize(d->side);
     if (d->tail) (void) hipStreamSynchronize(d->tail);
-    (void) hipFree(d->d_chans); (void) hipFree(d->d_nco);
-    for (int p = 0; p < 2; p++) { (void) hipFree(d->d_local[p]); (void) hipFree(d->d_tau[p]); (void) hipFree(d->d_c0rel[p]); }
-    (void) hipFree(d->d_hist);
-    (void) hipFree(d->d_endco);
-    for (int p = 0; p < 2; p++) { (void) hipFree(d->d_wgtot[p]); (void) hipFree(d->d_wgbase[p]); (void) hipFree(d->d_wgtau[p]); }
-    kg_stage_cache_free(&d->pack_cache);
-    if (d->side) { (void) hipEventDestroy(d->ev_fork); (void) hipEventDestroy(d->ev_join); if (!d->side_borrowed) kg_stream_put(d->ctx->device, d->side); }
-    if (d->tail) {
-        (void) hipEventDestroy(d->ev_runs); (void) hipEventDestroy(d->ev_tail[0]); (void) hipEventDestroy(d->ev_tail[1]);
-        (void) hipEventDestroy(d->ev_adc);
-        kg_stream_put(d->ctx->device, d->tail);
-    }
+    for (hipEvent_t e : {d->ev_fork, d->ev_join, d->ev_runs, d->ev_tail[0], d->ev_tail[1], d->ev_adc})
+        if (e) (void) hipEventDestroy(e);
+    if (d->side && !d->side_borrowed) kg_stream_put(d->ctx->device, d->side);
+    kg_stream_put(d->ctx->device, d->tail);       // null passes
     delete d;
 }
 
@@ -1521,9 +1523,8 @@ static int ddc_push_impl(kg_ddc *d, const void *d_adc, size_t n, const int32_t *
     }
     if (c0_need > d->c0_cap[par]) {
         if ((rc = ddc_sync_all(d))) return rc;
-        (void) hipFree(d->d_c0rel[par]);
-        d->d_c0rel[par] = nullptr; d->c0_cap[par] = 0;  // nothing dangles if the allocation below fails
-        KG_HIP(hipMalloc((void **) &d->d_c0rel[par], sizeof(u32) * (size_t) (c0_need + 16)));
+        d->d_c0rel[par].reset(); d->c0_cap[par] = 0;    // nothing dangles if the allocation below fails
+        KG_TRY(d->d_c0rel[par].alloc((size_t) (c0_need + 16), "kg_ddc_wf_push_dev: comb inputs"));
         d->c0_cap[par] = c0_need;
     }
     ddc_state4 *const d_local = d->d_local[par];
@@ -1603,7 +1604,7 @@ static int ddc_push_impl(kg_ddc *d, const void *d_adc, size_t n, const int32_t *
     if (const char *e = kg_tuning_env("KIWIGPU_DDC_SIDE")) side_on = atoi(e) != 0;
     auto side_ready = [&]() -> int {
         if (!d->side) {
-            { const int rc_ = kg_stream_get(d->ctx->device, &d->side); if (rc_) return rc_; }
+            KG_TRY(kg_stream_get(d->ctx->device, &d->side));
             KG_HIP(hipEventCreateWithFlags(&d->ev_fork, hipEventDisableTiming));
             KG_HIP(hipEventCreateWithFlags(&d->ev_join, hipEventDisableTiming));
         }

@@ -107,8 +107,8 @@ struct kg_eph {
     kg_ctx *ctx;
     int nchan;
     std::vector<int> sat;               // the host's mirror of the bindings (-1: none)
-    eph_state *d_st;
-    upd *d_ws;                          // the field kernel's answers, ws_cap per channel
+    kg_dbuf<eph_state> d_st;
+    kg_dbuf<upd> d_ws;                          // the field kernel's answers, ws_cap per channel
     int ws_cap;
 };
 
@@ -117,11 +117,21 @@ static int eph_reserve(kg_eph *v, int cap)
 {
     if (cap <= v->ws_cap) return KG_OK;
     KG_HIP(hipStreamSynchronize(v->ctx->stream));                       // kernels of earlier pushes still use the old one
-    (void) hipFree(v->d_ws);
-    v->d_ws = nullptr; v->ws_cap = 0;
+    v->d_ws.reset(); v->ws_cap = 0;
     const int c = (cap + 63) & ~63;
-    KG_HIP(hipMalloc((void **) &v->d_ws, sizeof(upd) * (size_t) c * v->nchan));
+    KG_TRY(v->d_ws.alloc((size_t) c * v->nchan, "kg_eph: workspace"));
     v->ws_cap = c;
+    return KG_OK;
+}
+
+static int eph_init(kg_eph *v)
+{
+    v->sat.assign(v->nchan, -1);
+    int rc = v->d_st.alloc(1, "kg_eph_create: state");
+    if (rc) return rc;
+    hipLaunchKernelGGL(eph_zero_kernel, dim3(1), dim3(256), 0, v->ctx->stream, v->d_st.p);
+    KG_TRY(eph_reserve(v, 64));
+    KG_REQUIRE(hipGetLastError() == hipSuccess, KG_ERR_HIP, "kg_eph_create: launch failed");
     return KG_OK;
 }
 
@@ -137,20 +147,8 @@ int kg_eph_create(kg_ctx *ctx, int nchan, kg_eph **out)
     kg_eph *v = new (std::nothrow) kg_eph();
     KG_REQUIRE(v != nullptr, KG_ERR_NOMEM, "kg_eph_create: alloc");
     v->ctx = ctx; v->nchan = nchan;
-    v->sat.assign(nchan, -1);
-    v->d_st = nullptr; v->d_ws = nullptr; v->ws_cap = 0;
-    hipError_t e = hipMalloc((void **) &v->d_st, sizeof(eph_state));
-    if (e != hipSuccess) {
-        delete v;
-        KG_HIP(e);
-    }
-    hipLaunchKernelGGL(eph_zero_kernel, dim3(1), dim3(256), 0, ctx->stream, v->d_st);
-    rc = eph_reserve(v, 64);
-    if (rc == KG_OK && hipGetLastError() != hipSuccess) { kg_set_error("kg_eph_create: launch failed"); rc = KG_ERR_HIP; }
-    if (rc) {
-        kg_eph_destroy(v);
-        return rc;
-    }
+    rc = eph_init(v);
+    if (rc) { kg_eph_destroy(v); return rc; }
     *out = v;
     return KG_OK;
 }
@@ -160,8 +158,6 @@ void kg_eph_destroy(kg_eph *v)
     if (!v) return;
     (void) hipSetDevice(v->ctx->device);
     (void) hipStreamSynchronize(v->ctx->stream);
-    (void) hipFree(v->d_st);
-    (void) hipFree(v->d_ws);
     delete v;
 }
 
@@ -241,21 +237,17 @@ int kg_eph_push_frames(kg_eph *v, const kg_nav_frame *frames, size_t frame_strid
     kg_eph_note *d_no = nullptr;
     int32_t *d_cnt = nullptr;
     hipStream_t s = v->ctx->stream;
-    hipError_t e = hipMalloc((void **) &d_fr, sizeof(kg_nav_frame) * fs * rows);
-    if (e == hipSuccess) e = hipMalloc((void **) &d_no, sizeof(kg_eph_note) * ns * rows);
-    if (e == hipSuccess) e = hipMalloc((void **) &d_cnt, sizeof(int32_t) * rows);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_cnt, n.data(), sizeof(int32_t) * rows, hipMemcpyHostToDevice, s);
-    for (int ch = 0; ch < v->nchan && e == hipSuccess; ch++)
-        if (n[ch]) e = hipMemcpyAsync(d_fr + (size_t) ch * fs, frames + (size_t) ch * frame_stride, sizeof(kg_nav_frame) * n[ch], hipMemcpyHostToDevice, s);
-    rc = KG_OK;
-    if (e == hipSuccess) rc = kg_eph_push_frames_dev(v, d_fr, fs, d_cnt, cap, d_no, ns);
-    for (int ch = 0; ch < v->nchan && e == hipSuccess && rc == KG_OK; ch++)
-        if (n[ch]) e = hipMemcpyAsync(notes + (size_t) ch * note_stride, d_no + (size_t) ch * ns, sizeof(kg_eph_note) * n[ch], hipMemcpyDeviceToHost, s);
-    (void) hipStreamSynchronize(s);                     // n[] and the device buffers are in use until here
-    (void) hipFree(d_fr); (void) hipFree(d_no); (void) hipFree(d_cnt);
-    if (rc) return rc;
-    KG_HIP(e);
-    return KG_OK;
+    kg_scope tmp(v->ctx);                               // n[] and the device buffers are in use until it has drained the stream
+    KG_TRY(tmp.alloc(&d_fr, fs * rows, "kg_eph_push_frames: frames"));
+    KG_TRY(tmp.alloc(&d_no, ns * rows, "kg_eph_push_frames: notes"));
+    KG_TRY(tmp.alloc(&d_cnt, rows, "kg_eph_push_frames: counts"));
+    KG_HIP(hipMemcpyAsync(d_cnt, n.data(), sizeof(int32_t) * rows, hipMemcpyHostToDevice, s));
+    for (int ch = 0; ch < v->nchan; ch++)
+        if (n[ch]) KG_HIP(hipMemcpyAsync(d_fr + (size_t) ch * fs, frames + (size_t) ch * frame_stride, sizeof(kg_nav_frame) * n[ch], hipMemcpyHostToDevice, s));
+    KG_TRY(kg_eph_push_frames_dev(v, d_fr, fs, d_cnt, cap, d_no, ns));
+    for (int ch = 0; ch < v->nchan; ch++)
+        if (n[ch]) KG_HIP(hipMemcpyAsync(notes + (size_t) ch * note_stride, d_no + (size_t) ch * ns, sizeof(kg_eph_note) * n[ch], hipMemcpyDeviceToHost, s));
+    return KG_OK;                                       // tmp drains the stream: `notes` is filled when the caller sees it
 }
 
 int kg_eph_get(kg_eph *v, int sat, kg_ephem *out)
@@ -318,18 +310,14 @@ int kg_eph_sv(kg_eph *v, const kg_eph_snap *snaps, int nsnap, kg_eph_pos *out)
     kg_eph_snap *d_in = nullptr;
     kg_eph_pos *d_o = nullptr;
     hipStream_t s = v->ctx->stream;
-    hipError_t e = hipMalloc((void **) &d_in, sizeof(kg_eph_snap) * nsnap);
-    if (e == hipSuccess) e = hipMalloc((void **) &d_o, sizeof(kg_eph_pos) * nsnap);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_in, snaps, sizeof(kg_eph_snap) * nsnap, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_o, out, sizeof(kg_eph_pos) * nsnap, hipMemcpyHostToDevice, s);      // a refused snapshot keeps its row's values
-    rc = KG_OK;
-    if (e == hipSuccess) rc = kg_eph_sv_dev(v, d_in, nsnap, d_o);
-    if (e == hipSuccess && rc == KG_OK) e = hipMemcpyAsync(out, d_o, sizeof(kg_eph_pos) * nsnap, hipMemcpyDeviceToHost, s);
-    (void) hipStreamSynchronize(s);
-    (void) hipFree(d_in); (void) hipFree(d_o);
-    if (rc) return rc;
-    KG_HIP(e);
-    return KG_OK;
+    kg_scope tmp(v->ctx);
+    KG_TRY(tmp.alloc(&d_in, nsnap, "kg_eph_sv: snapshots"));
+    KG_TRY(tmp.alloc(&d_o, nsnap, "kg_eph_sv: rows"));
+    KG_HIP(hipMemcpyAsync(d_in, snaps, sizeof(kg_eph_snap) * nsnap, hipMemcpyHostToDevice, s));
+    KG_HIP(hipMemcpyAsync(d_o, out, sizeof(kg_eph_pos) * nsnap, hipMemcpyHostToDevice, s));      // a refused snapshot keeps its row's values
+    KG_TRY(kg_eph_sv_dev(v, d_in, nsnap, d_o));
+    KG_HIP(hipMemcpyAsync(out, d_o, sizeof(kg_eph_pos) * nsnap, hipMemcpyDeviceToHost, s));
+    return KG_OK;                                       // tmp drains the stream: `out` is filled when the caller sees it
 }
 
 void kg_eph_replica(uint32_t word, int32_t *chips, int32_t *cg_phase)

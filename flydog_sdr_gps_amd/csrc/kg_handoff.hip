@@ -82,7 +82,7 @@ __global__ __launch_bounds__(256) void aper_report_kernel(const float *__restric
 struct kg_aper {
     kg_ctx *ctx;
     int nchan;
-    float *d_avg;
+    kg_dbuf<float> d_avg;
 };
 
 extern "C" {
@@ -106,6 +106,13 @@ void kg_acq_chan_start(int is_e1b, int lo_shift, int ca_shift, double secs, kg_c
     o->ca_pause = ca_pause; o->code_creep = code_creep;
 }
 
+static int aper_init(kg_aper *a)
+{
+    KG_TRY(a->d_avg.alloc(APER_LEN * (size_t) a->nchan, "kg_aper_create: averages"));
+    KG_HIP(hipMemset(a->d_avg, 0, sizeof(float) * APER_LEN * (size_t) a->nchan));
+    return KG_OK;
+}
+
 int kg_aper_create(kg_ctx *ctx, int nchan, kg_aper **out)
 {
     int rc = kg_ctx_use(ctx);
@@ -116,8 +123,8 @@ int kg_aper_create(kg_ctx *ctx, int nchan, kg_aper **out)
     kg_aper *a = new (std::nothrow) kg_aper();
     KG_REQUIRE(a != nullptr, KG_ERR_NOMEM, "kg_aper_create: alloc");
     a->ctx = ctx; a->nchan = nchan;
-    KG_HIP(hipMalloc((void **) &a->d_avg, sizeof(float) * APER_LEN * (size_t) nchan));
-    KG_HIP(hipMemset(a->d_avg, 0, sizeof(float) * APER_LEN * (size_t) nchan));
+    rc = aper_init(a);
+    if (rc) { kg_aper_destroy(a); return rc; }
     *out = a;
     return KG_OK;
 }
@@ -127,7 +134,6 @@ void kg_aper_destroy(kg_aper *a)
     if (!a) return;
     (void) hipSetDevice(a->ctx->device);
     (void) hipStreamSynchronize(a->ctx->stream);
-    (void) hipFree(a->d_avg);
     delete a;
 }
 
@@ -171,16 +177,15 @@ int kg_aper_report(kg_aper *a, const int32_t *chans, int n, const int32_t *audio
     }
     void *d_in = nullptr;
     if ((rc = kg_ctx_scratch_upload(a->ctx, h.data(), sizeof(int) * h.size(), &d_in))) return rc;
+    std::vector<int> r(3 * (size_t) n);
     int *d_out = nullptr;
-    KG_HIP(hipMalloc((void **) &d_out, sizeof(int) * 3 * n));
+    kg_scope tmp(a->ctx);
+    KG_TRY(tmp.alloc(&d_out, 3 * (size_t) n, "kg_aper_report"));
     hipLaunchKernelGGL(aper_report_kernel, dim3(n), dim3(256), 0, a->ctx->stream, (const float *) a->d_avg,
                        (const int *) d_in, (const int *) d_in + n, d_out);
-    hipError_t e = hipGetLastError();
-    std::vector<int> r(3 * (size_t) n);
-    if (e == hipSuccess) e = hipMemcpyAsync(r.data(), d_out, sizeof(int) * 3 * n, hipMemcpyDeviceToHost, a->ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(a->ctx->stream);
-    (void) hipFree(d_out);
-    KG_HIP(e);
+    KG_HIP(hipGetLastError());
+    KG_HIP(hipMemcpyAsync(r.data(), d_out, sizeof(int) * 3 * n, hipMemcpyDeviceToHost, a->ctx->stream));
+    KG_HIP(hipStreamSynchronize(a->ctx->stream));
     for (int i = 0; i < n; i++) {
         KG_REQUIRE(!r[3 * i + 2], KG_ERR_INVALID, "kg_aper_report: channel %d holds an average above 1000 dBm", chans[i]);
         signal[i] = r[3 * i]; noise[i] = r[3 * i + 1];

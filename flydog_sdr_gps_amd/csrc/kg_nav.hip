@@ -186,9 +186,12 @@ struct kg_nav {
     kg_ctx *ctx;
     int nchan;
     std::vector<int> mode;              // the host's mirror (the cap bound, which stage 1 kernels to launch)
-    chan *d_chan;
-    nav_ws ws;
-    uint32_t ws_bits;                   // the window length the workspace holds
+    kg_dbuf<chan> d_chan;
+    kg_dbuf<uint32_t> d_win;            // the workspace: all three or none
+    kg_dbuf<uint64_t> d_match;
+    kg_dbuf<res> d_rs;
+    nav_ws ws;                          // the kernels' view of the workspace
+    uint32_t ws_bits;                   // the window length the workspace holds (published last)
 };
 
 // the workspace for windows of up to wbits bits: grows, never shrinks
@@ -196,15 +199,18 @@ static int nav_reserve(kg_nav *v, uint64_t wbits)
 {
     if (wbits <= v->ws_bits) return KG_OK;
     KG_HIP(hipStreamSynchronize(v->ctx->stream));                       // kernels of earlier pushes still use the old one
-    (void) hipFree(v->ws.win); (void) hipFree(v->ws.match); (void) hipFree(v->ws.rs);
-    v->ws.win = nullptr; v->ws.match = nullptr; v->ws.rs = nullptr; v->ws_bits = 0;
+    v->d_win.reset(); v->d_match.reset(); v->d_rs.reset();
+    v->ws = nav_ws{nullptr, nullptr, nullptr, 0, 0, 0}; v->ws_bits = 0;
     const uint64_t bits = (wbits + 4095) & ~(uint64_t) 4095;
-    v->ws.win_stride = (uint32_t) (bits / 32 + 4);
-    v->ws.match_stride = (uint32_t) (bits / 64 + 4);
-    v->ws.res_stride = (uint32_t) bits;
-    KG_HIP(hipMalloc((void **) &v->ws.win, sizeof(uint32_t) * v->ws.win_stride * v->nchan));
-    KG_HIP(hipMalloc((void **) &v->ws.match, sizeof(uint64_t) * v->ws.match_stride * v->nchan));
-    KG_HIP(hipMalloc((void **) &v->ws.rs, sizeof(res) * v->ws.res_stride * v->nchan));
+    const uint32_t win_stride = (uint32_t) (bits / 32 + 4), match_stride = (uint32_t) (bits / 64 + 4), res_stride = (uint32_t) bits;
+    int rc;
+    if ((rc = v->d_win.alloc((size_t) win_stride * v->nchan, "kg_nav: windows")) != KG_OK ||
+        (rc = v->d_match.alloc((size_t) match_stride * v->nchan, "kg_nav: matches")) != KG_OK ||
+        (rc = v->d_rs.alloc((size_t) res_stride * v->nchan, "kg_nav: results")) != KG_OK) {
+        v->d_win.reset(); v->d_match.reset();
+        return rc;
+    }
+    v->ws = nav_ws{v->d_win, v->d_match, v->d_rs, win_stride, match_stride, res_stride};
     v->ws_bits = (uint32_t) bits;
     return KG_OK;
 }
@@ -233,6 +239,17 @@ static int nav_check_out(const char *who, const kg_nav_frame *d_frames, size_t f
     return KG_OK;
 }
 
+static int nav_init(kg_nav *v)
+{
+    v->mode.assign(v->nchan, MODE_L1);
+    int rc = v->d_chan.alloc(v->nchan, "kg_nav_create: channels");
+    if (rc) return rc;
+    for (int ch = 0; ch < v->nchan; ch++) hipLaunchKernelGGL(nav_reset_kernel, dim3(1), dim3(1), 0, v->ctx->stream, v->d_chan.p, ch, (int) MODE_L1);
+    KG_TRY(nav_reserve(v, 4096));
+    KG_REQUIRE(hipGetLastError() == hipSuccess, KG_ERR_HIP, "kg_nav_create: launch failed");
+    return KG_OK;
+}
+
 extern "C" {
 
 int kg_nav_create(kg_ctx *ctx, int nchan, kg_nav **out)
@@ -245,22 +262,8 @@ int kg_nav_create(kg_ctx *ctx, int nchan, kg_nav **out)
     kg_nav *v = new (std::nothrow) kg_nav();
     KG_REQUIRE(v != nullptr, KG_ERR_NOMEM, "kg_nav_create: alloc");
     v->ctx = ctx; v->nchan = nchan;
-    v->mode.assign(nchan, MODE_L1);
-    v->d_chan = nullptr;
-    v->ws = nav_ws{nullptr, nullptr, nullptr, 0, 0, 0};
-    v->ws_bits = 0;
-    hipError_t e = hipMalloc((void **) &v->d_chan, sizeof(chan) * nchan);
-    if (e != hipSuccess) {
-        delete v;
-        KG_HIP(e);
-    }
-    for (int ch = 0; ch < nchan; ch++) hipLaunchKernelGGL(nav_reset_kernel, dim3(1), dim3(1), 0, ctx->stream, v->d_chan, ch, (int) MODE_L1);
-    rc = nav_reserve(v, 4096);
-    if (rc == KG_OK && hipGetLastError() != hipSuccess) { kg_set_error("kg_nav_create: launch failed"); rc = KG_ERR_HIP; }
-    if (rc) {
-        kg_nav_destroy(v);
-        return rc;
-    }
+    rc = nav_init(v);
+    if (rc) { kg_nav_destroy(v); return rc; }
     *out = v;
     return KG_OK;
 }
@@ -270,8 +273,6 @@ void kg_nav_destroy(kg_nav *v)
     if (!v) return;
     (void) hipSetDevice(v->ctx->device);
     (void) hipStreamSynchronize(v->ctx->stream);
-    (void) hipFree(v->d_chan);
-    (void) hipFree(v->ws.win); (void) hipFree(v->ws.match); (void) hipFree(v->ws.rs);
     delete v;
 }
 
@@ -365,28 +366,23 @@ int kg_nav_push_bits(kg_nav *v, const uint8_t *bits, size_t chan_stride, const i
     }
     KG_REQUIRE((int64_t) cap >= need, KG_ERR_INVALID, "kg_nav_push_bits: cap %d below %lld (one record per 30 new bits of a C/A channel, per 250 of an E1B one)",
                cap, (long long) need);
-    const size_t fbytes = sizeof(kg_nav_frame) * (frame_stride ? frame_stride : 1) * v->nchan;
+    const size_t fcount = (frame_stride ? frame_stride : 1) * v->nchan;
     uint8_t *d_bits = nullptr;
     kg_nav_frame *d_fr = nullptr;
     int32_t *d_cnt = nullptr;
     hipStream_t s = v->ctx->stream;
-    hipError_t e = hipMalloc((void **) &d_bits, in_bytes ? in_bytes : 1);
-    if (e == hipSuccess) e = hipMalloc((void **) &d_fr, fbytes);
-    if (e == hipSuccess) e = hipMalloc((void **) &d_cnt, sizeof(int32_t) * v->nchan);
-    for (int ch = 0; ch < v->nchan && e == hipSuccess; ch++)
-        if (nbits[ch]) e = hipMemcpyAsync(d_bits + (size_t) ch * chan_stride, bits + (size_t) ch * chan_stride, (size_t) nbits[ch], hipMemcpyHostToDevice, s);
-    rc = KG_OK;
-    if (e == hipSuccess) rc = kg_nav_push_bits_dev(v, d_bits, chan_stride, nbits, d_fr, frame_stride, cap, d_cnt);
-    if (e == hipSuccess && rc == KG_OK) e = hipMemcpyAsync(counts, d_cnt, sizeof(int32_t) * v->nchan, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && rc == KG_OK) e = hipStreamSynchronize(s);
-    if (e == hipSuccess && rc == KG_OK)
-        for (int ch = 0; ch < v->nchan && e == hipSuccess; ch++)
-            if (counts[ch] > 0)
-                e = hipMemcpy(frames + (size_t) ch * frame_stride, d_fr + (size_t) ch * frame_stride, sizeof(kg_nav_frame) * counts[ch], hipMemcpyDeviceToHost);
-    (void) hipStreamSynchronize(s);
-    (void) hipFree(d_bits); (void) hipFree(d_fr); (void) hipFree(d_cnt);
-    if (rc) return rc;
-    KG_HIP(e);
+    kg_scope tmp(v->ctx);
+    KG_TRY(tmp.alloc(&d_bits, in_bytes ? in_bytes : 1, "kg_nav_push_bits: bits"));
+    KG_TRY(tmp.alloc(&d_fr, fcount, "kg_nav_push_bits: frames"));
+    KG_TRY(tmp.alloc(&d_cnt, v->nchan, "kg_nav_push_bits: counts"));
+    for (int ch = 0; ch < v->nchan; ch++)
+        if (nbits[ch]) KG_HIP(hipMemcpyAsync(d_bits + (size_t) ch * chan_stride, bits + (size_t) ch * chan_stride, (size_t) nbits[ch], hipMemcpyHostToDevice, s));
+    KG_TRY(kg_nav_push_bits_dev(v, d_bits, chan_stride, nbits, d_fr, frame_stride, cap, d_cnt));
+    KG_HIP(hipMemcpyAsync(counts, d_cnt, sizeof(int32_t) * v->nchan, hipMemcpyDeviceToHost, s));
+    KG_HIP(hipStreamSynchronize(s));
+    for (int ch = 0; ch < v->nchan; ch++)
+        if (counts[ch] > 0)
+            KG_HIP(hipMemcpy(frames + (size_t) ch * frame_stride, d_fr + (size_t) ch * frame_stride, sizeof(kg_nav_frame) * counts[ch], hipMemcpyDeviceToHost));
     return KG_OK;
 }
 

@@ -183,35 +183,35 @@ __global__ __launch_bounds__(256) void nb_reset_kernel(kg_nbk::st *S, float *mag
 // ---------------------------------------------------------------------------
 struct kg_nb_store {
     int nchan;
-    kg_nbk::st *d_st;
-    float *d_mag;
-    float2 *d_dly;
+    kg_dbuf<kg_nbk::st> d_st;
+    kg_dbuf<float> d_mag;
+    kg_dbuf<float2> d_dly;
     std::vector<kg_nbk::st> h;                 // the derived M, D, G, ratio of each channel's last setup
     std::vector<char> was;                    // set up at least once
 };
+
+static int nb_store_init(kg_nb_store *s, int nchan)
+{
+    s->nchan = nchan;
+    s->h.assign(nchan, kg_nbk::st{});
+    s->was.assign(nchan, 0);
+    KG_TRY(s->d_st.alloc(nchan, "kg_nb: states"));
+    KG_TRY(s->d_mag.alloc(NB_MAG_STRIDE * (size_t) nchan, "kg_nb: magnitudes"));
+    return s->d_dly.alloc(NB_DLY_STRIDE * (size_t) nchan, "kg_nb: delay lines");
+}
 
 int kg_nb_store_create(int nchan, kg_nb_store **out)
 {
     *out = nullptr;
     kg_nb_store *s = new (std::nothrow) kg_nb_store();
     KG_REQUIRE(s != nullptr, KG_ERR_NOMEM, "kg_nb: alloc");
-    s->nchan = nchan;
-    s->d_st = nullptr; s->d_mag = nullptr; s->d_dly = nullptr;
-    s->h.assign(nchan, kg_nbk::st{});
-    s->was.assign(nchan, 0);
+    const int rc = nb_store_init(s, nchan);
+    if (rc) { kg_nb_store_destroy(s); return rc; }
     *out = s;
-    KG_HIP(hipMalloc((void **) &s->d_st, sizeof(kg_nbk::st) * nchan));
-    KG_HIP(hipMalloc((void **) &s->d_mag, sizeof(float) * NB_MAG_STRIDE * (size_t) nchan));
-    KG_HIP(hipMalloc((void **) &s->d_dly, sizeof(float2) * NB_DLY_STRIDE * (size_t) nchan));
     return KG_OK;
 }
 
-void kg_nb_store_destroy(kg_nb_store *s)
-{
-    if (!s) return;
-    (void) hipFree(s->d_st); (void) hipFree(s->d_mag); (void) hipFree(s->d_dly);
-    delete s;
-}
+void kg_nb_store_destroy(kg_nb_store *s) { delete s; }
 
 int kg_nb_store_was_setup(const kg_nb_store *s, int ch) { return s->was[ch]; }
 
@@ -269,7 +269,7 @@ struct kg_nb {
     kg_ctx *ctx;
     int nchan, max_in;
     kg_nb_store *st;
-    float2 *d_stage;                          // kg_nb_process's staging row
+    kg_dbuf<float2> d_stage;                  // kg_nb_process's staging row
     std::vector<char> seen;
 };
 
@@ -287,9 +287,9 @@ int kg_nb_create(kg_ctx *ctx, int nchan, int max_in, kg_nb **out)
     KG_REQUIRE(max_in >= 1 && max_in <= (1 << 24), KG_ERR_INVALID, "kg_nb_create: max_in %d", max_in);
     kg_nb *b = new (std::nothrow) kg_nb();
     KG_REQUIRE(b != nullptr, KG_ERR_NOMEM, "kg_nb_create: alloc");
-    b->ctx = ctx; b->nchan = nchan; b->max_in = max_in; b->st = nullptr; b->d_stage = nullptr;
+    b->ctx = ctx; b->nchan = nchan; b->max_in = max_in;
     b->seen.assign(nchan, 0);
-    if ((rc = kg_nb_store_create(nchan, &b->st)) != KG_OK) { kg_nb_store_destroy(b->st); delete b; return rc; }
+    if ((rc = kg_nb_store_create(nchan, &b->st)) != KG_OK) { kg_nb_destroy(b); return rc; }
     *out = b;
     return KG_OK;
 }
@@ -300,7 +300,6 @@ void kg_nb_destroy(kg_nb *nb)
     (void) hipSetDevice(nb->ctx->device);
     (void) hipStreamSynchronize(nb->ctx->stream);
     kg_nb_store_destroy(nb->st);
-    (void) hipFree(nb->d_stage);
     delete nb;
 }
 
@@ -365,7 +364,7 @@ int kg_nb_process(kg_nb *nb, int ch, const float *in, int n, float *out)
     KG_REQUIRE(kg_nb_store_was_setup(nb->st, ch), KG_ERR_STATE, "kg_nb_process: channel %d was never set up (kg_nb_setup)", ch);
     if (n == 0) return KG_OK;
     hipStream_t st = nb->ctx->stream;
-    if (!nb->d_stage) KG_HIP(hipMalloc((void **) &nb->d_stage, sizeof(float2) * nb->max_in));
+    if (!nb->d_stage && (rc = nb->d_stage.alloc(nb->max_in, "kg_nb_process: staging")) != KG_OK) return rc;
     KG_HIP(hipMemcpyAsync(nb->d_stage, in, sizeof(float2) * n, hipMemcpyHostToDevice, st));
     const int32_t c = ch, cnt = n;
     if ((rc = kg_nb_process_dev(nb, &c, 1, nb->d_stage, nb->max_in, &cnt, nb->d_stage, nb->max_in))) return rc;

@@ -2,6 +2,9 @@
 // with tools/pos_host_driver.cpp.  kg_pos_solve_dev is ONE launch of three single-wave workgroups, one per solver of SolveTask (all
 // satellites, not Galileo, only Galileo): they share nothing but the compacted epoch, which each forms itself, and walk the call's
 // epochs in order with their solver's state and every indexed matrix in LDS.  No barrier between workgroups, no atomics.
+#include <memory>
+#include <new>
+
 #include "kg_common.h"
 #include "kg_pos.h"
 
@@ -62,7 +65,7 @@ __global__ __launch_bounds__(64) void pos_solve_kernel(pos_state *__restrict__ s
 
 struct kg_pos {
     kg_ctx *ctx;
-    pos_state *d_st;
+    kg_dbuf<pos_state> d_st;
 };
 
 static int pos_cmd(kg_pos *v, int what, int use_kalman, int plot_e1b)
@@ -71,6 +74,20 @@ static int pos_cmd(kg_pos *v, int what, int use_kalman, int plot_e1b)
     if (rc) return rc;
     hipLaunchKernelGGL(pos_cmd_kernel, dim3(1), dim3(1), 0, v->ctx->stream, v->d_st, what, use_kalman, plot_e1b);
     KG_HIP(hipGetLastError());
+    return KG_OK;
+}
+
+static int pos_init(kg_pos *v, const int32_t kinds[64], double uere, double f_osc)
+{
+    std::unique_ptr<pos_state> h(new (std::nothrow) pos_state());
+    KG_REQUIRE(h != nullptr, KG_ERR_NOMEM, "kg_pos_create: alloc");
+    for (int k = 0; k < 3; k++) solver_init(h->s[k]);
+    for (int k = 0; k < MAX_SATS; k++) h->kinds[k] = kinds[k];
+    h->use_kalman = 1; h->plot_e1b = 0; h->uere = uere; h->f_osc = f_osc;
+    KG_TRY(v->d_st.alloc(1, "kg_pos_create: state"));
+    kg_scope tmp(v->ctx);                           // h is in use until the stream has drained
+    KG_HIP(hipMemcpyAsync(v->d_st, h.get(), sizeof(pos_state), hipMemcpyHostToDevice, v->ctx->stream));
+    KG_HIP(hipStreamSynchronize(v->ctx->stream));
     return KG_OK;
 }
 
@@ -89,24 +106,9 @@ int kg_pos_create(kg_ctx *ctx, const int32_t kinds[64], double uere, double f_os
                f_osc);
     kg_pos *v = new (std::nothrow) kg_pos();
     KG_REQUIRE(v != nullptr, KG_ERR_NOMEM, "kg_pos_create: alloc");
-    v->ctx = ctx; v->d_st = nullptr;
-    pos_state *h = new (std::nothrow) pos_state();
-    if (!h) {
-        delete v;
-        KG_REQUIRE(false, KG_ERR_NOMEM, "kg_pos_create: alloc");
-    }
-    for (int k = 0; k < 3; k++) solver_init(h->s[k]);
-    for (int k = 0; k < MAX_SATS; k++) h->kinds[k] = kinds[k];
-    h->use_kalman = 1; h->plot_e1b = 0; h->uere = uere; h->f_osc = f_osc;
-    hipError_t e = hipMalloc((void **) &v->d_st, sizeof(pos_state));
-    if (e == hipSuccess) e = hipMemcpyAsync(v->d_st, h, sizeof(pos_state), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);         // h is in use until here
-    delete h;
-    if (e != hipSuccess) {
-        (void) hipFree(v->d_st);
-        delete v;
-        KG_HIP(e);
-    }
+    v->ctx = ctx;
+    rc = pos_init(v, kinds, uere, f_osc);
+    if (rc) { kg_pos_destroy(v); return rc; }
     *out = v;
     return KG_OK;
 }
@@ -116,7 +118,6 @@ void kg_pos_destroy(kg_pos *v)
     if (!v) return;
     (void) hipSetDevice(v->ctx->device);
     (void) hipStreamSynchronize(v->ctx->stream);
-    (void) hipFree(v->d_st);
     delete v;
 }
 
@@ -163,21 +164,17 @@ int kg_pos_solve(kg_pos *v, const kg_eph_snap *snaps, const kg_eph_pos *sv, int 
                  o_out = o_tk + sizeof(uint64_t) * nepoch, o_skip = o_out + sizeof(kg_pos_epoch) * nepoch, total = o_skip + sizeof(uint32_t) * nepoch;
     char *d = nullptr;
     hipStream_t s = v->ctx->stream;
-    hipError_t e = hipMalloc((void **) &d, total);
-    if (e == hipSuccess) e = hipMemcpyAsync(d + o_snap, snaps, sizeof(kg_eph_snap) * n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d + o_sv, sv, sizeof(kg_eph_pos) * n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d + o_tk, ticks, sizeof(uint64_t) * nepoch, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && skip) e = hipMemcpyAsync(d + o_skip, skip, sizeof(uint32_t) * nepoch, hipMemcpyHostToDevice, s);
-    rc = KG_OK;
-    if (e == hipSuccess)
-        rc = kg_pos_solve_dev(v, (const kg_eph_snap *) (d + o_snap), (const kg_eph_pos *) (d + o_sv), nrow, nepoch, (const uint64_t *) (d + o_tk),
-                              skip ? (const uint32_t *) (d + o_skip) : nullptr, (kg_pos_epoch *) (d + o_out));
-    if (e == hipSuccess && rc == KG_OK) e = hipMemcpyAsync(out, d + o_out, sizeof(kg_pos_epoch) * nepoch, hipMemcpyDeviceToHost, s);
-    (void) hipStreamSynchronize(s);
-    (void) hipFree(d);
+    kg_scope tmp(v->ctx);
+    KG_TRY(tmp.alloc(&d, total, "kg_pos_solve"));
+    KG_HIP(hipMemcpyAsync(d + o_snap, snaps, sizeof(kg_eph_snap) * n, hipMemcpyHostToDevice, s));
+    KG_HIP(hipMemcpyAsync(d + o_sv, sv, sizeof(kg_eph_pos) * n, hipMemcpyHostToDevice, s));
+    KG_HIP(hipMemcpyAsync(d + o_tk, ticks, sizeof(uint64_t) * nepoch, hipMemcpyHostToDevice, s));
+    if (skip) KG_HIP(hipMemcpyAsync(d + o_skip, skip, sizeof(uint32_t) * nepoch, hipMemcpyHostToDevice, s));
+    rc = kg_pos_solve_dev(v, (const kg_eph_snap *) (d + o_snap), (const kg_eph_pos *) (d + o_sv), nrow, nepoch, (const uint64_t *) (d + o_tk),
+                          skip ? (const uint32_t *) (d + o_skip) : nullptr, (kg_pos_epoch *) (d + o_out));
     if (rc) return rc;
-    KG_HIP(e);
-    return KG_OK;
+    KG_HIP(hipMemcpyAsync(out, d + o_out, sizeof(kg_pos_epoch) * nepoch, hipMemcpyDeviceToHost, s));
+    return KG_OK;                                   // tmp drains the stream: `out` is filled when the caller sees it
 }
 
 int kg_pos_get_state(kg_pos *v, int solver_index, kg_pos_state *out)

@@ -987,26 +987,26 @@ struct post_nrs_host {            // NR_SPECTRAL's host side: s->norm_locut / no
 struct kg_post {
     kg_ctx *ctx;
     int nchan;
-    post_chan *d_chan;
-    float2 *d_ring_in;
-    float *d_ring_mag;
-    post_cfir *d_cfir;                   // [nchan][POST_NFIR]
-    post_sam *d_sam;                     // [nchan]
+    kg_dbuf<post_chan> d_chan;
+    kg_dbuf<float2> d_ring_in;
+    kg_dbuf<float> d_ring_mag;
+    kg_dbuf<post_cfir> d_cfir;           // [nchan][POST_NFIR]
+    kg_dbuf<post_sam> d_sam;             // [nchan]
     std::vector<post_sam> h_sam;         // parameters only (the PLL type, its gains, the snd_rate constants, mparam)
     std::vector<post_chan> h_chan;       // parameters only; the state lives on the device
     std::vector<post_host> h_args;
     std::vector<post_cfir> h_cfir;       // taps as designed / handed over; pos and hist are the device's
     std::vector<char> h_fir_ready;       // [nchan][POST_NFIR]: initialised since create
     std::vector<char> h_sq_ready;        // kg_post_squelch_setup AND kg_post_squelch_set were called
-    post_nr *d_nr;                       // [nchan]
+    kg_dbuf<post_nr> d_nr;               // [nchan]
     std::vector<post_nr_host> h_nr;      // s->nr_algo, s->nr_enable[], s->nr_param[][] (the filter states are the device's)
-    kg_nrs::state_t *d_nrs;              // [nchan]: nr_spectral[] (NR_spectral.cpp:69)
+    kg_dbuf<kg_nrs::state_t> d_nrs;      // [nchan]: nr_spectral[] (NR_spectral.cpp:69)
     std::vector<post_nrs_host> h_nrs;
     int nrs_snd_rate;                    // the reference's global snd_rate as NR_SPECTRAL sees it (kg_post_nrs_setup; 12000 at create)
     kg_nrs::rate_t nrs_rate;             // tinc .. ap, snr_prio_min at that rate
-    kg_nbw::state_t *d_nbw;              // [nchan]: nb_Wild[] (NB_Wild.cpp:36) and the stage's switch
+    kg_dbuf<kg_nbw::state_t> d_nbw;      // [nchan]: nb_Wild[] (NB_Wild.cpp:36) and the stage's switch
     std::vector<kg_nbw::state_t> h_nbw;  // thresh, taps, impulse_samples and the switch (hist is the device's)
-    kg_stage_cache list_cache = {};      // the channel list of the last process call
+    kg_stage_cache list_cache;           // the channel list of the last process call
     std::vector<uint32_t> mode_cmds;     // per channel: kg_post_set_mode / kg_post_set_sam_mparam calls so far (kg_post_mode_cmds_)
 };
 
@@ -1247,29 +1247,21 @@ static int nr_put_ctl(kg_post *p, int ch)          // s->nr_algo and s->nr_enabl
     return KG_OK;
 }
 
-extern "C" {
-
-int kg_post_create(kg_ctx *ctx, int nchan, kg_post **out)
+static int post_init(kg_post *p)
 {
-    int rc = kg_ctx_use(ctx);
-    if (rc) return rc;
-    KG_REQUIRE(out != nullptr, KG_ERR_INVALID, "kg_post_create: out is null");
-    *out = nullptr;
-    KG_REQUIRE(nchan >= 1 && nchan <= 65536, KG_ERR_INVALID, "kg_post_create: nchan %d", nchan);
-    kg_post *p = new (std::nothrow) kg_post();
-    KG_REQUIRE(p != nullptr, KG_ERR_NOMEM, "kg_post_create: alloc");
-    p->ctx = ctx; p->nchan = nchan;
-    KG_HIP(hipMalloc((void **) &p->d_chan, sizeof(post_chan) * nchan));
-    KG_HIP(hipMalloc((void **) &p->d_ring_in, sizeof(float2) * POST_CIRC * (size_t) nchan));
-    KG_HIP(hipMalloc((void **) &p->d_ring_mag, sizeof(float) * POST_CIRC * (size_t) nchan));
-    KG_HIP(hipMalloc((void **) &p->d_cfir, sizeof(post_cfir) * POST_NFIR * (size_t) nchan));
-    KG_HIP(hipMalloc((void **) &p->d_sam, sizeof(post_sam) * (size_t) nchan));
-    KG_HIP(hipMalloc((void **) &p->d_nr, sizeof(post_nr) * (size_t) nchan));
+    kg_ctx *const ctx = p->ctx;
+    const int nchan = p->nchan;
+    KG_TRY(p->d_chan.alloc(nchan, "kg_post_create: channels"));
+    KG_TRY(p->d_ring_in.alloc(POST_CIRC * (size_t) nchan, "kg_post_create: AGC rings"));
+    KG_TRY(p->d_ring_mag.alloc(POST_CIRC * (size_t) nchan, "kg_post_create: AGC rings"));
+    KG_TRY(p->d_cfir.alloc(POST_NFIR * (size_t) nchan, "kg_post_create: filters"));
+    KG_TRY(p->d_sam.alloc(nchan, "kg_post_create: SAM states"));
+    KG_TRY(p->d_nr.alloc(nchan, "kg_post_create: noise reduction"));
     KG_HIP(hipMemsetAsync(p->d_nr, 0, sizeof(post_nr) * (size_t) nchan, ctx->stream));     // the zeroed statics, NR_OFF_
     post_nr_host nh;
     memset(&nh, 0, sizeof nh);
     p->h_nr.assign(nchan, nh);
-    KG_HIP(hipMalloc((void **) &p->d_nrs, sizeof(kg_nrs::state_t) * (size_t) nchan));
+    KG_TRY(p->d_nrs.alloc(nchan, "kg_post_create: spectral noise reduction"));
     KG_HIP(hipMemsetAsync(p->d_nrs, 0, sizeof(kg_nrs::state_t) * (size_t) nchan, ctx->stream));     // the zeroed static nr_spectral[]
     post_nrs_host sh;
     memset(&sh, 0, sizeof sh);
@@ -1279,7 +1271,7 @@ int kg_post_create(kg_ctx *ctx, int nchan, kg_post **out)
     p->h_nrs.assign(nchan, sh);
     hipLaunchKernelGGL(post_nrs_vad_kernel, dim3((nchan + 255) / 256), dim3(256), 0, ctx->stream, p->d_nrs, nchan, sh.vad[0], sh.vad[1]);
     KG_HIP(hipGetLastError());
-    KG_HIP(hipMalloc((void **) &p->d_nbw, sizeof(kg_nbw::state_t) * (size_t) nchan));
+    KG_TRY(p->d_nbw.alloc(nchan, "kg_post_create: Wild blanker"));
     KG_HIP(hipMemsetAsync(p->d_nbw, 0, sizeof(kg_nbw::state_t) * (size_t) nchan, ctx->stream));     // the zeroed static nb_Wild[]
     kg_nbw::state_t wh;
     memset(&wh, 0, sizeof wh);
@@ -1314,18 +1306,33 @@ int kg_post_create(kg_ctx *ctx, int nchan, kg_post **out)
                        p->d_ring_in, p->d_ring_mag, 0);
     KG_HIP(hipGetLastError());
     KG_HIP(hipStreamSynchronize(ctx->stream));
+    return KG_OK;
+}
+
+extern "C" {
+
+int kg_post_create(kg_ctx *ctx, int nchan, kg_post **out)
+{
+    int rc = kg_ctx_use(ctx);
+    if (rc) return rc;
+    KG_REQUIRE(out != nullptr, KG_ERR_INVALID, "kg_post_create: out is null");
+    *out = nullptr;
+    KG_REQUIRE(nchan >= 1 && nchan <= 65536, KG_ERR_INVALID, "kg_post_create: nchan %d", nchan);
+    kg_post *p = new (std::nothrow) kg_post();
+    KG_REQUIRE(p != nullptr, KG_ERR_NOMEM, "kg_post_create: alloc");
+    p->ctx = ctx; p->nchan = nchan;
+    rc = post_init(p);
+    if (rc) { kg_post_destroy(p); return rc; }
     *out = p;
     return KG_OK;
 }
+
 
 void kg_post_destroy(kg_post *p)
 {
     if (!p) return;
     (void) hipSetDevice(p->ctx->device);
     (void) hipStreamSynchronize(p->ctx->stream);
-    (void) hipFree(p->d_chan); (void) hipFree(p->d_ring_in); (void) hipFree(p->d_ring_mag); (void) hipFree(p->d_cfir);
-    (void) hipFree(p->d_sam); (void) hipFree(p->d_nr); (void) hipFree(p->d_nrs); (void) hipFree(p->d_nbw);
-    kg_stage_cache_free(&p->list_cache);
     delete p;
 }
 

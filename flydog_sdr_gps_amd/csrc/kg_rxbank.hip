@@ -69,22 +69,22 @@ struct kg_rxbank {
     std::vector<char> spec_on;
     std::vector<kg_spec::emit_t> spec_mirror, spec_mirror2;
     std::vector<uint32_t> spec_cmds;
-    unsigned char *d_spec; size_t spec_max;     // [spec_max][1024] u8: the step's rows in map order
+    kg_dbuf<unsigned char> d_spec; size_t spec_max;     // [spec_max][1024] u8: the step's rows in map order
     int spec_n;                                 // rows of the last step
     std::vector<int32_t> spec_rx, spec_inst, spec_blk, spec_rx2, spec_inst2, spec_blk2;     // the last step's map; this pass's
     std::vector<char> sam_null;                 // scratch, per active entry: runs kg_post in channel-null SAM this step
     std::vector<int32_t> pb_inst, pb_n, pb_base, null_row, null_list, null_each, null_inst, null_n, null_base;
     // device buffers
-    short2 *d_wfiq; size_t wf_stride;           // [nrx][wf_stride] iq_t: a one-shot receiver uses pairs 0 .. 8191 of its row, an overlapped one all of it
-    unsigned char *d_rows, *d_pkts;             // [frame][1024], [frame][BANK_PKT_STRIDE]
-    unsigned char *d_raw; size_t nrec_max;      // [nrx][nrec_max] rx_iq_t (6 bytes)
-    float2 *d_xin, *d_firo; size_t firo_stride; // [nrx][nrec_max], [nrx][firo_stride]
-    short *d_s16; unsigned char *d_pay;         // [nrx][firo_stride], [nrx][firo_stride / 2]
-    float2 *d_agc; unsigned char *d_iqpay;      // [nrx][firo_stride] the AGC's complex output, [nrx][4 firo_stride] the IQ mode's payload
+    kg_dbuf<short2> d_wfiq; size_t wf_stride;         // [nrx][wf_stride] iq_t: a one-shot receiver uses pairs 0 .. 8191 of its row, an overlapped one all of it
+    kg_dbuf<unsigned char> d_rows, d_pkts;         // [frame][1024], [frame][BANK_PKT_STRIDE]
+    kg_dbuf<unsigned char> d_raw; size_t nrec_max;     // [nrx][nrec_max] rx_iq_t (6 bytes)
+    kg_dbuf<float2> d_xin, d_firo; size_t firo_stride; // [nrx][nrec_max], [nrx][firo_stride]
+    kg_dbuf<short> d_s16; kg_dbuf<unsigned char> d_pay; // [nrx][firo_stride], [nrx][firo_stride / 2]
+    kg_dbuf<float2> d_agc; kg_dbuf<unsigned char> d_iqpay; // [nrx][firo_stride] the AGC's complex output, [nrx][4 firo_stride] the IQ mode's payload
     std::vector<char> little_endian;            // per receiver: s->little_endian
     std::vector<int32_t> real_list, iq_le_list, iq_be_list;
     // step tables: BANK_SLOTS pinned host / device slots
-    kg_arena arena; unsigned char *h_slots, *d_slots; size_t slot_bytes;
+    kg_arena arena; kg_hbuf<unsigned char> h_slots; kg_dbuf<unsigned char> d_slots; size_t slot_bytes;
     hipEvent_t ev_end[BANK_SLOTS][3];           // behind a step's last enqueue on main / side / tail
     bool ev_end_rec[BANK_SLOTS];
     hipEvent_t ev_tab, ev_fir, ev_tail, ev_frames, ev_pk;
@@ -498,6 +498,116 @@ int kg_rxbank_nb_cmd_state(kg_rxbank *b, int rx, int32_t *ints, float *flts)
     return KG_OK;
 }
 
+static int bank_init(kg_rxbank *b)
+{
+    const int device = b->device, nrx = b->nrx, rx_mode = b->mode;
+    // The four streams that carry kernels are created back to back, the upload's fifth.  Which hardware queue (and, behind
+    // it, which of the four dispatch pipes) a stream lands on is the HIP runtime's choice -- the least-shared queue of its pool
+    // at that moment -- and depends on every stream the process created before: measured on one bank, 0.98 ms per step or
+    // 1.25 ... 1.38 by what had run earlier in the process (DESIGN 6.9; tools/micro/stream_pairs.hip measures which pairs of
+    // streams run side by side).  Creating them together at least keeps them off one another's queues while the pool has
+    // free ones.
+    bool reused = false;
+    {
+        std::lock_guard<std::mutex> lk(g_free_mutex);
+        for (size_t i = 0; i < g_free_sets.size(); i++)
+            if (g_free_sets[i].device == device) {
+                const bank_stream_set st = g_free_sets[i];
+                g_free_sets.erase(g_free_sets.begin() + (long) i);
+                b->s_main = st.s[0]; b->s_side = st.s[1]; b->s_tail = st.s[2]; b->s_ddc2 = st.s[3]; b->s_up = st.s[4];
+                reused = true;
+                break;
+            }
+    }
+    if (!reused)
+        for (hipStream_t *st : {&b->s_main, &b->s_side, &b->s_tail, &b->s_ddc2, &b->s_up}) KG_HIP(hipStreamCreateWithFlags(st, hipStreamNonBlocking));
+    KG_TRY(kg_ctx_create_on_stream(device, b->s_main, &b->c_main));
+    KG_TRY(kg_ctx_create_on_stream(device, b->s_side, &b->c_side));
+    KG_TRY(kg_ctx_create_on_stream(device, b->s_tail, &b->c_tail));
+    KG_TRY(kg_ddc_create(b->c_main, nrx, b->n, &b->ddc));
+    KG_TRY(kg_ddc_use_side_stream(b->ddc, b->s_ddc2));
+    KG_TRY(kg_wf_create(b->c_main, nrx, &b->wf));
+    KG_TRY(kg_rxddc_create_mode(b->c_side, nrx, b->n, rx_mode, &b->rx));
+    b->decim_rx = kg_rxddc_decim(b->rx);
+    b->nrec_max = b->n / (size_t) b->decim_rx + 2;
+    KG_TRY(kg_fir_create(b->c_side, nrx, (int) b->nrec_max, &b->fir));
+    KG_TRY(kg_nb_create(b->c_side, nrx, (int) b->nrec_max, &b->nb));
+    KG_TRY(kg_post_create(b->c_tail, nrx, &b->post));
+    KG_TRY(kg_adpcm_create(b->c_tail, nrx, &b->adpcm));
+    KG_TRY(kg_fir_create(b->c_tail, nrx, KG_FIR_OUT, &b->nullfir));
+    b->wf_stride = BANK_RING_PAIRS;
+    b->firo_stride = ((b->nrec_max + KG_FIR_OUT - 1) / KG_FIR_OUT + 1) * KG_FIR_OUT;
+    KG_TRY(b->d_wfiq.alloc(b->wf_stride * nrx, "kg_rxbank_create: wfiq"));
+    KG_HIP(hipMemset(b->d_wfiq, 0, sizeof(short2) * b->wf_stride * nrx));
+    KG_TRY(b->d_rows.alloc((size_t) KG_WF_WIDTH * nrx, "kg_rxbank_create: rows"));
+    KG_TRY(b->d_pkts.alloc((size_t) BANK_PKT_STRIDE * nrx, "kg_rxbank_create: pkts"));
+    KG_TRY(b->d_raw.alloc(6 * b->nrec_max * nrx, "kg_rxbank_create: raw"));
+    KG_TRY(b->d_xin.alloc(b->nrec_max * nrx, "kg_rxbank_create: xin"));
+    KG_TRY(b->d_firo.alloc(b->firo_stride * nrx, "kg_rxbank_create: firo"));
+    KG_TRY(b->d_s16.alloc(b->firo_stride * nrx, "kg_rxbank_create: s16"));
+    KG_TRY(b->d_pay.alloc(b->firo_stride / 2 * nrx, "kg_rxbank_create: pay"));
+    KG_HIP(hipMemset(b->d_rows, 0, (size_t) KG_WF_WIDTH * nrx));
+    KG_HIP(hipMemset(b->d_pkts, 0, (size_t) BANK_PKT_STRIDE * nrx));
+    KG_HIP(hipMemset(b->d_s16, 0, sizeof(short) * b->firo_stride * nrx));
+    KG_HIP(hipMemset(b->d_pay, 0, b->firo_stride / 2 * nrx));
+    KG_TRY(b->d_agc.alloc(b->firo_stride * nrx, "kg_rxbank_create: agc"));
+    KG_TRY(b->d_iqpay.alloc(4 * b->firo_stride * nrx, "kg_rxbank_create: iqpay"));
+    KG_HIP(hipMemset(b->d_agc, 0, sizeof(float2) * b->firo_stride * nrx));
+    KG_HIP(hipMemset(b->d_iqpay, 0, 4 * b->firo_stride * nrx));
+    b->little_endian.assign(nrx, 0);
+    {   // what a step's tables can take: <= 12 of them + a channel list for S-meter / AGC / detector and one for the coder per sound
+        // block (a receiver can complete nrec_max / 512 + 1 blocks in a step) -- checked HERE, not found out by every later step
+        // (+ one for the channel-null filter per sound block)
+        const size_t blocks_max = b->blocks_max = b->nrec_max / KG_FIR_OUT + 1;
+        if (16 + 5 * blocks_max > KG_ARENA_MAX_ENTRIES) {
+            kg_set_error("kg_rxbank_create: %zu ADC samples per step are up to %zu sound blocks per receiver and step; the step table holds %d "
+                         "(a step of at most %zu samples)", b->n, blocks_max, (KG_ARENA_MAX_ENTRIES - 16) / 5,
+                         (size_t) ((KG_ARENA_MAX_ENTRIES - 16) / 5 - 1) * KG_FIR_OUT * (size_t) b->decim_rx);
+            return KG_ERR_INVALID;
+        }
+        // (+ 64 per receiver: the blankers' tables; the audio spectrum: 12 bytes per receiver in CFastFIR's table, and per sound block
+        // the channel-null filter's table of 8 ints per receiver and its alignment; + 64 per table -- up to 12 and 4 per sound
+        // block -- for the 64-byte alignment arena_stage gives every entry)
+        b->slot_bytes = (8192 + 64 * blocks_max + 64 * (12 + 4 * blocks_max) + (size_t) (448 + 16 + (12 + 32) * blocks_max) * nrx + 63) & ~(size_t) 63;
+        b->spec_max = 2 * blocks_max * (size_t) nrx;                         // a passband and a channel-null row per sound block
+    }
+    KG_TRY(b->h_slots.alloc(b->slot_bytes * BANK_SLOTS, "kg_rxbank_create: slots"));
+    KG_TRY(b->d_slots.alloc(b->slot_bytes * BANK_SLOTS, "kg_rxbank_create: slots"));
+    for (int i = 0; i < BANK_SLOTS; i++) {
+        // hipEventBlockingSync: a host that has run BANK_SLOTS steps ahead SLEEPS in kg_rxbank_step's slot wait instead of spinning
+        // (the reference's server is one cooperative thread: it asks kg_rxbank_ready first and yields instead)
+        for (int j = 0; j < 3; j++) KG_HIP(hipEventCreateWithFlags(&b->ev_end[i][j], hipEventDisableTiming | hipEventBlockingSync));
+        b->ev_end_rec[i] = false;
+    }
+    for (hipEvent_t *e : {&b->ev_tab, &b->ev_fir, &b->ev_tail, &b->ev_frames, &b->ev_pk})
+        KG_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    // rescale = MPOW(2, -RXOUT_SCALE + CUTESDR_SCALE) * MPOW(10, CICF_GAIN_dB / 20), rx/data_pump.cpp:73-74 (kg_rxbank_set_unpack overrides)
+    b->rescale = powf(2.f, -23 + 15) * powf(10.f, 4.5f / 20.f); b->dc_i = b->dc_q = 0.f; b->spectral_inversion = 0;
+    b->tail_pending = b->pk_pending = false; b->step = 0;
+    b->active.assign(nrx, 1); b->snd_seq.assign(nrx, 0); b->last_nrec.assign(nrx, 0); b->last_nfir.assign(nrx, 0);
+    b->c_main->rows_by_chan = b->c_side->rows_by_chan = b->c_tail->rows_by_chan = 1;      // buffers hold one row per RECEIVER
+    b->decim.assign(nrx, 0); b->wf_set.assign(nrx, 0); b->overlapped.assign(nrx, 0);
+    b->ring_w.assign(nrx, 0); b->ring_total.assign(nrx, 0); b->ring_w2.assign(nrx, 0); b->ring_total2.assign(nrx, 0);
+    b->pkt.assign(nrx, kg_wf_pkt_info{0, 0, 0, 1});
+    b->all.resize(nrx); for (int i = 0; i < nrx; i++) b->all[i] = i;
+    b->h_nrec.assign(nrx, 0); b->h_nfir.assign(nrx, 0); b->chan_of.assign(nrx, 0); b->pkt_bytes.assign(nrx, 0); b->rx_of_frame.assign(nrx, -1);
+    b->out_off.assign(nrx, 0); b->max_out.assign(nrx, 0); b->h_nw.assign(nrx, 0); b->frame_off.assign(nrx, 0);
+    b->enabled.assign(nrx, 1); b->pkt_step.resize(nrx);
+    b->nbc.assign(nrx, kg_rxbank::nb_cmd{});
+    KG_TRY(b->d_spec.alloc(b->spec_max * KG_SPEC_ROW, "kg_rxbank_create: spec"));
+    KG_HIP(hipMemset(b->d_spec, 0, b->spec_max * KG_SPEC_ROW));
+    b->spec_on.assign(nrx, 0); b->spec_mirror.assign(nrx, kg_spec::emit_t{KG_SPEC_PASSBAND}); b->spec_mirror2 = b->spec_mirror;
+    b->spec_cmds.assign(nrx, 0); b->spec_n = 0;
+    for (std::vector<int32_t> *v : {&b->spec_rx, &b->spec_inst, &b->spec_blk, &b->spec_rx2, &b->spec_inst2, &b->spec_blk2}) v->assign(b->spec_max, 0);
+    b->sam_null.assign(nrx, 0); b->pb_inst.assign(nrx, KG_SPEC_PASSBAND); b->pb_n.assign(nrx, 0); b->pb_base.assign(nrx, 0);
+    b->null_row.assign(b->blocks_max * (size_t) nrx, -1);
+    b->null_each.assign(nrx, KG_FIR_OUT); b->null_inst.assign(nrx, KG_SPEC_CHAN_NULL);
+    memset(&b->arena, 0, sizeof b->arena);
+    memset(&b->last, 0, sizeof b->last);
+    KG_HIP(hipDeviceSynchronize());
+    return KG_OK;
+}
+
 void kg_rxbank_destroy(kg_rxbank *b)
 {
     if (!b) return;
@@ -507,11 +617,6 @@ void kg_rxbank_destroy(kg_rxbank *b)
     kg_adpcm_destroy(b->adpcm); kg_post_destroy(b->post); kg_fir_destroy(b->nullfir); kg_fir_destroy(b->fir); kg_rxddc_destroy(b->rx); kg_nb_destroy(b->nb);
     kg_wf_destroy(b->wf); kg_ddc_destroy(b->ddc);
     kg_ctx_destroy(b->c_tail); kg_ctx_destroy(b->c_side); kg_ctx_destroy(b->c_main);
-    (void) hipFree(b->d_wfiq); (void) hipFree(b->d_rows); (void) hipFree(b->d_pkts); (void) hipFree(b->d_raw);
-    (void) hipFree(b->d_xin); (void) hipFree(b->d_firo); (void) hipFree(b->d_s16); (void) hipFree(b->d_pay);
-    (void) hipFree(b->d_agc); (void) hipFree(b->d_iqpay); (void) hipFree(b->d_spec);
-    if (b->h_slots) (void) hipHostFree(b->h_slots);
-    (void) hipFree(b->d_slots);
     for (int i = 0; i < BANK_SLOTS; i++) for (int j = 0; j < 3; j++) if (b->ev_end[i][j]) (void) hipEventDestroy(b->ev_end[i][j]);
     for (hipEvent_t e : {b->ev_tab, b->ev_fir, b->ev_tail, b->ev_frames, b->ev_pk}) if (e) (void) hipEventDestroy(e);
     if (b->s_main && b->s_side && b->s_tail && b->s_ddc2 && b->s_up) {          // a complete set: kept for the next bank
@@ -530,146 +635,27 @@ int kg_rxbank_create(int device, int nrx, size_t adc_samples_per_step, int rx_mo
     KG_REQUIRE(nrx >= 1 && nrx <= 4096, KG_ERR_INVALID, "kg_rxbank_create: nrx %d (1..4096)", nrx);
     KG_REQUIRE(adc_samples_per_step >= 8192 && adc_samples_per_step <= ((size_t) 1 << 27), KG_ERR_INVALID,
                "kg_rxbank_create: %zu ADC samples per step (8192 .. 2^27)", adc_samples_per_step);
-    kg_rxbank *b = new (std::nothrow) kg_rxbank();
-    KG_REQUIRE(b != nullptr, KG_ERR_NOMEM, "kg_rxbank_create: alloc");
-    b->device = device; b->nrx = nrx; b->mode = rx_mode; b->n = adc_samples_per_step;
-    int rc = KG_OK;
     {   // (what says "no gfx950 device": there is no CPU fallback)
         int ndev = 0;
         const hipError_t e = hipGetDeviceCount(&ndev);
-        if (e != hipSuccess || ndev <= 0) {
-            kg_set_error("kg_rxbank_create: no HIP device (%s); libkiwigpu has no CPU fallback", e == hipSuccess ? "device count 0" : hipGetErrorString(e));
-            delete b;
-            return KG_ERR_NO_DEVICE;
-        }
-        if (device < 0 || device >= ndev) { kg_set_error("kg_rxbank_create: device %d out of range (0..%d)", device, ndev - 1); delete b; return KG_ERR_INVALID; }
+        KG_REQUIRE(e == hipSuccess && ndev > 0, KG_ERR_NO_DEVICE, "kg_rxbank_create: no HIP device (%s); libkiwigpu has no CPU fallback",
+                   e == hipSuccess ? "device count 0" : hipGetErrorString(e));
+        KG_REQUIRE(device >= 0 && device < ndev, KG_ERR_INVALID, "kg_rxbank_create: device %d out of range (0..%d)", device, ndev - 1);
     }
-#define BANK_TRY(call) do { if ((rc = (call)) != KG_OK) { kg_rxbank_destroy(b); return rc; } } while (0)
-#define BANK_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { kg_set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #call, \
-                            hipGetErrorString(e_)); kg_rxbank_destroy(b); return KG_ERR_HIP; } } while (0)
-    // The four streams that carry kernels are created back to back, the upload's fifth.  Which hardware queue (and, behind
-    // it, which of the four dispatch pipes) a stream lands on is the HIP runtime's choice -- the least-shared queue of its pool
-    // at that moment -- and depends on every stream the process created before: measured on one bank, 0.98 ms per step or
-    // 1.25 ... 1.38 by what had run earlier in the process (DESIGN 6.9; tools/micro/stream_pairs.hip measures which pairs of
-    // streams run side by side).  Creating them together at least keeps them off one another's queues while the pool has
-    // free ones.
-    BANK_HIP(hipSetDevice(device));
+    KG_HIP(hipSetDevice(device));
     {
         hipDeviceProp_t prop;
-        BANK_HIP(hipGetDeviceProperties(&prop, device));
-        if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-            kg_set_error("kg_rxbank_create: device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
-            delete b;
-            return KG_ERR_NO_DEVICE;
-        }
+        KG_HIP(hipGetDeviceProperties(&prop, device));
+        KG_REQUIRE(strncmp(prop.gcnArchName, "gfx950", 6) == 0, KG_ERR_NO_DEVICE,
+                   "kg_rxbank_create: device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
     }
-    bool reused = false;
-    {
-        std::lock_guard<std::mutex> lk(g_free_mutex);
-        for (size_t i = 0; i < g_free_sets.size(); i++)
-            if (g_free_sets[i].device == device) {
-                const bank_stream_set st = g_free_sets[i];
-                g_free_sets.erase(g_free_sets.begin() + (long) i);
-                b->s_main = st.s[0]; b->s_side = st.s[1]; b->s_tail = st.s[2]; b->s_ddc2 = st.s[3]; b->s_up = st.s[4];
-                reused = true;
-                break;
-            }
-    }
-    if (!reused) {
-    BANK_HIP(hipStreamCreateWithFlags(&b->s_main, hipStreamNonBlocking));
-    BANK_HIP(hipStreamCreateWithFlags(&b->s_side, hipStreamNonBlocking));
-    BANK_HIP(hipStreamCreateWithFlags(&b->s_tail, hipStreamNonBlocking));
-    BANK_HIP(hipStreamCreateWithFlags(&b->s_ddc2, hipStreamNonBlocking));
-    BANK_HIP(hipStreamCreateWithFlags(&b->s_up, hipStreamNonBlocking));
-    }
-    BANK_TRY(kg_ctx_create_on_stream(device, b->s_main, &b->c_main));
-    BANK_TRY(kg_ctx_create_on_stream(device, b->s_side, &b->c_side));
-    BANK_TRY(kg_ctx_create_on_stream(device, b->s_tail, &b->c_tail));
-    BANK_TRY(kg_ddc_create(b->c_main, nrx, b->n, &b->ddc));
-    BANK_TRY(kg_ddc_use_side_stream(b->ddc, b->s_ddc2));
-    BANK_TRY(kg_wf_create(b->c_main, nrx, &b->wf));
-    BANK_TRY(kg_rxddc_create_mode(b->c_side, nrx, b->n, rx_mode, &b->rx));
-    b->decim_rx = kg_rxddc_decim(b->rx);
-    b->nrec_max = b->n / (size_t) b->decim_rx + 2;
-    BANK_TRY(kg_fir_create(b->c_side, nrx, (int) b->nrec_max, &b->fir));
-    BANK_TRY(kg_nb_create(b->c_side, nrx, (int) b->nrec_max, &b->nb));
-    BANK_TRY(kg_post_create(b->c_tail, nrx, &b->post));
-    BANK_TRY(kg_adpcm_create(b->c_tail, nrx, &b->adpcm));
-    BANK_TRY(kg_fir_create(b->c_tail, nrx, KG_FIR_OUT, &b->nullfir));
-    b->wf_stride = BANK_RING_PAIRS;
-    b->firo_stride = ((b->nrec_max + KG_FIR_OUT - 1) / KG_FIR_OUT + 1) * KG_FIR_OUT;
-    BANK_HIP(hipMalloc((void **) &b->d_wfiq, sizeof(short2) * b->wf_stride * nrx));
-    BANK_HIP(hipMemset(b->d_wfiq, 0, sizeof(short2) * b->wf_stride * nrx));
-    BANK_HIP(hipMalloc((void **) &b->d_rows, (size_t) KG_WF_WIDTH * nrx));
-    BANK_HIP(hipMalloc((void **) &b->d_pkts, (size_t) BANK_PKT_STRIDE * nrx));
-    BANK_HIP(hipMalloc((void **) &b->d_raw, 6 * b->nrec_max * nrx));
-    BANK_HIP(hipMalloc((void **) &b->d_xin, sizeof(float2) * b->nrec_max * nrx));
-    BANK_HIP(hipMalloc((void **) &b->d_firo, sizeof(float2) * b->firo_stride * nrx));
-    BANK_HIP(hipMalloc((void **) &b->d_s16, sizeof(short) * b->firo_stride * nrx));
-    BANK_HIP(hipMalloc((void **) &b->d_pay, b->firo_stride / 2 * nrx));
-    BANK_HIP(hipMemset(b->d_rows, 0, (size_t) KG_WF_WIDTH * nrx));
-    BANK_HIP(hipMemset(b->d_pkts, 0, (size_t) BANK_PKT_STRIDE * nrx));
-    BANK_HIP(hipMemset(b->d_s16, 0, sizeof(short) * b->firo_stride * nrx));
-    BANK_HIP(hipMemset(b->d_pay, 0, b->firo_stride / 2 * nrx));
-    BANK_HIP(hipMalloc((void **) &b->d_agc, sizeof(float2) * b->firo_stride * nrx));
-    BANK_HIP(hipMalloc((void **) &b->d_iqpay, 4 * b->firo_stride * nrx));
-    BANK_HIP(hipMemset(b->d_agc, 0, sizeof(float2) * b->firo_stride * nrx));
-    BANK_HIP(hipMemset(b->d_iqpay, 0, 4 * b->firo_stride * nrx));
-    b->little_endian.assign(nrx, 0);
-    {   // what a step's tables can take: <= 12 of them + a channel list for S-meter / AGC / detector and one for the coder per sound
-        // block (a receiver can complete nrec_max / 512 + 1 blocks in a step) -- checked HERE, not found out by every later step
-        // (+ one for the channel-null filter per sound block)
-        const size_t blocks_max = b->blocks_max = b->nrec_max / KG_FIR_OUT + 1;
-        if (16 + 5 * blocks_max > KG_ARENA_MAX_ENTRIES) {
-            kg_set_error("kg_rxbank_create: %zu ADC samples per step are up to %zu sound blocks per receiver and step; the step table holds %d "
-                         "(a step of at most %zu samples)", b->n, blocks_max, (KG_ARENA_MAX_ENTRIES - 16) / 5,
-                         (size_t) ((KG_ARENA_MAX_ENTRIES - 16) / 5 - 1) * KG_FIR_OUT * (size_t) b->decim_rx);
-            kg_rxbank_destroy(b);
-            return KG_ERR_INVALID;
-        }
-        // (+ 64 per receiver: the blankers' tables; the audio spectrum: 12 bytes per receiver in CFastFIR's table, and per sound block
-        // the channel-null filter's table of 8 ints per receiver and its alignment)
-        b->slot_bytes = (8192 + 64 * blocks_max + (size_t) (448 + 16 + (12 + 32) * blocks_max) * nrx + 63) & ~(size_t) 63;
-        b->spec_max = 2 * blocks_max * (size_t) nrx;                         // a passband and a channel-null row per sound block
-    }
-    BANK_HIP(hipHostMalloc((void **) &b->h_slots, b->slot_bytes * BANK_SLOTS, hipHostMallocDefault));
-    BANK_HIP(hipMalloc((void **) &b->d_slots, b->slot_bytes * BANK_SLOTS));
-    for (int i = 0; i < BANK_SLOTS; i++) {
-        // hipEventBlockingSync: a host that has run BANK_SLOTS steps ahead SLEEPS in kg_rxbank_step's slot wait instead of spinning
-        // (the reference's server is one cooperative thread: it asks kg_rxbank_ready first and yields instead)
-        for (int j = 0; j < 3; j++) BANK_HIP(hipEventCreateWithFlags(&b->ev_end[i][j], hipEventDisableTiming | hipEventBlockingSync));
-        b->ev_end_rec[i] = false;
-    }
-    for (hipEvent_t *e : {&b->ev_tab, &b->ev_fir, &b->ev_tail, &b->ev_frames, &b->ev_pk})
-        BANK_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
-    // rescale = MPOW(2, -RXOUT_SCALE + CUTESDR_SCALE) * MPOW(10, CICF_GAIN_dB / 20), rx/data_pump.cpp:73-74 (kg_rxbank_set_unpack overrides)
-    b->rescale = powf(2.f, -23 + 15) * powf(10.f, 4.5f / 20.f); b->dc_i = b->dc_q = 0.f; b->spectral_inversion = 0;
-    b->tail_pending = b->pk_pending = false; b->step = 0;
-    b->active.assign(nrx, 1); b->snd_seq.assign(nrx, 0); b->last_nrec.assign(nrx, 0); b->last_nfir.assign(nrx, 0);
-    b->c_main->rows_by_chan = b->c_side->rows_by_chan = b->c_tail->rows_by_chan = 1;      // buffers hold one row per RECEIVER
-    b->decim.assign(nrx, 0); b->wf_set.assign(nrx, 0); b->overlapped.assign(nrx, 0);
-    b->ring_w.assign(nrx, 0); b->ring_total.assign(nrx, 0); b->ring_w2.assign(nrx, 0); b->ring_total2.assign(nrx, 0);
-    b->pkt.assign(nrx, kg_wf_pkt_info{0, 0, 0, 1});
-    b->all.resize(nrx); for (int i = 0; i < nrx; i++) b->all[i] = i;
-    b->h_nrec.assign(nrx, 0); b->h_nfir.assign(nrx, 0); b->chan_of.assign(nrx, 0); b->pkt_bytes.assign(nrx, 0); b->rx_of_frame.assign(nrx, -1);
-    b->out_off.assign(nrx, 0); b->max_out.assign(nrx, 0); b->h_nw.assign(nrx, 0); b->frame_off.assign(nrx, 0);
-    b->enabled.assign(nrx, 1); b->pkt_step.resize(nrx);
-    b->nbc.assign(nrx, kg_rxbank::nb_cmd{});
-    BANK_HIP(hipMalloc((void **) &b->d_spec, b->spec_max * KG_SPEC_ROW));
-    BANK_HIP(hipMemset(b->d_spec, 0, b->spec_max * KG_SPEC_ROW));
-    b->spec_on.assign(nrx, 0); b->spec_mirror.assign(nrx, kg_spec::emit_t{KG_SPEC_PASSBAND}); b->spec_mirror2 = b->spec_mirror;
-    b->spec_cmds.assign(nrx, 0); b->spec_n = 0;
-    for (std::vector<int32_t> *v : {&b->spec_rx, &b->spec_inst, &b->spec_blk, &b->spec_rx2, &b->spec_inst2, &b->spec_blk2}) v->assign(b->spec_max, 0);
-    b->sam_null.assign(nrx, 0); b->pb_inst.assign(nrx, KG_SPEC_PASSBAND); b->pb_n.assign(nrx, 0); b->pb_base.assign(nrx, 0);
-    b->null_row.assign(b->blocks_max * (size_t) nrx, -1);
-    b->null_each.assign(nrx, KG_FIR_OUT); b->null_inst.assign(nrx, KG_SPEC_CHAN_NULL);
-    memset(&b->arena, 0, sizeof b->arena);
-    memset(&b->last, 0, sizeof b->last);
-    BANK_HIP(hipDeviceSynchronize());
+    kg_rxbank *b = new (std::nothrow) kg_rxbank();
+    KG_REQUIRE(b != nullptr, KG_ERR_NOMEM, "kg_rxbank_create: alloc");
+    b->device = device; b->nrx = nrx; b->mode = rx_mode; b->n = adc_samples_per_step;
+    const int rc = bank_init(b);
+    if (rc) { kg_rxbank_destroy(b); return rc; }
     *out = b;
     return KG_OK;
-#undef BANK_TRY
-#undef BANK_HIP
 }
 
 kg_ddc *kg_rxbank_ddc(kg_rxbank *b) { return b ? b->ddc : nullptr; }

@@ -408,16 +408,44 @@ struct kg_rxddc {
     kg_ctx *ctx;
     rx_mode md;
     int nchan; long max_samples;
-    rx_chan *d_chans; std::vector<rx_chan> h;
-    u32 *d_nco;
-    u64 *d_st; u32 *d_c0rel, *d_tau, *d_hist;
-    u64 *d_wg;                                 // [nchan][4][64]: workgroup totals / bases of the end-referred carry scan
-    u32 *d_wgt;                                // [nchan][2][64]: likewise for the integrator-3 totals
-    int *d_c1buf; long c1_stride;
+    kg_dbuf<rx_chan> d_chans; std::vector<rx_chan> h;
+    kg_dbuf<u32> d_nco;
+    kg_dbuf<u64> d_st; kg_dbuf<u32> d_c0rel, d_tau, d_hist;
+    kg_dbuf<u64> d_wg;                         // [nchan][4][64]: workgroup totals / bases of the end-referred carry scan
+    kg_dbuf<u32> d_wgt;                        // [nchan][2][64]: likewise for the integrator-3 totals
+    kg_dbuf<int> d_c1buf; long c1_stride;
     int max_runs; long max_out;
     kg_stage_cache pack_cache;                 // the per-call tables of the last push (a steady stream repeats them: no upload)
     std::vector<char> seen;                    // scratch of a push: channels listed so far
 };
+
+static int rxddc_init(kg_rxddc *d)
+{
+    const int nchan = d->nchan, RX_R1 = d->md.r1;
+    const size_t max_samples = (size_t) d->max_samples;
+    d->h.assign(nchan, rx_chan());
+    for (auto &c : d->h) memset(&c, 0, sizeof c);
+    d->max_runs = (int) ((max_samples + 63) / 64);
+    if (d->max_runs > 16384) d->max_runs = 16384;
+    d->max_out = (long) (max_samples / RX_R1) + 2;
+    d->c1_stride = RX_HIST + d->max_out + RX_HIST;
+    KG_TRY(d->d_chans.alloc(nchan, "kg_rxddc_create: channels"));
+    KG_HIP(hipMemset(d->d_chans, 0, sizeof(rx_chan) * nchan));
+    KG_TRY(d->d_nco.alloc(sizeof(short) * RX_TAB / sizeof(u32), "kg_rxddc_create: NCO table"));
+    KG_TRY(d->d_st.alloc(4 * (size_t) nchan * d->max_runs, "kg_rxddc_create: run states"));
+    KG_TRY(d->d_wg.alloc(4 * (size_t) nchan * 64, "kg_rxddc_create: workgroup totals"));
+    KG_TRY(d->d_wgt.alloc(2 * (size_t) nchan * 64, "kg_rxddc_create: workgroup totals"));
+    KG_TRY(d->d_tau.alloc(2 * (size_t) nchan * d->max_runs, "kg_rxddc_create: run totals"));
+    KG_TRY(d->d_c0rel.alloc(2 * (size_t) nchan * d->max_out, "kg_rxddc_create: comb inputs"));
+    KG_TRY(d->d_hist.alloc(6 * (size_t) nchan, "kg_rxddc_create: histories"));
+    KG_TRY(d->d_c1buf.alloc(2 * (size_t) nchan * d->c1_stride, "kg_rxddc_create: stage-1 outputs"));
+    KG_HIP(hipMemset(d->d_c1buf, 0, sizeof(int) * 2 * (size_t) nchan * d->c1_stride));
+    // the NCO table as one 16-bit sine table of 10240 entries: cos(a) = T[a + 2048] (kg_common.h, kg_nco_table_build)
+    std::vector<short> tab(RX_TAB);
+    kg_nco_table_build(tab.data());
+    KG_HIP(hipMemcpy(d->d_nco, tab.data(), sizeof(short) * RX_TAB, hipMemcpyHostToDevice));
+    return KG_OK;
+}
 
 extern "C" {
 
@@ -442,28 +470,8 @@ int kg_rxddc_create_mode(kg_ctx *ctx, int nchan, size_t max_samples, int mode, k
     KG_REQUIRE(d != nullptr, KG_ERR_NOMEM, "kg_rxddc_create: alloc");
     d->ctx = ctx; d->nchan = nchan; d->max_samples = (long) max_samples;
     d->md = RX_MODES[mode];
-    const int RX_R1 = d->md.r1;
-    d->h.assign(nchan, rx_chan());
-    for (auto &c : d->h) memset(&c, 0, sizeof c);
-    d->max_runs = (int) ((max_samples + 63) / 64);
-    if (d->max_runs > 16384) d->max_runs = 16384;
-    d->max_out = (long) (max_samples / RX_R1) + 2;
-    d->c1_stride = RX_HIST + d->max_out + RX_HIST;
-    KG_HIP(hipMalloc((void **) &d->d_chans, sizeof(rx_chan) * nchan));
-    KG_HIP(hipMemset(d->d_chans, 0, sizeof(rx_chan) * nchan));
-    KG_HIP(hipMalloc((void **) &d->d_nco, sizeof(short) * RX_TAB));
-    KG_HIP(hipMalloc((void **) &d->d_st, sizeof(u64) * 4 * (size_t) nchan * d->max_runs));
-    KG_HIP(hipMalloc((void **) &d->d_wg, sizeof(u64) * 4 * (size_t) nchan * 64));
-    KG_HIP(hipMalloc((void **) &d->d_wgt, sizeof(u32) * 2 * (size_t) nchan * 64));
-    KG_HIP(hipMalloc((void **) &d->d_tau, sizeof(u32) * 2 * (size_t) nchan * d->max_runs));
-    KG_HIP(hipMalloc((void **) &d->d_c0rel, sizeof(u32) * 2 * (size_t) nchan * d->max_out));
-    KG_HIP(hipMalloc((void **) &d->d_hist, sizeof(u32) * 6 * (size_t) nchan));
-    KG_HIP(hipMalloc((void **) &d->d_c1buf, sizeof(int) * 2 * (size_t) nchan * d->c1_stride));
-    KG_HIP(hipMemset(d->d_c1buf, 0, sizeof(int) * 2 * (size_t) nchan * d->c1_stride));
-    // the NCO table as one 16-bit sine table of 10240 entries: cos(a) = T[a + 2048] (kg_common.h, kg_nco_table_build)
-    std::vector<short> tab(RX_TAB);
-    kg_nco_table_build(tab.data());
-    KG_HIP(hipMemcpy(d->d_nco, tab.data(), sizeof(short) * RX_TAB, hipMemcpyHostToDevice));
+    rc = rxddc_init(d);
+    if (rc) { kg_rxddc_destroy(d); return rc; }
     *out = d;
     return KG_OK;
 }
@@ -473,11 +481,6 @@ void kg_rxddc_destroy(kg_rxddc *d)
     if (!d) return;
     (void) hipSetDevice(d->ctx->device);
     (void) hipStreamSynchronize(d->ctx->stream);
-    (void) hipFree(d->d_chans); (void) hipFree(d->d_nco); 
-    
-    (void) hipFree(d->d_st); (void) hipFree(d->d_wg); (void) hipFree(d->d_wgt); (void) hipFree(d->d_tau); (void) hipFree(d->d_c0rel); (void) hipFree(d->d_hist);
-    (void) hipFree(d->d_c1buf);
-    kg_stage_cache_free(&d->pack_cache);
     delete d;
 }
 

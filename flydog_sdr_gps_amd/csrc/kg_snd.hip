@@ -339,9 +339,10 @@ struct kg_fir {
     kg_ctx *ctx;
     int nchan, max_in;
     long hist_stride;
-    float2 *d_hist, *d_coef, *d_coef0, *d_taps, *d_stage_in, *d_stage_out;   // d_coef0: m_pFilterCoef (no CIC compensation)
-    float *d_cic;
-    int *d_cic_on;                            // per channel: m_do_CIC_comp (SetupCICFilter, fastfir.cpp:148-158)
+    kg_dbuf<float2> d_hist, d_coef, d_coef0, d_taps;   // d_coef0: m_pFilterCoef (no CIC compensation)
+    kg_dbuf<float2> d_stage_in, d_stage_out;  // kg_fir_process's staging pair: both or neither
+    kg_dbuf<float> d_cic;
+    kg_dbuf<int> d_cic_on;                            // per channel: m_do_CIC_comp (SetupCICFilter, fastfir.cpp:148-158)
     std::vector<int> fill;                    // pending new samples per channel = FirPos()
     std::vector<char> coef_set;
     std::vector<char> seen;                   // scratch of a call: channels listed so far
@@ -381,6 +382,26 @@ static void fir_cic_table(int snd_rate_3ch, float *cic)       // fastfir.cpp:61-
     }
 }
 
+static int fir_init(kg_fir *f)
+{
+    const int nchan = f->nchan;
+    f->hist_stride = FIR_OUT + (FIR_OUT - 1) + f->max_in;   // history + leftover + one push
+    f->fill.assign(nchan, 0); f->coef_set.assign(nchan, 0);
+    f->window_func = -2; f->cic_3ch = -1;
+    KG_TRY(f->d_hist.alloc(f->hist_stride * nchan, "kg_fir_create: history"));
+    KG_HIP(hipMemset(f->d_hist, 0, sizeof(float2) * f->hist_stride * nchan));   // m_pFFTBuf[] = 0, :61-66
+    KG_TRY(f->d_coef.alloc(FIR_FFT * (size_t) nchan, "kg_fir_create: coefficients"));
+    KG_TRY(f->d_coef0.alloc(FIR_FFT * (size_t) nchan, "kg_fir_create: coefficients"));
+    KG_TRY(f->d_taps.alloc(FIR_FFT, "kg_fir_create: taps"));
+    KG_TRY(f->d_cic.alloc(FIR_FFT, "kg_fir_create: CIC table"));
+    KG_TRY(f->d_cic_on.alloc(nchan, "kg_fir_create: CIC switches"));
+    KG_HIP(hipMemset(f->d_cic_on, 0, sizeof(int) * nchan));
+    fir_cic_table(0, f->cic);                                          // the constructor's m_CIC, fastfir.cpp:61-79
+    f->cic_3ch = 0;
+    KG_HIP(hipMemcpy(f->d_cic, f->cic, sizeof f->cic, hipMemcpyHostToDevice));
+    return KG_OK;
+}
+
 extern "C" {
 
 int kg_fir_create(kg_ctx *ctx, int nchan, int max_in, kg_fir **out)
@@ -394,21 +415,8 @@ int kg_fir_create(kg_ctx *ctx, int nchan, int max_in, kg_fir **out)
     kg_fir *f = new (std::nothrow) kg_fir();
     KG_REQUIRE(f != nullptr, KG_ERR_NOMEM, "kg_fir_create: alloc");
     f->ctx = ctx; f->nchan = nchan; f->max_in = max_in;
-    f->hist_stride = FIR_OUT + (FIR_OUT - 1) + max_in;      // history + leftover + one push
-    f->fill.assign(nchan, 0); f->coef_set.assign(nchan, 0);
-    f->window_func = -2; f->cic_3ch = -1;
-    f->d_stage_in = f->d_stage_out = nullptr;
-    KG_HIP(hipMalloc((void **) &f->d_hist, sizeof(float2) * f->hist_stride * nchan));
-    KG_HIP(hipMemset(f->d_hist, 0, sizeof(float2) * f->hist_stride * nchan));   // m_pFFTBuf[] = 0, :61-66
-    KG_HIP(hipMalloc((void **) &f->d_coef, sizeof(float2) * FIR_FFT * (size_t) nchan));
-    KG_HIP(hipMalloc((void **) &f->d_coef0, sizeof(float2) * FIR_FFT * (size_t) nchan));
-    KG_HIP(hipMalloc((void **) &f->d_taps, sizeof(float2) * FIR_FFT));
-    KG_HIP(hipMalloc((void **) &f->d_cic, sizeof(float) * FIR_FFT));
-    KG_HIP(hipMalloc((void **) &f->d_cic_on, sizeof(int) * nchan));
-    KG_HIP(hipMemset(f->d_cic_on, 0, sizeof(int) * nchan));
-    fir_cic_table(0, f->cic);                                          // the constructor's m_CIC, fastfir.cpp:61-79
-    f->cic_3ch = 0;
-    KG_HIP(hipMemcpy(f->d_cic, f->cic, sizeof f->cic, hipMemcpyHostToDevice));
+    rc = fir_init(f);
+    if (rc) { kg_fir_destroy(f); return rc; }
     *out = f;
     return KG_OK;
 }
@@ -418,9 +426,6 @@ void kg_fir_destroy(kg_fir *f)
     if (!f) return;
     (void) hipSetDevice(f->ctx->device);
     (void) hipStreamSynchronize(f->ctx->stream);
-    (void) hipFree(f->d_hist); (void) hipFree(f->d_coef); (void) hipFree(f->d_coef0); (void) hipFree(f->d_taps); (void) hipFree(f->d_cic); (void) hipFree(f->d_cic_on);
-    
-    (void) hipFree(f->d_stage_in); (void) hipFree(f->d_stage_out);
     delete f;
 }
 
@@ -763,9 +768,9 @@ int kg_fir_process(kg_fir *f, int ch, const float *in, int n, float *out)
     KG_REQUIRE(n >= 0 && n <= f->max_in, KG_ERR_INVALID, "kg_fir_process: n %d (max %d)", n, f->max_in);
     if (n == 0) return 0;
     hipStream_t st = f->ctx->stream;
-    if (!f->d_stage_in) {
-        KG_HIP(hipMalloc((void **) &f->d_stage_in, sizeof(float2) * f->max_in));
-        KG_HIP(hipMalloc((void **) &f->d_stage_out, sizeof(float2) * (f->max_in + FIR_OUT)));
+    if (!f->d_stage_out) {                                  // the pair is made whole: d_stage_out, the test, comes last
+        KG_TRY(f->d_stage_in.alloc(f->max_in, "kg_fir_process: staging"));
+        if ((rc = f->d_stage_out.alloc((size_t) f->max_in + FIR_OUT, "kg_fir_process: staging")) != KG_OK) { f->d_stage_in.reset(); return rc; }
     }
     KG_HIP(hipMemcpyAsync(f->d_stage_in, in, sizeof(float2) * n, hipMemcpyHostToDevice, st));
     const int32_t c = ch;

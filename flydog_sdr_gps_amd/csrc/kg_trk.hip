@@ -50,8 +50,8 @@ struct kg_trk {
     std::vector<chan> h;            // the host's copy of the channels: current unless host_stale
     std::vector<chan_tab> tab;
     std::vector<chan_tab> e1b;      // the code memory's column of each channel
-    chan *d_chan;
-    chan_tab *d_tab;
+    kg_dbuf<chan> d_chan;
+    kg_dbuf<chan_tab> d_tab;
     bool host_stale, dev_stale, tab_stale;
     uint32_t cg_cnt, mask;
     uint64_t clock;
@@ -73,6 +73,24 @@ static int trk_fetch(kg_trk *t)     // make the host's copy current
     KG_REQUIRE((ch_) >= 0 && (ch_) < (t_)->nchan, KG_ERR_INVALID, who_ ": channel %d of %d", (ch_), (t_)->nchan); \
     { int rc_ = trk_fetch(t_); if (rc_) return rc_; }
 
+static int trk_init(kg_trk *t, int nchan, int lo_delay, int cg_delay)
+{
+    t->h.assign(nchan, chan());
+    t->tab.assign(nchan, chan_tab());
+    t->e1b.assign(nchan, chan_tab());
+    for (chan &c : t->h) {
+        memset(&c, 0, sizeof c);
+        c.cg_en = 1; c.loop_on = 1;
+        c.ms1_due = c.lo_due = c.cg_due = -1;
+        c.lo_delay = lo_delay; c.cg_delay = cg_delay;
+    }
+    for (int i = 0; i < nchan; i++) { memset(&t->tab[i], 0, sizeof(chan_tab)); memset(&t->e1b[i], 0, sizeof(chan_tab)); }
+    t->host_stale = false; t->dev_stale = true; t->tab_stale = true;
+    t->cg_cnt = 0; t->mask = 0; t->clock = 0;
+    KG_TRY(t->d_chan.alloc(nchan, "kg_trk_create: channels"));
+    return t->d_tab.alloc(nchan, "kg_trk_create: code tables");
+}
+
 extern "C" {
 
 int kg_trk_create(kg_ctx *ctx, int nchan, int lo_delay, int cg_delay, kg_trk **out)
@@ -91,26 +109,8 @@ int kg_trk_create(kg_ctx *ctx, int nchan, int lo_delay, int cg_delay, kg_trk **o
     kg_trk *t = new (std::nothrow) kg_trk();
     KG_REQUIRE(t != nullptr, KG_ERR_NOMEM, "kg_trk_create: alloc");
     t->ctx = ctx; t->nchan = nchan;
-    t->h.assign(nchan, chan());
-    t->tab.assign(nchan, chan_tab());
-    t->e1b.assign(nchan, chan_tab());
-    for (chan &c : t->h) {
-        memset(&c, 0, sizeof c);
-        c.cg_en = 1; c.loop_on = 1;
-        c.ms1_due = c.lo_due = c.cg_due = -1;
-        c.lo_delay = lo_delay; c.cg_delay = cg_delay;
-    }
-    for (int i = 0; i < nchan; i++) { memset(&t->tab[i], 0, sizeof(chan_tab)); memset(&t->e1b[i], 0, sizeof(chan_tab)); }
-    t->d_chan = nullptr; t->d_tab = nullptr;
-    t->host_stale = false; t->dev_stale = true; t->tab_stale = true;
-    t->cg_cnt = 0; t->mask = 0; t->clock = 0;
-    hipError_t e = hipMalloc((void **) &t->d_chan, sizeof(chan) * nchan);
-    if (e == hipSuccess) e = hipMalloc((void **) &t->d_tab, sizeof(chan_tab) * nchan);
-    if (e != hipSuccess) {
-        (void) hipFree(t->d_chan);
-        delete t;
-        KG_HIP(e);
-    }
+    rc = trk_init(t, nchan, lo_delay, cg_delay);
+    if (rc) { kg_trk_destroy(t); return rc; }
     *out = t;
     return KG_OK;
 }
@@ -120,8 +120,6 @@ void kg_trk_destroy(kg_trk *t)
     if (!t) return;
     (void) hipSetDevice(t->ctx->device);
     (void) hipStreamSynchronize(t->ctx->stream);
-    (void) hipFree(t->d_chan);
-    (void) hipFree(t->d_tab);
     delete t;
 }
 
@@ -306,24 +304,19 @@ int kg_trk_process_bits(kg_trk *t, const uint8_t *bits, size_t nclocks, kg_trk_e
     uint8_t *d_bits = nullptr;
     kg_trk_epoch *d_ep = nullptr;
     int32_t *d_cnt = nullptr;
-    hipError_t e = hipMalloc((void **) &d_bits, nbytes);
-    if (e == hipSuccess) e = hipMalloc((void **) &d_ep, ebytes);
-    if (e == hipSuccess) e = hipMalloc((void **) &d_cnt, sizeof(int32_t) * t->nchan);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_bits, bits, nbytes, hipMemcpyHostToDevice, t->ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_ep, 0, ebytes, t->ctx->stream);
-    rc = KG_OK;
-    if (e == hipSuccess) rc = kg_trk_process_bits_dev(t, d_bits, nclocks, d_ep, chan_stride, cap, d_cnt);
-    if (e == hipSuccess && rc == KG_OK) e = hipMemcpyAsync(counts, d_cnt, sizeof(int32_t) * t->nchan, hipMemcpyDeviceToHost, t->ctx->stream);
-    if (e == hipSuccess && rc == KG_OK) e = hipStreamSynchronize(t->ctx->stream);
-    if (e == hipSuccess && rc == KG_OK)
-        for (int ch = 0; ch < t->nchan && e == hipSuccess; ch++)
-            if (counts[ch] > 0 || counts[ch] < -1)
-                e = hipMemcpy(epochs + (size_t) ch * chan_stride, d_ep + (size_t) ch * chan_stride,
-                              sizeof(kg_trk_epoch) * (counts[ch] < 0 ? -1 - counts[ch] : counts[ch]), hipMemcpyDeviceToHost);
-    (void) hipStreamSynchronize(t->ctx->stream);
-    (void) hipFree(d_bits); (void) hipFree(d_ep); (void) hipFree(d_cnt);
-    if (rc) return rc;
-    KG_HIP(e);
+    kg_scope tmp(t->ctx);
+    KG_TRY(tmp.alloc(&d_bits, nbytes, "kg_trk_process_bits: bits"));
+    KG_TRY(tmp.alloc(&d_ep, chan_stride * t->nchan, "kg_trk_process_bits: epochs"));
+    KG_TRY(tmp.alloc(&d_cnt, t->nchan, "kg_trk_process_bits: counts"));
+    KG_HIP(hipMemcpyAsync(d_bits, bits, nbytes, hipMemcpyHostToDevice, t->ctx->stream));
+    KG_HIP(hipMemsetAsync(d_ep, 0, ebytes, t->ctx->stream));
+    KG_TRY(kg_trk_process_bits_dev(t, d_bits, nclocks, d_ep, chan_stride, cap, d_cnt));
+    KG_HIP(hipMemcpyAsync(counts, d_cnt, sizeof(int32_t) * t->nchan, hipMemcpyDeviceToHost, t->ctx->stream));
+    KG_HIP(hipStreamSynchronize(t->ctx->stream));
+    for (int ch = 0; ch < t->nchan; ch++)
+        if (counts[ch] > 0 || counts[ch] < -1)
+            KG_HIP(hipMemcpy(epochs + (size_t) ch * chan_stride, d_ep + (size_t) ch * chan_stride,
+                             sizeof(kg_trk_epoch) * (counts[ch] < 0 ? -1 - counts[ch] : counts[ch]), hipMemcpyDeviceToHost));
     return KG_OK;
 }
 

@@ -362,14 +362,14 @@ __global__ __launch_bounds__(256, 2) void wf_frame_kernel(
 struct kg_wf {
     kg_ctx *ctx;
     int nchan;
-    wf_chan_dev *d_chans;
-    float *d_windows, *d_cic;
-    short2 *d_iq;    unsigned char *d_out;  int stage_cap;      // staging for host-buffer calls
+    kg_dbuf<wf_chan_dev> d_chans;
+    kg_dbuf<float> d_windows, d_cic;
+    kg_dbuf<short2> d_iq;  kg_dbuf<unsigned char> d_out;  int stage_cap;    // staging for host-buffer calls: both, stage_cap frames, or neither
     kg_stage_cache chan_of_cache[WF_TABLE_WAYS];   // the {channel, offset} records of the last few distinct batches (a stream cycles through a few)
     int chan_of_victim;
     std::vector<int2> frame_tab;
-    float *d_tap_pwr, *d_tap_pwr_out, *d_tap_db;
-    int *d_claim;                             // the frame kernels' claim counters, zero between launches
+    kg_dbuf<float> d_tap_pwr, d_tap_pwr_out, d_tap_db;    // the debug call's taps, stage_cap frames: all three (d_tap_db last) or none
+    kg_dbuf<int> d_claim;                             // the frame kernels' claim counters, zero between launches
     std::vector<char> chan_set;
     bool tables_set;
     int grid;
@@ -378,7 +378,7 @@ struct kg_wf {
     kg_nb_store *nb;
     std::vector<char> nb_on;
     std::vector<int> win_of;
-    float2 *d_nbf; int nbf_cap;
+    kg_dbuf<float2> d_nbf; int nbf_cap;
     std::vector<int> nb_slot, nb_chan_first;
     struct pre_chan { int ch, first, count, wfn; };
     struct pre_frame { unsigned off; int slot; };
@@ -386,28 +386,17 @@ struct kg_wf {
     std::vector<pre_frame> pre_f;
 };
 
-extern "C" {
-
-int kg_wf_create(kg_ctx *ctx, int nchan, kg_wf **out)
+static int wf_init(kg_wf *w)
 {
-    int rc = kg_ctx_use(ctx);
-    if (rc) return rc;
-    KG_REQUIRE(out != nullptr, KG_ERR_INVALID, "kg_wf_create: out is null");
-    *out = nullptr;
-    KG_REQUIRE(nchan >= 1 && nchan <= 65536, KG_ERR_INVALID, "kg_wf_create: nchan %d", nchan);
-    kg_wf *w = new (std::nothrow) kg_wf();
-    KG_REQUIRE(w != nullptr, KG_ERR_NOMEM, "kg_wf_create: alloc");
-    w->ctx = ctx; w->nchan = nchan; w->tables_set = false;
+    kg_ctx *const ctx = w->ctx;
+    const int nchan = w->nchan;
     w->chan_set.assign(nchan, 0);
-    w->d_iq = nullptr; w->d_out = nullptr; w->stage_cap = 0;
-    w->d_tap_pwr = w->d_tap_pwr_out = w->d_tap_db = nullptr;
-    w->nb = nullptr; w->d_nbf = nullptr; w->nbf_cap = 0;
     w->nb_on.assign(nchan, 0); w->win_of.assign(nchan, 0);
-    if ((rc = kg_nb_store_create(nchan, &w->nb)) != KG_OK) return rc;
-    KG_HIP(hipMalloc((void **) &w->d_chans, sizeof(wf_chan_dev) * nchan));
-    KG_HIP(hipMalloc((void **) &w->d_windows, sizeof(float) * 4 * WF_NFFT));
-    KG_HIP(hipMalloc((void **) &w->d_cic, sizeof(float) * WF_NFFT));
-    KG_HIP(hipMalloc((void **) &w->d_claim, sizeof(int) * 9 * WF_CLAIM_STRIDE));
+    KG_TRY(kg_nb_store_create(nchan, &w->nb));
+    KG_TRY(w->d_chans.alloc(nchan, "kg_wf_create: channels"));
+    KG_TRY(w->d_windows.alloc(4 * WF_NFFT, "kg_wf_create: windows"));
+    KG_TRY(w->d_cic.alloc(WF_NFFT, "kg_wf_create: CIC table"));
+    KG_TRY(w->d_claim.alloc(9 * WF_CLAIM_STRIDE, "kg_wf_create: claim counters"));
     KG_HIP(hipMemset(w->d_claim, 0, sizeof(int) * 9 * WF_CLAIM_STRIDE));
     KG_HIP(hipFuncSetAttribute((const void *) wf_frame_kernel<false, false>,
                                hipFuncAttributeMaxDynamicSharedMemorySize, WF_LDS_BYTES));
@@ -425,21 +414,34 @@ int kg_wf_create(kg_ctx *ctx, int nchan, kg_wf **out)
         if (v >= 1 && v < occ) occ = v;
     }
     w->grid = ctx->num_cus * occ;
+    return KG_OK;
+}
+
+extern "C" {
+
+int kg_wf_create(kg_ctx *ctx, int nchan, kg_wf **out)
+{
+    int rc = kg_ctx_use(ctx);
+    if (rc) return rc;
+    KG_REQUIRE(out != nullptr, KG_ERR_INVALID, "kg_wf_create: out is null");
+    *out = nullptr;
+    KG_REQUIRE(nchan >= 1 && nchan <= 65536, KG_ERR_INVALID, "kg_wf_create: nchan %d", nchan);
+    kg_wf *w = new (std::nothrow) kg_wf();
+    KG_REQUIRE(w != nullptr, KG_ERR_NOMEM, "kg_wf_create: alloc");
+    w->ctx = ctx; w->nchan = nchan;
+    rc = wf_init(w);
+    if (rc) { kg_wf_destroy(w); return rc; }
     *out = w;
     return KG_OK;
 }
+
 
 void kg_wf_destroy(kg_wf *w)
 {
     if (!w) return;
     (void) hipSetDevice(w->ctx->device);
     (void) hipStreamSynchronize(w->ctx->stream);
-    (void) hipFree(w->d_chans); (void) hipFree(w->d_windows); (void) hipFree(w->d_cic); (void) hipFree(w->d_claim);
-    (void) hipFree(w->d_iq); (void) hipFree(w->d_out);
-    (void) hipFree(w->d_tap_pwr); (void) hipFree(w->d_tap_pwr_out); (void) hipFree(w->d_tap_db);
-    (void) hipFree(w->d_nbf);
     kg_nb_store_destroy(w->nb);
-    for (int k = 0; k < WF_TABLE_WAYS; k++) kg_stage_cache_free(&w->chan_of_cache[k]);
     delete w;
 }
 
@@ -574,9 +576,8 @@ static int wf_prepass(kg_wf *w, int nframes, const int32_t *chan_of, const uint6
     if (!d_rows) {
         if (nb > w->nbf_cap) {
             KG_HIP(hipStreamSynchronize(w->ctx->stream));       // frames in flight may still read the old rows
-            (void) hipFree(w->d_nbf);
-            w->d_nbf = nullptr; w->nbf_cap = 0;
-            KG_HIP(hipMalloc((void **) &w->d_nbf, sizeof(float2) * WF_NFFT * (size_t) nb));
+            w->d_nbf.reset(); w->nbf_cap = 0;
+            KG_TRY(w->d_nbf.alloc(WF_NFFT * (size_t) nb, "kg_wf: blanked frames"));
             w->nbf_cap = nb;
         }
         d_rows = w->d_nbf;
@@ -668,18 +669,31 @@ int kg_wf_frames_at_dev(kg_wf *w, int nframes, const int32_t *chan_of, const uin
     return wf_launch(w, nframes, chan_of, frame_off, iq_len, d_iq, d_out, false);
 }
 
+static void wf_taps_release(kg_wf *w) { w->d_tap_pwr.reset(); w->d_tap_pwr_out.reset(); w->d_tap_db.reset(); }
+
 static int wf_stage(kg_wf *w, int nframes)
 {
     if (nframes > w->stage_cap) {
         KG_HIP(hipStreamSynchronize(w->ctx->stream));
-        (void) hipFree(w->d_iq); (void) hipFree(w->d_out);
-        (void) hipFree(w->d_tap_pwr); (void) hipFree(w->d_tap_pwr_out); (void) hipFree(w->d_tap_db);
-        w->d_tap_pwr = w->d_tap_pwr_out = w->d_tap_db = nullptr;
-        KG_HIP(hipMalloc((void **) &w->d_iq, sizeof(short2) * WF_NFFT * (size_t) nframes));
-        KG_HIP(hipMalloc((void **) &w->d_out, (size_t) WF_WIDTH * nframes));
+        w->d_iq.reset(); w->d_out.reset(); w->stage_cap = 0;
+        wf_taps_release(w);                                     // sized by stage_cap: they go with it
+        int rc;
+        KG_TRY(w->d_iq.alloc(WF_NFFT * (size_t) nframes, "kg_wf_frames: staging"));
+        if ((rc = w->d_out.alloc((size_t) WF_WIDTH * nframes, "kg_wf_frames: staging")) != KG_OK) { w->d_iq.reset(); return rc; }
         w->stage_cap = nframes;
     }
     return KG_OK;
+}
+
+static int wf_taps(kg_wf *w)                                    // after wf_stage
+{
+    if (w->d_tap_db) return KG_OK;
+    int rc;
+    if ((rc = w->d_tap_pwr.alloc(SUB * (size_t) w->stage_cap, "kg_wf_debug_frame: taps")) != KG_OK ||
+        (rc = w->d_tap_pwr_out.alloc(WF_WIDTH * (size_t) w->stage_cap, "kg_wf_debug_frame: taps")) != KG_OK ||
+        (rc = w->d_tap_db.alloc(WF_WIDTH * (size_t) w->stage_cap, "kg_wf_debug_frame: taps")) != KG_OK)
+        wf_taps_release(w);
+    return rc;
 }
 
 int kg_wf_frames(kg_wf *w, int nframes, const int32_t *chan_of, const int16_t *iq, uint8_t *out)
@@ -688,10 +702,10 @@ int kg_wf_frames(kg_wf *w, int nframes, const int32_t *chan_of, const int16_t *i
     int rc = kg_ctx_use(w->ctx);
     if (rc) return rc;
     KG_REQUIRE(nframes >= 1, KG_ERR_INVALID, "kg_wf_frames: nframes %d", nframes);
-    if ((rc = wf_stage(w, nframes)) != KG_OK) return rc;
+    KG_TRY(wf_stage(w, nframes));
     hipStream_t st = w->ctx->stream;
     KG_HIP(hipMemcpyAsync(w->d_iq, iq, sizeof(short2) * WF_NFFT * (size_t) nframes, hipMemcpyHostToDevice, st));
-    if ((rc = wf_launch(w, nframes, chan_of, nullptr, 0, w->d_iq, w->d_out, false)) != KG_OK) return rc;
+    KG_TRY(wf_launch(w, nframes, chan_of, nullptr, 0, w->d_iq, w->d_out, false));
     KG_HIP(hipMemcpyAsync(out, w->d_out, (size_t) WF_WIDTH * nframes, hipMemcpyDeviceToHost, st));
     KG_HIP(hipStreamSynchronize(st));
     return KG_OK;
@@ -702,17 +716,13 @@ int kg_wf_debug_frame(kg_wf *w, int ch, const int16_t *iq, uint8_t *out, float *
     KG_REQUIRE(w && iq && out && pwr && pwr_out && dB, KG_ERR_INVALID, "kg_wf_debug_frame: null argument");
     int rc = kg_ctx_use(w->ctx);
     if (rc) return rc;
-    if ((rc = wf_stage(w, 1)) != KG_OK) return rc;
+    KG_TRY(wf_stage(w, 1));
     hipStream_t st = w->ctx->stream;
-    if (!w->d_tap_pwr) {
-        KG_HIP(hipMalloc((void **) &w->d_tap_pwr, sizeof(float) * SUB * (size_t) w->stage_cap));
-        KG_HIP(hipMalloc((void **) &w->d_tap_pwr_out, sizeof(float) * WF_WIDTH * (size_t) w->stage_cap));
-        KG_HIP(hipMalloc((void **) &w->d_tap_db, sizeof(float) * WF_WIDTH * (size_t) w->stage_cap));
-    }
+    KG_TRY(wf_taps(w));
     KG_HIP(hipMemsetAsync(w->d_tap_pwr, 0, sizeof(float) * SUB, st));
     KG_HIP(hipMemcpyAsync(w->d_iq, iq, sizeof(short2) * WF_NFFT, hipMemcpyHostToDevice, st));
     const int32_t c = ch;
-    if ((rc = wf_launch(w, 1, &c, nullptr, 0, w->d_iq, w->d_out, true)) != KG_OK) return rc;
+    KG_TRY(wf_launch(w, 1, &c, nullptr, 0, w->d_iq, w->d_out, true));
     KG_HIP(hipMemcpyAsync(out, w->d_out, WF_WIDTH, hipMemcpyDeviceToHost, st));
     KG_HIP(hipMemcpyAsync(pwr, w->d_tap_pwr, sizeof(float) * SUB, hipMemcpyDeviceToHost, st));
     KG_HIP(hipMemcpyAsync(pwr_out, w->d_tap_pwr_out, sizeof(float) * WF_WIDTH, hipMemcpyDeviceToHost, st));

@@ -146,9 +146,16 @@ __global__ __launch_bounds__(64) void wf_packet_kernel(const unsigned char *__re
 struct kg_adpcm {
     kg_ctx *ctx;
     int nchan;
-    adpcm_state *d_state;
+    kg_dbuf<adpcm_state> d_state;
     kg_stage_cache list_cache;           // the channel list of the last encode call
 };
+
+static int adpcm_init(kg_adpcm *a)
+{
+    KG_TRY(a->d_state.alloc(a->nchan, "kg_adpcm_create: states"));
+    KG_HIP(hipMemset(a->d_state, 0, sizeof(adpcm_state) * a->nchan));
+    return KG_OK;
+}
 
 extern "C" {
 
@@ -162,8 +169,8 @@ int kg_adpcm_create(kg_ctx *ctx, int nchan, kg_adpcm **out)
     kg_adpcm *a = new (std::nothrow) kg_adpcm();
     KG_REQUIRE(a != nullptr, KG_ERR_NOMEM, "kg_adpcm_create: alloc");
     a->ctx = ctx; a->nchan = nchan;
-    KG_HIP(hipMalloc((void **) &a->d_state, sizeof(adpcm_state) * nchan));
-    KG_HIP(hipMemset(a->d_state, 0, sizeof(adpcm_state) * nchan));
+    rc = adpcm_init(a);
+    if (rc) { kg_adpcm_destroy(a); return rc; }
     *out = a;
     return KG_OK;
 }
@@ -173,8 +180,6 @@ void kg_adpcm_destroy(kg_adpcm *a)
     if (!a) return;
     (void) hipSetDevice(a->ctx->device);
     (void) hipStreamSynchronize(a->ctx->stream);
-    (void) hipFree(a->d_state);
-    kg_stage_cache_free(&a->list_cache);
     delete a;
 }
 

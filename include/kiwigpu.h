@@ -56,6 +56,15 @@ const char *kg_strerror(int status);
 const char *kg_last_error(void);
 int kg_abi_version(void);
 
+/* Memory and failure.  A kg_*_create that fails leaves *out NULL and holds nothing: whatever it had allocated is released
+ * before it returns.  An allocation the device refuses is KG_ERR_NOMEM, with the byte count and the buffer's name in
+ * kg_last_error(), from every entry point; other HIP failures stay KG_ERR_HIP.  A call refused with KG_ERR_NOMEM leaves its
+ * object as it was or with its grow-on-demand staging empty: the object stays usable, and the same call made again simply grows
+ * the staging again.
+ * kg_dev_live_allocs: the device and pinned host allocations the library holds in this process at this moment, kg_dev_alloc's
+ * included (a leak check: the count is back at its earlier value once everything created since was destroyed). */
+int64_t kg_dev_live_allocs(void);
+
 /* ------------------------------------------------------------------------ */
 /* Context: one per GPU per process.                                         */
 /* ------------------------------------------------------------------------ */

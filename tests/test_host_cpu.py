@@ -1001,3 +1001,42 @@ def test_bench_summary_line_fits_and_names_every_workload():
     for wl in bench.ALL_WORKLOADS:
         assert wl.replace("receivers", "rx").replace("cfg2_chain", "chain") + "=1.234/0.432v/3.0x/ok" in s, (wl, s)
     assert bench.acq_flops_per_cell(16384, 4092) == 1257460 and bench.acq_flops_per_cell(16384, 16368) == 1294288
+
+
+def _c_function_body(text, start):
+    """The text of the braced body that opens at or after text[start]."""
+    i = text.index("{", start)
+    depth, j = 0, i
+    while True:
+        depth += {"{": 1, "}": -1}.get(text[j], 0)
+        j += 1
+        if depth == 0:
+            return text[i:j]
+
+
+def test_device_memory_has_one_door_and_every_create_cleans_up_through_its_destroy():
+    """DESIGN.md 6.14.  hipMalloc / hipHostMalloc / hipFree / hipHostFree are called by kg_mem_alloc and kg_mem_free
+    (kg_ctx.hip) and by nothing else in csrc/; the bank's own failure macros are gone; and every kg_*_create* that news an
+    object calls that object's destroy (its one failure exit)."""
+    import glob
+    calls = re.compile(r"\bhip(?:Host)?(?:Malloc|Free)\s*\(")
+    found = 0
+    for f in sorted(glob.glob(os.path.join(ROOT, "flydog_sdr_gps_amd", "csrc", "*.h*"))):
+        text = open(f).read()
+        assert "BANK_HIP" not in text and "BANK_TRY" not in text, f
+        if os.path.basename(f) == "kg_ctx.hip":
+            for name in ("kg_mem_alloc", "kg_mem_free"):
+                m = re.search(r"^int %s\(" % name, text, re.M)
+                assert m, name
+                body = _c_function_body(text, m.start())
+                assert calls.search(body), name
+                text = text.replace(body, "")
+        code = re.sub(r"//[^\n]*|/\*.*?\*/", "", text, flags=re.S)
+        assert not calls.search(code), (f, calls.search(code).group(0))
+        for m in re.finditer(r"^(?:static )?int (kg_\w+_create\w*)\(", text, re.M):
+            body = _c_function_body(text, m.start())
+            made = re.search(r"= new \(std::nothrow\) (kg_\w+)\(\)", body)
+            if made:
+                found += 1
+                assert re.search(r"\b%s_destroy\(" % made.group(1), body), (f, m.group(1))
+    assert found >= 15, found

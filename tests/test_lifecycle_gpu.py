@@ -1,10 +1,19 @@
 """Lifecycle: every object of the C ABI created, used once and destroyed, many times over; the
-device's free memory must come back (no leak in create/destroy or in the per-call scratch)."""
+device's free memory must come back (no leak in create/destroy or in the per-call scratch).
+
+The failure paths: the library counts its live device and pinned allocations (live_allocs) and, under
+KIWIGPU_TUNING=1, refuses the k-th allocation for KIWIGPU_FAIL_ALLOC=k -- on the host, no device memory is filled.  Every create is
+refused at every allocation it makes and must hold nothing afterwards; every grow-on-demand site is refused at every allocation
+it makes and must work afterwards as if nothing had happened."""
+import gc
+
 import numpy as np
 import pytest
 
-from flydog_sdr_gps_amd import (Adpcm, Aperture, Context, Ddc, FastFir, Post, RxDdc, Searcher, Waterfall, WfParams,
-                                handoff, post, prn, sats, synth, wf, wire)
+from flydog_sdr_gps_amd import (Adpcm, Aperture, Context, Ddc, Ephemerides, FastFir, KiwiGpuError, NavSync, NoiseBlanker, PositionSolver,
+                                Post, RxDdc, Searcher, Tracker, Waterfall, WfParams, acq, ddc, handoff, live_allocs, nav, post, prn, sats,
+                                synth, wf, wire)
+from flydog_sdr_gps_amd.rxbank import RxBank
 
 pytestmark = pytest.mark.gpu
 
@@ -68,6 +77,8 @@ def test_create_use_destroy_returns_device_memory():
 
 
 def test_contexts_come_and_go():
+    gc.collect()
+    live0 = live_allocs()
     free = []
     for _ in range(6):
         c = Context(0)
@@ -76,6 +87,7 @@ def test_contexts_come_and_go():
         free.append(c.mem_info()[0])
         c.close()
     assert max(free) - min(free[1:]) < 64 * 2 ** 20
+    assert live_allocs() == live0
 
 
 
@@ -87,3 +99,260 @@ def test_mark_rejects_tags_out_of_range(gpu_ctx):
     for bad in (0, -3, 65536):
         with pytest.raises(KiwiGpuError):
             gpu_ctx.mark(bad)
+
+
+# ---- exact accounting, and every allocation refused once -------------------------------------------------------------
+NOMEM = -4
+P3 = WfParams.for_zoom(3, 1000.0)
+IQ = synth.wf_iq_frame(seed=2)
+ROW = np.random.Generator(np.random.PCG64(7)).integers(0, 256, 1024, dtype=np.uint8)
+APER_CFG = [(handoff.MMA, 8.0, True, False)]
+
+
+def rng_of(seed):
+    return np.random.Generator(np.random.PCG64(seed))
+
+
+def run_ctx(c):
+    c.mark(7)
+    c.sync()
+
+
+def prep_searcher(s):
+    s.set_code(0, prn.cacode(*sats.SATS[0][1:3]))
+
+
+def run_searcher(s):
+    s.sample_iq16(rng_of(3).integers(-100, 100, 2 * s.nsamples).astype(np.int16), block=0)
+    s.correlate_async([0], nblocks=1)
+    return s.fetch()
+
+
+def prep_waterfall(w):
+    w.set_tables()
+    w.set_channel(0, P3)
+
+
+def prep_ddc(d):
+    d.set_wf(0, P3.i_offset, P3.decim)
+
+
+def prep_post(p):
+    p.set_agc(0, True, False, -100, 50, 6, 1000, 12000.0)
+    p.set_mode(0, post.MODE_SSB)
+
+
+def run_post(p):
+    p.process([0], np.ones((1, 512), np.complex64))
+    p.smeter([0])
+
+
+def run_aperture(a):
+    a.update([0], ROW[None], APER_CFG)
+    return a.report([0])
+
+
+def run_bank(bank):
+    from .test_receivers_gpu import _small_mix
+    bank.configure(_small_mix([5, 6], bank.n))
+    adc = synth.adc_stream(bank.n, 0x5EED0047)
+    d_adc = bank.ctx.alloc(adc.nbytes)
+    bank.ctx.upload(d_adc, adc)
+    bank.step(d_adc)
+    bank.sync()
+    bank.ctx.free(d_adc)
+
+
+def prep_tracker(t):
+    from . import trk_common as tc
+    for ch, word in ((0, tc.CA1), (1, tc.CA7)):
+        t.set_sat(ch, word)
+        t.set_rate_cg(ch, tc.NOM)
+    t.sampler_reset()
+
+
+def run_tracker(t):
+    bits = rng_of(13).integers(0, 256, 4096, dtype=np.uint8)
+    return t.process(bits, 8 * bits.size)
+
+
+def run_nav(v):
+    r = rng_of(17)
+    return v.push([r.integers(0, 2, 6000, dtype=np.uint8), r.integers(0, 2, 5000, dtype=np.uint8)])      # past the workspace made at create
+
+
+def eph_golden():
+    from .test_eph_cpu import load_golden
+    from .test_eph_gpu import segments
+    g = load_golden()
+    binds, rows, _ = segments(g["gal"]["ev"])[0]
+    frames = [np.resize(g["gal"]["frames"][rows[ch]], 70) for ch in range(2)]           # 70 a channel: past the workspace made at create
+    return binds[:2], frames, g["ca"]["snaps"][:16]
+
+
+def prep_eph(e):
+    for ch, sat, kind in eph_golden()[0]:
+        e.set_sat(ch, sat, kind)
+
+
+def run_eph(e):
+    return e.push_frames(eph_golden()[1])
+
+
+def run_eph_sv(e):
+    return e.sv(eph_golden()[2])
+
+
+def run_pos(p):
+    from .test_pos_cpu import load_golden
+    s = load_golden()["main"]
+    return p.solve(np.ascontiguousarray(s["snaps"][5:8]), np.ascontiguousarray(s["sv"][5:8]), s["ticks"][5:8].copy(), np.array([0, 1, 0x802], np.uint32))
+
+
+# name -> (create(ctx), configure, use once); the shapes are use_everything's
+CREATES = {
+    "Context": (lambda c: Context(0), None, run_ctx),
+    "Searcher-16384": (lambda c: Searcher(c, max_blocks=2), prep_searcher, run_searcher),
+    "Searcher-65536": (lambda c: Searcher(c, max_blocks=2, nsamples=acq.NSAMPLES_10MS, fft_len=acq.FFT_LEN_10MS), prep_searcher, run_searcher),
+    "Waterfall": (lambda c: Waterfall(c, nchan=2), prep_waterfall, lambda w: w.frames([0], IQ[None])),
+    "Ddc": (lambda c: Ddc(c, nchan=2, max_samples=1 << 16), prep_ddc, lambda d: d.push(np.zeros(1 << 14, np.int16), [0])),
+    "RxDdc-std": (lambda c: RxDdc(c, nchan=2, max_samples=1 << 16, mode=ddc.RX_STD), lambda r: r.set_freq(0, 12345),
+                  lambda r: r.push(np.zeros(1 << 15, np.int16), [0])),
+    "RxDdc-wide": (lambda c: RxDdc(c, nchan=2, max_samples=1 << 16, mode=ddc.RX_WIDE), lambda r: r.set_freq(0, 12345),
+                   lambda r: r.push(np.zeros(1 << 15, np.int16), [0])),
+    "RxDdc-rx14": (lambda c: RxDdc(c, nchan=2, max_samples=1 << 16, mode=ddc.RX_14), lambda r: r.set_freq(0, 12345),
+                   lambda r: r.push(np.zeros(1 << 15, np.int16), [0])),
+    "FastFir": (lambda c: FastFir(c, nchan=2, max_in=1024), lambda f: f.setup(0, 300.0, 2700.0, 0.0, 12000.0),
+                lambda f: f.process(0, np.ones(1024, np.complex64))),
+    "Post": (lambda c: Post(c, nchan=2), prep_post, run_post),
+    "Adpcm": (lambda c: Adpcm(c, nchan=2), None, lambda a: a.encode([0], np.zeros((1, 512), np.int16))),
+    "Aperture": (lambda c: Aperture(c, nchan=2), None, run_aperture),
+    "NoiseBlanker": (lambda c: NoiseBlanker(c, nchan=2, max_in=1024), lambda b: b.setup(0, 12000.0, [100.0, 50.0]),
+                     lambda b: b.process(0, rng_of(11).standard_normal((512, 2)).astype(np.float32))),
+    "RxBank": (lambda c: RxBank(2, 8192 * 16), None, run_bank),
+    "Tracker": (lambda c: Tracker(c, 2), prep_tracker, run_tracker),
+    "NavSync": (lambda c: NavSync(c, 2, [nav.L1, nav.E1B]), None, run_nav),
+    "Ephemerides": (lambda c: Ephemerides(c, 2), prep_eph, run_eph),
+    "PositionSolver": (lambda c: PositionSolver(c), lambda p: p.set_mode(1, 1), run_pos),
+}
+
+
+def refused_until_it_works(monkeypatch, call, cap, after_refusal=None):
+    """call() under KIWIGPU_FAIL_ALLOC = 1, 2, ...: status -4 naming the variable until the first success, which must come by k = cap
+    and after at least one refusal -> (what the successful call returned, refusals).  The variables are gone afterwards."""
+    monkeypatch.setenv("KIWIGPU_TUNING", "1")
+    try:
+        for k in range(1, cap + 1):
+            monkeypatch.setenv("KIWIGPU_FAIL_ALLOC", str(k))
+            try:
+                out = call()
+            except KiwiGpuError as e:
+                assert e.status == NOMEM and "KIWIGPU_FAIL_ALLOC" in str(e), (k, e)
+                if after_refusal:
+                    after_refusal(k)
+                continue
+            assert k > 1, "allocation 1 was not refused: the call allocates nothing or the switch is dead"
+            return out, k - 1
+        pytest.fail("no success up to KIWIGPU_FAIL_ALLOC=%d" % cap)
+    finally:
+        monkeypatch.delenv("KIWIGPU_FAIL_ALLOC")
+        monkeypatch.delenv("KIWIGPU_TUNING")
+
+
+def as_bytes(x):
+    return [as_bytes(v) for v in x] if isinstance(x, (list, tuple)) else np.ascontiguousarray(x).tobytes()
+
+
+def test_live_allocations_return_exactly():
+    gc.collect()
+    live0 = live_allocs()
+    ctx = Context(0)
+    assert live_allocs() > live0
+    use_everything(ctx)
+    ctx.close()
+    assert live_allocs() == live0
+    for name in ("RxBank", "Tracker", "NavSync", "Ephemerides", "PositionSolver"):
+        create, prep, run = CREATES[name]
+        ctx = Context(0)
+        obj = create(ctx)
+        if prep:
+            prep(obj)
+        run(obj)
+        if name == "Ephemerides":
+            run_eph_sv(obj)
+        obj.close()
+        ctx.close()
+        assert live_allocs() == live0, name
+
+
+@pytest.mark.parametrize("name", list(CREATES))
+def test_create_survives_every_refused_allocation(monkeypatch, name):
+    create, prep, run = CREATES[name]
+    gc.collect()
+    live0 = live_allocs()
+    ctx = None if name == "Context" else Context(0)
+    live1 = live_allocs()
+
+    def nothing_held(k):
+        assert live_allocs() == live1, "after the refusal of allocation %d" % k
+
+    obj, refusals = refused_until_it_works(monkeypatch, lambda: create(ctx), 400 if name == "RxBank" else 64, nothing_held)
+    print("%s: %d allocations, each refused once" % (name, refusals))
+    assert refusals >= 1
+    if prep:
+        prep(obj)
+    run(obj)
+    obj.close()
+    if ctx is not None:
+        ctx.close()
+    assert live_allocs() == live0
+
+
+def then(prep, run):
+    return lambda o: ((prep(o) if prep else None), run(o))[1]
+
+
+# name -> (create(ctx), what comes before (no refusal yet), the call that grows something); outputs compared with a fresh object's
+GROWTHS = {
+    "Waterfall.frames": CREATES["Waterfall"],
+    "Waterfall.debug_frame": (CREATES["Waterfall"][0], then(*CREATES["Waterfall"][1:]), lambda w: w.debug_frame(0, IQ)),     # only the taps grow
+    "Waterfall.debug_frame-first": (CREATES["Waterfall"][0], prep_waterfall, lambda w: w.debug_frame(0, IQ)),                # staging and taps
+    "FastFir.process": CREATES["FastFir"],
+    "NoiseBlanker.process": CREATES["NoiseBlanker"],
+    "kg_ctx_stage": (CREATES["Aperture"][0], None, lambda a: (a.update([0], ROW[None], APER_CFG), a.get(0))[1]),   # a fresh context's ring
+    "Ephemerides.push_frames": CREATES["Ephemerides"],
+    "Ephemerides.sv": (CREATES["Ephemerides"][0], then(prep_eph, run_eph), run_eph_sv),
+    "NavSync.push": CREATES["NavSync"],
+    "Tracker.process": CREATES["Tracker"],
+    "PositionSolver.solve": CREATES["PositionSolver"],
+    "Aperture.report": (CREATES["Aperture"][0], lambda a: a.update([0], ROW[None], APER_CFG), lambda a: a.report([0])),
+}
+
+
+@pytest.mark.parametrize("name", list(GROWTHS))
+def test_growth_survives_every_refused_allocation(monkeypatch, name):
+    create, prepare, call = GROWTHS[name]
+    gc.collect()
+    live0 = live_allocs()
+
+    def fresh():
+        c = Context(0)
+        o = create(c)
+        if prepare:
+            prepare(o)
+        return c, o
+
+    ctx, obj = fresh()
+    first, refusals = refused_until_it_works(monkeypatch, lambda: call(obj), 64)
+    print("%s: %d allocations, each refused once" % (name, refusals))
+    assert refusals >= 1
+    again = call(obj)                                   # the variable is gone: the same call on the same object
+    obj.close()
+    ctx.close()
+    assert live_allocs() == live0
+    ctx, obj = fresh()                                  # an object that never saw a refusal
+    want = [as_bytes(call(obj)), as_bytes(call(obj))]
+    obj.close()
+    ctx.close()
+    assert [as_bytes(first), as_bytes(again)] == want
+    assert live_allocs() == live0
