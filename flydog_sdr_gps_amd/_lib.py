@@ -198,6 +198,25 @@ SYMBOLS = {
     "kg_rxbank_spec_map": (_i, [_vp, _vp, _vp, _vp]),
     "kg_rxbank_spec_rows": (_i, [_vp, _vp, _vp]),
     "kg_fir_set_coef_plain": (_i, [_vp, _i, _vp]),
+    "kg_fftext_create": (_i, [_vp, _i, C.POINTER(_vp)]),
+    "kg_fftext_destroy": (None, [_vp]),
+    "kg_fftext_set_rate": (_i, [_vp, C.c_double]),
+    "kg_fftext_set_run": (_i, [_vp, _i, _i, _i, _i]),
+    "kg_fftext_set_itime": (_i, [_vp, _i, C.c_double]),
+    "kg_fftext_clear": (_i, [_vp, _i]),
+    "kg_fftext_restart": (_i, [_vp, _i]),
+    "kg_fftext_process_dev": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _sz, _vp, _sz, _i, _vp, _vp, _vp, _vp]),
+    "kg_fftext_process": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _sz, _vp, _sz, _i, _vp, _vp, _vp, _vp]),
+    "kg_fftext_due": (_i, [_vp, _i, C.c_uint32]),
+    "kg_fftext_state": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "kg_rxbank_fftext_set_rate": (_i, [_vp, C.c_double]),
+    "kg_rxbank_fftext_set_run": (_i, [_vp, _i, _i]),
+    "kg_rxbank_fftext_set_itime": (_i, [_vp, _i, C.c_double]),
+    "kg_rxbank_fftext_clear": (_i, [_vp, _i]),
+    "kg_rxbank_fftext": (_vp, [_vp]),
+    "kg_rxbank_fftext_max": (_i, [_vp]),
+    "kg_rxbank_fftext_map": (_i, [_vp, _vp, _vp, _vp]),
+    "kg_rxbank_fftext_rows": (_i, [_vp, _vp, _vp]),
     "kg_snd_gps_begin": (None, [_vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]),
     "kg_snd_gps_stamp": (None, [_vp, _i, _i, _i, _i, _i, C.c_double, C.c_double, C.c_uint64, _vp]),
     "kg_acq_chan_start": (None, [_i, _i, _i, C.c_double, _vp]),

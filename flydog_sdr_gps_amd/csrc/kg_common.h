@@ -215,6 +215,18 @@ __attribute__((visibility("hidden"))) int kg_fir_process_rows_(kg_fir *f, const 
                                                                const int32_t *n_each, void *d_out, size_t out_stride, int32_t *nout,
                                                                const kg_fir_spec_req *req);
 
+// the same with the filtered spectrum of every completed block stored too (kg_fir_process_taps_dev's d_post), rows or not (req may be null)
+__attribute__((visibility("hidden"))) int kg_fir_process_post_(kg_fir *f, const int32_t *chans, int nch, const void *d_in, size_t in_stride,
+                                                               const int32_t *n_each, void *d_out, size_t out_stride, int32_t *nout,
+                                                               const kg_fir_spec_req *req, void *d_post, size_t tap_stride);
+
+// kg_fftext.hip, for kg_rxbank.hip (not part of the ABI): kg_fftext_process_dev with entry i's spectra at row spec_row[i] of d_spec
+struct kg_fftext;
+__attribute__((visibility("hidden"))) int kg_fftext_process_rows_(kg_fftext *fx, const int32_t *chans, int nch, const int32_t *nblk, const int32_t *inst,
+                                                                  const int32_t *spec_row, const float *d_spec, size_t spec_stride, uint8_t *d_rows,
+                                                                  size_t row_stride, int max_rows, int32_t *rx_of_row, int32_t *ent_of_row,
+                                                                  int32_t *blk_of_row, int32_t *bin_of_row);
+
 // kg_post.hip, for kg_rxbank.hip: how many kg_post_set_mode / kg_post_set_sam_mparam calls channel ch has seen (each clears
 // s->isChanNull, rx_sound_cmd.cpp:202-228), and its s->SAM_mparam
 __attribute__((visibility("hidden"))) uint32_t kg_post_mode_cmds_(const kg_post *p, int ch);

@@ -74,6 +74,18 @@ struct kg_rxbank {
     std::vector<int32_t> spec_rx, spec_inst, spec_blk, spec_rx2, spec_inst2, spec_blk2;     // the last step's map; this pass's
     std::vector<char> sam_null;                 // scratch, per active entry: runs kg_post in channel-null SAM this step
     std::vector<int32_t> pb_inst, pb_n, pb_base, null_row, null_list, null_each, null_inst, null_n, null_base;
+    // the FFT extension (extensions/FFT/FFT.cpp; kg_fftext), made by the first kg_rxbank_fftext_* call: a bank that was never told holds
+    // nothing for it and enqueues what it always did.  While a receiver's function is on, both filters store their filtered spectra
+    // (receive_FFT(POST_FILTERED), fastfir.cpp:293-302) and the extension runs ONCE per step over the step's blocks, on the tail stream.
+    kg_fftext *fx; double fx_rate;
+    std::vector<char> fx_on;                    // per receiver: run != FUNC_OFF
+    // d_fxpost, in blocks of 1024 complex floats (the taps of a CFastFIR call lie by LIST ENTRY): [nrx][blocks_max] m_PassbandFIR's
+    // blocks of the step, entry i of the step's active list; then [blocks_max][nrx] m_chan_null_FIR's, entry p of sound block blk's list
+    kg_dbuf<float2> d_fxpost; size_t fx_stride;
+    kg_dbuf<unsigned char> d_fxrows; size_t fx_max;    // [fx_max][1024] u8: the step's rows in map order
+    int fx_n;                                   // rows of the last step
+    std::vector<int32_t> fx_rx, fx_blk, fx_bin, fx_list, fx_nblk, fx_inst, fx_row;      // the last step's map; this pass's entries
+    std::vector<int32_t> fx_blk0, fx_ent, fx_nullpos;                                   // an entry's first sound block; scratch
     // device buffers
     kg_dbuf<short2> d_wfiq; size_t wf_stride;         // [nrx][wf_stride] iq_t: a one-shot receiver uses pairs 0 .. 8191 of its row, an overlapped one all of it
     kg_dbuf<unsigned char> d_rows, d_pkts;         // [frame][1024], [frame][BANK_PKT_STRIDE]
@@ -155,7 +167,7 @@ static int bank_pass(kg_rxbank *b, const void *d_adc, bool plan)
     }
     const int NA = (int) b->act.size();
     const int32_t *act = b->act.data();
-    int nrec_max = 0, nfir_max = 0, nspec = 0;
+    int nrec_max = 0, nfir_max = 0, nspec = 0, nfx = 0;
     bool any_pb = false;
     if (!plan) for (int k = 0; k < NR; k++) { b->last_nrec[k] = 0; b->last_nfir[k] = 0; }
     // ---- audio chain (side stream): rx.v -> rx_iq_t -> snd_service() unpack -> CFastFIR; the tail: S-meter, CAgc, detector, ADPCM
@@ -187,6 +199,8 @@ static int bank_pass(kg_rxbank *b, const void *d_adc, bool plan)
         // which blocks of this step give a row: the reference's rule (kg_spec.h), walked on a copy of the mirror that the real
         // pass commits.  Rows are numbered in emission order, receiver by receiver.
         nspec = 0;
+        b->fx_list.clear(); b->fx_nblk.clear(); b->fx_inst.clear(); b->fx_row.clear(); b->fx_blk0.clear();
+        std::fill(b->fx_nullpos.begin(), b->fx_nullpos.end(), 0);
         for (int i = 0; i < NA; i++) {
             const int k = act[i];
             kg_spec::emit_t m = b->spec_mirror[k];
@@ -196,6 +210,17 @@ static int bank_pass(kg_rxbank *b, const void *d_adc, bool plan)
             b->sam_null[i] = mode == KG_POST_SAM && (kg_post_sam_mparam_(b->post, k) & 3);
             const int nblk = (kg_fir_pos(b->fir, k) + b->h_nrec[i]) / KG_FIR_OUT;
             b->pb_inst[i] = KG_SPEC_PASSBAND; b->pb_n[i] = 0; b->pb_base[i] = 0;
+            if (b->fx && b->fx_on[k] && nblk > 0) {        // each filter hands every block of its own to fft_data, which takes one instance's
+                b->fx_list.push_back(k); b->fx_nblk.push_back(nblk); b->fx_inst.push_back(KG_SPEC_PASSBAND);
+                b->fx_row.push_back((int32_t) ((size_t) i * b->blocks_max)); b->fx_blk0.push_back(0);
+            }
+            if (b->fx && b->sam_null[i])                   // where sound block blk's channel-null call leaves this receiver's spectrum
+                for (int blk = 0; blk < nblk; blk++) {
+                    const int p = b->fx_nullpos[blk]++;
+                    if (!b->fx_on[k]) continue;
+                    b->fx_list.push_back(k); b->fx_nblk.push_back(1); b->fx_inst.push_back(KG_SPEC_CHAN_NULL);
+                    b->fx_row.push_back((int32_t) ((size_t) NR * b->blocks_max + (size_t) blk * NR + p)); b->fx_blk0.push_back(blk);
+                }
             for (int blk = 0; blk < nblk; blk++) {
                 const kg_spec::rows_t r = kg_spec::emit_block(m, b->spec_on[k] != 0, sam_family, b->sam_null[i] != 0);
                 if (r.passband) {                          // only ever the leading blocks: the mirror leaves PASSBAND once per step at most
@@ -208,7 +233,11 @@ static int bank_pass(kg_rxbank *b, const void *d_adc, bool plan)
             }
             b->spec_mirror2[k] = m;
         }
-        if (any_pb) {
+        if (!b->fx_list.empty()) {
+            const kg_fir_spec_req req = {b->d_spec, KG_SPEC_ROW, b->spec_max * KG_SPEC_ROW, b->pb_inst.data(), b->pb_n.data(), b->pb_base.data()};
+            rc = kg_fir_process_post_(b->fir, act, NA, b->d_xin, b->nrec_max, b->h_nrec.data(), b->d_firo, b->firo_stride, b->h_nfir.data(),
+                                      any_pb ? &req : nullptr, b->d_fxpost, b->fx_stride);
+        } else if (any_pb) {
             const kg_fir_spec_req req = {b->d_spec, KG_SPEC_ROW, b->spec_max * KG_SPEC_ROW, b->pb_inst.data(), b->pb_n.data(), b->pb_base.data()};
             rc = kg_fir_process_rows_(b->fir, act, NA, b->d_xin, b->nrec_max, b->h_nrec.data(), b->d_firo, b->firo_stride, b->h_nfir.data(), &req);
         } else {
@@ -242,9 +271,13 @@ static int bank_pass(kg_rxbank *b, const void *d_adc, bool plan)
             if (!b->null_list.empty()) {
                 const int NN = (int) b->null_list.size();
                 const kg_fir_spec_req req = {b->d_spec, KG_SPEC_ROW, b->spec_max * KG_SPEC_ROW, b->null_inst.data(), b->null_n.data(), b->null_base.data()};
-                if ((rc = kg_fir_process_rows_(b->nullfir, b->null_list.data(), NN, b->d_agc + o, b->firo_stride, b->null_each.data(), nullptr, 0,
-                                               nullptr, &req)))
-                    return rc;
+                if (!b->fx_list.empty())                    // block blk of the step's channel-null spectra
+                    rc = kg_fir_process_post_(b->nullfir, b->null_list.data(), NN, b->d_agc + o, b->firo_stride, b->null_each.data(), nullptr, 0,
+                                              nullptr, &req, b->d_fxpost + ((size_t) NR * b->blocks_max + (size_t) blk * NR) * KG_FFTEXT_ROW, KG_FFTEXT_ROW);
+                else
+                    rc = kg_fir_process_rows_(b->nullfir, b->null_list.data(), NN, b->d_agc + o, b->firo_stride, b->null_each.data(), nullptr, 0,
+                                              nullptr, &req);
+                if (rc) return rc;
             }
             tk.lap(b, PF_POST, pf);
             // the real modes' blocks go through the ADPCM coder, the stereo modes' (IS_STEREO: IQ, SAS, QAM) as (s2_t) pairs of the agc
@@ -268,6 +301,15 @@ static int bank_pass(kg_rxbank *b, const void *d_adc, bool plan)
                     return rc;
             }
             tk.lap(b, PF_ADPCM, pf);
+        }
+        if (!b->fx_list.empty()) {                        // fft_data over the step's blocks: one launch, behind both filters
+            rc = kg_fftext_process_rows_(b->fx, b->fx_list.data(), (int) b->fx_list.size(), b->fx_nblk.data(), b->fx_inst.data(), b->fx_row.data(),
+                                         (const float *) b->d_fxpost.p, KG_FFTEXT_ROW, b->d_fxrows, KG_FFTEXT_ROW, (int) b->fx_max,
+                                         plan ? nullptr : b->fx_rx.data(), plan ? nullptr : b->fx_ent.data(), plan ? nullptr : b->fx_blk.data(),
+                                         plan ? nullptr : b->fx_bin.data());
+            if (rc < 0) return rc;
+            nfx = rc;
+            if (!plan) for (int r = 0; r < nfx; r++) b->fx_blk[r] += b->fx_blk0[b->fx_ent[r]];       // the sound block of the step
         }
         if (!plan) {
             KG_HIP(hipEventRecord(b->ev_tail, b->s_tail));
@@ -357,6 +399,7 @@ static int bank_pass(kg_rxbank *b, const void *d_adc, bool plan)
             b->spec_cmds[act[i]] = kg_post_mode_cmds_(b->post, act[i]);
         }
         b->spec_n = nspec;
+        b->fx_n = nfx;
         b->spec_rx.swap(b->spec_rx2); b->spec_inst.swap(b->spec_inst2); b->spec_blk.swap(b->spec_blk2);
         kg_rxbank_step_info &s = b->last;
         const int first = NA > 0 ? act[0] : 0;             // the step's scalar audio fields: the lowest-numbered active receiver's
@@ -568,7 +611,8 @@ static int bank_init(kg_rxbank *b)
         // (+ 64 per receiver: the blankers' tables; the audio spectrum: 12 bytes per receiver in CFastFIR's table, and per sound block
         // the channel-null filter's table of 8 ints per receiver and its alignment; + 64 per table -- up to 12 and 4 per sound
         // block -- for the 64-byte alignment arena_stage gives every entry)
-        b->slot_bytes = (8192 + 64 * blocks_max + 64 * (12 + 4 * blocks_max) + (size_t) (448 + 16 + (12 + 32) * blocks_max) * nrx + 63) & ~(size_t) 63;
+        // (+ the FFT extension's table: 2 groups of 32 bytes and 2 ops of 16 per sound block, per receiver)
+        b->slot_bytes = (8192 + 64 * blocks_max + 64 * (13 + 4 * blocks_max) + (size_t) (448 + 16 + 64 + (12 + 32 + 32) * blocks_max) * nrx + 63) & ~(size_t) 63;
         b->spec_max = 2 * blocks_max * (size_t) nrx;                         // a passband and a channel-null row per sound block
     }
     KG_TRY(b->h_slots.alloc(b->slot_bytes * BANK_SLOTS, "kg_rxbank_create: slots"));
@@ -602,6 +646,8 @@ static int bank_init(kg_rxbank *b)
     b->sam_null.assign(nrx, 0); b->pb_inst.assign(nrx, KG_SPEC_PASSBAND); b->pb_n.assign(nrx, 0); b->pb_base.assign(nrx, 0);
     b->null_row.assign(b->blocks_max * (size_t) nrx, -1);
     b->null_each.assign(nrx, KG_FIR_OUT); b->null_inst.assign(nrx, KG_SPEC_CHAN_NULL);
+    b->fx = nullptr; b->fx_rate = 0; b->fx_on.assign(nrx, 0); b->fx_n = 0;
+    b->fx_stride = b->blocks_max * KG_FFTEXT_ROW; b->fx_max = b->blocks_max * (size_t) nrx;      // a receiver's function takes ONE instance's blocks
     memset(&b->arena, 0, sizeof b->arena);
     memset(&b->last, 0, sizeof b->last);
     KG_HIP(hipDeviceSynchronize());
@@ -614,6 +660,7 @@ void kg_rxbank_destroy(kg_rxbank *b)
     (void) hipSetDevice(b->device);
     for (hipStream_t s : {b->s_main, b->s_side, b->s_tail, b->s_ddc2, b->s_up}) if (s) (void) hipStreamSynchronize(s);
     if (b->c_main && b->c_side && b->c_tail) bank_set_arena(b, KG_ARENA_OFF);
+    kg_fftext_destroy(b->fx);
     kg_adpcm_destroy(b->adpcm); kg_post_destroy(b->post); kg_fir_destroy(b->nullfir); kg_fir_destroy(b->fir); kg_rxddc_destroy(b->rx); kg_nb_destroy(b->nb);
     kg_wf_destroy(b->wf); kg_ddc_destroy(b->ddc);
     kg_ctx_destroy(b->c_tail); kg_ctx_destroy(b->c_side); kg_ctx_destroy(b->c_main);
@@ -700,6 +747,90 @@ int kg_rxbank_spec_rows(kg_rxbank *b, void **d_rows, size_t *row_stride)
     return KG_OK;
 }
 
+// The extension's object and buffers, made whole or not at all by the first call that names the extension.  Drains the bank's streams.
+static int bank_fx_ensure(kg_rxbank *b)
+{
+    if (b->fx) return KG_OK;
+    KG_HIP(hipSetDevice(b->device));
+    for (hipStream_t s : {b->s_up, b->s_main, b->s_side, b->s_tail}) KG_HIP(hipStreamSynchronize(s));
+    kg_fftext *fx = nullptr;
+    int rc = kg_fftext_create(b->c_tail, b->nrx, &fx);
+    if (rc == KG_OK) rc = b->d_fxpost.alloc(2 * (size_t) b->nrx * b->fx_stride, "kg_rxbank_fftext: spectra");
+    if (rc == KG_OK) rc = b->d_fxrows.alloc(b->fx_max * KG_FFTEXT_ROW, "kg_rxbank_fftext: rows");
+    if (rc == KG_OK && (hipMemset(b->d_fxpost, 0, sizeof(float2) * 2 * (size_t) b->nrx * b->fx_stride) != hipSuccess ||
+                        hipMemset(b->d_fxrows, 0, b->fx_max * KG_FFTEXT_ROW) != hipSuccess)) {
+        kg_set_error("kg_rxbank_fftext: hipMemset failed");
+        rc = KG_ERR_HIP;
+    }
+    if (rc == KG_OK && b->fx_rate > 0) rc = kg_fftext_set_rate(fx, b->fx_rate);
+    if (rc) { kg_fftext_destroy(fx); b->d_fxpost.reset(); b->d_fxrows.reset(); return rc; }
+    for (std::vector<int32_t> *v : {&b->fx_rx, &b->fx_blk, &b->fx_bin, &b->fx_ent}) v->assign(b->fx_max, 0);
+    b->fx_nullpos.assign(b->blocks_max, 0);
+    b->fx = fx;
+    return KG_OK;
+}
+
+int kg_rxbank_fftext_set_rate(kg_rxbank *b, double sample_rate)
+{
+    KG_REQUIRE(b != nullptr, KG_ERR_INVALID, "kg_rxbank_fftext_set_rate: null argument");
+    KG_REQUIRE(sample_rate > 0 && sample_rate <= 1e12, KG_ERR_INVALID, "kg_rxbank_fftext_set_rate: sample rate %g", sample_rate);
+    if (b->fx) KG_TRY(kg_fftext_set_rate(b->fx, sample_rate));
+    b->fx_rate = sample_rate;
+    return KG_OK;
+}
+
+// `SET run=%d` (FFT.cpp:206-244): snd->isSAM and snd->mode == MODE_QAM are the bank's view of kg_post's mode NOW, as the reference reads them
+int kg_rxbank_fftext_set_run(kg_rxbank *b, int rx, int run)
+{
+    KG_REQUIRE(b && rx >= 0 && rx < b->nrx, KG_ERR_INVALID, "kg_rxbank_fftext_set_run: receiver %d", rx);
+    KG_REQUIRE(run >= KG_FFTEXT_OFF && run <= KG_FFTEXT_INTEG, KG_ERR_INVALID, "kg_rxbank_fftext_set_run: run %d (-1..2)", run);
+    KG_TRY(bank_fx_ensure(b));
+    const int mode = kg_post_get_mode(b->post, rx);
+    KG_TRY(kg_fftext_set_run(b->fx, rx, run, mode >= KG_POST_SAM && mode <= KG_POST_QAM, mode == KG_POST_QAM));
+    b->fx_on[rx] = run != KG_FFTEXT_OFF;
+    return KG_OK;
+}
+
+int kg_rxbank_fftext_set_itime(kg_rxbank *b, int rx, double itime)
+{
+    KG_REQUIRE(b && rx >= 0 && rx < b->nrx, KG_ERR_INVALID, "kg_rxbank_fftext_set_itime: receiver %d", rx);
+    KG_TRY(bank_fx_ensure(b));
+    return kg_fftext_set_itime(b->fx, rx, itime);
+}
+
+int kg_rxbank_fftext_clear(kg_rxbank *b, int rx)
+{
+    KG_REQUIRE(b && rx >= 0 && rx < b->nrx, KG_ERR_INVALID, "kg_rxbank_fftext_clear: receiver %d", rx);
+    KG_TRY(bank_fx_ensure(b));
+    return kg_fftext_clear(b->fx, rx);
+}
+
+kg_fftext *kg_rxbank_fftext(kg_rxbank *b) { return b ? b->fx : nullptr; }
+
+int kg_rxbank_fftext_max(kg_rxbank *b)
+{
+    KG_REQUIRE(b != nullptr, KG_ERR_INVALID, "kg_rxbank_fftext_max: null argument");
+    return (int) b->fx_max;
+}
+
+int kg_rxbank_fftext_map(kg_rxbank *b, int32_t *rx_of_row, int32_t *blk_of_row, int32_t *bin_of_row)
+{
+    KG_REQUIRE(b != nullptr, KG_ERR_INVALID, "kg_rxbank_fftext_map: null argument");
+    for (int r = 0; r < b->fx_n; r++) {
+        if (rx_of_row) rx_of_row[r] = b->fx_rx[r];
+        if (blk_of_row) blk_of_row[r] = b->fx_blk[r];
+        if (bin_of_row) bin_of_row[r] = b->fx_bin[r];
+    }
+    return b->fx_n;
+}
+
+int kg_rxbank_fftext_rows(kg_rxbank *b, uint8_t **d_rows, size_t *row_stride)
+{
+    KG_REQUIRE(b && d_rows && row_stride, KG_ERR_INVALID, "kg_rxbank_fftext_rows: null argument");
+    *d_rows = b->d_fxrows; *row_stride = KG_FFTEXT_ROW;            // null until the extension was named
+    return KG_OK;
+}
+
 int kg_rxbank_set_wf(kg_rxbank *b, int rx, uint64_t phase_inc, int decim, int overlapped)
 {
     KG_REQUIRE(b != nullptr, KG_ERR_INVALID, "kg_rxbank_set_wf: null argument");
@@ -730,6 +861,8 @@ int kg_rxbank_leave(kg_rxbank *b, int rx)
 {
     KG_REQUIRE(b && rx >= 0 && rx < b->nrx, KG_ERR_INVALID, "kg_rxbank_leave: receiver %d", rx);
     b->active[rx] = 0;
+    b->fx_on[rx] = 0;                                      // ext_unregister_receive_FFT_samps at the connection's end; its fft_t is gone with it
+    if (b->fx) KG_TRY(kg_fftext_restart(b->fx, rx));
     return KG_OK;
 }
 
@@ -754,6 +887,8 @@ int kg_rxbank_join(kg_rxbank *b, int rx)
     b->wf_set[rx] = 0; b->ring_w[rx] = 0; b->ring_total[rx] = 0;
     b->spec_on[rx] = 0; kg_spec::emit_clear(b->spec_mirror[rx]);      // memset(snd_t): specAF_FFT NULL, isChanNull false
     b->spec_cmds[rx] = kg_post_mode_cmds_(b->post, rx);
+    b->fx_on[rx] = 0;                                      // the extension's state is the connection's: function off, nothing latched, sums zero
+    if (b->fx && (rc = kg_fftext_restart(b->fx, rx))) return rc;
     b->nbc[rx] = kg_rxbank::nb_cmd{};                      // memset(snd_t) / memset(wf_inst_t): algo NB_OFF, enables and params 0;
     if ((rc = kg_wf_set_nb(b->wf, rx, 0))) return rc;     // the blankers' states stay (the reference's CNoiseProc arrays are globals)
     b->active[rx] = 1;

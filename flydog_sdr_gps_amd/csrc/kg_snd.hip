@@ -646,6 +646,13 @@ int kg_fir_process_rows_(kg_fir *f, const int32_t *chans, int nch, const void *d
                             "kg_fir_process_rows_");
 }
 
+int kg_fir_process_post_(kg_fir *f, const int32_t *chans, int nch, const void *d_in, size_t in_stride, const int32_t *n_each,
+                         void *d_out, size_t out_stride, int32_t *nout, const kg_fir_spec_req *req, void *d_post, size_t tap_stride)
+{
+    return fir_process_impl(f, chans, nch, d_in, in_stride, 0, d_out, out_stride, nout, nullptr, d_post, tap_stride, n_each, req,
+                            "kg_fir_process_post_");
+}
+
 static int fir_process_impl(kg_fir *f, const int32_t *chans, int nch, const void *d_in, size_t in_stride, int n,
                             void *d_out, size_t out_stride, int32_t *nout, void *d_pre, void *d_post, size_t tap_stride,
                             const int32_t *n_each, const kg_fir_spec_req *spec, const char *who)

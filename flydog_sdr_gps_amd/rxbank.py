@@ -253,6 +253,44 @@ class RxBank:
             self.ctx.download(int(d.value), out)
         return out[:, :1024]
 
+    def fftext_set_rate(self, sample_rate):
+        """what ext_update_get_sample_rateHz answers for the FFT extension (extensions/FFT/FFT.cpp:79)"""
+        check(self.lib.kg_rxbank_fftext_set_rate(self.h, float(sample_rate)), "kg_rxbank_fftext_set_rate")
+
+    def fftext_set_run(self, rx, run):
+        """`SET run=%d` of the FFT extension (fftext.OFF / WF / SPEC / INTEG); isSAM and QAM are read from receiver rx's mode now"""
+        check(self.lib.kg_rxbank_fftext_set_run(self.h, int(rx), int(run)), "kg_rxbank_fftext_set_run")
+
+    def fftext_set_itime(self, rx, itime):
+        check(self.lib.kg_rxbank_fftext_set_itime(self.h, int(rx), float(itime)), "kg_rxbank_fftext_set_itime")
+
+    def fftext_clear(self, rx):
+        check(self.lib.kg_rxbank_fftext_clear(self.h, int(rx)), "kg_rxbank_fftext_clear")
+
+    @property
+    def fftext(self):
+        """the bank's FftExt (None until one of the fftext_* commands was sent): due(), state()"""
+        from . import fftext as fx_mod
+        h = self.lib.kg_rxbank_fftext(self.h)
+        return borrow(fx_mod.FftExt, self.ctx, h, nchan=self.nrx) if h else None
+
+    def fftext_map(self):
+        """-> (rx_of_row, blk_of_row, bin_of_row) of the last step's extension rows, per receiver in block order"""
+        m = check(self.lib.kg_rxbank_fftext_max(self.h), "kg_rxbank_fftext_max")
+        rx_of, blk, bins = (np.zeros(m, np.int32) for _ in range(3))
+        n = check(self.lib.kg_rxbank_fftext_map(self.h, ptr(rx_of), ptr(blk), ptr(bins)), "kg_rxbank_fftext_map")
+        return rx_of[:n], blk[:n], bins[:n]
+
+    def fftext_rows(self):
+        """-> uint8 [rows, 1024]: the last step's extension rows (after sync()), row r described by fftext_map()[.][r]"""
+        n = check(self.lib.kg_rxbank_fftext_map(self.h, None, None, None), "kg_rxbank_fftext_map")
+        d, stride = C.c_void_p(), C.c_size_t()
+        check(self.lib.kg_rxbank_fftext_rows(self.h, C.byref(d), C.byref(stride)), "kg_rxbank_fftext_rows")
+        out = np.zeros((n, int(stride.value)), np.uint8)
+        if n:
+            self.ctx.download(int(d.value), out)
+        return out[:, :1024]
+
     def set_little_endian(self, rx, little_endian):
         check(self.lib.kg_rxbank_set_little_endian(self.h, int(rx), int(bool(little_endian))), "kg_rxbank_set_little_endian")
         self.little_endian[rx] = bool(little_endian)

@@ -1161,6 +1161,80 @@ int kg_fir_process_spec_dev(kg_fir *fir, const int32_t *chans, int nch, const vo
                             const int32_t *n_each, void *d_out, size_t out_stride, int32_t *nout, void *d_rows,
                             size_t row_stride, const int32_t *inst, void *d_post, size_t tap_stride);
 
+/* ---------------------------------------------------------------------------
+ * The FFT extension (extensions/FFT/FFT.cpp), the one consumer of receive_FFT(POST_FILTERED): fft_msgs (:193-261) and fft_data
+ * (:69-191) over the filtered spectrum of every completed CFastFIR block (what kg_fir_process_taps_dev / kg_fir_process_spec_dev
+ * leave in d_post).  Three functions (:66): wf, a waterfall line per block; spec, a spectrum whose sending is limited to one per
+ * 100 ms; integ, the integrator -- the passband power folded into up to 200 time bins of 1024 sums over a period the user sets, a
+ * line per block.  A row is 1024 bytes: per column pwr -- re * re of this block outside integ (the real part only, :116), the bin's
+ * running sum of re * re + im * im under it (:127-139) -- then 10.0 * log10f(pwr * scale + 1e-30) clamped to [-200, 0], decremented,
+ * (u1_t) (int), stored at column ^ 512 (:157-167).  The 1025-byte message of :188 is the row's bin followed by the row.
+ * A column's sum is added to in block order, one addition per block, and the device's log10f is the host libm's bit for bit: sums and
+ * rows are an exact function of the spectra (csrc/kg_fftext.h is the one definition for device and host).  NaN input is outside the
+ * contract as for the audio spectrum rows; +-inf and overflow give byte 255.
+ * The schedule (:72-101: which instance, the latched reset, the bin of a block, the blocks dropped at bin >= 200) depends on no
+ * sample: it runs on the host, nothing here synchronises but the calls that say so.
+ *   kg_fftext_create    nchan channels (1 .. 1024), each with 200 x 1024 float sums (800 KiB of device memory) and ncma[200]; a
+ *                       channel starts like a fresh connection: function off, time 0, nothing latched, sums zero.
+ *   kg_fftext_set_rate  what ext_update_get_sample_rateHz answers (:79), a double; finite and above 0, else KG_ERR_INVALID.
+ *   kg_fftext_set_run   `SET run=%d` (:206-244); is_sam / is_qam: snd->isSAM and snd->mode == MODE_QAM AT THE COMMAND.  Chooses the
+ *                       instance (KG_SPEC_CHAN_NULL only for KG_FFTEXT_SPEC while is_sam) and the scale: (float) (20.0 / (float)
+ *                       (32767^2 * 1024^2)) times 1e4 (wf, integ), 1e6 (spec) or 100 (spec while is_sam); zeroes the limiter's
+ *                       last_ms under spec.  Does NOT latch a reset: the sums of the function before carry over, as in the
+ *                       reference.  run outside -1 .. 2: KG_ERR_INVALID, nothing changed.
+ *   kg_fftext_set_itime `SET itime=%lf` (:246-252): stores the period and latches a reset.  Any double is stored.
+ *   kg_fftext_clear     `SET clear` (:254-258): latches a reset.
+ *   kg_fftext_restart   ours: the channel as kg_fftext_create left it (a new connection); the sums are zeroed by the next call that
+ *                       takes a block of it, or read as zero by kg_fftext_state.
+ * A latched reset is applied ahead of the first block of the channel's instance (:78-90): fft_sec = 1.0 / (rate * 2 / 1024), bins =
+ * trunc(time / fft_sec), fi = 0, sums and ncma zeroed.  Under integ the block's bin is trunc(fmod(fi, time) / time * bins), then
+ * fi += fft_sec, and a block whose bin is 200 or more is dropped (:92-98); otherwise the bin is 0. */
+typedef struct kg_fftext kg_fftext;
+enum { KG_FFTEXT_OFF = -1, KG_FFTEXT_WF = 0, KG_FFTEXT_SPEC = 1, KG_FFTEXT_INTEG = 2 };     /* FUNC_*, FFT.cpp:66 */
+#define KG_FFTEXT_ROW 1024                                 /* INTEG_WIDTH, FFT.cpp:33 */
+#define KG_FFTEXT_MAX_BINS 200                             /* MAX_BINS, FFT.cpp:38 */
+#define KG_FFTEXT_UPDATE_MS 100                            /* UPDATE_MS, FFT.cpp:177 */
+typedef struct kg_fftext_info {
+    int32_t run, instance;                 /* KG_FFTEXT_*, KG_SPEC_* */
+    float fft_scale, spectrum_scale;
+    int32_t bins, reset;                   /* reset: 1 while a reset is latched */
+    uint32_t last_ms;
+    int32_t reserved;
+    double fi, fft_sec, time;
+} kg_fftext_info;
+int kg_fftext_create(kg_ctx *ctx, int nchan, kg_fftext **out);
+void kg_fftext_destroy(kg_fftext *fx);
+int kg_fftext_set_rate(kg_fftext *fx, double sample_rate);
+int kg_fftext_set_run(kg_fftext *fx, int ch, int run, int is_sam, int is_qam);
+int kg_fftext_set_itime(kg_fftext *fx, int ch, double itime);
+int kg_fftext_clear(kg_fftext *fx, int ch);
+int kg_fftext_restart(kg_fftext *fx, int ch);
+/* fft_data for nblk[i] blocks of channel chans[i] from the filter of instance inst[i] (KG_SPEC_*), entries in list order, a
+ * channel's blocks in block order (a channel may be listed more than once: passband and channel-null blocks interleaved): block b of
+ * entry i is the 1024 complex floats at d_spec + 2 * (i*spec_stride + 1024 b) (spec_stride in complex samples; d_spec 8-byte
+ * aligned).  Every block the schedule takes gives one row, numbered from 0 in that order: row r at d_rows + r*row_stride (d_rows and
+ * row_stride multiples of 4 bytes, row_stride >= 1024), and, on the host and without a sync, its channel, its list entry, the
+ * block's index within that entry and its bin in rx_of_row / ent_of_row / blk_of_row / bin_of_row[r] (max_rows entries each, any may
+ * be NULL).  Returns the number of
+ * rows.  ONE kernel launch (none when no block is taken and nothing is to be zeroed).  1 <= nch <= 65536, 0 <= nblk[i] <= 4096.
+ * Refused, with nothing changed and nothing enqueued: KG_ERR_INVALID for an argument out of range or more rows than max_rows;
+ * KG_ERR_STATE for what the reference leaves undefined -- no rate set, an integ block while the period is not finite or not above 0
+ * (fmod(fi, 0) is NaN and (int) of it indexes pwr), a reset whose time / fft_sec does not fit an int.
+ * Read: 8 * 1024 * nblk[i] bytes of row i of d_spec.  Written: 1024 bytes of each of the returned number of rows.  Enqueue only. */
+int kg_fftext_process_dev(kg_fftext *fx, const int32_t *chans, int nch, const int32_t *nblk, const int32_t *inst, const float *d_spec,
+                          size_t spec_stride, uint8_t *d_rows, size_t row_stride, int max_rows, int32_t *rx_of_row, int32_t *ent_of_row,
+                          int32_t *blk_of_row, int32_t *bin_of_row);
+/* the same on host memory; synchronises */
+int kg_fftext_process(kg_fftext *fx, const int32_t *chans, int nch, const int32_t *nblk, const int32_t *inst, const float *spec,
+                      size_t spec_stride, uint8_t *rows, size_t row_stride, int max_rows, int32_t *rx_of_row, int32_t *ent_of_row,
+                      int32_t *blk_of_row, int32_t *bin_of_row);
+/* "limit spectrum update rate" (:174-186), host only, the clock is the caller's: 1 when the row of a block handed over at now_ms is
+ * to be sent (ext_send_msg_data, :188), 0 when it is held back.  Only KG_FFTEXT_SPEC is limited: fires when now_ms > last_ms + 100;
+ * then last_ms += 100 if it is non-zero, else last_ms = now_ms.  Call it once per row, in row order. */
+int kg_fftext_due(kg_fftext *fx, int ch, uint32_t now_ms);
+/* Channel ch's state; pwr (200 x 1024 floats) and ncma (200) may be NULL.  With pwr it synchronises. */
+int kg_fftext_state(kg_fftext *fx, int ch, kg_fftext_info *info, float *pwr, int32_t *ncma);
+
 /* Diagnostics: re-runs the 4096-point stage of the forward FFT of `block` in a
  * stamped build of the kernel and returns 4 s_memrealtime readings (100 MHz):
  * start, inputs + twiddles loaded, transform done, results stored. */
@@ -1263,6 +1337,32 @@ kg_fir *kg_rxbank_null_fir(kg_rxbank *bank);
 int kg_rxbank_spec_max(kg_rxbank *bank);
 int kg_rxbank_spec_map(kg_rxbank *bank, int32_t *rx_of_row, int32_t *inst_of_row, int32_t *blk_of_row);
 int kg_rxbank_spec_rows(kg_rxbank *bank, void **d_rows, size_t *row_stride);
+
+/* The FFT extension of the bank's receivers (kg_fftext above; extensions/FFT/FFT.cpp).  The first of these calls makes the bank's
+ * kg_fftext object and two buffers (the step's filtered spectra of both filters, the rows) and drains the bank's streams; a bank that
+ * was never told holds nothing for the extension and enqueues exactly what it enqueued without it.
+ *   kg_rxbank_fftext_set_rate   what ext_update_get_sample_rateHz answers (the bank's audio rate as the host knows it, a double)
+ *   kg_rxbank_fftext_set_run    `SET run=%d`: snd->isSAM and snd->mode == MODE_QAM are read from the receiver's kg_post mode AT THE
+ *                               COMMAND, as the reference reads them (a later `SET mod=` does not move the instance or the boost)
+ *   kg_rxbank_fftext_set_itime  `SET itime=%lf`;   kg_rxbank_fftext_clear  `SET clear`
+ * While a receiver's function is on, its passband filter's spectrum of every completed block is stored, and in channel-null SAM the
+ * second filter's too; the extension runs once per step, in one launch over the step's blocks of all such receivers, behind both
+ * filters.  spec chosen in a SAM-family mode listens to the second filter, which is fed in channel-null SAM only: in plain SAM the
+ * function shows nothing, as in the reference.  kg_rxbank_join and kg_rxbank_leave put the receiver's extension state back to a new
+ * connection's (function off, period 0, sums zero).  A step whose blocks the extension refuses (an integ block before any period was
+ * set: KG_ERR_STATE) is refused as a whole, nothing enqueued.
+ *   kg_rxbank_fftext       the object (NULL until one of the calls above): kg_fftext_due per row, kg_fftext_state
+ *   kg_rxbank_fftext_map   the rows of the last step, row r at d_rows + r*row_stride: receiver, sound block of the step and bin (arrays
+ *                          of kg_rxbank_fftext_max() entries, any may be NULL), per receiver in block order.  Returns the number of rows.
+ *   kg_rxbank_fftext_rows  the device buffer (NULL until the extension was named; read behind kg_rxbank_sync). */
+int kg_rxbank_fftext_set_rate(kg_rxbank *bank, double sample_rate);
+int kg_rxbank_fftext_set_run(kg_rxbank *bank, int rx, int run);
+int kg_rxbank_fftext_set_itime(kg_rxbank *bank, int rx, double itime);
+int kg_rxbank_fftext_clear(kg_rxbank *bank, int rx);
+kg_fftext *kg_rxbank_fftext(kg_rxbank *bank);
+int kg_rxbank_fftext_max(kg_rxbank *bank);
+int kg_rxbank_fftext_map(kg_rxbank *bank, int32_t *rx_of_row, int32_t *blk_of_row, int32_t *bin_of_row);
+int kg_rxbank_fftext_rows(kg_rxbank *bank, uint8_t **d_rows, size_t *row_stride);
 /* CmdSetWFFreq + CmdSetWFDecim + the sampler mode sample_wf() decides on (rx/rx_waterfall.cpp:962-1008):
  *   overlapped == 0   CmdWFReset + the one-shot sampler every step: the non-overlapped frame (:1005-1041); needs
  *                     8192 * decim <= adc_samples_per_step
