@@ -16,9 +16,11 @@
 //
 // The per-seam objects are the bank's and are configured with their own entry points (kg_rxbank_ddc() ... kg_rxbank_adpcm());
 // what the bank adds is the step: which kernel goes on which of its three streams (waterfall chain, audio chain, the two
-// sequential coders), the events between them, and ONE upload per step for the small tables of all stages: every entry point
-// below is called twice per step, first in the context's PLAN mode (kg_common.h, kg_arena: tables collected, nothing
-// launched, no state advanced), then -- behind the one transfer -- for real.
+// sequential coders), the events between them, and ONE upload per step for the small tables of all stages.  A step is
+//   plan      bank_plan_step decides what the step is -- lists, rows, ring moves, frames, every next value -- from host state alone
+//   enqueue   bank_pass calls the entry points as the plan says, twice: first in the context's PLAN mode (kg_common.h, kg_arena:
+//             tables collected, nothing launched, no state advanced), then -- behind the one transfer -- for real
+//   commit    bank_commit moves the plan's next values and maps into the bank, after a real pass that succeeded
 #include "kg_common.h"
 #include "kg_nb.h"
 #include "kg_spec.h"
@@ -45,47 +47,91 @@ __global__ __launch_bounds__(256) void rxbank_move_kernel(short2 *__restrict__ i
     for (int i = threadIdx.x; i < m.cnt; i += 256) row[m.dst + i] = row[m.src + i];
 }
 
-struct kg_rxbank {
-    int device, nrx, mode, decim_rx;
+// the noise-blanker command state of snd_t and wf_inst_t (rx/rx_sound_cmd.cpp:454-501, :660-672)
+struct bank_nb_cmd {
+    int algo, snd_en[4], wf_en[4];
+    float snd_param[4][8], wf_param[4][8];
+    int wf_change[4], wf_setup;
+};
 
+// One receiver.  Connections come and go one at a time (rx/rx_sound.cpp:264-269: every c2s_sound() has its own CFastFIR position,
+// sequence number and loop): a receiver is stepped while `active`; its audio DDC / CFastFIR were reset when IT joined, so what a
+// step yields -- records, sound blocks -- is per receiver.
+struct bank_rx {
+    // the connection's: kg_rxbank_join starts all of these over
+    char active = 1;
+    uint32_t snd_seq = 0;                       // sound blocks emitted since it joined (the seq of its packets)
+    int32_t last_nrec = 0, last_nfir = 0;       // the last step's counts (kg_rxbank_audio_map)
+    char wf_set = 0;
+    long ring_w = 0, ring_total = 0;            // overlapped: next write position, outputs written since the sampler was set
+    // the audio spectrum (`SET spc_=2`, rx/rx_sound.cpp:175-220): s->specAF_FFT != NULL, the host's mirror of s->specAF_instance /
+    // s->isChanNull and the kg_post mode commands it has seen (each clears the mirror)
+    char spec_on = 0;
+    kg_spec::emit_t spec_mirror = {KG_SPEC_PASSBAND};
+    uint32_t spec_cmds = 0;
+    char fx_on = 0;                             // the FFT extension's run != FUNC_OFF
+    bank_nb_cmd nbc = {};
+    // the settings a join leaves alone
+    int decim = 0; char overlapped = 0;         // kg_rxbank_set_wf
+    char little_endian = 0;                     // s->little_endian
+    kg_wf_pkt_info pkt = {0, 0, 0, 1};
+};
+
+// a sound block's channel lists, in the order they are enqueued
+enum { BL_POST = 0, BL_NULL, BL_REAL, BL_IQ_BE, BL_IQ_LE, BL_N };
+
+// What one step is.  bank_plan_step fills it from host state; both enqueue passes read it; bank_commit moves it into the bank.
+// The vectors keep their capacity: a step allocates nothing.
+struct bank_plan {
+    // the active list: entry i is receiver act[i]
+    std::vector<int32_t> act, nrec, nfir, mode;         // rx_iq_t records and CFastFIR outputs of the step, the kg_post mode
+    std::vector<uint8_t> enabled;                       // per RECEIVER: active
+    std::vector<char> sam_null;                         // runs kg_post in channel-null SAM this step (SAM_mparam & 3)
+    int nrec_max, nfir_max;
+    std::vector<int32_t> nb_list, nb_cnt;               // the blanked receivers (NB_STD) and their record counts
+    // the audio spectrum's rows in emission order, receiver by receiver; CFastFIR's request per entry
+    int nspec; bool any_pb;
+    std::vector<int32_t> spec_rx, spec_inst, spec_blk, pb_inst, pb_n, pb_base;
+    std::vector<int32_t> null_row;                      // [entry][blocks_max]: the channel-null row of a sound block, or -1
+    std::vector<int32_t> null_each, null_inst;          // constants: 512 samples, KG_SPEC_CHAN_NULL
+    // the FFT extension's entries: receiver, blocks, instance, where the spectra lie in d_fxpost, the entry's first sound block
+    std::vector<int32_t> fx_list, fx_nblk, fx_inst, fx_row, fx_blk0, fx_nullpos;
+    // per sound block: list j of block blk is blk_chan[blk_at[BL_N * blk + j] .. blk_at[BL_N * blk + j + 1]); beside a BL_NULL
+    // entry its row count and row
+    std::vector<int32_t> blk_chan, blk_at, blk_null_n, blk_null_base;
+    int at(int blk, int j) const { return blk_at[(size_t) BL_N * blk + j]; }
+    int count(int blk, int j) const { return blk_at[(size_t) BL_N * blk + j + 1] - blk_at[(size_t) BL_N * blk + j]; }
+    // the waterfall chain: ring moves, where each entry's DDC writes, the frame table
+    std::vector<bank_move> moves;
+    std::vector<int64_t> out_off, max_out;
+    int nframes, wf_unset;                              // wf_unset: the first active receiver without a waterfall setting, or -1
+    std::vector<int32_t> chan_of; std::vector<uint64_t> frame_off; std::vector<kg_wf_pkt_info> pkt_step;
+    // the next values of what the step advances, per entry
+    std::vector<long> ring_w, ring_total;
+    std::vector<kg_spec::emit_t> mirror; std::vector<uint32_t> cmds;
+    // what the entry points hand back
+    std::vector<int32_t> got_nrec, got_nfir, pkt_bytes, fx_rx, fx_ent, fx_blk, fx_bin;
+    std::vector<int64_t> h_nw;
+    int fx_n;
+};
+
+struct kg_rxbank {
+    // configuration
+    int device, nrx, mode, decim_rx;
     size_t n;                                   // ADC samples per step
     size_t blocks_max;                          // sound blocks a receiver can complete in one step
+    float rescale, dc_i, dc_q; int spectral_inversion;      // snd_service() unpack, rx/data_pump.cpp:73-74,145-208
+    // streams, contexts, the per-seam objects
     hipStream_t s_main, s_side, s_tail, s_up;   // waterfall chain / audio chain / both sequential coders / the table upload
-    hipStream_t s_ddc2;                         // the waterfall DDC's second stream (R = 1 bypass, pass B of R <= 8 beside the rest)
+    hipStream_t s_ddc_side;                         // the waterfall DDC's second stream (R = 1 bypass, pass B of R <= 8 beside the rest)
     kg_ctx *c_main, *c_side, *c_tail;
     kg_ddc *ddc; kg_wf *wf; kg_rxddc *rx; kg_fir *fir; kg_post *post; kg_adpcm *adpcm;
     kg_nb *nb;                                  // m_NoiseProc_snd[] (the waterfall's blankers are kg_wf's)
-    // per receiver: the noise-blanker command state of snd_t and wf_inst_t (rx/rx_sound_cmd.cpp:454-501, :660-672)
-    struct nb_cmd {
-        int algo, snd_en[4], wf_en[4];
-        float snd_param[4][8], wf_param[4][8];
-        int wf_change[4], wf_setup;
-    };
-    std::vector<nb_cmd> nbc;
-    std::vector<int32_t> nb_list, nb_cnt;       // scratch: this step's blanked receivers and their record counts
-    // the audio spectrum (`SET spc_=2`, rx/rx_sound.cpp:175-220): per receiver s->specAF_FFT != NULL, the host's mirror of
-    // s->specAF_instance / s->isChanNull and the kg_post mode commands it has seen (each clears the mirror)
     kg_fir *nullfir;                            // m_chan_null_FIR[] (rx_sound.cpp:151), on the tail stream behind kg_post
-    std::vector<char> spec_on;
-    std::vector<kg_spec::emit_t> spec_mirror, spec_mirror2;
-    std::vector<uint32_t> spec_cmds;
-    kg_dbuf<unsigned char> d_spec; size_t spec_max;     // [spec_max][1024] u8: the step's rows in map order
-    int spec_n;                                 // rows of the last step
-    std::vector<int32_t> spec_rx, spec_inst, spec_blk, spec_rx2, spec_inst2, spec_blk2;     // the last step's map; this pass's
-    std::vector<char> sam_null;                 // scratch, per active entry: runs kg_post in channel-null SAM this step
-    std::vector<int32_t> pb_inst, pb_n, pb_base, null_row, null_list, null_each, null_inst, null_n, null_base;
     // the FFT extension (extensions/FFT/FFT.cpp; kg_fftext), made by the first kg_rxbank_fftext_* call: a bank that was never told holds
     // nothing for it and enqueues what it always did.  While a receiver's function is on, both filters store their filtered spectra
     // (receive_FFT(POST_FILTERED), fastfir.cpp:293-302) and the extension runs ONCE per step over the step's blocks, on the tail stream.
     kg_fftext *fx; double fx_rate;
-    std::vector<char> fx_on;                    // per receiver: run != FUNC_OFF
-    // d_fxpost, in blocks of 1024 complex floats (the taps of a CFastFIR call lie by LIST ENTRY): [nrx][blocks_max] m_PassbandFIR's
-    // blocks of the step, entry i of the step's active list; then [blocks_max][nrx] m_chan_null_FIR's, entry p of sound block blk's list
-    kg_dbuf<float2> d_fxpost; size_t fx_stride;
-    kg_dbuf<unsigned char> d_fxrows; size_t fx_max;    // [fx_max][1024] u8: the step's rows in map order
-    int fx_n;                                   // rows of the last step
-    std::vector<int32_t> fx_rx, fx_blk, fx_bin, fx_list, fx_nblk, fx_inst, fx_row;      // the last step's map; this pass's entries
-    std::vector<int32_t> fx_blk0, fx_ent, fx_nullpos;                                   // an entry's first sound block; scratch
     // device buffers
     kg_dbuf<short2> d_wfiq; size_t wf_stride;         // [nrx][wf_stride] iq_t: a one-shot receiver uses pairs 0 .. 8191 of its row, an overlapped one all of it
     kg_dbuf<unsigned char> d_rows, d_pkts;         // [frame][1024], [frame][BANK_PKT_STRIDE]
@@ -93,8 +139,19 @@ struct kg_rxbank {
     kg_dbuf<float2> d_xin, d_firo; size_t firo_stride; // [nrx][nrec_max], [nrx][firo_stride]
     kg_dbuf<short> d_s16; kg_dbuf<unsigned char> d_pay; // [nrx][firo_stride], [nrx][firo_stride / 2]
     kg_dbuf<float2> d_agc; kg_dbuf<unsigned char> d_iqpay; // [nrx][firo_stride] the AGC's complex output, [nrx][4 firo_stride] the IQ mode's payload
-    std::vector<char> little_endian;            // per receiver: s->little_endian
-    std::vector<int32_t> real_list, iq_le_list, iq_be_list;
+    kg_dbuf<unsigned char> d_spec; size_t spec_max;     // [spec_max][1024] u8: the step's rows in map order
+    // d_fxpost, in blocks of 1024 complex floats (the taps of a CFastFIR call lie by LIST ENTRY): [nrx][blocks_max] m_PassbandFIR's
+    // blocks of the step, entry i of the step's active list; then [blocks_max][nrx] m_chan_null_FIR's, entry p of sound block blk's list
+    kg_dbuf<float2> d_fxpost; size_t fx_stride;
+    kg_dbuf<unsigned char> d_fxrows; size_t fx_max;    // [fx_max][1024] u8: the step's rows in map order
+    // the receivers, and the step being made
+    std::vector<bank_rx> rcv;
+    bank_plan plan;
+    // the last step's maps (kg_rxbank_spec_map, _fftext_map, _frame_map) and info
+    int spec_n, fx_n;
+    std::vector<int32_t> spec_rx, spec_inst, spec_blk, fx_rx, fx_blk, fx_bin, frame_rx, pkt_bytes;
+    std::vector<uint64_t> frame_off;
+    kg_rxbank_step_info last;
     // step tables: BANK_SLOTS pinned host / device slots
     kg_arena arena; kg_hbuf<unsigned char> h_slots; kg_dbuf<unsigned char> d_slots; size_t slot_bytes;
     hipEvent_t ev_end[BANK_SLOTS][3];           // behind a step's last enqueue on main / side / tail
@@ -102,24 +159,6 @@ struct kg_rxbank {
     hipEvent_t ev_tab, ev_fir, ev_tail, ev_frames, ev_pk;
     bool tail_pending, pk_pending;
     uint64_t step;
-    float rescale, dc_i, dc_q; int spectral_inversion;      // snd_service() unpack, rx/data_pump.cpp:73-74,145-208
-    // per receiver
-    std::vector<int> decim; std::vector<char> wf_set, overlapped;
-    // Connections come and go one at a time (rx/rx_sound.cpp:264-269: every c2s_sound() has its own CFastFIR position, sequence
-    // number and loop): a receiver is stepped while `active`; its audio DDC / CFastFIR were reset when IT joined, so what a step
-    // yields -- records, sound blocks -- is per receiver.
-    std::vector<char> active;
-    std::vector<uint32_t> snd_seq;              // per receiver: sound blocks emitted since it joined (the seq of its packets)
-    std::vector<int32_t> last_nrec, last_nfir;  // per receiver: the last step's counts (kg_rxbank_audio_map)
-    std::vector<int32_t> act, blk_list, nfir_act;   // scratch: this step's active receivers; one sound block's receivers
-    std::vector<long> ring_w, ring_total;       // overlapped: next write position, outputs written since the sampler was set
-    std::vector<kg_wf_pkt_info> pkt;
-    // scratch of a step
-    std::vector<int32_t> all, h_nrec, h_nfir, chan_of, pkt_bytes, rx_of_frame;
-    std::vector<int64_t> out_off, max_out, h_nw; std::vector<uint64_t> frame_off;
-    std::vector<uint8_t> enabled; std::vector<bank_move> moves; std::vector<kg_wf_pkt_info> pkt_step;
-    std::vector<long> ring_w2, ring_total2;
-    kg_rxbank_step_info last;
     // where the host's share of a step goes (kg_rxbank_host_profile): seconds per phase, summed over `prof_steps` steps
     double prof[16]; uint64_t prof_steps;
 };
@@ -153,279 +192,339 @@ static void bank_set_arena(kg_rxbank *b, int mode)
     b->c_main->arena = a; b->c_side->arena = a; b->c_tail->arena = a;
 }
 
-// One pass over the step's entry points, in the order their tables sit in the slot.
-static int bank_pass(kg_rxbank *b, const void *d_adc, bool plan)
+static int bank_rx_check(kg_rxbank *b, int rx, const char *who)
 {
-    const int NR = b->nrx;
-    int rc;
-    bank_tick tk;
-    const bool pf = !plan;
-    b->act.clear();
-    for (int k = 0; k < NR; k++) {
-        b->enabled[k] = b->active[k] ? 1 : 0;
-        if (b->active[k]) b->act.push_back(k);
+    KG_REQUIRE(b != nullptr, KG_ERR_INVALID, "%s: null argument", who);
+    KG_REQUIRE(rx >= 0 && rx < b->nrx, KG_ERR_INVALID, "%s: receiver %d (0..%d)", who, rx, b->nrx - 1);
+    return KG_OK;
+}
+
+// the host waits for everything the bank has enqueued (with_upload: the table upload's stream too)
+static int bank_drain(kg_rxbank *b, bool with_upload)
+{
+    if (with_upload) KG_HIP(hipStreamSynchronize(b->s_up));
+    for (hipStream_t s : {b->s_main, b->s_side, b->s_tail}) KG_HIP(hipStreamSynchronize(s));
+    return KG_OK;
+}
+
+// ---- plan: what the step is.  No HIP call, no table staged, no bank state written: only b->plan.
+
+// Entry i's rows: which of its nblk sound blocks give an audio spectrum row -- the reference's rule (kg_spec.h), walked on a copy of
+// the mirror that the commit stores; rows are numbered in emission order -- and what the FFT extension takes from it.
+static void bank_plan_rows(kg_rxbank *b, int i, int nblk)
+{
+    bank_plan &p = b->plan;
+    const int k = p.act[i], NR = b->nrx;
+    const bank_rx &r = b->rcv[k];
+    const bool sam_family = p.mode[i] >= KG_POST_SAM && p.mode[i] <= KG_POST_QAM;
+    kg_spec::emit_t m = r.spec_mirror;
+    p.cmds[i] = kg_post_mode_cmds_(b->post, k);
+    if (p.cmds[i] != r.spec_cmds) kg_spec::emit_clear(m);
+    p.pb_n[i] = 0; p.pb_base[i] = 0;
+    if (b->fx && r.fx_on && nblk > 0) {                // each filter hands every block of its own to fft_data, which takes one instance's
+        p.fx_list.push_back(k); p.fx_nblk.push_back(nblk); p.fx_inst.push_back(KG_SPEC_PASSBAND);
+        p.fx_row.push_back((int32_t) ((size_t) i * b->blocks_max)); p.fx_blk0.push_back(0);
     }
-    const int NA = (int) b->act.size();
-    const int32_t *act = b->act.data();
-    int nrec_max = 0, nfir_max = 0, nspec = 0, nfx = 0;
-    bool any_pb = false;
-    if (!plan) for (int k = 0; k < NR; k++) { b->last_nrec[k] = 0; b->last_nfir[k] = 0; }
-    // ---- audio chain (side stream): rx.v -> rx_iq_t -> snd_service() unpack -> CFastFIR; the tail: S-meter, CAgc, detector, ADPCM
-    if (NA > 0) {
-        if ((rc = kg_rxddc_push_dev(b->rx, d_adc, b->n, act, NA, b->d_raw, b->nrec_max, b->h_nrec.data()))) return rc;
-        tk.lap(b, PF_RXDDC, pf);
-        for (int i = 0; i < NA; i++) if (b->h_nrec[i] > nrec_max) nrec_max = b->h_nrec[i];
-        // (rows are unpacked up to the largest count of the step; a receiver's CFastFIR takes its own count of them)
-        if (nrec_max > 0 &&
-            (rc = kg_dpump_unpack_rows_dev(b->c_side, b->d_raw, b->nrec_max, nrec_max, NR, b->enabled.data(), b->rescale, b->dc_i, b->dc_q,
-                                           b->spectral_inversion, b->d_xin, b->nrec_max)))
-            return rc;
-        // the pre-filter blanker (rx_sound.cpp:593-598): in place on the unpacked rows, before CFastFIR
-        b->nb_list.clear(); b->nb_cnt.clear();
-        for (int i = 0; i < NA; i++) {
-            const kg_rxbank::nb_cmd &c = b->nbc[act[i]];
-            if (c.snd_en[KG_NB_BLANKER] && c.algo == KG_NB_STD) { b->nb_list.push_back(act[i]); b->nb_cnt.push_back(b->h_nrec[i]); }
+    if (b->fx && p.sam_null[i])                        // where sound block blk's channel-null call leaves this receiver's spectrum
+        for (int blk = 0; blk < nblk; blk++) {
+            const int pos = p.fx_nullpos[blk]++;
+            if (!r.fx_on) continue;
+            p.fx_list.push_back(k); p.fx_nblk.push_back(1); p.fx_inst.push_back(KG_SPEC_CHAN_NULL);
+            p.fx_row.push_back((int32_t) ((size_t) NR * b->blocks_max + (size_t) blk * NR + pos)); p.fx_blk0.push_back(blk);
         }
-        if (!b->nb_list.empty() &&
-            (rc = kg_nb_process_dev(b->nb, b->nb_list.data(), (int) b->nb_list.size(), b->d_xin, b->nrec_max, b->nb_cnt.data(), b->d_xin,
-                                    b->nrec_max)))
-            return rc;
-        tk.lap(b, PF_UNPACK, pf);
-        if (!plan && b->tail_pending) {                       // the coders of the step before have read fir_out
-            KG_HIP(hipStreamWaitEvent(b->s_side, b->ev_tail, 0));
-            b->tail_pending = false;
+    for (int blk = 0; blk < nblk; blk++) {
+        const kg_spec::rows_t rows = kg_spec::emit_block(m, r.spec_on != 0, sam_family, p.sam_null[i] != 0);
+        if (rows.passband) {                           // only ever the leading blocks: the mirror leaves PASSBAND once per step at most
+            if (p.pb_n[i]++ == 0) p.pb_base[i] = p.nspec;
+            p.spec_rx[p.nspec] = k; p.spec_inst[p.nspec] = KG_SPEC_PASSBAND; p.spec_blk[p.nspec] = blk; p.nspec++;
+            p.any_pb = true;
         }
-        tk.lap(b, PF_EVENTS, pf);
-        // which blocks of this step give a row: the reference's rule (kg_spec.h), walked on a copy of the mirror that the real
-        // pass commits.  Rows are numbered in emission order, receiver by receiver.
-        nspec = 0;
-        b->fx_list.clear(); b->fx_nblk.clear(); b->fx_inst.clear(); b->fx_row.clear(); b->fx_blk0.clear();
-        std::fill(b->fx_nullpos.begin(), b->fx_nullpos.end(), 0);
-        for (int i = 0; i < NA; i++) {
-            const int k = act[i];
-            kg_spec::emit_t m = b->spec_mirror[k];
-            if (kg_post_mode_cmds_(b->post, k) != b->spec_cmds[k]) kg_spec::emit_clear(m);
-            const int mode = kg_post_get_mode(b->post, k);
-            const bool sam_family = mode >= KG_POST_SAM && mode <= KG_POST_QAM;
-            b->sam_null[i] = mode == KG_POST_SAM && (kg_post_sam_mparam_(b->post, k) & 3);
-            const int nblk = (kg_fir_pos(b->fir, k) + b->h_nrec[i]) / KG_FIR_OUT;
-            b->pb_inst[i] = KG_SPEC_PASSBAND; b->pb_n[i] = 0; b->pb_base[i] = 0;
-            if (b->fx && b->fx_on[k] && nblk > 0) {        // each filter hands every block of its own to fft_data, which takes one instance's
-                b->fx_list.push_back(k); b->fx_nblk.push_back(nblk); b->fx_inst.push_back(KG_SPEC_PASSBAND);
-                b->fx_row.push_back((int32_t) ((size_t) i * b->blocks_max)); b->fx_blk0.push_back(0);
-            }
-            if (b->fx && b->sam_null[i])                   // where sound block blk's channel-null call leaves this receiver's spectrum
-                for (int blk = 0; blk < nblk; blk++) {
-                    const int p = b->fx_nullpos[blk]++;
-                    if (!b->fx_on[k]) continue;
-                    b->fx_list.push_back(k); b->fx_nblk.push_back(1); b->fx_inst.push_back(KG_SPEC_CHAN_NULL);
-                    b->fx_row.push_back((int32_t) ((size_t) NR * b->blocks_max + (size_t) blk * NR + p)); b->fx_blk0.push_back(blk);
-                }
-            for (int blk = 0; blk < nblk; blk++) {
-                const kg_spec::rows_t r = kg_spec::emit_block(m, b->spec_on[k] != 0, sam_family, b->sam_null[i] != 0);
-                if (r.passband) {                          // only ever the leading blocks: the mirror leaves PASSBAND once per step at most
-                    if (b->pb_n[i]++ == 0) b->pb_base[i] = nspec;
-                    b->spec_rx2[nspec] = k; b->spec_inst2[nspec] = KG_SPEC_PASSBAND; b->spec_blk2[nspec] = blk; nspec++;
-                }
-                b->null_row[(size_t) i * b->blocks_max + blk] = r.chan_null ? nspec : -1;
-                if (r.chan_null) { b->spec_rx2[nspec] = k; b->spec_inst2[nspec] = KG_SPEC_CHAN_NULL; b->spec_blk2[nspec] = blk; nspec++; }
-                if (r.passband) any_pb = true;
-            }
-            b->spec_mirror2[k] = m;
-        }
-        if (!b->fx_list.empty()) {
-            const kg_fir_spec_req req = {b->d_spec, KG_SPEC_ROW, b->spec_max * KG_SPEC_ROW, b->pb_inst.data(), b->pb_n.data(), b->pb_base.data()};
-            rc = kg_fir_process_post_(b->fir, act, NA, b->d_xin, b->nrec_max, b->h_nrec.data(), b->d_firo, b->firo_stride, b->h_nfir.data(),
-                                      any_pb ? &req : nullptr, b->d_fxpost, b->fx_stride);
-        } else if (any_pb) {
-            const kg_fir_spec_req req = {b->d_spec, KG_SPEC_ROW, b->spec_max * KG_SPEC_ROW, b->pb_inst.data(), b->pb_n.data(), b->pb_base.data()};
-            rc = kg_fir_process_rows_(b->fir, act, NA, b->d_xin, b->nrec_max, b->h_nrec.data(), b->d_firo, b->firo_stride, b->h_nfir.data(), &req);
-        } else {
-            rc = kg_fir_process_each_dev(b->fir, act, NA, b->d_xin, b->nrec_max, b->h_nrec.data(), b->d_firo, b->firo_stride, b->h_nfir.data());
-        }
-        if (rc) return rc;
-        tk.lap(b, PF_FIR, pf);
-        for (int i = 0; i < NA; i++) if (b->h_nfir[i] > nfir_max) nfir_max = b->h_nfir[i];
+        p.null_row[(size_t) i * b->blocks_max + blk] = rows.chan_null ? p.nspec : -1;
+        if (rows.chan_null) { p.spec_rx[p.nspec] = k; p.spec_inst[p.nspec] = KG_SPEC_CHAN_NULL; p.spec_blk[p.nspec] = blk; p.nspec++; }
     }
-    if (nfir_max > 0) {
-        if (!plan) {
-            KG_HIP(hipEventRecord(b->ev_fir, b->s_side));
-            KG_HIP(hipStreamWaitEvent(b->s_tail, b->ev_fir, 0));
-        }
-        tk.lap(b, PF_EVENTS, pf);
-        for (int blk = 0; blk < nfir_max / KG_FIR_OUT; blk++) {         // one sound packet per 512 samples (rx_sound.cpp:601-1170)
-            const size_t o = (size_t) blk * KG_FIR_OUT;
-            b->blk_list.clear();                                          // the receivers that completed this block in this step
-            for (int i = 0; i < NA; i++) if (b->h_nfir[i] >= (int) (o + KG_FIR_OUT)) b->blk_list.push_back(act[i]);
-            const int NB = (int) b->blk_list.size();
-            if ((rc = kg_post_process_dev(b->post, b->blk_list.data(), NB, b->d_firo + o, b->firo_stride, KG_FIR_OUT, b->d_s16 + o, nullptr,
-                                          b->d_agc + o, b->firo_stride)))
-                return rc;
-            // rx_sound.cpp:804: the block's nulled pair through m_chan_null_FIR without an output buffer, rows on or not
-            b->null_list.clear(); b->null_n.clear(); b->null_base.clear();
-            for (int i = 0; i < NA; i++)
-                if (b->sam_null[i] && b->h_nfir[i] >= (int) (o + KG_FIR_OUT)) {
-                    const int row = b->null_row[(size_t) i * b->blocks_max + blk];
-                    b->null_list.push_back(act[i]); b->null_n.push_back(row >= 0 ? 1 : 0); b->null_base.push_back(row >= 0 ? row : 0);
-                }
-            if (!b->null_list.empty()) {
-                const int NN = (int) b->null_list.size();
-                const kg_fir_spec_req req = {b->d_spec, KG_SPEC_ROW, b->spec_max * KG_SPEC_ROW, b->null_inst.data(), b->null_n.data(), b->null_base.data()};
-                if (!b->fx_list.empty())                    // block blk of the step's channel-null spectra
-                    rc = kg_fir_process_post_(b->nullfir, b->null_list.data(), NN, b->d_agc + o, b->firo_stride, b->null_each.data(), nullptr, 0,
-                                              nullptr, &req, b->d_fxpost + ((size_t) NR * b->blocks_max + (size_t) blk * NR) * KG_FFTEXT_ROW, KG_FFTEXT_ROW);
-                else
-                    rc = kg_fir_process_rows_(b->nullfir, b->null_list.data(), NN, b->d_agc + o, b->firo_stride, b->null_each.data(), nullptr, 0,
-                                              nullptr, &req);
-                if (rc) return rc;
-            }
-            tk.lap(b, PF_POST, pf);
-            // the real modes' blocks go through the ADPCM coder, the stereo modes' (IS_STEREO: IQ, SAS, QAM) as (s2_t) pairs of the agc
-            // buffer, where SAS / QAM leave their (L, R) pair (rx_sound.cpp:1042-1140)
-            b->real_list.clear(); b->iq_le_list.clear(); b->iq_be_list.clear();
-            for (int i = 0; i < NB; i++) {
-                const int k = b->blk_list[i];
-                const int m = kg_post_get_mode(b->post, k);
-                if (m != KG_POST_IQ && m != KG_POST_SAS && m != KG_POST_QAM) b->real_list.push_back(k);
-                else (b->little_endian[k] ? b->iq_le_list : b->iq_be_list).push_back(k);
-            }
-            if (!b->real_list.empty() &&
-                (rc = kg_adpcm_encode_dev(b->adpcm, b->real_list.data(), (int) b->real_list.size(), b->d_s16 + o, b->firo_stride, KG_FIR_OUT,
-                                          b->d_pay + o / 2, b->firo_stride / 2)))
-                return rc;
-            for (int le = 0; le < 2; le++) {
-                std::vector<int32_t> &l = le ? b->iq_le_list : b->iq_be_list;
-                if (!l.empty() &&
-                    (rc = kg_snd_iq_payload_dev(b->c_tail, l.data(), (int) l.size(), b->d_agc + o, b->firo_stride, KG_FIR_OUT, le,
-                                                b->d_iqpay + 4 * o, 4 * b->firo_stride)))
-                    return rc;
-            }
-            tk.lap(b, PF_ADPCM, pf);
-        }
-        if (!b->fx_list.empty()) {                        // fft_data over the step's blocks: one launch, behind both filters
-            rc = kg_fftext_process_rows_(b->fx, b->fx_list.data(), (int) b->fx_list.size(), b->fx_nblk.data(), b->fx_inst.data(), b->fx_row.data(),
-                                         (const float *) b->d_fxpost.p, KG_FFTEXT_ROW, b->d_fxrows, KG_FFTEXT_ROW, (int) b->fx_max,
-                                         plan ? nullptr : b->fx_rx.data(), plan ? nullptr : b->fx_ent.data(), plan ? nullptr : b->fx_blk.data(),
-                                         plan ? nullptr : b->fx_bin.data());
-            if (rc < 0) return rc;
-            nfx = rc;
-            if (!plan) for (int r = 0; r < nfx; r++) b->fx_blk[r] += b->fx_blk0[b->fx_ent[r]];       // the sound block of the step
-        }
-        if (!plan) {
-            KG_HIP(hipEventRecord(b->ev_tail, b->s_tail));
-            b->tail_pending = true;
-        }
-        tk.lap(b, PF_EVENTS, pf);
+    p.mirror[i] = m;
+}
+
+// The active list and, per entry, the counts its audio DDC and its CFastFIR will hand back (kg_rxddc_outputs is kg_rxddc_push_dev's
+// own arithmetic, a CFastFIR call leaves (FirPos() + n) / 512 blocks), its mode, its blanker, its rows.  A receiver whose query refuses
+// (no frequency set) is planned with nothing: the entry point says why.
+static void bank_plan_audio(kg_rxbank *b)
+{
+    bank_plan &p = b->plan;
+    for (std::vector<int32_t> *v : {&p.act, &p.nb_list, &p.nb_cnt, &p.fx_list, &p.fx_nblk, &p.fx_inst, &p.fx_row, &p.fx_blk0}) v->clear();
+    std::fill(p.fx_nullpos.begin(), p.fx_nullpos.end(), 0);
+    p.nrec_max = p.nfir_max = p.nspec = p.fx_n = 0;
+    p.any_pb = false;
+    for (int k = 0; k < b->nrx; k++) {
+        const bank_rx &r = b->rcv[k];
+        p.enabled[k] = r.active ? 1 : 0;
+        if (!r.active) continue;
+        const int i = (int) p.act.size();
+        p.act.push_back(k);
+        const long outputs = kg_rxddc_outputs(b->rx, k, b->n);
+        const int nrec = outputs > 0 ? (int) outputs : 0;
+        const int nblk = (kg_fir_pos(b->fir, k) + nrec) / KG_FIR_OUT;
+        p.nrec[i] = nrec; p.nfir[i] = nblk * KG_FIR_OUT;
+        if (p.nrec[i] > p.nrec_max) p.nrec_max = p.nrec[i];
+        if (p.nfir[i] > p.nfir_max) p.nfir_max = p.nfir[i];
+        // the pre-filter blanker (rx_sound.cpp:593-598)
+        if (r.nbc.snd_en[KG_NB_BLANKER] && r.nbc.algo == KG_NB_STD) { p.nb_list.push_back(k); p.nb_cnt.push_back(nrec); }
+        p.mode[i] = kg_post_get_mode(b->post, k);
+        p.sam_null[i] = p.mode[i] == KG_POST_SAM && (kg_post_sam_mparam_(b->post, k) & 3);
+        bank_plan_rows(b, i, nblk);
     }
-    // ---- waterfall chain (main stream)
-    int nframes = 0;
-    b->moves.clear();
-    for (int i = 0; i < NA; i++) {
-        const int k = act[i];
-        KG_REQUIRE(b->wf_set[k], KG_ERR_STATE, "kg_rxbank_step: kg_rxbank_set_wf was not called for receiver %d (since it joined)", k);
-        if (b->overlapped[k]) {
-            const long m = (long) (b->n / (size_t) b->decim[k]);
-            long w = b->ring_w[k];
+}
+
+// One sound packet per 512 samples (rx_sound.cpp:601-1170): per sound block of the step the receivers that completed it, those of
+// them whose nulled pair goes through m_chan_null_FIR (rx_sound.cpp:804, rows on or not), and who goes to which coder -- the real
+// modes' blocks through the ADPCM coder, the stereo modes' (IS_STEREO: IQ, SAS, QAM) as (s2_t) pairs (rx_sound.cpp:1042-1140).
+static void bank_plan_blocks(kg_rxbank *b)
+{
+    bank_plan &p = b->plan;
+    const int NA = (int) p.act.size();
+    for (std::vector<int32_t> *v : {&p.blk_chan, &p.blk_at, &p.blk_null_n, &p.blk_null_base}) v->clear();
+    auto put = [&p](int k, int n, int base) { p.blk_chan.push_back(k); p.blk_null_n.push_back(n); p.blk_null_base.push_back(base); };
+    for (int blk = 0; blk < p.nfir_max / KG_FIR_OUT; blk++)
+        for (int j = 0; j < BL_N; j++) {
+            p.blk_at.push_back((int32_t) p.blk_chan.size());
+            for (int i = 0; i < NA; i++) {
+                if (p.nfir[i] < (blk + 1) * KG_FIR_OUT) continue;
+                const int k = p.act[i], m = p.mode[i], row = p.null_row[(size_t) i * b->blocks_max + blk];
+                const bool stereo = m == KG_POST_IQ || m == KG_POST_SAS || m == KG_POST_QAM, le = b->rcv[k].little_endian != 0;
+                if (j == BL_POST || (j == BL_REAL && !stereo) || (j == BL_IQ_BE && stereo && !le) || (j == BL_IQ_LE && stereo && le)) put(k, 0, 0);
+                if (j == BL_NULL && p.sam_null[i]) put(k, row >= 0 ? 1 : 0, row >= 0 ? row : 0);
+            }
+        }
+    p.blk_at.push_back((int32_t) p.blk_chan.size());
+}
+
+// The waterfall chain: where each entry's DDC writes, which rings wrap first, which receivers have a frame and where it lies.
+static void bank_plan_wf(kg_rxbank *b)
+{
+    bank_plan &p = b->plan;
+    p.moves.clear();
+    p.nframes = 0; p.wf_unset = -1;
+    for (int i = 0; i < (int) p.act.size(); i++) {
+        const int k = p.act[i];
+        const bank_rx &r = b->rcv[k];
+        long w = r.ring_w, total = r.ring_total;
+        bool frame = true;
+        p.out_off[i] = 0; p.max_out[i] = KG_WF_NFFT;
+        uint64_t off = (uint64_t) k * b->wf_stride;
+        if (!r.wf_set) {
+            if (p.wf_unset < 0) p.wf_unset = k;
+            frame = false;
+        } else if (r.overlapped) {
+            const long m = (long) (b->n / (size_t) r.decim);
             if (w + m > BANK_RING_PAIRS) {
                 const long keep = KG_WF_NFFT - m;
-                if (keep > 0) b->moves.push_back(bank_move{k, (int) (w - keep), 0, (int) keep});
+                if (keep > 0) p.moves.push_back(bank_move{k, (int) (w - keep), 0, (int) keep});
                 w = keep;
             }
-            b->out_off[i] = w; b->max_out[i] = 0;
-            b->ring_w2[k] = w + m; b->ring_total2[k] = b->ring_total[k] + m;
-            if (b->ring_total2[k] >= KG_WF_NFFT) {                       // (before that: the reference sleeps, "fill pipe", :978)
-                b->chan_of[nframes] = k;
-                b->frame_off[nframes] = (uint64_t) k * b->wf_stride + (uint64_t) (w + m - KG_WF_NFFT);
-                nframes++;
-            }
-        } else {
-            b->out_off[i] = 0; b->max_out[i] = KG_WF_NFFT;
-            b->chan_of[nframes] = k;
-            b->frame_off[nframes] = (uint64_t) k * b->wf_stride;
-            nframes++;
+            p.out_off[i] = w; p.max_out[i] = 0;
+            w += m; total += m;
+            frame = total >= KG_WF_NFFT;                                 // (before that: the reference sleeps, "fill pipe", :978)
+            off += (uint64_t) (w - KG_WF_NFFT);
         }
+        p.ring_w[i] = w; p.ring_total[i] = total;
+        if (!frame) continue;
+        p.chan_of[p.nframes] = k; p.frame_off[p.nframes] = off;
+        p.pkt_step[p.nframes] = r.pkt;
+        p.pkt_step[p.nframes].seq = r.snd_seq;                           // out->seq = wf->snd_seq, rx_waterfall.cpp:1635
+        p.nframes++;
     }
-    if (!b->moves.empty()) {
-        void *d_mv = nullptr;
-        if ((rc = kg_ctx_stage(b->c_main, b->moves.data(), sizeof(bank_move) * b->moves.size(), &d_mv))) return rc;
-        if (!plan) {
-            hipLaunchKernelGGL(rxbank_move_kernel, dim3((unsigned) b->moves.size()), dim3(256), 0, b->s_main, b->d_wfiq, (long) b->wf_stride,
-                               (const bank_move *) d_mv);
-            KG_HIP(hipGetLastError());
-        }
-    }
-    if (NA > 0 &&
-        (rc = kg_ddc_wf_step_dev(b->ddc, d_adc, b->n, act, NA, b->d_wfiq, b->wf_stride, b->out_off.data(), b->max_out.data(),
-                                 b->h_nw.data())))
-        return rc;
-    tk.lap(b, PF_DDC, pf);
-    if (!plan && b->pk_pending) {                         // the packets of the step before have read the rows
-        KG_HIP(hipStreamWaitEvent(b->s_main, b->ev_pk, 0));
-        b->pk_pending = false;
-    }
-    tk.lap(b, PF_EVENTS, pf);
-    if (nframes > 0) {
-        if ((rc = kg_wf_frames_at_dev(b->wf, nframes, b->chan_of.data(), b->frame_off.data(), (uint64_t) NR * b->wf_stride, b->d_wfiq,
-                                      b->d_rows)))
-            return rc;
-        tk.lap(b, PF_FRAMES, pf);
-        if (!plan) {
-            KG_HIP(hipEventRecord(b->ev_frames, b->s_main));
-            KG_HIP(hipStreamWaitEvent(b->s_tail, b->ev_frames, 0));
-        }
-        tk.lap(b, PF_EVENTS, pf);
-        for (int f = 0; f < nframes; f++) {
-            b->pkt_step[f] = b->pkt[b->chan_of[f]];
-            b->pkt_step[f].seq = b->snd_seq[b->chan_of[f]];              // out->seq = wf->snd_seq, rx_waterfall.cpp:1635
-        }
-        if ((rc = kg_wf_packets_dev(b->c_tail, b->d_rows, KG_WF_WIDTH, nframes, b->pkt_step.data(), b->d_pkts, BANK_PKT_STRIDE,
-                                    b->pkt_bytes.data())))
-            return rc;
-        tk.lap(b, PF_PKT, pf);
-        if (!plan) {
-            KG_HIP(hipEventRecord(b->ev_pk, b->s_tail));
-            b->pk_pending = true;
-        }
-        tk.lap(b, PF_EVENTS, pf);
-    }
-    if (!plan) {
-        for (int i = 0; i < NA; i++) {
-            const int k = act[i];
-            if (b->overlapped[k]) { b->ring_w[k] = b->ring_w2[k]; b->ring_total[k] = b->ring_total2[k]; }
-        }
-        for (int f = 0; f < nframes; f++) b->rx_of_frame[f] = b->chan_of[f];
-        for (int i = 0; i < NA; i++) {
-            b->spec_mirror[act[i]] = b->spec_mirror2[act[i]];
-            b->spec_cmds[act[i]] = kg_post_mode_cmds_(b->post, act[i]);
-        }
-        b->spec_n = nspec;
-        b->fx_n = nfx;
-        b->spec_rx.swap(b->spec_rx2); b->spec_inst.swap(b->spec_inst2); b->spec_blk.swap(b->spec_blk2);
-        kg_rxbank_step_info &s = b->last;
-        const int first = NA > 0 ? act[0] : 0;             // the step's scalar audio fields: the lowest-numbered active receiver's
-        s.step = b->step; s.nframes = nframes; s.nrec = NA > 0 ? b->h_nrec[0] : 0; s.nfir = NA > 0 ? b->h_nfir[0] : 0;
-        s.fir_pos = kg_fir_pos(b->fir, first);
-        s.snd_seq = b->snd_seq[first]; s.table_bytes = (int32_t) b->arena.used; s.nmoves = (int32_t) b->moves.size();
-        for (int i = 0; i < NA; i++) {
-            b->last_nrec[act[i]] = b->h_nrec[i]; b->last_nfir[act[i]] = b->h_nfir[i];
-            b->snd_seq[act[i]] += (uint32_t) (b->h_nfir[i] / KG_FIR_OUT);
-        }
-    }
+}
+
+static void bank_plan_step(kg_rxbank *b)
+{
+    bank_plan_audio(b);
+    bank_plan_blocks(b);
+    bank_plan_wf(b);
+}
+
+// ---- enqueue: the entry points in the order their tables sit in the slot.  Reads the plan; decides and commits nothing.
+
+// An edge of the stream graph, and the one place that tells the two passes apart: the PLAN pass enqueues none.  `from` records ev
+// (null: an earlier step did, if *pending), `to` waits for it (null: the next step's reader will, so *pending is set).
+static int bank_edge(bool real, hipEvent_t ev, hipStream_t from, hipStream_t to, bool *pending = nullptr)
+{
+    if (!real) return KG_OK;
+    if (from) KG_HIP(hipEventRecord(ev, from));
+    if (to && (from || *pending)) KG_HIP(hipStreamWaitEvent(to, ev, 0));
+    if (pending) *pending = from != nullptr;
     return KG_OK;
+}
+
+static bool bank_real(const kg_rxbank *b) { return b->arena.mode != KG_ARENA_PLAN; }
+
+// what an entry point handed back against what the plan counted
+static int bank_counts_agree(const bank_plan &p, const std::vector<int32_t> &plan, const std::vector<int32_t> &got, const char *what, const char *who)
+{
+    for (size_t i = 0; i < p.act.size(); i++)
+        KG_REQUIRE(got[i] == plan[i], KG_ERR_STATE, "kg_rxbank_step: receiver %d: %d %s planned, %s hands back %d", p.act[i], plan[i], what, who,
+                   got[i]);
+    return KG_OK;
+}
+
+// the step's ring moves, staged and launched the way an entry point does it
+static int bank_moves_dev(kg_rxbank *b)
+{
+    const bank_plan &p = b->plan;
+    void *d_mv = nullptr;
+    KG_TRY(kg_ctx_stage(b->c_main, p.moves.data(), sizeof(bank_move) * p.moves.size(), &d_mv));
+    KG_PLAN_ONLY(b->c_main);
+    hipLaunchKernelGGL(rxbank_move_kernel, dim3((unsigned) p.moves.size()), dim3(256), 0, b->s_main, b->d_wfiq, (long) b->wf_stride,
+                       (const bank_move *) d_mv);
+    KG_HIP(hipGetLastError());
+    return KG_OK;
+}
+
+// audio chain (side stream): rx.v -> rx_iq_t -> snd_service() unpack -> the pre-filter blanker -> CFastFIR
+static int bank_audio_front(kg_rxbank *b, const void *d_adc)
+{
+    bank_plan &p = b->plan;
+    const int NA = (int) p.act.size(), NR = b->nrx;
+    if (NA == 0) return KG_OK;
+    const bool real = bank_real(b);
+    const int32_t *act = p.act.data();
+    bank_tick tk;
+    KG_TRY(kg_rxddc_push_dev(b->rx, d_adc, b->n, act, NA, b->d_raw, b->nrec_max, p.got_nrec.data()));
+    KG_TRY(bank_counts_agree(p, p.nrec, p.got_nrec, "records", "kg_rxddc_push_dev"));
+    tk.lap(b, PF_RXDDC, real);
+    // (rows are unpacked up to the largest count of the step; a receiver's CFastFIR takes its own count of them)
+    if (p.nrec_max > 0)
+        KG_TRY(kg_dpump_unpack_rows_dev(b->c_side, b->d_raw, b->nrec_max, p.nrec_max, NR, p.enabled.data(), b->rescale, b->dc_i, b->dc_q,
+                                        b->spectral_inversion, b->d_xin, b->nrec_max));
+    if (!p.nb_list.empty())                                // in place on the unpacked rows, before CFastFIR
+        KG_TRY(kg_nb_process_dev(b->nb, p.nb_list.data(), (int) p.nb_list.size(), b->d_xin, b->nrec_max, p.nb_cnt.data(), b->d_xin, b->nrec_max));
+    tk.lap(b, PF_UNPACK, real);
+    KG_TRY(bank_edge(real, b->ev_tail, nullptr, b->s_side, &b->tail_pending));     // the coders of the step before have read fir_out
+    tk.lap(b, PF_EVENTS, real);
+    const kg_fir_spec_req req = {b->d_spec, KG_SPEC_ROW, b->spec_max * KG_SPEC_ROW, p.pb_inst.data(), p.pb_n.data(), p.pb_base.data()};
+    int rc;
+    if (!p.fx_list.empty())
+        rc = kg_fir_process_post_(b->fir, act, NA, b->d_xin, b->nrec_max, p.nrec.data(), b->d_firo, b->firo_stride, p.got_nfir.data(),
+                                  p.any_pb ? &req : nullptr, b->d_fxpost, b->fx_stride);
+    else if (p.any_pb)
+        rc = kg_fir_process_rows_(b->fir, act, NA, b->d_xin, b->nrec_max, p.nrec.data(), b->d_firo, b->firo_stride, p.got_nfir.data(), &req);
+    else
+        rc = kg_fir_process_each_dev(b->fir, act, NA, b->d_xin, b->nrec_max, p.nrec.data(), b->d_firo, b->firo_stride, p.got_nfir.data());
+    if (rc) return rc;
+    KG_TRY(bank_counts_agree(p, p.nfir, p.got_nfir, "CFastFIR outputs", "kg_fir"));
+    tk.lap(b, PF_FIR, real);
+    return KG_OK;
+}
+
+// the tail stream, per sound block: S-meter, CAgc, detector; the channel-null filter; the coders.  Then the FFT extension.
+static int bank_audio_tail(kg_rxbank *b)
+{
+    bank_plan &p = b->plan;
+    if (p.nfir_max == 0) return KG_OK;
+    const bool real = bank_real(b), fx = !p.fx_list.empty();
+    const size_t NR = (size_t) b->nrx;
+    bank_tick tk;
+    KG_TRY(bank_edge(real, b->ev_fir, b->s_side, b->s_tail));
+    tk.lap(b, PF_EVENTS, real);
+    for (int blk = 0; blk < p.nfir_max / KG_FIR_OUT; blk++) {
+        const size_t o = (size_t) blk * KG_FIR_OUT;
+        const int32_t *chan = p.blk_chan.data();
+        KG_TRY(kg_post_process_dev(b->post, chan + p.at(blk, BL_POST), p.count(blk, BL_POST), b->d_firo + o, b->firo_stride, KG_FIR_OUT, b->d_s16 + o,
+                                   nullptr, b->d_agc + o, b->firo_stride));
+        if (const int NN = p.count(blk, BL_NULL)) {        // without an output buffer; with the extension on, block blk of the channel-null spectra
+            const int at = p.at(blk, BL_NULL);
+            const kg_fir_spec_req req = {b->d_spec, KG_SPEC_ROW, b->spec_max * KG_SPEC_ROW, p.null_inst.data(), p.blk_null_n.data() + at,
+                                         p.blk_null_base.data() + at};
+            if (fx)
+                KG_TRY(kg_fir_process_post_(b->nullfir, chan + at, NN, b->d_agc + o, b->firo_stride, p.null_each.data(), nullptr, 0, nullptr, &req,
+                                            b->d_fxpost + (NR * b->blocks_max + (size_t) blk * NR) * KG_FFTEXT_ROW, KG_FFTEXT_ROW));
+            else
+                KG_TRY(kg_fir_process_rows_(b->nullfir, chan + at, NN, b->d_agc + o, b->firo_stride, p.null_each.data(), nullptr, 0, nullptr, &req));
+        }
+        tk.lap(b, PF_POST, real);
+        if (const int NL = p.count(blk, BL_REAL))
+            KG_TRY(kg_adpcm_encode_dev(b->adpcm, chan + p.at(blk, BL_REAL), NL, b->d_s16 + o, b->firo_stride, KG_FIR_OUT, b->d_pay + o / 2,
+                                       b->firo_stride / 2));
+        for (int le = 0; le < 2; le++)                     // SAS / QAM leave their (L, R) pair in the agc buffer
+            if (const int NL = p.count(blk, BL_IQ_BE + le))
+                KG_TRY(kg_snd_iq_payload_dev(b->c_tail, chan + p.at(blk, BL_IQ_BE + le), NL, b->d_agc + o, b->firo_stride, KG_FIR_OUT, le,
+                                             b->d_iqpay + 4 * o, 4 * b->firo_stride));
+        tk.lap(b, PF_ADPCM, real);
+    }
+    if (fx) {                                              // fft_data over the step's blocks: one launch, behind both filters
+        const int rc = kg_fftext_process_rows_(b->fx, p.fx_list.data(), (int) p.fx_list.size(), p.fx_nblk.data(), p.fx_inst.data(), p.fx_row.data(),
+                                               (const float *) b->d_fxpost.p, KG_FFTEXT_ROW, b->d_fxrows, KG_FFTEXT_ROW, (int) b->fx_max,
+                                               p.fx_rx.data(), p.fx_ent.data(), p.fx_blk.data(), p.fx_bin.data());
+        if (rc < 0) return rc;
+        p.fx_n = rc;
+    }
+    KG_TRY(bank_edge(real, b->ev_tail, b->s_tail, nullptr, &b->tail_pending));
+    tk.lap(b, PF_EVENTS, real);
+    return KG_OK;
+}
+
+// waterfall chain (main stream): ring moves, DDC, frames; the packets on the tail stream
+static int bank_wf_chain(kg_rxbank *b, const void *d_adc)
+{
+    bank_plan &p = b->plan;
+    const int NA = (int) p.act.size();
+    const bool real = bank_real(b);
+    bank_tick tk;
+    KG_REQUIRE(p.wf_unset < 0, KG_ERR_STATE, "kg_rxbank_step: kg_rxbank_set_wf was not called for receiver %d (since it joined)", p.wf_unset);
+    if (!p.moves.empty()) KG_TRY(bank_moves_dev(b));
+    if (NA > 0)
+        KG_TRY(kg_ddc_wf_step_dev(b->ddc, d_adc, b->n, p.act.data(), NA, b->d_wfiq, b->wf_stride, p.out_off.data(), p.max_out.data(), p.h_nw.data()));
+    tk.lap(b, PF_DDC, real);
+    KG_TRY(bank_edge(real, b->ev_pk, nullptr, b->s_main, &b->pk_pending));         // the packets of the step before have read the rows
+    tk.lap(b, PF_EVENTS, real);
+    if (p.nframes == 0) return KG_OK;
+    KG_TRY(kg_wf_frames_at_dev(b->wf, p.nframes, p.chan_of.data(), p.frame_off.data(), (uint64_t) b->nrx * b->wf_stride, b->d_wfiq, b->d_rows));
+    tk.lap(b, PF_FRAMES, real);
+    KG_TRY(bank_edge(real, b->ev_frames, b->s_main, b->s_tail));
+    tk.lap(b, PF_EVENTS, real);
+    KG_TRY(kg_wf_packets_dev(b->c_tail, b->d_rows, KG_WF_WIDTH, p.nframes, p.pkt_step.data(), b->d_pkts, BANK_PKT_STRIDE, p.pkt_bytes.data()));
+    tk.lap(b, PF_PKT, real);
+    KG_TRY(bank_edge(real, b->ev_pk, b->s_tail, nullptr, &b->pk_pending));
+    tk.lap(b, PF_EVENTS, real);
+    return KG_OK;
+}
+
+static int bank_pass(kg_rxbank *b, const void *d_adc)
+{
+    KG_TRY(bank_audio_front(b, d_adc));
+    KG_TRY(bank_audio_tail(b));
+    return bank_wf_chain(b, d_adc);
+}
+
+// ---- commit: the step has been enqueued; the plan's next values and maps become the bank's
+static void bank_commit(kg_rxbank *b)
+{
+    bank_plan &p = b->plan;
+    const int NA = (int) p.act.size();
+    kg_rxbank_step_info &s = b->last;
+    const int first = NA > 0 ? p.act[0] : 0;               // the step's scalar audio fields: the lowest-numbered active receiver's
+    s.step = b->step; s.nframes = p.nframes; s.nrec = NA > 0 ? p.nrec[0] : 0; s.nfir = NA > 0 ? p.nfir[0] : 0;
+    s.fir_pos = kg_fir_pos(b->fir, first);
+    s.snd_seq = b->rcv[first].snd_seq; s.table_bytes = (int32_t) b->arena.used; s.nmoves = (int32_t) p.moves.size();
+    for (bank_rx &r : b->rcv) { r.last_nrec = 0; r.last_nfir = 0; }
+    for (int i = 0; i < NA; i++) {
+        bank_rx &r = b->rcv[p.act[i]];
+        r.ring_w = p.ring_w[i]; r.ring_total = p.ring_total[i];
+        r.spec_mirror = p.mirror[i]; r.spec_cmds = p.cmds[i];
+        r.last_nrec = p.nrec[i]; r.last_nfir = p.nfir[i];
+        r.snd_seq += (uint32_t) (p.nfir[i] / KG_FIR_OUT);
+    }
+    for (int r = 0; r < p.fx_n; r++) p.fx_blk[r] += p.fx_blk0[p.fx_ent[r]];      // the sound block of the step
+    b->spec_n = p.nspec; b->fx_n = p.fx_n;
+    b->spec_rx.swap(p.spec_rx); b->spec_inst.swap(p.spec_inst); b->spec_blk.swap(p.spec_blk);
+    b->fx_rx.swap(p.fx_rx); b->fx_blk.swap(p.fx_blk); b->fx_bin.swap(p.fx_bin);
+    b->frame_rx.swap(p.chan_of); b->frame_off.swap(p.frame_off); b->pkt_bytes.swap(p.pkt_bytes);
 }
 
 // `SET zoom=` with a new zoom (rx_waterfall.cpp:460): the waterfall blanker is set up again before the next frame
 static void bank_nb_zoom_change(kg_rxbank *b, int rx)
 {
-    kg_rxbank::nb_cmd &c = b->nbc[rx];
+    bank_nb_cmd &c = b->rcv[rx].nbc;
     if (c.wf_en[KG_NB_BLANKER] && c.wf_en[KG_NB_WF]) c.wf_change[KG_NB_BLANKER] = 1;
-}
-
-static int bank_nb_rx(kg_rxbank *b, int rx, const char *who)
-{
-    KG_REQUIRE(b != nullptr, KG_ERR_INVALID, "%s: null argument", who);
-    KG_REQUIRE(rx >= 0 && rx < b->nrx, KG_ERR_INVALID, "%s: receiver %d (0..%d)", who, rx, b->nrx - 1);
-    return KG_OK;
 }
 
 // SetupBlanker's refusals for a parameter vector at `rate`, without touching any blanker
@@ -444,7 +543,7 @@ static int bank_nb_algo(kg_rxbank *b, int rx, int algo)
 {
     int rc = kg_post_set_nbw(b->post, rx, 0);
     if (rc) return rc;
-    kg_rxbank::nb_cmd &c = b->nbc[rx];
+    bank_nb_cmd &c = b->rcv[rx].nbc;
     c.algo = algo;
     memset(c.snd_en, 0, sizeof c.snd_en);
     memset(c.wf_en, 0, sizeof c.wf_en);
@@ -455,8 +554,7 @@ extern "C" {
 
 int kg_rxbank_set_nb_algo(kg_rxbank *b, int rx, int algo)
 {
-    int rc = bank_nb_rx(b, rx, "kg_rxbank_set_nb_algo");
-    if (rc) return rc;
+    KG_TRY(bank_rx_check(b, rx, "kg_rxbank_set_nb_algo"));
     KG_REQUIRE(algo == KG_NB_OFF || algo == KG_NB_STD, KG_ERR_INVALID, "kg_rxbank_set_nb_algo: algo %d (%s)", algo,
                algo == KG_NB_WILD ? "NB_WILD is selected by kg_rxbank_nbw_select" : "not an nb_algo_e");
     return bank_nb_algo(b, rx, algo);
@@ -464,18 +562,17 @@ int kg_rxbank_set_nb_algo(kg_rxbank *b, int rx, int algo)
 
 int kg_rxbank_nbw_select(kg_rxbank *b, int rx)
 {
-    int rc = bank_nb_rx(b, rx, "kg_rxbank_nbw_select");
-    if (rc) return rc;
+    KG_TRY(bank_rx_check(b, rx, "kg_rxbank_nbw_select"));
     return bank_nb_algo(b, rx, KG_NB_WILD);
 }
 
 int kg_rxbank_set_nb_enable(kg_rxbank *b, int rx, int type, int en)
 {
-    int rc = bank_nb_rx(b, rx, "kg_rxbank_set_nb_enable");
+    int rc = bank_rx_check(b, rx, "kg_rxbank_set_nb_enable");
     if (rc) return rc;
     KG_REQUIRE(type >= 0 && type < 4, KG_ERR_INVALID, "kg_rxbank_set_nb_enable: type %d (0..3)", type);
     KG_REQUIRE(!(type == KG_NB_CLICK && en), KG_ERR_INVALID, "kg_rxbank_set_nb_enable: NB_CLICK test pulses are not implemented");
-    kg_rxbank::nb_cmd &c = b->nbc[rx];
+    bank_nb_cmd &c = b->rcv[rx].nbc;
     KG_REQUIRE(!(type == KG_NB_BLANKER && en && c.algo == KG_NB_STD && !kg_nb_was_setup(b->nb, rx)), KG_ERR_STATE,
                "kg_rxbank_set_nb_enable: receiver %d's audio blanker was never set up (send its parameters first)", rx);
     if (type == KG_NB_BLANKER && c.algo == KG_NB_WILD && (rc = kg_post_set_nbw(b->post, rx, en))) return rc;   // rx_sound.cpp:924-929
@@ -486,10 +583,10 @@ int kg_rxbank_set_nb_enable(kg_rxbank *b, int rx, int type, int en)
 
 int kg_rxbank_set_nb_param(kg_rxbank *b, int rx, int type, int param, float pval, float frate)
 {
-    int rc = bank_nb_rx(b, rx, "kg_rxbank_set_nb_param");
+    int rc = bank_rx_check(b, rx, "kg_rxbank_set_nb_param");
     if (rc) return rc;
     KG_REQUIRE(type >= 0 && type < 4 && param >= 0 && param < 8, KG_ERR_INVALID, "kg_rxbank_set_nb_param: type %d param %d", type, param);
-    kg_rxbank::nb_cmd &c = b->nbc[rx];
+    bank_nb_cmd &c = b->rcv[rx].nbc;
     float snd[8], wfp[8];
     memcpy(snd, c.snd_param[type], sizeof snd);
     memcpy(wfp, c.wf_param[type], sizeof wfp);
@@ -511,9 +608,9 @@ int kg_rxbank_set_nb_param(kg_rxbank *b, int rx, int type, int param, float pval
 
 int kg_rxbank_set_nb_gate(kg_rxbank *b, int rx, int nb, int th, float frate)
 {
-    int rc = bank_nb_rx(b, rx, "kg_rxbank_set_nb_gate");
+    int rc = bank_rx_check(b, rx, "kg_rxbank_set_nb_gate");
     if (rc) return rc;
-    kg_rxbank::nb_cmd &c = b->nbc[rx];
+    bank_nb_cmd &c = b->rcv[rx].nbc;
     float snd[8];
     memcpy(snd, c.snd_param[KG_NB_BLANKER], sizeof snd);
     snd[KG_NB_GATE] = nb;                                                        // rx_sound_cmd.cpp:660-672
@@ -529,9 +626,8 @@ int kg_rxbank_set_nb_gate(kg_rxbank *b, int rx, int nb, int th, float frate)
 
 int kg_rxbank_nb_cmd_state(kg_rxbank *b, int rx, int32_t *ints, float *flts)
 {
-    int rc = bank_nb_rx(b, rx, "kg_rxbank_nb_cmd_state");
-    if (rc) return rc;
-    const kg_rxbank::nb_cmd &c = b->nbc[rx];
+    KG_TRY(bank_rx_check(b, rx, "kg_rxbank_nb_cmd_state"));
+    const bank_nb_cmd &c = b->rcv[rx].nbc;
     if (ints) {
         ints[0] = c.algo;
         for (int t = 0; t < 4; t++) { ints[1 + t] = c.snd_en[t]; ints[5 + t] = c.wf_en[t]; ints[9 + t] = c.wf_change[t]; }
@@ -541,36 +637,48 @@ int kg_rxbank_nb_cmd_state(kg_rxbank *b, int rx, int32_t *ints, float *flts)
     return KG_OK;
 }
 
-static int bank_init(kg_rxbank *b)
+}  // extern "C"
+
+// The four streams that carry kernels are created back to back, the upload's fifth.  Which hardware queue (and, behind
+// it, which of the four dispatch pipes) a stream lands on is the HIP runtime's choice -- the least-shared queue of its pool
+// at that moment -- and depends on every stream the process created before: measured on one bank, 0.98 ms per step or
+// 1.25 ... 1.38 by what had run earlier in the process (tools/micro/stream_pairs.hip measures which pairs of
+// streams run side by side).  Creating them together at least keeps them off one another's queues while the pool has
+// free ones.
+static int bank_streams(kg_rxbank *b)
 {
-    const int device = b->device, nrx = b->nrx, rx_mode = b->mode;
-    // The four streams that carry kernels are created back to back, the upload's fifth.  Which hardware queue (and, behind
-    // it, which of the four dispatch pipes) a stream lands on is the HIP runtime's choice -- the least-shared queue of its pool
-    // at that moment -- and depends on every stream the process created before: measured on one bank, 0.98 ms per step or
-    // 1.25 ... 1.38 by what had run earlier in the process (tools/micro/stream_pairs.hip measures which pairs of
-    // streams run side by side).  Creating them together at least keeps them off one another's queues while the pool has
-    // free ones.
-    bool reused = false;
     {
         std::lock_guard<std::mutex> lk(g_free_mutex);
         for (size_t i = 0; i < g_free_sets.size(); i++)
-            if (g_free_sets[i].device == device) {
+            if (g_free_sets[i].device == b->device) {
                 const bank_stream_set st = g_free_sets[i];
                 g_free_sets.erase(g_free_sets.begin() + (long) i);
-                b->s_main = st.s[0]; b->s_side = st.s[1]; b->s_tail = st.s[2]; b->s_ddc2 = st.s[3]; b->s_up = st.s[4];
-                reused = true;
-                break;
+                b->s_main = st.s[0]; b->s_side = st.s[1]; b->s_tail = st.s[2]; b->s_ddc_side = st.s[3]; b->s_up = st.s[4];
+                return KG_OK;
             }
     }
-    if (!reused)
-        for (hipStream_t *st : {&b->s_main, &b->s_side, &b->s_tail, &b->s_ddc2, &b->s_up}) KG_HIP(hipStreamCreateWithFlags(st, hipStreamNonBlocking));
+    for (hipStream_t *st : {&b->s_main, &b->s_side, &b->s_tail, &b->s_ddc_side, &b->s_up}) KG_HIP(hipStreamCreateWithFlags(st, hipStreamNonBlocking));
+    return KG_OK;
+}
+
+template <class T> static int bank_zalloc(kg_dbuf<T> &d, size_t count, const char *what)
+{
+    KG_TRY(d.alloc(count, what));
+    KG_HIP(hipMemset(d, 0, sizeof(T) * count));
+    return KG_OK;
+}
+
+// the contexts, the per-seam objects and the device buffers
+static int bank_alloc(kg_rxbank *b)
+{
+    const int device = b->device, nrx = b->nrx;
     KG_TRY(kg_ctx_create_on_stream(device, b->s_main, &b->c_main));
     KG_TRY(kg_ctx_create_on_stream(device, b->s_side, &b->c_side));
     KG_TRY(kg_ctx_create_on_stream(device, b->s_tail, &b->c_tail));
     KG_TRY(kg_ddc_create(b->c_main, nrx, b->n, &b->ddc));
-    KG_TRY(kg_ddc_use_side_stream(b->ddc, b->s_ddc2));
+    KG_TRY(kg_ddc_use_side_stream(b->ddc, b->s_ddc_side));
     KG_TRY(kg_wf_create(b->c_main, nrx, &b->wf));
-    KG_TRY(kg_rxddc_create_mode(b->c_side, nrx, b->n, rx_mode, &b->rx));
+    KG_TRY(kg_rxddc_create_mode(b->c_side, nrx, b->n, b->mode, &b->rx));
     b->decim_rx = kg_rxddc_decim(b->rx);
     b->nrec_max = b->n / (size_t) b->decim_rx + 2;
     KG_TRY(kg_fir_create(b->c_side, nrx, (int) b->nrec_max, &b->fir));
@@ -580,24 +688,42 @@ static int bank_init(kg_rxbank *b)
     KG_TRY(kg_fir_create(b->c_tail, nrx, KG_FIR_OUT, &b->nullfir));
     b->wf_stride = BANK_RING_PAIRS;
     b->firo_stride = ((b->nrec_max + KG_FIR_OUT - 1) / KG_FIR_OUT + 1) * KG_FIR_OUT;
-    KG_TRY(b->d_wfiq.alloc(b->wf_stride * nrx, "kg_rxbank_create: wfiq"));
-    KG_HIP(hipMemset(b->d_wfiq, 0, sizeof(short2) * b->wf_stride * nrx));
-    KG_TRY(b->d_rows.alloc((size_t) KG_WF_WIDTH * nrx, "kg_rxbank_create: rows"));
-    KG_TRY(b->d_pkts.alloc((size_t) BANK_PKT_STRIDE * nrx, "kg_rxbank_create: pkts"));
+    KG_TRY(bank_zalloc(b->d_wfiq, b->wf_stride * nrx, "kg_rxbank_create: wfiq"));
+    KG_TRY(bank_zalloc(b->d_rows, (size_t) KG_WF_WIDTH * nrx, "kg_rxbank_create: rows"));
+    KG_TRY(bank_zalloc(b->d_pkts, (size_t) BANK_PKT_STRIDE * nrx, "kg_rxbank_create: pkts"));
     KG_TRY(b->d_raw.alloc(6 * b->nrec_max * nrx, "kg_rxbank_create: raw"));
     KG_TRY(b->d_xin.alloc(b->nrec_max * nrx, "kg_rxbank_create: xin"));
     KG_TRY(b->d_firo.alloc(b->firo_stride * nrx, "kg_rxbank_create: firo"));
-    KG_TRY(b->d_s16.alloc(b->firo_stride * nrx, "kg_rxbank_create: s16"));
-    KG_TRY(b->d_pay.alloc(b->firo_stride / 2 * nrx, "kg_rxbank_create: pay"));
-    KG_HIP(hipMemset(b->d_rows, 0, (size_t) KG_WF_WIDTH * nrx));
-    KG_HIP(hipMemset(b->d_pkts, 0, (size_t) BANK_PKT_STRIDE * nrx));
-    KG_HIP(hipMemset(b->d_s16, 0, sizeof(short) * b->firo_stride * nrx));
-    KG_HIP(hipMemset(b->d_pay, 0, b->firo_stride / 2 * nrx));
-    KG_TRY(b->d_agc.alloc(b->firo_stride * nrx, "kg_rxbank_create: agc"));
-    KG_TRY(b->d_iqpay.alloc(4 * b->firo_stride * nrx, "kg_rxbank_create: iqpay"));
-    KG_HIP(hipMemset(b->d_agc, 0, sizeof(float2) * b->firo_stride * nrx));
-    KG_HIP(hipMemset(b->d_iqpay, 0, 4 * b->firo_stride * nrx));
-    b->little_endian.assign(nrx, 0);
+    KG_TRY(bank_zalloc(b->d_s16, b->firo_stride * nrx, "kg_rxbank_create: s16"));
+    KG_TRY(bank_zalloc(b->d_pay, b->firo_stride / 2 * nrx, "kg_rxbank_create: pay"));
+    KG_TRY(bank_zalloc(b->d_agc, b->firo_stride * nrx, "kg_rxbank_create: agc"));
+    KG_TRY(bank_zalloc(b->d_iqpay, 4 * b->firo_stride * nrx, "kg_rxbank_create: iqpay"));
+    return KG_OK;
+}
+
+// the plan's arrays at the size of the largest step: per receiver, per (receiver, sound block), per row
+static void bank_plan_init(bank_plan &p, size_t nrx, size_t blocks_max, size_t spec_max)
+{
+    for (std::vector<int32_t> *v : {&p.nrec, &p.nfir, &p.mode, &p.pb_n, &p.pb_base, &p.chan_of, &p.got_nrec, &p.got_nfir, &p.pkt_bytes}) v->assign(nrx, 0);
+    for (std::vector<int32_t> *v : {&p.spec_rx, &p.spec_inst, &p.spec_blk}) v->assign(spec_max, 0);
+    for (std::vector<int32_t> *v : {&p.act, &p.nb_list, &p.nb_cnt}) v->reserve(nrx);
+    for (std::vector<int32_t> *v : {&p.fx_list, &p.fx_nblk, &p.fx_inst, &p.fx_row, &p.fx_blk0}) v->reserve(2 * nrx * blocks_max);
+    for (std::vector<int32_t> *v : {&p.blk_chan, &p.blk_null_n, &p.blk_null_base}) v->reserve(3 * nrx * blocks_max);
+    p.blk_at.reserve(BL_N * blocks_max + 1);
+    p.pb_inst.assign(nrx, KG_SPEC_PASSBAND); p.null_inst.assign(nrx, KG_SPEC_CHAN_NULL); p.null_each.assign(nrx, KG_FIR_OUT);
+    p.null_row.assign(blocks_max * nrx, -1); p.fx_nullpos.assign(blocks_max, 0);
+    p.enabled.assign(nrx, 1); p.sam_null.assign(nrx, 0);
+    p.moves.reserve(nrx); p.out_off.assign(nrx, 0); p.max_out.assign(nrx, 0); p.h_nw.assign(nrx, 0);
+    p.frame_off.assign(nrx, 0); p.pkt_step.resize(nrx);
+    p.ring_w.assign(nrx, 0); p.ring_total.assign(nrx, 0); p.mirror.assign(nrx, kg_spec::emit_t{KG_SPEC_PASSBAND}); p.cmds.assign(nrx, 0);
+    p.nrec_max = p.nfir_max = p.nspec = p.nframes = p.fx_n = 0; p.wf_unset = -1; p.any_pb = false;
+}
+
+static int bank_init(kg_rxbank *b)
+{
+    const int nrx = b->nrx;
+    KG_TRY(bank_streams(b));
+    KG_TRY(bank_alloc(b));
     {   // what a step's tables can take: <= 12 of them + a channel list for S-meter / AGC / detector and one for the coder per sound
         // block (a receiver can complete nrec_max / 512 + 1 blocks in a step) -- checked HERE, not found out by every later step
         // (+ one for the channel-null filter per sound block)
@@ -628,37 +754,28 @@ static int bank_init(kg_rxbank *b)
     // rescale = MPOW(2, -RXOUT_SCALE + CUTESDR_SCALE) * MPOW(10, CICF_GAIN_dB / 20), rx/data_pump.cpp:73-74 (kg_rxbank_set_unpack overrides)
     b->rescale = powf(2.f, -23 + 15) * powf(10.f, 4.5f / 20.f); b->dc_i = b->dc_q = 0.f; b->spectral_inversion = 0;
     b->tail_pending = b->pk_pending = false; b->step = 0;
-    b->active.assign(nrx, 1); b->snd_seq.assign(nrx, 0); b->last_nrec.assign(nrx, 0); b->last_nfir.assign(nrx, 0);
     b->c_main->rows_by_chan = b->c_side->rows_by_chan = b->c_tail->rows_by_chan = 1;      // buffers hold one row per RECEIVER
-    b->decim.assign(nrx, 0); b->wf_set.assign(nrx, 0); b->overlapped.assign(nrx, 0);
-    b->ring_w.assign(nrx, 0); b->ring_total.assign(nrx, 0); b->ring_w2.assign(nrx, 0); b->ring_total2.assign(nrx, 0);
-    b->pkt.assign(nrx, kg_wf_pkt_info{0, 0, 0, 1});
-    b->all.resize(nrx); for (int i = 0; i < nrx; i++) b->all[i] = i;
-    b->h_nrec.assign(nrx, 0); b->h_nfir.assign(nrx, 0); b->chan_of.assign(nrx, 0); b->pkt_bytes.assign(nrx, 0); b->rx_of_frame.assign(nrx, -1);
-    b->out_off.assign(nrx, 0); b->max_out.assign(nrx, 0); b->h_nw.assign(nrx, 0); b->frame_off.assign(nrx, 0);
-    b->enabled.assign(nrx, 1); b->pkt_step.resize(nrx);
-    b->nbc.assign(nrx, kg_rxbank::nb_cmd{});
-    KG_TRY(b->d_spec.alloc(b->spec_max * KG_SPEC_ROW, "kg_rxbank_create: spec"));
-    KG_HIP(hipMemset(b->d_spec, 0, b->spec_max * KG_SPEC_ROW));
-    b->spec_on.assign(nrx, 0); b->spec_mirror.assign(nrx, kg_spec::emit_t{KG_SPEC_PASSBAND}); b->spec_mirror2 = b->spec_mirror;
-    b->spec_cmds.assign(nrx, 0); b->spec_n = 0;
-    for (std::vector<int32_t> *v : {&b->spec_rx, &b->spec_inst, &b->spec_blk, &b->spec_rx2, &b->spec_inst2, &b->spec_blk2}) v->assign(b->spec_max, 0);
-    b->sam_null.assign(nrx, 0); b->pb_inst.assign(nrx, KG_SPEC_PASSBAND); b->pb_n.assign(nrx, 0); b->pb_base.assign(nrx, 0);
-    b->null_row.assign(b->blocks_max * (size_t) nrx, -1);
-    b->null_each.assign(nrx, KG_FIR_OUT); b->null_inst.assign(nrx, KG_SPEC_CHAN_NULL);
-    b->fx = nullptr; b->fx_rate = 0; b->fx_on.assign(nrx, 0); b->fx_n = 0;
+    KG_TRY(bank_zalloc(b->d_spec, b->spec_max * KG_SPEC_ROW, "kg_rxbank_create: spec"));
+    b->fx = nullptr; b->fx_rate = 0;
     b->fx_stride = b->blocks_max * KG_FFTEXT_ROW; b->fx_max = b->blocks_max * (size_t) nrx;      // a receiver's function takes ONE instance's blocks
+    b->rcv.assign(nrx, bank_rx{});
+    bank_plan_init(b->plan, (size_t) nrx, b->blocks_max, b->spec_max);
+    b->spec_n = b->fx_n = 0;
+    for (std::vector<int32_t> *v : {&b->spec_rx, &b->spec_inst, &b->spec_blk}) v->assign(b->spec_max, 0);
+    b->frame_rx.assign(nrx, -1); b->pkt_bytes.assign(nrx, 0); b->frame_off.assign(nrx, 0);
     memset(&b->arena, 0, sizeof b->arena);
     memset(&b->last, 0, sizeof b->last);
     KG_HIP(hipDeviceSynchronize());
     return KG_OK;
 }
 
+extern "C" {
+
 void kg_rxbank_destroy(kg_rxbank *b)
 {
     if (!b) return;
     (void) hipSetDevice(b->device);
-    for (hipStream_t s : {b->s_main, b->s_side, b->s_tail, b->s_ddc2, b->s_up}) if (s) (void) hipStreamSynchronize(s);
+    for (hipStream_t s : {b->s_main, b->s_side, b->s_tail, b->s_ddc_side, b->s_up}) if (s) (void) hipStreamSynchronize(s);
     if (b->c_main && b->c_side && b->c_tail) bank_set_arena(b, KG_ARENA_OFF);
     kg_fftext_destroy(b->fx);
     kg_adpcm_destroy(b->adpcm); kg_post_destroy(b->post); kg_fir_destroy(b->nullfir); kg_fir_destroy(b->fir); kg_rxddc_destroy(b->rx); kg_nb_destroy(b->nb);
@@ -666,11 +783,11 @@ void kg_rxbank_destroy(kg_rxbank *b)
     kg_ctx_destroy(b->c_tail); kg_ctx_destroy(b->c_side); kg_ctx_destroy(b->c_main);
     for (int i = 0; i < BANK_SLOTS; i++) for (int j = 0; j < 3; j++) if (b->ev_end[i][j]) (void) hipEventDestroy(b->ev_end[i][j]);
     for (hipEvent_t e : {b->ev_tab, b->ev_fir, b->ev_tail, b->ev_frames, b->ev_pk}) if (e) (void) hipEventDestroy(e);
-    if (b->s_main && b->s_side && b->s_tail && b->s_ddc2 && b->s_up) {          // a complete set: kept for the next bank
+    if (b->s_main && b->s_side && b->s_tail && b->s_ddc_side && b->s_up) {          // a complete set: kept for the next bank
         std::lock_guard<std::mutex> lk(g_free_mutex);
-        g_free_sets.push_back(bank_stream_set{b->device, {b->s_main, b->s_side, b->s_tail, b->s_ddc2, b->s_up}});
+        g_free_sets.push_back(bank_stream_set{b->device, {b->s_main, b->s_side, b->s_tail, b->s_ddc_side, b->s_up}});
     } else {
-        for (hipStream_t s : {b->s_main, b->s_side, b->s_tail, b->s_ddc2, b->s_up}) if (s) (void) hipStreamDestroy(s);
+        for (hipStream_t s : {b->s_main, b->s_side, b->s_tail, b->s_ddc_side, b->s_up}) if (s) (void) hipStreamDestroy(s);
     }
     delete b;
 }
@@ -718,8 +835,8 @@ kg_fir *kg_rxbank_null_fir(kg_rxbank *b) { return b ? b->nullfir : nullptr; }
 // `SET spc_=%d` (rx_sound_cmd.cpp:332-339)
 int kg_rxbank_set_spec(kg_rxbank *b, int rx, int n)
 {
-    KG_REQUIRE(b && rx >= 0 && rx < b->nrx, KG_ERR_INVALID, "kg_rxbank_set_spec: receiver %d", rx);
-    b->spec_on[rx] = kg_spec::cmd_on(n) ? 1 : 0;
+    KG_TRY(bank_rx_check(b, rx, "kg_rxbank_set_spec"));
+    b->rcv[rx].spec_on = kg_spec::cmd_on(n) ? 1 : 0;
     return KG_OK;
 }
 
@@ -752,7 +869,7 @@ static int bank_fx_ensure(kg_rxbank *b)
 {
     if (b->fx) return KG_OK;
     KG_HIP(hipSetDevice(b->device));
-    for (hipStream_t s : {b->s_up, b->s_main, b->s_side, b->s_tail}) KG_HIP(hipStreamSynchronize(s));
+    KG_TRY(bank_drain(b, true));
     kg_fftext *fx = nullptr;
     int rc = kg_fftext_create(b->c_tail, b->nrx, &fx);
     if (rc == KG_OK) rc = b->d_fxpost.alloc(2 * (size_t) b->nrx * b->fx_stride, "kg_rxbank_fftext: spectra");
@@ -764,8 +881,8 @@ static int bank_fx_ensure(kg_rxbank *b)
     }
     if (rc == KG_OK && b->fx_rate > 0) rc = kg_fftext_set_rate(fx, b->fx_rate);
     if (rc) { kg_fftext_destroy(fx); b->d_fxpost.reset(); b->d_fxrows.reset(); return rc; }
-    for (std::vector<int32_t> *v : {&b->fx_rx, &b->fx_blk, &b->fx_bin, &b->fx_ent}) v->assign(b->fx_max, 0);
-    b->fx_nullpos.assign(b->blocks_max, 0);
+    bank_plan &p = b->plan;
+    for (std::vector<int32_t> *v : {&b->fx_rx, &b->fx_blk, &b->fx_bin, &p.fx_rx, &p.fx_blk, &p.fx_bin, &p.fx_ent}) v->assign(b->fx_max, 0);
     b->fx = fx;
     return KG_OK;
 }
@@ -782,25 +899,25 @@ int kg_rxbank_fftext_set_rate(kg_rxbank *b, double sample_rate)
 // `SET run=%d` (FFT.cpp:206-244): snd->isSAM and snd->mode == MODE_QAM are the bank's view of kg_post's mode NOW, as the reference reads them
 int kg_rxbank_fftext_set_run(kg_rxbank *b, int rx, int run)
 {
-    KG_REQUIRE(b && rx >= 0 && rx < b->nrx, KG_ERR_INVALID, "kg_rxbank_fftext_set_run: receiver %d", rx);
+    KG_TRY(bank_rx_check(b, rx, "kg_rxbank_fftext_set_run"));
     KG_REQUIRE(run >= KG_FFTEXT_OFF && run <= KG_FFTEXT_INTEG, KG_ERR_INVALID, "kg_rxbank_fftext_set_run: run %d (-1..2)", run);
     KG_TRY(bank_fx_ensure(b));
     const int mode = kg_post_get_mode(b->post, rx);
     KG_TRY(kg_fftext_set_run(b->fx, rx, run, mode >= KG_POST_SAM && mode <= KG_POST_QAM, mode == KG_POST_QAM));
-    b->fx_on[rx] = run != KG_FFTEXT_OFF;
+    b->rcv[rx].fx_on = run != KG_FFTEXT_OFF;
     return KG_OK;
 }
 
 int kg_rxbank_fftext_set_itime(kg_rxbank *b, int rx, double itime)
 {
-    KG_REQUIRE(b && rx >= 0 && rx < b->nrx, KG_ERR_INVALID, "kg_rxbank_fftext_set_itime: receiver %d", rx);
+    KG_TRY(bank_rx_check(b, rx, "kg_rxbank_fftext_set_itime"));
     KG_TRY(bank_fx_ensure(b));
     return kg_fftext_set_itime(b->fx, rx, itime);
 }
 
 int kg_rxbank_fftext_clear(kg_rxbank *b, int rx)
 {
-    KG_REQUIRE(b && rx >= 0 && rx < b->nrx, KG_ERR_INVALID, "kg_rxbank_fftext_clear: receiver %d", rx);
+    KG_TRY(bank_rx_check(b, rx, "kg_rxbank_fftext_clear"));
     KG_TRY(bank_fx_ensure(b));
     return kg_fftext_clear(b->fx, rx);
 }
@@ -833,8 +950,7 @@ int kg_rxbank_fftext_rows(kg_rxbank *b, uint8_t **d_rows, size_t *row_stride)
 
 int kg_rxbank_set_wf(kg_rxbank *b, int rx, uint64_t phase_inc, int decim, int overlapped)
 {
-    KG_REQUIRE(b != nullptr, KG_ERR_INVALID, "kg_rxbank_set_wf: null argument");
-    KG_REQUIRE(rx >= 0 && rx < b->nrx, KG_ERR_INVALID, "kg_rxbank_set_wf: receiver %d (0..%d)", rx, b->nrx - 1);
+    KG_TRY(bank_rx_check(b, rx, "kg_rxbank_set_wf"));
     KG_REQUIRE(decim >= 1 && (decim & (decim - 1)) == 0 && decim <= 8192, KG_ERR_INVALID, "kg_rxbank_set_wf: decimation %d", decim);
     if (overlapped) {
         const size_t m = b->n / (size_t) decim;
@@ -847,21 +963,22 @@ int kg_rxbank_set_wf(kg_rxbank *b, int rx, uint64_t phase_inc, int decim, int ov
                    "kg_rxbank_set_wf: a one-shot frame at R = %d takes %zu samples, a step has %zu: use the overlapped mode "
                    "(rx_waterfall.cpp:967-983)", decim, (size_t) KG_WF_NFFT * (size_t) decim, b->n);
     }
-    for (hipStream_t s : {b->s_main, b->s_side, b->s_tail}) KG_HIP(hipStreamSynchronize(s));
+    KG_TRY(bank_drain(b, false));
     int rc = kg_ddc_set_wf(b->ddc, rx, phase_inc, decim);
     if (rc) return rc;
-    if (b->wf_set[rx] && decim != b->decim[rx]) bank_nb_zoom_change(b, rx);
-    b->decim[rx] = decim; b->overlapped[rx] = overlapped ? 1 : 0; b->wf_set[rx] = 1;
-    b->ring_w[rx] = 0; b->ring_total[rx] = 0;             // CmdWFReset: the sampler starts empty ("fill pipe")
+    bank_rx &r = b->rcv[rx];
+    if (r.wf_set && decim != r.decim) bank_nb_zoom_change(b, rx);
+    r.decim = decim; r.overlapped = overlapped ? 1 : 0; r.wf_set = 1;
+    r.ring_w = 0; r.ring_total = 0;                        // CmdWFReset: the sampler starts empty ("fill pipe")
     return KG_OK;
 }
 
 // A connection ends: the receiver is left out of every stage from the next step on (its state stays where it is).
 int kg_rxbank_leave(kg_rxbank *b, int rx)
 {
-    KG_REQUIRE(b && rx >= 0 && rx < b->nrx, KG_ERR_INVALID, "kg_rxbank_leave: receiver %d", rx);
-    b->active[rx] = 0;
-    b->fx_on[rx] = 0;                                      // ext_unregister_receive_FFT_samps at the connection's end; its fft_t is gone with it
+    KG_TRY(bank_rx_check(b, rx, "kg_rxbank_leave"));
+    b->rcv[rx].active = 0;
+    b->rcv[rx].fx_on = 0;                                  // ext_unregister_receive_FFT_samps at the connection's end; its fft_t is gone with it
     if (b->fx) KG_TRY(kg_fftext_restart(b->fx, rx));
     return KG_OK;
 }
@@ -873,32 +990,33 @@ int kg_rxbank_leave(kg_rxbank *b, int rx)
 // (kg_rxddc_set_freq, kg_fir_setup, kg_post_*) as for a fresh bank.  Drains the bank's streams.
 int kg_rxbank_join(kg_rxbank *b, int rx)
 {
-    KG_REQUIRE(b && rx >= 0 && rx < b->nrx, KG_ERR_INVALID, "kg_rxbank_join: receiver %d", rx);
+    KG_TRY(bank_rx_check(b, rx, "kg_rxbank_join"));
     KG_HIP(hipSetDevice(b->device));
-    for (hipStream_t s : {b->s_up, b->s_main, b->s_side, b->s_tail}) KG_HIP(hipStreamSynchronize(s));
-    int rc;
-    if ((rc = kg_rxddc_reset(b->rx, rx))) return rc;
-    if ((rc = kg_fir_reset(b->fir, rx))) return rc;
-    if ((rc = kg_fir_reset(b->nullfir, rx))) return rc;
-    if ((rc = kg_post_reset(b->post, rx))) return rc;
-    if ((rc = kg_adpcm_set_state(b->adpcm, rx, 0, 0))) return rc;
-    for (hipStream_t s : {b->s_side, b->s_tail}) KG_HIP(hipStreamSynchronize(s));
-    b->snd_seq[rx] = 0; b->last_nrec[rx] = 0; b->last_nfir[rx] = 0;
-    b->wf_set[rx] = 0; b->ring_w[rx] = 0; b->ring_total[rx] = 0;
-    b->spec_on[rx] = 0; kg_spec::emit_clear(b->spec_mirror[rx]);      // memset(snd_t): specAF_FFT NULL, isChanNull false
-    b->spec_cmds[rx] = kg_post_mode_cmds_(b->post, rx);
-    b->fx_on[rx] = 0;                                      // the extension's state is the connection's: function off, nothing latched, sums zero
-    if (b->fx && (rc = kg_fftext_restart(b->fx, rx))) return rc;
-    b->nbc[rx] = kg_rxbank::nb_cmd{};                      // memset(snd_t) / memset(wf_inst_t): algo NB_OFF, enables and params 0;
-    if ((rc = kg_wf_set_nb(b->wf, rx, 0))) return rc;     // the blankers' states stay (the reference's CNoiseProc arrays are globals)
-    b->active[rx] = 1;
+    KG_TRY(bank_drain(b, true));
+    KG_TRY(kg_rxddc_reset(b->rx, rx));
+    KG_TRY(kg_fir_reset(b->fir, rx));
+    KG_TRY(kg_fir_reset(b->nullfir, rx));
+    KG_TRY(kg_post_reset(b->post, rx));
+    KG_TRY(kg_adpcm_set_state(b->adpcm, rx, 0, 0));
+    KG_TRY(bank_drain(b, false));
+    bank_rx &r = b->rcv[rx];
+    // the connection's fields, in bank_rx's order (the settings below them stay)
+    r.snd_seq = 0; r.last_nrec = 0; r.last_nfir = 0;
+    r.wf_set = 0; r.ring_w = 0; r.ring_total = 0;
+    r.spec_on = 0; kg_spec::emit_clear(r.spec_mirror);     // memset(snd_t): specAF_FFT NULL, isChanNull false
+    r.spec_cmds = kg_post_mode_cmds_(b->post, rx);
+    r.fx_on = 0;                                           // the extension's state is the connection's: function off, nothing latched, sums zero
+    if (b->fx) KG_TRY(kg_fftext_restart(b->fx, rx));
+    r.nbc = bank_nb_cmd{};                                 // memset(snd_t) / memset(wf_inst_t): algo NB_OFF, enables and params 0;
+    KG_TRY(kg_wf_set_nb(b->wf, rx, 0));                    // the blankers' states stay (the reference's CNoiseProc arrays are globals)
+    r.active = 1;
     return KG_OK;
 }
 
 int kg_rxbank_is_active(kg_rxbank *b, int rx)
 {
-    KG_REQUIRE(b && rx >= 0 && rx < b->nrx, KG_ERR_INVALID, "kg_rxbank_is_active: receiver %d", rx);
-    return b->active[rx] ? 1 : 0;
+    KG_TRY(bank_rx_check(b, rx, "kg_rxbank_is_active"));
+    return b->rcv[rx].active ? 1 : 0;
 }
 
 // Per receiver, after the last step (arrays of nrx entries, any may be NULL): rx_iq_t records and CFastFIR outputs the step gave
@@ -908,18 +1026,18 @@ int kg_rxbank_audio_map(kg_rxbank *b, int32_t *nrec, int32_t *nfir, int32_t *fir
 {
     KG_REQUIRE(b != nullptr, KG_ERR_INVALID, "kg_rxbank_audio_map: null argument");
     for (int k = 0; k < b->nrx; k++) {
-        if (nrec) nrec[k] = b->last_nrec[k];
-        if (nfir) nfir[k] = b->last_nfir[k];
+        if (nrec) nrec[k] = b->rcv[k].last_nrec;
+        if (nfir) nfir[k] = b->rcv[k].last_nfir;
         if (fir_pos) fir_pos[k] = kg_fir_pos(b->fir, k);
-        if (snd_seq) snd_seq[k] = b->snd_seq[k];
+        if (snd_seq) snd_seq[k] = b->rcv[k].snd_seq;
     }
     return KG_OK;
 }
 
 int kg_rxbank_set_little_endian(kg_rxbank *b, int rx, int little_endian)
 {
-    KG_REQUIRE(b && rx >= 0 && rx < b->nrx, KG_ERR_INVALID, "kg_rxbank_set_little_endian: receiver %d", rx);
-    b->little_endian[rx] = little_endian ? 1 : 0;
+    KG_TRY(bank_rx_check(b, rx, "kg_rxbank_set_little_endian"));
+    b->rcv[rx].little_endian = little_endian ? 1 : 0;
     return KG_OK;
 }
 
@@ -932,9 +1050,45 @@ int kg_rxbank_set_unpack(kg_rxbank *b, float rescale, float dc_i, float dc_q, in
 
 int kg_rxbank_set_wf_pkt(kg_rxbank *b, int rx, uint32_t x_bin_server, uint32_t zoom, int use_compression)
 {
-    KG_REQUIRE(b && rx >= 0 && rx < b->nrx, KG_ERR_INVALID, "kg_rxbank_set_wf_pkt: receiver %d", rx);
-    if (zoom != b->pkt[rx].zoom) bank_nb_zoom_change(b, rx);
-    b->pkt[rx].x_bin_server = x_bin_server; b->pkt[rx].zoom = zoom; b->pkt[rx].use_compression = use_compression ? 1 : 0;
+    KG_TRY(bank_rx_check(b, rx, "kg_rxbank_set_wf_pkt"));
+    kg_wf_pkt_info &pkt = b->rcv[rx].pkt;
+    if (zoom != pkt.zoom) bank_nb_zoom_change(b, rx);
+    pkt.x_bin_server = x_bin_server; pkt.zoom = zoom; pkt.use_compression = use_compression ? 1 : 0;
+    return KG_OK;
+}
+
+// rx_waterfall.cpp:1087-1096: a pending parameter change is set up before the receiver's next frame, once both enables are on
+static int bank_wf_nb_pending(kg_rxbank *b)
+{
+    for (int k = 0; k < b->nrx; k++) {
+        if (!b->rcv[k].active) continue;
+        bank_nb_cmd &c = b->rcv[k].nbc;
+        const bool both = c.wf_en[KG_NB_BLANKER] && c.wf_en[KG_NB_WF];
+        if (both && c.wf_change[KG_NB_BLANKER]) {
+            KG_TRY(kg_wf_nb_setup(b->wf, k, c.wf_param[KG_NB_BLANKER]));
+            c.wf_change[KG_NB_BLANKER] = 0;
+            c.wf_setup = 1;
+        }
+        KG_TRY(kg_wf_set_nb(b->wf, k, both && c.wf_setup));
+    }
+    return KG_OK;
+}
+
+// the ONE transfer of the step, on a stream of its own (ordered behind nothing but earlier uploads: the slot is free)
+static int bank_upload(kg_rxbank *b, void *adc_ready_event)
+{
+    const kg_arena &a = b->arena;
+    hipStream_t us = b->s_up;
+    if (const char *ev = kg_tuning_env("KIWIGPU_BANK_UPLOAD")) us = ev[0] == 'm' ? b->s_main : (ev[0] == 's' ? b->s_side : b->s_up);
+    hipError_t e = hipMemcpyAsync(a.d_base, a.h_base, a.used, hipMemcpyHostToDevice, us);
+    if (e == hipSuccess) e = hipEventRecord(b->ev_tab, us);
+    if (e == hipSuccess && us != b->s_main) e = hipStreamWaitEvent(b->s_main, b->ev_tab, 0);
+    if (e == hipSuccess && us != b->s_side) e = hipStreamWaitEvent(b->s_side, b->ev_tab, 0);
+    if (e == hipSuccess && adc_ready_event) {
+        e = hipStreamWaitEvent(b->s_main, (hipEvent_t) adc_ready_event, 0);
+        if (e == hipSuccess) e = hipStreamWaitEvent(b->s_side, (hipEvent_t) adc_ready_event, 0);
+    }
+    if (e != hipSuccess) { kg_set_error("kg_rxbank_step: %s", hipGetErrorString(e)); return KG_ERR_HIP; }
     return KG_OK;
 }
 
@@ -950,45 +1104,21 @@ int kg_rxbank_step(kg_rxbank *b, const void *d_adc, void *adc_ready_event, kg_rx
     a.h_base = b->h_slots + (size_t) slot * b->slot_bytes; a.d_base = b->d_slots + (size_t) slot * b->slot_bytes;
     a.cap = b->slot_bytes; a.used = 0; a.nent = 0; a.cursor = 0;
     tk.lap(b, PF_UPLOAD, true);
-    {   // rx_waterfall.cpp:1087-1096: a pending parameter change is set up before the receiver's next frame, once both enables are on
-        int rc0;
-        for (int k = 0; k < b->nrx; k++) {
-            if (!b->active[k]) continue;
-            kg_rxbank::nb_cmd &c = b->nbc[k];
-            const bool both = c.wf_en[KG_NB_BLANKER] && c.wf_en[KG_NB_WF];
-            if (both && c.wf_change[KG_NB_BLANKER]) {
-                if ((rc0 = kg_wf_nb_setup(b->wf, k, c.wf_param[KG_NB_BLANKER]))) return rc0;
-                c.wf_change[KG_NB_BLANKER] = 0;
-                c.wf_setup = 1;
-            }
-            if ((rc0 = kg_wf_set_nb(b->wf, k, both && c.wf_setup))) return rc0;
-        }
-    }
+    KG_TRY(bank_wf_nb_pending(b));
+    bank_plan_step(b);
     bank_set_arena(b, KG_ARENA_PLAN);
-    int rc = bank_pass(b, d_adc, true);
+    int rc = bank_pass(b, d_adc);
     tk.lap(b, PF_PLAN, true);
-    if (rc == KG_OK) {
-        // the ONE transfer of the step, on a stream of its own (ordered behind nothing but earlier uploads: the slot is free)
-        hipStream_t us = b->s_up;
-        if (const char *ev = kg_tuning_env("KIWIGPU_BANK_UPLOAD")) us = ev[0] == 'm' ? b->s_main : (ev[0] == 's' ? b->s_side : b->s_up);
-        hipError_t e = hipMemcpyAsync(a.d_base, a.h_base, a.used, hipMemcpyHostToDevice, us);
-        if (e == hipSuccess) e = hipEventRecord(b->ev_tab, us);
-        if (e == hipSuccess && us != b->s_main) e = hipStreamWaitEvent(b->s_main, b->ev_tab, 0);
-        if (e == hipSuccess && us != b->s_side) e = hipStreamWaitEvent(b->s_side, b->ev_tab, 0);
-        if (e == hipSuccess && adc_ready_event) {
-            e = hipStreamWaitEvent(b->s_main, (hipEvent_t) adc_ready_event, 0);
-            if (e == hipSuccess) e = hipStreamWaitEvent(b->s_side, (hipEvent_t) adc_ready_event, 0);
-        }
-        if (e != hipSuccess) { kg_set_error("kg_rxbank_step: %s", hipGetErrorString(e)); rc = KG_ERR_HIP; }
-    }
+    if (rc == KG_OK) rc = bank_upload(b, adc_ready_event);
     tk.lap(b, PF_UPLOAD, true);
     if (rc == KG_OK) {
         a.mode = KG_ARENA_REPLAY;
-        rc = bank_pass(b, d_adc, false);
+        rc = bank_pass(b, d_adc);
         if (rc == KG_OK && a.cursor != a.nent) { kg_set_error("kg_rxbank_step: %d of %d planned tables replayed", a.cursor, a.nent); rc = KG_ERR_STATE; }
     }
     bank_set_arena(b, KG_ARENA_OFF);
     if (rc) return rc;
+    bank_commit(b);
     tk = bank_tick();
     KG_HIP(hipEventRecord(b->ev_end[slot][0], b->s_main));
     KG_HIP(hipEventRecord(b->ev_end[slot][1], b->s_side));
@@ -1047,8 +1177,7 @@ int kg_rxbank_sync(kg_rxbank *b)
 {
     KG_REQUIRE(b != nullptr, KG_ERR_INVALID, "kg_rxbank_sync: null argument");
     KG_HIP(hipSetDevice(b->device));
-    for (hipStream_t s : {b->s_up, b->s_main, b->s_side, b->s_tail}) KG_HIP(hipStreamSynchronize(s));
-    return KG_OK;
+    return bank_drain(b, true);
 }
 
 // The host's share of the steps since the last call (or since create), by phase: text into buf.  The slot wait is where a
@@ -1083,7 +1212,7 @@ int kg_rxbank_frame_map(kg_rxbank *b, int32_t *rx_of_frame, uint64_t *frame_off,
 {
     KG_REQUIRE(b != nullptr, KG_ERR_INVALID, "kg_rxbank_frame_map: null argument");
     for (int f = 0; f < b->last.nframes; f++) {
-        if (rx_of_frame) rx_of_frame[f] = b->rx_of_frame[f];
+        if (rx_of_frame) rx_of_frame[f] = b->frame_rx[f];
         if (frame_off) frame_off[f] = b->frame_off[f];
         if (pkt_bytes) pkt_bytes[f] = b->pkt_bytes[f];
     }

@@ -3,7 +3,7 @@ import os
 import sys
 import time
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")      # (the library's constructor does the same; torch is imported first)
+os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")      # (the host's to set, as bench.py does: the library leaves the environment alone)
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from flydog_sdr_gps_amd import synth                                   # noqa: E402
