@@ -134,7 +134,8 @@ def test_bank_error_paths():
     # settings that could only fail later, on every step, fail when they are made (the advisor's round-5 finding): an overlapped
     # sampler that yields an odd number of outputs per step.  (The other one -- the largest step, 2^27 samples of the rx3
     # instance, is 43 sound blocks per receiver and needed more table entries than a step had -- is sized for now: the step table
-    # holds 58 blocks, and kg_rxbank_create checks its step against that.)
+    # holds 45 blocks (16 + 5 per block <= KG_ARENA_MAX_ENTRIES = 244), and kg_rxbank_create checks its step against that;
+    # tests/test_rxbank_stepsize_gpu.py steps that bank.)
     bank = RxBank(1, 8192)
     try:
         p14 = WfParams.for_zoom(14, 1.0e6 / hz, adc_clock=ADC_CLOCK, ui_srate=UI_SRATE)     # R = 8192: one output per step
