@@ -209,6 +209,34 @@ SYMBOLS = {
     "kg_fftext_process": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _sz, _vp, _sz, _i, _vp, _vp, _vp, _vp]),
     "kg_fftext_due": (_i, [_vp, _i, C.c_uint32]),
     "kg_fftext_state": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "kg_iqd_create": (_i, [_vp, _i, C.POINTER(_vp)]),
+    "kg_iqd_destroy": (None, [_vp]),
+    "kg_iqd_init": (_i, [_vp, _i]),
+    "kg_iqd_set_run": (_i, [_vp, _i, _i, C.c_double]),
+    "kg_iqd_set_gain": (_i, [_vp, _i, _i]),
+    "kg_iqd_set_points": (_i, [_vp, _i, _i]),
+    "kg_iqd_set_pll_mode": (_i, [_vp, _i, _i, _i]),
+    "kg_iqd_set_pll_bandwidth": (_i, [_vp, _i, C.c_float]),
+    "kg_iqd_set_draw": (_i, [_vp, _i, _i]),
+    "kg_iqd_set_display_mode": (_i, [_vp, _i, _i]),
+    "kg_iqd_clear": (_i, [_vp, _i]),
+    "kg_iqd_process_dev": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _i, _vp]),
+    "kg_iqd_process": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _i, _vp]),
+    "kg_iqd_state": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    "kg_iqd_math_dev": (_i, [_vp, _i, _vp, _vp, _sz, _vp]),
+    "kg_rxbank_iqd_init": (_i, [_vp, _i]),
+    "kg_rxbank_iqd_set_run": (_i, [_vp, _i, _i, C.c_double]),
+    "kg_rxbank_iqd_set_gain": (_i, [_vp, _i, _i]),
+    "kg_rxbank_iqd_set_points": (_i, [_vp, _i, _i]),
+    "kg_rxbank_iqd_set_pll_mode": (_i, [_vp, _i, _i, _i]),
+    "kg_rxbank_iqd_set_pll_bandwidth": (_i, [_vp, _i, C.c_float]),
+    "kg_rxbank_iqd_set_draw": (_i, [_vp, _i, _i]),
+    "kg_rxbank_iqd_set_display_mode": (_i, [_vp, _i, _i]),
+    "kg_rxbank_iqd_clear": (_i, [_vp, _i]),
+    "kg_rxbank_iqd": (_vp, [_vp]),
+    "kg_rxbank_iqd_map": (_i, [_vp, _vp, _i]),
+    "kg_rxbank_iqd_rows": (_i, [_vp, _vp, _vp]),
+    "kg_rxbank_iqd_status": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "kg_rxbank_fftext_set_rate": (_i, [_vp, C.c_double]),
     "kg_rxbank_fftext_set_run": (_i, [_vp, _i, _i]),
     "kg_rxbank_fftext_set_itime": (_i, [_vp, _i, C.c_double]),

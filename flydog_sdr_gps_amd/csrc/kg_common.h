@@ -227,6 +227,12 @@ __attribute__((visibility("hidden"))) int kg_fftext_process_rows_(kg_fftext *fx,
                                                                   size_t row_stride, int max_rows, int32_t *rx_of_row, int32_t *ent_of_row,
                                                                   int32_t *blk_of_row, int32_t *bin_of_row);
 
+// kg_iqd.hip, for kg_rxbank.hip (not part of the ABI): kg_iqd_process_dev with entry i's samples at row iq_row[i] of d_iq
+__attribute__((visibility("hidden"))) int kg_iqd_process_rows_(kg_iqd *q, const int32_t *chans, int nch, const int32_t *nblk, const int32_t *inst,
+                                                               const int32_t *iq_row, int ns, const float *d_iq, size_t iq_stride, uint8_t *d_rows,
+                                                               size_t rows_cap, kg_iqd_status *d_status, size_t status_cap, kg_iqd_row *row_map,
+                                                               int max_rows, int32_t *status_sent);
+
 // kg_post.hip, for kg_rxbank.hip: how many kg_post_set_mode / kg_post_set_sam_mparam calls channel ch has seen (each clears
 // s->isChanNull, rx_sound_cmd.cpp:202-228), and its s->SAM_mparam
 __attribute__((visibility("hidden"))) uint32_t kg_post_mode_cmds_(const kg_post *p, int ch);

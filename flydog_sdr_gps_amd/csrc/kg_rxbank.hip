@@ -70,6 +70,7 @@ struct bank_rx {
     kg_spec::emit_t spec_mirror = {KG_SPEC_PASSBAND};
     uint32_t spec_cmds = 0;
     char fx_on = 0;                             // the FFT extension's run != FUNC_OFF
+    char iq_on = 0;                             // the IQ display's `SET run=` (ext_register_receive_iq_samps)
     bank_nb_cmd nbc = {};
     // the settings a join leaves alone
     int decim = 0; char overlapped = 0;         // kg_rxbank_set_wf
@@ -96,6 +97,10 @@ struct bank_plan {
     std::vector<int32_t> null_each, null_inst;          // constants: 512 samples, KG_SPEC_CHAN_NULL
     // the FFT extension's entries: receiver, blocks, instance, where the spectra lie in d_fxpost, the entry's first sound block
     std::vector<int32_t> fx_list, fx_nblk, fx_inst, fx_row, fx_blk0, fx_nullpos;
+    // the IQ display's entries: receiver, blocks, instance (0), the receiver's row of d_firo; what the call hands back
+    std::vector<int32_t> iq_list, iq_nblk, iq_inst, iq_row, iq_sent;
+    std::vector<kg_iqd_row> iq_rows;
+    int iq_n;
     // per sound block: list j of block blk is blk_chan[blk_at[BL_N * blk + j] .. blk_at[BL_N * blk + j + 1]); beside a BL_NULL
     // entry its row count and row
     std::vector<int32_t> blk_chan, blk_at, blk_null_n, blk_null_base;
@@ -132,6 +137,15 @@ struct kg_rxbank {
     // nothing for it and enqueues what it always did.  While a receiver's function is on, both filters store their filtered spectra
     // (receive_FFT(POST_FILTERED), fastfir.cpp:293-302) and the extension runs ONCE per step over the step's blocks, on the tail stream.
     kg_fftext *fx; double fx_rate;
+    // the IQ display extension (extensions/IQ_display/iq_display.cpp; kg_iqd), made by the first kg_rxbank_iqd_* call.  While a receiver
+    // has run on and is not in NBFM, its CFastFIR output of the step (receive_iq_pre_agc, rx_sound.cpp:668-669) feeds it: ONE launch per
+    // step over all such receivers and their sound blocks, on the tail stream.
+    kg_iqd *iq;
+    kg_dbuf<unsigned char> d_iqrows; size_t iq_cap; int iq_max_rows;      // the step's rows back to back: (512 B + 16384) * 4 bytes a receiver
+    kg_dbuf<kg_iqd_status> d_iqst;                                        // a record per (entry, sound block) of the step's call
+    int iq_n, iq_nblk;
+    std::vector<kg_iqd_row> iq_rows;
+    std::vector<int32_t> iq_blk_rx, iq_blk_blk, iq_sent;
     // device buffers
     kg_dbuf<short2> d_wfiq; size_t wf_stride;         // [nrx][wf_stride] iq_t: a one-shot receiver uses pairs 0 .. 8191 of its row, an overlapped one all of it
     kg_dbuf<unsigned char> d_rows, d_pkts;         // [frame][1024], [frame][BANK_PKT_STRIDE]
@@ -243,6 +257,9 @@ static void bank_plan_rows(kg_rxbank *b, int i, int nblk)
         if (rows.chan_null) { p.spec_rx[p.nspec] = k; p.spec_inst[p.nspec] = KG_SPEC_CHAN_NULL; p.spec_blk[p.nspec] = blk; p.nspec++; }
     }
     p.mirror[i] = m;
+    if (b->iq && r.iq_on && nblk > 0 && p.mode[i] != KG_POST_NBFM) {      // receive_iq_pre_agc is NULL while isNBFM (rx_sound.cpp:492)
+        p.iq_list.push_back(k); p.iq_nblk.push_back(nblk); p.iq_inst.push_back(0); p.iq_row.push_back(k);
+    }
 }
 
 // The active list and, per entry, the counts its audio DDC and its CFastFIR will hand back (kg_rxddc_outputs is kg_rxddc_push_dev's
@@ -251,9 +268,11 @@ static void bank_plan_rows(kg_rxbank *b, int i, int nblk)
 static void bank_plan_audio(kg_rxbank *b)
 {
     bank_plan &p = b->plan;
-    for (std::vector<int32_t> *v : {&p.act, &p.nb_list, &p.nb_cnt, &p.fx_list, &p.fx_nblk, &p.fx_inst, &p.fx_row, &p.fx_blk0}) v->clear();
+    for (std::vector<int32_t> *v : {&p.act, &p.nb_list, &p.nb_cnt, &p.fx_list, &p.fx_nblk, &p.fx_inst, &p.fx_row, &p.fx_blk0, &p.iq_list, &p.iq_nblk, &p.iq_inst,
+                                    &p.iq_row})
+        v->clear();
     std::fill(p.fx_nullpos.begin(), p.fx_nullpos.end(), 0);
-    p.nrec_max = p.nfir_max = p.nspec = p.fx_n = 0;
+    p.nrec_max = p.nfir_max = p.nspec = p.fx_n = p.iq_n = 0;
     p.any_pb = false;
     for (int k = 0; k < b->nrx; k++) {
         const bank_rx &r = b->rcv[k];
@@ -415,7 +434,7 @@ static int bank_audio_front(kg_rxbank *b, const void *d_adc)
     return KG_OK;
 }
 
-// the tail stream, per sound block: S-meter, CAgc, detector; the channel-null filter; the coders.  Then the FFT extension.
+// the tail stream, per sound block: S-meter, CAgc, detector; the channel-null filter; the coders.  Then the FFT extension and the IQ display.
 static int bank_audio_tail(kg_rxbank *b)
 {
     bank_plan &p = b->plan;
@@ -456,6 +475,13 @@ static int bank_audio_tail(kg_rxbank *b)
                                                p.fx_rx.data(), p.fx_ent.data(), p.fx_blk.data(), p.fx_bin.data());
         if (rc < 0) return rc;
         p.fx_n = rc;
+    }
+    if (!p.iq_list.empty()) {                              // iq_display_data over the step's blocks: one launch, behind the filter, ahead of ev_tail
+        const int rc = kg_iqd_process_rows_(b->iq, p.iq_list.data(), (int) p.iq_list.size(), p.iq_nblk.data(), p.iq_inst.data(), p.iq_row.data(), KG_FIR_OUT,
+                                            (const float *) b->d_firo.p, b->firo_stride, b->d_iqrows, b->iq_cap, b->d_iqst, NR * b->blocks_max,
+                                            p.iq_rows.data(), b->iq_max_rows, p.iq_sent.data());
+        if (rc < 0) return rc;
+        p.iq_n = rc;
     }
     KG_TRY(bank_edge(real, b->ev_tail, b->s_tail, nullptr, &b->tail_pending));
     tk.lap(b, PF_EVENTS, real);
@@ -515,6 +541,12 @@ static void bank_commit(kg_rxbank *b)
     }
     for (int r = 0; r < p.fx_n; r++) p.fx_blk[r] += p.fx_blk0[p.fx_ent[r]];      // the sound block of the step
     b->spec_n = p.nspec; b->fx_n = p.fx_n;
+    b->iq_n = p.iq_n; b->iq_nblk = 0;
+    if (b->iq) {
+        b->iq_rows.swap(p.iq_rows); b->iq_sent.swap(p.iq_sent);
+        for (size_t e = 0; e < p.iq_list.size(); e++)
+            for (int blk = 0; blk < p.iq_nblk[e]; blk++) { b->iq_blk_rx[b->iq_nblk] = p.iq_list[e]; b->iq_blk_blk[b->iq_nblk] = blk; b->iq_nblk++; }
+    }
     b->spec_rx.swap(p.spec_rx); b->spec_inst.swap(p.spec_inst); b->spec_blk.swap(p.spec_blk);
     b->fx_rx.swap(p.fx_rx); b->fx_blk.swap(p.fx_blk); b->fx_bin.swap(p.fx_bin);
     b->frame_rx.swap(p.chan_of); b->frame_off.swap(p.frame_off); b->pkt_bytes.swap(p.pkt_bytes);
@@ -708,6 +740,7 @@ static void bank_plan_init(bank_plan &p, size_t nrx, size_t blocks_max, size_t s
     for (std::vector<int32_t> *v : {&p.spec_rx, &p.spec_inst, &p.spec_blk}) v->assign(spec_max, 0);
     for (std::vector<int32_t> *v : {&p.act, &p.nb_list, &p.nb_cnt}) v->reserve(nrx);
     for (std::vector<int32_t> *v : {&p.fx_list, &p.fx_nblk, &p.fx_inst, &p.fx_row, &p.fx_blk0}) v->reserve(2 * nrx * blocks_max);
+    for (std::vector<int32_t> *v : {&p.iq_list, &p.iq_nblk, &p.iq_inst, &p.iq_row}) v->reserve(nrx);
     for (std::vector<int32_t> *v : {&p.blk_chan, &p.blk_null_n, &p.blk_null_base}) v->reserve(3 * nrx * blocks_max);
     p.blk_at.reserve(BL_N * blocks_max + 1);
     p.pb_inst.assign(nrx, KG_SPEC_PASSBAND); p.null_inst.assign(nrx, KG_SPEC_CHAN_NULL); p.null_each.assign(nrx, KG_FIR_OUT);
@@ -716,7 +749,7 @@ static void bank_plan_init(bank_plan &p, size_t nrx, size_t blocks_max, size_t s
     p.moves.reserve(nrx); p.out_off.assign(nrx, 0); p.max_out.assign(nrx, 0); p.h_nw.assign(nrx, 0);
     p.frame_off.assign(nrx, 0); p.pkt_step.resize(nrx);
     p.ring_w.assign(nrx, 0); p.ring_total.assign(nrx, 0); p.mirror.assign(nrx, kg_spec::emit_t{KG_SPEC_PASSBAND}); p.cmds.assign(nrx, 0);
-    p.nrec_max = p.nfir_max = p.nspec = p.nframes = p.fx_n = 0; p.wf_unset = -1; p.any_pb = false;
+    p.nrec_max = p.nfir_max = p.nspec = p.nframes = p.fx_n = p.iq_n = 0; p.wf_unset = -1; p.any_pb = false;
 }
 
 static int bank_init(kg_rxbank *b)
@@ -738,7 +771,9 @@ static int bank_init(kg_rxbank *b)
         // the channel-null filter's table of 8 ints per receiver and its alignment; + 64 per table -- up to 12 and 4 per sound
         // block -- for the 64-byte alignment arena_stage gives every entry)
         // (+ the FFT extension's table: 2 groups of 32 bytes and 2 ops of 16 per sound block, per receiver)
-        b->slot_bytes = (8192 + 64 * blocks_max + 64 * (13 + 4 * blocks_max) + (size_t) (448 + 16 + 64 + (12 + 32 + 32) * blocks_max) * nrx + 63) & ~(size_t) 63;
+        // (+ the IQ display's table: a group of 112 bytes per receiver, an op of 32 per sound block, and its alignment)
+        b->slot_bytes = (8192 + 64 + 64 * blocks_max + 64 * (13 + 4 * blocks_max) + (size_t) (448 + 16 + 64 + 112 + (12 + 32 + 32 + 32) * blocks_max) * nrx + 63) &
+                        ~(size_t) 63;
         b->spec_max = 2 * blocks_max * (size_t) nrx;                         // a passband and a channel-null row per sound block
     }
     KG_TRY(b->h_slots.alloc(b->slot_bytes * BANK_SLOTS, "kg_rxbank_create: slots"));
@@ -761,6 +796,12 @@ static int bank_init(kg_rxbank *b)
     b->rcv.assign(nrx, bank_rx{});
     bank_plan_init(b->plan, (size_t) nrx, b->blocks_max, b->spec_max);
     b->spec_n = b->fx_n = 0;
+    b->iq = nullptr; b->iq_n = b->iq_nblk = 0;
+    b->iq_cap = (size_t) nrx * (KG_FIR_OUT * b->blocks_max + KG_IQD_RING) * 4;
+    {   // a row per sample at points = 1; the map is the host's, so a large bank's is bounded (a step with more rows is refused)
+        const size_t rows = (size_t) nrx * b->blocks_max * KG_FIR_OUT;
+        b->iq_max_rows = (int) (rows < ((size_t) 1 << 18) ? rows : ((size_t) 1 << 18));
+    }
     for (std::vector<int32_t> *v : {&b->spec_rx, &b->spec_inst, &b->spec_blk}) v->assign(b->spec_max, 0);
     b->frame_rx.assign(nrx, -1); b->pkt_bytes.assign(nrx, 0); b->frame_off.assign(nrx, 0);
     memset(&b->arena, 0, sizeof b->arena);
@@ -778,6 +819,7 @@ void kg_rxbank_destroy(kg_rxbank *b)
     for (hipStream_t s : {b->s_main, b->s_side, b->s_tail, b->s_ddc_side, b->s_up}) if (s) (void) hipStreamSynchronize(s);
     if (b->c_main && b->c_side && b->c_tail) bank_set_arena(b, KG_ARENA_OFF);
     kg_fftext_destroy(b->fx);
+    kg_iqd_destroy(b->iq);
     kg_adpcm_destroy(b->adpcm); kg_post_destroy(b->post); kg_fir_destroy(b->nullfir); kg_fir_destroy(b->fir); kg_rxddc_destroy(b->rx); kg_nb_destroy(b->nb);
     kg_wf_destroy(b->wf); kg_ddc_destroy(b->ddc);
     kg_ctx_destroy(b->c_tail); kg_ctx_destroy(b->c_side); kg_ctx_destroy(b->c_main);
@@ -948,6 +990,85 @@ int kg_rxbank_fftext_rows(kg_rxbank *b, uint8_t **d_rows, size_t *row_stride)
     return KG_OK;
 }
 
+// The IQ display's object and buffers, made whole or not at all by the first call that names the extension.  Drains the bank's streams.
+static int bank_iq_ensure(kg_rxbank *b)
+{
+    if (b->iq) return KG_OK;
+    KG_HIP(hipSetDevice(b->device));
+    KG_TRY(bank_drain(b, true));
+    kg_iqd *iq = nullptr;
+    const size_t nst = (size_t) b->nrx * b->blocks_max;
+    int rc = kg_iqd_create(b->c_tail, b->nrx, &iq);
+    if (rc == KG_OK) rc = b->d_iqrows.alloc(b->iq_cap, "kg_rxbank_iqd: rows");
+    if (rc == KG_OK) rc = b->d_iqst.alloc(nst, "kg_rxbank_iqd: status");
+    if (rc == KG_OK && (hipMemset(b->d_iqrows, 0, b->iq_cap) != hipSuccess || hipMemset(b->d_iqst, 0, sizeof(kg_iqd_status) * nst) != hipSuccess)) {
+        kg_set_error("kg_rxbank_iqd: hipMemset failed");
+        rc = KG_ERR_HIP;
+    }
+    if (rc) { kg_iqd_destroy(iq); b->d_iqrows.reset(); b->d_iqst.reset(); return rc; }
+    bank_plan &p = b->plan;
+    for (std::vector<kg_iqd_row> *v : {&b->iq_rows, &p.iq_rows}) v->assign((size_t) b->iq_max_rows, kg_iqd_row{});
+    for (std::vector<int32_t> *v : {&b->iq_sent, &p.iq_sent, &b->iq_blk_rx, &b->iq_blk_blk}) v->assign(nst, 0);
+    b->iq = iq;
+    return KG_OK;
+}
+
+#define BANK_IQ(who)                                   \
+    KG_TRY(bank_rx_check(b, rx, who));                 \
+    KG_TRY(bank_iq_ensure(b))
+
+int kg_rxbank_iqd_init(kg_rxbank *b, int rx)
+{
+    BANK_IQ("kg_rxbank_iqd_init");
+    b->rcv[rx].iq_on = 0;                                  // a fresh object is not registered
+    return kg_iqd_init(b->iq, rx);
+}
+
+int kg_rxbank_iqd_set_run(kg_rxbank *b, int rx, int run, double rate)
+{
+    BANK_IQ("kg_rxbank_iqd_set_run");
+    KG_TRY(kg_iqd_set_run(b->iq, rx, run, rate));
+    b->rcv[rx].iq_on = run != 0;
+    return KG_OK;
+}
+
+int kg_rxbank_iqd_set_gain(kg_rxbank *b, int rx, int gain) { BANK_IQ("kg_rxbank_iqd_set_gain"); return kg_iqd_set_gain(b->iq, rx, gain); }
+int kg_rxbank_iqd_set_points(kg_rxbank *b, int rx, int points) { BANK_IQ("kg_rxbank_iqd_set_points"); return kg_iqd_set_points(b->iq, rx, points); }
+int kg_rxbank_iqd_set_pll_mode(kg_rxbank *b, int rx, int pll_mode, int arg) { BANK_IQ("kg_rxbank_iqd_set_pll_mode"); return kg_iqd_set_pll_mode(b->iq, rx, pll_mode, arg); }
+int kg_rxbank_iqd_set_pll_bandwidth(kg_rxbank *b, int rx, float bandwidth) { BANK_IQ("kg_rxbank_iqd_set_pll_bandwidth"); return kg_iqd_set_pll_bandwidth(b->iq, rx, bandwidth); }
+int kg_rxbank_iqd_set_draw(kg_rxbank *b, int rx, int draw) { BANK_IQ("kg_rxbank_iqd_set_draw"); return kg_iqd_set_draw(b->iq, rx, draw); }
+int kg_rxbank_iqd_set_display_mode(kg_rxbank *b, int rx, int display_mode) { BANK_IQ("kg_rxbank_iqd_set_display_mode"); return kg_iqd_set_display_mode(b->iq, rx, display_mode); }
+int kg_rxbank_iqd_clear(kg_rxbank *b, int rx) { BANK_IQ("kg_rxbank_iqd_clear"); return kg_iqd_clear(b->iq, rx); }
+
+kg_iqd *kg_rxbank_iqd(kg_rxbank *b) { return b ? b->iq : nullptr; }
+
+int kg_rxbank_iqd_map(kg_rxbank *b, kg_iqd_row *row_map, int max_rows)
+{
+    KG_REQUIRE(b != nullptr && max_rows >= 0, KG_ERR_INVALID, "kg_rxbank_iqd_map: bad argument");
+    KG_REQUIRE(!row_map || max_rows >= b->iq_n, KG_ERR_INVALID, "kg_rxbank_iqd_map: %d rows, room for %d", b->iq_n, max_rows);
+    if (row_map && b->iq_n) memcpy(row_map, b->iq_rows.data(), sizeof(kg_iqd_row) * (size_t) b->iq_n);
+    return b->iq_n;
+}
+
+int kg_rxbank_iqd_rows(kg_rxbank *b, uint8_t **d_rows, size_t *rows_cap)
+{
+    KG_REQUIRE(b && d_rows && rows_cap, KG_ERR_INVALID, "kg_rxbank_iqd_rows: null argument");
+    *d_rows = b->d_iqrows; *rows_cap = b->iq_cap;                 // null until the extension was named
+    return KG_OK;
+}
+
+int kg_rxbank_iqd_status(kg_rxbank *b, kg_iqd_status **d_status, int32_t *rx_of_blk, int32_t *blk_of_blk, int32_t *sent_of_blk)
+{
+    KG_REQUIRE(b != nullptr, KG_ERR_INVALID, "kg_rxbank_iqd_status: null argument");
+    if (d_status) *d_status = b->d_iqst;
+    for (int k = 0; k < b->iq_nblk; k++) {
+        if (rx_of_blk) rx_of_blk[k] = b->iq_blk_rx[k];
+        if (blk_of_blk) blk_of_blk[k] = b->iq_blk_blk[k];
+        if (sent_of_blk) sent_of_blk[k] = b->iq_sent[k];
+    }
+    return b->iq_nblk;
+}
+
 int kg_rxbank_set_wf(kg_rxbank *b, int rx, uint64_t phase_inc, int decim, int overlapped)
 {
     KG_TRY(bank_rx_check(b, rx, "kg_rxbank_set_wf"));
@@ -980,6 +1101,8 @@ int kg_rxbank_leave(kg_rxbank *b, int rx)
     b->rcv[rx].active = 0;
     b->rcv[rx].fx_on = 0;                                  // ext_unregister_receive_FFT_samps at the connection's end; its fft_t is gone with it
     if (b->fx) KG_TRY(kg_fftext_restart(b->fx, rx));
+    b->rcv[rx].iq_on = 0;                                  // iq_display_close: the object goes with the connection
+    if (b->iq) KG_TRY(kg_iqd_init(b->iq, rx));
     return KG_OK;
 }
 
@@ -1007,6 +1130,8 @@ int kg_rxbank_join(kg_rxbank *b, int rx)
     r.spec_cmds = kg_post_mode_cmds_(b->post, rx);
     r.fx_on = 0;                                           // the extension's state is the connection's: function off, nothing latched, sums zero
     if (b->fx) KG_TRY(kg_fftext_restart(b->fx, rx));
+    r.iq_on = 0;                                           // the IQ display's object is the connection's: a fresh one, not registered
+    if (b->iq) KG_TRY(kg_iqd_init(b->iq, rx));
     r.nbc = bank_nb_cmd{};                                 // memset(snd_t) / memset(wf_inst_t): algo NB_OFF, enables and params 0;
     KG_TRY(kg_wf_set_nb(b->wf, rx, 0));                    // the blankers' states stay (the reference's CNoiseProc arrays are globals)
     r.active = 1;

@@ -253,6 +253,68 @@ class RxBank:
             self.ctx.download(int(d.value), out)
         return out[:, :1024]
 
+    # ---- the IQ display extension (extensions/IQ_display/iq_display.cpp): kg_iqd's commands per receiver
+    def iqd_init(self, rx):
+        check(self.lib.kg_rxbank_iqd_init(self.h, int(rx)), "kg_rxbank_iqd_init")
+
+    def iqd_set_run(self, rx, run, rate):
+        check(self.lib.kg_rxbank_iqd_set_run(self.h, int(rx), int(run), float(rate)), "kg_rxbank_iqd_set_run")
+
+    def iqd_set_gain(self, rx, gain):
+        check(self.lib.kg_rxbank_iqd_set_gain(self.h, int(rx), int(gain)), "kg_rxbank_iqd_set_gain")
+
+    def iqd_set_points(self, rx, points):
+        check(self.lib.kg_rxbank_iqd_set_points(self.h, int(rx), int(points)), "kg_rxbank_iqd_set_points")
+
+    def iqd_set_pll_mode(self, rx, pll_mode, arg):
+        check(self.lib.kg_rxbank_iqd_set_pll_mode(self.h, int(rx), int(pll_mode), int(arg)), "kg_rxbank_iqd_set_pll_mode")
+
+    def iqd_set_pll_bandwidth(self, rx, bandwidth):
+        check(self.lib.kg_rxbank_iqd_set_pll_bandwidth(self.h, int(rx), float(bandwidth)), "kg_rxbank_iqd_set_pll_bandwidth")
+
+    def iqd_set_draw(self, rx, draw):
+        check(self.lib.kg_rxbank_iqd_set_draw(self.h, int(rx), int(draw)), "kg_rxbank_iqd_set_draw")
+
+    def iqd_set_display_mode(self, rx, display_mode):
+        check(self.lib.kg_rxbank_iqd_set_display_mode(self.h, int(rx), int(display_mode)), "kg_rxbank_iqd_set_display_mode")
+
+    def iqd_clear(self, rx):
+        check(self.lib.kg_rxbank_iqd_clear(self.h, int(rx)), "kg_rxbank_iqd_clear")
+
+    @property
+    def iqd(self):
+        """the bank's IqDisplay (None until one of the iqd_* commands was sent): state()"""
+        from . import iqd as iq_mod
+        h = self.lib.kg_rxbank_iqd(self.h)
+        return borrow(iq_mod.IqDisplay, self.ctx, h, nchan=self.nrx) if h else None
+
+    def iqd_rows(self):
+        """-> (row map [rows] of iqd.row_dtype -- ch the receiver, blk the sound block of the step --, the rows' bytes uint8) of the
+        last step (after sync())"""
+        from . import iqd as iq_mod
+        n = check(self.lib.kg_rxbank_iqd_map(self.h, None, 0), "kg_rxbank_iqd_map")
+        m = np.zeros(max(n, 1), iq_mod.row_dtype)
+        check(self.lib.kg_rxbank_iqd_map(self.h, ptr(m), int(m.size)), "kg_rxbank_iqd_map")
+        m = m[:n]
+        d, cap = C.c_void_p(), C.c_size_t()
+        check(self.lib.kg_rxbank_iqd_rows(self.h, C.byref(d), C.byref(cap)), "kg_rxbank_iqd_rows")
+        out = np.zeros(int(m["off"][-1] + m["len"][-1]) if n else 0, np.uint8)
+        if out.size:
+            self.ctx.download(int(d.value), out)
+        return m, out
+
+    def iqd_status(self):
+        """-> (records of iqd.status_dtype, rx_of_blk, blk_of_blk, sent_of_blk) of the last step (after sync())"""
+        from . import iqd as iq_mod
+        n = check(self.lib.kg_rxbank_iqd_status(self.h, None, None, None, None), "kg_rxbank_iqd_status")
+        rx_of, blk, sent = (np.zeros(max(n, 1), np.int32) for _ in range(3))
+        d = C.c_void_p()
+        check(self.lib.kg_rxbank_iqd_status(self.h, C.byref(d), ptr(rx_of), ptr(blk), ptr(sent)), "kg_rxbank_iqd_status")
+        st = np.zeros(n, iq_mod.status_dtype)
+        if n:
+            self.ctx.download(int(d.value), st)
+        return st, rx_of[:n], blk[:n], sent[:n]
+
     def fftext_set_rate(self, sample_rate):
         """what ext_update_get_sample_rateHz answers for the FFT extension (extensions/FFT/FFT.cpp:79)"""
         check(self.lib.kg_rxbank_fftext_set_rate(self.h, float(sample_rate)), "kg_rxbank_fftext_set_rate")

@@ -1235,6 +1235,87 @@ int kg_fftext_due(kg_fftext *fx, int ch, uint32_t now_ms);
 /* Channel ch's state; pwr (200 x 1024 floats) and ncma (200) may be NULL.  With pwr it synchronises. */
 int kg_fftext_state(kg_fftext *fx, int ch, kg_fftext_info *info, float *pwr, int32_t *ncma);
 
+/* The IQ display extension (extensions/IQ_display/iq_display.cpp with rx/kiwi/pll.h), a consumer of receive_iq_samps(PRE_AGC): the
+ * CFastFIR output of every sound block (kg_fir_process_dev's d_out; none while the receiver is in NBFM).  The constellation in
+ * points mode (per ring entry the byte pairs of the sample that was there and of the new one, a row of points * 4 bytes whenever the
+ * ring comes round) and in density mode (a row of points * 2 bytes from the map both instances share); carrier recovery by a
+ * second-order PLL on the sample raised to a power (1 / 2 / 4 / 8: BPSK .. 8PSK) or by two PLLs on its square (MSK); the running
+ * complex mean and amplitude mean, and the four numbers of the text message (cmaI, cmaQ, df, phase).  Every byte and every float
+ * is an exact function of the samples: csrc/kg_iqd.h is the one definition for device and host, the device's sinf / cosf / atan2f /
+ * fmodf / hypotf are the host libm's bit for bit.  NaN or infinite samples, and overflow inside the power (|s|^8 needs |s| < 6e4),
+ * are outside the contract.
+ * The schedule (ring positions, rows, maN, nsamp -- :71-111) depends on no sample: it runs on the host, and nothing here synchronises
+ * but the calls that say so.  Commands take effect between calls, in call order.
+ *   kg_iqd_create            nchan channels (1 .. 1024), 416 KiB of device memory each (_iq, _plot, _map) plus the scalars
+ *   kg_iqd_init              `SET ext_server_init`: the constructor's state (points 1024, exponent 1, 12 kHz, bandwidth 10, gain auto,
+ *                            every array zero).  Every other call on a channel needs it first (KG_ERR_STATE).
+ *   kg_iqd_set_run           `SET run=%d`: run != 0 is set_sample_rate((float) rate) -- maNsend = fs / 4 and the three PLLs re-initialised,
+ *                            nothing else; rate as ext_update_get_sample_rateHz answers (1 .. 1e9, else KG_ERR_INVALID).
+ *   kg_iqd_set_gain          `SET gain=%d`: (float) pow(10.0, ((float) gain - 50) / 10.0), 0 for auto
+ *   kg_iqd_set_points        `SET points=%d`; outside 1 .. 16384 KG_ERR_INVALID (the reference leaves its arrays or sends a negative length)
+ *   kg_iqd_set_pll_mode      `SET pll_mode=%d arg=%d`: <= 1: exponent = arg (0: PLL off), MSK off; 2: exponent 2, MSK on, baud = arg; all
+ *                            re-initialise the PLLs.  A negative exponent is KG_ERR_INVALID: not ported (its division is libgcc's).
+ *   kg_iqd_set_pll_bandwidth / kg_iqd_set_draw (0 points, 1 density, anything else: no sample is processed) / kg_iqd_set_display_mode
+ *                            (0 multiplies by the carrier, anything else shows the carrier) / kg_iqd_clear (`SET clear`: cma, ama, maN,
+ *                            nsamp, the PLLs; the rings stay) */
+typedef struct kg_iqd kg_iqd;
+enum { KG_IQD_POINTS = 0, KG_IQD_DENSITY = 1 };            /* IQ_POINTS, IQ_DENSITY, iq_display.cpp:21-22 */
+enum { KG_IQD_MATH_HYPOTF = 0, KG_IQD_MATH_FMODF = 1 };
+#define KG_IQD_RING 16384                                  /* N_IQ_RING, iq_display.cpp:25 */
+#define KG_IQD_MAX_NS 512
+typedef struct kg_iqd_status {             /* what the text message of :108 carries */
+    float cmaI, cmaQ;
+    double df;
+    float phase;
+    int32_t reserved;
+} kg_iqd_status;
+typedef struct kg_iqd_row {                /* one ext_send_msg_data of :82 / :93 */
+    int32_t ch, ent, blk, samp;            /* channel, list entry, block within the entry, the sample behind which the row went out */
+    int32_t cmd, len;                      /* (draw << 1) + instance; points * 4 or points * 2 bytes */
+    int64_t off;                           /* from d_rows */
+} kg_iqd_row;
+typedef struct kg_iqd_info {
+    int32_t inited, run, points, nsamp, exponent, msk_mode, msk_baud, draw, display_mode, maN, maNsend, ring[2], reserved;
+    float gain, fs, pll_bandwidth, cmaI, cmaQ, ama;
+    float pll[3][7];                       /* _pll, _pllMinus, _pllPlus: fs, fc, df, phase, b[0], b[1], ud */
+} kg_iqd_info;
+int kg_iqd_create(kg_ctx *ctx, int nchan, kg_iqd **out);
+void kg_iqd_destroy(kg_iqd *q);
+int kg_iqd_init(kg_iqd *q, int ch);
+int kg_iqd_set_run(kg_iqd *q, int ch, int run, double rate);
+int kg_iqd_set_gain(kg_iqd *q, int ch, int gain);
+int kg_iqd_set_points(kg_iqd *q, int ch, int points);
+int kg_iqd_set_pll_mode(kg_iqd *q, int ch, int pll_mode, int arg);
+int kg_iqd_set_pll_bandwidth(kg_iqd *q, int ch, float bandwidth);
+int kg_iqd_set_draw(kg_iqd *q, int ch, int draw);
+int kg_iqd_set_display_mode(kg_iqd *q, int ch, int display_mode);
+int kg_iqd_clear(kg_iqd *q, int ch);
+/* display_data for nblk[i] blocks of ns samples (1 .. 512) of channel chans[i] as instance inst[i] (0 / 1: the `ch` of the class; the
+ * call site of rx_sound.cpp passes 0), entries in list order, a channel's blocks in block order (a channel may be listed more than
+ * once): block b of entry i is the ns complex floats at d_iq + 2 * (i*iq_stride + ns*b) (iq_stride in complex samples; d_iq 8-byte
+ * aligned).  Rows are packed back to back into d_rows (16-byte aligned, rows_cap bytes) in the order the reference sends them;
+ * row_map[r] (max_rows entries; may be NULL) says whose row r is, where it is and how long.  The k-th block of the call (list order)
+ * leaves its status record in d_status[k] (8-byte aligned, status_cap records) and, on the host, status_sent[k] (may be NULL): 1
+ * when the reference sends the text message behind that block (nsamp > maNsend).  Returns the number of rows.  ONE kernel launch.
+ * 1 <= nch <= 4096, 0 <= nblk[i] <= 4096, at most 8192 blocks a call.
+ * Refused, with nothing changed and nothing enqueued: KG_ERR_INVALID for an argument out of range (ns, an instance), more row bytes
+ * than rows_cap, more rows than max_rows, more blocks than status_cap; KG_ERR_STATE for a channel without kg_iqd_init or without a
+ * sample rate (kg_iqd_set_run with run != 0).
+ * Read: 8 * ns * nblk[i] bytes of row i of d_iq.  Written: the bytes the row map names, one status record per block.  Enqueue only. */
+int kg_iqd_process_dev(kg_iqd *q, const int32_t *chans, int nch, const int32_t *nblk, const int32_t *inst, int ns, const float *d_iq, size_t iq_stride,
+                       uint8_t *d_rows, size_t rows_cap, kg_iqd_status *d_status, size_t status_cap, kg_iqd_row *row_map, int max_rows,
+                       int32_t *status_sent);
+/* the same on host memory (row_map is needed); synchronises */
+int kg_iqd_process(kg_iqd *q, const int32_t *chans, int nch, const int32_t *nblk, const int32_t *inst, int ns, const float *iq, size_t iq_stride,
+                   uint8_t *rows, size_t rows_cap, kg_iqd_status *status, size_t status_cap, kg_iqd_row *row_map, int max_rows, int32_t *status_sent);
+/* Channel ch's whole state, for tests: iq (2 x 16384 complex floats), plot (2 x 16384 x 4 bytes) and map (16384 x 2 bytes) may be NULL.
+ * Synchronises. */
+int kg_iqd_state(kg_iqd *q, int ch, kg_iqd_info *info, float *iq, uint8_t *plot, uint8_t *map);
+/* d_out[i] = hypotf(d_a[i], d_b[i]) (KG_IQD_MATH_HYPOTF: std::abs of a complex float) or fmodf(d_a[i], d_b[i]) (KG_IQD_MATH_FMODF: the
+ * PLL's phase wrap) as the device code of kg_iqd computes them: the host libm's values, bit for bit (tests/test_iqd_gpu.py).  4-byte
+ * aligned arrays of n floats.  Enqueue only. */
+int kg_iqd_math_dev(kg_ctx *ctx, int fn, const float *d_a, const float *d_b, size_t n, float *d_out);
+
 /* Diagnostics: re-runs the 4096-point stage of the forward FFT of `block` in a
  * stamped build of the kernel and returns 4 s_memrealtime readings (100 MHz):
  * start, inputs + twiddles loaded, transform done, results stored. */
@@ -1363,6 +1444,38 @@ kg_fftext *kg_rxbank_fftext(kg_rxbank *bank);
 int kg_rxbank_fftext_max(kg_rxbank *bank);
 int kg_rxbank_fftext_map(kg_rxbank *bank, int32_t *rx_of_row, int32_t *blk_of_row, int32_t *bin_of_row);
 int kg_rxbank_fftext_rows(kg_rxbank *bank, uint8_t **d_rows, size_t *row_stride);
+
+/* The IQ display extension of the bank's receivers (kg_iqd above; extensions/IQ_display/iq_display.cpp).  The first of these calls makes
+ * the bank's kg_iqd object and two buffers (the rows, the status records) and drains the bank's streams; a bank that was never told
+ * holds nothing for the extension (but room for its table in the step's arena slots, whose size is fixed at kg_rxbank_create) and
+ * enqueues exactly what it enqueued without it.  The commands are kg_iqd's, per receiver:
+ * kg_rxbank_iqd_init (`SET ext_server_init`), kg_rxbank_iqd_set_run (`SET run=%d` with what ext_update_get_sample_rateHz answers) and
+ * the seven of process_msg.  While a receiver has run on and is not in KG_POST_NBFM in a step (receive_iq_pre_agc is NULL while isNBFM,
+ * rx_sound.cpp:492), the CFastFIR output of its sound blocks of that step feeds the extension as instance 0: ONE launch per step over
+ * all such receivers, on the tail stream behind the filter.  kg_rxbank_join and kg_rxbank_leave give the receiver a fresh object, run
+ * off.  A step the extension refuses (more rows than the map holds: 512 per receiver and sound block, 2^18 at most) is refused as a
+ * whole, nothing enqueued.
+ *   kg_rxbank_iqd         the object (NULL until one of the calls above): kg_iqd_state
+ *   kg_rxbank_iqd_map     the rows of the last step (kg_iqd_row: ch the receiver, blk the sound block of the step, off from d_rows);
+ *                         row_map may be NULL.  Returns the number of rows.
+ *   kg_rxbank_iqd_rows    the device buffer and its size, (512 B + 16384) * 4 bytes per receiver for a step of up to B sound blocks
+ *                         (NULL until the extension was named; read behind kg_rxbank_sync)
+ *   kg_rxbank_iqd_status  the status records of the last step, one per fed (receiver, sound block) in the order of the call: the
+ *                         device buffer, and on the host whose record k is and whether the reference sends it (arrays of nrx x the
+ *                         step's largest block count; any may be NULL).  Returns the number of records. */
+int kg_rxbank_iqd_init(kg_rxbank *bank, int rx);
+int kg_rxbank_iqd_set_run(kg_rxbank *bank, int rx, int run, double rate);
+int kg_rxbank_iqd_set_gain(kg_rxbank *bank, int rx, int gain);
+int kg_rxbank_iqd_set_points(kg_rxbank *bank, int rx, int points);
+int kg_rxbank_iqd_set_pll_mode(kg_rxbank *bank, int rx, int pll_mode, int arg);
+int kg_rxbank_iqd_set_pll_bandwidth(kg_rxbank *bank, int rx, float bandwidth);
+int kg_rxbank_iqd_set_draw(kg_rxbank *bank, int rx, int draw);
+int kg_rxbank_iqd_set_display_mode(kg_rxbank *bank, int rx, int display_mode);
+int kg_rxbank_iqd_clear(kg_rxbank *bank, int rx);
+kg_iqd *kg_rxbank_iqd(kg_rxbank *bank);
+int kg_rxbank_iqd_map(kg_rxbank *bank, kg_iqd_row *row_map, int max_rows);
+int kg_rxbank_iqd_rows(kg_rxbank *bank, uint8_t **d_rows, size_t *rows_cap);
+int kg_rxbank_iqd_status(kg_rxbank *bank, kg_iqd_status **d_status, int32_t *rx_of_blk, int32_t *blk_of_blk, int32_t *sent_of_blk);
 /* CmdSetWFFreq + CmdSetWFDecim + the sampler mode sample_wf() decides on (rx/rx_waterfall.cpp:962-1008):
  *   overlapped == 0   CmdWFReset + the one-shot sampler every step: the non-overlapped frame (:1005-1041); needs
  *                     8192 * decim <= adc_samples_per_step
