@@ -237,6 +237,31 @@ SYMBOLS = {
     "kg_rxbank_iqd_map": (_i, [_vp, _vp, _i]),
     "kg_rxbank_iqd_rows": (_i, [_vp, _vp, _vp]),
     "kg_rxbank_iqd_status": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "kg_lorc_create": (_i, [_vp, _i, C.POINTER(_vp)]),
+    "kg_lorc_destroy": (None, [_vp]),
+    "kg_lorc_init": (_i, [_vp, _i, C.c_double, _i]),
+    "kg_lorc_set_gri": (_i, [_vp, _i, _i, _i]),
+    "kg_lorc_set_offset": (_i, [_vp, _i, _i, _i]),
+    "kg_lorc_set_gain": (_i, [_vp, _i, _i, _i]),
+    "kg_lorc_set_avg_algo": (_i, [_vp, _i, _i, _i]),
+    "kg_lorc_set_avg_param": (_i, [_vp, _i, _i, C.c_double]),
+    "kg_lorc_start": (_i, [_vp, _i]),
+    "kg_lorc_stop": (_i, [_vp, _i]),
+    "kg_lorc_process": (_i, [_vp, _vp, _i, _vp, _i, _vp, _sz, _vp, _sz, _vp, _i, _vp]),
+    "kg_lorc_plan": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    "kg_lorc_state": (_i, [_vp, _i, _vp, _vp]),
+    "kg_lorc_ms_per_bin": (C.c_float, [C.c_double, _i]),
+    "kg_rxbank_lorc_init": (_i, [_vp, _i, C.c_double, _i]),
+    "kg_rxbank_lorc_set_gri": (_i, [_vp, _i, _i, _i]),
+    "kg_rxbank_lorc_set_offset": (_i, [_vp, _i, _i, _i]),
+    "kg_rxbank_lorc_set_gain": (_i, [_vp, _i, _i, _i]),
+    "kg_rxbank_lorc_set_avg_algo": (_i, [_vp, _i, _i, _i]),
+    "kg_rxbank_lorc_set_avg_param": (_i, [_vp, _i, _i, C.c_double]),
+    "kg_rxbank_lorc_start": (_i, [_vp, _i]),
+    "kg_rxbank_lorc_stop": (_i, [_vp, _i]),
+    "kg_rxbank_lorc": (_vp, [_vp]),
+    "kg_rxbank_lorc_map": (_i, [_vp, _vp, _i]),
+    "kg_rxbank_lorc_rows": (_i, [_vp, _vp, _vp]),
     "kg_rxbank_fftext_set_rate": (_i, [_vp, C.c_double]),
     "kg_rxbank_fftext_set_run": (_i, [_vp, _i, _i]),
     "kg_rxbank_fftext_set_itime": (_i, [_vp, _i, C.c_double]),

@@ -233,6 +233,17 @@ __attribute__((visibility("hidden"))) int kg_iqd_process_rows_(kg_iqd *q, const 
                                                                size_t rows_cap, kg_iqd_status *d_status, size_t status_cap, kg_iqd_row *row_map,
                                                                int max_rows, int32_t *status_sent);
 
+// kg_lorc.hip, for kg_rxbank.hip (not part of the ABI): kg_lorc_process on device memory, entry i's samples at row in_row[i] of d_iq
+// (null: row i), the rows packed into d_rows (16-byte aligned, each row at a multiple of 16); the bytes a call's table takes when no
+// channel has more than runs_per_channel runs; kg_lorc_set_gri refusing a GRI of fewer than min_spg samples too
+__attribute__((visibility("hidden"))) int kg_lorc_process_rows_(kg_lorc *q, const int32_t *conns, int nconn, const int32_t *nblk, const int32_t *in_row, int ns,
+                                                                const float *d_iq, size_t iq_stride, uint8_t *d_rows, size_t rows_cap, kg_lorc_row *row_map,
+                                                                int max_rows, int32_t *nrows);
+__attribute__((visibility("hidden"))) size_t kg_lorc_table_bytes_(size_t nconn, size_t runs_per_channel);
+__attribute__((visibility("hidden"))) int kg_lorc_set_gri_min_(kg_lorc *q, int conn, int ch, int gri, double min_spg);
+// connection conn as a new connection finds it: all zero, stopped, not initialised
+__attribute__((visibility("hidden"))) int kg_lorc_reset_(kg_lorc *q, int conn);
+
 // kg_post.hip, for kg_rxbank.hip: how many kg_post_set_mode / kg_post_set_sam_mparam calls channel ch has seen (each clears
 // s->isChanNull, rx_sound_cmd.cpp:202-228), and its s->SAM_mparam
 __attribute__((visibility("hidden"))) uint32_t kg_post_mode_cmds_(const kg_post *p, int ch);

@@ -31,6 +31,10 @@
 #include <mutex>
 #include <vector>
 
+// Loran-C in a bank: a GRI is BANK_LO_MIN_SPG samples or more, so a channel has at most 4 B + 4 runs (and rows) in a step of B sound
+// blocks: 4 B whole GRIs, a partial one, and the cuts where samp and the unsigned difference wrap
+#define BANK_LO_MIN_SPG 128.0
+#define BANK_LO_RUNS(blocks_) (4 * (size_t) (blocks_) + 4)
 #define BANK_SLOTS KG_RXBANK_SLOTS         // step-table slots in flight (a slot is reused BANK_SLOTS steps later)
 #define BANK_RING_PAIRS (8 * KG_WF_NFFT)   // an overlapped receiver's sample ring (iq_t pairs); >= 2 frames
 #define BANK_PKT_STRIDE 1056               // >= KG_WF_PKT_MAX, a multiple of 16
@@ -71,6 +75,7 @@ struct bank_rx {
     uint32_t spec_cmds = 0;
     char fx_on = 0;                             // the FFT extension's run != FUNC_OFF
     char iq_on = 0;                             // the IQ display's `SET run=` (ext_register_receive_iq_samps)
+    char lo_on = 0;                             // Loran-C's `SET start` (the same registration: one of the two at most)
     bank_nb_cmd nbc = {};
     // the settings a join leaves alone
     int decim = 0; char overlapped = 0;         // kg_rxbank_set_wf
@@ -101,6 +106,10 @@ struct bank_plan {
     std::vector<int32_t> iq_list, iq_nblk, iq_inst, iq_row, iq_sent;
     std::vector<kg_iqd_row> iq_rows;
     int iq_n;
+    // Loran-C's entries: receiver, blocks, the receiver's row of d_firo; what the call hands back
+    std::vector<int32_t> lo_list, lo_nblk, lo_row;
+    std::vector<kg_lorc_row> lo_rows;
+    int32_t lo_n;
     // per sound block: list j of block blk is blk_chan[blk_at[BL_N * blk + j] .. blk_at[BL_N * blk + j + 1]); beside a BL_NULL
     // entry its row count and row
     std::vector<int32_t> blk_chan, blk_at, blk_null_n, blk_null_base;
@@ -146,6 +155,13 @@ struct kg_rxbank {
     int iq_n, iq_nblk;
     std::vector<kg_iqd_row> iq_rows;
     std::vector<int32_t> iq_blk_rx, iq_blk_blk, iq_sent;
+    // the Loran-C extension (extensions/Loran_C/loran_c.cpp; kg_lorc), made by the first kg_rxbank_lorc_* call, which also grows the
+    // arena slots by its table.  While a receiver is started and not in NBFM, its CFastFIR output of the step feeds it in place: ONE
+    // launch per step over all such receivers, on the tail stream where the IQ display's launch sits.
+    kg_lorc *lo;
+    kg_dbuf<unsigned char> d_lorows; size_t lo_cap; int lo_max_rows;      // the step's rows, each at a multiple of 16 bytes
+    int lo_n;
+    std::vector<kg_lorc_row> lo_rows;
     // device buffers
     kg_dbuf<short2> d_wfiq; size_t wf_stride;         // [nrx][wf_stride] iq_t: a one-shot receiver uses pairs 0 .. 8191 of its row, an overlapped one all of it
     kg_dbuf<unsigned char> d_rows, d_pkts;         // [frame][1024], [frame][BANK_PKT_STRIDE]
@@ -260,6 +276,7 @@ static void bank_plan_rows(kg_rxbank *b, int i, int nblk)
     if (b->iq && r.iq_on && nblk > 0 && p.mode[i] != KG_POST_NBFM) {      // receive_iq_pre_agc is NULL while isNBFM (rx_sound.cpp:492)
         p.iq_list.push_back(k); p.iq_nblk.push_back(nblk); p.iq_inst.push_back(0); p.iq_row.push_back(k);
     }
+    if (b->lo && r.lo_on && nblk > 0 && p.mode[i] != KG_POST_NBFM) { p.lo_list.push_back(k); p.lo_nblk.push_back(nblk); p.lo_row.push_back(k); }
 }
 
 // The active list and, per entry, the counts its audio DDC and its CFastFIR will hand back (kg_rxddc_outputs is kg_rxddc_push_dev's
@@ -269,10 +286,11 @@ static void bank_plan_audio(kg_rxbank *b)
 {
     bank_plan &p = b->plan;
     for (std::vector<int32_t> *v : {&p.act, &p.nb_list, &p.nb_cnt, &p.fx_list, &p.fx_nblk, &p.fx_inst, &p.fx_row, &p.fx_blk0, &p.iq_list, &p.iq_nblk, &p.iq_inst,
-                                    &p.iq_row})
+                                    &p.iq_row, &p.lo_list, &p.lo_nblk, &p.lo_row})
         v->clear();
     std::fill(p.fx_nullpos.begin(), p.fx_nullpos.end(), 0);
     p.nrec_max = p.nfir_max = p.nspec = p.fx_n = p.iq_n = 0;
+    p.lo_n = 0;
     p.any_pb = false;
     for (int k = 0; k < b->nrx; k++) {
         const bank_rx &r = b->rcv[k];
@@ -483,6 +501,9 @@ static int bank_audio_tail(kg_rxbank *b)
         if (rc < 0) return rc;
         p.iq_n = rc;
     }
+    if (!p.lo_list.empty())                                // loran_c_data over the step's blocks: one launch, reading d_firo in place
+        KG_TRY(kg_lorc_process_rows_(b->lo, p.lo_list.data(), (int) p.lo_list.size(), p.lo_nblk.data(), p.lo_row.data(), KG_FIR_OUT, (const float *) b->d_firo.p,
+                                     b->firo_stride, b->d_lorows, b->lo_cap, p.lo_rows.data(), b->lo_max_rows, &p.lo_n));
     KG_TRY(bank_edge(real, b->ev_tail, b->s_tail, nullptr, &b->tail_pending));
     tk.lap(b, PF_EVENTS, real);
     return KG_OK;
@@ -547,6 +568,8 @@ static void bank_commit(kg_rxbank *b)
         for (size_t e = 0; e < p.iq_list.size(); e++)
             for (int blk = 0; blk < p.iq_nblk[e]; blk++) { b->iq_blk_rx[b->iq_nblk] = p.iq_list[e]; b->iq_blk_blk[b->iq_nblk] = blk; b->iq_nblk++; }
     }
+    b->lo_n = p.lo_n;
+    if (b->lo) b->lo_rows.swap(p.lo_rows);
     b->spec_rx.swap(p.spec_rx); b->spec_inst.swap(p.spec_inst); b->spec_blk.swap(p.spec_blk);
     b->fx_rx.swap(p.fx_rx); b->fx_blk.swap(p.fx_blk); b->fx_bin.swap(p.fx_bin);
     b->frame_rx.swap(p.chan_of); b->frame_off.swap(p.frame_off); b->pkt_bytes.swap(p.pkt_bytes);
@@ -740,7 +763,7 @@ static void bank_plan_init(bank_plan &p, size_t nrx, size_t blocks_max, size_t s
     for (std::vector<int32_t> *v : {&p.spec_rx, &p.spec_inst, &p.spec_blk}) v->assign(spec_max, 0);
     for (std::vector<int32_t> *v : {&p.act, &p.nb_list, &p.nb_cnt}) v->reserve(nrx);
     for (std::vector<int32_t> *v : {&p.fx_list, &p.fx_nblk, &p.fx_inst, &p.fx_row, &p.fx_blk0}) v->reserve(2 * nrx * blocks_max);
-    for (std::vector<int32_t> *v : {&p.iq_list, &p.iq_nblk, &p.iq_inst, &p.iq_row}) v->reserve(nrx);
+    for (std::vector<int32_t> *v : {&p.iq_list, &p.iq_nblk, &p.iq_inst, &p.iq_row, &p.lo_list, &p.lo_nblk, &p.lo_row}) v->reserve(nrx);
     for (std::vector<int32_t> *v : {&p.blk_chan, &p.blk_null_n, &p.blk_null_base}) v->reserve(3 * nrx * blocks_max);
     p.blk_at.reserve(BL_N * blocks_max + 1);
     p.pb_inst.assign(nrx, KG_SPEC_PASSBAND); p.null_inst.assign(nrx, KG_SPEC_CHAN_NULL); p.null_each.assign(nrx, KG_FIR_OUT);
@@ -749,7 +772,7 @@ static void bank_plan_init(bank_plan &p, size_t nrx, size_t blocks_max, size_t s
     p.moves.reserve(nrx); p.out_off.assign(nrx, 0); p.max_out.assign(nrx, 0); p.h_nw.assign(nrx, 0);
     p.frame_off.assign(nrx, 0); p.pkt_step.resize(nrx);
     p.ring_w.assign(nrx, 0); p.ring_total.assign(nrx, 0); p.mirror.assign(nrx, kg_spec::emit_t{KG_SPEC_PASSBAND}); p.cmds.assign(nrx, 0);
-    p.nrec_max = p.nfir_max = p.nspec = p.nframes = p.fx_n = p.iq_n = 0; p.wf_unset = -1; p.any_pb = false;
+    p.nrec_max = p.nfir_max = p.nspec = p.nframes = p.fx_n = p.iq_n = 0; p.lo_n = 0; p.wf_unset = -1; p.any_pb = false;
 }
 
 static int bank_init(kg_rxbank *b)
@@ -802,6 +825,10 @@ static int bank_init(kg_rxbank *b)
         const size_t rows = (size_t) nrx * b->blocks_max * KG_FIR_OUT;
         b->iq_max_rows = (int) (rows < ((size_t) 1 << 18) ? rows : ((size_t) 1 << 18));
     }
+    b->lo = nullptr; b->lo_n = 0;
+    // a row per run at most: BANK_LO_RUNS rows of up to 1200 bytes per receiver and Loran channel
+    b->lo_max_rows = (int) ((size_t) nrx * 2 * BANK_LO_RUNS(b->blocks_max));
+    b->lo_cap = (size_t) b->lo_max_rows * 1200;
     for (std::vector<int32_t> *v : {&b->spec_rx, &b->spec_inst, &b->spec_blk}) v->assign(b->spec_max, 0);
     b->frame_rx.assign(nrx, -1); b->pkt_bytes.assign(nrx, 0); b->frame_off.assign(nrx, 0);
     memset(&b->arena, 0, sizeof b->arena);
@@ -820,6 +847,7 @@ void kg_rxbank_destroy(kg_rxbank *b)
     if (b->c_main && b->c_side && b->c_tail) bank_set_arena(b, KG_ARENA_OFF);
     kg_fftext_destroy(b->fx);
     kg_iqd_destroy(b->iq);
+    kg_lorc_destroy(b->lo);
     kg_adpcm_destroy(b->adpcm); kg_post_destroy(b->post); kg_fir_destroy(b->nullfir); kg_fir_destroy(b->fir); kg_rxddc_destroy(b->rx); kg_nb_destroy(b->nb);
     kg_wf_destroy(b->wf); kg_ddc_destroy(b->ddc);
     kg_ctx_destroy(b->c_tail); kg_ctx_destroy(b->c_side); kg_ctx_destroy(b->c_main);
@@ -1027,6 +1055,7 @@ int kg_rxbank_iqd_init(kg_rxbank *b, int rx)
 int kg_rxbank_iqd_set_run(kg_rxbank *b, int rx, int run, double rate)
 {
     BANK_IQ("kg_rxbank_iqd_set_run");
+    KG_REQUIRE(!run || !b->rcv[rx].lo_on, KG_ERR_STATE, "kg_rxbank_iqd_set_run: receiver %d has Loran-C started; the tap holds one callback", rx);
     KG_TRY(kg_iqd_set_run(b->iq, rx, run, rate));
     b->rcv[rx].iq_on = run != 0;
     return KG_OK;
@@ -1069,6 +1098,81 @@ int kg_rxbank_iqd_status(kg_rxbank *b, kg_iqd_status **d_status, int32_t *rx_of_
     return b->iq_nblk;
 }
 
+// Loran-C's object and row buffer, and arena slots grown by its table, made whole or not at all by the first call that names the
+// extension.  Drains the bank's streams: no step is in flight while the slots change.
+static int bank_lo_ensure(kg_rxbank *b)
+{
+    if (b->lo) return KG_OK;
+    KG_HIP(hipSetDevice(b->device));
+    KG_TRY(bank_drain(b, true));
+    kg_lorc *lo = nullptr;
+    kg_hbuf<unsigned char> h;
+    kg_dbuf<unsigned char> d, rows;
+    const size_t grown = (b->slot_bytes + kg_lorc_table_bytes_((size_t) b->nrx, BANK_LO_RUNS(b->blocks_max)) + 63) & ~(size_t) 63;
+    KG_TRY(h.alloc(grown * BANK_SLOTS, "kg_rxbank_lorc: slots"));
+    KG_TRY(d.alloc(grown * BANK_SLOTS, "kg_rxbank_lorc: slots"));
+    KG_TRY(rows.alloc(b->lo_cap, "kg_rxbank_lorc: rows"));
+    if (hipMemset(rows, 0, b->lo_cap) != hipSuccess) { kg_set_error("kg_rxbank_lorc: hipMemset failed"); return KG_ERR_HIP; }
+    KG_TRY(kg_lorc_create(b->c_tail, b->nrx, &lo));
+    for (std::vector<kg_lorc_row> *v : {&b->lo_rows, &b->plan.lo_rows}) v->assign((size_t) b->lo_max_rows, kg_lorc_row{});
+    std::swap(b->h_slots.p, h.p); std::swap(b->d_slots.p, d.p); std::swap(b->d_lorows.p, rows.p);      // the old slots go with h and d
+    b->slot_bytes = grown;
+    b->lo = lo;
+    return KG_OK;
+}
+
+// the connection's end or beginning: loran_c[rx] as a new connection finds it -- stopped, waiting for its `SET ext_server_init`
+static int bank_lo_fresh(kg_rxbank *b, int rx)
+{
+    b->rcv[rx].lo_on = 0;
+    return b->lo ? kg_lorc_reset_(b->lo, rx) : KG_OK;
+}
+
+#define BANK_LO(who)                                   \
+    KG_TRY(bank_rx_check(b, rx, who));                 \
+    KG_TRY(bank_lo_ensure(b))
+
+int kg_rxbank_lorc_init(kg_rxbank *b, int rx, double srate, int i_srate) { BANK_LO("kg_rxbank_lorc_init"); return kg_lorc_init(b->lo, rx, srate, i_srate); }
+int kg_rxbank_lorc_set_gri(kg_rxbank *b, int rx, int ch, int gri) { BANK_LO("kg_rxbank_lorc_set_gri"); return kg_lorc_set_gri_min_(b->lo, rx, ch, gri, BANK_LO_MIN_SPG); }
+int kg_rxbank_lorc_set_offset(kg_rxbank *b, int rx, int ch, int offset) { BANK_LO("kg_rxbank_lorc_set_offset"); return kg_lorc_set_offset(b->lo, rx, ch, offset); }
+int kg_rxbank_lorc_set_gain(kg_rxbank *b, int rx, int ch, int gain) { BANK_LO("kg_rxbank_lorc_set_gain"); return kg_lorc_set_gain(b->lo, rx, ch, gain); }
+int kg_rxbank_lorc_set_avg_algo(kg_rxbank *b, int rx, int ch, int avg_algo) { BANK_LO("kg_rxbank_lorc_set_avg_algo"); return kg_lorc_set_avg_algo(b->lo, rx, ch, avg_algo); }
+int kg_rxbank_lorc_set_avg_param(kg_rxbank *b, int rx, int ch, double avg_param) { BANK_LO("kg_rxbank_lorc_set_avg_param"); return kg_lorc_set_avg_param(b->lo, rx, ch, avg_param); }
+
+int kg_rxbank_lorc_start(kg_rxbank *b, int rx)
+{
+    BANK_LO("kg_rxbank_lorc_start");
+    KG_REQUIRE(!b->rcv[rx].iq_on, KG_ERR_STATE, "kg_rxbank_lorc_start: receiver %d has the IQ display running; the tap holds one callback", rx);
+    KG_TRY(kg_lorc_start(b->lo, rx));
+    b->rcv[rx].lo_on = 1;
+    return KG_OK;
+}
+
+int kg_rxbank_lorc_stop(kg_rxbank *b, int rx)
+{
+    BANK_LO("kg_rxbank_lorc_stop");
+    KG_TRY(kg_lorc_stop(b->lo, rx));
+    b->rcv[rx].lo_on = 0;
+    return KG_OK;
+}
+
+kg_lorc *kg_rxbank_lorc(kg_rxbank *b) { return b ? b->lo : nullptr; }
+
+int kg_rxbank_lorc_map(kg_rxbank *b, kg_lorc_row *row_map, int max_rows)
+{
+    KG_REQUIRE(b != nullptr && max_rows >= 0, KG_ERR_INVALID, "kg_rxbank_lorc_map: bad argument");
+    KG_REQUIRE(!row_map || max_rows >= b->lo_n, KG_ERR_INVALID, "kg_rxbank_lorc_map: %d rows, room for %d", b->lo_n, max_rows);
+    if (row_map && b->lo_n) memcpy(row_map, b->lo_rows.data(), sizeof(kg_lorc_row) * (size_t) b->lo_n);
+    return b->lo_n;
+}
+
+int kg_rxbank_lorc_rows(kg_rxbank *b, uint8_t **d_rows, size_t *cap)
+{
+    KG_REQUIRE(b && d_rows && cap, KG_ERR_INVALID, "kg_rxbank_lorc_rows: null argument");
+    *d_rows = b->d_lorows; *cap = b->lo_cap;                      // null until the extension was named
+    return KG_OK;
+}
+
 int kg_rxbank_set_wf(kg_rxbank *b, int rx, uint64_t phase_inc, int decim, int overlapped)
 {
     KG_TRY(bank_rx_check(b, rx, "kg_rxbank_set_wf"));
@@ -1103,6 +1207,7 @@ int kg_rxbank_leave(kg_rxbank *b, int rx)
     if (b->fx) KG_TRY(kg_fftext_restart(b->fx, rx));
     b->rcv[rx].iq_on = 0;                                  // iq_display_close: the object goes with the connection
     if (b->iq) KG_TRY(kg_iqd_init(b->iq, rx));
+    KG_TRY(bank_lo_fresh(b, rx));
     return KG_OK;
 }
 
@@ -1132,6 +1237,7 @@ int kg_rxbank_join(kg_rxbank *b, int rx)
     if (b->fx) KG_TRY(kg_fftext_restart(b->fx, rx));
     r.iq_on = 0;                                           // the IQ display's object is the connection's: a fresh one, not registered
     if (b->iq) KG_TRY(kg_iqd_init(b->iq, rx));
+    KG_TRY(bank_lo_fresh(b, rx));
     r.nbc = bank_nb_cmd{};                                 // memset(snd_t) / memset(wf_inst_t): algo NB_OFF, enables and params 0;
     KG_TRY(kg_wf_set_nb(b->wf, rx, 0));                    // the blankers' states stay (the reference's CNoiseProc arrays are globals)
     r.active = 1;

@@ -315,6 +315,53 @@ class RxBank:
             self.ctx.download(int(d.value), st)
         return st, rx_of[:n], blk[:n], sent[:n]
 
+    # ---- the Loran-C extension (extensions/Loran_C/loran_c.cpp): kg_lorc's commands per receiver
+    def lorc_init(self, rx, srate, i_srate):
+        check(self.lib.kg_rxbank_lorc_init(self.h, int(rx), float(srate), int(i_srate)), "kg_rxbank_lorc_init")
+
+    def lorc_set_gri(self, rx, ch, gri):
+        check(self.lib.kg_rxbank_lorc_set_gri(self.h, int(rx), int(ch), int(gri)), "kg_rxbank_lorc_set_gri")
+
+    def lorc_set_offset(self, rx, ch, offset):
+        check(self.lib.kg_rxbank_lorc_set_offset(self.h, int(rx), int(ch), int(offset)), "kg_rxbank_lorc_set_offset")
+
+    def lorc_set_gain(self, rx, ch, gain):
+        check(self.lib.kg_rxbank_lorc_set_gain(self.h, int(rx), int(ch), int(gain)), "kg_rxbank_lorc_set_gain")
+
+    def lorc_set_avg_algo(self, rx, ch, avg_algo):
+        check(self.lib.kg_rxbank_lorc_set_avg_algo(self.h, int(rx), int(ch), int(avg_algo)), "kg_rxbank_lorc_set_avg_algo")
+
+    def lorc_set_avg_param(self, rx, ch, avg_param):
+        check(self.lib.kg_rxbank_lorc_set_avg_param(self.h, int(rx), int(ch), float(avg_param)), "kg_rxbank_lorc_set_avg_param")
+
+    def lorc_start(self, rx):
+        check(self.lib.kg_rxbank_lorc_start(self.h, int(rx)), "kg_rxbank_lorc_start")
+
+    def lorc_stop(self, rx):
+        check(self.lib.kg_rxbank_lorc_stop(self.h, int(rx)), "kg_rxbank_lorc_stop")
+
+    @property
+    def lorc(self):
+        """the bank's LoranC (None until one of the lorc_* commands was sent): state()"""
+        from . import lorc as lo_mod
+        h = self.lib.kg_rxbank_lorc(self.h)
+        return borrow(lo_mod.LoranC, self.ctx, h, nconn=self.nrx) if h else None
+
+    def lorc_rows(self):
+        """-> (row map [rows] of lorc.row_dtype -- conn the receiver, blk the sound block of the step --, the rows' bytes uint8 from the
+        buffer's start to the last row's end) of the last step (after sync())"""
+        from . import lorc as lo_mod
+        n = check(self.lib.kg_rxbank_lorc_map(self.h, None, 0), "kg_rxbank_lorc_map")
+        m = np.zeros(max(n, 1), lo_mod.row_dtype)
+        check(self.lib.kg_rxbank_lorc_map(self.h, ptr(m), int(m.size)), "kg_rxbank_lorc_map")
+        m = m[:n]
+        d, cap = C.c_void_p(), C.c_size_t()
+        check(self.lib.kg_rxbank_lorc_rows(self.h, C.byref(d), C.byref(cap)), "kg_rxbank_lorc_rows")
+        out = np.zeros(int(m["off"][-1] + m["len"][-1]) if n else 0, np.uint8)
+        if out.size:
+            self.ctx.download(int(d.value), out)
+        return m, out
+
     def fftext_set_rate(self, sample_rate):
         """what ext_update_get_sample_rateHz answers for the FFT extension (extensions/FFT/FFT.cpp:79)"""
         check(self.lib.kg_rxbank_fftext_set_rate(self.h, float(sample_rate)), "kg_rxbank_fftext_set_rate")

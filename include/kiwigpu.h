@@ -1316,6 +1316,87 @@ int kg_iqd_state(kg_iqd *q, int ch, kg_iqd_info *info, float *iq, uint8_t *plot,
  * aligned arrays of n floats.  Enqueue only. */
 int kg_iqd_math_dev(kg_ctx *ctx, int fn, const float *d_a, const float *d_b, size_t n, float *d_out);
 
+/* The Loran-C extension (extensions/Loran_C/loran_c.cpp), the second consumer of receive_iq_samps(PRE_AGC): the CFastFIR output of
+ * every sound block (none while the receiver is in NBFM).  The power of every sample is folded into time buckets that cover one Group
+ * Repetition Interval (GRI) of a Loran-C chain -- bucket bn = floor(fmod(samp - offset, samp_per_GRI)) --, for two chains (Loran
+ * channels 0 and 1) at once, each under one of three averaging rules (CMA with a time-out, EMA, IIR); whenever a channel comes to
+ * bucket 0 with more than i_srate samples behind its last row, its averages go out as a row of nbucket + 1 bytes, the "scope".
+ * Every byte and every float is an exact function of the samples: csrc/kg_lorc.h is the one definition for device and host, in the
+ * reference's operand types, and the device's expf is the host libm's bit for bit.  Samples are finite with |re|, |im| <= 3e4.
+ * The schedule (buckets, rows, clears, navgs) depends on no sample: it runs on the host, and nothing here synchronises but the calls
+ * that say so.  Commands take effect between calls, in call order.  What the reference does not define is refused with
+ * KG_ERR_INVALID, nothing changed: a Loran channel outside 0 .. 1; a gri outside 1 .. 9999; a gri whose nbucket -- floor(srate * gri /
+ * 1e5) + 1, halved with samp_per_GRI when above 1199 -- is 1199 or more (the reference then writes one past its scope[] array: GRI
+ * 9990 at 12 kHz); an offset before the channel has a GRI; an avg_algo outside 0 .. 2; and, at the push, a started connection one of
+ * whose channels has no GRI, is under EMA with lround(avg_param) < 1 or under IIR with a negative or non-finite avg_param.  Every
+ * other call on a connection needs kg_lorc_init first (KG_ERR_STATE). */
+typedef struct kg_lorc kg_lorc;
+enum { KG_LORC_CMA = 0, KG_LORC_EMA = 1, KG_LORC_IIR = 2 };                /* AVG_CMA, AVG_EMA, AVG_IIR, loran_c.cpp:58-60 */
+enum { KG_LORC_SCOPE_DATA = 0, KG_LORC_SCOPE_RESET = 1 };                  /* loran_c.cpp:17-18 */
+#define KG_LORC_MAX_GRI 9999                               /* loran_c.cpp:23 */
+#define KG_LORC_MAX_BUCKET 1199                            /* loran_c.cpp:24 */
+#define KG_LORC_MAX_NS 512
+typedef struct kg_lorc_row {               /* one ext_send_msg_data of :119-120 */
+    int32_t conn, blk, samp, ch;           /* connection, block of its entry, sample of the block the row went out AHEAD of, Loran channel */
+    int32_t cmd, len;                      /* KG_LORC_SCOPE_RESET for the first row behind a `SET gri` or `SET start`, else _DATA; nbucket + 1 */
+    int64_t off;                           /* from the rows' first byte; a multiple of 16 */
+} kg_lorc_row;
+typedef struct kg_lorc_chan {              /* loran_c_ch_t, :29-39, without avg[] */
+    uint32_t gri, samp, nbucket, dsp_samps, avg_samps, navgs;
+    double samp_per_GRI;
+    float gain, max;
+    int32_t offset, avg_algo;
+    double avg_param_f;
+    int32_t avg_param_i, restart;
+} kg_lorc_chan;
+typedef struct kg_lorc_info {              /* loran_c_t, :41-52 */
+    int32_t inited, started;
+    uint32_t i_srate;
+    int32_t redraw_legend;
+    double srate;
+    kg_lorc_chan ch[2];
+} kg_lorc_info;
+/* nconn (1 .. 1024) objects of loran_c[] (:54), 9.4 KiB of device memory each (avg[2][1199], max) */
+int kg_lorc_create(kg_ctx *ctx, int nconn, kg_lorc **out);
+/* the object with its connections (the extension's close; loran_c.cpp:54 is static) */
+void kg_lorc_destroy(kg_lorc *q);
+/* `SET ext_server_init` (:218-228): the memset; srate is what ext_update_get_sample_rateHz answers (1 .. 1e9), i_srate is snd_rate
+ * (>= 0).  Whether the connection is started stays: the registration is not part of the struct. */
+int kg_lorc_init(kg_lorc *q, int conn, double srate, int i_srate);
+/* `SET gri%d=%d` (:230-240) with init_gri (:198-208): samp_per_GRI, nbucket, the halving; redraw_legend and restart set */
+int kg_lorc_set_gri(kg_lorc *q, int conn, int ch, int gri);
+/* `SET offset%d=%d` (:242-250): (offset + delta) % nbucket with the int sum converted to unsigned first -- not the residue of a
+ * negative sum; restart set */
+int kg_lorc_set_offset(kg_lorc *q, int conn, int ch, int offset);
+/* `SET gain%d=%d` (:252-260): (float) pow(10.0, ((float) -gain) / 10.0), 0 for auto; restart set */
+int kg_lorc_set_gain(kg_lorc *q, int conn, int ch, int gain);
+/* `SET avg_algo%d=%d` (:262-269): KG_LORC_CMA / _EMA / _IIR; restart set */
+int kg_lorc_set_avg_algo(kg_lorc *q, int conn, int ch, int avg_algo);
+/* `SET avg_param%d=%lf` (:271-280): avg_param_f and avg_param_i = lround(avg_param); restart set */
+int kg_lorc_set_avg_param(kg_lorc *q, int conn, int ch, double avg_param);
+/* `SET start` (:282-292): redraw_legend and both restarts set, loran_c_data registered */
+int kg_lorc_start(kg_lorc *q, int conn);
+/* `SET stop` (:294-302): unregistered; the state is kept, as the reference keeps it */
+int kg_lorc_stop(kg_lorc *q, int conn);
+/* loran_c_data (:65-196) for nblk[i] blocks (0 .. 256) of ns samples (1 .. 512) of connection conns[i] (each at most once), on HOST
+ * arrays: block b of entry i is the ns complex floats at iq + 2 * (i*iq_stride + ns*b) (iq_stride in complex samples).  A connection
+ * that is not started takes nothing (its callback is not registered).  Rows go to rows + row_map[r].off in the reference's send order
+ * -- per connection in list order, sample-major, channel 0 ahead of channel 1 on the same sample --, each at the next multiple of 16;
+ * the bytes between them stay as they are.  *nrows: how many.  ONE kernel launch.  Refused with nothing changed and nothing enqueued:
+ * an argument out of range, more row bytes than rows_cap, more rows than max_rows, and the pushes named above.  Synchronises. */
+int kg_lorc_process(kg_lorc *q, const int32_t *conns, int nconn, const int32_t *nblk, int ns, const float *iq, size_t iq_stride,
+                    uint8_t *rows, size_t rows_cap, kg_lorc_row *row_map, int max_rows, int32_t *nrows);
+/* The schedule of that push (:85-88, :121-146: buckets, rows, clears -- no sample enters it), walked on copies: how many runs it has
+ * (maximal stretches of samples over which the bucket rises by one a sample; the kernel's table holds one entry each), how many rows
+ * it sends and the bytes from the rows' first byte to the last row's end -- what `rows` must hold.  Any of the three may be NULL.
+ * Changes nothing, enqueues nothing; refuses what the push refuses, but for the capacities. */
+int kg_lorc_plan(kg_lorc *q, const int32_t *conns, int nconn, const int32_t *nblk, int ns, int32_t *nruns, int32_t *nrows, size_t *row_bytes);
+/* Connection conn's whole state (loran_c_t, :29-52), for tests: every scalar of both channels and avg[2][1199] (may be NULL).
+ * Synchronises. */
+int kg_lorc_state(kg_lorc *q, int conn, kg_lorc_info *info, float *avg);
+/* the number of the `EXT ms_per_bin=` line (:223-225): float(1.0 / srate * 1e3), doubled in float when i_srate > 12000 */
+float kg_lorc_ms_per_bin(double srate, int i_srate);
+
 /* Diagnostics: re-runs the 4096-point stage of the forward FFT of `block` in a
  * stamped build of the kernel and returns 4 s_memrealtime readings (100 MHz):
  * start, inputs + twiddles loaded, transform done, results stored. */
@@ -1476,6 +1557,39 @@ kg_iqd *kg_rxbank_iqd(kg_rxbank *bank);
 int kg_rxbank_iqd_map(kg_rxbank *bank, kg_iqd_row *row_map, int max_rows);
 int kg_rxbank_iqd_rows(kg_rxbank *bank, uint8_t **d_rows, size_t *rows_cap);
 int kg_rxbank_iqd_status(kg_rxbank *bank, kg_iqd_status **d_status, int32_t *rx_of_blk, int32_t *blk_of_blk, int32_t *sent_of_blk);
+
+/* The Loran-C extension of the bank's receivers (kg_lorc above; extensions/Loran_C/loran_c.cpp).  The first of these calls makes the
+ * bank's kg_lorc object and its row buffer, grows the step's arena slots by the size of the extension's table and drains the bank's
+ * streams; a bank that was never told holds nothing for the extension and enqueues exactly what it enqueued without it.  While a
+ * receiver is started and not in KG_POST_NBFM in a step (receive_iq_pre_agc is NULL while isNBFM, rx_sound.cpp:492), the CFastFIR
+ * output of its sound blocks of that step feeds the extension in place: ONE launch per step over all such receivers, on the tail
+ * stream behind the filter.  kg_rxbank_join and kg_rxbank_leave give the receiver a fresh object, stopped.  The tap holds ONE callback
+ * (ext_users[rx].receive_iq_pre_agc): kg_rxbank_lorc_start on a receiver whose IQ display has run on, and kg_rxbank_iqd_set_run(.., 1,
+ * ..) on a receiver with Loran-C started, are refused (KG_ERR_STATE). */
+/* `SET ext_server_init` (:218-228) of receiver rx: kg_lorc_init */
+int kg_rxbank_lorc_init(kg_rxbank *bank, int rx, double srate, int i_srate);
+/* `SET gri%d=%d` (:230-240): kg_lorc_set_gri; a bank also refuses a GRI of fewer than 128 samples (it bounds a step's table by it) */
+int kg_rxbank_lorc_set_gri(kg_rxbank *bank, int rx, int ch, int gri);
+/* `SET offset%d=%d` (:242-250): kg_lorc_set_offset */
+int kg_rxbank_lorc_set_offset(kg_rxbank *bank, int rx, int ch, int offset);
+/* `SET gain%d=%d` (:252-260): kg_lorc_set_gain */
+int kg_rxbank_lorc_set_gain(kg_rxbank *bank, int rx, int ch, int gain);
+/* `SET avg_algo%d=%d` (:262-269): kg_lorc_set_avg_algo */
+int kg_rxbank_lorc_set_avg_algo(kg_rxbank *bank, int rx, int ch, int avg_algo);
+/* `SET avg_param%d=%lf` (:271-280): kg_lorc_set_avg_param */
+int kg_rxbank_lorc_set_avg_param(kg_rxbank *bank, int rx, int ch, double avg_param);
+/* `SET start` (:282-292): kg_lorc_start.  A step with a started receiver whose push kg_lorc refuses (a channel without a GRI, EMA
+ * below 1, IIR negative or non-finite) is refused as a whole, nothing enqueued. */
+int kg_rxbank_lorc_start(kg_rxbank *bank, int rx);
+/* `SET stop` (:294-302): kg_lorc_stop */
+int kg_rxbank_lorc_stop(kg_rxbank *bank, int rx);
+/* the object (NULL until one of the calls above), for kg_lorc_state (:29-52) */
+kg_lorc *kg_rxbank_lorc(kg_rxbank *bank);
+/* the rows of the last step (ext_send_msg_data, :119-120; kg_lorc_row: conn the receiver, blk the sound block of the step, off from
+ * d_rows); row_map may be NULL.  Returns the number of rows. */
+int kg_rxbank_lorc_map(kg_rxbank *bank, kg_lorc_row *row_map, int max_rows);
+/* the device buffer of the step's rows (e->scope, :50) and its size (NULL until the extension was named; read behind kg_rxbank_sync) */
+int kg_rxbank_lorc_rows(kg_rxbank *bank, uint8_t **d_rows, size_t *cap);
 /* CmdSetWFFreq + CmdSetWFDecim + the sampler mode sample_wf() decides on (rx/rx_waterfall.cpp:962-1008):
  *   overlapped == 0   CmdWFReset + the one-shot sampler every step: the non-overlapped frame (:1005-1041); needs
  *                     8192 * decim <= adc_samples_per_step
