@@ -233,12 +233,14 @@ def run_limiter_exe(exe, clocks, tmpdir):
 
 
 # ---- a script on the device object
-def run_script_dev(fx, ctx, lines, spec, cuts=None, row_stride=W, fill=0xAA):
-    """Runs a script on channel 0 of fx (a FftExt): consecutive B lines are ONE kg_fftext_process_dev call of one entry per line, cut
-    where a command stands between them and after the block counts in `cuts` (block numbers of the script).  -> the keys of parse(),
+def run_script_dev(fx, ctx, lines, spec, cuts=None, row_stride=W, fill=0xAA, merge=False):
+    """Runs a script on channel 0 of fx (a FftExt): consecutive B lines are ONE kg_fftext_process_dev call of one entry per line -- or
+    with `merge` one entry per run of lines of one instance --, cut where a command stands between them and after the block counts in
+    `cuts` (block numbers of the script).  -> the keys of parse(),
     plus "calls", and "pad": whether every byte of the row buffer outside the rows still holds `fill`."""
     nb = nblocks(lines)
-    d_spec, d_rows = ctx.alloc(max(nb, 1) * W * 8), ctx.alloc(max(nb, 1) * row_stride)      # a call gathers its blocks: at most all of them
+    d_rows = ctx.alloc(max(nb, 1) * row_stride)
+    d_spec = [0, 0]                                  # a call gathers its blocks: the buffer and its bytes, grown to the largest call
     host_rows = np.full((max(nb, 1), row_stride), fill, np.uint8)
     sent, bins, calls, at, seen = np.zeros(nb, np.int32), [], 0, 0, 0
     cuts = set(cuts or ())
@@ -248,16 +250,29 @@ def run_script_dev(fx, ctx, lines, spec, cuts=None, row_stride=W, fill=0xAA):
         nonlocal at, calls
         if not pend:
             return
-        inst = np.array([p[0] for p in pend], np.int32)
-        # one entry per block: entry i reads the spectrum at i * spec_stride, so the blocks are gathered per call
-        blocks = np.ascontiguousarray(spec[[p[1] for p in pend]])
-        ctx.upload(d_spec, blocks)
-        m = fx.process_dev([0] * len(pend), [1] * len(pend), inst, d_spec, W, d_rows + at * row_stride, row_stride, len(pend))
+        ents = []                                    # [instance, [positions in pend]]
+        for i, p in enumerate(pend):
+            if merge and ents and ents[-1][0] == p[0]:
+                ents[-1][1].append(i)
+            else:
+                ents.append([p[0], [i]])
+        # entry i reads its spectra from i * spec_stride on, so the blocks are gathered per call (one entry per block: back to back)
+        most = max(len(e[1]) for e in ents)
+        blocks = np.zeros((len(ents), most, W), np.complex64)
+        for i, e in enumerate(ents):
+            blocks[i, :len(e[1])] = spec[[pend[j][1] for j in e[1]]]
+        if blocks.nbytes > d_spec[1]:                # (the call before has drained: every call ends in a sync)
+            if d_spec[0]:
+                ctx.free(d_spec[0])
+            d_spec[0], d_spec[1] = 0, 0
+            d_spec[0], d_spec[1] = ctx.alloc(blocks.nbytes), blocks.nbytes
+        ctx.upload(d_spec[0], blocks)
+        m = fx.process_dev([0] * len(ents), [len(e[1]) for e in ents], [e[0] for e in ents], d_spec[0], most * W, d_rows + at * row_stride, row_stride, len(pend))
         ctx.sync()                                   # the next call's upload reuses d_spec
         for ch, ent, blk, b in m:
-            assert ch == 0 and blk == 0
+            assert ch == 0 and (merge or blk == 0)
             bins.append(int(b))
-            sent[pend[ent][2]] = 1
+            sent[pend[ents[ent][1][blk]][2]] = 1
         at += m.shape[0]
         calls += 1
         pend.clear()
@@ -287,7 +302,8 @@ def run_script_dev(fx, ctx, lines, spec, cuts=None, row_stride=W, fill=0xAA):
         ctx.sync()
         ctx.download(d_rows, host_rows)
     finally:
-        ctx.free(d_spec)
+        if d_spec[0]:
+            ctx.free(d_spec[0])
         ctx.free(d_rows)
     info, ncma, pwr = fx.state(0, sums=True)
     n = len(bins)

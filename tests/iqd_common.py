@@ -284,7 +284,7 @@ def run_script_dev(q, ctx, lines, samples, ch=0, cuts=None, merge=False):
         host = np.zeros((len(ents), stride), np.complex64)
         for i, e in enumerate(ents):
             host[i, :ns * len(e[1])] = np.concatenate([samples[o:o + ns] for o in e[2]])
-        cap = (ns * len(pend) + RING) * 4
+        cap = (ns * len(pend) + 2 * RING) * 4       # a row's samples, and a first row of each instance behind a change of points
         d_iq, d_rows, d_st = ctx.alloc(host.nbytes), ctx.alloc(cap), ctx.alloc(24 * len(pend))
         try:
             ctx.upload(d_iq, host)

@@ -207,3 +207,39 @@ def test_fftext_symbols_declared_bound_and_exported():
     src = open(os.path.join(ROOT, "flydog_sdr_gps_amd", "csrc", "kg_fftext.h")).read()
     for lit in ("WIDTH = 1024", "MAX_BINS = 200", "UPDATE_MS = 100", "FUNC_OFF = -1, FUNC_WF = 0, FUNC_SPEC = 1, FUNC_INTEG = 2"):
         assert lit in src, lit
+
+
+# ---- seeded random scripts (tests/ext_random.py): the combinations of commands and blocks nobody wrote down
+@pytest.fixture(scope="module")
+def random_ref():
+    from . import ext_random as er
+    return er.load("fftext")
+
+
+def test_random_scripts_host_model_equals_the_fixture(random_ref, pool, driver, tmp_path):
+    """every seed's script is the one the reference was fed, the host model takes it (exit status 0) and equals the reference in every
+    field the fixture keeps: which blocks sent a row and its bin, the end state's scalars and ncma, and the digests of the rows and of
+    the 200 x 1024 sums"""
+    from . import ext_random as er
+    for seed in range(er.NSEED):
+        lines = er.fftext_script(seed)
+        er.check_record("fftext", seed, lines, fc.run_script_exe(driver, lines, pool[1], tmp_path), er.unpack(random_ref, seed))
+
+
+def test_random_fixture_meets_its_conditions(random_ref):
+    """conditions, not measurements: what the 40 seeds must reach between them (ext_random.FFTEXT_CONDITIONS), computed from the fixture
+    and the regenerated scripts; none of the 40 was refused by the reference.  The walk also holds its own answer of which blocks send
+    a row to the reference's.  "block dropped past bin 199" is a block for which the reference sent nothing because its bin was 200 or
+    above: the long integrations of the generator reach it"""
+    from . import ext_random as er
+    er.check_conditions("fftext", random_ref)
+    assert os.path.getsize(er.fixture_path("fftext")) <= 64 * 1024
+
+
+@pytest.mark.parametrize("resident", [False, True], ids=["host_arrays", "device_resident"])
+def test_random_side_by_side_plans_share_their_calls(resident):
+    """the calls tests/test_fftext_gpu.py makes with the seeds three at a time on one object are decided ahead of the run
+    (ext_random_dev.plan_side_by_side): over all the groups at least half of them carry more than one channel"""
+    from . import ext_random_dev as ed
+    every, both = ed.shared_in_all("fftext", resident)
+    assert 2 * both >= every, (both, every)

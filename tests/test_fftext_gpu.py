@@ -237,3 +237,78 @@ def test_host_array_twin(gpu_ctx, golden, pool):
         assert np.array_equal(rows, golden["s_wf_rows"][:5]) and m.tolist() == [[0, 0, b, 0] for b in range(5)]
     finally:
         fx.close()
+
+
+# ---- seeded random scripts (tests/ext_random.py) under random call partitions: the device against the host model, in full
+PARTS = 4                                                                  # the 40 seeds, ten a test
+
+
+@pytest.fixture(scope="module")
+def random_ref():
+    from . import ext_random as er, ext_random_dev as ed
+    return er.load("fftext")
+
+
+@pytest.fixture(scope="module")
+def random_host(driver, pool, tmp_path_factory):
+    """the host driver's result of every seed: made once, shared, left unchanged"""
+    from . import ext_random as er, ext_random_dev as ed
+    tmp = tmp_path_factory.mktemp("fftext_random")
+    return [fc.run_script_exe(driver, er.fftext_script(seed), pool[1], tmp) for seed in range(er.NSEED)]
+
+
+@pytest.mark.parametrize("part", range(PARTS))
+def test_random_scripts_under_a_random_partition(gpu_ctx, random_ref, random_host, pool, part):
+    """every seed's script cut into calls by a generator of its own (cuts, entries merged or not), and again a call a block: both equal
+    the host model in every row byte, bin, taken / ignored / dropped block and the whole end state with all 200 x 1024 sums, hence
+    each other, and the fixture's digests"""
+    from . import ext_random as er, ext_random_dev as ed
+    for seed in range(part * er.NSEED // PARTS, (part + 1) * er.NSEED // PARTS):
+        lines = er.fftext_script(seed)
+        nb = fc.nblocks(lines)
+        cuts, merge = ed.partition("fftext", seed, nb)
+        fx = fftext.FftExt(gpu_ctx, nchan=1)
+        try:
+            got = fc.run_script_dev(fx, gpu_ctx, lines, pool[1], cuts=cuts, merge=merge, row_stride=fc.W + PAD)
+            fx.restart(0)                                                  # a new connection: also zeroes the sums of the run before
+            each = fc.run_script_dev(fx, gpu_ctx, lines, pool[1], cuts=set(range(1, nb)))
+        finally:
+            fx.close()
+        ed.fftext_same(got, random_host[seed], "seed %d" % seed, "cuts %s, merge %s" % (sorted(cuts), merge))
+        ed.fftext_same(each, random_host[seed], "seed %d" % seed, "a call a block")
+        assert got["pad"] and each["pad"] and each["calls"] >= got["calls"]
+        er.check_record("fftext", seed, lines, got, er.unpack(random_ref, seed))
+
+
+def _side_by_side(gpu_ctx, random_ref, random_host, pool, group, resident):
+    from . import ext_random as er, ext_random_dev as ed
+    seeds, scripts, steps, rng = ed.planned("fftext", group, resident)
+    chans = [2, 0, 1]                                                      # not in channel order
+    fx = fftext.FftExt(gpu_ctx, nchan=3)
+    try:
+        got, calls, shared = ed.fftext_run_plan(fx, gpu_ctx, steps, chans, scripts, pool[1], resident=resident, rng=rng)
+    finally:
+        fx.close()
+    for seed, lines, g in zip(seeds, scripts, got):
+        ed.fftext_same(g, random_host[seed], "seed %d of %s" % (seed, seeds), "channel %d" % chans[seeds.index(seed)])
+        er.check_record("fftext", seed, lines, g, er.unpack(random_ref, seed))
+    # the calls were the plan's: tests/test_fftext_cpu.py::test_random_side_by_side_plans_share_their_calls holds the plans to their share
+    assert (calls, shared) == ed.calls_of(steps)[:2] and shared >= 1
+
+
+@pytest.mark.parametrize("group", range(14))
+def test_random_scripts_side_by_side(gpu_ctx, random_ref, random_host, pool, group):
+    """the seeds three at a time on three channels of one object, out of order: every call carries every channel whose script stands at
+    the round's sample rate (the object's, taken up at a channel's reset), a random number of blocks each, their entries shuffled into
+    each other; the commands go between the calls.  Each channel equals the host model of its own script in full, and the fixture"""
+    _side_by_side(gpu_ctx, random_ref, random_host, pool, group, False)
+
+
+@pytest.mark.parametrize("group", range(14))
+def test_random_scripts_from_device_resident_input(gpu_ctx, random_ref, random_host, pool, group):
+    """the same from ONE device buffer that holds every call's spectra, uploaded ahead of the first call: an entry's spectra stand at a
+    stride larger than its blocks and -- entries of no block between them -- not at the row of its position among the entries that
+    have some; the buffer is NaN outside the blocks.  A gap: the row list itself (spec_row of kg_fftext_process_rows_) is the bank's,
+    not part of the ABI, so here every entry still reads row i of its list, and the spec_row[i] branch of the host walk stays with
+    tests/test_fftext_bank_gpu.py"""
+    _side_by_side(gpu_ctx, random_ref, random_host, pool, group, True)

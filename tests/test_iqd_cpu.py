@@ -180,3 +180,37 @@ def test_iqd_symbols_declared_bound_and_exported():
         assert lit in src, lit
     sizes = {"kg_iqd_status": iqd.status_dtype.itemsize, "kg_iqd_row": iqd.row_dtype.itemsize, "kg_iqd_info": iqd.info_dtype.itemsize}
     assert sizes == {"kg_iqd_status": 24, "kg_iqd_row": 32, "kg_iqd_info": 164}
+
+
+# ---- seeded random scripts (tests/ext_random.py): the combinations of commands and blocks nobody wrote down
+@pytest.fixture(scope="module")
+def random_ref():
+    from . import ext_random as er
+    return er.load("iqd")
+
+
+def test_random_scripts_host_model_equals_the_fixture(random_ref, pool, driver, tmp_path):
+    """every seed's script is the one the reference was fed, the host model takes it (exit status 0) and equals the reference in every
+    field the fixture keeps: rows per block, cmd, len, sent, the end state's scalars, and the digests of the row stream, the status
+    records, _iq, _plot and _map"""
+    from . import ext_random as er
+    for seed in range(er.NSEED):
+        lines = er.iqd_script(seed)
+        er.check_record("iqd", seed, lines, ic.run_script_exe(driver, lines, pool, tmp_path), er.unpack(random_ref, seed))
+
+
+def test_random_fixture_meets_its_conditions(random_ref):
+    """conditions, not measurements: what the 40 seeds must reach between them (ext_random.IQD_CONDITIONS, 5000 rows), computed from the
+    fixture and the regenerated scripts; none of the 40 was refused by the reference"""
+    from . import ext_random as er
+    er.check_conditions("iqd", random_ref)
+    assert os.path.getsize(er.fixture_path("iqd")) <= 64 * 1024
+
+
+@pytest.mark.parametrize("resident", [False, True], ids=["host_arrays", "device_resident"])
+def test_random_side_by_side_plans_share_their_calls(resident):
+    """the calls tests/test_iqd_gpu.py makes with the seeds three at a time on one object are decided ahead of the run
+    (ext_random_dev.plan_side_by_side): over all the groups at least half of them carry more than one channel"""
+    from . import ext_random_dev as ed
+    every, both = ed.shared_in_all("iqd", resident)
+    assert 2 * both >= every, (both, every)

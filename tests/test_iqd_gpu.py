@@ -295,3 +295,78 @@ def test_device_hypotf_and_fmodf_equal_the_hosts(gpu_ctx, fn):
     assert bad.size == 0, (bad.size, a[bad[:4]], b[bad[:4]], got[bad[:4]], want[bad[:4]])
     assert nan.sum() > 1000 and (np.abs(want[~nan]) < 1.2e-38).sum() > 1000                  # NaN results and subnormal ones were reached
     assert fn == iqd.HYPOTF or (want[~nan] == 0).sum() > 100000                                 # equal operands: a signed zero
+
+
+# ---- seeded random scripts (tests/ext_random.py) under random call partitions: the device against the host model, in full
+PARTS = 4                                                                  # the 40 seeds, ten a test
+
+
+@pytest.fixture(scope="module")
+def random_ref():
+    from . import ext_random as er, ext_random_dev as ed
+    return er.load("iqd")
+
+
+@pytest.fixture(scope="module")
+def random_host(driver, pool, tmp_path_factory):
+    """the host driver's result of every seed: made once, shared, left unchanged"""
+    from . import ext_random as er, ext_random_dev as ed
+    tmp = tmp_path_factory.mktemp("iqd_random")
+    return [ic.run_script_exe(driver, er.iqd_script(seed), pool, tmp) for seed in range(er.NSEED)]
+
+
+@pytest.mark.parametrize("part", range(PARTS))
+def test_random_scripts_under_a_random_partition(gpu_ctx, random_ref, random_host, pool, part):
+    """every seed's script cut into calls by a generator of its own (cuts, entries merged or not), and again a call a block: both equal
+    the host model in every row byte, map and status field and the whole end state, hence each other, and the fixture's digests"""
+    from . import ext_random as er, ext_random_dev as ed
+    q = iqd.IqDisplay(gpu_ctx, nchan=1)
+    try:
+        for seed in range(part * er.NSEED // PARTS, (part + 1) * er.NSEED // PARTS):
+            lines = er.iqd_script(seed)
+            nb = ic.nblocks(lines)
+            cuts, merge = ed.partition("iqd", seed, nb)
+            got = ic.run_script_dev(q, gpu_ctx, lines, pool, cuts=cuts, merge=merge)
+            each = ic.run_script_dev(q, gpu_ctx, lines, pool, cuts=set(range(1, nb)))
+            ed.iqd_same(got, random_host[seed], "seed %d" % seed, "cuts %s, merge %s" % (sorted(cuts), merge))
+            ed.iqd_same(each, random_host[seed], "seed %d" % seed, "a call a block")
+            assert np.array_equal(got["samp"], samp_of_rows(lines)) and np.array_equal(each["samp"], got["samp"]), (seed, "the row map's sample index")
+            assert ic.stream(got) == ic.stream(each) and each["calls"] >= got["calls"]
+            er.check_record("iqd", seed, lines, got, er.unpack(random_ref, seed))
+    finally:
+        q.close()
+
+
+def _side_by_side(gpu_ctx, random_ref, random_host, pool, group, resident):
+    from . import ext_random as er, ext_random_dev as ed
+    seeds, scripts, steps, rng = ed.planned("iqd", group, resident)
+    chans = [2, 0, 1]                                                      # not in channel order
+    q = iqd.IqDisplay(gpu_ctx, nchan=3)
+    try:
+        got, calls, shared = ed.iqd_run_plan(q, gpu_ctx, steps, chans, scripts, pool, resident=resident, rng=rng)
+    finally:
+        q.close()
+    for seed, lines, g in zip(seeds, scripts, got):
+        ed.iqd_same(g, random_host[seed], "seed %d of %s" % (seed, seeds), "channel %d" % chans[seeds.index(seed)])
+        assert np.array_equal(g["samp"], samp_of_rows(lines)), (seed, "the row map's sample index")
+        er.check_record("iqd", seed, lines, g, er.unpack(random_ref, seed))
+    # the calls were the plan's: tests/test_iqd_cpu.py::test_random_side_by_side_plans_share_their_calls holds the plans to their share
+    assert (calls, shared) == ed.calls_of(steps)[:2]
+
+
+@pytest.mark.parametrize("group", range(14))
+def test_random_scripts_side_by_side(gpu_ctx, random_ref, random_host, pool, group):
+    """the seeds three at a time on three channels of one object, out of order: every call carries every channel whose next blocks
+    share the round's ns, a random number of blocks each, their entries shuffled into each other; the commands go between the calls.
+    Each channel equals the host model of its own script in full, and the fixture"""
+    _side_by_side(gpu_ctx, random_ref, random_host, pool, group, False)
+
+
+@pytest.mark.parametrize("group", range(14))
+def test_random_scripts_from_device_resident_input(gpu_ctx, random_ref, random_host, pool, group):
+    """the same from ONE device buffer that holds every call's samples, uploaded ahead of the first call: an entry's samples stand at a
+    stride larger than its blocks and -- entries of no block between them -- not at the row of its position among the entries that
+    have some; the buffer is NaN outside the blocks; no copy to or from the device stands between two calls.  A gap: the row list
+    itself (iq_row of kg_iqd_process_rows_) is the bank's, not part of the ABI, so here every entry still reads row i of its list, and
+    the iq_row[i] branch of the host walk stays with tests/test_iqd_bank_gpu.py"""
+    _side_by_side(gpu_ctx, random_ref, random_host, pool, group, True)

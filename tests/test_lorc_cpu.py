@@ -261,3 +261,31 @@ def test_lorc_symbols_declared_bound_and_exported():
     src = open(os.path.join(ROOT, "flydog_sdr_gps_amd", "csrc", "kg_lorc.h")).read()
     assert "NCH = 2, MAX_GRI = 9999, MAX_BUCKET = 1199, HALF_THRESHOLD = 12000, MAX_NS = 512" in src
     assert (lorc.row_dtype.itemsize, lorc.info_dtype.itemsize) == (32, 152)
+
+
+# ---- seeded random scripts (tests/ext_random.py): the combinations of commands and blocks nobody wrote down
+@pytest.fixture(scope="module")
+def random_ref():
+    from . import ext_random as er
+    return er.load("lorc")
+
+
+@pytest.mark.parametrize("by_runs", [False, True], ids=["per_sample", "by_runs"])
+def test_random_scripts_host_model_equals_the_fixture(random_ref, pool, driver, tmp_path, by_runs):
+    """every seed's script is the one the reference was fed, the host model takes it (exit status 0) and equals the reference in every
+    field the fixture keeps: rows per block, sample, channel, command and length of every row, the scalars of the end state bit for
+    bit, and the digests of the row bytes and of avg[2][1199]"""
+    from . import ext_random as er
+    for seed in range(er.NSEED):
+        lines = er.lorc_script(seed)
+        er.check_record("lorc", seed, lines, lc.run_script_exe(driver, lines, pool, tmp_path, by_runs=by_runs), er.unpack(random_ref, seed))
+
+
+def test_random_fixture_meets_its_conditions(random_ref):
+    """conditions, not measurements: what the 40 seeds must reach between them (ext_random.LORC_CONDITIONS, 300 rows), computed from the
+    fixture and the regenerated scripts; none of the 40 was refused by the reference.  SCOPE_RESET is sent behind `SET gri` and `SET
+    start` alone (loran_c.cpp:119-121; the walk asserts it of every row), so what no command causes is the CMA's reset by time-out
+    (:126): that is the condition"""
+    from . import ext_random as er
+    er.check_conditions("lorc", random_ref)
+    assert os.path.getsize(er.fixture_path("lorc")) <= 64 * 1024

@@ -38,14 +38,16 @@ def _items(lines):
     return out
 
 
-def run_side_by_side(q, scripts, samples, most=8):
+def run_side_by_side(q, scripts, samples, most=8, rng=None):
     """scripts[c] on connection c of q, in lockstep: every round each connection takes its commands up to its next block, then ONE call
     feeds every connection whose next blocks have the round's ns -- up to `most` consecutive blocks each, so the entries differ in
-    length.  -> per connection the keys of lorc_common.parse(), and the number of calls with more than one connection"""
+    length.  With rng (a numpy Generator) the round's ns is the one most connections wait with, each takes a random number of blocks up
+    to `most`, and a connection alone in its call all its consecutive blocks (256 at most): the calls are spent where they are shared.
+    -> per connection the keys of lorc_common.parse(), the number of calls with more than one connection, and with rng the calls"""
     items = [_items(s) for s in scripts]
     at = [0] * len(items)
     rec = [lc.Recorder(lc.nblocks(s)) for s in scripts]
-    shared = 0
+    shared = calls = 0
     while any(a < len(it) for a, it in zip(at, items)):
         for c, it in enumerate(items):
             while at[c] < len(it) and it[at[c]][0] == "cmd":
@@ -54,14 +56,15 @@ def run_side_by_side(q, scripts, samples, most=8):
         ready = [c for c, it in enumerate(items) if at[c] < len(it)]
         if not ready:
             break
-        ns = items[ready[0]][at[ready[0]]][1]
+        waits = [items[c][at[c]][1] for c in ready]
+        ns = waits[0] if rng is None else max(sorted(set(waits)), key=waits.count)
         take = {}
         for c in ready:
             it, k = items[c], at[c]
             if it[k][1] != ns:
                 continue
-            n = 1
-            while n < most and k + n < len(it) and it[k + n][0] == "blk" and it[k + n][1] == ns and it[k + n][2] == it[k + n - 1][2] + ns:
+            n, lim = 1, most if rng is None else int(rng.integers(1, most + 1)) if waits.count(ns) > 1 else 256
+            while n < lim and k + n < len(it) and it[k + n][0] == "blk" and it[k + n][1] == ns and it[k + n][2] == it[k + n - 1][2] + ns:
                 n += 1
             take[c] = it[k:k + n]
         conns = sorted(take, key=lambda c: -c)                            # not in connection order: the list's order is the caller's
@@ -76,7 +79,9 @@ def run_side_by_side(q, scripts, samples, most=8):
             rec[c].add([b[3] for b in take[c]], m[m["conn"] == c], rows)
             at[c] += len(take[c])
         shared += len(conns) > 1
-    return [r.result(lc.state_of(q, c)) for c, r in enumerate(rec)], shared
+        calls += 1
+    got = [r.result(lc.state_of(q, c)) for c, r in enumerate(rec)]
+    return (got, shared) if rng is None else (got, shared, calls)
 
 
 @pytest.mark.parametrize("group", range(len(TRIPLES)))
@@ -189,3 +194,85 @@ def test_a_stopped_connection_takes_nothing(gpu_ctx, pool):
         assert m.size == 0 and int(info["ch"][0]["samp"]) == 0 and not avg.any() and not rows.any()
     finally:
         q.close()
+
+
+# ---- seeded random scripts (tests/ext_random.py) under random call partitions: the device against the host model, in full
+PARTS = 4                                                                  # the 40 seeds, ten a test
+
+
+@pytest.fixture(scope="module")
+def random_ref():
+    from . import ext_random as er, ext_random_dev as ed
+    return er.load("lorc")
+
+
+@pytest.fixture(scope="module")
+def random_host(pool, tmp_path_factory):
+    """the host driver's result of every seed, sample by sample: made once, shared, left unchanged"""
+    from . import ext_random as er, ext_random_dev as ed
+    tmp = tmp_path_factory.mktemp("lorc_random")
+    driver = lc.build_driver(tmp)
+    return [lc.run_script_exe(driver, er.lorc_script(seed), pool, tmp) for seed in range(er.NSEED)]
+
+
+@pytest.mark.parametrize("part", range(PARTS))
+def test_random_scripts_under_a_random_partition(gpu_ctx, random_ref, random_host, pool, part):
+    """every seed's script with at most max_blocks (drawn from 1, 2, 5, 48 by a generator of its own) blocks a call, and again a call a
+    block: both equal the host model in every row byte and map field and the whole end state with avg[2][1199], hence each other, and
+    the fixture's digests"""
+    from . import ext_random as er, ext_random_dev as ed
+    q = lorc.LoranC(gpu_ctx, nconn=2)
+    try:
+        for seed in range(part * er.NSEED // PARTS, (part + 1) * er.NSEED // PARTS):
+            lines = er.lorc_script(seed)
+            most = ed.partition("lorc", seed, lc.nblocks(lines))
+            got = lc.run_script_dev(q, lines, pool, conn=0, max_blocks=most)
+            each = lc.run_script_dev(q, lines, pool, conn=1, max_blocks=1)
+            ed.lorc_same(got, random_host[seed], "seed %d" % seed, "max_blocks %d" % most)
+            ed.lorc_same(each, random_host[seed], "seed %d" % seed, "a call a block")
+            assert lc.all_bytes(got).tobytes() == lc.all_bytes(each).tobytes() and each["calls"] >= got["calls"]
+            er.check_record("lorc", seed, lines, got, er.unpack(random_ref, seed))
+    finally:
+        q.close()
+
+
+class _Planned:
+    """stands in for a LoranC where only the schedule of run_side_by_side is wanted: takes every command and call, answers no row"""
+
+    def __getattr__(self, name):
+        return lambda *a, **k: None
+
+    def process(self, conns, x, nblk=None):
+        return np.zeros(0, np.uint8), np.zeros(0, lorc.row_dtype)
+
+    def state(self, conn):
+        return np.zeros(1, lorc.info_dtype)[0], np.zeros((2, lc.MAX_BUCKET), np.float32)
+
+
+def _random_group(q, pool, group):
+    from . import ext_random as er, ext_random_dev as ed
+    seeds = ed.triples()[group]
+    return seeds, run_side_by_side(q, [er.lorc_script(s) for s in seeds], pool, most=4, rng=ed.plan_rng("lorc", group))
+
+
+@pytest.mark.parametrize("group", range(14))
+def test_random_scripts_side_by_side(gpu_ctx, random_ref, random_host, pool, group):
+    """the seeds three at a time on three connections of one object, listed out of order: every call carries every connection whose next
+    blocks share the round's ns, a random number of blocks each; the commands go between the calls.  Each connection equals the host
+    model of its own script in full, and the fixture"""
+    from . import ext_random as er, ext_random_dev as ed
+    q = lorc.LoranC(gpu_ctx, nconn=3)
+    try:
+        seeds, (got, shared, calls) = _random_group(q, pool, group)
+    finally:
+        q.close()
+    for seed, g in zip(seeds, got):
+        ed.lorc_same(g, random_host[seed], "seed %d of %s" % (seed, seeds))
+        er.check_record("lorc", seed, er.lorc_script(seed), g, er.unpack(random_ref, seed))
+    assert shared >= 1 and calls >= shared
+
+
+def test_random_side_by_side_calls_are_shared(pool):
+    """at least half of the calls of all the groups carry more than one connection: the schedule alone, which no row decides"""
+    every = [_random_group(_Planned(), pool, k)[1][1:] for k in range(14)]
+    assert 2 * sum(s for s, _ in every) >= sum(c for _, c in every), every

@@ -13,6 +13,8 @@ Two pins (tests/fftext_common.py holds the inputs):
   2. limiter   fft_data under FUNC_SPEC and scripted clocks: sent / last_ms per call
 
     python tools/make_ref_fftext_golden.py
+    python tools/make_ref_fftext_golden.py --random     tests/golden/fftext_rand_ref.npz: the seeded random scripts of tests/ext_random.py, by
+                                                        digest and integers alone
 """
 import os
 import subprocess
@@ -90,6 +92,12 @@ def build(tmp):
     return exe
 
 
+def random_main():
+    from tests import ext_random
+    with tempfile.TemporaryDirectory() as tmp:
+        ext_random.write_fixture("fftext", build(tmp), C.pool()[1], tmp)
+
+
 def main():
     out = {}
     names, spec = C.pool()
@@ -135,4 +143,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    random_main() if sys.argv[1:] == ["--random"] else main()

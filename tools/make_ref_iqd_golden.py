@@ -12,6 +12,8 @@ message and its four numbers, and the end state: every scalar bit for bit, _iq /
 tests/test_iqd_cpu.py::test_golden_file_meets_its_conditions are checked here on the reference's output before the file is written.
 
     python tools/make_ref_iqd_golden.py
+    python tools/make_ref_iqd_golden.py --random     tests/golden/iqd_rand_ref.npz: the seeded random scripts of tests/ext_random.py, by
+                                                     digest and integers alone
 """
 import os
 import subprocess
@@ -81,6 +83,12 @@ def final_df(got, lines):
     return float(got["status"]["df"][-1])
 
 
+def random_main():
+    from tests import ext_random
+    with tempfile.TemporaryDirectory() as tmp:
+        ext_random.write_fixture("iqd", build(tmp), C.pool(), tmp)
+
+
 def main():
     out = {}
     samples = C.pool()
@@ -115,4 +123,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    random_main() if sys.argv[1:] == ["--random"] else main()

@@ -13,6 +13,8 @@ The conditions of tests/test_lorc_cpu.py::test_golden_file_meets_its_conditions 
 file is kept.
 
     python tools/make_ref_lorc_golden.py
+    python tools/make_ref_lorc_golden.py --random     tests/golden/lorc_rand_ref.npz: the seeded random scripts of tests/ext_random.py, by
+                                                      digest and integers alone
 """
 import os
 import shutil
@@ -98,6 +100,12 @@ def build(tmp):
     return exe
 
 
+def random_main():
+    from tests import ext_random
+    with tempfile.TemporaryDirectory() as tmp:
+        ext_random.write_fixture("lorc", build(tmp), C.pool(), tmp)
+
+
 def main():
     out = {}
     samples = C.pool()
@@ -127,4 +135,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    random_main() if sys.argv[1:] == ["--random"] else main()
