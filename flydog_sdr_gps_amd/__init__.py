@@ -21,7 +21,8 @@ from .eph import Ephemerides  # noqa: F401
 from .pos import PositionSolver  # noqa: F401
 from .fftext import FftExt  # noqa: F401
 from .lorc import LoranC  # noqa: F401
-from . import sats, prn, synth, shard, wf, snd, post, wire, handoff, nb, trk, nav, eph, pos, fftext, lorc  # noqa: F401
+from .fax import FaxDecoder  # noqa: F401
+from . import sats, prn, synth, shard, wf, snd, post, wire, handoff, nb, trk, nav, eph, pos, fftext, lorc, fax  # noqa: F401
 
-__all__ = ["KiwiGpuError", "Context", "Searcher", "AcqResult", "Waterfall", "WfParams", "Ddc", "RxDdc", "FastFir", "Post", "NoiseBlanker", "Adpcm", "Aperture", "chan_start", "Tracker", "NavSync", "Ephemerides", "FftExt", "LoranC",
+__all__ = ["KiwiGpuError", "Context", "Searcher", "AcqResult", "Waterfall", "WfParams", "Ddc", "RxDdc", "FastFir", "Post", "NoiseBlanker", "Adpcm", "Aperture", "chan_start", "Tracker", "NavSync", "Ephemerides", "FftExt", "LoranC", "FaxDecoder",
            "load_library", "library_path", "live_allocs", "sats", "prn", "synth", "shard", "wf"]

@@ -251,6 +251,14 @@ SYMBOLS = {
     "kg_lorc_plan": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
     "kg_lorc_state": (_i, [_vp, _i, _vp, _vp]),
     "kg_lorc_ms_per_bin": (C.c_float, [C.c_double, _i]),
+    "kg_fax_create": (_i, [_vp, _i, C.POINTER(_vp)]),
+    "kg_fax_destroy": (None, [_vp]),
+    "kg_fax_start": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.c_double, C.c_double]),
+    "kg_fax_set_shift": (_i, [_vp, _i, C.c_float]),
+    "kg_fax_stop": (_i, [_vp, _i]),
+    "kg_fax_max_lines": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
+    "kg_fax_push": (_i, [_vp, _vp, _i, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _i, _vp]),
+    "kg_fax_state": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "kg_rxbank_lorc_init": (_i, [_vp, _i, C.c_double, _i]),
     "kg_rxbank_lorc_set_gri": (_i, [_vp, _i, _i, _i]),
     "kg_rxbank_lorc_set_offset": (_i, [_vp, _i, _i, _i]),
@@ -262,6 +270,11 @@ SYMBOLS = {
     "kg_rxbank_lorc": (_vp, [_vp]),
     "kg_rxbank_lorc_map": (_i, [_vp, _vp, _i]),
     "kg_rxbank_lorc_rows": (_i, [_vp, _vp, _vp]),
+    "kg_rxbank_fax_start": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.c_double, C.c_double]),
+    "kg_rxbank_fax_set_shift": (_i, [_vp, _i, C.c_float]),
+    "kg_rxbank_fax_stop": (_i, [_vp, _i]),
+    "kg_rxbank_fax": (_vp, [_vp]),
+    "kg_rxbank_fax_out": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
     "kg_rxbank_fftext_set_rate": (_i, [_vp, C.c_double]),
     "kg_rxbank_fftext_set_run": (_i, [_vp, _i, _i]),
     "kg_rxbank_fftext_set_itime": (_i, [_vp, _i, C.c_double]),

@@ -244,6 +244,14 @@ __attribute__((visibility("hidden"))) int kg_lorc_set_gri_min_(kg_lorc *q, int c
 // connection conn as a new connection finds it: all zero, stopped, not initialised
 __attribute__((visibility("hidden"))) int kg_lorc_reset_(kg_lorc *q, int conn);
 
+// kg_fax.hip, for kg_rxbank.hip (not part of the ABI): kg_fax_push on device memory, samples and outputs alike, entry i's samples at
+// in_off[i] samples from d_s16 (null: i * stride), enqueue only; the bytes a push's table takes; connection conn as a new connection finds it: the zeroed object, not started
+__attribute__((visibility("hidden"))) int kg_fax_push_at_(kg_fax *q, const int32_t *conns, int nconn, const int32_t *nblk, const int64_t *in_off, const int16_t *d_s16,
+                                                          size_t stride, const double *srate, uint8_t *d_rows, size_t row_stride, kg_fax_rec *d_recs, int max_lines,
+                                                          int32_t *d_counts);
+__attribute__((visibility("hidden"))) size_t kg_fax_table_bytes_(size_t nconn);
+__attribute__((visibility("hidden"))) int kg_fax_reset_(kg_fax *q, int conn);
+
 // kg_post.hip, for kg_rxbank.hip: how many kg_post_set_mode / kg_post_set_sam_mparam calls channel ch has seen (each clears
 // s->isChanNull, rx_sound_cmd.cpp:202-228), and its s->SAM_mparam
 __attribute__((visibility("hidden"))) uint32_t kg_post_mode_cmds_(const kg_post *p, int ch);

@@ -35,6 +35,10 @@
 // blocks: 4 B whole GRIs, a partial one, and the cuts where samp and the unsigned difference wrap
 #define BANK_LO_MIN_SPG 128.0
 #define BANK_LO_RUNS(blocks_) (4 * (size_t) (blocks_) + 4)
+// FAX in a bank: a line is BANK_FAX_MIN_SPL samples or more and an image BANK_FAX_MAX_WIDTH pixels or fewer, which bounds the lines
+// and the row bytes of a step (kg_fax_max_lines' rule: a block gives at most 1026 picks)
+#define BANK_FAX_MIN_SPL 1024
+#define BANK_FAX_MAX_WIDTH 4096
 #define BANK_SLOTS KG_RXBANK_SLOTS         // step-table slots in flight (a slot is reused BANK_SLOTS steps later)
 #define BANK_RING_PAIRS (8 * KG_WF_NFFT)   // an overlapped receiver's sample ring (iq_t pairs); >= 2 frames
 #define BANK_PKT_STRIDE 1056               // >= KG_WF_PKT_MAX, a multiple of 16
@@ -76,6 +80,8 @@ struct bank_rx {
     char fx_on = 0;                             // the FFT extension's run != FUNC_OFF
     char iq_on = 0;                             // the IQ display's `SET run=` (ext_register_receive_iq_samps)
     char lo_on = 0;                             // Loran-C's `SET start` (the same registration: one of the two at most)
+    char fax_on = 0;                            // FAX's `SET fax_start` (ext_register_receive_real_samps_task: the OTHER tap)
+    double fax_rate = 0;                        // what ext_update_get_sample_rateHz answers for it: kg_rxbank_fax_start's srate
     bank_nb_cmd nbc = {};
     // the settings a join leaves alone
     int decim = 0; char overlapped = 0;         // kg_rxbank_set_wf
@@ -110,6 +116,10 @@ struct bank_plan {
     std::vector<int32_t> lo_list, lo_nblk, lo_row;
     std::vector<kg_lorc_row> lo_rows;
     int32_t lo_n;
+    // FAX's entries: receiver, blocks, where the receiver's row of d_s16 begins, its sample rate
+    std::vector<int32_t> fa_list, fa_nblk;
+    std::vector<int64_t> fa_off;
+    std::vector<double> fa_rate;
     // per sound block: list j of block blk is blk_chan[blk_at[BL_N * blk + j] .. blk_at[BL_N * blk + j + 1]); beside a BL_NULL
     // entry its row count and row
     std::vector<int32_t> blk_chan, blk_at, blk_null_n, blk_null_base;
@@ -162,6 +172,16 @@ struct kg_rxbank {
     kg_dbuf<unsigned char> d_lorows; size_t lo_cap; int lo_max_rows;      // the step's rows, each at a multiple of 16 bytes
     int lo_n;
     std::vector<kg_lorc_row> lo_rows;
+    // the FAX extension (extensions/FAX/FaxDecoder.cpp; kg_fax), made by the first kg_rxbank_fax_* call, which also grows the arena
+    // slots by its table.  While a receiver is started and its blocks go on the mono list (the branch in which the reference advances
+    // real_wr_pos, rx_sound.cpp:701-703, :1103: not IQ, SAS or QAM), the step's d_s16 blocks feed it in place: ONE launch per step
+    // over all such receivers, on the tail stream behind kg_post_process_dev and ahead of ev_tail.  The counts are the device's.
+    kg_fax *fa;
+    kg_dbuf<unsigned char> d_farows; size_t fa_row_stride; int fa_max_lines;      // [entry][fa_max_lines][fa_row_stride]
+    kg_dbuf<kg_fax_rec> d_farecs;                                                 // [entry][fa_max_lines]
+    kg_dbuf<int32_t> d_facounts;                                                  // [entry][4]
+    int fa_n;                                                                     // the last step's entries
+    std::vector<int32_t> fa_rx;                                                   // their receivers
     // device buffers
     kg_dbuf<short2> d_wfiq; size_t wf_stride;         // [nrx][wf_stride] iq_t: a one-shot receiver uses pairs 0 .. 8191 of its row, an overlapped one all of it
     kg_dbuf<unsigned char> d_rows, d_pkts;         // [frame][1024], [frame][BANK_PKT_STRIDE]
@@ -277,6 +297,10 @@ static void bank_plan_rows(kg_rxbank *b, int i, int nblk)
         p.iq_list.push_back(k); p.iq_nblk.push_back(nblk); p.iq_inst.push_back(0); p.iq_row.push_back(k);
     }
     if (b->lo && r.lo_on && nblk > 0 && p.mode[i] != KG_POST_NBFM) { p.lo_list.push_back(k); p.lo_nblk.push_back(nblk); p.lo_row.push_back(k); }
+    const bool stereo = p.mode[i] == KG_POST_IQ || p.mode[i] == KG_POST_SAS || p.mode[i] == KG_POST_QAM;      // the BL_REAL rule of bank_plan_blocks
+    if (b->fa && r.fax_on && nblk > 0 && !stereo) {        // real_wr_pos advances for the mono blocks alone: fax_task sees no other
+        p.fa_list.push_back(k); p.fa_nblk.push_back(nblk); p.fa_off.push_back((int64_t) ((size_t) k * b->firo_stride)); p.fa_rate.push_back(r.fax_rate);
+    }
 }
 
 // The active list and, per entry, the counts its audio DDC and its CFastFIR will hand back (kg_rxddc_outputs is kg_rxddc_push_dev's
@@ -286,8 +310,9 @@ static void bank_plan_audio(kg_rxbank *b)
 {
     bank_plan &p = b->plan;
     for (std::vector<int32_t> *v : {&p.act, &p.nb_list, &p.nb_cnt, &p.fx_list, &p.fx_nblk, &p.fx_inst, &p.fx_row, &p.fx_blk0, &p.iq_list, &p.iq_nblk, &p.iq_inst,
-                                    &p.iq_row, &p.lo_list, &p.lo_nblk, &p.lo_row})
+                                    &p.iq_row, &p.lo_list, &p.lo_nblk, &p.lo_row, &p.fa_list, &p.fa_nblk})
         v->clear();
+    p.fa_off.clear(); p.fa_rate.clear();
     std::fill(p.fx_nullpos.begin(), p.fx_nullpos.end(), 0);
     p.nrec_max = p.nfir_max = p.nspec = p.fx_n = p.iq_n = 0;
     p.lo_n = 0;
@@ -504,6 +529,9 @@ static int bank_audio_tail(kg_rxbank *b)
     if (!p.lo_list.empty())                                // loran_c_data over the step's blocks: one launch, reading d_firo in place
         KG_TRY(kg_lorc_process_rows_(b->lo, p.lo_list.data(), (int) p.lo_list.size(), p.lo_nblk.data(), p.lo_row.data(), KG_FIR_OUT, (const float *) b->d_firo.p,
                                      b->firo_stride, b->d_lorows, b->lo_cap, p.lo_rows.data(), b->lo_max_rows, &p.lo_n));
+    if (!p.fa_list.empty())                                // ProcessSamples over the step's blocks: one launch, reading d_s16 in place
+        KG_TRY(kg_fax_push_at_(b->fa, p.fa_list.data(), (int) p.fa_list.size(), p.fa_nblk.data(), p.fa_off.data(), (const int16_t *) b->d_s16.p, b->firo_stride,
+                               p.fa_rate.data(), b->d_farows, b->fa_row_stride, b->d_farecs, b->fa_max_lines, b->d_facounts));
     KG_TRY(bank_edge(real, b->ev_tail, b->s_tail, nullptr, &b->tail_pending));
     tk.lap(b, PF_EVENTS, real);
     return KG_OK;
@@ -570,6 +598,8 @@ static void bank_commit(kg_rxbank *b)
     }
     b->lo_n = p.lo_n;
     if (b->lo) b->lo_rows.swap(p.lo_rows);
+    b->fa_n = (int) p.fa_list.size();
+    for (int e = 0; e < b->fa_n; e++) b->fa_rx[e] = p.fa_list[e];
     b->spec_rx.swap(p.spec_rx); b->spec_inst.swap(p.spec_inst); b->spec_blk.swap(p.spec_blk);
     b->fx_rx.swap(p.fx_rx); b->fx_blk.swap(p.fx_blk); b->fx_bin.swap(p.fx_bin);
     b->frame_rx.swap(p.chan_of); b->frame_off.swap(p.frame_off); b->pkt_bytes.swap(p.pkt_bytes);
@@ -763,7 +793,8 @@ static void bank_plan_init(bank_plan &p, size_t nrx, size_t blocks_max, size_t s
     for (std::vector<int32_t> *v : {&p.spec_rx, &p.spec_inst, &p.spec_blk}) v->assign(spec_max, 0);
     for (std::vector<int32_t> *v : {&p.act, &p.nb_list, &p.nb_cnt}) v->reserve(nrx);
     for (std::vector<int32_t> *v : {&p.fx_list, &p.fx_nblk, &p.fx_inst, &p.fx_row, &p.fx_blk0}) v->reserve(2 * nrx * blocks_max);
-    for (std::vector<int32_t> *v : {&p.iq_list, &p.iq_nblk, &p.iq_inst, &p.iq_row, &p.lo_list, &p.lo_nblk, &p.lo_row}) v->reserve(nrx);
+    for (std::vector<int32_t> *v : {&p.iq_list, &p.iq_nblk, &p.iq_inst, &p.iq_row, &p.lo_list, &p.lo_nblk, &p.lo_row, &p.fa_list, &p.fa_nblk}) v->reserve(nrx);
+    p.fa_off.reserve(nrx); p.fa_rate.reserve(nrx);
     for (std::vector<int32_t> *v : {&p.blk_chan, &p.blk_null_n, &p.blk_null_base}) v->reserve(3 * nrx * blocks_max);
     p.blk_at.reserve(BL_N * blocks_max + 1);
     p.pb_inst.assign(nrx, KG_SPEC_PASSBAND); p.null_inst.assign(nrx, KG_SPEC_CHAN_NULL); p.null_each.assign(nrx, KG_FIR_OUT);
@@ -829,6 +860,10 @@ static int bank_init(kg_rxbank *b)
     // a row per run at most: BANK_LO_RUNS rows of up to 1200 bytes per receiver and Loran channel
     b->lo_max_rows = (int) ((size_t) nrx * 2 * BANK_LO_RUNS(b->blocks_max));
     b->lo_cap = (size_t) b->lo_max_rows * 1200;
+    b->fa = nullptr; b->fa_n = 0;
+    b->fa_max_lines = (int) ((b->blocks_max * (2 * KG_FAX_BLK + 2) + BANK_FAX_MIN_SPL - 1) / BANK_FAX_MIN_SPL) + 1;
+    b->fa_row_stride = (BANK_FAX_MAX_WIDTH + 1 + 15) & ~(size_t) 15;
+    b->fa_rx.assign(nrx, -1);
     for (std::vector<int32_t> *v : {&b->spec_rx, &b->spec_inst, &b->spec_blk}) v->assign(b->spec_max, 0);
     b->frame_rx.assign(nrx, -1); b->pkt_bytes.assign(nrx, 0); b->frame_off.assign(nrx, 0);
     memset(&b->arena, 0, sizeof b->arena);
@@ -848,6 +883,7 @@ void kg_rxbank_destroy(kg_rxbank *b)
     kg_fftext_destroy(b->fx);
     kg_iqd_destroy(b->iq);
     kg_lorc_destroy(b->lo);
+    kg_fax_destroy(b->fa);
     kg_adpcm_destroy(b->adpcm); kg_post_destroy(b->post); kg_fir_destroy(b->nullfir); kg_fir_destroy(b->fir); kg_rxddc_destroy(b->rx); kg_nb_destroy(b->nb);
     kg_wf_destroy(b->wf); kg_ddc_destroy(b->ddc);
     kg_ctx_destroy(b->c_tail); kg_ctx_destroy(b->c_side); kg_ctx_destroy(b->c_main);
@@ -1173,6 +1209,94 @@ int kg_rxbank_lorc_rows(kg_rxbank *b, uint8_t **d_rows, size_t *cap)
     return KG_OK;
 }
 
+}  // extern "C"
+
+// FAX's object and output buffers, and arena slots grown by its table, made whole or not at all by the first call that names the
+// extension.  Drains the bank's streams: no step is in flight while the slots change.
+static int bank_fa_ensure(kg_rxbank *b)
+{
+    if (b->fa) return KG_OK;
+    KG_HIP(hipSetDevice(b->device));
+    KG_TRY(bank_drain(b, true));
+    kg_fax *fa = nullptr;
+    kg_hbuf<unsigned char> h;
+    kg_dbuf<unsigned char> d, rows;
+    kg_dbuf<kg_fax_rec> recs;
+    kg_dbuf<int32_t> counts;
+    const size_t grown = (b->slot_bytes + kg_fax_table_bytes_((size_t) b->nrx) + 63) & ~(size_t) 63;
+    const size_t nrows = (size_t) b->nrx * (size_t) b->fa_max_lines;
+    KG_TRY(h.alloc(grown * BANK_SLOTS, "kg_rxbank_fax: slots"));
+    KG_TRY(d.alloc(grown * BANK_SLOTS, "kg_rxbank_fax: slots"));
+    KG_TRY(rows.alloc(nrows * b->fa_row_stride, "kg_rxbank_fax: rows"));
+    KG_TRY(recs.alloc(nrows, "kg_rxbank_fax: records"));
+    KG_TRY(counts.alloc((size_t) 4 * b->nrx, "kg_rxbank_fax: counts"));
+    if (hipMemset(rows, 0, nrows * b->fa_row_stride) != hipSuccess || hipMemset(recs, 0, nrows * sizeof(kg_fax_rec)) != hipSuccess ||
+        hipMemset(counts, 0, sizeof(int32_t) * 4 * (size_t) b->nrx) != hipSuccess) {
+        kg_set_error("kg_rxbank_fax: hipMemset failed");
+        return KG_ERR_HIP;
+    }
+    KG_TRY(kg_fax_create(b->c_tail, b->nrx, &fa));
+    std::swap(b->h_slots.p, h.p); std::swap(b->d_slots.p, d.p);          // the old slots go with h and d
+    std::swap(b->d_farows.p, rows.p); std::swap(b->d_farecs.p, recs.p); std::swap(b->d_facounts.p, counts.p);
+    b->slot_bytes = grown;
+    b->fa = fa;
+    return KG_OK;
+}
+
+// the connection's end or beginning: m_FaxDecoder[rx] and fax[rx] as a new connection finds them -- zeroed, no task
+static int bank_fa_fresh(kg_rxbank *b, int rx)
+{
+    b->rcv[rx].fax_on = 0;
+    b->rcv[rx].fax_rate = 0;
+    return b->fa ? kg_fax_reset_(b->fa, rx) : KG_OK;
+}
+
+#define BANK_FA(who)                                   \
+    KG_TRY(bank_rx_check(b, rx, who));                 \
+    KG_TRY(bank_fa_ensure(b))
+
+extern "C" {
+
+int kg_rxbank_fax_start(kg_rxbank *b, int rx, int lpm, int imagewidth, int carrier, int deviation, int bandwidth, int include_headers, int phasing, int autostop,
+                        int debug, double nom_rate, double srate)
+{
+    BANK_FA("kg_rxbank_fax_start");
+    KG_REQUIRE(imagewidth <= BANK_FAX_MAX_WIDTH, KG_ERR_INVALID, "kg_rxbank_fax_start: imagewidth %d; a receiver bank takes %d or fewer", imagewidth,
+               BANK_FAX_MAX_WIDTH);
+    KG_REQUIRE(!(lpm >= 1 && nom_rate >= 1) || nom_rate * 60.0 / lpm >= BANK_FAX_MIN_SPL, KG_ERR_INVALID,
+               "kg_rxbank_fax_start: %g samples a line; a receiver bank takes %d or more (it bounds a step's lines by it)", nom_rate * 60.0 / lpm, BANK_FAX_MIN_SPL);
+    KG_TRY(kg_fax_start(b->fa, rx, lpm, imagewidth, carrier, deviation, bandwidth, include_headers, phasing, autostop, debug, nom_rate, srate));
+    b->rcv[rx].fax_on = 1;
+    b->rcv[rx].fax_rate = srate;
+    return KG_OK;
+}
+
+int kg_rxbank_fax_set_shift(kg_rxbank *b, int rx, float shift) { BANK_FA("kg_rxbank_fax_set_shift"); return kg_fax_set_shift(b->fa, rx, shift); }
+
+int kg_rxbank_fax_stop(kg_rxbank *b, int rx)
+{
+    BANK_FA("kg_rxbank_fax_stop");
+    KG_TRY(kg_fax_stop(b->fa, rx));
+    b->rcv[rx].fax_on = 0;
+    return KG_OK;
+}
+
+kg_fax *kg_rxbank_fax(kg_rxbank *b) { return b ? b->fa : nullptr; }
+
+int kg_rxbank_fax_out(kg_rxbank *b, uint8_t **d_rows, size_t *row_stride, kg_fax_rec **d_recs, int32_t **d_counts, int32_t *max_lines, int32_t *rx_of_entry,
+                      int max_entries)
+{
+    KG_REQUIRE(b != nullptr && max_entries >= 0, KG_ERR_INVALID, "kg_rxbank_fax_out: bad argument");
+    KG_REQUIRE(!rx_of_entry || max_entries >= b->fa_n, KG_ERR_INVALID, "kg_rxbank_fax_out: %d entries, room for %d", b->fa_n, max_entries);
+    if (d_rows) *d_rows = b->d_farows;                                   // null until the extension was named
+    if (row_stride) *row_stride = b->fa_row_stride;
+    if (d_recs) *d_recs = b->d_farecs;
+    if (d_counts) *d_counts = b->d_facounts;
+    if (max_lines) *max_lines = b->fa_max_lines;
+    if (rx_of_entry && b->fa_n) memcpy(rx_of_entry, b->fa_rx.data(), sizeof(int32_t) * (size_t) b->fa_n);
+    return b->fa_n;
+}
+
 int kg_rxbank_set_wf(kg_rxbank *b, int rx, uint64_t phase_inc, int decim, int overlapped)
 {
     KG_TRY(bank_rx_check(b, rx, "kg_rxbank_set_wf"));
@@ -1208,6 +1332,7 @@ int kg_rxbank_leave(kg_rxbank *b, int rx)
     b->rcv[rx].iq_on = 0;                                  // iq_display_close: the object goes with the connection
     if (b->iq) KG_TRY(kg_iqd_init(b->iq, rx));
     KG_TRY(bank_lo_fresh(b, rx));
+    KG_TRY(bank_fa_fresh(b, rx));
     return KG_OK;
 }
 
@@ -1238,6 +1363,7 @@ int kg_rxbank_join(kg_rxbank *b, int rx)
     r.iq_on = 0;                                           // the IQ display's object is the connection's: a fresh one, not registered
     if (b->iq) KG_TRY(kg_iqd_init(b->iq, rx));
     KG_TRY(bank_lo_fresh(b, rx));
+    KG_TRY(bank_fa_fresh(b, rx));
     r.nbc = bank_nb_cmd{};                                 // memset(snd_t) / memset(wf_inst_t): algo NB_OFF, enables and params 0;
     KG_TRY(kg_wf_set_nb(b->wf, rx, 0));                    // the blankers' states stay (the reference's CNoiseProc arrays are globals)
     r.active = 1;

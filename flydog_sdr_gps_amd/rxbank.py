@@ -362,6 +362,51 @@ class RxBank:
             self.ctx.download(int(d.value), out)
         return m, out
 
+    # ---- the FAX extension (extensions/FAX/FaxDecoder.cpp, fax.cpp): kg_fax's commands per receiver
+    def fax_start(self, rx, lpm=120, imagewidth=1024, carrier=1900, deviation=400, bandwidth=1, include_headers=True, phasing=True, autostop=True, debug=0,
+                  nom_rate=12000.0, srate=None):
+        """`SET fax_start` (the defaults are what fax.cpp:131-145 passes); srate stays the receiver's sample rate until the next start"""
+        check(self.lib.kg_rxbank_fax_start(self.h, int(rx), int(lpm), int(imagewidth), int(carrier), int(deviation), int(bandwidth), int(bool(include_headers)),
+                                           int(bool(phasing)), int(bool(autostop)), int(debug), float(nom_rate), float(nom_rate if srate is None else srate)),
+              "kg_rxbank_fax_start")
+
+    def fax_set_shift(self, rx, shift):
+        check(self.lib.kg_rxbank_fax_set_shift(self.h, int(rx), float(shift)), "kg_rxbank_fax_set_shift")
+
+    def fax_stop(self, rx):
+        check(self.lib.kg_rxbank_fax_stop(self.h, int(rx)), "kg_rxbank_fax_stop")
+
+    @property
+    def fax(self):
+        """the bank's FaxDecoder (None until one of the fax_* commands was sent): state()"""
+        from . import fax as fa_mod
+        h = self.lib.kg_rxbank_fax(self.h)
+        return borrow(fa_mod.FaxDecoder, self.ctx, h, nconn=self.nrx) if h else None
+
+    def fax_out(self):
+        """-> {receiver: (records of fax.rec_dtype -- blk the sound block of the step --, rows uint8 [rows, row_stride])} of the last step
+        (after sync()): the receivers the step fed"""
+        from . import fax as fa_mod
+        rxs = np.zeros(self.nrx, np.int32)
+        d_rows, stride, d_recs, d_counts, ml = C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_void_p(), C.c_int32()
+        n = check(self.lib.kg_rxbank_fax_out(self.h, C.byref(d_rows), C.byref(stride), C.byref(d_recs), C.byref(d_counts), C.byref(ml), ptr(rxs), int(rxs.size)),
+                  "kg_rxbank_fax_out")
+        out = {}
+        if n == 0:
+            return out
+        counts = np.zeros((n, 4), np.int32)
+        self.ctx.download(int(d_counts.value), counts)
+        assert not counts[:, 2].any(), "a capacity was exceeded"
+        for e in range(n):
+            recs = np.zeros(int(counts[e, 1]), fa_mod.rec_dtype)
+            rows = np.zeros((int(counts[e, 0]), int(stride.value)), np.uint8)
+            if recs.size:
+                self.ctx.download(int(d_recs.value) + e * ml.value * fa_mod.rec_dtype.itemsize, recs)
+            if rows.size:
+                self.ctx.download(int(d_rows.value) + e * ml.value * int(stride.value), rows)
+            out[int(rxs[e])] = (recs, rows)
+        return out
+
     def fftext_set_rate(self, sample_rate):
         """what ext_update_get_sample_rateHz answers for the FFT extension (extensions/FFT/FFT.cpp:79)"""
         check(self.lib.kg_rxbank_fftext_set_rate(self.h, float(sample_rate)), "kg_rxbank_fftext_set_rate")

@@ -1397,6 +1397,73 @@ int kg_lorc_state(kg_lorc *q, int conn, kg_lorc_info *info, float *avg);
 /* the number of the `EXT ms_per_bin=` line (:223-225): float(1.0 / srate * 1e3), doubled in float when i_srate > 12000 */
 float kg_lorc_ms_per_bin(double srate, int i_srate);
 
+/* ---- The FAX extension (extensions/FAX/FaxDecoder.cpp, FaxDecoder.h, fax.cpp): HF weather fax from the 16-bit mono audio a sound block
+ * ends as (receive_real_samps, rx/rx_sound.cpp:1100-1111) -- the other tap of c2s_sound().  Per audio sample a quadrature mix, two
+ * 17-tap FIR filters, a normalisation and a phase-difference discriminator; per line two single-frequency Fourier sums (start and stop
+ * tone), a wedge search (phasing), a resample to imagewidth pixels and a blend of successive lines.  Every row byte and every decision
+ * is an exact function of the samples: csrc/kg_fax.h is the one definition for device and host, in the reference's operand types.
+ *
+ * The SCHEDULE depends on the samples (the phasing result moves every later line boundary, the stop tone suppresses rows), so the whole
+ * FaxDecoder of a connection lives on the device and a push's outputs carry counts the DEVICE writes: for entry i of the list, with
+ * max_lines the capacity the caller chose (kg_fax_max_lines gives the least one),
+ *   counts[4*i]      rows sent;  counts[4*i + 1]  lines completed;  counts[4*i + 2]  1 if a capacity was exceeded (never, by the bound)
+ *   rows + (i*max_lines + r) * row_stride     row r: KG_FAX_MSG_DRAW, then imagewidth bytes (ext_send_msg_data, :404)
+ *   recs + i*max_lines + l                    line l (kg_fax_rec)
+ * Defined here where the reference leaves it open: what `new` and kiwi_imalloc hand out is zeros (so the line a row is blended with
+ * behind lines that autostop counted without decoding is zeros); a pixel whose discriminator is NaN (silence) is byte 0.
+ * Refused with nothing changed: lpm < 1, deviation 0, a bandwidth outside 0 .. 2, imagewidth < 1, fewer samples a line than
+ * imagewidth, more than KG_FAX_MAX_SPL samples a line, a nominal rate outside 1 .. 1e6 Hz, a sample rate outside half to twice the
+ * nominal, a shift that is negative, above 1 or not finite.  Not ported: the pgm file, the shell commands, fax_task's sequence numbers. */
+typedef struct kg_fax kg_fax;
+#define KG_FAX_MAX_SPL 24576                               /* samples a line: 60 lpm at 20250 Hz is 20250 */
+#define KG_FAX_BLK 512                                     /* FASTFIR_OUTBUF_SIZE, fax.cpp:85 */
+#define KG_FAX_MSG_DRAW 254                                /* FaxDecoder.h:34 */
+enum { KG_FAX_IMAGE = 0, KG_FAX_START = 1, KG_FAX_STOP = 2 };              /* FaxDecoder.h:102 */
+enum { KG_FAX_SPS_CHANGED = 1, KG_FAX_AUTOSTOPPED_0 = 2, KG_FAX_AUTOSTOPPED_1 = 4, KG_FAX_PHASED = 8,     /* the ext_send_msg texts :294, :209, :216, :274 */
+       KG_FAX_ROW_SENT = 16, KG_FAX_PHASING_REJECTED = 32, KG_FAX_MEDIAN = 64 };                           /* :404, :240-243, :238 */
+typedef struct kg_fax_rec {                /* one completed line, as it stands behind DecodeFaxLine (:437) */
+    int32_t blk, off;                      /* the block of the push and i of :431, counted from behind the skip, at which it completed */
+    int32_t type, typecount, imageline, phasingLinesLeft, skip;
+    int32_t phasing_pos;                   /* FaxPhasingLinePosition of this line (:227), or -1 */
+    int32_t flags;                         /* KG_FAX_* */
+    int32_t phasingSkipData, ten_pct, ninety_pct;          /* under KG_FAX_MEDIAN: what :239 prints */
+} kg_fax_rec;
+typedef struct kg_fax_info {               /* FaxDecoder.h:72-137, what the port keeps of it; fax_t's capture and shift (fax.cpp:20-29) */
+    double nom, frac, frac_prev, ratio, fi, lineIncrFrac, lineIncrAcc, lineBlend, carrier, deviation;
+    int32_t lpm, imagewidth, bandwidth, include_headers, use_phasing, autostop, autostopped, debug, skip_header_detection, spl;
+    int32_t skip, samp_idx, lasttype, typecount, imageline, phasingLinesLeft, phasingSkipData, have_phasing, fir_current, started;
+    float Iprev, Qprev;
+    float fir[2][17];                      /* firfilter::buffer of the I and the Q filter, in the reference's circular layout */
+    int32_t phasingPos[40];
+    float shift; int32_t pad;
+} kg_fax_info;
+/* nconn FaxDecoder objects (FaxDecoder.cpp:51), each zeroed as the static array is; 1 .. 256 */
+int kg_fax_create(kg_ctx *ctx, int nconn, kg_fax **out);
+/* ~FaxDecoder (FaxDecoder.h:53); drains the context's stream first */
+void kg_fax_destroy(kg_fax *q);
+/* `SET fax_start` (fax.cpp:128-156): Configure (FaxDecoder.cpp:467-515) with reset, every parameter of it; nom_rate is snd_rate, srate
+ * what ext_update_get_sample_rateHz answers now (:92-97).  Iprev, Qprev, m_lineBlend, m_skip and m_SamplesPerSec_frac_prev are carried
+ * over, as the reference carries them.  One small launch. */
+int kg_fax_start(kg_fax *q, int conn, int lpm, int imagewidth, int carrier, int deviation, int bandwidth, int include_headers, int phasing, int autostop, int debug,
+                 double nom_rate, double srate);
+/* `SET fax_shift=%f` (fax.cpp:159-165): the next pushed block of a started connection takes it (FaxDecoder.cpp:416) */
+int kg_fax_set_shift(kg_fax *q, int conn, float shift);
+/* `SET fax_stop` (fax.cpp:167-171, fax_close :94-107): no more samples are taken, the pending shift is dropped; the decoder stays */
+int kg_fax_stop(kg_fax *q, int conn);
+/* The least max_lines a push of nblk[i] blocks of connection conns[i] needs (FaxDecoder.cpp:426-441: a block gives at most 1026 picks
+ * at a rate ratio of 1/2) and the widest imagewidth among the started ones.  Either may be NULL. */
+int kg_fax_max_lines(kg_fax *q, const int32_t *conns, int nconn, const int32_t *nblk, int32_t *max_lines, int32_t *max_width);
+/* ProcessSamples (FaxDecoder.cpp:410-447) as fax_task calls it (fax.cpp:85-88) for nblk[i] blocks (0 .. 256) of 512 samples of connection
+ * conns[i] (each at most once), on HOST arrays: block b of entry i is at s16 + i*stride + 512*b.  srate[i] is what
+ * ext_update_get_sample_rateHz answers for every line that completes in this push (:94).  A connection that is not started takes
+ * nothing and counts zeros.  Outputs as laid out above; row_stride >= imagewidth + 1.  ONE kernel launch.  Synchronises.  (The push on
+ * device-resident audio, enqueue only, is the receiver bank's: kg_rxbank_fax_* below.) */
+int kg_fax_push(kg_fax *q, const int32_t *conns, int nconn, const int32_t *nblk, const int16_t *s16, size_t stride, const double *srate, uint8_t *rows,
+                size_t row_stride, kg_fax_rec *recs, int max_lines, int32_t *counts);
+/* Connection conn's whole object (FaxDecoder.h:72-137), for tests: the scalars, m_samples and m_demod_data, the previous image line
+ * (zeros while m_imageline is 0) and m_outImage, KG_FAX_MAX_SPL entries each (any may be NULL).  Synchronises. */
+int kg_fax_state(kg_fax *q, int conn, kg_fax_info *info, int16_t *samples, uint8_t *demod, uint8_t *prev, uint8_t *out);
+
 /* Diagnostics: re-runs the 4096-point stage of the forward FFT of `block` in a
  * stamped build of the kernel and returns 4 s_memrealtime readings (100 MHz):
  * start, inputs + twiddles loaded, transform done, results stored. */
@@ -1590,6 +1657,30 @@ kg_lorc *kg_rxbank_lorc(kg_rxbank *bank);
 int kg_rxbank_lorc_map(kg_rxbank *bank, kg_lorc_row *row_map, int max_rows);
 /* the device buffer of the step's rows (e->scope, :50) and its size (NULL until the extension was named; read behind kg_rxbank_sync) */
 int kg_rxbank_lorc_rows(kg_rxbank *bank, uint8_t **d_rows, size_t *cap);
+
+/* The FAX extension of the bank's receivers (kg_fax above; extensions/FAX/FaxDecoder.cpp, fax.cpp).  The first of these calls makes the
+ * bank's kg_fax object and its output buffers, grows the step's arena slots by the size of the extension's table and drains the
+ * bank's streams; a bank that was never told holds nothing for the extension and enqueues exactly what it enqueued without it.  While
+ * a receiver is started and the step puts its blocks on the mono list -- the branch in which the reference advances real_wr_pos
+ * (rx_sound.cpp:701-703, :1103), so not in KG_POST_IQ, _SAS or _QAM --, the 16-bit audio of its sound blocks of that step feeds the
+ * extension in place: ONE launch per step over all such receivers, on the tail stream behind the detectors and ahead of the coders'
+ * event.  kg_rxbank_join and kg_rxbank_leave give the receiver a fresh object, not started.  The real-samples tap is another callback
+ * than the IQ tap (ext_users[rx].receive_real_tid): FAX runs beside a running IQ display or Loran-C. */
+/* `SET fax_start` (fax.cpp:128-156): kg_fax_start; srate stays the receiver's ext_update_get_sample_rateHz (FaxDecoder.cpp:94) until
+ * the next start.  A bank also refuses fewer than 1024 samples a line and an imagewidth above 4096 (they bound a step's outputs). */
+int kg_rxbank_fax_start(kg_rxbank *bank, int rx, int lpm, int imagewidth, int carrier, int deviation, int bandwidth, int include_headers, int phasing, int autostop,
+                        int debug, double nom_rate, double srate);
+/* `SET fax_shift=%f` (fax.cpp:159-165): kg_fax_set_shift */
+int kg_rxbank_fax_set_shift(kg_rxbank *bank, int rx, float shift);
+/* `SET fax_stop` (fax.cpp:167-171): kg_fax_stop */
+int kg_rxbank_fax_stop(kg_rxbank *bank, int rx);
+/* the object (NULL until one of the calls above), for kg_fax_state (FaxDecoder.h:72-137) */
+kg_fax *kg_rxbank_fax(kg_rxbank *bank);
+/* The outputs of the last step (FaxDecoder.cpp:404, :437), device memory laid out as kg_fax_push lays its outputs out (NULL until the
+ * extension was named; read behind kg_rxbank_sync): entry e is receiver rx_of_entry[e], in receiver order; a record's blk is the sound
+ * block of the step.  Any pointer may be NULL.  Returns the number of entries: the receivers the step fed. */
+int kg_rxbank_fax_out(kg_rxbank *bank, uint8_t **d_rows, size_t *row_stride, kg_fax_rec **d_recs, int32_t **d_counts, int32_t *max_lines, int32_t *rx_of_entry,
+                      int max_entries);
 /* CmdSetWFFreq + CmdSetWFDecim + the sampler mode sample_wf() decides on (rx/rx_waterfall.cpp:962-1008):
  *   overlapped == 0   CmdWFReset + the one-shot sampler every step: the non-overlapped frame (:1005-1041); needs
  *                     8192 * decim <= adc_samples_per_step
