@@ -77,11 +77,6 @@ struct bank_rx {
     char spec_on = 0;
     kg_spec::emit_t spec_mirror = {KG_SPEC_PASSBAND};
     uint32_t spec_cmds = 0;
-    char fx_on = 0;                             // the FFT extension's run != FUNC_OFF
-    char iq_on = 0;                             // the IQ display's `SET run=` (ext_register_receive_iq_samps)
-    char lo_on = 0;                             // Loran-C's `SET start` (the same registration: one of the two at most)
-    char fax_on = 0;                            // FAX's `SET fax_start` (ext_register_receive_real_samps_task: the OTHER tap)
-    double fax_rate = 0;                        // what ext_update_get_sample_rateHz answers for it: kg_rxbank_fax_start's srate
     bank_nb_cmd nbc = {};
     // the settings a join leaves alone
     int decim = 0; char overlapped = 0;         // kg_rxbank_set_wf
@@ -106,20 +101,6 @@ struct bank_plan {
     std::vector<int32_t> spec_rx, spec_inst, spec_blk, pb_inst, pb_n, pb_base;
     std::vector<int32_t> null_row;                      // [entry][blocks_max]: the channel-null row of a sound block, or -1
     std::vector<int32_t> null_each, null_inst;          // constants: 512 samples, KG_SPEC_CHAN_NULL
-    // the FFT extension's entries: receiver, blocks, instance, where the spectra lie in d_fxpost, the entry's first sound block
-    std::vector<int32_t> fx_list, fx_nblk, fx_inst, fx_row, fx_blk0, fx_nullpos;
-    // the IQ display's entries: receiver, blocks, instance (0), the receiver's row of d_firo; what the call hands back
-    std::vector<int32_t> iq_list, iq_nblk, iq_inst, iq_row, iq_sent;
-    std::vector<kg_iqd_row> iq_rows;
-    int iq_n;
-    // Loran-C's entries: receiver, blocks, the receiver's row of d_firo; what the call hands back
-    std::vector<int32_t> lo_list, lo_nblk, lo_row;
-    std::vector<kg_lorc_row> lo_rows;
-    int32_t lo_n;
-    // FAX's entries: receiver, blocks, where the receiver's row of d_s16 begins, its sample rate
-    std::vector<int32_t> fa_list, fa_nblk;
-    std::vector<int64_t> fa_off;
-    std::vector<double> fa_rate;
     // per sound block: list j of block blk is blk_chan[blk_at[BL_N * blk + j] .. blk_at[BL_N * blk + j + 1]); beside a BL_NULL
     // entry its row count and row
     std::vector<int32_t> blk_chan, blk_at, blk_null_n, blk_null_base;
@@ -134,9 +115,78 @@ struct bank_plan {
     std::vector<long> ring_w, ring_total;
     std::vector<kg_spec::emit_t> mirror; std::vector<uint32_t> cmds;
     // what the entry points hand back
-    std::vector<int32_t> got_nrec, got_nfir, pkt_bytes, fx_rx, fx_ent, fx_blk, fx_bin;
+    std::vector<int32_t> got_nrec, got_nfir, pkt_bytes;
     std::vector<int64_t> h_nw;
-    int fx_n;
+};
+
+// ---- the extensions: one record each, holding ALL the bank keeps for it.  A record's object and device buffers are made by the first
+// kg_rxbank_<ext>_* call (bank_<ext>_ensure): a bank that was never told holds nothing for the extension and enqueues what it always
+// did.  `on` is per receiver; `plan` is the step being made (the plan pass writes nothing else, the enqueue fills in what the entry
+// point hands back); `last` is the last step's maps, moved there by the commit.
+
+// The FFT extension (extensions/FFT/FFT.cpp; kg_fftext).  While a receiver's function is on, both filters store their filtered spectra
+// (receive_FFT(POST_FILTERED), fastfir.cpp:293-302) and the extension runs ONCE per step over the step's blocks, on the tail stream.
+struct bank_fx {
+    kg_fftext *obj; double rate;                        // rate: kg_rxbank_fftext_set_rate's, kept for an object made later
+    // d_post, in blocks of 1024 complex floats (the taps of a CFastFIR call lie by LIST ENTRY): [nrx][blocks_max] m_PassbandFIR's
+    // blocks of the step, entry i of the step's active list; then [blocks_max][nrx] m_chan_null_FIR's, entry p of sound block blk's list
+    kg_dbuf<float2> d_post; size_t stride;
+    kg_dbuf<unsigned char> d_rows; size_t max;          // [max][1024] u8: the step's rows in map order
+    std::vector<char> on;                               // run != FUNC_OFF
+    struct {
+        // the entries: receiver, blocks, instance, where the spectra lie in d_post, the entry's first sound block
+        std::vector<int32_t> list, nblk, inst, row, blk0;
+        std::vector<int32_t> nullpos;                   // per sound block: entries of its channel-null list so far
+        std::vector<int32_t> rx, ent, blk, bin; int n;  // handed back: the rows
+    } plan;
+    struct { std::vector<int32_t> rx, blk, bin; int n; } last;        // kg_rxbank_fftext_map
+};
+
+// The IQ display (extensions/IQ_display/iq_display.cpp; kg_iqd).  While a receiver has run on and is not in NBFM, its CFastFIR output
+// of the step (receive_iq_pre_agc, rx_sound.cpp:668-669) feeds it: ONE launch per step over all such receivers and their sound
+// blocks, on the tail stream.
+struct bank_iq {
+    kg_iqd *obj;
+    kg_dbuf<unsigned char> d_rows; size_t cap; int max_rows;          // the step's rows back to back: (512 B + 16384) * 4 bytes a receiver
+    kg_dbuf<kg_iqd_status> d_st;                                      // a record per (entry, sound block) of the step's call
+    std::vector<char> on;                               // `SET run=` (ext_register_receive_iq_samps)
+    struct {
+        std::vector<int32_t> list, nblk, inst, row;     // the entries: receiver, blocks, instance (0), the receiver's row of d_firo
+        std::vector<kg_iqd_row> rows; std::vector<int32_t> sent; int n;           // handed back
+    } plan;
+    struct { std::vector<kg_iqd_row> rows; std::vector<int32_t> blk_rx, blk_blk, sent; int n, nblk; } last;   // kg_rxbank_iqd_map, _iqd_status
+};
+
+// Loran-C (extensions/Loran_C/loran_c.cpp; kg_lorc); its first call also grows the arena slots by its table.  While a receiver is
+// started and not in NBFM, its CFastFIR output of the step feeds it in place: ONE launch per step over all such receivers, on the
+// tail stream where the IQ display's launch sits.
+struct bank_lo {
+    kg_lorc *obj;
+    kg_dbuf<unsigned char> d_rows; size_t cap; int max_rows;          // the step's rows, each at a multiple of 16 bytes
+    std::vector<char> on;                               // `SET start` (the IQ display's registration: one of the two at most)
+    struct {
+        std::vector<int32_t> list, nblk, row;           // the entries: receiver, blocks, the receiver's row of d_firo
+        std::vector<kg_lorc_row> rows; int32_t n;       // handed back
+    } plan;
+    struct { std::vector<kg_lorc_row> rows; int n; } last;            // kg_rxbank_lorc_map
+};
+
+// FAX (extensions/FAX/FaxDecoder.cpp; kg_fax); its first call also grows the arena slots by its table.  While a receiver is started
+// and its blocks go on the mono list (the branch in which the reference advances real_wr_pos, rx_sound.cpp:701-703, :1103: not IQ,
+// SAS or QAM), the step's d_s16 blocks feed it in place: ONE launch per step over all such receivers, on the tail stream behind
+// kg_post_process_dev and ahead of ev_tail.  The counts are the device's.
+struct bank_fa {
+    kg_fax *obj;
+    kg_dbuf<unsigned char> d_rows; size_t row_stride; int max_lines;  // [entry][max_lines][row_stride]
+    kg_dbuf<kg_fax_rec> d_recs;                                       // [entry][max_lines]
+    kg_dbuf<int32_t> d_counts;                                        // [entry][4]
+    std::vector<char> on;                               // `SET fax_start` (ext_register_receive_real_samps_task: the OTHER tap)
+    std::vector<double> rate;                           // what ext_update_get_sample_rateHz answers: kg_rxbank_fax_start's srate
+    struct {
+        // the entries: receiver, blocks, where the receiver's row of d_s16 begins, its sample rate
+        std::vector<int32_t> list, nblk; std::vector<int64_t> off; std::vector<double> rate;
+    } plan;
+    struct { std::vector<int32_t> rx; int n; } last;    // kg_rxbank_fax_out: the last step's entries and their receivers
 };
 
 struct kg_rxbank {
@@ -152,36 +202,7 @@ struct kg_rxbank {
     kg_ddc *ddc; kg_wf *wf; kg_rxddc *rx; kg_fir *fir; kg_post *post; kg_adpcm *adpcm;
     kg_nb *nb;                                  // m_NoiseProc_snd[] (the waterfall's blankers are kg_wf's)
     kg_fir *nullfir;                            // m_chan_null_FIR[] (rx_sound.cpp:151), on the tail stream behind kg_post
-    // the FFT extension (extensions/FFT/FFT.cpp; kg_fftext), made by the first kg_rxbank_fftext_* call: a bank that was never told holds
-    // nothing for it and enqueues what it always did.  While a receiver's function is on, both filters store their filtered spectra
-    // (receive_FFT(POST_FILTERED), fastfir.cpp:293-302) and the extension runs ONCE per step over the step's blocks, on the tail stream.
-    kg_fftext *fx; double fx_rate;
-    // the IQ display extension (extensions/IQ_display/iq_display.cpp; kg_iqd), made by the first kg_rxbank_iqd_* call.  While a receiver
-    // has run on and is not in NBFM, its CFastFIR output of the step (receive_iq_pre_agc, rx_sound.cpp:668-669) feeds it: ONE launch per
-    // step over all such receivers and their sound blocks, on the tail stream.
-    kg_iqd *iq;
-    kg_dbuf<unsigned char> d_iqrows; size_t iq_cap; int iq_max_rows;      // the step's rows back to back: (512 B + 16384) * 4 bytes a receiver
-    kg_dbuf<kg_iqd_status> d_iqst;                                        // a record per (entry, sound block) of the step's call
-    int iq_n, iq_nblk;
-    std::vector<kg_iqd_row> iq_rows;
-    std::vector<int32_t> iq_blk_rx, iq_blk_blk, iq_sent;
-    // the Loran-C extension (extensions/Loran_C/loran_c.cpp; kg_lorc), made by the first kg_rxbank_lorc_* call, which also grows the
-    // arena slots by its table.  While a receiver is started and not in NBFM, its CFastFIR output of the step feeds it in place: ONE
-    // launch per step over all such receivers, on the tail stream where the IQ display's launch sits.
-    kg_lorc *lo;
-    kg_dbuf<unsigned char> d_lorows; size_t lo_cap; int lo_max_rows;      // the step's rows, each at a multiple of 16 bytes
-    int lo_n;
-    std::vector<kg_lorc_row> lo_rows;
-    // the FAX extension (extensions/FAX/FaxDecoder.cpp; kg_fax), made by the first kg_rxbank_fax_* call, which also grows the arena
-    // slots by its table.  While a receiver is started and its blocks go on the mono list (the branch in which the reference advances
-    // real_wr_pos, rx_sound.cpp:701-703, :1103: not IQ, SAS or QAM), the step's d_s16 blocks feed it in place: ONE launch per step
-    // over all such receivers, on the tail stream behind kg_post_process_dev and ahead of ev_tail.  The counts are the device's.
-    kg_fax *fa;
-    kg_dbuf<unsigned char> d_farows; size_t fa_row_stride; int fa_max_lines;      // [entry][fa_max_lines][fa_row_stride]
-    kg_dbuf<kg_fax_rec> d_farecs;                                                 // [entry][fa_max_lines]
-    kg_dbuf<int32_t> d_facounts;                                                  // [entry][4]
-    int fa_n;                                                                     // the last step's entries
-    std::vector<int32_t> fa_rx;                                                   // their receivers
+    bank_fx fx; bank_iq iq; bank_lo lo; bank_fa fa;     // the extensions (above)
     // device buffers
     kg_dbuf<short2> d_wfiq; size_t wf_stride;         // [nrx][wf_stride] iq_t: a one-shot receiver uses pairs 0 .. 8191 of its row, an overlapped one all of it
     kg_dbuf<unsigned char> d_rows, d_pkts;         // [frame][1024], [frame][BANK_PKT_STRIDE]
@@ -190,16 +211,12 @@ struct kg_rxbank {
     kg_dbuf<short> d_s16; kg_dbuf<unsigned char> d_pay; // [nrx][firo_stride], [nrx][firo_stride / 2]
     kg_dbuf<float2> d_agc; kg_dbuf<unsigned char> d_iqpay; // [nrx][firo_stride] the AGC's complex output, [nrx][4 firo_stride] the IQ mode's payload
     kg_dbuf<unsigned char> d_spec; size_t spec_max;     // [spec_max][1024] u8: the step's rows in map order
-    // d_fxpost, in blocks of 1024 complex floats (the taps of a CFastFIR call lie by LIST ENTRY): [nrx][blocks_max] m_PassbandFIR's
-    // blocks of the step, entry i of the step's active list; then [blocks_max][nrx] m_chan_null_FIR's, entry p of sound block blk's list
-    kg_dbuf<float2> d_fxpost; size_t fx_stride;
-    kg_dbuf<unsigned char> d_fxrows; size_t fx_max;    // [fx_max][1024] u8: the step's rows in map order
     // the receivers, and the step being made
     std::vector<bank_rx> rcv;
     bank_plan plan;
-    // the last step's maps (kg_rxbank_spec_map, _fftext_map, _frame_map) and info
-    int spec_n, fx_n;
-    std::vector<int32_t> spec_rx, spec_inst, spec_blk, fx_rx, fx_blk, fx_bin, frame_rx, pkt_bytes;
+    // the last step's maps (kg_rxbank_spec_map, _frame_map) and info
+    int spec_n;
+    std::vector<int32_t> spec_rx, spec_inst, spec_blk, frame_rx, pkt_bytes;
     std::vector<uint64_t> frame_off;
     kg_rxbank_step_info last;
     // step tables: BANK_SLOTS pinned host / device slots
@@ -257,31 +274,329 @@ static int bank_drain(kg_rxbank *b, bool with_upload)
     return KG_OK;
 }
 
-// ---- plan: what the step is.  No HIP call, no table staged, no bank state written: only b->plan.
+// IS_STEREO (IQ, SAS, QAM): the blocks that go out as (s2_t) pairs and never onto the mono list
+static bool bank_stereo(int mode) { return mode == KG_POST_IQ || mode == KG_POST_SAS || mode == KG_POST_QAM; }
+
+// ---- the extensions' functions, the same set for each record:
+//   _sizes       at create: what the bank can hold for it, the host lists' capacity (a step allocates nothing)
+//   _ensure      the first call that names it: object and buffers, through bank_ext_ensure
+//   _fresh       a connection's end or beginning on one receiver
+//   _plan_clear, _plan    the step's lists: emptied, then entry i of the active list (receiver p.act[i], nblk sound blocks)
+//   _enqueue     its ONE launch of the step, on the tail stream; what the entry point hands back goes into the record's plan
+//   _commit      the plan's maps become the last step's
+// The general functions call the four by name, in the order fx, iq, lo, fa: that is the order of the launches on the tail stream
+// and of the tables in the slot.
+
+// A device buffer of a record: where its pointer goes, its size, its name in a refusal
+struct bank_want { void **p; size_t bytes; const char *what; };
+template <class T> static bank_want bank_buf(kg_dbuf<T> &d, size_t count, const char *what) { return bank_want{(void **) &d.p, sizeof(T) * count, what}; }
+
+// An extension's first use, made whole or not at all: the buffers zeroed, the arena slots grown by `table` bytes (0: as they are;
+// the growth is cumulative: slot_bytes + table, rounded to 64, BANK_SLOTS of them pinned and on the device), then `make`, which
+// creates the object and stores it in its record as its last act.  Everything is allocated into locals and changes hands by swap once
+// nothing can fail any more.  Drains the bank's streams, the upload's included: no step is in flight while the slots change.
+static int bank_ext_ensure(kg_rxbank *b, const char *who, std::initializer_list<bank_want> bufs, size_t table, int (*make)(kg_rxbank *))
+{
+    KG_HIP(hipSetDevice(b->device));
+    KG_TRY(bank_drain(b, true));
+    char slots[64];
+    snprintf(slots, sizeof slots, "%s: slots", who);
+    kg_hbuf<unsigned char> h;
+    kg_dbuf<unsigned char> d;
+    std::vector<kg_dbuf<unsigned char>> got(bufs.size());
+    const size_t grown = (b->slot_bytes + table + 63) & ~(size_t) 63;
+    if (table) {
+        KG_TRY(h.alloc(grown * BANK_SLOTS, slots));
+        KG_TRY(d.alloc(grown * BANK_SLOTS, slots));
+    }
+    size_t n = 0;
+    for (const bank_want &w : bufs) {
+        KG_TRY(got[n].alloc(w.bytes, w.what));
+        if (hipMemset(got[n++], 0, w.bytes) != hipSuccess) { kg_set_error("%s: hipMemset failed", who); return KG_ERR_HIP; }
+    }
+    KG_TRY(make(b));
+    n = 0;
+    for (const bank_want &w : bufs) { void *old = *w.p; *w.p = got[n].p; got[n++].p = (unsigned char *) old; }
+    if (table) { std::swap(b->h_slots.p, h.p); std::swap(b->d_slots.p, d.p); b->slot_bytes = grown; }      // the old slots go with h and d
+    return KG_OK;
+}
+
+static void bank_fx_sizes(kg_rxbank *b)
+{
+    bank_fx &x = b->fx;
+    x.stride = b->blocks_max * KG_FFTEXT_ROW; x.max = b->blocks_max * (size_t) b->nrx;        // a receiver's function takes ONE instance's blocks
+    x.on.assign((size_t) b->nrx, 0);
+    for (std::vector<int32_t> *v : {&x.plan.list, &x.plan.nblk, &x.plan.inst, &x.plan.row, &x.plan.blk0}) v->reserve(2 * x.max);
+    x.plan.nullpos.assign(b->blocks_max, 0);
+}
+
+static int bank_fx_ensure(kg_rxbank *b)
+{
+    bank_fx &x = b->fx;
+    if (x.obj) return KG_OK;
+    KG_TRY(bank_ext_ensure(b, "kg_rxbank_fftext",
+                           {bank_buf(x.d_post, 2 * (size_t) b->nrx * x.stride, "kg_rxbank_fftext: spectra"),
+                            bank_buf(x.d_rows, x.max * KG_FFTEXT_ROW, "kg_rxbank_fftext: rows")},
+                           0, [](kg_rxbank *b) {           // a rate set before the first use goes to the new object
+                               kg_fftext *fx = nullptr;
+                               int rc = kg_fftext_create(b->c_tail, b->nrx, &fx);
+                               if (rc == KG_OK && b->fx.rate > 0) rc = kg_fftext_set_rate(fx, b->fx.rate);
+                               if (rc == KG_OK) b->fx.obj = fx; else kg_fftext_destroy(fx);
+                               return rc;
+                           }));
+    for (std::vector<int32_t> *v : {&x.last.rx, &x.last.blk, &x.last.bin, &x.plan.rx, &x.plan.blk, &x.plan.bin, &x.plan.ent}) v->assign(x.max, 0);
+    return KG_OK;
+}
+
+// ext_unregister_receive_FFT_samps at the connection's end, its fft_t gone with it; a new one's: function off, nothing latched, sums zero
+static int bank_fx_fresh(kg_rxbank *b, int rx) { b->fx.on[rx] = 0; return b->fx.obj ? kg_fftext_restart(b->fx.obj, rx) : KG_OK; }
+
+static void bank_fx_plan_clear(kg_rxbank *b)
+{
+    bank_fx &x = b->fx;
+    for (std::vector<int32_t> *v : {&x.plan.list, &x.plan.nblk, &x.plan.inst, &x.plan.row, &x.plan.blk0}) v->clear();
+    std::fill(x.plan.nullpos.begin(), x.plan.nullpos.end(), 0);
+    x.plan.n = 0;
+}
+
+static void bank_fx_plan(kg_rxbank *b, int i, int nblk)
+{
+    bank_fx &x = b->fx;
+    const bank_plan &p = b->plan;
+    if (!x.obj) return;
+    const int k = p.act[i], NR = b->nrx;
+    auto put = [&x, k](int n, int inst, size_t row, int blk0) {
+        x.plan.list.push_back(k); x.plan.nblk.push_back(n); x.plan.inst.push_back(inst); x.plan.row.push_back((int32_t) row); x.plan.blk0.push_back(blk0);
+    };
+    if (x.on[k] && nblk > 0) put(nblk, KG_SPEC_PASSBAND, (size_t) i * b->blocks_max, 0);      // each filter hands every block of its own to fft_data, which takes one instance's
+    if (p.sam_null[i])                                     // where sound block blk's channel-null call leaves this receiver's spectrum
+        for (int blk = 0; blk < nblk; blk++) {
+            const int pos = x.plan.nullpos[blk]++;
+            if (x.on[k]) put(1, KG_SPEC_CHAN_NULL, (size_t) NR * b->blocks_max + (size_t) blk * NR + pos, blk);
+        }
+}
+
+// fft_data over the step's blocks: one launch, behind both filters
+static int bank_fx_enqueue(kg_rxbank *b)
+{
+    bank_fx &x = b->fx;
+    if (x.plan.list.empty()) return KG_OK;
+    const int rc = kg_fftext_process_rows_(x.obj, x.plan.list.data(), (int) x.plan.list.size(), x.plan.nblk.data(), x.plan.inst.data(), x.plan.row.data(),
+                                           (const float *) x.d_post.p, KG_FFTEXT_ROW, x.d_rows, KG_FFTEXT_ROW, (int) x.max, x.plan.rx.data(), x.plan.ent.data(),
+                                           x.plan.blk.data(), x.plan.bin.data());
+    if (rc < 0) return rc;
+    x.plan.n = rc;
+    return KG_OK;
+}
+
+static void bank_fx_commit(kg_rxbank *b)
+{
+    bank_fx &x = b->fx;
+    for (int r = 0; r < x.plan.n; r++) x.plan.blk[r] += x.plan.blk0[x.plan.ent[r]];       // the sound block of the step
+    x.last.n = x.plan.n;
+    x.last.rx.swap(x.plan.rx); x.last.blk.swap(x.plan.blk); x.last.bin.swap(x.plan.bin);
+}
+
+static void bank_iq_sizes(kg_rxbank *b)
+{
+    bank_iq &x = b->iq;
+    const size_t nrx = (size_t) b->nrx;
+    x.cap = nrx * (KG_FIR_OUT * b->blocks_max + KG_IQD_RING) * 4;
+    // a row per sample at points = 1; the map is the host's, so a large bank's is bounded (a step with more rows is refused)
+    const size_t rows = nrx * b->blocks_max * KG_FIR_OUT;
+    x.max_rows = (int) (rows < ((size_t) 1 << 18) ? rows : ((size_t) 1 << 18));
+    x.on.assign(nrx, 0);
+    for (std::vector<int32_t> *v : {&x.plan.list, &x.plan.nblk, &x.plan.inst, &x.plan.row}) v->reserve(nrx);
+}
+
+static int bank_iq_ensure(kg_rxbank *b)
+{
+    bank_iq &x = b->iq;
+    if (x.obj) return KG_OK;
+    const size_t nst = (size_t) b->nrx * b->blocks_max;
+    KG_TRY(bank_ext_ensure(b, "kg_rxbank_iqd", {bank_buf(x.d_rows, x.cap, "kg_rxbank_iqd: rows"), bank_buf(x.d_st, nst, "kg_rxbank_iqd: status")}, 0,
+                           [](kg_rxbank *b) { return kg_iqd_create(b->c_tail, b->nrx, &b->iq.obj); }));
+    for (std::vector<kg_iqd_row> *v : {&x.last.rows, &x.plan.rows}) v->assign((size_t) x.max_rows, kg_iqd_row{});
+    for (std::vector<int32_t> *v : {&x.last.sent, &x.plan.sent, &x.last.blk_rx, &x.last.blk_blk}) v->assign(nst, 0);
+    return KG_OK;
+}
+
+// iq_display_close: the object goes with the connection; a new connection's is a fresh one, not registered
+static int bank_iq_fresh(kg_rxbank *b, int rx) { b->iq.on[rx] = 0; return b->iq.obj ? kg_iqd_init(b->iq.obj, rx) : KG_OK; }
+
+static void bank_iq_plan_clear(kg_rxbank *b)
+{
+    bank_iq &x = b->iq;
+    for (std::vector<int32_t> *v : {&x.plan.list, &x.plan.nblk, &x.plan.inst, &x.plan.row}) v->clear();
+    x.plan.n = 0;
+}
+
+static void bank_iq_plan(kg_rxbank *b, int i, int nblk)
+{
+    bank_iq &x = b->iq;
+    const int k = b->plan.act[i];
+    if (!x.obj || !x.on[k] || nblk <= 0 || b->plan.mode[i] == KG_POST_NBFM) return;       // receive_iq_pre_agc is NULL while isNBFM (rx_sound.cpp:492)
+    x.plan.list.push_back(k); x.plan.nblk.push_back(nblk); x.plan.inst.push_back(0); x.plan.row.push_back(k);
+}
+
+// iq_display_data over the step's blocks: one launch, behind the filter, ahead of ev_tail
+static int bank_iq_enqueue(kg_rxbank *b)
+{
+    bank_iq &x = b->iq;
+    if (x.plan.list.empty()) return KG_OK;
+    const int rc = kg_iqd_process_rows_(x.obj, x.plan.list.data(), (int) x.plan.list.size(), x.plan.nblk.data(), x.plan.inst.data(), x.plan.row.data(), KG_FIR_OUT,
+                                        (const float *) b->d_firo.p, b->firo_stride, x.d_rows, x.cap, x.d_st, (size_t) b->nrx * b->blocks_max,
+                                        x.plan.rows.data(), x.max_rows, x.plan.sent.data());
+    if (rc < 0) return rc;
+    x.plan.n = rc;
+    return KG_OK;
+}
+
+static void bank_iq_commit(kg_rxbank *b)
+{
+    bank_iq &x = b->iq;
+    x.last.n = x.plan.n; x.last.nblk = 0;
+    if (!x.obj) return;
+    x.last.rows.swap(x.plan.rows); x.last.sent.swap(x.plan.sent);
+    for (size_t e = 0; e < x.plan.list.size(); e++)
+        for (int blk = 0; blk < x.plan.nblk[e]; blk++) { x.last.blk_rx[x.last.nblk] = x.plan.list[e]; x.last.blk_blk[x.last.nblk] = blk; x.last.nblk++; }
+}
+
+static void bank_lo_sizes(kg_rxbank *b)
+{
+    bank_lo &x = b->lo;
+    const size_t nrx = (size_t) b->nrx;
+    // a row per run at most: BANK_LO_RUNS rows of up to 1200 bytes per receiver and Loran channel
+    x.max_rows = (int) (nrx * 2 * BANK_LO_RUNS(b->blocks_max));
+    x.cap = (size_t) x.max_rows * 1200;
+    x.on.assign(nrx, 0);
+    for (std::vector<int32_t> *v : {&x.plan.list, &x.plan.nblk, &x.plan.row}) v->reserve(nrx);
+}
+
+static int bank_lo_ensure(kg_rxbank *b)
+{
+    bank_lo &x = b->lo;
+    if (x.obj) return KG_OK;
+    KG_TRY(bank_ext_ensure(b, "kg_rxbank_lorc", {bank_buf(x.d_rows, x.cap, "kg_rxbank_lorc: rows")},
+                           kg_lorc_table_bytes_((size_t) b->nrx, BANK_LO_RUNS(b->blocks_max)),
+                           [](kg_rxbank *b) { return kg_lorc_create(b->c_tail, b->nrx, &b->lo.obj); }));
+    for (std::vector<kg_lorc_row> *v : {&x.last.rows, &x.plan.rows}) v->assign((size_t) x.max_rows, kg_lorc_row{});
+    return KG_OK;
+}
+
+// the connection's end or beginning: loran_c[rx] as a new connection finds it -- stopped, waiting for its `SET ext_server_init`
+static int bank_lo_fresh(kg_rxbank *b, int rx) { b->lo.on[rx] = 0; return b->lo.obj ? kg_lorc_reset_(b->lo.obj, rx) : KG_OK; }
+
+static void bank_lo_plan_clear(kg_rxbank *b) { b->lo.plan.list.clear(); b->lo.plan.nblk.clear(); b->lo.plan.row.clear(); b->lo.plan.n = 0; }
+
+static void bank_lo_plan(kg_rxbank *b, int i, int nblk)
+{
+    bank_lo &x = b->lo;
+    const int k = b->plan.act[i];
+    if (!x.obj || !x.on[k] || nblk <= 0 || b->plan.mode[i] == KG_POST_NBFM) return;       // the IQ display's tap, and its NBFM rule
+    x.plan.list.push_back(k); x.plan.nblk.push_back(nblk); x.plan.row.push_back(k);
+}
+
+// loran_c_data over the step's blocks: one launch, reading d_firo in place
+static int bank_lo_enqueue(kg_rxbank *b)
+{
+    bank_lo &x = b->lo;
+    if (x.plan.list.empty()) return KG_OK;
+    return kg_lorc_process_rows_(x.obj, x.plan.list.data(), (int) x.plan.list.size(), x.plan.nblk.data(), x.plan.row.data(), KG_FIR_OUT, (const float *) b->d_firo.p,
+                                 b->firo_stride, x.d_rows, x.cap, x.plan.rows.data(), x.max_rows, &x.plan.n);
+}
+
+static void bank_lo_commit(kg_rxbank *b) { b->lo.last.n = b->lo.plan.n; if (b->lo.obj) b->lo.last.rows.swap(b->lo.plan.rows); }
+
+static void bank_fa_sizes(kg_rxbank *b)
+{
+    bank_fa &x = b->fa;
+    const size_t nrx = (size_t) b->nrx;
+    x.max_lines = (int) ((b->blocks_max * (2 * KG_FAX_BLK + 2) + BANK_FAX_MIN_SPL - 1) / BANK_FAX_MIN_SPL) + 1;
+    x.row_stride = (BANK_FAX_MAX_WIDTH + 1 + 15) & ~(size_t) 15;
+    x.on.assign(nrx, 0); x.rate.assign(nrx, 0.0);
+    for (std::vector<int32_t> *v : {&x.plan.list, &x.plan.nblk}) v->reserve(nrx);
+    x.plan.off.reserve(nrx); x.plan.rate.reserve(nrx);
+    x.last.rx.assign(nrx, -1);
+}
+
+static int bank_fa_ensure(kg_rxbank *b)
+{
+    bank_fa &x = b->fa;
+    if (x.obj) return KG_OK;
+    const size_t nrows = (size_t) b->nrx * (size_t) x.max_lines;
+    return bank_ext_ensure(b, "kg_rxbank_fax",
+                           {bank_buf(x.d_rows, nrows * x.row_stride, "kg_rxbank_fax: rows"), bank_buf(x.d_recs, nrows, "kg_rxbank_fax: records"),
+                            bank_buf(x.d_counts, (size_t) 4 * b->nrx, "kg_rxbank_fax: counts")},
+                           kg_fax_table_bytes_((size_t) b->nrx), [](kg_rxbank *b) { return kg_fax_create(b->c_tail, b->nrx, &b->fa.obj); });
+}
+
+// the connection's end or beginning: m_FaxDecoder[rx] and fax[rx] as a new connection finds them -- zeroed, no task
+static int bank_fa_fresh(kg_rxbank *b, int rx) { b->fa.on[rx] = 0; b->fa.rate[rx] = 0; return b->fa.obj ? kg_fax_reset_(b->fa.obj, rx) : KG_OK; }
+
+static void bank_fa_plan_clear(kg_rxbank *b) { b->fa.plan.list.clear(); b->fa.plan.nblk.clear(); b->fa.plan.off.clear(); b->fa.plan.rate.clear(); }
+
+static void bank_fa_plan(kg_rxbank *b, int i, int nblk)
+{
+    bank_fa &x = b->fa;
+    const int k = b->plan.act[i];
+    if (!x.obj || !x.on[k] || nblk <= 0 || bank_stereo(b->plan.mode[i])) return;      // real_wr_pos advances for the mono blocks alone: fax_task sees no other
+    x.plan.list.push_back(k); x.plan.nblk.push_back(nblk); x.plan.off.push_back((int64_t) ((size_t) k * b->firo_stride)); x.plan.rate.push_back(x.rate[k]);
+}
+
+// ProcessSamples over the step's blocks: one launch, reading d_s16 in place
+static int bank_fa_enqueue(kg_rxbank *b)
+{
+    bank_fa &x = b->fa;
+    if (x.plan.list.empty()) return KG_OK;
+    return kg_fax_push_at_(x.obj, x.plan.list.data(), (int) x.plan.list.size(), x.plan.nblk.data(), x.plan.off.data(), (const int16_t *) b->d_s16.p, b->firo_stride,
+                           x.plan.rate.data(), x.d_rows, x.row_stride, x.d_recs, x.max_lines, x.d_counts);
+}
+
+static void bank_fa_commit(kg_rxbank *b)
+{
+    bank_fa &x = b->fa;
+    x.last.n = (int) x.plan.list.size();
+    for (int e = 0; e < x.last.n; e++) x.last.rx[e] = x.plan.list[e];
+}
+
+// a connection ends or begins on receiver rx: every extension as a new connection finds it
+static int bank_ext_fresh(kg_rxbank *b, int rx)
+{
+    KG_TRY(bank_fx_fresh(b, rx));
+    KG_TRY(bank_iq_fresh(b, rx));
+    KG_TRY(bank_lo_fresh(b, rx));
+    return bank_fa_fresh(b, rx);
+}
+
+// The IQ tap (ext_users[rx].receive_iq_pre_agc) holds one callback, the IQ display's or Loran-C's: whoever asks for it is refused while
+// the other has it
+static int bank_tap_free(const kg_rxbank *b, int rx, const char *who, bool lorc_asks)
+{
+    KG_REQUIRE(!(lorc_asks ? b->iq.on[rx] : b->lo.on[rx]), KG_ERR_STATE, "%s: receiver %d has %s; the tap holds one callback", who, rx,
+               lorc_asks ? "the IQ display running" : "Loran-C started");
+    return KG_OK;
+}
+
+// the prologue of an extension's per-receiver entry point: the receiver exists, the extension is made
+#define BANK_EXT(who, ensure)                          \
+    KG_TRY(bank_rx_check(b, rx, who));                 \
+    KG_TRY(ensure(b))
+
+// ---- plan: what the step is.  No HIP call, no table staged, no bank state written: only b->plan and the records' plan halves.
 
 // Entry i's rows: which of its nblk sound blocks give an audio spectrum row -- the reference's rule (kg_spec.h), walked on a copy of
-// the mirror that the commit stores; rows are numbered in emission order -- and what the FFT extension takes from it.
+// the mirror that the commit stores; rows are numbered in emission order -- and what each extension takes from it.
 static void bank_plan_rows(kg_rxbank *b, int i, int nblk)
 {
     bank_plan &p = b->plan;
-    const int k = p.act[i], NR = b->nrx;
+    const int k = p.act[i];
     const bank_rx &r = b->rcv[k];
     const bool sam_family = p.mode[i] >= KG_POST_SAM && p.mode[i] <= KG_POST_QAM;
     kg_spec::emit_t m = r.spec_mirror;
     p.cmds[i] = kg_post_mode_cmds_(b->post, k);
     if (p.cmds[i] != r.spec_cmds) kg_spec::emit_clear(m);
     p.pb_n[i] = 0; p.pb_base[i] = 0;
-    if (b->fx && r.fx_on && nblk > 0) {                // each filter hands every block of its own to fft_data, which takes one instance's
-        p.fx_list.push_back(k); p.fx_nblk.push_back(nblk); p.fx_inst.push_back(KG_SPEC_PASSBAND);
-        p.fx_row.push_back((int32_t) ((size_t) i * b->blocks_max)); p.fx_blk0.push_back(0);
-    }
-    if (b->fx && p.sam_null[i])                        // where sound block blk's channel-null call leaves this receiver's spectrum
-        for (int blk = 0; blk < nblk; blk++) {
-            const int pos = p.fx_nullpos[blk]++;
-            if (!r.fx_on) continue;
-            p.fx_list.push_back(k); p.fx_nblk.push_back(1); p.fx_inst.push_back(KG_SPEC_CHAN_NULL);
-            p.fx_row.push_back((int32_t) ((size_t) NR * b->blocks_max + (size_t) blk * NR + pos)); p.fx_blk0.push_back(blk);
-        }
     for (int blk = 0; blk < nblk; blk++) {
         const kg_spec::rows_t rows = kg_spec::emit_block(m, r.spec_on != 0, sam_family, p.sam_null[i] != 0);
         if (rows.passband) {                           // only ever the leading blocks: the mirror leaves PASSBAND once per step at most
@@ -293,14 +608,10 @@ static void bank_plan_rows(kg_rxbank *b, int i, int nblk)
         if (rows.chan_null) { p.spec_rx[p.nspec] = k; p.spec_inst[p.nspec] = KG_SPEC_CHAN_NULL; p.spec_blk[p.nspec] = blk; p.nspec++; }
     }
     p.mirror[i] = m;
-    if (b->iq && r.iq_on && nblk > 0 && p.mode[i] != KG_POST_NBFM) {      // receive_iq_pre_agc is NULL while isNBFM (rx_sound.cpp:492)
-        p.iq_list.push_back(k); p.iq_nblk.push_back(nblk); p.iq_inst.push_back(0); p.iq_row.push_back(k);
-    }
-    if (b->lo && r.lo_on && nblk > 0 && p.mode[i] != KG_POST_NBFM) { p.lo_list.push_back(k); p.lo_nblk.push_back(nblk); p.lo_row.push_back(k); }
-    const bool stereo = p.mode[i] == KG_POST_IQ || p.mode[i] == KG_POST_SAS || p.mode[i] == KG_POST_QAM;      // the BL_REAL rule of bank_plan_blocks
-    if (b->fa && r.fax_on && nblk > 0 && !stereo) {        // real_wr_pos advances for the mono blocks alone: fax_task sees no other
-        p.fa_list.push_back(k); p.fa_nblk.push_back(nblk); p.fa_off.push_back((int64_t) ((size_t) k * b->firo_stride)); p.fa_rate.push_back(r.fax_rate);
-    }
+    bank_fx_plan(b, i, nblk);
+    bank_iq_plan(b, i, nblk);
+    bank_lo_plan(b, i, nblk);
+    bank_fa_plan(b, i, nblk);
 }
 
 // The active list and, per entry, the counts its audio DDC and its CFastFIR will hand back (kg_rxddc_outputs is kg_rxddc_push_dev's
@@ -309,14 +620,13 @@ static void bank_plan_rows(kg_rxbank *b, int i, int nblk)
 static void bank_plan_audio(kg_rxbank *b)
 {
     bank_plan &p = b->plan;
-    for (std::vector<int32_t> *v : {&p.act, &p.nb_list, &p.nb_cnt, &p.fx_list, &p.fx_nblk, &p.fx_inst, &p.fx_row, &p.fx_blk0, &p.iq_list, &p.iq_nblk, &p.iq_inst,
-                                    &p.iq_row, &p.lo_list, &p.lo_nblk, &p.lo_row, &p.fa_list, &p.fa_nblk})
-        v->clear();
-    p.fa_off.clear(); p.fa_rate.clear();
-    std::fill(p.fx_nullpos.begin(), p.fx_nullpos.end(), 0);
-    p.nrec_max = p.nfir_max = p.nspec = p.fx_n = p.iq_n = 0;
-    p.lo_n = 0;
+    for (std::vector<int32_t> *v : {&p.act, &p.nb_list, &p.nb_cnt}) v->clear();
+    p.nrec_max = p.nfir_max = p.nspec = 0;
     p.any_pb = false;
+    bank_fx_plan_clear(b);
+    bank_iq_plan_clear(b);
+    bank_lo_plan_clear(b);
+    bank_fa_plan_clear(b);
     for (int k = 0; k < b->nrx; k++) {
         const bank_rx &r = b->rcv[k];
         p.enabled[k] = r.active ? 1 : 0;
@@ -352,7 +662,7 @@ static void bank_plan_blocks(kg_rxbank *b)
             for (int i = 0; i < NA; i++) {
                 if (p.nfir[i] < (blk + 1) * KG_FIR_OUT) continue;
                 const int k = p.act[i], m = p.mode[i], row = p.null_row[(size_t) i * b->blocks_max + blk];
-                const bool stereo = m == KG_POST_IQ || m == KG_POST_SAS || m == KG_POST_QAM, le = b->rcv[k].little_endian != 0;
+                const bool stereo = bank_stereo(m), le = b->rcv[k].little_endian != 0;
                 if (j == BL_POST || (j == BL_REAL && !stereo) || (j == BL_IQ_BE && stereo && !le) || (j == BL_IQ_LE && stereo && le)) put(k, 0, 0);
                 if (j == BL_NULL && p.sam_null[i]) put(k, row >= 0 ? 1 : 0, row >= 0 ? row : 0);
             }
@@ -464,9 +774,9 @@ static int bank_audio_front(kg_rxbank *b, const void *d_adc)
     tk.lap(b, PF_EVENTS, real);
     const kg_fir_spec_req req = {b->d_spec, KG_SPEC_ROW, b->spec_max * KG_SPEC_ROW, p.pb_inst.data(), p.pb_n.data(), p.pb_base.data()};
     int rc;
-    if (!p.fx_list.empty())
+    if (!b->fx.plan.list.empty())                          // the FFT extension's entries: the filter stores its spectra for them, by list entry
         rc = kg_fir_process_post_(b->fir, act, NA, b->d_xin, b->nrec_max, p.nrec.data(), b->d_firo, b->firo_stride, p.got_nfir.data(),
-                                  p.any_pb ? &req : nullptr, b->d_fxpost, b->fx_stride);
+                                  p.any_pb ? &req : nullptr, b->fx.d_post, b->fx.stride);
     else if (p.any_pb)
         rc = kg_fir_process_rows_(b->fir, act, NA, b->d_xin, b->nrec_max, p.nrec.data(), b->d_firo, b->firo_stride, p.got_nfir.data(), &req);
     else
@@ -477,12 +787,12 @@ static int bank_audio_front(kg_rxbank *b, const void *d_adc)
     return KG_OK;
 }
 
-// the tail stream, per sound block: S-meter, CAgc, detector; the channel-null filter; the coders.  Then the FFT extension and the IQ display.
+// the tail stream, per sound block: S-meter, CAgc, detector; the channel-null filter; the coders.  Then the extensions' launches, ahead of ev_tail.
 static int bank_audio_tail(kg_rxbank *b)
 {
     bank_plan &p = b->plan;
     if (p.nfir_max == 0) return KG_OK;
-    const bool real = bank_real(b), fx = !p.fx_list.empty();
+    const bool real = bank_real(b), fx = !b->fx.plan.list.empty();
     const size_t NR = (size_t) b->nrx;
     bank_tick tk;
     KG_TRY(bank_edge(real, b->ev_fir, b->s_side, b->s_tail));
@@ -498,7 +808,7 @@ static int bank_audio_tail(kg_rxbank *b)
                                          p.blk_null_base.data() + at};
             if (fx)
                 KG_TRY(kg_fir_process_post_(b->nullfir, chan + at, NN, b->d_agc + o, b->firo_stride, p.null_each.data(), nullptr, 0, nullptr, &req,
-                                            b->d_fxpost + (NR * b->blocks_max + (size_t) blk * NR) * KG_FFTEXT_ROW, KG_FFTEXT_ROW));
+                                            b->fx.d_post + (NR * b->blocks_max + (size_t) blk * NR) * KG_FFTEXT_ROW, KG_FFTEXT_ROW));
             else
                 KG_TRY(kg_fir_process_rows_(b->nullfir, chan + at, NN, b->d_agc + o, b->firo_stride, p.null_each.data(), nullptr, 0, nullptr, &req));
         }
@@ -512,26 +822,10 @@ static int bank_audio_tail(kg_rxbank *b)
                                              b->d_iqpay + 4 * o, 4 * b->firo_stride));
         tk.lap(b, PF_ADPCM, real);
     }
-    if (fx) {                                              // fft_data over the step's blocks: one launch, behind both filters
-        const int rc = kg_fftext_process_rows_(b->fx, p.fx_list.data(), (int) p.fx_list.size(), p.fx_nblk.data(), p.fx_inst.data(), p.fx_row.data(),
-                                               (const float *) b->d_fxpost.p, KG_FFTEXT_ROW, b->d_fxrows, KG_FFTEXT_ROW, (int) b->fx_max,
-                                               p.fx_rx.data(), p.fx_ent.data(), p.fx_blk.data(), p.fx_bin.data());
-        if (rc < 0) return rc;
-        p.fx_n = rc;
-    }
-    if (!p.iq_list.empty()) {                              // iq_display_data over the step's blocks: one launch, behind the filter, ahead of ev_tail
-        const int rc = kg_iqd_process_rows_(b->iq, p.iq_list.data(), (int) p.iq_list.size(), p.iq_nblk.data(), p.iq_inst.data(), p.iq_row.data(), KG_FIR_OUT,
-                                            (const float *) b->d_firo.p, b->firo_stride, b->d_iqrows, b->iq_cap, b->d_iqst, NR * b->blocks_max,
-                                            p.iq_rows.data(), b->iq_max_rows, p.iq_sent.data());
-        if (rc < 0) return rc;
-        p.iq_n = rc;
-    }
-    if (!p.lo_list.empty())                                // loran_c_data over the step's blocks: one launch, reading d_firo in place
-        KG_TRY(kg_lorc_process_rows_(b->lo, p.lo_list.data(), (int) p.lo_list.size(), p.lo_nblk.data(), p.lo_row.data(), KG_FIR_OUT, (const float *) b->d_firo.p,
-                                     b->firo_stride, b->d_lorows, b->lo_cap, p.lo_rows.data(), b->lo_max_rows, &p.lo_n));
-    if (!p.fa_list.empty())                                // ProcessSamples over the step's blocks: one launch, reading d_s16 in place
-        KG_TRY(kg_fax_push_at_(b->fa, p.fa_list.data(), (int) p.fa_list.size(), p.fa_nblk.data(), p.fa_off.data(), (const int16_t *) b->d_s16.p, b->firo_stride,
-                               p.fa_rate.data(), b->d_farows, b->fa_row_stride, b->d_farecs, b->fa_max_lines, b->d_facounts));
+    KG_TRY(bank_fx_enqueue(b));
+    KG_TRY(bank_iq_enqueue(b));
+    KG_TRY(bank_lo_enqueue(b));
+    KG_TRY(bank_fa_enqueue(b));
     KG_TRY(bank_edge(real, b->ev_tail, b->s_tail, nullptr, &b->tail_pending));
     tk.lap(b, PF_EVENTS, real);
     return KG_OK;
@@ -588,20 +882,12 @@ static void bank_commit(kg_rxbank *b)
         r.last_nrec = p.nrec[i]; r.last_nfir = p.nfir[i];
         r.snd_seq += (uint32_t) (p.nfir[i] / KG_FIR_OUT);
     }
-    for (int r = 0; r < p.fx_n; r++) p.fx_blk[r] += p.fx_blk0[p.fx_ent[r]];      // the sound block of the step
-    b->spec_n = p.nspec; b->fx_n = p.fx_n;
-    b->iq_n = p.iq_n; b->iq_nblk = 0;
-    if (b->iq) {
-        b->iq_rows.swap(p.iq_rows); b->iq_sent.swap(p.iq_sent);
-        for (size_t e = 0; e < p.iq_list.size(); e++)
-            for (int blk = 0; blk < p.iq_nblk[e]; blk++) { b->iq_blk_rx[b->iq_nblk] = p.iq_list[e]; b->iq_blk_blk[b->iq_nblk] = blk; b->iq_nblk++; }
-    }
-    b->lo_n = p.lo_n;
-    if (b->lo) b->lo_rows.swap(p.lo_rows);
-    b->fa_n = (int) p.fa_list.size();
-    for (int e = 0; e < b->fa_n; e++) b->fa_rx[e] = p.fa_list[e];
+    b->spec_n = p.nspec;
     b->spec_rx.swap(p.spec_rx); b->spec_inst.swap(p.spec_inst); b->spec_blk.swap(p.spec_blk);
-    b->fx_rx.swap(p.fx_rx); b->fx_blk.swap(p.fx_blk); b->fx_bin.swap(p.fx_bin);
+    bank_fx_commit(b);
+    bank_iq_commit(b);
+    bank_lo_commit(b);
+    bank_fa_commit(b);
     b->frame_rx.swap(p.chan_of); b->frame_off.swap(p.frame_off); b->pkt_bytes.swap(p.pkt_bytes);
 }
 
@@ -792,18 +1078,15 @@ static void bank_plan_init(bank_plan &p, size_t nrx, size_t blocks_max, size_t s
     for (std::vector<int32_t> *v : {&p.nrec, &p.nfir, &p.mode, &p.pb_n, &p.pb_base, &p.chan_of, &p.got_nrec, &p.got_nfir, &p.pkt_bytes}) v->assign(nrx, 0);
     for (std::vector<int32_t> *v : {&p.spec_rx, &p.spec_inst, &p.spec_blk}) v->assign(spec_max, 0);
     for (std::vector<int32_t> *v : {&p.act, &p.nb_list, &p.nb_cnt}) v->reserve(nrx);
-    for (std::vector<int32_t> *v : {&p.fx_list, &p.fx_nblk, &p.fx_inst, &p.fx_row, &p.fx_blk0}) v->reserve(2 * nrx * blocks_max);
-    for (std::vector<int32_t> *v : {&p.iq_list, &p.iq_nblk, &p.iq_inst, &p.iq_row, &p.lo_list, &p.lo_nblk, &p.lo_row, &p.fa_list, &p.fa_nblk}) v->reserve(nrx);
-    p.fa_off.reserve(nrx); p.fa_rate.reserve(nrx);
     for (std::vector<int32_t> *v : {&p.blk_chan, &p.blk_null_n, &p.blk_null_base}) v->reserve(3 * nrx * blocks_max);
     p.blk_at.reserve(BL_N * blocks_max + 1);
     p.pb_inst.assign(nrx, KG_SPEC_PASSBAND); p.null_inst.assign(nrx, KG_SPEC_CHAN_NULL); p.null_each.assign(nrx, KG_FIR_OUT);
-    p.null_row.assign(blocks_max * nrx, -1); p.fx_nullpos.assign(blocks_max, 0);
+    p.null_row.assign(blocks_max * nrx, -1);
     p.enabled.assign(nrx, 1); p.sam_null.assign(nrx, 0);
     p.moves.reserve(nrx); p.out_off.assign(nrx, 0); p.max_out.assign(nrx, 0); p.h_nw.assign(nrx, 0);
     p.frame_off.assign(nrx, 0); p.pkt_step.resize(nrx);
     p.ring_w.assign(nrx, 0); p.ring_total.assign(nrx, 0); p.mirror.assign(nrx, kg_spec::emit_t{KG_SPEC_PASSBAND}); p.cmds.assign(nrx, 0);
-    p.nrec_max = p.nfir_max = p.nspec = p.nframes = p.fx_n = p.iq_n = 0; p.lo_n = 0; p.wf_unset = -1; p.any_pb = false;
+    p.nrec_max = p.nfir_max = p.nspec = p.nframes = 0; p.wf_unset = -1; p.any_pb = false;
 }
 
 static int bank_init(kg_rxbank *b)
@@ -845,25 +1128,13 @@ static int bank_init(kg_rxbank *b)
     b->tail_pending = b->pk_pending = false; b->step = 0;
     b->c_main->rows_by_chan = b->c_side->rows_by_chan = b->c_tail->rows_by_chan = 1;      // buffers hold one row per RECEIVER
     KG_TRY(bank_zalloc(b->d_spec, b->spec_max * KG_SPEC_ROW, "kg_rxbank_create: spec"));
-    b->fx = nullptr; b->fx_rate = 0;
-    b->fx_stride = b->blocks_max * KG_FFTEXT_ROW; b->fx_max = b->blocks_max * (size_t) nrx;      // a receiver's function takes ONE instance's blocks
     b->rcv.assign(nrx, bank_rx{});
     bank_plan_init(b->plan, (size_t) nrx, b->blocks_max, b->spec_max);
-    b->spec_n = b->fx_n = 0;
-    b->iq = nullptr; b->iq_n = b->iq_nblk = 0;
-    b->iq_cap = (size_t) nrx * (KG_FIR_OUT * b->blocks_max + KG_IQD_RING) * 4;
-    {   // a row per sample at points = 1; the map is the host's, so a large bank's is bounded (a step with more rows is refused)
-        const size_t rows = (size_t) nrx * b->blocks_max * KG_FIR_OUT;
-        b->iq_max_rows = (int) (rows < ((size_t) 1 << 18) ? rows : ((size_t) 1 << 18));
-    }
-    b->lo = nullptr; b->lo_n = 0;
-    // a row per run at most: BANK_LO_RUNS rows of up to 1200 bytes per receiver and Loran channel
-    b->lo_max_rows = (int) ((size_t) nrx * 2 * BANK_LO_RUNS(b->blocks_max));
-    b->lo_cap = (size_t) b->lo_max_rows * 1200;
-    b->fa = nullptr; b->fa_n = 0;
-    b->fa_max_lines = (int) ((b->blocks_max * (2 * KG_FAX_BLK + 2) + BANK_FAX_MIN_SPL - 1) / BANK_FAX_MIN_SPL) + 1;
-    b->fa_row_stride = (BANK_FAX_MAX_WIDTH + 1 + 15) & ~(size_t) 15;
-    b->fa_rx.assign(nrx, -1);
+    b->spec_n = 0;
+    bank_fx_sizes(b);
+    bank_iq_sizes(b);
+    bank_lo_sizes(b);
+    bank_fa_sizes(b);
     for (std::vector<int32_t> *v : {&b->spec_rx, &b->spec_inst, &b->spec_blk}) v->assign(b->spec_max, 0);
     b->frame_rx.assign(nrx, -1); b->pkt_bytes.assign(nrx, 0); b->frame_off.assign(nrx, 0);
     memset(&b->arena, 0, sizeof b->arena);
@@ -880,10 +1151,10 @@ void kg_rxbank_destroy(kg_rxbank *b)
     (void) hipSetDevice(b->device);
     for (hipStream_t s : {b->s_main, b->s_side, b->s_tail, b->s_ddc_side, b->s_up}) if (s) (void) hipStreamSynchronize(s);
     if (b->c_main && b->c_side && b->c_tail) bank_set_arena(b, KG_ARENA_OFF);
-    kg_fftext_destroy(b->fx);
-    kg_iqd_destroy(b->iq);
-    kg_lorc_destroy(b->lo);
-    kg_fax_destroy(b->fa);
+    kg_fftext_destroy(b->fx.obj);
+    kg_iqd_destroy(b->iq.obj);
+    kg_lorc_destroy(b->lo.obj);
+    kg_fax_destroy(b->fa.obj);
     kg_adpcm_destroy(b->adpcm); kg_post_destroy(b->post); kg_fir_destroy(b->nullfir); kg_fir_destroy(b->fir); kg_rxddc_destroy(b->rx); kg_nb_destroy(b->nb);
     kg_wf_destroy(b->wf); kg_ddc_destroy(b->ddc);
     kg_ctx_destroy(b->c_tail); kg_ctx_destroy(b->c_side); kg_ctx_destroy(b->c_main);
@@ -970,35 +1241,12 @@ int kg_rxbank_spec_rows(kg_rxbank *b, void **d_rows, size_t *row_stride)
     return KG_OK;
 }
 
-// The extension's object and buffers, made whole or not at all by the first call that names the extension.  Drains the bank's streams.
-static int bank_fx_ensure(kg_rxbank *b)
-{
-    if (b->fx) return KG_OK;
-    KG_HIP(hipSetDevice(b->device));
-    KG_TRY(bank_drain(b, true));
-    kg_fftext *fx = nullptr;
-    int rc = kg_fftext_create(b->c_tail, b->nrx, &fx);
-    if (rc == KG_OK) rc = b->d_fxpost.alloc(2 * (size_t) b->nrx * b->fx_stride, "kg_rxbank_fftext: spectra");
-    if (rc == KG_OK) rc = b->d_fxrows.alloc(b->fx_max * KG_FFTEXT_ROW, "kg_rxbank_fftext: rows");
-    if (rc == KG_OK && (hipMemset(b->d_fxpost, 0, sizeof(float2) * 2 * (size_t) b->nrx * b->fx_stride) != hipSuccess ||
-                        hipMemset(b->d_fxrows, 0, b->fx_max * KG_FFTEXT_ROW) != hipSuccess)) {
-        kg_set_error("kg_rxbank_fftext: hipMemset failed");
-        rc = KG_ERR_HIP;
-    }
-    if (rc == KG_OK && b->fx_rate > 0) rc = kg_fftext_set_rate(fx, b->fx_rate);
-    if (rc) { kg_fftext_destroy(fx); b->d_fxpost.reset(); b->d_fxrows.reset(); return rc; }
-    bank_plan &p = b->plan;
-    for (std::vector<int32_t> *v : {&b->fx_rx, &b->fx_blk, &b->fx_bin, &p.fx_rx, &p.fx_blk, &p.fx_bin, &p.fx_ent}) v->assign(b->fx_max, 0);
-    b->fx = fx;
-    return KG_OK;
-}
-
 int kg_rxbank_fftext_set_rate(kg_rxbank *b, double sample_rate)
 {
     KG_REQUIRE(b != nullptr, KG_ERR_INVALID, "kg_rxbank_fftext_set_rate: null argument");
     KG_REQUIRE(sample_rate > 0 && sample_rate <= 1e12, KG_ERR_INVALID, "kg_rxbank_fftext_set_rate: sample rate %g", sample_rate);
-    if (b->fx) KG_TRY(kg_fftext_set_rate(b->fx, sample_rate));
-    b->fx_rate = sample_rate;
+    if (b->fx.obj) KG_TRY(kg_fftext_set_rate(b->fx.obj, sample_rate));
+    b->fx.rate = sample_rate;
     return KG_OK;
 }
 
@@ -1006,295 +1254,176 @@ int kg_rxbank_fftext_set_rate(kg_rxbank *b, double sample_rate)
 int kg_rxbank_fftext_set_run(kg_rxbank *b, int rx, int run)
 {
     KG_TRY(bank_rx_check(b, rx, "kg_rxbank_fftext_set_run"));
-    KG_REQUIRE(run >= KG_FFTEXT_OFF && run <= KG_FFTEXT_INTEG, KG_ERR_INVALID, "kg_rxbank_fftext_set_run: run %d (-1..2)", run);
+    KG_REQUIRE(run >= KG_FFTEXT_OFF && run <= KG_FFTEXT_INTEG, KG_ERR_INVALID, "kg_rxbank_fftext_set_run: run %d (-1..2)", run);      // (refused before anything is made)
     KG_TRY(bank_fx_ensure(b));
     const int mode = kg_post_get_mode(b->post, rx);
-    KG_TRY(kg_fftext_set_run(b->fx, rx, run, mode >= KG_POST_SAM && mode <= KG_POST_QAM, mode == KG_POST_QAM));
-    b->rcv[rx].fx_on = run != KG_FFTEXT_OFF;
+    KG_TRY(kg_fftext_set_run(b->fx.obj, rx, run, mode >= KG_POST_SAM && mode <= KG_POST_QAM, mode == KG_POST_QAM));
+    b->fx.on[rx] = run != KG_FFTEXT_OFF;
     return KG_OK;
 }
 
-int kg_rxbank_fftext_set_itime(kg_rxbank *b, int rx, double itime)
-{
-    KG_TRY(bank_rx_check(b, rx, "kg_rxbank_fftext_set_itime"));
-    KG_TRY(bank_fx_ensure(b));
-    return kg_fftext_set_itime(b->fx, rx, itime);
-}
+int kg_rxbank_fftext_set_itime(kg_rxbank *b, int rx, double itime) { BANK_EXT("kg_rxbank_fftext_set_itime", bank_fx_ensure); return kg_fftext_set_itime(b->fx.obj, rx, itime); }
+int kg_rxbank_fftext_clear(kg_rxbank *b, int rx) { BANK_EXT("kg_rxbank_fftext_clear", bank_fx_ensure); return kg_fftext_clear(b->fx.obj, rx); }
 
-int kg_rxbank_fftext_clear(kg_rxbank *b, int rx)
-{
-    KG_TRY(bank_rx_check(b, rx, "kg_rxbank_fftext_clear"));
-    KG_TRY(bank_fx_ensure(b));
-    return kg_fftext_clear(b->fx, rx);
-}
-
-kg_fftext *kg_rxbank_fftext(kg_rxbank *b) { return b ? b->fx : nullptr; }
+kg_fftext *kg_rxbank_fftext(kg_rxbank *b) { return b ? b->fx.obj : nullptr; }
 
 int kg_rxbank_fftext_max(kg_rxbank *b)
 {
     KG_REQUIRE(b != nullptr, KG_ERR_INVALID, "kg_rxbank_fftext_max: null argument");
-    return (int) b->fx_max;
+    return (int) b->fx.max;
 }
 
 int kg_rxbank_fftext_map(kg_rxbank *b, int32_t *rx_of_row, int32_t *blk_of_row, int32_t *bin_of_row)
 {
     KG_REQUIRE(b != nullptr, KG_ERR_INVALID, "kg_rxbank_fftext_map: null argument");
-    for (int r = 0; r < b->fx_n; r++) {
-        if (rx_of_row) rx_of_row[r] = b->fx_rx[r];
-        if (blk_of_row) blk_of_row[r] = b->fx_blk[r];
-        if (bin_of_row) bin_of_row[r] = b->fx_bin[r];
+    for (int r = 0; r < b->fx.last.n; r++) {
+        if (rx_of_row) rx_of_row[r] = b->fx.last.rx[r];
+        if (blk_of_row) blk_of_row[r] = b->fx.last.blk[r];
+        if (bin_of_row) bin_of_row[r] = b->fx.last.bin[r];
     }
-    return b->fx_n;
+    return b->fx.last.n;
 }
 
 int kg_rxbank_fftext_rows(kg_rxbank *b, uint8_t **d_rows, size_t *row_stride)
 {
     KG_REQUIRE(b && d_rows && row_stride, KG_ERR_INVALID, "kg_rxbank_fftext_rows: null argument");
-    *d_rows = b->d_fxrows; *row_stride = KG_FFTEXT_ROW;            // null until the extension was named
+    *d_rows = b->fx.d_rows; *row_stride = KG_FFTEXT_ROW;          // null until the extension was named
     return KG_OK;
 }
-
-// The IQ display's object and buffers, made whole or not at all by the first call that names the extension.  Drains the bank's streams.
-static int bank_iq_ensure(kg_rxbank *b)
-{
-    if (b->iq) return KG_OK;
-    KG_HIP(hipSetDevice(b->device));
-    KG_TRY(bank_drain(b, true));
-    kg_iqd *iq = nullptr;
-    const size_t nst = (size_t) b->nrx * b->blocks_max;
-    int rc = kg_iqd_create(b->c_tail, b->nrx, &iq);
-    if (rc == KG_OK) rc = b->d_iqrows.alloc(b->iq_cap, "kg_rxbank_iqd: rows");
-    if (rc == KG_OK) rc = b->d_iqst.alloc(nst, "kg_rxbank_iqd: status");
-    if (rc == KG_OK && (hipMemset(b->d_iqrows, 0, b->iq_cap) != hipSuccess || hipMemset(b->d_iqst, 0, sizeof(kg_iqd_status) * nst) != hipSuccess)) {
-        kg_set_error("kg_rxbank_iqd: hipMemset failed");
-        rc = KG_ERR_HIP;
-    }
-    if (rc) { kg_iqd_destroy(iq); b->d_iqrows.reset(); b->d_iqst.reset(); return rc; }
-    bank_plan &p = b->plan;
-    for (std::vector<kg_iqd_row> *v : {&b->iq_rows, &p.iq_rows}) v->assign((size_t) b->iq_max_rows, kg_iqd_row{});
-    for (std::vector<int32_t> *v : {&b->iq_sent, &p.iq_sent, &b->iq_blk_rx, &b->iq_blk_blk}) v->assign(nst, 0);
-    b->iq = iq;
-    return KG_OK;
-}
-
-#define BANK_IQ(who)                                   \
-    KG_TRY(bank_rx_check(b, rx, who));                 \
-    KG_TRY(bank_iq_ensure(b))
 
 int kg_rxbank_iqd_init(kg_rxbank *b, int rx)
 {
-    BANK_IQ("kg_rxbank_iqd_init");
-    b->rcv[rx].iq_on = 0;                                  // a fresh object is not registered
-    return kg_iqd_init(b->iq, rx);
+    BANK_EXT("kg_rxbank_iqd_init", bank_iq_ensure);
+    b->iq.on[rx] = 0;                                      // a fresh object is not registered
+    return kg_iqd_init(b->iq.obj, rx);
 }
 
 int kg_rxbank_iqd_set_run(kg_rxbank *b, int rx, int run, double rate)
 {
-    BANK_IQ("kg_rxbank_iqd_set_run");
-    KG_REQUIRE(!run || !b->rcv[rx].lo_on, KG_ERR_STATE, "kg_rxbank_iqd_set_run: receiver %d has Loran-C started; the tap holds one callback", rx);
-    KG_TRY(kg_iqd_set_run(b->iq, rx, run, rate));
-    b->rcv[rx].iq_on = run != 0;
+    BANK_EXT("kg_rxbank_iqd_set_run", bank_iq_ensure);
+    if (run) KG_TRY(bank_tap_free(b, rx, "kg_rxbank_iqd_set_run", false));
+    KG_TRY(kg_iqd_set_run(b->iq.obj, rx, run, rate));
+    b->iq.on[rx] = run != 0;
     return KG_OK;
 }
 
-int kg_rxbank_iqd_set_gain(kg_rxbank *b, int rx, int gain) { BANK_IQ("kg_rxbank_iqd_set_gain"); return kg_iqd_set_gain(b->iq, rx, gain); }
-int kg_rxbank_iqd_set_points(kg_rxbank *b, int rx, int points) { BANK_IQ("kg_rxbank_iqd_set_points"); return kg_iqd_set_points(b->iq, rx, points); }
-int kg_rxbank_iqd_set_pll_mode(kg_rxbank *b, int rx, int pll_mode, int arg) { BANK_IQ("kg_rxbank_iqd_set_pll_mode"); return kg_iqd_set_pll_mode(b->iq, rx, pll_mode, arg); }
-int kg_rxbank_iqd_set_pll_bandwidth(kg_rxbank *b, int rx, float bandwidth) { BANK_IQ("kg_rxbank_iqd_set_pll_bandwidth"); return kg_iqd_set_pll_bandwidth(b->iq, rx, bandwidth); }
-int kg_rxbank_iqd_set_draw(kg_rxbank *b, int rx, int draw) { BANK_IQ("kg_rxbank_iqd_set_draw"); return kg_iqd_set_draw(b->iq, rx, draw); }
-int kg_rxbank_iqd_set_display_mode(kg_rxbank *b, int rx, int display_mode) { BANK_IQ("kg_rxbank_iqd_set_display_mode"); return kg_iqd_set_display_mode(b->iq, rx, display_mode); }
-int kg_rxbank_iqd_clear(kg_rxbank *b, int rx) { BANK_IQ("kg_rxbank_iqd_clear"); return kg_iqd_clear(b->iq, rx); }
+int kg_rxbank_iqd_set_gain(kg_rxbank *b, int rx, int gain) { BANK_EXT("kg_rxbank_iqd_set_gain", bank_iq_ensure); return kg_iqd_set_gain(b->iq.obj, rx, gain); }
+int kg_rxbank_iqd_set_points(kg_rxbank *b, int rx, int points) { BANK_EXT("kg_rxbank_iqd_set_points", bank_iq_ensure); return kg_iqd_set_points(b->iq.obj, rx, points); }
+int kg_rxbank_iqd_set_pll_mode(kg_rxbank *b, int rx, int pll_mode, int arg) { BANK_EXT("kg_rxbank_iqd_set_pll_mode", bank_iq_ensure); return kg_iqd_set_pll_mode(b->iq.obj, rx, pll_mode, arg); }
+int kg_rxbank_iqd_set_pll_bandwidth(kg_rxbank *b, int rx, float bandwidth) { BANK_EXT("kg_rxbank_iqd_set_pll_bandwidth", bank_iq_ensure); return kg_iqd_set_pll_bandwidth(b->iq.obj, rx, bandwidth); }
+int kg_rxbank_iqd_set_draw(kg_rxbank *b, int rx, int draw) { BANK_EXT("kg_rxbank_iqd_set_draw", bank_iq_ensure); return kg_iqd_set_draw(b->iq.obj, rx, draw); }
+int kg_rxbank_iqd_set_display_mode(kg_rxbank *b, int rx, int display_mode) { BANK_EXT("kg_rxbank_iqd_set_display_mode", bank_iq_ensure); return kg_iqd_set_display_mode(b->iq.obj, rx, display_mode); }
+int kg_rxbank_iqd_clear(kg_rxbank *b, int rx) { BANK_EXT("kg_rxbank_iqd_clear", bank_iq_ensure); return kg_iqd_clear(b->iq.obj, rx); }
 
-kg_iqd *kg_rxbank_iqd(kg_rxbank *b) { return b ? b->iq : nullptr; }
+kg_iqd *kg_rxbank_iqd(kg_rxbank *b) { return b ? b->iq.obj : nullptr; }
 
 int kg_rxbank_iqd_map(kg_rxbank *b, kg_iqd_row *row_map, int max_rows)
 {
     KG_REQUIRE(b != nullptr && max_rows >= 0, KG_ERR_INVALID, "kg_rxbank_iqd_map: bad argument");
-    KG_REQUIRE(!row_map || max_rows >= b->iq_n, KG_ERR_INVALID, "kg_rxbank_iqd_map: %d rows, room for %d", b->iq_n, max_rows);
-    if (row_map && b->iq_n) memcpy(row_map, b->iq_rows.data(), sizeof(kg_iqd_row) * (size_t) b->iq_n);
-    return b->iq_n;
+    KG_REQUIRE(!row_map || max_rows >= b->iq.last.n, KG_ERR_INVALID, "kg_rxbank_iqd_map: %d rows, room for %d", b->iq.last.n, max_rows);
+    if (row_map && b->iq.last.n) memcpy(row_map, b->iq.last.rows.data(), sizeof(kg_iqd_row) * (size_t) b->iq.last.n);
+    return b->iq.last.n;
 }
 
 int kg_rxbank_iqd_rows(kg_rxbank *b, uint8_t **d_rows, size_t *rows_cap)
 {
     KG_REQUIRE(b && d_rows && rows_cap, KG_ERR_INVALID, "kg_rxbank_iqd_rows: null argument");
-    *d_rows = b->d_iqrows; *rows_cap = b->iq_cap;                 // null until the extension was named
+    *d_rows = b->iq.d_rows; *rows_cap = b->iq.cap;                // null until the extension was named
     return KG_OK;
 }
 
 int kg_rxbank_iqd_status(kg_rxbank *b, kg_iqd_status **d_status, int32_t *rx_of_blk, int32_t *blk_of_blk, int32_t *sent_of_blk)
 {
     KG_REQUIRE(b != nullptr, KG_ERR_INVALID, "kg_rxbank_iqd_status: null argument");
-    if (d_status) *d_status = b->d_iqst;
-    for (int k = 0; k < b->iq_nblk; k++) {
-        if (rx_of_blk) rx_of_blk[k] = b->iq_blk_rx[k];
-        if (blk_of_blk) blk_of_blk[k] = b->iq_blk_blk[k];
-        if (sent_of_blk) sent_of_blk[k] = b->iq_sent[k];
+    if (d_status) *d_status = b->iq.d_st;
+    for (int k = 0; k < b->iq.last.nblk; k++) {
+        if (rx_of_blk) rx_of_blk[k] = b->iq.last.blk_rx[k];
+        if (blk_of_blk) blk_of_blk[k] = b->iq.last.blk_blk[k];
+        if (sent_of_blk) sent_of_blk[k] = b->iq.last.sent[k];
     }
-    return b->iq_nblk;
+    return b->iq.last.nblk;
 }
 
-// Loran-C's object and row buffer, and arena slots grown by its table, made whole or not at all by the first call that names the
-// extension.  Drains the bank's streams: no step is in flight while the slots change.
-static int bank_lo_ensure(kg_rxbank *b)
-{
-    if (b->lo) return KG_OK;
-    KG_HIP(hipSetDevice(b->device));
-    KG_TRY(bank_drain(b, true));
-    kg_lorc *lo = nullptr;
-    kg_hbuf<unsigned char> h;
-    kg_dbuf<unsigned char> d, rows;
-    const size_t grown = (b->slot_bytes + kg_lorc_table_bytes_((size_t) b->nrx, BANK_LO_RUNS(b->blocks_max)) + 63) & ~(size_t) 63;
-    KG_TRY(h.alloc(grown * BANK_SLOTS, "kg_rxbank_lorc: slots"));
-    KG_TRY(d.alloc(grown * BANK_SLOTS, "kg_rxbank_lorc: slots"));
-    KG_TRY(rows.alloc(b->lo_cap, "kg_rxbank_lorc: rows"));
-    if (hipMemset(rows, 0, b->lo_cap) != hipSuccess) { kg_set_error("kg_rxbank_lorc: hipMemset failed"); return KG_ERR_HIP; }
-    KG_TRY(kg_lorc_create(b->c_tail, b->nrx, &lo));
-    for (std::vector<kg_lorc_row> *v : {&b->lo_rows, &b->plan.lo_rows}) v->assign((size_t) b->lo_max_rows, kg_lorc_row{});
-    std::swap(b->h_slots.p, h.p); std::swap(b->d_slots.p, d.p); std::swap(b->d_lorows.p, rows.p);      // the old slots go with h and d
-    b->slot_bytes = grown;
-    b->lo = lo;
-    return KG_OK;
-}
-
-// the connection's end or beginning: loran_c[rx] as a new connection finds it -- stopped, waiting for its `SET ext_server_init`
-static int bank_lo_fresh(kg_rxbank *b, int rx)
-{
-    b->rcv[rx].lo_on = 0;
-    return b->lo ? kg_lorc_reset_(b->lo, rx) : KG_OK;
-}
-
-#define BANK_LO(who)                                   \
-    KG_TRY(bank_rx_check(b, rx, who));                 \
-    KG_TRY(bank_lo_ensure(b))
-
-int kg_rxbank_lorc_init(kg_rxbank *b, int rx, double srate, int i_srate) { BANK_LO("kg_rxbank_lorc_init"); return kg_lorc_init(b->lo, rx, srate, i_srate); }
-int kg_rxbank_lorc_set_gri(kg_rxbank *b, int rx, int ch, int gri) { BANK_LO("kg_rxbank_lorc_set_gri"); return kg_lorc_set_gri_min_(b->lo, rx, ch, gri, BANK_LO_MIN_SPG); }
-int kg_rxbank_lorc_set_offset(kg_rxbank *b, int rx, int ch, int offset) { BANK_LO("kg_rxbank_lorc_set_offset"); return kg_lorc_set_offset(b->lo, rx, ch, offset); }
-int kg_rxbank_lorc_set_gain(kg_rxbank *b, int rx, int ch, int gain) { BANK_LO("kg_rxbank_lorc_set_gain"); return kg_lorc_set_gain(b->lo, rx, ch, gain); }
-int kg_rxbank_lorc_set_avg_algo(kg_rxbank *b, int rx, int ch, int avg_algo) { BANK_LO("kg_rxbank_lorc_set_avg_algo"); return kg_lorc_set_avg_algo(b->lo, rx, ch, avg_algo); }
-int kg_rxbank_lorc_set_avg_param(kg_rxbank *b, int rx, int ch, double avg_param) { BANK_LO("kg_rxbank_lorc_set_avg_param"); return kg_lorc_set_avg_param(b->lo, rx, ch, avg_param); }
+int kg_rxbank_lorc_init(kg_rxbank *b, int rx, double srate, int i_srate) { BANK_EXT("kg_rxbank_lorc_init", bank_lo_ensure); return kg_lorc_init(b->lo.obj, rx, srate, i_srate); }
+int kg_rxbank_lorc_set_gri(kg_rxbank *b, int rx, int ch, int gri) { BANK_EXT("kg_rxbank_lorc_set_gri", bank_lo_ensure); return kg_lorc_set_gri_min_(b->lo.obj, rx, ch, gri, BANK_LO_MIN_SPG); }
+int kg_rxbank_lorc_set_offset(kg_rxbank *b, int rx, int ch, int offset) { BANK_EXT("kg_rxbank_lorc_set_offset", bank_lo_ensure); return kg_lorc_set_offset(b->lo.obj, rx, ch, offset); }
+int kg_rxbank_lorc_set_gain(kg_rxbank *b, int rx, int ch, int gain) { BANK_EXT("kg_rxbank_lorc_set_gain", bank_lo_ensure); return kg_lorc_set_gain(b->lo.obj, rx, ch, gain); }
+int kg_rxbank_lorc_set_avg_algo(kg_rxbank *b, int rx, int ch, int avg_algo) { BANK_EXT("kg_rxbank_lorc_set_avg_algo", bank_lo_ensure); return kg_lorc_set_avg_algo(b->lo.obj, rx, ch, avg_algo); }
+int kg_rxbank_lorc_set_avg_param(kg_rxbank *b, int rx, int ch, double avg_param) { BANK_EXT("kg_rxbank_lorc_set_avg_param", bank_lo_ensure); return kg_lorc_set_avg_param(b->lo.obj, rx, ch, avg_param); }
 
 int kg_rxbank_lorc_start(kg_rxbank *b, int rx)
 {
-    BANK_LO("kg_rxbank_lorc_start");
-    KG_REQUIRE(!b->rcv[rx].iq_on, KG_ERR_STATE, "kg_rxbank_lorc_start: receiver %d has the IQ display running; the tap holds one callback", rx);
-    KG_TRY(kg_lorc_start(b->lo, rx));
-    b->rcv[rx].lo_on = 1;
+    BANK_EXT("kg_rxbank_lorc_start", bank_lo_ensure);
+    KG_TRY(bank_tap_free(b, rx, "kg_rxbank_lorc_start", true));
+    KG_TRY(kg_lorc_start(b->lo.obj, rx));
+    b->lo.on[rx] = 1;
     return KG_OK;
 }
 
 int kg_rxbank_lorc_stop(kg_rxbank *b, int rx)
 {
-    BANK_LO("kg_rxbank_lorc_stop");
-    KG_TRY(kg_lorc_stop(b->lo, rx));
-    b->rcv[rx].lo_on = 0;
+    BANK_EXT("kg_rxbank_lorc_stop", bank_lo_ensure);
+    KG_TRY(kg_lorc_stop(b->lo.obj, rx));
+    b->lo.on[rx] = 0;
     return KG_OK;
 }
 
-kg_lorc *kg_rxbank_lorc(kg_rxbank *b) { return b ? b->lo : nullptr; }
+kg_lorc *kg_rxbank_lorc(kg_rxbank *b) { return b ? b->lo.obj : nullptr; }
 
 int kg_rxbank_lorc_map(kg_rxbank *b, kg_lorc_row *row_map, int max_rows)
 {
     KG_REQUIRE(b != nullptr && max_rows >= 0, KG_ERR_INVALID, "kg_rxbank_lorc_map: bad argument");
-    KG_REQUIRE(!row_map || max_rows >= b->lo_n, KG_ERR_INVALID, "kg_rxbank_lorc_map: %d rows, room for %d", b->lo_n, max_rows);
-    if (row_map && b->lo_n) memcpy(row_map, b->lo_rows.data(), sizeof(kg_lorc_row) * (size_t) b->lo_n);
-    return b->lo_n;
+    KG_REQUIRE(!row_map || max_rows >= b->lo.last.n, KG_ERR_INVALID, "kg_rxbank_lorc_map: %d rows, room for %d", b->lo.last.n, max_rows);
+    if (row_map && b->lo.last.n) memcpy(row_map, b->lo.last.rows.data(), sizeof(kg_lorc_row) * (size_t) b->lo.last.n);
+    return b->lo.last.n;
 }
 
 int kg_rxbank_lorc_rows(kg_rxbank *b, uint8_t **d_rows, size_t *cap)
 {
     KG_REQUIRE(b && d_rows && cap, KG_ERR_INVALID, "kg_rxbank_lorc_rows: null argument");
-    *d_rows = b->d_lorows; *cap = b->lo_cap;                      // null until the extension was named
+    *d_rows = b->lo.d_rows; *cap = b->lo.cap;                     // null until the extension was named
     return KG_OK;
 }
-
-}  // extern "C"
-
-// FAX's object and output buffers, and arena slots grown by its table, made whole or not at all by the first call that names the
-// extension.  Drains the bank's streams: no step is in flight while the slots change.
-static int bank_fa_ensure(kg_rxbank *b)
-{
-    if (b->fa) return KG_OK;
-    KG_HIP(hipSetDevice(b->device));
-    KG_TRY(bank_drain(b, true));
-    kg_fax *fa = nullptr;
-    kg_hbuf<unsigned char> h;
-    kg_dbuf<unsigned char> d, rows;
-    kg_dbuf<kg_fax_rec> recs;
-    kg_dbuf<int32_t> counts;
-    const size_t grown = (b->slot_bytes + kg_fax_table_bytes_((size_t) b->nrx) + 63) & ~(size_t) 63;
-    const size_t nrows = (size_t) b->nrx * (size_t) b->fa_max_lines;
-    KG_TRY(h.alloc(grown * BANK_SLOTS, "kg_rxbank_fax: slots"));
-    KG_TRY(d.alloc(grown * BANK_SLOTS, "kg_rxbank_fax: slots"));
-    KG_TRY(rows.alloc(nrows * b->fa_row_stride, "kg_rxbank_fax: rows"));
-    KG_TRY(recs.alloc(nrows, "kg_rxbank_fax: records"));
-    KG_TRY(counts.alloc((size_t) 4 * b->nrx, "kg_rxbank_fax: counts"));
-    if (hipMemset(rows, 0, nrows * b->fa_row_stride) != hipSuccess || hipMemset(recs, 0, nrows * sizeof(kg_fax_rec)) != hipSuccess ||
-        hipMemset(counts, 0, sizeof(int32_t) * 4 * (size_t) b->nrx) != hipSuccess) {
-        kg_set_error("kg_rxbank_fax: hipMemset failed");
-        return KG_ERR_HIP;
-    }
-    KG_TRY(kg_fax_create(b->c_tail, b->nrx, &fa));
-    std::swap(b->h_slots.p, h.p); std::swap(b->d_slots.p, d.p);          // the old slots go with h and d
-    std::swap(b->d_farows.p, rows.p); std::swap(b->d_farecs.p, recs.p); std::swap(b->d_facounts.p, counts.p);
-    b->slot_bytes = grown;
-    b->fa = fa;
-    return KG_OK;
-}
-
-// the connection's end or beginning: m_FaxDecoder[rx] and fax[rx] as a new connection finds them -- zeroed, no task
-static int bank_fa_fresh(kg_rxbank *b, int rx)
-{
-    b->rcv[rx].fax_on = 0;
-    b->rcv[rx].fax_rate = 0;
-    return b->fa ? kg_fax_reset_(b->fa, rx) : KG_OK;
-}
-
-#define BANK_FA(who)                                   \
-    KG_TRY(bank_rx_check(b, rx, who));                 \
-    KG_TRY(bank_fa_ensure(b))
-
-extern "C" {
 
 int kg_rxbank_fax_start(kg_rxbank *b, int rx, int lpm, int imagewidth, int carrier, int deviation, int bandwidth, int include_headers, int phasing, int autostop,
                         int debug, double nom_rate, double srate)
 {
-    BANK_FA("kg_rxbank_fax_start");
+    BANK_EXT("kg_rxbank_fax_start", bank_fa_ensure);
     KG_REQUIRE(imagewidth <= BANK_FAX_MAX_WIDTH, KG_ERR_INVALID, "kg_rxbank_fax_start: imagewidth %d; a receiver bank takes %d or fewer", imagewidth,
                BANK_FAX_MAX_WIDTH);
     KG_REQUIRE(!(lpm >= 1 && nom_rate >= 1) || nom_rate * 60.0 / lpm >= BANK_FAX_MIN_SPL, KG_ERR_INVALID,
                "kg_rxbank_fax_start: %g samples a line; a receiver bank takes %d or more (it bounds a step's lines by it)", nom_rate * 60.0 / lpm, BANK_FAX_MIN_SPL);
-    KG_TRY(kg_fax_start(b->fa, rx, lpm, imagewidth, carrier, deviation, bandwidth, include_headers, phasing, autostop, debug, nom_rate, srate));
-    b->rcv[rx].fax_on = 1;
-    b->rcv[rx].fax_rate = srate;
+    KG_TRY(kg_fax_start(b->fa.obj, rx, lpm, imagewidth, carrier, deviation, bandwidth, include_headers, phasing, autostop, debug, nom_rate, srate));
+    b->fa.on[rx] = 1;
+    b->fa.rate[rx] = srate;
     return KG_OK;
 }
 
-int kg_rxbank_fax_set_shift(kg_rxbank *b, int rx, float shift) { BANK_FA("kg_rxbank_fax_set_shift"); return kg_fax_set_shift(b->fa, rx, shift); }
+int kg_rxbank_fax_set_shift(kg_rxbank *b, int rx, float shift) { BANK_EXT("kg_rxbank_fax_set_shift", bank_fa_ensure); return kg_fax_set_shift(b->fa.obj, rx, shift); }
 
 int kg_rxbank_fax_stop(kg_rxbank *b, int rx)
 {
-    BANK_FA("kg_rxbank_fax_stop");
-    KG_TRY(kg_fax_stop(b->fa, rx));
-    b->rcv[rx].fax_on = 0;
+    BANK_EXT("kg_rxbank_fax_stop", bank_fa_ensure);
+    KG_TRY(kg_fax_stop(b->fa.obj, rx));
+    b->fa.on[rx] = 0;
     return KG_OK;
 }
 
-kg_fax *kg_rxbank_fax(kg_rxbank *b) { return b ? b->fa : nullptr; }
+kg_fax *kg_rxbank_fax(kg_rxbank *b) { return b ? b->fa.obj : nullptr; }
 
 int kg_rxbank_fax_out(kg_rxbank *b, uint8_t **d_rows, size_t *row_stride, kg_fax_rec **d_recs, int32_t **d_counts, int32_t *max_lines, int32_t *rx_of_entry,
                       int max_entries)
 {
     KG_REQUIRE(b != nullptr && max_entries >= 0, KG_ERR_INVALID, "kg_rxbank_fax_out: bad argument");
-    KG_REQUIRE(!rx_of_entry || max_entries >= b->fa_n, KG_ERR_INVALID, "kg_rxbank_fax_out: %d entries, room for %d", b->fa_n, max_entries);
-    if (d_rows) *d_rows = b->d_farows;                                   // null until the extension was named
-    if (row_stride) *row_stride = b->fa_row_stride;
-    if (d_recs) *d_recs = b->d_farecs;
-    if (d_counts) *d_counts = b->d_facounts;
-    if (max_lines) *max_lines = b->fa_max_lines;
-    if (rx_of_entry && b->fa_n) memcpy(rx_of_entry, b->fa_rx.data(), sizeof(int32_t) * (size_t) b->fa_n);
-    return b->fa_n;
+    const bank_fa &x = b->fa;
+    KG_REQUIRE(!rx_of_entry || max_entries >= x.last.n, KG_ERR_INVALID, "kg_rxbank_fax_out: %d entries, room for %d", x.last.n, max_entries);
+    if (d_rows) *d_rows = x.d_rows;                                      // null until the extension was named
+    if (row_stride) *row_stride = x.row_stride;
+    if (d_recs) *d_recs = x.d_recs;
+    if (d_counts) *d_counts = x.d_counts;
+    if (max_lines) *max_lines = x.max_lines;
+    if (rx_of_entry && x.last.n) memcpy(rx_of_entry, x.last.rx.data(), sizeof(int32_t) * (size_t) x.last.n);
+    return x.last.n;
 }
 
 int kg_rxbank_set_wf(kg_rxbank *b, int rx, uint64_t phase_inc, int decim, int overlapped)
@@ -1327,13 +1456,7 @@ int kg_rxbank_leave(kg_rxbank *b, int rx)
 {
     KG_TRY(bank_rx_check(b, rx, "kg_rxbank_leave"));
     b->rcv[rx].active = 0;
-    b->rcv[rx].fx_on = 0;                                  // ext_unregister_receive_FFT_samps at the connection's end; its fft_t is gone with it
-    if (b->fx) KG_TRY(kg_fftext_restart(b->fx, rx));
-    b->rcv[rx].iq_on = 0;                                  // iq_display_close: the object goes with the connection
-    if (b->iq) KG_TRY(kg_iqd_init(b->iq, rx));
-    KG_TRY(bank_lo_fresh(b, rx));
-    KG_TRY(bank_fa_fresh(b, rx));
-    return KG_OK;
+    return bank_ext_fresh(b, rx);
 }
 
 // A connection starts on receiver rx (rx/rx_sound.cpp:236-269, rx/rx_waterfall.cpp:205-330): its audio DDC, CFastFIR position,
@@ -1358,12 +1481,7 @@ int kg_rxbank_join(kg_rxbank *b, int rx)
     r.wf_set = 0; r.ring_w = 0; r.ring_total = 0;
     r.spec_on = 0; kg_spec::emit_clear(r.spec_mirror);     // memset(snd_t): specAF_FFT NULL, isChanNull false
     r.spec_cmds = kg_post_mode_cmds_(b->post, rx);
-    r.fx_on = 0;                                           // the extension's state is the connection's: function off, nothing latched, sums zero
-    if (b->fx) KG_TRY(kg_fftext_restart(b->fx, rx));
-    r.iq_on = 0;                                           // the IQ display's object is the connection's: a fresh one, not registered
-    if (b->iq) KG_TRY(kg_iqd_init(b->iq, rx));
-    KG_TRY(bank_lo_fresh(b, rx));
-    KG_TRY(bank_fa_fresh(b, rx));
+    KG_TRY(bank_ext_fresh(b, rx));                         // the extensions' state is the connection's
     r.nbc = bank_nb_cmd{};                                 // memset(snd_t) / memset(wf_inst_t): algo NB_OFF, enables and params 0;
     KG_TRY(kg_wf_set_nb(b->wf, rx, 0));                    // the blankers' states stay (the reference's CNoiseProc arrays are globals)
     r.active = 1;

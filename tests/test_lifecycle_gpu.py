@@ -163,6 +163,62 @@ def run_bank(bank):
     bank.ctx.free(d_adc)
 
 
+def prep_bank(bank):
+    """run_bank up to its step; the ADC block stays for the bank's steps and goes when the bank is closed"""
+    from .test_receivers_gpu import _small_mix
+    bank.configure(_small_mix([5, 6], bank.n))
+    adc = synth.adc_stream(bank.n, 0x5EED0047)
+    bank.d_adc = bank.ctx.alloc(adc.nbytes)
+    bank.ctx.upload(bank.d_adc, adc)
+    close = bank.close
+
+    def close_with_adc():
+        if bank.h:
+            bank.ctx.free(bank.d_adc)
+        close()
+    bank.close = close_with_adc
+
+
+# The smallest number of steps after which a fresh bank's audio_map() reports one completed sound block for receiver 0: a step of
+# 8192 * 16 = 131072 ADC samples at the audio DDC's decimation of 10416 (RX_STD) is 12.58 rx_iq_t records (12 or 13 a step,
+# floor(12.5837 k) after k steps), a sound block takes 512: 40 steps give 503, 41 give 515.  The call's last step is the one that
+# completes the block, so every extension has rows to show for it.
+BANK_EXT_STEPS = 41
+
+
+def bank_ext(tell, outputs):
+    """-> the call of a bank extension's growth case: its first commands for receiver 0, BANK_EXT_STEPS steps, the last step's outputs"""
+    def call(bank):
+        tell(bank)
+        for _ in range(BANK_EXT_STEPS):
+            bank.step(bank.d_adc)
+        bank.sync()
+        return [outputs(bank), bank.audio_map()]
+    return call
+
+
+def tell_fftext(bank):
+    from flydog_sdr_gps_amd import fftext
+    bank.fftext_set_rate(bank.fs)
+    bank.fftext_set_run(0, fftext.SPEC)
+
+
+def tell_iqd(bank):
+    bank.iqd_init(0)
+    bank.iqd_set_run(0, 1, bank.fs)
+
+
+def tell_lorc(bank):
+    bank.lorc_init(0, bank.fs, 600)
+    bank.lorc_set_gri(0, 0, 2990)
+    bank.lorc_set_gri(0, 1, 4970)
+    bank.lorc_start(0)
+
+
+def fax_flat(bank):
+    return [[rx, recs, rows] for rx, (recs, rows) in sorted(bank.fax_out().items())]
+
+
 def prep_tracker(t):
     from . import trk_common as tc
     for ch, word in ((0, tc.CA1), (1, tc.CA7)):
@@ -326,6 +382,11 @@ GROWTHS = {
     "Tracker.process": CREATES["Tracker"],
     "PositionSolver.solve": CREATES["PositionSolver"],
     "Aperture.report": (CREATES["Aperture"][0], lambda a: a.update([0], ROW[None], APER_CFG), lambda a: a.report([0])),
+    # an extension's first use in a receiver bank: the object, its buffers and (Loran-C, FAX) the grown step-table slots
+    "RxBank.fftext": (CREATES["RxBank"][0], prep_bank, bank_ext(tell_fftext, lambda b: [b.fftext_map(), b.fftext_rows()])),
+    "RxBank.iqd": (CREATES["RxBank"][0], prep_bank, bank_ext(tell_iqd, lambda b: [b.iqd_rows(), b.iqd_status()])),
+    "RxBank.lorc": (CREATES["RxBank"][0], prep_bank, bank_ext(tell_lorc, lambda b: b.lorc_rows())),
+    "RxBank.fax": (CREATES["RxBank"][0], prep_bank, bank_ext(lambda b: b.fax_start(0), fax_flat)),
 }
 
 
