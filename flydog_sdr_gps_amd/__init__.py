@@ -22,7 +22,8 @@ from .pos import PositionSolver  # noqa: F401
 from .fftext import FftExt  # noqa: F401
 from .lorc import LoranC  # noqa: F401
 from .fax import FaxDecoder  # noqa: F401
-from . import sats, prn, synth, shard, wf, snd, post, wire, handoff, nb, trk, nav, eph, pos, fftext, lorc, fax  # noqa: F401
+from .cw import CwDecoder  # noqa: F401
+from . import sats, prn, synth, shard, wf, snd, post, wire, handoff, nb, trk, nav, eph, pos, fftext, lorc, fax, cw  # noqa: F401
 
-__all__ = ["KiwiGpuError", "Context", "Searcher", "AcqResult", "Waterfall", "WfParams", "Ddc", "RxDdc", "FastFir", "Post", "NoiseBlanker", "Adpcm", "Aperture", "chan_start", "Tracker", "NavSync", "Ephemerides", "FftExt", "LoranC", "FaxDecoder",
+__all__ = ["KiwiGpuError", "Context", "Searcher", "AcqResult", "Waterfall", "WfParams", "Ddc", "RxDdc", "FastFir", "Post", "NoiseBlanker", "Adpcm", "Aperture", "chan_start", "Tracker", "NavSync", "Ephemerides", "FftExt", "LoranC", "FaxDecoder", "CwDecoder",
            "load_library", "library_path", "live_allocs", "sats", "prn", "synth", "shard", "wf"]

@@ -259,6 +259,18 @@ SYMBOLS = {
     "kg_fax_max_lines": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "kg_fax_push": (_i, [_vp, _vp, _i, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _i, _vp]),
     "kg_fax_state": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "kg_cw_create": (_i, [_vp, _i, C.POINTER(_vp)]),
+    "kg_cw_destroy": (None, [_vp]),
+    "kg_cw_start": (_i, [_vp, _i, _i, C.c_double, C.c_double]),
+    "kg_cw_set_wpm": (_i, [_vp, _i, _i, _i]),
+    "kg_cw_set_pboff": (_i, [_vp, _i, C.c_uint32]),
+    "kg_cw_set_wsc": (_i, [_vp, _i, _i]),
+    "kg_cw_set_auto_threshold": (_i, [_vp, _i, _i]),
+    "kg_cw_set_threshold": (_i, [_vp, _i, _i]),
+    "kg_cw_stop": (_i, [_vp, _i]),
+    "kg_cw_max_events": (_i, [_i]),
+    "kg_cw_push": (_i, [_vp, _vp, _i, _vp, _vp, _sz, _vp, _vp, _i, _vp]),
+    "kg_cw_state": (_i, [_vp, _i, _vp]),
     "kg_rxbank_lorc_init": (_i, [_vp, _i, C.c_double, _i]),
     "kg_rxbank_lorc_set_gri": (_i, [_vp, _i, _i, _i]),
     "kg_rxbank_lorc_set_offset": (_i, [_vp, _i, _i, _i]),
@@ -275,6 +287,16 @@ SYMBOLS = {
     "kg_rxbank_fax_stop": (_i, [_vp, _i]),
     "kg_rxbank_fax": (_vp, [_vp]),
     "kg_rxbank_fax_out": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    "kg_rxbank_cw_start": (_i, [_vp, _i, _i, C.c_double, C.c_double]),
+    "kg_rxbank_cw_set_wpm": (_i, [_vp, _i, _i, _i]),
+    "kg_rxbank_cw_set_pboff": (_i, [_vp, _i, C.c_uint32]),
+    "kg_rxbank_cw_set_wsc": (_i, [_vp, _i, _i]),
+    "kg_rxbank_cw_set_auto_threshold": (_i, [_vp, _i, _i]),
+    "kg_rxbank_cw_set_threshold": (_i, [_vp, _i, _i]),
+    "kg_rxbank_cw_stop": (_i, [_vp, _i]),
+    "kg_rxbank_cw_set_now": (_i, [_vp, C.c_uint32]),
+    "kg_rxbank_cw": (_vp, [_vp]),
+    "kg_rxbank_cw_out": (_i, [_vp, _vp, _vp, _vp, _vp, _i]),
     "kg_rxbank_fftext_set_rate": (_i, [_vp, C.c_double]),
     "kg_rxbank_fftext_set_run": (_i, [_vp, _i, _i]),
     "kg_rxbank_fftext_set_itime": (_i, [_vp, _i, C.c_double]),

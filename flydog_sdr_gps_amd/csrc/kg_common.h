@@ -252,6 +252,13 @@ __attribute__((visibility("hidden"))) int kg_fax_push_at_(kg_fax *q, const int32
 __attribute__((visibility("hidden"))) size_t kg_fax_table_bytes_(size_t nconn);
 __attribute__((visibility("hidden"))) int kg_fax_reset_(kg_fax *q, int conn);
 
+// kg_cw.hip, for kg_rxbank.hip (not part of the ABI): kg_cw_push on device memory, samples and outputs alike, entry i's samples at
+// in_off[i] samples from d_s16 (null: i * stride), enqueue only; the bytes a push's table takes; connection conn as a new connection finds it: the zeroed object, not started
+__attribute__((visibility("hidden"))) int kg_cw_push_at_(kg_cw *q, const int32_t *conns, int nconn, const int32_t *nblk, const int64_t *in_off, const int16_t *d_s16,
+                                                         size_t stride, const uint32_t *now_sec, kg_cw_ev *d_evs, int max_events, int32_t *d_counts);
+__attribute__((visibility("hidden"))) size_t kg_cw_table_bytes_(size_t nconn);
+__attribute__((visibility("hidden"))) int kg_cw_reset_(kg_cw *q, int conn);
+
 // kg_post.hip, for kg_rxbank.hip: how many kg_post_set_mode / kg_post_set_sam_mparam calls channel ch has seen (each clears
 // s->isChanNull, rx_sound_cmd.cpp:202-228), and its s->SAM_mparam
 __attribute__((visibility("hidden"))) uint32_t kg_post_mode_cmds_(const kg_post *p, int ch);

@@ -189,6 +189,23 @@ struct bank_fa {
     struct { std::vector<int32_t> rx; int n; } last;    // kg_rxbank_fax_out: the last step's entries and their receivers
 };
 
+// The CW decoder (extensions/CW_decoder/uhsdr_cw_decoder.cpp; kg_cw); its first call also grows the arena slots by its table.  It is
+// the second consumer of the real-samples task tap, fed exactly as FAX is: while a receiver is started and its blocks go on the mono
+// list, the step's d_s16 blocks feed it in place: ONE launch per step over all such receivers, on the tail stream behind FAX's and
+// ahead of ev_tail.  The counts are the device's; now is what timer_sec() answers during the step (kg_rxbank_cw_set_now).
+struct bank_cw {
+    kg_cw *obj;
+    kg_dbuf<kg_cw_ev> d_evs; int max_events;                          // [entry][max_events]
+    kg_dbuf<int32_t> d_counts;                                        // [entry][4]
+    std::vector<char> on;                               // `SET cw_start` (ext_register_receive_real_samps_task: one task per receiver)
+    uint32_t now;
+    struct {
+        // the entries: receiver, blocks, where the receiver's row of d_s16 begins, the step's clock
+        std::vector<int32_t> list, nblk; std::vector<int64_t> off; std::vector<uint32_t> now;
+    } plan;
+    struct { std::vector<int32_t> rx; int n; } last;    // kg_rxbank_cw_out: the last step's entries and their receivers
+};
+
 struct kg_rxbank {
     // configuration
     int device, nrx, mode, decim_rx;
@@ -202,7 +219,7 @@ struct kg_rxbank {
     kg_ddc *ddc; kg_wf *wf; kg_rxddc *rx; kg_fir *fir; kg_post *post; kg_adpcm *adpcm;
     kg_nb *nb;                                  // m_NoiseProc_snd[] (the waterfall's blankers are kg_wf's)
     kg_fir *nullfir;                            // m_chan_null_FIR[] (rx_sound.cpp:151), on the tail stream behind kg_post
-    bank_fx fx; bank_iq iq; bank_lo lo; bank_fa fa;     // the extensions (above)
+    bank_fx fx; bank_iq iq; bank_lo lo; bank_fa fa; bank_cw cw;         // the extensions (above)
     // device buffers
     kg_dbuf<short2> d_wfiq; size_t wf_stride;         // [nrx][wf_stride] iq_t: a one-shot receiver uses pairs 0 .. 8191 of its row, an overlapped one all of it
     kg_dbuf<unsigned char> d_rows, d_pkts;         // [frame][1024], [frame][BANK_PKT_STRIDE]
@@ -284,7 +301,7 @@ static bool bank_stereo(int mode) { return mode == KG_POST_IQ || mode == KG_POST
 //   _plan_clear, _plan    the step's lists: emptied, then entry i of the active list (receiver p.act[i], nblk sound blocks)
 //   _enqueue     its ONE launch of the step, on the tail stream; what the entry point hands back goes into the record's plan
 //   _commit      the plan's maps become the last step's
-// The general functions call the four by name, in the order fx, iq, lo, fa: that is the order of the launches on the tail stream
+// The general functions call the five by name, in the order fx, iq, lo, fa, cw: that is the order of the launches on the tail stream
 // and of the tables in the slot.
 
 // A device buffer of a record: where its pointer goes, its size, its name in a refusal
@@ -560,13 +577,75 @@ static void bank_fa_commit(kg_rxbank *b)
     for (int e = 0; e < x.last.n; e++) x.last.rx[e] = x.plan.list[e];
 }
 
+static void bank_cw_sizes(kg_rxbank *b)
+{
+    bank_cw &x = b->cw;
+    const size_t nrx = (size_t) b->nrx;
+    x.max_events = KG_CW_EVENTS_PER_GBLK * (int) ((b->blocks_max * KG_CW_BLK + KG_CW_GBLK - 1) / KG_CW_GBLK);       // kg_cw_max_events' rule
+    x.on.assign(nrx, 0);
+    x.now = 0;
+    for (std::vector<int32_t> *v : {&x.plan.list, &x.plan.nblk}) v->reserve(nrx);
+    x.plan.off.reserve(nrx); x.plan.now.reserve(nrx);
+    x.last.rx.assign(nrx, -1);
+}
+
+static int bank_cw_ensure(kg_rxbank *b)
+{
+    bank_cw &x = b->cw;
+    if (x.obj) return KG_OK;
+    KG_REQUIRE(kg_cw_max_events((int) b->blocks_max) >= 0, KG_ERR_INVALID, "kg_rxbank_cw: a step of up to %zu sound blocks a receiver; a push takes 256", b->blocks_max);
+    return bank_ext_ensure(b, "kg_rxbank_cw",
+                           {bank_buf(x.d_evs, (size_t) b->nrx * (size_t) x.max_events, "kg_rxbank_cw: events"),
+                            bank_buf(x.d_counts, (size_t) 4 * b->nrx, "kg_rxbank_cw: counts")},
+                           kg_cw_table_bytes_((size_t) b->nrx), [](kg_rxbank *b) { return kg_cw_create(b->c_tail, b->nrx, &b->cw.obj); });
+}
+
+// the connection's end or beginning: cw_decoder[rx] as a new connection finds it -- zeroed, no task
+static int bank_cw_fresh(kg_rxbank *b, int rx) { b->cw.on[rx] = 0; return b->cw.obj ? kg_cw_reset_(b->cw.obj, rx) : KG_OK; }
+
+static void bank_cw_plan_clear(kg_rxbank *b) { b->cw.plan.list.clear(); b->cw.plan.nblk.clear(); b->cw.plan.off.clear(); b->cw.plan.now.clear(); }
+
+static void bank_cw_plan(kg_rxbank *b, int i, int nblk)
+{
+    bank_cw &x = b->cw;
+    const int k = b->plan.act[i];
+    if (!x.obj || !x.on[k] || nblk <= 0 || bank_stereo(b->plan.mode[i])) return;      // real_wr_pos advances for the mono blocks alone: cw_task sees no other
+    x.plan.list.push_back(k); x.plan.nblk.push_back(nblk); x.plan.off.push_back((int64_t) ((size_t) k * b->firo_stride)); x.plan.now.push_back(x.now);
+}
+
+// CwDecode_RxProcessor over the step's blocks: one launch, reading d_s16 in place
+static int bank_cw_enqueue(kg_rxbank *b)
+{
+    bank_cw &x = b->cw;
+    if (x.plan.list.empty()) return KG_OK;
+    return kg_cw_push_at_(x.obj, x.plan.list.data(), (int) x.plan.list.size(), x.plan.nblk.data(), x.plan.off.data(), (const int16_t *) b->d_s16.p, b->firo_stride,
+                          x.plan.now.data(), x.d_evs, x.max_events, x.d_counts);
+}
+
+static void bank_cw_commit(kg_rxbank *b)
+{
+    bank_cw &x = b->cw;
+    x.last.n = (int) x.plan.list.size();
+    for (int e = 0; e < x.last.n; e++) x.last.rx[e] = x.plan.list[e];
+}
+
 // a connection ends or begins on receiver rx: every extension as a new connection finds it
 static int bank_ext_fresh(kg_rxbank *b, int rx)
 {
     KG_TRY(bank_fx_fresh(b, rx));
     KG_TRY(bank_iq_fresh(b, rx));
     KG_TRY(bank_lo_fresh(b, rx));
-    return bank_fa_fresh(b, rx);
+    KG_TRY(bank_fa_fresh(b, rx));
+    return bank_cw_fresh(b, rx);
+}
+
+// The real-samples task tap (ext_register_receive_real_samps_task) holds one task per receiver, FAX's or the CW decoder's: whoever
+// asks for it is refused while the other has it
+static int bank_real_tap_free(const kg_rxbank *b, int rx, const char *who, bool cw_asks)
+{
+    KG_REQUIRE(!(cw_asks ? b->fa.on[rx] : b->cw.on[rx]), KG_ERR_STATE, "%s: receiver %d has %s; the tap holds one task", who, rx,
+               cw_asks ? "FAX started" : "the CW decoder started");
+    return KG_OK;
 }
 
 // The IQ tap (ext_users[rx].receive_iq_pre_agc) holds one callback, the IQ display's or Loran-C's: whoever asks for it is refused while
@@ -612,6 +691,7 @@ static void bank_plan_rows(kg_rxbank *b, int i, int nblk)
     bank_iq_plan(b, i, nblk);
     bank_lo_plan(b, i, nblk);
     bank_fa_plan(b, i, nblk);
+    bank_cw_plan(b, i, nblk);
 }
 
 // The active list and, per entry, the counts its audio DDC and its CFastFIR will hand back (kg_rxddc_outputs is kg_rxddc_push_dev's
@@ -627,6 +707,7 @@ static void bank_plan_audio(kg_rxbank *b)
     bank_iq_plan_clear(b);
     bank_lo_plan_clear(b);
     bank_fa_plan_clear(b);
+    bank_cw_plan_clear(b);
     for (int k = 0; k < b->nrx; k++) {
         const bank_rx &r = b->rcv[k];
         p.enabled[k] = r.active ? 1 : 0;
@@ -826,6 +907,7 @@ static int bank_audio_tail(kg_rxbank *b)
     KG_TRY(bank_iq_enqueue(b));
     KG_TRY(bank_lo_enqueue(b));
     KG_TRY(bank_fa_enqueue(b));
+    KG_TRY(bank_cw_enqueue(b));
     KG_TRY(bank_edge(real, b->ev_tail, b->s_tail, nullptr, &b->tail_pending));
     tk.lap(b, PF_EVENTS, real);
     return KG_OK;
@@ -888,6 +970,7 @@ static void bank_commit(kg_rxbank *b)
     bank_iq_commit(b);
     bank_lo_commit(b);
     bank_fa_commit(b);
+    bank_cw_commit(b);
     b->frame_rx.swap(p.chan_of); b->frame_off.swap(p.frame_off); b->pkt_bytes.swap(p.pkt_bytes);
 }
 
@@ -1135,6 +1218,7 @@ static int bank_init(kg_rxbank *b)
     bank_iq_sizes(b);
     bank_lo_sizes(b);
     bank_fa_sizes(b);
+    bank_cw_sizes(b);
     for (std::vector<int32_t> *v : {&b->spec_rx, &b->spec_inst, &b->spec_blk}) v->assign(b->spec_max, 0);
     b->frame_rx.assign(nrx, -1); b->pkt_bytes.assign(nrx, 0); b->frame_off.assign(nrx, 0);
     memset(&b->arena, 0, sizeof b->arena);
@@ -1155,6 +1239,7 @@ void kg_rxbank_destroy(kg_rxbank *b)
     kg_iqd_destroy(b->iq.obj);
     kg_lorc_destroy(b->lo.obj);
     kg_fax_destroy(b->fa.obj);
+    kg_cw_destroy(b->cw.obj);
     kg_adpcm_destroy(b->adpcm); kg_post_destroy(b->post); kg_fir_destroy(b->nullfir); kg_fir_destroy(b->fir); kg_rxddc_destroy(b->rx); kg_nb_destroy(b->nb);
     kg_wf_destroy(b->wf); kg_ddc_destroy(b->ddc);
     kg_ctx_destroy(b->c_tail); kg_ctx_destroy(b->c_side); kg_ctx_destroy(b->c_main);
@@ -1389,6 +1474,7 @@ int kg_rxbank_fax_start(kg_rxbank *b, int rx, int lpm, int imagewidth, int carri
                         int debug, double nom_rate, double srate)
 {
     BANK_EXT("kg_rxbank_fax_start", bank_fa_ensure);
+    KG_TRY(bank_real_tap_free(b, rx, "kg_rxbank_fax_start", false));
     KG_REQUIRE(imagewidth <= BANK_FAX_MAX_WIDTH, KG_ERR_INVALID, "kg_rxbank_fax_start: imagewidth %d; a receiver bank takes %d or fewer", imagewidth,
                BANK_FAX_MAX_WIDTH);
     KG_REQUIRE(!(lpm >= 1 && nom_rate >= 1) || nom_rate * 60.0 / lpm >= BANK_FAX_MIN_SPL, KG_ERR_INVALID,
@@ -1422,6 +1508,66 @@ int kg_rxbank_fax_out(kg_rxbank *b, uint8_t **d_rows, size_t *row_stride, kg_fax
     if (d_recs) *d_recs = x.d_recs;
     if (d_counts) *d_counts = x.d_counts;
     if (max_lines) *max_lines = x.max_lines;
+    if (rx_of_entry && x.last.n) memcpy(rx_of_entry, x.last.rx.data(), sizeof(int32_t) * (size_t) x.last.n);
+    return x.last.n;
+}
+
+int kg_rxbank_cw_start(kg_rxbank *b, int rx, int training_interval, double nom_rate, double srate)
+{
+    BANK_EXT("kg_rxbank_cw_start", bank_cw_ensure);
+    KG_TRY(bank_real_tap_free(b, rx, "kg_rxbank_cw_start", true));
+    KG_TRY(kg_cw_start(b->cw.obj, rx, training_interval, nom_rate, srate));
+    b->cw.on[rx] = 1;
+    return KG_OK;
+}
+
+int kg_rxbank_cw_set_wpm(kg_rxbank *b, int rx, int wpm, int training_interval)
+{
+    BANK_EXT("kg_rxbank_cw_set_wpm", bank_cw_ensure);
+    return kg_cw_set_wpm(b->cw.obj, rx, wpm, training_interval);
+}
+
+int kg_rxbank_cw_set_pboff(kg_rxbank *b, int rx, uint32_t pboff) { BANK_EXT("kg_rxbank_cw_set_pboff", bank_cw_ensure); return kg_cw_set_pboff(b->cw.obj, rx, pboff); }
+
+int kg_rxbank_cw_set_wsc(kg_rxbank *b, int rx, int wsc) { BANK_EXT("kg_rxbank_cw_set_wsc", bank_cw_ensure); return kg_cw_set_wsc(b->cw.obj, rx, wsc); }
+
+int kg_rxbank_cw_set_auto_threshold(kg_rxbank *b, int rx, int on)
+{
+    BANK_EXT("kg_rxbank_cw_set_auto_threshold", bank_cw_ensure);
+    return kg_cw_set_auto_threshold(b->cw.obj, rx, on);
+}
+
+int kg_rxbank_cw_set_threshold(kg_rxbank *b, int rx, int threshold)
+{
+    BANK_EXT("kg_rxbank_cw_set_threshold", bank_cw_ensure);
+    return kg_cw_set_threshold(b->cw.obj, rx, threshold);
+}
+
+int kg_rxbank_cw_stop(kg_rxbank *b, int rx)
+{
+    BANK_EXT("kg_rxbank_cw_stop", bank_cw_ensure);
+    KG_TRY(kg_cw_stop(b->cw.obj, rx));
+    b->cw.on[rx] = 0;
+    return KG_OK;
+}
+
+int kg_rxbank_cw_set_now(kg_rxbank *b, uint32_t now_sec)
+{
+    KG_REQUIRE(b != nullptr, KG_ERR_INVALID, "kg_rxbank_cw_set_now: null handle");
+    b->cw.now = now_sec;                        // the plan of every later step copies it into the step's table
+    return KG_OK;
+}
+
+kg_cw *kg_rxbank_cw(kg_rxbank *b) { return b ? b->cw.obj : nullptr; }
+
+int kg_rxbank_cw_out(kg_rxbank *b, kg_cw_ev **d_evs, int32_t **d_counts, int32_t *max_events, int32_t *rx_of_entry, int max_entries)
+{
+    KG_REQUIRE(b != nullptr && max_entries >= 0, KG_ERR_INVALID, "kg_rxbank_cw_out: bad argument");
+    const bank_cw &x = b->cw;
+    KG_REQUIRE(!rx_of_entry || max_entries >= x.last.n, KG_ERR_INVALID, "kg_rxbank_cw_out: %d entries, room for %d", x.last.n, max_entries);
+    if (d_evs) *d_evs = x.d_evs;                                        // null until the extension was named
+    if (d_counts) *d_counts = x.d_counts;
+    if (max_events) *max_events = x.max_events;
     if (rx_of_entry && x.last.n) memcpy(rx_of_entry, x.last.rx.data(), sizeof(int32_t) * (size_t) x.last.n);
     return x.last.n;
 }

@@ -407,6 +407,62 @@ class RxBank:
             out[int(rxs[e])] = (recs, rows)
         return out
 
+    # ---- the CW decoder extension (extensions/CW_decoder/uhsdr_cw_decoder.cpp, cw_decoder.cpp): kg_cw's commands per receiver
+    def cw_start(self, rx, training_interval=100, nom_rate=12000.0, srate=None):
+        """`SET cw_start=` / `SET cw_train=`; refused while FAX is started on the receiver (the real-samples tap holds one task)"""
+        check(self.lib.kg_rxbank_cw_start(self.h, int(rx), int(training_interval), float(nom_rate), float(nom_rate if srate is None else srate)),
+              "kg_rxbank_cw_start")
+
+    def cw_set_wpm(self, rx, wpm, training_interval=100):
+        check(self.lib.kg_rxbank_cw_set_wpm(self.h, int(rx), int(wpm), int(training_interval)), "kg_rxbank_cw_set_wpm")
+        return "EXT cw_train=0" if int(wpm) != 0 else None
+
+    def cw_set_pboff(self, rx, pboff):
+        check(self.lib.kg_rxbank_cw_set_pboff(self.h, int(rx), int(pboff) & 0xffffffff), "kg_rxbank_cw_set_pboff")
+
+    def cw_set_wsc(self, rx, wsc):
+        check(self.lib.kg_rxbank_cw_set_wsc(self.h, int(rx), int(wsc)), "kg_rxbank_cw_set_wsc")
+
+    def cw_set_auto_threshold(self, rx, on):
+        check(self.lib.kg_rxbank_cw_set_auto_threshold(self.h, int(rx), int(on)), "kg_rxbank_cw_set_auto_threshold")
+
+    def cw_set_threshold(self, rx, threshold):
+        check(self.lib.kg_rxbank_cw_set_threshold(self.h, int(rx), int(threshold)), "kg_rxbank_cw_set_threshold")
+
+    def cw_stop(self, rx):
+        check(self.lib.kg_rxbank_cw_stop(self.h, int(rx)), "kg_rxbank_cw_stop")
+
+    def cw_set_now(self, now_sec):
+        """what timer_sec() answers during every later step"""
+        check(self.lib.kg_rxbank_cw_set_now(self.h, int(now_sec) & 0xffffffff), "kg_rxbank_cw_set_now")
+
+    @property
+    def cw(self):
+        """the bank's CwDecoder (None until one of the per-receiver cw_* commands was sent): state()"""
+        from . import cw as cw_mod
+        h = self.lib.kg_rxbank_cw(self.h)
+        return borrow(cw_mod.CwDecoder, self.ctx, h, nconn=self.nrx) if h else None
+
+    def cw_out(self):
+        """-> {receiver: events of cw.ev_dtype -- blk the sound block of the step --} of the last step (after sync()): the receivers the
+        step fed"""
+        from . import cw as cw_mod
+        rxs = np.zeros(self.nrx, np.int32)
+        d_evs, d_counts, me = C.c_void_p(), C.c_void_p(), C.c_int32()
+        n = check(self.lib.kg_rxbank_cw_out(self.h, C.byref(d_evs), C.byref(d_counts), C.byref(me), ptr(rxs), int(rxs.size)), "kg_rxbank_cw_out")
+        out = {}
+        if n == 0:
+            return out
+        counts = np.zeros((n, 4), np.int32)
+        self.ctx.download(int(d_counts.value), counts)
+        assert not counts[:, 2].any(), "the event capacity was exceeded"
+        for e in range(n):
+            evs = np.zeros(int(counts[e, 0]), cw_mod.ev_dtype)
+            if evs.size:
+                self.ctx.download(int(d_evs.value) + e * me.value * cw_mod.ev_dtype.itemsize, evs)
+            out[int(rxs[e])] = evs
+        return out
+
     def fftext_set_rate(self, sample_rate):
         """what ext_update_get_sample_rateHz answers for the FFT extension (extensions/FFT/FFT.cpp:79)"""
         check(self.lib.kg_rxbank_fftext_set_rate(self.h, float(sample_rate)), "kg_rxbank_fftext_set_rate")

@@ -1464,6 +1464,86 @@ int kg_fax_push(kg_fax *q, const int32_t *conns, int nconn, const int32_t *nblk,
  * (zeros while m_imageline is 0) and m_outImage, KG_FAX_MAX_SPL entries each (any may be NULL).  Synchronises. */
 int kg_fax_state(kg_fax *q, int conn, kg_fax_info *info, int16_t *samples, uint8_t *demod, uint8_t *prev, uint8_t *out);
 
+/* ---- The CW decoder extension (extensions/CW_decoder/uhsdr_cw_decoder.cpp, cw_decoder.cpp): Morse code from the 16-bit mono audio a
+ * sound block ends as, taken by the real-samples task tap.  Per block of 88 samples a Goertzel magnitude at the passband offset; per
+ * magnitude a threshold (fixed or automatic), a ring of mark / space durations, the training of the dot, dash and space averages, the
+ * recognition of characters with two corrective actions, the PARIS speed.  Every event is an exact function of the samples and of
+ * now_sec: csrc/kg_cw.h is the one definition for device and host, in the reference's operand types, and cites the reference lines item
+ * by item.
+ *
+ * The SCHEDULE depends on the samples, so the whole cw_decoder_t of a connection lives on the device and a push's outputs carry counts
+ * the DEVICE writes: for entry i of the list, with max_events the capacity the caller chose (kg_cw_max_events gives the least one),
+ *   counts[4*i]      events;  counts[4*i + 1]  Goertzel blocks completed;  counts[4*i + 2]  1 if the capacity was exceeded (never, by the bound)
+ *   evs + i*max_events + k                    event k (kg_cw_ev)
+ * TIME IS AN INPUT: the reference reads timer_sec() for `cw_wpm` (at most once per 4 s, :983-987) and for err_timeout (:1277, :1289); a
+ * push carries now_sec[i], which holds for every block of entry i.  No host clock is read.
+ * Defined here where the reference leaves it open (csrc/kg_cw.h has each): `static int slowdown` (:519) is per connection; the float to
+ * uint8_t / int16_t conversions of :606 and :1007 are x86-64 gcc's; data[data_len - 1] with data_len 0 (:862, :874) reads sig_timer.
+ * Refused with nothing changed: training_interval outside 1 .. 255, wpm negative, a pboff whose Goertzel bin leaves 0 .. 44 or before the
+ * first start, a nominal rate outside 88 .. 1e6 Hz, a sample rate that is not finite, not positive or outside half to twice the nominal.
+ * Not ported: the test-file player, cw_task's sequence numbers, the printfs. */
+typedef struct kg_cw kg_cw;
+#define KG_CW_BLK 512                                      /* FASTFIR_OUTBUF_SIZE, cw_decoder.cpp:101 */
+#define KG_CW_GBLK 88                                      /* CW_DECODER_BLOCKSIZE_DEFAULT, uhsdr_cw_decoder.h:23 */
+#define KG_CW_EVENTS_PER_GBLK 7                            /* csrc/kg_cw.h derives it */
+enum { KG_CW_CHARS = 0, KG_CW_WPM = 1, KG_CW_TRAIN = 2, KG_CW_PLOT = 3 };  /* cw_chars :961, cw_wpm :985, cw_train :672 :1278 :1292, cw_plot :525 */
+typedef struct kg_cw_ev {                  /* one message of ext_send_msg / ext_send_msg_encoded */
+    int32_t blk;                           /* the sound block of the push in which the Goertzel block ended */
+    int32_t gblk;                          /* the Goertzel block among those that ended in that sound block */
+    int32_t kind;                          /* KG_CW_* */
+    int32_t a, b, c;                       /* CHARS a: the character, the prosign index 0..11 (<aa> <ar> <as> <bk> <bt> <cl> <ct> <hh> <kn> <nj> <sk> <sn>),
+                                              0xff for [err], or ' ';  WPM a: the speed;  TRAIN a: the value, negative for the error count;
+                                              PLOT a, c: the bits of the two floats of `%.2f`, b: the flag */
+} kg_cw_ev;
+typedef struct kg_cw_info {                /* cw_decoder_t (:106-174), what the port keeps of it; a sigbuf_t is bit 0 state, bits 1..31 time */
+    int32_t process_samples; uint32_t wpm_update; int32_t wsc, err_cnt, err_timeout; float sampling_freq; int32_t speed, isAutoThreshold;
+    uint32_t weight_linear, threshold_linear; int32_t blocksize;
+    int32_t g_a; float g_b, g_sin, g_cos, g_r;             /* Goertzel (:71-79); b0..b2 are zero between blocks */
+    int32_t sig_lastrx, sig_incount, sig_outcount, sig_timer;
+    int32_t data_len; uint32_t code; int32_t state, initialized, dash, wspace, timeout, track;
+    float pulse_avg, dot_avg, dash_avg, symspace_avg, cwspace_avg; int32_t w_space;
+    int32_t timer_stepsize, cur_time, cur_outcount, last_outcount;
+    float CW_env, CW_mag, CW_noise, old_siglevel, speed_wpm_avg;
+    int32_t prevstate, noisecancel_change, sample_counter, startpos, progress, initializing, processed, training_interval;
+    int32_t snd_rate, slowdown, started, pad0, pad1;       /* snd_rate (:59), the static of :519, the task tap (cw_decoder.cpp:149) */
+    uint32_t sig[256];
+    uint32_t data[40];
+    float raw[88];                         /* raw_signal_buffer (:128) */
+} kg_cw_info;
+/* nconn cw_decoder_t objects (:176), each zeroed as the static array is; 1 .. 256 */
+int kg_cw_create(kg_ctx *ctx, int nconn, kg_cw **out);
+/* nothing in the reference frees them (:176 is static); drains the context's stream first */
+void kg_cw_destroy(kg_cw *q);
+/* `SET cw_start=%d` and `SET cw_train=%d` (cw_decoder.cpp:135-167): CwDecode_Init(rx_chan, 0, training_interval) (:345-392), a memset with
+ * defaults -- the thresholds, the Goertzel and process_samples fall back to 0 until they are sent again -- and the task tap
+ * (cw_decoder.cpp:149).  nom_rate is snd_rate (:59), srate what ext_update_get_sample_rateHz answers now (:356).  One small launch. */
+int kg_cw_start(kg_cw *q, int conn, int training_interval, double nom_rate, double srate);
+/* `SET cw_wpm=%d,%d` (cw_decoder.cpp:186-190): CwDecode_wpm (:628-633), CwDecode_Init with the fixed-WPM branch (:362-385) for wpm != 0; the
+ * rates are those of the last kg_cw_start.  Its `EXT cw_train=0` (:385) is implied by the call. */
+int kg_cw_set_wpm(kg_cw *q, int conn, int wpm, int training_interval);
+/* `SET cw_pboff=%d` (cw_decoder.cpp:179-183): CwDecode_pboff with AudioFilter_CalcGoertzel (:296-305, :394-402); samples are taken from here on */
+int kg_cw_set_pboff(kg_cw *q, int conn, uint32_t pboff);
+/* `SET cw_wsc=%d` (cw_decoder.cpp:193-197): CwDecode_wsc (:1020-1024) */
+int kg_cw_set_wsc(kg_cw *q, int conn, int wsc);
+/* `SET cw_auto_thresh=%d` (cw_decoder.cpp:200-204): CwDecode_threshold type 0 (:1030-1036) */
+int kg_cw_set_auto_threshold(kg_cw *q, int conn, int on);
+/* `SET cw_threshold=%d` (cw_decoder.cpp:207-211): CwDecode_threshold type 1 (:1038) */
+int kg_cw_set_threshold(kg_cw *q, int conn, int threshold);
+/* `SET cw_stop` (cw_decoder.cpp:155-160, cw_close :107-119): no more samples are taken; the decoder stays */
+int kg_cw_stop(kg_cw *q, int conn);
+/* The least max_events of a push of nblk sound blocks (0 .. 256): KG_CW_EVENTS_PER_GBLK for each of the (512 nblk + 87) / 88 Goertzel
+ * blocks it can complete (:620-623); -1 outside that range */
+int kg_cw_max_events(int nblk);
+/* CwDecode_RxProcessor (:609-625) as cw_task calls it (cw_decoder.cpp:101) for nblk[i] blocks (0 .. 256) of 512 samples of connection
+ * conns[i] (each at most once), on HOST arrays: block b of entry i is at s16 + i*stride + 512*b.  now_sec[i] is what timer_sec() answers
+ * during entry i (:983, :1277, :1289).  A connection that is not started, or has had no pboff since its start (:613), takes nothing and
+ * counts zeros.  Outputs as laid out above.  ONE kernel launch.  Synchronises.  (The push on device-resident audio, enqueue only, is the
+ * receiver bank's: kg_rxbank_cw_* below.) */
+int kg_cw_push(kg_cw *q, const int32_t *conns, int nconn, const int32_t *nblk, const int16_t *s16, size_t stride, const uint32_t *now_sec, kg_cw_ev *evs,
+               int max_events, int32_t *counts);
+/* Connection conn's whole object (:106-174), for tests: the scalars, the ring and data[].  Synchronises. */
+int kg_cw_state(kg_cw *q, int conn, kg_cw_info *info);
+
 /* Diagnostics: re-runs the 4096-point stage of the forward FFT of `block` in a
  * stamped build of the kernel and returns 4 s_memrealtime readings (100 MHz):
  * start, inputs + twiddles loaded, transform done, results stored. */
@@ -1681,6 +1761,38 @@ kg_fax *kg_rxbank_fax(kg_rxbank *bank);
  * block of the step.  Any pointer may be NULL.  Returns the number of entries: the receivers the step fed. */
 int kg_rxbank_fax_out(kg_rxbank *bank, uint8_t **d_rows, size_t *row_stride, kg_fax_rec **d_recs, int32_t **d_counts, int32_t *max_lines, int32_t *rx_of_entry,
                       int max_entries);
+
+/* The CW decoder extension of the bank's receivers (kg_cw above; extensions/CW_decoder/uhsdr_cw_decoder.cpp, cw_decoder.cpp).  The first
+ * of the per-receiver calls makes the bank's kg_cw object and its output buffers, grows the step's arena slots by the size of the
+ * extension's table and drains the bank's streams; a bank that was never told holds nothing for the extension and enqueues exactly
+ * what it enqueued without it.  A started receiver is fed exactly as FAX is: while the step puts its blocks on the mono list
+ * (rx_sound.cpp:701-703, :1103; not KG_POST_IQ, _SAS or _QAM), the 16-bit audio of its sound blocks of that step feeds the extension
+ * in place: ONE launch per step over all such receivers, on the tail stream behind FAX's and ahead of the coders' event.
+ * kg_rxbank_join and kg_rxbank_leave give the receiver the zeroed object, not started.  The real-samples task tap holds ONE task per
+ * receiver (ext_register_receive_real_samps_task, cw_decoder.cpp:149, fax.cpp:150): kg_rxbank_cw_start beside a started FAX and
+ * kg_rxbank_fax_start beside a started CW decoder are refused (KG_ERR_STATE); the CW decoder runs beside the IQ display or Loran-C. */
+/* `SET cw_start=%d` / `SET cw_train=%d` (cw_decoder.cpp:135-167): kg_cw_start */
+int kg_rxbank_cw_start(kg_rxbank *bank, int rx, int training_interval, double nom_rate, double srate);
+/* `SET cw_wpm=%d,%d` (cw_decoder.cpp:186-190): kg_cw_set_wpm */
+int kg_rxbank_cw_set_wpm(kg_rxbank *bank, int rx, int wpm, int training_interval);
+/* `SET cw_pboff=%d` (cw_decoder.cpp:179-183): kg_cw_set_pboff */
+int kg_rxbank_cw_set_pboff(kg_rxbank *bank, int rx, uint32_t pboff);
+/* `SET cw_wsc=%d` (cw_decoder.cpp:193-197): kg_cw_set_wsc */
+int kg_rxbank_cw_set_wsc(kg_rxbank *bank, int rx, int wsc);
+/* `SET cw_auto_thresh=%d` (cw_decoder.cpp:200-204): kg_cw_set_auto_threshold */
+int kg_rxbank_cw_set_auto_threshold(kg_rxbank *bank, int rx, int on);
+/* `SET cw_threshold=%d` (cw_decoder.cpp:207-211): kg_cw_set_threshold */
+int kg_rxbank_cw_set_threshold(kg_rxbank *bank, int rx, int threshold);
+/* `SET cw_stop` (cw_decoder.cpp:155-160): kg_cw_stop */
+int kg_rxbank_cw_stop(kg_rxbank *bank, int rx);
+/* what timer_sec() answers (uhsdr_cw_decoder.cpp:983, :1277, :1289) during every later step: it goes into the step's table.  Makes nothing. */
+int kg_rxbank_cw_set_now(kg_rxbank *bank, uint32_t now_sec);
+/* the object (NULL until one of the per-receiver calls above), for kg_cw_state (uhsdr_cw_decoder.cpp:106-174) */
+kg_cw *kg_rxbank_cw(kg_rxbank *bank);
+/* The outputs of the last step (uhsdr_cw_decoder.cpp:525, :672, :961, :985), device memory laid out as kg_cw_push lays its outputs out
+ * (NULL until the extension was named; read behind kg_rxbank_sync): entry e is receiver rx_of_entry[e], in receiver order; an event's
+ * blk is the sound block of the step.  Any pointer may be NULL.  Returns the number of entries: the receivers the step fed. */
+int kg_rxbank_cw_out(kg_rxbank *bank, kg_cw_ev **d_evs, int32_t **d_counts, int32_t *max_events, int32_t *rx_of_entry, int max_entries);
 /* CmdSetWFFreq + CmdSetWFDecim + the sampler mode sample_wf() decides on (rx/rx_waterfall.cpp:962-1008):
  *   overlapped == 0   CmdWFReset + the one-shot sampler every step: the non-overlapped frame (:1005-1041); needs
  *                     8192 * decim <= adc_samples_per_step
