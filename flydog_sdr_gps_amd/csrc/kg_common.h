@@ -186,6 +186,16 @@ static inline int kg_ctx_use(kg_ctx *ctx)
     return KG_OK;
 }
 
+// The whole destroy of an object that owns nothing beyond its members (null passes): its context's stream is drained first,
+// because kernels enqueued there may still use the device memory that `delete` releases.
+template <typename T> static inline void kg_drain_delete(T *obj)
+{
+    if (!obj) return;
+    (void) hipSetDevice(obj->ctx->device);
+    (void) hipStreamSynchronize(obj->ctx->stream);
+    delete obj;
+}
+
 // The DDCs' NCO reads: ph holds the 48-bit accumulator in its top bits, the table index is its top 13 (KG_NCO_* below).
 // (What the table reads cost -- against no reads at all, and against the hardware's v_sin_f32 / v_cos_f32 -- was measured
 // once with two builds that computed wrong values: profiles/r06_nco_knockout.txt)

@@ -16,11 +16,8 @@
 //     the event records.
 // LDS: 1490 * 4 + sizeof(state_t) (1760) + 16 = 7736 bytes a workgroup; four waves a workgroup.  Neither bounds the occupancy: a push
 // has one workgroup per connection, at most 256 of them.
-#include "kg_common.h"
+#include "kg_ext.h"
 #include "kg_cw.h"
-
-#include <new>
-#include <vector>
 
 using namespace kg_cw_cf;
 
@@ -141,13 +138,7 @@ static int cw_table(kg_cw *q, const int32_t *conns, int nconn, const int32_t *nb
     std::vector<char> listed((size_t) q->nconn, 0);
     for (int i = 0; i < nconn; i++) {
         const int c = conns[i];
-        KG_REQUIRE(c >= 0 && c < q->nconn, KG_ERR_INVALID, "%s: conns[%d] = %d of %d", who, i, c, q->nconn);
-        KG_REQUIRE(!listed[c], KG_ERR_INVALID, "%s: connection %d is listed twice", who, c);
-        listed[c] = 1;
-        KG_REQUIRE(nblk[i] >= 0 && nblk[i] <= CW_MAX_BLK, KG_ERR_INVALID, "%s: nblk[%d] = %d (0..%d)", who, i, nblk[i], CW_MAX_BLK);
-        KG_REQUIRE(nblk[i] <= 0 || nconn == 1 || in_off || stride >= (size_t) BLK * nblk[i], KG_ERR_INVALID, "%s: stride %zu below the %d blocks of entry %d", who,
-                   stride, nblk[i], i);
-        KG_REQUIRE(!in_off || in_off[i] >= 0, KG_ERR_INVALID, "%s: sample offset %lld of entry %d", who, in_off ? (long long) in_off[i] : 0, i);
+        KG_TRY(kg_ext_list_entry(who, listed, nconn, i, c, nblk[i], CW_MAX_BLK, "stride", stride, BLK, in_off != nullptr, "sample offset", in_off ? in_off[i] : 0));
         cw_entry e;
         memset(&e, 0, sizeof e);
         e.conn = c; e.nblk = nblk[i]; e.max_events = max_events_;
@@ -207,42 +198,20 @@ extern "C" {
 
 int kg_cw_create(kg_ctx *ctx, int nconn, kg_cw **out)
 {
-    int rc = kg_ctx_use(ctx);
-    if (rc) return rc;
-    KG_REQUIRE(out != nullptr, KG_ERR_INVALID, "kg_cw_create: out is null");
-    *out = nullptr;
-    KG_REQUIRE(nconn >= 1 && nconn <= CW_MAX_CONNS, KG_ERR_INVALID, "kg_cw_create: nconn %d (1..%d)", nconn, CW_MAX_CONNS);
-    kg_cw *q = new (std::nothrow) kg_cw();
-    KG_REQUIRE(q != nullptr, KG_ERR_NOMEM, "kg_cw_create: alloc");
-    q->ctx = ctx; q->nconn = nconn;
-    q->c.resize(nconn);
-    for (cw_conn &c : q->c) memset(&c, 0, sizeof c);
-    rc = q->d_state.alloc((size_t) nconn, "kg_cw_create: connection state");
-    if (rc) { kg_cw_destroy(q); return rc; }
-    if (hipMemsetAsync(q->d_state.p, 0, sizeof(state_t) * (size_t) nconn, ctx->stream) != hipSuccess) {
-        kg_set_error("kg_cw_create: hipMemsetAsync failed");
-        kg_cw_destroy(q);
-        return KG_ERR_HIP;
-    }
-    *out = q;
-    return KG_OK;
+    return kg_ext_create(ctx, nconn, CW_MAX_CONNS, "kg_cw_create", "nconn", out, [=](kg_cw *q) {
+        q->nconn = nconn;
+        q->c.resize(nconn);
+        for (cw_conn &c : q->c) memset(&c, 0, sizeof c);
+        KG_TRY(q->d_state.alloc((size_t) nconn, "kg_cw_create: connection state"));
+        return kg_ext_zero(ctx, q->d_state.p, (size_t) nconn, "kg_cw_create");
+    });
 }
 
-void kg_cw_destroy(kg_cw *q)
-{
-    if (!q) return;
-    (void) hipSetDevice(q->ctx->device);
-    (void) hipStreamSynchronize(q->ctx->stream);
-    delete q;
-}
-
-#define CW_CONN(who)                                                                                 \
-    KG_REQUIRE(q != nullptr, KG_ERR_INVALID, who ": null handle");                                    \
-    KG_REQUIRE(conn >= 0 && conn < q->nconn, KG_ERR_INVALID, who ": connection %d of %d", conn, q->nconn)
+void kg_cw_destroy(kg_cw *q) { kg_drain_delete(q); }
 
 int kg_cw_start(kg_cw *q, int conn, int training_interval, double nom_rate, double srate)
 {
-    CW_CONN("kg_cw_start");
+    KG_EXT_INDEX("kg_cw_start", q, conn, q->nconn, "connection");
     int rc = kg_ctx_use(q->ctx);
     if (rc) return rc;
     const int bad = start_check(training_interval, nom_rate, srate);
@@ -257,7 +226,7 @@ int kg_cw_start(kg_cw *q, int conn, int training_interval, double nom_rate, doub
 
 int kg_cw_set_wpm(kg_cw *q, int conn, int wpm, int training_interval)
 {
-    CW_CONN("kg_cw_set_wpm");
+    KG_EXT_INDEX("kg_cw_set_wpm", q, conn, q->nconn, "connection");
     int rc = kg_ctx_use(q->ctx);
     if (rc) return rc;
     const cw_conn &k = q->c[conn];
@@ -271,7 +240,7 @@ int kg_cw_set_wpm(kg_cw *q, int conn, int wpm, int training_interval)
 
 int kg_cw_set_pboff(kg_cw *q, int conn, uint32_t pboff)
 {
-    CW_CONN("kg_cw_set_pboff");
+    KG_EXT_INDEX("kg_cw_set_pboff", q, conn, q->nconn, "connection");
     int rc = kg_ctx_use(q->ctx);
     if (rc) return rc;
     const cw_conn &k = q->c[conn];
@@ -284,7 +253,7 @@ int kg_cw_set_pboff(kg_cw *q, int conn, uint32_t pboff)
 
 int kg_cw_set_wsc(kg_cw *q, int conn, int wsc)
 {
-    CW_CONN("kg_cw_set_wsc");
+    KG_EXT_INDEX("kg_cw_set_wsc", q, conn, q->nconn, "connection");
     int rc = kg_ctx_use(q->ctx);
     if (rc) return rc;
     const cw_cmd c = {OP_WSC, wsc, 0, 0, 0.0};
@@ -293,7 +262,7 @@ int kg_cw_set_wsc(kg_cw *q, int conn, int wsc)
 
 int kg_cw_set_auto_threshold(kg_cw *q, int conn, int on)
 {
-    CW_CONN("kg_cw_set_auto_threshold");
+    KG_EXT_INDEX("kg_cw_set_auto_threshold", q, conn, q->nconn, "connection");
     int rc = kg_ctx_use(q->ctx);
     if (rc) return rc;
     const cw_cmd c = {OP_AUTO, on, 0, 0, 0.0};
@@ -302,7 +271,7 @@ int kg_cw_set_auto_threshold(kg_cw *q, int conn, int on)
 
 int kg_cw_set_threshold(kg_cw *q, int conn, int threshold)
 {
-    CW_CONN("kg_cw_set_threshold");
+    KG_EXT_INDEX("kg_cw_set_threshold", q, conn, q->nconn, "connection");
     int rc = kg_ctx_use(q->ctx);
     if (rc) return rc;
     const cw_cmd c = {OP_THRESHOLD, threshold, 0, 0, 0.0};
@@ -311,7 +280,7 @@ int kg_cw_set_threshold(kg_cw *q, int conn, int threshold)
 
 int kg_cw_stop(kg_cw *q, int conn)
 {
-    CW_CONN("kg_cw_stop");
+    KG_EXT_INDEX("kg_cw_stop", q, conn, q->nconn, "connection");
     q->c[conn].started = 0;                     // cw_close (cw_decoder.cpp:107-119): the task tap goes; the decoder stays
     return KG_OK;
 }
@@ -356,7 +325,7 @@ int kg_cw_push(kg_cw *q, const int32_t *conns, int nconn, const int32_t *nblk, c
 
 int kg_cw_state(kg_cw *q, int conn, kg_cw_info *info)
 {
-    CW_CONN("kg_cw_state");
+    KG_EXT_INDEX("kg_cw_state", q, conn, q->nconn, "connection");
     KG_REQUIRE(info != nullptr, KG_ERR_INVALID, "kg_cw_state: info is null");
     int rc = kg_ctx_use(q->ctx);
     if (rc) return rc;

@@ -153,13 +153,7 @@ int kg_eph_create(kg_ctx *ctx, int nchan, kg_eph **out)
     return KG_OK;
 }
 
-void kg_eph_destroy(kg_eph *v)
-{
-    if (!v) return;
-    (void) hipSetDevice(v->ctx->device);
-    (void) hipStreamSynchronize(v->ctx->stream);
-    delete v;
-}
+void kg_eph_destroy(kg_eph *v) { kg_drain_delete(v); }
 
 static int eph_cmd(kg_eph *v, int what, int ch, int sat, int kind)
 {

@@ -18,11 +18,8 @@
 //   phasing     one candidate position per lane, then the workgroup's minimum of (total, position): the first minimum;
 //   decode      one pixel per lane: the integer average, the blend with the previous line, the row;
 // the scalar decisions between them (machine_pre / machine_post / blend_decide / machine_tail of kg_fax.h) are one lane's.
-#include "kg_common.h"
+#include "kg_ext.h"
 #include "kg_fax.h"
-
-#include <new>
-#include <vector>
 
 using namespace kg_fax_cf;
 
@@ -328,13 +325,7 @@ static int fx_table(kg_fax *q, const int32_t *conns, int nconn, const int32_t *n
     std::vector<char> listed((size_t) q->nconn, 0);
     for (int i = 0; i < nconn; i++) {
         const int c = conns[i];
-        KG_REQUIRE(c >= 0 && c < q->nconn, KG_ERR_INVALID, "%s: conns[%d] = %d of %d", who, i, c, q->nconn);
-        KG_REQUIRE(!listed[c], KG_ERR_INVALID, "%s: connection %d is listed twice", who, c);
-        listed[c] = 1;
-        KG_REQUIRE(nblk[i] >= 0 && nblk[i] <= FX_MAX_BLK, KG_ERR_INVALID, "%s: nblk[%d] = %d (0..%d)", who, i, nblk[i], FX_MAX_BLK);
-        KG_REQUIRE(nblk[i] <= 0 || nconn == 1 || in_off || stride >= (size_t) BLK * nblk[i], KG_ERR_INVALID, "%s: stride %zu below the %d blocks of entry %d", who,
-                   stride, nblk[i], i);
-        KG_REQUIRE(!in_off || in_off[i] >= 0, KG_ERR_INVALID, "%s: sample offset %lld of entry %d", who, in_off ? (long long) in_off[i] : 0, i);
+        KG_TRY(kg_ext_list_entry(who, listed, nconn, i, c, nblk[i], FX_MAX_BLK, "stride", stride, BLK, in_off != nullptr, "sample offset", in_off ? in_off[i] : 0));
         const fx_conn &k = q->c[c];
         fx_entry e;
         memset(&e, 0, sizeof e);
@@ -394,43 +385,21 @@ extern "C" {
 
 int kg_fax_create(kg_ctx *ctx, int nconn, kg_fax **out)
 {
-    int rc = kg_ctx_use(ctx);
-    if (rc) return rc;
-    KG_REQUIRE(out != nullptr, KG_ERR_INVALID, "kg_fax_create: out is null");
-    *out = nullptr;
-    KG_REQUIRE(nconn >= 1 && nconn <= FX_MAX_CONNS, KG_ERR_INVALID, "kg_fax_create: nconn %d (1..%d)", nconn, FX_MAX_CONNS);
-    kg_fax *q = new (std::nothrow) kg_fax();
-    KG_REQUIRE(q != nullptr, KG_ERR_NOMEM, "kg_fax_create: alloc");
-    q->ctx = ctx; q->nconn = nconn;
-    q->c.resize(nconn);
-    for (fx_conn &c : q->c) memset(&c, 0, sizeof c);
-    rc = q->d_state.alloc((size_t) nconn, "kg_fax_create: connection state");
-    if (rc) { kg_fax_destroy(q); return rc; }
-    if (hipMemsetAsync(q->d_state.p, 0, sizeof(fx_dev) * (size_t) nconn, ctx->stream) != hipSuccess) {
-        kg_set_error("kg_fax_create: hipMemsetAsync failed");
-        kg_fax_destroy(q);
-        return KG_ERR_HIP;
-    }
-    *out = q;
-    return KG_OK;
+    return kg_ext_create(ctx, nconn, FX_MAX_CONNS, "kg_fax_create", "nconn", out, [=](kg_fax *q) {
+        q->nconn = nconn;
+        q->c.resize(nconn);
+        for (fx_conn &c : q->c) memset(&c, 0, sizeof c);
+        KG_TRY(q->d_state.alloc((size_t) nconn, "kg_fax_create: connection state"));
+        return kg_ext_zero(ctx, q->d_state.p, (size_t) nconn, "kg_fax_create");
+    });
 }
 
-void kg_fax_destroy(kg_fax *q)
-{
-    if (!q) return;
-    (void) hipSetDevice(q->ctx->device);
-    (void) hipStreamSynchronize(q->ctx->stream);
-    delete q;
-}
-
-#define FX_CONN(who)                                                                                 \
-    KG_REQUIRE(q != nullptr, KG_ERR_INVALID, who ": null handle");                                    \
-    KG_REQUIRE(conn >= 0 && conn < q->nconn, KG_ERR_INVALID, who ": connection %d of %d", conn, q->nconn)
+void kg_fax_destroy(kg_fax *q) { kg_drain_delete(q); }
 
 int kg_fax_start(kg_fax *q, int conn, int lpm, int imagewidth, int carrier, int deviation, int bandwidth, int include_headers, int phasing, int autostop, int debug,
                  double nom_rate, double srate)
 {
-    FX_CONN("kg_fax_start");
+    KG_EXT_INDEX("kg_fax_start", q, conn, q->nconn, "connection");
     int rc = kg_ctx_use(q->ctx);
     if (rc) return rc;
     int spl = 0;
@@ -455,7 +424,7 @@ int kg_fax_start(kg_fax *q, int conn, int lpm, int imagewidth, int carrier, int 
 
 int kg_fax_set_shift(kg_fax *q, int conn, float shift)
 {
-    FX_CONN("kg_fax_set_shift");
+    KG_EXT_INDEX("kg_fax_set_shift", q, conn, q->nconn, "connection");
     KG_REQUIRE(shift_ok(shift), KG_ERR_INVALID, "kg_fax_set_shift: shift %g (0 .. 1: a negative skip walks the sample pointer backwards)", (double) shift);
     q->c[conn].shift = shift;
     return KG_OK;
@@ -463,7 +432,7 @@ int kg_fax_set_shift(kg_fax *q, int conn, float shift)
 
 int kg_fax_stop(kg_fax *q, int conn)
 {
-    FX_CONN("kg_fax_stop");
+    KG_EXT_INDEX("kg_fax_stop", q, conn, q->nconn, "connection");
     q->c[conn].started = 0;                     // fax_close (fax.cpp:94-107): the task goes, fax_t is cleared; the decoder stays
     q->c[conn].shift = 0;
     return KG_OK;
@@ -528,7 +497,7 @@ int kg_fax_push(kg_fax *q, const int32_t *conns, int nconn, const int32_t *nblk,
 
 int kg_fax_state(kg_fax *q, int conn, kg_fax_info *info, int16_t *samples, uint8_t *demod, uint8_t *prev, uint8_t *out)
 {
-    FX_CONN("kg_fax_state");
+    KG_EXT_INDEX("kg_fax_state", q, conn, q->nconn, "connection");
     int rc = kg_ctx_use(q->ctx);
     if (rc) return rc;
     const fx_dev *d = q->d_state.p + conn;

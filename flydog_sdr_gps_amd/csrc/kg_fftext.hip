@@ -10,12 +10,9 @@
 // (14 channels: 56 units, not 14), each wave with its CU's whole issue rate -- the work per block is a chain of four log10f behind one
 // load, so what hides its latency is other waves on other units, not more waves in a workgroup; nothing is exchanged between lanes,
 // so the kernel has no LDS and no barrier.
-#include "kg_common.h"
+#include "kg_ext.h"
 #include "kg_fftext.h"
 #include "kg_spec.h"
-
-#include <new>
-#include <vector>
 
 using namespace kg_fftext_cf;
 
@@ -146,34 +143,17 @@ extern "C" {
 
 int kg_fftext_create(kg_ctx *ctx, int nchan, kg_fftext **out)
 {
-    int rc = kg_ctx_use(ctx);
-    if (rc) return rc;
-    KG_REQUIRE(out != nullptr, KG_ERR_INVALID, "kg_fftext_create: out is null");
-    *out = nullptr;
-    KG_REQUIRE(nchan >= 1 && nchan <= FX_MAX_CHANS, KG_ERR_INVALID, "kg_fftext_create: nchan %d (1..%d)", nchan, FX_MAX_CHANS);
-    kg_fftext *fx = new (std::nothrow) kg_fftext();
-    KG_REQUIRE(fx != nullptr, KG_ERR_NOMEM, "kg_fftext_create: alloc");
-    fx->ctx = ctx; fx->nchan = nchan; fx->rate = 0;
-    fx->ch.resize(nchan);
-    for (fx_chan &c : fx->ch) chan_fresh(c, false);
-    const size_t n = (size_t) nchan * MAX_BINS * WIDTH;
-    rc = fx->d_pwr.alloc(n, "kg_fftext_create: sums");
-    if (rc == KG_OK && hipMemsetAsync(fx->d_pwr.p, 0, sizeof(float) * n, ctx->stream) != hipSuccess) {
-        kg_set_error("kg_fftext_create: hipMemsetAsync failed");
-        rc = KG_ERR_HIP;
-    }
-    if (rc) { kg_fftext_destroy(fx); return rc; }
-    *out = fx;
-    return KG_OK;
+    return kg_ext_create(ctx, nchan, FX_MAX_CHANS, "kg_fftext_create", "nchan", out, [=](kg_fftext *fx) {
+        fx->nchan = nchan; fx->rate = 0;
+        fx->ch.resize(nchan);
+        for (fx_chan &c : fx->ch) chan_fresh(c, false);
+        const size_t n = (size_t) nchan * MAX_BINS * WIDTH;
+        KG_TRY(fx->d_pwr.alloc(n, "kg_fftext_create: sums"));
+        return kg_ext_zero(ctx, fx->d_pwr.p, n, "kg_fftext_create");
+    });
 }
 
-void kg_fftext_destroy(kg_fftext *fx)
-{
-    if (!fx) return;
-    (void) hipSetDevice(fx->ctx->device);
-    (void) hipStreamSynchronize(fx->ctx->stream);
-    delete fx;
-}
+void kg_fftext_destroy(kg_fftext *fx) { kg_drain_delete(fx); }
 
 int kg_fftext_set_rate(kg_fftext *fx, double sample_rate)
 {
@@ -183,41 +163,37 @@ int kg_fftext_set_rate(kg_fftext *fx, double sample_rate)
     return KG_OK;
 }
 
-#define FX_CHAN(who)                                                                                  \
-    KG_REQUIRE(fx != nullptr, KG_ERR_INVALID, who ": null handle");                                   \
-    KG_REQUIRE(ch >= 0 && ch < fx->nchan, KG_ERR_INVALID, who ": channel %d of %d", ch, fx->nchan)
-
 int kg_fftext_set_run(kg_fftext *fx, int ch, int run, int is_sam, int is_qam)
 {
-    FX_CHAN("kg_fftext_set_run");
+    KG_EXT_INDEX("kg_fftext_set_run", fx, ch, fx->nchan, "channel");
     KG_REQUIRE(cmd_run(fx->ch[ch].st, run, is_sam != 0, is_qam != 0) == 0, KG_ERR_INVALID, "kg_fftext_set_run: run %d (-1..2)", run);
     return KG_OK;
 }
 
 int kg_fftext_set_itime(kg_fftext *fx, int ch, double itime)
 {
-    FX_CHAN("kg_fftext_set_itime");
+    KG_EXT_INDEX("kg_fftext_set_itime", fx, ch, fx->nchan, "channel");
     cmd_itime(fx->ch[ch].st, itime);
     return KG_OK;
 }
 
 int kg_fftext_clear(kg_fftext *fx, int ch)
 {
-    FX_CHAN("kg_fftext_clear");
+    KG_EXT_INDEX("kg_fftext_clear", fx, ch, fx->nchan, "channel");
     cmd_clear(fx->ch[ch].st);
     return KG_OK;
 }
 
 int kg_fftext_restart(kg_fftext *fx, int ch)
 {
-    FX_CHAN("kg_fftext_restart");
+    KG_EXT_INDEX("kg_fftext_restart", fx, ch, fx->nchan, "channel");
     chan_fresh(fx->ch[ch], true);
     return KG_OK;
 }
 
 int kg_fftext_due(kg_fftext *fx, int ch, uint32_t now_ms)
 {
-    FX_CHAN("kg_fftext_due");
+    KG_EXT_INDEX("kg_fftext_due", fx, ch, fx->nchan, "channel");
     return due(fx->ch[ch].st, now_ms);
 }
 
@@ -322,7 +298,7 @@ int kg_fftext_process(kg_fftext *fx, const int32_t *chans, int nch, const int32_
 
 int kg_fftext_state(kg_fftext *fx, int ch, kg_fftext_info *info, float *pwr, int32_t *ncma)
 {
-    FX_CHAN("kg_fftext_state");
+    KG_EXT_INDEX("kg_fftext_state", fx, ch, fx->nchan, "channel");
     const fx_chan &c = fx->ch[ch];
     if (info) {
         const state_t &e = c.st;

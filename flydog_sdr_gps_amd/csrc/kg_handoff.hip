@@ -129,13 +129,7 @@ int kg_aper_create(kg_ctx *ctx, int nchan, kg_aper **out)
     return KG_OK;
 }
 
-void kg_aper_destroy(kg_aper *a)
-{
-    if (!a) return;
-    (void) hipSetDevice(a->ctx->device);
-    (void) hipStreamSynchronize(a->ctx->stream);
-    delete a;
-}
+void kg_aper_destroy(kg_aper *a) { kg_drain_delete(a); }
 
 int kg_aper_update_dev(kg_aper *a, const int32_t *chans, int nrows, const void *d_rows, size_t row_stride,
                        const kg_aper_cfg *cfg, int waterfall_cal)

@@ -16,11 +16,8 @@
 //      the next lap from overwriting what the copy still reads.
 // With the PLL off A to C's PLL part falls away.  Nothing is reassociated.  One wave a workgroup: a barrier costs a wait for the
 // wave's own memory operations, and 14 channels land on 14 compute units.
-#include "kg_common.h"
+#include "kg_ext.h"
 #include "kg_iqd.h"
-
-#include <new>
-#include <vector>
 
 using namespace kg_iqd_cf;
 
@@ -262,40 +259,23 @@ extern "C" {
 
 int kg_iqd_create(kg_ctx *ctx, int nchan, kg_iqd **out)
 {
-    int rc = kg_ctx_use(ctx);
-    if (rc) return rc;
-    KG_REQUIRE(out != nullptr, KG_ERR_INVALID, "kg_iqd_create: out is null");
-    *out = nullptr;
-    KG_REQUIRE(nchan >= 1 && nchan <= IQ_MAX_CHANS, KG_ERR_INVALID, "kg_iqd_create: nchan %d (1..%d)", nchan, IQ_MAX_CHANS);
-    kg_iqd *q = new (std::nothrow) kg_iqd();
-    KG_REQUIRE(q != nullptr, KG_ERR_NOMEM, "kg_iqd_create: alloc");
-    q->ctx = ctx; q->nchan = nchan;
-    q->ch.resize(nchan);
-    for (iq_chan &c : q->ch) { memset(&c.st, 0, sizeof c.st); c.zflags = Z_ALL; }
-    rc = q->d_state.alloc((size_t) nchan, "kg_iqd_create: channel state");
-    if (rc) { kg_iqd_destroy(q); return rc; }
-    *out = q;
-    return KG_OK;
+    return kg_ext_create(ctx, nchan, IQ_MAX_CHANS, "kg_iqd_create", "nchan", out, [=](kg_iqd *q) {
+        q->nchan = nchan;
+        q->ch.resize(nchan);
+        for (iq_chan &c : q->ch) { memset(&c.st, 0, sizeof c.st); c.zflags = Z_ALL; }      // Z_ALL: the device state needs no zeroing here
+        return q->d_state.alloc((size_t) nchan, "kg_iqd_create: channel state");
+    });
 }
 
-void kg_iqd_destroy(kg_iqd *q)
-{
-    if (!q) return;
-    (void) hipSetDevice(q->ctx->device);
-    (void) hipStreamSynchronize(q->ctx->stream);
-    delete q;
-}
+void kg_iqd_destroy(kg_iqd *q) { kg_drain_delete(q); }
 
-#define IQ_CHAN(who)                                                                                 \
-    KG_REQUIRE(q != nullptr, KG_ERR_INVALID, who ": null handle");                                    \
-    KG_REQUIRE(ch >= 0 && ch < q->nchan, KG_ERR_INVALID, who ": channel %d of %d", ch, q->nchan)
 #define IQ_INITED(who)                                                                               \
-    IQ_CHAN(who);                                                                                     \
+    KG_EXT_INDEX(who, q, ch, q->nchan, "channel");                                                    \
     KG_REQUIRE(q->ch[ch].st.inited, KG_ERR_STATE, who ": channel %d was never initialised (kg_iqd_init)", ch)
 
 int kg_iqd_init(kg_iqd *q, int ch)
 {
-    IQ_CHAN("kg_iqd_init");
+    KG_EXT_INDEX("kg_iqd_init", q, ch, q->nchan, "channel");
     fresh(q->ch[ch].st);
     q->ch[ch].zflags = Z_ALL;
     return KG_OK;
@@ -466,7 +446,7 @@ int kg_iqd_process(kg_iqd *q, const int32_t *chans, int nch, const int32_t *nblk
 
 int kg_iqd_state(kg_iqd *q, int ch, kg_iqd_info *info, float *iq, uint8_t *plot, uint8_t *map)
 {
-    IQ_CHAN("kg_iqd_state");
+    KG_EXT_INDEX("kg_iqd_state", q, ch, q->nchan, "channel");
     int rc = kg_ctx_use(q->ctx);
     if (rc) return rc;
     const iq_chan &c = q->ch[ch];

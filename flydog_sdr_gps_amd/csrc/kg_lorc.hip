@@ -13,11 +13,8 @@
 //   the update one sample a lane, 64 at a time: power, then the rule's recurrence on the sample's own bucket, unreassociated.
 // The two channels of a connection share nothing on the device (their rows' places and commands are the host's), so each has a
 // workgroup of its own; one wave a workgroup makes a barrier a wait for the wave's own memory operations.
-#include "kg_common.h"
+#include "kg_ext.h"
 #include "kg_lorc.h"
-
-#include <new>
-#include <vector>
 
 using namespace kg_lorc_cf;
 
@@ -136,13 +133,8 @@ static int lo_walk(kg_lorc *q, const int32_t *conns, int nconn, const int32_t *n
     plan_t sp;
     for (int i = 0; i < nconn; i++) {
         const int c = conns[i];
-        KG_REQUIRE(c >= 0 && c < q->nconn, KG_ERR_INVALID, "%s: conns[%d] = %d of %d", who, i, c, q->nconn);
-        KG_REQUIRE(!listed[c], KG_ERR_INVALID, "%s: connection %d is listed twice", who, c);
-        listed[c] = 1;
-        KG_REQUIRE(nblk[i] >= 0 && nblk[i] <= LO_MAX_BLK, KG_ERR_INVALID, "%s: nblk[%d] = %d (0..%d)", who, i, nblk[i], LO_MAX_BLK);
-        KG_REQUIRE(nblk[i] <= 0 || nconn == 1 || iq_stride >= (size_t) ns * nblk[i], KG_ERR_INVALID, "%s: iq_stride %zu below the %d blocks of entry %d", who,
-                   iq_stride, nblk[i], i);
-        KG_REQUIRE(!in_row || in_row[i] >= 0, KG_ERR_INVALID, "%s: sample row %d of entry %d", who, in_row ? in_row[i] : 0, i);
+        // a row is a multiple of the stride: the stride bounds an entry's blocks whoever places the rows
+        KG_TRY(kg_ext_list_entry(who, listed, nconn, i, c, nblk[i], LO_MAX_BLK, "iq_stride", iq_stride, (size_t) ns, false, "sample row", in_row ? in_row[i] : 0));
         KG_REQUIRE(q->c[c].st.inited, KG_ERR_STATE, "%s: connection %d was never initialised (kg_lorc_init)", who, c);
         if (!q->c[c].st.started || nblk[i] == 0) continue;             // loran_c_data is not registered: the samples go nowhere
         const int bad = push_check(q->c[c].st);
@@ -239,41 +231,24 @@ extern "C" {
 
 int kg_lorc_create(kg_ctx *ctx, int nconn, kg_lorc **out)
 {
-    int rc = kg_ctx_use(ctx);
-    if (rc) return rc;
-    KG_REQUIRE(out != nullptr, KG_ERR_INVALID, "kg_lorc_create: out is null");
-    *out = nullptr;
-    KG_REQUIRE(nconn >= 1 && nconn <= LO_MAX_CONNS, KG_ERR_INVALID, "kg_lorc_create: nconn %d (1..%d)", nconn, LO_MAX_CONNS);
-    kg_lorc *q = new (std::nothrow) kg_lorc();
-    KG_REQUIRE(q != nullptr, KG_ERR_NOMEM, "kg_lorc_create: alloc");
-    q->ctx = ctx; q->nconn = nconn;
-    q->c.resize(nconn);
-    for (lo_conn &c : q->c) { memset(&c.st, 0, sizeof c.st); c.fresh = 1; }
-    rc = q->d_state.alloc((size_t) nconn, "kg_lorc_create: connection state");
-    if (rc) { kg_lorc_destroy(q); return rc; }
-    *out = q;
-    return KG_OK;
+    return kg_ext_create(ctx, nconn, LO_MAX_CONNS, "kg_lorc_create", "nconn", out, [=](kg_lorc *q) {
+        q->nconn = nconn;
+        q->c.resize(nconn);
+        for (lo_conn &c : q->c) { memset(&c.st, 0, sizeof c.st); c.fresh = 1; }     // fresh: the device state needs no zeroing here
+        return q->d_state.alloc((size_t) nconn, "kg_lorc_create: connection state");
+    });
 }
 
-void kg_lorc_destroy(kg_lorc *q)
-{
-    if (!q) return;
-    (void) hipSetDevice(q->ctx->device);
-    (void) hipStreamSynchronize(q->ctx->stream);
-    delete q;
-}
+void kg_lorc_destroy(kg_lorc *q) { kg_drain_delete(q); }
 
-#define LO_CONN(who)                                                                                 \
-    KG_REQUIRE(q != nullptr, KG_ERR_INVALID, who ": null handle");                                    \
-    KG_REQUIRE(conn >= 0 && conn < q->nconn, KG_ERR_INVALID, who ": connection %d of %d", conn, q->nconn)
 #define LO_INITED(who)                                                                               \
-    LO_CONN(who);                                                                                     \
+    KG_EXT_INDEX(who, q, conn, q->nconn, "connection");                                               \
     KG_REQUIRE(q->c[conn].st.inited, KG_ERR_STATE, who ": connection %d was never initialised (kg_lorc_init)", conn)
 #define LO_CH(who) KG_REQUIRE(ch_ok(ch), KG_ERR_INVALID, who ": Loran channel %d (0..1)", ch)
 
 int kg_lorc_init(kg_lorc *q, int conn, double srate, int i_srate)
 {
-    LO_CONN("kg_lorc_init");
+    KG_EXT_INDEX("kg_lorc_init", q, conn, q->nconn, "connection");
     KG_REQUIRE(srate >= 1 && srate <= 1e9 && i_srate >= 0, KG_ERR_INVALID, "kg_lorc_init: sample rate %g (1 .. 1e9), snd_rate %d", srate, i_srate);
     cmd_init(q->c[conn].st, srate, i_srate);
     q->c[conn].fresh = 1;
@@ -380,7 +355,7 @@ int kg_lorc_plan(kg_lorc *q, const int32_t *conns, int nconn, const int32_t *nbl
 
 int kg_lorc_state(kg_lorc *q, int conn, kg_lorc_info *info, float *avg)
 {
-    LO_CONN("kg_lorc_state");
+    KG_EXT_INDEX("kg_lorc_state", q, conn, q->nconn, "connection");
     int rc = kg_ctx_use(q->ctx);
     if (rc) return rc;
     const lo_conn &c = q->c[conn];

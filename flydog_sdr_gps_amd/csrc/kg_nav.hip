@@ -268,13 +268,7 @@ int kg_nav_create(kg_ctx *ctx, int nchan, kg_nav **out)
     return KG_OK;
 }
 
-void kg_nav_destroy(kg_nav *v)
-{
-    if (!v) return;
-    (void) hipSetDevice(v->ctx->device);
-    (void) hipStreamSynchronize(v->ctx->stream);
-    delete v;
-}
+void kg_nav_destroy(kg_nav *v) { kg_drain_delete(v); }
 
 int kg_nav_set_mode(kg_nav *v, int ch, int mode)
 {

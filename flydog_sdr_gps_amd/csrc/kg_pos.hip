@@ -113,13 +113,7 @@ int kg_pos_create(kg_ctx *ctx, const int32_t kinds[64], double uere, double f_os
     return KG_OK;
 }
 
-void kg_pos_destroy(kg_pos *v)
-{
-    if (!v) return;
-    (void) hipSetDevice(v->ctx->device);
-    (void) hipStreamSynchronize(v->ctx->stream);
-    delete v;
-}
+void kg_pos_destroy(kg_pos *v) { kg_drain_delete(v); }
 
 int kg_pos_set_mode(kg_pos *v, int use_kalman, int plot_e1b)
 {

@@ -1328,13 +1328,7 @@ int kg_post_create(kg_ctx *ctx, int nchan, kg_post **out)
 }
 
 
-void kg_post_destroy(kg_post *p)
-{
-    if (!p) return;
-    (void) hipSetDevice(p->ctx->device);
-    (void) hipStreamSynchronize(p->ctx->stream);
-    delete p;
-}
+void kg_post_destroy(kg_post *p) { kg_drain_delete(p); }
 
 int kg_post_set_agc(kg_post *p, int ch, int agc_on, int use_hang, int threshold, int manual_gain,
                     int slope_factor, int decay, float sample_rate)

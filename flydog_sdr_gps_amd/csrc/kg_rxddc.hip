@@ -476,13 +476,7 @@ int kg_rxddc_create_mode(kg_ctx *ctx, int nchan, size_t max_samples, int mode, k
     return KG_OK;
 }
 
-void kg_rxddc_destroy(kg_rxddc *d)
-{
-    if (!d) return;
-    (void) hipSetDevice(d->ctx->device);
-    (void) hipStreamSynchronize(d->ctx->stream);
-    delete d;
-}
+void kg_rxddc_destroy(kg_rxddc *d) { kg_drain_delete(d); }
 
 // CmdSetRXFreq (rx_sound_cmd.cpp:41-51: i_phase = round(f / adc_clk * 2^48)).  The FPGA keeps
 // its filters running when the frequency changes; so does this: only the increment changes.

@@ -421,13 +421,7 @@ int kg_fir_create(kg_ctx *ctx, int nchan, int max_in, kg_fir **out)
     return KG_OK;
 }
 
-void kg_fir_destroy(kg_fir *f)
-{
-    if (!f) return;
-    (void) hipSetDevice(f->ctx->device);
-    (void) hipStreamSynchronize(f->ctx->stream);
-    delete f;
-}
+void kg_fir_destroy(kg_fir *f) { kg_drain_delete(f); }
 
 static int fir_chan_ok(kg_fir *f, int ch, const char *who)
 {

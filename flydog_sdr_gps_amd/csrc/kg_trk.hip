@@ -115,13 +115,7 @@ int kg_trk_create(kg_ctx *ctx, int nchan, int lo_delay, int cg_delay, kg_trk **o
     return KG_OK;
 }
 
-void kg_trk_destroy(kg_trk *t)
-{
-    if (!t) return;
-    (void) hipSetDevice(t->ctx->device);
-    (void) hipStreamSynchronize(t->ctx->stream);
-    delete t;
-}
+void kg_trk_destroy(kg_trk *t) { kg_drain_delete(t); }
 
 int kg_trk_set_sat(kg_trk *t, int ch, int codegen_init)
 {

@@ -175,13 +175,7 @@ int kg_adpcm_create(kg_ctx *ctx, int nchan, kg_adpcm **out)
     return KG_OK;
 }
 
-void kg_adpcm_destroy(kg_adpcm *a)
-{
-    if (!a) return;
-    (void) hipSetDevice(a->ctx->device);
-    (void) hipStreamSynchronize(a->ctx->stream);
-    delete a;
-}
+void kg_adpcm_destroy(kg_adpcm *a) { kg_drain_delete(a); }
 
 int kg_adpcm_set_state(kg_adpcm *a, int chan, int index, int previous)
 {

@@ -5,12 +5,14 @@ compiled for the host with the reference's flags) and the runner of a script on 
 
 A signal here is a tone at TONE Hz (the centre of the Goertzel bin that pboff 818 selects at 12 kHz) keyed by a list of (key down,
 length in dots): raised edges (a 4 ms Hann window over the keying), Gaussian noise, Gaussian jitter of every length."""
-import hashlib
 import os
-import shutil
-import subprocess
 
 import numpy as np
+
+from flydog_sdr_gps_amd.cw import ev_dtype, info_dtype
+
+from . import script_common
+from .script_common import digest, script_steps  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
@@ -26,24 +28,7 @@ MORSE = {"A": ".-", "B": "-...", "C": "-.-.", "D": "-..", "E": ".", "F": "..-.",
          "8": "---..", "9": "----.", "/": "-..-.", "?": "..--..", "=": "-...-", ".": ".-.-.-", ",": "--..--",
          "<ar>": ".-.-.", "<kn>": "-.--.", "<sk>": "...-.-", "<bt>": "-...-"}
 
-ev_dtype = np.dtype([(n, "<i4") for n in ("blk", "gblk", "kind", "a", "b", "c")])
-_scalars = ([("process_samples", "<i4"), ("wpm_update", "<u4"), ("wsc", "<i4"), ("err_cnt", "<i4"), ("err_timeout", "<i4"), ("sampling_freq", "<f4"), ("speed", "<i4"),
-             ("isAutoThreshold", "<i4"), ("weight_linear", "<u4"), ("threshold_linear", "<u4"), ("blocksize", "<i4"),
-             ("g_a", "<i4"), ("g_b", "<f4"), ("g_sin", "<f4"), ("g_cos", "<f4"), ("g_r", "<f4"),
-             ("sig_lastrx", "<i4"), ("sig_incount", "<i4"), ("sig_outcount", "<i4"), ("sig_timer", "<i4"),
-             ("data_len", "<i4"), ("code", "<u4"), ("state", "<i4"), ("initialized", "<i4"), ("dash", "<i4"), ("wspace", "<i4"), ("timeout", "<i4"), ("track", "<i4"),
-             ("pulse_avg", "<f4"), ("dot_avg", "<f4"), ("dash_avg", "<f4"), ("symspace_avg", "<f4"), ("cwspace_avg", "<f4"), ("w_space", "<i4"),
-             ("timer_stepsize", "<i4"), ("cur_time", "<i4"), ("cur_outcount", "<i4"), ("last_outcount", "<i4"),
-             ("CW_env", "<f4"), ("CW_mag", "<f4"), ("CW_noise", "<f4"), ("old_siglevel", "<f4"), ("speed_wpm_avg", "<f4"),
-             ("prevstate", "<i4"), ("noisecancel_change", "<i4"), ("sample_counter", "<i4"), ("startpos", "<i4"), ("progress", "<i4"), ("initializing", "<i4"),
-             ("processed", "<i4"), ("training_interval", "<i4"),
-             ("snd_rate", "<i4"), ("slowdown", "<i4"), ("started", "<i4"), ("pad0", "<i4"), ("pad1", "<i4")])
-info_dtype = np.dtype(_scalars + [("sig", "<u4", (256,)), ("data", "<u4", (40,)), ("raw", "<f4", (GBLK,))])
-assert ev_dtype.itemsize == 24 and len(_scalars) == 56 and info_dtype.itemsize == 1760
-
-
-def digest(b):
-    return hashlib.sha256(bytes(b)).digest()[:16]
+assert ev_dtype.itemsize == 24 and len(info_dtype.names) == 56 + 3 and info_dtype.itemsize == 1760
 
 
 def max_events(nblk):
@@ -256,44 +241,15 @@ def check_against_golden(g, name, got):
 
 # ---- the host driver
 def build_driver(tmpdir):
-    gxx = shutil.which("g++")
-    assert gxx, "g++ is needed to build the host driver"
-    exe = os.path.join(str(tmpdir), "cw_host_driver")
-    subprocess.run([gxx, "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-o", exe, os.path.join(ROOT, "tools", "cw_host_driver.cpp")], check=True)
-    return exe
+    return script_common.build_driver(tmpdir, "cw_host_driver")
 
 
 def run_script_exe(exe, lines, samples, tmpdir, expect=0, keep_on=False):
-    P = lambda f: os.path.join(str(tmpdir), f)
-    open(P("s.txt"), "w").write("\n".join(lines) + "\n")
-    if not os.path.exists(P("pool.bin")):
-        np.ascontiguousarray(samples, np.int16).tofile(P("pool.bin"))
-    r = subprocess.run([exe] + (["-k"] if keep_on else []) + [P("s.txt"), P("pool.bin"), P("out.bin")])
-    assert r.returncode == expect, (r.returncode, expect)
-    return parse(open(P("out.bin"), "rb").read(), lines) if expect == 0 else None
+    out = script_common.run_script(exe, ["-k"] if keep_on else [], lines, samples, np.int16, tmpdir, expect)
+    return parse(out, lines) if expect == 0 else None
 
 
 # ---- a script on the device object
-def script_steps(lines, cuts):
-    """a script as a list of steps: ("cmd", line) or ("push", [pool offsets], [block numbers]) -- consecutive B lines, cut where `cuts`
-    (a callable: blocks wanted next) says"""
-    steps, seen, want = [], 0, None
-    for l in lines:
-        if l[0] == "B":
-            off = int(l.split()[1])
-            last = steps[-1] if steps else None
-            if last and last[0] == "push" and len(last[1]) < want:
-                last[1].append(off)
-                last[2].append(seen)
-            else:
-                want = int(cuts())
-                steps.append(("push", [off], [seen]))
-            seen += 1
-        else:
-            steps.append(("cmd", l))
-    return steps
-
-
 def apply_command(q, conn, l, now):
     """-> the clock behind the command"""
     a = l.split()

@@ -6,12 +6,14 @@ block scripts, the parser of what the reference harness and the host driver writ
 A fax signal here is an FM tone at 1900 Hz +- 400 Hz (black 1500, white 2300), amplitude 9000, under Gaussian noise; a segment is a
 list of (kind, lines): image lines, the 300 Hz start tone and the 450 Hz stop tone as black / white square waves, phasing lines of 95 %
 black with a 5 % white pulse (or the opposite polarity) rotated by some samples."""
-import hashlib
 import os
-import shutil
-import subprocess
 
 import numpy as np
+
+from flydog_sdr_gps_amd.fax import info_dtype, rec_dtype
+
+from . import script_common
+from .script_common import digest, script_steps  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
@@ -37,20 +39,9 @@ for _name, _fs, _lpm, _sig, _plan in SEGMENTS:
     NBLK[_name] = (_n + BLK - 1) // BLK
     POOL += NBLK[_name] * BLK
 
-rec_dtype = np.dtype([(n, "<i4") for n in ("blk", "off", "type", "typecount", "imageline", "phasingLinesLeft", "skip", "phasing_pos", "flags", "phasingSkipData",
-                                           "ten_pct", "ninety_pct")])
-info_dtype = np.dtype([(n, "<f8") for n in ("nom", "frac", "frac_prev", "ratio", "fi", "lineIncrFrac", "lineIncrAcc", "lineBlend", "carrier", "deviation")]
-                      + [(n, "<i4") for n in ("lpm", "imagewidth", "bandwidth", "include_headers", "use_phasing", "autostop", "autostopped", "debug",
-                                              "skip_header_detection", "spl", "skip", "samp_idx", "lasttype", "typecount", "imageline", "phasingLinesLeft",
-                                              "phasingSkipData", "have_phasing", "fir_current", "started")]
-                      + [("Iprev", "<f4"), ("Qprev", "<f4"), ("fir", "<f4", (2, 17)), ("phasingPos", "<i4", (40,)), ("shift", "<f4"), ("pad", "<i4")])
 assert rec_dtype.itemsize == 48 and info_dtype.itemsize == 472
 IMAGE, START, STOP = 0, 1, 2
 F_SPS_CHANGED, F_AUTOSTOPPED_0, F_AUTOSTOPPED_1, F_PHASED, F_ROW_SENT, F_PHASING_REJECTED, F_MEDIAN = 1, 2, 4, 8, 16, 32, 64
-
-
-def digest(b):
-    return hashlib.sha256(bytes(b)).digest()[:16]
 
 
 def _brightness(kind, n, spl, fs, lpm, line0):
@@ -244,21 +235,12 @@ def check_against_golden(g, name, got):
 
 # ---- the host driver
 def build_driver(tmpdir):
-    gxx = shutil.which("g++")
-    assert gxx, "g++ is needed to build the host driver"
-    exe = os.path.join(str(tmpdir), "fax_host_driver")
-    subprocess.run([gxx, "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-o", exe, os.path.join(ROOT, "tools", "fax_host_driver.cpp")], check=True)
-    return exe
+    return script_common.build_driver(tmpdir, "fax_host_driver")
 
 
 def run_script_exe(exe, lines, samples, tmpdir, expect=0, keep_on=False):
-    P = lambda f: os.path.join(str(tmpdir), f)
-    open(P("s.txt"), "w").write("\n".join(lines) + "\n")
-    if not os.path.exists(P("pool.bin")):
-        np.ascontiguousarray(samples, np.int16).tofile(P("pool.bin"))
-    r = subprocess.run([exe] + (["-k"] if keep_on else []) + [P("s.txt"), P("pool.bin"), P("out.bin")])
-    assert r.returncode == expect, (r.returncode, expect)
-    return parse(open(P("out.bin"), "rb").read(), lines) if expect == 0 else None
+    out = script_common.run_script(exe, ["-k"] if keep_on else [], lines, samples, np.int16, tmpdir, expect)
+    return parse(out, lines) if expect == 0 else None
 
 
 # ---- a script on the device object
@@ -292,26 +274,6 @@ def state_of(q, conn):
     info, samples, demod, prev, out = q.state(conn)
     spl, w = int(info["spl"]), int(info["imagewidth"])
     return {"info": info, "samples": samples[:spl], "demod": demod[:spl], "prev": prev[:w], "out": out[:w]}
-
-
-def script_steps(lines, cuts):
-    """a script as a list of steps: ("cmd", line) or ("push", [pool offsets], [block numbers]) -- consecutive B lines, cut where `cuts`
-    (a callable: blocks wanted next) says"""
-    steps, seen, want = [], 0, None
-    for l in lines:
-        if l[0] == "B":
-            off = int(l.split()[1])
-            last = steps[-1] if steps else None
-            if last and last[0] == "push" and len(last[1]) < want:
-                last[1].append(off)
-                last[2].append(seen)
-            else:
-                want = int(cuts())
-                steps.append(("push", [off], [seen]))
-            seen += 1
-        else:
-            steps.append(("cmd", l))
-    return steps
 
 
 def apply_command(q, conn, l, rate):

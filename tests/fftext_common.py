@@ -5,12 +5,13 @@ tools/fftext_host_driver.cpp (csrc/kg_fftext.h compiled for the host with the re
 device object.
 
 No spectrum of the pool holds a NaN: (int) NaN is undefined in the reference, so NaN input is outside the row's contract."""
-import hashlib
 import os
-import shutil
 import subprocess
 
 import numpy as np
+
+from . import script_common
+from .script_common import digest  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
@@ -23,10 +24,6 @@ USB, SAM, QAM = 2, 11, 15                       # the reference's mode_e numbers
 _S0 = np.float32(20.0 / float(np.float32(32767.0) * np.float32(32767.0) * np.float32(1024.0) * np.float32(1024.0)))
 SCALES = {"1e4": np.float32(_S0 * np.float32(1e4)), "1e6": np.float32(_S0 * np.float32(1e6)), "100": np.float32(_S0 * np.float32(100.0))}
 FFT_SEC = {12000: 1.0 / (12000.0 * 2 / 1024), 20250: 1.0 / (20250.0 * 2 / 1024)}
-
-
-def digest(b):
-    return hashlib.sha256(bytes(b)).digest()[:16]
 
 
 EDGE_STEPS = (-64, -16, -3, -1, 0, 1, 3, 16, 64)
@@ -207,20 +204,12 @@ def check_against_golden(g, name, got):
 
 # ---- the host driver
 def build_driver(tmpdir):
-    gxx = shutil.which("g++")
-    assert gxx, "g++ is needed to build the host driver"
-    exe = os.path.join(str(tmpdir), "fftext_host_driver")
-    subprocess.run([gxx, "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-o", exe, os.path.join(ROOT, "tools", "fftext_host_driver.cpp")], check=True)
-    return exe
+    return script_common.build_driver(tmpdir, "fftext_host_driver")
 
 
 def run_script_exe(exe, lines, spec, tmpdir, expect=0):
-    P = lambda f: os.path.join(str(tmpdir), f)
-    open(P("s.txt"), "w").write("\n".join(lines) + "\n")
-    np.ascontiguousarray(spec, np.complex64).tofile(P("pool.bin"))
-    r = subprocess.run([exe, "script", P("s.txt"), P("pool.bin"), P("out.bin")])
-    assert r.returncode == expect, (r.returncode, expect)
-    return parse(open(P("out.bin"), "rb").read(), nblocks(lines)) if expect == 0 else None
+    out = script_common.run_script(exe, ["script"], lines, spec, np.complex64, tmpdir, expect)
+    return parse(out, nblocks(lines)) if expect == 0 else None
 
 
 def run_limiter_exe(exe, clocks, tmpdir):

@@ -5,12 +5,12 @@ tools/iqd_host_driver.cpp (csrc/kg_iqd.h compiled for the host with the referenc
 object.
 
 Amplitudes stay below 3e4 and no sample is NaN or infinite: overflow inside the power and NaN input are outside the contract."""
-import hashlib
 import os
-import shutil
-import subprocess
 
 import numpy as np
+
+from . import script_common
+from .script_common import digest  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
@@ -25,10 +25,6 @@ SEGMENTS = ("cw", "bpsk", "qpsk", "psk8", "noise", "silence_noise", "msk")
 AT = {n: i * SEG for i, n in enumerate(SEGMENTS)}
 POOL = AT["msk"] + MSK_BLOCKS * 512
 STATE_BYTES = 44 + 24 + 84 + 2 * RING * 8 + 2 * RING * 4 + RING * 2
-
-
-def digest(b):
-    return hashlib.sha256(bytes(b)).digest()[:16]
 
 
 def pool():
@@ -205,21 +201,12 @@ def check_against_golden(g, name, got):
 
 # ---- the host driver
 def build_driver(tmpdir):
-    gxx = shutil.which("g++")
-    assert gxx, "g++ is needed to build the host driver"
-    exe = os.path.join(str(tmpdir), "iqd_host_driver")
-    subprocess.run([gxx, "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-o", exe, os.path.join(ROOT, "tools", "iqd_host_driver.cpp")], check=True)
-    return exe
+    return script_common.build_driver(tmpdir, "iqd_host_driver")
 
 
 def run_script_exe(exe, lines, samples, tmpdir, expect=0):
-    P = lambda f: os.path.join(str(tmpdir), f)
-    open(P("s.txt"), "w").write("\n".join(lines) + "\n")
-    if not os.path.exists(P("pool.bin")):
-        np.ascontiguousarray(samples, np.complex64).tofile(P("pool.bin"))
-    r = subprocess.run([exe, P("s.txt"), P("pool.bin"), P("out.bin")])
-    assert r.returncode == expect, (r.returncode, expect)
-    return parse(open(P("out.bin"), "rb").read(), nblocks(lines)) if expect == 0 else None
+    out = script_common.run_script(exe, [], lines, samples, np.complex64, tmpdir, expect)
+    return parse(out, nblocks(lines)) if expect == 0 else None
 
 
 # ---- a script on the device object

@@ -5,12 +5,14 @@ tools/lorc_host_driver.cpp (csrc/kg_lorc.h compiled for the host with the refere
 object.
 
 Amplitudes stay at or below 3e4 and no sample is NaN or infinite: the contract of csrc/kg_lorc.h."""
-import hashlib
 import os
-import shutil
-import subprocess
 
 import numpy as np
+
+from flydog_sdr_gps_amd.lorc import chan_dtype
+
+from . import script_common
+from .script_common import digest  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
@@ -27,15 +29,8 @@ SILENCE = 3000                                   # leading zeros of "silence_noi
 SCALARS = 16 + 2 * 64
 STATE_BYTES = SCALARS + 2 * MAX_BUCKET * 4
 
-chan_dtype = np.dtype([("gri", "<u4"), ("samp", "<u4"), ("nbucket", "<u4"), ("dsp_samps", "<u4"), ("avg_samps", "<u4"), ("navgs", "<u4"),
-                       ("samp_per_GRI", "<f8"), ("gain", "<f4"), ("max", "<f4"), ("offset", "<i4"), ("avg_algo", "<i4"), ("avg_param_f", "<f8"),
-                       ("avg_param_i", "<i4"), ("restart", "<i4")])
 scalars_dtype = np.dtype([("i_srate", "<u4"), ("redraw_legend", "<i4"), ("srate", "<f8"), ("ch", chan_dtype, (2,))])
 assert chan_dtype.itemsize == 64 and scalars_dtype.itemsize == SCALARS
-
-
-def digest(b):
-    return hashlib.sha256(bytes(b)).digest()[:16]
 
 
 def pool():
@@ -188,21 +183,12 @@ def check_against_golden(g, name, got):
 
 # ---- the host driver
 def build_driver(tmpdir):
-    gxx = shutil.which("g++")
-    assert gxx, "g++ is needed to build the host driver"
-    exe = os.path.join(str(tmpdir), "lorc_host_driver")
-    subprocess.run([gxx, "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-o", exe, os.path.join(ROOT, "tools", "lorc_host_driver.cpp")], check=True)
-    return exe
+    return script_common.build_driver(tmpdir, "lorc_host_driver")
 
 
 def run_script_exe(exe, lines, samples, tmpdir, expect=0, by_runs=False, keep_on=False):
-    P = lambda f: os.path.join(str(tmpdir), f)
-    open(P("s.txt"), "w").write("\n".join(lines) + "\n")
-    if not os.path.exists(P("pool.bin")):
-        np.ascontiguousarray(samples, np.complex64).tofile(P("pool.bin"))
-    r = subprocess.run([exe] + (["-r"] if by_runs else []) + (["-k"] if keep_on else []) + [P("s.txt"), P("pool.bin"), P("out.bin")])
-    assert r.returncode == expect, (r.returncode, expect)
-    return parse(open(P("out.bin"), "rb").read(), nblocks(lines)) if expect == 0 else None
+    out = script_common.run_script(exe, (["-r"] if by_runs else []) + (["-k"] if keep_on else []), lines, samples, np.complex64, tmpdir, expect)
+    return parse(out, nblocks(lines)) if expect == 0 else None
 
 
 # ---- a script on the device object

@@ -6,9 +6,11 @@ checkcrc_e1b on the 25 right-aligned bytes through a CRC-24Q table.  It shares n
 works on packed words.  tests/golden/nav_ref.npz (the reference's own output) is what holds THIS model."""
 import numpy as np
 
+from flydog_sdr_gps_amd.nav import frame_dtype
+
 L1, E1B = 0, 1
 ERR_SLIP, ERR_CRC, ERR_ALERT, ERR_OOS, ERR_PAGE, ERR_PARITY = 1, 2, 3, 4, 5, 16
-frame_dtype = np.dtype([("bit", "<u8"), ("err", "<i4"), ("consumed", "<i4"), ("inverted", "<i4"), ("id", "<i4"), ("data", "u1", (40,))])
+assert frame_dtype.itemsize == 64
 
 L1_UP, L1_INV = [1, 0, 0, 0, 1, 0, 1, 1], [0, 1, 1, 1, 0, 1, 0, 0]
 E1B_UP, E1B_INV = [0, 1, 0, 1, 1, 0, 0, 0, 0, 0], [1, 0, 1, 0, 0, 1, 1, 1, 1, 1]

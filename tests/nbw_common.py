@@ -2,12 +2,13 @@
 tools/make_ref_nbw_golden.py): the seeded pool of int16 streams, the scenarios of tests/golden/nbw_ref.npz and their inputs rebuilt
 from the pool, the digests, and the host driver tools/nbw_host_driver.cpp (csrc/kg_nbw.h compiled for the host with the reference's
 flags)."""
-import hashlib
 import os
-import shutil
 import subprocess
 
 import numpy as np
+
+from . import script_common
+from .script_common import digest  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
@@ -72,10 +73,6 @@ def names(g):
     return [str(n) for n in g["names"]]
 
 
-def digest(b):
-    return hashlib.sha256(bytes(b)).digest()[:16]
-
-
 def script(g, name):
     return [str(l) for l in g[name + "_script"]]
 
@@ -98,11 +95,7 @@ def scenario_input(g, name, streams):
 
 
 def build_driver(tmpdir):
-    gxx = shutil.which("g++")
-    assert gxx, "g++ is needed to build the host driver"
-    exe = os.path.join(str(tmpdir), "nbw_host_driver")
-    subprocess.run([gxx, "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-o", exe, os.path.join(ROOT, "tools", "nbw_host_driver.cpp")], check=True)
-    return exe
+    return script_common.build_driver(tmpdir, "nbw_host_driver")
 
 
 def split_states(raw):

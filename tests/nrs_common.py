@@ -1,12 +1,13 @@
 """What the spectral noise-reduction tests share (tests/test_nrs_cpu.py, test_nrs_gpu.py, test_nrs_bank_gpu.py, tools/fuzz_parity.py):
 the scenarios of tests/golden/nrs_ref.npz (tools/make_ref_nrs_golden.py), their inputs rebuilt from the pool, the digests, and the
 host driver tools/nrs_host_driver.cpp (csrc/kg_nrs.h compiled for the host with the reference's flags)."""
-import hashlib
 import os
-import shutil
 import subprocess
 
 import numpy as np
+
+from . import script_common
+from .script_common import digest  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
@@ -21,10 +22,6 @@ def load():
 
 def names(g):
     return [str(n) for n in g["names"]]
-
-
-def digest(b):
-    return hashlib.sha256(bytes(b)).digest()[:16]
 
 
 def fdigest(a):
@@ -50,11 +47,7 @@ def scenario_input(g, name):
 
 
 def build_driver(tmpdir):
-    gxx = shutil.which("g++")
-    assert gxx, "g++ is needed to build the host driver"
-    exe = os.path.join(str(tmpdir), "nrs_host_driver")
-    subprocess.run([gxx, "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-o", exe, os.path.join(ROOT, "tools", "nrs_host_driver.cpp")], check=True)
-    return exe
+    return script_common.build_driver(tmpdir, "nrs_host_driver")
 
 
 def run_driver(exe, rate, lines, x, tmpdir):

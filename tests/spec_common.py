@@ -4,12 +4,13 @@ the pool's digest, not the spectra), the limiter's clock scripts, the emission s
 tools/spec_host_driver.cpp (csrc/kg_spec.h compiled for the host with the reference's flags).
 
 No spectrum of the pool holds a NaN: (int) NaN is undefined in the reference, so NaN input is outside the row's contract."""
-import hashlib
 import os
-import shutil
 import subprocess
 
 import numpy as np
+
+from . import script_common
+from .script_common import digest  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
@@ -22,10 +23,6 @@ SCALE = (np.float32(_S0 * np.float32(1e6)), np.float32(_S0 * np.float32(0.0004))
 # the reference's mode_e numbers (rx/mode.h:69-70), by name, for the emission scripts
 MODES = ["AM", "AMN", "USB", "LSB", "CW", "CWN", "NBFM", "IQ", "DRM", "USN", "LSN", "SAM", "SAU", "SAL", "SAS", "QAM", "NNFM"]
 NULL_LSB, NULL_USB = 1, 2                       # CHAN_NULL_LSB, CHAN_NULL_USB (rx/wdsp/wdsp.h:7-8)
-
-
-def digest(b):
-    return hashlib.sha256(bytes(b)).digest()[:16]
 
 
 EDGE_STEPS = (-64, -16, -3, -1, 0, 1, 3, 16, 64)
@@ -161,11 +158,7 @@ def emit_golden(g, name):
 
 # ---- the host driver
 def build_driver(tmpdir):
-    gxx = shutil.which("g++")
-    assert gxx, "g++ is needed to build the host driver"
-    exe = os.path.join(str(tmpdir), "spec_host_driver")
-    subprocess.run([gxx, "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-o", exe, os.path.join(ROOT, "tools", "spec_host_driver.cpp")], check=True)
-    return exe
+    return script_common.build_driver(tmpdir, "spec_host_driver")
 
 
 def host_rows(exe, spec, tmpdir):

@@ -1,7 +1,6 @@
 """The standard noise blanker (NB_STD) on the CPU: flydog_sdr_gps_amd/csrc/kg_nb.h -- the arithmetic the kernels share -- through
 tools/nb_host_driver.cpp against the reference's own CNoiseProc (tests/golden/nb_ref.npz, tools/make_ref_nb_golden.py), bit for bit,
 end states included; SetupBlanker's derivation over a grid; the constants and the C ABI."""
-import hashlib
 import os
 import re
 import subprocess
@@ -10,6 +9,7 @@ import numpy as np
 import pytest
 
 from tests import nb_signals
+from tests.script_common import digest_u8 as digest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G = np.load(os.path.join(ROOT, "tests", "golden", "nb_ref.npz"))
@@ -21,10 +21,6 @@ def driver(tmp_path_factory):
     subprocess.run(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-o", exe, os.path.join(ROOT, "tools", "nb_host_driver.cpp")],
                    check=True)
     return exe
-
-
-def digest(b):
-    return np.frombuffer(hashlib.sha256(bytes(b)).digest()[:16], np.uint8)
 
 
 def scenario_input(name):

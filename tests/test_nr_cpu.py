@@ -4,7 +4,6 @@ driver tools/nr_host_driver.cpp, against every unit scenario of tests/golden/nr_
 the reference's own statements) -- BIT-EXACT: every output sample, the end states, the weight vectors through their digests.
 Then the C ABI: the header's NR constants equal the reference's enum values and parameter indices, and the new entry points are
 declared, bound and exported."""
-import hashlib
 import os
 import re
 import shutil
@@ -12,6 +11,8 @@ import subprocess
 
 import numpy as np
 import pytest
+
+from tests import script_common
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
@@ -24,7 +25,7 @@ def digest(b):
     weights are NaN on either machine, with the sign bit of each machine's default NaN)"""
     u = np.frombuffer(bytes(b), np.uint32).copy()
     u[np.isnan(u.view(np.float32))] = 0x7FC00000
-    return hashlib.sha256(u.tobytes()).digest()[:16]
+    return script_common.digest(u.tobytes())
 
 
 @pytest.fixture(scope="module")

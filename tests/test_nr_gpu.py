@@ -4,7 +4,6 @@ through kg_post_set_nr_* and kg_post_nr_process_dev, with the end states through
 kg_post_process_dev equal to the same audio without NR followed by the standalone filters; mixed batches and changing channel
 lists equal to each channel alone; NR-off channels byte-identical to a run that never touched NR; the state semantics of algo
 switches, kg_post_reset and mode changes; argument errors."""
-import hashlib
 import os
 
 import numpy as np
@@ -12,6 +11,7 @@ import pytest
 
 from flydog_sdr_gps_amd import Post, post
 from flydog_sdr_gps_amd._lib import KiwiGpuError
+from tests import script_common
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -27,7 +27,7 @@ def digest(a):
     """as tests/golden/nr_ref.npz keeps the weight vectors: SHA-256 prefix with every NaN as 0x7FC00000"""
     u = np.ascontiguousarray(a, np.float32).view(np.uint32).copy()
     u[np.isnan(u.view(np.float32))] = 0x7FC00000
-    return hashlib.sha256(u.tobytes()).digest()[:16]
+    return script_common.digest(u.tobytes())
 
 
 def run_unit(P, ch, g, name):

@@ -5,7 +5,6 @@ its taps, out_samps_s2, agc_samps_c (the AGC output, or the stereo / nulled pair
 s->isChanNull; per packet every payload byte (ADPCM, raw, IQ pairs in either byte order) and the header -- BIT-EXACT (agc_samps_c
 and the payloads through SHA-256 digests of their bytes, which the golden file keeps instead of the bytes).
 Then: a batch of mixed-mode channels equals each channel run alone, channel lists that change between calls, argument errors."""
-import hashlib
 import os
 
 import numpy as np
@@ -13,6 +12,7 @@ import pytest
 
 from flydog_sdr_gps_amd import Post, post, wire
 from flydog_sdr_gps_amd._lib import KiwiGpuError
+from tests.script_common import digest_u8 as digest
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -28,10 +28,6 @@ S_METER_CAL = np.float32(-13)
 
 def bits(a):
     return np.ascontiguousarray(a).view(np.uint32)
-
-
-def digest(b):
-    return np.frombuffer(hashlib.sha256(bytes(b)).digest()[:16], np.uint8)
 
 
 def run_scenario(ctx, g, name):

@@ -15,18 +15,13 @@ file is kept.
     python tools/make_ref_cw_golden.py [--show]
 """
 import os
-import shutil
 import subprocess
 import sys
-import tempfile
 
-import numpy as np
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import ref_cut
+from ref_cut import ROOT  # ref_cut puts the repository root on sys.path
 from tests import cw_common as C  # noqa: E402
 
-R = os.environ.get("REFERENCE", "/root/reference")
 U, X, HH = "extensions/CW_decoder/uhsdr_cw_decoder.cpp", "extensions/CW_decoder/cw_decoder.cpp", "extensions/CW_decoder/uhsdr_cw_decoder.h"
 
 # file, name, first line, last line, text of the first, text of the last
@@ -80,51 +75,25 @@ PINS = [(U, 51, "#define SIGNAL_TAU 0.1"),
         ("rx/CuteSDR/datatypes.h", 104, "#define K_PI (3.14159265358979323846)")]
 
 
-def read(rel):
-    return open(os.path.join(R, rel), encoding="latin-1").read().split("\n")
-
-
 def build(tmp):
-    for rel, macro, a, b, t1, t2 in CUTS:
-        lines = read(rel)
-        assert lines[a - 1].strip() == t1 and lines[b - 1].strip() == t2, ("cut moved", rel, macro, a, b, lines[a - 1], lines[b - 1])
-        open(os.path.join(tmp, macro + ".inc"), "w", encoding="latin-1").write("\n".join(lines[a - 1:b]) + "\n")
-    for rel, ln, t in PINS:
-        assert " ".join(t.split()) in " ".join(read(rel)[ln - 1].split()), ("statement moved", rel, ln, t, read(rel)[ln - 1])      # white space aside
+    ref_cut.cut(tmp, CUTS, whole=True)
+    ref_cut.pin(PINS, white_space_aside=True)
     exe = os.path.join(tmp, "cw_ref")
     subprocess.run(["g++", "-O2", "-ffp-contract=off", "-w", "-I" + tmp, "-o", exe, os.path.join(ROOT, "tools", "ref", "ref_cw_main.cpp"), "-lm"], check=True)
     return exe
 
 
+def report(name, got, out, k):
+    e = got["evs"]
+    tr = e[e["kind"] == C.TRAIN]["a"]
+    print("   %-20s %4d blocks %5d events, stats %s, train<0 %s, wpm %s\n        %r" % (
+        name, got["nev"].size, e.size, got["stats"][:5].tolist(), tr[tr < 0].tolist(), sorted(set(e[e["kind"] == C.WPM]["a"].tolist())), C.text_of(e)))
+    if "--show" in sys.argv:
+        print("        train:", tr.tolist()[:80])
+
+
 def main():
-    show = "--show" in sys.argv
-    out = {}
-    samples = C.pool()
-    out["pool_sha"] = np.frombuffer(C.digest(samples.tobytes()), np.uint8)
-    sc = C.scripts()
-    out["script_names"] = np.array(sorted(sc))
-    with tempfile.TemporaryDirectory() as tmp:
-        exe = build(tmp)
-        for name in sorted(sc):
-            got = C.run_script_exe(exe, sc[name], samples, tmp)
-            k = "s_%s_" % name
-            out[k + "script_sha"] = np.frombuffer(C.digest("\n".join(sc[name]).encode()), np.uint8)
-            for key, v in C.golden_of(got).items():
-                out[k + key] = v
-            e = got["evs"]
-            tr = e[e["kind"] == C.TRAIN]["a"]
-            print("   %-20s %4d blocks %5d events, stats %s, train<0 %s, wpm %s\n        %r" % (
-                name, got["nev"].size, e.size, got["stats"][:5].tolist(), tr[tr < 0].tolist(), sorted(set(e[e["kind"] == C.WPM]["a"].tolist())), C.text_of(e)))
-            if show:
-                print("        train:", tr.tolist()[:80])
-        path = os.path.join(tmp, "cw_ref.npz")
-        np.savez_compressed(path, **out)
-        if "--nocheck" not in sys.argv:
-            from tests.test_cw_cpu import golden_conditions
-            golden_conditions(np.load(path), os.path.getsize(path))
-        final = os.path.join(C.GOLD, "cw_ref.npz")
-        shutil.copyfile(path, final)
-    print("wrote %s, %d bytes" % (final, os.path.getsize(final)))
+    ref_cut.script_golden_main(C, build, "cw_ref.npz", ref_cut.script_by_digest, report, check="--nocheck" not in sys.argv)
 
 
 if __name__ == "__main__":

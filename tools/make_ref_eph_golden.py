@@ -12,49 +12,47 @@ The conditions at the end keep every later test from passing on an empty set.
 """
 import os
 import subprocess
-import sys
 import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import ref_cut
+from ref_cut import ROOT, read  # ref_cut puts the repository root on sys.path
 from flydog_sdr_gps_amd import eph, nav  # noqa: E402
 
 GOLD = os.path.join(ROOT, "tests", "golden")
-R = os.environ.get("REFERENCE", "/root/reference")
 GPSH, GPSC, EH, EC, SOLVE, CH = "gps/gps.h", "gps/gps.cpp", "gps/ephemeris.h", "gps/ephemeris.cpp", "gps/solve.cpp", "gps/channel.cpp"
 RTKH, RTK, NAVC, GAL, SDRH = ("gps/GNSS-SDRLIB/rtklib.h", "gps/GNSS-SDRLIB/rtkcmn.cpp", "gps/GNSS-SDRLIB/sdrnav.cpp", "gps/GNSS-SDRLIB/sdrnav_gal.cpp",
                               "gps/GNSS-SDRLIB/gnss_sdrlib.h")
 
-# (macro, file, first, last, text of the first line, text of the last line)
+# (file, macro, first, last, text of the first line, text of the last line)
 CUTS = [
-    ("EPH_CUT_GPS_RATES", GPSH, 46, 55, "#define CPS 1.023e6", "#define E1B_BPS 250.0"),
-    ("EPH_CUT_GPS_CONST", GPSH, 87, 94, "const double PI = 3.1415926535898;", "const double F = -4.442807633e-10;"),
-    ("EPH_CUT_GPSERR", GPSH, 187, 191, "#define GPS_ERR_SLIP    1", "#define GPS_ERR_PAGE    5"),
-    ("EPH_CUT_UMS", GPSH, 289, 296, "struct UMS {", "};"),
-    ("EPH_CUT_BIN", GPSC, 32, 36, "unsigned bin(char *s, int n) {", "}"),
-    ("EPH_CUT_EPHEM_H", EH, 23, 82, "class EPHEM {", "};"),
-    ("EPH_CUT_EPHEM_TIME", EC, 31, 47, "static double TimeFromEpoch(double t, double t_ref) {", "};"),
-    ("EPH_CUT_EPHEM_SUB", EC, 51, 110, "void EPHEM::Subframe1(char *nav) {", "}"),
-    ("EPH_CUT_EPHEM_POS", EC, 114, 207, "double EPHEM::TimeOfEphemerisAge(double t) const {", "}"),
-    ("EPH_CUT_EPHEM_FRAME", EC, 211, 252, "void EPHEM::Init(int sat) {", "}"),
-    ("EPH_CUT_EPHEM_PAGES", EC, 256, 370, "void EPHEM::PageN(unsigned page) {", "}"),
-    ("EPH_CUT_SNAPSHOT", SOLVE, 42, 52, "struct SNAPSHOT {", "};"),
-    ("EPH_CUT_GETCLOCK", SOLVE, 168, 244, "double SNAPSHOT::GetClock() const {", "}"),
-    ("EPH_CUT_SC2RAD", RTKH, 61, 61, "#define SC2RAD      3.1415926535898 ", "#define SC2RAD"),
-    ("EPH_CUT_P2", RTKH, 421, 444, "#define P2_5        0.03125 ", "#define P2_55       2.775557561562891E-17"),
-    ("EPH_CUT_GTIME", RTKH, 464, 467, "typedef struct {        /* time struct */", "} gtime_t;"),
-    ("EPH_CUT_EPH_T", RTKH, 525, 544, "typedef struct {        /* GPS/QZS/GAL broadcast ephemeris type */", "} eph_t;"),
-    ("EPH_CUT_EPOCHS", RTK, 125, 126, "const static double gpst0[]={1980,1, 6,0,0,0};", "const static double gst0 []={1999,8,22,0,0,0};"),
-    ("EPH_CUT_GETBIT", RTK, 598, 610, "extern unsigned int getbitu(", "}"),
-    ("EPH_CUT_EPOCH2TIME", RTK, 1201, 1215, "extern gtime_t epoch2time(const double *ep)", "}"),
-    ("EPH_CUT_TIME2GPST", RTK, 1261, 1269, "extern double time2gpst(gtime_t t, int *week)", "}"),
-    ("EPH_CUT_GST2TIME", RTK, 1276, 1284, "extern gtime_t gst2time(int week, double sec)", "}"),
-    ("EPH_CUT_GETBIT2", NAVC, 94, 104, "extern uint32_t getbitu2(", "}"),
-    ("EPH_CUT_GAL_DEFS", GAL, 16, 20, "#define P2_34       5.820766091346741E-11", "#define OFFSET2     122"),
-    ("EPH_CUT_GAL_WORDS", GAL, 28, 286, "void decode_word1(const uint8_t *buff, sdrnav_t *nav)", "}"),
-    ("EPH_CUT_GAL_PAGE", GAL, 327, 359, "extern int decode_page_e1b(const uint8_t *buff1, const uint8_t *buff2,", "}"),
+    (GPSH, "EPH_CUT_GPS_RATES", 46, 55, "#define CPS 1.023e6", "#define E1B_BPS 250.0"),
+    (GPSH, "EPH_CUT_GPS_CONST", 87, 94, "const double PI = 3.1415926535898;", "const double F = -4.442807633e-10;"),
+    (GPSH, "EPH_CUT_GPSERR", 187, 191, "#define GPS_ERR_SLIP    1", "#define GPS_ERR_PAGE    5"),
+    (GPSH, "EPH_CUT_UMS", 289, 296, "struct UMS {", "};"),
+    (GPSC, "EPH_CUT_BIN", 32, 36, "unsigned bin(char *s, int n) {", "}"),
+    (EH, "EPH_CUT_EPHEM_H", 23, 82, "class EPHEM {", "};"),
+    (EC, "EPH_CUT_EPHEM_TIME", 31, 47, "static double TimeFromEpoch(double t, double t_ref) {", "};"),
+    (EC, "EPH_CUT_EPHEM_SUB", 51, 110, "void EPHEM::Subframe1(char *nav) {", "}"),
+    (EC, "EPH_CUT_EPHEM_POS", 114, 207, "double EPHEM::TimeOfEphemerisAge(double t) const {", "}"),
+    (EC, "EPH_CUT_EPHEM_FRAME", 211, 252, "void EPHEM::Init(int sat) {", "}"),
+    (EC, "EPH_CUT_EPHEM_PAGES", 256, 370, "void EPHEM::PageN(unsigned page) {", "}"),
+    (SOLVE, "EPH_CUT_SNAPSHOT", 42, 52, "struct SNAPSHOT {", "};"),
+    (SOLVE, "EPH_CUT_GETCLOCK", 168, 244, "double SNAPSHOT::GetClock() const {", "}"),
+    (RTKH, "EPH_CUT_SC2RAD", 61, 61, "#define SC2RAD      3.1415926535898 ", "#define SC2RAD"),
+    (RTKH, "EPH_CUT_P2", 421, 444, "#define P2_5        0.03125 ", "#define P2_55       2.775557561562891E-17"),
+    (RTKH, "EPH_CUT_GTIME", 464, 467, "typedef struct {        /* time struct */", "} gtime_t;"),
+    (RTKH, "EPH_CUT_EPH_T", 525, 544, "typedef struct {        /* GPS/QZS/GAL broadcast ephemeris type */", "} eph_t;"),
+    (RTK, "EPH_CUT_EPOCHS", 125, 126, "const static double gpst0[]={1980,1, 6,0,0,0};", "const static double gst0 []={1999,8,22,0,0,0};"),
+    (RTK, "EPH_CUT_GETBIT", 598, 610, "extern unsigned int getbitu(", "}"),
+    (RTK, "EPH_CUT_EPOCH2TIME", 1201, 1215, "extern gtime_t epoch2time(const double *ep)", "}"),
+    (RTK, "EPH_CUT_TIME2GPST", 1261, 1269, "extern double time2gpst(gtime_t t, int *week)", "}"),
+    (RTK, "EPH_CUT_GST2TIME", 1276, 1284, "extern gtime_t gst2time(int week, double sec)", "}"),
+    (NAVC, "EPH_CUT_GETBIT2", 94, 104, "extern uint32_t getbitu2(", "}"),
+    (GAL, "EPH_CUT_GAL_DEFS", 16, 20, "#define P2_34       5.820766091346741E-11", "#define OFFSET2     122"),
+    (GAL, "EPH_CUT_GAL_WORDS", 28, 286, "void decode_word1(const uint8_t *buff, sdrnav_t *nav)", "}"),
+    (GAL, "EPH_CUT_GAL_PAGE", 327, 359, "extern int decode_page_e1b(const uint8_t *buff1, const uint8_t *buff2,", "}"),
 ]
 # what the harness restates: (file, line, text)
 PINS = [
@@ -100,21 +98,14 @@ REF_KIND = {eph.NAVSTAR: 0, eph.CA: 2, eph.E1B: 3}                     # sat_e: 
 
 
 def build(tmp):
-    text = {}
-    for f in set([c[1] for c in CUTS] + [p[0] for p in PINS] + [c[0] for c in CONSTS]):
-        text[f] = open(os.path.join(R, f), encoding="latin-1").read().split("\n")
-    for macro, f, a, b, t1, t2 in CUTS:
-        lines = text[f]
-        assert t1 in lines[a - 1] and t2 in lines[b - 1], ("a cut moved", macro, f, a, b)
-        open(os.path.join(tmp, macro + ".inc"), "w", encoding="latin-1").write("\n".join(lines[a - 1:b]) + "\n")
-    for f, ln, t in PINS:
-        assert t in text[f][ln - 1], ("a restated statement moved", f, ln, t)
+    ref_cut.cut(tmp, CUTS)
+    ref_cut.pin(PINS)
     for f, ln, name, t, hx in CONSTS:
-        words = text[f][ln - 1].replace("=", " ").replace(";", " ").split()
+        words = read(f)[ln - 1].replace("=", " ").replace(";", " ").split()
         assert name in words and t in words, ("a constant's text changed", f, ln, name, t)
         assert float(t).hex() == hx, (name, float(t).hex(), hx)
     exe = os.path.join(tmp, "eph_ref")
-    cmd = (["g++", "-O2", "-w", "-std=gnu++11", "-ffp-contract=off", "-I" + tmp] + ['-D%s="%s.inc"' % (m, m) for m, *_ in CUTS] +
+    cmd = (["g++", "-O2", "-w", "-std=gnu++11", "-ffp-contract=off", "-I" + tmp] + ref_cut.cut_macros(CUTS) +
            ["-o", exe, os.path.join(ROOT, "tools", "ref", "ref_eph_main.cpp")])
     subprocess.run(cmd, check=True)
     return exe

@@ -14,18 +14,12 @@ tests/test_fax_cpu.py::test_golden_file_meets_its_conditions are checked here, b
     python tools/make_ref_fax_golden.py
 """
 import os
-import shutil
 import subprocess
-import sys
-import tempfile
 
-import numpy as np
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import ref_cut
+from ref_cut import ROOT  # ref_cut puts the repository root on sys.path
 from tests import fax_common as C  # noqa: E402
 
-R = os.environ.get("REFERENCE", "/root/reference")
 H, F, X = "extensions/FAX/FaxDecoder.h", "extensions/FAX/FaxDecoder.cpp", "extensions/FAX/fax.cpp"
 
 # file, name, first line, last line, text of the first, text of the last
@@ -72,48 +66,24 @@ PINS = [(H, 34, "#define FAX_MSG_DRAW 254"),
         ("rx/rx_sound.cpp", 1103, "rx->real_wr_pos = (rx->real_wr_pos+1) & (N_DPBUF-1);")]
 
 
-def read(rel):
-    return open(os.path.join(R, rel), encoding="latin-1").read().split("\n")
-
-
 def build(tmp):
-    for rel, macro, a, b, t1, t2 in CUTS:
-        lines = read(rel)
-        assert lines[a - 1].strip() == t1 and lines[b - 1].strip() == t2, ("cut moved", rel, macro, a, b, lines[a - 1], lines[b - 1])
-        open(os.path.join(tmp, macro + ".inc"), "w", encoding="latin-1").write("\n".join(lines[a - 1:b]) + "\n")
-    for rel, ln, t in PINS:
-        assert " ".join(t.split()) in " ".join(read(rel)[ln - 1].split()), ("statement moved", rel, ln, t, read(rel)[ln - 1])      # white space aside
+    ref_cut.cut(tmp, CUTS, whole=True)
+    ref_cut.pin(PINS, white_space_aside=True)
     exe = os.path.join(tmp, "fax_ref")
     subprocess.run(["g++", "-O2", "-ffp-contract=off", "-w", "-I" + tmp, "-o", exe, os.path.join(ROOT, "tools", "ref", "ref_fax_main.cpp"), "-lm"], check=True)
     return exe
 
 
+def report(name, got, out, k):
+    r = got["recs"]
+    print("   %-20s %4d blocks %3d lines (%d start %d stop) %3d rows, flags %s, skip %d, medians %s" % (
+        name, got["nlines"].size, r.size, int((r["type"] == 1).sum()), int((r["type"] == 2).sum()), len(got["rows"]),
+        sorted(set(int(f) for f in r["flags"])), int(got["info"]["skip"]),
+        [(int(x["phasingSkipData"]), int(x["ten_pct"]), int(x["ninety_pct"])) for x in r if x["flags"] & C.F_MEDIAN]))
+
+
 def main():
-    out = {}
-    samples = C.pool()
-    out["pool_sha"] = np.frombuffer(C.digest(samples.tobytes()), np.uint8)
-    sc = C.scripts()
-    out["script_names"] = np.array(sorted(sc))
-    with tempfile.TemporaryDirectory() as tmp:
-        exe = build(tmp)
-        for name in sorted(sc):
-            got = C.run_script_exe(exe, sc[name], samples, tmp)
-            k = "s_%s_" % name
-            out[k + "script_sha"] = np.frombuffer(C.digest("\n".join(sc[name]).encode()), np.uint8)
-            for key, v in C.golden_of(got).items():
-                out[k + key] = v
-            r = got["recs"]
-            print("   %-20s %4d blocks %3d lines (%d start %d stop) %3d rows, flags %s, skip %d, medians %s" % (
-                name, got["nlines"].size, r.size, int((r["type"] == 1).sum()), int((r["type"] == 2).sum()), len(got["rows"]),
-                sorted(set(int(f) for f in r["flags"])), int(got["info"]["skip"]),
-                [(int(x["phasingSkipData"]), int(x["ten_pct"]), int(x["ninety_pct"])) for x in r if x["flags"] & C.F_MEDIAN]))
-        path = os.path.join(tmp, "fax_ref.npz")
-        np.savez_compressed(path, **out)
-        from tests.test_fax_cpu import golden_conditions
-        golden_conditions(np.load(path), os.path.getsize(path))
-        final = os.path.join(C.GOLD, "fax_ref.npz")
-        shutil.copyfile(path, final)
-    print("wrote %s, %d bytes" % (final, os.path.getsize(final)))
+    ref_cut.script_golden_main(C, build, "fax_ref.npz", ref_cut.script_by_digest, report)
 
 
 if __name__ == "__main__":

@@ -22,11 +22,10 @@ import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import ref_cut
+from ref_cut import ROOT  # ref_cut puts the repository root on sys.path
 from tests import iqd_common as C  # noqa: E402
 
-R = os.environ.get("REFERENCE", "/root/reference")
 F, P = "extensions/IQ_display/iq_display.cpp", "rx/kiwi/pll.h"
 
 CUTS = [
@@ -61,17 +60,9 @@ PINS = [(F, 21, "#define IQ_POINTS       0"),
         ("rx/rx_sound.cpp", 669, "receive_iq_pre_agc")]
 
 
-def read(rel):
-    return open(os.path.join(R, rel), encoding="latin-1").read().split("\n")
-
-
 def build(tmp):
-    for rel, macro, a, b, t1, t2 in CUTS:
-        lines = read(rel)
-        assert t1 in lines[a - 1] and t2 in lines[b - 1], ("cut moved", rel, macro, a, b)
-        open(os.path.join(tmp, macro + ".inc"), "w", encoding="latin-1").write("\n".join(lines[a - 1:b]) + "\n")
-    for rel, ln, t in PINS:
-        assert t in read(rel)[ln - 1], ("statement moved", rel, ln, t, read(rel)[ln - 1])
+    ref_cut.cut(tmp, CUTS)
+    ref_cut.pin(PINS)
     exe = os.path.join(tmp, "iqd_ref")
     subprocess.run(["g++", "-O2", "-ffp-contract=off", "-std=gnu++11", "-w", "-I" + tmp, "-o", exe, os.path.join(ROOT, "tools", "ref", "ref_iqd_main.cpp"), "-lm"],
                    check=True)

@@ -17,18 +17,14 @@ file is kept.
                                                       digest and integers alone
 """
 import os
-import shutil
 import subprocess
 import sys
 import tempfile
 
-import numpy as np
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import ref_cut
+from ref_cut import ROOT  # ref_cut puts the repository root on sys.path
 from tests import lorc_common as C  # noqa: E402
 
-R = os.environ.get("REFERENCE", "/root/reference")
 F = "extensions/Loran_C/loran_c.cpp"
 
 # file, name, first line, last line, text of the first, text of the last, a line of ours ahead of the cut (the conditional the cut's
@@ -84,17 +80,9 @@ PINS = [(F, 17, "#define	SCOPE_DATA	0"),
         ("rx/rx_sound.cpp", 669, "receive_iq_pre_agc")]
 
 
-def read(rel):
-    return open(os.path.join(R, rel), encoding="latin-1").read().split("\n")
-
-
 def build(tmp):
-    for rel, macro, a, b, t1, t2, ahead in CUTS:
-        lines = read(rel)
-        assert lines[a - 1].strip() == t1 and lines[b - 1].strip() == t2, ("cut moved", rel, macro, a, b)
-        open(os.path.join(tmp, macro + ".inc"), "w", encoding="latin-1").write((ahead + "\n" if ahead else "") + "\n".join(lines[a - 1:b]) + "\n")
-    for rel, ln, t in PINS:
-        assert " ".join(t.split()) in " ".join(read(rel)[ln - 1].split()), ("statement moved", rel, ln, t, read(rel)[ln - 1])      # white space aside
+    ref_cut.cut(tmp, CUTS, whole=True)
+    ref_cut.pin(PINS, white_space_aside=True)
     exe = os.path.join(tmp, "lorc_ref")
     subprocess.run(["g++", "-O2", "-ffp-contract=off", "-w", "-I" + tmp, "-o", exe, os.path.join(ROOT, "tools", "ref", "ref_lorc_main.cpp"), "-lm"], check=True)
     return exe
@@ -106,32 +94,16 @@ def random_main():
         ext_random.write_fixture("lorc", build(tmp), C.pool(), tmp)
 
 
+def report(name, got, out, k):
+    allb = out[k + "rows"]
+    edge = int(((allb == 0) | (allb == 255)).sum())
+    print("   %-20s %3d blocks %3d rows (%d reset) %7d bytes (%5.1f%% at 0 / 255), navgs %s" % (
+        name, got["nrows"].size, int(got["nrows"].sum()), int((got["cmd"] == 1).sum()), allb.size, 100.0 * edge / max(allb.size, 1),
+        got["scalars"]["ch"]["navgs"].tolist()))
+
+
 def main():
-    out = {}
-    samples = C.pool()
-    out["pool_sha"] = np.frombuffer(C.digest(samples.tobytes()), np.uint8)
-    sc = C.scripts()
-    out["script_names"] = np.array(sorted(sc))
-    with tempfile.TemporaryDirectory() as tmp:
-        exe = build(tmp)
-        for name in sorted(sc):
-            got = C.run_script_exe(exe, sc[name], samples, tmp)
-            k = "s_%s_" % name
-            out[k + "script"] = np.array(sc[name])
-            for key, v in C.golden_of(got).items():
-                out[k + key] = v
-            allb = out[k + "rows"]
-            edge = int(((allb == 0) | (allb == 255)).sum())
-            print("   %-20s %3d blocks %3d rows (%d reset) %7d bytes (%5.1f%% at 0 / 255), navgs %s" % (
-                name, got["nrows"].size, int(got["nrows"].sum()), int((got["cmd"] == 1).sum()), allb.size, 100.0 * edge / max(allb.size, 1),
-                got["scalars"]["ch"]["navgs"].tolist()))
-        path = os.path.join(tmp, "lorc_ref.npz")
-        np.savez_compressed(path, **out)
-        from tests.test_lorc_cpu import golden_conditions
-        golden_conditions(np.load(path), os.path.getsize(path))
-        final = os.path.join(C.GOLD, "lorc_ref.npz")
-        shutil.copyfile(path, final)
-    print("wrote %s, %d bytes" % (final, os.path.getsize(final)))
+    ref_cut.script_golden_main(C, build, "lorc_ref.npz", ref_cut.script_by_text, report)
 
 
 if __name__ == "__main__":

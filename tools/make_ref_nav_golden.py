@@ -13,34 +13,32 @@ keep every later test from passing on an empty set.
 """
 import os
 import subprocess
-import sys
 import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import ref_cut
+from ref_cut import R, ROOT  # ref_cut puts the repository root on sys.path
 from flydog_sdr_gps_amd import nav  # noqa: E402
 
 GOLD = os.path.join(ROOT, "tests", "golden")
-R = os.environ.get("REFERENCE", "/root/reference")
 CH, GAL, NAVC, RTK = "gps/channel.cpp", "gps/GNSS-SDRLIB/sdrnav_gal.cpp", "gps/GNSS-SDRLIB/sdrnav.cpp", "gps/GNSS-SDRLIB/rtkcmn.cpp"
 
-# (macro, file, first, last, text of the first line, text of the last line)
+# (file, macro, first, last, text of the first line, text of the last line)
 CUTS = [
-    ("NAV_CUT_GPSERR", "gps/gps.h", 187, 191, "#define GPS_ERR_SLIP    1", "#define GPS_ERR_PAGE    5"),
-    ("NAV_CUT_CRCTAB", RTK, 271, 304, "static const unsigned int tbl_CRC24Q[]={", "};"),
-    ("NAV_CUT_GETBITU", RTK, 598, 604, "extern unsigned int getbitu(", "}"),
-    ("NAV_CUT_CRC24Q", RTK, 662, 671, "extern unsigned int crc24q(", "}"),
-    ("NAV_CUT_SDRNAV", NAVC, 154, 190, "extern void bits2byte(", "}"),
-    ("NAV_CUT_OFFSETS", GAL, 19, 20, "#define OFFSET1     2", "#define OFFSET2     122"),
-    ("NAV_CUT_WORD5", GAL, 162, 174, "e5bhs          =getbitu(buff,OFFSET1+67, 2);", "}"),
-    ("NAV_CUT_CHECKCRC", GAL, 293, 319, "extern int checkcrc_e1b(", "}"),
-    ("NAV_CUT_E1B_SUBFRAME", GAL, 382, 514, "extern int E1B_subframe(sdrnav_t *nav, int *error)", "}"),
-    ("NAV_CUT_PREAMBLES", CH, 120, 145, "#define L1_PRELEN 8", "const char E1BpreambleInverse [] = {1,0,1,0,0,1,1,1,1,1};"),
-    ("NAV_CUT_POLYS", CH, 414, 416, "int polys[2] = { 0x4f, 0x6d };", "nav.fec = create_viterbi27_port(E1B_NBIT);"),
-    ("NAV_CUT_LOOP", CH, 452, 506, "while (holding >= subframe_bits) {", "memmove(buf, buf+nbits, holding-=nbits);"),
-    ("NAV_CUT_PARITYCHECK", CH, 731, 832, "int CHANNEL::ParityCheck(char *buf, int *nbits) {", "}"),
+    ("gps/gps.h", "NAV_CUT_GPSERR", 187, 191, "#define GPS_ERR_SLIP    1", "#define GPS_ERR_PAGE    5"),
+    (RTK, "NAV_CUT_CRCTAB", 271, 304, "static const unsigned int tbl_CRC24Q[]={", "};"),
+    (RTK, "NAV_CUT_GETBITU", 598, 604, "extern unsigned int getbitu(", "}"),
+    (RTK, "NAV_CUT_CRC24Q", 662, 671, "extern unsigned int crc24q(", "}"),
+    (NAVC, "NAV_CUT_SDRNAV", 154, 190, "extern void bits2byte(", "}"),
+    (GAL, "NAV_CUT_OFFSETS", 19, 20, "#define OFFSET1     2", "#define OFFSET2     122"),
+    (GAL, "NAV_CUT_WORD5", 162, 174, "e5bhs          =getbitu(buff,OFFSET1+67, 2);", "}"),
+    (GAL, "NAV_CUT_CHECKCRC", 293, 319, "extern int checkcrc_e1b(", "}"),
+    (GAL, "NAV_CUT_E1B_SUBFRAME", 382, 514, "extern int E1B_subframe(sdrnav_t *nav, int *error)", "}"),
+    (CH, "NAV_CUT_PREAMBLES", 120, 145, "#define L1_PRELEN 8", "const char E1BpreambleInverse [] = {1,0,1,0,0,1,1,1,1,1};"),
+    (CH, "NAV_CUT_POLYS", 414, 416, "int polys[2] = { 0x4f, 0x6d };", "nav.fec = create_viterbi27_port(E1B_NBIT);"),
+    (CH, "NAV_CUT_LOOP", 452, 506, "while (holding >= subframe_bits) {", "memmove(buf, buf+nbits, holding-=nbits);"),
+    (CH, "NAV_CUT_PARITYCHECK", 731, 832, "int CHANNEL::ParityCheck(char *buf, int *nbits) {", "}"),
 ]
 # what the harness restates: (file, line, text)
 PINS = [
@@ -55,18 +53,11 @@ PINS = [
 
 
 def build(tmp):
-    text = {}
-    for f in set([c[1] for c in CUTS] + [p[0] for p in PINS]):
-        text[f] = open(os.path.join(R, f), encoding="latin-1").read().split("\n")
-    for macro, f, a, b, t1, t2 in CUTS:
-        lines = text[f]
-        assert t1 in lines[a - 1] and t2 in lines[b - 1], ("a cut moved", macro, f, a, b)
-        open(os.path.join(tmp, macro + ".inc"), "w", encoding="latin-1").write("\n".join(lines[a - 1:b]) + "\n")
-    for f, ln, t in PINS:
-        assert t in text[f][ln - 1], ("a restated statement moved", f, ln, t)
+    ref_cut.cut(tmp, CUTS)
+    ref_cut.pin(PINS)
     exe = os.path.join(tmp, "nav_ref")
     cmd = (["g++", "-O2", "-w", "-std=gnu++11", "-I" + os.path.join(R, "gps", "ka9q-fec"), "-I" + tmp] +
-           ['-D%s="%s.inc"' % (m, m) for m, *_ in CUTS] +
+           ref_cut.cut_macros(CUTS) +
            ["-o", exe, os.path.join(ROOT, "tools", "ref", "ref_nav_main.cpp"), os.path.join(R, "gps", "ka9q-fec", "viterbi27_port.cpp")])
     subprocess.run(cmd, check=True)
     return exe

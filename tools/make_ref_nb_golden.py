@@ -12,7 +12,6 @@ the repository.  Needs oracle/_ref/gen/kiwi.gen.h (oracle/build_ref.sh makes it;
 
     python tools/make_ref_nb_golden.py
 """
-import hashlib
 import os
 import subprocess
 import sys
@@ -20,14 +19,13 @@ import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import ref_cut
+from ref_cut import R, REF, ROOT, read  # ref_cut puts the repository root on sys.path
+from tests.script_common import digest_u8 as digest  # noqa: E402
 from tests import nb_signals  # noqa: E402
 from flydog_sdr_gps_amd import wf as wf_mod  # noqa: E402
 
-REF = os.path.join(ROOT, "oracle", "_ref")
 GOLD = os.path.join(ROOT, "tests", "golden")
-R = os.environ.get("REFERENCE", "/root/reference")
 
 # (file, macro, first, last, text of the first line, text of the last line)
 CUTS = [
@@ -53,10 +51,6 @@ ENUMS = [("rx/rx_noise.h", "typedef enum { NB_OFF = 0, NB_STD = 1, NB_WILD = 2 }
 PARAMS = ["NB_GATE", "NB_THRESHOLD"]
 
 
-def read(rel):
-    return open(os.path.join(R, rel), encoding="latin-1").read().split("\n")
-
-
 def consts():
     """name -> value of the reference's NB constants, read from its text"""
     for rel, t in ENUMS:
@@ -71,12 +65,8 @@ def consts():
 
 
 def build(tmp):
-    for rel, macro, a, b, t1, t2 in CUTS:
-        lines = read(rel)
-        assert t1 in lines[a - 1] and t2 in lines[b - 1], ("cut moved", rel, macro, a, b)
-        open(os.path.join(tmp, macro + ".inc"), "w", encoding="latin-1").write("\n".join(lines[a - 1:b]) + "\n")
-    for rel, ln, t in PINS:
-        assert t in read(rel)[ln - 1], ("statement moved", rel, ln, t)
+    ref_cut.cut(tmp, CUTS)
+    ref_cut.pin(PINS)
     gen = os.path.join(REF, "gen")
     if not os.path.isfile(os.path.join(gen, "kiwi.gen.h")):
         sys.exit("oracle/_ref/gen/kiwi.gen.h missing: run oracle/build_ref.sh first")
@@ -124,10 +114,6 @@ WF = [
     ("wf_setup_between", ["W 600 40"] + ["F"] * 4 + ["T", "W 2000 20"] + ["F"] * 4 + ["T"], "noise_pulses", 23, 8, wf_mod.WINF_HAMMING),
 ]
 KEEP_FRAMES = {"wf_seq": [0, 5], "wf_wide_flush": [2], "wf_setup_between": [4]}
-
-
-def digest(b):
-    return np.frombuffer(hashlib.sha256(bytes(b)).digest()[:16], np.uint8)
 
 
 def run(exe, tmp, script, x):

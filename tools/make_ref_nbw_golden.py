@@ -23,12 +23,10 @@ import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import ref_cut
+from ref_cut import R, REF, ROOT, read  # ref_cut puts the repository root on sys.path
 from tests import nbw_common as C  # noqa: E402
 
-REF = os.path.join(ROOT, "oracle", "_ref")
-R = os.environ.get("REFERENCE", "/root/reference")
 BLK = C.BLK
 
 CUTS = [
@@ -60,10 +58,6 @@ WILD_CONSTS = [("MAX_ORDER", "#define MAX_ORDER"), ("MAX_IMPULSE_LEN", "#define 
 CMSIS = ["arm_dot_prod_f32", "arm_fir_init_f32", "arm_fir_f32", "arm_var_f32", "arm_power_f32", "arm_negate_f32", "arm_mult_f32", "arm_add_f32"]
 
 
-def read(rel):
-    return open(os.path.join(R, rel), encoding="latin-1").read().split("\n")
-
-
 def consts():
     for rel, t in ENUMS:
         assert any(t in l for l in read(rel)), ("reference enum moved", rel, t)
@@ -82,12 +76,8 @@ def consts():
 
 
 def build(tmp):
-    for rel, macro, a, b, t1, t2 in CUTS:
-        lines = read(rel)
-        assert t1 in lines[a - 1] and t2 in lines[b - 1], ("cut moved", rel, macro, a, b)
-        open(os.path.join(tmp, macro + ".inc"), "w", encoding="latin-1").write("\n".join(lines[a - 1:b]) + "\n")
-    for rel, ln, t in PINS:
-        assert t in read(rel)[ln - 1], ("statement moved", rel, ln, t)
+    ref_cut.cut(tmp, CUTS)
+    ref_cut.pin(PINS)
     # the scalar forms are what the reference's build compiles: no Makefile asks for another (and the harness refuses to compile if
     # arm_math.h switches one on for this machine)
     for f in os.listdir(R):

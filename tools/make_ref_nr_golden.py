@@ -11,7 +11,6 @@ and oracle/_ref/fftw3_api (oracle/build_ref.sh makes both; run first if absent).
 
     python tools/make_ref_nr_golden.py
 """
-import hashlib
 import os
 import subprocess
 import sys
@@ -19,10 +18,10 @@ import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = os.path.join(ROOT, "oracle", "_ref")
+import ref_cut
+from ref_cut import R, REF, ROOT, read  # ref_cut puts the repository root on sys.path
+from tests.script_common import digest_u8 as digest  # noqa: E402
 GOLD = os.path.join(ROOT, "tests", "golden")
-R = os.environ.get("REFERENCE", "/root/reference")
 
 # (file, macro, first, last, text of the first line, text of the last line)
 CUTS = [
@@ -46,10 +45,6 @@ ENUMS = [("rx/rx_noise.h", "typedef enum { NR_OFF_ = 0, NR_WDSP = 1, NR_ORIG = 2
 PARAMS = ["NR_DELAY", "NR_BETA", "NR_DECAY", "NR_TAPS", "NR_DLY", "NR_GAIN", "NR_LEAKAGE"]
 
 
-def read(rel):
-    return open(os.path.join(R, rel), encoding="latin-1").read().split("\n")
-
-
 def consts():
     """name -> value of the reference's NR constants, read from its text"""
     out = {}
@@ -65,12 +60,8 @@ def consts():
 
 
 def build(tmp):
-    for rel, macro, a, b, t1, t2 in CUTS:
-        lines = read(rel)
-        assert t1 in lines[a - 1] and t2 in lines[b - 1], ("cut moved", rel, macro, a, b)
-        open(os.path.join(tmp, macro + ".inc"), "w", encoding="latin-1").write("\n".join(lines[a - 1:b]) + "\n")
-    for rel, ln, t in PINS:
-        assert t in read(rel)[ln - 1], ("statement moved", rel, ln, t)
+    ref_cut.cut(tmp, CUTS)
+    ref_cut.pin(PINS)
     gen, fftw = os.path.join(REF, "gen"), os.path.join(REF, "fftw3_api")
     if not os.path.isfile(os.path.join(gen, "kiwi.gen.h")) or not os.path.isdir(fftw):
         sys.exit("oracle/_ref/gen/kiwi.gen.h or oracle/_ref/fftw3_api missing: run oracle/build_ref.sh first")
@@ -169,10 +160,6 @@ sc = [
     ("enable_values", ["A 1"] + wdsp_params(DN, 64, 16, 1e-4, 0.1) + ["E 0 7", "B 512 0", "E 0 -1", "B 512 0", "E 0 0", "B 512 0", "S"],
      lambda n, t0: speech(n, t0, 1000)),
 ]
-
-
-def digest(b):
-    return np.frombuffer(hashlib.sha256(bytes(b)).digest()[:16], np.uint8)
 
 
 def fdigest(b):

@@ -20,7 +20,6 @@ a few short scenarios and as per-block SHA-256 prefixes for the rest; the state 
 
     python tools/make_ref_nrs_golden.py
 """
-import hashlib
 import math
 import os
 import subprocess
@@ -29,10 +28,10 @@ import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = os.path.join(ROOT, "oracle", "_ref")
+import ref_cut
+from ref_cut import R, REF, ROOT, read  # ref_cut puts the repository root on sys.path
+from tests.script_common import digest_u8 as digest  # noqa: E402
 GOLD = os.path.join(ROOT, "tests", "golden")
-R = os.environ.get("REFERENCE", "/root/reference")
 
 CUTS = [
     ("rx/rx_sound_cmd.cpp", "NR_CUT_ALGO", 464, 471, "case CMD_NR_ALGO:", "break;"),
@@ -58,10 +57,6 @@ SPECTRAL_CONSTS = [("FFT_FULL", "#define FFT_FULL"), ("psthr", "const f32_t psth
                    ("psini", "const f32_t psini ="), ("pspri", "const f32_t pspri ="), ("NR_width", "const int NR_width ="),
                    ("power_threshold", "const f32_t power_threshold ="), ("snr_prio_min_dB", "const f32_t snr_prio_min_dB =")]
 PARAMS = ["NR_S_GAIN", "NR_ALPHA", "NR_ASNR"]
-
-
-def read(rel):
-    return open(os.path.join(R, rel), encoding="latin-1").read().split("\n")
 
 
 def consts():
@@ -91,12 +86,8 @@ def twiddle():
 
 
 def build(tmp):
-    for rel, macro, a, b, t1, t2 in CUTS:
-        lines = read(rel)
-        assert t1 in lines[a - 1] and t2 in lines[b - 1], ("cut moved", rel, macro, a, b)
-        open(os.path.join(tmp, macro + ".inc"), "w", encoding="latin-1").write("\n".join(lines[a - 1:b]) + "\n")
-    for rel, ln, t in PINS:
-        assert t in read(rel)[ln - 1], ("statement moved", rel, ln, t)
+    ref_cut.cut(tmp, CUTS)
+    ref_cut.pin(PINS)
     # the tables are declared and nowhere defined: the reason this builder supplies them
     for d, _, files in os.walk(os.path.join(R, "rx")):
         for f in files:
@@ -220,10 +211,6 @@ sc = [
      [SSB, "A 3"] + params() + B(12) + B(2, 1) + B(10) + B(1, 1) + B(6) + ["S"]),
     ("long_tones_on", 12000, "long", 0, [], False, False, [SSB, "A 3"] + params() + B(80) + ["S"]),
 ]
-
-
-def digest(b):
-    return np.frombuffer(hashlib.sha256(bytes(b)).digest()[:16], np.uint8)
 
 
 def fdigest(b):

@@ -19,30 +19,28 @@ otherwise.  The conditions at the end keep every later test from passing on an e
 import os
 import re
 import subprocess
-import sys
 import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import ref_cut
+from ref_cut import R, ROOT  # ref_cut puts the repository root on sys.path
 from flydog_sdr_gps_amd import eph, pos  # noqa: E402
 
 GOLD = os.path.join(ROOT, "tests", "golden")
-R = os.environ.get("REFERENCE", "/root/reference")
 SOLVE, GPSH, PSC, SPP, EKF, BASE, ELL, CLK, TYPES = ("gps/solve.cpp", "gps/gps.h", "gps/PosSolver.cpp", "gps/SinglePointPositionSolver.h",
                                                      "gps/EKFPositionSolver.h", "gps/PositionSolverBase.h", "gps/Ellipsoid.h", "init/clk.h", "types.h")
 LU, UTILS, A2U = "pkgs/TNT_JAMA/jama/lu.h", "pkgs/TNT_JAMA/tnt/utils.h", "pkgs/TNT_JAMA/tnt/array2d_utils.h"
 
-# (macro, file, first, last, text of the first line, text of the last line)
+# (file, macro, first, last, text of the first line, text of the last line)
 CUTS = [
-    ("POS_CUT_UMS", GPSH, 289, 296, "struct UMS {", "};"),
-    ("POS_CUT_EPOCH", SOLVE, 251, 389, "class GNSSDataForEpoch {", "} ;"),
-    ("POS_CUT_GYR", SOLVE, 497, 498, "const int grn_yel_red = (pos_solvers[0]->ekf_valid() ? 0 : (pos_solvers[0]->spp_valid() ? 1 : 2));",
+    (GPSH, "POS_CUT_UMS", 289, 296, "struct UMS {", "};"),
+    (SOLVE, "POS_CUT_EPOCH", 251, 389, "class GNSSDataForEpoch {", "} ;"),
+    (SOLVE, "POS_CUT_GYR", 497, 498, "const int grn_yel_red = (pos_solvers[0]->ekf_valid() ? 0 : (pos_solvers[0]->spp_valid() ? 1 : 2));",
      "GPSstat(STAT_SOLN, 0, grn_yel_red, gnssDataForEpoch.ch_has_soln());"),
-    ("POS_CUT_AZEL", SOLVE, 501, 516, "const auto elev_azim = pos_solvers[0]->elev_azim(gnssDataForEpoch.sv());", "continue;"),
-    ("POS_CUT_SOLVERS", SOLVE, 571, 578, "std::array<PosSolver::sptr, 3> posSolvers = {", "auto const predOnlyGalileo = [](int type) { return (type == E1B); };"),
-    ("POS_CUT_SOLVE", SOLVE, 616, 639, "if (good == 0) continue;", "}"),
+    (SOLVE, "POS_CUT_AZEL", 501, 516, "const auto elev_azim = pos_solvers[0]->elev_azim(gnssDataForEpoch.sv());", "continue;"),
+    (SOLVE, "POS_CUT_SOLVERS", 571, 578, "std::array<PosSolver::sptr, 3> posSolvers = {", "auto const predOnlyGalileo = [](int type) { return (type == E1B); };"),
+    (SOLVE, "POS_CUT_SOLVE", 616, 639, "if (good == 0) continue;", "}"),
 ]
 # what the harness and csrc/kg_pos.h restate: (file, line, text)
 PINS = [
@@ -87,15 +85,8 @@ QUANT = ("x", "y", "z", "t_rx", "osc_corr", "lambda", "phi", "alt", "elev_deg", 
 
 
 def build(tmp):
-    text = {}
-    for f in set([c[1] for c in CUTS] + [p[0] for p in PINS]):
-        text[f] = open(os.path.join(R, f), encoding="latin-1").read().split("\n")
-    for macro, f, a, b, t1, t2 in CUTS:
-        lines = text[f]
-        assert t1 in lines[a - 1] and t2 in lines[b - 1], ("a cut moved", macro, f, a, b)
-        open(os.path.join(tmp, macro + ".inc"), "w", encoding="latin-1").write("\n".join(lines[a - 1:b]) + "\n")
-    for f, ln, t in PINS:
-        assert t in text[f][ln - 1], ("a restated statement moved", f, ln, t, text[f][ln - 1])
+    ref_cut.cut(tmp, CUTS)
+    ref_cut.pin(PINS)
     assert pos.UERE == float("6.0") and pos.F_OSC == float("124.999900") * 1000000
     hdr = open(os.path.join(ROOT, "flydog_sdr_gps_amd", "csrc", "kg_pos.h")).read()
     for name, t in HEADER_CONSTS:
@@ -104,7 +95,7 @@ def build(tmp):
     for name, extra in (("pos_ref", []), ("pos_ref_dbg", ["-DDEBUG_POS_SOLVER"])):
         exe = os.path.join(tmp, name)
         cmd = (["g++", "-O2", "-w", "-std=gnu++14", "-ffp-contract=off", "-I" + tmp, "-I" + os.path.join(R, "gps"), "-I" + os.path.join(R, "pkgs", "TNT_JAMA")] +
-               extra + ['-D%s="%s.inc"' % (m, m) for m, *_ in CUTS] + ["-o", exe, os.path.join(ROOT, "tools", "ref", "ref_pos_main.cpp")])
+               extra + ref_cut.cut_macros(CUTS) + ["-o", exe, os.path.join(ROOT, "tools", "ref", "ref_pos_main.cpp")])
         subprocess.run(cmd, check=True)
         exes.append(exe)
     return exes

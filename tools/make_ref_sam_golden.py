@@ -11,7 +11,6 @@ repository.  Needs oracle/_ref/gen/kiwi.gen.h and oracle/_ref/fftw3_api (oracle/
 
     python tools/make_ref_sam_golden.py
 """
-import hashlib
 import os
 import subprocess
 import sys
@@ -19,41 +18,37 @@ import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = os.path.join(ROOT, "oracle", "_ref")
+import ref_cut
+from ref_cut import R, REF, ROOT  # ref_cut puts the repository root on sys.path
+from tests.script_common import digest_u8 as digest  # noqa: E402
 GOLD = os.path.join(ROOT, "tests", "golden")
-R = os.environ.get("REFERENCE", "/root/reference")
-SND = os.path.join(R, "rx", "rx_sound.cpp")
+SND = "rx/rx_sound.cpp"
 
-# the cuts of oracle/build_ref.sh's sndpath_ref: (macro, first, last, text of the first line, text of the last line)
+# the cuts of oracle/build_ref.sh's sndpath_ref: (file, macro, first, last, text of the first line, text of the last line)
 CUTS = [
-    ("SND_CUT_GPSCONST", 92, 93, "const double gps_delay    = ", "const double gps_week_sec = "),
-    ("SND_CUT_DECLS", 244, 250, "double z1 = 0;", "float sMeterAvg_dB = 0, sMeter_dBm;"),
-    ("SND_CUT_NORM", 306, 319, "int ref_nrx_samps = NRX_SAMPS_CHANS(8);", "}"),
-    ("SND_CUT_TICKS", 536, 537, "const u64_t ticks   = rx->ticks[rx->rd_pos];", "const u64_t dticks  = time_diff48(ticks, clk.ticks);"),
-    ("SND_CUT_GPSSEC", 557, 557, "s->gpssec = fmod(gps_week_sec + clk.gps_secs", "s->gpssec = fmod("),
-    ("SND_CUT_GPSSTAMP", 638, 661, "int sample_filter_delays = norm_nrx_samps - fir_pos;", "s->last_gpssec = s->gpssec;"),
-    ("SND_CUT_PKTINIT", 252, 255, 'strncpy(s->out_pkt_real.h.id, "SND", 3);', "s->seq = 0;"),
-    ("SND_CUT_MASKED", 285, 285, "bool masked = false, masked_area = false, check_masked = false;", "bool masked = false"),
-    ("SND_CUT_OVERLOAD", 295, 295, "bool squelched_overload = false;", "bool squelched_overload = false;"),
-    ("SND_CUT_FLAGS", 461, 482, "#define\tSND_FLAG_LPF", "bool do_de_emp = "),
-    ("SND_CUT_HOOKS", 488, 497, "u2_t bc = 0;", "tid_t receive_real_tid"),
-    ("SND_CUT_PATH", 676, 908, "TYPECPX *s_samps_c = fir_samps_c;", "}"),
-    ("SND_CUT_PACKET", 1035, 1140, "#define SILENCE_VALUE 1", "}"),
-    ("SND_CUT_HEADER", 1222, 1253, "#define SMETER_BIAS 127.0", "wf->snd_seq = s->seq;"),
+    (SND, "SND_CUT_GPSCONST", 92, 93, "const double gps_delay    = ", "const double gps_week_sec = "),
+    (SND, "SND_CUT_DECLS", 244, 250, "double z1 = 0;", "float sMeterAvg_dB = 0, sMeter_dBm;"),
+    (SND, "SND_CUT_NORM", 306, 319, "int ref_nrx_samps = NRX_SAMPS_CHANS(8);", "}"),
+    (SND, "SND_CUT_TICKS", 536, 537, "const u64_t ticks   = rx->ticks[rx->rd_pos];", "const u64_t dticks  = time_diff48(ticks, clk.ticks);"),
+    (SND, "SND_CUT_GPSSEC", 557, 557, "s->gpssec = fmod(gps_week_sec + clk.gps_secs", "s->gpssec = fmod("),
+    (SND, "SND_CUT_GPSSTAMP", 638, 661, "int sample_filter_delays = norm_nrx_samps - fir_pos;", "s->last_gpssec = s->gpssec;"),
+    (SND, "SND_CUT_PKTINIT", 252, 255, 'strncpy(s->out_pkt_real.h.id, "SND", 3);', "s->seq = 0;"),
+    (SND, "SND_CUT_MASKED", 285, 285, "bool masked = false, masked_area = false, check_masked = false;", "bool masked = false"),
+    (SND, "SND_CUT_OVERLOAD", 295, 295, "bool squelched_overload = false;", "bool squelched_overload = false;"),
+    (SND, "SND_CUT_FLAGS", 461, 482, "#define\tSND_FLAG_LPF", "bool do_de_emp = "),
+    (SND, "SND_CUT_HOOKS", 488, 497, "u2_t bc = 0;", "tid_t receive_real_tid"),
+    (SND, "SND_CUT_PATH", 676, 908, "TYPECPX *s_samps_c = fir_samps_c;", "}"),
+    (SND, "SND_CUT_PACKET", 1035, 1140, "#define SILENCE_VALUE 1", "}"),
+    (SND, "SND_CUT_HEADER", 1222, 1253, "#define SMETER_BIAS 127.0", "wf->snd_seq = s->seq;"),
 ]
 # the SAM arm inside the path cut
-ARM = [(791, "case MODE_SAM:"), (802, "wdsp_SAM_demod(rx_chan, s->mode, s->SAM_mparam, ns_out, agc_samps_c, out_samps_s2);"),
-       (804, "m_chan_null_FIR[rx_chan].ProcessData(rx_chan, ns_out, agc_samps_c, NULL);")]
+ARM = [(SND, 791, "case MODE_SAM:"), (SND, 802, "wdsp_SAM_demod(rx_chan, s->mode, s->SAM_mparam, ns_out, agc_samps_c, out_samps_s2);"),
+       (SND, 804, "m_chan_null_FIR[rx_chan].ProcessData(rx_chan, ns_out, agc_samps_c, NULL);")]
 
 
 def build(tmp):
-    lines = open(SND, encoding="latin-1").read().split("\n")
-    for macro, a, b, t1, t2 in CUTS:
-        assert t1 in lines[a - 1] and t2 in lines[b - 1], ("rx_sound.cpp cut moved", macro, a, b)
-        open(os.path.join(tmp, macro + ".inc"), "w", encoding="latin-1").write("\n".join(lines[a - 1:b]) + "\n")
-    for ln, t in ARM:
-        assert t in lines[ln - 1], ("the SAM arm moved", ln, t)
+    ref_cut.cut(tmp, CUTS)
+    ref_cut.pin(ARM)
     gen, fftw = os.path.join(REF, "gen"), os.path.join(REF, "fftw3_api")
     if not os.path.isfile(os.path.join(gen, "kiwi.gen.h")) or not os.path.isdir(fftw):
         sys.exit("oracle/_ref/gen/kiwi.gen.h or oracle/_ref/fftw3_api missing: run oracle/build_ref.sh first")
@@ -68,7 +63,7 @@ def build(tmp):
         inc += [os.path.join(R, top, d) for d in sorted(os.listdir(os.path.join(R, top))) if os.path.isdir(os.path.join(R, top, d))]
     dfn = ["-std=gnu++11", "-DKIWI", "-DKIWISDR", "-DHOST", "-DDEBIAN_VERSION=11", "-DVERSION_MAJ=1", "-DVERSION_MIN=663", "-DARCH_CPU=x86",
            "-DCPU_AM3359", "-DPLATFORM_beaglebone_black"]
-    cuts = ['-D%s="%s.inc"' % (m, m) for m, *_ in CUTS]
+    cuts = ref_cut.cut_macros(CUTS)
     exe = os.path.join(tmp, "sam_ref")
     cmd = (["g++", "-O2", "-ffp-contract=off", "-w"] + dfn + ["-I" + fftw, "-I/opt/rocm/include/hipfft", "-I/opt/rocm/include"]
            + ["-I" + d for d in inc] + ["-I" + gen, "-I" + tmp] + cuts + ["-no-pie", "-o", exe, os.path.join(ROOT, "tools", "ref", "ref_sam_main.cpp")]
@@ -143,10 +138,6 @@ def script_of(rate, lines):
         if ln[0] != "#":
             script.append(ln)
     return script
-
-
-def digest(b):
-    return np.frombuffer(hashlib.sha256(bytes(b)).digest()[:16], np.uint8)
 
 
 def pack(script, y):

@@ -22,12 +22,10 @@ import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import ref_cut
+from ref_cut import R, REF, ROOT  # ref_cut puts the repository root on sys.path
 from tests import spec_common as C  # noqa: E402
 
-REF = os.path.join(ROOT, "oracle", "_ref")
-R = os.environ.get("REFERENCE", "/root/reference")
 
 CUTS = [
     ("rx/rx_sound.cpp", "SPEC_CUT_ROW", 175, 220, "bool specAF_FFT(int rx_chan, int instance, int flags, int ratio, int ns_out, TYPECPX *samps)", "}"),
@@ -74,17 +72,9 @@ PINS = [("rx/rx_sound.cpp", 198, "pwr[i] = samps[i].re * samps[i].re;"),
         ("kiwi.h", 43, "#define CUTESDR_MAX_VAL ((float) ((1 << CUTESDR_SCALE) - 1))")]
 
 
-def read(rel):
-    return open(os.path.join(R, rel), encoding="latin-1").read().split("\n")
-
-
 def build(tmp):
-    for rel, macro, a, b, t1, t2 in CUTS:
-        lines = read(rel)
-        assert t1 in lines[a - 1] and t2 in lines[b - 1], ("cut moved", rel, macro, a, b)
-        open(os.path.join(tmp, macro + ".inc"), "w", encoding="latin-1").write("\n".join(lines[a - 1:b]) + "\n")
-    for rel, ln, t in PINS:
-        assert t in read(rel)[ln - 1], ("statement moved", rel, ln, t)
+    ref_cut.cut(tmp, CUTS)
+    ref_cut.pin(PINS)
     gen, fftw = os.path.join(REF, "gen"), os.path.join(REF, "fftw3_api")
     if not os.path.isfile(os.path.join(gen, "kiwi.gen.h")) or not os.path.isdir(fftw):
         sys.exit("oracle/_ref/gen/kiwi.gen.h or oracle/_ref/fftw3_api missing: run oracle/build_ref.sh first")
