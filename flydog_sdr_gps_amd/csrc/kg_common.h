@@ -66,7 +66,9 @@ template <typename T> using kg_hbuf = kg_buf<T, true>;       // pinned host memo
 // One step's small tables of EVERY stage of a receiver bank in one pinned host block, uploaded with ONE transfer
 // (kg_rxbank.hip).  While a context's `arena` is set and active, kg_ctx_stage / kg_ctx_stage_cached[_ways] neither copy
 // nor cache: in the PLAN pass they append the table to the host block and answer the address it will have on the
-// device (the entry point then returns before its first launch and before it touches its state: KG_PLAN_ONLY); in the
+// device (the entry point then returns before its first launch and before it advances its state: KG_PLAN_ONLY.  What it does
+// in front of that line it does in the PLAN pass too: an entry point that grows a buffer or makes a stream wait for an
+// earlier call's event there -- the waterfall DDC's push does both -- says at that place why a PLAN pass may); in the
 // REPLAY pass -- the same calls with the same arguments, after the block's one upload was enqueued -- they answer the same
 // addresses again, checking that the table is the one planned.
 enum { KG_ARENA_OFF = 0, KG_ARENA_PLAN = 1, KG_ARENA_REPLAY = 2 };

@@ -42,6 +42,7 @@
 // states are stored 128 bits wide (upper limb zero).
 #include <type_traits>
 #include "kg_common.h"
+#include "kg_ddc_plan.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -1170,7 +1171,8 @@ struct kg_ddc {
     kg_dbuf<u32> d_wgtau[2];                   // likewise: the integrator-5 totals of pass B's workgroups, then their start values
 };
 
-static const int DDC_RUN_MIN = 64, DDC_RUN_MAX = 8192, DDC_TARGET_RUNS = 8192;
+static_assert(DDC_PLAN_THREADS == DDC_THREADS && DDC_PLAN_COMB_TILE == DDC_COMB_TILE && DDC_PLAN_BYPASS_BLOCK == BYP_G * 1024 &&
+              DDC_PLAN_ALL == DDC_ALL && DDC_PLAN_NARROW == DDC_NARROW && DDC_PLAN_WIDE == DDC_WIDE, "kg_ddc_plan.h plans for these kernels");
 static const int DDC_MAX_GX = DDC_TARGET_RUNS * 2 / DDC_THREADS;      // workgroups of a run pass per channel: one lane each in ddc_wf_scan_wg_kernel
 static_assert(DDC_MAX_GX <= 64, "ddc_wf_scan_wg_kernel scans one workgroup total per lane");
 static_assert(DDC_THREADS == 256, "ddc_wf_comb_kernel finds a run's pass-B workgroup as run >> 8");
@@ -1419,343 +1421,340 @@ int kg_ddc_wf_tail_after(kg_ddc *d, void *event)
 // when it holds max_out pairs: only the first max_out << log2r samples of the block reach a channel's filters).
 // kg_ddc_wf_step_dev: the sampler mode PER ENTRY (max_out_tab[i]: 0 continuous, >= 1 reset + one-shot of that many pairs) and
 // an offset into each entry's row (out_off[i] pairs): a bank of receivers in both modes in one set of launches.
-static int ddc_push_impl(kg_ddc *d, const void *d_adc, size_t n, const int32_t *chan_list, int nlist,
-                         void *d_out, size_t out_stride, size_t max_out, int64_t *nouts,
-                         const int64_t *max_out_tab = nullptr, const int64_t *out_off = nullptr)
+//
+// ddc_push_impl is the list of a push's steps: check, resets, plan (kg_ddc_plan.h: every decision of the call, pure host
+// arithmetic), buffers, tables, enqueue (which decides nothing), commit.
+struct ddc_push_args {
+    const void *d_adc; size_t n; const int32_t *chan_list; int nlist; void *d_out; size_t out_stride; size_t max_out;
+    int64_t *nouts; const int64_t *max_out_tab, *out_off;
+    u64 cap(int i) const { return max_out_tab ? (u64) max_out_tab[i] : (u64) max_out; }      // 0: continuous sampler
+};
+
+// Step 1: the arguments.
+static int ddc_push_check(kg_ddc *d, const ddc_push_args &a)
 {
-    KG_REQUIRE(d && d_adc && chan_list && d_out, KG_ERR_INVALID, "kg_ddc_wf_push_dev: null argument");
-    auto cap_of = [&](int i) -> u64 { return max_out_tab ? (u64) max_out_tab[i] : (u64) max_out; };     // 0: continuous sampler
-    bool capture = false;                                           // some entry of the call captures
-    for (int i = 0; i < nlist; i++) {
-        KG_REQUIRE(!max_out_tab || (max_out_tab[i] >= 0 && max_out_tab[i] <= ((int64_t) 1 << 31)), KG_ERR_INVALID,
-                   "kg_ddc_wf_step_dev: max_out[%d] = %lld", i, (long long) max_out_tab[i]);
-        KG_REQUIRE(!out_off || (out_off[i] >= 0 && (size_t) out_off[i] <= out_stride), KG_ERR_INVALID,
-                   "kg_ddc_wf_step_dev: out_off[%d] = %lld outside the row", i, out_off ? (long long) out_off[i] : 0ll);
-        capture = capture || cap_of(i) != 0;
+    KG_REQUIRE(d && a.d_adc && a.chan_list && a.d_out, KG_ERR_INVALID, "kg_ddc_wf_push_dev: null argument");
+    for (int i = 0; i < a.nlist; i++) {
+        KG_REQUIRE(!a.max_out_tab || (a.max_out_tab[i] >= 0 && a.max_out_tab[i] <= ((int64_t) 1 << 31)), KG_ERR_INVALID,
+                   "kg_ddc_wf_step_dev: max_out[%d] = %lld", i, (long long) a.max_out_tab[i]);
+        KG_REQUIRE(!a.out_off || (a.out_off[i] >= 0 && (size_t) a.out_off[i] <= a.out_stride), KG_ERR_INVALID,
+                   "kg_ddc_wf_step_dev: out_off[%d] = %lld outside the row", i, a.out_off ? (long long) a.out_off[i] : 0ll);
     }
-    int rc = kg_ctx_use(d->ctx);
-    if (rc) return rc;
-    KG_REQUIRE(n >= 1 && (long) n <= d->max_samples, KG_ERR_INVALID, "kg_ddc_wf_push_dev: n %zu (max %ld)", n, d->max_samples);
-    KG_REQUIRE(nlist >= 1 && nlist <= d->nchan, KG_ERR_INVALID, "kg_ddc_wf_push_dev: nlist %d", nlist);
-    KG_REQUIRE(((uintptr_t) d_adc & 1) == 0 && ((uintptr_t) d_out & 3) == 0, KG_ERR_INVALID,
+    KG_TRY(kg_ctx_use(d->ctx));
+    KG_REQUIRE(a.n >= 1 && (long) a.n <= d->max_samples, KG_ERR_INVALID, "kg_ddc_wf_push_dev: n %zu (max %ld)", a.n, d->max_samples);
+    KG_REQUIRE(a.nlist >= 1 && a.nlist <= d->nchan, KG_ERR_INVALID, "kg_ddc_wf_push_dev: nlist %d", a.nlist);
+    KG_REQUIRE(((uintptr_t) a.d_adc & 1) == 0 && ((uintptr_t) a.d_out & 3) == 0, KG_ERR_INVALID,
                "kg_ddc_wf_push_dev: misaligned pointer");
-    {
-        std::vector<char> &seen = d->seen;                          // (a flag per channel: no quadratic search of the list)
-        seen.assign(d->nchan, 0);
-        for (int i = 0; i < nlist; i++) {
-            const int ch = chan_list[i];
-            KG_REQUIRE(ch >= 0 && ch < d->nchan && d->h_chans[ch].active, KG_ERR_STATE,
-                       "kg_ddc_wf_push_dev: channel %d is not configured", ch);
-            KG_REQUIRE(!seen[ch], KG_ERR_INVALID, "kg_ddc_wf_push_dev: channel %d listed twice", ch);
-            seen[ch] = 1;
+    std::vector<char> &seen = d->seen;                              // (a flag per channel: no quadratic search of the list)
+    seen.assign(d->nchan, 0);
+    for (int i = 0; i < a.nlist; i++) {
+        const int ch = a.chan_list[i];
+        KG_REQUIRE(ch >= 0 && ch < d->nchan && d->h_chans[ch].active, KG_ERR_STATE,
+                   "kg_ddc_wf_push_dev: channel %d is not configured", ch);
+        KG_REQUIRE(!seen[ch], KG_ERR_INVALID, "kg_ddc_wf_push_dev: channel %d listed twice", ch);
+        seen[ch] = 1;
+    }
+    return KG_OK;
+}
+
+// Step 2, not in a bank's PLAN pass (which changes nothing: the planner computes with the counts the reset WILL leave, refuses
+// a rebase, and the replay pass comes here).  Synchronising, rare.
+// A channel a capture left behind holds the filter state of a block cut short: the next CONTINUOUS push starts it
+// from the reset state, as the reference does when it changes sampler mode (CmdWFReset with WF_SAMP_CONTIN,
+// rx/rx_waterfall.cpp:971-978).  (Before the ages are compared: a reset moves the channel's reference point.)
+// Then the 2^62 rule (DDC_PLAN_REBASE_AT): every channel of the call moves its reference point to "now".
+static int ddc_push_resets(kg_ddc *d, const ddc_push_args &a)
+{
+    u64 oldest = 0;
+    for (int i = 0; i < a.nlist; i++) {
+        const int ch = a.chan_list[i];
+        if (a.cap(i) == 0 && d->h_stale[ch]) {
+            KG_TRY(kg_ddc_reset_wf(d, ch));
+            d->h_stale[ch] = 0;
         }
+        if (d->h_pushed[ch] > oldest) oldest = d->h_pushed[ch];
     }
-    // A channel a capture left behind holds the filter state of a block cut short: the next CONTINUOUS push starts it
-    // from the reset state, as the reference does when it changes sampler mode (CmdWFReset with WF_SAMP_CONTIN,
-    // rx/rx_waterfall.cpp:971-978).  Synchronising, rare.  (Before the ages are compared: a reset moves the channel's
-    // reference point.)
-    // (A bank's PLAN pass changes nothing: it computes with the counts the reset WILL leave and the replay pass resets.)
-    const bool plan_pass = d->ctx->arena && d->ctx->arena->mode == KG_ARENA_PLAN;
-    std::vector<char> will_reset(nlist, 0);
-    for (int i = 0; i < nlist; i++)
-            if (cap_of(i) == 0 && d->h_stale[chan_list[i]]) {
-                if (plan_pass) { will_reset[i] = 1; continue; }
-                if ((rc = kg_ddc_reset_wf(d, chan_list[i]))) return rc;
-                d->h_stale[chan_list[i]] = 0;
-            }
-    // Channels whose reference points differ in age (one was retuned -- the most common command of a connection -- or joined
-    // later, or was left out of earlier calls): the call passes the YOUNGEST age as `pushed` and a table of what each entry has
-    // on top of it.  The table is the same from push to push while no channel is touched (every age grows by n), so it rides in
-    // the content-cached per-call tables; rounds 4-5 re-based every other channel of the call instead: two blocking copies per
-    // channel, ~2000 for a bank of 1024 receivers after ONE `SET zoom=`.
-    auto age_of = [&](int i) -> u64 { return will_reset[i] ? 0ull : d->h_pushed[chan_list[i]]; };
-    u64 pushed = age_of(0), oldest = pushed;
-    for (int i = 1; i < nlist; i++) {
-        const u64 a = age_of(i);
-        if (a < pushed) pushed = a;
-        if (a > oldest) oldest = a;
+    if (oldest + (u64) a.n >= DDC_PLAN_REBASE_AT)
+        for (int i = 0; i < a.nlist; i++) KG_TRY(ddc_rebase(d, a.chan_list[i]));
+    return KG_OK;
+}
+
+static ddc_plan_switch ddc_switch_of(const char *text)
+{
+    const ddc_plan_switch s = {text != nullptr, text ? atoi(text) : 0};
+    return s;
+}
+
+// Step 3: the object's state and the tuning switches -> the planner; its refusals in the order it makes its checks.
+static int ddc_push_plan(kg_ddc *d, const ddc_push_args &a, bool plan_pass, ddc_plan &P)
+{
+    std::vector<ddc_plan_entry> e(a.nlist);
+    for (int i = 0; i < a.nlist; i++) {
+        const int ch = a.chan_list[i];
+        const ddc_plan_entry ei = {ch, d->h_chans[ch].log2r, ddc_cur_cnt(d, ch), d->h_pushed[ch], d->h_stale[ch] != 0, a.cap(i),
+                                   a.out_off ? (long) a.out_off[i] : 0l};
+        e[i] = ei;
     }
-    // (the kernels form (age + sample index) x phase_inc in 64 bits mod 2^48: re-base long before anything wraps -- 2^62 samples)
-    KG_REQUIRE(!(plan_pass && oldest + (u64) n >= (1ull << 62)), KG_ERR_STATE, "kg_ddc_wf_push_dev: 2^62 samples since a channel was last set");
-    if (oldest + (u64) n >= (1ull << 62)) {
-        for (int i = 0; i < nlist; i++) if ((rc = ddc_rebase(d, chan_list[i]))) return rc;
-        pushed = 0;
-    }
-    std::vector<u64> h_pdelta(nlist);
-    for (int i = 0; i < nlist; i++) h_pdelta[i] = age_of(i) - pushed;
-    std::vector<long> h_nouts(nlist), h_off(nlist), h_nlim(nlist), h_outoff(nlist);
-    std::vector<int> h_wg(nlist + 1), h_bypass, h_run, h_small, h_rest, h_big, h_reset(nlist);
-    long max_nout = 0, c0_need = 0, comb_wgs = 0, n_run_max = 0, n_by_max = 0, n_run_sum = 0;
-    for (int i = 0; i < nlist; i++) {
-        const int ch = chan_list[i];
-        const ddc_chan &c = d->h_chans[ch];
-        // samples of the block this channel's filters see: all of them, or (capture) what fills the one-shot sampler
-        const bool cap = cap_of(i) != 0;
-        const u64 want = cap ? cap_of(i) << c.log2r : (u64) n;
-        h_reset[i] = cap ? 1 : 0;
-        h_outoff[i] = out_off ? (long) out_off[i] : 0l;
-        h_nlim[i] = (long) (want < (u64) n ? want : (u64) n);
-        h_nouts[i] = (long) (((cap || will_reset[i] ? 0ull : (u64) ddc_cur_cnt(d, ch)) + (u64) h_nlim[i]) >> c.log2r);
-        if (c.log2r) { if (h_nlim[i] > n_run_max) n_run_max = h_nlim[i]; n_run_sum += h_nlim[i]; }
-        else if (h_nlim[i] > n_by_max) n_by_max = h_nlim[i];
-        KG_REQUIRE((size_t) (h_nouts[i] + h_outoff[i]) <= out_stride, KG_ERR_INVALID,
-                   "kg_ddc_wf_push_dev: out_stride %zu < %ld outputs of channel %d (at offset %ld)", out_stride, h_nouts[i], ch, h_outoff[i]);
-        if (h_nouts[i] > max_nout) max_nout = h_nouts[i];
-        if (nouts) nouts[i] = h_nouts[i];
-        h_off[i] = c0_need;
-        if (c.log2r) c0_need += 2 * ((h_nouts[i] + 3) & ~3l);             // I and Q planes, each a multiple of 16 bytes
-        h_wg[i] = (int) comb_wgs;
-        if (c.log2r) comb_wgs += (h_nouts[i] + DDC_COMB_TILE - 1) / DDC_COMB_TILE;
-        else h_bypass.push_back(i);
-        if (c.log2r) { h_run.push_back(i); (c.log2r <= 3 ? h_small : (c.log2r <= 8 ? h_rest : h_big)).push_back(i); }
-    }
-    const size_t nmid = h_rest.size();            // h_rest = the 16 <= R <= 256 entries, then the R >= 512 ones
-    h_rest.insert(h_rest.end(), h_big.begin(), h_big.end());
-    h_wg[nlist] = (int) comb_wgs;
-    KG_REQUIRE(comb_wgs < (1l << 31), KG_ERR_INVALID, "kg_ddc_wf_push_dev: too many outputs in one call");
-    hipStream_t st = d->ctx->stream;
-    const bool defer = d->deferred;
-    const int par = d->parity;                     // this push's buffer set
-    // The buffer set was last used two pushes ago: its output stage must have drained it (deferred mode; long done).
+    const ddc_plan_in in = {(long) a.n, a.out_stride, d->ctx->num_cus, d->max_runs, plan_pass,
+                            ddc_switch_of(kg_tuning_env("KIWIGPU_DDC_RUNS")), ddc_switch_of(kg_tuning_env("KIWIGPU_DDC_SIDE")),
+                            ddc_switch_of(kg_tuning_env("KIWIGPU_DDC_STAGED"))};
+    ddc_plan_make(e.data(), a.nlist, in, P);
+    KG_REQUIRE(P.refusal != DDC_REFUSE_AGE, KG_ERR_STATE, "kg_ddc_wf_push_dev: 2^62 samples since a channel was last set");
+    const int ncounted = P.refusal == DDC_REFUSE_OUT_STRIDE ? P.bad : a.nlist;
+    if (a.nouts) for (int i = 0; i < ncounted; i++) a.nouts[i] = P.nouts[i];
+    KG_REQUIRE(P.refusal != DDC_REFUSE_OUT_STRIDE, KG_ERR_INVALID, "kg_ddc_wf_push_dev: out_stride %zu < %ld outputs of channel %d (at offset %ld)",
+               a.out_stride, P.nouts[P.bad], a.chan_list[P.bad], P.outoff[P.bad]);
+    KG_REQUIRE(P.refusal != DDC_REFUSE_COMB_WGS, KG_ERR_INVALID, "kg_ddc_wf_push_dev: too many outputs in one call");
+    KG_REQUIRE(P.refusal != DDC_REFUSE_NRUNS, KG_ERR_INVALID, "kg_ddc_wf_push_dev: %d runs > %d", P.nruns, d->max_runs);
+    return KG_OK;
+}
+
+// Steps 4 and 5 run in a bank's PLAN pass too, up to the KG_PLAN_ONLY behind them, and there they do more than arithmetic:
+//   - d_c0rel[par] may grow, behind a ddc_sync_all.  This push has enqueued nothing yet, so the drain waits only for
+//     earlier pushes, and the REPLAY pass finds the capacity there.  (The drain clears tail_unjoined, rightly: the
+//     context's stream has then waited for everything.)
+// and, if the object has an output stream (it was in deferred mode once; a receiver bank's DDC never is):
+//   - the context's stream and the second stream are made to wait for ev_tail[par], the output stage that last used this
+//     push's buffer set.  One more wait for an event recorded two pushes ago orders nothing new, and the REPLAY pass
+//     enqueues the same waits again in front of its launches.
+//   - a CHANGED table block makes the context's stream wait for the previous output stage and clears tail_unjoined.  (With
+//     an arena the stage cache is neither asked nor filled, so every block counts as changed.)  The wait lands in front of
+//     the owner's one upload of the step's tables, where it has to be: that upload is what rewrites the tables.  The
+//     REPLAY pass then finds nothing left to join.
+// None of this touches a channel's state, the buffer parity or an event of this push: after a PLAN pass that is never
+// replayed the object computes what it would have computed without it.
+
+// Step 4: this push's buffer set.  It was last used two pushes ago: its output stage must have drained it (deferred mode; long done).
+static int ddc_push_buffers(kg_ddc *d, const ddc_plan &P)
+{
+    const int par = d->parity;
     if (d->tail && d->tail_rec[par]) {
-        KG_HIP(hipStreamWaitEvent(st, d->ev_tail[par], 0));
+        KG_HIP(hipStreamWaitEvent(d->ctx->stream, d->ev_tail[par], 0));
         if (d->side) KG_HIP(hipStreamWaitEvent(d->side, d->ev_tail[par], 0));
     }
-    if (c0_need > d->c0_cap[par]) {
-        if ((rc = ddc_sync_all(d))) return rc;
+    if (P.c0_need > d->c0_cap[par]) {
+        KG_TRY(ddc_sync_all(d));
         d->d_c0rel[par].reset(); d->c0_cap[par] = 0;    // nothing dangles if the allocation below fails
-        KG_TRY(d->d_c0rel[par].alloc((size_t) (c0_need + 16), "kg_ddc_wf_push_dev: comb inputs"));
-        d->c0_cap[par] = c0_need;
+        KG_TRY(d->d_c0rel[par].alloc((size_t) (P.c0_need + 16), "kg_ddc_wf_push_dev: comb inputs"));
+        d->c0_cap[par] = P.c0_need;
     }
-    ddc_state4 *const d_local = d->d_local[par];
-    u32 *const d_c0rel = d->d_c0rel[par], *const d_tau = d->d_tau[par];
-    // run length: a power of two between 64 and 8192, about 8192 runs per call
-    // One thread per (channel, run): with few channels take more, shorter runs so that the two
-    // run passes still put about four waves on every SIMD (14 channels on MI355X: 16384 runs
-    // instead of 8192 = 2.18 -> 1.91 ms per 2^24 samples, although the state scan doubles).
-    int target = DDC_TARGET_RUNS;
-    {
-        const long want_threads = (long) d->ctx->num_cus * 4 * 4 * 64;
-        const long per_chan = (want_threads + nlist - 1) / nlist;
-        if (per_chan > target) target = per_chan < d->max_runs ? (int) per_chan : d->max_runs;
+    return KG_OK;
+}
+
+struct ddc_tabs {                                 // the staged tables of a push, on the device
+    const long *c0off, *nouts, *nlim, *outoff; const u64 *pdelta; const int *list, *wgoff, *bypass, *run, *small, *rest, *reset;
+};
+
+// Step 5.  The per-call tables go through the context's staging ring in one piece: no stream synchronisation, and the
+// previous call's kernels keep their own copy.
+static int ddc_push_tables(kg_ddc *d, const ddc_plan &P, ddc_tabs &t)
+{
+    const int par = d->parity;
+    // a CHANGED table is rewritten in the order of the context's stream: the previous push's output stage, on its own
+    // stream in deferred mode, may still be reading the old one -- join it first (a steady stream never gets here)
+    if (d->tail && d->tail_rec[par ^ 1] && d->tail_unjoined &&
+        !(d->pack_cache.bytes == P.block.size() && d->pack_cache.host && memcmp(d->pack_cache.host, P.block.data(), P.block.size()) == 0)) {
+        KG_HIP(hipStreamWaitEvent(d->ctx->stream, d->ev_tail[par ^ 1], 0));
+        d->tail_unjoined = false;
     }
-    if (const char *e = kg_tuning_env("KIWIGPU_DDC_RUNS")) { const int v = atoi(e); if (v >= 64 && v <= d->max_runs) target = v; }
-    // the runs cover the longest share of the block any filtered channel takes (the whole block unless capturing)
-    const long n_cover = n_run_max > 0 ? n_run_max : 1;
-    int L = DDC_RUN_MIN;
-    while (L < DDC_RUN_MAX && (long) ((n_cover + L - 1) / L) > target) L <<= 1;
-    if (capture) {
-        // a capture's channels take very different shares (8192 R samples each): size the runs by the TOTAL work, about
-        // four waves per SIMD over all of them, inside what the longest share allows
-        const long want_threads = (long) d->ctx->num_cus * 4 * 4 * 64;
-        // (runs of at most 1024 samples: pass A then integrates every decimation in 64 bits -- short_zero_run in
-        // ddc_wf_run_body; with SURVEY's receiver mix, 352 M sample-channels per step, the total-work rule alone chose 2048 and
-        // pass A of the R >= 512 channels ran its 128-bit form: 1.13 ms per step against pass B's 0.71)
-        int Lw = DDC_RUN_MIN;
-        while (Lw < 1024 && n_run_sum / Lw > want_threads) Lw <<= 1;
-        if (Lw > L) L = Lw;
-        while (L < DDC_RUN_MAX && (n_cover + L - 1) / L > d->max_runs) L <<= 1;
+    void *base = nullptr;
+    KG_TRY(kg_ctx_stage_cached(d->ctx, &d->pack_cache, P.block.data(), P.block.size(), &base));
+    const unsigned char *b = (const unsigned char *) base;
+    t.c0off = (const long *) (b + P.o_c0off); t.nouts = (const long *) (b + P.o_nouts); t.nlim = (const long *) (b + P.o_nlim);
+    t.pdelta = (const u64 *) (b + P.o_pdelta); t.list = (const int *) (b + P.o_list); t.wgoff = (const int *) (b + P.o_wgoff);
+    t.bypass = (const int *) (b + P.o_bypass); t.run = (const int *) (b + P.o_run);
+    t.small = (const int *) (b + P.o_small); t.rest = (const int *) (b + P.o_rest);
+    t.reset = (const int *) (b + P.o_reset); t.outoff = (const long *) (b + P.o_outoff);
+    return KG_OK;
+}
+
+// Step 6 in three parts, each enqueueing what the plan says where the plan says.
+struct ddc_push_job {
+    kg_ddc *d; const ddc_push_args &a; const ddc_plan &P; const ddc_tabs &t;
+    int par;                                       // this push's buffer set
+    bool defer;
+    hipStream_t st, ost;                           // the context's stream; where the writers of the caller's rows run
+    bool side_used;
+};
+
+static int ddc_side_ready(kg_ddc *d)
+{
+    if (!d->side) {
+        KG_TRY(kg_stream_get(d->ctx->device, &d->side));
+        KG_HIP(hipEventCreateWithFlags(&d->ev_fork, hipEventDisableTiming));
+        KG_HIP(hipEventCreateWithFlags(&d->ev_join, hipEventDisableTiming));
     }
-    const int nruns = (int) ((n_cover + L - 1) / L);
-    int log2L = 0;
-    while ((1 << log2L) < L) log2L++;
-    KG_REQUIRE(nruns <= d->max_runs, KG_ERR_INVALID, "kg_ddc_wf_push_dev: %d runs > %d", nruns, d->max_runs);
-    // The per-call tables go through the context's staging ring in one piece: no stream
-    // synchronisation, and the previous call's kernels keep their own copy.
-    const long *s_c0off, *s_nouts, *s_nlim, *s_outoff; const u64 *s_pdelta; const int *s_list, *s_wgoff, *s_bypass, *s_selrun, *s_selsmall, *s_selrest, *s_reset;
-    {
-        std::vector<unsigned char> pack;
-        auto put = [&](const void *src, size_t bytes) -> size_t {
-            const size_t at = (pack.size() + 15) & ~(size_t) 15;
-            pack.resize(at + bytes);
-            if (bytes) memcpy(pack.data() + at, src, bytes);
-            return at;
-        };
-        const size_t o_off = put(h_off.data(), sizeof(long) * nlist), o_nouts = put(h_nouts.data(), sizeof(long) * nlist);
-        const size_t o_nlim = put(h_nlim.data(), sizeof(long) * nlist), o_pdelta = put(h_pdelta.data(), sizeof(u64) * nlist);
-        const size_t o_list = put(chan_list, sizeof(int) * nlist);
-        const size_t o_wg = put(h_wg.data(), sizeof(int) * (nlist + 1));
-        const size_t o_by = put(h_bypass.data(), sizeof(int) * h_bypass.size());
-        const size_t o_run = put(h_run.data(), sizeof(int) * h_run.size());
-        const size_t o_small = put(h_small.data(), sizeof(int) * h_small.size());
-        const size_t o_rest = put(h_rest.data(), sizeof(int) * h_rest.size());
-        const size_t o_reset = put(h_reset.data(), sizeof(int) * nlist), o_outoff = put(h_outoff.data(), sizeof(long) * nlist);
-        // a CHANGED table is rewritten in the order of the context's stream: the previous push's output stage, on its own
-        // stream in deferred mode, may still be reading the old one -- join it first (a steady stream never gets here)
-        if (d->tail && d->tail_rec[par ^ 1] && d->tail_unjoined &&
-            !(d->pack_cache.bytes == pack.size() && d->pack_cache.host && memcmp(d->pack_cache.host, pack.data(), pack.size()) == 0)) {
-            KG_HIP(hipStreamWaitEvent(st, d->ev_tail[par ^ 1], 0));
-            d->tail_unjoined = false;
-        }
-        void *base = nullptr;
-        if ((rc = kg_ctx_stage_cached(d->ctx, &d->pack_cache, pack.data(), pack.size(), &base))) return rc;
-        const unsigned char *b = (const unsigned char *) base;
-        s_c0off = (const long *) (b + o_off); s_nouts = (const long *) (b + o_nouts); s_nlim = (const long *) (b + o_nlim);
-        s_list = (const int *) (b + o_list); s_wgoff = (const int *) (b + o_wg);
-        s_bypass = (const int *) (b + o_by); s_selrun = (const int *) (b + o_run);
-        s_selsmall = (const int *) (b + o_small); s_selrest = (const int *) (b + o_rest);
-        s_reset = (const int *) (b + o_reset); s_outoff = (const long *) (b + o_outoff); s_pdelta = (const u64 *) (b + o_pdelta);
-    }
-    KG_PLAN_ONLY(d->ctx);
-    // The object's second stream: work that does not depend on the pass A -> scan -> pass B chain runs beside
-    // it -- the R = 1 bypass channels (no filter state at all) from the start, pass B of the R <= 8 channels
-    // (below) -- and joins before the call's last kernels.  KIWIGPU_DDC_SIDE=0: everything in line.
-    bool side_on = true, side_used = false;
-    if (const char *e = kg_tuning_env("KIWIGPU_DDC_SIDE")) side_on = atoi(e) != 0;
-    auto side_ready = [&]() -> int {
-        if (!d->side) {
-            KG_TRY(kg_stream_get(d->ctx->device, &d->side));
-            KG_HIP(hipEventCreateWithFlags(&d->ev_fork, hipEventDisableTiming));
-            KG_HIP(hipEventCreateWithFlags(&d->ev_join, hipEventDisableTiming));
-        }
-        return KG_OK;
-    };
+    return KG_OK;
+}
+
+// Where the output stage runs, and the R = 1 bypass kernel.
+static int ddc_enqueue_bypass(ddc_push_job &j)
+{
+    kg_ddc *d = j.d; const ddc_push_args &a = j.a; const ddc_plan &P = j.P; const ddc_tabs &t = j.t;
     // Deferred mode: the output stage's stream starts behind the tables and the caller's samples (fork event), behind the
     // previous push's output stage (stream order) and behind the caller's last reader of the rows (kg_ddc_wf_tail_after).
-    hipStream_t ost = st;                          // where the writers of the caller's rows run
-    if (defer) {
-        if ((rc = side_ready())) return rc;
-        ost = d->tail;
-        KG_HIP(hipEventRecord(d->ev_fork, st));
-        KG_HIP(hipStreamWaitEvent(ost, d->ev_fork, 0));
-        if (d->after_ev) KG_HIP(hipStreamWaitEvent(ost, (hipEvent_t) d->after_ev, 0));
+    if (j.defer) {
+        KG_TRY(ddc_side_ready(d));
+        j.ost = d->tail;
+        KG_HIP(hipEventRecord(d->ev_fork, j.st));
+        KG_HIP(hipStreamWaitEvent(j.ost, d->ev_fork, 0));
+        if (d->after_ev) KG_HIP(hipStreamWaitEvent(j.ost, (hipEvent_t) d->after_ev, 0));
     } else if (d->after_ev) {
-        KG_HIP(hipStreamWaitEvent(st, (hipEvent_t) d->after_ev, 0));
+        KG_HIP(hipStreamWaitEvent(j.st, (hipEvent_t) d->after_ev, 0));
     }
     d->after_ev = nullptr;
-    if (!h_bypass.empty()) {
-        hipStream_t bst = ost;
-        if (!defer && side_on && !h_run.empty()) {
-            if ((rc = side_ready())) return rc;
-            KG_HIP(hipEventRecord(d->ev_fork, st));                  // behind the staged tables
-            KG_HIP(hipStreamWaitEvent(d->side, d->ev_fork, 0));
-            bst = d->side; side_used = true;
-        }
-        const long nblk_by = (n_by_max + BYP_G * 1024 - 1) / (BYP_G * 1024), cap_by = (long) d->ctx->num_cus * 4;   // LDS: 20 KiB each, 4 per CU
-        hipLaunchKernelGGL(ddc_wf_bypass_kernel, dim3((unsigned) (nblk_by < cap_by ? nblk_by : cap_by)), dim3(256),
-                           0, bst, (const short *) d_adc, (long) n_by_max, (const ddc_chan *) d->d_chans, s_list,
-                           s_bypass, (int) h_bypass.size(), (const u32 *) d->d_nco, (short2 *) d_out, (long) out_stride, pushed, s_pdelta, s_nlim, s_outoff, d->ctx->rows_by_chan);
-        KG_HIP(hipGetLastError());
-        if (defer) KG_HIP(hipEventRecord(d->ev_adc, bst));           // the output stream's only reader of d_adc
+    if (P.bypass.empty()) return KG_OK;
+    hipStream_t bst = j.ost;
+    if (!j.defer && P.bypass_beside) {
+        KG_TRY(ddc_side_ready(d));
+        KG_HIP(hipEventRecord(d->ev_fork, j.st));                    // behind the staged tables
+        KG_HIP(hipStreamWaitEvent(d->side, d->ev_fork, 0));
+        bst = d->side; j.side_used = true;
     }
+    hipLaunchKernelGGL(ddc_wf_bypass_kernel, dim3((unsigned) P.bypass_blocks), dim3(256),
+                       0, bst, (const short *) a.d_adc, (long) P.n_by_max, (const ddc_chan *) d->d_chans, t.list,
+                       t.bypass, (int) P.bypass.size(), (const u32 *) d->d_nco, (short2 *) a.d_out, (long) a.out_stride, P.pushed, t.pdelta, t.nlim, t.outoff, d->ctx->rows_by_chan);
+    KG_HIP(hipGetLastError());
+    if (j.defer) KG_HIP(hipEventRecord(d->ev_adc, bst));             // the output stream's only reader of d_adc
+    return KG_OK;
+}
+
+// The run passes on the context's stream: end coefficients, pass A, the state scan, pass B.
+static int ddc_enqueue_runs(ddc_push_job &j)
+{
+    kg_ddc *d = j.d; const ddc_push_args &a = j.a; const ddc_plan &P = j.P; const ddc_tabs &t = j.t;
+    const int par = j.par;
+    hipStream_t st = j.st;
+    ddc_state4 *const d_local = d->d_local[par];
+    u32 *const d_c0rel = d->d_c0rel[par], *const d_tau = d->d_tau[par];
     // end-referred carry states (round 4): the coefficients of the runs' distances to the end, then prefix sums inside
     // pass A's workgroups + one wave per (channel, I/Q) over the workgroup totals
-    if (!h_run.empty() && (d->endco_n != n_cover || d->endco_L != L || d->endco_runs != nruns)) {
+    if (!P.run.empty() && (d->endco_n != P.n_cover || d->endco_L != P.L || d->endco_runs != P.nruns)) {
         // (a changed block length: rare.  The previous push's pass B may still be reading the old table on the object's
         // second stream)
-        if ((rc = ddc_sync_all(d))) return rc;
-        hipLaunchKernelGGL(ddc_endco_kernel, dim3((unsigned) ((nruns + 1 + 255) / 256)), dim3(256), 0, st, d->d_endco, n_cover, L, nruns);
+        KG_TRY(ddc_sync_all(d));
+        hipLaunchKernelGGL(ddc_endco_kernel, dim3((unsigned) ((P.nruns + 1 + 255) / 256)), dim3(256), 0, st, d->d_endco, P.n_cover, P.L, P.nruns);
         KG_HIP(hipGetLastError());
-        d->endco_n = n_cover; d->endco_L = L; d->endco_runs = nruns;
+        d->endco_n = P.n_cover; d->endco_L = P.L; d->endco_runs = P.nruns;
     }
-    const unsigned gx = (unsigned) ((nruns + DDC_THREADS - 1) / DDC_THREADS);
-    if (!h_run.empty()) {
-        // (runs of at most 1024 samples: every decimation integrates from zero in 64 bits -- the narrow form alone)
-        auto pass_a = L <= 1024 ? ddc_wf_run_kernel<false, DDC_NARROW> : ddc_wf_run_kernel<false, DDC_ALL>;
-        hipLaunchKernelGGL(pass_a, dim3(gx, (unsigned) h_run.size()), dim3(DDC_THREADS), 0, st,
-                           (const short *) d_adc, (long) n, L, nruns, (const ddc_chan *) d->d_chans, s_list,
-                           (const u32 *) d->d_nco, d_local, d_c0rel, d_tau, s_c0off,
-                           s_nouts, s_selrun, 0, pushed, s_pdelta, s_nlim, s_reset, (const ddc_endco *) d->d_endco, d->endco_n,
+    if (!P.run.empty()) {
+        auto pass_a = P.a_narrow ? ddc_wf_run_kernel<false, DDC_NARROW> : ddc_wf_run_kernel<false, DDC_ALL>;
+        hipLaunchKernelGGL(pass_a, dim3((unsigned) P.gx, (unsigned) P.run.size()), dim3(DDC_THREADS), 0, st,
+                           (const short *) a.d_adc, (long) a.n, P.L, P.nruns, (const ddc_chan *) d->d_chans, t.list,
+                           (const u32 *) d->d_nco, d_local, d_c0rel, d_tau, t.c0off,
+                           t.nouts, t.run, 0, P.pushed, t.pdelta, t.nlim, t.reset, (const ddc_endco *) d->d_endco, d->endco_n,
                            d->d_wgtot[par], (const ddc_state4 *) nullptr, (u32 *) nullptr);
         KG_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(ddc_wf_scan_wg_kernel, dim3((unsigned) (2 * nlist)), dim3(64), 0, st, (const ddc_state4 *) d->d_wgtot[par],
-                       d->d_wgbase[par], (int) gx, d->d_chans, s_list, s_nlim, s_reset);
+    hipLaunchKernelGGL(ddc_wf_scan_wg_kernel, dim3((unsigned) (2 * a.nlist)), dim3(64), 0, st, (const ddc_state4 *) d->d_wgtot[par],
+                       d->d_wgbase[par], P.gx, d->d_chans, t.list, t.nlim, t.reset);
     KG_HIP(hipGetLastError());
-    // Pass B.  The staged strobe flush (R <= 8) needs 34 KiB more LDS, hence its own launch.  Neither
-    // launch fills the GPU by itself (a lane walks a whole run: 64 workgroups per channel), so when both
-    // kinds of channel are present the staged launch runs beside the other one on a second stream of the
-    // object (fork after the state scan, join before the run-total prefix); with only small decimations
-    // it pays once those channels fill the GPU by themselves, otherwise the scattered stores are cheaper
-    // than the smaller grid.
-    bool staged = (long) h_small.size() * nruns >= (long) d->ctx->num_cus * 4 * 2 * 64;
-    const bool beside = side_on && !h_small.empty() && !h_rest.empty();
-    if (const char *e = kg_tuning_env("KIWIGPU_DDC_STAGED")) staged = atoi(e) != 0 && !h_small.empty();
-    auto pass_b = [&](hipStream_t s, size_t nwhich, const int *sel, int stage, int mode) {
-        auto k = mode == DDC_NARROW ? ddc_wf_run_kernel<true, DDC_NARROW> : (mode == DDC_WIDE ? ddc_wf_run_kernel<true, DDC_WIDE> : ddc_wf_run_kernel<true, DDC_ALL>);
-        hipLaunchKernelGGL(k, dim3(gx, (unsigned) nwhich), dim3(DDC_THREADS), stage, s,
-                           (const short *) d_adc, (long) n, L, nruns, (const ddc_chan *) d->d_chans, s_list,
-                           (const u32 *) d->d_nco, d_local, d_c0rel, d_tau, s_c0off, s_nouts, sel, stage, pushed, s_pdelta, s_nlim, s_reset, (const ddc_endco *) d->d_endco, d->endco_n,
+    // Pass B (ddc_plan_launches): the one launch on the second stream forks behind the state scan and joins before the
+    // run-total prefix.
+    const int *const sels[3] = {t.run, t.small, t.rest};
+    for (int k = 0; k < P.nb; k++) {
+        const ddc_plan_launch &l = P.b[k];
+        hipStream_t s = st;
+        if (l.side) {
+            KG_TRY(ddc_side_ready(d));
+            j.side_used = true;
+            KG_HIP(hipEventRecord(d->ev_fork, st));
+            KG_HIP(hipStreamWaitEvent(d->side, d->ev_fork, 0));
+            s = d->side;
+        }
+        const int stage = l.staged ? DDC_STAGE_BYTES : 0;
+        auto pass_b = l.mode == DDC_NARROW ? ddc_wf_run_kernel<true, DDC_NARROW> : (l.mode == DDC_WIDE ? ddc_wf_run_kernel<true, DDC_WIDE> : ddc_wf_run_kernel<true, DDC_ALL>);
+        hipLaunchKernelGGL(pass_b, dim3((unsigned) P.gx, (unsigned) l.count), dim3(DDC_THREADS), stage, s,
+                           (const short *) a.d_adc, (long) a.n, P.L, P.nruns, (const ddc_chan *) d->d_chans, t.list,
+                           (const u32 *) d->d_nco, d_local, d_c0rel, d_tau, t.c0off, t.nouts, sels[l.sel] + l.first, stage, P.pushed, t.pdelta, t.nlim, t.reset, (const ddc_endco *) d->d_endco, d->endco_n,
                            (ddc_state4 *) nullptr, (const ddc_state4 *) d->d_wgbase[par], d->d_wgtau[par]);
-    };
-    // The entries above R = 8 by the form they need (DDC_NARROW / DDC_WIDE: fewer registers, more waves per SIMD) -- as two
-    // launches when each of them fills the GPU by itself (a bank of receivers), as one launch of the general form otherwise
-    // (configs[2]'s five and three such channels: two half-empty launches one after the other would lose more than the
-    // waves gain).
-    const long fill = (long) d->ctx->num_cus * 4 * 2 * 64;
-    const size_t nbig = h_rest.size() - nmid;
-    const bool split = (nmid == 0 || (long) nmid * nruns >= fill) && (nbig == 0 || (long) nbig * nruns >= fill);
-    auto pass_b_rest = [&](hipStream_t s) {
-        if (h_rest.empty()) return;
-        if (!split) { pass_b(s, h_rest.size(), s_selrest, 0, DDC_ALL); return; }
-        if (nmid) pass_b(s, nmid, s_selrest, 0, DDC_NARROW);
-        if (nbig) pass_b(s, nbig, s_selrest + nmid, 0, DDC_WIDE);
-    };
-    if (beside) {
-        if ((rc = side_ready())) return rc;
-        side_used = true;
-        KG_HIP(hipEventRecord(d->ev_fork, st));
-        KG_HIP(hipStreamWaitEvent(d->side, d->ev_fork, 0));
-        pass_b(d->side, h_small.size(), s_selsmall, DDC_STAGE_BYTES, DDC_ALL);
-        KG_HIP(hipGetLastError());
-        pass_b_rest(st);
-        KG_HIP(hipGetLastError());
-    } else if (staged) {
-        pass_b(st, h_small.size(), s_selsmall, DDC_STAGE_BYTES, DDC_ALL);
-        KG_HIP(hipGetLastError());
-        pass_b_rest(st);
-        KG_HIP(hipGetLastError());
-    } else if (!h_small.empty()) {
-        pass_b(st, h_run.size(), s_selrun, 0, DDC_ALL);           // a few R <= 8 entries, not staged: everything in one launch
-        KG_HIP(hipGetLastError());
-    } else if (!h_run.empty()) {
-        pass_b_rest(st);
         KG_HIP(hipGetLastError());
     }
-    // The output stage: run-total prefix, combs, comb history -- in line on the context's stream, or (deferred) on the
-    // object's output stream behind this push's run passes, with the context's stream free for the next push's.
-    if (defer) {
+    return KG_OK;
+}
+
+// The output stage: run-total prefix, combs, comb history -- in line on the context's stream, or (deferred) on the
+// object's output stream behind this push's run passes, with the context's stream free for the next push's.
+static int ddc_enqueue_output(ddc_push_job &j)
+{
+    kg_ddc *d = j.d; const ddc_push_args &a = j.a; const ddc_plan &P = j.P; const ddc_tabs &t = j.t;
+    const int par = j.par;
+    hipStream_t st = j.st, ost = j.ost;
+    if (j.defer) {
         KG_HIP(hipEventRecord(d->ev_runs, st));
         KG_HIP(hipStreamWaitEvent(ost, d->ev_runs, 0));
     }
-    if (side_used) {                              // everything the second stream did is behind this point of the output stage
+    if (j.side_used) {                            // everything the second stream did is behind this point of the output stage
         KG_HIP(hipEventRecord(d->ev_join, d->side));
         KG_HIP(hipStreamWaitEvent(ost, d->ev_join, 0));
     }
-    hipLaunchKernelGGL(ddc_wf_tau_wg_kernel, dim3(2 * nlist), dim3(64), 0, ost, d->d_wgtau[par], (int) gx, d->d_chans, s_list,
-                       s_reset);
+    hipLaunchKernelGGL(ddc_wf_tau_wg_kernel, dim3(2 * a.nlist), dim3(64), 0, ost, d->d_wgtau[par], P.gx, d->d_chans, t.list,
+                       t.reset);
     KG_HIP(hipGetLastError());
-    if (comb_wgs > 0) {
-        hipLaunchKernelGGL(ddc_wf_comb_kernel, dim3((unsigned) comb_wgs), dim3(256), 0, ost,
-                           (const u32 *) d_c0rel, (const u32 *) d_tau, log2L, nruns, s_c0off,
-                           (const ddc_chan *) d->d_chans, s_list, s_nouts,
-                           pushed, s_pdelta, s_reset, s_wgoff, nlist, (short2 *) d_out, (long) out_stride, s_outoff,
-                           d->d_hist, (const u32 *) d->d_wgtau[par], (int) gx, d->ctx->rows_by_chan);
+    if (P.comb_wgs > 0) {
+        hipLaunchKernelGGL(ddc_wf_comb_kernel, dim3((unsigned) P.comb_wgs), dim3(256), 0, ost,
+                           (const u32 *) d->d_c0rel[par], (const u32 *) d->d_tau[par], P.log2L, P.nruns, t.c0off,
+                           (const ddc_chan *) d->d_chans, t.list, t.nouts,
+                           P.pushed, t.pdelta, t.reset, t.wgoff, a.nlist, (short2 *) a.d_out, (long) a.out_stride, t.outoff,
+                           d->d_hist, (const u32 *) d->d_wgtau[par], P.gx, d->ctx->rows_by_chan);
         KG_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(ddc_wf_finish_kernel, dim3((nlist + 63) / 64), dim3(64), 0, ost, d->d_chans,
-                       s_list, nlist, (long) n, s_nouts, (const u32 *) d->d_hist, s_reset);
+    hipLaunchKernelGGL(ddc_wf_finish_kernel, dim3((a.nlist + 63) / 64), dim3(64), 0, ost, d->d_chans,
+                       t.list, a.nlist, (long) a.n, t.nouts, (const u32 *) d->d_hist, t.reset);
     KG_HIP(hipGetLastError());
     if (d->tail) {                                // (also in line: a later deferred push finds its buffer set covered)
         KG_HIP(hipEventRecord(d->ev_tail[par], ost));
         d->tail_rec[par] = true;
-        d->tail_unjoined = defer;
+        d->tail_unjoined = j.defer;
     }
-    if (defer) {
+    if (j.defer) {
         // Everything that READS the caller's samples is ordered in front of whatever the caller enqueues next on the
         // context's stream (a streaming caller refills or recycles d_adc there): the run passes are on that stream already;
         // the bypass kernel (output stream) and pass B of the small decimations (second stream) are joined here.  Only the
         // readers: the output stage proper (run-total prefix, combs) stays free to run beside the next push.
-        if (!h_bypass.empty()) KG_HIP(hipStreamWaitEvent(st, d->ev_adc, 0));
-        if (side_used) KG_HIP(hipStreamWaitEvent(st, d->ev_join, 0));
-    }
-    d->parity = par ^ 1;
-    for (int i = 0; i < nlist; i++) {
-        d->h_pushed[chan_list[i]] += (u64) n;                      // the NCO runs through the whole block either way
-        if (cap_of(i) != 0) d->h_stale[chan_list[i]] = 1;          // filters stopped short of the block's end
+        if (!P.bypass.empty()) KG_HIP(hipStreamWaitEvent(st, d->ev_adc, 0));
+        if (j.side_used) KG_HIP(hipStreamWaitEvent(st, d->ev_join, 0));
     }
     return KG_OK;
 }
+
+static int ddc_push_enqueue(kg_ddc *d, const ddc_push_args &a, const ddc_plan &P, const ddc_tabs &t)
+{
+    ddc_push_job j = {d, a, P, t, d->parity, d->deferred, d->ctx->stream, d->ctx->stream, false};
+    KG_TRY(ddc_enqueue_bypass(j));
+    KG_TRY(ddc_enqueue_runs(j));
+    return ddc_enqueue_output(j);
+}
+
+// Step 7: the push is in the queues.
+static void ddc_push_commit(kg_ddc *d, const ddc_push_args &a)
+{
+    d->parity ^= 1;
+    for (int i = 0; i < a.nlist; i++) {
+        d->h_pushed[a.chan_list[i]] += (u64) a.n;                  // the NCO runs through the whole block either way
+        if (a.cap(i) != 0) d->h_stale[a.chan_list[i]] = 1;         // filters stopped short of the block's end
+    }
+}
+
+static int ddc_push_impl(kg_ddc *d, const void *d_adc, size_t n, const int32_t *chan_list, int nlist,
+                         void *d_out, size_t out_stride, size_t max_out, int64_t *nouts,
+                         const int64_t *max_out_tab = nullptr, const int64_t *out_off = nullptr)
+{
+    const ddc_push_args a = {d_adc, n, chan_list, nlist, d_out, out_stride, max_out, nouts, max_out_tab, out_off};
+    KG_TRY(ddc_push_check(d, a));
+    const bool plan_pass = d->ctx->arena && d->ctx->arena->mode == KG_ARENA_PLAN;
+    if (!plan_pass) KG_TRY(ddc_push_resets(d, a));
+    ddc_plan P;
+    ddc_tabs t;
+    KG_TRY(ddc_push_plan(d, a, plan_pass, P));
+    KG_TRY(ddc_push_buffers(d, P));
+    KG_TRY(ddc_push_tables(d, P, t));
+    KG_PLAN_ONLY(d->ctx);
+    KG_TRY(ddc_push_enqueue(d, a, P, t));
+    ddc_push_commit(d, a);
+    return KG_OK;
+}
+
 
 int kg_ddc_wf_push_dev(kg_ddc *d, const void *d_adc, size_t n, const int32_t *chan_list, int nlist,
                        void *d_out, size_t out_stride, int64_t *nouts)

@@ -586,7 +586,7 @@ static int wf_prepass(kg_wf *w, int nframes, const int32_t *chan_of, const uint6
     int rc = kg_ctx_stage(w->ctx, w->pre_c.data(), sizeof(kg_wf::pre_chan) * w->pre_c.size(), &d_c);
     if (rc) return rc;
     if ((rc = kg_ctx_stage(w->ctx, w->pre_f.data(), sizeof(kg_wf::pre_frame) * w->pre_f.size(), &d_f))) return rc;
-    if (w->ctx->arena && w->ctx->arena->mode == KG_ARENA_PLAN) return KG_OK;
+    KG_PLAN_ONLY(w->ctx);
     return kg_nb_wf_launch(w->ctx, w->nb, (int) w->pre_c.size(), d_c, d_f, d_iq, w->d_windows, d_rows);
 }
 

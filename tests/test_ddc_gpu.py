@@ -332,6 +332,52 @@ def test_many_small_decimations_take_the_staged_strobe_path(gpu_ctx, oracle):
         d.close()
 
 
+def test_small_decimations_alone_take_the_staged_launch_in_line(gpu_ctx, oracle):
+    """Eight channels with R = 2, 4, 8 and nothing else, 2^20 - 27 samples: the planner (csrc/kg_ddc_plan.h) raises the target
+    to max_runs = 16384 runs of 64, and 8 x 16384 = 131072 runs fill a 256-CU device (fill = CUs x 512), so pass B is ONE staged
+    launch on the context's stream -- no launch beside it, which every other test with staged channels has.  This is the smallest
+    such shape: a staged launch needs channels x ceil(n / 64) >= 131072.  The second, short push takes the plain one-launch form
+    with the counters no longer aligned.  Bit-exact per channel, state carried."""
+    rng = np.random.default_rng(32)
+    l2 = [1, 2, 3, 1, 2, 3, 1, 2]
+    nch = len(l2)
+    incs = [int(rng.integers(0, 1 << 48)) for _ in range(nch)]
+    d = Ddc(gpu_ctx, nchan=nch, max_samples=1 << 20)
+    try:
+        for ch in range(nch):
+            d.set_wf(ch, incs[ch], 1 << l2[ch])
+        states = [None] * nch
+        for n, seed in (((1 << 20) - 27, 61), ((1 << 16) + 5, 62)):
+            adc = adc_stream(n, seed=seed)
+            got = d.push(adc, list(range(nch)))
+            for ch in range(nch):
+                want, states[ch] = oracle.ddc_wf(adc, incs[ch], l2[ch], states[ch])
+                assert got[ch].shape == want.shape and np.array_equal(got[ch], want), (ch, l2[ch], n)
+    finally:
+        d.close()
+
+
+def test_runs_longer_than_1024_samples_take_the_wide_pass_a(gpu_ctx, oracle):
+    """2^24 + 1 samples, two channels: the target is capped at max_runs = 16384 and 16385 runs of 1024 are one too many, so the
+    planner takes 8193 runs of 2048 (33 workgroups, the last with one run of one sample) and pass A is the general form: 64-bit
+    for R = 64, 128-bit for R = 1024.  No shorter block gets there on a 256-CU device: the target is at least 8192 runs, and it
+    is 16384 for fewer than 17 channels."""
+    n = (1 << 24) + 1
+    adc = adc_stream(n, seed=63, tones=((0.0123, 9000.0),))
+    chans = [(inc_for(0.0123 + 2.0 ** -22), 6), (inc_for(0.0123 - 2.0 ** -21), 10)]
+    d = Ddc(gpu_ctx, nchan=len(chans), max_samples=n)
+    try:
+        for ch, (inc, log2r) in enumerate(chans):
+            d.set_wf(ch, inc, 1 << log2r)
+        got = d.push(adc, [0, 1])
+        for ch, (inc, log2r) in enumerate(chans):
+            want, _ = oracle.ddc_wf(adc, inc, log2r)
+            assert got[ch].shape == want.shape and np.array_equal(got[ch], want), ch
+            assert np.abs(want[8:].astype(int)).max() > 1000
+    finally:
+        d.close()
+
+
 # ---- the other RX instances: rx3 (wide, 20.25 kHz) and rx14 (17-tap CICF) ----------------------
 from flydog_sdr_gps_amd.ddc import RX_14, RX_DECIM_WIDE, RX_STD, RX_WIDE   # noqa: E402
 
