@@ -138,6 +138,7 @@ class CwDecoder:
         check(self.lib.kg_cw_push(self.h, ptr(conns), int(nent), ptr(nblk), ptr(s16), int(max(nb, 1) * BLK), ptr(now_sec), ptr(evs), int(me), ptr(counts)),
               "kg_cw_push")
         counts = counts.reshape(nent, 4)
+        self.last_counts = counts                # per entry: events, Goertzel blocks completed, overflow, 0
         assert not counts[:, 2].any(), "the event capacity was exceeded"
         return [evs[i, :counts[i, 0]].copy() for i in range(nent)]
 

@@ -292,9 +292,61 @@ class Recorder:
         return {"nev": self.nev, "evs": np.concatenate(self.evs) if self.evs else np.zeros(0, ev_dtype), "info": info}
 
 
+def _items(lines):
+    out, seen = [], 0
+    for l in lines:
+        if l[0] == "B":
+            out.append(("blk", int(l.split()[1]), seen))
+            seen += 1
+        else:
+            out.append(("cmd", l))
+    return out
+
+
+def run_side_by_side(q, scripts, samples, rng, most=24):
+    """scripts[c] on connection c of q (a CwDecoder), in lockstep: every round each script takes its commands up to its next block,
+    then ONE push feeds every connection with blocks left, 1 to `most` consecutive blocks each (drawn from rng, a numpy Generator) under
+    its own now_sec, listed out of connection order.  Nothing of the schedule depends on what the device answers: with q None only the
+    schedule is walked.  -> (per script the keys of parse() -- None without q --, pushes, pushes that carried more than one connection)"""
+    items = [_items(s) for s in scripts]
+    at, now = [0] * len(items), [0] * len(items)
+    rec = [Recorder(nblocks(s)) for s in scripts]
+    shared = calls = 0
+    while any(a < len(it) for a, it in zip(at, items)):
+        for c, it in enumerate(items):
+            while at[c] < len(it) and it[at[c]][0] == "cmd":
+                if q is not None:
+                    now[c] = apply_command(q, c, it[at[c]][1], now[c])
+                at[c] += 1
+        take = {}
+        for c, it in enumerate(items):
+            n = 0
+            lim = int(rng.integers(1, most + 1))
+            while n < lim and at[c] + n < len(it) and it[at[c] + n][0] == "blk":
+                n += 1
+            if n:
+                take[c] = it[at[c]:at[c] + n]
+        if not take:
+            break
+        conns = sorted(take, key=lambda c: -c)
+        if q is not None:
+            x = np.zeros((len(conns), max(len(v) for v in take.values()), BLK), np.int16)
+            for e, c in enumerate(conns):
+                for b, (_, off, _) in enumerate(take[c]):
+                    x[e, b] = samples[off:off + BLK]
+            evs = q.push(conns, x, [now[c] for c in conns], nblk=[len(take[c]) for c in conns])
+        for e, c in enumerate(conns):
+            if q is not None:
+                rec[c].add([b for _, _, b in take[c]], evs[e])
+            at[c] += len(take[c])
+        shared += len(conns) > 1
+        calls += 1
+    return [rec[c].result(q.state(c)) if q is not None else None for c in range(len(scripts))], calls, shared
+
+
 def run_script_dev(q, lines, samples, conn=0, cuts=lambda: 64):
-    """Runs a script on connection conn of q (a CwDecoder): every push one call.  -> the keys of parse(), and "calls"."""
-    rec, calls, now = Recorder(nblocks(lines)), 0, 0
+    """Runs a script on connection conn of q (a CwDecoder): every push one call.  -> the keys of parse(), "calls" and "gblocks"."""
+    rec, calls, now, gblocks = Recorder(nblocks(lines)), 0, 0, []
     for st in script_steps(lines, cuts):
         if st[0] == "cmd":
             now = apply_command(q, conn, st[1], now)
@@ -303,7 +355,8 @@ def run_script_dev(q, lines, samples, conn=0, cuts=lambda: 64):
         x = np.stack([samples[o:o + BLK] for o in offs])[None]
         evs = q.push([conn], x, [now])
         rec.add(blocks, evs[0])
+        gblocks.append((len(offs), int(q.last_counts[0, 1])))
         calls += 1
     out = rec.result(q.state(conn))
-    out["calls"] = calls
+    out["calls"], out["gblocks"] = calls, gblocks                          # per push: its sound blocks, the Goertzel blocks the device counted
     return out

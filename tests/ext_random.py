@@ -1,24 +1,29 @@
-"""Seeded random command scripts for the three extension modules kg_iqd, kg_lorc and kg_fftext (tests/test_{iqd,lorc,fftext}_{cpu,gpu}.py,
-tools/make_ref_{iqd,lorc,fftext}_golden.py --random): the hand-written scripts of the three *_common.py pin one case each; these draw
-the combinations nobody wrote down -- a command of one kind behind one of another in mid-lap, points changed while both instances
-alternate, a GRI behind a stop / start, a function change behind a rate change behind a clear.
+"""Seeded random command scripts for the five extension modules kg_iqd, kg_lorc, kg_fftext, kg_fax and kg_cw
+(tests/test_{iqd,lorc,fftext,fax,cw}_{cpu,gpu}.py, tools/make_ref_{iqd,lorc,fftext,fax,cw}_golden.py --random): the hand-written scripts
+of the five *_common.py pin one case each; these draw the combinations nobody wrote down -- a command of one kind behind one of another
+in mid-lap, points changed while both instances alternate, a GRI behind a stop / start, a function change behind a rate change behind
+a clear, a fax line of 1024 or 10 samples at half the nominal rate, 300 sound blocks of Morse in one push.
 
 A generator is a pure function of an integer seed and answers a script in its module's own script language over the module's own
 seeded pool; it draws from the domain on which the reference harness and the host model take every script (exit status 0).  What the
-reference wrote for seeds 0 .. NSEED-1 is kept in tests/golden/{iqd,lorc,fftext}_rand_ref.npz: integers in full, bytes by digest
-(RECORD / pack / unpack).  FEATURES walks a script beside its record and names what it reached: the conditions of
-test_random_fixture_meets_its_conditions.  tests/ext_random_dev.py runs the scripts on the device."""
+reference wrote for seeds 0 .. NSEED-1 is kept in tests/golden/{iqd,lorc,fftext,fax,cw}_rand_ref.npz: integers in full, bytes by
+digest (RECORD / pack / unpack).  FEATURES walks a script beside its record and names what it reached: the conditions of
+test_random_fixture_meets_its_conditions.  fax and cw keep, behind the 40 seeds, the records of a short fixed list of named shape
+scripts (SHAPES): the kernel-shape edges held whatever the seeds draw; they count towards no condition.  tests/ext_random_dev.py runs
+the scripts on the device."""
 import os
 import shutil
 
 import numpy as np
 
+from . import cw_common as cwc
+from . import fax_common as fxc
 from . import fftext_common as fc
 from . import iqd_common as ic
 from . import lorc_common as lc
 
 NSEED = 40
-BASE = {"iqd": 0x49510400, "lorc": 0x4C4F0400, "fftext": 0x46580000}      # the first bases whose 40 seeds reach every condition (check_conditions)
+BASE = {"iqd": 0x49510400, "lorc": 0x4C4F0400, "fftext": 0x46580000, "fax": 0x46410700, "cw": 0x43570000}      # the first bases whose 40 seeds reach every condition (check_conditions)
 PARTITION = 0x50415254                           # added to the base for the generator of a script's partition into calls
 NS = (1, 7, 170, 511, 512)
 
@@ -175,8 +180,341 @@ def fftext_script(seed):
     return lines
 
 
-SCRIPT = {"iqd": iqd_script, "lorc": lorc_script, "fftext": fftext_script}
-COMMON = {"iqd": ic, "lorc": lc, "fftext": fc}
+# ---- kg_fax.  C lpm imagewidth carrier deviation bandwidth headers phasing autostop debug nom srate | R srate | H shift | T | B off
+MOST_BLOCKS = 400                                # a fax or cw script has no more blocks
+LONG = (257, 400)                                # one script in five holds a stretch of so many blocks with no other line between them
+FAX_LINES = 255                                  # the reference harness ends a run whose configuration outgrows 256 lines (exit 9)
+FAX_WIDTHS = (1, 7, 255, 256, 257, 333, 640, 1024, 1809, 1900)         # and spl
+FAX_TUNINGS = ((1900, 400), (1800, 450), (1900, -400))
+FAX_SPLS = (10, 16, 17, 100, 255, 256, 257, 1023, 1024, 1025, 1030, 1039, 1040, 2048, 2049, 2999, 3000, 3001, 4096, 20250, 24575, 24576)
+FAX_SHIFTS = ("0.0", "0.0245", "0.37", "0.9", "1.0")
+FAX_NATIVE = tuple(s for s in fxc.SEGMENTS if s[0] != "zeros")
+FAX_DENSE = ((1039, 257), (1039, 258), (1040, 257), (1040, 258), (2048, 400))     # (spl, blocks) at half the nominal rate: 200 lines or more, under 256
+FAX_NPOOL = fxc.POOL // fxc.BLK
+
+
+def fax_rates(nom):
+    """half the nominal rate exactly and just above, the nominal and just above, twice the nominal just below and exactly"""
+    return (nom / 2, nom / 2 * 1.002, float(nom), nom * 1.0001, 2 * nom * 0.998, 2.0 * nom)
+
+
+class _Fax:
+    """a fax script under way: its lines, the blocks it may still hold and the bound on the lines since the last C, computed from the
+    script alone -- a block gives at most 512 / ratio + 1 picks, under the least ratio a line since the C can have begun with"""
+
+    def __init__(self):
+        self.lines, self.left, self.on = [], MOST_BLOCKS, False
+        self.spl = self.nom = self.picks = 0
+        self.rmin = 1.0
+
+    def config(self, lpm, w, tuning, bw, hdr, ph, stop, dbg, nom, srate):
+        self.lines.append(fxc._C(lpm, w, tuning[0], tuning[1], bw, hdr, ph, stop, dbg, nom, srate))
+        self.spl, self.nom, self.rmin, self.picks, self.on = int(nom * 60.0 / lpm), nom, srate / nom, 0.0, True
+
+    def rate(self, srate):
+        self.lines.append("R %r" % float(srate))
+        self.rmin = min(self.rmin, srate / self.nom)
+
+    def room(self):
+        if not self.on:
+            return self.left
+        return max(0, min(self.left, int((FAX_LINES * self.spl - self.picks) // (fxc.BLK / self.rmin + 1))))
+
+    def blocks(self, first, n):
+        """n pool blocks from block `first` on, around the pool's end; as many of them as fit -> how many"""
+        n = min(n, self.room())
+        self.lines += ["B %d" % (fxc.BLK * ((first + k) % FAX_NPOOL)) for k in range(n)]
+        self.left -= n
+        if self.on:
+            self.picks += n * (fxc.BLK / self.rmin + 1)
+        return n
+
+    def stop(self, rng):
+        """T with blocks behind it"""
+        self.lines.append("T")
+        self.on = False
+        self.blocks(int(rng.integers(FAX_NPOOL)), int(rng.integers(1, 5)))
+
+
+def _fax_flags(rng):
+    """headers, phasing, autostop, debug"""
+    return int(rng.random() < 0.7), int(rng.random() < 0.6), int(rng.random() < 0.6), int(rng.random() < 0.2)
+
+
+def _fax_native(g, rng, seg, story):
+    """a pool segment at its own lpm and nominal rate, the sample rate within 2 Hz of it -> what gives the next stretch's first block"""
+    name, fs, lpm, _, plan = seg
+    spl = fs * 60 // lpm
+    hdr, ph, stop, dbg = (int(rng.random() < 0.5), 1, int(rng.integers(2)), 0) if story else _fax_flags(rng)
+    g.config(lpm, _pick(rng, FAX_WIDTHS + (spl,)), _pick(rng, FAX_TUNINGS[:2] if story else FAX_TUNINGS), int(rng.integers(3)), hdr, ph, stop, dbg, fs,
+             round(fs + float(rng.uniform(-2, 2)), 2))
+    starts = np.cumsum([0] + [n for _, n in plan])[:-1] * spl // fxc.BLK          # the first block of every part of the segment
+    kinds = [k for k, _ in plan]
+    # under autostop, two times in five: the stop tone first, then the start tone behind it
+    order = [starts[kinds.index("stop")], starts[kinds.index("start")]] if stop and "stop" in kinds and rng.random() < 0.4 else []
+
+    def first():
+        at = order.pop(0) if order else _pick(rng, starts)
+        return fxc.AT[name] // fxc.BLK + int(np.clip(at + rng.integers(-3, 4), 0, fxc.NBLK[name] - 1))
+    return first
+
+
+def _fax_foreign(g, rng, spl=None, srate=None):
+    """60 lpm at a nominal rate equal to the wanted line length, over any blocks of the pool"""
+    spl = _pick(rng, FAX_SPLS) if spl is None else spl
+    g.config(60, min(_pick(rng, FAX_WIDTHS + (spl,)), spl), _pick(rng, FAX_TUNINGS), int(rng.integers(3)), *_fax_flags(rng), spl,
+             _pick(rng, fax_rates(spl)) if srate is None else srate)
+    return lambda: int(rng.integers(FAX_NPOOL))
+
+
+def fax_script(seed):
+    """Two to five configurations, native or foreign, each with one to four stretches of blocks (60 to 140 of a native segment or of a line above 20000 samples, 3 to 80 otherwise) and
+    between two stretches sometimes a command: R (either end of the accepted range, or anywhere in it), H, a second C in mid-line, or T with blocks behind it and a C.  One
+    script in four is the 240 lpm segment from its start tone through its phasing lines, 372 blocks or more: phased, or -- with a shift in
+    the middle of the phasing lines -- rejected.  One in five holds a stretch of 257 to 400 blocks with no other line between them; half
+    of the foreign ones are FAX_DENSE, where the stretch completes 200 lines or more and stays under the 256."""
+    rng = _rng("fax", seed)
+    g = _Fax()
+    if rng.random() < 0.25:
+        first = _fax_native(g, rng, fxc.SEGMENTS[2], True)
+        at, n = fxc.AT["a240"] // fxc.BLK + int(rng.integers(10, 30)), int(rng.integers(372, 391))
+        if rng.random() < 0.5:
+            k = int(rng.integers(200, 300))                                # the phasing lines are blocks 146 to 404 of the segment
+            g.blocks(at, k)
+            g.lines.append("H %s" % _pick(rng, FAX_SHIFTS[2:4]))
+            g.blocks(at + k, n - k)
+        else:
+            g.blocks(at, n)
+        g.blocks(first(), int(rng.integers(1, 11)))
+        return g.lines
+    nlong = int(rng.integers(LONG[0], LONG[1] + 1)) if rng.random() < 0.2 else 0
+    nconf = int(rng.integers(2, 6))
+    long_at = int(rng.integers(nconf)) if nlong else -1
+    g.left -= nlong                                                        # kept for the long stretch
+    for c in range(nconf):
+        if c and rng.random() < 0.3:
+            g.stop(rng)
+        if c == long_at:
+            g.left += nlong
+            if rng.random() < 0.4:
+                seg = _pick(rng, [s for s in FAX_NATIVE if fxc.NBLK[s[0]] >= nlong])
+                _fax_native(g, rng, seg, False)
+                g.blocks(fxc.AT[seg[0]] // fxc.BLK + int(rng.integers(fxc.NBLK[seg[0]] - nlong + 1)), nlong)
+            elif rng.random() < 0.5:
+                spl, n = _pick(rng, [d for d in FAX_DENSE if d[1] <= g.left] or FAX_DENSE[:1])
+                first = _fax_foreign(g, rng, spl, fax_rates(spl)[0])
+                g.blocks(first(), n)
+            else:
+                fits = [(s, r) for s in FAX_SPLS for r in fax_rates(s) if nlong * (fxc.BLK / (r / s) + 1) <= FAX_LINES * s]
+                first = _fax_foreign(g, rng, *_pick(rng, fits))
+                g.blocks(first(), nlong)
+            continue
+        native = rng.random() < 0.35
+        seg = _pick(rng, FAX_NATIVE)
+        again = (lambda: _fax_native(g, rng, seg, False)) if native else (lambda: _fax_foreign(g, rng))
+        first = again()
+        for s in range(int(rng.integers(1, 5))):
+            if s:
+                k = int(rng.integers(6))
+                if k == 0:
+                    g.rate(_pick(rng, (g.nom / 2, 2.0 * g.nom, round(float(rng.uniform(g.nom / 2, 2 * g.nom)), 3))))
+                elif k == 1:
+                    g.lines.append("H %s" % _pick(rng, FAX_SHIFTS))
+                elif k == 2:
+                    first = again()
+                elif k == 3:
+                    g.stop(rng)
+                    first = again()
+            g.blocks(first(), int(rng.integers(60, 141)) if native or g.spl >= 20000 else int(rng.integers(3, 81)))
+    return g.lines
+
+
+def fax_shapes():
+    """the kernel-shape edges of csrc/kg_fax.hip, one script each: the pick walk's bound (1024 picks at half the rate), the demodulator's
+    chunk of 1024 (a line of exactly one, two and 24 chunks, a last chunk shorter than the 16 carried products, a line shorter than
+    them, than the workgroup), the detector's cap of 3000 from either side, the phasing search at its smallest stride (w == spl) and at
+    one candidate (w == 1).  60 lpm at a nominal rate of 10 or 100 calls every line with a mean brightness above 5 a start line (300 Hz
+    is a whole number of turns a sample): blocks of signal arm the phasing and blocks of silence, image lines, run it."""
+    C, B, Z = fxc._C, fxc._B, fxc._B("zeros", 0, 18)
+    s = {
+        "ratio_half": [C(120, srate=6000.0)] + B("a120", 40, 60),
+        "ratio_just_above_half": [C(120, srate=6000.0 * 1.002)] + B("a120", 40, 60),
+        "ratio_twice": [C(120, srate=24000.0)] + B("a120", 40, 100),
+        "spl_10": [C(60, w=7, nom=10)] + B("a120", 50, 1) + Z[:3],
+        "spl_100": [C(60, w=100, nom=100, bw=2)] + B("a120", 50, 20) + Z[:10],
+        "spl_255_w255": [C(60, w=255, nom=255)] + B("a240", 20, 50),
+        "spl_1024_w1024": [C(60, w=1024, nom=1024, bw=0)] + B("a120", 40, 60),
+        "spl_1030": [C(60, w=640, nom=1030)] + B("a120", 40, 60),
+        "spl_4096": [C(60, w=1809, nom=4096, dev=-400)] + B("a60", 20, 80),
+        "spl_24576": [C(60, w=1024, nom=24576)] + B("a60_20250", 30, 100),
+        "spl_2999": [C(60, w=333, nom=2999)] + B("a240", 10, 60),
+        "spl_3001": [C(60, w=333, nom=3001)] + B("a240", 10, 60),
+        "w_equals_spl": [C(240, w=3000, stop=0)] + B("a240", 17, 60) + [C(60, w=100, nom=100)] + B("a120", 50, 2) + Z,
+        "w_1": [C(120, w=1)] + B("a120", 40, 40) + [C(60, w=1, nom=100)] + B("a120", 50, 2) + Z,
+        "rate_walk": [C(120, w=640)] + B("a120", 40, 20) + ["R 6000.0"] + B("a120", 60, 25) + ["R 24000.0"] + B("a120", 85, 30) + ["H 1.0"] + B("a120", 115, 25),
+    }
+    return s
+
+
+# ---- kg_cw.  S training_interval nom srate | W wpm training_interval | P pboff | C wsc | A on | H threshold | T | N now | B off
+CW_INTERVALS = (1, 2, 30, 40, 100, 255)
+CW_NOMS = (12000, 12000, 12000, 12000, 12000, 12000, 20250, 20250, 20250, 88, 1000)
+CW_RATIOS = (0.5, 1.0, 1.0, 1.0 + 1e-4, 1.0 - 1e-4, 2.0)
+CW_WPMS = (0, 5, 25, 30, 60)
+CW_THRESHOLDS = (-5, 0, 3000, 15000, 20000)
+CW_PER_SEC = (6, 23, 40)
+CW_BIN = {12000: 6, 20250: 4}                    # the pool's tone (cw_common.TONE)
+
+
+def cw_pboff_a(srate, pboff):
+    """g->a of kg_cw.h (pboff_a): the command is taken where it is within 0 .. 44"""
+    return int(0.5 + float(np.float32(np.float32(pboff) * np.float32(88) / np.float32(srate))))
+
+
+def cw_pboffs(srate, tone_bin):
+    """0, the offset of the pool's tone bin, an offset of an empty bin, the largest accepted"""
+    most = int(44.5 * srate / 88) + 2
+    while cw_pboff_a(srate, most) > 44:
+        most -= 1
+    out = (0, int(round(tone_bin * srate / 88)), int(round(11 * srate / 88)), most)
+    assert all(0 <= cw_pboff_a(srate, p) <= 44 for p in out) and cw_pboff_a(srate, out[1]) == tone_bin and cw_pboff_a(srate, most + 1) > 44, (srate, out)
+    return out
+
+
+class _Cw:
+    """a cw script under way: its lines, the blocks it may still hold, the clock of the N lines and the rate in force"""
+
+    def __init__(self, now):
+        cwc.pool()
+        self.lines, self.left, self.now, self.srate, self.bin = [], MOST_BLOCKS, now, 0.0, 6
+
+    def start(self, ti, nom, ratio, seg):
+        self.srate, self.bin = nom * ratio, CW_BIN[cwc.FS[seg]]
+        self.lines.append("S %d %d %r" % (ti, nom, float(self.srate)))
+
+    def tone(self):
+        self.lines.append("P %d" % cw_pboffs(self.srate, self.bin)[1])
+
+    def clock(self, step=1):
+        self.now = (self.now + step) % (1 << 32)
+        self.lines.append("N %d" % self.now)
+
+    def blocks(self, seg, first, n, per_sec):
+        """n blocks of the segment (around its end), the clock moving every per_sec blocks; per_sec 0: no line between them"""
+        n = min(n, self.left)
+        for k in range(n):
+            if per_sec and k % per_sec == 0:
+                self.clock()
+            self.lines.append("B %d" % (cwc.AT[seg] + cwc.BLK * ((first + k) % cwc.NBLK[seg])))
+        self.left -= n
+
+
+def _cw_command(g, rng):
+    k = int(rng.integers(8))
+    if k == 0:
+        return ["P %d" % _pick(rng, cw_pboffs(g.srate, g.bin))]
+    if k == 1:
+        return ["C %d" % int(rng.integers(2))]
+    if k == 2:
+        return ["A %d" % int(rng.integers(2))]
+    if k == 3:
+        return ["H %d" % _pick(rng, CW_THRESHOLDS)]
+    if k == 4:                                   # CwDecode_Init: samples wait for the next pboff
+        return ["W %d %d" % (_pick(rng, CW_WPMS), _pick(rng, CW_INTERVALS))] + (["P %d" % cw_pboffs(g.srate, g.bin)[1], "H 20000"] if rng.random() < 0.8 else [])
+    if k == 5:
+        g.clock(-int(rng.integers(1, 50)))       # the clock jumps backwards
+        return []
+    if k == 6:
+        g.clock(int(rng.integers(2, 30)))
+        return []
+    return []
+
+
+def cw_script(seed):
+    """Half the scripts are a listening: one segment of the pool from its first block at its own rate (within 1e-4), the tone's bin, a
+    training interval of 30 or 40, a fixed or the automatic threshold, tracked or (at 30 wpm) fixed speed -- so that the text, its
+    word spaces, prosigns, [err], the retraining and the error time-out are reached -- with a command or two thrown in late.  The other
+    half is commands at large: any interval, nominal rate (88 and 1000 too) and ratio, S in mid-stream, T then blocks then S, every
+    command between stretches of 5 to 120 blocks.  The clock begins anywhere, a few seconds short of 2^32 in one script in six, moves
+    every 6, 23 or 40 blocks and sometimes jumps backwards.  One script in five holds a stretch of 257 to 400 blocks with no N or other
+    line between them."""
+    rng = _rng("cw", seed)
+    g = _Cw(int(_pick(rng, (100, 100, 5, 0x7ffffff0, 0xfffffff4, 0xfffffffa))))
+    nlong = int(rng.integers(LONG[0], LONG[1] + 1)) if rng.random() < 0.2 else 0
+    segs = sorted(cwc.NBLK)
+    if rng.random() < 0.5:
+        seg = _pick(rng, segs)
+        g.start(_pick(rng, (30, 40)), cwc.FS[seg], _pick(rng, (1.0, 1.0, 1.0 + 1e-4, 1.0 - 1e-4)), seg)
+        if rng.random() < 0.25:
+            g.lines.append("W %d 40" % _pick(rng, (30, 25)))
+        g.tone()
+        g.lines.append("A 1" if rng.random() < 0.25 else "H %d" % _pick(rng, (15000, 20000)))
+        per_sec = _pick(rng, CW_PER_SEC)
+        n = min(cwc.NBLK[seg], MOST_BLOCKS - 10)
+        if nlong:
+            g.clock()
+            g.blocks(seg, 0, nlong, 0)
+            g.blocks(seg, nlong, max(n - nlong, 0), per_sec)
+        else:
+            cut = int(rng.integers(150, n))
+            g.blocks(seg, 0, cut, per_sec)
+            g.lines += _cw_command(g, rng) if rng.random() < 0.5 else []
+            g.blocks(seg, cut, n - cut, per_sec)
+        return g.lines
+    nstretch = int(rng.integers(3, 9))
+    long_at = int(rng.integers(nstretch)) if nlong else -1
+    g.left -= nlong
+    seg = _pick(rng, segs)
+    for s in range(nstretch):
+        if s == 0 or rng.random() < 0.3:
+            if s and rng.random() < 0.4:
+                g.lines.append("T")
+                g.blocks(seg, int(rng.integers(cwc.NBLK[seg])), int(rng.integers(1, 5)), 0)
+            seg = _pick(rng, segs)
+            nom = _pick(rng, CW_NOMS)
+            g.start(_pick(rng, CW_INTERVALS), nom, _pick(rng, CW_RATIOS), seg)
+            if rng.random() < 0.85:
+                g.tone()
+            if rng.random() < 0.7:
+                g.lines.append("H %d" % _pick(rng, CW_THRESHOLDS))
+        else:
+            for _ in range(int(rng.integers(1, 4))):
+                g.lines += _cw_command(g, rng)
+        first = 0 if rng.random() < 0.4 else int(rng.integers(cwc.NBLK[seg]))
+        if s == long_at:
+            g.left += nlong
+            g.blocks(seg, first, nlong, 0)
+        else:
+            g.blocks(seg, first, int(rng.integers(5, 121)), _pick(rng, CW_PER_SEC))
+    return g.lines
+
+
+def cw_shapes():
+    """the kernel-shape edges of csrc/kg_cw.hip, one script each: a push of 256 sound blocks (1489 or 1490 Goertzel blocks: six turns
+    of phase A's loop, the whole of its magnitudes) and then one of 1; the ends of what the commands accept"""
+    B = cwc._B
+    head = lambda ti=40, nom=12000, srate=None, p=cwc.PBOFF, h=20000: [cwc._S(ti, nom, srate), "P %d" % p, "H %d" % h]
+    plain = lambda seg, n: ["B %d" % (cwc.AT[seg] + cwc.BLK * k) for k in range(n)]
+    cwc.pool()
+    return {
+        "one_push_256": head() + ["N 100"] + plain("clean", 256) + ["N 111"] + plain("clean", 257)[256:],
+        "ti_1": head(ti=1) + B("clean", 0, 100),
+        "ti_255": head(ti=255) + B("jitter", 0, 100),
+        "threshold_0": head(h=0) + B("clean", 0, 40) + ["H 20000"] + B("clean", 40, 40),
+        "ratio_half": head(srate=6000.0, p=409) + B("clean", 0, 100),
+        "ratio_twice": head(srate=24000.0, p=1636) + B("clean", 0, 100),
+        "nom_88": head(nom=88, p=6) + B("clean", 0, 100),
+        "clock_backwards": head() + B("errtime", 0, 50, now=4294967280, per_sec=6) + ["N 3"] + B("errtime", 50, 30, now=1000, per_sec=6) + B("errtime", 80, 20, now=500, per_sec=6),
+    }
+
+
+SCRIPT = {"iqd": iqd_script, "lorc": lorc_script, "fftext": fftext_script, "fax": fax_script, "cw": cw_script}
+COMMON = {"iqd": ic, "lorc": lc, "fftext": fc, "fax": fxc, "cw": cwc}
+SHAPES = {"fax": fax_shapes, "cw": cw_shapes}
+
+
+def shape_names(mod):
+    return list(SHAPES[mod]())
 
 
 def script_digest(lines):
@@ -214,12 +552,52 @@ def fftext_record(lines, got):
             "pwr_sha": _sha(np.ascontiguousarray(got["pwr"], np.float32).tobytes())}
 
 
-RECORD = {"iqd": iqd_record, "lorc": lorc_record, "fftext": fftext_record}
+def _one_nan(rec):
+    """a copy of a record with every NaN as one bit pattern (the device's is the positive quiet one, x86's the negative) and `pad` zeroed"""
+    out = np.array(rec).reshape(1).copy()
+    for name in out.dtype.names:
+        if out.dtype[name].base.kind == "f":
+            v = out[name]
+            v[np.isnan(v)] = np.nan
+        elif name == "pad":
+            out[name] = 0
+    return out
 
 
-def pack(records):
-    """per-seed records -> the arrays of the file: every field end to end over the seeds, and how many elements each seed has"""
-    out = {"nseed": np.array([len(records)], np.int32)}
+def fax_record(lines, got):
+    """in full what places a failure: the lines of every block, and per line its type, flags and the pick at which it completed"""
+    r = got["recs"]
+    rest = r.copy()
+    for f in ("blk", "off", "type", "flags"):
+        rest[f] = 0
+    return {"script_sha": script_digest(lines), "nlines": got["nlines"].astype(np.int16), "type": r["type"].astype(np.uint8), "flags": r["flags"].astype(np.uint8),
+            "off": r["off"].astype(np.int16), "recs_sha": _sha(rest.tobytes()), "rows_sha": _sha(fxc.all_bytes(got).tobytes()),
+            "info_sha": _sha(_one_nan(got["info"]).tobytes()), "samples_sha": _sha(np.ascontiguousarray(got["samples"], np.int16).tobytes()),
+            "demod_sha": _sha(np.ascontiguousarray(got["demod"], np.uint8).tobytes()), "prev_sha": _sha(np.ascontiguousarray(got["prev"], np.uint8).tobytes()),
+            "out_sha": _sha(np.ascontiguousarray(got["out"], np.uint8).tobytes())}
+
+
+def cw_record(lines, got):
+    """in full what places a failure: the events of every block and the text; of the other kinds their number and, for the walk of
+    cw_features, every TRAIN event below 1 that does not repeat the TRAIN before it, as (block, value)"""
+    e = got["evs"]
+    tr = e[e["kind"] == cwc.TRAIN]
+    new = np.ones(tr.size, bool)
+    new[1:] = tr["a"][1:] != tr["a"][:-1]
+    marks = tr[new & (tr["a"] <= 0)]
+    return {"script_sha": script_digest(lines), "nev": got["nev"].astype(np.int16), "text": e[e["kind"] == cwc.CHARS]["a"].astype(np.uint8),
+            "kinds": np.array([(e["kind"] == k).sum() for k in range(4)], np.int32),
+            "marks": np.stack([marks["blk"], marks["a"]], axis=1).astype(np.int32).reshape(-1),
+            "evs_sha": _sha(np.ascontiguousarray(e).tobytes()), "info_sha": _sha(np.array(got["info"]).tobytes())}
+
+
+RECORD = {"iqd": iqd_record, "lorc": lorc_record, "fftext": fftext_record, "fax": fax_record, "cw": cw_record}
+
+
+def pack(records, nseed=None):
+    """per-seed records -> the arrays of the file: every field end to end over the seeds, and how many elements each seed has; where
+    the records of shape scripts stand behind those of the nseed seeds, "nseed" counts the seeds alone"""
+    out = {"nseed": np.array([len(records) if nseed is None else nseed], np.int32)}
     for key in records[0]:
         parts = [np.ascontiguousarray(r[key]).reshape(-1) for r in records]
         assert len({p.dtype for p in parts}) == 1, key
@@ -512,8 +890,185 @@ FFTEXT_CONDITIONS = (["rows of function %d" % k for k in (fc.WF, fc.SPEC, fc.INT
                         "bin 100 or above filled", "integ walk wrapped",
                         "function change without C", "rate change taken up at a reset", "S -1 with blocks behind it"])
 
-FEATURES = {"iqd": iqd_features, "lorc": lorc_features, "fftext": fftext_features}
-CONDITIONS = {"iqd": IQD_CONDITIONS, "lorc": LORC_CONDITIONS, "fftext": FFTEXT_CONDITIONS}
+def fax_features(lines, rec):
+    """the commands of kg_fax.h and the head of ProcessSamples (block_head) walked beside the reference's record of the script.  The
+    ratio a line is demodulated with is that of the block it completes in (line_begin).  `skip` is a bound, from the script and the
+    flags alone, on the samples still to come off the front of the next blocks (a shift, the phasing result; a restart keeps it): a
+    block with nothing to skip that completes no line leaves the line begun, which is what "a C in mid-line" is told by"""
+    f = set()
+    nl, typ, flg = rec["nlines"], rec["type"], rec["flags"]
+    on = mid = after_stop = False
+    spl = w = bw = dev = dbg = skip = stretch = stretch_lines = 0
+    nom = srate = shift = 0.0
+    r_end, h1 = None, False
+    blk = line = 0
+
+    def close_stretch():
+        if stretch >= LONG[0]:
+            f.add("a stretch of 257 blocks or more")
+            if stretch_lines >= 200:
+                f.add("a stretch that completes 200 lines or more")
+
+    for l in lines:
+        a = l.split()
+        if a[0] != "B":
+            close_stretch()
+            stretch = stretch_lines = 0
+        if a[0] == "C":
+            if mid:
+                f.add("a C in mid-line")
+            lpm, w, dev, bw, dbg, nom, srate = int(a[1]), int(a[2]), int(a[4]), int(a[5]), int(a[9]), float(a[10]), float(a[11])
+            spl, on, mid, r_end, h1 = int(nom * 60.0 / lpm), True, False, None, False
+        elif a[0] == "R":
+            srate = float(a[1])
+            r_end = "half" if srate == nom / 2 else "twice" if srate == nom * 2 else None
+        elif a[0] == "H":
+            shift = float(a[1])
+        elif a[0] == "T":
+            on, shift, after_stop = False, 0.0, True
+        elif a[0] == "B":
+            n = int(nl[blk])
+            blk += 1
+            if not on:
+                assert n == 0
+                if after_stop:
+                    f.add("T with blocks behind it")
+                continue
+            if shift:
+                if shift == 1.0 and spl > fxc.BLK:
+                    h1 = True
+                skip, shift = spl, 0.0
+            if h1:
+                f.add("H 1.0: a skip larger than a block")
+                h1 = False
+            mid = (skip < fxc.BLK and n == 0) or (mid and skip >= fxc.BLK)
+            skip = max(skip - fxc.BLK, 0)
+            stretch, stretch_lines = stretch + 1, stretch_lines + n
+            if n >= 2:
+                f.add("a block that completes 2 lines or more")
+            for k in range(line, line + n):
+                f.add("line type %d" % typ[k])
+                f |= {"flag %d" % b for b in (1, 2, 4, 8, 16, 32, 64) if flg[k] & b}
+                if flg[k] & fxc.F_PHASED:
+                    skip = spl                                             # phased is sent with a non-zero skip, and only then
+                if dbg and flg[k] & fxc.F_ROW_SENT:
+                    f.add("debug rows")
+            line += n
+            if n:
+                mid = False
+                ratio = srate / nom
+                f |= {"lines at ratio <= 0.501"} if ratio <= 0.501 else {"lines at ratio >= 1.996"} if ratio >= 1.996 else set()
+                if r_end:
+                    f.add("R to %s the nominal rate with lines behind it" % r_end)
+                f.add("bandwidth %d" % bw)
+                if dev < 0:
+                    f.add("negative deviation")
+                f |= {"spl a multiple of 1024"} if spl % 1024 == 0 else set()
+                f |= {"spl in 1025..1039"} if 1025 <= spl <= 1039 else set()
+                f |= {"spl below 256"} if spl < 256 else set()
+                f |= {"spl below 17"} if spl < 17 else set()
+                f |= {"spl %d" % spl} if spl in (2999, 3000, 3001, 24576) else set()
+                f |= {"w == spl"} if w == spl else set()
+                f |= {"w == 1"} if w == 1 else set()
+                f |= {"w in 255..257"} if w in (255, 256, 257) else set()
+    close_stretch()
+    assert blk == nl.size and line == typ.size
+    return f
+
+
+FAX_CONDITIONS = (["lines at ratio <= 0.501", "lines at ratio >= 1.996", "spl a multiple of 1024", "spl in 1025..1039", "spl below 256", "spl below 17", "spl 2999", "spl 3000",
+                   "spl 3001", "spl 24576", "w == spl", "w == 1", "w in 255..257", "bandwidth 0", "bandwidth 1", "bandwidth 2", "negative deviation", "debug rows"]
+                  + ["line type %d" % t for t in range(3)] + ["flag %d" % b for b in (1, 2, 4, 8, 16, 32, 64)]      # 8: phased, with a non-zero skip; 32: rejected
+                  + ["R to half the nominal rate with lines behind it", "R to twice the nominal rate with lines behind it", "H 1.0: a skip larger than a block",
+                     "a C in mid-line", "T with blocks behind it", "a block that completes 2 lines or more", "a stretch of 257 blocks or more",
+                     "a stretch that completes 200 lines or more"])
+
+
+def cw_features(lines, rec):
+    """the commands of kg_cw.h walked beside the reference's record of the script.  A TRAIN of -4 is the fourth error, which restarts
+    the training; a TRAIN of 0 behind one of -1 .. -3 with no S or W between their blocks is the error time-out's (cw_train sends its
+    own only while the decoder is not initialised, which an error count above 0 rules out)"""
+    f = set()
+    nev, text, kinds, marks = rec["nev"], rec["text"], rec["kinds"], rec["marks"].reshape(-1, 2)
+    f |= {"event kind %d" % k for k in range(4) if kinds[k]}
+    f |= {"a word space"} if (text == ord(" ")).any() else set()
+    f |= {"a prosign"} if (text < 12).any() else set()
+    f |= {"[err]"} if (text == 0xff).any() else set()
+    on = taking = auto_waits = after_stop = False
+    nom = ratio = 0.0
+    ti = wpm = fed = stretch = 0
+    threshold, now, back, wrapped = 0, None, False, False
+    inits, blk = [], 0                                                     # the blocks ahead of which an S or W came
+    for l in lines:
+        a = l.split()
+        if a[0] != "B":
+            if stretch >= LONG[0]:
+                f.add("a stretch of 257 blocks or more")
+            stretch = 0
+        if a[0] == "S":
+            if fed and on:
+                f.add("S in mid-stream")
+            if after_stop:
+                f.add("T then S")
+            ti, nom, ratio, wpm = int(a[1]), float(a[2]), float(a[3]) / float(a[2]), 0
+            on, taking, threshold, after_stop, fed, auto_waits = True, False, 0, False, 0, False
+            inits.append(blk)
+        elif a[0] == "W":
+            wpm, ti, taking, threshold, fed, auto_waits = int(a[1]), int(a[2]), False, 0, 0, False
+            inits.append(blk)
+        elif a[0] == "P":
+            if taking and (fxc.BLK * fed) % cwc.GBLK:
+                f.add("a P in mid Goertzel block")
+            taking = True
+        elif a[0] == "A":
+            auto_waits = int(a[1]) == 1
+        elif a[0] == "H":
+            threshold = int(a[1])
+        elif a[0] == "T":
+            on, after_stop = False, True
+        elif a[0] == "N":
+            v = int(a[1])
+            if now is not None and v < now:
+                wrapped, back = (True, back) if now >= (1 << 32) - 64 and v < 64 else (wrapped, True)
+            now = v
+        elif a[0] == "B":
+            n, blk = int(nev[blk]), blk + 1
+            if not (on and taking):
+                assert n == 0
+                continue
+            fed, stretch = fed + 1, stretch + 1
+            f.add("fixed speed" if wpm else "tracked speed")
+            f.add("nominal %d" % nom if nom in (12000, 20250) else "nominal 88 or 1000")
+            f |= {"ratio 0.5"} if ratio == 0.5 else {"ratio 2"} if ratio == 2 else set()
+            f |= {"training interval %d" % ti} if not wpm and ti in (1, 255) else set()
+            f |= {"threshold <= 0"} if threshold <= 0 else set()
+            f |= {"a sound block with 8 events or more"} if n >= 8 else set()
+            if auto_waits:
+                f.add("automatic threshold switched on with blocks behind it")
+                auto_waits = False
+            if back:
+                f.add("the clock going backwards")
+            if wrapped:
+                f.add("the clock crossing 2^32")
+            back = wrapped = False
+    if stretch >= LONG[0]:
+        f.add("a stretch of 257 blocks or more")
+    if (marks[:, 1] == -4).any():
+        f.add("a retraining")
+    for (b0, a0), (b1, a1) in zip(marks[:-1], marks[1:]):
+        if -3 <= a0 <= -1 and a1 == 0 and not any(b0 < i <= b1 for i in inits):
+            f.add("err_timeout taken")
+    return f
+
+
+CW_CONDITIONS = (["event kind %d" % k for k in range(4)]
+                 + ["a word space", "a prosign", "[err]", "a retraining", "fixed speed", "tracked speed", "automatic threshold switched on with blocks behind it",
+                    "a P in mid Goertzel block", "S in mid-stream", "T then S", "nominal 12000", "nominal 20250", "nominal 88 or 1000", "ratio 0.5", "ratio 2",
+                    "training interval 1", "training interval 255", "threshold <= 0", "a sound block with 8 events or more", "the clock going backwards",
+                    "the clock crossing 2^32", "err_timeout taken", "a stretch of 257 blocks or more"])
+
+FEATURES = {"iqd": iqd_features, "lorc": lorc_features, "fftext": fftext_features, "fax": fax_features, "cw": cw_features}
+CONDITIONS = {"iqd": IQD_CONDITIONS, "lorc": LORC_CONDITIONS, "fftext": FFTEXT_CONDITIONS, "fax": FAX_CONDITIONS, "cw": CW_CONDITIONS}
 
 
 def reached(mod, g):
@@ -527,7 +1082,7 @@ def reached(mod, g):
             if c in by:
                 by[c].append(seed)
         blocks += COMMON[mod].nblocks(lines)
-        rows += int(rec["sent"].sum()) if mod == "fftext" else int(rec["nrows"].sum())
+        rows += int(rec[{"fftext": "sent", "fax": "nlines", "cw": "nev"}.get(mod, "nrows")].sum())
     return by, rows, blocks
 
 
@@ -536,19 +1091,19 @@ def check_conditions(mod, g):
     missed = [c for c, seeds in by.items() if not seeds]
     assert not missed, (mod, "no seed reaches", missed)
     assert int(g["nseed"][0]) == NSEED
-    assert rows >= {"iqd": IQD_MIN_ROWS, "lorc": LORC_MIN_ROWS, "fftext": 1}[mod], (mod, rows)
+    assert rows >= {"iqd": IQD_MIN_ROWS, "lorc": LORC_MIN_ROWS}.get(mod, 1), (mod, rows)
     return by, rows, blocks
 
 
 def write_fixture(mod, exe, samples, tmp):
-    """tools/make_ref_*_golden.py --random: seeds 0 .. NSEED-1 through the reference harness `exe`; none may be refused"""
+    """tools/make_ref_*_golden.py --random: seeds 0 .. NSEED-1 and then the module's shape scripts, in the order of SHAPES, through
+    the reference harness `exe`; none may be refused"""
     C, recs = COMMON[mod], []
-    for seed in range(NSEED):
-        lines = SCRIPT[mod](seed)
+    for lines in [SCRIPT[mod](seed) for seed in range(NSEED)] + list(SHAPES[mod]().values() if mod in SHAPES else ()):
         got = C.run_script_exe(exe, lines, samples, tmp)                   # asserts exit status 0
         recs.append(RECORD[mod](lines, got))
     path = os.path.join(str(tmp), "rand.npz")
-    np.savez_compressed(path, **pack(recs))
+    np.savez_compressed(path, **pack(recs, NSEED))
     by, rows, blocks = reached(mod, np.load(path))
     for c, seeds in by.items():
         print("   %-36s %2d seeds" % (c, len(seeds)))

@@ -1,13 +1,16 @@
-"""Seeded random command scripts (tests/ext_random.py) on the device, for tests/test_{iqd,lorc,fftext}_gpu.py: the comparison of a device
-result with the host driver's in full, the random partition of one script into calls, and three scripts side by side on three
-channels of one object (iqd, fftext; lorc has its lock-step runner in tests/test_lorc_gpu.py), fed from host arrays call by call or
-from one device-resident buffer.  The schedule of the calls is decided ahead of the run, so what it reaches is checked without a GPU."""
+"""Seeded random command scripts (tests/ext_random.py) on the device, for tests/test_{iqd,lorc,fftext,fax,cw}_gpu.py: the comparison of
+a device result with the host driver's in full, the random partition of one script into calls, and three scripts side by side on
+three channels of one object (iqd, fftext: fed from host arrays call by call or from one device-resident buffer; lorc, fax and cw have
+their lock-step runners in tests/test_lorc_gpu.py, tests/fax_common.py and tests/cw_common.py).  The schedule of the calls is decided
+ahead of the run, so what it reaches is checked without a GPU."""
 import numpy as np
 
+from . import cw_common as cwc
+from . import fax_common as fxc
 from . import fftext_common as fc
 from . import iqd_common as ic
 from . import lorc_common as lc
-from .ext_random import BASE, NSEED, PARTITION, SCRIPT, _pick, _rng, same
+from .ext_random import BASE, COMMON, NSEED, PARTITION, SCRIPT, SHAPES, _pick, _rng, same
 
 # A device result (the keys of the module's parse(), from run_script_dev or from run_plan below) against the host driver's, in full: a
 # failure names the first differing row or element.
@@ -50,14 +53,42 @@ def fftext_same(dev, host, *what):
     same(np.asarray(dev["pwr"], np.float32), host["pwr"], *what + ("sums",))
 
 
-SAME = {"iqd": iqd_same, "lorc": lorc_same, "fftext": fftext_same}
+def fax_same(dev, host, *what):
+    same(dev["nlines"], host["nlines"], *what + ("lines per block",))
+    for f in fxc.rec_dtype.names:
+        if f != "blk":                                                     # the block of the push; nlines places a line in the script
+            same(dev["recs"][f], host["recs"][f], *what + ("line", f))
+    assert len(dev["rows"]) == len(host["rows"]), what + ("rows", len(dev["rows"]), len(host["rows"]))
+    for i, (a, b) in enumerate(zip(dev["rows"], host["rows"])):
+        same(a, b, *what + ("row %d" % i,))
+    for f in fxc.info_dtype.names:
+        if f != "pad":
+            a, b = np.asarray(dev["info"][f]), np.asarray(host["info"][f])
+            assert fxc._same_float(a, b) if a.dtype.kind == "f" else np.array_equal(a, b), what + ("end state", f, a, b)
+    for k in ("samples", "demod", "prev", "out"):
+        same(dev[k], host[k], *what + ("end state", k))
+
+
+def cw_same(dev, host, *what):
+    same(dev["nev"], host["nev"], *what + ("events per block",))
+    for f in cwc.ev_dtype.names:
+        same(dev["evs"][f], host["evs"][f], *what + ("event", f))
+    for f in cwc.info_dtype.names:
+        same(dev["info"][f], host["info"][f], *what + ("end state", f))
+
+
+SAME = {"iqd": iqd_same, "lorc": lorc_same, "fftext": fftext_same, "fax": fax_same, "cw": cw_same}
+PUSHES = (1, 2, 7, 64, 256)                      # blocks a push of a fax or cw partition: 256 is the most kg_fax_push and kg_cw_push take
 
 
 def partition(mod, seed, nb):
-    """how the seed's script is cut into calls, from a generator of its own: (cuts behind block numbers, merge); for lorc max_blocks"""
+    """how the seed's script is cut into calls, from a generator of its own: (cuts behind block numbers, merge); for lorc max_blocks;
+    for fax and cw the `cuts` of script_steps, which draws the blocks of the next push from PUSHES"""
     rng = _rng(mod, seed, partition=True)
     if mod == "lorc":
         return _pick(rng, (1, 2, 5, 48))
+    if mod in ("fax", "cw"):
+        return lambda: _pick(rng, PUSHES)
     p = _pick(rng, (0.02, 0.1, 0.3))
     return {b for b in range(1, nb) if rng.random() < p}, bool(rng.integers(2))
 
@@ -339,7 +370,33 @@ def calls_of(steps):
     return len(calls), sum(len({e[0] for e in s[2] if e[2]}) > 1 for s in calls), sum(len(e[2]) for s in calls for e in s[2])
 
 
+def pushes(mod, lines, cuts):
+    """fax, cw: the blocks of every push of run_script_dev(.., cuts=cuts), decided ahead of the run"""
+    return [len(st[1]) for st in COMMON[mod].script_steps(lines, cuts) if st[0] == "push"]
+
+
+def planned_pushes(mod):
+    """fax, cw: the blocks of every push of test_random_scripts_under_a_random_partition and test_shape_scripts"""
+    out = []
+    for seed in range(NSEED):
+        lines = SCRIPT[mod](seed)
+        out += pushes(mod, lines, partition(mod, seed, COMMON[mod].nblocks(lines))) + pushes(mod, lines, lambda: 1)
+    for lines in SHAPES[mod]().values():
+        out += pushes(mod, lines, lambda: 256) + pushes(mod, lines, lambda: 1)
+    return out
+
+
+def side_by_side(mod, q, pool, group):
+    """fax, cw: the group's three seeds on connections 0 .. 2 of q in lock step (q None: the schedule alone)
+    -> (the seeds, per seed the device's result, pushes, pushes that carried more than one connection)"""
+    seeds = triples()[group]
+    return (seeds,) + COMMON[mod].run_side_by_side(q, [SCRIPT[mod](s) for s in seeds], pool, plan_rng(mod, group))
+
+
 def shared_in_all(mod, resident=False):
     """over all the groups: (calls, calls that carry more than one script)"""
+    if mod in ("fax", "cw"):
+        n = [side_by_side(mod, None, None, g)[2:] for g in range(len(TRIPLES))]
+        return sum(v[0] for v in n), sum(v[1] for v in n)
     n = [calls_of(planned(mod, g, resident)[2]) for g in range(len(TRIPLES))]
     return sum(v[0] for v in n), sum(v[1] for v in n)

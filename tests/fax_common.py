@@ -295,6 +295,60 @@ def apply_command(q, conn, l, rate):
     return rate
 
 
+def _items(lines):
+    out, seen = [], 0
+    for l in lines:
+        if l[0] == "B":
+            out.append(("blk", int(l.split()[1]), seen))
+            seen += 1
+        else:
+            out.append(("cmd", l))
+    return out
+
+
+def run_side_by_side(q, scripts, samples, rng, most=24):
+    """scripts[c] on connection c of q (a FaxDecoder), in lockstep: every round each script takes its commands up to its next block,
+    then ONE push feeds every connection with blocks left, 1 to `most` consecutive blocks each (drawn from rng, a numpy Generator),
+    listed out of connection order.  Nothing of the schedule depends on what the device answers: with q None only the schedule is
+    walked.  -> (per script the keys of parse() -- None without q --, pushes, pushes that carried more than one connection)"""
+    items = [_items(s) for s in scripts]
+    at, rate, width = [0] * len(items), [0.0] * len(items), [0] * len(items)
+    rec = [Recorder(nblocks(s)) for s in scripts]
+    shared = calls = 0
+    while any(a < len(it) for a, it in zip(at, items)):
+        for c, it in enumerate(items):
+            while at[c] < len(it) and it[at[c]][0] == "cmd":
+                if q is not None:
+                    rate[c] = apply_command(q, c, it[at[c]][1], rate[c])
+                if it[at[c]][1][0] == "C":
+                    width[c] = int(it[at[c]][1].split()[2])
+                at[c] += 1
+        take = {}
+        for c, it in enumerate(items):
+            n = 0
+            lim = int(rng.integers(1, most + 1))
+            while n < lim and at[c] + n < len(it) and it[at[c] + n][0] == "blk":
+                n += 1
+            if n:
+                take[c] = it[at[c]:at[c] + n]
+        if not take:
+            break
+        conns = sorted(take, key=lambda c: -c)
+        if q is not None:
+            x = np.zeros((len(conns), max(len(v) for v in take.values()), BLK), np.int16)
+            for e, c in enumerate(conns):
+                for b, (_, off, _) in enumerate(take[c]):
+                    x[e, b] = samples[off:off + BLK]
+            recs, rows = q.push(conns, x, [rate[c] for c in conns], nblk=[len(take[c]) for c in conns])
+        for e, c in enumerate(conns):
+            if q is not None:
+                rec[c].add([b for _, _, b in take[c]], recs[e], rows[e], width[c])
+            at[c] += len(take[c])
+        shared += len(conns) > 1
+        calls += 1
+    return [rec[c].result(state_of(q, c)) if q is not None else None for c in range(len(scripts))], calls, shared
+
+
 def run_script_dev(q, lines, samples, conn=0, cuts=lambda: 64):
     """Runs a script on connection conn of q (a FaxDecoder): every push one call.  -> the keys of parse(), and "calls"."""
     rec, calls, rate, width = Recorder(nblocks(lines)), 0, 0.0, 0

@@ -281,3 +281,45 @@ def test_cw_symbols_declared_bound_and_exported():
     ev["a"] = [8, 0xff, 30, np.float32(47.5).view(np.int32)]
     ev["b"], ev["c"] = 1, np.float32(43.0103).view(np.int32)
     assert cw.messages(ev) == ["EXT cw_chars=<kn>", "EXT cw_chars=[err]", "EXT cw_wpm=30", "EXT cw_plot=47.50,1,43.01"] and cw.text(ev) == "<kn>[err]"
+
+
+# ---- seeded random scripts and shape scripts (tests/ext_random.py): what the hand-written scripts leave out
+@pytest.fixture(scope="module")
+def random_ref():
+    from . import ext_random as er
+    return er.load("cw")
+
+
+def test_random_scripts_host_model_equals_the_fixture(random_ref, pool, driver, tmp_path):
+    """every seed's script and every shape script is the one the reference was fed, the host model takes it (exit status 0) and equals
+    the reference in every field the fixture keeps: the events of every block, the text, the number of events of every kind, and the digests of the events and of the end state"""
+    from . import ext_random as er
+    scripts = [er.cw_script(seed) for seed in range(er.NSEED)] + list(er.cw_shapes().values())
+    assert int(random_ref["n_script_sha"].size) == len(scripts)
+    for k, lines in enumerate(scripts):
+        assert cc.nblocks(lines) <= er.MOST_BLOCKS
+        er.check_record("cw", k, lines, cc.run_script_exe(driver, lines, pool, tmp_path), er.unpack(random_ref, k))
+
+
+def test_random_fixture_meets_its_conditions(random_ref):
+    """conditions, not measurements: what the 40 seeds must reach between them (ext_random.CW_CONDITIONS), computed from the fixture
+    and the regenerated scripts; none of the 40 was refused by the reference.  The shape scripts count towards none"""
+    from . import ext_random as er
+    er.check_conditions("cw", random_ref)
+    assert os.path.getsize(er.fixture_path("cw")) <= 64 * 1024
+
+
+def test_random_pushes_reach_every_size():
+    """the pushes tests/test_cw_gpu.py makes with the seeds under their partitions and with the shape scripts are decided ahead of
+    any run: one holds 256 blocks (the most a push takes), one 45 to 255 (a second turn of phase A's loop over the Goertzel blocks, and not the whole of it), one a single block"""
+    from . import ext_random_dev as ed
+    n = ed.planned_pushes("cw")
+    assert max(n) == 256 and any(45 <= k <= 255 for k in n) and 1 in n and min(n) >= 1
+
+
+def test_random_side_by_side_pushes_are_shared():
+    """the pushes tests/test_cw_gpu.py makes with the seeds three at a time on one object are decided ahead of the run
+    (cw_common.run_side_by_side): over all the groups at least half of them carry more than one connection"""
+    from . import ext_random_dev as ed
+    every, both = ed.shared_in_all("cw")
+    assert 2 * both >= every, (both, every)

@@ -3,7 +3,14 @@ sound block, every event's fields and the end state -- every scalar, the ring, d
 random partitions of 1 to 64 blocks a push.  A push of 7 blocks (which straddles Goertzel blocks: 512 is no multiple of 88) equals 7
 pushes of one; four connections with different scripts side by side in one push equal each alone; a pboff between two pushes lands in
 mid Goertzel block; a refused command leaves the object as it was; one connection with one block gives 5 Goertzel blocks and carries 72
-samples.  Every comparison is an equality."""
+samples.  The largest push of the hand-written scripts holds 40 blocks (233 Goertzel blocks): their N lines, the clock, cut every
+stretch of blocks, so phase A's loop over the Goertzel blocks of a push takes one turn there.
+
+The seeded random scripts and the shape scripts of tests/ext_random.py go further: pushes of 1, 2, 7, 64 and 256 blocks (256 is the
+most kg_cw_push takes: 1489 or 1490 Goertzel blocks, six turns of that loop and the whole of its magnitudes), training intervals of 1
+and 255, nominal rates of 88 and 1000, ratios of 0.5 and 2, thresholds of 0 and below, a clock that jumps backwards or passes 2^32;
+against the host model (csrc/kg_cw.h through tools/cw_host_driver.cpp) in full and against tests/golden/cw_rand_ref.npz, the
+reference's record of the same scripts.  Every comparison is an equality."""
 import zlib
 
 import numpy as np
@@ -12,6 +19,7 @@ import pytest
 from flydog_sdr_gps_amd import Context, CwDecoder, KiwiGpuError
 
 from . import cw_common as cc
+from .ext_random import shape_names
 
 pytestmark = pytest.mark.gpu
 
@@ -94,57 +102,16 @@ def test_a_pboff_between_two_pushes_lands_in_mid_goertzel_block(golden, pool, ct
     q.close()
 
 
-def _items(lines):
-    out, seen = [], 0
-    for l in lines:
-        if l[0] == "B":
-            out.append(("blk", int(l.split()[1]), seen))
-            seen += 1
-        else:
-            out.append(("cmd", l))
-    return out
-
-
 def test_connections_side_by_side_equal_each_alone(golden, pool, ctx):
     """four scripts on four connections of one object, in lockstep: every round ONE push feeds every connection with blocks left, 1 to
     24 consecutive blocks each under its own now_sec, listed out of connection order; each equals the reference, which is what it gives
     alone"""
     rng = np.random.Generator(np.random.PCG64(0xC351DE))
-    scripts = [cc.scripts()[n] for n in SIDE]
     q = CwDecoder(ctx, nconn=len(SIDE) + 1)
-    items = [_items(s) for s in scripts]
-    at, now = [0] * len(items), [0] * len(items)
-    rec = [cc.Recorder(cc.nblocks(s)) for s in scripts]
-    shared = 0
-    while any(a < len(it) for a, it in zip(at, items)):
-        for c, it in enumerate(items):
-            while at[c] < len(it) and it[at[c]][0] == "cmd":
-                now[c] = cc.apply_command(q, c, it[at[c]][1], now[c])
-                at[c] += 1
-        take = {}
-        for c, it in enumerate(items):
-            n = 0
-            lim = int(rng.integers(1, 25))
-            while n < lim and at[c] + n < len(it) and it[at[c] + n][0] == "blk":
-                n += 1
-            if n:
-                take[c] = it[at[c]:at[c] + n]
-        if not take:
-            break
-        conns = sorted(take, key=lambda c: -c)
-        most = max(len(v) for v in take.values())
-        x = np.zeros((len(conns), most, cc.BLK), np.int16)
-        for e, c in enumerate(conns):
-            for b, (_, off, _) in enumerate(take[c]):
-                x[e, b] = pool[off:off + cc.BLK]
-        evs = q.push(conns, x, [now[c] for c in conns], nblk=[len(take[c]) for c in conns])
-        for e, c in enumerate(conns):
-            rec[c].add([b for _, _, b in take[c]], evs[e])
-            at[c] += len(take[c])
-        shared += len(conns) > 1
+    got, _, shared = cc.run_side_by_side(q, [cc.scripts()[n] for n in SIDE], pool, rng)
     assert shared >= 10
     for c, name in enumerate(SIDE):
-        cc.check_against_golden(golden, name, rec[c].result(q.state(c)))
+        cc.check_against_golden(golden, name, got[c])
     assert q.state(len(SIDE))["blocksize"] == 0 and q.state(len(SIDE))["slowdown"] == 0
     q.close()
 
@@ -185,3 +152,84 @@ def test_a_refusal_changes_nothing_on_the_device(pool, ctx):
     after = q.state(0)
     assert after["started"] == 0 and mid["started"] == 0 and after.tobytes() == mid.tobytes()
     q.close()
+
+
+# ---- seeded random scripts and shape scripts (tests/ext_random.py): the device against the host model in full, and the fixture.  A
+# script begins on a fresh object: what a restart carries over would otherwise come from the script before it.
+PARTS = 4                                                                  # the 40 seeds, ten a test
+
+
+@pytest.fixture(scope="module")
+def random_ref():
+    from . import ext_random as er
+    return er.load("cw")
+
+
+@pytest.fixture(scope="module")
+def random_host(pool, tmp_path_factory):
+    """k -> the host driver's result of seed k, or of shape script k - NSEED, sample by sample: made once when first asked for, shared,
+    left unchanged"""
+    from . import ext_random as er
+    tmp = tmp_path_factory.mktemp("cw_random")
+    driver, scripts, made = cc.build_driver(tmp), [er.cw_script(s) for s in range(er.NSEED)] + list(er.cw_shapes().values()), {}
+
+    def host(k):
+        if k not in made:
+            made[k] = cc.run_script_exe(driver, scripts[k], pool, tmp)
+        return made[k]
+    return host
+
+
+@pytest.mark.parametrize("part", range(PARTS))
+def test_random_scripts_under_a_random_partition(ctx, random_ref, random_host, pool, part):
+    """every seed's script with 1, 2, 7, 64 or 256 blocks a push (drawn push by push by a generator of its own) on one connection, and
+    a block a push on another: both equal the host model in full, hence each other, and the fixture"""
+    from . import ext_random as er, ext_random_dev as ed
+    for seed in range(part * er.NSEED // PARTS, (part + 1) * er.NSEED // PARTS):
+        lines = er.cw_script(seed)
+        q = CwDecoder(ctx, nconn=2)
+        try:
+            got = cc.run_script_dev(q, lines, pool, conn=0, cuts=ed.partition("cw", seed, cc.nblocks(lines)))
+            each = cc.run_script_dev(q, lines, pool, conn=1, cuts=lambda: 1)
+        finally:
+            q.close()
+        ed.cw_same(got, random_host(seed), "seed %d" % seed, "the partition")
+        ed.cw_same(each, random_host(seed), "seed %d" % seed, "a push a block")
+        assert each["calls"] == cc.nblocks(lines) >= got["calls"]
+        er.check_record("cw", seed, lines, got, er.unpack(random_ref, seed))
+
+
+@pytest.mark.parametrize("name", shape_names("cw"))
+def test_shape_scripts(ctx, random_ref, random_host, pool, name):
+    """a kernel-shape edge (ext_random.cw_shapes), once with up to 256 blocks a push and once with one: both equal the host model
+    in full and the fixture"""
+    from . import ext_random as er, ext_random_dev as ed
+    k = er.NSEED + er.shape_names("cw").index(name)
+    lines, runs = er.cw_shapes()[name], []
+    for cut in (256, 1):
+        q = CwDecoder(ctx, nconn=1)
+        try:
+            runs.append(cc.run_script_dev(q, lines, pool, cuts=lambda: cut))
+        finally:
+            q.close()
+        ed.cw_same(runs[-1], random_host(k), name, "%d blocks a push" % cut)
+        er.check_record("cw", k, lines, runs[-1], er.unpack(random_ref, k))
+    assert runs[1]["calls"] == cc.nblocks(lines) > runs[0]["calls"]
+    if name == "one_push_256":                                                 # the device's own count: 256 * 512 = 1489 * 88 + 40, then 40 + 512 = 6 * 88 + 24
+        assert runs[0]["gblocks"] == [(256, 1489), (1, 6)]
+
+
+@pytest.mark.parametrize("group", range(14))
+def test_random_scripts_side_by_side(ctx, random_ref, random_host, pool, group):
+    """the seeds three at a time on three connections of one object, in lock step (cw_common.run_side_by_side, drawn from
+    ext_random_dev.plan_rng): each connection equals the host model of its own script in full, and the fixture"""
+    from . import ext_random as er, ext_random_dev as ed
+    q = CwDecoder(ctx, nconn=3)
+    try:
+        seeds, got, calls, shared = ed.side_by_side("cw", q, pool, group)
+    finally:
+        q.close()
+    for seed, g in zip(seeds, got):
+        ed.cw_same(g, random_host(seed), "seed %d of %s" % (seed, seeds))
+        er.check_record("cw", seed, er.cw_script(seed), g, er.unpack(random_ref, seed))
+    assert shared >= 1 and calls >= shared

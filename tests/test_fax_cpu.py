@@ -263,3 +263,45 @@ def test_fax_symbols_declared_bound_and_exported():
     src = open(os.path.join(ROOT, "flydog_sdr_gps_amd", "csrc", "kg_fax.h")).read()
     assert "DET_CAP = 3000, MAX_SPL = 24576, MSG_DRAW = 254" in src
     assert (fax.rec_dtype, fax.info_dtype) == (fc.rec_dtype, fc.info_dtype)
+
+
+# ---- seeded random scripts and shape scripts (tests/ext_random.py): what the hand-written scripts leave out
+@pytest.fixture(scope="module")
+def random_ref():
+    from . import ext_random as er
+    return er.load("fax")
+
+
+def test_random_scripts_host_model_equals_the_fixture(random_ref, pool, driver, tmp_path):
+    """every seed's script and every shape script is the one the reference was fed, the host model takes it (exit status 0) and equals
+    the reference in every field the fixture keeps: the lines of every block, every line's type, flags and pick, and the digests of the other record fields, the rows and the end state"""
+    from . import ext_random as er
+    scripts = [er.fax_script(seed) for seed in range(er.NSEED)] + list(er.fax_shapes().values())
+    assert int(random_ref["n_script_sha"].size) == len(scripts)
+    for k, lines in enumerate(scripts):
+        assert fc.nblocks(lines) <= er.MOST_BLOCKS
+        er.check_record("fax", k, lines, fc.run_script_exe(driver, lines, pool, tmp_path), er.unpack(random_ref, k))
+
+
+def test_random_fixture_meets_its_conditions(random_ref):
+    """conditions, not measurements: what the 40 seeds must reach between them (ext_random.FAX_CONDITIONS), computed from the fixture
+    and the regenerated scripts; none of the 40 was refused by the reference.  The shape scripts count towards none"""
+    from . import ext_random as er
+    er.check_conditions("fax", random_ref)
+    assert os.path.getsize(er.fixture_path("fax")) <= 64 * 1024
+
+
+def test_random_pushes_reach_every_size():
+    """the pushes tests/test_fax_gpu.py makes with the seeds under their partitions and with the shape scripts are decided ahead of
+    any run: one holds 256 blocks (the most a push takes), one 45 to 255, one a single block"""
+    from . import ext_random_dev as ed
+    n = ed.planned_pushes("fax")
+    assert max(n) == 256 and any(45 <= k <= 255 for k in n) and 1 in n and min(n) >= 1
+
+
+def test_random_side_by_side_pushes_are_shared():
+    """the pushes tests/test_fax_gpu.py makes with the seeds three at a time on one object are decided ahead of the run
+    (fax_common.run_side_by_side): over all the groups at least half of them carry more than one connection"""
+    from . import ext_random_dev as ed
+    every, both = ed.shared_in_all("fax")
+    assert 2 * both >= every, (both, every)

@@ -4,7 +4,15 @@ partitions of 1 to 64 blocks a push.  A script pushed a block at a time equals t
 scripts side by side in one push equal each alone; a refused command leaves the object as it was (the push on device-resident audio is
 the receiver bank's: tests/test_fax_bank_gpu.py holds it to the host-array push).  The shapes: 240 lpm (3000 samples a line, the
 detector's cap exactly), 120 lpm (the cap below the line), 60 lpm at 20250 Hz (the longest line), a push that ends one sample short of
-a line, a skip larger than a block.  Every comparison is an equality."""
+a line, a skip larger than a block.  The largest push of the hand-written scripts holds 64 blocks (the 256 asked for `shift_mid` are cut
+to 40 by its commands).
+
+The seeded random scripts and the shape scripts of tests/ext_random.py go further: pushes of 1, 2, 7, 64 and 256 blocks (256 is the
+most kg_fax_push takes), lines of 10 to 24576 samples -- exact multiples of the demodulator's chunk of 1024, a last chunk shorter than
+the 16 carried products, lines shorter than them and than the workgroup, 2999 and 3001 around the detector's cap --, rate ratios of
+exactly 0.5 (1024 picks a block, the pick walk's bound) and 2, an imagewidth of 1 and of the whole line; against the host model
+(csrc/kg_fax.h through tools/fax_host_driver.cpp) in full and against tests/golden/fax_rand_ref.npz, the reference's record of the
+same scripts.  Every comparison is an equality."""
 import zlib
 
 import numpy as np
@@ -13,6 +21,7 @@ import pytest
 from flydog_sdr_gps_amd import Context, FaxDecoder, KiwiGpuError
 
 from . import fax_common as fc
+from .ext_random import shape_names
 
 pytestmark = pytest.mark.gpu
 
@@ -80,58 +89,15 @@ def test_one_sample_short_of_a_line(golden, pool, ctx):
     q2.close()
 
 
-def _items(lines):
-    out, seen = [], 0
-    for l in lines:
-        if l[0] == "B":
-            out.append(("blk", int(l.split()[1]), seen))
-            seen += 1
-        else:
-            out.append(("cmd", l))
-    return out
-
-
 def test_connections_side_by_side_equal_each_alone(golden, pool, ctx):
     """six scripts on six connections of one object, in lockstep: every round ONE push feeds every connection with blocks left, 1 to 24
     consecutive blocks each, listed out of connection order; each equals the reference, which is what it gives alone"""
     rng = np.random.Generator(np.random.PCG64(0xFA51DE))
-    scripts = [fc.scripts()[n] for n in SIDE]
     q = FaxDecoder(ctx, nconn=len(SIDE) + 1)
-    items = [_items(s) for s in scripts]
-    at, rate, width = [0] * len(items), [0.0] * len(items), [0] * len(items)
-    rec = [fc.Recorder(fc.nblocks(s)) for s in scripts]
-    shared = 0
-    while any(a < len(it) for a, it in zip(at, items)):
-        for c, it in enumerate(items):
-            while at[c] < len(it) and it[at[c]][0] == "cmd":
-                rate[c] = fc.apply_command(q, c, it[at[c]][1], rate[c])
-                if it[at[c]][1][0] == "C":
-                    width[c] = int(it[at[c]][1].split()[2])
-                at[c] += 1
-        take = {}
-        for c, it in enumerate(items):
-            n = 0
-            lim = int(rng.integers(1, 25))
-            while n < lim and at[c] + n < len(it) and it[at[c] + n][0] == "blk":
-                n += 1
-            if n:
-                take[c] = it[at[c]:at[c] + n]
-        if not take:
-            break
-        conns = sorted(take, key=lambda c: -c)
-        most = max(len(v) for v in take.values())
-        x = np.zeros((len(conns), most, fc.BLK), np.int16)
-        for e, c in enumerate(conns):
-            for b, (_, off, _) in enumerate(take[c]):
-                x[e, b] = pool[off:off + fc.BLK]
-        recs, rows = q.push(conns, x, [rate[c] for c in conns], nblk=[len(take[c]) for c in conns])
-        for e, c in enumerate(conns):
-            rec[c].add([b for _, _, b in take[c]], recs[e], rows[e], width[c])
-            at[c] += len(take[c])
-        shared += len(conns) > 1
+    got, _, shared = fc.run_side_by_side(q, [fc.scripts()[n] for n in SIDE], pool, rng)
     assert shared >= 5
     for c, name in enumerate(SIDE):
-        fc.check_against_golden(golden, name, rec[c].result(fc.state_of(q, c)))
+        fc.check_against_golden(golden, name, got[c])
     assert q.state(len(SIDE))[0]["spl"] == 0                                     # the idle connection is still the zeroed object
     q.close()
 
@@ -161,3 +127,81 @@ def test_a_refusal_changes_nothing_on_the_device(pool, ctx):
     after = q.state(0)
     assert after[0]["started"] == 0 and [np.asarray(a).tobytes() for a in after[1:]] == before[1:]
     q.close()
+
+
+# ---- seeded random scripts and shape scripts (tests/ext_random.py): the device against the host model in full, and the fixture.  A
+# script begins on a fresh object: what a restart carries over would otherwise come from the script before it.
+PARTS = 4                                                                  # the 40 seeds, ten a test
+
+
+@pytest.fixture(scope="module")
+def random_ref():
+    from . import ext_random as er
+    return er.load("fax")
+
+
+@pytest.fixture(scope="module")
+def random_host(pool, tmp_path_factory):
+    """k -> the host driver's result of seed k, or of shape script k - NSEED, sample by sample: made once when first asked for, shared,
+    left unchanged"""
+    from . import ext_random as er
+    tmp = tmp_path_factory.mktemp("fax_random")
+    driver, scripts, made = fc.build_driver(tmp), [er.fax_script(s) for s in range(er.NSEED)] + list(er.fax_shapes().values()), {}
+
+    def host(k):
+        if k not in made:
+            made[k] = fc.run_script_exe(driver, scripts[k], pool, tmp)
+        return made[k]
+    return host
+
+
+@pytest.mark.parametrize("part", range(PARTS))
+def test_random_scripts_under_a_random_partition(ctx, random_ref, random_host, pool, part):
+    """every seed's script with 1, 2, 7, 64 or 256 blocks a push (drawn push by push by a generator of its own) on one connection, and
+    a block a push on another: both equal the host model in full, hence each other, and the fixture"""
+    from . import ext_random as er, ext_random_dev as ed
+    for seed in range(part * er.NSEED // PARTS, (part + 1) * er.NSEED // PARTS):
+        lines = er.fax_script(seed)
+        q = FaxDecoder(ctx, nconn=2)
+        try:
+            got = fc.run_script_dev(q, lines, pool, conn=0, cuts=ed.partition("fax", seed, fc.nblocks(lines)))
+            each = fc.run_script_dev(q, lines, pool, conn=1, cuts=lambda: 1)
+        finally:
+            q.close()
+        ed.fax_same(got, random_host(seed), "seed %d" % seed, "the partition")
+        ed.fax_same(each, random_host(seed), "seed %d" % seed, "a push a block")
+        assert each["calls"] == fc.nblocks(lines) >= got["calls"]
+        er.check_record("fax", seed, lines, got, er.unpack(random_ref, seed))
+
+
+@pytest.mark.parametrize("name", shape_names("fax"))
+def test_shape_scripts(ctx, random_ref, random_host, pool, name):
+    """a kernel-shape edge (ext_random.fax_shapes), once with up to 256 blocks a push and once with one: both equal the host model
+    in full and the fixture"""
+    from . import ext_random as er, ext_random_dev as ed
+    k = er.NSEED + er.shape_names("fax").index(name)
+    lines, runs = er.fax_shapes()[name], []
+    for cut in (256, 1):
+        q = FaxDecoder(ctx, nconn=1)
+        try:
+            runs.append(fc.run_script_dev(q, lines, pool, cuts=lambda: cut))
+        finally:
+            q.close()
+        ed.fax_same(runs[-1], random_host(k), name, "%d blocks a push" % cut)
+        er.check_record("fax", k, lines, runs[-1], er.unpack(random_ref, k))
+    assert runs[1]["calls"] == fc.nblocks(lines) > runs[0]["calls"]
+
+@pytest.mark.parametrize("group", range(14))
+def test_random_scripts_side_by_side(ctx, random_ref, random_host, pool, group):
+    """the seeds three at a time on three connections of one object, in lock step (fax_common.run_side_by_side, drawn from
+    ext_random_dev.plan_rng): each connection equals the host model of its own script in full, and the fixture"""
+    from . import ext_random as er, ext_random_dev as ed
+    q = FaxDecoder(ctx, nconn=3)
+    try:
+        seeds, got, calls, shared = ed.side_by_side("fax", q, pool, group)
+    finally:
+        q.close()
+    for seed, g in zip(seeds, got):
+        ed.fax_same(g, random_host(seed), "seed %d of %s" % (seed, seeds))
+        er.check_record("fax", seed, er.fax_script(seed), g, er.unpack(random_ref, seed))
+    assert shared >= 1 and calls >= shared

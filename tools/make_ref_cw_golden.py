@@ -13,10 +13,13 @@ The conditions of tests/test_cw_cpu.py::test_golden_file_meets_its_conditions ar
 file is kept.
 
     python tools/make_ref_cw_golden.py [--show]
+    python tools/make_ref_cw_golden.py --random     tests/golden/cw_rand_ref.npz: the seeded random scripts and the shape scripts of
+                                                    tests/ext_random.py, by digest and integers alone
 """
 import os
 import subprocess
 import sys
+import tempfile
 
 import ref_cut
 from ref_cut import ROOT  # ref_cut puts the repository root on sys.path
@@ -96,5 +99,11 @@ def main():
     ref_cut.script_golden_main(C, build, "cw_ref.npz", ref_cut.script_by_digest, report, check="--nocheck" not in sys.argv)
 
 
+def random_main():
+    from tests import ext_random
+    with tempfile.TemporaryDirectory() as tmp:
+        ext_random.write_fixture("cw", build(tmp), C.pool(), tmp)
+
+
 if __name__ == "__main__":
-    main()
+    random_main() if sys.argv[1:] == ["--random"] else main()

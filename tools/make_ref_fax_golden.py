@@ -12,9 +12,13 @@ completed, every line's record, every row and the end state, every scalar and ar
 tests/test_fax_cpu.py::test_golden_file_meets_its_conditions are checked here, by that very function, before the file is kept.
 
     python tools/make_ref_fax_golden.py
+    python tools/make_ref_fax_golden.py --random     tests/golden/fax_rand_ref.npz: the seeded random scripts and the shape scripts of
+                                                    tests/ext_random.py, by digest and integers alone
 """
 import os
 import subprocess
+import sys
+import tempfile
 
 import ref_cut
 from ref_cut import ROOT  # ref_cut puts the repository root on sys.path
@@ -86,5 +90,11 @@ def main():
     ref_cut.script_golden_main(C, build, "fax_ref.npz", ref_cut.script_by_digest, report)
 
 
+def random_main():
+    from tests import ext_random
+    with tempfile.TemporaryDirectory() as tmp:
+        ext_random.write_fixture("fax", build(tmp), C.pool(), tmp)
+
+
 if __name__ == "__main__":
-    main()
+    random_main() if sys.argv[1:] == ["--random"] else main()
