@@ -271,6 +271,23 @@ SYMBOLS = {
     "kg_cw_max_events": (_i, [_i]),
     "kg_cw_push": (_i, [_vp, _vp, _i, _vp, _vp, _sz, _vp, _vp, _i, _vp]),
     "kg_cw_state": (_i, [_vp, _i, _vp]),
+    "kg_wspr_create": (_i, [_vp, _i, C.POINTER(_vp)]),
+    "kg_wspr_destroy": (None, [_vp]),
+    "kg_wspr_init": (_i, [_vp, _i, C.c_double]),
+    "kg_wspr_set_capture": (_i, [_vp, _i, _i]),
+    "kg_wspr_set_type": (_i, [_vp, _i, _i]),
+    "kg_wspr_set_more_candidates": (_i, [_vp, _i, _i]),
+    "kg_wspr_push": (_i, [_vp, _vp, _i, _vp, _i, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "kg_wspr_plan": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "kg_wspr_state": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    "kg_wspr_load": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "kg_rxbank_wspr_init": (_i, [_vp, _i, C.c_double]),
+    "kg_rxbank_wspr_set_capture": (_i, [_vp, _i, _i]),
+    "kg_rxbank_wspr_set_type": (_i, [_vp, _i, _i]),
+    "kg_rxbank_wspr_set_more_candidates": (_i, [_vp, _i, _i]),
+    "kg_rxbank_wspr_set_now": (_i, [_vp, _i, _i]),
+    "kg_rxbank_wspr": (_vp, [_vp]),
+    "kg_rxbank_wspr_out": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i]),
     "kg_rxbank_lorc_init": (_i, [_vp, _i, C.c_double, _i]),
     "kg_rxbank_lorc_set_gri": (_i, [_vp, _i, _i, _i]),
     "kg_rxbank_lorc_set_offset": (_i, [_vp, _i, _i, _i]),

@@ -271,6 +271,18 @@ __attribute__((visibility("hidden"))) int kg_cw_push_at_(kg_cw *q, const int32_t
 __attribute__((visibility("hidden"))) size_t kg_cw_table_bytes_(size_t nconn);
 __attribute__((visibility("hidden"))) int kg_cw_reset_(kg_cw *q, int conn);
 
+// kg_wspr.hip, for kg_rxbank.hip (not part of the ABI): kg_wspr_push on device memory, samples and outputs alike, entry i's samples at row
+// in_row[i] of d_iq (null: row i), rows at multiples of KG_WSPR_ROW_STRIDE in list order, cycles and counts an entry of the list each,
+// enqueue only; the bytes a push's table takes when no connection has more than ops_per_conn ops; connection conn as a new connection
+// finds it: the zeroed object, not initialised
+struct kg_wspr;
+__attribute__((visibility("hidden"))) int kg_wspr_push_rows_(kg_wspr *q, const int32_t *conns, int nconn, const int32_t *nblk, const int32_t *in_row, int ns,
+                                                             const float *d_iq, size_t iq_stride, const int32_t *minute, const int32_t *second, size_t time_stride,
+                                                             uint8_t *d_rows, size_t rows_cap, kg_wspr_row *row_map, int max_rows, int32_t *nrows, kg_wspr_ev *evs,
+                                                             int max_events, int32_t *nevents, kg_wspr_cycle *d_cycles, int32_t *d_counts);
+__attribute__((visibility("hidden"))) size_t kg_wspr_table_bytes_(size_t nconn, size_t ops_per_conn);
+__attribute__((visibility("hidden"))) int kg_wspr_reset_(kg_wspr *q, int conn);
+
 // kg_post.hip, for kg_rxbank.hip: how many kg_post_set_mode / kg_post_set_sam_mparam calls channel ch has seen (each clears
 // s->isChanNull, rx_sound_cmd.cpp:202-228), and its s->SAM_mparam
 __attribute__((visibility("hidden"))) uint32_t kg_post_mode_cmds_(const kg_post *p, int ch);

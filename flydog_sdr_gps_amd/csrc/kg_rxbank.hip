@@ -206,6 +206,25 @@ struct bank_cw {
     struct { std::vector<int32_t> rx; int n; } last;    // kg_rxbank_cw_out: the last step's entries and their receivers
 };
 
+// WSPR, stage 1 (extensions/wspr/; kg_wspr); its first call also grows the arena slots by its table.  The third consumer of the IQ tap
+// (ext_register_receive_iq_samps, wspr_main.cpp:891): while a receiver captures and is not in NBFM, its CFastFIR output of the step feeds it
+// in place, exactly as the IQ display and Loran-C are fed: ONE launch per step over all such receivers, and the cycle-end launch behind it
+// when a receiver completes group 85, on the tail stream ahead of ev_tail.  Every block of a step carries the minute and second of the
+// last kg_rxbank_wspr_set_now.  Rows, cycles and counts are the device's; the row map and the events are the host's schedule.
+struct bank_ws {
+    kg_wspr *obj;
+    kg_dbuf<unsigned char> d_rows; size_t cap; int max_rows, max_events;   // the step's rows at multiples of KG_WSPR_ROW_STRIDE, in list order
+    kg_dbuf<kg_wspr_cycle> d_cycles;                                       // [entry]
+    kg_dbuf<int32_t> d_counts;                                             // [entry][4]
+    std::vector<char> on;                               // `SET capture=1` (ext_register_receive_iq_samps: one of the three at most)
+    int32_t min, sec;
+    struct {
+        std::vector<int32_t> list, nblk, row, min, sec; // the entries: receiver, blocks, the receiver's row of d_firo; the clock of every block
+        std::vector<kg_wspr_row> rows; std::vector<kg_wspr_ev> evs; int32_t n, ne;      // handed back
+    } plan;
+    struct { std::vector<kg_wspr_row> rows; std::vector<kg_wspr_ev> evs; std::vector<int32_t> rx; int n, ne, nent; } last;      // kg_rxbank_wspr_out
+};
+
 struct kg_rxbank {
     // configuration
     int device, nrx, mode, decim_rx;
@@ -219,7 +238,7 @@ struct kg_rxbank {
     kg_ddc *ddc; kg_wf *wf; kg_rxddc *rx; kg_fir *fir; kg_post *post; kg_adpcm *adpcm;
     kg_nb *nb;                                  // m_NoiseProc_snd[] (the waterfall's blankers are kg_wf's)
     kg_fir *nullfir;                            // m_chan_null_FIR[] (rx_sound.cpp:151), on the tail stream behind kg_post
-    bank_fx fx; bank_iq iq; bank_lo lo; bank_fa fa; bank_cw cw;         // the extensions (above)
+    bank_fx fx; bank_iq iq; bank_lo lo; bank_fa fa; bank_cw cw; bank_ws ws;     // the extensions (above)
     // device buffers
     kg_dbuf<short2> d_wfiq; size_t wf_stride;         // [nrx][wf_stride] iq_t: a one-shot receiver uses pairs 0 .. 8191 of its row, an overlapped one all of it
     kg_dbuf<unsigned char> d_rows, d_pkts;         // [frame][1024], [frame][BANK_PKT_STRIDE]
@@ -301,7 +320,7 @@ static bool bank_stereo(int mode) { return mode == KG_POST_IQ || mode == KG_POST
 //   _plan_clear, _plan    the step's lists: emptied, then entry i of the active list (receiver p.act[i], nblk sound blocks)
 //   _enqueue     its ONE launch of the step, on the tail stream; what the entry point hands back goes into the record's plan
 //   _commit      the plan's maps become the last step's
-// The general functions call the five by name, in the order fx, iq, lo, fa, cw: that is the order of the launches on the tail stream
+// The general functions call the six by name, in the order fx, iq, lo, fa, cw, ws: that is the order of the launches on the tail stream
 // and of the tables in the slot.
 
 // A device buffer of a record: where its pointer goes, its size, its name in a refusal
@@ -629,6 +648,73 @@ static void bank_cw_commit(kg_rxbank *b)
     for (int e = 0; e < x.last.n; e++) x.last.rx[e] = x.plan.list[e];
 }
 
+#define BANK_WS_OPS(blocks_) (4 * (size_t) (blocks_) + 4)      /* a callback of 512 samples: a clear, two copy runs and a group at most */
+
+static void bank_ws_sizes(kg_rxbank *b)
+{
+    bank_ws &x = b->ws;
+    const size_t nrx = (size_t) b->nrx;
+    x.max_rows = (int) (nrx * (b->blocks_max + 1));     // a group a callback at most (int_decimate >= 1)
+    x.cap = (size_t) x.max_rows * KG_WSPR_ROW_STRIDE;
+    x.max_events = (int) (nrx * 16);                    // 8 pending, the sync, DECODING / PEAKS / resume of the one cycle end a step can hold
+    x.on.assign(nrx, 0);
+    x.min = x.sec = 0;
+    for (std::vector<int32_t> *v : {&x.plan.list, &x.plan.nblk, &x.plan.row}) v->reserve(nrx);
+    for (std::vector<int32_t> *v : {&x.plan.min, &x.plan.sec}) v->reserve(nrx * b->blocks_max);
+    x.last.rx.assign(nrx, -1);
+}
+
+static int bank_ws_ensure(kg_rxbank *b)
+{
+    bank_ws &x = b->ws;
+    if (x.obj) return KG_OK;
+    KG_TRY(bank_ext_ensure(b, "kg_rxbank_wspr",
+                           {bank_buf(x.d_rows, x.cap, "kg_rxbank_wspr: rows"), bank_buf(x.d_cycles, (size_t) b->nrx, "kg_rxbank_wspr: cycles"),
+                            bank_buf(x.d_counts, (size_t) 4 * b->nrx, "kg_rxbank_wspr: counts")},
+                           kg_wspr_table_bytes_((size_t) b->nrx, BANK_WS_OPS(b->blocks_max)), [](kg_rxbank *b) { return kg_wspr_create(b->c_tail, b->nrx, &b->ws.obj); }));
+    for (std::vector<kg_wspr_row> *v : {&x.last.rows, &x.plan.rows}) v->assign((size_t) x.max_rows, kg_wspr_row{});
+    for (std::vector<kg_wspr_ev> *v : {&x.last.evs, &x.plan.evs}) v->assign((size_t) x.max_events, kg_wspr_ev{});
+    return KG_OK;
+}
+
+// the connection's end or beginning: wspr[rx] as a new connection finds it -- zeroed, not capturing, waiting for its `SET ext_server_init`
+static int bank_ws_fresh(kg_rxbank *b, int rx) { b->ws.on[rx] = 0; return b->ws.obj ? kg_wspr_reset_(b->ws.obj, rx) : KG_OK; }
+
+static void bank_ws_plan_clear(kg_rxbank *b)
+{
+    bank_ws &x = b->ws;
+    for (std::vector<int32_t> *v : {&x.plan.list, &x.plan.nblk, &x.plan.row, &x.plan.min, &x.plan.sec}) v->clear();
+    x.plan.n = x.plan.ne = 0;
+}
+
+static void bank_ws_plan(kg_rxbank *b, int i, int nblk)
+{
+    bank_ws &x = b->ws;
+    const int k = b->plan.act[i];
+    if (!x.obj || !x.on[k] || nblk <= 0 || b->plan.mode[i] == KG_POST_NBFM) return;       // the IQ display's tap, and its NBFM rule
+    x.plan.list.push_back(k); x.plan.nblk.push_back(nblk); x.plan.row.push_back(k);
+    x.plan.min.insert(x.plan.min.end(), b->blocks_max, x.min); x.plan.sec.insert(x.plan.sec.end(), b->blocks_max, x.sec);
+}
+
+// wspr_data over the step's blocks: one launch, reading d_firo in place, and the cycle-end launch when one is due
+static int bank_ws_enqueue(kg_rxbank *b)
+{
+    bank_ws &x = b->ws;
+    if (x.plan.list.empty()) return KG_OK;
+    return kg_wspr_push_rows_(x.obj, x.plan.list.data(), (int) x.plan.list.size(), x.plan.nblk.data(), x.plan.row.data(), KG_FIR_OUT, (const float *) b->d_firo.p,
+                              b->firo_stride, x.plan.min.data(), x.plan.sec.data(), b->blocks_max, x.d_rows, x.cap, x.plan.rows.data(), x.max_rows, &x.plan.n,
+                              x.plan.evs.data(), x.max_events, &x.plan.ne, x.d_cycles, x.d_counts);
+}
+
+static void bank_ws_commit(kg_rxbank *b)
+{
+    bank_ws &x = b->ws;
+    x.last.n = x.plan.n; x.last.ne = x.plan.ne; x.last.nent = (int) x.plan.list.size();
+    if (!x.obj) return;
+    x.last.rows.swap(x.plan.rows); x.last.evs.swap(x.plan.evs);
+    for (int e = 0; e < x.last.nent; e++) x.last.rx[e] = x.plan.list[e];
+}
+
 // a connection ends or begins on receiver rx: every extension as a new connection finds it
 static int bank_ext_fresh(kg_rxbank *b, int rx)
 {
@@ -636,7 +722,8 @@ static int bank_ext_fresh(kg_rxbank *b, int rx)
     KG_TRY(bank_iq_fresh(b, rx));
     KG_TRY(bank_lo_fresh(b, rx));
     KG_TRY(bank_fa_fresh(b, rx));
-    return bank_cw_fresh(b, rx);
+    KG_TRY(bank_cw_fresh(b, rx));
+    return bank_ws_fresh(b, rx);
 }
 
 // The real-samples task tap (ext_register_receive_real_samps_task) holds one task per receiver, FAX's or the CW decoder's: whoever
@@ -648,12 +735,20 @@ static int bank_real_tap_free(const kg_rxbank *b, int rx, const char *who, bool 
     return KG_OK;
 }
 
-// The IQ tap (ext_users[rx].receive_iq_pre_agc) holds one callback, the IQ display's or Loran-C's: whoever asks for it is refused while
-// the other has it
+// The IQ tap (ext_users[rx].receive_iq_pre_agc) holds one callback, the IQ display's, Loran-C's or WSPR's: whoever asks for it is refused
+// while another has it
 static int bank_tap_free(const kg_rxbank *b, int rx, const char *who, bool lorc_asks)
 {
+    KG_REQUIRE(!b->ws.on[rx], KG_ERR_STATE, "%s: receiver %d has WSPR capturing; the tap holds one callback", who, rx);
     KG_REQUIRE(!(lorc_asks ? b->iq.on[rx] : b->lo.on[rx]), KG_ERR_STATE, "%s: receiver %d has %s; the tap holds one callback", who, rx,
                lorc_asks ? "the IQ display running" : "Loran-C started");
+    return KG_OK;
+}
+
+static int bank_tap_free_for_wspr(const kg_rxbank *b, int rx, const char *who)
+{
+    KG_REQUIRE(!b->iq.on[rx] && !b->lo.on[rx], KG_ERR_STATE, "%s: receiver %d has %s; the tap holds one callback", who, rx,
+               b->iq.on[rx] ? "the IQ display running" : "Loran-C started");
     return KG_OK;
 }
 
@@ -692,6 +787,7 @@ static void bank_plan_rows(kg_rxbank *b, int i, int nblk)
     bank_lo_plan(b, i, nblk);
     bank_fa_plan(b, i, nblk);
     bank_cw_plan(b, i, nblk);
+    bank_ws_plan(b, i, nblk);
 }
 
 // The active list and, per entry, the counts its audio DDC and its CFastFIR will hand back (kg_rxddc_outputs is kg_rxddc_push_dev's
@@ -708,6 +804,7 @@ static void bank_plan_audio(kg_rxbank *b)
     bank_lo_plan_clear(b);
     bank_fa_plan_clear(b);
     bank_cw_plan_clear(b);
+    bank_ws_plan_clear(b);
     for (int k = 0; k < b->nrx; k++) {
         const bank_rx &r = b->rcv[k];
         p.enabled[k] = r.active ? 1 : 0;
@@ -908,6 +1005,7 @@ static int bank_audio_tail(kg_rxbank *b)
     KG_TRY(bank_lo_enqueue(b));
     KG_TRY(bank_fa_enqueue(b));
     KG_TRY(bank_cw_enqueue(b));
+    KG_TRY(bank_ws_enqueue(b));
     KG_TRY(bank_edge(real, b->ev_tail, b->s_tail, nullptr, &b->tail_pending));
     tk.lap(b, PF_EVENTS, real);
     return KG_OK;
@@ -971,6 +1069,7 @@ static void bank_commit(kg_rxbank *b)
     bank_lo_commit(b);
     bank_fa_commit(b);
     bank_cw_commit(b);
+    bank_ws_commit(b);
     b->frame_rx.swap(p.chan_of); b->frame_off.swap(p.frame_off); b->pkt_bytes.swap(p.pkt_bytes);
 }
 
@@ -1219,6 +1318,7 @@ static int bank_init(kg_rxbank *b)
     bank_lo_sizes(b);
     bank_fa_sizes(b);
     bank_cw_sizes(b);
+    bank_ws_sizes(b);
     for (std::vector<int32_t> *v : {&b->spec_rx, &b->spec_inst, &b->spec_blk}) v->assign(b->spec_max, 0);
     b->frame_rx.assign(nrx, -1); b->pkt_bytes.assign(nrx, 0); b->frame_off.assign(nrx, 0);
     memset(&b->arena, 0, sizeof b->arena);
@@ -1240,6 +1340,7 @@ void kg_rxbank_destroy(kg_rxbank *b)
     kg_lorc_destroy(b->lo.obj);
     kg_fax_destroy(b->fa.obj);
     kg_cw_destroy(b->cw.obj);
+    kg_wspr_destroy(b->ws.obj);
     kg_adpcm_destroy(b->adpcm); kg_post_destroy(b->post); kg_fir_destroy(b->nullfir); kg_fir_destroy(b->fir); kg_rxddc_destroy(b->rx); kg_nb_destroy(b->nb);
     kg_wf_destroy(b->wf); kg_ddc_destroy(b->ddc);
     kg_ctx_destroy(b->c_tail); kg_ctx_destroy(b->c_side); kg_ctx_destroy(b->c_main);
@@ -1559,6 +1660,54 @@ int kg_rxbank_cw_set_now(kg_rxbank *b, uint32_t now_sec)
 }
 
 kg_cw *kg_rxbank_cw(kg_rxbank *b) { return b ? b->cw.obj : nullptr; }
+
+int kg_rxbank_wspr_init(kg_rxbank *b, int rx, double snd_rate) { BANK_EXT("kg_rxbank_wspr_init", bank_ws_ensure); return kg_wspr_init(b->ws.obj, rx, snd_rate); }
+
+int kg_rxbank_wspr_set_capture(kg_rxbank *b, int rx, int capture)
+{
+    BANK_EXT("kg_rxbank_wspr_set_capture", bank_ws_ensure);
+    if (capture) KG_TRY(bank_tap_free_for_wspr(b, rx, "kg_rxbank_wspr_set_capture"));
+    KG_TRY(kg_wspr_set_capture(b->ws.obj, rx, capture));
+    b->ws.on[rx] = capture ? 1 : 0;
+    return KG_OK;
+}
+
+int kg_rxbank_wspr_set_type(kg_rxbank *b, int rx, int type) { BANK_EXT("kg_rxbank_wspr_set_type", bank_ws_ensure); return kg_wspr_set_type(b->ws.obj, rx, type); }
+
+int kg_rxbank_wspr_set_more_candidates(kg_rxbank *b, int rx, int on)
+{
+    BANK_EXT("kg_rxbank_wspr_set_more_candidates", bank_ws_ensure);
+    return kg_wspr_set_more_candidates(b->ws.obj, rx, on);
+}
+
+int kg_rxbank_wspr_set_now(kg_rxbank *b, int minute, int second)
+{
+    KG_REQUIRE(b != nullptr, KG_ERR_INVALID, "kg_rxbank_wspr_set_now: null handle");
+    KG_REQUIRE(minute >= 0 && minute <= 59 && second >= 0 && second <= 59, KG_ERR_INVALID, "kg_rxbank_wspr_set_now: %d:%d (0..59 each)", minute, second);
+    b->ws.min = minute; b->ws.sec = second;     // the plan of every later step copies them into the step's table
+    return KG_OK;
+}
+
+kg_wspr *kg_rxbank_wspr(kg_rxbank *b) { return b ? b->ws.obj : nullptr; }
+
+int kg_rxbank_wspr_out(kg_rxbank *b, uint8_t **d_rows, kg_wspr_cycle **d_cycles, int32_t **d_counts, kg_wspr_row *row_map, int max_rows, int32_t *nrows,
+                       kg_wspr_ev *evs, int max_events, int32_t *nevents, int32_t *rx_of_entry, int max_entries)
+{
+    KG_REQUIRE(b != nullptr && max_rows >= 0 && max_events >= 0 && max_entries >= 0, KG_ERR_INVALID, "kg_rxbank_wspr_out: bad argument");
+    const bank_ws &x = b->ws;
+    KG_REQUIRE(!row_map || max_rows >= x.last.n, KG_ERR_INVALID, "kg_rxbank_wspr_out: %d rows, room for %d", x.last.n, max_rows);
+    KG_REQUIRE(!evs || max_events >= x.last.ne, KG_ERR_INVALID, "kg_rxbank_wspr_out: %d events, room for %d", x.last.ne, max_events);
+    KG_REQUIRE(!rx_of_entry || max_entries >= x.last.nent, KG_ERR_INVALID, "kg_rxbank_wspr_out: %d entries, room for %d", x.last.nent, max_entries);
+    if (d_rows) *d_rows = x.d_rows.p;
+    if (d_cycles) *d_cycles = x.d_cycles.p;
+    if (d_counts) *d_counts = x.d_counts.p;
+    if (row_map && x.last.n) memcpy(row_map, x.last.rows.data(), sizeof(kg_wspr_row) * (size_t) x.last.n);
+    if (evs && x.last.ne) memcpy(evs, x.last.evs.data(), sizeof(kg_wspr_ev) * (size_t) x.last.ne);
+    if (nrows) *nrows = x.last.n;
+    if (nevents) *nevents = x.last.ne;
+    for (int e = 0; rx_of_entry && e < x.last.nent; e++) rx_of_entry[e] = x.last.rx[e];
+    return x.last.nent;
+}
 
 int kg_rxbank_cw_out(kg_rxbank *b, kg_cw_ev **d_evs, int32_t **d_counts, int32_t *max_events, int32_t *rx_of_entry, int max_entries)
 {

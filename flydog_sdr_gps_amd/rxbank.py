@@ -436,6 +436,57 @@ class RxBank:
         """what timer_sec() answers during every later step"""
         check(self.lib.kg_rxbank_cw_set_now(self.h, int(now_sec) & 0xffffffff), "kg_rxbank_cw_set_now")
 
+    # ---- the WSPR extension, stage 1 (extensions/wspr/wspr_main.cpp, wspr.cpp): kg_wspr's commands per receiver
+    def wspr_init(self, rx, snd_rate=12000.0):
+        """`SET ext_server_init`; int_decimate = (int) (snd_rate / 375.0)"""
+        check(self.lib.kg_rxbank_wspr_init(self.h, int(rx), float(snd_rate)), "kg_rxbank_wspr_init")
+
+    def wspr_set_capture(self, rx, capture):
+        """`SET capture=`; on, refused while the IQ display runs or Loran-C is started on the receiver (the IQ tap holds one callback)"""
+        check(self.lib.kg_rxbank_wspr_set_capture(self.h, int(rx), int(capture)), "kg_rxbank_wspr_set_capture")
+
+    def wspr_set_type(self, rx, wspr_type):
+        check(self.lib.kg_rxbank_wspr_set_type(self.h, int(rx), int(wspr_type)), "kg_rxbank_wspr_set_type")
+
+    def wspr_set_more_candidates(self, rx, on):
+        check(self.lib.kg_rxbank_wspr_set_more_candidates(self.h, int(rx), int(on)), "kg_rxbank_wspr_set_more_candidates")
+
+    def wspr_set_now(self, minute, second):
+        """what utc_hour_min_sec answers during every later step"""
+        check(self.lib.kg_rxbank_wspr_set_now(self.h, int(minute), int(second)), "kg_rxbank_wspr_set_now")
+
+    @property
+    def wspr(self):
+        """the bank's Wspr (None until one of the per-receiver wspr_* commands was sent): state()"""
+        from . import wspr as ws
+        h = self.lib.kg_rxbank_wspr(self.h)
+        return borrow(ws.Wspr, self.ctx, h, nconn=self.nrx) if h else None
+
+    def wspr_out(self):
+        """-> (rows [n, 412] uint8, row map of wspr.row_dtype -- conn the receiver, blk the sound block of the step --, events of
+        wspr.ev_dtype, {receiver: cycle record} of the receivers whose cycle ended, {receiver: counts [4]}) of the last step (after sync())"""
+        from . import wspr as ws
+        m, ev, rxs = np.zeros(self.nrx * 256, ws.row_dtype), np.zeros(self.nrx * 16, ws.ev_dtype), np.zeros(self.nrx, np.int32)
+        d_rows, d_cyc, d_cnt, n, ne = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int32(), C.c_int32()
+        nent = check(self.lib.kg_rxbank_wspr_out(self.h, C.byref(d_rows), C.byref(d_cyc), C.byref(d_cnt), ptr(m), int(m.size), C.byref(n), ptr(ev), int(ev.size),
+                                                 C.byref(ne), ptr(rxs), int(rxs.size)), "kg_rxbank_wspr_out")
+        rows = np.zeros((n.value, ws.NBINS + 1), np.uint8)
+        cycles, counts = {}, {}
+        if nent:
+            cy, cn = np.zeros(nent, ws.cycle_dtype), np.zeros((nent, 4), np.int32)
+            self.ctx.download(int(d_cyc.value), cy)
+            self.ctx.download(int(d_cnt.value), cn)
+            for e in range(nent):
+                counts[int(rxs[e])] = cn[e].copy()
+                if cy[e]["due"]:
+                    cycles[int(rxs[e])] = cy[e].copy()
+        if n.value:
+            slots = np.zeros((n.value, ws.ROW_STRIDE), np.uint8)
+            self.ctx.download(int(d_rows.value), slots)
+            assert not slots[:, ws.NBINS + 1:].any()
+            rows[:] = slots[:, :ws.NBINS + 1]
+        return rows, m[:n.value].copy(), ev[:ne.value].copy(), cycles, counts
+
     @property
     def cw(self):
         """the bank's CwDecoder (None until one of the per-receiver cw_* commands was sent): state()"""

@@ -1544,6 +1544,80 @@ int kg_cw_push(kg_cw *q, const int32_t *conns, int nconn, const int32_t *nblk, c
 /* Connection conn's whole object (:106-174), for tests: the scalars, the ring and data[].  Synchronises. */
 int kg_cw_state(kg_cw *q, int conn, kg_cw_info *info);
 
+/* ---- The WSPR extension, stage 1 (extensions/wspr/wspr_main.cpp, wspr.cpp): from the IQ tap (receive_iq_samps: CFastFIR's output of
+ * every sound block) to the candidate list.  Capture with drop-sample decimation to 375 Hz into two ping-pong halves synchronised to the
+ * even minute (wspr_data, wspr_main.cpp:595-788); per group of four half-symbol steps the windowed 512-point transforms, pwr_samp,
+ * pwr_sampavg, savg and the display row of 412 bytes (WSPR_FFT, :117-240, renormalize, wspr.cpp:214-253); at the end of a cycle pass 0
+ * of wspr_decode: the peak list (wspr.cpp:555-628) and the coarse search over frequency, time and drift (wspr.cpp:658-714).
+ * csrc/kg_wspr.h is the one definition for device and host, in the reference's operand types, and cites the reference item by item.
+ * Not in this stage: sync_and_demodulate and everything behind it (the decoders, the hash table, subtraction, later passes),
+ * abort_decode, autorun / IWBP, uploads, the test-file player.  i_data / q_data of both halves stay on the device for them.
+ *
+ * The SCHEDULE depends on no sample: the host walks a push block by block and the kernels get a table; the status changes
+ * (wspr_status, :96-114) come out as event records.  TIME IS AN INPUT: every block of a push carries the minute and second that
+ * utc_hour_min_sec (:629) would have answered for its callback.  No host clock is read.
+ * What passes through the transform (pwr_samp, pwr_sampavg, the rows) is held to a bound, everything from the planes on -- peaks and
+ * candidates -- is an exact function of them.  The outputs carry counts the DEVICE writes: for entry i of the list
+ *   counts[4*i]  rows written;  counts[4*i + 1]  1 if a cycle ended;  counts[4*i + 2]  its peaks;  cycles[i]  the cycle end (due 0: none)
+ * Defined here where the reference leaves it open: the decoder of this stage takes no time (a cycle end's events are DECODING, PEAKS,
+ * then status_resume); a row byte whose y is NaN (silence) is 0 and such a cycle has no peaks; ties in snr0 keep frequency order; memory
+ * handed out is zeros.  Refused with nothing changed: snd_rate below 375 or not finite, a type other than 2 / 15, a minute or second
+ * outside 0 .. 59, a push before kg_wspr_init (KG_ERR_STATE), a push in which one connection completes two cycles. */
+typedef struct kg_wspr kg_wspr;
+#define KG_WSPR_NBINS 411                                  /* nbins_411, wspr_main.cpp:1155 */
+#define KG_WSPR_NFFT 512                                   /* NFFT, wspr.h:160 */
+#define KG_WSPR_NT 348                                     /* FPG*GROUPS, wspr.h:225 */
+#define KG_WSPR_TPOINTS 45000                              /* wspr.h:147 */
+#define KG_WSPR_MAX_NPK 12                                 /* wspr.h:183 */
+#define KG_WSPR_ROW_STRIDE 416                             /* a row's 412 bytes (WSPR_DATA, :238) start at multiples of this */
+enum { KG_WSPR_IDLE = 1, KG_WSPR_SYNC = 2, KG_WSPR_RUNNING = 3, KG_WSPR_DECODING = 4 };            /* wspr_main.cpp:49-53 */
+enum { KG_WSPR_EV_STATUS = 0, KG_WSPR_EV_PEAKS = 1 };
+typedef struct kg_wspr_row {               /* one ext_send_msg_data of :238 */
+    int32_t conn, blk, samp;               /* the block of the push and the sample of it at which the group was due */
+    int32_t group, half, tsync;            /* FFTtask_group, fft_ping_pong, byte 0 */
+    int64_t off;                           /* of the row in the byte array */
+} kg_wspr_row;
+typedef struct kg_wspr_ev {                /* STATUS: a the status, b the resume (0: NONE), `EXT WSPR_STATUS=` (:106); PEAKS: a the half, `WSPR_PEAKS` (:299) */
+    int32_t conn, blk, samp, kind, a, b;   /* blk -1: sent by a command since the last push */
+} kg_wspr_ev;
+typedef struct kg_wspr_pk { int32_t bin0; float freq0, snr0; int32_t pad; } kg_wspr_pk;            /* frequency order, wspr.cpp:612-624 */
+typedef struct kg_wspr_cand { float freq0; int32_t shift0; float drift0, sync0; int32_t freq_idx, bin0; } kg_wspr_cand;    /* SNR order, wspr.cpp:627, :701-705 */
+typedef struct kg_wspr_cycle { int32_t due, half, npk, pad; kg_wspr_pk pk[KG_WSPR_MAX_NPK]; kg_wspr_cand cand[KG_WSPR_MAX_NPK]; } kg_wspr_cycle;
+typedef struct kg_wspr_info {              /* wspr_t (wspr.h:239-312), what this stage keeps of it */
+    int32_t inited, capture, reset, tsync, ping_pong, fft_ping_pong, decode_ping_pong, decim, didx, group;
+    int32_t status, status_resume, last_sec, abort_decode, wspr_type, more_candidates, int_decimate, cycles;
+    double snd_rate;
+} kg_wspr_info;
+/* nconn wspr_t / wspr_buf_t pairs (wspr.h:223-312), zeroed as wspr_main does (:1163), and the window of :1186-1188; 1 .. 256 */
+int kg_wspr_create(kg_ctx *ctx, int nconn, kg_wspr **out);
+/* wspr_close (:802-824) frees nothing of them; drains the context's stream first */
+void kg_wspr_destroy(kg_wspr *q);
+/* `SET ext_server_init` (:834-838): status IDLE; int_decimate = (int) (snd_rate / 375.0) as wspr_main has it (:1193), per connection */
+int kg_wspr_init(kg_wspr *q, int conn, double snd_rate);
+/* `SET capture=%d` (:880-900): on, a reset at the next callback and status SYNC; off, wspr_close with wspr_reset (:790-800) */
+int kg_wspr_set_capture(kg_wspr *q, int conn, int capture);
+/* wspr_type (wspr.h:255-257, set by wspr_main, :1170): 2 or 15; it selects snr_scaling_factor (wspr.cpp:247) */
+int kg_wspr_set_type(kg_wspr *q, int conn, int type);
+/* more_candidates (wspr.h:254, read at wspr.cpp:565) */
+int kg_wspr_set_more_candidates(kg_wspr *q, int conn, int on);
+/* wspr_data (:595-788) for nblk[i] callbacks (0 .. 4096) of ns complex samples (1 .. 131072) of connection conns[i] (each at most once),
+ * on HOST arrays: block b of entry i is at iq + 2*(i*iq_stride + ns*b), its time at minute / second[i*time_stride + b].  Rows go to
+ * rows + row_map[r].off (412 bytes each), in the order the reference sends them; events in order per entry, entries in list order.
+ * ONE kernel launch, and one more when a cycle ends.  Synchronises. */
+int kg_wspr_push(kg_wspr *q, const int32_t *conns, int nconn, const int32_t *nblk, int ns, const float *iq, size_t iq_stride, const int32_t *minute,
+                 const int32_t *second, size_t time_stride, uint8_t *rows, size_t rows_cap, kg_wspr_row *row_map, int max_rows, int32_t *nrows, kg_wspr_ev *evs,
+                 int max_events, int32_t *nevents, kg_wspr_cycle *cycles, int32_t *counts);
+/* The schedule of kg_wspr_push (:595-788) walked on copies: how many ops (copy runs, clears, groups), rows, events and cycle ends the
+ * push will emit (any may be NULL).  Changes nothing, touches no device. */
+int kg_wspr_plan(kg_wspr *q, const int32_t *conns, int nconn, const int32_t *nblk, int ns, const int32_t *minute, const int32_t *second, size_t time_stride,
+                 int32_t *nops, int32_t *nrows, int32_t *nevents, int32_t *ncycles);
+/* Connection conn's object (wspr.h:223-312), for tests and for a host that saves it: the scalars, pwr_sampavg [2][512], pwr_samp
+ * [2][512][348] and i_data then q_data [2][2][45000], each as the reference lays it out (any may be NULL).  Synchronises. */
+int kg_wspr_state(kg_wspr *q, int conn, kg_wspr_info *info, float *pwr_sampavg, float *pwr_samp, float *iq_data);
+/* For a host that resumes, and for tests: pwr_samp [512][348] and pwr_sampavg [512] placed into a half, then the cycle end on it (pass 0
+ * of wspr_decode, wspr.cpp:555-714) under the connection's type and more_candidates.  One launch.  Synchronises. */
+int kg_wspr_load(kg_wspr *q, int conn, int half, const float *pwr_samp, const float *pwr_sampavg, kg_wspr_cycle *cycle);
+
 /* Diagnostics: re-runs the 4096-point stage of the forward FFT of `block` in a
  * stamped build of the kernel and returns 4 s_memrealtime readings (100 MHz):
  * start, inputs + twiddles loaded, transform done, results stored. */
@@ -1793,6 +1867,32 @@ kg_cw *kg_rxbank_cw(kg_rxbank *bank);
  * (NULL until the extension was named; read behind kg_rxbank_sync): entry e is receiver rx_of_entry[e], in receiver order; an event's
  * blk is the sound block of the step.  Any pointer may be NULL.  Returns the number of entries: the receivers the step fed. */
 int kg_rxbank_cw_out(kg_rxbank *bank, kg_cw_ev **d_evs, int32_t **d_counts, int32_t *max_events, int32_t *rx_of_entry, int max_entries);
+
+/* The WSPR extension of the bank's receivers, stage 1 (kg_wspr above; extensions/wspr/wspr_main.cpp, wspr.cpp).  The first of the
+ * per-receiver calls makes the bank's kg_wspr object and its output buffers, grows the step's arena slots by the size of the extension's
+ * table and drains the bank's streams; a bank that was never told holds nothing for it.  A refusal at first use leaves the bank as it was.
+ * WSPR is the third consumer of the IQ tap (ext_register_receive_iq_samps, wspr_main.cpp:891): while a receiver captures and is not in
+ * NBFM, the step's CFastFIR output feeds it in place -- ONE launch per step, and the cycle-end launch behind it when a receiver
+ * completes group 85, on the tail stream ahead of the step's end.  The tap holds ONE callback: kg_rxbank_wspr_set_capture(1) beside a
+ * running IQ display or a started Loran-C is refused (KG_ERR_STATE), and they are refused beside it.  Join and leave give the receiver
+ * a fresh object. */
+/* `SET ext_server_init` (wspr_main.cpp:834-838): kg_wspr_init */
+int kg_rxbank_wspr_init(kg_rxbank *bank, int rx, double snd_rate);
+/* `SET capture=%d` (wspr_main.cpp:880-900): kg_wspr_set_capture; on, it takes the IQ tap */
+int kg_rxbank_wspr_set_capture(kg_rxbank *bank, int rx, int capture);
+/* wspr_type (wspr.h:255-257): kg_wspr_set_type */
+int kg_rxbank_wspr_set_type(kg_rxbank *bank, int rx, int type);
+/* more_candidates (wspr.h:254): kg_wspr_set_more_candidates */
+int kg_rxbank_wspr_set_more_candidates(kg_rxbank *bank, int rx, int on);
+/* what utc_hour_min_sec (wspr_main.cpp:629) answers during every later step: all blocks of a step carry it.  0 .. 59 each */
+int kg_rxbank_wspr_set_now(kg_rxbank *bank, int minute, int second);
+/* the object (NULL until one of the per-receiver calls above), for kg_wspr_state (wspr.h:223-312) */
+kg_wspr *kg_rxbank_wspr(kg_rxbank *bank);
+/* The outputs of the last step (wspr_main.cpp:106, :238, :299): the rows' device buffer (row r at row_map[r].off, conn the receiver, blk the
+ * sound block of the step), the cycles and counts of every list entry as kg_wspr_push lays them out, device memory valid until the next
+ * step; the row map and the events, which are the host's; the receivers of the entries.  Any may be NULL.  Returns the entries. */
+int kg_rxbank_wspr_out(kg_rxbank *bank, uint8_t **d_rows, kg_wspr_cycle **d_cycles, int32_t **d_counts, kg_wspr_row *row_map, int max_rows, int32_t *nrows,
+                       kg_wspr_ev *evs, int max_events, int32_t *nevents, int32_t *rx_of_entry, int max_entries);
 /* CmdSetWFFreq + CmdSetWFDecim + the sampler mode sample_wf() decides on (rx/rx_waterfall.cpp:962-1008):
  *   overlapped == 0   CmdWFReset + the one-shot sampler every step: the non-overlapped frame (:1005-1041); needs
  *                     8192 * decim <= adc_samples_per_step
