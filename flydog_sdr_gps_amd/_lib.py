@@ -409,6 +409,19 @@ SYMBOLS = {
     "kg_acq_debug_corr_stamps": (_i, [_vp, _i, _vp, _i, _vp, _i]),
 }
 
+# include/kiwigpu_wspr_dec.h (stage 2 of the WSPR extension; kiwigpu.h includes it)
+WSPR_DEC_SYMBOLS = {
+    "kg_wspr_set_metric_table": (_i, [_vp, _vp]),
+    "kg_wspr_load_iq": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i]),
+    "kg_wspr_decode": (_i, [_vp, _vp, _i, C.c_uint32, _i, _i, _vp, _vp]),
+    "kg_wspr_fano": (_i, [_vp, _vp, _i, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
+    "kg_wspr_set_decode": (_i, [_vp, _i, _i]),
+    "kg_wspr_decodes": (_i, [_vp, _i, _vp, _vp]),
+    "kg_rxbank_wspr_set_metric_table": (_i, [_vp, _vp]),
+    "kg_rxbank_wspr_set_decode": (_i, [_vp, _i, _i]),
+    "kg_rxbank_wspr_dec_out": (_i, [_vp, _vp, _vp, _vp, _i]),
+}
+
 
 def _share_hip_runtime_with_torch():
     """PyTorch-ROCm wheels carry their own libamdhip64 / libhsa-runtime64.  Two HIP runtimes in one
@@ -443,7 +456,7 @@ def load_library():
                            "CPU fallback" % path)
     _share_hip_runtime_with_torch()
     lib = C.CDLL(path)
-    for name, (res, args) in SYMBOLS.items():
+    for name, (res, args) in list(SYMBOLS.items()) + list(WSPR_DEC_SYMBOLS.items()):
         fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -282,6 +282,9 @@ __attribute__((visibility("hidden"))) int kg_wspr_push_rows_(kg_wspr *q, const i
                                                              int max_events, int32_t *nevents, kg_wspr_cycle *d_cycles, int32_t *d_counts);
 __attribute__((visibility("hidden"))) size_t kg_wspr_table_bytes_(size_t nconn, size_t ops_per_conn);
 __attribute__((visibility("hidden"))) int kg_wspr_reset_(kg_wspr *q, int conn);
+// stage 2: the device records and counts of the pushes' pass 0, [connection][12] and [connection]; whether a connection's decode is on
+__attribute__((visibility("hidden"))) void kg_wspr_dec_buffers_(kg_wspr *q, kg_wspr_dec **d_decs, int32_t **d_ncand);
+__attribute__((visibility("hidden"))) int kg_wspr_decode_on_(const kg_wspr *q, int conn);
 
 // kg_post.hip, for kg_rxbank.hip: how many kg_post_set_mode / kg_post_set_sam_mparam calls channel ch has seen (each clears
 // s->isChanNull, rx_sound_cmd.cpp:202-228), and its s->SAM_mparam

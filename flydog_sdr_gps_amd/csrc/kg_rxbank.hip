@@ -1709,6 +1709,38 @@ int kg_rxbank_wspr_out(kg_rxbank *b, uint8_t **d_rows, kg_wspr_cycle **d_cycles,
     return x.last.nent;
 }
 
+// ---- WSPR stage 2: the table, pass 0 behind a step's cycle end, its records
+int kg_rxbank_wspr_set_metric_table(kg_rxbank *b, const int32_t mettab[2][256])
+{
+    KG_REQUIRE(b != nullptr, KG_ERR_INVALID, "kg_rxbank_wspr_set_metric_table: null handle");
+    KG_TRY(bank_ws_ensure(b));
+    return kg_wspr_set_metric_table(b->ws.obj, mettab);
+}
+
+int kg_rxbank_wspr_set_decode(kg_rxbank *b, int rx, int on) { BANK_EXT("kg_rxbank_wspr_set_decode", bank_ws_ensure); return kg_wspr_set_decode(b->ws.obj, rx, on); }
+
+int kg_rxbank_wspr_dec_out(kg_rxbank *b, kg_wspr_dec **d_decs, int32_t **d_ncand, int32_t *rx_decoded, int max_rx)
+{
+    KG_REQUIRE(b != nullptr && max_rx >= 0, KG_ERR_INVALID, "kg_rxbank_wspr_dec_out: bad argument");
+    const bank_ws &x = b->ws;
+    if (d_decs) *d_decs = nullptr;
+    if (d_ncand) *d_ncand = nullptr;
+    if (!x.obj) return 0;                                               // never told
+    kg_wspr_dec *dd = nullptr;
+    int32_t *dn = nullptr;
+    kg_wspr_dec_buffers_(x.obj, &dd, &dn);
+    if (d_decs) *d_decs = dd;
+    if (d_ncand) *d_ncand = dn;
+    int n = 0;
+    for (int e = 0; e < x.last.ne; e++)
+        if (x.last.evs[e].kind == KG_WSPR_EV_DECODES) {
+            KG_REQUIRE(!rx_decoded || n < max_rx, KG_ERR_INVALID, "kg_rxbank_wspr_dec_out: more than %d receivers decoded", max_rx);
+            if (rx_decoded) rx_decoded[n] = x.last.evs[e].conn;
+            n++;
+        }
+    return n;
+}
+
 int kg_rxbank_cw_out(kg_rxbank *b, kg_cw_ev **d_evs, int32_t **d_counts, int32_t *max_events, int32_t *rx_of_entry, int max_entries)
 {
     KG_REQUIRE(b != nullptr && max_entries >= 0, KG_ERR_INVALID, "kg_rxbank_cw_out: bad argument");

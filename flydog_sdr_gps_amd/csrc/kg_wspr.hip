@@ -18,12 +18,16 @@
 // pki searches candidate pki: the ROOTS of the 16 x 343 powers the candidate's hypotheses can touch are formed once into LDS (21 KB),
 // ifd of :678 -- which depends on no sample -- once per (ifr, idrift, symbol) into LDS (7 KB),
 // the 1440 hypotheses go over the 256 lanes, each lane sums its 162 symbols in order k = 0 .. 161, and the first maximum in the order
-// ifr, k0, idrift wins by a reduction on (sync1, hypothesis index).
+// ifr, k0, idrift wins by a reduction on (sync1, hypothesis index).  It also leaves the candidates with the object, for stage 2.
+//
+// Stage 2 (csrc/kg_wspr_dec.h: fine sync, soft symbols, the Fano decoder; kg_wspr_decode) is described above its kernels below.
 #include "kg_ext.h"
 #include "kg_fft.h"
 #include "kg_wspr.h"
+#include "kg_wspr_dec.h"
 
 using namespace kg_wspr_cf;
+namespace wd = kg_wspr_df;
 
 static_assert(sizeof(kg_wspr_row) == 32 && sizeof(kg_wspr_ev) == 24 && sizeof(kg_wspr_pk) == 16 && sizeof(kg_wspr_cand) == 24 && sizeof(kg_wspr_cycle) == 496 &&
               sizeof(kg_wspr_info) == 80, "kg_wspr_* layout");
@@ -45,6 +49,8 @@ struct ws_entry { int32_t conn, first, nops, type, dec, pad; int64_t in_off; };
 struct ws_op { int32_t kind, half, a, b, n, pad; int64_t src, row_off; };
 struct ws_cyc { int32_t conn, half, type, more, slot, pad[3]; };
 static_assert(sizeof(ws_entry) == 32 && sizeof(ws_op) == 40 && sizeof(ws_cyc) == 32, "table layout");
+// what stage 2 reads of a connection's last cycle end: the candidates in SNR order, the decode half, and p->ignore (wspr.h:190) per candidate
+struct wd_hold { int32_t ncand, half; int32_t ignore[MAX_NPK]; kg_wspr_cand cand[MAX_NPK]; };
 
 __device__ __constant__ const unsigned char ws_pr3[NSYM] = KG_WSPR_PR3;
 
@@ -154,7 +160,7 @@ __global__ __launch_bounds__(WS_THREADS) void wspr_push_kernel(const ws_entry *_
 }
 
 __global__ __launch_bounds__(WS_THREADS) void wspr_cycle_kernel(const ws_cyc *__restrict__ tab, const ws_dev *__restrict__ dev, kg_wspr_cycle *out, int32_t *counts,
-                                                                float min_snr)
+                                                                float min_snr, wd_hold *hold)
 {
     __shared__ float s_avg[NFFT];
     __shared__ float s_raw[NBINS + 5], s_sm[NBINS + 5];
@@ -182,6 +188,7 @@ __global__ __launch_bounds__(WS_THREADS) void wspr_cycle_kernel(const ws_cyc *__
     const int npk = s_npk;
     if (pki == 0) {
         if (tid == 0) { res->due = 1; res->half = e.half; res->npk = npk; res->pad = 0; counts[4 * e.slot + 1] = 1; counts[4 * e.slot + 2] = npk; }
+        if (tid == 0) { hold[e.conn].ncand = npk; hold[e.conn].half = e.half; }
         if (tid < MAX_NPK) {
             pk_t z = {0, 0.0f, 0.0f, 0};
             const pk_t v = tid < npk ? s_pk[tid] : z;
@@ -189,7 +196,7 @@ __global__ __launch_bounds__(WS_THREADS) void wspr_cycle_kernel(const ws_cyc *__
         }
     }
     if (pki >= npk) {
-        if (tid == 0) { kg_wspr_cand z = {0.0f, 0, 0.0f, 0.0f, 0, 0}; res->cand[pki] = z; }
+        if (tid == 0) { kg_wspr_cand z = {0.0f, 0, 0.0f, 0.0f, 0, 0}; res->cand[pki] = z; hold[e.conn].cand[pki] = z; hold[e.conn].ignore[pki] = 0; }
         return;
     }
     const int if0 = if0_of(s_cand[pki].freq0);                          // wspr.cpp:665: before the loops overwrite freq0
@@ -229,12 +236,280 @@ __global__ __launch_bounds__(WS_THREADS) void wspr_cycle_kernel(const ws_cyc *__
         if (s_besth[0] >= 0) take_hyp(c, s_besth[0], if0, s_best[0]);
         kg_wspr_cand o = {c.freq0, c.shift0, c.drift0, c.sync0, c.freq_idx, c.bin0};
         res->cand[pki] = o;
+        hold[e.conn].cand[pki] = o;                                     // stage 2 starts from here, with ignore clear (wspr.cpp:560: the memset)
+        hold[e.conn].ignore[pki] = 0;
     }
+}
+
+// ---- stage 2 (csrc/kg_wspr_dec.h is the one definition of its arithmetic): one pass of wspr_decode's candidate loop (wspr.cpp:733-883)
+// over the held candidates of the listed connections, as a chain of launches on the context's stream with no host read between them:
+//   begin    a slot per (list entry, candidate): the held estimates, or inactive (no such candidate, or p->ignore set);
+//   six times corr + pick -- the refinement calls of :759-805 -- then corr + soft for ALL jiggles of :819-867 at once, fano, finish.
+// corr: one workgroup per (symbol, slot).  The symbol's span of i_data / q_data over every lag of the call goes to LDS once (at most 512
+// samples); a lane owns a (tone, hypotheses) pair: it seeds the tone's recurrence (kg_libm_dtrig.h), runs its 255 steps ONCE and adds
+// every sample into the float sums of its hypotheses -- the 5 lags of a lag call, or 5 neighbouring jiggles (their samples lie iifac
+// apart in LDS); a frequency call's hypotheses differ in the recurrence itself: one each.  The tone's root power goes to the workspace
+// [slot][hypothesis][symbol][tone] in double.  pick / soft: a lane per hypothesis sums its 162 symbols IN SYMBOL ORDER (totp in
+// double, ss in float: the order is part of the result, no tree), lane 0 takes the first maximum in the order of the reference's loops
+// and moves the slot's estimates on; soft makes every jiggle's bytes, rms and gate.  fano: a lane per (slot, jiggle) that passed the
+// gate, 32 lanes a workgroup, the 82 nodes of a lane in LDS as [node][lane] words (a lane keeps to its bank; 52 KB a workgroup), the
+// branch metrics formed from the symbols and the table (LDS too) where they are needed.  finish: a lane per slot walks the jiggles in
+// the reference's order idt = 0, 1, 2 ... to the first whose fano run succeeded and writes the record of that SEQUENTIAL loop.
+enum { WD_THREADS = 128, WD_NL = 5, WD_SPAN = 512, WD_SOFT_THREADS = 192, WD_FANO_LANES = 32, WD_CALL_SOFT = 6, WD_MAX_FANO = 4096 };
+static_assert(sizeof(wd::rec_t) == sizeof(kg_wspr_dec) && wd::MAX_IDT <= WD_SOFT_THREADS && (wd::MAX_IDT + WD_NL - 1) / WD_NL * 4 <= WD_THREADS, "stage 2 shapes");
+static_assert(KG_WSPR_SKIPPED == wd::R_SKIPPED && KG_WSPR_MINSYNC1 == wd::R_MINSYNC1 && KG_WSPR_NO_CHANGE == wd::R_NO_CHANGE && KG_WSPR_TIME_UP == wd::R_TIME_UP &&
+              KG_WSPR_DECODED == wd::R_DECODED && KG_WSPR_QUICK_MISS == wd::R_QUICK_MISS, "result classes");
+
+struct wd_slot {                                                        // one candidate's chain
+    int32_t conn, pki, half, exists, skipped, active, minsync_ok, pad;  // active: the next call runs; cleared where minsync1 fails
+    float f1; int32_t shift1; float drift1, sync1, syncp, syncm;
+    float tr_f[wd::NCALLS]; int32_t tr_shift[wd::NCALLS]; float tr_sync[wd::NCALLS];
+};
+struct wd_jig { float sync, rms; int32_t gate, pad; uint8_t sym[164]; };
+struct wd_fano { int32_t ok; uint32_t metric, cycles, maxnp; uint8_t data[12]; };
+// the hypotheses of call c: how many, whether they differ in frequency (else in lag), fstep, the first lag and the lag step, the drift's offset
+struct wd_call { int32_t nh, freq; float fstep; int32_t lag0, stride; float ddrift; };
+__device__ __forceinline__ wd_call wd_call_of(int call, const wd_slot &sl, int iifac, int nidt)
+{
+    switch (call) {
+    case 0: return wd_call{5, 0, 0.0f, sl.shift1 - 128, 64, 0.0f};      // :759-764
+    case 1: return wd_call{5, 1, 0.25f, sl.shift1, 0, 0.0f};            // :766-768
+    case 2: return wd_call{1, 1, 0.0f, sl.shift1, 0, 0.5f};             // :771-775
+    case 3: return wd_call{1, 1, 0.0f, sl.shift1, 0, -0.5f};            // :777-779
+    case 4: return wd_call{5, 0, 0.0f, sl.shift1 - 32, 16, 0.0f};       // :798-800
+    case 5: return wd_call{5, 1, 0.05f, sl.shift1, 0, 0.0f};            // :803-805
+    default: return wd_call{nidt, 0, 0.05f, sl.shift1 - (nidt / 2) * iifac, iifac, 0.0f};     // :819-828, sorted by lag
+    }
+}
+__device__ __forceinline__ float wd_drift_of(const wd_slot &sl, const wd_call &c)
+{
+    const float d = c.ddrift > 0.0f ? sl.drift1 + 0.5 : c.ddrift < 0.0f ? sl.drift1 - 0.5 : sl.drift1;     // :773, :777
+    return d;
+}
+// the jiggle step idt whose lag is the h-th smallest: m = h - nidt / 2 steps of iifac; an odd idt is the negative side (:820-822)
+__device__ __forceinline__ int wd_idt_of_sorted(int h, int nidt) { const int m = h - nidt / 2; return m > 0 ? 2 * m : m < 0 ? -2 * m - 1 : 0; }
+
+__global__ void wspr_dec_begin_kernel(const int32_t *__restrict__ conns, int nslots, const wd_hold *__restrict__ hold, wd_slot *slots)
+{
+    const int s = (int) (blockIdx.x * blockDim.x + threadIdx.x);
+    if (s >= nslots) return;
+    const int conn = conns[s / MAX_NPK], pki = s % MAX_NPK;
+    const wd_hold &h = hold[conn];
+    wd_slot sl;
+    memset(&sl, 0, sizeof sl);
+    sl.conn = conn; sl.pki = pki; sl.half = h.half & 1;
+    sl.exists = pki < h.ncand;
+    sl.skipped = sl.exists && h.ignore[pki] != 0;                       // :740
+    sl.active = sl.exists && !sl.skipped;
+    const kg_wspr_cand c = h.cand[pki];
+    sl.f1 = c.freq0; sl.shift1 = c.shift0; sl.drift1 = c.drift0; sl.sync1 = c.sync0;                         // :745-749
+    slots[s] = sl;
+}
+
+template <int NL>
+__global__ __launch_bounds__(WD_THREADS) void wspr_corr_kernel(const wd_slot *__restrict__ slots, const ws_dev *__restrict__ dev, double *pw, int call, int iifac, int nidt)
+{
+    __shared__ float s_i[WD_SPAN], s_q[WD_SPAN];
+    const wd_slot sl = slots[blockIdx.y];
+    if (!sl.active) return;                                             // the whole workgroup
+    const wd_call c = wd_call_of(call, sl, iifac, nidt);
+    const int i = (int) blockIdx.x, tid = (int) threadIdx.x, tone = tid & 3, grp = tid >> 2;
+    const int k0 = c.lag0 + i * SPS;                                    // the first sample of the span
+    const int len = (c.nh - 1) * c.stride + SPS;                        // <= 512: 4 * 64 + 256, 128 + 256
+    const ws_dev *d = dev + sl.conn;
+    for (int t = tid; t < len && t < WD_SPAN; t += WD_THREADS) {
+        const int k = k0 + t;
+        const bool in = k >= 0 && k < TPOINTS;
+        s_i[t] = in ? d->idat[sl.half][k] : 0.0f;
+        s_q[t] = in ? d->qdat[sl.half][k] : 0.0f;
+    }
+    __syncthreads();
+    const int h0 = grp * NL;
+    if (h0 >= c.nh) return;
+    const float f0 = wd::f0_of(sl.f1, c.freq ? h0 - c.nh / 2 : 0, c.fstep);                                   // :88; ifreq = -2 .. 2, or 0
+    const float fp = wd::fp_of(f0, wd_drift_of(sl, c), i);
+    double cd, sd, cc = 1, ss = 0;
+    wd::seed_of(wd::dphi_of(fp, tone), &cd, &sd);
+    wd::acc_t ai[NL], aq[NL];
+#pragma unroll
+    for (int l = 0; l < NL; l++) { ai[l] = 0.0; aq[l] = 0.0; }
+    for (int j = 0; j < SPS; j++) {
+        if (j) wd::rot_step(cc, ss, cd, sd);
+#pragma unroll
+        for (int l = 0; l < NL; l++) {
+            const int off = (h0 + l) * c.stride + j;                    // a frequency call: stride 0
+            if (h0 + l < c.nh && wd::k_used(k0 + off, TPOINTS)) wd::acc_step(ai[l], aq[l], s_i[off], s_q[off], cc, ss);
+        }
+    }
+#pragma unroll
+    for (int l = 0; l < NL; l++) {
+        const int h = h0 + l;
+        if (h < c.nh) {
+            const int o = call == WD_CALL_SOFT ? wd_idt_of_sorted(h, nidt) : h;
+            pw[(((size_t) blockIdx.y * wd::MAX_IDT + o) * NSYM + i) * 4 + tone] = wd::p_of(ai[l], aq[l]);
+        }
+    }
+}
+
+// calls 0 .. 5: ss of every hypothesis, the first maximum, and what wspr_decode does with it
+__global__ __launch_bounds__(64) void wspr_pick_kernel(wd_slot *slots, const double *__restrict__ pw, int call)
+{
+    __shared__ float s_ss[8];
+    wd_slot *sp = slots + blockIdx.x;
+    if (!sp->active) return;
+    const wd_slot sl = *sp;
+    const wd_call c = wd_call_of(call, sl, 1, 1);
+    const int h = (int) threadIdx.x;
+    if (h < c.nh) {
+        const double *p = pw + ((size_t) blockIdx.x * wd::MAX_IDT + h) * NSYM * 4;
+        double totp = 0.0;
+        float ss = 0.0;
+        for (int i = 0; i < NSYM; i++) wd::sym_step(totp, ss, p[4 * i], p[4 * i + 1], p[4 * i + 2], p[4 * i + 3], ws_pr3[i]);
+        s_ss[h] = wd::ss_of(ss, totp);
+    }
+    __syncthreads();
+    if (h != 0) return;
+    double syncmax = -1e30;
+    int best = -1;
+    for (int k = 0; k < c.nh; k++)                                      // ifreq outside, lag inside: a call has one of the two
+        if (wd::ss_wins(s_ss[k], syncmax)) { syncmax = s_ss[k]; best = k; }
+    const float sync = syncmax;
+    const float fbest = best < 0 ? 0.0f : wd::f0_of(sl.f1, c.freq ? best - c.nh / 2 : 0, c.fstep);          // :78-79: silence returns 0.0 and 0
+    const int best_shift = best < 0 ? 0 : c.lag0 + best * c.stride;
+    sp->f1 = fbest; sp->shift1 = best_shift;                            // :186-188
+    sp->tr_f[call] = fbest; sp->tr_shift[call] = best_shift; sp->tr_sync[call] = sync;
+    if (call == 2) sp->syncp = sync;
+    else if (call == 3) {
+        sp->syncm = sync;
+        float drift1 = sl.drift1, sync1 = sl.sync1;
+        const float driftp = sl.drift1 + 0.5, driftm = sl.drift1 - 0.5;
+        if (sl.syncp > sync1) { drift1 = driftp; sync1 = sl.syncp; }   // :781-789
+        else if (sync > sync1) { drift1 = driftm; sync1 = sync; }
+        sp->drift1 = drift1; sp->sync1 = sync1;
+        const int ok = sync1 > KG_WSPR_DEC_MINSYNC1;                        // :795
+        sp->minsync_ok = ok;
+        if (!ok) sp->active = 0;                                        // the chain ends here; finish reports MINSYNC1
+    } else sp->sync1 = sync;
+}
+
+// every jiggle of a slot: sync, the bytes, rms, the gate (:826-838)
+__global__ __launch_bounds__(WD_SOFT_THREADS) void wspr_soft_kernel(const wd_slot *__restrict__ slots, const double *__restrict__ pw, wd_jig *jig, int nidt)
+{
+    const int idt = (int) threadIdx.x;
+    if (idt >= wd::MAX_IDT) return;
+    wd_jig *out = jig + (size_t) blockIdx.x * wd::MAX_IDT + idt;
+    if (!slots[blockIdx.x].active || idt >= nidt) { out->gate = 0; return; }
+    const double *p = pw + ((size_t) blockIdx.x * wd::MAX_IDT + idt) * NSYM * 4;
+    double totp = 0.0;
+    float ss = 0.0, fsum = 0.0, f2sum = 0.0;
+    for (int i = 0; i < NSYM; i++) {
+        wd::sym_step(totp, ss, p[4 * i], p[4 * i + 1], p[4 * i + 2], p[4 * i + 3], ws_pr3[i]);
+        wd::norm_step(fsum, f2sum, wd::fsymb_of(p[4 * i], p[4 * i + 1], p[4 * i + 2], p[4 * i + 3], ws_pr3[i]));
+    }
+    ss = wd::ss_of(ss, totp);
+    const float sync = wd::ss_wins(ss, -1e30) ? ss : (float) -1e30;
+    const double fac = wd::fac_of(fsum, f2sum);
+    float sq = 0.0;
+    for (int i = 0; i < NSYM; i++) {
+        const uint8_t b = wd::soft_byte(wd::soft_value(wd::fsymb_of(p[4 * i], p[4 * i + 1], p[4 * i + 2], p[4 * i + 3], ws_pr3[i]), fac, wd::SYMFAC));
+        out->sym[i] = b;
+        wd::rms_step(sq, b);
+    }
+    const float rms = wd::rms_of(sq);
+    out->sync = sync; out->rms = rms; out->pad = 0;
+    out->gate = wd::gate_of(sync, rms);
+}
+
+struct wd_nodes {                                                       // a lane's 82 nodes, [node][lane] in LDS
+    uint32_t (*e)[WD_FANO_LANES]; int32_t (*g)[WD_FANO_LANES], (*a)[WD_FANO_LANES], (*b)[WD_FANO_LANES]; uint8_t (*r)[WD_FANO_LANES];
+    int lane;
+    __device__ uint32_t &enc(int n) { return e[n][lane]; }
+    __device__ int32_t &gamma(int n) { return g[n][lane]; }
+    __device__ int32_t &tm0(int n) { return a[n][lane]; }
+    __device__ int32_t &tm1(int n) { return b[n][lane]; }
+    __device__ uint8_t &br(int n) { return r[n][lane]; }
+};
+// set k: its 162 bytes at sym + k * stride, taken through the deinterleaver where deint; run where gate (null: every set) says so
+__global__ __launch_bounds__(WD_FANO_LANES) void wspr_fano_kernel(const uint8_t *__restrict__ sym, size_t stride, const int32_t *__restrict__ gate, size_t gate_stride, int deint,
+                                                                  int n, const int32_t *__restrict__ mettab, uint32_t maxcycles, wd_fano *out)
+{
+    __shared__ int32_t s_met[512];
+    __shared__ uint32_t s_e[wd::NNODES][WD_FANO_LANES];
+    __shared__ int32_t s_g[wd::NNODES][WD_FANO_LANES], s_a[wd::NNODES][WD_FANO_LANES], s_b[wd::NNODES][WD_FANO_LANES];
+    __shared__ uint8_t s_r[wd::NNODES][WD_FANO_LANES];
+    __shared__ uint8_t s_sym[NSYM][WD_FANO_LANES];
+    __shared__ uint8_t s_perm[NSYM];
+    const int lane = (int) threadIdx.x, k = (int) (blockIdx.x * WD_FANO_LANES) + lane;
+    for (int t = lane; t < 512; t += WD_FANO_LANES) s_met[t] = mettab[t];
+    if (lane == 0) wd::deint_table(s_perm);
+    for (int m = 0; m < wd::NNODES; m++) { s_e[m][lane] = 0; s_g[m][lane] = 0; s_a[m][lane] = 0; s_b[m][lane] = 0; s_r[m][lane] = 0; }
+    __syncthreads();
+    if (k >= n) return;
+    wd_fano o;
+    memset(&o, 0, sizeof o);
+    const bool run = gate == nullptr || *(const int32_t *) ((const char *) gate + (size_t) k * gate_stride) != 0;
+    if (run) {
+        const uint8_t *src = sym + (size_t) k * stride;
+        for (int p = 0; p < NSYM; p++) s_sym[p][lane] = src[deint ? s_perm[p] : p];
+        wd_nodes ns = {s_e, s_g, s_a, s_b, s_r, lane};
+        o.ok = wd::fano(ns, [&](int p) { return s_sym[p][lane]; }, [&](int a, int v) { return s_met[a * 256 + v]; }, wd::DELTA, maxcycles, &o.metric, &o.cycles, &o.maxnp,
+                        o.data);
+    }
+    out[k] = o;
+}
+
+// the record of the sequential loop (:812-883), a lane per slot
+__global__ __launch_bounds__(64) void wspr_dec_finish_kernel(const wd_slot *__restrict__ slots, int nslots, const wd_jig *__restrict__ jig, const wd_fano *__restrict__ fano,
+                                                             wd_hold *hold, kg_wspr_dec *out_base, int32_t *ncand, int iifac, int nidt, int quickmode,
+                                                             int by_conn)
+{
+    __shared__ uint8_t s_perm[NSYM];
+    if (threadIdx.x == 0) wd::deint_table(s_perm);
+    __syncthreads();
+    const int s = (int) (blockIdx.x * blockDim.x + threadIdx.x);
+    if (s >= nslots) return;
+    const wd_slot sl = slots[s];
+    kg_wspr_dec *out = by_conn ? out_base + ((size_t) sl.conn * MAX_NPK + sl.pki) - s : out_base;          // out[s]: by list entry, or by connection
+    kg_wspr_dec r;
+    memset(&r, 0, sizeof r);
+    if (sl.pki == 0) ncand[by_conn ? sl.conn : s / MAX_NPK] = hold[sl.conn].ncand;
+    if (!sl.exists) { out[s] = r; return; }
+    if (sl.skipped) { r.result = KG_WSPR_SKIPPED; r.ignore = 1; out[s] = r; return; }
+    for (int c = 0; c < wd::NCALLS; c++) { r.tr_f[c] = sl.tr_f[c]; r.tr_shift[c] = sl.tr_shift[c]; r.tr_sync[c] = sl.tr_sync[c]; }
+    r.f1 = sl.f1; r.shift1 = sl.shift1; r.drift1 = sl.drift1; r.sync1 = sl.sync1;
+    if (!sl.minsync_ok) {
+        r.result = KG_WSPR_MINSYNC1; r.ignore = 1;                      // :807
+        hold[sl.conn].ignore[sl.pki] = 1;
+        out[s] = r;
+        return;
+    }
+    const wd_jig *jg = jig + (size_t) s * wd::MAX_IDT;
+    const wd_fano *fn = fano + (size_t) s * wd::MAX_IDT;
+    int idt = 0, last = 0, gates = 0, decoded = 0, lastf = -1;
+    while (!decoded && idt < nidt) {                                    // :819
+        last = idt;
+        if (jg[idt].gate) { gates++; lastf = idt; decoded = fn[idt].ok; }
+        idt++;
+        if (quickmode) break;
+    }
+    const bool time_up = !decoded && idt > wd::JIG_RANGE / iifac;       // :869
+    r.result = decoded ? KG_WSPR_DECODED : (time_up && gates == 0) ? KG_WSPR_NO_CHANGE : time_up ? KG_WSPR_TIME_UP : KG_WSPR_QUICK_MISS;
+    r.ignore = decoded || (time_up && gates == 0);                      // :875, :883
+    if (r.ignore) hold[sl.conn].ignore[sl.pki] = 1;
+    r.sync1 = jg[last].sync; r.rms = jg[last].rms;
+    r.idt = idt; r.ii = wd::ii_of(last, iifac); r.jig_shift = sl.shift1 + r.ii; r.gates = gates;
+    if (lastf >= 0) {
+        r.metric = fn[lastf].metric; r.cycles = fn[lastf].cycles; r.maxnp = fn[lastf].maxnp;
+        for (int k = 0; k < wd::NDATA; k++) r.decdata[k] = fn[lastf].data[k];
+    }
+    for (int p = 0; p < NSYM; p++) r.symbols[p] = jg[last].sym[jg[last].gate ? s_perm[p] : p];            // deinterleaved only behind the gate (:839)
+    out[s] = r;
 }
 
 struct ws_conn {
     state_t st;
     std::vector<ev_t> pending;                  // the status changes of commands since the last push (blk -1)
+    int decode_on = 0;                          // kg_wspr_set_decode: a cycle end of a push also runs pass 0 (200, 2)
 };
 
 // a command's status change waits for the connection's next push; the last WS_PENDING of them are kept (a host that sends commands and
@@ -252,6 +527,15 @@ struct kg_wspr {
     std::vector<ws_conn> c;
     kg_dbuf<ws_dev> d_state;                    // [nconn]
     kg_dbuf<float> d_window;                    // [512], :1186-1188
+    // stage 2
+    kg_dbuf<wd_hold> d_hold;                    // [nconn]
+    kg_dbuf<int32_t> d_mettab;                  // [2][256], the caller's (kg_wspr_set_metric_table)
+    bool have_table = false;
+    size_t ws_slots = 0;                        // the decode workspace holds this many candidates: grown whole, capacity published last
+    kg_dbuf<kg_wspr_dec> d_dec;                 // [nconn][12]: the records of a connection's last pass 0 run by a push (kg_wspr_decodes)
+    kg_dbuf<int32_t> d_dec_ncand;               // [nconn]
+    kg_dbuf<unsigned char> d_slots, d_jig, d_fano;
+    kg_dbuf<double> d_pow;
 };
 
 struct ws_plan {
@@ -260,9 +544,57 @@ struct ws_plan {
     std::vector<ws_entry> ents;
     std::vector<ws_op> ops;
     std::vector<ws_cyc> cyc;
+    std::vector<int32_t> dec;                   // the connections whose cycle end also runs pass 0
     std::vector<kg_wspr_row> rows;
     std::vector<kg_wspr_ev> evs;
 };
+
+// the decode workspace for nslots candidates: released whole, allocated whole, its capacity published last
+static int wd_workspace(kg_wspr *q, size_t nslots, const char *who)
+{
+    if (nslots <= q->ws_slots) return KG_OK;
+    q->ws_slots = 0;
+    q->d_slots.reset(); q->d_jig.reset(); q->d_fano.reset(); q->d_pow.reset();
+    KG_TRY(q->d_slots.alloc(nslots * sizeof(wd_slot), who));
+    KG_TRY(q->d_jig.alloc(nslots * wd::MAX_IDT * sizeof(wd_jig), who));
+    KG_TRY(q->d_fano.alloc(nslots * wd::MAX_IDT * sizeof(wd_fano), who));
+    KG_TRY(q->d_pow.alloc(nslots * wd::MAX_IDT * NSYM * 4, who));
+    q->ws_slots = nslots;
+    return KG_OK;
+}
+
+// One pass over the held candidates of the listed connections, enqueued on the context's stream: d_conns [nconn] on the device,
+// d_out [nconn][12] and d_ncand [nconn] too -- by list entry, or (by_conn) by connection.  Enqueue only; the workspace is sized by the caller.
+static int wd_enqueue(kg_wspr *q, const int32_t *d_conns, int nconn, uint32_t maxcycles, int iifac, int quickmode, kg_wspr_dec *d_out, int32_t *d_ncand, int by_conn)
+{
+    hipStream_t s = q->ctx->stream;
+    const int nslots = nconn * MAX_NPK, nidt = wd::nidt_of(iifac, quickmode);
+    wd_slot *slots = (wd_slot *) q->d_slots.p;
+    wd_jig *jig = (wd_jig *) q->d_jig.p;
+    wd_fano *fano = (wd_fano *) q->d_fano.p;
+    const ws_dev *dev = q->d_state.p;
+    hipLaunchKernelGGL(wspr_dec_begin_kernel, dim3((unsigned) ((nslots + 63) / 64)), dim3(64), 0, s, d_conns, nslots, (const wd_hold *) q->d_hold.p, slots);
+    KG_HIP(hipGetLastError());
+    for (int call = 0; call < wd::NCALLS; call++) {
+        if (call == 0 || call == 4) hipLaunchKernelGGL(wspr_corr_kernel<WD_NL>, dim3(NSYM, (unsigned) nslots), dim3(WD_THREADS), 0, s, (const wd_slot *) slots, dev, q->d_pow.p, call, 1, 1);
+        else hipLaunchKernelGGL(wspr_corr_kernel<1>, dim3(NSYM, (unsigned) nslots), dim3(WD_THREADS), 0, s, (const wd_slot *) slots, dev, q->d_pow.p, call, 1, 1);
+        KG_HIP(hipGetLastError());
+        hipLaunchKernelGGL(wspr_pick_kernel, dim3((unsigned) nslots), dim3(64), 0, s, slots, (const double *) q->d_pow.p, call);
+        KG_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(wspr_corr_kernel<WD_NL>, dim3(NSYM, (unsigned) nslots), dim3(WD_THREADS), 0, s, (const wd_slot *) slots, dev, q->d_pow.p, (int) WD_CALL_SOFT, iifac, nidt);
+    KG_HIP(hipGetLastError());
+    hipLaunchKernelGGL(wspr_soft_kernel, dim3((unsigned) nslots), dim3(WD_SOFT_THREADS), 0, s, (const wd_slot *) slots, (const double *) q->d_pow.p, jig, nidt);
+    KG_HIP(hipGetLastError());
+    const int nf = nslots * wd::MAX_IDT;
+    hipLaunchKernelGGL(wspr_fano_kernel, dim3((unsigned) ((nf + WD_FANO_LANES - 1) / WD_FANO_LANES)), dim3(WD_FANO_LANES), 0, s, (const uint8_t *) jig + offsetof(wd_jig, sym),
+                       sizeof(wd_jig), (const int32_t *) ((const char *) jig + offsetof(wd_jig, gate)), sizeof(wd_jig), 1, nf, (const int32_t *) q->d_mettab.p, maxcycles, fano);
+    KG_HIP(hipGetLastError());
+    hipLaunchKernelGGL(wspr_dec_finish_kernel, dim3((unsigned) ((nslots + 63) / 64)), dim3(64), 0, s, (const wd_slot *) slots, nslots, (const wd_jig *) jig,
+                       (const wd_fano *) fano, q->d_hold.p, d_out, d_ncand, iifac, nidt, quickmode, by_conn);
+    KG_HIP(hipGetLastError());
+    return KG_OK;
+}
 
 static int ws_walk(kg_wspr *q, const int32_t *conns, int nconn, const int32_t *nblk, const int32_t *in_row, int ns, size_t iq_stride, const int32_t *minute, const int32_t *second,
                    size_t time_stride, size_t rows_cap, int max_rows, int max_events, ws_plan &p, const char *who)
@@ -301,9 +633,13 @@ static int ws_walk(kg_wspr *q, const int32_t *conns, int nconn, const int32_t *n
             }
             p.ops.push_back(d);
         }
-        for (const ev_t &m : sp.evs) p.evs.push_back(kg_wspr_ev{c, m.blk, m.samp, m.kind, m.a, m.b});
+        for (const ev_t &m : sp.evs) {
+            p.evs.push_back(kg_wspr_ev{c, m.blk, m.samp, m.kind, m.a, m.b});
+            if (m.kind == EV_PEAKS && q->c[c].decode_on) p.evs.push_back(kg_wspr_ev{c, m.blk, m.samp, KG_WSPR_EV_DECODES, m.a, 0});        // between PEAKS and the resume
+        }
         KG_REQUIRE(p.evs.size() <= (size_t) max_events, KG_ERR_INVALID, "%s: more events than max_events = %d", who, max_events);
         if (sp.ncycle) p.cyc.push_back(ws_cyc{c, sp.cycle_half, st.wspr_type, st.more_candidates, i, {0, 0, 0}});
+        if (sp.ncycle && q->c[c].decode_on) p.dec.push_back(c);
         p.ents.push_back(e);
         p.conn.push_back(c);
         p.st.push_back(st);
@@ -317,11 +653,12 @@ static int ws_enqueue(kg_wspr *q, ws_plan &p, int nconn, const float *d_iq, uint
                       kg_wspr_cycle *d_cycles, int32_t *d_counts)
 {
     hipStream_t s = q->ctx->stream;
-    const size_t ne = sizeof(ws_entry) * p.ents.size(), no = sizeof(ws_op) * p.ops.size(), nc = sizeof(ws_cyc) * p.cyc.size();
-    std::vector<unsigned char> tab(ne + no + nc);
+    const size_t ne = sizeof(ws_entry) * p.ents.size(), no = sizeof(ws_op) * p.ops.size(), nc = sizeof(ws_cyc) * p.cyc.size(), nd = sizeof(int32_t) * p.dec.size();
+    std::vector<unsigned char> tab(ne + no + nc + nd);
     memcpy(tab.data(), p.ents.data(), ne);
     if (no) memcpy(tab.data() + ne, p.ops.data(), no);
     if (nc) memcpy(tab.data() + ne + no, p.cyc.data(), nc);
+    if (nd) memcpy(tab.data() + ne + no + nc, p.dec.data(), nd);
     void *d_tab = nullptr;
     KG_TRY(kg_ctx_stage(q->ctx, tab.data(), tab.size(), &d_tab));
     KG_PLAN_ONLY(q->ctx);
@@ -333,9 +670,11 @@ static int ws_enqueue(kg_wspr *q, ws_plan &p, int nconn, const float *d_iq, uint
     KG_HIP(hipGetLastError());
     if (nc) {
         hipLaunchKernelGGL(wspr_cycle_kernel, dim3(MAX_NPK, (unsigned) p.cyc.size()), dim3(WS_THREADS), 0, s, (const ws_cyc *) (t + ne + no), (const ws_dev *) q->d_state.p,
-                           d_cycles, d_counts, q->min_snr);
+                           d_cycles, d_counts, q->min_snr, q->d_hold.p);
         KG_HIP(hipGetLastError());
     }
+    // pass 0 (wspr.cpp:505, :508) behind the cycle end, on the same stream: no host wait; its workspace is kg_wspr_set_decode's
+    if (nd) KG_TRY(wd_enqueue(q, (const int32_t *) (t + ne + no + nc), (int) p.dec.size(), 200, 2, 0, q->d_dec.p, q->d_dec_ncand.p, 1));
     for (size_t k = 0; k < p.conn.size(); k++) { q->c[p.conn[k]].st = p.st[k]; q->c[p.conn[k]].pending.clear(); }       // commit: the enqueue succeeded
     if (row_map && !p.rows.empty()) memcpy(row_map, p.rows.data(), sizeof(kg_wspr_row) * p.rows.size());
     if (evs && !p.evs.empty()) memcpy(evs, p.evs.data(), sizeof(kg_wspr_ev) * p.evs.size());
@@ -359,8 +698,12 @@ int kg_wspr_push_rows_(kg_wspr *q, const int32_t *conns, int nconn, const int32_
     return ws_enqueue(q, p, nconn, d_iq, d_rows, row_map, nrows, evs, nevents, d_cycles, d_counts);
 }
 
+// the records and counts of the pushes' pass 0, by connection (device memory of the object), for kg_rxbank.hip
+void kg_wspr_dec_buffers_(kg_wspr *q, kg_wspr_dec **d_decs, int32_t **d_ncand) { *d_decs = q->d_dec.p; *d_ncand = q->d_dec_ncand.p; }
+int kg_wspr_decode_on_(const kg_wspr *q, int conn) { return q->c[conn].decode_on; }
+
 // what the table of a push over nconn connections takes when no connection has more than ops_per_conn ops (and its alignment)
-size_t kg_wspr_table_bytes_(size_t nconn, size_t ops_per_conn) { return 64 + nconn * (sizeof(ws_entry) + sizeof(ws_op) * ops_per_conn + sizeof(ws_cyc)); }
+size_t kg_wspr_table_bytes_(size_t nconn, size_t ops_per_conn) { return 64 + nconn * (sizeof(ws_entry) + sizeof(ws_op) * ops_per_conn + sizeof(ws_cyc) + sizeof(int32_t)); }
 
 // connection conn as a new connection finds it: the zeroed object, not initialised, nothing pending.  Enqueue only.
 int kg_wspr_reset_(kg_wspr *q, int conn)
@@ -369,6 +712,10 @@ int kg_wspr_reset_(kg_wspr *q, int conn)
     int rc = kg_ctx_use(q->ctx);
     if (rc) return rc;
     KG_HIP(hipMemsetAsync(q->d_state.p + conn, 0, sizeof(ws_dev), q->ctx->stream));
+    KG_HIP(hipMemsetAsync(q->d_hold.p + conn, 0, sizeof(wd_hold), q->ctx->stream));            // the candidates and their ignore flags
+    KG_HIP(hipMemsetAsync(q->d_dec.p + (size_t) conn * MAX_NPK, 0, sizeof(kg_wspr_dec) * MAX_NPK, q->ctx->stream));
+    KG_HIP(hipMemsetAsync(q->d_dec_ncand.p + conn, 0, sizeof(int32_t), q->ctx->stream));
+    q->c[conn].decode_on = 0;
     memset(&q->c[conn].st, 0, sizeof q->c[conn].st);
     q->c[conn].pending.clear();
     return KG_OK;
@@ -385,6 +732,13 @@ int kg_wspr_create(kg_ctx *ctx, int nconn, kg_wspr **out)
         for (ws_conn &c : q->c) memset(&c.st, 0, sizeof c.st);
         KG_TRY(q->d_state.alloc((size_t) nconn, "kg_wspr_create: connection state"));
         KG_TRY(q->d_window.alloc(NFFT, "kg_wspr_create: window"));
+        KG_TRY(q->d_hold.alloc((size_t) nconn, "kg_wspr_create: held candidates"));
+        KG_TRY(q->d_mettab.alloc(512, "kg_wspr_create: metric table"));
+        KG_TRY(kg_ext_zero(ctx, q->d_hold.p, (size_t) nconn, "kg_wspr_create"));
+        KG_TRY(q->d_dec.alloc((size_t) nconn * MAX_NPK, "kg_wspr_create: decode records"));
+        KG_TRY(q->d_dec_ncand.alloc((size_t) nconn, "kg_wspr_create: decode counts"));
+        KG_TRY(kg_ext_zero(ctx, q->d_dec.p, (size_t) nconn * MAX_NPK, "kg_wspr_create"));
+        KG_TRY(kg_ext_zero(ctx, q->d_dec_ncand.p, (size_t) nconn, "kg_wspr_create"));
         float win[NFFT];
         for (int i = 0; i < NFFT; i++) win[i] = window_at(i);
         KG_HIP(hipMemcpyAsync(q->d_window.p, win, sizeof win, hipMemcpyHostToDevice, ctx->stream));
@@ -546,11 +900,142 @@ int kg_wspr_load(kg_wspr *q, int conn, int half, const float *pwr_samp, const fl
     const ws_cyc cyc = {conn, half, w.wspr_type, w.more_candidates, 0, {0, 0, 0}};
     void *d_tab = nullptr;
     KG_TRY(kg_ctx_stage(q->ctx, &cyc, sizeof cyc, &d_tab));
-    hipLaunchKernelGGL(wspr_cycle_kernel, dim3(MAX_NPK, 1), dim3(WS_THREADS), 0, s, (const ws_cyc *) d_tab, (const ws_dev *) q->d_state.p, d_cycle, d_counts, q->min_snr);
+    hipLaunchKernelGGL(wspr_cycle_kernel, dim3(MAX_NPK, 1), dim3(WS_THREADS), 0, s, (const ws_cyc *) d_tab, (const ws_dev *) q->d_state.p, d_cycle, d_counts, q->min_snr, q->d_hold.p);
     KG_HIP(hipGetLastError());
     KG_HIP(hipMemcpyAsync(cycle, d_cycle, sizeof(kg_wspr_cycle), hipMemcpyDeviceToHost, s));
     KG_HIP(hipStreamSynchronize(s));
     q->c[conn].st.decode_ping_pong = half;
+    return KG_OK;                                       // tmp drains the stream
+}
+
+// ---- stage 2
+int kg_wspr_set_metric_table(kg_wspr *q, const int32_t mettab[2][256])
+{
+    KG_REQUIRE(q != nullptr && mettab != nullptr, KG_ERR_INVALID, "kg_wspr_set_metric_table: null argument");
+    int rc = kg_ctx_use(q->ctx);
+    if (rc) return rc;
+    for (int i = 0; i < 512; i++)
+        KG_REQUIRE(mettab[i >> 8][i & 255] <= wd::MAX_METRIC && mettab[i >> 8][i & 255] >= -wd::MAX_METRIC, KG_ERR_INVALID,
+                   "kg_wspr_set_metric_table: mettab[%d][%d] = %d (within +-%d)", i >> 8, i & 255, mettab[i >> 8][i & 255], (int) wd::MAX_METRIC);
+    KG_HIP(hipMemcpyAsync(q->d_mettab.p, mettab, sizeof(int32_t) * 512, hipMemcpyHostToDevice, q->ctx->stream));
+    KG_HIP(hipStreamSynchronize(q->ctx->stream));       // mettab is the caller's
+    q->have_table = true;
+    return KG_OK;
+}
+
+int kg_wspr_load_iq(kg_wspr *q, int conn, int half, const float *i_data, const float *q_data, const kg_wspr_cand *cands, int ncand)
+{
+    WS_INITED("kg_wspr_load_iq");
+    KG_REQUIRE(half == 0 || half == 1, KG_ERR_INVALID, "kg_wspr_load_iq: half %d (0..1)", half);
+    KG_REQUIRE(i_data && q_data && (cands || ncand == 0), KG_ERR_INVALID, "kg_wspr_load_iq: null argument");
+    KG_REQUIRE(ncand >= 0 && ncand <= MAX_NPK, KG_ERR_INVALID, "kg_wspr_load_iq: ncand %d (0..%d)", ncand, (int) MAX_NPK);
+    wd_hold h;
+    memset(&h, 0, sizeof h);
+    h.ncand = ncand; h.half = half;
+    for (int c = 0; c < ncand; c++) {                   // every dphi of the refinement stays inside kg_libm_dtrig.h's domain
+        KG_REQUIRE(fabsf(cands[c].freq0) <= 113.0f && cands[c].shift0 >= -TPOINTS && cands[c].shift0 <= TPOINTS && fabsf(cands[c].drift0) <= 4.0f, KG_ERR_INVALID,
+                   "kg_wspr_load_iq: candidate %d: freq0 %g (+-113), shift0 %d (+-%d), drift0 %g (+-4)", c, (double) cands[c].freq0, cands[c].shift0, (int) TPOINTS,
+                   (double) cands[c].drift0);
+        h.cand[c] = cands[c];
+    }
+    int rc = kg_ctx_use(q->ctx);
+    if (rc) return rc;
+    ws_dev *d = q->d_state.p + conn;
+    hipStream_t s = q->ctx->stream;
+    KG_HIP(hipMemcpyAsync(d->idat[half], i_data, sizeof(float) * TPOINTS, hipMemcpyHostToDevice, s));
+    KG_HIP(hipMemcpyAsync(d->qdat[half], q_data, sizeof(float) * TPOINTS, hipMemcpyHostToDevice, s));
+    KG_HIP(hipMemcpyAsync(q->d_hold.p + conn, &h, sizeof h, hipMemcpyHostToDevice, s));
+    KG_HIP(hipStreamSynchronize(s));                    // the arrays are the caller's, h this frame's; the schedule's state (st) is not touched
+    return KG_OK;
+}
+
+int kg_wspr_decode(kg_wspr *q, const int32_t *conns, int nconn, uint32_t maxcycles, int iifac, int quickmode, kg_wspr_dec *out, int32_t *ncand)
+{
+    KG_REQUIRE(q && conns && out && ncand, KG_ERR_INVALID, "kg_wspr_decode: null argument");
+    int rc = kg_ctx_use(q->ctx);
+    if (rc) return rc;
+    KG_REQUIRE(q->have_table, KG_ERR_STATE, "kg_wspr_decode: no metric table yet (kg_wspr_set_metric_table)");
+    KG_REQUIRE(nconn >= 1 && nconn <= q->nconn, KG_ERR_INVALID, "kg_wspr_decode: nconn %d (1..%d)", nconn, q->nconn);
+    KG_REQUIRE(iifac >= 1 && iifac <= wd::JIG_RANGE, KG_ERR_INVALID, "kg_wspr_decode: iifac %d (1..%d)", iifac, (int) wd::JIG_RANGE);
+    KG_REQUIRE(maxcycles >= 1 && maxcycles <= (uint32_t) wd::MAX_MAXCYCLES, KG_ERR_INVALID, "kg_wspr_decode: maxcycles %u (1..%d)", maxcycles, (int) wd::MAX_MAXCYCLES);
+    std::vector<char> listed((size_t) q->nconn, 0);
+    for (int i = 0; i < nconn; i++) {
+        const int c = conns[i];
+        KG_REQUIRE(c >= 0 && c < q->nconn, KG_ERR_INVALID, "kg_wspr_decode: conns[%d] = %d of %d", i, c, q->nconn);
+        KG_REQUIRE(!listed[c], KG_ERR_INVALID, "kg_wspr_decode: connection %d is listed twice", c);
+        listed[c] = 1;
+        KG_REQUIRE(q->c[c].st.inited, KG_ERR_STATE, "kg_wspr_decode: connection %d was never initialised (kg_wspr_init)", c);
+    }
+    const size_t nslots = (size_t) nconn * MAX_NPK;
+    KG_TRY(wd_workspace(q, nslots, "kg_wspr_decode: workspace"));
+    hipStream_t s = q->ctx->stream;
+    kg_wspr_dec *d_out = nullptr;
+    int32_t *d_ncand = nullptr;
+    void *d_conns = nullptr;
+    kg_scope tmp(q->ctx);                               // out and ncand are in use until the stream has drained
+    KG_TRY(tmp.alloc(&d_out, nslots, "kg_wspr_decode: records"));
+    KG_TRY(tmp.alloc(&d_ncand, (size_t) nconn, "kg_wspr_decode: counts"));
+    KG_TRY(kg_ctx_stage(q->ctx, conns, sizeof(int32_t) * (size_t) nconn, &d_conns));
+    KG_TRY(wd_enqueue(q, (const int32_t *) d_conns, nconn, maxcycles, iifac, quickmode != 0, d_out, d_ncand, 0));
+    KG_HIP(hipMemcpyAsync(out, d_out, sizeof(kg_wspr_dec) * nslots, hipMemcpyDeviceToHost, s));
+    KG_HIP(hipMemcpyAsync(ncand, d_ncand, sizeof(int32_t) * (size_t) nconn, hipMemcpyDeviceToHost, s));
+    KG_HIP(hipStreamSynchronize(s));
+    return KG_OK;                                       // tmp drains the stream
+}
+
+int kg_wspr_set_decode(kg_wspr *q, int conn, int on)
+{
+    WS_INITED("kg_wspr_set_decode");
+    if (on) {
+        KG_REQUIRE(q->have_table, KG_ERR_STATE, "kg_wspr_set_decode: no metric table yet (kg_wspr_set_metric_table)");
+        int rc = kg_ctx_use(q->ctx);
+        if (rc) return rc;
+        if ((size_t) q->nconn * MAX_NPK > q->ws_slots) KG_HIP(hipStreamSynchronize(q->ctx->stream));       // a pass under way still reads the workspace that grows
+        KG_TRY(wd_workspace(q, (size_t) q->nconn * MAX_NPK, "kg_wspr_set_decode: workspace"));             // a push must not allocate
+    }
+    q->c[conn].decode_on = on != 0;
+    return KG_OK;
+}
+
+int kg_wspr_decodes(kg_wspr *q, int conn, kg_wspr_dec *out, int32_t *ncand)
+{
+    KG_EXT_INDEX("kg_wspr_decodes", q, conn, q->nconn, "connection");
+    KG_REQUIRE(out && ncand, KG_ERR_INVALID, "kg_wspr_decodes: null argument");
+    int rc = kg_ctx_use(q->ctx);
+    if (rc) return rc;
+    hipStream_t s = q->ctx->stream;
+    KG_HIP(hipMemcpyAsync(out, q->d_dec.p + (size_t) conn * MAX_NPK, sizeof(kg_wspr_dec) * MAX_NPK, hipMemcpyDeviceToHost, s));
+    KG_HIP(hipMemcpyAsync(ncand, q->d_dec_ncand.p + conn, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    KG_HIP(hipStreamSynchronize(s));
+    return KG_OK;
+}
+
+int kg_wspr_fano(kg_wspr *q, const uint8_t *symbols, int n, uint32_t maxcycles, int32_t *ok, uint32_t *metric, uint32_t *cycles, uint32_t *maxnp,
+                 uint8_t *data)
+{
+    KG_REQUIRE(q && symbols && ok && metric && cycles && maxnp && data, KG_ERR_INVALID, "kg_wspr_fano: null argument");
+    int rc = kg_ctx_use(q->ctx);
+    if (rc) return rc;
+    KG_REQUIRE(q->have_table, KG_ERR_STATE, "kg_wspr_fano: no metric table yet (kg_wspr_set_metric_table)");
+    KG_REQUIRE(n >= 1 && n <= WD_MAX_FANO, KG_ERR_INVALID, "kg_wspr_fano: n %d (1..%d)", n, (int) WD_MAX_FANO);
+    KG_REQUIRE(maxcycles >= 1 && maxcycles <= (uint32_t) wd::MAX_MAXCYCLES, KG_ERR_INVALID, "kg_wspr_fano: maxcycles %u (1..%d)", maxcycles, (int) wd::MAX_MAXCYCLES);
+    hipStream_t s = q->ctx->stream;
+    uint8_t *d_sym = nullptr;
+    wd_fano *d_res = nullptr;
+    kg_scope tmp(q->ctx);
+    KG_TRY(tmp.alloc(&d_sym, (size_t) n * NSYM, "kg_wspr_fano: symbols"));
+    KG_TRY(tmp.alloc(&d_res, (size_t) n, "kg_wspr_fano: results"));
+    KG_HIP(hipMemcpyAsync(d_sym, symbols, (size_t) n * NSYM, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(wspr_fano_kernel, dim3((unsigned) ((n + WD_FANO_LANES - 1) / WD_FANO_LANES)), dim3(WD_FANO_LANES), 0, s, (const uint8_t *) d_sym, (size_t) NSYM,
+                       (const int32_t *) nullptr, (size_t) 0, 0, n, (const int32_t *) q->d_mettab.p, maxcycles, d_res);
+    KG_HIP(hipGetLastError());
+    std::vector<wd_fano> res((size_t) n);
+    KG_HIP(hipMemcpyAsync(res.data(), d_res, sizeof(wd_fano) * (size_t) n, hipMemcpyDeviceToHost, s));
+    KG_HIP(hipStreamSynchronize(s));
+    for (int k = 0; k < n; k++) {
+        ok[k] = res[k].ok; metric[k] = res[k].metric; cycles[k] = res[k].cycles; maxnp[k] = res[k].maxnp;
+        memcpy(data + (size_t) k * wd::NDATA, res[k].data, wd::NDATA);
+    }
     return KG_OK;                                       // tmp drains the stream
 }
 

@@ -455,6 +455,31 @@ class RxBank:
         """what utc_hour_min_sec answers during every later step"""
         check(self.lib.kg_rxbank_wspr_set_now(self.h, int(minute), int(second)), "kg_rxbank_wspr_set_now")
 
+    def wspr_set_metric_table(self, mettab):
+        """stage 2: mettab int32 [2, 256] for the bank's Wspr"""
+        mt = np.ascontiguousarray(mettab, np.int32)
+        assert mt.shape == (2, 256)
+        check(self.lib.kg_rxbank_wspr_set_metric_table(self.h, ptr(mt)), "kg_rxbank_wspr_set_metric_table")
+
+    def wspr_set_decode(self, rx, on):
+        """on: a step that holds the receiver's cycle end also enqueues pass 0 (200, 2) behind it"""
+        check(self.lib.kg_rxbank_wspr_set_decode(self.h, int(rx), int(on)), "kg_rxbank_wspr_set_decode")
+
+    def wspr_dec_out(self):
+        """-> ({receiver: records of wspr.dec_dtype} of the receivers whose pass 0 the last step enqueued; after sync())"""
+        from . import wspr as ws
+        rxs = np.zeros(self.nrx, np.int32)
+        d_decs, d_n = C.c_void_p(), C.c_void_p()
+        n = check(self.lib.kg_rxbank_wspr_dec_out(self.h, C.byref(d_decs), C.byref(d_n), ptr(rxs), int(rxs.size)), "kg_rxbank_wspr_dec_out")
+        out = {}
+        if n:
+            recs, cnt = np.zeros((self.nrx, ws.MAX_NPK), ws.dec_dtype), np.zeros(self.nrx, np.int32)
+            self.ctx.download(int(d_decs.value), recs)
+            self.ctx.download(int(d_n.value), cnt)
+            for rx in rxs[:n].tolist():
+                out[rx] = recs[rx][:cnt[rx]].copy()
+        return out
+
     @property
     def wspr(self):
         """the bank's Wspr (None until one of the per-receiver wspr_* commands was sent): state()"""

@@ -1617,6 +1617,9 @@ int kg_wspr_state(kg_wspr *q, int conn, kg_wspr_info *info, float *pwr_sampavg, 
 /* For a host that resumes, and for tests: pwr_samp [512][348] and pwr_sampavg [512] placed into a half, then the cycle end on it (pass 0
  * of wspr_decode, wspr.cpp:555-714) under the connection's type and more_candidates.  One launch.  Synchronises. */
 int kg_wspr_load(kg_wspr *q, int conn, int half, const float *pwr_samp, const float *pwr_sampavg, kg_wspr_cycle *cycle);
+/* Stage 2 of the WSPR extension -- fine sync, soft symbols and the Fano decoder on the candidates a connection holds -- is declared in a
+ * header of its own, in this directory. */
+#include "kiwigpu_wspr_dec.h"
 
 /* Diagnostics: re-runs the 4096-point stage of the forward FFT of `block` in a
  * stamped build of the kernel and returns 4 s_memrealtime readings (100 MHz):
