@@ -24,7 +24,8 @@ from .lorc import LoranC  # noqa: F401
 from .fax import FaxDecoder  # noqa: F401
 from .cw import CwDecoder  # noqa: F401
 from .wspr import Wspr  # noqa: F401
-from . import sats, prn, synth, shard, wf, snd, post, wire, handoff, nb, trk, nav, eph, pos, fftext, lorc, fax, cw, wspr  # noqa: F401
+from .ft8 import Ft8  # noqa: F401
+from . import sats, prn, synth, shard, wf, snd, post, wire, handoff, nb, trk, nav, eph, pos, fftext, lorc, fax, cw, wspr, ft8  # noqa: F401
 
-__all__ = ["KiwiGpuError", "Context", "Searcher", "AcqResult", "Waterfall", "WfParams", "Ddc", "RxDdc", "FastFir", "Post", "NoiseBlanker", "Adpcm", "Aperture", "chan_start", "Tracker", "NavSync", "Ephemerides", "FftExt", "LoranC", "FaxDecoder", "CwDecoder", "Wspr",
+__all__ = ["KiwiGpuError", "Context", "Searcher", "AcqResult", "Waterfall", "WfParams", "Ddc", "RxDdc", "FastFir", "Post", "NoiseBlanker", "Adpcm", "Aperture", "chan_start", "Tracker", "NavSync", "Ephemerides", "FftExt", "LoranC", "FaxDecoder", "CwDecoder", "Wspr", "Ft8",
            "load_library", "library_path", "live_allocs", "sats", "prn", "synth", "shard", "wf"]

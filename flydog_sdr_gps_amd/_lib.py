@@ -423,6 +423,25 @@ WSPR_DEC_SYMBOLS = {
 }
 
 
+# include/kiwigpu_ft8.h (the FT8 / FT4 extension, stage 1; kiwigpu.h includes it)
+FT8_SYMBOLS = {
+    "kg_ft8_create": (_i, [_vp, _i, C.POINTER(_vp)]),
+    "kg_ft8_destroy": (None, [_vp]),
+    "kg_ft8_set_snr_adj": (_i, [_vp, C.c_float]),
+    "kg_ft8_init": (_i, [_vp, _i, _i, C.c_double]),
+    "kg_ft8_push": (_i, [_vp, _vp, _i, _vp, _i, _vp, _sz, _vp, _sz, _vp, _i, _vp, _vp, _i, _vp]),
+    "kg_ft8_plan": (_i, [_vp, _vp, _i, _vp, _i, _vp, _sz, _vp, _vp, _vp]),
+    "kg_ft8_state": (_i, [_vp, _i, _vp, _vp, _vp, _i]),
+    "kg_ft8_load_wf": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp]),
+    "kg_rxbank_ft8_init": (_i, [_vp, _i, _i, C.c_double]),
+    "kg_rxbank_ft8_start": (_i, [_vp, _i]),
+    "kg_rxbank_ft8_stop": (_i, [_vp, _i]),
+    "kg_rxbank_ft8_set_now": (_i, [_vp, C.c_double]),
+    "kg_rxbank_ft8": (_vp, [_vp]),
+    "kg_rxbank_ft8_out": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i]),
+}
+
+
 def _share_hip_runtime_with_torch():
     """PyTorch-ROCm wheels carry their own libamdhip64 / libhsa-runtime64.  Two HIP runtimes in one
     process cannot both own the GPU: whichever initialises second reports "No HIP GPUs are
@@ -456,7 +475,7 @@ def load_library():
                            "CPU fallback" % path)
     _share_hip_runtime_with_torch()
     lib = C.CDLL(path)
-    for name, (res, args) in list(SYMBOLS.items()) + list(WSPR_DEC_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(WSPR_DEC_SYMBOLS.items()) + list(FT8_SYMBOLS.items()):
         fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

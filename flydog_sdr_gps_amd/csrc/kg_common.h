@@ -270,6 +270,13 @@ __attribute__((visibility("hidden"))) int kg_cw_push_at_(kg_cw *q, const int32_t
                                                          size_t stride, const uint32_t *now_sec, kg_cw_ev *d_evs, int max_events, int32_t *d_counts);
 __attribute__((visibility("hidden"))) size_t kg_cw_table_bytes_(size_t nconn);
 __attribute__((visibility("hidden"))) int kg_cw_reset_(kg_cw *q, int conn);
+// kg_ft8.hip, for kg_rxbank.hip (not part of the ABI): kg_ft8_push on device memory with the entries placed by offsets; what its table takes; a reset.
+__attribute__((visibility("hidden"))) int kg_ft8_push_at_(kg_ft8 *q, const int32_t *conns, int nconn, const int32_t *ncb, const int64_t *in_off, int ns, const int16_t *d_in,
+                                                          size_t sample_stride, const double *times, size_t time_stride, kg_ft8_ev *evs, int max_events, int32_t *nevents,
+                                                          kg_ft8_slot *d_slots, int max_slots, int32_t *slot_conn, int32_t *nslots);
+__attribute__((visibility("hidden"))) size_t kg_ft8_table_bytes_(size_t nconn, size_t ncb);
+__attribute__((visibility("hidden"))) int kg_ft8_reset_(kg_ft8 *q, int conn);
+__attribute__((visibility("hidden"))) int kg_ft8_inited_(const kg_ft8 *q, int conn);
 
 // kg_wspr.hip, for kg_rxbank.hip (not part of the ABI): kg_wspr_push on device memory, samples and outputs alike, entry i's samples at row
 // in_row[i] of d_iq (null: row i), rows at multiples of KG_WSPR_ROW_STRIDE in list order, cycles and counts an entry of the list each,

@@ -225,6 +225,25 @@ struct bank_ws {
     struct { std::vector<kg_wspr_row> rows; std::vector<kg_wspr_ev> evs; std::vector<int32_t> rx; int n, ne, nent; } last;      // kg_rxbank_wspr_out
 };
 
+// FT8 / FT4, stage 1 (extensions/FT8/; kg_ft8); its first call also grows the arena slots by its table.  The third holder of the
+// real-samples task tap (ext_register_receive_real_samps_task, FT8.cpp), fed exactly as FAX and the CW decoder are: while a receiver is
+// started and its blocks go on the mono list, the step's d_s16 blocks feed it in place -- a callback a sound block --: the copy, tail
+// and monitor launches of the step and, when a receiver's slot ends, sync scores, selection and likelihoods behind them with no host
+// wait, on the tail stream behind WSPR's and ahead of ev_tail.  Every callback of a step carries the clock reading of the last
+// kg_rxbank_ft8_set_now.  The slot records are the device's; the events and which receiver a record belongs to are the host's schedule.
+struct bank_f8 {
+    kg_ft8 *obj;
+    kg_dbuf<kg_ft8_slot> d_slots;                                          // [nrx]: record k is the k-th receiver of the step whose slot ended
+    int max_events;
+    std::vector<char> on;                               // kg_rxbank_ft8_start (ext_register_receive_real_samps_task: one task per receiver)
+    double now;
+    struct {
+        std::vector<int32_t> list, nblk; std::vector<int64_t> off; std::vector<double> now;        // the entries: receiver, blocks, its row of d_s16; the clock of every block
+        std::vector<kg_ft8_ev> evs; std::vector<int32_t> slot_rx; int32_t ne, nsl;                  // handed back
+    } plan;
+    struct { std::vector<kg_ft8_ev> evs; std::vector<int32_t> slot_rx; int ne, nsl; } last;        // kg_rxbank_ft8_out
+};
+
 struct kg_rxbank {
     // configuration
     int device, nrx, mode, decim_rx;
@@ -238,7 +257,7 @@ struct kg_rxbank {
     kg_ddc *ddc; kg_wf *wf; kg_rxddc *rx; kg_fir *fir; kg_post *post; kg_adpcm *adpcm;
     kg_nb *nb;                                  // m_NoiseProc_snd[] (the waterfall's blankers are kg_wf's)
     kg_fir *nullfir;                            // m_chan_null_FIR[] (rx_sound.cpp:151), on the tail stream behind kg_post
-    bank_fx fx; bank_iq iq; bank_lo lo; bank_fa fa; bank_cw cw; bank_ws ws;     // the extensions (above)
+    bank_fx fx; bank_iq iq; bank_lo lo; bank_fa fa; bank_cw cw; bank_ws ws; bank_f8 f8;     // the extensions (above)
     // device buffers
     kg_dbuf<short2> d_wfiq; size_t wf_stride;         // [nrx][wf_stride] iq_t: a one-shot receiver uses pairs 0 .. 8191 of its row, an overlapped one all of it
     kg_dbuf<unsigned char> d_rows, d_pkts;         // [frame][1024], [frame][BANK_PKT_STRIDE]
@@ -320,7 +339,7 @@ static bool bank_stereo(int mode) { return mode == KG_POST_IQ || mode == KG_POST
 //   _plan_clear, _plan    the step's lists: emptied, then entry i of the active list (receiver p.act[i], nblk sound blocks)
 //   _enqueue     its ONE launch of the step, on the tail stream; what the entry point hands back goes into the record's plan
 //   _commit      the plan's maps become the last step's
-// The general functions call the six by name, in the order fx, iq, lo, fa, cw, ws: that is the order of the launches on the tail stream
+// The general functions call the six by name, in the order fx, iq, lo, fa, cw, ws, f8: that is the order of the launches on the tail stream
 // and of the tables in the slot.
 
 // A device buffer of a record: where its pointer goes, its size, its name in a refusal
@@ -715,6 +734,68 @@ static void bank_ws_commit(kg_rxbank *b)
     for (int e = 0; e < x.last.nent; e++) x.last.rx[e] = x.plan.list[e];
 }
 
+static void bank_f8_sizes(kg_rxbank *b)
+{
+    bank_f8 &x = b->f8;
+    const size_t nrx = (size_t) b->nrx;
+    x.max_events = (int) (nrx * 4);                     // a sync, the one slot end a step can hold, the next sync
+    x.on.assign(nrx, 0);
+    x.now = 0.0;
+    for (std::vector<int32_t> *v : {&x.plan.list, &x.plan.nblk}) v->reserve(nrx);
+    x.plan.off.reserve(nrx); x.plan.now.reserve(nrx * b->blocks_max);
+    x.plan.ne = x.plan.nsl = x.last.ne = x.last.nsl = 0;
+}
+
+static int bank_f8_ensure(kg_rxbank *b)
+{
+    bank_f8 &x = b->f8;
+    if (x.obj) return KG_OK;
+    KG_REQUIRE(b->blocks_max <= 4096 && b->blocks_max * KG_FIR_OUT < 85248, KG_ERR_INVALID,
+               "kg_rxbank_ft8: a step of up to %zu sound blocks a receiver; a step may hold one slot end (under 166 blocks)", b->blocks_max);
+    KG_TRY(bank_ext_ensure(b, "kg_rxbank_ft8", {bank_buf(x.d_slots, (size_t) b->nrx, "kg_rxbank_ft8: slot records")}, kg_ft8_table_bytes_((size_t) b->nrx, b->blocks_max),
+                           [](kg_rxbank *b) { return kg_ft8_create(b->c_tail, b->nrx, &b->f8.obj); }));
+    for (std::vector<kg_ft8_ev> *v : {&x.last.evs, &x.plan.evs}) v->assign((size_t) x.max_events, kg_ft8_ev{});
+    for (std::vector<int32_t> *v : {&x.last.slot_rx, &x.plan.slot_rx}) v->assign((size_t) b->nrx, -1);
+    return KG_OK;
+}
+
+// the connection's end or beginning: decode_ft8[rx] as a new connection finds it -- not initialised, no task, last_frame zeroed
+static int bank_f8_fresh(kg_rxbank *b, int rx) { b->f8.on[rx] = 0; return b->f8.obj ? kg_ft8_reset_(b->f8.obj, rx) : KG_OK; }
+
+static void bank_f8_plan_clear(kg_rxbank *b)
+{
+    bank_f8 &x = b->f8;
+    x.plan.list.clear(); x.plan.nblk.clear(); x.plan.off.clear(); x.plan.now.clear();
+    x.plan.ne = x.plan.nsl = 0;
+}
+
+static void bank_f8_plan(kg_rxbank *b, int i, int nblk)
+{
+    bank_f8 &x = b->f8;
+    const int k = b->plan.act[i];
+    if (!x.obj || !x.on[k] || nblk <= 0 || bank_stereo(b->plan.mode[i])) return;      // real_wr_pos advances for the mono blocks alone
+    x.plan.list.push_back(k); x.plan.nblk.push_back(nblk); x.plan.off.push_back((int64_t) ((size_t) k * b->firo_stride));
+    x.plan.now.insert(x.plan.now.end(), b->blocks_max, x.now);
+}
+
+// decode_ft8_samples over the step's blocks, reading d_s16 in place: the monitor's launches and the slot-end chain when one is due
+static int bank_f8_enqueue(kg_rxbank *b)
+{
+    bank_f8 &x = b->f8;
+    if (x.plan.list.empty()) return KG_OK;
+    return kg_ft8_push_at_(x.obj, x.plan.list.data(), (int) x.plan.list.size(), x.plan.nblk.data(), x.plan.off.data(), KG_FIR_OUT, (const int16_t *) b->d_s16.p,
+                           b->firo_stride, x.plan.now.data(), b->blocks_max, x.plan.evs.data(), x.max_events, &x.plan.ne, x.d_slots, b->nrx, x.plan.slot_rx.data(),
+                           &x.plan.nsl);
+}
+
+static void bank_f8_commit(kg_rxbank *b)
+{
+    bank_f8 &x = b->f8;
+    x.last.ne = x.plan.ne; x.last.nsl = x.plan.nsl;
+    if (!x.obj) return;
+    x.last.evs.swap(x.plan.evs); x.last.slot_rx.swap(x.plan.slot_rx);
+}
+
 // a connection ends or begins on receiver rx: every extension as a new connection finds it
 static int bank_ext_fresh(kg_rxbank *b, int rx)
 {
@@ -723,15 +804,18 @@ static int bank_ext_fresh(kg_rxbank *b, int rx)
     KG_TRY(bank_lo_fresh(b, rx));
     KG_TRY(bank_fa_fresh(b, rx));
     KG_TRY(bank_cw_fresh(b, rx));
-    return bank_ws_fresh(b, rx);
+    KG_TRY(bank_ws_fresh(b, rx));
+    return bank_f8_fresh(b, rx);
 }
 
-// The real-samples task tap (ext_register_receive_real_samps_task) holds one task per receiver, FAX's or the CW decoder's: whoever
-// asks for it is refused while the other has it
-static int bank_real_tap_free(const kg_rxbank *b, int rx, const char *who, bool cw_asks)
+// The real-samples task tap (ext_register_receive_real_samps_task) holds one task per receiver, FAX's, the CW decoder's or FT8's: whoever
+// asks for it is refused while one of the other two has it
+enum { TAP_FAX = 0, TAP_CW = 1, TAP_FT8 = 2 };
+static int bank_real_tap_free(const kg_rxbank *b, int rx, const char *who, int asker)
 {
-    KG_REQUIRE(!(cw_asks ? b->fa.on[rx] : b->cw.on[rx]), KG_ERR_STATE, "%s: receiver %d has %s; the tap holds one task", who, rx,
-               cw_asks ? "FAX started" : "the CW decoder started");
+    const char *holder = asker != TAP_FT8 && b->f8.on[rx] ? "FT8 started" : asker != TAP_FAX && b->fa.on[rx] ? "FAX started" :
+                         asker != TAP_CW && b->cw.on[rx] ? "the CW decoder started" : nullptr;
+    KG_REQUIRE(holder == nullptr, KG_ERR_STATE, "%s: receiver %d has %s; the tap holds one task", who, rx, holder);
     return KG_OK;
 }
 
@@ -788,6 +872,7 @@ static void bank_plan_rows(kg_rxbank *b, int i, int nblk)
     bank_fa_plan(b, i, nblk);
     bank_cw_plan(b, i, nblk);
     bank_ws_plan(b, i, nblk);
+    bank_f8_plan(b, i, nblk);
 }
 
 // The active list and, per entry, the counts its audio DDC and its CFastFIR will hand back (kg_rxddc_outputs is kg_rxddc_push_dev's
@@ -805,6 +890,7 @@ static void bank_plan_audio(kg_rxbank *b)
     bank_fa_plan_clear(b);
     bank_cw_plan_clear(b);
     bank_ws_plan_clear(b);
+    bank_f8_plan_clear(b);
     for (int k = 0; k < b->nrx; k++) {
         const bank_rx &r = b->rcv[k];
         p.enabled[k] = r.active ? 1 : 0;
@@ -1006,6 +1092,7 @@ static int bank_audio_tail(kg_rxbank *b)
     KG_TRY(bank_fa_enqueue(b));
     KG_TRY(bank_cw_enqueue(b));
     KG_TRY(bank_ws_enqueue(b));
+    KG_TRY(bank_f8_enqueue(b));
     KG_TRY(bank_edge(real, b->ev_tail, b->s_tail, nullptr, &b->tail_pending));
     tk.lap(b, PF_EVENTS, real);
     return KG_OK;
@@ -1070,6 +1157,7 @@ static void bank_commit(kg_rxbank *b)
     bank_fa_commit(b);
     bank_cw_commit(b);
     bank_ws_commit(b);
+    bank_f8_commit(b);
     b->frame_rx.swap(p.chan_of); b->frame_off.swap(p.frame_off); b->pkt_bytes.swap(p.pkt_bytes);
 }
 
@@ -1319,6 +1407,7 @@ static int bank_init(kg_rxbank *b)
     bank_fa_sizes(b);
     bank_cw_sizes(b);
     bank_ws_sizes(b);
+    bank_f8_sizes(b);
     for (std::vector<int32_t> *v : {&b->spec_rx, &b->spec_inst, &b->spec_blk}) v->assign(b->spec_max, 0);
     b->frame_rx.assign(nrx, -1); b->pkt_bytes.assign(nrx, 0); b->frame_off.assign(nrx, 0);
     memset(&b->arena, 0, sizeof b->arena);
@@ -1341,6 +1430,7 @@ void kg_rxbank_destroy(kg_rxbank *b)
     kg_fax_destroy(b->fa.obj);
     kg_cw_destroy(b->cw.obj);
     kg_wspr_destroy(b->ws.obj);
+    kg_ft8_destroy(b->f8.obj);
     kg_adpcm_destroy(b->adpcm); kg_post_destroy(b->post); kg_fir_destroy(b->nullfir); kg_fir_destroy(b->fir); kg_rxddc_destroy(b->rx); kg_nb_destroy(b->nb);
     kg_wf_destroy(b->wf); kg_ddc_destroy(b->ddc);
     kg_ctx_destroy(b->c_tail); kg_ctx_destroy(b->c_side); kg_ctx_destroy(b->c_main);
@@ -1575,7 +1665,7 @@ int kg_rxbank_fax_start(kg_rxbank *b, int rx, int lpm, int imagewidth, int carri
                         int debug, double nom_rate, double srate)
 {
     BANK_EXT("kg_rxbank_fax_start", bank_fa_ensure);
-    KG_TRY(bank_real_tap_free(b, rx, "kg_rxbank_fax_start", false));
+    KG_TRY(bank_real_tap_free(b, rx, "kg_rxbank_fax_start", TAP_FAX));
     KG_REQUIRE(imagewidth <= BANK_FAX_MAX_WIDTH, KG_ERR_INVALID, "kg_rxbank_fax_start: imagewidth %d; a receiver bank takes %d or fewer", imagewidth,
                BANK_FAX_MAX_WIDTH);
     KG_REQUIRE(!(lpm >= 1 && nom_rate >= 1) || nom_rate * 60.0 / lpm >= BANK_FAX_MIN_SPL, KG_ERR_INVALID,
@@ -1616,7 +1706,7 @@ int kg_rxbank_fax_out(kg_rxbank *b, uint8_t **d_rows, size_t *row_stride, kg_fax
 int kg_rxbank_cw_start(kg_rxbank *b, int rx, int training_interval, double nom_rate, double srate)
 {
     BANK_EXT("kg_rxbank_cw_start", bank_cw_ensure);
-    KG_TRY(bank_real_tap_free(b, rx, "kg_rxbank_cw_start", true));
+    KG_TRY(bank_real_tap_free(b, rx, "kg_rxbank_cw_start", TAP_CW));
     KG_TRY(kg_cw_start(b->cw.obj, rx, training_interval, nom_rate, srate));
     b->cw.on[rx] = 1;
     return KG_OK;
@@ -1739,6 +1829,52 @@ int kg_rxbank_wspr_dec_out(kg_rxbank *b, kg_wspr_dec **d_decs, int32_t **d_ncand
             n++;
         }
     return n;
+}
+
+// ---- FT8 / FT4 (include/kiwigpu_ft8.h)
+int kg_rxbank_ft8_init(kg_rxbank *b, int rx, int protocol, double snd_rate)
+{
+    BANK_EXT("kg_rxbank_ft8_init", bank_f8_ensure);
+    return kg_ft8_init(b->f8.obj, rx, protocol, snd_rate);
+}
+
+int kg_rxbank_ft8_start(kg_rxbank *b, int rx)
+{
+    BANK_EXT("kg_rxbank_ft8_start", bank_f8_ensure);
+    KG_TRY(bank_real_tap_free(b, rx, "kg_rxbank_ft8_start", TAP_FT8));
+    KG_REQUIRE(kg_ft8_inited_(b->f8.obj, rx), KG_ERR_STATE, "kg_rxbank_ft8_start: receiver %d was never initialised (kg_rxbank_ft8_init)", rx);
+    b->f8.on[rx] = 1;
+    return KG_OK;
+}
+
+int kg_rxbank_ft8_stop(kg_rxbank *b, int rx)
+{
+    KG_TRY(bank_rx_check(b, rx, "kg_rxbank_ft8_stop"));
+    b->f8.on[rx] = 0;                           // a bank that was never told has nothing to stop, and makes nothing for it
+    return KG_OK;
+}
+
+int kg_rxbank_ft8_set_now(kg_rxbank *b, double now)
+{
+    KG_REQUIRE(b != nullptr, KG_ERR_INVALID, "kg_rxbank_ft8_set_now: null handle");
+    KG_REQUIRE(now >= 0.0 && now <= 1099511627776.0, KG_ERR_INVALID, "kg_rxbank_ft8_set_now: time %g (finite, 0 .. 2^40)", now);
+    b->f8.now = now;                            // the plan of every later step copies it into the step's callbacks
+    return KG_OK;
+}
+
+kg_ft8 *kg_rxbank_ft8(kg_rxbank *b) { return b ? b->f8.obj : nullptr; }
+
+int kg_rxbank_ft8_out(kg_rxbank *b, kg_ft8_slot **d_slots, kg_ft8_ev *evs, int max_events, int32_t *nevents, int32_t *rx_of_slot, int max_slots)
+{
+    KG_REQUIRE(b != nullptr && max_events >= 0 && max_slots >= 0, KG_ERR_INVALID, "kg_rxbank_ft8_out: bad argument");
+    const bank_f8 &x = b->f8;
+    KG_REQUIRE(!evs || max_events >= x.last.ne, KG_ERR_INVALID, "kg_rxbank_ft8_out: %d events, room for %d", x.last.ne, max_events);
+    KG_REQUIRE(!rx_of_slot || max_slots >= x.last.nsl, KG_ERR_INVALID, "kg_rxbank_ft8_out: %d slot records, room for %d", x.last.nsl, max_slots);
+    if (d_slots) *d_slots = x.d_slots;                                  // null until the extension was named
+    if (evs && x.last.ne) memcpy(evs, x.last.evs.data(), sizeof(kg_ft8_ev) * (size_t) x.last.ne);
+    if (nevents) *nevents = x.last.ne;
+    if (rx_of_slot && x.last.nsl) memcpy(rx_of_slot, x.last.slot_rx.data(), sizeof(int32_t) * (size_t) x.last.nsl);
+    return x.last.nsl;
 }
 
 int kg_rxbank_cw_out(kg_rxbank *b, kg_cw_ev **d_evs, int32_t **d_counts, int32_t *max_events, int32_t *rx_of_entry, int max_entries)

@@ -512,6 +512,45 @@ class RxBank:
             rows[:] = slots[:, :ws.NBINS + 1]
         return rows, m[:n.value].copy(), ev[:ne.value].copy(), cycles, counts
 
+    # ---- the FT8 / FT4 extension, stage 1 (extensions/FT8/ft8_lib): kg_ft8's commands per receiver
+    def ft8_init(self, rx, protocol=0, snd_rate=12000.0):
+        """decode_ft8_init / decode_ft8_protocol: the receiver's connection begins again"""
+        check(self.lib.kg_rxbank_ft8_init(self.h, int(rx), int(protocol), float(snd_rate)), "kg_rxbank_ft8_init")
+
+    def ft8_start(self, rx):
+        """registers the real-samples task; refused while FAX or the CW decoder is started on the receiver (the tap holds one task)"""
+        check(self.lib.kg_rxbank_ft8_start(self.h, int(rx)), "kg_rxbank_ft8_start")
+
+    def ft8_stop(self, rx):
+        check(self.lib.kg_rxbank_ft8_stop(self.h, int(rx)), "kg_rxbank_ft8_stop")
+
+    def ft8_set_now(self, now):
+        """what clock_gettime answers, in seconds, during every later step"""
+        check(self.lib.kg_rxbank_ft8_set_now(self.h, float(now)), "kg_rxbank_ft8_set_now")
+
+    @property
+    def ft8(self):
+        """the bank's Ft8 (None until one of the per-receiver ft8_* commands was sent): state(), set_snr_adj()"""
+        from . import ft8 as f8
+        h = self.lib.kg_rxbank_ft8(self.h)
+        return borrow(f8.Ft8, self.ctx, h, nconn=self.nrx) if h else None
+
+    def ft8_out(self):
+        """-> (events of ft8.ev_dtype -- conn the receiver, cb the sound block of the step --, {receiver: slot record of ft8.slot_dtype} of
+        the receivers whose slot ended) of the last step (after sync())"""
+        from . import ft8 as f8
+        ev, rxs = np.zeros(self.nrx * 4, f8.ev_dtype), np.zeros(self.nrx, np.int32)
+        d_slots, ne = C.c_void_p(), C.c_int32()
+        n = check(self.lib.kg_rxbank_ft8_out(self.h, C.byref(d_slots), ptr(ev), int(ev.size), C.byref(ne), ptr(rxs), int(rxs.size)), "kg_rxbank_ft8_out")
+        slots = {}
+        if n:
+            recs = np.zeros(n, f8.slot_dtype)
+            self.ctx.download(int(d_slots.value), recs)
+            for k in range(n):
+                assert recs[k]["due"] == 1 and recs[k]["conn"] == rxs[k]
+                slots[int(rxs[k])] = recs[k].copy()
+        return ev[:ne.value].copy(), slots
+
     @property
     def cw(self):
         """the bank's CwDecoder (None until one of the per-receiver cw_* commands was sent): state()"""

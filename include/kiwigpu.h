@@ -1620,6 +1620,7 @@ int kg_wspr_load(kg_wspr *q, int conn, int half, const float *pwr_samp, const fl
 /* Stage 2 of the WSPR extension -- fine sync, soft symbols and the Fano decoder on the candidates a connection holds -- is declared in a
  * header of its own, in this directory. */
 #include "kiwigpu_wspr_dec.h"
+#include "kiwigpu_ft8.h"
 
 /* Diagnostics: re-runs the 4096-point stage of the forward FFT of `block` in a
  * stamped build of the kernel and returns 4 s_memrealtime readings (100 MHz):
